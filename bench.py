@@ -1,9 +1,11 @@
 """bench.py -- predicted frames/s of the VMAE predictor path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3           # the headline alone: set up, warm up, time the steps, print the line
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full    # + every check and side measurement (roofline, secondary mode, prompts256, CPU baseline)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --workload prompts256 --gpus N          # BASELINE configs[3] alone: 256 prompts on one frame pair, sharded over N ranks
     python bench.py --workload flowstats | prompt_build      # the kernels after / before the predictor path (one GPU)
-                                                            # (strong scaling; per_rank_ms = every rank's {build, broadcast, own_prompts, predict, gather})
+                                                            # (prompts256: strong scaling; with --full, per_rank_ms = every rank's {build, broadcast, own_prompts, predict, gather})
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -61,13 +63,15 @@ def build_info():
 
 def timed_steps(G, x, mask, n_vis, steps, distributed):
     """K steps of the reference's `predict` (prediction.py:406-454) on the wrapper `G`: mask rectangulariser (its one host
-    read-back per call included), normalise, forward, un-embed; all frames returned."""
+    read-back per call included), normalise, forward, un-embed; all frames returned.  Returns (seconds, the last step's frames)."""
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    y = None
     for _ in range(steps):
-        G.predict(x, mask, frame=None)
+        y = None  # (the previous step's frames are released first: every step reuses one allocation, as when nothing is kept)
+        y = G.predict(x, mask, frame=None)
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -76,7 +80,39 @@ def timed_steps(G, x, mask, n_vis, steps, distributed):
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    return dt
+    return dt, y
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6  # --dump-outputs: the arrays written (their .npy headers aside) stay under 64 MB in all
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: what the timed path returned in its last step, one DIR/<name>.npy per array (float32; float64 stays float64; masks as
+    0.0 / 1.0).  When they exceed DUMP_BUDGET_BYTES together, the arrays above an equal share of it are viewed as rows of their last axis and keep a
+    fixed, seeded subset of those rows in ascending order (the same subset in every run and every build of the same command); the others are whole."""
+    import numpy as np
+
+    if out_dir is None or not arrays:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: (v.detach() if v.dtype == torch.float64 else v.detach().float()) for k, v in arrays.items()}
+    nbytes = {k: v.numel() * v.element_size() for k, v in arrays.items()}
+    share = DUMP_BUDGET_BYTES / len(arrays)
+    small = sum(b for b in nbytes.values() if b <= share)
+    large = sum(b for b in nbytes.values() if b > share)
+    frac = (DUMP_BUDGET_BYTES - small) / large if sum(nbytes.values()) > DUMP_BUDGET_BYTES else 1.0
+    written, sampled = 0, []
+    for name, v in arrays.items():
+        if frac < 1.0 and nbytes[name] > share:
+            v = v.reshape(-1, v.shape[-1])
+            rows = torch.randperm(v.shape[0], generator=torch.Generator().manual_seed(0))[:max(1, int(v.shape[0] * frac))].sort().values
+            v = v.index_select(0, rows.to(v.device))
+            sampled.append(name)
+        a = v.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+    sys.stderr.write("bench.py: wrote %d output array(s), %.1f MB, to %s%s\n"
+                     % (len(arrays), written / 1e6, out_dir, " (a seeded sample of the rows of %s)" % ", ".join(sampled) if sampled else ""))
 
 
 def pmc_profile(workload, mode, kernel):
@@ -155,7 +191,7 @@ def n_gpus_expected(world, distributed):
 def prompts_measure(args, rank, local_rank, world, distributed, model=None, steps=None, warmup=None):
     """BASELINE configs[3], strong scaling: 256 prompts on ONE frame pair, sharded over the ranks (dist.py: one packed RCCL
     broadcast, per-rank prompt construction + 32-row predictor calls with no host sync in between, one all-gather).
-    value = prompts / max-over-ranks time.  Returns the result dict (rank 0 prints it or embeds it)."""
+    value = prompts / max-over-ranks time.  Returns (the last timed step's predictions, the result dict: rank 0 prints it or embeds it)."""
     from counterfactualworldmodels_amd import dist as cdist, segmentation
 
     cfg = C.CONFIGS[PROMPTS["cfg"]]
@@ -186,7 +222,8 @@ def prompts_measure(args, rank, local_rank, world, distributed, model=None, step
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        y = None
+        y = step()
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -195,24 +232,26 @@ def prompts_measure(args, rank, local_rank, world, distributed, model=None, step
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # one more (untimed) step with HIP-event spans around its phases, from every rank: a bad curve on the multi-GPU node can then be read from
+    # --full: one more (untimed) step with HIP-event spans around its phases, from every rank: a bad curve on the multi-GPU node can then be read from
     # ONE run -- which rank, which phase (rank 0 alone builds all prompts and rectangularises; the gather runs on a side stream)
-    ph = cdist.PhaseTimes(dev)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    cdist.sharded_counterfactual_predictions(x0, table, *hooks, dev, chunk=PROMPTS["chunk"], gather=True, comm=comm, shapes=shapes, times=ph)
-    torch.cuda.synchronize()
-    mine = {k: round(v, 3) for k, v in ph.result().items()}
-    mine["wall"] = round(1e3 * (time.perf_counter() - t1), 3)
-    per_rank = [mine]
-    if distributed:
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine)
+    per_rank = None
+    if args.full:
+        ph = cdist.PhaseTimes(dev)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        cdist.sharded_counterfactual_predictions(x0, table, *hooks, dev, chunk=PROMPTS["chunk"], gather=True, comm=comm, shapes=shapes, times=ph)
+        torch.cuda.synchronize()
+        mine = {k: round(v, 3) for k, v in ph.result().items()}
+        mine["wall"] = round(1e3 * (time.perf_counter() - t1), 3)
+        per_rank = [mine]
+        if distributed:
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, mine)
     n_gpus = world if distributed else 1
-    # N > 1: the gathered result must be the same on every rank and equal, bit for bit, to the single-process result of the same prompts under the same torch
-    # seed (the rectangulariser's draws happen on rank 0 either way; every predictor call covers the same 32 consecutive prompts in both runs)
+    # --full, N > 1: the gathered result must be the same on every rank and equal, bit for bit, to the single-process result of the same prompts under the
+    # same torch seed (the rectangulariser's draws happen on rank 0 either way; every predictor call covers the same 32 consecutive prompts in both runs)
     check = None
-    if distributed:
+    if distributed and args.full:
         torch.manual_seed(4321)
         y_sh = step()
         mine = [float(y_sh.double().sum()), float(y_sh[::37].double().abs().sum())]
@@ -227,7 +266,7 @@ def prompts_measure(args, rank, local_rank, world, distributed, model=None, step
             del y_ref
         del y_sh
         dist.barrier()
-    return {
+    return y, {
         "sharded_result_check": check,
         "per_rank_ms": per_rank,
         "metric": "predicted frames/sec (2x224x224, ViT-B/8)", "value": PROMPTS["total"] * steps / dt, "unit": "frames/s",
@@ -243,7 +282,10 @@ def prompts_measure(args, rank, local_rank, world, distributed, model=None, step
 def run_prompts(args, rank, local_rank, world, distributed):
     from counterfactualworldmodels_amd import dist as cdist
 
-    out = prompts_measure(args, rank, local_rank, world, distributed)
+    y, out = prompts_measure(args, rank, local_rank, world, distributed)
+    if rank == 0:
+        dump_outputs(args.dump_outputs, {"video": y})
+    del y
     if distributed:
         torch.cuda.synchronize()
         dist.barrier()
@@ -278,8 +320,10 @@ def run_imu(args, rank, local_rank, world, distributed):
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        y = None
         for _ in range(args.steps):
-            step()
+            y = None
+            y = step()
         torch.cuda.synchronize()
         if distributed:
             dist.barrier()
@@ -288,7 +332,7 @@ def run_imu(args, rank, local_rank, world, distributed):
             t = torch.tensor([dt], device="cuda", dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dt
+        return dt, y
 
     step()
     model.set_lanes(args.lanes)
@@ -296,22 +340,10 @@ def run_imu(args, rank, local_rank, world, distributed):
         model.set_option("conj_ctx_stream", 0)          # kernels overlap and per-kernel durations mean what they say
     for _ in range(max(args.warmup, 1)):
         step()
-    dt = region()
-    # kernel region (as in the headline workload): the same steps on ONE lane with HIP events around every launch of a class
-    classes = {"gemm_wide": _lib.KCLASS_GEMM_WIDE, "gemm_narrow": _lib.KCLASS_GEMM_NARROW, "attention": _lib.KCLASS_ATTENTION,
-               "cross_attention": _lib.KCLASS_CROSS_ATTN, "context_self_attention": _lib.KCLASS_SMALL_ATTN}
-    model.set_lanes(1)
-    for _ in range(2):
-        step()
-    for kc in [_lib.KCLASS_GEMM, _lib.KCLASS_ATTENTION, _lib.KCLASS_CROSS_ATTN, _lib.KCLASS_SMALL_ATTN] + [kc for _, kc in EDGE_CLASSES]:
-        model.timing_enable(kc, True)
-    dt_one = region()
-    model.timing_collect(_lib.KCLASS_GEMM)  # books the wide / narrow split
-    stats = {name: model.timing_collect(kc) for name, kc in classes.items()}
-    edge = edge_kernels(model.timing_collect)
-    for kc in [_lib.KCLASS_GEMM, _lib.KCLASS_ATTENTION, _lib.KCLASS_CROSS_ATTN, _lib.KCLASS_SMALL_ATTN] + [kc for _, kc in EDGE_CLASSES]:
-        model.timing_enable(kc, False)
-    model.set_lanes(args.lanes)
+    dt, y = region()
+    if rank == 0:  # (the model returns its main stream's tokens, or the tuple (main, context) when it is set to output both)
+        dump_outputs(args.dump_outputs, dict(zip(("tokens", "context_tokens"), y)) if isinstance(y, tuple) else {"tokens": y})
+    del y
     n_gpus = world if distributed else 1
     flops_pair = 1.422e12  # SURVEY.md §8(d), cfg 5 (k=4)
     value = B * n_gpus * args.steps / dt
@@ -323,6 +355,33 @@ def run_imu(args, rank, local_rank, world, distributed):
                    "per_gpu_batch": B, "mode": args.mode, "lanes": args.lanes, "tokens_decoder": cfg.main.num_tokens + cfg.main_max_pad},
         "model_tflops": flops_pair * value / 1e12, "model_frac_of_bf16_peak": flops_pair * value / 1e12 / (PEAK_BF16_TFLOPS * n_gpus),
     }
+    if args.full:
+        imu_kernel_region(args, model, step, region, out, B, n_gpus)
+    if distributed:
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        out["build"] = build_info()
+        print(json.dumps(out))
+
+
+def imu_kernel_region(args, model, step, region, out, B, n_gpus):
+    """--full: the kernel region of the IMU workload (as in the headline workload): the same steps on ONE lane with HIP events around every launch of a
+    class -> out["roofline"]."""
+    classes = {"gemm_wide": _lib.KCLASS_GEMM_WIDE, "gemm_narrow": _lib.KCLASS_GEMM_NARROW, "attention": _lib.KCLASS_ATTENTION,
+               "cross_attention": _lib.KCLASS_CROSS_ATTN, "context_self_attention": _lib.KCLASS_SMALL_ATTN}
+    model.set_lanes(1)
+    for _ in range(2):
+        step()
+    for kc in [_lib.KCLASS_GEMM, _lib.KCLASS_ATTENTION, _lib.KCLASS_CROSS_ATTN, _lib.KCLASS_SMALL_ATTN] + [kc for _, kc in EDGE_CLASSES]:
+        model.timing_enable(kc, True)
+    dt_one, _ = region()
+    model.timing_collect(_lib.KCLASS_GEMM)  # books the wide / narrow split
+    stats = {name: model.timing_collect(kc) for name, kc in classes.items()}
+    edge = edge_kernels(model.timing_collect)
+    for kc in [_lib.KCLASS_GEMM, _lib.KCLASS_ATTENTION, _lib.KCLASS_CROSS_ATTN, _lib.KCLASS_SMALL_ATTN] + [kc for _, kc in EDGE_CLASSES]:
+        model.timing_enable(kc, False)
+    model.set_lanes(args.lanes)
 
     def entry(st):
         tf = st["total_flops"] / (st["total_ms"] * 1e-3) / 1e12 if st["total_ms"] > 0 else 0.0
@@ -339,12 +398,6 @@ def run_imu(args, rank, local_rank, world, distributed):
                            region={"lanes": 1, "steps": args.steps, "ms_per_step": 1e3 * dt_one / args.steps, "value": B * n_gpus * args.steps / dt_one},
                            note="algorithmic FLOPs of the class's launches / their summed HIP-event durations in a one-lane kernel region (rank 0)",
                            other_kernel={names[k]: entry(v) for k, v in stats.items() if k != dom})
-    if distributed:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        out["build"] = build_info()
-        print(json.dumps(out))
 
 
 # ---- the kernels on either side of the predictor path (prompt construction before it, flow-sample statistics after it) -------
@@ -400,10 +453,11 @@ def aux_traffic(workload, prefix):
     return aux_profile(workload, prefix)[0]
 
 
-def flowstats_measure(S_samples, steps, dev, cpu=False):
+def flowstats_measure(S_samples, steps, dev, cpu=False, full=True):
     """One frame pair's S counterfactual flow samples [1, 2, 224, 224, S] (the reference's layout: sample axis innermost) through the reductions of
     segmentation.py:250-276, 479-547 at downsample 2 (P = 112 x 112 = 12544 positions): pooled magnitudes -> z-score prologue -> covariance [P, P] ->
-    mean motion map.  Every stage timed on its own; `value` is samples reduced per second over the default chain (features + covariance + motion map)."""
+    mean motion map.  `value` is samples reduced per second over the default chain (features + covariance + motion map); with `full` every stage is also
+    timed on its own (`stages`).  res["outputs"] = the last timed chain's results."""
     from counterfactualworldmodels_amd import flowstats as FS
 
     H = W = 224
@@ -411,6 +465,47 @@ def flowstats_measure(S_samples, steps, dev, cpu=False):
     P = (H // ds) * (W // ds)
     g = torch.Generator().manual_seed(0)
     flows = (torch.randn(1, 2, H, W, S_samples, generator=g) * 2).to(dev)
+    stages = flowstats_stages(flows, ds, P, S_samples, steps) if full else None
+
+    def chain():
+        return (FS.compute_flow_corrs(flows, downsample=ds, use_covariance=True),
+                FS.compute_mean_motion_map(flows, normalize_per_sample=True))
+
+    for _ in range(2):
+        chain()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    y = None
+    for _ in range(steps):
+        y = None
+        y = chain()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    res = {"value": S_samples * steps / dt, "ms_per_step": 1e3 * dt / steps, "stages": stages, "samples": S_samples, "positions": P,
+           "outputs": {"corrs": y[0], "motion_map": y[1]}}
+    if cpu:
+        from oracle import flowstats_oracle as FO
+
+        torch.set_num_threads(min(16, os.cpu_count() or 1))
+        fc = flows.cpu()
+        t0 = time.perf_counter()
+        n = 0
+        while n < 4 and time.perf_counter() - t0 < 20.0:
+            FO.compute_flow_corrs(fc, ds, True)
+            FO.compute_mean_motion_map(fc, normalize_per_sample=True, normalize=True)
+            n += 1
+        dtc = time.perf_counter() - t0
+        res["cpu_baseline"] = {"value": S_samples * n / dtc, "unit": "samples/s", "cores": torch.get_num_threads(), "kind": "port",
+                               "sample": "%d passes of the same chain (S = %d, 224x224, downsample 2) through oracle/flowstats_oracle.py, torch CPU fp32 on %d threads"
+                                         % (n, S_samples, torch.get_num_threads())}
+    return res
+
+
+def flowstats_stages(flows, ds, P, S_samples, steps):
+    """--full: every stage of the flow-statistics chain timed on its own (HIP events on the launching stream)."""
+    from counterfactualworldmodels_amd import flowstats as FS
+
+    H, W = flows.shape[2:4]
     x = FS.flow_features(flows, ds)
     stages = {}
     f_bytes = flows.numel() * 4
@@ -434,60 +529,36 @@ def flowstats_measure(S_samples, steps, dev, cpu=False):
     stages["covariance"] = cov
     ms = _stage_ms(lambda: FS.compute_mean_motion_map(flows, normalize_per_sample=True), steps, "motion")
     stages["motion_map"] = _hbm_entry(2 * f_bytes + H * W * 4 * 3, ms, ["flow_mag_minmax_*_kernel", "flow_motion_sum_*_kernel", "flow_map_finish_kernel"], "motion")
-
-    def chain():
-        FS.compute_flow_corrs(flows, downsample=ds, use_covariance=True)
-        FS.compute_mean_motion_map(flows, normalize_per_sample=True)
-
-    for _ in range(2):
-        chain()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        chain()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    res = {"value": S_samples * steps / dt, "ms_per_step": 1e3 * dt / steps, "stages": stages, "samples": S_samples, "positions": P}
-    if cpu:
-        from oracle import flowstats_oracle as FO
-
-        torch.set_num_threads(min(16, os.cpu_count() or 1))
-        fc = flows.cpu()
-        t0 = time.perf_counter()
-        n = 0
-        while n < 4 and time.perf_counter() - t0 < 20.0:
-            FO.compute_flow_corrs(fc, ds, True)
-            FO.compute_mean_motion_map(fc, normalize_per_sample=True, normalize=True)
-            n += 1
-        dtc = time.perf_counter() - t0
-        res["cpu_baseline"] = {"value": S_samples * n / dtc, "unit": "samples/s", "cores": torch.get_num_threads(), "kind": "port",
-                               "sample": "%d passes of the same chain (S = %d, 224x224, downsample 2) through oracle/flowstats_oracle.py, torch CPU fp32 on %d threads"
-                                         % (n, S_samples, torch.get_num_threads())}
-    return res
+    return stages
 
 
 def run_flowstats(args):
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     main_S, other_S = 256, 24
-    r = flowstats_measure(main_S, args.steps, dev, cpu=not args.no_cpu_baseline)
+    r = flowstats_measure(main_S, args.steps, dev, cpu=args.full and not args.no_cpu_baseline, full=args.full)
+    dump_outputs(args.dump_outputs, r.pop("outputs"))
+    out = {
+        "metric": "counterfactual flow samples reduced/sec (224x224, downsample 2: features -> covariance [12544^2] -> motion map)", "value": r["value"], "unit": "samples/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": 2, "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic", "config": {"workload": "flow-sample statistics of one frame pair (SURVEY.md 8 f-4; segmentation.py:250-276, 479-547), S = 256 samples",
+                                        "samples": main_S, "positions": r["positions"], "downsample": 2},
+        "build": build_info(),
+    }
+    if not args.full:
+        print(json.dumps(out))
+        return
     r2 = flowstats_measure(other_S, args.steps, dev)
+    r2.pop("outputs")
     cov = r["stages"]["covariance"]
     roof = dict(cov["as_mfma"], kernel="cwm::flow_cov_kernel (+ flow_center_kernel)", avg_launch_us=cov["avg_us"], traffic=aux_traffic("flowstats", "cwm::flow_cov_kernel<true, 2>"), mfma_busy=aux_profile("flowstats", "cwm::flow_cov_kernel<true, 2>")[1],
                 as_hbm={k: cov[k] for k in ("achieved", "peak", "unit", "frac", "bytes_per_call")},
                 stages={k: v for k, v in r["stages"].items() if k != "covariance"},
                 note="S = 256: 2 P^2 S = 80.6 GFLOP of exact-fp32 MFMA against a 629-MB result: the fp32 matrix pipe bounds it (0.51 ms at peak vs 0.08 ms of HBM write); "
                      "at S = 24 (secondary) the same kernel is bound by the 629-MB write.  HIP events around the stage's calls on the launching stream")
-    out = {
-        "metric": "counterfactual flow samples reduced/sec (224x224, downsample 2: features -> covariance [12544^2] -> motion map)", "value": r["value"], "unit": "samples/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": 2, "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic", "config": {"workload": "flow-sample statistics of one frame pair (SURVEY.md 8 f-4; segmentation.py:250-276, 479-547), S = 256 samples",
-                                        "samples": main_S, "positions": r["positions"], "downsample": 2},
-        "roofline": roof,
-        "secondary": {"samples": other_S, "value": r2["value"], "unit": "samples/s", "ms_per_step": r2["ms_per_step"], "stages": r2["stages"],
-                      "note": "S = 24 (the demo notebooks' sample count): the covariance stage is bound by the HBM write of the [P, P] result"},
-        "build": build_info(),
-    }
+    out["roofline"] = roof
+    out["secondary"] = {"samples": other_S, "value": r2["value"], "unit": "samples/s", "ms_per_step": r2["ms_per_step"], "stages": r2["stages"],
+                        "note": "S = 24 (the demo notebooks' sample count): the covariance stage is bound by the HBM write of the [P, P] result"}
     if "cpu_baseline" in r:
         out["cpu_baseline"] = r["cpu_baseline"]
     print(json.dumps(out))
@@ -513,38 +584,45 @@ def run_prompt_build(args):
     in_bytes = 3 * cfg.img_size[0] * cfg.img_size[1] * 4
     xs, ms_ = build(x0, table)
     assert xs.shape == (n, 2, 3) + tuple(cfg.img_size) and ms_.shape == (n, cfg.num_tokens)
-    t_all = _stage_ms(lambda: build(x0, table), args.steps)
-    t_masks = _stage_ms(lambda: build(x0, table, frames=False), args.steps)
-    t_32 = _stage_ms(lambda: build(x0, table[:32]), args.steps)
-    # the frames kernel alone through the C ABI (no torch index ops around it)
-    passive = (torch.arange(cfg.num_tokens, device=dev) >= cfg.tokens_per_frame)[None].expand(n, -1).contiguous()
-    active = passive.clone()
-    gw = cfg.img_size[1] // cfg.patch
-    active[torch.arange(n, device=dev), cfg.tokens_per_frame + table[:, 0].long() * gw + table[:, 1].long()] = False
-    shifts = table[:, 2:4].contiguous()
-    xb = x0.expand(-1, 2, -1, -1, -1)
-    t_kernel = _stage_ms(lambda: G._shift_rows(xb, passive, active, shifts, 1, True, samples_per_movie=n, masks=False), args.steps)
-    t_mask_kernel = _stage_ms(lambda: G._shift_rows(xb, passive, active, shifts, 1, True, samples_per_movie=n, frames=False), args.steps)
+    del xs, ms_
+    if args.full:  # every call and kernel timed on its own -> `roofline`
+        t_all = _stage_ms(lambda: build(x0, table), args.steps)
+        t_masks = _stage_ms(lambda: build(x0, table, frames=False), args.steps)
+        t_32 = _stage_ms(lambda: build(x0, table[:32]), args.steps)
+        # the frames kernel alone through the C ABI (no torch index ops around it)
+        passive = (torch.arange(cfg.num_tokens, device=dev) >= cfg.tokens_per_frame)[None].expand(n, -1).contiguous()
+        active = passive.clone()
+        gw = cfg.img_size[1] // cfg.patch
+        active[torch.arange(n, device=dev), cfg.tokens_per_frame + table[:, 0].long() * gw + table[:, 1].long()] = False
+        shifts = table[:, 2:4].contiguous()
+        xb = x0.expand(-1, 2, -1, -1, -1)
+        t_kernel = _stage_ms(lambda: G._shift_rows(xb, passive, active, shifts, 1, True, samples_per_movie=n, masks=False), args.steps)
+        t_mask_kernel = _stage_ms(lambda: G._shift_rows(xb, passive, active, shifts, 1, True, samples_per_movie=n, frames=False), args.steps)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    y = None
     for _ in range(args.steps):
-        build(x0, table)
+        y = None
+        y = build(x0, table)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    dump_outputs(args.dump_outputs, {"frames": y[0], "masks": y[1]})
+    del y
     out = {
         "metric": "motion-counterfactual prompts built/sec (2x224x224 frames + 1568-token masks, ViT-B/8 grid)", "value": n * args.steps / dt, "unit": "prompts/s", "n_gpus": 1,
         "steps": args.steps, "warmup": 1, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32 copies, u8 masks",
         "data": "synthetic", "config": {"workload": "device-side construction of the 256 prompts of BASELINE configs[3] (SURVEY.md 8 f-1; segmentation.py:324-338, "
                                                     "perturbation.py:245-289)", "prompts": n, "predictor_grid": cfg.name},
-        "roofline": dict(_hbm_entry(frame_bytes + in_bytes, t_kernel, ["shift_prompts_x_kernel"]), kernel="cwm::shift_prompts_x_kernel", avg_launch_us=1e3 * t_kernel,
-                         traffic=aux_traffic("prompt_build", "cwm::shift_prompts_x_kernel"),
-                         other_kernel={"cwm::shift_prompts_mask_kernel": _hbm_entry(3 * mask_bytes, t_mask_kernel, ["shift_prompts_mask_kernel"])},
-                         host_call_ms={"frames + masks, 256 prompts (torch index ops + both kernels)": t_all, "masks only, 256 prompts (rank 0 of a sharded call)": t_masks,
-                                       "frames + masks, 32 prompts (one rank's shard at 8 ranks)": t_32},
-                         note="algorithmic bytes = 256 x 1.2 MB of frames written + the 602-KB image read once; HIP events around the C-ABI call on the launching stream"),
         "build": build_info(),
     }
-    if not args.no_cpu_baseline:
+    if args.full:
+        out["roofline"] = dict(_hbm_entry(frame_bytes + in_bytes, t_kernel, ["shift_prompts_x_kernel"]), kernel="cwm::shift_prompts_x_kernel", avg_launch_us=1e3 * t_kernel,
+                               traffic=aux_traffic("prompt_build", "cwm::shift_prompts_x_kernel"),
+                               other_kernel={"cwm::shift_prompts_mask_kernel": _hbm_entry(3 * mask_bytes, t_mask_kernel, ["shift_prompts_mask_kernel"])},
+                               host_call_ms={"frames + masks, 256 prompts (torch index ops + both kernels)": t_all, "masks only, 256 prompts (rank 0 of a sharded call)": t_masks,
+                                             "frames + masks, 32 prompts (one rank's shard at 8 ranks)": t_32},
+                               note="algorithmic bytes = 256 x 1.2 MB of frames written + the 602-KB image read once; HIP events around the C-ABI call on the launching stream")
+    if args.full and not args.no_cpu_baseline:
         from oracle import vmae_oracle as O
 
         torch.set_num_threads(min(16, os.cpu_count() or 1))
@@ -609,6 +687,109 @@ def self_launch(args):
     return subprocess.run(cmd, env=env).returncode
 
 
+def full_extras(args, out, model, G, x, mask, n_vis, cfg, wl, B, checksum_before, rank, local_rank, world, distributed):
+    """--full, after the timed region of the base8 / large4 workloads: the output-stability check, the one-lane kernel region (`roofline`), the other
+    arithmetic mode (`secondary`), BASELINE configs[3] beside the headline (`prompts256`) and the CPU baseline -- each into `out`."""
+    n_gpus = world if distributed else 1
+    checksum_after = float(G.predict(x, mask, frame=None).double().sum())
+    # one more (untimed) step before and after the timed region: same input, same bits expected (a timing-dependent fault would show here)
+    out["output_stable"] = bool(checksum_before == checksum_after and checksum_after == checksum_after)
+
+    # ---- kernel region: the same K steps on ONE lane with a HIP event pair around every GEMM launch -> `roofline`.  With two lanes a
+    # launch shares the chip with whatever the other lane runs, so its duration says nothing about the kernel; here launches are alone.
+    # With --lanes 1 the two regions are the same thing (and that is the command the rocprofv3 summaries under profiles/ are taken from).
+    model.set_lanes(1)
+    if args.lanes != 1:
+        for _ in range(2):
+            G.predict(x, mask, frame=None)
+    model.timing_enable(_lib.KCLASS_GEMM, True)
+    model.timing_enable(_lib.KCLASS_ATTENTION, True)
+    for _, kc in EDGE_CLASSES:
+        model.timing_enable(kc, True)
+    dt_one, _ = timed_steps(G, x, mask, n_vis, args.steps, distributed)
+    gemm = model.timing_collect(_lib.KCLASS_GEMM)                 # every GEMM launch ...
+    gemm_wide = model.timing_collect(_lib.KCLASS_GEMM_WIDE)       # ... split by the kernel that ran it
+    gemm_narrow = model.timing_collect(_lib.KCLASS_GEMM_NARROW)
+    attn = model.timing_collect(_lib.KCLASS_ATTENTION)            # softmax(q k^T) v: 4 N^2 64 FLOP per (batch, head)
+    edge = edge_kernels(model.timing_collect)
+    model.timing_enable(_lib.KCLASS_GEMM, False)
+    model.timing_enable(_lib.KCLASS_ATTENTION, False)
+    for _, kc in EDGE_CLASSES:
+        model.timing_enable(kc, False)
+    model.set_lanes(args.lanes)
+
+    planes = 2 if args.mode == "parity" else 1
+    kernels = {  # (names as rocprofv3 prints them)
+        "cwm::gemm8p_kernel<%d>" % planes: gemm_wide,                          # 256x256 8-phase: qkv, fc1, whole rounds of fc2
+        "cwm::gemm_bf16_kernel<%d, 128, 128, 2, 4, 2>" % planes: gemm_narrow,  # 128x128, 8 waves: proj, narrow outputs, remainders
+        "cwm::attention_pipe_kernel<%d, 4>" % planes: attn,   # softmax(q k^T) v
+    }
+
+    def tflops(st):
+        return st["total_flops"] / (st["total_ms"] * 1e-3) / 1e12 if st["total_ms"] > 0 else 0.0
+
+    def kentry(k, v):
+        tf = tflops(v)
+        return dict({"achieved": tf, "frac": tf / PEAK_BF16_TFLOPS, "launches": v["launches"], "avg_launch_us": 1e3 * v["total_ms"] / max(v["launches"], 1),
+                     "share_of_step": v["total_ms"] / (1e3 * dt_one) if dt_one > 0 else None}, **profile_fields(args.workload, args.mode, k, tf / PEAK_BF16_TFLOPS))
+
+    dom = max(kernels, key=lambda k: kernels[k]["total_ms"])  # dominant kernel = most device time in the kernel region (attention included)
+    st = kernels[dom]
+    ach = tflops(st)
+    out["roofline"] = {
+        "bound": "mfma", "kernel": dom, "achieved": ach, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_BF16_TFLOPS,
+        **profile_fields(args.workload, args.mode, dom, ach / PEAK_BF16_TFLOPS),
+        "edge_kernels": edge,
+        "launches": st["launches"], "avg_launch_us": 1e3 * st["total_ms"] / max(st["launches"], 1),
+        "share_of_step": st["total_ms"] / (1e3 * dt_one) if dt_one > 0 else None,
+        "region": {"lanes": 1, "steps": args.steps, "ms_per_step": 1e3 * dt_one / args.steps, "value": B * n_gpus * args.steps / dt_one,
+                   "note": "kernel region: the same steps as the timed region, one lane, HIP events around every GEMM / attention launch"},
+        "note": "algorithmic FLOPs (2*M*N*K per GEMM launch, 4*N^2*64 per (batch, head) of an attention launch) of this kernel's launches in the "
+                "kernel region / their summed HIP-event durations (rank 0)"
+                + ("; parity mode executes 3x these FLOPs on the MFMA pipe (executed_frac)" if args.mode == "parity" else ""),
+        "all_gemm": {"achieved": tflops(gemm), "launches": gemm["launches"], "avg_launch_us": 1e3 * gemm["total_ms"] / max(gemm["launches"], 1),
+                     "share_of_step": gemm["total_ms"] / (1e3 * dt_one) if dt_one > 0 else None},
+        "other_kernel": {k: kentry(k, v) for k, v in kernels.items() if k != dom},
+    }
+
+    if not args.no_secondary:
+        other = "fast" if args.mode == "parity" else "parity"
+        model.mode = other
+        for _ in range(2):
+            G.predict(x, mask, frame=None)
+        dt2, _ = timed_steps(G, x, mask, n_vis, args.steps, distributed)
+        out["secondary"] = {"mode": other, "value": B * n_gpus * args.steps / dt2, "unit": "frames/s",
+                            "ms_per_step": 1e3 * dt2 / args.steps,
+                            "note": "plain-bf16 fast mode does NOT meet the 1e-3 parity tolerance (see tests/test_model_gpu.py)"
+                            if other == "fast" else "split-bf16 parity mode"}
+        model.mode = args.mode
+
+    # ---- BASELINE configs[3] beside the headline, at every N: the >= 6x target of the north star is quoted on this STRONG-scaling
+    # batch (256 prompts in total), while `value` above is the weak-scaling frame-pair throughput.  Measurement plumbing only: a
+    # failure here is reported in the line, it does not take the headline down.
+    if args.workload == "base8" and not args.no_prompts:
+        try:
+            _, pm = prompts_measure(args, rank, local_rank, world, distributed, model=model, steps=max(3, args.steps // 4), warmup=2)
+            out["prompts256"] = {k: pm[k] for k in ("value", "unit", "n_gpus", "ms_per_step", "scaling", "steps", "per_rank_ms", "sharded_result_check")}
+            out["prompts256"]["config"] = pm["config"]
+            out["rccl_ranks"], out["collectives"] = pm["config"]["comm_world"], pm["config"]["collectives"]
+        except Exception as e:  # noqa: BLE001
+            out["prompts256"] = {"error": "%s: %s" % (type(e).__name__, e)}
+            if distributed:
+                # the multi-rank path IS what N > 1 is run for: a broken broadcast / gather must not exit 0.  The headline measured above is
+                # still printed (with the error in it), then every rank that saw the failure leaves with a non-zero code -- without the
+                # teardown collectives, which ranks that are out of step with each other could not complete
+                import traceback
+
+                traceback.print_exc()
+                if rank == 0:
+                    print(json.dumps(out), flush=True)
+                os._exit(3)
+
+    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(cfg, wl["k_vis"], wl["clump"], 0)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -617,9 +798,14 @@ def main():
     ap.add_argument("--workload", default="base8", choices=sorted(WORKLOADS) + ["prompts256", "imu4", "flowstats", "prompt_build"])
     ap.add_argument("--mode", default="parity", choices=["parity", "fast"])
     ap.add_argument("--batch", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the extra fast-mode measurement")
-    ap.add_argument("--no-prompts", action="store_true", help="skip the 256-prompt strong-scaling measurement beside the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every check and side measurement beside the headline (output stability, roofline kernel region, the other "
+                         "arithmetic mode, prompts256, per-rank phases, per-stage timings, CPU baseline); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all: a seeded sample of larger outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the extra fast-mode measurement")
+    ap.add_argument("--no-prompts", action="store_true", help="with --full: skip the 256-prompt strong-scaling measurement beside the headline")
     ap.add_argument("--lanes", type=int, default=2, choices=[1, 2, 3, 4],
                     help="2 (library default): the batch runs as two half batches on two HIP streams; 1: one stream")
     args = ap.parse_args()
@@ -675,38 +861,19 @@ def main():
     G = segmentation.FlowGenerator(predictor=model, imagenet_normalize_inputs=True, temporal_dim=2)
     model.sync_weights()
     model.set_lanes(args.lanes)
-    model.predict_video(x, mask, normalize=True, n_vis=n_vis, check=True)  # validates the synthetic masks once (device-side row check)
+    if args.full:
+        model.predict_video(x, mask, normalize=True, n_vis=n_vis, check=True)  # validates the synthetic masks once (device-side row check)
     for _ in range(max(args.warmup, 1)):
         G.predict(x, mask, frame=None)
-    checksum_before = float(G.predict(x, mask, frame=None).double().sum())  # (untimed) the same step again after the timed region must give the same bits
+    if args.full:
+        checksum_before = float(G.predict(x, mask, frame=None).double().sum())  # (untimed) the same step again after the timed region must give the same bits
     torch.cuda.synchronize()
 
     # ---- timed region: `value` -------------------------------------------------------------------------------------------------
-    dt = timed_steps(G, x, mask, n_vis, args.steps, distributed)
-    checksum_after = float(G.predict(x, mask, frame=None).double().sum())
-
-    # ---- kernel region: the same K steps on ONE lane with a HIP event pair around every GEMM launch -> `roofline`.  With two lanes a
-    # launch shares the chip with whatever the other lane runs, so its duration says nothing about the kernel; here launches are alone.
-    # With --lanes 1 the two regions are the same thing (and that is the command the rocprofv3 summaries under profiles/ are taken from).
-    model.set_lanes(1)
-    if args.lanes != 1:
-        for _ in range(2):
-            G.predict(x, mask, frame=None)
-    model.timing_enable(_lib.KCLASS_GEMM, True)
-    model.timing_enable(_lib.KCLASS_ATTENTION, True)
-    for _, kc in EDGE_CLASSES:
-        model.timing_enable(kc, True)
-    dt_one = timed_steps(G, x, mask, n_vis, args.steps, distributed)
-    gemm = model.timing_collect(_lib.KCLASS_GEMM)                 # every GEMM launch ...
-    gemm_wide = model.timing_collect(_lib.KCLASS_GEMM_WIDE)       # ... split by the kernel that ran it
-    gemm_narrow = model.timing_collect(_lib.KCLASS_GEMM_NARROW)
-    attn = model.timing_collect(_lib.KCLASS_ATTENTION)            # softmax(q k^T) v: 4 N^2 64 FLOP per (batch, head)
-    edge = edge_kernels(model.timing_collect)
-    model.timing_enable(_lib.KCLASS_GEMM, False)
-    model.timing_enable(_lib.KCLASS_ATTENTION, False)
-    for _, kc in EDGE_CLASSES:
-        model.timing_enable(kc, False)
-    model.set_lanes(args.lanes)
+    dt, y = timed_steps(G, x, mask, n_vis, args.steps, distributed)
+    if rank == 0:
+        dump_outputs(args.dump_outputs, {"video": y})
+    del y
 
     value = B * n_gpus * args.steps / dt
     flops_pair = C.algorithmic_flops(cfg, n_vis)
@@ -727,80 +894,10 @@ def main():
         },
         "model_tflops": flops_pair * value / 1e12,
         "model_frac_of_bf16_peak": flops_pair * value / 1e12 / (PEAK_BF16_TFLOPS * n_gpus),
-        # one more (untimed) step before and after the timed region: same input, same bits expected (a timing-dependent fault would show here)
-        "output_stable": bool(checksum_before == checksum_after and checksum_after == checksum_after),
         "build": build_info(),
     }
-    planes = 2 if args.mode == "parity" else 1
-    kernels = {  # (names as rocprofv3 prints them)
-        "cwm::gemm8p_kernel<%d>" % planes: gemm_wide,                          # 256x256 8-phase: qkv, fc1, whole rounds of fc2
-        "cwm::gemm_bf16_kernel<%d, 128, 128, 2, 4, 2>" % planes: gemm_narrow,  # 128x128, 8 waves: proj, narrow outputs, remainders
-        "cwm::attention_pipe_kernel<%d, 4>" % planes: attn,   # softmax(q k^T) v
-    }
-
-    def tflops(st):
-        return st["total_flops"] / (st["total_ms"] * 1e-3) / 1e12 if st["total_ms"] > 0 else 0.0
-
-    def kentry(k, v):
-        tf = tflops(v)
-        return dict({"achieved": tf, "frac": tf / PEAK_BF16_TFLOPS, "launches": v["launches"], "avg_launch_us": 1e3 * v["total_ms"] / max(v["launches"], 1),
-                     "share_of_step": v["total_ms"] / (1e3 * dt_one) if dt_one > 0 else None}, **profile_fields(args.workload, args.mode, k, tf / PEAK_BF16_TFLOPS))
-
-    dom = max(kernels, key=lambda k: kernels[k]["total_ms"])  # dominant kernel = most device time in the kernel region (attention included)
-    st = kernels[dom]
-    ach = tflops(st)
-    out["roofline"] = {
-        "bound": "mfma", "kernel": dom, "achieved": ach, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_BF16_TFLOPS,
-        **profile_fields(args.workload, args.mode, dom, ach / PEAK_BF16_TFLOPS),
-        "edge_kernels": edge,
-        "launches": st["launches"], "avg_launch_us": 1e3 * st["total_ms"] / max(st["launches"], 1),
-        "share_of_step": st["total_ms"] / (1e3 * dt_one) if dt_one > 0 else None,
-        "region": {"lanes": 1, "steps": args.steps, "ms_per_step": 1e3 * dt_one / args.steps, "value": B * n_gpus * args.steps / dt_one,
-                   "note": "kernel region: the same steps as the timed region, one lane, HIP events around every GEMM / attention launch"},
-        "note": "algorithmic FLOPs (2*M*N*K per GEMM launch, 4*N^2*64 per (batch, head) of an attention launch) of this kernel's launches in the "
-                "kernel region / their summed HIP-event durations (rank 0)"
-                + ("; parity mode executes 3x these FLOPs on the MFMA pipe (executed_frac)" if args.mode == "parity" else ""),
-        "all_gemm": {"achieved": tflops(gemm), "launches": gemm["launches"], "avg_launch_us": 1e3 * gemm["total_ms"] / max(gemm["launches"], 1),
-                     "share_of_step": gemm["total_ms"] / (1e3 * dt_one) if dt_one > 0 else None},
-        "other_kernel": {k: kentry(k, v) for k, v in kernels.items() if k != dom},
-    }
-
-    if not args.no_secondary:
-        other = "fast" if args.mode == "parity" else "parity"
-        model.mode = other
-        for _ in range(2):
-            G.predict(x, mask, frame=None)
-        dt2 = timed_steps(G, x, mask, n_vis, args.steps, distributed)
-        out["secondary"] = {"mode": other, "value": B * n_gpus * args.steps / dt2, "unit": "frames/s",
-                            "ms_per_step": 1e3 * dt2 / args.steps,
-                            "note": "plain-bf16 fast mode does NOT meet the 1e-3 parity tolerance (see tests/test_model_gpu.py)"
-                            if other == "fast" else "split-bf16 parity mode"}
-        model.mode = args.mode
-
-    # ---- BASELINE configs[3] beside the headline, at every N: the >= 6x target of the north star is quoted on this STRONG-scaling
-    # batch (256 prompts in total), while `value` above is the weak-scaling frame-pair throughput.  Measurement plumbing only: a
-    # failure here is reported in the line, it does not take the headline down.
-    if args.workload == "base8" and not args.no_prompts:
-        try:
-            pm = prompts_measure(args, rank, local_rank, world, distributed, model=model, steps=max(3, args.steps // 4), warmup=2)
-            out["prompts256"] = {k: pm[k] for k in ("value", "unit", "n_gpus", "ms_per_step", "scaling", "steps", "per_rank_ms", "sharded_result_check")}
-            out["prompts256"]["config"] = pm["config"]
-            out["rccl_ranks"], out["collectives"] = pm["config"]["comm_world"], pm["config"]["collectives"]
-        except Exception as e:  # noqa: BLE001
-            out["prompts256"] = {"error": "%s: %s" % (type(e).__name__, e)}
-            if distributed:
-                # the multi-rank path IS what N > 1 is run for: a broken broadcast / gather must not exit 0.  The headline measured above is
-                # still printed (with the error in it), then every rank that saw the failure leaves with a non-zero code -- without the
-                # teardown collectives, which ranks that are out of step with each other could not complete
-                import traceback
-
-                traceback.print_exc()
-                if rank == 0:
-                    print(json.dumps(out), flush=True)
-                os._exit(3)
-
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(cfg, wl["k_vis"], wl["clump"], 0)
+    if args.full:
+        full_extras(args, out, model, G, x, mask, n_vis, cfg, wl, B, checksum_before, rank, local_rank, world, distributed)
     if distributed:
         from counterfactualworldmodels_amd import dist as cdist
 

@@ -650,6 +650,152 @@ def run_round4_cases(ns, skip_large=False):
     print(f"[golden] conj_imu400_ctx_b1.npz y_ctx {tuple(y_c.shape)} std {y_c.std():.4f} ({time.time() - t0:.1f}s)")
 
 
+def _watch_reads(model, log, writes):
+    """Make `model` log every attribute that code of the reference tree reads from it: name -> summary of the first successful read
+    (value for plain data, shape for tensors, "<callable>" / "<object>" otherwise), "<missing>" while a read only ever failed; and into
+    `writes`, in order, every attribute that code sets on it: [name, summary]."""
+    import json as _json
+
+    cls = type(model)
+    root = os.path.realpath(ref_import.REFERENCE_ROOT) + os.sep
+
+    def summary(v):
+        if isinstance(v, torch.Tensor):
+            return {"tensor": list(v.shape)}
+        try:
+            _json.dumps(v)
+            return {"value": v}
+        except (TypeError, ValueError):
+            return "<callable>" if callable(v) else "<object>"
+
+    def __getattribute__(self, name):
+        caller = os.path.realpath(sys._getframe(1).f_code.co_filename)
+        try:
+            v = cls.__getattribute__(self, name)
+        except AttributeError:
+            if caller.startswith(root):
+                log.setdefault(name, "<missing>")
+            raise
+        if caller.startswith(root) and log.get(name, "<missing>") == "<missing>":
+            log[name] = summary(v)
+        return v
+
+    def __getattr__(self, name):  # nn.Module's parameters / buffers / submodules
+        caller = os.path.realpath(sys._getframe(1).f_code.co_filename)
+        try:
+            v = cls.__getattr__(self, name)
+        except AttributeError:
+            if caller.startswith(root):
+                log.setdefault(name, "<missing>")
+            raise
+        if caller.startswith(root) and log.get(name, "<missing>") == "<missing>":
+            log[name] = summary(v)
+        return v
+
+    def __setattr__(self, name, v):
+        if os.path.realpath(sys._getframe(1).f_code.co_filename).startswith(root):
+            writes.append([name, summary(v)])
+        cls.__setattr__(self, name, v)
+
+    model.__class__ = type(cls.__name__, (cls,), {"__getattribute__": __getattribute__, "__getattr__": __getattr__, "__setattr__": __setattr__})
+
+
+def run_seam_case(ns):
+    """The drop-in seam as the reference's own wrapper (`FlowGenerator`, prediction.py:17 / segmentation.py:62) drives it over THIS package's
+    predictor modules, with only the library call stubbed: every call at `self.predictor(self._preprocess(x), mask, ...)` (prediction.py:419-422)
+    -- shapes, dtypes, positional / keyword arguments, the masks and (sub-sampled) inputs it received -- and every attribute the wrapper read
+    from the predictor.  tests/test_reference_seam.py holds this package's predictors and preprocessing to it without the reference tree."""
+    import json
+
+    from counterfactualworldmodels_amd import conjoined_vmae as CV, vmae
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_conj_oracle import TINY_CONJ
+
+    class DummyFlow(torch.nn.Module):
+        def forward(self, x, backward=False, **k):
+            return torch.zeros(x.shape[0], x.shape[1] - 1, 2, *x.shape[-2:])
+
+    out = {}
+    # ---- ViT-B/8: one predict over 2 frame pairs, then the batch driver over 3 prompts of one image
+    model = vmae.base_8x8patch_2frames_1tube()
+    calls, reads = [], {}
+
+    def forward(x, mask, *args, **kwargs):
+        calls.append((x, mask, args, kwargs))
+        B, Nt = mask.shape
+        n_masked = int(mask[0].sum())
+        return torch.zeros(B, n_masked if n_masked else Nt, model.cfg.out_dim)
+
+    model.forward = forward
+    writes = []
+    _watch_reads(model, reads, writes)
+    Psi = ns.segmentation.FlowGenerator(predictor=model, flow_model=DummyFlow(), imagenet_normalize_inputs=True, temporal_dim=2, seed=0)
+    x = torch.rand(2, 2, 3, 224, 224, generator=torch.Generator().manual_seed(0))
+    Psi.set_input(x)
+    mask = Psi.get_zeros_mask().clone()
+    mask[:, 784 + 5] = False
+    y = Psi.predict(x, mask, frame=-1)
+    n, S_n = 784, 3
+    active = torch.ones(1, 2 * n, S_n, dtype=torch.bool)
+    active[:, :n] = False
+    for s in range(S_n):
+        active[0, n + 10 + s, s] = False
+    ys, fs = Psi.predict_counterfactual_videos_and_flows(x[:1, 0], active_patches=active, shifts=[[1, 0], [0, 1], [-1, 1]], num_samples=S_n,
+                                                         sample_batch_size=64)
+    sub = (slice(None), slice(None), slice(None), slice(None, None, 8), slice(None, None, 8))  # [B, C, T, H, W] at a spatial stride of 8
+    out["plain_x_in"] = x[:, :, :, ::8, ::8].numpy()
+    out["plain_seam_x0"] = calls[0][0][sub].numpy()
+    out["plain_masks"] = np.concatenate([c[1].numpy() for c in calls])
+    out["plain_init_mask"] = mask.numpy()
+    out["plain_json"] = np.array(json.dumps({
+        "calls": [{"x_shape": list(c[0].shape), "x_dtype": str(c[0].dtype), "mask_shape": list(c[1].shape), "mask_dtype": str(c[1].dtype),
+                   "n_args": len(c[2]), "kwargs": sorted(c[3])} for c in calls],
+        "reads": reads, "writes": writes, "patch_size": list(Psi.patch_size), "mask_shape": list(Psi.mask_shape),
+        "y_shape": list(y.shape), "ys_shape": list(ys.shape), "fs_shape": list(fs.shape), "shifts": [[int(v) for v in s_] for s_ in Psi.shifts]}))
+
+    # ---- tiny IMU-conditioned conjoined predictor: predict with the context stream's keywords
+    cfg = TINY_CONJ
+    model = CV.ConjoinedPaddedVisionTransformer(cfg)
+    calls, reads = [], {}
+
+    def forward_c(x, mask, timestamps=None, x_context=None, mask_context=None, output_main=None, output_context=None, *args, **kwargs):
+        calls.append(dict(x=x, mask=mask, x_context=x_context, mask_context=mask_context, extra=(args, kwargs)))
+        vis = (~mask).sum(-1)
+        vmax = int(vis.max())
+        model._record_padding_state(mask, vis, vmax)   # what the real forward leaves behind (conjoined_vmae.py:49-116)
+        return torch.zeros(mask.shape[0], mask.shape[1] + cfg.main_max_pad - vmax, cfg.main.out_dim)
+
+    model.forward = forward_c
+    writes_c = []
+    _watch_reads(model, reads, writes_c)
+    Psi = ns.segmentation.FlowGenerator(predictor=model, flow_model=DummyFlow(), imagenet_normalize_inputs=True, temporal_dim=2, seed=0)
+    B, n = 2, cfg.main.tokens_per_frame
+    g = torch.Generator().manual_seed(1)
+    x = torch.rand(B, 2, 3, 32, 32, generator=g)
+    mask = torch.zeros(B, 2 * n, dtype=torch.bool)
+    mask[:, n:] = True
+    mask[:, n + 3] = False
+    imu = torch.randn(B, 6, cfg.ctx_seq_len, generator=g) * 0.1
+    mc = torch.zeros(B, cfg.ctx_tokens, dtype=torch.bool)
+    y = Psi.predict(x, mask, frame=None, reset_masks=False, x_context=imu, mask_context=mc)
+    c = calls[-1]
+    pad_after_predict = list(model.padding_mask.shape) if hasattr(model, "padding_mask") else None
+    Psi.reset_padding_masks()
+    out["conj_x_in"] = x.numpy()
+    out["conj_seam_x"] = c["x"].numpy()
+    out["conj_mask"] = mask.numpy()
+    out["conj_imu"] = imu.numpy()
+    out["conj_json"] = np.array(json.dumps({
+        "n_calls": len(calls), "x_shape": list(c["x"].shape), "mask_shape": list(c["mask"].shape), "mask_dtype": str(c["mask"].dtype),
+        "x_context_is_input": c["x_context"] is imu, "mask_context_is_input": c["mask_context"] is mc,
+        "extra_args": len(c["extra"][0]), "extra_kwargs": sorted(c["extra"][1]), "reads": reads, "writes": writes_c, "y_shape": list(y.shape),
+        "padding_mask_after_predict": pad_after_predict, "padding_mask_after_reset": hasattr(model, "padding_mask")}))
+    np.savez_compressed(os.path.join(HERE, "reference_seam.npz"), **out)
+    print("[golden] reference_seam.npz: %d + %d seam calls, %d + %d predictor attributes read"
+          % (len(json.loads(str(out["plain_json"]))["calls"]), len(calls), len(json.loads(str(out["plain_json"]))["reads"]), len(reads)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-large", action="store_true")
@@ -681,11 +827,15 @@ def main():
     if args.only == "r4":
         run_round4_cases(ns, args.skip_large)
         return
+    if args.only == "seam":
+        run_seam_case(ns)
+        return
     run_init_case(ns)
     run_flowstats_case(ns)
     run_shift_cases(ns)
     run_conj_cases(ns, args.skip_large)
     run_wrapper_cases(ns)
+    run_seam_case(ns)
     run_index_cases(ns)
     run_block_case(ns)
     run_model_case(ns, TINY, batch=3, k_vis=4, clump=1, seed=3, out_name="tiny_8x8_k4.npz")

@@ -1,33 +1,47 @@
-"""The drop-in boundary, pinned from the REFERENCE side: the reference's own wrapper classes (`FlowGenerator`,
-prediction.py:17 / segmentation.py:62, imported from /root/reference in the build container) run over THIS package's
-predictor modules with only the library call stubbed, and the seam `self.predictor(self._preprocess(x), mask, ...)`
-(prediction.py:419-422) must receive what `cwm_forward` / `cwm_conj_forward` are declared to take -- shapes, dtypes, keyword
-names -- and every attribute the wrapper reads must exist.  CPU only; skipped where the reference tree is absent (the GPU box)."""
+"""The drop-in boundary, pinned from the REFERENCE side: what the reference's own wrapper classes (`FlowGenerator`, prediction.py:17 /
+segmentation.py:62) did when they ran over THIS package's predictor modules with only the library call stubbed is stored in
+tests/golden/reference_seam.npz (tests/golden/make_golden.py::run_seam_case).  The seam `self.predictor(self._preprocess(x), mask, ...)`
+(prediction.py:419-422) must receive what `cwm_forward` / `cwm_conj_forward` are declared to take -- shapes, dtypes, keyword names --,
+this package's preprocessing must give the input the reference gave, and every attribute the wrapper read must exist with the value
+it read.  CPU only."""
+import inspect
+import json
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
-import ref_import  # noqa: E402
-
-from counterfactualworldmodels_amd import config as C, conjoined_vmae as CV, vmae  # noqa: E402
-from test_conj_oracle import TINY_CONJ  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not ref_import.reference_available(), reason="reference tree not present (build container only)")
-
-
-class DummyFlow(torch.nn.Module):
-    def forward(self, x, backward=False, **k):
-        return torch.zeros(x.shape[0], x.shape[1] - 1, 2, *x.shape[-2:])
+from counterfactualworldmodels_amd import config as C, conjoined_vmae as CV, prediction, segmentation, vmae
+from test_conj_oracle import TINY_CONJ
 
 
 @pytest.fixture(scope="module")
-def ns():
-    return ref_import.import_reference()
+def seam(golden_dir):
+    g = np.load(os.path.join(golden_dir, "reference_seam.npz"))
+    return {k: (json.loads(str(g[k])) if k.endswith("_json") else g[k]) for k in g.files}
+
+
+def _check_reads(model, rec):
+    """The attributes the reference wrapper set on the predictor are accepted here (replayed in order), every attribute it read exists here with the
+    value / shape it read, and every attribute it probed for and never found is absent here too (its presence would send the wrapper down another
+    branch)."""
+    for name, seen in rec["writes"]:
+        assert isinstance(seen, dict) and "value" in seen, (name, seen)   # plain data only: what a wrapper may set on a module it was handed
+        setattr(model, name, tuple(seen["value"]) if isinstance(seen["value"], list) else seen["value"])
+    for name, seen in rec["reads"].items():
+        if seen == "<missing>":
+            assert not hasattr(model, name), name
+            continue
+        assert hasattr(model, name), name
+        got = getattr(model, name)
+        if isinstance(seen, dict) and "value" in seen:
+            want = seen["value"]
+            assert (list(got) if isinstance(got, (tuple, list)) else got) == want, (name, got, want)
+        elif isinstance(seen, dict) and "tensor" in seen:
+            assert list(got.shape) == seen["tensor"], (name, tuple(got.shape))
+        else:
+            assert callable(got) or got is not None, name
 
 
 def _stub_plain(model, calls):
@@ -41,49 +55,53 @@ def _stub_plain(model, calls):
     model.forward = forward
 
 
-def test_reference_wrapper_over_plain_predictor(ns):
+def test_reference_wrapper_over_plain_predictor(seam):
+    rec = seam["plain_json"]
     cfg = C.CONFIGS["base_8x8patch_2frames_1tube"]
     model = vmae.base_8x8patch_2frames_1tube()
-    calls = []
-    _stub_plain(model, calls)
-    Psi = ns.segmentation.FlowGenerator(predictor=model, flow_model=DummyFlow(), imagenet_normalize_inputs=True, temporal_dim=2, seed=0)
-    assert Psi.patch_size == (1, 8, 8) and model.t_dim == 2 and model.c_dim == 1   # attributes written / read by the wrapper
-    B = 2
-    x = torch.rand(B, 2, 3, 224, 224)
-    Psi.set_input(x)
-    assert tuple(Psi.mask_shape) == (2, 28, 28) == tuple(model.mask_size)
-    mask = Psi.get_zeros_mask().clone()
-    mask[:, 784 + 5] = False
-    y = Psi.predict(x, mask, frame=-1)
-    xs, ms, args, kwargs = calls[-1]
-    assert tuple(xs.shape) == (B, 3, 2, 224, 224) and xs.dtype == torch.float32   # [B,C,T,H,W], imagenet-normalised
-    assert tuple(ms.shape) == (B, 1568) and ms.dtype == torch.bool and not args and not kwargs
+    _check_reads(model, rec)
+    assert {w[0] for w in rec["writes"]} == {"t_dim", "c_dim", "image_size"} and tuple(model.image_size) == (224, 224)
+    assert rec["patch_size"] == [1, 8, 8] and model.t_dim == 2 and model.c_dim == 1   # attributes written / read by the wrapper
+    assert rec["mask_shape"] == [2, 28, 28] == list(model.mask_size)
+    # the seam calls: predict over 2 frame pairs ([B,C,T,H,W], imagenet-normalised; bool masks; nothing else), then the batch driver's 3 prompts
+    # of one image as '(b s)' rows in one call -- every one of them accepted by the predictor's own forward
+    calls = rec["calls"]
+    assert [c["x_shape"] for c in calls] == [[2, 3, 2, 224, 224], [3, 3, 2, 224, 224]]
+    assert all(c["x_dtype"] == "torch.float32" and c["mask_dtype"] == "torch.bool" and c["mask_shape"][1] == cfg.num_tokens for c in calls)
+    assert all(c["n_args"] == 0 and c["kwargs"] == [] for c in calls)
+    sig = inspect.signature(vmae.PretrainVisionTransformer.forward)
+    for c in calls:
+        sig.bind(model, torch.zeros(c["x_shape"]), torch.zeros(c["mask_shape"], dtype=torch.bool))
+    # this package's preprocessing gives the input the reference gave at the seam (elementwise: compared at a spatial stride of 8)
+    x_in = torch.from_numpy(seam["plain_x_in"])
+    assert torch.allclose(prediction.imagenet_normalize(x_in.transpose(1, 2), temporal_dim=2), torch.from_numpy(seam["plain_seam_x0"]), atol=1e-6)
     mean = torch.tensor(C.IMAGENET_MEAN).view(1, 3, 1, 1, 1)
     std = torch.tensor(C.IMAGENET_STD).view(1, 3, 1, 1, 1)
-    assert torch.allclose(xs, (x.transpose(1, 2) - mean) / std, atol=1e-6)
-    assert tuple(y.shape) == (B, 1, 3, 224, 224)
-    assert model.image_size == (224, 224) or tuple(model.image_size) == (224, 224)
-    # the batch driver: S prompts over one image -> '(b s)' rows at the seam, flows from the plugged flow model
-    calls.clear()
-    n = 784
-    S = 3
-    active = torch.ones(1, 2 * n, S, dtype=torch.bool)
-    active[:, :n] = False
-    for s in range(S):
-        active[0, n + 10 + s, s] = False
-    ys, fs = Psi.predict_counterfactual_videos_and_flows(x[:1, 0], active_patches=active, shifts=[[1, 0], [0, 1], [-1, 1]], num_samples=S,
-                                                         sample_batch_size=64)
-    assert tuple(ys.shape) == (S, 2, 3, 224, 224) and tuple(fs.shape) == (S, 1, 2, 224, 224)
-    assert sum(c[0].shape[0] for c in calls) == S and all(c[1].shape[1] == 1568 and c[1].dtype == torch.bool for c in calls)
-    assert all(int(c[1][0].sum()) == 783 for c in calls)   # frame 2 masked except the moved patch
-    assert [tuple(int(v) for v in s_) for s_ in Psi.shifts] == [(1, 0), (0, 1), (-1, 1)]
+    assert torch.allclose(torch.from_numpy(seam["plain_seam_x0"]), (x_in.transpose(1, 2) - mean) / std, atol=1e-6)
+    # the masks at the seam: the caller's (one visible patch in frame 2), then frame 2 masked except each prompt's moved patch
+    masks = torch.from_numpy(seam["plain_masks"])
+    assert torch.equal(masks[:2], torch.from_numpy(seam["plain_init_mask"]))
+    assert (masks[2:].sum(-1) == 783).all() and not masks[2:, :784].any()
+    assert ((~masks[2:, 784:]).sum(-1) == 1).all() and len({int(r.nonzero()) for r in ~masks[2:, 784:]}) == 3   # one moved patch per prompt
+    # this package's wrapper makes the reference's first seam call from the same input: its preprocessing and mask rectangulariser
+    # (`predict_tokens`, the seam of prediction.py:419) hand the predictor the recorded input and mask and nothing else
+    got = []
+    _stub_plain(model, got)
+    G = segmentation.FlowGenerator(predictor=model, imagenet_normalize_inputs=True, temporal_dim=2)
+    G.predict_tokens(x_in, torch.from_numpy(seam["plain_init_mask"]).clone())
+    (xs, ms, args, kwargs), = got
+    assert xs.dtype == torch.float32 and ms.dtype == torch.bool and args == () and kwargs == {}
+    assert torch.allclose(xs, torch.from_numpy(seam["plain_seam_x0"]), atol=1e-6) and torch.equal(ms, masks[:2])
+    assert rec["y_shape"] == [2, 1, 3, 224, 224] and rec["ys_shape"] == [3, 2, 3, 224, 224] and rec["fs_shape"] == [3, 1, 2, 224, 224]
+    assert rec["shifts"] == [[1, 0], [0, 1], [-1, 1]]
     # checkpoint surface: reference key names / shapes (prediction.py:81-107)
     sd = model.state_dict()
     assert tuple(sd["encoder.patch_embed.proj.weight"].shape) == (768, 3, 1, 8, 8) and "encoder_to_decoder.weight" in sd and "mask_token" in sd
     assert sum(v.numel() for v in sd.values()) == 92661312
 
 
-def test_reference_wrapper_over_conjoined_predictor(ns):
+def test_reference_wrapper_over_conjoined_predictor(seam):
+    rec = seam["conj_json"]
     cfg = TINY_CONJ
     model = CV.ConjoinedPaddedVisionTransformer(cfg)
     calls = []
@@ -95,26 +113,33 @@ def test_reference_wrapper_over_conjoined_predictor(ns):
         model._record_padding_state(mask, vis, vmax)   # what the real forward leaves behind (conjoined_vmae.py:49-116)
         return torch.zeros(mask.shape[0], mask.shape[1] + cfg.main_max_pad - vmax, cfg.main.out_dim)
 
-    model.forward = forward
-    Psi = ns.segmentation.FlowGenerator(predictor=model, flow_model=DummyFlow(), imagenet_normalize_inputs=True, temporal_dim=2, seed=0)
     # attributes the wrapper / UI read on a conjoined predictor
     assert model.context_stream.encoder.num_tokens == cfg.ctx_tokens and model.context_stream.patch_size[0] == cfg.ctx_tubelet
     assert model.get_context_input.num_channels == 6 and model.main_stream.max_padding_tokens == cfg.main_max_pad
     assert not hasattr(model, "padding_mask")          # before a forward, as in the reference (conjoined_vmae.py:347-354)
     B, n = 2, cfg.main.tokens_per_frame
-    x = torch.rand(B, 2, 3, 32, 32)
-    mask = torch.zeros(B, 2 * n, dtype=torch.bool)
-    mask[:, n:] = True
-    mask[:, n + 3] = False
-    imu = torch.randn(B, 6, cfg.ctx_seq_len) * 0.1
+    x = torch.from_numpy(seam["conj_x_in"])
+    mask = torch.from_numpy(seam["conj_mask"])
+    imu = torch.from_numpy(seam["conj_imu"])
     mc = torch.zeros(B, cfg.ctx_tokens, dtype=torch.bool)
-    y = Psi.predict(x, mask, frame=None, reset_masks=False, x_context=imu, mask_context=mc)
-    c = calls[-1]
-    assert tuple(c["x"].shape) == (B, 3, 2, 32, 32) and tuple(c["mask"].shape) == (B, 2 * n) and c["mask"].dtype == torch.bool
-    assert c["x_context"] is imu and c["mask_context"] is mc and c["extra"] == ((), {})
-    assert tuple(y.shape) == (B, 2, 3, 32, 32)         # pad rows dropped, `get_current_inputs` used for the un-embed
-    assert hasattr(model, "padding_mask") and tuple(model.padding_mask.shape) == (B, cfg.main_max_pad)
-    (cx, cm, _), = model.get_current_inputs(Psi._preprocess(x), mask, x_context=imu, mask_context=mc)
+    assert tuple(x.shape) == (B, 2, 3, 32, 32) and tuple(mask.shape) == (B, 2 * n) and mask[:, n:].sum() == B * (n - 1) and not mask[:, :n].any()
+    # the one seam call of `predict(..., x_context=imu, mask_context=mc)`: [B,C,T,H,W] + bool mask, the context keywords passed through as given,
+    # nothing else -- accepted by the predictor's own forward
+    assert rec["n_calls"] == 1 and rec["x_shape"] == [B, 3, 2, 32, 32] and rec["mask_shape"] == [B, 2 * n] and rec["mask_dtype"] == "torch.bool"
+    assert rec["x_context_is_input"] and rec["mask_context_is_input"] and rec["extra_args"] == 0 and rec["extra_kwargs"] == []
+    inspect.signature(CV.ConjoinedPaddedVisionTransformer.forward).bind(model, x.transpose(1, 2), mask, x_context=imu, mask_context=mc)
+    seam_x = torch.from_numpy(seam["conj_seam_x"])
+    assert torch.allclose(prediction.imagenet_normalize(x.transpose(1, 2), temporal_dim=2), seam_x, atol=1e-6)
+    # the stubbed forward leaves the padding state the wrapper then reads (`padding_mask` [B, max_pad]) and un-embeds against
+    model.forward = forward
+    y = model(seam_x, mask, x_context=imu, mask_context=mc)
+    assert tuple(y.shape) == (B, 2 * n + cfg.main_max_pad - int((~mask).sum(-1).max()), cfg.main.out_dim)
+    assert rec["y_shape"] == [B, 2, 3, 32, 32]         # pad rows dropped, `get_current_inputs` used for the un-embed
+    assert hasattr(model, "padding_mask") and [*model.padding_mask.shape] == rec["padding_mask_after_predict"] == [B, cfg.main_max_pad]
+    _check_reads(model, rec)
+    (cx, cm, _), = model.get_current_inputs(seam_x, mask, x_context=imu, mask_context=mc)
     assert tuple(cx.shape) == (B, 3, 2, 32, 32) and torch.equal(cm, mask)
-    Psi.reset_padding_masks()
+    # the wrapper's reset leaves no padding state behind, in the reference as here
+    assert rec["padding_mask_after_reset"] is False
+    segmentation.FlowGenerator(predictor=model, imagenet_normalize_inputs=True, temporal_dim=2).reset_padding_masks()
     assert not hasattr(model, "padding_mask")

@@ -15,7 +15,7 @@ export CWM_CONJ_CTX_STREAM=0
 fail=0
 for wl in base8 large4 imu4; do
   steps=5; [ $wl = base8 ] || steps=3
-  BENCH="python3 bench.py --workload $wl --steps $steps --warmup 1 --no-cpu-baseline --no-secondary --no-prompts --lanes 1"
+  BENCH="python3 bench.py --full --workload $wl --steps $steps --warmup 1 --no-cpu-baseline --no-secondary --no-prompts --lanes 1"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_${wl}_parity -- $BENCH > $OUT/stats_${wl}_parity.log 2>&1
   grep '^{"metric"' $OUT/stats_${wl}_parity.log | tail -1 > $OUT/bench_under_rocprof_${wl}_parity.json
   [ -s $OUT/bench_under_rocprof_${wl}_parity.json ] || { echo "NO BENCH LINE for $wl (see $OUT/stats_${wl}_parity.log)"; fail=1; }
@@ -24,7 +24,7 @@ for wl in base8 large4 imu4; do
   rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pmc_mfma_$wl -- $BENCH > $OUT/pmc_mfma_$wl.log 2>&1 || fail=1
 done
 unset CWM_CONJ_CTX_STREAM
-BENCH="python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-secondary --no-prompts"
+BENCH="python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-secondary --no-prompts"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_base8_fast -- $BENCH --lanes 1 --mode fast > $OUT/stats_base8_fast.log 2>&1
 # the default command (two lanes in the timed region + the one-lane kernel region): launch durations of the first overlap
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_base8_parity_default -- $BENCH > $OUT/stats_base8_parity_default.log 2>&1
@@ -36,7 +36,7 @@ done
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_b1 -- python3 tools/latency_b1.py 1 > $OUT/stats_b1.log 2>&1
 # the kernels either side of the predictor path: kernel stats + FETCH / WRITE passes of the two edge workloads
 for wl in flowstats prompt_build; do
-  BENCH="python3 bench.py --workload $wl --steps 5 --no-cpu-baseline"
+  BENCH="python3 bench.py --full --workload $wl --steps 5 --no-cpu-baseline"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_${wl}_f32 -- $BENCH > $OUT/stats_${wl}_f32.log 2>&1
   grep '^{"metric"' $OUT/stats_${wl}_f32.log | tail -1 > $OUT/bench_under_rocprof_${wl}_f32.json
   [ -s $OUT/bench_under_rocprof_${wl}_f32.json ] || { echo "NO BENCH LINE for $wl (see $OUT/stats_${wl}_f32.log)"; fail=1; }
@@ -44,7 +44,7 @@ for wl in flowstats prompt_build; do
   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write_$wl -- $BENCH > $OUT/pmc_write_$wl.log 2>&1 || fail=1
 done
 # the covariance kernel runs on the fp32 matrix pipe: its MFMA-busy share and clock
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pmc_mfma_flowstats -- python3 bench.py --workload flowstats --steps 5 --no-cpu-baseline > $OUT/pmc_mfma_flowstats.log 2>&1 || fail=1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pmc_mfma_flowstats -- python3 bench.py --full --workload flowstats --steps 5 --no-cpu-baseline > $OUT/pmc_mfma_flowstats.log 2>&1 || fail=1
 find $OUT -name "*.csv" | wc -l
 # a Python traceback in any log of the set = the set is not evidence (round 5 committed one as a "per-shape kernel rate" log)
 if grep -l "Traceback (most recent call last)" $OUT/*.log 2>/dev/null; then echo "TRACEBACK in the logs listed above"; fail=1; fi

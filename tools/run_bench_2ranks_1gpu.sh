@@ -7,5 +7,5 @@ N=${1:-2}
 echo "# without the hooks: must fail loudly (exit 2) on a 1-GPU box"
 timeout 120 python bench.py --gpus $N --steps 2 --warmup 1; echo "exit code $?"
 export CWM_BENCH_ONE_DEVICE=1 CWM_BENCH_BACKEND=gloo CWM_COMM=torch
-timeout 150 python bench.py --gpus $N --steps 3 --warmup 1 --no-secondary 2>/dev/null | tail -1
-timeout 150 python bench.py --gpus $N --steps 2 --warmup 1 --workload prompts256 2>/dev/null | tail -1
+timeout 150 python bench.py --full --gpus $N --steps 3 --warmup 1 --no-secondary 2>/dev/null | tail -1
+timeout 150 python bench.py --full --gpus $N --steps 2 --warmup 1 --workload prompts256 2>/dev/null | tail -1

@@ -5,15 +5,15 @@ OUT=gpurun_out/final_$TAG
 mkdir -p $OUT
 timeout 1500 python -m pytest tests -m gpu -q -s > $OUT/pytest_gpu.log 2>&1; tail -1 $OUT/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench_base8.json 2> $OUT/bench_base8.err
-timeout 600 python bench.py --steps 20 --warmup 5 --lanes 1 --no-cpu-baseline --no-prompts > $OUT/bench_base8_lanes1.json 2>/dev/null
-timeout 600 python bench.py --workload large4 --steps 8 --warmup 2 --no-cpu-baseline > $OUT/bench_large4.json 2> $OUT/bench_large4.err
-timeout 600 python bench.py --workload large4 --mode fast --steps 8 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/bench_large4_fast.json 2>/dev/null
-timeout 600 python bench.py --workload imu4 --steps 8 --warmup 2 > $OUT/bench_imu4.json 2> $OUT/bench_imu4.err
-timeout 600 python bench.py --workload imu4 --mode fast --steps 8 --warmup 2 > $OUT/bench_imu4_fast.json 2>/dev/null
-timeout 600 python bench.py --workload prompts256 --steps 8 --warmup 2 > $OUT/bench_prompts256.json 2>/dev/null
-timeout 300 python bench.py --workload flowstats --steps 10 > $OUT/bench_flowstats.json 2> $OUT/bench_flowstats.err
-timeout 300 python bench.py --workload prompt_build --steps 20 > $OUT/bench_prompt_build.json 2> $OUT/bench_prompt_build.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_base8.json 2> $OUT/bench_base8.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --lanes 1 --no-cpu-baseline --no-prompts > $OUT/bench_base8_lanes1.json 2>/dev/null
+timeout 600 python bench.py --full --workload large4 --steps 8 --warmup 2 --no-cpu-baseline > $OUT/bench_large4.json 2> $OUT/bench_large4.err
+timeout 600 python bench.py --full --workload large4 --mode fast --steps 8 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/bench_large4_fast.json 2>/dev/null
+timeout 600 python bench.py --full --workload imu4 --steps 8 --warmup 2 > $OUT/bench_imu4.json 2> $OUT/bench_imu4.err
+timeout 600 python bench.py --full --workload imu4 --mode fast --steps 8 --warmup 2 > $OUT/bench_imu4_fast.json 2>/dev/null
+timeout 600 python bench.py --full --workload prompts256 --steps 8 --warmup 2 > $OUT/bench_prompts256.json 2>/dev/null
+timeout 300 python bench.py --full --workload flowstats --steps 10 > $OUT/bench_flowstats.json 2> $OUT/bench_flowstats.err
+timeout 300 python bench.py --full --workload prompt_build --steps 20 > $OUT/bench_prompt_build.json 2> $OUT/bench_prompt_build.err
 timeout 600 python tools/latency.py > $OUT/latency.log 2>&1
 timeout 600 python tools/microbench.py gemm > $OUT/microbench_gemm_b8.log 2>&1
 timeout 600 python tools/microbench.py attn > $OUT/microbench_attn.log 2>&1

@@ -60,7 +60,7 @@ f = one("stats_b1/**/*kernel_stats.csv")
 if f:
     shutil.copy(f, os.path.join(dst, "%s_kernel_stats_latency_b1_parity.csv" % tag))
 
-out = {"tag": tag, "command": "python3 bench.py --workload <w> --steps 5|3 --warmup 1 --no-cpu-baseline --no-secondary --no-prompts --lanes 1 (parity mode; "
+out = {"tag": tag, "command": "python3 bench.py --full --workload <w> --steps 5|3 --warmup 1 --no-cpu-baseline --no-secondary --no-prompts --lanes 1 (parity mode; "
                               "imu4 with CWM_CONJ_CTX_STREAM=0: no two kernels overlap)", "workloads": {}}
 latest = {"entries": {}}
 for wl in WORKLOADS:
