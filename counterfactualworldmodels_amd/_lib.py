@@ -115,6 +115,24 @@ class CwmConjForwardArgs(C.Structure):
         ("check", C.c_int32),
         ("stream", C.c_void_p),
         ("y_ctx_tokens_dev", C.c_void_p),
+        ("flow_fwd_dev", C.c_void_p),
+        ("flow_fwd_stride_b", C.c_int64),
+        ("flow_fwd_stride_c", C.c_int64),
+        ("flow_bwd_dev", C.c_void_p),
+        ("flow_bwd_stride_b", C.c_int64),
+        ("flow_bwd_stride_c", C.c_int64),
+    ]
+
+
+CONJ_INPUT_FRAMES, CONJ_INPUT_FLOWBACK_RGB01 = 0, 1
+
+
+class CwmConjVariant(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("padded", C.c_int32),
+        ("ctx_dummy_token", C.c_int32),
+        ("main_input", C.c_int32),
     ]
 
 
@@ -145,6 +163,7 @@ SIGNATURES = {
     "cwm_model_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "cwm_conj_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "cwm_conj_create": (C.c_int, [C.POINTER(CwmConjConfig), C.POINTER(C.c_void_p)]),
+    "cwm_conj_create_ex": (C.c_int, [C.POINTER(CwmConjConfig), C.POINTER(CwmConjVariant), C.POINTER(C.c_void_p)]),
     "cwm_conj_destroy": (None, [C.c_void_p]),
     "cwm_conj_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "cwm_conj_missing_weights": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),

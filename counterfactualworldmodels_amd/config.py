@@ -147,6 +147,10 @@ class ConjConfig:
     dec_cross: Tuple[int, ...] = (0, 1, 2, 3)
     cross_heads: int = 4
     cross_mlp_ratio: int = 2
+    # the unpadded flow -> IMU variant (ConjoinedPretrainVisionTransformer, conjoined_vmae.py:212-887); the defaults are the padded model
+    padded: bool = True
+    ctx_dummy_token: bool = False  # ImuEncoder(concat_dummy_token=True): a learned, always visible 26th IMU token (:1013-1147)
+    main_input: str = "rgb01"      # or "flowback_rgb01" (preprocessor.py:208-277, 356): 7 channels from two flows and frame 1
 
     @property
     def ctx_tokens(self) -> int:
@@ -157,7 +161,22 @@ class ConjConfig:
         return self.ctx_in_chans * self.ctx_tubelet
 
 
-CONJ_CONFIGS: Dict[str, ConjConfig] = {"imu400_base_4x4patch_2frames_1tube": ConjConfig()}
+CONJ_CONFIGS: Dict[str, ConjConfig] = {
+    "imu400_base_4x4patch_2frames_1tube": ConjConfig(),
+    # the flow -> IMU head-motion predictor (conjoined_vmae.py:1218-1228): one 7-channel frame of 784 tokens, cross blocks before
+    # encoder layers 0 and 11 (conjoin_encoder_layers=[0, -1]) and after every decoder layer
+    "imu400_8x8patch_2frames_1tube_flowbackrgb01": ConjConfig(
+        name="imu400_8x8patch_2frames_1tube_flowbackrgb01",
+        main=VmaeConfig(name="flow2imu_main_8x8", patch=8, num_frames=1, in_chans=7),
+        main_max_pad=0,
+        ctx_max_pad=0,
+        enc_cross=(0, 11),
+        dec_cross=(0, 1, 2, 3),
+        padded=False,
+        ctx_dummy_token=True,
+        main_input="flowback_rgb01",
+    ),
+}
 
 
 def _cross_schema(pre: str, ci: int, cs: int, ratio: int, out: "OrderedDict[str, tuple]") -> None:
@@ -194,15 +213,19 @@ def conj_state_dict_schema(cfg: ConjConfig) -> "OrderedDict[str, tuple]":
     m = cfg.main
     main = state_dict_schema(m)
     s["main_stream.mask_token"] = main["mask_token"]
-    s["main_stream.null_token_enc"] = (1, 1, m.enc_dim)
-    s["main_stream.null_token_dec"] = (1, 1, m.dec_dim)
+    if cfg.padded:
+        s["main_stream.null_token_enc"] = (1, 1, m.enc_dim)
+        s["main_stream.null_token_dec"] = (1, 1, m.dec_dim)
     for k, v in main.items():
         if k != "mask_token":
             s["main_stream." + k] = v
     c = "context_stream."
     s[c + "mask_token"] = (1, 1, cfg.ctx_dec_dim)
-    s[c + "null_token_enc"] = (1, 1, cfg.ctx_enc_dim)
-    s[c + "null_token_dec"] = (1, 1, cfg.ctx_dec_dim)
+    if cfg.padded:
+        s[c + "null_token_enc"] = (1, 1, cfg.ctx_enc_dim)
+        s[c + "null_token_dec"] = (1, 1, cfg.ctx_dec_dim)
+    if cfg.ctx_dummy_token:
+        s[c + "encoder.dummy_token"] = (1, cfg.ctx_in_chans, cfg.ctx_tubelet, 1, 1)
     s[c + "encoder.patch_embed.proj.weight"] = (cfg.ctx_enc_dim, cfg.ctx_in_chans, cfg.ctx_tubelet, 1, 1)
     s[c + "encoder.patch_embed.proj.bias"] = (cfg.ctx_enc_dim,)
     for i in range(m.enc_depth):

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .config import CONJ_CONFIGS, LN_EPS, ConjConfig, conj_state_dict_schema
+from .config import CONJ_CONFIGS, IMAGENET_MEAN, IMAGENET_STD, LN_EPS, ConjConfig, conj_state_dict_schema
 from .vmae import WeightSync
 
 
@@ -180,11 +180,14 @@ class ConjoinedPaddedVisionTransformer(WeightSync, nn.Module):
         cc.cross_heads, cc.cross_mlp_ratio = c.cross_heads, c.cross_mlp_ratio
         h = C.c_void_p()
         with torch.cuda.device(device):
-            self._check(lib.cwm_conj_create(C.byref(cc), C.byref(h)))
+            self._check(self._create(lib, cc, h))
         self._handle, self._handle_device, self._loaded = h.value, device, {}
         for k, v in self.__dict__.get("_options", {}).items():
             self._check(lib.cwm_conj_set_option(self._handle, k.encode(), v))
         return self._handle
+
+    def _create(self, lib, cc, h):
+        return lib.cwm_conj_create(C.byref(cc), C.byref(h))
 
     def _release(self):
         if getattr(self, "_handle", None) is not None:
@@ -326,3 +329,156 @@ class ConjoinedPaddedVisionTransformer(WeightSync, nn.Module):
 def imu400_base_4x4patch_2frames_1tube(**kwargs):
     """conjoined_vmae.py:1230-1243"""
     return ConjoinedPaddedVisionTransformer(CONJ_CONFIGS["imu400_base_4x4patch_2frames_1tube"], **kwargs)
+
+
+class ConjoinedPretrainVisionTransformer(ConjoinedPaddedVisionTransformer):
+    """The unpadded conjoined model of the flow -> IMU head-motion predictor (`ConjoinedPretrainVisionTransformer`,
+    conjoined_vmae.py:212-887; factory `imu400_8x8patch_2frames_1tube_flowbackrgb01` :1218-1228).
+
+    Same surface as the reference: the 583 state-dict keys, `forward(x, mask, timestamps=None, x_context=None, mask_context=None,
+    output_main=None, output_context=None)` on the imagenet-normalised frames [B,3,2,H,W] and a mask over both frames
+    (`mask_size` (2, 28, 28); the main stream reads its frame-1 half).  The main stream's 7 input channels (`FlowBackRGB01`,
+    preprocessor.py:208-277) come from `flow_model` -- any module with RAFT's multi-frame call signature, run in PyTorch on the
+    un-normalised frames -- and frame 1; scaling, normalisation and the patch gather happen in-kernel.  Every row must have the same
+    visible count in each stream (the reference reshapes `x[~mask]`).  The context stream appends its learned dummy token (always
+    visible), so an entirely masked IMU leaves the context encoder one token.  `output_context=True` returns the context stream's
+    predictions [B, 25 - visible IMU tokens, 96]."""
+
+    def __init__(self, cfg: ConjConfig, mode: str = "parity", flow_model=None, raft_iters: int = 24, **unused):
+        assert not cfg.padded and cfg.ctx_dummy_token and cfg.main_input == "flowback_rgb01", cfg
+        super().__init__(cfg, mode=mode)
+        self.num_frames = 2  # mask_size covers both input frames (conjoined_vmae.py:356-360)
+        self.get_main_input = type("FlowBackRGB01", (), {"num_channels": cfg.main.in_chans, "num_frames": 1, "frames_list": [0, 1]})()
+        # a plain attribute, not a submodule: the flow model's parameters are not part of this model's state dict
+        object.__setattr__(self, "flow_model", flow_model)
+        self.raft_iters = raft_iters
+        for stream in (self.main_stream, self.context_stream):  # the unpadded streams have no padding state (hasattr is False)
+            for k in ("padding_mask", "full_input_mask", "null_mask", "_reset_padding_mask", "max_padding_tokens", "min_padding_tokens"):
+                stream.__dict__.pop(k, None)
+
+    def _reset_padding_mask(self):
+        pass
+
+    @property
+    def max_padding_tokens(self):
+        return 0
+
+    @property
+    def min_padding_tokens(self):
+        return 0
+
+    def set_flow_model(self, flow_model):
+        object.__setattr__(self, "flow_model", flow_model)
+
+    def _create(self, lib, cc, h):
+        v = _lib.CwmConjVariant(C.sizeof(_lib.CwmConjVariant), 0, 1, _lib.CONJ_INPUT_FLOWBACK_RGB01)
+        return lib.cwm_conj_create_ex(C.byref(cc), C.byref(v), C.byref(h))
+
+    @property
+    def padding_mask(self):
+        raise AttributeError("the unpadded conjoined model has no padding_mask")
+
+    def get_current_inputs(self, x, mask, *args, **kwargs):  # pragma: no cover - the reference's training helper
+        raise NotImplementedError("get_current_inputs is not provided for the flow -> IMU model")
+
+    def _require_flow_model(self):
+        if self.flow_model is None:
+            raise RuntimeError("this flow -> IMU model has no flow_model: pass flow_model= (RAFT, or any module called as "
+                               "flow_model(x[B,2,3,H,W] in [0,1], iters=..., backward=...) -> [B,1,2,H,W]) to the factory, or set_flow_model()")
+
+    def compute_flows(self, x, normalized: bool = True):
+        """(forward, backward) flow of frames 0 -> 1, each [B,2,H,W] in pixels, from the frames x [B,3,2,H,W]: imagenet-normalised
+        (`FramePairFlow.get_flow` on `imagenet_unnormalize(x)`, preprocessor.py:226-277) or, with normalized=False, in [0,1]."""
+        self._require_flow_model()
+        x01 = x[:, :, :2]
+        if normalized:
+            mean = torch.tensor(IMAGENET_MEAN, device=x.device, dtype=x.dtype).view(1, 3, 1, 1, 1)
+            std = torch.tensor(IMAGENET_STD, device=x.device, dtype=x.dtype).view(1, 3, 1, 1, 1)
+            x01 = x01 * std + mean
+        x01 = x01.transpose(1, 2)
+        fwd = self.flow_model(x01, iters=self.raft_iters, backward=False)
+        bwd = self.flow_model(x01, iters=self.raft_iters, backward=True)
+        return fwd[:, 0], bwd[:, 0]
+
+    @staticmethod
+    def _flow_operand(f, B, H, W):
+        f = f.to(dtype=torch.float32)
+        if tuple(f.shape) != (B, 2, H, W):
+            raise RuntimeError("expected a flow of shape [B,2,H,W] = %s, got %s" % ((B, 2, H, W), tuple(f.shape)))
+        if f.stride(-1) != 1 or f.stride(-2) != W or f.stride(0) % 4 or f.stride(1) % 4 or f.data_ptr() % 16:
+            f = f.contiguous()
+        return f
+
+    @torch.no_grad()
+    def forward(self, x, mask, timestamps=None, x_context=None, mask_context=None, output_main=None, output_context=None,
+                *args, flows=None, normalize: bool = False, check: bool = True, **kwargs):
+        """`flows`: (forward, backward) [B,2,H,W] pixel flows instead of calling flow_model (any strides with contiguous rows).
+        `normalize=True`: x holds the frames in [0,1] (the flow model's input as it is) and frame 1 is imagenet-normalised in-kernel,
+        as the padded model's `normalize`; by default x is imagenet-normalised, as the reference's forward takes it."""
+        if timestamps is not None:
+            raise NotImplementedError("timestamps are not supported (the IMU-conditioned path ignores them as well)")
+        if flows is None:
+            self._require_flow_model()
+        _lib.require_gpu()
+        if output_main is not None:
+            self._output_main = bool(output_main)
+        if output_context is not None:
+            self._output_context = bool(output_context)
+        want_main, want_ctx = self._output_main, self._output_context
+        if not want_main and not want_ctx:
+            want_main = want_ctx = True
+        c, m = self.cfg, self.cfg.main
+        H, W = m.img_size
+        if x_context is None:
+            raise RuntimeError("the flow -> IMU model needs x_context [B,%d,%d] (an all-masked zero IMU to predict it from the video)"
+                               % (c.ctx_in_chans, c.ctx_seq_len))
+        if not x.is_cuda:
+            raise RuntimeError("ConjoinedPretrainVisionTransformer.forward needs CUDA/HIP tensors (no CPU fallback); got %s" % x.device)
+        if x.dim() != 5 or x.shape[1] != 3 or x.shape[2] < 2 or tuple(x.shape[-2:]) != (H, W):
+            raise RuntimeError("expected x of shape [B,3,2,%d,%d], got %s" % (H, W, tuple(x.shape)))
+        dev, B, Nt = x.device, x.shape[0], m.num_tokens
+        if flows is None:
+            flows = self.compute_flows(x, normalized=not normalize)
+        fwd, bwd = (self._flow_operand(f.to(dev), B, H, W) for f in flows)
+        self.sync_weights(dev)
+        if x.dtype != torch.float32:
+            x = x.float()
+        if x.stride(-1) != 1 or x.stride(-2) != W or x.stride(0) % 4 or x.stride(1) % 4 or x.data_ptr() % 16:
+            x = x.contiguous()
+        frame1 = x[:, :, 1]
+        mask = mask.to(device=dev, dtype=torch.bool).reshape(B, -1)
+        if mask.shape[1] != 2 * Nt:
+            raise RuntimeError("mask has %d tokens per row, model expects %d (both frames)" % (mask.shape[1], 2 * Nt))
+        mask_m = mask[:, Nt:].contiguous()  # the main stream reads the frame-1 half (get_stream_inputs :430-486)
+        ctx = x_context.to(device=dev, dtype=torch.float32).reshape(B, c.ctx_in_chans, c.ctx_seq_len).contiguous()
+        if mask_context is None:
+            mask_context = torch.zeros(B, c.ctx_tokens, dtype=torch.bool, device=dev)
+        mc = mask_context.to(device=dev, dtype=torch.bool).reshape(B, c.ctx_tokens).contiguous()
+        # the largest visible counts; the library rejects rows that differ (CWM_ERR_INVALID)
+        vm, vc = (int(v) for v in torch.stack([(~mask_m).sum(-1).max(), (~mc).sum(-1).max()]).tolist())
+        vc += 1  # the dummy token
+        n_out, n_out_c = Nt - vm, c.ctx_tokens + 1 - vc
+        y = torch.empty((B, n_out, m.out_dim), device=dev, dtype=torch.float32) if want_main else None
+        y_ctx = torch.empty((B, n_out_c, c.ctx_out_dim), device=dev, dtype=torch.float32) if want_ctx else None
+        args_ = _lib.CwmConjForwardArgs()
+        args_.struct_size = C.sizeof(_lib.CwmConjForwardArgs)
+        args_.x_dev, args_.x_stride_b, args_.x_stride_c, args_.normalize = frame1.data_ptr(), frame1.stride(0), frame1.stride(1), int(normalize)
+        args_.mask_dev, args_.batch, args_.n_vis_max = mask_m.data_ptr(), B, vm
+        args_.ctx_dev, args_.ctx_mask_dev, args_.n_vis_ctx_max = ctx.data_ptr(), mc.data_ptr(), vc
+        args_.y_tokens_dev = y.data_ptr() if (y is not None and n_out > 0) else None
+        args_.y_ctx_tokens_dev = _lib.ptr(y_ctx)
+        args_.mode, args_.check, args_.stream = _lib.mode_id(self.mode), int(check), _lib.current_stream_handle(dev)
+        args_.flow_fwd_dev, args_.flow_fwd_stride_b, args_.flow_fwd_stride_c = fwd.data_ptr(), fwd.stride(0), fwd.stride(1)
+        args_.flow_bwd_dev, args_.flow_bwd_stride_b, args_.flow_bwd_stride_c = bwd.data_ptr(), bwd.stride(0), bwd.stride(1)
+        if args_.y_tokens_dev is None and args_.y_ctx_tokens_dev is None:
+            return y  # nothing to compute: every main token visible and no context output asked for
+        with torch.cuda.device(dev):
+            self._check(self._library().cwm_conj_forward(self._handle, C.byref(args_)))
+        if want_main and want_ctx:
+            return y, y_ctx
+        return y if want_main else y_ctx
+
+
+def imu400_8x8patch_2frames_1tube_flowbackrgb01(flow_model=None, **kwargs):
+    """conjoined_vmae.py:1218-1228: the flow -> IMU head-motion predictor.  `flow_model` (RAFT in the reference) may be set later."""
+    return ConjoinedPretrainVisionTransformer(CONJ_CONFIGS["imu400_8x8patch_2frames_1tube_flowbackrgb01"], flow_model=flow_model, **kwargs)

@@ -105,6 +105,32 @@ int launch_imu_gather(const ImuGatherParams& p, int planes, hipStream_t stream) 
     return 0;
 }
 
+__global__ void imu_append_dummy_kernel(const float* imu, const uint8_t* mask, const float* dummy, int C, int L, int T, int n, float* out, uint8_t* mask_out,
+                                        int64_t total, int total_mask) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid < total_mask) {
+        const int b = (int)gid / (n + 1), j = (int)gid - b * (n + 1);
+        mask_out[gid] = j < n ? mask[(size_t)b * n + j] : (uint8_t)0;
+    }
+    if (gid >= total) return;
+    const int LT = L + T;
+    const int64_t bc = gid / LT;
+    const int l = (int)(gid - bc * LT);
+    const int c = (int)(bc % C);
+    out[gid] = l < L ? imu[bc * L + l] : dummy[c * T + (l - L)];
+}
+
+int launch_imu_append_dummy(const float* imu, const uint8_t* mask, const float* dummy, int B, int C, int L, int T, int n, float* out, uint8_t* mask_out,
+                            hipStream_t stream) {
+    const int64_t total = (int64_t)B * C * (L + T);
+    const int total_mask = B * (n + 1);
+    const int64_t work = std::max<int64_t>(total, total_mask);
+    hipLaunchKernelGGL(imu_append_dummy_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, stream, imu, mask, dummy, C, L, T, n, out, mask_out, total,
+                       total_mask);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Short-sequence self-attention (context stream): one 64-thread workgroup per (batch, head), thread n
 // owns query n; K and V of the head live in LDS.  `Attention.forward` VideoMAE/utils.py:87-121, fp32.

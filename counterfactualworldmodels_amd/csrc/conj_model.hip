@@ -36,7 +36,12 @@ struct StreamW {
 struct cwm_conj_model {
     Engine eng;
     cwm_conj_config cfg;
+    cwm_conj_variant var;  // cwm_conj_create_ex; cwm_conj_create: padded, no dummy token, frames
     StreamW main, ctx;
+    float* dummy = nullptr;  // context_stream.encoder.dummy_token [ctx_in_chans][ctx_tubelet] (var.ctx_dummy_token)
+    // var.ctx_dummy_token: the call's IMU [B][C][L] + dummy as [B][C][L + tubelet] and its mask + the visible dummy as [B][n + 1]
+    float* ctx_stage = nullptr;
+    uint8_t* ctx_mask_stage = nullptr;
     std::vector<CrossW> enc_cross, dec_cross;
     // workspace shared by the cross blocks
     int ws_batch = 0, ws_vmain = 0, ws_vctx = 0;
@@ -130,7 +135,7 @@ ConjLane conj_lane(cwm_conj_model* m, int lane, int b0) {
 namespace {
 
 int make_stream(Engine& E, StreamW& S, const std::string& pre, int embed_k, std::vector<int64_t> embed_shape, int depth_e, int depth_d,
-                int mlp_ratio, bool sinusoid_f64) {
+                int mlp_ratio, bool sinusoid_f64, bool null_tokens) {
     int rc;
     S.embed_k = embed_k;
     S.embed_kpad = round_up(embed_k, 64);
@@ -156,7 +161,7 @@ int make_stream(Engine& E, StreamW& S, const std::string& pre, int embed_k, std:
     E.add_vec_slot(pre + "decoder.head.bias", S.head.bias, {S.out_dim});
     if ((rc = E.make_vec(&S.mask_token, S.dec_dim)) || (rc = E.make_vec(&S.null_enc, S.enc_dim))) return rc;
     E.add_vec_slot(pre + "mask_token", S.mask_token, {1, 1, S.dec_dim});
-    E.add_vec_slot(pre + "null_token_enc", S.null_enc, {1, 1, S.enc_dim});
+    if (null_tokens) E.add_vec_slot(pre + "null_token_enc", S.null_enc, {1, 1, S.enc_dim});
     // positional tables with max_pad extra rows; the decoder's pad rows hold null_token_dec (_pad_pos_embed :154-165)
     if (sinusoid_f64) {
         if ((rc = E.make_sinusoid(&S.pos_enc_ext, S.n_tok, S.enc_dim, S.max_pad)) || (rc = E.make_sinusoid(&S.pos_dec_ext, S.n_tok, S.dec_dim, S.max_pad)))
@@ -166,7 +171,7 @@ int make_stream(Engine& E, StreamW& S, const std::string& pre, int embed_k, std:
             (rc = E.make_pos_embedding_f32(&S.pos_dec_ext, S.n_tok, S.dec_dim, S.max_pad)))
             return rc;
     }
-    E.add_vec_slot(pre + "null_token_dec", S.pos_dec_ext + (size_t)S.n_tok * S.dec_dim, {1, 1, S.dec_dim}, S.max_pad);
+    if (null_tokens) E.add_vec_slot(pre + "null_token_dec", S.pos_dec_ext + (size_t)S.n_tok * S.dec_dim, {1, 1, S.dec_dim}, S.max_pad);
     return 0;
 }
 
@@ -238,6 +243,9 @@ int ensure_workspace(cwm_conj_model* m, int B, int vmain, int vctx) {
         (rc = E.ws(&m->v_src, Mmax * Dmax)) || (rc = E.ws(&m->scores_t, Nmax * m->cfg.cross_heads * Mtok)) ||
         (rc = E.ws(&m->cross_partial, cross_partial_floats(Bc, m->cfg.cross_heads, Mtok, (int)Dmax / m->cfg.cross_heads))) || (rc = E.ws(&m->ybuf, 2 * Nmax * Dmax)) ||
         (rc = E.ws(&m->ysbuf, 2 * Mmax * Dmax)))
+        return rc;
+    if (m->var.ctx_dummy_token &&
+        ((rc = E.ws(&m->ctx_stage, (size_t)Bc * m->cfg.ctx_in_chans * (m->cfg.ctx_seq_len + m->cfg.ctx_tubelet))) || (rc = E.ws(&m->ctx_mask_stage, (size_t)Bc * m->ctx.n_tok))))
         return rc;
     m->ws_batch = Bc;
     m->ws_vmain = vm;
@@ -360,6 +368,7 @@ int embed_stream(cwm_conj_model* m, StreamW& S, int B, int vmax, int planes, hip
     g.epi = EPI_F32; g.C = S.x_enc; g.ldc = S.enc_dim;
     g.resid = S.pos_enc_ext; g.ldr = S.enc_dim; g.resid_rowmap = S.perm; g.rows_in = vmax; g.rows_out = vmax; g.map_stride = next;
     if (int rc = E.run_gemm(g, planes, s)) return rc;
+    if (S.max_pad == 0) return 0;  // unpadded variant: no pad slots
     return launch_fix_pad_rows(S.x_enc, S.perm, B, next, vmax, S.n_tok, S.enc_dim, S.null_enc, s);
 }
 
@@ -381,14 +390,37 @@ int to_decoder(cwm_conj_model* m, StreamW& S, int B, int vmax, int planes, hipSt
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-extern "C" int cwm_conj_create(const cwm_conj_config* cfg, cwm_conj_model** out) {
+extern "C" int cwm_conj_create(const cwm_conj_config* cfg, cwm_conj_model** out) { return cwm_conj_create_ex(cfg, nullptr, out); }
+
+extern "C" int cwm_conj_create_ex(const cwm_conj_config* cfg, const cwm_conj_variant* variant, cwm_conj_model** out) {
     CWM_REQUIRE(cfg && out, "cwm_conj_create: null argument");
     const cwm_conj_config& c = *cfg;
     const cwm_config& mc = c.main;
+    cwm_conj_variant v;
+    memset(&v, 0, sizeof(v));
+    v.padded = 1;
+    if (variant) {
+        CWM_REQUIRE(variant->struct_size >= offsetof(cwm_conj_variant, padded) + sizeof(int32_t) && variant->struct_size <= 4096,
+                    "cwm_conj_create_ex: variant->struct_size = %u is not a cwm_conj_variant", variant->struct_size);
+        memcpy(&v, variant, std::min<size_t>(variant->struct_size, sizeof(v)));
+    }
+    v.struct_size = sizeof(v);
+    CWM_REQUIRE(v.padded == 0 || v.padded == 1, "cwm_conj_create_ex: padded must be 0 or 1");
+    CWM_REQUIRE(v.ctx_dummy_token == 0 || v.ctx_dummy_token == 1, "cwm_conj_create_ex: ctx_dummy_token must be 0 or 1");
+    CWM_REQUIRE(v.main_input == CWM_CONJ_INPUT_FRAMES || v.main_input == CWM_CONJ_INPUT_FLOWBACK_RGB01, "cwm_conj_create_ex: unknown main_input %d", v.main_input);
+    // the two models the reference ships: the padded IMU-conditioned predictor and the unpadded flow -> IMU predictor (a padded
+    // model with the dummy token would put null_token_dec after the dummy's position row, which the reference never defines)
+    CWM_REQUIRE((v.padded && !v.ctx_dummy_token && v.main_input == CWM_CONJ_INPUT_FRAMES) ||
+                    (!v.padded && v.ctx_dummy_token && v.main_input == CWM_CONJ_INPUT_FLOWBACK_RGB01),
+                "cwm_conj_create_ex: supported variants are {padded, no dummy token, frames} and {unpadded, dummy token, flowback_rgb01}");
+    CWM_REQUIRE(v.padded || (c.main_max_pad == 0 && c.ctx_max_pad == 0), "cwm_conj_create_ex: an unpadded model needs main_max_pad = ctx_max_pad = 0");
+    CWM_REQUIRE(v.main_input != CWM_CONJ_INPUT_FLOWBACK_RGB01 || (mc.in_chans == 7 && mc.num_frames == 1),
+                "cwm_conj_create_ex: the flowback_rgb01 input needs main.in_chans = 7 and main.num_frames = 1");
+    const int ctx_tokens = c.ctx_tubelet > 0 ? c.ctx_seq_len / c.ctx_tubelet + v.ctx_dummy_token : 0;
     CWM_REQUIRE(mc.patch > 0 && mc.patch % 4 == 0 && mc.img_h % mc.patch == 0 && mc.img_w % mc.patch == 0 && mc.img_w % 4 == 0, "bad image/patch size");
     CWM_REQUIRE(mc.enc_dim == 64 * mc.enc_heads && mc.dec_dim == 64 * mc.dec_heads, "main stream needs head_dim 64");
     CWM_REQUIRE(mc.enc_dim % 128 == 0 && mc.dec_dim % 128 == 0 && mc.enc_dim <= 1024, "main stream widths must be multiples of 128");
-    CWM_REQUIRE(c.ctx_seq_len % c.ctx_tubelet == 0 && c.ctx_seq_len / c.ctx_tubelet + c.ctx_max_pad <= 64, "context stream: at most 64 tokens incl. padding");
+    CWM_REQUIRE(c.ctx_tubelet > 0 && c.ctx_seq_len % c.ctx_tubelet == 0 && ctx_tokens + c.ctx_max_pad <= 64, "context stream: at most 64 tokens incl. padding");
     CWM_REQUIRE(c.ctx_enc_dim % c.ctx_enc_heads == 0 && c.ctx_dec_dim % c.ctx_dec_heads == 0 && c.ctx_enc_dim / c.ctx_enc_heads <= 64 &&
                     c.ctx_dec_dim / c.ctx_dec_heads <= 64, "context stream head_dim must be <= 64");
     CWM_REQUIRE(c.ctx_enc_dim % 16 == 0 && c.ctx_dec_dim % 16 == 0 && c.ctx_enc_dim <= 1024, "context widths must be multiples of 16");
@@ -396,6 +428,7 @@ extern "C" int cwm_conj_create(const cwm_conj_config* cfg, cwm_conj_model** out)
     CWM_REQUIRE(c.n_enc_cross >= 0 && c.n_enc_cross <= 16 && c.n_dec_cross >= 0 && c.n_dec_cross <= 16, "too many conjoining blocks");
     cwm_conj_model* m = new cwm_conj_model();
     m->cfg = c;
+    m->var = v;
     Engine& E = m->eng;
     E.ln_eps = mc.ln_eps;
     CWM_HIP_CHECK(hipGetDevice(&E.device));
@@ -404,15 +437,19 @@ extern "C" int cwm_conj_create(const cwm_conj_config* cfg, cwm_conj_model** out)
     A.n_tok = (mc.img_h / mc.patch) * (mc.img_w / mc.patch) * mc.num_frames; A.max_pad = c.main_max_pad; A.out_dim = mc.in_chans * mc.patch * mc.patch;
     StreamW& S = m->ctx;
     S.enc_dim = c.ctx_enc_dim; S.dec_dim = c.ctx_dec_dim; S.enc_heads = c.ctx_enc_heads; S.dec_heads = c.ctx_dec_heads;
-    S.n_tok = c.ctx_seq_len / c.ctx_tubelet; S.max_pad = c.ctx_max_pad; S.out_dim = c.ctx_in_chans * c.ctx_tubelet;
+    S.n_tok = ctx_tokens; S.max_pad = c.ctx_max_pad; S.out_dim = c.ctx_in_chans * c.ctx_tubelet;
     int rc = 0;
     do {
         if ((rc = make_stream(E, A, "main_stream.", mc.in_chans * mc.patch * mc.patch, {mc.enc_dim, mc.in_chans, 1, mc.patch, mc.patch}, mc.enc_depth,
-                              mc.dec_depth, mc.mlp_ratio, true)))
+                              mc.dec_depth, mc.mlp_ratio, true, v.padded)))
             break;
         if ((rc = make_stream(E, S, "context_stream.", c.ctx_in_chans * c.ctx_tubelet, {c.ctx_enc_dim, c.ctx_in_chans, c.ctx_tubelet, 1, 1}, mc.enc_depth,
-                              mc.dec_depth, mc.mlp_ratio, false)))
+                              mc.dec_depth, mc.mlp_ratio, false, v.padded)))
             break;
+        if (v.ctx_dummy_token) {  // ImuEncoder.dummy_token, registered between context_stream.mask_token and the patch embed
+            if ((rc = E.make_vec(&m->dummy, c.ctx_in_chans * c.ctx_tubelet))) break;
+            E.add_vec_slot("context_stream.encoder.dummy_token", m->dummy, {1, c.ctx_in_chans, c.ctx_tubelet, 1, 1});
+        }
         // loaded from the checkpoints but never used on this path (vmae.py:368-369)
         E.add_ignored_slot("context_stream.pos_embed_encoder.weight", {c.ctx_dec_dim, 2 * c.ctx_dec_dim});
         E.add_ignored_slot("context_stream.pos_embed_encoder.bias", {c.ctx_dec_dim});
@@ -468,9 +505,10 @@ static int conj_forward_lane(ConjLane& L, const cwm_conj_forward_args* a, int b0
     const int planes = a->mode == CWM_MODE_PARITY ? 2 : 1;
     const float* x_in = a->x_dev + (int64_t)b0 * a->x_stride_b;
     const uint8_t* mask_in = a->mask_dev + (size_t)b0 * A.n_tok;
-    const float* ctx_in = a->ctx_dev + (size_t)b0 * c.ctx_in_chans * c.ctx_seq_len;
+    const int ctx_len = S.n_tok * c.ctx_tubelet;  // (+ the dummy's samples: a->ctx_dev is then the engine's staging buffer)
+    const float* ctx_in = a->ctx_dev + (size_t)b0 * c.ctx_in_chans * ctx_len;
     const uint8_t* ctx_mask_in = a->ctx_mask_dev + (size_t)b0 * S.n_tok;
-    float* y_tokens = a->y_tokens_dev + (size_t)b0 * n_out * A.out_dim;
+    float* y_tokens = a->y_tokens_dev ? a->y_tokens_dev + (size_t)b0 * n_out * A.out_dim : nullptr;
     int rc;
     bool side = E.tune.conj_ctx_stream != 0;  // (0 keeps the context stream's blocks on the lane's own stream)
     for (int k = 0; k < CWM_KCLASS_COUNT; ++k) side = side && !E.timers[k].enabled;
@@ -508,16 +546,29 @@ static int conj_forward_lane(ConjLane& L, const cwm_conj_forward_args* a, int b0
     if ((rc = launch_mask_to_perm(S.ext_mask, B, Mx, vc, S.perm, L.err, s))) return rc;
 
     // a2/a14: tokenise both streams (visible slots only)
-    PatchGatherParams pg;
-    memset(&pg, 0, sizeof(pg));
-    pg.x = x_in; pg.sb = a->x_stride_b; pg.sc = a->x_stride_c; pg.st = a->x_stride_t; pg.normalize = a->normalize;
-    pg.C = mc.in_chans; pg.H = mc.img_h; pg.W = mc.img_w; pg.P = mc.patch; pg.perm = A.perm; pg.Nt = A.n_tok; pg.perm_stride = Nx; pg.n_rows = vm; pg.B = B;
-    pg.out = A.tokens_in; pg.out_plane = (int64_t)B * vm * A.embed_kpad; pg.ld = A.embed_kpad;
-    if ((rc = E.run_patch_gather(pg, planes, s))) return rc;
+    if (m->var.main_input == CWM_CONJ_INPUT_FLOWBACK_RGB01) {
+        FlowRgbGatherParams fg;
+        memset(&fg, 0, sizeof(fg));
+        fg.fwd = a->flow_fwd_dev + b0 * a->flow_fwd_stride_b; fg.f_sb = a->flow_fwd_stride_b; fg.f_sc = a->flow_fwd_stride_c;
+        fg.bwd = a->flow_bwd_dev + b0 * a->flow_bwd_stride_b; fg.b_sb = a->flow_bwd_stride_b; fg.b_sc = a->flow_bwd_stride_c;
+        fg.x = x_in; fg.sb = a->x_stride_b; fg.sc = a->x_stride_c; fg.normalize = a->normalize;
+        fg.H = mc.img_h; fg.W = mc.img_w; fg.P = mc.patch; fg.perm = A.perm; fg.Nt = A.n_tok; fg.perm_stride = Nx; fg.n_rows = vm; fg.B = B;
+        fg.out = A.tokens_in; fg.out_plane = (int64_t)B * vm * A.embed_kpad; fg.ld = A.embed_kpad;
+        if ((rc = E.timed(CWM_KCLASS_PATCH_GATHER, (double)B * vm * 7 * mc.patch * mc.patch * (4.0 + 2.0 * planes), s,
+                          [&] { return launch_flow_rgb_gather(fg, planes, s); })))
+            return rc;
+    } else {
+        PatchGatherParams pg;
+        memset(&pg, 0, sizeof(pg));
+        pg.x = x_in; pg.sb = a->x_stride_b; pg.sc = a->x_stride_c; pg.st = a->x_stride_t; pg.normalize = a->normalize;
+        pg.C = mc.in_chans; pg.H = mc.img_h; pg.W = mc.img_w; pg.P = mc.patch; pg.perm = A.perm; pg.Nt = A.n_tok; pg.perm_stride = Nx; pg.n_rows = vm; pg.B = B;
+        pg.out = A.tokens_in; pg.out_plane = (int64_t)B * vm * A.embed_kpad; pg.ld = A.embed_kpad;
+        if ((rc = E.run_patch_gather(pg, planes, s))) return rc;
+    }
     if ((rc = embed_stream(m, A, B, vm, planes, s))) return rc;
     ImuGatherParams ig;
     memset(&ig, 0, sizeof(ig));
-    ig.imu = ctx_in; ig.B = B; ig.C = c.ctx_in_chans; ig.L = c.ctx_seq_len; ig.tubelet = c.ctx_tubelet; ig.perm = S.perm; ig.perm_stride = Mx;
+    ig.imu = ctx_in; ig.B = B; ig.C = c.ctx_in_chans; ig.L = ctx_len; ig.tubelet = c.ctx_tubelet; ig.perm = S.perm; ig.perm_stride = Mx;
     ig.n_rows = vc; ig.n_real = S.n_tok; ig.out = S.tokens_in; ig.out_plane = (int64_t)B * vc * S.embed_kpad; ig.ld = S.embed_kpad;
     if ((rc = launch_imu_gather(ig, planes, s))) return rc;
     if ((rc = embed_stream(m, S, B, vc, planes, s))) return rc;
@@ -564,7 +615,8 @@ static int conj_forward_lane(ConjLane& L, const cwm_conj_forward_args* a, int b0
     }
     if ((rc = main_follows_ctx())) return rc;  // the call's stream semantics cover the context stream's work too
 
-    // main output: head(norm(x[:, -n_out:])) * ~null_mask   (conjoined_decode :984-1002)
+    // main output: head(norm(x[:, -n_out:])) * ~null_mask   (conjoined_decode :984-1002); the flow -> IMU model may skip it
+    if (!y_tokens || n_out == 0) return CWM_OK;
     LayerNormParams ln;
     memset(&ln, 0, sizeof(ln));
     ln.x = A.x_dec; ln.ldx = A.dec_dim; ln.gamma = A.dec_norm_g; ln.beta = A.dec_norm_b; ln.eps = E.ln_eps; ln.D = A.dec_dim;
@@ -587,11 +639,17 @@ extern "C" int cwm_conj_forward(cwm_conj_model* m, const cwm_conj_forward_args* 
     memcpy(&a_copy, a_in, std::min<size_t>(a_in->struct_size, sizeof(a_copy)));
     const cwm_conj_forward_args* a = &a_copy;
     if (int rc = cwm_require_device(m->eng.device, "cwm_conj_forward")) return rc;
-    CWM_REQUIRE(a->x_dev && a->mask_dev && a->ctx_dev && a->ctx_mask_dev && a->y_tokens_dev, "cwm_conj_forward: x, mask, context, context mask and y are required");
+    const bool flowback = m->var.main_input == CWM_CONJ_INPUT_FLOWBACK_RGB01;
+    CWM_REQUIRE(a->x_dev && a->mask_dev && a->ctx_dev && a->ctx_mask_dev && (a->y_tokens_dev || flowback),
+                "cwm_conj_forward: x, mask, context, context mask and y are required");
+    CWM_REQUIRE(!flowback || (a->flow_fwd_dev && a->flow_bwd_dev), "cwm_conj_forward: the flowback_rgb01 input needs flow_fwd_dev and flow_bwd_dev");
+    CWM_REQUIRE(a->y_tokens_dev || a->y_ctx_tokens_dev, "cwm_conj_forward: no output requested");
     CWM_REQUIRE(a->mode == CWM_MODE_FAST || a->mode == CWM_MODE_PARITY, "cwm_conj_forward: bad mode %d", a->mode);
     const int B = a->batch, vm = a->n_vis_max, vc = a->n_vis_ctx_max;
     const int Nx = m->main.n_tok + m->main.max_pad;
-    CWM_REQUIRE(B > 0 && vm > 0 && vm < Nx && vc > 0 && vc <= m->ctx.n_tok, "cwm_conj_forward: bad batch / visible counts (%d, %d, %d)", B, vm, vc);
+    // (unpadded: a fully visible main stream is allowed when only the context output is asked for -- the decoder then has Nm = 0)
+    CWM_REQUIRE(B > 0 && vm > 0 && (vm < Nx || (!m->var.padded && !(a->y_tokens_dev && vm == Nx))) && vc > 0 && vc <= m->ctx.n_tok,
+                "cwm_conj_forward: bad batch / visible counts (%d, %d, %d)", B, vm, vc);
     {
         char miss[256];
         const int nmiss = m->eng.missing_weights(miss, sizeof(miss));
@@ -599,6 +657,14 @@ extern "C" int cwm_conj_forward(cwm_conj_model* m, const cwm_conj_forward_args* 
     }
     if (int rc = ensure_workspace(m, B, vm, vc)) return rc;
     hipStream_t s = (hipStream_t)a->stream;
+    if (m->var.ctx_dummy_token) {  // the lanes read the IMU and its mask with the dummy token appended, from the engine's staging buffers
+        const cwm_conj_config& c = m->cfg;
+        if (int rc = launch_imu_append_dummy(a->ctx_dev, a->ctx_mask_dev, m->dummy, B, c.ctx_in_chans, c.ctx_seq_len, c.ctx_tubelet, m->ctx.n_tok - 1, m->ctx_stage,
+                                             m->ctx_mask_stage, s))
+            return rc;
+        a_copy.ctx_dev = m->ctx_stage;
+        a_copy.ctx_mask_dev = m->ctx_mask_stage;
+    }
 
     // two lanes as in cwm_forward (model.hip): the halves share n_vis_max / n_vis_ctx_max, so the padded layout of every row is unchanged
     const bool two = m->lanes >= 2 && B >= 2 && (int64_t)(B / 2) * vm >= (m->eng.tune.min_lane_rows > 0 ? m->eng.tune.min_lane_rows : kMinLaneRowsConj);
@@ -632,6 +698,10 @@ extern "C" int cwm_conj_forward(cwm_conj_model* m, const cwm_conj_forward_args* 
         int herr[2] = {0, 0};
         CWM_HIP_CHECK(hipMemcpyAsync(herr, m->err, (two ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, s));
         CWM_HIP_CHECK(hipStreamSynchronize(s));
+        if ((herr[0] || herr[1]) && !m->var.padded) {
+            cwm_set_error("unpadded model: every row needs exactly n_vis_max visible main tokens and n_vis_ctx_max visible context tokens");
+            return CWM_ERR_INVALID;
+        }
         if (herr[0] || herr[1]) {
             cwm_set_error("n_vis_max / n_vis_ctx_max do not match the masks (a row has more visible tokens, or the padding budget is exceeded)");
             return CWM_ERR_MASK;

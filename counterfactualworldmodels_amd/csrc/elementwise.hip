@@ -225,6 +225,89 @@ int launch_patch_gather(const PatchGatherParams& p, int planes, hipStream_t stre
 }
 
 // ---------------------------------------------------------------------------------------------
+// Flow + RGB tubelet gather of the flow -> IMU predictor: `FlowBackRGB01` (preprocessor.py:208-277, 356) followed by the
+// Conv3d patch embed's im2col, for the visible tokens only.  The reference concatenates
+//     [fwd / (W/2, H/2), bwd / (W/2, H/2), imagenet_normalize(frame 1)]
+// into a [B,7,1,H,W] tensor and embeds it; here the 7 channels are read from their three sources directly.
+// One thread per (row, c, ph) as patch_gather_kernel: P contiguous pixels as float4 loads, P contiguous bf16 stores.
+// ---------------------------------------------------------------------------------------------
+template <int PLANES>
+__global__ __launch_bounds__(256) void flow_rgb_gather_kernel(const FlowRgbGatherParams p) {
+    constexpr int C = 7;
+    const int per_row = C * p.P;
+    const int64_t total = (int64_t)p.B * p.n_rows * per_row;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= total) return;
+    const int row = (int)(gid / per_row);
+    const int rem = (int)(gid - (int64_t)row * per_row);
+    const int c = rem / p.P, ph = rem - c * p.P;
+    const int b = row / p.n_rows, i = row - b * p.n_rows;
+    const int tau = p.perm[(size_t)b * p.perm_stride + i];
+    const bool pad_slot = tau >= p.Nt;
+    const int gw = p.W / p.P;
+    const int hy = pad_slot ? 0 : tau / gw, wx = pad_slot ? 0 : tau - (tau / gw) * gw;
+    const int64_t pix = (int64_t)(hy * p.P + ph) * p.W + wx * p.P;
+    const float* src;
+    float div = 1.f, shift = 0.f;
+    if (c < 4) {  // flow / (size / 2), size = (W, H) per (x, y) channel (_normalize_flow, preprocessor.py:254-266)
+        src = (c < 2 ? p.fwd + b * p.f_sb + (c & 1) * p.f_sc : p.bwd + b * p.b_sb + (c & 1) * p.b_sc) + pix;
+        div = 0.5f * (float)((c & 1) ? p.H : p.W);
+    } else {
+        const int rc = c - 4;
+        src = p.x + b * p.sb + rc * p.sc + pix;
+        if (p.normalize) {
+            const float mean = (rc == 0) ? 0.485f : (rc == 1) ? 0.456f : 0.406f;
+            const float stdv = (rc == 0) ? 0.229f : (rc == 1) ? 0.224f : 0.225f;
+            div = stdv;
+            shift = mean;
+        }
+    }
+    const int kbase = c * p.P * p.P + ph * p.P;
+    for (int pw = 0; pw < p.P; pw += 4) {
+        const float4 v = pad_slot ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(src + pw);
+        float f[4] = {v.x, v.y, v.z, v.w};
+        bf16x4 hv, lv;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float a = pad_slot ? 0.f : (f[e] - shift) / div;
+            bf16 hi, lo;
+            split_bf16(a, hi, lo);
+            hv[e] = hi;
+            lv[e] = lo;
+        }
+        bf16* dst = p.out + a_pos<PLANES>(row, p.ld, kbase + pw);
+        *reinterpret_cast<bf16x4*>(dst) = hv;
+        if constexpr (PLANES == 2) *reinterpret_cast<bf16x4*>(dst + kLoOffset) = lv;
+    }
+    if (rem == 0) {  // K padding, once per row
+        for (int k = C * p.P * p.P; k < p.ld; ++k) {
+            bf16* z = p.out + a_pos<PLANES>(row, p.ld, k);
+            *z = (bf16)0.f;
+            if constexpr (PLANES == 2) z[kLoOffset] = (bf16)0.f;
+        }
+    }
+}
+
+int launch_flow_rgb_gather(const FlowRgbGatherParams& p, int planes, hipStream_t stream) {
+    CWM_REQUIRE(p.P % 4 == 0 && p.W % 4 == 0 && p.H % p.P == 0 && p.W % p.P == 0, "flow_rgb_gather: patch size and width must be multiples of 4");
+    CWM_REQUIRE(p.ld >= 7 * p.P * p.P && p.ld % 4 == 0, "flow_rgb_gather: bad ld");
+    CWM_REQUIRE(p.perm_stride >= p.n_rows && p.Nt == (p.H / p.P) * (p.W / p.P), "flow_rgb_gather: bad token counts");
+    const float* ptrs[3] = {p.fwd, p.bwd, p.x};
+    const int64_t strides[6] = {p.f_sb, p.f_sc, p.b_sb, p.b_sc, p.sb, p.sc};
+    for (const float* q : ptrs) CWM_REQUIRE(q && ((uintptr_t)q & 15) == 0, "flow_rgb_gather: flow and frame pointers must be 16-byte aligned");
+    for (int64_t st : strides) CWM_REQUIRE(st % 4 == 0, "flow_rgb_gather: batch / channel strides must be multiples of 4 elements");
+    const int64_t total = (int64_t)p.B * p.n_rows * 7 * p.P;
+    const int blocks = (int)((total + 255) / 256);
+    if (blocks == 0) return 0;
+    if (planes == 1)
+        hipLaunchKernelGGL(flow_rgb_gather_kernel<1>, dim3(blocks), dim3(256), 0, stream, p);
+    else
+        hipLaunchKernelGGL(flow_rgb_gather_kernel<2>, dim3(blocks), dim3(256), 0, stream, p);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // The index prologue of a forward in ONE launch (round 5): mask -> permutation (visible tokens ascending, then masked ascending:
 // vmae.py:167, :555-557), its inverse `rank` (what the un-embed scatter reads, prediction.py:252-259), the per-row check of the visible
 // count (the reference's reshape failure at vmae.py:167) and the patch gather above.  Until round 4 these were four dependent launches

@@ -160,6 +160,24 @@ struct PatchGatherParams {
 };
 
 int launch_patch_gather(const PatchGatherParams& p, int planes, hipStream_t stream);
+
+// The 7-channel `FlowBackRGB01` tubelet gather of the flow -> IMU predictor (elementwise.hip flow_rgb_gather_kernel):
+// K order (c, ph, pw) over c = [fwd x, fwd y, bwd x, bwd y, R, G, B], flow scaled by 2/W (x) and 2/H (y), RGB as patch_gather.
+struct FlowRgbGatherParams {
+    const float* fwd;  // forward flow, element (b,c,y,x) at b*f_sb + c*f_sc + y*W + x
+    const float* bwd;  // backward flow, the same with b_sb / b_sc
+    int64_t f_sb, f_sc, b_sb, b_sc;
+    const float* x;    // frame 1, element (b,c,y,x) at b*sb + c*sc + y*W + x
+    int64_t sb, sc;
+    int normalize;     // imagenet-normalise the RGB channels in-kernel
+    int H, W, P;
+    const int* perm;   // [B][perm_stride]; entries >= Nt are pad slots (zero rows)
+    int Nt, n_rows, perm_stride, B;
+    bf16* out;         // [planes][B*n_rows][ld], zero-padded to ld
+    int64_t out_plane;
+    int ld;
+};
+int launch_flow_rgb_gather(const FlowRgbGatherParams& p, int planes, hipStream_t stream);
 // mask[B][L] (L = perm_stride or Nt) -> perm[B][L], rank[B][L] (inverse; may be nullptr), err_rows[b] = (visible count of row b != n_vis), and the
 // gather of the first n_rows visible tokens of every sample, in one launch (elementwise.hip index_gather_kernel); p.perm is not read
 int launch_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_vis, int* perm, int* rank, int* err_rows, int planes, hipStream_t stream);
@@ -221,6 +239,10 @@ struct ImuGatherParams {
     int ld;
 };
 int launch_imu_gather(const ImuGatherParams& p, int planes, hipStream_t stream);
+// ImuEncoder concat_dummy_token (conjoined_vmae.py:1124-1147): out[b] = [imu[b] (C x L) | dummy (C x T)] as [B][C][L + T], and
+// mask_out[b] = [mask[b] (n) | 0] as [B][n + 1] (the dummy token is always visible)
+int launch_imu_append_dummy(const float* imu, const uint8_t* mask, const float* dummy, int B, int C, int L, int T, int n, float* out, uint8_t* mask_out,
+                            hipStream_t stream);
 
 struct CrossAttnParams {
     const float* qk;      // [B*N][2D] main stream (fp32)                 -- VALU kernels (conj_kernels.hip)

@@ -211,23 +211,109 @@ class FlowGenerator(PredictorBasedGenerator):
         return flowstats.compute_flow_corrs(flow_samples, *args, **kwargs)
 
 
+class ImuGenerator(FlowGenerator):
+    """The part of the reference's `ImuGenerator` (segmentation.py:549-754) that the IMU-conditioned driver and the UI use, around
+    a conjoined predictor with an IMU context stream (the flow -> IMU head-motion predictor): an all-visible default mask
+    generator over the predictor's `mask_size`, `_preprocess`, `num_head_tokens`, `reshape_input` / `reshape_output` and
+    `_is_padded`.  Prediction from dataset dicts (`predict_imu`, `forward`) is not provided."""
+
+    def __init__(self, *args, head_mask_generator=None, head_mask_ratio=0, always_use_predicted=False, require_none_missing=False, **kwargs):
+        super().__init__(*args, **kwargs)
+        assert hasattr(self.predictor, "context_stream")
+        self.num_head_tokens = self.predictor.context_stream.encoder.num_tokens
+        if self.mask_generator is None:
+            from .masking import MaskingGenerator
+
+            self.mask_generator = MaskingGenerator(input_size=self.predictor.mask_size, mask_ratio=0, always_batch=True, create_on_cpu=False)
+        self.head_mask_generator = head_mask_generator
+        self.head_mask_ratio = head_mask_ratio
+        self._always_use_predicted = always_use_predicted
+        self._require_none_missing = require_none_missing
+        self.missing_imu = None
+
+    @property
+    def _is_padded(self):
+        return hasattr(self.predictor.context_stream, "padding_mask")
+
+    def reshape_input(self, x, tubelet_size=None):
+        """[B,C,(T pt)] -> [B,T,(pt C)] (segmentation.py:640-643)."""
+        pt = tubelet_size or self.predictor.context_stream.patch_size[0]
+        B, Cc, L = x.shape
+        return x.reshape(B, Cc, L // pt, pt).permute(0, 2, 3, 1).reshape(B, L // pt, pt * Cc)
+
+    def reshape_output(self, y, tubelet_size=None):
+        """[B,T,(pt C)] -> [B,C,(T pt)] (segmentation.py:645-649)."""
+        pt = tubelet_size or self.predictor.context_stream.patch_size[0]
+        B, T, F = y.shape
+        Cc = F // pt
+        return y.reshape(B, T, pt, Cc).permute(0, 3, 1, 2).reshape(B, Cc, T * pt)
+
+
 class ImuConditionedFlowGenerator(FlowGenerator):
-    """The IMU-conditioned variant (segmentation.py:760-963) for a conjoined RGB+IMU predictor.  The reference derives the
-    head motion from a second (flow -> IMU) model whose preprocessing needs a RAFT checkpoint; here the head motion is an input
-    (`head_motion` [B,6,400] in the predictor's layout), and it is forwarded exactly as the reference forwards it: as
-    `x_context`, with an all-visible (or, with mask_head_motion, all-masked) `mask_context`, tiled over every movie's prompts."""
+    """The IMU-conditioned variant (segmentation.py:760-963) for a conjoined RGB+IMU predictor.  The head motion is either an
+    input (`head_motion` [B,6,400] in the predictor's layout) or, with a `head_motion_predictor` (the flow -> IMU model
+    `imu400_8x8patch_2frames_1tube_flowbackrgb01`, which needs a flow model: the generator's `flow_model` is handed to it), estimated
+    from the video: `static_head_motion=True` (the default) -> `get_static_imu`, False -> `predict_imu_from_video` (:834-880).  It is
+    forwarded exactly as the reference forwards it: as `x_context`, with an all-visible (or, with mask_head_motion, all-masked)
+    `mask_context`, tiled over every movie's prompts."""
+
+    def __init__(self, *args, head_motion_predictor=None, head_motion_load_path=None, head_motion_generator=ImuGenerator,
+                 head_motion_kwargs=None, head_motion_mask_generator=None, **kwargs):
+        super().__init__(*args, **kwargs)
+        if head_motion_predictor is None:
+            return  # no `head_motion_generator` attribute: head_motion must be passed (interface.py's hasattr guard)
+        hk = dict(head_motion_kwargs) if head_motion_kwargs is not None else {"head_mask_ratio": 1}
+        hk.setdefault("imagenet_normalize_inputs", self.imagenet_normalize_inputs)
+        hk.setdefault("temporal_dim", self.predictor.t_dim)
+        hk["predictor_load_path"] = head_motion_load_path
+        if not isinstance(head_motion_predictor, torch.nn.Module):
+            head_motion_predictor = head_motion_predictor()
+        if getattr(head_motion_predictor, "flow_model", "absent") is None and self.flow_model is not None:
+            head_motion_predictor.set_flow_model(self.flow_model)
+        self.head_motion_generator = head_motion_generator(predictor=head_motion_predictor, mask_generator=head_motion_mask_generator,
+                                                           flow_model=self.flow_model, **hk)
+
+    def get_fake_head_motion(self, x):
+        """An all-zero, entirely masked IMU: what the flow -> IMU model is given to predict the head motion (segmentation.py:818-832)."""
+        B = x.size(0)
+        h = torch.zeros((B, self.head_tubelet_size * self.num_head_tokens, self.head_motion_channels), device=x.device, dtype=x.dtype)
+        h_mask = torch.ones((B, self.num_head_tokens), device=x.device, dtype=torch.bool)
+        if self.head_motion_generator.t_dim == 2:
+            h = h.transpose(1, 2)
+        return h, h_mask
+
+    def predict_imu_from_video(self, x, timestamps=None):
+        """[B,25,96]: the head motion the flow -> IMU model predicts from frames 0 and 1 of x [B,T,C,H,W] (segmentation.py:834-870)."""
+        if not hasattr(self, "head_motion_generator"):
+            raise RuntimeError("this generator has no head_motion_predictor: pass head_motion= to the counterfactual calls")
+        G = self.head_motion_generator
+        fake_imu, imu_mask = self.get_fake_head_motion(x)
+        mask = G.mask_generator(x).to(x.device)
+        return G.predictor(G._preprocess(x), mask=mask, timestamps=timestamps, x_context=fake_imu, mask_context=imu_mask, output_main=False,
+                           output_context=True)
+
+    def get_static_imu(self, x=None, timestamps=None):
+        """The head motion of a static movie: frame 0 repeated (segmentation.py:873-877)."""
+        x = self.x if x is None else x
+        return self.predict_imu_from_video(x[:, 0:1].expand(-1, x.size(1), -1, -1, -1).contiguous(), timestamps=timestamps)
+
+    def _head_model(self):
+        """The model that defines the head-motion layout: the head-motion predictor when there is one (segmentation.py:799-809), else the
+        conditioned predictor."""
+        G = getattr(self, "head_motion_generator", None)
+        return G.predictor if G is not None else self.predictor
 
     @property
     def num_head_tokens(self):
-        return self.predictor.context_stream.encoder.num_tokens
+        return self._head_model().context_stream.encoder.num_tokens
 
     @property
     def head_tubelet_size(self):
-        return self.predictor.context_stream.patch_size[0]
+        return self._head_model().context_stream.patch_size[0]
 
     @property
     def head_motion_channels(self):
-        return getattr(self.predictor.get_context_input, "num_channels", 6)
+        return getattr(self._head_model().get_context_input, "num_channels", 6)
 
     def get_zeros_imu(self, x=None):
         x = self.x if x is None else x
@@ -238,11 +324,19 @@ class ImuConditionedFlowGenerator(FlowGenerator):
         kw = dict(kwargs)
         head_motion = kw.pop("head_motion", None)
         mask_head_motion = kw.pop("mask_head_motion", False)
-        kw.pop("static_head_motion", None)
+        static_head_motion = kw.pop("static_head_motion", True)
         kw.pop("timestamps", None)
+        if head_motion is None and hasattr(self, "head_motion_generator"):  # predict_imu_video_and_flow, segmentation.py:884-910, 931-963
+            movie, _ = self._two_frame_movie(x, True)
+            self.set_input(movie)
+            if self.mask_generator is not None:
+                self.generate_mask(movie)  # unused, as in the reference: drawn for its place in the global RNG sequence (:895-898)
+            h = self.get_static_imu(movie) if static_head_motion else self.predict_imu_from_video(movie)
+            head_motion = self.head_motion_generator.reshape_output(h)
         if head_motion is None:
-            raise RuntimeError("pass head_motion [B,%d,%d]: estimating it from the video needs the reference's flow->IMU model (RAFT), "
-                               "which is outside this package" % (self.head_motion_channels, self.head_tubelet_size * self.num_head_tokens))
+            raise RuntimeError("pass head_motion [B,%d,%d], or build the generator with head_motion_predictor= (the flow->IMU model "
+                               "conjoined_vmae.imu400_8x8patch_2frames_1tube_flowbackrgb01) to estimate it from the video"
+                               % (self.head_motion_channels, self.head_tubelet_size * self.num_head_tokens))
         h_mask = torch.zeros(head_motion.shape[0], self.num_head_tokens, dtype=torch.bool, device=head_motion.device)
         if mask_head_motion:
             h_mask = ~h_mask

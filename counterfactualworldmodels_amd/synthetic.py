@@ -7,6 +7,7 @@ bit-identical full-size tensors without shipping them.
 """
 from __future__ import annotations
 
+import functools
 import zlib
 from typing import Dict, Optional, Tuple
 
@@ -110,3 +111,33 @@ def synthetic_prompts(num: int, cfg: VmaeConfig, seed: int = 0, max_shift: int =
                 break
         out[s, 2], out[s, 3] = dy, dx
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def _synthetic_flow_module():
+    import torch
+
+    class SyntheticFlow(torch.nn.Module):
+        """Deterministic stand-in for RAFT with the multi-frame call contract of the reference
+        (`raft/raft_model.py:276-300`): `flow_model(x[B,T,3,H,W] in [0,1], iters=..., backward=False)` -> [B,T-1,2,H,W] pixels.
+
+        Every output depends on the frame content (a static movie gives a different flow from a moving one), x differs from y
+        and forward differs from backward (not by a sign), and the magnitudes are several pixels, so the 2/W, 2/H flow scaling
+        of the flow -> IMU input shows in the results.  It has no parameters."""
+
+        def forward(self, x, iters=None, backward=False, **kwargs):
+            a, b = x[:, :-1].float(), x[:, 1:].float()
+            d = b - a
+            if not backward:
+                fx = 12.0 * d[:, :, 0] + 4.0 * a[:, :, 1] - 1.5
+                fy = -9.0 * d[:, :, 2] + 6.0 * a[:, :, 0] * b[:, :, 1] - 2.0
+            else:
+                fx = -7.0 * d[:, :, 1] + 5.0 * b[:, :, 2] * b[:, :, 2] - 2.5
+                fy = 10.0 * d[:, :, 0] - 3.0 * b[:, :, 0] + 1.0
+            return torch.stack([fx, fy], 2)
+
+    return SyntheticFlow
+
+
+def SyntheticFlow():  # noqa: N802 -- a class factory, so that importing this module needs no torch
+    return _synthetic_flow_module()()

@@ -147,6 +147,31 @@ CWM_API void cwm_conj_destroy(cwm_conj_model* m);
 CWM_API int cwm_conj_load_weight(cwm_conj_model* m, const char* key, const float* data, int on_device, const int64_t* shape, int ndim);
 CWM_API int cwm_conj_missing_weights(cwm_conj_model* m, char* buf, int buflen);
 
+/* ---- conjoined variants (0.8) ---------------------------------------------------------------------
+ * The unpadded `ConjoinedPretrainVisionTransformer` (conjoined_vmae.py:212-887) of the flow -> IMU head-motion predictor
+ * `imu400_8x8patch_2frames_1tube_flowbackrgb01` (:1218-1228) runs on the same engine.  cwm_conj_config has no size field, so
+ * the variant is a struct of its own; cwm_conj_create(cfg) is cwm_conj_create_ex(cfg, NULL, out) with the padded defaults.
+ *   padded = 0: no null-token padding (main_max_pad and ctx_max_pad must be 0), no `null_token_*` weights, and every row of
+ *     a call has the same visible count in each stream (the reference's `x[~mask].reshape(B, -1, C)`, vmae.py:155-167);
+ *     other masks are CWM_ERR_INVALID.
+ *   ctx_dummy_token = 1: the ImuEncoder's `concat_dummy_token` (conjoined_vmae.py:1013-1147): the learned weight
+ *     `context_stream.encoder.dummy_token` [1, ctx_in_chans, ctx_tubelet, 1, 1] is appended to the IMU as sample block
+ *     ctx_seq_len / ctx_tubelet, always visible (`_concat_excess_tokens` :595-609), with that position row of both tables.
+ *   main_input = CWM_CONJ_INPUT_FLOWBACK_RGB01: the main stream's 7 channels are `FlowBackRGB01` (preprocessor.py:208-277, 356):
+ *     [forward flow / (W/2, H/2), backward flow / (W/2, H/2), frame 1], gathered in-kernel from the flow_* arguments of
+ *     cwm_conj_forward_args and x_dev (config: main.in_chans = 7, main.num_frames = 1).
+ * Two variants are accepted: {padded = 1, ctx_dummy_token = 0, CWM_CONJ_INPUT_FRAMES} (the default) and {padded = 0,
+ * ctx_dummy_token = 1, CWM_CONJ_INPUT_FLOWBACK_RGB01}; any other combination is CWM_ERR_INVALID. */
+#define CWM_CONJ_INPUT_FRAMES 0
+#define CWM_CONJ_INPUT_FLOWBACK_RGB01 1
+typedef struct cwm_conj_variant {
+    uint32_t struct_size;        /* sizeof(cwm_conj_variant) as the caller knows it; fields beyond it take their defaults */
+    int32_t padded;              /* 1 (ConjoinedPaddedVisionTransformer) or 0 (ConjoinedPretrainVisionTransformer) */
+    int32_t ctx_dummy_token;     /* 0 or 1 */
+    int32_t main_input;          /* CWM_CONJ_INPUT_* */
+} cwm_conj_variant;
+CWM_API int cwm_conj_create_ex(const cwm_conj_config* cfg, const cwm_conj_variant* variant, cwm_conj_model** out);
+
 typedef struct cwm_conj_forward_args {
     uint32_t struct_size;        /* sizeof(cwm_conj_forward_args) as the caller knows it (see cwm_forward_args): y_ctx_tokens_dev, added in 0.5, is read only
                                   * when the size covers it */
@@ -167,6 +192,14 @@ typedef struct cwm_conj_forward_args {
      * rows at masked pad slots are 0 -- `forward(..., output_context=True)` returns it, alone or in a tuple with y_tokens
      * (conjoined_vmae.py:852-887, 990-1011) */
     float* y_ctx_tokens_dev;
+    /* CWM_CONJ_INPUT_FLOWBACK_RGB01 only (added in 0.8, read only when struct_size covers them): the forward and backward flow of
+     * frames 0 -> 1, each fp32 [B, 2, H, W] in pixels (x, y), element (b, c, y, x) at b*stride_b + c*stride_c + y*W + x, 16-byte
+     * aligned with strides that are multiples of 4.  x_dev then points at frame 1 ([B, 3, H, W] with x_stride_b / x_stride_c;
+     * normalize as above).  For this input y_tokens_dev may be NULL: the main head is skipped, the main decoder still runs. */
+    const float* flow_fwd_dev;
+    int64_t flow_fwd_stride_b, flow_fwd_stride_c;
+    const float* flow_bwd_dev;
+    int64_t flow_bwd_stride_b, flow_bwd_stride_c;
 } cwm_conj_forward_args;
 
 /* replaces: `self.predictor(self._preprocess(x), mask, x_context=..., mask_context=...)` (prediction.py:419-422) */
