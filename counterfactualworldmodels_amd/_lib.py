@@ -136,6 +136,38 @@ class CwmConjVariant(C.Structure):
     ]
 
 
+class CwmRaftForwardArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("image1_dev", C.c_void_p),
+        ("image1_stride_b", C.c_int64),
+        ("image1_stride_t", C.c_int64),
+        ("image1_stride_c", C.c_int64),
+        ("image2_dev", C.c_void_p),
+        ("image2_stride_b", C.c_int64),
+        ("image2_stride_t", C.c_int64),
+        ("image2_stride_c", C.c_int64),
+        ("batch", C.c_int32),
+        ("pairs", C.c_int32),
+        ("height", C.c_int32),
+        ("width", C.c_int32),
+        ("input_scale", C.c_float),
+        ("iters", C.c_int32),
+        ("flow_dev", C.c_void_p),
+        ("flow_stride_b", C.c_int64),
+        ("flow_stride_t", C.c_int64),
+        ("flow_stride_c", C.c_int64),
+        ("flow_low_dev", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
+def new_raft_forward_args() -> CwmRaftForwardArgs:
+    a = CwmRaftForwardArgs()
+    a.struct_size = C.sizeof(CwmRaftForwardArgs)
+    return a
+
+
 def new_forward_args() -> CwmForwardArgs:
     a = CwmForwardArgs()
     a.struct_size = C.sizeof(CwmForwardArgs)
@@ -210,6 +242,13 @@ SIGNATURES = {
     "cwm_allgather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cwm_allgatherv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
     "cwm_allreduce_sum_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cwm_raft_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "cwm_raft_destroy": (None, [C.c_void_p]),
+    "cwm_raft_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "cwm_raft_missing_weights": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    "cwm_raft_forward": (C.c_int, [C.c_void_p, C.POINTER(CwmRaftForwardArgs)]),
+    "cwm_raft_corr_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cwm_raft_convex_upsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_last_error": (C.c_char_p, []),
     "cwm_version": (C.c_char_p, []),
     "cwm_source_hash": (C.c_char_p, []),

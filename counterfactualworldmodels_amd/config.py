@@ -247,3 +247,75 @@ def conj_state_dict_schema(cfg: ConjConfig) -> "OrderedDict[str, tuple]":
     for i in cfg.dec_cross:
         _cross_schema(f"decoder_conjoining_blocks.{i}-{i}.", m.dec_dim, cfg.ctx_dec_dim, cfg.cross_mlp_ratio, s)
     return s
+
+
+# ---- RAFT-large optical flow (cwm/models/raft/raft_model.py:103-161, extractor.py:6-57, 118-192, update.py:6-137) ----------------------
+RAFT_HIDDEN = 128  # hidden_dim = context_dim of RAFT-large
+RAFT_CORR_LEVELS = 4
+RAFT_CORR_RADIUS = 4
+RAFT_BN_EPS = 1e-5
+RAFT_IN_EPS = 1e-5
+
+
+def _raft_encoder_schema(pre: str, norm: str, out_dim: int, out: "OrderedDict[str, tuple]") -> None:
+    def conv(name, n, c, k):
+        out[pre + name + ".weight"] = (n, c, k, k)
+        out[pre + name + ".bias"] = (n,)
+
+    def bn(name, c):
+        if norm == "batch":
+            for p in ("weight", "bias", "running_mean", "running_var"):
+                out[pre + name + "." + p] = (c,)
+            out[pre + name + ".num_batches_tracked"] = ()
+
+    bn("norm1", 64)  # BasicEncoder registers norm1 before conv1
+    conv("conv1", 64, 3, 7)
+    cin = 64
+    for li, dim in ((1, 64), (2, 96), (3, 128)):
+        for bi in range(2):
+            b = "layer%d.%d." % (li, bi)
+            stride = 2 if (bi == 0 and li > 1) else 1
+            conv(b + "conv1", dim, cin, 3)
+            conv(b + "conv2", dim, dim, 3)
+            bn(b + "norm1", dim)
+            bn(b + "norm2", dim)
+            if stride != 1:
+                bn(b + "norm3", dim)  # the same module as downsample.1: the state dict lists it twice
+                conv(b + "downsample.0", dim, cin, 1)
+                bn(b + "downsample.1", dim)
+            cin = dim
+    conv("conv2", out_dim, 128, 1)
+
+
+def raft_state_dict_schema() -> "OrderedDict[str, tuple]":
+    """State-dict names -> shapes of RAFT-large in the reference's order (179 tensors, `num_batches_tracked` included)."""
+    s: "OrderedDict[str, tuple]" = OrderedDict()
+    _raft_encoder_schema("fnet.", "instance", 256, s)
+    _raft_encoder_schema("cnet.", "batch", 2 * RAFT_HIDDEN, s)
+    cor_planes = RAFT_CORR_LEVELS * (2 * RAFT_CORR_RADIUS + 1) ** 2
+    for name, n, c, kh, kw in (("encoder.convc1", 256, cor_planes, 1, 1), ("encoder.convc2", 192, 256, 3, 3), ("encoder.convf1", 128, 2, 7, 7),
+                               ("encoder.convf2", 64, 128, 3, 3), ("encoder.conv", 126, 256, 3, 3),
+                               ("gru.convz1", 128, 384, 1, 5), ("gru.convr1", 128, 384, 1, 5), ("gru.convq1", 128, 384, 1, 5),
+                               ("gru.convz2", 128, 384, 5, 1), ("gru.convr2", 128, 384, 5, 1), ("gru.convq2", 128, 384, 5, 1),
+                               ("flow_head.conv1", 256, 128, 3, 3), ("flow_head.conv2", 2, 256, 3, 3),
+                               ("mask.0", 256, 128, 3, 3), ("mask.2", 576, 256, 1, 1)):
+        s["update_block." + name + ".weight"] = (n, c, kh, kw)
+        s["update_block." + name + ".bias"] = (n,)
+    return s
+
+
+def raft_algorithmic_flops(height: int, width: int, iters: int) -> float:
+    """FLOPs one frame pair costs on this package's path (2*M*N*K per convolution and for the correlation; the mask head and the
+    convex upsampling run once, after the last iteration)."""
+    def conv(hw, n, c, k):
+        return 2.0 * hw * n * c * k
+
+    h2, h4, h8 = (height // 2) * (width // 2), (height // 4) * (width // 4), (height // 8) * (width // 8)
+    enc = conv(h2, 64, 3, 49) + 4 * conv(h2, 64, 64, 9)
+    enc += conv(h4, 96, 64, 9) + conv(h4, 96, 96, 9) * 3 + conv(h4, 96, 64, 1)
+    enc += conv(h8, 128, 96, 9) + conv(h8, 128, 128, 9) * 3 + conv(h8, 128, 96, 1) + conv(h8, 256, 128, 1)
+    corr = 2.0 * h8 * h8 * 256
+    upd = (conv(h8, 256, 324, 1) + conv(h8, 192, 256, 9) + conv(h8, 128, 2, 49) + conv(h8, 64, 128, 9) + conv(h8, 126, 256, 9)
+           + 6 * conv(h8, 128, 384, 5) + conv(h8, 256, 128, 9) + conv(h8, 2, 256, 9))
+    mask = conv(h8, 256, 128, 9) + conv(h8, 576, 256, 1)
+    return 3 * enc + corr + iters * upd + mask

@@ -272,4 +272,70 @@ int launch_perm_to_rank(const int* perm, int* rank, int B, int Nt, hipStream_t s
 
 int launch_split_bf16(const float* x, int64_t n, bf16* hi, bf16* lo, hipStream_t stream);
 
+// ---- RAFT-large optical flow (raft_kernels.hip) ------------------------------------------------------
+// One channel segment of a convolution input: fp32 NHWC, pixel `pix` at p + pix * ld.  The value a consumer reads is
+// relu?((v - mean) * rstd) * sigmoid(gate)?, or, with `coords`, the flow coords[pix] - (x, y) of a 2-channel coordinate field.
+struct ConvSrc {
+    const float* p;
+    int ld, C;
+    const float* stats;  // [img][C] (mean, rstd) pairs (instance norm) or nullptr
+    int relu;
+    const float* gate;   // multiply by sigmoid(gate[pix * gate_ld + c]) (the GRU's r * h) or nullptr
+    int gate_ld;
+    const float* coords; // [pix][2] coordinates: value = coords - (x, y)
+};
+// The input frames of the encoders: image i of a launch is pair (img0 + i) % P of frame (img0 + i) / P (0: image1, 1: image2); pair pr is
+// (g, t) = (pr / ppg, pr % ppg); element (c, y, x) at base[which][g * sb + t * st + c * sc + y * W + x], scaled to 2 * (v * scale / 255) - 1
+struct ImageSrc {
+    const float* base[2];
+    int64_t sb[2], st[2], sc[2];
+    int P, ppg;
+    float scale;
+};
+struct Im2colParams {
+    ConvSrc src[2];  // the input channels are src[0] then src[1] (nsrc = 2: the GRU's [h | x])
+    int nsrc;
+    ImageSrc image;  // image.base[0] != nullptr: the frames instead of src (conv1 of the encoders; src[0].C = 3)
+    int img0;
+    int n_img, H, W, OH, OW, kh, kw, stride, pad_h, pad_w;
+    int c_lo, c_hi;  // c_hi > c_lo: rewrite only input channels [c_lo, c_hi) of every tap (the rest of A, K padding included, is kept)
+    bf16* A;         // parity layout [n_img * OH * OW][2 * Kpad], K order (ky, kx, c), zero padded
+    int Kpad;
+};
+struct CorrLookupParams {
+    const float* pyr[4];  // level l: [M][h[l]][w[l]]
+    int h[4], w[4], levels;
+    const float* coords;  // [M][2]
+    int64_t M;
+    bf16* A;              // [M][2 * Kpad] parity layout, feature l*81 + a*9 + b, zero padded
+    int Kpad;
+    float* out;           // instead of A (out != nullptr): fp32 [M][out_ld], features [0, levels*81) (cwm_raft_corr_lookup)
+    int out_ld;
+};
+struct ConvexUpParams {
+    const float* coords;  // [P][h8][w8][2] (flow = coords - (x, y)), or nullptr: flow [P][2][h8][w8]
+    const float* flow;
+    const float* mask;    // [P][h8][w8][mask_ld]: channel k*64 + i*8 + j, times mask_scale
+    int mask_ld;
+    float mask_scale;
+    int P, ppg, h8, w8;
+    float* out;           // pair pr = (g, t): out + g * out_sb + t * out_st + c * out_sc + Y * 8w8 + X
+    int64_t out_sb, out_st, out_sc;
+};
+int launch_im2col(const Im2colParams& p, hipStream_t s);
+// stats [n_img][C] (mean, rstd) pairs; work: 2 * n_img * kInstNormMaxChunks * C doubles
+constexpr int kInstNormMaxChunks = 16;
+int launch_instnorm_stats(const float* x, int n_img, int HW, int C, float eps, float* stats, double* work, hipStream_t s);
+int launch_residual_join(const ConvSrc& X, const ConvSrc& Y, int n_img, int HW, float* out, hipStream_t s);
+int launch_cnet_split(const float* cn, int64_t M, float* h, float* x, hipStream_t s);
+int launch_coords_init(float* coords, int64_t M, int h8, int w8, hipStream_t s);
+int launch_corr(const float* f1, const float* f2, int P, int N, int D, float* corr, hipStream_t s);
+int launch_corr_pool(const float* in, int64_t maps, int h, int w, float* out, hipStream_t s);
+int launch_corr_lookup(const CorrLookupParams& p, hipStream_t s);
+int launch_motion_finish(float* x, const float* coords, int64_t M, int h8, int w8, hipStream_t s);
+int launch_gru_update(float* h, const float* zr, const float* q, int64_t M, hipStream_t s);
+int launch_flow_update(float* coords, const float* delta, int ld, int64_t M, hipStream_t s);
+int launch_convex_upsample(const ConvexUpParams& p, hipStream_t s);
+int launch_flow_low(const float* coords, int P, int h8, int w8, float* out, hipStream_t s);
+
 }  // namespace cwm

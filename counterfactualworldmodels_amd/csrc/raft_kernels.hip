@@ -1,0 +1,431 @@
+// RAFT-large optical flow (cwm/models/raft): the kernels around the convolution GEMMs.  Activations are fp32 NHWC; a convolution is an
+// explicit im2col into the GEMM's split-bf16 A operand (common.h a_pos, K order (ky, kx, c), zero padded to Kpad) and one launch_gemm with
+// the EPI_F32 epilogue.  Activation functions, normalisations and the GRU's r*h are applied where an operand is read, never as a pass of
+// their own, except the residual join of the encoders and the GRU state update.
+#include <math.h>
+
+#include <algorithm>
+
+#include "kernels.h"
+
+namespace cwm {
+
+namespace {
+
+__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
+
+__device__ __forceinline__ void store_split(bf16* A, int64_t row, int Kpad, int k, float v) {
+    bf16 h, l;
+    split_bf16(v, h, l);
+    bf16* d = A + a_pos<2>(row, Kpad, k);
+    d[0] = h;
+    d[kLoOffset] = l;
+}
+
+// value of channel c of one source at pixel `pix` (of image `img`, spatial position (y, x))
+__device__ __forceinline__ float src_value(const ConvSrc& s, int64_t pix, int img, int y, int x, int c) {
+    if (s.coords) return s.coords[pix * 2 + c] - (float)(c ? y : x);  // flow = coords1 - coords0
+    float v = s.p[pix * s.ld + c];
+    if (s.stats) {
+        const float2 st = reinterpret_cast<const float2*>(s.stats)[(int64_t)img * s.C + c];
+        v = (v - st.x) * st.y;
+    }
+    if (s.relu) v = fmaxf(v, 0.f);
+    if (s.gate) v = v * sigmoidf_(s.gate[pix * s.gate_ld + c]);
+    return v;
+}
+
+// One thread per 8 consecutive k of one row: they lie in one [32 hi | 32 lo] block of the parity layout, so the thread ends with one
+// 16-byte store per plane.  (K order (ky, kx, c): the 8 channels of a thread come from at most two taps.)
+__global__ void im2col_kernel(const Im2colParams p) {
+    const int Ctot = p.src[0].C + (p.nsrc > 1 ? p.src[1].C : 0);
+    const int K = p.kh * p.kw * Ctot;
+    const int kg = p.Kpad >> 3, ohw = p.OH * p.OW;
+    const int total = p.n_img * ohw * kg;
+    const bool partial = p.c_hi > p.c_lo;
+    for (int gi = blockIdx.x * blockDim.x + threadIdx.x; gi < total; gi += gridDim.x * blockDim.x) {
+        const int m = gi / kg, kb = (gi - m * kg) << 3;
+        if (partial && kb >= K) continue;
+        int tap = kb / Ctot, c = kb - tap * Ctot;
+        if (partial && (c < p.c_lo || c >= p.c_hi)) continue;  // channel ranges are multiples of 8: a group is wholly in or out
+        const int img = m / ohw, r = m - img * ohw;
+        const int oy = r / p.OW, ox = r - oy * p.OW;
+        bf16x8 hv, lv;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float v = 0.f;
+            if (kb + j < K) {
+                const int ky = tap / p.kw, kx = tap - ky * p.kw;
+                const int y = oy * p.stride - p.pad_h + ky, x = ox * p.stride - p.pad_w + kx;
+                if (y >= 0 && y < p.H && x >= 0 && x < p.W) {
+                    if (p.image.base[0]) {  // the input frames: NCHW (any batch / time / channel strides), scaled 2 * (x * scale / 255) - 1
+                        const ImageSrc& I = p.image;
+                        const int ii = p.img0 + img;
+                        const int which = ii / I.P, pr = ii - which * I.P;
+                        const int g = pr / I.ppg, t = pr - g * I.ppg;
+                        const float xv = I.base[which][g * I.sb[which] + t * I.st[which] + c * I.sc[which] + (int64_t)y * p.W + x];
+                        float sv = xv * I.scale;
+                        sv = sv / 255.f;
+                        v = 2.f * sv - 1.f;
+                    } else {
+                        const int64_t pix = ((int64_t)img * p.H + y) * p.W + x;
+                        v = c < p.src[0].C ? src_value(p.src[0], pix, img, y, x, c) : src_value(p.src[1], pix, img, y, x, c - p.src[0].C);
+                    }
+                }
+            }
+            bf16 h, l;
+            split_bf16(v, h, l);
+            hv[j] = h;
+            lv[j] = l;
+            if (++c == Ctot) {
+                c = 0;
+                ++tap;
+            }
+        }
+        bf16* d = p.A + a_pos<2>(m, p.Kpad, kb);
+        *reinterpret_cast<bf16x8*>(d) = hv;
+        *reinterpret_cast<bf16x8*>(d + kLoOffset) = lv;
+    }
+}
+
+// InstanceNorm2d statistics (no affine, biased variance) per image and channel over H*W: partial sums of x and x^2 in double over
+// pixel chunks (grid: image x 64-channel group x chunk), then one thread per (image, channel) adds the chunks in order (deterministic)
+__global__ void __launch_bounds__(512) instnorm_partial_kernel(const float* x, int HW, int C, int chunk, double2* part) {
+    __shared__ double2 red[8][64];
+    const int img = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6, ch = blockIdx.z;
+    const float* base = x + (int64_t)img * HW * C;
+    const int p0 = ch * chunk, p1 = min(HW, p0 + chunk);
+    double s = 0.0, q = 0.0;
+    if (c < C)
+        for (int pp = p0 + g; pp < p1; pp += 8) {
+            const double v = (double)base[(int64_t)pp * C + c];
+            s += v;
+            q += v * v;
+        }
+    red[g][threadIdx.x & 63] = make_double2(s, q);
+    __syncthreads();
+    if (g == 0 && c < C) {
+        double2 t = red[0][threadIdx.x];
+        for (int j = 1; j < 8; ++j) {
+            t.x += red[j][threadIdx.x].x;
+            t.y += red[j][threadIdx.x].y;
+        }
+        part[((int64_t)img * gridDim.z + ch) * C + c] = t;
+    }
+}
+
+__global__ void instnorm_finish_kernel(const double2* part, int n_img, int HW, int C, int nchunk, float eps, float2* stats) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_img * C) return;
+    const int img = i / C, c = i - img * C;
+    double s = 0.0, q = 0.0;
+    for (int ch = 0; ch < nchunk; ++ch) {
+        const double2 t = part[((int64_t)img * nchunk + ch) * C + c];
+        s += t.x;
+        q += t.y;
+    }
+    const double mean = s / HW, var = fmax(q / HW - mean * mean, 0.0);
+    stats[i] = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
+}
+
+// ResidualBlock.forward's last line: out = relu(X + relu(norm2(y)))  (X: the block input, or norm3(downsample(x)))
+__global__ void residual_join_kernel(const ConvSrc X, const ConvSrc Y, int64_t total, int HW, float* out) {
+    const int C = Y.C;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t pix = i / C;
+        const int c = (int)(i - pix * C), img = (int)(pix / HW);
+        const float a = src_value(X, pix, img, 0, 0, c), b = src_value(Y, pix, img, 0, 0, c);
+        out[i] = fmaxf(a + b, 0.f);
+    }
+}
+
+// cnet output [M][256] -> h = tanh(net) [M][128], x[:, 0:128] = relu(inp)  (x row stride 256)
+__global__ void cnet_split_kernel(const float* cn, int64_t M, float* h, float* x) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M * 128; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t m = i >> 7;
+        const int c = (int)(i & 127);
+        h[i] = tanhf(cn[m * 256 + c]);
+        x[m * 256 + c] = fmaxf(cn[m * 256 + 128 + c], 0.f);
+    }
+}
+
+__global__ void coords_init_kernel(float* coords, int64_t M, int h8, int w8) {
+    for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (int64_t)gridDim.x * blockDim.x) {
+        const int r = (int)(m % ((int64_t)h8 * w8));
+        coords[2 * m] = (float)(r % w8);
+        coords[2 * m + 1] = (float)(r / w8);
+    }
+}
+
+// corr[p][i][j] = <f1[p][i], f2[p][j]> / sqrt(256), fp32 FMA (CorrBlock.corr); 64 x 64 tiles, 4 x 4 per thread
+__global__ void __launch_bounds__(256) corr_kernel(const float* f1, const float* f2, int N, int D, float scale, float* corr) {
+    __shared__ float As[16][64 + 4];
+    __shared__ float Bs[16][64 + 4];
+    const int p = blockIdx.z, i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
+    const float* a = f1 + (int64_t)p * N * D;
+    const float* b = f2 + (int64_t)p * N * D;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int lr = threadIdx.x >> 2, lk = (threadIdx.x & 3) * 4;
+    float acc[4][4] = {};
+    for (int k0 = 0; k0 < D; k0 += 16) {
+        const int ia = min(i0 + lr, N - 1), jb = min(j0 + lr, N - 1);
+        const float4 va = *reinterpret_cast<const float4*>(a + (int64_t)ia * D + k0 + lk);
+        const float4 vb = *reinterpret_cast<const float4*>(b + (int64_t)jb * D + k0 + lk);
+        As[lk + 0][lr] = va.x; As[lk + 1][lr] = va.y; As[lk + 2][lr] = va.z; As[lk + 3][lr] = va.w;
+        Bs[lk + 0][lr] = vb.x; Bs[lk + 1][lr] = vb.y; Bs[lk + 2][lr] = vb.z; Bs[lk + 3][lr] = vb.w;
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+            float av[4], bv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                av[u] = As[kk][ty * 4 + u];
+                bv[u] = Bs[kk][tx * 4 + u];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) acc[u][v] = fmaf(av[u], bv[v], acc[u][v]);
+        }
+        __syncthreads();
+    }
+    for (int u = 0; u < 4; ++u) {
+        const int i = i0 + ty * 4 + u;
+        if (i >= N) continue;
+        for (int v = 0; v < 4; ++v) {
+            const int j = j0 + tx * 4 + v;
+            if (j < N) corr[((int64_t)p * N + i) * N + j] = acc[u][v] * scale;
+        }
+    }
+}
+
+// avg_pool2d(2, stride 2) of every [h][w] map (floor): the next pyramid level
+__global__ void corr_pool_kernel(const float* in, int64_t maps, int h, int w, float* out, int oh, int ow) {
+    const int64_t total = maps * oh * ow;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / ((int64_t)oh * ow);
+        const int q = (int)(i - r * oh * ow), y = q / ow, x = q - y * ow;
+        const float* s = in + r * h * w + (int64_t)(2 * y) * w + 2 * x;
+        float acc = s[0];
+        acc += s[1];
+        acc += s[w];
+        acc += s[w + 1];
+        out[i] = acc / 4.f;
+    }
+}
+
+// CorrBlock.__call__: feature l*81 + a*9 + b of row m samples level l at (x + a - 4, y + b - 4) (the meshgrid(dy, dx) order), bilinear with
+// zero padding as grid_sample(align_corners=True) after bilinear_sampler's normalisation; written as convc1's A operand (Kpad 384)
+__global__ void corr_lookup_kernel(const CorrLookupParams p) {
+    const int64_t total = p.M * (int64_t)p.Kpad;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t m = i / p.Kpad;
+        const int f = (int)(i - m * p.Kpad);
+        float v = 0.f;
+        if (f < p.levels * 81) {
+            const int l = f / 81, a = (f - l * 81) / 9, b = f % 9;
+            const int H = p.h[l], W = p.w[l];
+            const float cx = p.coords[2 * m] / (float)(1 << l) + (float)(a - 4);
+            const float cy = p.coords[2 * m + 1] / (float)(1 << l) + (float)(b - 4);
+            const float gx = 2.f * cx / (float)(W - 1) - 1.f, gy = 2.f * cy / (float)(H - 1) - 1.f;
+            const float ix = (gx + 1.f) * (0.5f * (float)(W - 1)), iy = (gy + 1.f) * (0.5f * (float)(H - 1));
+            const float fx = floorf(ix), fy = floorf(iy);
+            const int x0 = (int)fx, y0 = (int)fy;
+            const float wx = ix - fx, wy = iy - fy;
+            const float* map = p.pyr[l] + m * (int64_t)H * W;
+            auto at = [&](int yy, int xx) { return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? map[(int64_t)yy * W + xx] : 0.f; };
+            v = at(y0, x0) * ((1.f - wx) * (1.f - wy)) + at(y0, x0 + 1) * (wx * (1.f - wy)) + at(y0 + 1, x0) * ((1.f - wx) * wy) +
+                at(y0 + 1, x0 + 1) * (wx * wy);
+        } else if (p.out) {
+            continue;
+        }
+        if (p.out) p.out[m * p.out_ld + f] = v;
+        else store_split(p.A, m, p.Kpad, f, v);
+    }
+}
+
+// BasicMotionEncoder's output: x[:, 128:254] = relu(conv(...)), x[:, 254:256] = flow
+__global__ void motion_finish_kernel(float* x, const float* coords, int64_t M, int h8, int w8) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M * 128; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t m = i >> 7;
+        const int c = (int)(i & 127);
+        float* d = x + m * 256 + 128 + c;
+        if (c < 126) {
+            *d = fmaxf(*d, 0.f);
+        } else {
+            const int r = (int)(m % ((int64_t)h8 * w8));
+            *d = coords[2 * m + (c - 126)] - (float)(c == 126 ? r % w8 : r / w8);
+        }
+    }
+}
+
+// SepConvGRU state update: h = (1 - z) h + z tanh(q), z = sigmoid(zr[:, :128])
+__global__ void gru_update_kernel(float* h, const float* zr, const float* q, int64_t M) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M * 128; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t m = i >> 7;
+        const int c = (int)(i & 127);
+        const float z = sigmoidf_(zr[m * 256 + c]);
+        const float qq = tanhf(q[i]);
+        h[i] = (1.f - z) * h[i] + z * qq;
+    }
+}
+
+__global__ void flow_update_kernel(float* coords, const float* delta, int ld, int64_t M) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * M; i += (int64_t)gridDim.x * blockDim.x)
+        coords[i] = coords[i] + delta[(i >> 1) * ld + (i & 1)];
+}
+
+// RAFT.upsample_flow: out[c, 8y+i, 8x+j] = sum_k softmax_k(mask[k*64 + i*8 + j]) * 8 flow[c, y+ky-1, x+kx-1] (k = 3ky + kx, zero padding)
+__global__ void convex_upsample_kernel(const ConvexUpParams p) {
+    const int H = 8 * p.h8, W = 8 * p.w8;
+    const int64_t total = (int64_t)p.P * H * W;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int pr = (int)(i / ((int64_t)H * W));
+        const int q = (int)(i - (int64_t)pr * H * W), Y = q / W, X = q - Y * W;
+        const int y = Y >> 3, x = X >> 3, sub = (Y & 7) * 8 + (X & 7);
+        const int64_t pix = ((int64_t)pr * p.h8 + y) * p.w8 + x;
+        const float* mk = p.mask + pix * p.mask_ld + sub;
+        float e[9], mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            e[k] = mk[k * 64] * p.mask_scale;
+            mx = fmaxf(mx, e[k]);
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            e[k] = expf(e[k] - mx);
+            s += e[k];
+        }
+        float o0 = 0.f, o1 = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
+            float f0 = 0.f, f1 = 0.f;
+            if (yy >= 0 && yy < p.h8 && xx >= 0 && xx < p.w8) {
+                const int64_t n = ((int64_t)pr * p.h8 + yy) * p.w8 + xx;
+                if (p.coords) {
+                    f0 = 8.f * (p.coords[2 * n] - (float)xx);
+                    f1 = 8.f * (p.coords[2 * n + 1] - (float)yy);
+                } else {
+                    f0 = 8.f * p.flow[(int64_t)pr * 2 * p.h8 * p.w8 + (int64_t)yy * p.w8 + xx];
+                    f1 = 8.f * p.flow[((int64_t)pr * 2 + 1) * p.h8 * p.w8 + (int64_t)yy * p.w8 + xx];
+                }
+            }
+            const float w = e[k] / s;
+            o0 += w * f0;
+            o1 += w * f1;
+        }
+        const int g = pr / p.ppg, t = pr - g * p.ppg;
+        float* o = p.out + g * p.out_sb + t * p.out_st + (int64_t)Y * W + X;
+        o[0] = o0;
+        o[p.out_sc] = o1;
+    }
+}
+
+// flow_low[p][c][y][x] = coords1 - coords0 (the two-image call's first output)
+__global__ void flow_low_kernel(const float* coords, int P, int h8, int w8, float* out) {
+    const int64_t n = (int64_t)P * h8 * w8;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t m = i >> 1;
+        const int c = (int)(i & 1);
+        const int pr = (int)(m / ((int64_t)h8 * w8)), r = (int)(m - (int64_t)pr * h8 * w8);
+        out[((int64_t)pr * 2 + c) * h8 * w8 + r] = coords[i] - (float)(c ? r / w8 : r % w8);
+    }
+}
+
+unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 1 << 20); }
+
+}  // namespace
+
+int launch_im2col(const Im2colParams& p, hipStream_t s) {
+    CWM_REQUIRE(p.Kpad % 64 == 0 && (p.c_hi <= p.c_lo || (p.c_lo % 8 == 0 && p.c_hi % 8 == 0)), "im2col: Kpad = %d, channel range [%d, %d)", p.Kpad,
+                p.c_lo, p.c_hi);
+    const int64_t total = (int64_t)p.n_img * p.OH * p.OW * (p.Kpad / 8);
+    CWM_REQUIRE(total < (1ll << 31), "im2col: %lld groups exceed 32-bit indexing", (long long)total);
+    hipLaunchKernelGGL(im2col_kernel, dim3(grid_for(total)), dim3(256), 0, s, p);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int instnorm_chunks(int HW) { return std::min(kInstNormMaxChunks, (HW + 1023) / 1024); }
+
+int launch_instnorm_stats(const float* x, int n_img, int HW, int C, float eps, float* stats, double* work, hipStream_t s) {
+    const int nch = instnorm_chunks(HW), chunk = (HW + nch - 1) / nch;
+    hipLaunchKernelGGL(instnorm_partial_kernel, dim3(n_img, (C + 63) / 64, nch), dim3(512), 0, s, x, HW, C, chunk, (double2*)work);
+    hipLaunchKernelGGL(instnorm_finish_kernel, dim3((n_img * C + 255) / 256), dim3(256), 0, s, (const double2*)work, n_img, HW, C, nch, eps,
+                       (float2*)stats);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_residual_join(const ConvSrc& X, const ConvSrc& Y, int n_img, int HW, float* out, hipStream_t s) {
+    const int64_t total = (int64_t)n_img * HW * Y.C;
+    hipLaunchKernelGGL(residual_join_kernel, dim3(grid_for(total)), dim3(256), 0, s, X, Y, total, HW, out);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_cnet_split(const float* cn, int64_t M, float* h, float* x, hipStream_t s) {
+    hipLaunchKernelGGL(cnet_split_kernel, dim3(grid_for(M * 128)), dim3(256), 0, s, cn, M, h, x);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_coords_init(float* coords, int64_t M, int h8, int w8, hipStream_t s) {
+    hipLaunchKernelGGL(coords_init_kernel, dim3(grid_for(M)), dim3(256), 0, s, coords, M, h8, w8);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_corr(const float* f1, const float* f2, int P, int N, int D, float* corr, hipStream_t s) {
+    CWM_REQUIRE(D % 16 == 0, "corr: feature width %d must be a multiple of 16", D);
+    hipLaunchKernelGGL(corr_kernel, dim3((N + 63) / 64, (N + 63) / 64, P), dim3(256), 0, s, f1, f2, N, D, 1.f / sqrtf((float)D), corr);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_corr_pool(const float* in, int64_t maps, int h, int w, float* out, hipStream_t s) {
+    const int oh = h / 2, ow = w / 2;
+    hipLaunchKernelGGL(corr_pool_kernel, dim3(grid_for(maps * oh * ow)), dim3(256), 0, s, in, maps, h, w, out, oh, ow);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_corr_lookup(const CorrLookupParams& p, hipStream_t s) {
+    hipLaunchKernelGGL(corr_lookup_kernel, dim3(grid_for(p.M * p.Kpad)), dim3(256), 0, s, p);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_motion_finish(float* x, const float* coords, int64_t M, int h8, int w8, hipStream_t s) {
+    hipLaunchKernelGGL(motion_finish_kernel, dim3(grid_for(M * 128)), dim3(256), 0, s, x, coords, M, h8, w8);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_gru_update(float* h, const float* zr, const float* q, int64_t M, hipStream_t s) {
+    hipLaunchKernelGGL(gru_update_kernel, dim3(grid_for(M * 128)), dim3(256), 0, s, h, zr, q, M);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_flow_update(float* coords, const float* delta, int ld, int64_t M, hipStream_t s) {
+    hipLaunchKernelGGL(flow_update_kernel, dim3(grid_for(2 * M)), dim3(256), 0, s, coords, delta, ld, M);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_convex_upsample(const ConvexUpParams& p, hipStream_t s) {
+    hipLaunchKernelGGL(convex_upsample_kernel, dim3(grid_for((int64_t)p.P * 64 * p.h8 * p.w8)), dim3(256), 0, s, p);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_flow_low(const float* coords, int P, int h8, int w8, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(flow_low_kernel, dim3(grid_for((int64_t)2 * P * h8 * w8)), dim3(256), 0, s, coords, P, h8, w8, out);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace cwm

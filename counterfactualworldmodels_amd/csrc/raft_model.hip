@@ -1,0 +1,547 @@
+// RAFT-large optical flow behind the C ABI (include/cwm_hip.h cwm_raft_*): cwm/models/raft/raft_model.py:103-300 in its inference
+// configuration -- BasicEncoder fnet (instance norm) and cnet (eval batch norm, folded into the convolutions at load), 4-level all-pairs
+// correlation of radius 4, BasicUpdateBlock with SepConvGRU, convex upsampling.  Every convolution is an im2col (raft_kernels.hip) and a
+// parity (split-bf16) GEMM on launch_gemm whose fp32 epilogue writes straight into a channel slice of an NHWC buffer.  The mask head and
+// the upsampling run once, after the last iteration (the reference computes them every iteration and returns the last).
+#include <stddef.h>
+
+#include "engine.h"
+
+using namespace cwm;
+
+namespace {
+
+constexpr int kPlanes = 2;
+constexpr int kFeat = 256;  // fnet output width
+constexpr int kLookupKpad = 384;  // 4 levels x 81 = 324 correlation features, padded to the GEMM's K granule
+constexpr int kMaxEncImages = 32;  // images per encoder pass (bounds the im2col buffer: 29 MB per 224^2 image)
+
+struct Raw {
+    std::vector<int64_t> shape;
+    int64_t numel = 0;
+    float* dev = nullptr;
+    bool loaded = false;
+    bool required = true;
+};
+
+struct ConvPart {
+    std::string w, b, bn;  // weight / bias keys; bn: prefix of the batch norm folded into this convolution ("" = none)
+    int n = 0;             // output channels
+};
+
+struct RaftConv {
+    LinearW L;  // N = output channels of all parts rounded up to 16 (zero rows / bias beyond), K = kh * kw * cin
+    int cin = 0, kh = 1, kw = 1, stride = 1, pad_h = 0, pad_w = 0;
+    std::vector<ConvPart> parts;
+};
+
+struct Block {
+    RaftConv c1, c2, down;
+    bool has_down = false;
+};
+
+struct Encoder {
+    bool instance = false;
+    RaftConv conv1, conv2;
+    Block blocks[6];
+};
+
+__global__ void pack_conv_kernel(const float* w, const float* gamma, const float* var, float eps, int N, int C, int kh, int kw, int Kpad, int row0,
+                                 bf16* il) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * Kpad) return;
+    const int n = (int)(i / Kpad), k = (int)(i - (int64_t)n * Kpad);
+    float v = 0.f;
+    if (k < kh * kw * C) {
+        const int tap = k / C, c = k - tap * C, ky = tap / kw, kx = tap - ky * kw;
+        v = w[(((int64_t)n * C + c) * kh + ky) * kw + kx];
+        if (gamma) v = v * (gamma[n] / sqrtf(var[n] + eps));
+    }
+    bf16 h, l;
+    split_bf16(v, h, l);
+    bf16* d = il + a_pos<2>(row0 + n, Kpad, k);
+    d[0] = h;
+    d[kLoOffset] = l;
+}
+
+__global__ void pack_bias_kernel(const float* b, const float* gamma, const float* beta, const float* mean, const float* var, float eps, int N,
+                                 float* dst) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    dst[n] = gamma ? (b[n] - mean[n]) * (gamma[n] / sqrtf(var[n] + eps)) + beta[n] : b[n];
+}
+
+ConvSrc src_of(const float* p, int C, const float* stats = nullptr, int relu = 0, int ld = 0) {
+    ConvSrc s;
+    memset(&s, 0, sizeof(s));
+    s.p = p;
+    s.C = C;
+    s.ld = ld ? ld : C;
+    s.stats = stats;
+    s.relu = relu;
+    return s;
+}
+
+}  // namespace
+
+struct cwm_raft_model {
+    Engine eng;
+    std::map<std::string, Raw> raw;
+    std::vector<RaftConv*> convs;
+    bool dirty = true;
+    Encoder fnet, cnet;
+    RaftConv convc1, convc2, convf1, convf2, conv, zr[2], q[2], fh1, fh2, mask0, mask2;
+    // workspace (cached by shape)
+    int ws_P = 0, ws_H = 0, ws_W = 0;
+    float *enc_act[4] = {nullptr, nullptr, nullptr, nullptr}, *enc_stats[4] = {nullptr, nullptr, nullptr, nullptr};
+    bf16* enc_A = nullptr;
+    double* enc_norm_work = nullptr;
+    float *fmap = nullptr, *cn = nullptr, *pyr[4] = {nullptr, nullptr, nullptr, nullptr};
+    bf16 *corrA = nullptr, *updA = nullptr;
+    float *c1 = nullptr, *cf = nullptr, *f1 = nullptr, *x = nullptr, *h = nullptr, *zrb = nullptr, *qb = nullptr, *fh = nullptr, *d = nullptr,
+          *coords = nullptr, *mask = nullptr;
+};
+
+namespace {
+
+void add_raw(cwm_raft_model* m, const std::string& key, std::vector<int64_t> shape, bool required = true) {
+    Raw r;
+    r.shape = shape;
+    r.numel = 1;
+    for (auto v : shape) r.numel *= v;
+    r.required = required;
+    m->raw[key] = r;
+}
+
+void add_bn(cwm_raft_model* m, const std::string& pre, int c) {
+    for (const char* p : {"weight", "bias", "running_mean", "running_var"}) add_raw(m, pre + "." + p, {c});
+    add_raw(m, pre + ".num_batches_tracked", {}, false);
+}
+
+int make_conv(cwm_raft_model* m, RaftConv& cv, std::vector<ConvPart> parts, int cin, int kh, int kw, int stride, int pad_h, int pad_w) {
+    cv.cin = cin;
+    cv.kh = kh;
+    cv.kw = kw;
+    cv.stride = stride;
+    cv.pad_h = pad_h;
+    cv.pad_w = pad_w;
+    cv.parts = parts;
+    int n = 0;
+    for (auto& p : parts) {
+        add_raw(m, p.w, {p.n, cin, kh, kw});
+        add_raw(m, p.b, {p.n});
+        n += p.n;
+    }
+    m->convs.push_back(&cv);
+    return m->eng.make_linear(cv.L, round_up(n, 16), kh * kw * cin, true);
+}
+
+int make_encoder(cwm_raft_model* m, Encoder& e, const std::string& pre, bool instance, int out_dim) {
+    e.instance = instance;
+    auto bn = [&](const std::string& name, int c) -> std::string {
+        if (instance) return "";
+        add_bn(m, pre + name, c);
+        return pre + name;
+    };
+    const std::string n1 = bn("norm1", 64);
+    int rc;
+    if ((rc = make_conv(m, e.conv1, {{pre + "conv1.weight", pre + "conv1.bias", n1, 64}}, 3, 7, 7, 2, 3, 3))) return rc;
+    int cin = 64, bi = 0;
+    const int dims[3] = {64, 96, 128};
+    for (int li = 0; li < 3; ++li)
+        for (int j = 0; j < 2; ++j, ++bi) {
+            Block& B = e.blocks[bi];
+            const std::string b = pre + "layer" + std::to_string(li + 1) + "." + std::to_string(j) + ".";
+            const std::string bl = "layer" + std::to_string(li + 1) + "." + std::to_string(j) + ".";
+            const int dim = dims[li], stride = (li > 0 && j == 0) ? 2 : 1;
+            const std::string bn1 = bn(bl + "norm1", dim), bn2 = bn(bl + "norm2", dim);
+            if ((rc = make_conv(m, B.c1, {{b + "conv1.weight", b + "conv1.bias", bn1, dim}}, cin, 3, 3, stride, 1, 1))) return rc;
+            if ((rc = make_conv(m, B.c2, {{b + "conv2.weight", b + "conv2.bias", bn2, dim}}, dim, 3, 3, 1, 1, 1))) return rc;
+            if (stride != 1) {
+                B.has_down = true;
+                bn(bl + "norm3", dim);  // the same module as downsample.1 (listed twice in the state dict); downsample.1 is what load_state_dict keeps
+                const std::string bn3 = bn(bl + "downsample.1", dim);
+                if ((rc = make_conv(m, B.down, {{b + "downsample.0.weight", b + "downsample.0.bias", bn3, dim}}, cin, 1, 1, 2, 0, 0))) return rc;
+            }
+            cin = dim;
+        }
+    return make_conv(m, e.conv2, {{pre + "conv2.weight", pre + "conv2.bias", "", out_dim}}, 128, 1, 1, 1, 0, 0);
+}
+
+int prepare(cwm_raft_model* m) {
+    if (!m->dirty) return 0;
+    char buf[256];
+    const int missing = cwm_raft_missing_weights(m, buf, sizeof(buf));
+    CWM_REQUIRE(missing == 0, "cwm_raft_forward: %d weights missing (first: %s)", missing, buf);
+    for (RaftConv* cv : m->convs) {
+        int row0 = 0;
+        for (auto& p : cv->parts) {
+            const float *g = nullptr, *be = nullptr, *mu = nullptr, *var = nullptr;
+            if (!p.bn.empty()) {
+                g = m->raw[p.bn + ".weight"].dev;
+                be = m->raw[p.bn + ".bias"].dev;
+                mu = m->raw[p.bn + ".running_mean"].dev;
+                var = m->raw[p.bn + ".running_var"].dev;
+            }
+            const int64_t total = (int64_t)p.n * cv->L.Kpad;
+            hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, m->raw[p.w].dev, g, var, 1e-5f, p.n, cv->cin,
+                               cv->kh, cv->kw, cv->L.Kpad, row0, cv->L.w_il);
+            hipLaunchKernelGGL(pack_bias_kernel, dim3((p.n + 255) / 256), dim3(256), 0, 0, m->raw[p.b].dev, g, be, mu, var, 1e-5f, p.n, cv->L.bias + row0);
+            row0 += p.n;
+        }
+    }
+    CWM_HIP_CHECK(hipGetLastError());
+    CWM_HIP_CHECK(hipDeviceSynchronize());
+    m->dirty = false;
+    return 0;
+}
+
+int level_sides(int s, int l) {
+    for (int i = 0; i < l; ++i) s /= 2;
+    return s;
+}
+
+int ensure_workspace(cwm_raft_model* m, int P, int H, int W) {
+    if (m->ws_P >= P && m->ws_H == H && m->ws_W == W) return 0;
+    Engine& E = m->eng;
+    if (int rc = E.free_workspace()) return rc;
+    m->ws_P = 0;
+    const int64_t hw2 = (int64_t)(H / 2) * (W / 2), hw8 = (int64_t)(H / 8) * (W / 8), M = P * hw8;
+    const int64_t n = std::min(2 * P, kMaxEncImages);
+    int rc = 0;
+    for (int i = 0; i < 4 && !rc; ++i) rc = E.ws(&m->enc_act[i], (size_t)(n * hw2 * 64));
+    for (int i = 0; i < 4 && !rc; ++i) rc = E.ws(&m->enc_stats[i], (size_t)(n * 128 * 2));
+    if (rc || (rc = E.ws(&m->enc_A, (size_t)(n * hw2 * 576 * 2))) || (rc = E.ws(&m->enc_norm_work, (size_t)(2 * n * kInstNormMaxChunks * 128))))
+        return rc;
+    if ((rc = E.ws(&m->fmap, (size_t)(2 * M * kFeat))) || (rc = E.ws(&m->cn, (size_t)(M * 256)))) return rc;
+    for (int l = 0; l < 4 && !rc; ++l) rc = E.ws(&m->pyr[l], (size_t)(M * level_sides(H / 8, l) * level_sides(W / 8, l)));
+    if (rc || (rc = E.ws(&m->corrA, (size_t)(M * kLookupKpad * 2))) || (rc = E.ws(&m->updA, (size_t)(M * 2304 * 2)))) return rc;
+    if ((rc = E.ws(&m->c1, (size_t)(M * 256))) || (rc = E.ws(&m->cf, (size_t)(M * 256))) || (rc = E.ws(&m->f1, (size_t)(M * 128))) ||
+        (rc = E.ws(&m->x, (size_t)(M * 256))) || (rc = E.ws(&m->h, (size_t)(M * 128))) || (rc = E.ws(&m->zrb, (size_t)(M * 256))) ||
+        (rc = E.ws(&m->qb, (size_t)(M * 128))) || (rc = E.ws(&m->fh, (size_t)(M * 256))) || (rc = E.ws(&m->d, (size_t)(M * 16))) ||
+        (rc = E.ws(&m->coords, (size_t)(M * 2))) || (rc = E.ws(&m->mask, (size_t)(M * 576))))
+        return rc;
+    m->ws_P = P;
+    m->ws_H = H;
+    m->ws_W = W;
+    return 0;
+}
+
+// one convolution: im2col of `ip` (its sources, image and channel range already set) into A, then the GEMM into C (row stride ldc)
+int run_conv(cwm_raft_model* m, const RaftConv& cv, Im2colParams ip, int n_img, int H, int W, bf16* A, float* C, int ldc, hipStream_t s,
+             bool skip_im2col = false) {
+    ip.n_img = n_img;
+    ip.H = H;
+    ip.W = W;
+    ip.kh = cv.kh;
+    ip.kw = cv.kw;
+    ip.stride = cv.stride;
+    ip.pad_h = cv.pad_h;
+    ip.pad_w = cv.pad_w;
+    ip.OH = (H + 2 * cv.pad_h - cv.kh) / cv.stride + 1;
+    ip.OW = (W + 2 * cv.pad_w - cv.kw) / cv.stride + 1;
+    ip.A = A;
+    ip.Kpad = cv.L.Kpad;
+    if (!skip_im2col)
+        if (int rc = launch_im2col(ip, s)) return rc;
+    GemmParams g = gemm_base(A, cv.L.Kpad, cv.L, n_img * ip.OH * ip.OW, kPlanes);
+    g.epi = EPI_F32;
+    g.C = C;
+    g.ldc = ldc;
+    return m->eng.run_gemm(g, kPlanes, s);
+}
+
+Im2colParams im2col_of(const ConvSrc& a, const ConvSrc* b = nullptr) {
+    Im2colParams ip;
+    memset(&ip, 0, sizeof(ip));
+    ip.src[0] = a;
+    ip.nsrc = 1;
+    if (b) {
+        ip.src[1] = *b;
+        ip.nsrc = 2;
+    }
+    return ip;
+}
+
+// BasicEncoder.forward (extractor.py:160-192) on images [img0, img0 + n) of `image`; output [n][H/8 * W/8][out width] at `out`
+int run_encoder(cwm_raft_model* m, const Encoder& e, const ImageSrc& image, int img0, int n, int H, int W, float* out, hipStream_t s) {
+    int rc;
+    float** act = m->enc_act;
+    float** st = m->enc_stats;
+    const float eps = 1e-5f;
+    // conv1 7x7/2 -> norm1 -> relu
+    Im2colParams ip = im2col_of(src_of(nullptr, 3));
+    ip.image = image;
+    ip.img0 = img0;
+    if ((rc = run_conv(m, e.conv1, ip, n, H, W, m->enc_A, act[0], 64, s))) return rc;
+    int h = H / 2, w = W / 2, C = 64;
+    if (e.instance && (rc = launch_instnorm_stats(act[0], n, h * w, C, eps, st[0], m->enc_norm_work, s))) return rc;
+    ConvSrc a = src_of(act[0], C, e.instance ? st[0] : nullptr, 1);
+    for (int bi = 0; bi < 6; ++bi) {
+        const Block& B = e.blocks[bi];
+        const int dim = B.c1.L.N, stride = B.c1.stride;
+        const int oh = (h - 1) / stride + 1, ow = (w - 1) / stride + 1;
+        // y = relu(norm1(conv1(x))); y = relu(norm2(conv2(y)))
+        if ((rc = run_conv(m, B.c1, im2col_of(a), n, h, w, m->enc_A, act[1], dim, s))) return rc;
+        if (e.instance && (rc = launch_instnorm_stats(act[1], n, oh * ow, dim, eps, st[1], m->enc_norm_work, s))) return rc;
+        if ((rc = run_conv(m, B.c2, im2col_of(src_of(act[1], dim, e.instance ? st[1] : nullptr, 1)), n, oh, ow, m->enc_A, act[2], dim, s))) return rc;
+        if (e.instance && (rc = launch_instnorm_stats(act[2], n, oh * ow, dim, eps, st[2], m->enc_norm_work, s))) return rc;
+        ConvSrc X = a;
+        if (B.has_down) {  // x = norm3(downsample(x))
+            if ((rc = run_conv(m, B.down, im2col_of(a), n, h, w, m->enc_A, act[3], dim, s))) return rc;
+            if (e.instance && (rc = launch_instnorm_stats(act[3], n, oh * ow, dim, eps, st[3], m->enc_norm_work, s))) return rc;
+            X = src_of(act[3], dim, e.instance ? st[3] : nullptr, 0);
+        }
+        // relu(x + y), in place over the block input (an element is read and written by the same thread)
+        if ((rc = launch_residual_join(X, src_of(act[2], dim, e.instance ? st[2] : nullptr, 1), n, oh * ow, act[0], s))) return rc;
+        a = src_of(act[0], dim);
+        h = oh;
+        w = ow;
+        C = dim;
+    }
+    return run_conv(m, e.conv2, im2col_of(a), n, h, w, m->enc_A, out, e.conv2.L.N, s);
+}
+
+int forward(cwm_raft_model* m, const cwm_raft_forward_args& a) {
+    hipStream_t s = (hipStream_t)a.stream;
+    const int ppg = a.pairs > 0 ? a.pairs : 1;
+    const int P = a.batch * ppg, H = a.height, W = a.width, h8 = H / 8, w8 = W / 8;
+    const int64_t hw8 = (int64_t)h8 * w8, M = P * hw8;
+    int rc;
+    if ((rc = prepare(m)) || (rc = ensure_workspace(m, P, H, W))) return rc;
+    ImageSrc img;
+    memset(&img, 0, sizeof(img));
+    img.base[0] = a.image1_dev;
+    img.base[1] = a.image2_dev;
+    img.sb[0] = a.image1_stride_b; img.st[0] = a.image1_stride_t; img.sc[0] = a.image1_stride_c;
+    img.sb[1] = a.image2_stride_b; img.st[1] = a.image2_stride_t; img.sc[1] = a.image2_stride_c;
+    img.P = P;
+    img.ppg = ppg;
+    img.scale = a.input_scale;
+    // feature network over image1 and image2 of every pair (instance norm is per image: any grouping gives the same result)
+    for (int i0 = 0; i0 < 2 * P; i0 += kMaxEncImages) {
+        const int n = std::min(kMaxEncImages, 2 * P - i0);
+        if ((rc = run_encoder(m, m->fnet, img, i0, n, H, W, m->fmap + (int64_t)i0 * hw8 * kFeat, s))) return rc;
+    }
+    // context network over image1
+    for (int i0 = 0; i0 < P; i0 += kMaxEncImages) {
+        const int n = std::min(kMaxEncImages, P - i0);
+        if ((rc = run_encoder(m, m->cnet, img, i0, n, H, W, m->cn + (int64_t)i0 * hw8 * 256, s))) return rc;
+    }
+    if ((rc = launch_cnet_split(m->cn, M, m->h, m->x, s))) return rc;
+    // correlation pyramid
+    if ((rc = launch_corr(m->fmap, m->fmap + M * kFeat, P, (int)hw8, kFeat, m->pyr[0], s))) return rc;
+    CorrLookupParams lp;
+    memset(&lp, 0, sizeof(lp));
+    lp.levels = 4;
+    for (int l = 0; l < 4; ++l) {
+        lp.pyr[l] = m->pyr[l];
+        lp.h[l] = level_sides(h8, l);
+        lp.w[l] = level_sides(w8, l);
+        if (l > 0 && (rc = launch_corr_pool(m->pyr[l - 1], M, lp.h[l - 1], lp.w[l - 1], m->pyr[l], s))) return rc;
+    }
+    lp.coords = m->coords;
+    lp.M = M;
+    lp.A = m->corrA;
+    lp.Kpad = kLookupKpad;
+    if ((rc = launch_coords_init(m->coords, M, h8, w8, s))) return rc;
+    ConvSrc flow_src;
+    memset(&flow_src, 0, sizeof(flow_src));
+    flow_src.C = 2;
+    flow_src.coords = m->coords;
+    for (int it = 0; it < a.iters; ++it) {
+        // BasicMotionEncoder
+        if ((rc = launch_corr_lookup(lp, s))) return rc;
+        if ((rc = run_conv(m, m->convc1, Im2colParams{}, P, h8, w8, m->corrA, m->c1, 256, s, true))) return rc;
+        if ((rc = run_conv(m, m->convc2, im2col_of(src_of(m->c1, 256, nullptr, 1)), P, h8, w8, m->updA, m->cf, 256, s))) return rc;
+        if ((rc = run_conv(m, m->convf1, im2col_of(flow_src), P, h8, w8, m->updA, m->f1, 128, s))) return rc;
+        if ((rc = run_conv(m, m->convf2, im2col_of(src_of(m->f1, 128, nullptr, 1)), P, h8, w8, m->updA, m->cf + 192, 256, s))) return rc;
+        if ((rc = run_conv(m, m->conv, im2col_of(src_of(m->cf, 256, nullptr, 1)), P, h8, w8, m->updA, m->x + 128, 256, s))) return rc;
+        if ((rc = launch_motion_finish(m->x, m->coords, M, h8, w8, s))) return rc;
+        // SepConvGRU: (1,5) then (5,1)
+        for (int pass = 0; pass < 2; ++pass) {
+            const ConvSrc xs = src_of(m->x, 256);
+            if ((rc = run_conv(m, m->zr[pass], im2col_of(src_of(m->h, 128), &xs), P, h8, w8, m->updA, m->zrb, 256, s))) return rc;
+            ConvSrc rh = src_of(m->h, 128);
+            rh.gate = m->zrb + 128;
+            rh.gate_ld = 256;
+            Im2colParams iq = im2col_of(rh, &xs);
+            iq.c_lo = 0;
+            iq.c_hi = 128;  // only the h channels change: the x half of every tap is still in A
+            if ((rc = run_conv(m, m->q[pass], iq, P, h8, w8, m->updA, m->qb, 128, s))) return rc;
+            if ((rc = launch_gru_update(m->h, m->zrb, m->qb, M, s))) return rc;
+        }
+        // FlowHead; coords1 += delta
+        if ((rc = run_conv(m, m->fh1, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, s))) return rc;
+        if ((rc = run_conv(m, m->fh2, im2col_of(src_of(m->fh, 256, nullptr, 1)), P, h8, w8, m->updA, m->d, 16, s))) return rc;
+        if ((rc = launch_flow_update(m->coords, m->d, 16, M, s))) return rc;
+    }
+    // mask = 0.25 * mask.2(relu(mask.0(net))), once; convex upsampling of the last flow
+    if ((rc = run_conv(m, m->mask0, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, s))) return rc;
+    if ((rc = run_conv(m, m->mask2, im2col_of(src_of(m->fh, 256, nullptr, 1)), P, h8, w8, m->updA, m->mask, 576, s))) return rc;
+    ConvexUpParams up;
+    memset(&up, 0, sizeof(up));
+    up.coords = m->coords;
+    up.mask = m->mask;
+    up.mask_ld = 576;
+    up.mask_scale = 0.25f;
+    up.P = P;
+    up.ppg = ppg;
+    up.h8 = h8;
+    up.w8 = w8;
+    up.out = a.flow_dev;
+    up.out_sb = a.flow_stride_b;
+    up.out_st = a.flow_stride_t;
+    up.out_sc = a.flow_stride_c;
+    if ((rc = launch_convex_upsample(up, s))) return rc;
+    if (a.flow_low_dev && (rc = launch_flow_low(m->coords, P, h8, w8, a.flow_low_dev, s))) return rc;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int cwm_raft_create(cwm_raft_model** out) {
+    CWM_REQUIRE(out, "cwm_raft_create: null argument");
+    cwm_raft_model* m = new cwm_raft_model();
+    CWM_HIP_CHECK(hipGetDevice(&m->eng.device));
+    int rc = 0;
+    do {
+        if ((rc = make_encoder(m, m->fnet, "fnet.", true, kFeat)) || (rc = make_encoder(m, m->cnet, "cnet.", false, 256))) break;
+        const std::string u = "update_block.";
+        auto part = [&](const std::string& name, int n) { return ConvPart{u + name + ".weight", u + name + ".bias", "", n}; };
+        if ((rc = make_conv(m, m->convc1, {part("encoder.convc1", 256)}, 324, 1, 1, 1, 0, 0)) ||
+            (rc = make_conv(m, m->convc2, {part("encoder.convc2", 192)}, 256, 3, 3, 1, 1, 1)) ||
+            (rc = make_conv(m, m->convf1, {part("encoder.convf1", 128)}, 2, 7, 7, 1, 3, 3)) ||
+            (rc = make_conv(m, m->convf2, {part("encoder.convf2", 64)}, 128, 3, 3, 1, 1, 1)) ||
+            (rc = make_conv(m, m->conv, {part("encoder.conv", 126)}, 256, 3, 3, 1, 1, 1)))
+            break;
+        // z and r share their input: one GEMM with the two weights stacked (z: columns 0-127, r: 128-255)
+        if ((rc = make_conv(m, m->zr[0], {part("gru.convz1", 128), part("gru.convr1", 128)}, 384, 1, 5, 1, 0, 2)) ||
+            (rc = make_conv(m, m->q[0], {part("gru.convq1", 128)}, 384, 1, 5, 1, 0, 2)) ||
+            (rc = make_conv(m, m->zr[1], {part("gru.convz2", 128), part("gru.convr2", 128)}, 384, 5, 1, 1, 2, 0)) ||
+            (rc = make_conv(m, m->q[1], {part("gru.convq2", 128)}, 384, 5, 1, 1, 2, 0)))
+            break;
+        if ((rc = make_conv(m, m->fh1, {part("flow_head.conv1", 256)}, 128, 3, 3, 1, 1, 1)) ||
+            (rc = make_conv(m, m->fh2, {part("flow_head.conv2", 2)}, 256, 3, 3, 1, 1, 1)) ||
+            (rc = make_conv(m, m->mask0, {part("mask.0", 256)}, 128, 3, 3, 1, 1, 1)) ||
+            (rc = make_conv(m, m->mask2, {part("mask.2", 576)}, 256, 1, 1, 1, 0, 0)))
+            break;
+        for (auto& kv : m->raw)
+            if ((rc = m->eng.alloc((void**)&kv.second.dev, (size_t)std::max<int64_t>(kv.second.numel, 1) * sizeof(float), true, false))) break;
+    } while (0);
+    if (rc) {
+        delete m;
+        return rc;
+    }
+    *out = m;
+    return CWM_OK;
+}
+
+extern "C" void cwm_raft_destroy(cwm_raft_model* m) { delete m; }
+
+extern "C" int cwm_raft_load_weight(cwm_raft_model* m, const char* key, const float* data, int on_device, const int64_t* shape, int ndim) {
+    CWM_REQUIRE(m && key && data && (shape || ndim == 0), "cwm_raft_load_weight: null argument");
+    if (int rc = cwm_require_device(m->eng.device, "cwm_raft_load_weight")) return rc;
+    auto it = m->raw.find(key);
+    CWM_REQUIRE(it != m->raw.end(), "unexpected key in state_dict: %s", key);
+    Raw& r = it->second;
+    bool same = (int)r.shape.size() == ndim;
+    for (int i = 0; same && i < ndim; ++i) same = r.shape[i] == shape[i];
+    CWM_REQUIRE(same, "size mismatch for %s", key);
+    if (!r.required) {  // num_batches_tracked: accepted, not used
+        r.loaded = true;
+        return CWM_OK;
+    }
+    CWM_HIP_CHECK(hipMemcpy(r.dev, data, (size_t)r.numel * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    r.loaded = true;
+    m->dirty = true;
+    return CWM_OK;
+}
+
+extern "C" int cwm_raft_missing_weights(cwm_raft_model* m, char* buf, int buflen) {
+    int missing = 0;
+    if (buf && buflen > 0) buf[0] = 0;
+    for (auto& kv : m->raw)
+        if (kv.second.required && !kv.second.loaded) {
+            if (!missing && buf && buflen > 0) snprintf(buf, buflen, "%s", kv.first.c_str());
+            ++missing;
+        }
+    return missing;
+}
+
+extern "C" int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* args) {
+    CWM_REQUIRE(m && args, "cwm_raft_forward: null argument");
+    CWM_REQUIRE(args->struct_size >= sizeof(cwm_raft_forward_args) && args->struct_size <= 4096,
+                "cwm_raft_forward: args->struct_size = %u is not a cwm_raft_forward_args", args->struct_size);
+    const cwm_raft_forward_args& a = *args;
+    if (int rc = cwm_require_device(m->eng.device, "cwm_raft_forward")) return rc;
+    CWM_REQUIRE(a.image1_dev && a.image2_dev && a.flow_dev, "cwm_raft_forward: image1, image2 and flow are required");
+    CWM_REQUIRE(a.batch >= 1 && a.pairs >= 0, "cwm_raft_forward: batch = %d, pairs = %d", a.batch, a.pairs);
+    CWM_REQUIRE(a.height > 0 && a.width > 0 && a.height % 8 == 0 && a.width % 8 == 0, "cwm_raft_forward: H = %d and W = %d must be multiples of 8",
+                a.height, a.width);
+    CWM_REQUIRE(a.height / 8 >= 16 && a.width / 8 >= 16,
+                "cwm_raft_forward: H / 8 = %d and W / 8 = %d must be at least 16 (the coarsest correlation level would have a side of 1)", a.height / 8,
+                a.width / 8);
+    CWM_REQUIRE(a.iters >= 1, "cwm_raft_forward: iters = %d must be >= 1", a.iters);
+    const int64_t M = (int64_t)a.batch * std::max(a.pairs, 1) * (a.height / 8) * (a.width / 8);
+    CWM_REQUIRE(M * 2304 * kPlanes < (1ll << 32), "cwm_raft_forward: batch too large (%lld low-resolution pixels): split it", (long long)M);
+    char buf[256];
+    const int missing = cwm_raft_missing_weights(m, buf, sizeof(buf));
+    CWM_REQUIRE(missing == 0, "cwm_raft_forward: %d weights missing (first: %s)", missing, buf);
+    return forward(m, a);
+}
+
+// ---- stand-alone kernels (kernel tests) -------------------------------------------------------------------------------
+extern "C" int cwm_raft_corr_lookup(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev,
+                                    void* stream) {
+    CWM_REQUIRE(fmap1_dev && fmap2_dev && coords_dev && out_dev && P > 0 && h8 >= 8 && w8 >= 8, "cwm_raft_corr_lookup: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t N = (int64_t)h8 * w8, M = P * N;
+    float* pyr[4] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = 0;
+    CorrLookupParams lp;
+    memset(&lp, 0, sizeof(lp));
+    lp.levels = 4;
+    for (int l = 0; l < 4 && !rc; ++l) {
+        lp.h[l] = level_sides(h8, l);
+        lp.w[l] = level_sides(w8, l);
+        if (hipMalloc((void**)&pyr[l], (size_t)M * lp.h[l] * lp.w[l] * sizeof(float)) != hipSuccess) {
+            cwm_set_error("cwm_raft_corr_lookup: out of device memory");
+            rc = CWM_ERR_HIP;
+        }
+        lp.pyr[l] = pyr[l];
+    }
+    if (!rc) rc = launch_corr(fmap1_dev, fmap2_dev, P, (int)N, kFeat, pyr[0], s);
+    for (int l = 1; l < 4 && !rc; ++l) rc = launch_corr_pool(pyr[l - 1], M, lp.h[l - 1], lp.w[l - 1], pyr[l], s);
+    lp.coords = coords_dev;
+    lp.M = M;
+    lp.Kpad = kLookupKpad;
+    lp.out = out_dev;
+    lp.out_ld = 324;
+    if (!rc) rc = launch_corr_lookup(lp, s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) {
+        cwm_set_error("cwm_raft_corr_lookup: stream synchronisation failed");
+        rc = CWM_ERR_HIP;
+    }
+    for (float* p : pyr)
+        if (p) (void)hipFree(p);
+    return rc;
+}
+
+extern "C" int cwm_raft_convex_upsample(const float* flow_dev, const float* mask_dev, int P, int h8, int w8, float* out_dev, void* stream) {
+    CWM_REQUIRE(flow_dev && mask_dev && out_dev && P > 0 && h8 > 0 && w8 > 0, "cwm_raft_convex_upsample: bad argument");
+    ConvexUpParams up;
+    memset(&up, 0, sizeof(up));
+    up.flow = flow_dev;
+    up.mask = mask_dev;
+    up.mask_ld = 576;
+    up.mask_scale = 1.f;
+    up.P = P;
+    up.ppg = 1;
+    up.h8 = h8;
+    up.w8 = w8;
+    up.out = out_dev;
+    up.out_sb = (int64_t)2 * 64 * h8 * w8;
+    up.out_sc = (int64_t)64 * h8 * w8;
+    return launch_convex_upsample(up, (hipStream_t)stream);
+}

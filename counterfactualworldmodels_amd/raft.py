@@ -1,0 +1,323 @@
+"""RAFT-large optical flow on the GPU: drop-in for `cwm.models.raft.raft_model.load_raft_model` / `RAFT` (raft_model.py:55-300).
+
+The module keeps the reference's parameter tree (179 state-dict tensors: `fnet`, `cnet`, `update_block`), so checkpoints load unchanged,
+and runs its forward pass in libcwm_hip.so (`cwm_raft_forward`): HIP kernels and parity (split-bf16) GEMMs, no PyTorch operator and no
+CPU fallback.  The configuration is the reference's inference one: BasicEncoder fnet (instance norm) and cnet (eval batch norm),
+4 correlation levels of radius 4, BasicUpdateBlock with SepConvGRU, convex upsampling.
+
+    from counterfactualworldmodels_amd.raft import load_raft_model
+    flow_model = load_raft_model("raft-large.pth").cuda().eval()
+    flows = flow_model(x, iters=24)              # x [B,T,3,H,W] in [0,1] -> [B,T-1,2,H,W] pixels
+    flows_back = flow_model(x, backward=True)    # pairs (x[t+1], x[t]), in reversed order
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import os
+from typing import Dict, Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .config import RAFT_CORR_LEVELS, RAFT_CORR_RADIUS, RAFT_HIDDEN
+from .vmae import WeightSync
+
+default_raft_ckpt = "../../../checkpoints/raft_checkpoints/raft-large.pth"
+
+
+class _NoForward(nn.Module):
+    def forward(self, *args, **kwargs):  # pragma: no cover - the whole network runs in the library
+        raise RuntimeError("RAFT submodules hold parameters only: call the RAFT module itself")
+
+
+class ResidualBlock(_NoForward):
+    def __init__(self, in_planes: int, planes: int, norm_fn: str, stride: int = 1):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_planes, planes, kernel_size=3, padding=1, stride=stride)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, padding=1)
+        self.relu = nn.ReLU(inplace=True)
+        norm = nn.BatchNorm2d if norm_fn == "batch" else nn.InstanceNorm2d
+        self.norm1 = norm(planes)
+        self.norm2 = norm(planes)
+        if stride != 1:
+            self.norm3 = norm(planes)
+            self.downsample = nn.Sequential(nn.Conv2d(in_planes, planes, kernel_size=1, stride=stride), self.norm3)
+        else:
+            self.downsample = None
+
+
+class BasicEncoder(_NoForward):
+    def __init__(self, output_dim: int, norm_fn: str):
+        super().__init__()
+        self.norm_fn = norm_fn
+        self.norm1 = nn.BatchNorm2d(64) if norm_fn == "batch" else nn.InstanceNorm2d(64)
+        self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3)
+        self.relu1 = nn.ReLU(inplace=True)
+        self.in_planes = 64
+        self.layer1 = self._make_layer(64, 1)
+        self.layer2 = self._make_layer(96, 2)
+        self.layer3 = self._make_layer(128, 2)
+        self.conv2 = nn.Conv2d(128, output_dim, kernel_size=1)
+        self.dropout = None
+
+    def _make_layer(self, dim: int, stride: int) -> nn.Sequential:
+        layers = (ResidualBlock(self.in_planes, dim, self.norm_fn, stride), ResidualBlock(dim, dim, self.norm_fn, 1))
+        self.in_planes = dim
+        return nn.Sequential(*layers)
+
+
+class BasicMotionEncoder(_NoForward):
+    def __init__(self):
+        super().__init__()
+        cor_planes = RAFT_CORR_LEVELS * (2 * RAFT_CORR_RADIUS + 1) ** 2
+        self.convc1 = nn.Conv2d(cor_planes, 256, 1, padding=0)
+        self.convc2 = nn.Conv2d(256, 192, 3, padding=1)
+        self.convf1 = nn.Conv2d(2, 128, 7, padding=3)
+        self.convf2 = nn.Conv2d(128, 64, 3, padding=1)
+        self.conv = nn.Conv2d(64 + 192, 128 - 2, 3, padding=1)
+
+
+class SepConvGRU(_NoForward):
+    def __init__(self, hidden_dim: int = 128, input_dim: int = 192 + 128):
+        super().__init__()
+        for i, (k, p) in enumerate((((1, 5), (0, 2)), ((5, 1), (2, 0))), 1):
+            for g in "zrq":
+                setattr(self, "conv%s%d" % (g, i), nn.Conv2d(hidden_dim + input_dim, hidden_dim, k, padding=p))
+
+
+class FlowHead(_NoForward):
+    def __init__(self, input_dim: int = 128, hidden_dim: int = 256):
+        super().__init__()
+        self.conv1 = nn.Conv2d(input_dim, hidden_dim, 3, padding=1)
+        self.conv2 = nn.Conv2d(hidden_dim, 2, 3, padding=1)
+        self.relu = nn.ReLU(inplace=True)
+
+
+class BasicUpdateBlock(_NoForward):
+    def __init__(self, hidden_dim: int = 128):
+        super().__init__()
+        self.encoder = BasicMotionEncoder()
+        self.gru = SepConvGRU(hidden_dim=hidden_dim, input_dim=128 + hidden_dim)
+        self.flow_head = FlowHead(hidden_dim, hidden_dim=256)
+        self.mask = nn.Sequential(nn.Conv2d(128, 256, 3, padding=1), nn.ReLU(inplace=True), nn.Conv2d(256, 64 * 9, 1, padding=0))
+
+
+def _args(**kw) -> argparse.Namespace:
+    a = argparse.Namespace(corr_levels=RAFT_CORR_LEVELS, corr_radius=RAFT_CORR_RADIUS, output_dim=None, iters=None, dropout=0.0, mixed_precision=False,
+                           small=False, gpus=[0], multiframe=True, scale_inputs=True, alternate_corr=False)
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+class RAFT(WeightSync, nn.Module):
+    """Drop-in for the reference's `RAFT` (large, inference).  Calls:
+    - multiframe (default): `model(x[B,T,3,H,W], iters=24, backward=False)` -> [B,T-1,2,H,W] pixel flows (flow_up of the last iteration);
+      x is in [0,1] with scale_inputs=True (in [0,255] otherwise); backward=True computes the pairs (x[t+1], x[t]) and returns them in
+      reversed order, as the reference's `flows.insert(0, ...)`.
+    - multiframe=False: `model(image1, image2, iters=24, test_mode=True)` on [B,3,H,W] images in [0,255] -> (coords1 - coords0 [B,2,H/8,W/8],
+      flow_up [B,2,H,W]).
+    `self.iters`, when set, overrides the call's `iters`.  H and W must be multiples of 8 with H/8, W/8 >= 16."""
+
+    def __init__(self, args: Optional[argparse.Namespace] = None):
+        super().__init__()
+        self.args = args if args is not None else _args()
+        if getattr(self.args, "small", False):
+            raise NotImplementedError("RAFT-small (SmallEncoder / SmallUpdateBlock) is not provided: only RAFT-large runs on the GPU")
+        if getattr(self.args, "output_dim", None) is not None:
+            raise NotImplementedError("the output_dim head of RAFT is not provided")
+        if getattr(self.args, "alternate_corr", False):
+            raise NotImplementedError("alternate_corr (the alt_cuda_corr extension) is not provided: the all-pairs correlation runs in the library")
+        self.multiframe = getattr(self.args, "multiframe", True)
+        self.scale_inputs = getattr(self.args, "scale_inputs", True)
+        self.hidden_dim = RAFT_HIDDEN
+        self.context_dim = RAFT_HIDDEN
+        self._iters = getattr(self.args, "iters", None)
+        self.fnet = BasicEncoder(output_dim=256, norm_fn="instance")
+        self.cnet = BasicEncoder(output_dim=self.hidden_dim + self.context_dim, norm_fn="batch")
+        self.update_block = BasicUpdateBlock(hidden_dim=self.hidden_dim)
+        self.output_block = None
+        self._handle: Optional[int] = None
+        self._handle_device: Optional[torch.device] = None
+        self._loaded: Dict[str, Tuple[int, int]] = {}
+        self._init_weight_sync()
+
+    # ---- reference attribute surface -------------------------------------------------------------
+    @property
+    def iters(self):
+        return getattr(self, "_iters", None)
+
+    @iters.setter
+    def iters(self, value=None):
+        self._iters = value
+
+    def set_iters(self, value=None):
+        self.iters = value
+        return self
+
+    def freeze_bn(self):
+        for m in self.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.eval()
+
+    # ---- C-ABI plumbing --------------------------------------------------------------------------
+    def _ensure_handle(self, device: torch.device) -> int:
+        lib = _lib.get_lib()
+        if self._handle is not None and self._handle_device == device:
+            return self._handle
+        self._release()
+        h = C.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(lib.cwm_raft_create(C.byref(h)))
+        self._handle = h.value
+        self._handle_device = device
+        self._loaded = {}
+        return self._handle
+
+    def _release(self):
+        if getattr(self, "_handle", None) is not None:
+            try:
+                _lib.get_lib().cwm_raft_destroy(self._handle)
+            except Exception:
+                pass
+            object.__setattr__(self, "_handle", None)
+            object.__setattr__(self, "_loaded", {})
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def sync_weights(self, device: torch.device, force: bool = False) -> int:
+        """Upload every state-dict tensor that changed since the last call (see `WeightSync`); the library folds the batch norms
+        and packs the convolutions at the next forward."""
+        if not force and self._handle is not None and self._handle_device == device and self._params_unchanged():
+            return 0
+        h = self._ensure_handle(device)
+        lib = _lib.get_lib()
+        if force:
+            self._loaded = {}
+        n = 0
+        with torch.cuda.device(device):
+            for name, p in self.state_dict(keep_vars=True).items():
+                tag = (p.data_ptr(), p._version)
+                if self._loaded.get(name) == tag:
+                    continue
+                t = p.detach()
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    t = t.float().contiguous()
+                if t.is_cuda and t.device != device:
+                    t = t.to(device)
+                shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
+                _lib.check(lib.cwm_raft_load_weight(h, name.encode(), t.data_ptr(), 1 if t.is_cuda else 0, shape, t.dim()))
+                self._loaded[name] = tag
+                n += 1
+        self._remember_params()
+        return n
+
+    def invalidate_weights(self):
+        self._loaded = {}
+        self._plist = None
+
+    def _run(self, x1, x2, B, pairs, H, W, scale, iters, out, out_strides, flow_low=None):
+        dev = x1.device
+        self.sync_weights(dev)
+        a = _lib.new_raft_forward_args()
+        a.image1_dev, a.image2_dev = x1.data_ptr(), x2.data_ptr()
+        a.image1_stride_b, a.image1_stride_t, a.image1_stride_c = x1.stride(0), x1.stride(1), x1.stride(2)
+        a.image2_stride_b, a.image2_stride_t, a.image2_stride_c = x2.stride(0), x2.stride(1), x2.stride(2)
+        a.batch, a.pairs, a.height, a.width = B, pairs, H, W
+        a.input_scale = float(scale)
+        a.iters = int(iters)
+        a.flow_dev = out[0]
+        a.flow_stride_b, a.flow_stride_t, a.flow_stride_c = out_strides
+        a.flow_low_dev = _lib.ptr(flow_low)
+        a.stream = _lib.current_stream_handle(dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.get_lib().cwm_raft_forward(self._handle, C.byref(a)))
+
+    @staticmethod
+    def _frames(x: torch.Tensor) -> torch.Tensor:
+        _lib.require_gpu()
+        if not x.is_cuda:
+            raise RuntimeError("RAFT.forward needs a CUDA/HIP tensor (no CPU fallback); got %s" % x.device)
+        if x.dtype != torch.float32:
+            x = x.float()
+        if x.stride(-1) != 1 or x.stride(-2) != x.shape[-1]:
+            x = x.contiguous()
+        return x
+
+    @torch.no_grad()
+    def _forward_two_images(self, image1, image2, iters=24, flow_init=None, upsample=True, test_mode=True, **kwargs):
+        """raft_model.py:205-274 with test_mode=True: (coords1 - coords0, flow_up) for images in [0,255]."""
+        if flow_init is not None:
+            raise NotImplementedError("flow_init is not supported")
+        if not test_mode:
+            raise NotImplementedError("test_mode=False (the per-iteration flow list of training) is not supported")
+        if self.iters is not None:
+            iters = self.iters
+        x1, x2 = self._frames(image1), self._frames(image2)
+        if x1.dim() != 4 or x1.shape != x2.shape or x1.shape[1] != 3:
+            raise RuntimeError("expected two [B,3,H,W] images of one shape, got %s and %s" % (tuple(image1.shape), tuple(image2.shape)))
+        B, _, H, W = x1.shape
+        up = torch.empty(B, 2, H, W, device=x1.device)
+        low = torch.empty(B, 2, H // 8, W // 8, device=x1.device)
+        v1, v2 = x1.unsqueeze(1), x2.unsqueeze(1)
+        self._run(v1, v2, B, 1, H, W, 1.0, iters, (up.data_ptr(),), (up.stride(0), 0, up.stride(1)), flow_low=low)
+        return low, up
+
+    @torch.no_grad()
+    def forward(self, *args, **kwargs):
+        if not self.multiframe:
+            return self._forward_two_images(*args, **kwargs)
+        x = args[0]
+        iters = args[1] if len(args) > 1 else kwargs.get("iters", 24)
+        if kwargs.get("flow_init") is not None:
+            raise NotImplementedError("flow_init is not supported")
+        if self.iters is not None:
+            iters = self.iters
+        backward = kwargs.get("backward", False)
+        if x.dim() != 5:
+            raise RuntimeError("RAFT (multiframe) expects x [B,T,3,H,W], got %s" % (tuple(x.shape),))
+        x = self._frames(x)
+        B, T, Cc, H, W = x.shape
+        if Cc != 3:
+            raise RuntimeError("RAFT expects 3-channel frames, got %s" % (tuple(x.shape),))
+        scale = 255.0 if self.scale_inputs else 1.0
+        if T == 1:  # a single frame is repeated (raft_model.py:287-288): the pair (x0, x0)
+            first, second, pairs = x, x, 1
+        else:
+            first, second, pairs = x[:, :-1], x[:, 1:], T - 1
+        out = torch.empty(B, pairs, 2, H, W, device=x.device)
+        if backward:  # pairs (x[t+1], x[t]), stored at index pairs - 1 - t
+            first, second = second, first
+            ptr = out.data_ptr() + (pairs - 1) * out.stride(1) * out.element_size()
+            self._run(first, second, B, pairs, H, W, scale, iters, (ptr,), (out.stride(0), -out.stride(1), out.stride(2)))
+        else:
+            self._run(first, second, B, pairs, H, W, scale, iters, (out.data_ptr(),), (out.stride(0), out.stride(1), out.stride(2)))
+        return out
+
+
+def load_raft_model(load_path=default_raft_ckpt, ignore_prefix=None, multiframe=True, scale_inputs=True, output_dim=None, **kwargs):
+    """raft_model.py:55-101: builds RAFT-large and loads a checkpoint (`module.` and `ignore_prefix` stripped from the keys, strict=False)."""
+    if ((load_path is None) or (not os.path.exists(load_path))) and (output_dim is None):
+        print("%s is not a valid raft checkpoint" % load_path)
+        raise ValueError("You must download RAFT checkpoints with cwm/models/raft/download_raft_checkpoints.sh\n"
+                         + "Checkpoints will be downloaded to CounterfactualWorldModels/checkpoints/raft_checkpoints/")
+    if output_dim is not None:
+        raise NotImplementedError("the output_dim head of RAFT is not provided")
+    args = _args(**kwargs)
+    args.multiframe, args.scale_inputs, args.output_dim = multiframe, scale_inputs, output_dim
+    model = RAFT(args)
+    weight_dict = torch.load(load_path, map_location=torch.device("cpu"))
+    new_dict = {}
+    for k in weight_dict.keys():
+        new_dict[k.replace("module.", "") if "module" in k else k] = weight_dict[k]
+    if ignore_prefix is not None:
+        new_dict = {k.replace(ignore_prefix, ""): v for k, v in new_dict.items()}
+    did_load = model.load_state_dict(new_dict, strict=False)
+    print(did_load, type(model).__name__, load_path)
+    return model

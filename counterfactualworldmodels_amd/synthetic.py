@@ -141,3 +141,44 @@ def _synthetic_flow_module():
 
 def SyntheticFlow():  # noqa: N802 -- a class factory, so that importing this module needs no torch
     return _synthetic_flow_module()()
+
+
+def raft_state_dict(seed: int = 0) -> Dict[str, np.ndarray]:
+    """Synthetic RAFT-large weights by key (`synthetic_tensor`), with batch-norm running variances 1 + 5|v|, `num_batches_tracked` 0 and the
+    flow head's last convolution x 0.02: with plain xavier weights the flow grows by several pixels per iteration and after 24 iterations
+    almost every correlation lookup falls outside the pyramid."""
+    from .config import raft_state_dict_schema
+
+    out = {}
+    for k, shp in raft_state_dict_schema().items():
+        if k.endswith("num_batches_tracked"):
+            out[k] = np.zeros((), dtype=np.int64)
+            continue
+        v = synthetic_tensor(k, shp, seed)
+        if k.endswith("running_var"):
+            v = (1.0 + 5.0 * np.abs(v)).astype(np.float32)
+        if k.startswith("update_block.flow_head.conv2."):
+            v = (v * np.float32(0.02)).astype(np.float32)
+        out[k] = v
+    return out
+
+
+def raft_frames(batch: int, height: int, width: int, seed: int = 0, shift: Tuple[int, int] = (3, 5), frames: int = 2) -> np.ndarray:
+    """float32 [B,T,3,H,W] in [0,1): 5x5 box-filtered uniform noise; frame t is the crop of one noise field at t * shift = (dy, dx), so
+    consecutive frames are related by a pure translation (RAFT finds a smooth flow of a few pixels)."""
+    g = np.random.Generator(np.random.PCG64(seed))
+    dy, dx = shift
+    sy, sx = abs(dy) * (frames - 1), abs(dx) * (frames - 1)
+    noise = g.random((batch, 3, height + 4 + sy, width + 4 + sx), dtype=np.float32).astype(np.float64)
+    hh, ww = height + sy, width + sx
+    box = np.zeros((batch, 3, hh, ww), dtype=np.float64)
+    for i in range(5):
+        for j in range(5):
+            box += noise[:, :, i : i + hh, j : j + ww]
+    box = (box / 25.0).astype(np.float32)
+    y0, x0 = (sy if dy < 0 else 0), (sx if dx < 0 else 0)
+    out = np.empty((batch, frames, 3, height, width), dtype=np.float32)
+    for t in range(frames):
+        y, x = y0 + t * dy, x0 + t * dx
+        out[:, t] = box[:, :, y : y + height, x : x + width]
+    return out

@@ -345,6 +345,47 @@ CWM_API int cwm_allgather(cwm_comm* c, const void* send_dev, void* recv_dev, siz
 CWM_API int cwm_allgatherv(cwm_comm* c, const void* send_dev, void* recv_dev, const size_t* offsets, const size_t* counts, void* stream);
 CWM_API int cwm_allreduce_sum_f32(cwm_comm* c, float* buf_dev, size_t count, void* stream);
 
+/* ---- RAFT-large optical flow (0.9) --------------------------------------------------------------------
+ * replaces: `load_raft_model(...)` / `RAFT.forward` of cwm/models/raft/raft_model.py:55-300 in the reference's inference
+ * configuration (BasicEncoder fnet with instance norm, cnet with eval batch norm, 4 correlation levels of radius 4,
+ * BasicUpdateBlock with SepConvGRU, convex upsampling; alternate_corr = False, output_dim = None), in parity (split-bf16)
+ * arithmetic.  Weights: the reference's 179 state-dict keys and shapes (`num_batches_tracked` is accepted and ignored). */
+typedef struct cwm_raft_model cwm_raft_model;
+CWM_API int cwm_raft_create(cwm_raft_model** out);
+CWM_API void cwm_raft_destroy(cwm_raft_model* m);
+CWM_API int cwm_raft_load_weight(cwm_raft_model* m, const char* key, const float* data, int on_device, const int64_t* shape, int ndim);
+CWM_API int cwm_raft_missing_weights(cwm_raft_model* m, char* buf, int buflen);
+
+typedef struct cwm_raft_forward_args {
+    uint32_t struct_size;          /* sizeof(cwm_raft_forward_args) */
+    /* the frame pair (b, t), t < max(pairs, 1): image1 at image1_dev + b*image1_stride_b + t*image1_stride_t, channel c at + c*image1_stride_c,
+     * rows of `width` contiguous (fp32 [3, H, W]); image2 likewise.  The model sees 2 * (v * input_scale / 255) - 1: input_scale 255 for
+     * frames in [0, 1] (the multi-frame call, scale_inputs = True), 1 for frames in [0, 255] (the two-image call) */
+    const float* image1_dev;
+    int64_t image1_stride_b, image1_stride_t, image1_stride_c;
+    const float* image2_dev;
+    int64_t image2_stride_b, image2_stride_t, image2_stride_c;
+    int32_t batch, pairs;
+    int32_t height, width;         /* multiples of 8, H / 8 and W / 8 at least 16 */
+    float input_scale;
+    int32_t iters;                 /* >= 1 */
+    /* out: flow_up of the last iteration, pixels (x, y): element (c, Y, X) of pair (b, t) at flow_dev + b*flow_stride_b + t*flow_stride_t +
+     * c*flow_stride_c + Y*width + X (strides may be negative: the reversed pair order of the backward multi-frame call) */
+    float* flow_dev;
+    int64_t flow_stride_b, flow_stride_t, flow_stride_c;
+    float* flow_low_dev;           /* optional: coords1 - coords0, [batch * pairs, 2, H/8, W/8] contiguous (the two-image call's first output) */
+    void* stream;
+} cwm_raft_forward_args;
+CWM_API int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* args);
+
+/* Stand-alone RAFT kernels (kernel tests; the same launches as the model):
+ *   cwm_raft_corr_lookup      fmap1 / fmap2 [P, h8, w8, 256] (NHWC), coords [P, h8, w8, 2] (x, y) -> out [P, h8, w8, 324]: CorrBlock (corr.py:12-60)
+ *                             built and indexed at coords, feature l*81 + a*9 + b sampled at (x / 2^l + a - 4, y / 2^l + b - 4).  Synchronises.
+ *   cwm_raft_convex_upsample  flow [P, 2, h8, w8], mask [P, h8, w8, 576] (NHWC, already scaled) -> out [P, 2, 8 h8, 8 w8] (RAFT.upsample_flow) */
+CWM_API int cwm_raft_corr_lookup(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev,
+                                 void* stream);
+CWM_API int cwm_raft_convex_upsample(const float* flow_dev, const float* mask_dev, int P, int h8, int w8, float* out_dev, void* stream);
+
 CWM_API const char* cwm_last_error(void);
 /* "cwm_hip <version> gfx950" */
 CWM_API const char* cwm_version(void);

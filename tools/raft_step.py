@@ -1,0 +1,51 @@
+"""Time RAFT-large (counterfactualworldmodels_amd.raft) at 224^2, 24 iterations:  python tools/raft_step.py [--batch 1 8 32] [--steps 10] [--warmup 3]
+
+Reports ms per call, frame pairs/s and algorithmic TFLOP/s on the FLOPs this path computes (config.raft_algorithmic_flops: the mask head
+once, ~122 GFLOP per pair), one JSON line per batch size.  For the kernel split run it once under
+`rocprofv3 --kernel-trace --stats -- python tools/raft_step.py --batch 32 --steps 3`."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from counterfactualworldmodels_amd import config as C, synthetic as S  # noqa: E402
+from counterfactualworldmodels_amd.raft import RAFT  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, nargs="+", default=[1, 8, 32])
+    ap.add_argument("--size", type=int, nargs=2, default=[224, 224])
+    ap.add_argument("--iters", type=int, default=24)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    args = ap.parse_args()
+    H, W = args.size
+    m = RAFT()
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in S.raft_state_dict(0).items()})
+    m = m.cuda().eval()
+    flops = C.raft_algorithmic_flops(H, W, args.iters)
+    for B in args.batch:
+        x = torch.from_numpy(S.raft_frames(B, H, W, 1)).cuda()
+        for _ in range(args.warmup):
+            m(x, iters=args.iters)
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(args.steps):
+            t0 = time.perf_counter()
+            m(x, iters=args.iters)
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        ms = 1e3 * float(np.median(times))
+        print(json.dumps({"batch": B, "size": [H, W], "iters": args.iters, "ms_median": round(ms, 3), "ms_min": round(1e3 * min(times), 3),
+                          "pairs_per_s": round(B / (ms / 1e3), 2), "gflop_per_pair": round(flops / 1e9, 2),
+                          "tflops": round(B * flops / (ms / 1e3) / 1e12, 2)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
