@@ -12,7 +12,7 @@ LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libcwm_hip.so")
 DEV_LIB_PATH = os.path.join(LIB_DIR, "libcwm_hip_dev.so")  # the same objects + csrc/dev.hip (switches, micro-benchmarks: include/cwm_hip_dev.h)
 DEV_SOURCES = ["dev.hip"]
-SOURCES = ["gemm.hip", "attention.hip", "attention_pipe.hip", "elementwise.hip", "conj_kernels.hip", "conj_attention.hip", "flowstats.hip", "engine.hip", "model.hip",
+SOURCES = ["gemm.hip", "attention.hip", "attention_pipe.hip", "elementwise.hip", "conj_kernels.hip", "conj_attention.hip", "flowstats.hip", "flowfilter.hip", "engine.hip", "model.hip",
            "conj_model.hip", "comm.hip",
            "raft_kernels.hip", "raft_model.hip"]
 HEADERS = ["exports.map", "common.h", "kernels.h", "gemm_device.h", "attention_device.h", "attention_tail.h", "engine.h", os.path.join("..", "..", "include", "cwm_hip.h"),

@@ -499,6 +499,19 @@ class PredictorBasedGenerator(nn.Module):
         x_static, _ = self._shift_rows(x, m, torch.ones_like(m), zero, 1, fix_passive="make_static")
         return x_static, mask
 
+    # ---- keypoints (prediction.py:816-828): any module passed as `keypoint_predictor` ---------------------------------------
+    def predict_keypoints_map(self, x, *args, **kwargs):
+        assert x.dim() == 5, x.shape
+        if self.keypoint_predictor is None:
+            return torch.ones_like(x[:, 0:1, 0:1])
+        return self.keypoint_predictor(x, *args, **kwargs)
+
+    def predict_keypoints_distribution(self, x, power=8, eps=1e-3):
+        value = self.predict_keypoints_map(x).squeeze(-3)
+        value = (value.sigmoid()) ** power
+        value = value - value.amin((-2, -1))
+        return value / value.amax((-2, -1)).clamp(min=eps)
+
     def forward(self, x, mask=None, frame=None, *args, **kwargs):
         self.set_input(x, mask)
         if mask is None:

@@ -7,17 +7,20 @@ re-rectangularises and synchronises per chunk.  Here the whole prompt set is ONE
 mask come out of one pair of HIP kernels (`cwm_shift_prompts`), the masks are rectangularised once (the reference's single
 `mask_rectangularizer` call at segmentation.py:342: same global-RNG consumption, one host read-back), and the predictor then
 runs over row ranges of that batch with the masked count already known -- no further host round trip until the result is
-used.  The optical-flow model that follows in the reference (RAFT) is outside this package; any module with the reference's
-`flow_model(video, backward=...)` call signature can be plugged in.
+used.  The optical-flow model that follows in the reference is any module with the reference's `flow_model(video, backward=...)`
+call signature (this package's `raft.RAFT`, or a stand-in).  `sample_counterfactual_motion_map` (segmentation.py:434-477) puts the
+patch samplers and the flow-sample filter of `sampling.py` around that driver.
 """
 from __future__ import annotations
 
+import copy
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from .prediction import PredictorBasedGenerator, _RectBatch
+from .sampling import FlowSampleFilter, RotatedTableEnergyMaskingGenerator, boltzmann
 
 
 def _shift_list(shifts, num: int) -> List[Tuple[int, int]]:
@@ -43,12 +46,83 @@ def _shift_list(shifts, num: int) -> List[Tuple[int, int]]:
 class FlowGenerator(PredictorBasedGenerator):
     """Counterfactual videos (and, with a flow model, flows) from moving patches; reference class segmentation.py:62."""
 
-    def __init__(self, *args, flow_model=None, flow_model_load_path=None, raft_iters=None, **kwargs):
+    # segmentation.py:29-41
+    default_flow_filter_params = {"filter_methods": ["patch_magnitude", "flow_area", "num_corners"], "flow_magnitude_threshold": 5.0,
+                                  "flow_area_threshold": 0.75, "num_corners_threshold": 2}
+    default_patch_sampling_kwargs = {"energy_power": 1, "eps": 1e-16, "pool_mode": "mean", "resize": False}
+    _DEFAULT_FILTER = object()  # (the reference's default argument is one filter instance shared by every generator; here each gets its own)
+
+    def __init__(self, *args, flow_model=None, flow_model_load_path=None, raft_iters=None, flow_sample_filter=_DEFAULT_FILTER,
+                 flow_sample_filter_params=None, patch_sampling_func=RotatedTableEnergyMaskingGenerator, patch_sampling_kwargs=None, **kwargs):
         super().__init__(*args, **kwargs)
         self.flow_model = flow_model
         if flow_model is not None and flow_model_load_path is not None:
             self.load_predictor(flow_model_load_path, model=flow_model)
         self.raft_iters = raft_iters
+        # the filter of the flow samples (segmentation.py:62-63)
+        if flow_sample_filter is self._DEFAULT_FILTER:
+            flow_sample_filter = FlowSampleFilter(**(flow_sample_filter_params or self.default_flow_filter_params))
+        self.flow_sample_filter = flow_sample_filter
+        # the patch sampler (segmentation.py:65-69); creating it draws `rng.randint(9999)`, as in the reference
+        self._patch_sampling_func = patch_sampling_func
+        self._patch_sampling_kwargs = copy.deepcopy(self.default_patch_sampling_kwargs)
+        self._patch_sampling_kwargs.update(patch_sampling_kwargs or {})
+        self.set_patch_sampler()
+
+    # ---- patch sampling and the sample filter (segmentation.py:92-128) ------------------------------------------------------
+    def set_flow_sample_filter(self, params=None):
+        self.flow_sample_filter = None if params is None else FlowSampleFilter(**params)
+
+    def set_patch_sampler(self, num_visible=1, mask_ratio=None, **kwargs):
+        """(Re)create the sampler when there is none or keyword arguments are given -- each creation consumes one `self.rng.randint(9999)` --,
+        then set its mask ratio or its number of visible (clumped) patches."""
+        if (getattr(self, "patch_sampler", None) is None) or len(kwargs.keys()):
+            _kwargs = copy.deepcopy(self._patch_sampling_kwargs)
+            _kwargs.update(kwargs)
+            try:
+                mask_shape = self.mask_shape
+            except Exception:
+                mask_shape = self.predictor.mask_size
+            self.patch_sampler = self._patch_sampling_func(input_size=mask_shape, mask_ratio=(mask_ratio or 0), seed=self.rng.randint(9999),
+                                                           always_batch=True, **_kwargs)
+        if mask_ratio is not None:
+            self.patch_sampler.mask_ratio = mask_ratio
+        elif num_visible is not None:
+            self.patch_sampler.num_visible = num_visible * self.patch_sampler.clumping_factor ** 2
+
+    def sample_patches_from_energy(self, energy=None, num_samples=10, num_visible=1, beta=None, **kwargs):
+        """[B,Nt,S] bool masks (0 = visible) with `num_visible` (clumped) patches of the last frame drawn from `energy` [B,1,H,W] (None: uniform)."""
+        self.set_patch_sampler(num_visible, **kwargs)
+        if num_visible == 0:
+            return torch.stack([self.get_zeros_mask() for _ in range(num_samples)], -1)
+        if energy is None:
+            assert self.x is not None
+            energy = torch.ones_like(self.x[:, 0, 0:1])
+        energy = boltzmann(energy, beta)
+        torch.manual_seed(self.rng.randint(99999))
+        return torch.stack([self.patch_sampler(energy) for _ in range(num_samples)], -1)
+
+    def sample_counterfactual_motion_map(self, x, active_sampling_distribution=None, passive_sampling_distribution=None, active_patches=None,
+                                         passive_patches=None, num_active_patches=1, num_passive_patches=0, num_samples=8, sample_batch_size=8,
+                                         patch_sampling_kwargs={}, do_filter=True, **kwargs):
+        """(flows [B,2,H,W,S], active_patches, passive_patches): S counterfactual flows of x, the samples in which nothing or everything
+        moved zeroed by the `flow_sample_filter` (segmentation.py:434-477).  The flow model's output goes to the filter as the
+        `_batch_to_samples` view; the only full-size write is the contiguous result."""
+        self.set_input(x)
+
+        def _sample_patches(dist, num_visible):
+            return self.sample_patches_from_energy(energy=dist, num_samples=num_samples, num_visible=num_visible, **patch_sampling_kwargs)
+
+        if active_patches is None:
+            active_patches = _sample_patches(active_sampling_distribution, num_active_patches)
+        if passive_patches is None:
+            passive_patches = _sample_patches(passive_sampling_distribution, num_passive_patches)
+        ys, flows = self.predict_counterfactual_videos_and_flows(x, active_patches=active_patches, passive_patches=passive_patches,
+                                                                 num_samples=num_samples, sample_batch_size=sample_batch_size, fix_passive=True, **kwargs)
+        flows = self._batch_to_samples(flows)
+        if (self.flow_sample_filter is not None) and do_filter:
+            flows, filter_mask = self.flow_sample_filter(flows, active_patches)
+        return (flows, active_patches, passive_patches)
 
     # ---- flow model hook (segmentation.py:141-153) -------------------------------------------------------------------
     def set_raft_iters(self, iters=None):

@@ -182,3 +182,53 @@ def raft_frames(batch: int, height: int, width: int, seed: int = 0, shift: Tuple
         y, x = y0 + t * dy, x0 + t * dx
         out[:, t] = box[:, :, y : y + height, x : x + width]
     return out
+
+
+def blob_flow_samples(size: int, seed: int, blobs: np.ndarray, noise: float = 0.3, scaled_pixels=None, nan_pixels=None) -> np.ndarray:
+    """float32 [B,2,H,W,S] flow samples for the flow-sample filter: uniform background noise in [-noise, noise) from PCG64(seed) plus, per
+    (b, s), the blobs `blobs[b, s, k] = (cy, cx, r, ay, ax)` (r <= 0: unused): (ay, ax) / (1 + d^2 / r^2) added to (channel 1, channel 0).
+
+    Only exactly rounded float32 operations are used (add, multiply, divide), so every host regenerates the same bits (`flow_checksum`).
+    `scaled_pixels` [n,4] rows (b, s, y, x): both components multiplied by 1 + 1e-5 (a fixture's way of moving a magnitude off a threshold);
+    `nan_pixels` [n,4]: both components NaN."""
+    blobs = np.asarray(blobs, dtype=np.float32)
+    B, S = blobs.shape[:2]
+    g = np.random.Generator(np.random.PCG64(seed))
+    two, one = np.float32(2.0), np.float32(1.0)
+    out = (g.random((B, 2, size, size, S), dtype=np.float32) * two - one) * np.float32(noise)
+    yy = np.arange(size, dtype=np.float32)[:, None]
+    xx = np.arange(size, dtype=np.float32)[None, :]
+    for b in range(B):
+        for s in range(S):
+            for cy, cx, r, ay, ax in blobs[b, s]:
+                if r <= 0:
+                    continue
+                dy, dx = yy - cy, xx - cx
+                fall = one / (one + (dy * dy + dx * dx) / (r * r))
+                out[b, 0, :, :, s] += ax * fall
+                out[b, 1, :, :, s] += ay * fall
+    if scaled_pixels is not None:
+        for b, s, y, x in np.asarray(scaled_pixels, dtype=np.int64).reshape(-1, 4):
+            out[b, :, y, x, s] *= np.float32(1.0 + 1e-5)
+    if nan_pixels is not None:
+        for b, s, y, x in np.asarray(nan_pixels, dtype=np.int64).reshape(-1, 4):
+            out[b, :, y, x, s] = np.nan
+    return out
+
+
+def flow_checksum(flows: np.ndarray) -> str:
+    """sha256 of the float32 bytes of `flows` in C order."""
+    import hashlib
+
+    return hashlib.sha256(np.ascontiguousarray(flows, dtype=np.float32).tobytes()).hexdigest()
+
+
+def sampler_energy(batch: int, side: int, seed: int, one_hot: bool = False) -> np.ndarray:
+    """float32 [B,1,side,side] energy map for the patch samplers: uniform in [0,1), or all zero but one pixel per image."""
+    g = np.random.Generator(np.random.PCG64(seed))
+    if one_hot:
+        e = np.zeros((batch, 1, side, side), dtype=np.float32)
+        for b in range(batch):
+            e[b, 0, g.integers(side), g.integers(side)] = 1.0
+        return e
+    return g.random((batch, 1, side, side), dtype=np.float32)

@@ -318,6 +318,40 @@ CWM_API int cwm_flow_motion_sum(const float* flows_dev, const int64_t* strides, 
                         int normalize_per_sample, float eps, float* minmax_work_dev, float* sum_dev, void* stream);
 CWM_API int cwm_flow_map_finish(float* map_dev, int B, int HW, float scale, int normalize, float eps, void* stream);
 
+/* ---- the flow-sample filter (0.10): which of the S counterfactual flow samples are kept ------------------------------
+ * replaces: cwm/models/sampling.py FlowSampleFilter.compute_flow_magnitude :163-205, filter_by_patch_magnitude :207-215,
+ *           filter_by_flow_area :217-228, filter_by_num_corners :230-250 and forward :252-286
+ * flows: as above, [B,2,H,W,S] by five element strides (H == W, as the reference asserts).  Coalesced for the sample-outermost view of the
+ * flow model's [(b s),1,2,H,W] output (every (b,s,c) plane H W contiguous floats) and for the packed sample-innermost layout; any other
+ * strides take a strided form.  active: the bool / uint8 mask [B,Np,S] (0 = active) by three element strides, Np = 2 h w patches of two frames,
+ * h = w = int((Np/2)**0.5); only frame 2 (rows h w .. Np-1) is read.
+ *
+ * cwm_flow_filter_stats  per (b, s), all [B][S] contiguous:
+ *     patch_mag     fp32: mean over the active patches of frame 2 of the bilinearly resized (F.interpolate(size=[h,w], mode='bilinear'),
+ *                   align_corners=False, no antialiasing: source max((dst+.5) H/h - .5, 0), neighbours clamped to the last row / column)
+ *                   magnitude sqrt(u^2 + v^2), evaluated at the active patches only; an empty active set gives 0 / 1e-12 = 0.  (The
+ *                   reference multiplies the whole resized map by the 0/1 mask, so a NaN under an INACTIVE patch's taps makes its
+ *                   patch_mag NaN; here only a NaN under an active patch does.)  Summed in a fixed order: bitwise reproducible.
+ *     area_count    int32: #pixels with magnitude > flow_magnitude_threshold (the reference's flow_area is area_count / (H W))
+ *     corner_count  int32: how many of the four corner pixels exceed the threshold
+ *     reject        uint8: the OR over the enabled `methods` bits of  patch_mag < flow_magnitude_threshold,
+ *                   area_count / (H W) > flow_area_threshold,  corner_count >= num_corners_threshold  (NaN compares false, as in torch)
+ *   The streaming pass reads every flow element once; the patch mean then reads the 8 floats under each active patch's four taps.
+ * cwm_flow_filter_apply  zeroes, in place, both channels of every sample with reject != 0; reads no flow element and writes no other byte.
+ * cwm_flow_filter_pack   out[B][2][H][W][S] (contiguous) = the sample-outermost flows with rejected samples as zeros (not read): the packed tensor
+ *                   `forward` returns (`flow_samples.contiguous()`, :286).  Every sample must be one contiguous [2,H,W] block.
+ * CWM_ERR_INVALID: C != 2, H != W, Np odd or not 2 h w, S < 1, a null pointer, unknown method bits.  All asynchronous on `stream`. */
+#define CWM_FLOW_FILTER_PATCH_MAGNITUDE 1
+#define CWM_FLOW_FILTER_FLOW_AREA 2
+#define CWM_FLOW_FILTER_NUM_CORNERS 4
+CWM_API int cwm_flow_filter_stats(const float* flows_dev, const int64_t* strides, int B, int C, int H, int W, int S, const uint8_t* active_dev,
+                          const int64_t* active_strides, int Np, int methods, float flow_magnitude_threshold, float flow_area_threshold,
+                          float num_corners_threshold, float* patch_mag_dev, int32_t* area_count_dev, int32_t* corner_count_dev,
+                          uint8_t* reject_dev, void* stream);
+CWM_API int cwm_flow_filter_apply(float* flows_dev, const int64_t* strides, int B, int C, int H, int W, int S, const uint8_t* reject_dev, void* stream);
+CWM_API int cwm_flow_filter_pack(const float* flows_dev, const int64_t* strides, int B, int C, int H, int W, int S, const uint8_t* reject_dev,
+                         float* out_dev, void* stream);
+
 /* ---- collectives around the sharded counterfactual-sampling loop (SURVEY.md 8e / 8b "comm"; BASELINE configs[3]) ----------
  * The reference has no multi-GPU code: it chunks the S prompts of one frame pair over ONE device (prediction.py:513-540,
  * segmentation.py:423-430).  Here the prompts are sharded over one process per GPU and these entry points are the only
