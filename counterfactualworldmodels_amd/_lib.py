@@ -159,6 +159,10 @@ class CwmRaftForwardArgs(C.Structure):
         ("flow_stride_c", C.c_int64),
         ("flow_low_dev", C.c_void_p),
         ("stream", C.c_void_p),
+        ("head_dev", C.c_void_p),  # appended in 0.10.1 (the output head)
+        ("head_stride_b", C.c_int64),
+        ("head_stride_t", C.c_int64),
+        ("head_stride_c", C.c_int64),
     ]
 
 
@@ -253,6 +257,8 @@ SIGNATURES = {
     "cwm_raft_forward": (C.c_int, [C.c_void_p, C.POINTER(CwmRaftForwardArgs)]),
     "cwm_raft_corr_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_raft_convex_upsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cwm_raft_head_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "cwm_raft_convex_upsample1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_last_error": (C.c_char_p, []),
     "cwm_version": (C.c_char_p, []),
     "cwm_source_hash": (C.c_char_p, []),

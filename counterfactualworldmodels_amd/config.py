@@ -287,8 +287,9 @@ def _raft_encoder_schema(pre: str, norm: str, out_dim: int, out: "OrderedDict[st
     conv("conv2", out_dim, 128, 1)
 
 
-def raft_state_dict_schema() -> "OrderedDict[str, tuple]":
-    """State-dict names -> shapes of RAFT-large in the reference's order (179 tensors, `num_batches_tracked` included)."""
+def raft_state_dict_schema(output_dim=None) -> "OrderedDict[str, tuple]":
+    """State-dict names -> shapes of RAFT-large in the reference's order (179 tensors, `num_batches_tracked` included); with `output_dim`
+    the four tensors of `output_block` (raft_model.py:152-159: the keypoint head) follow, 183 in all."""
     s: "OrderedDict[str, tuple]" = OrderedDict()
     _raft_encoder_schema("fnet.", "instance", 256, s)
     _raft_encoder_schema("cnet.", "batch", 2 * RAFT_HIDDEN, s)
@@ -301,6 +302,11 @@ def raft_state_dict_schema() -> "OrderedDict[str, tuple]":
                                ("mask.0", 256, 128, 3, 3), ("mask.2", 576, 256, 1, 1)):
         s["update_block." + name + ".weight"] = (n, c, kh, kw)
         s["update_block." + name + ".bias"] = (n,)
+    if output_dim is not None:
+        s["output_block.0.weight"] = (256, RAFT_HIDDEN, 3, 3)
+        s["output_block.0.bias"] = (256,)
+        s["output_block.2.weight"] = (int(output_dim), 256, 1, 1)
+        s["output_block.2.bias"] = (int(output_dim),)
     return s
 
 

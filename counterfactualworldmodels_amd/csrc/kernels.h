@@ -337,5 +337,20 @@ int launch_gru_update(float* h, const float* zr, const float* q, int64_t M, hipS
 int launch_flow_update(float* coords, const float* delta, int ld, int64_t M, hipStream_t s);
 int launch_convex_upsample(const ConvexUpParams& p, hipStream_t s);
 int launch_flow_low(const float* coords, int P, int h8, int w8, float* out, hipStream_t s);
+// The output head (raft_model.py:152-159, 257-267; output_dim = 1).  launch_head_project: value[m] = bias[0] + sum_c w[c] * relu(hidden[m * ld + c]) over
+// the 256 channels of output_block.0's result, fp32, one wave per low-resolution pixel.  launch_convex_upsample1: RAFT.upsample_flow of that planar
+// one-channel map (times 8, as a flow) with the 9 x 64 softmax mask.
+struct ConvexUp1Params {
+    const float* value;   // [P][h8][w8]
+    const float* mask;    // [P][h8][w8][mask_ld]: channel k*64 + i*8 + j, times mask_scale
+    int mask_ld;
+    float mask_scale;
+    int P, ppg, h8, w8;
+    float* out;           // pair pr = (g, t): out + g * out_sb + t * out_st + Y * 8w8 + X
+    int64_t out_sb, out_st;
+};
+constexpr int kHeadHidden = 256;
+int launch_head_project(const float* hidden, int ld, const float* w, const float* bias, int64_t M, float* value, hipStream_t s);
+int launch_convex_upsample1(const ConvexUp1Params& p, hipStream_t s);
 
 }  // namespace cwm

@@ -334,6 +334,59 @@ __global__ void flow_low_kernel(const float* coords, int P, int h8, int w8, floa
     }
 }
 
+// output_block.2 on relu(output_block.0(net)): one wave per low-resolution pixel, four consecutive channels per lane (one 16-byte load of the
+// row and of the weight each), the 256 products summed in fp32 by the wave butterfly.
+__global__ void __launch_bounds__(256) head_project_kernel(const float* hidden, int ld, const float* w, const float* bias, int64_t M, float* value) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wpb = blockDim.x / kWave;
+    const float4 wv = reinterpret_cast<const float4*>(w)[lane];
+    const float b = bias[0];
+    for (int64_t m = (int64_t)blockIdx.x * wpb + threadIdx.x / kWave; m < M; m += (int64_t)gridDim.x * wpb) {
+        const float4 v = *reinterpret_cast<const float4*>(hidden + m * ld + 4 * lane);
+        float acc = fmaxf(v.x, 0.f) * wv.x;
+        acc = fmaf(fmaxf(v.y, 0.f), wv.y, acc);
+        acc = fmaf(fmaxf(v.z, 0.f), wv.z, acc);
+        acc = fmaf(fmaxf(v.w, 0.f), wv.w, acc);
+        acc = wave_sum(acc);
+        if (lane == 0) value[m] = acc + b;
+    }
+}
+
+// RAFT.upsample_flow of a one-channel planar map: out[8y+i, 8x+j] = sum_k softmax_k(mask[k*64 + i*8 + j]) * 8 value[y+ky-1, x+kx-1]
+__global__ void convex_upsample1_kernel(const ConvexUp1Params p) {
+    const int H = 8 * p.h8, W = 8 * p.w8;
+    const int64_t total = (int64_t)p.P * H * W;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int pr = (int)(i / ((int64_t)H * W));
+        const int q = (int)(i - (int64_t)pr * H * W), Y = q / W, X = q - Y * W;
+        const int y = Y >> 3, x = X >> 3, sub = (Y & 7) * 8 + (X & 7);
+        const int64_t pix = ((int64_t)pr * p.h8 + y) * p.w8 + x;
+        const float* mk = p.mask + pix * p.mask_ld + sub;
+        float e[9], mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            e[k] = mk[k * 64] * p.mask_scale;
+            mx = fmaxf(mx, e[k]);
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            e[k] = expf(e[k] - mx);
+            s += e[k];
+        }
+        float o = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
+            float f = 0.f;
+            if (yy >= 0 && yy < p.h8 && xx >= 0 && xx < p.w8) f = 8.f * p.value[((int64_t)pr * p.h8 + yy) * p.w8 + xx];
+            o += (e[k] / s) * f;
+        }
+        const int g = pr / p.ppg, t = pr - g * p.ppg;
+        p.out[g * p.out_sb + t * p.out_st + (int64_t)Y * W + X] = o;
+    }
+}
+
 unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 1 << 20); }
 
 }  // namespace
@@ -424,6 +477,20 @@ int launch_convex_upsample(const ConvexUpParams& p, hipStream_t s) {
 
 int launch_flow_low(const float* coords, int P, int h8, int w8, float* out, hipStream_t s) {
     hipLaunchKernelGGL(flow_low_kernel, dim3(grid_for((int64_t)2 * P * h8 * w8)), dim3(256), 0, s, coords, P, h8, w8, out);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_head_project(const float* hidden, int ld, const float* w, const float* bias, int64_t M, float* value, hipStream_t s) {
+    CWM_REQUIRE(ld >= kHeadHidden && ld % 4 == 0 && ((uintptr_t)hidden & 15) == 0 && ((uintptr_t)w & 15) == 0,
+                "head_project: rows of %d floats and 16-byte aligned operands are required (ld = %d)", kHeadHidden, ld);
+    hipLaunchKernelGGL(head_project_kernel, dim3(grid_for(M * kWave)), dim3(256), 0, s, hidden, ld, w, bias, M, value);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_convex_upsample1(const ConvexUp1Params& p, hipStream_t s) {
+    hipLaunchKernelGGL(convex_upsample1_kernel, dim3(grid_for((int64_t)p.P * 64 * p.h8 * p.w8)), dim3(256), 0, s, p);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }

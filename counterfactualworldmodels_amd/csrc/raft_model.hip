@@ -2,7 +2,9 @@
 // configuration -- BasicEncoder fnet (instance norm) and cnet (eval batch norm, folded into the convolutions at load), 4-level all-pairs
 // correlation of radius 4, BasicUpdateBlock with SepConvGRU, convex upsampling.  Every convolution is an im2col (raft_kernels.hip) and a
 // parity (split-bf16) GEMM on launch_gemm whose fp32 epilogue writes straight into a channel slice of an NHWC buffer.  The mask head and
-// the upsampling run once, after the last iteration (the reference computes them every iteration and returns the last).
+// the upsampling run once, after the last iteration (the reference computes them every iteration and returns the last).  So does the optional
+// output head (raft_model.py:152-159, output_dim = 1: the keypoint predictor): output_block.0 as one more 3x3 convolution, then the 256 -> 1
+// projection and the one-channel convex upsampling as kernels of their own (raft_kernels.hip).
 #include <stddef.h>
 
 #include "engine.h"
@@ -22,6 +24,7 @@ struct Raw {
     float* dev = nullptr;
     bool loaded = false;
     bool required = true;
+    bool head = false;  // output_block.*: loaded only by models with the output head; not counted as missing
 };
 
 struct ConvPart {
@@ -71,6 +74,9 @@ __global__ void pack_bias_kernel(const float* b, const float* gamma, const float
     dst[n] = gamma ? (b[n] - mean[n]) * (gamma[n] / sqrtf(var[n] + eps)) + beta[n] : b[n];
 }
 
+// the output head's state-dict keys, in the reference's order
+const char* const kHeadKeys[4] = {"output_block.0.weight", "output_block.0.bias", "output_block.2.weight", "output_block.2.bias"};
+
 ConvSrc src_of(const float* p, int C, const float* stats = nullptr, int relu = 0, int ld = 0) {
     ConvSrc s;
     memset(&s, 0, sizeof(s));
@@ -90,7 +96,7 @@ struct cwm_raft_model {
     std::vector<RaftConv*> convs;
     bool dirty = true;
     Encoder fnet, cnet;
-    RaftConv convc1, convc2, convf1, convf2, conv, zr[2], q[2], fh1, fh2, mask0, mask2;
+    RaftConv convc1, convc2, convf1, convf2, conv, zr[2], q[2], fh1, fh2, mask0, mask2, out0;
     // workspace (cached by shape)
     int ws_P = 0, ws_H = 0, ws_W = 0;
     float *enc_act[4] = {nullptr, nullptr, nullptr, nullptr}, *enc_stats[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -175,6 +181,7 @@ int prepare(cwm_raft_model* m) {
     CWM_REQUIRE(missing == 0, "cwm_raft_forward: %d weights missing (first: %s)", missing, buf);
     for (RaftConv* cv : m->convs) {
         int row0 = 0;
+        if (!m->raw[cv->parts[0].w].loaded || !m->raw[cv->parts[0].b].loaded) continue;  // output_block.0 of a model without the head
         for (auto& p : cv->parts) {
             const float *g = nullptr, *be = nullptr, *mu = nullptr, *var = nullptr;
             if (!p.bn.empty()) {
@@ -376,7 +383,7 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a) {
         if ((rc = run_conv(m, m->fh2, im2col_of(src_of(m->fh, 256, nullptr, 1)), P, h8, w8, m->updA, m->d, 16, s))) return rc;
         if ((rc = launch_flow_update(m->coords, m->d, 16, M, s))) return rc;
     }
-    // mask = 0.25 * mask.2(relu(mask.0(net))), once; convex upsampling of the last flow
+    // mask = 0.25 * mask.2(relu(mask.0(net))), once; convex upsampling of the last flow (skipped when only the head output is asked for)
     if ((rc = run_conv(m, m->mask0, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, s))) return rc;
     if ((rc = run_conv(m, m->mask2, im2col_of(src_of(m->fh, 256, nullptr, 1)), P, h8, w8, m->updA, m->mask, 576, s))) return rc;
     ConvexUpParams up;
@@ -393,8 +400,28 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a) {
     up.out_sb = a.flow_stride_b;
     up.out_st = a.flow_stride_t;
     up.out_sc = a.flow_stride_c;
-    if ((rc = launch_convex_upsample(up, s))) return rc;
+    if (a.flow_dev && (rc = launch_convex_upsample(up, s))) return rc;
     if (a.flow_low_dev && (rc = launch_flow_low(m->coords, P, h8, w8, a.flow_low_dev, s))) return rc;
+    if (a.head_dev) {
+        // out = output_block.2(relu(output_block.0(net))), upsampled with the same mask in place of the flow (raft_model.py:257-267).  `fh` is free
+        // once mask.2 has read it, and `d` (the flow head's delta) once the last flow update has: the projected map goes there.
+        if ((rc = run_conv(m, m->out0, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, s))) return rc;
+        if ((rc = launch_head_project(m->fh, 256, m->raw[kHeadKeys[2]].dev, m->raw[kHeadKeys[3]].dev, M, m->d, s))) return rc;
+        ConvexUp1Params u1;
+        memset(&u1, 0, sizeof(u1));
+        u1.value = m->d;
+        u1.mask = m->mask;
+        u1.mask_ld = 576;
+        u1.mask_scale = 0.25f;
+        u1.P = P;
+        u1.ppg = ppg;
+        u1.h8 = h8;
+        u1.w8 = w8;
+        u1.out = a.head_dev;
+        u1.out_sb = a.head_stride_b;
+        u1.out_st = a.head_stride_t;
+        if ((rc = launch_convex_upsample1(u1, s))) return rc;
+    }
     return 0;
 }
 
@@ -426,6 +453,10 @@ extern "C" int cwm_raft_create(cwm_raft_model** out) {
             (rc = make_conv(m, m->mask0, {part("mask.0", 256)}, 128, 3, 3, 1, 1, 1)) ||
             (rc = make_conv(m, m->mask2, {part("mask.2", 576)}, 256, 1, 1, 1, 0, 0)))
             break;
+        if ((rc = make_conv(m, m->out0, {ConvPart{kHeadKeys[0], kHeadKeys[1], "", kHeadHidden}}, 128, 3, 3, 1, 1, 1))) break;
+        add_raw(m, kHeadKeys[2], {1, kHeadHidden, 1, 1});
+        add_raw(m, kHeadKeys[3], {1});
+        for (const char* k : kHeadKeys) m->raw[k].head = true;
         for (auto& kv : m->raw)
             if ((rc = m->eng.alloc((void**)&kv.second.dev, (size_t)std::max<int64_t>(kv.second.numel, 1) * sizeof(float), true, false))) break;
     } while (0);
@@ -462,7 +493,7 @@ extern "C" int cwm_raft_missing_weights(cwm_raft_model* m, char* buf, int buflen
     int missing = 0;
     if (buf && buflen > 0) buf[0] = 0;
     for (auto& kv : m->raw)
-        if (kv.second.required && !kv.second.loaded) {
+        if (kv.second.required && !kv.second.head && !kv.second.loaded) {
             if (!missing && buf && buflen > 0) snprintf(buf, buflen, "%s", kv.first.c_str());
             ++missing;
         }
@@ -471,11 +502,15 @@ extern "C" int cwm_raft_missing_weights(cwm_raft_model* m, char* buf, int buflen
 
 extern "C" int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* args) {
     CWM_REQUIRE(m && args, "cwm_raft_forward: null argument");
-    CWM_REQUIRE(args->struct_size >= sizeof(cwm_raft_forward_args) && args->struct_size <= 4096,
-                "cwm_raft_forward: args->struct_size = %u is not a cwm_raft_forward_args", args->struct_size);
-    const cwm_raft_forward_args& a = *args;
+    // a caller built against the 0.10.0 header (the struct ended at `stream`) passes that size: the fields appended since read as zero
+    CWM_REQUIRE(args->struct_size >= offsetof(cwm_raft_forward_args, stream) + sizeof(void*) && args->struct_size <= 4096,
+                "cwm_raft_forward: args->struct_size = %u is not a cwm_raft_forward_args (set it to sizeof(cwm_raft_forward_args))", args->struct_size);
+    cwm_raft_forward_args a_copy;
+    memset(&a_copy, 0, sizeof(a_copy));
+    memcpy(&a_copy, args, std::min<size_t>(args->struct_size, sizeof(a_copy)));
+    const cwm_raft_forward_args& a = a_copy;
     if (int rc = cwm_require_device(m->eng.device, "cwm_raft_forward")) return rc;
-    CWM_REQUIRE(a.image1_dev && a.image2_dev && a.flow_dev, "cwm_raft_forward: image1, image2 and flow are required");
+    CWM_REQUIRE(a.image1_dev && a.image2_dev && (a.flow_dev || a.head_dev), "cwm_raft_forward: image1, image2 and one of flow / head are required");
     CWM_REQUIRE(a.batch >= 1 && a.pairs >= 0, "cwm_raft_forward: batch = %d, pairs = %d", a.batch, a.pairs);
     CWM_REQUIRE(a.height > 0 && a.width > 0 && a.height % 8 == 0 && a.width % 8 == 0, "cwm_raft_forward: H = %d and W = %d must be multiples of 8",
                 a.height, a.width);
@@ -488,6 +523,8 @@ extern "C" int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* 
     char buf[256];
     const int missing = cwm_raft_missing_weights(m, buf, sizeof(buf));
     CWM_REQUIRE(missing == 0, "cwm_raft_forward: %d weights missing (first: %s)", missing, buf);
+    if (a.head_dev)
+        for (const char* k : kHeadKeys) CWM_REQUIRE(m->raw[k].loaded, "cwm_raft_forward: the output head was asked for (head_dev) but %s is not loaded", k);
     return forward(m, a);
 }
 
@@ -544,4 +581,26 @@ extern "C" int cwm_raft_convex_upsample(const float* flow_dev, const float* mask
     up.out_sb = (int64_t)2 * 64 * h8 * w8;
     up.out_sc = (int64_t)64 * h8 * w8;
     return launch_convex_upsample(up, (hipStream_t)stream);
+}
+
+extern "C" int cwm_raft_head_project(const float* hidden_dev, const float* weight_dev, const float* bias_dev, int64_t M, float* value_dev, void* stream) {
+    CWM_REQUIRE(hidden_dev && weight_dev && bias_dev && value_dev && M > 0, "cwm_raft_head_project: bad argument");
+    return launch_head_project(hidden_dev, kHeadHidden, weight_dev, bias_dev, M, value_dev, (hipStream_t)stream);
+}
+
+extern "C" int cwm_raft_convex_upsample1(const float* value_dev, const float* mask_dev, int P, int h8, int w8, float* out_dev, void* stream) {
+    CWM_REQUIRE(value_dev && mask_dev && out_dev && P > 0 && h8 > 0 && w8 > 0, "cwm_raft_convex_upsample1: bad argument");
+    ConvexUp1Params up;
+    memset(&up, 0, sizeof(up));
+    up.value = value_dev;
+    up.mask = mask_dev;
+    up.mask_ld = 576;
+    up.mask_scale = 1.f;
+    up.P = P;
+    up.ppg = 1;
+    up.h8 = h8;
+    up.w8 = w8;
+    up.out = out_dev;
+    up.out_sb = (int64_t)64 * h8 * w8;
+    return launch_convex_upsample1(up, (hipStream_t)stream);
 }

@@ -9,6 +9,12 @@ CPU fallback.  The configuration is the reference's inference one: BasicEncoder 
     flow_model = load_raft_model("raft-large.pth").cuda().eval()
     flows = flow_model(x, iters=24)              # x [B,T,3,H,W] in [0,1] -> [B,T-1,2,H,W] pixels
     flows_back = flow_model(x, backward=True)    # pairs (x[t+1], x[t]), in reversed order
+
+With `output_dim=1` the model owns the reference's `output_block` (raft_model.py:152-159; 183 state-dict tensors) and returns its convex-upsampled
+value in place of the flow: the keypoint predictor of the demo notebook,
+
+    keypoint_predictor = load_raft_model(None, output_dim=1)   # then load_state_dict(checkpoint['model'])
+    keypoints = keypoint_predictor.cuda()(x)                   # [B,T-1,1,H,W]
 """
 from __future__ import annotations
 
@@ -119,15 +125,18 @@ class RAFT(WeightSync, nn.Module):
       reversed order, as the reference's `flows.insert(0, ...)`.
     - multiframe=False: `model(image1, image2, iters=24, test_mode=True)` on [B,3,H,W] images in [0,255] -> (coords1 - coords0 [B,2,H/8,W/8],
       flow_up [B,2,H,W]).
-    `self.iters`, when set, overrides the call's `iters`.  H and W must be multiples of 8 with H/8, W/8 >= 16."""
+    `self.iters`, when set, overrides the call's `iters`.  H and W must be multiples of 8 with H/8, W/8 >= 16.
+    With `args.output_dim == 1` the 2-channel flow_up above is the 1-channel upsampled `output_block(net)` (raft_model.py:257-267): [B,T-1,1,H,W],
+    and (coords1 - coords0, up [B,1,H,W]) from the two-image call."""
 
     def __init__(self, args: Optional[argparse.Namespace] = None):
         super().__init__()
         self.args = args if args is not None else _args()
         if getattr(self.args, "small", False):
             raise NotImplementedError("RAFT-small (SmallEncoder / SmallUpdateBlock) is not provided: only RAFT-large runs on the GPU")
-        if getattr(self.args, "output_dim", None) is not None:
-            raise NotImplementedError("the output_dim head of RAFT is not provided")
+        self.output_dim = getattr(self.args, "output_dim", None)
+        if self.output_dim is not None and self.output_dim != 1:
+            raise NotImplementedError("the output_dim head of RAFT is provided for output_dim = 1 only (the keypoint predictor), got %r" % (self.output_dim,))
         if getattr(self.args, "alternate_corr", False):
             raise NotImplementedError("alternate_corr (the alt_cuda_corr extension) is not provided: the all-pairs correlation runs in the library")
         self.multiframe = getattr(self.args, "multiframe", True)
@@ -138,7 +147,10 @@ class RAFT(WeightSync, nn.Module):
         self.fnet = BasicEncoder(output_dim=256, norm_fn="instance")
         self.cnet = BasicEncoder(output_dim=self.hidden_dim + self.context_dim, norm_fn="batch")
         self.update_block = BasicUpdateBlock(hidden_dim=self.hidden_dim)
-        self.output_block = None
+        if self.output_dim is not None:  # raft_model.py:152-159
+            self.output_block = nn.Sequential(nn.Conv2d(RAFT_HIDDEN, 256, 3, padding=1), nn.ReLU(inplace=True), nn.Conv2d(256, self.output_dim, 1, padding=0))
+        else:
+            self.output_block = None
         self._handle: Optional[int] = None
         self._handle_device: Optional[torch.device] = None
         self._loaded: Dict[str, Tuple[int, int]] = {}
@@ -232,8 +244,12 @@ class RAFT(WeightSync, nn.Module):
         a.batch, a.pairs, a.height, a.width = B, pairs, H, W
         a.input_scale = float(scale)
         a.iters = int(iters)
-        a.flow_dev = out[0]
-        a.flow_stride_b, a.flow_stride_t, a.flow_stride_c = out_strides
+        if self.output_dim is None:
+            a.flow_dev = out[0]
+            a.flow_stride_b, a.flow_stride_t, a.flow_stride_c = out_strides
+        else:  # the head's value is what is upsampled; the flow's own upsampling is not asked for
+            a.head_dev = out[0]
+            a.head_stride_b, a.head_stride_t, a.head_stride_c = out_strides
         a.flow_low_dev = _lib.ptr(flow_low)
         a.stream = _lib.current_stream_handle(dev)
         with torch.cuda.device(dev):
@@ -263,7 +279,7 @@ class RAFT(WeightSync, nn.Module):
         if x1.dim() != 4 or x1.shape != x2.shape or x1.shape[1] != 3:
             raise RuntimeError("expected two [B,3,H,W] images of one shape, got %s and %s" % (tuple(image1.shape), tuple(image2.shape)))
         B, _, H, W = x1.shape
-        up = torch.empty(B, 2, H, W, device=x1.device)
+        up = torch.empty(B, self.output_dim or 2, H, W, device=x1.device)
         low = torch.empty(B, 2, H // 8, W // 8, device=x1.device)
         v1, v2 = x1.unsqueeze(1), x2.unsqueeze(1)
         self._run(v1, v2, B, 1, H, W, 1.0, iters, (up.data_ptr(),), (up.stride(0), 0, up.stride(1)), flow_low=low)
@@ -291,7 +307,7 @@ class RAFT(WeightSync, nn.Module):
             first, second, pairs = x, x, 1
         else:
             first, second, pairs = x[:, :-1], x[:, 1:], T - 1
-        out = torch.empty(B, pairs, 2, H, W, device=x.device)
+        out = torch.empty(B, pairs, self.output_dim or 2, H, W, device=x.device)
         if backward:  # pairs (x[t+1], x[t]), stored at index pairs - 1 - t
             first, second = second, first
             ptr = out.data_ptr() + (pairs - 1) * out.stride(1) * out.element_size()
@@ -302,16 +318,18 @@ class RAFT(WeightSync, nn.Module):
 
 
 def load_raft_model(load_path=default_raft_ckpt, ignore_prefix=None, multiframe=True, scale_inputs=True, output_dim=None, **kwargs):
-    """raft_model.py:55-101: builds RAFT-large and loads a checkpoint (`module.` and `ignore_prefix` stripped from the keys, strict=False)."""
+    """raft_model.py:55-101: builds RAFT-large and loads a checkpoint (`module.` and `ignore_prefix` stripped from the keys, strict=False);
+    with `output_dim=1` and no path, a freshly initialised keypoint model."""
     if ((load_path is None) or (not os.path.exists(load_path))) and (output_dim is None):
         print("%s is not a valid raft checkpoint" % load_path)
         raise ValueError("You must download RAFT checkpoints with cwm/models/raft/download_raft_checkpoints.sh\n"
                          + "Checkpoints will be downloaded to CounterfactualWorldModels/checkpoints/raft_checkpoints/")
-    if output_dim is not None:
-        raise NotImplementedError("the output_dim head of RAFT is not provided")
     args = _args(**kwargs)
     args.multiframe, args.scale_inputs, args.output_dim = multiframe, scale_inputs, output_dim
     model = RAFT(args)
+    if load_path is None:
+        print("created a new %s with %d parameters" % (type(model).__name__, sum([v.numel() for v in model.parameters()])))
+        return model
     weight_dict = torch.load(load_path, map_location=torch.device("cpu"))
     new_dict = {}
     for k in weight_dict.keys():

@@ -143,14 +143,43 @@ def SyntheticFlow():  # noqa: N802 -- a class factory, so that importing this mo
     return _synthetic_flow_module()()
 
 
-def raft_state_dict(seed: int = 0) -> Dict[str, np.ndarray]:
+@functools.lru_cache(maxsize=None)
+def _synthetic_keypoints_module():
+    import torch
+
+    class SyntheticKeypoints(torch.nn.Module):
+        """Deterministic, parameter-free stand-in for the keypoint RAFT (`load_raft_model(None, output_dim=1)`) with its multi-frame call
+        contract: `keypoint_predictor(x[B,T,3,H,W] in [0,1])` -> [B,T-1,1,H,W] logits.  A function of the content of both frames of a pair,
+        spread over several units so that `sigmoid(v) ** 8` is far from flat."""
+
+        def forward(self, x, *args, **kwargs):
+            if x.size(1) == 1:
+                x = x.repeat(1, 2, 1, 1, 1)
+            a, b = x[:, :-1].float(), x[:, 1:].float()
+            v = 8.0 * (a[:, :, 0] - 0.5) + 5.0 * (b[:, :, 1] - a[:, :, 2]) + 0.5
+            return v.unsqueeze(2)
+
+    return SyntheticKeypoints
+
+
+def SyntheticKeypoints():  # noqa: N802 -- a class factory, as SyntheticFlow
+    return _synthetic_keypoints_module()()
+
+
+RAFT_KEYPOINT_OUT_SCALE = 0.5  # on `output_block.2.weight`: see raft_state_dict
+
+
+def raft_state_dict(seed: int = 0, output_dim=None) -> Dict[str, np.ndarray]:
     """Synthetic RAFT-large weights by key (`synthetic_tensor`), with batch-norm running variances 1 + 5|v|, `num_batches_tracked` 0 and the
     flow head's last convolution x 0.02: with plain xavier weights the flow grows by several pixels per iteration and after 24 iterations
-    almost every correlation lookup falls outside the pyramid."""
+    almost every correlation lookup falls outside the pyramid.  With `output_dim` the four `output_block` tensors follow (183 keys); the
+    projection `output_block.2.weight` is scaled by RAFT_KEYPOINT_OUT_SCALE so that the keypoint map spans a few units either side of zero
+    (measured on the reference: [-3.3, 7.6], std 2.4 at 224^2; unscaled, std 4.8 and most of `sigmoid(map) ** 8` saturated): the distribution
+    made from it is neither flat nor a step."""
     from .config import raft_state_dict_schema
 
     out = {}
-    for k, shp in raft_state_dict_schema().items():
+    for k, shp in raft_state_dict_schema(output_dim).items():
         if k.endswith("num_batches_tracked"):
             out[k] = np.zeros((), dtype=np.int64)
             continue
@@ -159,6 +188,8 @@ def raft_state_dict(seed: int = 0) -> Dict[str, np.ndarray]:
             v = (1.0 + 5.0 * np.abs(v)).astype(np.float32)
         if k.startswith("update_block.flow_head.conv2."):
             v = (v * np.float32(0.02)).astype(np.float32)
+        if k == "output_block.2.weight":
+            v = (v * np.float32(RAFT_KEYPOINT_OUT_SCALE)).astype(np.float32)
         out[k] = v
     return out
 

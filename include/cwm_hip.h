@@ -382,8 +382,11 @@ CWM_API int cwm_allreduce_sum_f32(cwm_comm* c, float* buf_dev, size_t count, voi
 /* ---- RAFT-large optical flow (0.9) --------------------------------------------------------------------
  * replaces: `load_raft_model(...)` / `RAFT.forward` of cwm/models/raft/raft_model.py:55-300 in the reference's inference
  * configuration (BasicEncoder fnet with instance norm, cnet with eval batch norm, 4 correlation levels of radius 4,
- * BasicUpdateBlock with SepConvGRU, convex upsampling; alternate_corr = False, output_dim = None), in parity (split-bf16)
- * arithmetic.  Weights: the reference's 179 state-dict keys and shapes (`num_batches_tracked` is accepted and ignored). */
+ * BasicUpdateBlock with SepConvGRU, convex upsampling; alternate_corr = False; output_dim = None or 1), in parity (split-bf16)
+ * arithmetic.  Weights: the reference's 179 state-dict keys and shapes (`num_batches_tracked` is accepted and ignored).
+ * The output head (0.10.1; raft_model.py:152-159, 257-267, output_dim = 1: the keypoint predictor of the demo notebook) is four more keys,
+ * `output_block.0.weight [256,128,3,3]`, `output_block.0.bias [256]`, `output_block.2.weight [1,256,1,1]`, `output_block.2.bias [1]`: optional
+ * (cwm_raft_missing_weights does not count them; a model without them is the flow model), needed only by a forward that sets `head_dev`. */
 typedef struct cwm_raft_model cwm_raft_model;
 CWM_API int cwm_raft_create(cwm_raft_model** out);
 CWM_API void cwm_raft_destroy(cwm_raft_model* m);
@@ -405,20 +408,32 @@ typedef struct cwm_raft_forward_args {
     int32_t iters;                 /* >= 1 */
     /* out: flow_up of the last iteration, pixels (x, y): element (c, Y, X) of pair (b, t) at flow_dev + b*flow_stride_b + t*flow_stride_t +
      * c*flow_stride_c + Y*width + X (strides may be negative: the reversed pair order of the backward multi-frame call) */
-    float* flow_dev;
+    float* flow_dev;               /* may be NULL (since 0.10.1) when head_dev is given: the flow's full-resolution upsampling is then skipped */
     int64_t flow_stride_b, flow_stride_t, flow_stride_c;
     float* flow_low_dev;           /* optional: coords1 - coords0, [batch * pairs, 2, H/8, W/8] contiguous (the two-image call's first output) */
     void* stream;
+    /* appended in 0.10.1, read only when struct_size covers them (a caller that passes the 0.10.0 size gets the 0.10.0 behaviour).
+     * out, optional: the convex-upsampled (times 8, as a flow) output_block(net) of the last iteration in place of the flow: element (Y, X) of
+     * pair (b, t) at head_dev + b*head_stride_b + t*head_stride_t + Y*width + X (strides may be negative).  head_stride_c is the channel stride
+     * of the [.., output_dim, H, W] tensor; with output_dim = 1 it addresses nothing.  CWM_ERR_INVALID, naming the first missing key, unless all
+     * four output_block weights are loaded.  At least one of flow_dev / head_dev must be given. */
+    float* head_dev;
+    int64_t head_stride_b, head_stride_t, head_stride_c;
 } cwm_raft_forward_args;
 CWM_API int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* args);
 
 /* Stand-alone RAFT kernels (kernel tests; the same launches as the model):
  *   cwm_raft_corr_lookup      fmap1 / fmap2 [P, h8, w8, 256] (NHWC), coords [P, h8, w8, 2] (x, y) -> out [P, h8, w8, 324]: CorrBlock (corr.py:12-60)
  *                             built and indexed at coords, feature l*81 + a*9 + b sampled at (x / 2^l + a - 4, y / 2^l + b - 4).  Synchronises.
- *   cwm_raft_convex_upsample  flow [P, 2, h8, w8], mask [P, h8, w8, 576] (NHWC, already scaled) -> out [P, 2, 8 h8, 8 w8] (RAFT.upsample_flow) */
+ *   cwm_raft_convex_upsample  flow [P, 2, h8, w8], mask [P, h8, w8, 576] (NHWC, already scaled) -> out [P, 2, 8 h8, 8 w8] (RAFT.upsample_flow)
+ *   cwm_raft_head_project     hidden [M, 256] (NHWC rows: output_block.0's result, before its ReLU), weight [256], bias [1] -> value [M] =
+ *                             bias + sum_c weight[c] relu(hidden[m, c]) in fp32 (output_block.1 and .2); 16-byte aligned hidden / weight
+ *   cwm_raft_convex_upsample1 value [P, h8, w8], mask as above -> out [P, 1, 8 h8, 8 w8]: upsample_flow of a one-channel map */
 CWM_API int cwm_raft_corr_lookup(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev,
                                  void* stream);
 CWM_API int cwm_raft_convex_upsample(const float* flow_dev, const float* mask_dev, int P, int h8, int w8, float* out_dev, void* stream);
+CWM_API int cwm_raft_head_project(const float* hidden_dev, const float* weight_dev, const float* bias_dev, int64_t M, float* value_dev, void* stream);
+CWM_API int cwm_raft_convex_upsample1(const float* value_dev, const float* mask_dev, int P, int h8, int w8, float* out_dev, void* stream);
 
 CWM_API const char* cwm_last_error(void);
 /* "cwm_hip <version> gfx950" */

@@ -2,7 +2,10 @@
 
 Reports ms per call, frame pairs/s and algorithmic TFLOP/s on the FLOPs this path computes (config.raft_algorithmic_flops: the mask head
 once, ~122 GFLOP per pair), one JSON line per batch size.  For the kernel split run it once under
-`rocprofv3 --kernel-trace --stats -- python tools/raft_step.py --batch 32 --steps 3`."""
+`rocprofv3 --kernel-trace --stats -- python tools/raft_step.py --batch 32 --steps 3`.
+
+`--output-dim 1` times the keypoint predictor instead (the model with the output head: one more 3x3 convolution, the 256 -> 1 projection and a
+one-channel convex upsampling in place of the flow's two-channel one); its FLOPs add the head's convolution and projection."""
 import argparse
 import json
 import os
@@ -14,7 +17,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from counterfactualworldmodels_amd import config as C, synthetic as S  # noqa: E402
-from counterfactualworldmodels_amd.raft import RAFT  # noqa: E402
+from counterfactualworldmodels_amd.raft import RAFT, _args  # noqa: E402
 
 
 def main():
@@ -24,12 +27,16 @@ def main():
     ap.add_argument("--iters", type=int, default=24)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--output-dim", type=int, default=None, choices=[1], help="time the keypoint forward (the output head) instead of the flow forward")
     args = ap.parse_args()
     H, W = args.size
-    m = RAFT()
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in S.raft_state_dict(0).items()})
+    m = RAFT(_args(output_dim=args.output_dim)) if args.output_dim else RAFT()
+    sd = S.raft_state_dict(0, output_dim=args.output_dim) if args.output_dim else S.raft_state_dict(0)
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
     m = m.cuda().eval()
     flops = C.raft_algorithmic_flops(H, W, args.iters)
+    if args.output_dim:  # output_block.0 (3x3, 128 -> 256) and output_block.2 (256 -> output_dim) at 1/8 resolution
+        flops += 2.0 * (H // 8) * (W // 8) * 256 * (128 * 9 + args.output_dim)
     for B in args.batch:
         x = torch.from_numpy(S.raft_frames(B, H, W, 1)).cuda()
         for _ in range(args.warmup):
@@ -42,7 +49,7 @@ def main():
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
         ms = 1e3 * float(np.median(times))
-        print(json.dumps({"batch": B, "size": [H, W], "iters": args.iters, "ms_median": round(ms, 3), "ms_min": round(1e3 * min(times), 3),
+        print(json.dumps({"output": "keypoints" if args.output_dim else "flow", "batch": B, "size": [H, W], "iters": args.iters, "ms_median": round(ms, 3), "ms_min": round(1e3 * min(times), 3),
                           "pairs_per_s": round(B / (ms / 1e3), 2), "gflop_per_pair": round(flops / 1e9, 2),
                           "tflops": round(B * flops / (ms / 1e3) / 1e12, 2)}), flush=True)
 
