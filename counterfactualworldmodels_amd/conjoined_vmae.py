@@ -12,21 +12,14 @@ The parameter tree holds no compute: the forward pass is one `cwm_conj_forward` 
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib
+from ._handle import LibraryModule, _NoForward
 from .config import CONJ_CONFIGS, IMAGENET_MEAN, IMAGENET_STD, LN_EPS, ConjConfig, conj_state_dict_schema
-from .vmae import WeightSync
-
-
-class _Params(nn.Module):
-    """Parameter container (one node of the reference's module tree); never called."""
-
-    def forward(self, *a, **k):  # pragma: no cover
-        raise RuntimeError("parameter container: the computation runs inside libcwm_hip.so")
 
 
 def _init_param(name: str, p: torch.Tensor) -> None:
@@ -48,14 +41,14 @@ def _build_tree(root: nn.Module, schema) -> None:
         parts = key.split(".")
         for part in parts[:-1]:
             if part not in node._modules:
-                node.add_module(part, _Params())
+                node.add_module(part, _NoForward())
             node = node._modules[part]
         p = nn.Parameter(torch.empty(shape))
         _init_param(key, p.data)
         node.register_parameter(parts[-1], p)
 
 
-class ConjoinedPaddedVisionTransformer(WeightSync, nn.Module):
+class ConjoinedPaddedVisionTransformer(LibraryModule):
     def __init__(self, cfg: ConjConfig, mode: str = "parity", **unused):
         super().__init__()
         self.cfg = cfg
@@ -84,10 +77,6 @@ class ConjoinedPaddedVisionTransformer(WeightSync, nn.Module):
         self.get_main_input = type("RGB01", (), {"num_channels": m.in_chans, "num_frames": m.num_frames})()
         self._output_main, self._output_context = True, False
         self.default_cfg = {}
-        self._handle: Optional[int] = None
-        self._handle_device: Optional[torch.device] = None
-        self._loaded: Dict[str, Tuple[int, int]] = {}
-        self._init_weight_sync()
 
     # ---- reference attribute surface ---------------------------------------------------------------
     @staticmethod
@@ -135,35 +124,10 @@ class ConjoinedPaddedVisionTransformer(WeightSync, nn.Module):
         """conjoined_vmae.py:722-732 with output_main only: the main stream sees (x, mask) unchanged ('rgb01')."""
         return ((x, mask, None),)
 
-    # ---- C-ABI plumbing --------------------------------------------------------------------------
-    def _library(self):
-        """The shared object this module's handle lives in: libcwm_hip.so unless `use_library` chose the development one."""
-        lib = getattr(self, "_cwm", None)
-        return lib if lib is not None else _lib.get_lib()
+    # ---- C-ABI plumbing (the handle, sync_weights and the options live in _handle.LibraryModule) -------
+    _ABI = {role: "cwm_conj_" + role for role in ("destroy", "load_weight", "forward", "set_option", "set_lanes", "timing_enable", "timing_collect")}
 
-    def _check(self, rc):
-        _lib.check(rc, self._library())
-
-    def use_library(self, lib):
-        """Create this model's handle in another build of the library (tools / tests: `_lib.get_dev_lib()`, whose per-shape tile overrides and
-        thread-local switches a handle of the production library never sees).  Call before the first forward; an existing handle is released."""
-        self._release()
-        object.__setattr__(self, "_cwm", lib)
-
-    def set_option(self, key: str, value: int):
-        """One execution option of THIS model (include/cwm_hip.h cwm_conj_set_option: "attn_kernel", "gemm_tile", "prune_last_block" ...): per handle, never
-        process-wide.  Options set before the first forward are applied when the handle is created.  An unknown key / a refused value raises and leaves nothing behind."""
-        if getattr(self, "_handle", None) is not None:  # the library validates; remembered (for a re-created handle) only once it accepted
-            self._check(self._library().cwm_conj_set_option(self._handle, key.encode(), int(value)))
-        else:
-            _lib.validate_option(key, int(value))
-        self.__dict__.setdefault("_options", {})[key] = int(value)
-
-    def _ensure_handle(self, device: torch.device) -> int:
-        lib = self._library()
-        if self._handle is not None and self._handle_device == device:
-            return self._handle
-        self._release()
+    def _conj_config(self):
         c, m = self.cfg, self.cfg.main
         cc = _lib.CwmConjConfig()
         cc.main = _lib.CwmConfig(m.img_size[0], m.img_size[1], m.patch, m.num_frames, m.in_chans, m.enc_dim, m.enc_depth, m.enc_heads,
@@ -178,58 +142,10 @@ class ConjoinedPaddedVisionTransformer(WeightSync, nn.Module):
         for i, v in enumerate(c.dec_cross):
             cc.dec_cross[i] = v
         cc.cross_heads, cc.cross_mlp_ratio = c.cross_heads, c.cross_mlp_ratio
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            self._check(self._create(lib, cc, h))
-        self._handle, self._handle_device, self._loaded = h.value, device, {}
-        for k, v in self.__dict__.get("_options", {}).items():
-            self._check(lib.cwm_conj_set_option(self._handle, k.encode(), v))
-        return self._handle
+        return cc
 
-    def _create(self, lib, cc, h):
-        return lib.cwm_conj_create(C.byref(cc), C.byref(h))
-
-    def _release(self):
-        if getattr(self, "_handle", None) is not None:
-            try:
-                self._library().cwm_conj_destroy(self._handle)
-            except Exception:
-                pass
-            # plain attributes: nn.Module.__setattr__ can already be half torn down when __del__ runs at interpreter exit
-            object.__setattr__(self, "_handle", None)
-            object.__setattr__(self, "_loaded", {})
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def sync_weights(self, device: Optional[torch.device] = None, force: bool = False) -> int:
-        """See `vmae.PretrainVisionTransformer.sync_weights` (in-place `.data` edits need force=True)."""
-        if device is None:
-            device = self._param_device()
-        if not force and self._handle is not None and self._handle_device == device and self._params_unchanged():
-            return 0
-        h = self._ensure_handle(device)
-        lib = self._library()
-        if force:
-            self._loaded = {}
-        n = 0
-        with torch.cuda.device(device):
-            for name, p in self.state_dict(keep_vars=True).items():
-                tag = (p.data_ptr(), p._version)
-                if self._loaded.get(name) == tag:
-                    continue
-                t = p.detach()
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    t = t.float().contiguous()
-                shape = (C.c_int64 * t.dim())(*t.shape)
-                self._check(lib.cwm_conj_load_weight(h, name.encode(), t.data_ptr(), 1 if t.is_cuda else 0, shape, t.dim()))
-                self._loaded[name] = tag
-                n += 1
-        self._remember_params()
-        return n
+    def _create(self, lib, h):
+        return lib.cwm_conj_create(C.byref(self._conj_config()), C.byref(h))
 
     # ---- reference forward: conjoined_vmae.py:852-887 ----------------------------------------------
     @torch.no_grad()
@@ -290,7 +206,7 @@ class ConjoinedPaddedVisionTransformer(WeightSync, nn.Module):
             x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), int(normalize), mask.data_ptr(), B, vmax, ctx.data_ptr(), mc.data_ptr(),
             vcmax, y.data_ptr(), _lib.mode_id(self.mode), int(check), _lib.current_stream_handle(dev), _lib.ptr(y_ctx))
         with torch.cuda.device(dev):
-            self._check(self._library().cwm_conj_forward(self._handle, C.byref(args_)))
+            self._check(self._fn["forward"](self._handle, C.byref(args_)))
         self._record_padding_state(mask, vis, vmax, mc, vis_c, vcmax)
         if want_main and want_ctx:
             return y, y_ctx
@@ -310,20 +226,6 @@ class ConjoinedPaddedVisionTransformer(WeightSync, nn.Module):
         record(self.main_stream, mask, vis, vmax, self.cfg.main_max_pad)
         if mask_ctx is not None:
             record(self.context_stream, mask_ctx, vis_ctx, vmax_ctx, self.cfg.ctx_max_pad)
-
-    def set_lanes(self, lanes: int):
-        """See `vmae.PretrainVisionTransformer.set_lanes`."""
-        if self._handle is None:
-            raise RuntimeError("run a forward pass (or sync_weights) before set_lanes")
-        self._check(self._library().cwm_conj_set_lanes(self._handle, int(lanes)))
-
-    def timing_enable(self, kclass: int, enable: bool = True):
-        self._check(self._library().cwm_conj_timing_enable(self._handle, kclass, int(enable)))
-
-    def timing_collect(self, kclass: int):
-        st = _lib.CwmKernelStats()
-        self._check(self._library().cwm_conj_timing_collect(self._handle, kclass, C.byref(st)))
-        return {"launches": st.launches, "total_ms": st.total_ms, "total_flops": st.total_flops}
 
 
 def imu400_base_4x4patch_2frames_1tube(**kwargs):
@@ -370,9 +272,9 @@ class ConjoinedPretrainVisionTransformer(ConjoinedPaddedVisionTransformer):
     def set_flow_model(self, flow_model):
         object.__setattr__(self, "flow_model", flow_model)
 
-    def _create(self, lib, cc, h):
+    def _create(self, lib, h):
         v = _lib.CwmConjVariant(C.sizeof(_lib.CwmConjVariant), 0, 1, _lib.CONJ_INPUT_FLOWBACK_RGB01)
-        return lib.cwm_conj_create_ex(C.byref(cc), C.byref(v), C.byref(h))
+        return lib.cwm_conj_create_ex(C.byref(self._conj_config()), C.byref(v), C.byref(h))
 
     @property
     def padding_mask(self):
@@ -473,7 +375,7 @@ class ConjoinedPretrainVisionTransformer(ConjoinedPaddedVisionTransformer):
         if args_.y_tokens_dev is None and args_.y_ctx_tokens_dev is None:
             return y  # nothing to compute: every main token visible and no context output asked for
         with torch.cuda.device(dev):
-            self._check(self._library().cwm_conj_forward(self._handle, C.byref(args_)))
+            self._check(self._fn["forward"](self._handle, C.byref(args_)))
         if want_main and want_ctx:
             return y, y_ctx
         return y if want_main else y_ctx

@@ -50,14 +50,12 @@ struct cwm_conj_model {
     bf16 *ybuf = nullptr, *ysbuf = nullptr;
     // batch lanes (cwm_conj_set_lanes; see cwm_model in model.hip)
     int lanes = 2;
-    hipStream_t lane_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    Lanes lane_set;
     // the context (IMU) stream of every lane runs its blocks on a stream of its own between two cross blocks (conj_forward_lane)
     hipStream_t ctx_stream[2] = {nullptr, nullptr};
     hipEvent_t ev_ctx[2] = {nullptr, nullptr}, ev_main[2] = {nullptr, nullptr};
     hipEvent_t ev_cross[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};  // run_cross
     ~cwm_conj_model() {
-        if (lane_stream) (void)hipStreamDestroy(lane_stream);
         for (int i = 0; i < 2; ++i) {
             if (ctx_stream[i]) (void)hipStreamDestroy(ctx_stream[i]);
             if (ev_ctx[i]) (void)hipEventDestroy(ev_ctx[i]);
@@ -65,8 +63,6 @@ struct cwm_conj_model {
             for (int k = 0; k < 4; ++k)
                 if (ev_cross[i][k]) (void)hipEventDestroy(ev_cross[i][k]);
         }
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
     }
 };
 
@@ -631,12 +627,8 @@ static int conj_forward_lane(ConjLane& L, const cwm_conj_forward_args* a, int b0
 
 extern "C" int cwm_conj_forward(cwm_conj_model* m, const cwm_conj_forward_args* a_in) {
     CWM_REQUIRE(m && a_in, "cwm_conj_forward: null argument");
-    // the caller's struct may end before the fields later versions appended: copy what it has, the rest stays zero (= not requested)
-    CWM_REQUIRE(a_in->struct_size >= offsetof(cwm_conj_forward_args, stream) + sizeof(void*) && a_in->struct_size <= 4096,
-                "cwm_conj_forward: args->struct_size = %u is not a cwm_conj_forward_args (set it to sizeof(cwm_conj_forward_args))", a_in->struct_size);
     cwm_conj_forward_args a_copy;
-    memset(&a_copy, 0, sizeof(a_copy));
-    memcpy(&a_copy, a_in, std::min<size_t>(a_in->struct_size, sizeof(a_copy)));
+    if (int rc = copy_args(a_copy, a_in, offsetof(cwm_conj_forward_args, stream) + sizeof(void*), "cwm_conj_forward")) return rc;
     const cwm_conj_forward_args* a = &a_copy;
     if (int rc = cwm_require_device(m->eng.device, "cwm_conj_forward")) return rc;
     const bool flowback = m->var.main_input == CWM_CONJ_INPUT_FLOWBACK_RGB01;
@@ -650,11 +642,7 @@ extern "C" int cwm_conj_forward(cwm_conj_model* m, const cwm_conj_forward_args* 
     // (unpadded: a fully visible main stream is allowed when only the context output is asked for -- the decoder then has Nm = 0)
     CWM_REQUIRE(B > 0 && vm > 0 && (vm < Nx || (!m->var.padded && !(a->y_tokens_dev && vm == Nx))) && vc > 0 && vc <= m->ctx.n_tok,
                 "cwm_conj_forward: bad batch / visible counts (%d, %d, %d)", B, vm, vc);
-    {
-        char miss[256];
-        const int nmiss = m->eng.missing_weights(miss, sizeof(miss));
-        CWM_REQUIRE(nmiss == 0, "cwm_conj_forward: %d state-dict tensors not loaded (first: %s)", nmiss, miss);
-    }
+    if (int rc = m->eng.require_weights("cwm_conj_forward")) return rc;
     if (int rc = ensure_workspace(m, B, vm, vc)) return rc;
     hipStream_t s = (hipStream_t)a->stream;
     if (m->var.ctx_dummy_token) {  // the lanes read the IMU and its mask with the dummy token appended, from the engine's staging buffers
@@ -669,15 +657,7 @@ extern "C" int cwm_conj_forward(cwm_conj_model* m, const cwm_conj_forward_args* 
     // two lanes as in cwm_forward (model.hip): the halves share n_vis_max / n_vis_ctx_max, so the padded layout of every row is unchanged
     const bool two = m->lanes >= 2 && B >= 2 && (int64_t)(B / 2) * vm >= (m->eng.tune.min_lane_rows > 0 ? m->eng.tune.min_lane_rows : kMinLaneRowsConj);
     const int B0 = two ? (B + 1) / 2 : B;
-    if (two) {
-        if (!m->lane_stream) {
-            CWM_HIP_CHECK(hipStreamCreateWithFlags(&m->lane_stream, hipStreamNonBlocking));
-            CWM_HIP_CHECK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-            CWM_HIP_CHECK(hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
-        }
-        CWM_HIP_CHECK(hipEventRecord(m->ev_fork, s));
-        CWM_HIP_CHECK(hipStreamWaitEvent(m->lane_stream, m->ev_fork, 0));
-    }
+    if (int rc = m->lane_set.fork(s, two ? 2 : 1)) return rc;
     ConjLane lanes[2] = {conj_lane(m, 0, 0), conj_lane(m, 1, two ? B0 : 0)};
     m->eng.overlapped = two;
     int rc = 0;
@@ -685,13 +665,10 @@ extern "C" int cwm_conj_forward(cwm_conj_model* m, const cwm_conj_forward_args* 
     const int n_stages = m->cfg.main.enc_depth + m->cfg.main.dec_depth + 3;
     for (int st = 0; st < n_stages && !rc; ++st) {
         rc = conj_forward_lane(lanes[0], a, 0, B0, s, 0, st, st + 1);
-        if (two && !rc) rc = conj_forward_lane(lanes[1], a, B0, B - B0, m->lane_stream, 1, st, st + 1);
+        if (two && !rc) rc = conj_forward_lane(lanes[1], a, B0, B - B0, m->lane_set.stream(1, s), 1, st, st + 1);
     }
     m->eng.overlapped = 0;
-    if (two) {  // join even after a failed launch: the caller's stream must not run ahead of work already queued on the lane
-        CWM_HIP_CHECK(hipEventRecord(m->ev_join, m->lane_stream));
-        CWM_HIP_CHECK(hipStreamWaitEvent(s, m->ev_join, 0));
-    }
+    if (int jrc = m->lane_set.join(s)) return jrc;  // (even after a failed launch)
     if (rc) return rc;
 
     if (a->check) {
@@ -712,10 +689,7 @@ extern "C" int cwm_conj_forward(cwm_conj_model* m, const cwm_conj_forward_args* 
 
 extern "C" int cwm_conj_set_option(cwm_conj_model* m, const char* key, int value) {
     CWM_REQUIRE(m && key, "cwm_conj_set_option: null argument");
-    const int rc = tuning_set_production(m->eng.tune, key, value);
-    CWM_REQUIRE(rc != -2, "cwm_conj_set_option: gemm_debug bits 1, 2 and 8 are timing-only ablations (wrong outputs): development library only (cwm_debug_set)");
-    CWM_REQUIRE(rc == 0, "cwm_conj_set_option: unknown option %s", key);
-    return CWM_OK;
+    return m->eng.set_option("cwm_conj_set_option", key, value);
 }
 
 extern "C" int cwm_conj_set_lanes(cwm_conj_model* m, int lanes) {

@@ -1,6 +1,6 @@
 // Shared host-side machinery of the model handles behind the C ABI: packed weights, state-dict slots,
-// activation workspace, timed launches and the transformer Block sequence.  Used by model.hip (plain
-// VMAE predictor) and conj_model.hip (IMU-conditioned conjoined predictor).
+// activation workspace, timed launches, batch lanes and the transformer Block sequence.  Used by model.hip
+// (plain VMAE predictor), conj_model.hip (conjoined predictors) and raft_model.hip (RAFT).
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -71,6 +71,21 @@ constexpr int kMinLaneRows = 3000;  // (Tuning.min_lane_rows overrides it per mo
 // batch 8 / 12 / 16 2.3 / 1.4 / 1.0 % faster (3172 visible rows per sample; rounds 1-3 split from batch 4)
 constexpr int kMinLaneRowsConj = 12000;
 
+// The streams and events of a forward that runs as batch lanes: lane 0 is the caller's stream, lanes 1 .. n - 1 non-blocking streams of the model, created on
+// first use.  fork() makes them wait for what the caller's stream holds so far, join() makes the caller's stream wait for them.  The caller decides the lane
+// count and the batch split, issues its launches stage by stage over stream(l, ...), and joins even after a failed launch: the caller's stream must not run
+// ahead of work already queued on a lane.
+struct Lanes {
+    static constexpr int kMax = 4;
+    hipStream_t streams[kMax - 1] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[kMax - 1] = {};
+    int forked = 1;  // lanes between fork() and join()
+    ~Lanes();
+    int fork(hipStream_t caller, int n_lanes);
+    hipStream_t stream(int l, hipStream_t caller) const { return l == 0 ? caller : streams[l - 1]; }
+    int join(hipStream_t caller);
+};
+
 struct Engine {
     int device = 0;
     int overlapped = 0;  // 1 while a forward call runs two batch lanes (passed to the GEMM kernel choice)
@@ -111,6 +126,8 @@ struct Engine {
 
     int load_weight(const char* key, const float* data, int on_device, const int64_t* shape, int ndim);
     int missing_weights(char* buf, int buflen);
+    int require_weights(const char* fn);                            // CWM_ERR_INVALID naming the first tensor that was never loaded
+    int set_option(const char* fn, const char* key, int value);  // cwm_model_set_option / cwm_conj_set_option
 
     int run_gemm(const GemmParams& p, int planes, hipStream_t s);
     int run_attention(const AttnParams& p, int planes, hipStream_t s);
@@ -138,6 +155,18 @@ struct Engine {
     int timing_enable(int kclass, int enable);
     int timing_collect(int kclass, cwm_kernel_stats* out);
 };
+
+// The versioned argument structs of the forward entry points (`struct_size` first): the caller's struct may end before fields a later version appended, so
+// copy what it has into a zeroed one (the rest reads as "not requested").  `min_size`: the end of the last field of the first version; the upper bound
+// catches a struct without the field.  `fn` names the entry point, whose struct is `<fn>_args`.
+template <typename Args>
+int copy_args(Args& dst, const Args* src, size_t min_size, const char* fn, const char* note = "") {
+    CWM_REQUIRE(src->struct_size >= min_size && src->struct_size <= 4096, "%s: args->struct_size = %u is not a %s_args (set it to sizeof(%s_args)%s)", fn,
+                src->struct_size, fn, fn, note);
+    memset(&dst, 0, sizeof(dst));
+    memcpy(&dst, src, std::min<size_t>(src->struct_size, sizeof(dst)));
+    return 0;
+}
 
 GemmParams gemm_base(const bf16* A, int lda, const LinearW& L, int M, int planes);
 

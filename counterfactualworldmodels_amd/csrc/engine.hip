@@ -313,6 +313,56 @@ int Engine::missing_weights(char* buf, int buflen) {
     return missing;
 }
 
+int Engine::require_weights(const char* fn) {
+    char miss[256];
+    const int nmiss = missing_weights(miss, sizeof(miss));
+    CWM_REQUIRE(nmiss == 0, "%s: %d state-dict tensors not loaded (first: %s)", fn, nmiss, miss);
+    return 0;
+}
+
+int Engine::set_option(const char* fn, const char* key, int value) {
+    const int rc = tuning_set_production(tune, key, value);
+    CWM_REQUIRE(rc != -2, "%s: gemm_debug bits 1, 2 and 8 are timing-only ablations (wrong outputs): development library only (cwm_debug_set)", fn);
+    CWM_REQUIRE(rc == 0, "%s: unknown option %s", fn, key);
+    return 0;
+}
+
+// ---- batch lanes ------------------------------------------------------------------------------
+Lanes::~Lanes() {
+    for (auto s : streams)
+        if (s) (void)hipStreamDestroy(s);
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    for (auto e : ev_join)
+        if (e) (void)hipEventDestroy(e);
+}
+
+int Lanes::fork(hipStream_t caller, int n_lanes) {
+    CWM_REQUIRE(n_lanes >= 1 && n_lanes <= kMax, "Lanes::fork: %d lanes", n_lanes);
+    if (n_lanes >= 2) {
+        if (!ev_fork) CWM_HIP_CHECK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+        CWM_HIP_CHECK(hipEventRecord(ev_fork, caller));  // inputs written on the caller's stream are complete for the other lanes
+        for (int l = 1; l < n_lanes; ++l) {
+            if (!streams[l - 1]) {
+                CWM_HIP_CHECK(hipStreamCreateWithFlags(&streams[l - 1], hipStreamNonBlocking));
+                CWM_HIP_CHECK(hipEventCreateWithFlags(&ev_join[l - 1], hipEventDisableTiming));
+            }
+            CWM_HIP_CHECK(hipStreamWaitEvent(streams[l - 1], ev_fork, 0));
+        }
+    }
+    forked = n_lanes;
+    return 0;
+}
+
+int Lanes::join(hipStream_t caller) {
+    const int n = forked;
+    forked = 1;
+    for (int l = 1; l < n; ++l) {
+        CWM_HIP_CHECK(hipEventRecord(ev_join[l - 1], streams[l - 1]));
+        CWM_HIP_CHECK(hipStreamWaitEvent(caller, ev_join[l - 1], 0));
+    }
+    return 0;
+}
+
 // ---- timed launches ---------------------------------------------------------------------------
 int Engine::timer_begin(int kclass, double flops, hipStream_t s, EventPair** out) {
     KernelTimer& t = timers[kclass];

@@ -24,19 +24,11 @@ struct cwm_model {
     bf16* patches = nullptr;
     float *x_enc = nullptr, *x_dec = nullptr;
     StreamBuffers sb;
-    // batch lanes (cwm_model_set_lanes): a batch whose halves keep >= kMinLaneRows encoder rows runs as two half batches, the first on the
-    // caller's stream and the second on `lane_stream`, joined by events before cwm_forward returns control of the stream
+    // batch lanes (cwm_model_set_lanes): a batch whose slices keep >= kMinLaneRows encoder rows each runs as up to `lanes` slices, the first on the
+    // caller's stream and the others on streams of `lane_set`, joined by events before cwm_forward returns control of the stream
     int lanes = 2;
-    static constexpr int kMaxLanes = 4;
-    hipStream_t lane_stream[kMaxLanes - 1] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[kMaxLanes - 1] = {nullptr, nullptr, nullptr};
-    ~cwm_model() {
-        for (auto s : lane_stream)
-            if (s) (void)hipStreamDestroy(s);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        for (auto e : ev_join)
-            if (e) (void)hipEventDestroy(e);
-    }
+    static constexpr int kMaxLanes = Lanes::kMax;
+    Lanes lane_set;
 };
 
 // per-lane view of the workspace: every buffer is batch-major, so the lane that starts at batch element b0 owns the slice
@@ -73,7 +65,7 @@ int ensure_workspace(cwm_model* m, int B, int n_vis) {
     return 0;
 }
 
-LaneWs lane_ws(const cwm_model* m, int lane, int b0) {
+LaneWs lane_ws(const cwm_model* m, int b0) {
     const cwm_config& c = m->cfg;
     const size_t rows_e = (size_t)b0 * m->ws_nvis, rows_d = (size_t)b0 * m->Nt;
     const size_t act = std::max(rows_e * c.enc_dim, rows_d * c.dec_dim);
@@ -81,7 +73,6 @@ LaneWs lane_ws(const cwm_model* m, int lane, int b0) {
     w.perm = m->perm + rows_d;
     w.rank = m->rank + rows_d;
     w.err = m->err + b0;  // one word per batch row (index_gather_kernel writes every row's, every call: no memset)
-    (void)lane;
     w.patches = m->patches + 2 * rows_e * m->patch_kpad;
     w.x_enc = m->x_enc + rows_e * c.enc_dim;
     w.x_dec = m->x_dec + rows_d * c.dec_dim;
@@ -266,14 +257,10 @@ static int forward_lane(cwm_model* m, const cwm_forward_args* a, int b0, int B, 
 
 extern "C" int cwm_forward(cwm_model* m, const cwm_forward_args* a_in) {
     CWM_REQUIRE(m && a_in, "cwm_forward: null argument");
-    // the caller's struct may end before fields a later version appends: copy what it has, the rest stays zero (= not requested).  The upper bound
-    // catches a caller built against the 0.5 header (no struct_size: the low half of its x_dev pointer lands here).
-    CWM_REQUIRE(a_in->struct_size >= offsetof(cwm_forward_args, stream) + sizeof(void*) && a_in->struct_size <= 4096,
-                "cwm_forward: args->struct_size = %u is not a cwm_forward_args (set it to sizeof(cwm_forward_args); callers built against the 0.5 header must be rebuilt)",
-                a_in->struct_size);
+    // (the upper bound of struct_size catches a caller built against the 0.5 header, which had no such field: the low half of its x_dev pointer lands there)
     cwm_forward_args a_copy;
-    memset(&a_copy, 0, sizeof(a_copy));
-    memcpy(&a_copy, a_in, std::min<size_t>(a_in->struct_size, sizeof(a_copy)));
+    if (int rc = copy_args(a_copy, a_in, offsetof(cwm_forward_args, stream) + sizeof(void*), "cwm_forward", "; callers built against the 0.5 header must be rebuilt"))
+        return rc;
     const cwm_forward_args* a = &a_copy;
     if (int rc = cwm_require_device(m->eng.device, "cwm_forward")) return rc;
     CWM_REQUIRE(a->x_dev && a->mask_dev && a->y_tokens_dev, "cwm_forward: x_dev, mask_dev and y_tokens_dev are required");
@@ -286,11 +273,7 @@ extern "C" int cwm_forward(cwm_model* m, const cwm_forward_args* a_in) {
     // compose a video from that (prediction.py:252-254 would assign Nt rows to an empty selection)
     CWM_REQUIRE(Nm > 0 || !a->y_video_dev, "cwm_forward: no token is masked, there is no predicted patch to un-embed");
     CWM_REQUIRE(!a->y_video_dev || a->xraw_dev || a->normalize, "cwm_forward: y_video_dev needs the raw frames (xraw_dev) when normalize=0");
-    {
-        char miss[256];
-        const int nmiss = m->eng.missing_weights(miss, sizeof(miss));
-        CWM_REQUIRE(nmiss == 0, "cwm_forward: %d state-dict tensors not loaded (first: %s)", nmiss, miss);
-    }
+    if (int rc = m->eng.require_weights("cwm_forward")) return rc;
     if (int rc = ensure_workspace(m, B, Nv)) return rc;
     hipStream_t s = (hipStream_t)a->stream;
 
@@ -299,33 +282,18 @@ extern "C" int cwm_forward(cwm_model* m, const cwm_forward_args* a_in) {
     const int min_rows = m->eng.tune.min_lane_rows > 0 ? m->eng.tune.min_lane_rows : kMinLaneRows;
     int n_lanes = 1;
     while (n_lanes < m->lanes && n_lanes < B && (int64_t)(B / (n_lanes + 1)) * Nv >= min_rows) ++n_lanes;
-    const bool two = n_lanes >= 2;
     int first[cwm_model::kMaxLanes + 1];
     for (int l = 0; l <= n_lanes; ++l) first[l] = (int)(((int64_t)B * l + n_lanes - 1) / n_lanes);  // lane l owns batch elements [first[l], first[l+1])
-    if (two) {
-        if (!m->ev_fork) CWM_HIP_CHECK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-        CWM_HIP_CHECK(hipEventRecord(m->ev_fork, s));  // inputs written on the caller's stream are complete for the other lanes
-        for (int l = 1; l < n_lanes; ++l) {
-            if (!m->lane_stream[l - 1]) {
-                CWM_HIP_CHECK(hipStreamCreateWithFlags(&m->lane_stream[l - 1], hipStreamNonBlocking));
-                CWM_HIP_CHECK(hipEventCreateWithFlags(&m->ev_join[l - 1], hipEventDisableTiming));
-            }
-            CWM_HIP_CHECK(hipStreamWaitEvent(m->lane_stream[l - 1], m->ev_fork, 0));
-        }
-    }
-    m->eng.overlapped = two;
+    if (int rc = m->lane_set.fork(s, n_lanes)) return rc;
+    m->eng.overlapped = n_lanes >= 2;
     int rc = 0;
     // launch order: stage by stage (one transformer block at a time) over all lanes, so that every lane's queue starts filling at once
     const int n_stages = c.enc_depth + c.dec_depth + 3;
     for (int st = 0; st < n_stages && !rc; ++st)
         for (int l = 0; l < n_lanes && !rc; ++l)
-            rc = forward_lane(m, a, first[l], first[l + 1] - first[l], lane_ws(m, l, first[l]), l == 0 ? s : m->lane_stream[l - 1], st, st + 1);
+            rc = forward_lane(m, a, first[l], first[l + 1] - first[l], lane_ws(m, first[l]), m->lane_set.stream(l, s), st, st + 1);
     m->eng.overlapped = 0;
-    // join even after a failed launch: the caller's stream must not run ahead of work already queued on a lane
-    for (int l = 1; l < n_lanes; ++l) {
-        CWM_HIP_CHECK(hipEventRecord(m->ev_join[l - 1], m->lane_stream[l - 1]));
-        CWM_HIP_CHECK(hipStreamWaitEvent(s, m->ev_join[l - 1], 0));
-    }
+    if (int jrc = m->lane_set.join(s)) return jrc;  // (even after a failed launch)
     if (rc) return rc;
 
     if (a->check) {
@@ -349,10 +317,7 @@ extern "C" int cwm_model_set_lanes(cwm_model* m, int lanes) {
 
 extern "C" int cwm_model_set_option(cwm_model* m, const char* key, int value) {
     CWM_REQUIRE(m && key, "cwm_model_set_option: null argument");
-    const int rc = tuning_set_production(m->eng.tune, key, value);
-    CWM_REQUIRE(rc != -2, "cwm_model_set_option: gemm_debug bits 1, 2 and 8 are timing-only ablations (wrong outputs): development library only (cwm_debug_set)");
-    CWM_REQUIRE(rc == 0, "cwm_model_set_option: unknown option %s", key);
-    return CWM_OK;
+    return m->eng.set_option("cwm_model_set_option", key, value);
 }
 
 extern "C" int cwm_timing_enable(cwm_model* m, int kclass, int enable) {

@@ -503,11 +503,8 @@ extern "C" int cwm_raft_missing_weights(cwm_raft_model* m, char* buf, int buflen
 extern "C" int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* args) {
     CWM_REQUIRE(m && args, "cwm_raft_forward: null argument");
     // a caller built against the 0.10.0 header (the struct ended at `stream`) passes that size: the fields appended since read as zero
-    CWM_REQUIRE(args->struct_size >= offsetof(cwm_raft_forward_args, stream) + sizeof(void*) && args->struct_size <= 4096,
-                "cwm_raft_forward: args->struct_size = %u is not a cwm_raft_forward_args (set it to sizeof(cwm_raft_forward_args))", args->struct_size);
     cwm_raft_forward_args a_copy;
-    memset(&a_copy, 0, sizeof(a_copy));
-    memcpy(&a_copy, args, std::min<size_t>(args->struct_size, sizeof(a_copy)));
+    if (int rc = copy_args(a_copy, args, offsetof(cwm_raft_forward_args, stream) + sizeof(void*), "cwm_raft_forward")) return rc;
     const cwm_raft_forward_args& a = a_copy;
     if (int rc = cwm_require_device(m->eng.device, "cwm_raft_forward")) return rc;
     CWM_REQUIRE(a.image1_dev && a.image2_dev && (a.flow_dev || a.head_dev), "cwm_raft_forward: image1, image2 and one of flow / head are required");

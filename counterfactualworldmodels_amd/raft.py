@@ -21,21 +21,16 @@ from __future__ import annotations
 import argparse
 import ctypes as C
 import os
-from typing import Dict, Optional, Tuple
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib
+from ._handle import LibraryModule, _NoForward
 from .config import RAFT_CORR_LEVELS, RAFT_CORR_RADIUS, RAFT_HIDDEN
-from .vmae import WeightSync
 
 default_raft_ckpt = "../../../checkpoints/raft_checkpoints/raft-large.pth"
-
-
-class _NoForward(nn.Module):
-    def forward(self, *args, **kwargs):  # pragma: no cover - the whole network runs in the library
-        raise RuntimeError("RAFT submodules hold parameters only: call the RAFT module itself")
 
 
 class ResidualBlock(_NoForward):
@@ -118,7 +113,7 @@ def _args(**kw) -> argparse.Namespace:
     return a
 
 
-class RAFT(WeightSync, nn.Module):
+class RAFT(LibraryModule):
     """Drop-in for the reference's `RAFT` (large, inference).  Calls:
     - multiframe (default): `model(x[B,T,3,H,W], iters=24, backward=False)` -> [B,T-1,2,H,W] pixel flows (flow_up of the last iteration);
       x is in [0,1] with scale_inputs=True (in [0,255] otherwise); backward=True computes the pairs (x[t+1], x[t]) and returns them in
@@ -151,10 +146,6 @@ class RAFT(WeightSync, nn.Module):
             self.output_block = nn.Sequential(nn.Conv2d(RAFT_HIDDEN, 256, 3, padding=1), nn.ReLU(inplace=True), nn.Conv2d(256, self.output_dim, 1, padding=0))
         else:
             self.output_block = None
-        self._handle: Optional[int] = None
-        self._handle_device: Optional[torch.device] = None
-        self._loaded: Dict[str, Tuple[int, int]] = {}
-        self._init_weight_sync()
 
     # ---- reference attribute surface -------------------------------------------------------------
     @property
@@ -174,65 +165,12 @@ class RAFT(WeightSync, nn.Module):
             if isinstance(m, nn.BatchNorm2d):
                 m.eval()
 
-    # ---- C-ABI plumbing --------------------------------------------------------------------------
-    def _ensure_handle(self, device: torch.device) -> int:
-        lib = _lib.get_lib()
-        if self._handle is not None and self._handle_device == device:
-            return self._handle
-        self._release()
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(lib.cwm_raft_create(C.byref(h)))
-        self._handle = h.value
-        self._handle_device = device
-        self._loaded = {}
-        return self._handle
+    # ---- C-ABI plumbing (the handle and sync_weights live in _handle.LibraryModule; the library folds the batch norms and packs the
+    # convolutions at the next forward.  cwm_raft_* has no per-handle options, lanes or kernel timing) -------
+    _ABI = {role: "cwm_raft_" + role for role in ("destroy", "load_weight", "forward")}
 
-    def _release(self):
-        if getattr(self, "_handle", None) is not None:
-            try:
-                _lib.get_lib().cwm_raft_destroy(self._handle)
-            except Exception:
-                pass
-            object.__setattr__(self, "_handle", None)
-            object.__setattr__(self, "_loaded", {})
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def sync_weights(self, device: torch.device, force: bool = False) -> int:
-        """Upload every state-dict tensor that changed since the last call (see `WeightSync`); the library folds the batch norms
-        and packs the convolutions at the next forward."""
-        if not force and self._handle is not None and self._handle_device == device and self._params_unchanged():
-            return 0
-        h = self._ensure_handle(device)
-        lib = _lib.get_lib()
-        if force:
-            self._loaded = {}
-        n = 0
-        with torch.cuda.device(device):
-            for name, p in self.state_dict(keep_vars=True).items():
-                tag = (p.data_ptr(), p._version)
-                if self._loaded.get(name) == tag:
-                    continue
-                t = p.detach()
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    t = t.float().contiguous()
-                if t.is_cuda and t.device != device:
-                    t = t.to(device)
-                shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-                _lib.check(lib.cwm_raft_load_weight(h, name.encode(), t.data_ptr(), 1 if t.is_cuda else 0, shape, t.dim()))
-                self._loaded[name] = tag
-                n += 1
-        self._remember_params()
-        return n
-
-    def invalidate_weights(self):
-        self._loaded = {}
-        self._plist = None
+    def _create(self, lib, h):
+        return lib.cwm_raft_create(C.byref(h))
 
     def _run(self, x1, x2, B, pairs, H, W, scale, iters, out, out_strides, flow_low=None):
         dev = x1.device
@@ -253,7 +191,7 @@ class RAFT(WeightSync, nn.Module):
         a.flow_low_dev = _lib.ptr(flow_low)
         a.stream = _lib.current_stream_handle(dev)
         with torch.cuda.device(dev):
-            _lib.check(_lib.get_lib().cwm_raft_forward(self._handle, C.byref(a)))
+            self._check(self._fn["forward"](self._handle, C.byref(a)))
 
     @staticmethod
     def _frames(x: torch.Tensor) -> torch.Tensor:

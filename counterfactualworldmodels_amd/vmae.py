@@ -11,12 +11,13 @@ hand-written HIP kernels.  There is no PyTorch fallback path.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib
+from ._handle import LibraryModule, _NoForward
 from .config import CONFIGS, LN_EPS, VmaeConfig
 
 
@@ -34,14 +35,6 @@ def _init_weights(m):
     elif isinstance(m, nn.LayerNorm):
         nn.init.constant_(m.bias, 0)
         nn.init.constant_(m.weight, 1.0)
-
-
-class _NoForward(nn.Module):
-    def forward(self, *a, **k):  # pragma: no cover
-        raise RuntimeError(
-            "%s is a parameter container: the computation runs inside libcwm_hip.so via "
-            "PretrainVisionTransformer.forward" % type(self).__name__
-        )
 
 
 class Attention(_NoForward):
@@ -113,50 +106,7 @@ class PretrainVisionTransformerDecoder(_NoForward):
         self.apply(_init_weights)
 
 
-class WeightSync:
-    """Mixin: a cheap "has any parameter changed since the last upload?" test for the modules that mirror their parameters into
-    the library.  Walking `state_dict()` costs ~0.3 ms per forward for ViT-B (218 tensors) -- GPU idle time whenever the caller
-    synchronises between forwards -- so the tensors are listed once, each with the module dict that owns it, and a forward only
-    checks (a) that every slot still holds the listed object (`setattr` / `register_parameter` replacing a Parameter, also through
-    a SUBMODULE's `.to()` when torch swaps parameter objects) and (b) the (storage pointer, version counter) pairs (`p.data = ...`,
-    `encoder.double()`, `copy_`, optimiser steps, `load_state_dict`): ~60 us.  Not visible to it: in-place edits through `.data`
-    that keep the storage (`p.data.mul_(2)`): call `sync_weights(force=True)` after those."""
-
-    def _init_weight_sync(self):
-        self._plist = None
-        self._psig = None
-        self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module._forget_params())
-
-    def _forget_params(self):
-        self._plist = None
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self._plist = None
-        return out
-
-    def _param_device(self):
-        return self._plist[0][2].device if self._plist else next(self.parameters()).device
-
-    def _params_unchanged(self) -> bool:
-        pl = self._plist
-        if pl is None:
-            return False
-        for slots, key, p in pl:
-            if slots.get(key) is not p:
-                return False
-        return tuple((p.data_ptr(), p._version) for _, _, p in pl) == self._psig
-
-    def _remember_params(self):
-        pl = []
-        for mod in self.modules():
-            pl += [(mod._parameters, k, p) for k, p in mod._parameters.items() if p is not None]
-            pl += [(mod._buffers, k, b) for k, b in mod._buffers.items() if b is not None and k not in mod._non_persistent_buffers_set]
-        self._plist = pl
-        self._psig = tuple((p.data_ptr(), p._version) for _, _, p in pl)
-
-
-class PretrainVisionTransformer(WeightSync, nn.Module):
+class PretrainVisionTransformer(LibraryModule):
     """Drop-in for `cwm.models.VideoMAE.vmae.PretrainVisionTransformer` (main_input=None models)."""
 
     def __init__(self, cfg: VmaeConfig, mode: str = "parity", use_flash_attention: bool = True, **unused):
@@ -177,10 +127,6 @@ class PretrainVisionTransformer(WeightSync, nn.Module):
         self.patch_size = self.encoder.patch_size
         self.image_size = tuple(cfg.img_size)
         self.default_cfg = {}
-        self._handle: Optional[int] = None
-        self._handle_device: Optional[torch.device] = None
-        self._loaded: Dict[str, Tuple[int, int]] = {}
-        self._init_weight_sync()
 
     # ---- reference attribute surface -------------------------------------------------------------
     @property
@@ -194,110 +140,22 @@ class PretrainVisionTransformer(WeightSync, nn.Module):
     def get_num_layers(self):
         return len(self.encoder.blocks)
 
-    # ---- C-ABI plumbing --------------------------------------------------------------------------
-    def _library(self):
-        """The shared object this module's handle lives in: libcwm_hip.so unless `use_library` chose the development one."""
-        lib = getattr(self, "_cwm", None)
-        return lib if lib is not None else _lib.get_lib()
+    # ---- C-ABI plumbing (the handle, sync_weights and the options live in _handle.LibraryModule) -------
+    _ABI = {"destroy": "cwm_model_destroy", "load_weight": "cwm_model_load_weight", "forward": "cwm_forward", "set_option": "cwm_model_set_option",
+            "set_lanes": "cwm_model_set_lanes", "timing_enable": "cwm_timing_enable", "timing_collect": "cwm_timing_collect"}
 
-    def _check(self, rc):
-        _lib.check(rc, self._library())
-
-    def use_library(self, lib):
-        """Create this model's handle in another build of the library (tools / tests: `_lib.get_dev_lib()`, whose per-shape tile overrides and
-        thread-local switches a handle of the production library never sees).  Call before the first forward; an existing handle is released."""
-        self._release()
-        object.__setattr__(self, "_cwm", lib)
-
-    def set_option(self, key: str, value: int):
-        """One execution option of THIS model (include/cwm_hip.h cwm_model_set_option: "attn_kernel", "gemm_tile", "prune_last_block" ...): per handle, never
-        process-wide.  Options set before the first forward are applied when the handle is created.  An unknown key / a refused value raises and leaves nothing behind."""
-        if getattr(self, "_handle", None) is not None:  # the library validates; remembered (for a re-created handle) only once it accepted
-            self._check(self._library().cwm_model_set_option(self._handle, key.encode(), int(value)))
-        else:
-            _lib.validate_option(key, int(value))
-        self.__dict__.setdefault("_options", {})[key] = int(value)
-
-    def _ensure_handle(self, device: torch.device) -> int:
-        lib = self._library()
-        if self._handle is not None and self._handle_device == device:
-            return self._handle
-        self._release()
+    def _create(self, lib, h):
         c = self.cfg
         ccfg = _lib.CwmConfig(
             c.img_size[0], c.img_size[1], c.patch, c.num_frames, c.in_chans, c.enc_dim, c.enc_depth, c.enc_heads,
             c.dec_dim, c.dec_depth, c.dec_heads, c.mlp_ratio, LN_EPS,
         )
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            self._check(lib.cwm_model_create(C.byref(ccfg), C.byref(h)))
-        self._handle = h.value
-        self._handle_device = device
-        self._loaded = {}
-        for k, v in self.__dict__.get("_options", {}).items():
-            self._check(lib.cwm_model_set_option(self._handle, k.encode(), v))
-        return self._handle
-
-    def _release(self):
-        if getattr(self, "_handle", None) is not None:
-            try:
-                self._library().cwm_model_destroy(self._handle)
-            except Exception:
-                pass
-            # plain attributes: nn.Module.__setattr__ can already be half torn down when __del__ runs at interpreter exit
-            object.__setattr__(self, "_handle", None)
-            object.__setattr__(self, "_loaded", {})
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def sync_weights(self, device: Optional[torch.device] = None, force: bool = False) -> int:
-        """Push every parameter that changed since the last call into the library (packs to bf16
-        hi/lo planes).  Counterpart of `load_state_dict` at the boundary (prediction.py:81-107).
-        A change is detected by object identity + (storage pointer, version counter) of every parameter (`WeightSync`):
-        `load_state_dict`, `copy_`, optimiser steps, `p.data = t`, `.to()` / `.double()` on the model or a submodule, a replaced
-        Parameter.  In-place edits through `.data` that keep the storage (`p.data.mul_(2)`) are NOT visible -- call
-        `sync_weights(force=True)` (or `invalidate_weights()`) after such an edit."""
-        if device is None:
-            device = self._param_device()
-        if not force and self._handle is not None and self._handle_device == device and self._params_unchanged():
-            return 0
-        h = self._ensure_handle(device)
-        lib = self._library()
-        if force:
-            self._loaded = {}
-        n = 0
-        with torch.cuda.device(device):
-            for name, p in self.state_dict(keep_vars=True).items():
-                tag = (p.data_ptr(), p._version)
-                if self._loaded.get(name) == tag:
-                    continue
-                t = p.detach()
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    t = t.float().contiguous()
-                on_dev = 1 if t.is_cuda else 0
-                if t.is_cuda and t.device != device:
-                    t = t.to(device)
-                shape = (C.c_int64 * t.dim())(*t.shape)
-                self._check(lib.cwm_model_load_weight(h, name.encode(), t.data_ptr(), on_dev, shape, t.dim()))
-                self._loaded[name] = tag
-                n += 1
-        self._remember_params()
-        return n
-
-    def invalidate_weights(self):
-        """Forget what has been uploaded: the next forward re-packs every parameter (see `sync_weights`)."""
-        self._loaded = {}
-        self._plist = None
+        return lib.cwm_model_create(C.byref(ccfg), C.byref(h))
 
     def _run(self, x, strides, normalize, mask, n_vis, want_video, xraw=None, check=True, out_tokens=None, out_video=None, weights_synced=False):
         _lib.require_gpu()
         if not x.is_cuda:
             raise RuntimeError("PretrainVisionTransformer.forward needs a CUDA/HIP tensor (no CPU fallback); got %s" % x.device)
-        lib = self._library()
         dev = x.device
         if not weights_synced or self._handle is None or self._handle_device != dev:
             self.sync_weights(dev)
@@ -318,7 +176,7 @@ class PretrainVisionTransformer(WeightSync, nn.Module):
             _lib.ptr(video), _lib.ptr(xraw), _lib.mode_id(self.mode), int(check), _lib.current_stream_handle(dev),
         )
         with torch.cuda.device(dev):
-            self._check(lib.cwm_forward(self._handle, C.byref(args)))
+            self._check(self._fn["forward"](self._handle, C.byref(args)))
         return y, video
 
     @staticmethod
@@ -367,25 +225,6 @@ class PretrainVisionTransformer(WeightSync, nn.Module):
         # parameters overlaps the previous call's kernels instead of delaying this call's first launch)
         return self._run(x, strides, normalize, mask, n_vis, True, xraw=x, check=check, out_tokens=out_tokens, out_video=out_video,
                          weights_synced=weights_synced)
-
-    # ---- execution options ----------------------------------------------------------------------------
-    def set_lanes(self, lanes: int):
-        """1: every kernel on the current stream; 2 (library default): batches whose halves keep >= 3000 encoder rows (ViT-B/8: batch >= 8) run as two half batches on two HIP
-        streams (forked / joined inside the library), which fills the idle time between dependent kernels."""
-        if self._handle is None:
-            raise RuntimeError("run a forward pass (or sync_weights) before set_lanes")
-        self._check(self._library().cwm_model_set_lanes(self._handle, int(lanes)))
-
-    # ---- kernel timing (bench.py roofline) ------------------------------------------------------------
-    def timing_enable(self, kclass: int, enable: bool = True):
-        if self._handle is None:
-            raise RuntimeError("run a forward pass (or sync_weights) before enabling timing")
-        self._check(self._library().cwm_timing_enable(self._handle, kclass, int(enable)))
-
-    def timing_collect(self, kclass: int):
-        st = _lib.CwmKernelStats()
-        self._check(self._library().cwm_timing_collect(self._handle, kclass, C.byref(st)))
-        return {"launches": st.launches, "total_ms": st.total_ms, "total_flops": st.total_flops}
 
 
 # ---- factories (same names / defaults as vmae.py:597-619) -------------------------------------------

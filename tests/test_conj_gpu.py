@@ -53,6 +53,20 @@ def test_tiny_conj_golden_ragged_and_wrapper():
     assert np.abs(yf - g["y_tokens"]).max() <= 8e-2
 
 
+def test_parameters_on_another_device_are_moved_before_upload():
+    """`sync_weights` of the shared handle base moves a CUDA parameter that lives on another device than the handle's before it hands the library the pointer
+    (the conjoined model used to pass `cuda:0`'s pointer as a device pointer of `cuda:1`).  Needs two visible devices."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs a second visible GPU")
+    g = np.load(os.path.join(GOLDEN, "conj_tiny.npz"))
+    m = build(TINY_CONJ, int(g["seed"]))                                     # parameters on cuda:0
+    G = prediction.PredictorBasedGenerator(predictor=m, imagenet_normalize_inputs=True, temporal_dim=2)
+    x, mask, imu, mc = (torch.from_numpy(g[k]).to("cuda:1") for k in ("x", "mask", "imu", "mask_context"))
+    assert m.sync_weights(torch.device("cuda:1")) == len(m.state_dict()) and next(m.parameters()).device == torch.device("cuda:0")
+    y = m(G._preprocess(x), mask, x_context=imu, mask_context=mc)
+    assert y.device == torch.device("cuda:1") and np.abs(y.cpu().numpy() - g["y_tokens"]).max() <= 3e-4
+
+
 def test_imu400_full_size_golden():
     g = np.load(os.path.join(GOLDEN, "conj_imu400_b2.npz"))
     cfg = C.CONJ_CONFIGS["imu400_base_4x4patch_2frames_1tube"]

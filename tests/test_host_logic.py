@@ -129,7 +129,7 @@ def test_oracle_spec_matches_config():
 
 
 def test_weight_sync_signature_sees_every_way_a_parameter_can_change():
-    """vmae.WeightSync (no GPU needed: only the host-side change detector).  Cases from the round-2 review: `p.data = t` (new storage,
+    """_handle.LibraryModule on a real model (no GPU needed: only the host-side change detector).  Cases from the round-2 review: `p.data = t` (new storage,
     same version counter), a dtype conversion of a SUBMODULE (never reaches the top-level `_apply`), a Parameter replaced with setattr."""
     import torch
     from counterfactualworldmodels_amd import config as C, vmae
@@ -159,6 +159,44 @@ def test_weight_sync_signature_sees_every_way_a_parameter_can_change():
     m._remember_params()
     m.load_state_dict(m.state_dict())          # post hook forgets the list
     assert not m._params_unchanged()
+
+
+def test_the_three_model_kinds_share_one_handle_base(monkeypatch):
+    """One `_handle.LibraryModule` behind the VMAE predictor, the conjoined predictors and RAFT: none of them carries a copy of the handle plumbing, an entry
+    point a model kind does not have (`cwm_raft_*`: no options, lanes or timing) raises a RuntimeError naming the class, and what needs a handle says so
+    before it reaches the library."""
+    from counterfactualworldmodels_amd import _handle, _lib, conjoined_vmae as CV, raft
+    from test_conj_oracle import TINY_CONJ
+
+    shared = ("sync_weights", "_ensure_handle", "_release", "__del__", "invalidate_weights", "use_library", "set_option", "set_lanes", "timing_enable",
+              "timing_collect", "_library", "_check", "_params_unchanged", "_remember_params")
+    for cls in (vmae.PretrainVisionTransformer, CV.ConjoinedPaddedVisionTransformer, CV.ConjoinedPretrainVisionTransformer, raft.RAFT):
+        assert issubclass(cls, _handle.LibraryModule)
+        for klass in cls.__mro__[:cls.__mro__.index(_handle.LibraryModule)]:
+            assert not [n for n in shared if n in vars(klass)], klass
+        assert {"destroy", "load_weight", "forward"} <= set(cls._ABI) and all(name in _lib.SIGNATURES for name in cls._ABI.values())
+        assert "_create" in vars(cls)
+    assert vmae._NoForward is raft._NoForward is CV._NoForward is _handle._NoForward
+
+    def no_library(*a, **k):
+        raise AssertionError("the library must not be reached")
+
+    monkeypatch.setattr(_lib, "get_lib", no_library)
+    flow = raft.RAFT()
+    for call in (lambda: flow.set_option("gemm_tile", 1), lambda: flow.set_lanes(1), lambda: flow.timing_enable(0), lambda: flow.timing_collect(0)):
+        with pytest.raises(RuntimeError, match="RAFT has no"):
+            call()
+    assert "_options" not in flow.__dict__
+    for m in (CV.ConjoinedPaddedVisionTransformer(TINY_CONJ), vmae.PretrainVisionTransformer(TINY)):
+        for call in (lambda: m.timing_enable(0), lambda: m.timing_collect(0), lambda: m.set_lanes(1)):
+            with pytest.raises(RuntimeError, match=r"run a forward pass \(or sync_weights\) before"):
+                call()
+        m.set_option("attn_kernel", 3)   # remembered for the handle to come, validated by the host mirror
+        assert m.__dict__["_options"] == {"attn_kernel": 3}
+        with pytest.raises(_lib.CwmHipError):
+            m.set_option("no_such_option", 1)
+        m.invalidate_weights()
+        assert m._handle is None and not m._params_unchanged()
 
 
 def test_bench_helpers_on_cpu(tmp_path, monkeypatch):
