@@ -163,6 +163,7 @@ class CwmRaftForwardArgs(C.Structure):
         ("head_stride_b", C.c_int64),
         ("head_stride_t", C.c_int64),
         ("head_stride_c", C.c_int64),
+        ("mode", C.c_int32),  # appended in 0.10.2: 0 or MODE_PARITY = parity, MODE_FAST = bf16-operand convolutions
     ]
 
 

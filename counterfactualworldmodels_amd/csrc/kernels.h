@@ -299,7 +299,7 @@ struct Im2colParams {
     int img0;
     int n_img, H, W, OH, OW, kh, kw, stride, pad_h, pad_w;
     int c_lo, c_hi;  // c_hi > c_lo: rewrite only input channels [c_lo, c_hi) of every tap (the rest of A, K padding included, is kept)
-    bf16* A;         // parity layout [n_img * OH * OW][2 * Kpad], K order (ky, kx, c), zero padded
+    bf16* A;         // [n_img * OH * OW] rows of Kpad (planes = 1) or 2 * Kpad (planes = 2, parity layout), K order (ky, kx, c), zero padded
     int Kpad;
 };
 struct CorrLookupParams {
@@ -307,7 +307,7 @@ struct CorrLookupParams {
     int h[4], w[4], levels;
     const float* coords;  // [M][2]
     int64_t M;
-    bf16* A;              // [M][2 * Kpad] parity layout, feature l*81 + a*9 + b, zero padded
+    bf16* A;              // [M] rows of Kpad (planes = 1) or 2 * Kpad (planes = 2, parity layout), feature l*81 + a*9 + b, zero padded
     int Kpad;
     float* out;           // instead of A (out != nullptr): fp32 [M][out_ld], features [0, levels*81) (cwm_raft_corr_lookup)
     int out_ld;
@@ -322,7 +322,8 @@ struct ConvexUpParams {
     float* out;           // pair pr = (g, t): out + g * out_sb + t * out_st + c * out_sc + Y * 8w8 + X
     int64_t out_sb, out_st, out_sc;
 };
-int launch_im2col(const Im2colParams& p, hipStream_t s);
+// planes: the layout of A (common.h a_pos): 2 = split-bf16 hi / lo (parity), 1 = one bf16 plane (fast); the same for launch_corr_lookup
+int launch_im2col(const Im2colParams& p, int planes, hipStream_t s);
 // stats [n_img][C] (mean, rstd) pairs; work: 2 * n_img * kInstNormMaxChunks * C doubles
 constexpr int kInstNormMaxChunks = 16;
 int launch_instnorm_stats(const float* x, int n_img, int HW, int C, float eps, float* stats, double* work, hipStream_t s);
@@ -331,7 +332,7 @@ int launch_cnet_split(const float* cn, int64_t M, float* h, float* x, hipStream_
 int launch_coords_init(float* coords, int64_t M, int h8, int w8, hipStream_t s);
 int launch_corr(const float* f1, const float* f2, int P, int N, int D, float* corr, hipStream_t s);
 int launch_corr_pool(const float* in, int64_t maps, int h, int w, float* out, hipStream_t s);
-int launch_corr_lookup(const CorrLookupParams& p, hipStream_t s);
+int launch_corr_lookup(const CorrLookupParams& p, int planes, hipStream_t s);
 int launch_motion_finish(float* x, const float* coords, int64_t M, int h8, int w8, hipStream_t s);
 int launch_gru_update(float* h, const float* zr, const float* q, int64_t M, hipStream_t s);
 int launch_flow_update(float* coords, const float* delta, int ld, int64_t M, hipStream_t s);

@@ -1,6 +1,6 @@
 // RAFT-large optical flow (cwm/models/raft): the kernels around the convolution GEMMs.  Activations are fp32 NHWC; a convolution is an
-// explicit im2col into the GEMM's split-bf16 A operand (common.h a_pos, K order (ky, kx, c), zero padded to Kpad) and one launch_gemm with
-// the EPI_F32 epilogue.  Activation functions, normalisations and the GRU's r*h are applied where an operand is read, never as a pass of
+// explicit im2col into the GEMM's A operand (common.h a_pos: split-bf16 hi/lo in parity mode, one bf16 plane in fast mode; K order
+// (ky, kx, c), zero padded to Kpad) and one launch_gemm with the EPI_F32 epilogue.  Activation functions, normalisations and the GRU's r*h are applied where an operand is read, never as a pass of
 // their own, except the residual join of the encoders and the GRU state update.
 #include <math.h>
 
@@ -14,12 +14,17 @@ namespace {
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
 
-__device__ __forceinline__ void store_split(bf16* A, int64_t row, int Kpad, int k, float v) {
-    bf16 h, l;
-    split_bf16(v, h, l);
-    bf16* d = A + a_pos<2>(row, Kpad, k);
-    d[0] = h;
-    d[kLoOffset] = l;
+template <int PLANES>
+__device__ __forceinline__ void store_operand(bf16* A, int64_t row, int Kpad, int k, float v) {
+    bf16* d = A + a_pos<PLANES>(row, Kpad, k);
+    if constexpr (PLANES == 1) {
+        d[0] = (bf16)v;
+    } else {
+        bf16 h, l;
+        split_bf16(v, h, l);
+        d[0] = h;
+        d[kLoOffset] = l;
+    }
 }
 
 // value of channel c of one source at pixel `pix` (of image `img`, spatial position (y, x))
@@ -36,7 +41,9 @@ __device__ __forceinline__ float src_value(const ConvSrc& s, int64_t pix, int im
 }
 
 // One thread per 8 consecutive k of one row: they lie in one [32 hi | 32 lo] block of the parity layout, so the thread ends with one
-// 16-byte store per plane.  (K order (ky, kx, c): the 8 channels of a thread come from at most two taps.)
+// 16-byte store per plane.  (K order (ky, kx, c): the 8 channels of a thread come from at most two taps.)  PLANES == 1 (fast mode): the
+// same values rounded once to bf16 into the row-major one-plane layout, one 16-byte store per thread, consecutive threads consecutive.
+template <int PLANES>
 __global__ void im2col_kernel(const Im2colParams p) {
     const int Ctot = p.src[0].C + (p.nsrc > 1 ? p.src[1].C : 0);
     const int K = p.kh * p.kw * Ctot;
@@ -73,18 +80,22 @@ __global__ void im2col_kernel(const Im2colParams p) {
                     }
                 }
             }
-            bf16 h, l;
-            split_bf16(v, h, l);
-            hv[j] = h;
-            lv[j] = l;
+            if constexpr (PLANES == 1) {
+                hv[j] = (bf16)v;
+            } else {
+                bf16 h, l;
+                split_bf16(v, h, l);
+                hv[j] = h;
+                lv[j] = l;
+            }
             if (++c == Ctot) {
                 c = 0;
                 ++tap;
             }
         }
-        bf16* d = p.A + a_pos<2>(m, p.Kpad, kb);
+        bf16* d = p.A + a_pos<PLANES>(m, p.Kpad, kb);
         *reinterpret_cast<bf16x8*>(d) = hv;
-        *reinterpret_cast<bf16x8*>(d + kLoOffset) = lv;
+        if constexpr (PLANES == 2) *reinterpret_cast<bf16x8*>(d + kLoOffset) = lv;
     }
 }
 
@@ -215,7 +226,9 @@ __global__ void corr_pool_kernel(const float* in, int64_t maps, int h, int w, fl
 }
 
 // CorrBlock.__call__: feature l*81 + a*9 + b of row m samples level l at (x + a - 4, y + b - 4) (the meshgrid(dy, dx) order), bilinear with
-// zero padding as grid_sample(align_corners=True) after bilinear_sampler's normalisation; written as convc1's A operand (Kpad 384)
+// zero padding as grid_sample(align_corners=True) after bilinear_sampler's normalisation; written as convc1's A operand (Kpad 384) in the
+// layout of PLANES, or as fp32 (p.out)
+template <int PLANES>
 __global__ void corr_lookup_kernel(const CorrLookupParams p) {
     const int64_t total = p.M * (int64_t)p.Kpad;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -240,7 +253,7 @@ __global__ void corr_lookup_kernel(const CorrLookupParams p) {
             continue;
         }
         if (p.out) p.out[m * p.out_ld + f] = v;
-        else store_split(p.A, m, p.Kpad, f, v);
+        else store_operand<PLANES>(p.A, m, p.Kpad, f, v);
     }
 }
 
@@ -391,12 +404,12 @@ unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 25
 
 }  // namespace
 
-int launch_im2col(const Im2colParams& p, hipStream_t s) {
+int launch_im2col(const Im2colParams& p, int planes, hipStream_t s) {
     CWM_REQUIRE(p.Kpad % 64 == 0 && (p.c_hi <= p.c_lo || (p.c_lo % 8 == 0 && p.c_hi % 8 == 0)), "im2col: Kpad = %d, channel range [%d, %d)", p.Kpad,
                 p.c_lo, p.c_hi);
     const int64_t total = (int64_t)p.n_img * p.OH * p.OW * (p.Kpad / 8);
     CWM_REQUIRE(total < (1ll << 31), "im2col: %lld groups exceed 32-bit indexing", (long long)total);
-    hipLaunchKernelGGL(im2col_kernel, dim3(grid_for(total)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(planes == 2 ? im2col_kernel<2> : im2col_kernel<1>, dim3(grid_for(total)), dim3(256), 0, s, p);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -445,8 +458,8 @@ int launch_corr_pool(const float* in, int64_t maps, int h, int w, float* out, hi
     return 0;
 }
 
-int launch_corr_lookup(const CorrLookupParams& p, hipStream_t s) {
-    hipLaunchKernelGGL(corr_lookup_kernel, dim3(grid_for(p.M * p.Kpad)), dim3(256), 0, s, p);
+int launch_corr_lookup(const CorrLookupParams& p, int planes, hipStream_t s) {
+    hipLaunchKernelGGL(planes == 2 ? corr_lookup_kernel<2> : corr_lookup_kernel<1>, dim3(grid_for(p.M * p.Kpad)), dim3(256), 0, s, p);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -1,7 +1,9 @@
 // RAFT-large optical flow behind the C ABI (include/cwm_hip.h cwm_raft_*): cwm/models/raft/raft_model.py:103-300 in its inference
 // configuration -- BasicEncoder fnet (instance norm) and cnet (eval batch norm, folded into the convolutions at load), 4-level all-pairs
 // correlation of radius 4, BasicUpdateBlock with SepConvGRU, convex upsampling.  Every convolution is an im2col (raft_kernels.hip) and a
-// parity (split-bf16) GEMM on launch_gemm whose fp32 epilogue writes straight into a channel slice of an NHWC buffer.  The mask head and
+// GEMM on launch_gemm whose fp32 epilogue writes straight into a channel slice of an NHWC buffer.  The call chooses the arithmetic of these
+// convolutions (cwm_raft_forward_args.mode): parity (split-bf16 operands, planes = 2) or fast (one bf16 plane per operand, planes = 1);
+// everything between them -- norm statistics, residual join, correlation, lookup, coordinates, GRU update, upsampling -- is fp32 in both.  The mask head and
 // the upsampling run once, after the last iteration (the reference computes them every iteration and returns the last).  So does the optional
 // output head (raft_model.py:152-159, output_dim = 1: the keypoint predictor): output_block.0 as one more 3x3 convolution, then the 256 -> 1
 // projection and the one-channel convex upsampling as kernels of their own (raft_kernels.hip).
@@ -13,7 +15,7 @@ using namespace cwm;
 
 namespace {
 
-constexpr int kPlanes = 2;
+constexpr int kMaxPlanes = 2;  // the im2col workspaces hold the parity layout, so one handle serves both modes
 constexpr int kFeat = 256;  // fnet output width
 constexpr int kLookupKpad = 384;  // 4 levels x 81 = 324 correlation features, padded to the GEMM's K granule
 constexpr int kMaxEncImages = 32;  // images per encoder pass (bounds the im2col buffer: 29 MB per 224^2 image)
@@ -50,7 +52,7 @@ struct Encoder {
 };
 
 __global__ void pack_conv_kernel(const float* w, const float* gamma, const float* var, float eps, int N, int C, int kh, int kw, int Kpad, int row0,
-                                 bf16* il) {
+                                 bf16* il, bf16* hi) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)N * Kpad) return;
     const int n = (int)(i / Kpad), k = (int)(i - (int64_t)n * Kpad);
@@ -65,6 +67,7 @@ __global__ void pack_conv_kernel(const float* w, const float* gamma, const float
     bf16* d = il + a_pos<2>(row0 + n, Kpad, k);
     d[0] = h;
     d[kLoOffset] = l;
+    hi[a_pos<1>(row0 + n, Kpad, k)] = h;  // the fast plane: the folded weight rounded once (split_bf16's hi is (bf16)v)
 }
 
 __global__ void pack_bias_kernel(const float* b, const float* gamma, const float* beta, const float* mean, const float* var, float eps, int N,
@@ -192,7 +195,7 @@ int prepare(cwm_raft_model* m) {
             }
             const int64_t total = (int64_t)p.n * cv->L.Kpad;
             hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, m->raw[p.w].dev, g, var, 1e-5f, p.n, cv->cin,
-                               cv->kh, cv->kw, cv->L.Kpad, row0, cv->L.w_il);
+                               cv->kh, cv->kw, cv->L.Kpad, row0, cv->L.w_il, cv->L.w);
             hipLaunchKernelGGL(pack_bias_kernel, dim3((p.n + 255) / 256), dim3(256), 0, 0, m->raw[p.b].dev, g, be, mu, var, 1e-5f, p.n, cv->L.bias + row0);
             row0 += p.n;
         }
@@ -218,11 +221,11 @@ int ensure_workspace(cwm_raft_model* m, int P, int H, int W) {
     int rc = 0;
     for (int i = 0; i < 4 && !rc; ++i) rc = E.ws(&m->enc_act[i], (size_t)(n * hw2 * 64));
     for (int i = 0; i < 4 && !rc; ++i) rc = E.ws(&m->enc_stats[i], (size_t)(n * 128 * 2));
-    if (rc || (rc = E.ws(&m->enc_A, (size_t)(n * hw2 * 576 * 2))) || (rc = E.ws(&m->enc_norm_work, (size_t)(2 * n * kInstNormMaxChunks * 128))))
+    if (rc || (rc = E.ws(&m->enc_A, (size_t)(n * hw2 * 576 * kMaxPlanes))) || (rc = E.ws(&m->enc_norm_work, (size_t)(2 * n * kInstNormMaxChunks * 128))))
         return rc;
     if ((rc = E.ws(&m->fmap, (size_t)(2 * M * kFeat))) || (rc = E.ws(&m->cn, (size_t)(M * 256)))) return rc;
     for (int l = 0; l < 4 && !rc; ++l) rc = E.ws(&m->pyr[l], (size_t)(M * level_sides(H / 8, l) * level_sides(W / 8, l)));
-    if (rc || (rc = E.ws(&m->corrA, (size_t)(M * kLookupKpad * 2))) || (rc = E.ws(&m->updA, (size_t)(M * 2304 * 2)))) return rc;
+    if (rc || (rc = E.ws(&m->corrA, (size_t)(M * kLookupKpad * kMaxPlanes))) || (rc = E.ws(&m->updA, (size_t)(M * 2304 * kMaxPlanes)))) return rc;
     if ((rc = E.ws(&m->c1, (size_t)(M * 256))) || (rc = E.ws(&m->cf, (size_t)(M * 256))) || (rc = E.ws(&m->f1, (size_t)(M * 128))) ||
         (rc = E.ws(&m->x, (size_t)(M * 256))) || (rc = E.ws(&m->h, (size_t)(M * 128))) || (rc = E.ws(&m->zrb, (size_t)(M * 256))) ||
         (rc = E.ws(&m->qb, (size_t)(M * 128))) || (rc = E.ws(&m->fh, (size_t)(M * 256))) || (rc = E.ws(&m->d, (size_t)(M * 16))) ||
@@ -234,8 +237,9 @@ int ensure_workspace(cwm_raft_model* m, int P, int H, int W) {
     return 0;
 }
 
-// one convolution: im2col of `ip` (its sources, image and channel range already set) into A, then the GEMM into C (row stride ldc)
-int run_conv(cwm_raft_model* m, const RaftConv& cv, Im2colParams ip, int n_img, int H, int W, bf16* A, float* C, int ldc, hipStream_t s,
+// one convolution: im2col of `ip` (its sources, image and channel range already set) into A, then the GEMM into C (row stride ldc), both in
+// the operand layout of `planes`
+int run_conv(cwm_raft_model* m, const RaftConv& cv, Im2colParams ip, int n_img, int H, int W, bf16* A, float* C, int ldc, int planes, hipStream_t s,
              bool skip_im2col = false) {
     ip.n_img = n_img;
     ip.H = H;
@@ -250,12 +254,12 @@ int run_conv(cwm_raft_model* m, const RaftConv& cv, Im2colParams ip, int n_img, 
     ip.A = A;
     ip.Kpad = cv.L.Kpad;
     if (!skip_im2col)
-        if (int rc = launch_im2col(ip, s)) return rc;
-    GemmParams g = gemm_base(A, cv.L.Kpad, cv.L, n_img * ip.OH * ip.OW, kPlanes);
+        if (int rc = launch_im2col(ip, planes, s)) return rc;
+    GemmParams g = gemm_base(A, cv.L.Kpad, cv.L, n_img * ip.OH * ip.OW, planes);
     g.epi = EPI_F32;
     g.C = C;
     g.ldc = ldc;
-    return m->eng.run_gemm(g, kPlanes, s);
+    return m->eng.run_gemm(g, planes, s);
 }
 
 Im2colParams im2col_of(const ConvSrc& a, const ConvSrc* b = nullptr) {
@@ -271,7 +275,7 @@ Im2colParams im2col_of(const ConvSrc& a, const ConvSrc* b = nullptr) {
 }
 
 // BasicEncoder.forward (extractor.py:160-192) on images [img0, img0 + n) of `image`; output [n][H/8 * W/8][out width] at `out`
-int run_encoder(cwm_raft_model* m, const Encoder& e, const ImageSrc& image, int img0, int n, int H, int W, float* out, hipStream_t s) {
+int run_encoder(cwm_raft_model* m, const Encoder& e, const ImageSrc& image, int img0, int n, int H, int W, float* out, int planes, hipStream_t s) {
     int rc;
     float** act = m->enc_act;
     float** st = m->enc_stats;
@@ -280,7 +284,7 @@ int run_encoder(cwm_raft_model* m, const Encoder& e, const ImageSrc& image, int 
     Im2colParams ip = im2col_of(src_of(nullptr, 3));
     ip.image = image;
     ip.img0 = img0;
-    if ((rc = run_conv(m, e.conv1, ip, n, H, W, m->enc_A, act[0], 64, s))) return rc;
+    if ((rc = run_conv(m, e.conv1, ip, n, H, W, m->enc_A, act[0], 64, planes, s))) return rc;
     int h = H / 2, w = W / 2, C = 64;
     if (e.instance && (rc = launch_instnorm_stats(act[0], n, h * w, C, eps, st[0], m->enc_norm_work, s))) return rc;
     ConvSrc a = src_of(act[0], C, e.instance ? st[0] : nullptr, 1);
@@ -289,13 +293,13 @@ int run_encoder(cwm_raft_model* m, const Encoder& e, const ImageSrc& image, int 
         const int dim = B.c1.L.N, stride = B.c1.stride;
         const int oh = (h - 1) / stride + 1, ow = (w - 1) / stride + 1;
         // y = relu(norm1(conv1(x))); y = relu(norm2(conv2(y)))
-        if ((rc = run_conv(m, B.c1, im2col_of(a), n, h, w, m->enc_A, act[1], dim, s))) return rc;
+        if ((rc = run_conv(m, B.c1, im2col_of(a), n, h, w, m->enc_A, act[1], dim, planes, s))) return rc;
         if (e.instance && (rc = launch_instnorm_stats(act[1], n, oh * ow, dim, eps, st[1], m->enc_norm_work, s))) return rc;
-        if ((rc = run_conv(m, B.c2, im2col_of(src_of(act[1], dim, e.instance ? st[1] : nullptr, 1)), n, oh, ow, m->enc_A, act[2], dim, s))) return rc;
+        if ((rc = run_conv(m, B.c2, im2col_of(src_of(act[1], dim, e.instance ? st[1] : nullptr, 1)), n, oh, ow, m->enc_A, act[2], dim, planes, s))) return rc;
         if (e.instance && (rc = launch_instnorm_stats(act[2], n, oh * ow, dim, eps, st[2], m->enc_norm_work, s))) return rc;
         ConvSrc X = a;
         if (B.has_down) {  // x = norm3(downsample(x))
-            if ((rc = run_conv(m, B.down, im2col_of(a), n, h, w, m->enc_A, act[3], dim, s))) return rc;
+            if ((rc = run_conv(m, B.down, im2col_of(a), n, h, w, m->enc_A, act[3], dim, planes, s))) return rc;
             if (e.instance && (rc = launch_instnorm_stats(act[3], n, oh * ow, dim, eps, st[3], m->enc_norm_work, s))) return rc;
             X = src_of(act[3], dim, e.instance ? st[3] : nullptr, 0);
         }
@@ -306,11 +310,12 @@ int run_encoder(cwm_raft_model* m, const Encoder& e, const ImageSrc& image, int 
         w = ow;
         C = dim;
     }
-    return run_conv(m, e.conv2, im2col_of(a), n, h, w, m->enc_A, out, e.conv2.L.N, s);
+    return run_conv(m, e.conv2, im2col_of(a), n, h, w, m->enc_A, out, e.conv2.L.N, planes, s);
 }
 
 int forward(cwm_raft_model* m, const cwm_raft_forward_args& a) {
     hipStream_t s = (hipStream_t)a.stream;
+    const int planes = a.mode == CWM_MODE_FAST ? 1 : 2;
     const int ppg = a.pairs > 0 ? a.pairs : 1;
     const int P = a.batch * ppg, H = a.height, W = a.width, h8 = H / 8, w8 = W / 8;
     const int64_t hw8 = (int64_t)h8 * w8, M = P * hw8;
@@ -328,12 +333,12 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a) {
     // feature network over image1 and image2 of every pair (instance norm is per image: any grouping gives the same result)
     for (int i0 = 0; i0 < 2 * P; i0 += kMaxEncImages) {
         const int n = std::min(kMaxEncImages, 2 * P - i0);
-        if ((rc = run_encoder(m, m->fnet, img, i0, n, H, W, m->fmap + (int64_t)i0 * hw8 * kFeat, s))) return rc;
+        if ((rc = run_encoder(m, m->fnet, img, i0, n, H, W, m->fmap + (int64_t)i0 * hw8 * kFeat, planes, s))) return rc;
     }
     // context network over image1
     for (int i0 = 0; i0 < P; i0 += kMaxEncImages) {
         const int n = std::min(kMaxEncImages, P - i0);
-        if ((rc = run_encoder(m, m->cnet, img, i0, n, H, W, m->cn + (int64_t)i0 * hw8 * 256, s))) return rc;
+        if ((rc = run_encoder(m, m->cnet, img, i0, n, H, W, m->cn + (int64_t)i0 * hw8 * 256, planes, s))) return rc;
     }
     if ((rc = launch_cnet_split(m->cn, M, m->h, m->x, s))) return rc;
     // correlation pyramid
@@ -358,34 +363,34 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a) {
     flow_src.coords = m->coords;
     for (int it = 0; it < a.iters; ++it) {
         // BasicMotionEncoder
-        if ((rc = launch_corr_lookup(lp, s))) return rc;
-        if ((rc = run_conv(m, m->convc1, Im2colParams{}, P, h8, w8, m->corrA, m->c1, 256, s, true))) return rc;
-        if ((rc = run_conv(m, m->convc2, im2col_of(src_of(m->c1, 256, nullptr, 1)), P, h8, w8, m->updA, m->cf, 256, s))) return rc;
-        if ((rc = run_conv(m, m->convf1, im2col_of(flow_src), P, h8, w8, m->updA, m->f1, 128, s))) return rc;
-        if ((rc = run_conv(m, m->convf2, im2col_of(src_of(m->f1, 128, nullptr, 1)), P, h8, w8, m->updA, m->cf + 192, 256, s))) return rc;
-        if ((rc = run_conv(m, m->conv, im2col_of(src_of(m->cf, 256, nullptr, 1)), P, h8, w8, m->updA, m->x + 128, 256, s))) return rc;
+        if ((rc = launch_corr_lookup(lp, planes, s))) return rc;
+        if ((rc = run_conv(m, m->convc1, Im2colParams{}, P, h8, w8, m->corrA, m->c1, 256, planes, s, true))) return rc;
+        if ((rc = run_conv(m, m->convc2, im2col_of(src_of(m->c1, 256, nullptr, 1)), P, h8, w8, m->updA, m->cf, 256, planes, s))) return rc;
+        if ((rc = run_conv(m, m->convf1, im2col_of(flow_src), P, h8, w8, m->updA, m->f1, 128, planes, s))) return rc;
+        if ((rc = run_conv(m, m->convf2, im2col_of(src_of(m->f1, 128, nullptr, 1)), P, h8, w8, m->updA, m->cf + 192, 256, planes, s))) return rc;
+        if ((rc = run_conv(m, m->conv, im2col_of(src_of(m->cf, 256, nullptr, 1)), P, h8, w8, m->updA, m->x + 128, 256, planes, s))) return rc;
         if ((rc = launch_motion_finish(m->x, m->coords, M, h8, w8, s))) return rc;
         // SepConvGRU: (1,5) then (5,1)
         for (int pass = 0; pass < 2; ++pass) {
             const ConvSrc xs = src_of(m->x, 256);
-            if ((rc = run_conv(m, m->zr[pass], im2col_of(src_of(m->h, 128), &xs), P, h8, w8, m->updA, m->zrb, 256, s))) return rc;
+            if ((rc = run_conv(m, m->zr[pass], im2col_of(src_of(m->h, 128), &xs), P, h8, w8, m->updA, m->zrb, 256, planes, s))) return rc;
             ConvSrc rh = src_of(m->h, 128);
             rh.gate = m->zrb + 128;
             rh.gate_ld = 256;
             Im2colParams iq = im2col_of(rh, &xs);
             iq.c_lo = 0;
             iq.c_hi = 128;  // only the h channels change: the x half of every tap is still in A
-            if ((rc = run_conv(m, m->q[pass], iq, P, h8, w8, m->updA, m->qb, 128, s))) return rc;
+            if ((rc = run_conv(m, m->q[pass], iq, P, h8, w8, m->updA, m->qb, 128, planes, s))) return rc;
             if ((rc = launch_gru_update(m->h, m->zrb, m->qb, M, s))) return rc;
         }
         // FlowHead; coords1 += delta
-        if ((rc = run_conv(m, m->fh1, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, s))) return rc;
-        if ((rc = run_conv(m, m->fh2, im2col_of(src_of(m->fh, 256, nullptr, 1)), P, h8, w8, m->updA, m->d, 16, s))) return rc;
+        if ((rc = run_conv(m, m->fh1, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, planes, s))) return rc;
+        if ((rc = run_conv(m, m->fh2, im2col_of(src_of(m->fh, 256, nullptr, 1)), P, h8, w8, m->updA, m->d, 16, planes, s))) return rc;
         if ((rc = launch_flow_update(m->coords, m->d, 16, M, s))) return rc;
     }
     // mask = 0.25 * mask.2(relu(mask.0(net))), once; convex upsampling of the last flow (skipped when only the head output is asked for)
-    if ((rc = run_conv(m, m->mask0, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, s))) return rc;
-    if ((rc = run_conv(m, m->mask2, im2col_of(src_of(m->fh, 256, nullptr, 1)), P, h8, w8, m->updA, m->mask, 576, s))) return rc;
+    if ((rc = run_conv(m, m->mask0, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, planes, s))) return rc;
+    if ((rc = run_conv(m, m->mask2, im2col_of(src_of(m->fh, 256, nullptr, 1)), P, h8, w8, m->updA, m->mask, 576, planes, s))) return rc;
     ConvexUpParams up;
     memset(&up, 0, sizeof(up));
     up.coords = m->coords;
@@ -405,7 +410,7 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a) {
     if (a.head_dev) {
         // out = output_block.2(relu(output_block.0(net))), upsampled with the same mask in place of the flow (raft_model.py:257-267).  `fh` is free
         // once mask.2 has read it, and `d` (the flow head's delta) once the last flow update has: the projected map goes there.
-        if ((rc = run_conv(m, m->out0, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, s))) return rc;
+        if ((rc = run_conv(m, m->out0, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, planes, s))) return rc;
         if ((rc = launch_head_project(m->fh, 256, m->raw[kHeadKeys[2]].dev, m->raw[kHeadKeys[3]].dev, M, m->d, s))) return rc;
         ConvexUp1Params u1;
         memset(&u1, 0, sizeof(u1));
@@ -502,7 +507,8 @@ extern "C" int cwm_raft_missing_weights(cwm_raft_model* m, char* buf, int buflen
 
 extern "C" int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* args) {
     CWM_REQUIRE(m && args, "cwm_raft_forward: null argument");
-    // a caller built against the 0.10.0 header (the struct ended at `stream`) passes that size: the fields appended since read as zero
+    // a caller built against the 0.10.0 header (the struct ended at `stream`) or the 0.10.1 one (at `head_stride_c`) passes that size: the fields
+    // appended since read as zero (no head; mode 0 = parity)
     cwm_raft_forward_args a_copy;
     if (int rc = copy_args(a_copy, args, offsetof(cwm_raft_forward_args, stream) + sizeof(void*), "cwm_raft_forward")) return rc;
     const cwm_raft_forward_args& a = a_copy;
@@ -515,8 +521,11 @@ extern "C" int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* 
                 "cwm_raft_forward: H / 8 = %d and W / 8 = %d must be at least 16 (the coarsest correlation level would have a side of 1)", a.height / 8,
                 a.width / 8);
     CWM_REQUIRE(a.iters >= 1, "cwm_raft_forward: iters = %d must be >= 1", a.iters);
+    CWM_REQUIRE(a.mode == 0 || a.mode == CWM_MODE_PARITY || a.mode == CWM_MODE_FAST,
+                "cwm_raft_forward: mode = %d must be 0 or CWM_MODE_PARITY (parity) or CWM_MODE_FAST", a.mode);
+    const int planes = a.mode == CWM_MODE_FAST ? 1 : 2;
     const int64_t M = (int64_t)a.batch * std::max(a.pairs, 1) * (a.height / 8) * (a.width / 8);
-    CWM_REQUIRE(M * 2304 * kPlanes < (1ll << 32), "cwm_raft_forward: batch too large (%lld low-resolution pixels): split it", (long long)M);
+    CWM_REQUIRE(M * 2304 * planes < (1ll << 32), "cwm_raft_forward: batch too large (%lld low-resolution pixels): split it", (long long)M);
     char buf[256];
     const int missing = cwm_raft_missing_weights(m, buf, sizeof(buf));
     CWM_REQUIRE(missing == 0, "cwm_raft_forward: %d weights missing (first: %s)", missing, buf);
@@ -552,7 +561,7 @@ extern "C" int cwm_raft_corr_lookup(const float* fmap1_dev, const float* fmap2_d
     lp.Kpad = kLookupKpad;
     lp.out = out_dev;
     lp.out_ld = 324;
-    if (!rc) rc = launch_corr_lookup(lp, s);
+    if (!rc) rc = launch_corr_lookup(lp, 2, s);  // fp32 `out`: the operand layout is not used
     if (hipStreamSynchronize(s) != hipSuccess && !rc) {
         cwm_set_error("cwm_raft_corr_lookup: stream synchronisation failed");
         rc = CWM_ERR_HIP;

@@ -1,9 +1,10 @@
 """RAFT-large optical flow on the GPU: drop-in for `cwm.models.raft.raft_model.load_raft_model` / `RAFT` (raft_model.py:55-300).
 
 The module keeps the reference's parameter tree (179 state-dict tensors: `fnet`, `cnet`, `update_block`), so checkpoints load unchanged,
-and runs its forward pass in libcwm_hip.so (`cwm_raft_forward`): HIP kernels and parity (split-bf16) GEMMs, no PyTorch operator and no
-CPU fallback.  The configuration is the reference's inference one: BasicEncoder fnet (instance norm) and cnet (eval batch norm),
-4 correlation levels of radius 4, BasicUpdateBlock with SepConvGRU, convex upsampling.
+and runs its forward pass in libcwm_hip.so (`cwm_raft_forward`): HIP kernels and GEMMs in parity (split-bf16) arithmetic by default or,
+with `mixed_precision=True` / `set_mode("fast")`, with bf16 operands; no PyTorch operator and no CPU fallback.  The configuration is the reference's inference one:
+BasicEncoder fnet (instance norm) and cnet (eval batch norm), 4 correlation levels of radius 4, BasicUpdateBlock with SepConvGRU, convex
+upsampling.
 
     from counterfactualworldmodels_amd.raft import load_raft_model
     flow_model = load_raft_model("raft-large.pth").cuda().eval()
@@ -15,6 +16,8 @@ value in place of the flow: the keypoint predictor of the demo notebook,
 
     keypoint_predictor = load_raft_model(None, output_dim=1)   # then load_state_dict(checkpoint['model'])
     keypoints = keypoint_predictor.cuda()(x)                   # [B,T-1,1,H,W]
+
+The reference's `--mixed_precision` is the fast mode: `load_raft_model(path, mixed_precision=True)`, or `model.set_mode("fast")` at any time.
 """
 from __future__ import annotations
 
@@ -122,7 +125,11 @@ class RAFT(LibraryModule):
       flow_up [B,2,H,W]).
     `self.iters`, when set, overrides the call's `iters`.  H and W must be multiples of 8 with H/8, W/8 >= 16.
     With `args.output_dim == 1` the 2-channel flow_up above is the 1-channel upsampled `output_block(net)` (raft_model.py:257-267): [B,T-1,1,H,W],
-    and (coords1 - coords0, up [B,1,H,W]) from the two-image call."""
+    and (coords1 - coords0, up [B,1,H,W]) from the two-image call.
+    Arithmetic: `self.mode` is "parity" (split-bf16 convolutions, the default) or "fast" (every convolution with bf16 operands and fp32 accumulation;
+    norm statistics, correlation, lookup, coordinates, GRU update and upsampling stay fp32: the reference's autocast split, raft_model.py:218-252).
+    It is "fast" when `args.mixed_precision` is true and changes with `set_mode`; nothing else chooses it.  In particular fp16 / bf16 frames do NOT turn
+    the fast mode on (the reference's autocast does, raft_model.py:219): they are upcast to fp32 and run in the model's mode."""
 
     def __init__(self, args: Optional[argparse.Namespace] = None):
         super().__init__()
@@ -139,6 +146,7 @@ class RAFT(LibraryModule):
         self.hidden_dim = RAFT_HIDDEN
         self.context_dim = RAFT_HIDDEN
         self._iters = getattr(self.args, "iters", None)
+        self.mode = "fast" if getattr(self.args, "mixed_precision", False) else "parity"
         self.fnet = BasicEncoder(output_dim=256, norm_fn="instance")
         self.cnet = BasicEncoder(output_dim=self.hidden_dim + self.context_dim, norm_fn="batch")
         self.update_block = BasicUpdateBlock(hidden_dim=self.hidden_dim)
@@ -160,13 +168,19 @@ class RAFT(LibraryModule):
         self.iters = value
         return self
 
+    def set_mode(self, mode: str):
+        """"fast" or "parity" for the forwards that follow (the packed weights hold both forms: nothing is re-packed)."""
+        _lib.mode_id(mode)
+        self.mode = mode
+        return self
+
     def freeze_bn(self):
         for m in self.modules():
             if isinstance(m, nn.BatchNorm2d):
                 m.eval()
 
     # ---- C-ABI plumbing (the handle and sync_weights live in _handle.LibraryModule; the library folds the batch norms and packs the
-    # convolutions at the next forward.  cwm_raft_* has no per-handle options, lanes or kernel timing) -------
+    # convolutions at the next forward.  cwm_raft_* has no per-handle options, lanes or kernel timing: the arithmetic mode travels with each call) -------
     _ABI = {role: "cwm_raft_" + role for role in ("destroy", "load_weight", "forward")}
 
     def _create(self, lib, h):
@@ -182,6 +196,7 @@ class RAFT(LibraryModule):
         a.batch, a.pairs, a.height, a.width = B, pairs, H, W
         a.input_scale = float(scale)
         a.iters = int(iters)
+        a.mode = _lib.mode_id(self.mode)
         if self.output_dim is None:
             a.flow_dev = out[0]
             a.flow_stride_b, a.flow_stride_t, a.flow_stride_c = out_strides

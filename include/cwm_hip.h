@@ -382,8 +382,16 @@ CWM_API int cwm_allreduce_sum_f32(cwm_comm* c, float* buf_dev, size_t count, voi
 /* ---- RAFT-large optical flow (0.9) --------------------------------------------------------------------
  * replaces: `load_raft_model(...)` / `RAFT.forward` of cwm/models/raft/raft_model.py:55-300 in the reference's inference
  * configuration (BasicEncoder fnet with instance norm, cnet with eval batch norm, 4 correlation levels of radius 4,
- * BasicUpdateBlock with SepConvGRU, convex upsampling; alternate_corr = False; output_dim = None or 1), in parity (split-bf16)
- * arithmetic.  Weights: the reference's 179 state-dict keys and shapes (`num_batches_tracked` is accepted and ignored).
+ * BasicUpdateBlock with SepConvGRU, convex upsampling; alternate_corr = False; output_dim = None or 1).
+ * Arithmetic, chosen per call by cwm_raft_forward_args.mode (0.10.2; one handle serves both, alternating, without re-packing or reallocation):
+ *   parity (mode 0 or CWM_MODE_PARITY, the default)  every convolution with split-bf16 operands (hi + lo, 3 MFMAs per product), fp32 accumulate:
+ *                                                    <= 1e-2 px from the fp32 reference at 24 iterations
+ *   fast   (CWM_MODE_FAST; the reference's --mixed_precision)  every convolution of fnet, cnet, the motion encoder, the GRU, the flow head, the
+ *                                                    mask head and output_block.0 with ONE bf16 plane per operand (activation and folded weight
+ *                                                    rounded to bf16), fp32 accumulate and fp32 epilogue
+ * In both modes the activations between the convolutions, the instance-norm statistics, the residual join, the all-pairs correlation, its pooling
+ * and lookup, the coordinates and the flow update, the GRU's pointwise update, output_block.2 and both convex upsamplings are fp32.
+ * Weights: the reference's 179 state-dict keys and shapes (`num_batches_tracked` is accepted and ignored).
  * The output head (0.10.1; raft_model.py:152-159, 257-267, output_dim = 1: the keypoint predictor of the demo notebook) is four more keys,
  * `output_block.0.weight [256,128,3,3]`, `output_block.0.bias [256]`, `output_block.2.weight [1,256,1,1]`, `output_block.2.bias [1]`: optional
  * (cwm_raft_missing_weights does not count them; a model without them is the flow model), needed only by a forward that sets `head_dev`. */
@@ -419,6 +427,9 @@ typedef struct cwm_raft_forward_args {
      * four output_block weights are loaded.  At least one of flow_dev / head_dev must be given. */
     float* head_dev;
     int64_t head_stride_b, head_stride_t, head_stride_c;
+    /* appended in 0.10.2, read only when struct_size covers it (a caller that passes the 0.10.0 or 0.10.1 size gets parity).
+     * 0 or CWM_MODE_PARITY: parity arithmetic; CWM_MODE_FAST: bf16-operand convolutions (see above); anything else is CWM_ERR_INVALID. */
+    int32_t mode;
 } cwm_raft_forward_args;
 CWM_API int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* args);
 

@@ -1,9 +1,9 @@
 """Time one `MovabilityPredictor.forward` at the demo notebook's settings (16 + 2 x 16 samples, sample_batch_size 4, 224^2, 24 RAFT iterations):
 
-    python tools/movability_step.py [--steps 3] [--warmup 1] [--samples 16] [--iters 2]
+    python tools/movability_step.py [--steps 3] [--warmup 1] [--samples 16] [--iters 2] [--raft-mode fast]
 
 The IMU-conditioned base-4x4 predictor and the flow -> IMU model carry synthetic weights, RAFT-large is the flow model and the keypoint RAFT
-(output_dim = 1) the keypoint predictor.  Prints one JSON line: ms per forward and its split into the predictors (the conditioned predictor and the
+(output_dim = 1) the keypoint predictor; `--raft-mode fast` runs both RAFT models with bf16-operand convolutions.  Prints one JSON line: ms per forward and its split into the predictors (the conditioned predictor and the
 flow -> IMU model, without the RAFT calls inside it), RAFT (flow and keypoint forwards) and the rest (sampling, prompts, filter, motion maps, host).
 The split synchronises around every model call, so `ms_split_total` is a little above the unsplit `ms_median`, which is timed in a pass of its own."""
 import argparse
@@ -65,10 +65,11 @@ def main():
     ap.add_argument("--samples", type=int, default=16)
     ap.add_argument("--iters", type=int, default=2)
     ap.add_argument("--sample-batch-size", type=int, default=4)
+    ap.add_argument("--raft-mode", default="parity", choices=["parity", "fast"], help="arithmetic of the flow model and the keypoint predictor")
     args = ap.parse_args()
     pred = conj(CV.imu400_base_4x4patch_2frames_1tube(), 1)
     f2i = conj(CV.imu400_8x8patch_2frames_1tube_flowbackrgb01(), 0)
-    flow_model, keypoints = raft(0), raft(10, 1)
+    flow_model, keypoints = raft(0).set_mode(args.raft_mode), raft(10, 1).set_mode(args.raft_mode)
     gen = masking.RotatedTableUniformMaskingGenerator(input_size=pred.mask_size, mask_ratio=0.99, clumping_factor=2)
     M = movability.MovabilityPredictor(
         predictor=pred, head_motion_predictor=f2i, flow_model=flow_model, keypoint_predictor=keypoints, temporal_dim=2, imagenet_normalize_inputs=True,
@@ -98,7 +99,7 @@ def main():
         split.append((dt, clock.total.get("predictor", 0.0), clock.total.get("raft", 0.0)))
     dt, p, r = (1e3 * float(np.median([s[i] for s in split])) for i in range(3))
     n = args.samples * (1 + args.iters)
-    print(json.dumps({"samples": n, "iterations": args.iters, "sample_batch_size": args.sample_batch_size, "ms_median": round(1e3 * float(np.median(times)), 2),
+    print(json.dumps({"raft_mode": args.raft_mode, "samples": n, "iterations": args.iters, "sample_batch_size": args.sample_batch_size, "ms_median": round(1e3 * float(np.median(times)), 2),
                       "ms_min": round(1e3 * min(times), 2), "ms_split_total": round(dt, 2), "ms_predictor": round(p, 2), "ms_raft": round(r, 2),
                       "ms_rest": round(dt - p - r, 2), "kept_samples": [int((f.abs().amax((1, 2, 3)) > 0).sum()) for f in M.flow_samples_per_iter]}), flush=True)
 

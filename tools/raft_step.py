@@ -1,11 +1,12 @@
-"""Time RAFT-large (counterfactualworldmodels_amd.raft) at 224^2, 24 iterations:  python tools/raft_step.py [--batch 1 8 32] [--steps 10] [--warmup 3]
+"""Time RAFT-large (counterfactualworldmodels_amd.raft) at 224^2, 24 iterations:  python tools/raft_step.py [--batch 1 8 32] [--steps 10] [--warmup 3] [--mode fast]
 
 Reports ms per call, frame pairs/s and algorithmic TFLOP/s on the FLOPs this path computes (config.raft_algorithmic_flops: the mask head
 once, ~122 GFLOP per pair), one JSON line per batch size.  For the kernel split run it once under
 `rocprofv3 --kernel-trace --stats -- python tools/raft_step.py --batch 32 --steps 3`.
 
 `--output-dim 1` times the keypoint predictor instead (the model with the output head: one more 3x3 convolution, the 256 -> 1 projection and a
-one-channel convex upsampling in place of the flow's two-channel one); its FLOPs add the head's convolution and projection."""
+one-channel convex upsampling in place of the flow's two-channel one); its FLOPs add the head's convolution and projection.
+`--mode fast` times the bf16-operand mode instead of parity; every line names its mode."""
 import argparse
 import json
 import os
@@ -28,9 +29,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--output-dim", type=int, default=None, choices=[1], help="time the keypoint forward (the output head) instead of the flow forward")
+    ap.add_argument("--mode", default="parity", choices=["parity", "fast"], help="arithmetic of the convolutions (RAFT.set_mode)")
     args = ap.parse_args()
     H, W = args.size
     m = RAFT(_args(output_dim=args.output_dim)) if args.output_dim else RAFT()
+    m.set_mode(args.mode)
     sd = S.raft_state_dict(0, output_dim=args.output_dim) if args.output_dim else S.raft_state_dict(0)
     m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
     m = m.cuda().eval()
@@ -49,7 +52,7 @@ def main():
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
         ms = 1e3 * float(np.median(times))
-        print(json.dumps({"output": "keypoints" if args.output_dim else "flow", "batch": B, "size": [H, W], "iters": args.iters, "ms_median": round(ms, 3), "ms_min": round(1e3 * min(times), 3),
+        print(json.dumps({"output": "keypoints" if args.output_dim else "flow", "mode": m.mode, "batch": B, "size": [H, W], "iters": args.iters, "ms_median": round(ms, 3), "ms_min": round(1e3 * min(times), 3),
                           "pairs_per_s": round(B / (ms / 1e3), 2), "gflop_per_pair": round(flops / 1e9, 2),
                           "tflops": round(B * flops / (ms / 1e3) / 1e12, 2)}), flush=True)
 
