@@ -173,6 +173,77 @@ def new_raft_forward_args() -> CwmRaftForwardArgs:
     return a
 
 
+class CwmDevConvSrc(C.Structure):
+    _fields_ = [
+        ("p", C.c_void_p),
+        ("ld", C.c_int32),
+        ("C", C.c_int32),
+        ("stats", C.c_void_p),
+        ("relu", C.c_int32),
+        ("gate", C.c_void_p),
+        ("gate_ld", C.c_int32),
+        ("coords", C.c_void_p),
+    ]
+
+
+class CwmDevConvPart(C.Structure):
+    _fields_ = [
+        ("w", C.c_void_p),
+        ("b", C.c_void_p),
+        ("n", C.c_int32),
+        ("bn_gamma", C.c_void_p),
+        ("bn_beta", C.c_void_p),
+        ("bn_mean", C.c_void_p),
+        ("bn_var", C.c_void_p),
+    ]
+
+
+DEV_CONV_OPERAND_ONLY, DEV_CONV_KEEP_OPERAND = 1, 2
+
+
+class CwmDevRaftConvArgs(C.Structure):
+    """include/cwm_hip_dev.h cwm_dev_raft_conv_args (development library only)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("nsrc", C.c_int32),
+        ("src", CwmDevConvSrc * 2),
+        ("image", C.c_void_p * 2),
+        ("image_sb", C.c_int64 * 2),
+        ("image_st", C.c_int64 * 2),
+        ("image_sc", C.c_int64 * 2),
+        ("P", C.c_int32),
+        ("ppg", C.c_int32),
+        ("scale", C.c_float),
+        ("img0", C.c_int32),
+        ("n_img", C.c_int32),
+        ("H", C.c_int32),
+        ("W", C.c_int32),
+        ("kh", C.c_int32),
+        ("kw", C.c_int32),
+        ("stride", C.c_int32),
+        ("pad_h", C.c_int32),
+        ("pad_w", C.c_int32),
+        ("nparts", C.c_int32),
+        ("part", CwmDevConvPart * 2),
+        ("bn_eps", C.c_float),
+        ("out", C.c_void_p),
+        ("ldc", C.c_int32),
+        ("col0", C.c_int32),
+        ("mode", C.c_int32),
+        ("c_lo", C.c_int32),
+        ("c_hi", C.c_int32),
+        ("A", C.c_void_p),
+        ("flags", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
+def new_dev_raft_conv_args() -> CwmDevRaftConvArgs:
+    a = CwmDevRaftConvArgs()
+    a.struct_size = C.sizeof(CwmDevRaftConvArgs)
+    return a
+
+
 def new_forward_args() -> CwmForwardArgs:
     a = CwmForwardArgs()
     a.struct_size = C.sizeof(CwmForwardArgs)
@@ -272,6 +343,14 @@ DEV_SIGNATURES = {
     "cwm_bench_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "cwm_debug_set": (C.c_int, [C.c_char_p, C.c_int]),
     "cwm_debug_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
+    "cwm_dev_raft_conv": (C.c_int, [C.POINTER(CwmDevRaftConvArgs)]),
+    "cwm_dev_raft_corr_lookup_operand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cwm_dev_raft_instnorm_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "cwm_dev_raft_residual_join": (C.c_int, [C.POINTER(CwmDevConvSrc), C.POINTER(CwmDevConvSrc), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cwm_dev_raft_cnet_split": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cwm_dev_raft_motion_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "cwm_dev_raft_gru_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "cwm_dev_raft_flow_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
 }
 
 # the keys cwm_model_set_option / cwm_conj_set_option know (include/cwm_hip.h; csrc/engine.hip tuning_field)

@@ -75,8 +75,9 @@ extern "C" int cwm_debug_get(const char* key, int* value) {
 }
 
 // Per-shape overrides of the tile choice (the tuning hook behind tools/autotune_step.py).  All configurations give bit-identical results
-// (tests/test_kernels_gpu.py), so an override can only change the speed.  The table is process-wide; it reaches a launch through
-// Tuning.tile_hook, which the first override installs in this thread's options (models created afterwards inherit it).
+// (tests/test_kernels_gpu.py; a split-K launch on 128x128 tiles up to the order of its fp32 sum), so an override can only change the speed.
+// The table is process-wide; it reaches a launch through Tuning.tile_hook, which the first override installs in this thread's options (models
+// created afterwards inherit it).
 namespace {
 struct TileKey {
     int M, N, K, epi, ovl;
@@ -196,5 +197,182 @@ extern "C" int cwm_bench_attention(int B, int H, int N, int mode, int iters, dou
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     *avg_us = 1e3 * ms / iters;
+    return CWM_OK;
+}
+
+// ---- RAFT kernels one at a time (tests/test_raft_kernels_gpu.py) ---------------------------------------------------------------------------------
+// The launches of raft_model.hip on caller-owned buffers: the model's packing kernels, launch_im2col and launch_gemm with this thread's options.
+namespace {
+ConvSrc conv_src_of(const cwm_dev_conv_src& d) {
+    ConvSrc s;
+    memset(&s, 0, sizeof(s));
+    s.p = d.p;
+    s.ld = d.ld ? d.ld : d.C;
+    s.C = d.C;
+    s.stats = d.stats;
+    s.relu = d.relu;
+    s.gate = d.gate;
+    s.gate_ld = d.gate_ld;
+    s.coords = d.coords;
+    return s;
+}
+bool conv_src_ok(const cwm_dev_conv_src& d) { return d.C > 0 && (d.coords ? d.C == 2 : d.p != nullptr) && (!d.gate || d.gate_ld >= d.C); }
+}  // namespace
+
+extern "C" int cwm_dev_raft_conv(const cwm_dev_raft_conv_args* args) {
+    CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_raft_conv_args), "cwm_dev_raft_conv: args->struct_size must be sizeof(cwm_dev_raft_conv_args)");
+    const cwm_dev_raft_conv_args& a = *args;
+    hipStream_t s = (hipStream_t)a.stream;
+    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_raft_conv: bad mode");
+    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    const bool frames = a.image[0] != nullptr, operand_only = a.flags & CWM_DEV_CONV_OPERAND_ONLY, keep = a.flags & CWM_DEV_CONV_KEEP_OPERAND;
+    CWM_REQUIRE(!(operand_only && keep), "cwm_dev_raft_conv: flags ask for the operand only and for no operand");
+    CWM_REQUIRE(a.n_img > 0 && a.H > 0 && a.W > 0 && a.kh > 0 && a.kw > 0 && a.stride > 0 && a.pad_h >= 0 && a.pad_w >= 0, "cwm_dev_raft_conv: bad geometry");
+    Im2colParams ip;
+    memset(&ip, 0, sizeof(ip));
+    if (frames) {
+        CWM_REQUIRE(a.image[1] && a.P > 0 && a.ppg > 0 && a.P % a.ppg == 0 && a.img0 >= 0 && a.img0 + a.n_img <= 2 * a.P,
+                    "cwm_dev_raft_conv: images [%d, %d) of 2 x %d pairs (%d per group)", a.img0, a.img0 + a.n_img, a.P, a.ppg);
+        ip.src[0].C = 3;
+        ip.nsrc = 1;
+        for (int f = 0; f < 2; ++f) {
+            ip.image.base[f] = a.image[f];
+            ip.image.sb[f] = a.image_sb[f];
+            ip.image.st[f] = a.image_st[f];
+            ip.image.sc[f] = a.image_sc[f];
+        }
+        ip.image.P = a.P;
+        ip.image.ppg = a.ppg;
+        ip.image.scale = a.scale;
+        ip.img0 = a.img0;
+    } else {
+        CWM_REQUIRE((a.nsrc == 1 || a.nsrc == 2) && conv_src_ok(a.src[0]) && (a.nsrc == 1 || conv_src_ok(a.src[1])), "cwm_dev_raft_conv: bad source");
+        ip.nsrc = a.nsrc;
+        for (int i = 0; i < a.nsrc; ++i) ip.src[i] = conv_src_of(a.src[i]);
+    }
+    const int cin = ip.src[0].C + (ip.nsrc > 1 ? ip.src[1].C : 0), K = a.kh * a.kw * cin, Kpad = round_up(K, 64);
+    ip.n_img = a.n_img;
+    ip.H = a.H;
+    ip.W = a.W;
+    ip.kh = a.kh;
+    ip.kw = a.kw;
+    ip.stride = a.stride;
+    ip.pad_h = a.pad_h;
+    ip.pad_w = a.pad_w;
+    ip.OH = (a.H + 2 * a.pad_h - a.kh) / a.stride + 1;
+    ip.OW = (a.W + 2 * a.pad_w - a.kw) / a.stride + 1;
+    ip.c_lo = a.c_lo;
+    ip.c_hi = a.c_hi;
+    ip.Kpad = Kpad;
+    CWM_REQUIRE(a.H + 2 * a.pad_h >= a.kh && a.W + 2 * a.pad_w >= a.kw, "cwm_dev_raft_conv: the kernel is larger than the padded input");
+    CWM_REQUIRE(a.c_hi <= a.c_lo || (a.A && a.c_lo >= 0 && a.c_hi <= cin), "cwm_dev_raft_conv: a partial rewrite [%d, %d) of %d channels needs the caller's A",
+                a.c_lo, a.c_hi, cin);
+    CWM_REQUIRE(a.A || !(operand_only || keep), "cwm_dev_raft_conv: flags = %d needs the caller's A", a.flags);
+    const int64_t M = (int64_t)a.n_img * ip.OH * ip.OW;
+    CWM_REQUIRE(M * Kpad * planes < (1ll << 32), "cwm_dev_raft_conv: operand too large");
+    Scratch sc;
+    bf16* A = (bf16*)a.A;
+    if (!A) {
+        A = sc.get<bf16>((size_t)M * Kpad * planes);
+        CWM_REQUIRE(A, "cwm_dev_raft_conv: out of device memory");
+    }
+    ip.A = A;
+    if (!keep)
+        if (int rc = launch_im2col(ip, planes, s)) return rc;
+    if (!operand_only) {
+        CWM_REQUIRE(a.nparts == 1 || a.nparts == 2, "cwm_dev_raft_conv: nparts = %d", a.nparts);
+        int n = 0;
+        for (int i = 0; i < a.nparts; ++i) {
+            const cwm_dev_conv_part& p = a.part[i];
+            CWM_REQUIRE(p.w && p.b && p.n > 0 && (!p.bn_gamma || (p.bn_beta && p.bn_mean && p.bn_var)), "cwm_dev_raft_conv: bad weight part %d", i);
+            n += p.n;
+        }
+        // the model's LinearW (engine.hip make_linear): N = the output channels rounded up to 16, zero rows / bias beyond them
+        const int N = round_up(n, 16), Npad = round_up(N, 256);
+        CWM_REQUIRE(a.out && a.col0 >= 0 && a.ldc >= a.col0 + N, "cwm_dev_raft_conv: columns [%d, %d) do not fit rows of %d", a.col0, a.col0 + N, a.ldc);
+        const size_t plane = (size_t)Npad * Kpad;
+        bf16* w_hi = sc.get<bf16>(plane);
+        bf16* w_il = sc.get<bf16>(2 * plane);
+        float* bias = sc.get<float>(Npad);
+        CWM_REQUIRE(w_hi && w_il && bias, "cwm_dev_raft_conv: out of device memory");
+        CWM_HIP_CHECK(hipMemsetAsync(w_hi, 0, plane * sizeof(bf16), s));
+        CWM_HIP_CHECK(hipMemsetAsync(w_il, 0, 2 * plane * sizeof(bf16), s));
+        CWM_HIP_CHECK(hipMemsetAsync(bias, 0, (size_t)Npad * sizeof(float), s));
+        int row0 = 0;
+        for (int i = 0; i < a.nparts; ++i) {
+            const cwm_dev_conv_part& p = a.part[i];
+            if (int rc = launch_pack_conv(p.w, p.b, p.bn_gamma, p.bn_beta, p.bn_mean, p.bn_var, a.bn_eps, p.n, cin, a.kh, a.kw, Kpad, row0, w_il, w_hi, bias, s))
+                return rc;
+            row0 += p.n;
+        }
+        GemmParams g;
+        memset(&g, 0, sizeof(g));
+        g.A = A;
+        g.lda = Kpad;
+        g.W = planes == 2 ? w_il : w_hi;
+        g.M = (int)M;
+        g.N = N;
+        g.K = Kpad;
+        g.bias = bias;
+        g.epi = EPI_F32;
+        g.C = a.out + a.col0;
+        g.ldc = a.ldc;
+        g.tune = &thread_tuning();
+        if (int rc = launch_gemm(g, planes, s)) return rc;
+    }
+    CWM_HIP_CHECK(hipStreamSynchronize(s));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_raft_corr_lookup_operand(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, int mode,
+                                                void* A_dev, void* stream) {
+    CWM_REQUIRE(fmap1_dev && fmap2_dev && coords_dev && A_dev && P > 0 && h8 >= 8 && w8 >= 8, "cwm_dev_raft_corr_lookup_operand: bad argument");
+    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_dev_raft_corr_lookup_operand: bad mode");
+    return raft_corr_lookup_run(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, nullptr, (bf16*)A_dev, mode == CWM_MODE_PARITY ? 2 : 1, (hipStream_t)stream);
+}
+
+extern "C" int cwm_dev_raft_instnorm_stats(const float* x_dev, int n_img, int HW, int C, float eps, float* stats_dev, void* stream) {
+    CWM_REQUIRE(x_dev && stats_dev && n_img > 0 && HW > 0 && C > 0, "cwm_dev_raft_instnorm_stats: bad argument");
+    Scratch sc;
+    double* work = sc.get<double>((size_t)2 * n_img * kInstNormMaxChunks * C);
+    CWM_REQUIRE(work, "cwm_dev_raft_instnorm_stats: out of device memory");
+    if (int rc = launch_instnorm_stats(x_dev, n_img, HW, C, eps, stats_dev, work, (hipStream_t)stream)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_raft_residual_join(const cwm_dev_conv_src* X, const cwm_dev_conv_src* Y, int n_img, int HW, float* out_dev, void* stream) {
+    CWM_REQUIRE(X && Y && out_dev && n_img > 0 && HW > 0 && X->p && Y->p && X->C == Y->C && Y->C > 0 && !X->coords && !Y->coords && !X->gate && !Y->gate,
+                "cwm_dev_raft_residual_join: bad argument");
+    if (int rc = launch_residual_join(conv_src_of(*X), conv_src_of(*Y), n_img, HW, out_dev, (hipStream_t)stream)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_raft_cnet_split(const float* cn_dev, int64_t M, float* h_dev, float* x_dev, void* stream) {
+    CWM_REQUIRE(cn_dev && h_dev && x_dev && M > 0, "cwm_dev_raft_cnet_split: bad argument");
+    if (int rc = launch_cnet_split(cn_dev, M, h_dev, x_dev, (hipStream_t)stream)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_raft_motion_finish(float* x_dev, const float* coords_dev, int64_t M, int h8, int w8, void* stream) {
+    CWM_REQUIRE(x_dev && coords_dev && M > 0 && h8 > 0 && w8 > 0, "cwm_dev_raft_motion_finish: bad argument");
+    if (int rc = launch_motion_finish(x_dev, coords_dev, M, h8, w8, (hipStream_t)stream)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_raft_gru_update(float* h_dev, const float* zr_dev, const float* q_dev, int64_t M, void* stream) {
+    CWM_REQUIRE(h_dev && zr_dev && q_dev && M > 0, "cwm_dev_raft_gru_update: bad argument");
+    if (int rc = launch_gru_update(h_dev, zr_dev, q_dev, M, (hipStream_t)stream)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_raft_flow_update(float* coords_dev, const float* delta_dev, int ld, int64_t M, void* stream) {
+    CWM_REQUIRE(coords_dev && delta_dev && ld >= 2 && M > 0, "cwm_dev_raft_flow_update: bad argument");
+    if (int rc = launch_flow_update(coords_dev, delta_dev, ld, M, (hipStream_t)stream)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return CWM_OK;
 }

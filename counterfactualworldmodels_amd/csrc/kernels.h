@@ -323,6 +323,10 @@ struct ConvexUpParams {
     int64_t out_sb, out_st, out_sc;
 };
 // planes: the layout of A (common.h a_pos): 2 = split-bf16 hi / lo (parity), 1 = one bf16 plane (fast); the same for launch_corr_lookup
+// One weight part [n][cin][kh][kw] (+ bias [n]) of a convolution -> rows row0 .. row0 + n of its packed GEMM operand (w_il: parity layout, w_hi: fast) and
+// bias[row0 ..]; gamma != nullptr folds the eval-mode batch norm (gamma, beta, mean, var, eps) that follows the convolution
+int launch_pack_conv(const float* w, const float* b, const float* gamma, const float* beta, const float* mean, const float* var, float eps, int n, int cin,
+                     int kh, int kw, int Kpad, int row0, bf16* w_il, bf16* w_hi, float* bias, hipStream_t s);
 int launch_im2col(const Im2colParams& p, int planes, hipStream_t s);
 // stats [n_img][C] (mean, rstd) pairs; work: 2 * n_img * kInstNormMaxChunks * C doubles
 constexpr int kInstNormMaxChunks = 16;
@@ -350,6 +354,9 @@ struct ConvexUp1Params {
     float* out;           // pair pr = (g, t): out + g * out_sb + t * out_st + Y * 8w8 + X
     int64_t out_sb, out_st;
 };
+// CorrBlock built from two feature maps [P][h8 * w8][256] and indexed at coords [P * h8 * w8][2]: the pyramid (allocated and freed inside), then the lookup
+// as fp32 `out` [M][324], or (out == nullptr) as convc1's Kpad = 384 operand A in the layout of `planes`.  Synchronises the stream.
+int raft_corr_lookup_run(const float* fmap1, const float* fmap2, const float* coords, int P, int h8, int w8, float* out, bf16* A, int planes, hipStream_t s);
 constexpr int kHeadHidden = 256;
 int launch_head_project(const float* hidden, int ld, const float* w, const float* bias, int64_t M, float* value, hipStream_t s);
 int launch_convex_upsample1(const ConvexUp1Params& p, hipStream_t s);

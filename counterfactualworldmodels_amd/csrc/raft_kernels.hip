@@ -400,9 +400,46 @@ __global__ void convex_upsample1_kernel(const ConvexUp1Params p) {
     }
 }
 
+// Convolution weights [N][C][kh][kw] -> rows row0 .. row0 + N of the GEMM's W operand in K order (ky, kx, c), zero padded to Kpad, in both layouts
+// (il: parity, hi: fast); an eval-mode batch norm after the convolution is folded in: w * gamma / sqrt(var + eps), (b - mean) * gamma / sqrt(var + eps) + beta
+__global__ void pack_conv_kernel(const float* w, const float* gamma, const float* var, float eps, int N, int C, int kh, int kw, int Kpad, int row0,
+                                 bf16* il, bf16* hi) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * Kpad) return;
+    const int n = (int)(i / Kpad), k = (int)(i - (int64_t)n * Kpad);
+    float v = 0.f;
+    if (k < kh * kw * C) {
+        const int tap = k / C, c = k - tap * C, ky = tap / kw, kx = tap - ky * kw;
+        v = w[(((int64_t)n * C + c) * kh + ky) * kw + kx];
+        if (gamma) v = v * (gamma[n] / sqrtf(var[n] + eps));
+    }
+    bf16 h, l;
+    split_bf16(v, h, l);
+    bf16* d = il + a_pos<2>(row0 + n, Kpad, k);
+    d[0] = h;
+    d[kLoOffset] = l;
+    hi[a_pos<1>(row0 + n, Kpad, k)] = h;  // the fast plane: the folded weight rounded once (split_bf16's hi is (bf16)v)
+}
+
+__global__ void pack_bias_kernel(const float* b, const float* gamma, const float* beta, const float* mean, const float* var, float eps, int N,
+                                 float* dst) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    dst[n] = gamma ? (b[n] - mean[n]) * (gamma[n] / sqrtf(var[n] + eps)) + beta[n] : b[n];
+}
+
 unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 1 << 20); }
 
 }  // namespace
+
+int launch_pack_conv(const float* w, const float* b, const float* gamma, const float* beta, const float* mean, const float* var, float eps, int n, int cin,
+                     int kh, int kw, int Kpad, int row0, bf16* w_il, bf16* w_hi, float* bias, hipStream_t s) {
+    const int64_t total = (int64_t)n * Kpad;
+    hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, gamma, var, eps, n, cin, kh, kw, Kpad, row0, w_il, w_hi);
+    hipLaunchKernelGGL(pack_bias_kernel, dim3((n + 255) / 256), dim3(256), 0, s, b, gamma, beta, mean, var, eps, n, bias + row0);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
 
 int launch_im2col(const Im2colParams& p, int planes, hipStream_t s) {
     CWM_REQUIRE(p.Kpad % 64 == 0 && (p.c_hi <= p.c_lo || (p.c_lo % 8 == 0 && p.c_hi % 8 == 0)), "im2col: Kpad = %d, channel range [%d, %d)", p.Kpad,

@@ -51,32 +51,6 @@ struct Encoder {
     Block blocks[6];
 };
 
-__global__ void pack_conv_kernel(const float* w, const float* gamma, const float* var, float eps, int N, int C, int kh, int kw, int Kpad, int row0,
-                                 bf16* il, bf16* hi) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)N * Kpad) return;
-    const int n = (int)(i / Kpad), k = (int)(i - (int64_t)n * Kpad);
-    float v = 0.f;
-    if (k < kh * kw * C) {
-        const int tap = k / C, c = k - tap * C, ky = tap / kw, kx = tap - ky * kw;
-        v = w[(((int64_t)n * C + c) * kh + ky) * kw + kx];
-        if (gamma) v = v * (gamma[n] / sqrtf(var[n] + eps));
-    }
-    bf16 h, l;
-    split_bf16(v, h, l);
-    bf16* d = il + a_pos<2>(row0 + n, Kpad, k);
-    d[0] = h;
-    d[kLoOffset] = l;
-    hi[a_pos<1>(row0 + n, Kpad, k)] = h;  // the fast plane: the folded weight rounded once (split_bf16's hi is (bf16)v)
-}
-
-__global__ void pack_bias_kernel(const float* b, const float* gamma, const float* beta, const float* mean, const float* var, float eps, int N,
-                                 float* dst) {
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= N) return;
-    dst[n] = gamma ? (b[n] - mean[n]) * (gamma[n] / sqrtf(var[n] + eps)) + beta[n] : b[n];
-}
-
 // the output head's state-dict keys, in the reference's order
 const char* const kHeadKeys[4] = {"output_block.0.weight", "output_block.0.bias", "output_block.2.weight", "output_block.2.bias"};
 
@@ -193,10 +167,9 @@ int prepare(cwm_raft_model* m) {
                 mu = m->raw[p.bn + ".running_mean"].dev;
                 var = m->raw[p.bn + ".running_var"].dev;
             }
-            const int64_t total = (int64_t)p.n * cv->L.Kpad;
-            hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, m->raw[p.w].dev, g, var, 1e-5f, p.n, cv->cin,
-                               cv->kh, cv->kw, cv->L.Kpad, row0, cv->L.w_il, cv->L.w);
-            hipLaunchKernelGGL(pack_bias_kernel, dim3((p.n + 255) / 256), dim3(256), 0, 0, m->raw[p.b].dev, g, be, mu, var, 1e-5f, p.n, cv->L.bias + row0);
+            if (int rc = launch_pack_conv(m->raw[p.w].dev, m->raw[p.b].dev, g, be, mu, var, 1e-5f, p.n, cv->cin, cv->kh, cv->kw, cv->L.Kpad, row0, cv->L.w_il,
+                                          cv->L.w, cv->L.bias, 0))
+                return rc;
             row0 += p.n;
         }
     }
@@ -535,10 +508,8 @@ extern "C" int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* 
 }
 
 // ---- stand-alone kernels (kernel tests) -------------------------------------------------------------------------------
-extern "C" int cwm_raft_corr_lookup(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev,
-                                    void* stream) {
-    CWM_REQUIRE(fmap1_dev && fmap2_dev && coords_dev && out_dev && P > 0 && h8 >= 8 && w8 >= 8, "cwm_raft_corr_lookup: bad argument");
-    hipStream_t s = (hipStream_t)stream;
+int cwm::raft_corr_lookup_run(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev, bf16* A,
+                              int planes, hipStream_t s) {
     const int64_t N = (int64_t)h8 * w8, M = P * N;
     float* pyr[4] = {nullptr, nullptr, nullptr, nullptr};
     int rc = 0;
@@ -559,9 +530,13 @@ extern "C" int cwm_raft_corr_lookup(const float* fmap1_dev, const float* fmap2_d
     lp.coords = coords_dev;
     lp.M = M;
     lp.Kpad = kLookupKpad;
-    lp.out = out_dev;
-    lp.out_ld = 324;
-    if (!rc) rc = launch_corr_lookup(lp, 2, s);  // fp32 `out`: the operand layout is not used
+    if (out_dev) {
+        lp.out = out_dev;
+        lp.out_ld = 324;
+    } else {
+        lp.A = A;
+    }
+    if (!rc) rc = launch_corr_lookup(lp, planes, s);  // (fp32 `out`: the operand layout is not used)
     if (hipStreamSynchronize(s) != hipSuccess && !rc) {
         cwm_set_error("cwm_raft_corr_lookup: stream synchronisation failed");
         rc = CWM_ERR_HIP;
@@ -569,6 +544,12 @@ extern "C" int cwm_raft_corr_lookup(const float* fmap1_dev, const float* fmap2_d
     for (float* p : pyr)
         if (p) (void)hipFree(p);
     return rc;
+}
+
+extern "C" int cwm_raft_corr_lookup(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev,
+                                    void* stream) {
+    CWM_REQUIRE(fmap1_dev && fmap2_dev && coords_dev && out_dev && P > 0 && h8 >= 8 && w8 >= 8, "cwm_raft_corr_lookup: bad argument");
+    return raft_corr_lookup_run(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, out_dev, nullptr, 2, (hipStream_t)stream);
 }
 
 extern "C" int cwm_raft_convex_upsample(const float* flow_dev, const float* mask_dev, int P, int h8, int w8, float* out_dev, void* stream) {

@@ -14,7 +14,8 @@ extern "C" {
 
 /* Tuning hook (tools/autotune_step.py): fix the output-tile configuration of every GEMM launch of one shape -- M, N, K as launched (K padded to
  * 64), epi 0 fp32 / 1 bf16+GELU / 2 bf16 / 3 QKV scatter, overlapped = inside a two-lane forward -- to cfg 1 (128x128), 4 (256x256 8-phase) or 6 (4 for
- * the whole rounds + 1 for the remaining rows); cfg 0 removes the entry, M <= 0 clears the table.  Every configuration gives bit-identical results.
+ * the whole rounds + 1 for the remaining rows); cfg 0 removes the entry, M <= 0 clears the table.  Every configuration gives bit-identical results,
+ * except that a small launch on 128x128 tiles may split K (a re-associated, deterministic fp32 sum; "gemm_debug" 32 switches the split off).
  * The table is process-wide; it reaches the launches of this thread's stand-alone calls and of models created on this thread AFTER the first call. */
 CWM_API int cwm_gemm_tile_override(int M, int N, int K, int epi, int overlapped, int cfg);
 
@@ -33,6 +34,82 @@ CWM_API int cwm_bench_attention(int B, int H, int N, int mode, int iters, double
 CWM_API int cwm_debug_set(const char* key, int value);
 /* The value of an option in this thread's copy (what a handle created on this thread now would start from). */
 CWM_API int cwm_debug_get(const char* key, int* value);
+
+/* ---- RAFT kernels one at a time (tests/test_raft_kernels_gpu.py) -------------------------------------------------------------------------------
+ * The launches of csrc/raft_model.hip on caller-owned device buffers, with this thread's execution options (cwm_debug_set).  Activations are fp32
+ * NHWC.  Every entry point synchronises the stream before it returns; none checks that the buffers are as large as the geometry says. */
+
+/* One channel segment of a convolution input (kernels.h ConvSrc): pixel `pix` of the [n_img][H][W] grid at p + pix * ld, C channels.  The value read is
+ * relu?((v - mean) * rstd) * sigmoid(gate[pix * gate_ld + c])?, with (mean, rstd) = stats[(img * C + c) * 2 ..]; or, with `coords` ([pix][2], C = 2),
+ * coords - (x, y). */
+typedef struct cwm_dev_conv_src {
+    const float* p;
+    int32_t ld, C;
+    const float* stats; /* optional */
+    int32_t relu;
+    const float* gate;  /* optional */
+    int32_t gate_ld;
+    const float* coords; /* optional: instead of p */
+} cwm_dev_conv_src;
+
+/* One weight part [n][cin][kh][kw] with bias [n]; bn_gamma != NULL folds the eval-mode batch norm (gamma, beta, running mean, running var, each [n])
+ * that follows the convolution, as the model does when it packs its weights. */
+typedef struct cwm_dev_conv_part {
+    const float* w;
+    const float* b;
+    int32_t n;
+    const float *bn_gamma, *bn_beta, *bn_mean, *bn_var;
+} cwm_dev_conv_part;
+
+#define CWM_DEV_CONV_OPERAND_ONLY 1 /* stop after writing the A operand (no weights, no output needed) */
+#define CWM_DEV_CONV_KEEP_OPERAND 2 /* do not write the operand: run the GEMM on `A` as it is (convc1 on the lookup's operand) */
+
+/* One convolution as the RAFT model runs it: out[m][col0 + j] = bias[j] + sum_k A[m][k] W[j][k] over the rows m = (img, oy, ox) of the output grid
+ * OH = (H + 2 pad_h - kh) / stride + 1 (OW likewise), K order (ky, kx, c), input channels = src[0] then src[1].  Output columns j < round_up(sum n, 16)
+ * are written (those beyond sum n as 0), nothing else of a row of ldc floats. */
+typedef struct cwm_dev_raft_conv_args {
+    uint32_t struct_size;
+    int32_t nsrc; /* 1 or 2; ignored with image[0] */
+    cwm_dev_conv_src src[2];
+    /* image[0] != NULL: the input frames instead of src (3 channels).  Image i of the call is pair (img0 + i) % P of frame (img0 + i) / P (0: image[0],
+     * 1: image[1]), pair pr = (g, t) = (pr / ppg, pr % ppg), element (c, y, x) at image[f] + g * image_sb[f] + t * image_st[f] + c * image_sc[f] + y * W + x;
+     * the value is 2 * (v * scale / 255) - 1 */
+    const float* image[2];
+    int64_t image_sb[2], image_st[2], image_sc[2];
+    int32_t P, ppg;
+    float scale;
+    int32_t img0;
+    int32_t n_img, H, W, kh, kw, stride, pad_h, pad_w;
+    int32_t nparts; /* 1 or 2: the output channels are part[0]'s then part[1]'s (the GRU's stacked z and r) */
+    cwm_dev_conv_part part[2];
+    float bn_eps;
+    float* out;
+    int32_t ldc, col0;
+    int32_t mode;       /* CWM_MODE_PARITY or CWM_MODE_FAST */
+    int32_t c_lo, c_hi; /* c_hi > c_lo (multiples of 8): rewrite only input channels [c_lo, c_hi) of every tap; the rest of A is kept (needs `A`) */
+    /* optional: the operand buffer, [n_img * OH * OW] rows of planes * Kpad bf16 (Kpad = round_up(kh * kw * cin, 64); planes 2 parity, 1 fast) in the
+     * layout of csrc/common.h a_pos; NULL: allocated inside */
+    void* A;
+    int32_t flags; /* CWM_DEV_CONV_* */
+    void* stream;
+} cwm_dev_raft_conv_args;
+CWM_API int cwm_dev_raft_conv(const cwm_dev_raft_conv_args* args);
+
+/* cwm_raft_corr_lookup's pyramid and lookup, written as convc1's operand: [P * h8 * w8] rows of planes * 384 bf16 (features 0..323, then zeros) */
+CWM_API int cwm_dev_raft_corr_lookup_operand(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, int mode,
+                                             void* A_dev, void* stream);
+/* InstanceNorm2d statistics of x [n_img][HW][C]: stats [n_img][C][2] = (mean, 1 / sqrt(biased var + eps)) */
+CWM_API int cwm_dev_raft_instnorm_stats(const float* x_dev, int n_img, int HW, int C, float eps, float* stats_dev, void* stream);
+/* out[pix][c] = relu(X + Y) over Y->C channels, both read as a cwm_dev_conv_src (no gate / coords); out [n_img * HW][C] may be X->p */
+CWM_API int cwm_dev_raft_residual_join(const cwm_dev_conv_src* X, const cwm_dev_conv_src* Y, int n_img, int HW, float* out_dev, void* stream);
+/* cn [M][256] -> h [M][128] = tanh(cn[:, :128]), x[m * 256 + c] = relu(cn[:, 128:]) for c < 128 */
+CWM_API int cwm_dev_raft_cnet_split(const float* cn_dev, int64_t M, float* h_dev, float* x_dev, void* stream);
+/* x [M][256]: columns 128..253 -> relu, 254 / 255 = coords [M][2] - (x, y) of the pixel on the h8 x w8 grid */
+CWM_API int cwm_dev_raft_motion_finish(float* x_dev, const float* coords_dev, int64_t M, int h8, int w8, void* stream);
+/* h [M][128] = (1 - z) h + z tanh(q), z = sigmoid(zr[m * 256 + c]), q [M][128] */
+CWM_API int cwm_dev_raft_gru_update(float* h_dev, const float* zr_dev, const float* q_dev, int64_t M, void* stream);
+/* coords [M][2] += delta[m * ld + (0, 1)] */
+CWM_API int cwm_dev_raft_flow_update(float* coords_dev, const float* delta_dev, int ld, int64_t M, void* stream);
 
 
 #ifdef __cplusplus

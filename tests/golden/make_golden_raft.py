@@ -113,6 +113,16 @@ def main():
                             shift=np.array([2, -3]), drift_fwd=np.array(df), drift_bwd=np.array(db))
         print(f"[golden] raft_128x160_t3 {yf.shape} drift {df:.3e} / {db:.3e} ({time.time() - t0:.0f}s)")
 
+    # ---- 3b: 136 x 152, B = 2: an ODD 1/8 grid (17 x 19; floor-pooled pyramid 17/8/4/2 x 19/9/4/2), 24 iterations and 1 iteration forward
+    if want("raft_136x152_b2"):
+        m, _ = build_raft(rm, 8)
+        x = torch.from_numpy(S.raft_frames(2, 136, 152, 9, shift=(-3, 2)))
+        (y24,), d24 = run_both(m, lambda mm, dt: mm(x.to(dt), iters=24))
+        (y1,), d1 = run_both(m, lambda mm, dt: mm(x.to(dt), iters=1))
+        np.savez_compressed(os.path.join(HERE, "raft_136x152_b2.npz"), flow=y24, flow_it1=y1, seed=np.array(8), frames_seed=np.array(9),
+                            shift=np.array([-3, 2]), drift=np.array(d24), drift_it1=np.array(d1))
+        print(f"[golden] raft_136x152_b2 {y24.shape} max |flow| {np.abs(y24).max():.2f} drift {d24:.3e} / it1 {d1:.3e} ({time.time() - t0:.0f}s)")
+
     # ---- 4: the flow -> IMU head-motion predictor with the reference's RAFT (synthetic weights) in place of the stand-in
     if want("head_motion_raft_b1"):
         ns = ref_import.import_reference()

@@ -74,6 +74,17 @@ def test_128x160_t3_forward_and_backward_vs_reference():
     check("128x160 bwd", m(x, iters=24, backward=True).cpu().numpy(), g["flow_bwd"], TOL_24)
 
 
+def test_136x152_b2_odd_grid_vs_reference():
+    """An odd 1/8 grid, 17 x 19: the floor-pooled pyramid 17/8/4/2 x 19/9/4/2 drops a row and a column at the first pooling and again at 9 -> 4, the
+    7x7 / 3x3 borders fall on odd sides, and no row count is a multiple of a GEMM tile."""
+    g = golden("raft_136x152_b2")
+    m = build(int(g["seed"]))
+    x = frames(2, 136, 152, int(g["frames_seed"]), shift=tuple(int(v) for v in g["shift"]))
+    print(f"reference fp32 vs float64: {float(g['drift']):.3e} px (24 iterations), {float(g['drift_it1']):.3e} px (1 iteration)")
+    check("136x152 it24", m(x, iters=24).cpu().numpy(), g["flow"], TOL_24)
+    check("136x152 it1", m(x, iters=1).cpu().numpy(), g["flow_it1"], TOL_1)
+
+
 # ---- stand-alone kernels against torch restatements --------------------------------------------------------------------
 def lookup_restated(f1, f2, coords):
     """CorrBlock (corr.py:12-60) restated: all-pairs dot products / sqrt(256), 3 x avg_pool2d(2), and at level l the 9 x 9 window of
@@ -163,13 +174,14 @@ def test_forward_is_deterministic():
 
 def test_batch_rows_agree_with_single_runs():
     m = build(1)
-    x = frames(3, 128, 160, 10)
-    y = m(x, iters=12)
-    for b in range(3):
-        y1 = m(x[b : b + 1].clone(), iters=12)
-        err = (y[b : b + 1] - y1).abs().max().item()
-        print(f"[batch row {b}] max-abs vs batch-1 run {err:.3e}")
-        assert err <= TOL_24
+    for H, W in ((128, 160), (136, 152)):  # an even 16 x 20 grid and an odd 17 x 19 one
+        x = frames(3, H, W, 10)
+        y = m(x, iters=12)
+        for b in range(3):
+            y1 = m(x[b : b + 1].clone(), iters=12)
+            err = (y[b : b + 1] - y1).abs().max().item()
+            print(f"[batch row {b} of {H}x{W}] max-abs vs batch-1 run {err:.3e}")
+            assert err <= TOL_24
 
 
 @pytest.mark.parametrize("H,W,iters", [(100, 128, 4), (64, 64, 4), (128, 128, 0)])
