@@ -16,19 +16,10 @@ struct CrossW {
     LinearW qk, qk_src, v, v_src, proj, proj_src, mlp_t0, mlp_t2, mlp_s0, mlp_s2;
 };
 
-struct StreamW {
-    int enc_dim = 0, dec_dim = 0, enc_heads = 0, dec_heads = 0, n_tok = 0, max_pad = 0, out_dim = 0, embed_k = 0, embed_kpad = 0;
-    std::vector<BlockW> enc, dec;
-    LinearW embed, e2d, head;
-    float *enc_norm_g = nullptr, *enc_norm_b = nullptr, *dec_norm_g = nullptr, *dec_norm_b = nullptr;
-    float *mask_token = nullptr, *null_enc = nullptr;
-    float *pos_enc_ext = nullptr, *pos_dec_ext = nullptr;  // [n_tok + max_pad][D]; pad rows: 0 (enc) / null_token_dec (dec)
-    // workspace
-    uint8_t* ext_mask = nullptr;
-    int* perm = nullptr;
-    bf16* tokens_in = nullptr;
-    float *x_enc = nullptr, *x_dec = nullptr;
-    StreamBuffers sb;
+// workspace shared by the cross blocks of a lane (batch-major, like a stream's)
+struct CrossWs {
+    float *qk = nullptr, *v = nullptr, *qk_src = nullptr, *v_src = nullptr, *scores_t = nullptr, *cross_partial = nullptr;
+    bf16 *ybuf = nullptr, *ysbuf = nullptr;
 };
 
 }  // namespace
@@ -43,11 +34,11 @@ struct cwm_conj_model {
     float* ctx_stage = nullptr;
     uint8_t* ctx_mask_stage = nullptr;
     std::vector<CrossW> enc_cross, dec_cross;
-    // workspace shared by the cross blocks
+    // workspace (grown on demand)
     int ws_batch = 0, ws_vmain = 0, ws_vctx = 0;
-    int* err = nullptr;
-    float *qk = nullptr, *v = nullptr, *qk_src = nullptr, *v_src = nullptr, *scores_t = nullptr, *cross_partial = nullptr;
-    bf16 *ybuf = nullptr, *ysbuf = nullptr;
+    StreamWs main_ws, ctx_ws;
+    CrossWs cross_ws;
+    int* err = nullptr;  // one word per lane
     // batch lanes (cwm_conj_set_lanes; see cwm_model in model.hip)
     int lanes = 2;
     Lanes lane_set;
@@ -68,108 +59,53 @@ struct cwm_conj_model {
 
 namespace {
 
-// One lane's view of the model: the weight pointers of both streams (copied), and the slice of every batch-major workspace buffer
-// that lies behind the capacity of the b0 batch elements of the lanes before it.
+// One lane's view of the workspace: the slice of every batch-major buffer that lies behind the capacity of the b0 batch elements of the
+// lanes before it (the weights are the model's: m->main, m->ctx).
 struct ConjLane {
     cwm_conj_model* m;
-    StreamW main, ctx;
+    StreamWs main, ctx;
+    CrossWs cross;
     int* err;
-    float *qk, *v, *qk_src, *v_src, *scores_t, *cross_partial;
-    bf16 *ybuf, *ysbuf;
     bool have_prev = false;  // a cross block of this forward has used the projection buffers (run_cross); carried from stage to stage
 };
-
-void shift_stream(StreamW& S, int b0, int vcap, int mlp_ratio, bool small) {
-    const int next = S.n_tok + S.max_pad;
-    const size_t rows_e = (size_t)b0 * vcap, rows_d = (size_t)b0 * next;
-    const size_t act = std::max(rows_e * S.enc_dim, rows_d * S.dec_dim);
-    S.ext_mask += rows_d;
-    S.perm += rows_d;
-    S.tokens_in += 2 * rows_e * S.embed_kpad;
-    S.x_enc += rows_e * S.enc_dim;
-    S.x_dec += rows_d * S.dec_dim;
-    S.sb.hbuf += 2 * act;
-    S.sb.gbuf += 2 * act * mlp_ratio;
-    if (small) {
-        S.sb.qkv_f32 += 3 * act;
-    } else {
-        S.sb.qbuf += 2 * act;
-        S.sb.kbuf += 2 * act;
-        S.sb.vbuf += 2 * act;
-    }
-}
 
 // scratch of the context-side partials: the larger of the two kernel forms' needs (conj_kernels.hip / conj_attention.hip)
 size_t cross_partial_floats(int B, int heads, int M, int head_dim) {
     return std::max(cross_attention_partial_floats(B, heads, M, head_dim), cross_attention_mfma_partial_floats(B, heads, M, head_dim));
 }
 
+// The layout of the cross blocks' workspace, in elements per batch element (engine.h for_each_stream_buffer has the two streams').
+template <typename Visit>
+int for_each_cross_buffer(const cwm_conj_model* m, CrossWs& w, Visit&& visit) {
+    const size_t N = m->main.n_slots(), M = m->ctx.n_slots(), Dmax = std::max(m->main.enc_dim, m->main.dec_dim), heads = m->cfg.cross_heads;
+    int rc;
+    if ((rc = visit(w.qk, N * 2 * Dmax)) || (rc = visit(w.v, N * Dmax)) || (rc = visit(w.qk_src, M * 2 * Dmax)) || (rc = visit(w.v_src, M * Dmax)) ||
+        (rc = visit(w.scores_t, N * heads * M)) || (rc = visit(w.cross_partial, cross_partial_floats(1, (int)heads, (int)M, (int)(Dmax / heads)))) ||
+        (rc = visit(w.ybuf, 2 * N * Dmax)))
+        return rc;
+    return visit(w.ysbuf, 2 * M * Dmax);
+}
+
+// every batch-major buffer of the model: both streams at their visible-row capacities, and the cross blocks'
+template <typename Visit>
+int for_each_buffer(const cwm_conj_model* m, StreamWs& main, StreamWs& ctx, CrossWs& cross, int vmain_cap, int vctx_cap, Visit&& visit) {
+    int rc;
+    if ((rc = for_each_stream_buffer(m->main, main, vmain_cap, m->cfg.main.mlp_ratio, false, visit)) ||
+        (rc = for_each_stream_buffer(m->ctx, ctx, vctx_cap, m->cfg.main.mlp_ratio, true, visit)))
+        return rc;
+    return for_each_cross_buffer(m, cross, visit);
+}
+
+// offsets at the workspace's capacities (ws_vmain, ws_vctx), whatever the call's counts
 ConjLane conj_lane(cwm_conj_model* m, int lane, int b0) {
-    ConjLane L;
-    L.m = m;
-    L.main = m->main;
-    L.ctx = m->ctx;
-    shift_stream(L.main, b0, m->ws_vmain, m->cfg.main.mlp_ratio, false);
-    shift_stream(L.ctx, b0, m->ws_vctx, m->cfg.main.mlp_ratio, true);
-    const size_t Nb = (size_t)b0 * (m->main.n_tok + m->main.max_pad), Mb = (size_t)b0 * (m->ctx.n_tok + m->ctx.max_pad);
-    const size_t Dmax = std::max(m->main.enc_dim, m->main.dec_dim);
-    const int Mtok = m->ctx.n_tok + m->ctx.max_pad;
-    L.err = m->err + lane;
-    L.qk = m->qk + Nb * 2 * Dmax;
-    L.v = m->v + Nb * Dmax;
-    L.qk_src = m->qk_src + Mb * 2 * Dmax;
-    L.v_src = m->v_src + Mb * Dmax;
-    L.scores_t = m->scores_t + Nb * m->cfg.cross_heads * Mtok;
-    L.cross_partial = m->cross_partial + cross_partial_floats(b0, m->cfg.cross_heads, Mtok, (int)Dmax / m->cfg.cross_heads);
-    L.ybuf = m->ybuf + 2 * Nb * Dmax;
-    L.ysbuf = m->ysbuf + 2 * Mb * Dmax;
+    ConjLane L{m, m->main_ws, m->ctx_ws, m->cross_ws, m->err + lane};
+    (void)for_each_buffer(m, L.main, L.ctx, L.cross, m->ws_vmain, m->ws_vctx, WsShift{(size_t)b0});
     return L;
 }
 
 }  // namespace
 
 namespace {
-
-int make_stream(Engine& E, StreamW& S, const std::string& pre, int embed_k, std::vector<int64_t> embed_shape, int depth_e, int depth_d,
-                int mlp_ratio, bool sinusoid_f64, bool null_tokens) {
-    int rc;
-    S.embed_k = embed_k;
-    S.embed_kpad = round_up(embed_k, 64);
-    if ((rc = E.make_linear(S.embed, S.enc_dim, embed_k, true))) return rc;
-    E.add_matrix_slot(pre + "encoder.patch_embed.proj.weight", &S.embed, embed_shape);
-    E.add_vec_slot(pre + "encoder.patch_embed.proj.bias", S.embed.bias, {S.enc_dim});
-    S.enc.resize(depth_e);
-    S.dec.resize(depth_d);
-    for (int i = 0; i < depth_e; ++i)
-        if ((rc = E.make_block(S.enc[i], pre + "encoder.blocks." + std::to_string(i) + ".", S.enc_dim, mlp_ratio * S.enc_dim))) return rc;
-    if ((rc = E.make_vec(&S.enc_norm_g, S.enc_dim)) || (rc = E.make_vec(&S.enc_norm_b, S.enc_dim))) return rc;
-    E.add_vec_slot(pre + "encoder.norm.weight", S.enc_norm_g, {S.enc_dim});
-    E.add_vec_slot(pre + "encoder.norm.bias", S.enc_norm_b, {S.enc_dim});
-    if ((rc = E.make_linear(S.e2d, S.dec_dim, S.enc_dim, false))) return rc;
-    E.add_matrix_slot(pre + "encoder_to_decoder.weight", &S.e2d, {S.dec_dim, S.enc_dim});
-    for (int i = 0; i < depth_d; ++i)
-        if ((rc = E.make_block(S.dec[i], pre + "decoder.blocks." + std::to_string(i) + ".", S.dec_dim, mlp_ratio * S.dec_dim))) return rc;
-    if ((rc = E.make_vec(&S.dec_norm_g, S.dec_dim)) || (rc = E.make_vec(&S.dec_norm_b, S.dec_dim))) return rc;
-    E.add_vec_slot(pre + "decoder.norm.weight", S.dec_norm_g, {S.dec_dim});
-    E.add_vec_slot(pre + "decoder.norm.bias", S.dec_norm_b, {S.dec_dim});
-    if ((rc = E.make_linear(S.head, S.out_dim, S.dec_dim, true))) return rc;
-    E.add_matrix_slot(pre + "decoder.head.weight", &S.head, {S.out_dim, S.dec_dim});
-    E.add_vec_slot(pre + "decoder.head.bias", S.head.bias, {S.out_dim});
-    if ((rc = E.make_vec(&S.mask_token, S.dec_dim)) || (rc = E.make_vec(&S.null_enc, S.enc_dim))) return rc;
-    E.add_vec_slot(pre + "mask_token", S.mask_token, {1, 1, S.dec_dim});
-    if (null_tokens) E.add_vec_slot(pre + "null_token_enc", S.null_enc, {1, 1, S.enc_dim});
-    // positional tables with max_pad extra rows; the decoder's pad rows hold null_token_dec (_pad_pos_embed :154-165)
-    if (sinusoid_f64) {
-        if ((rc = E.make_sinusoid(&S.pos_enc_ext, S.n_tok, S.enc_dim, S.max_pad)) || (rc = E.make_sinusoid(&S.pos_dec_ext, S.n_tok, S.dec_dim, S.max_pad)))
-            return rc;
-    } else {
-        if ((rc = E.make_pos_embedding_f32(&S.pos_enc_ext, S.n_tok, S.enc_dim, S.max_pad)) ||
-            (rc = E.make_pos_embedding_f32(&S.pos_dec_ext, S.n_tok, S.dec_dim, S.max_pad)))
-            return rc;
-    }
-    if (null_tokens) E.add_vec_slot(pre + "null_token_dec", S.pos_dec_ext + (size_t)S.n_tok * S.dec_dim, {1, 1, S.dec_dim}, S.max_pad);
-    return 0;
-}
 
 int make_cross(Engine& E, CrossW& C, const std::string& pre, int ci, int cs, int ratio) {
     int rc;
@@ -206,40 +142,16 @@ int make_cross(Engine& E, CrossW& C, const std::string& pre, int ci, int cs, int
     return 0;
 }
 
-int stream_workspace(Engine& E, StreamW& S, int B, int vmax, int mlp_ratio, bool small) {
-    const int next = S.n_tok + S.max_pad;
-    const size_t rows_e = (size_t)B * vmax, rows_d = (size_t)B * next;
-    int rc;
-    if ((rc = E.ws(&S.ext_mask, rows_d)) || (rc = E.ws(&S.perm, rows_d)) || (rc = E.ws(&S.tokens_in, 2 * rows_e * S.embed_kpad)) ||
-        (rc = E.ws(&S.x_enc, rows_e * S.enc_dim)) || (rc = E.ws(&S.x_dec, rows_d * S.dec_dim)))
-        return rc;
-    const size_t act = std::max(rows_e * S.enc_dim, rows_d * S.dec_dim);
-    if ((rc = E.ws(&S.sb.hbuf, 2 * act)) || (rc = E.ws(&S.sb.gbuf, 2 * act * mlp_ratio))) return rc;
-    if (small) {
-        if ((rc = E.ws(&S.sb.qkv_f32, 3 * act))) return rc;
-    } else {
-        if ((rc = E.ws(&S.sb.qbuf, 2 * act)) || (rc = E.ws(&S.sb.kbuf, 2 * act))) return rc;
-        if ((rc = E.ws(&S.sb.vbuf, 2 * act))) return rc;
-    }
-    return 0;
-}
-
 int ensure_workspace(cwm_conj_model* m, int B, int vmain, int vctx) {
     if (m->ws_batch > 0 && B <= m->ws_batch && vmain <= m->ws_vmain && vctx <= m->ws_vctx) return 0;
     Engine& E = m->eng;
-    if (int rc = E.free_workspace()) return rc;
     const int Bc = std::max(B, m->ws_batch), vm = std::max(vmain, m->ws_vmain), vc = std::max(vctx, m->ws_vctx);
+    m->ws_batch = 0;  // (nothing is usable until all of it is there again)
     int rc;
-    if ((rc = stream_workspace(E, m->main, Bc, vm, m->cfg.main.mlp_ratio, false)) || (rc = stream_workspace(E, m->ctx, Bc, vc, m->cfg.main.mlp_ratio, true)))
-        return rc;
-    const size_t Nmax = (size_t)Bc * (m->main.n_tok + m->main.max_pad), Mmax = (size_t)Bc * (m->ctx.n_tok + m->ctx.max_pad);
-    const size_t Dmax = std::max(m->main.enc_dim, m->main.dec_dim);
-    const int Mtok = m->ctx.n_tok + m->ctx.max_pad;
-    if ((rc = E.ws(&m->err, 4)) || (rc = E.ws(&m->qk, Nmax * 2 * Dmax)) || (rc = E.ws(&m->v, Nmax * Dmax)) || (rc = E.ws(&m->qk_src, Mmax * 2 * Dmax)) ||
-        (rc = E.ws(&m->v_src, Mmax * Dmax)) || (rc = E.ws(&m->scores_t, Nmax * m->cfg.cross_heads * Mtok)) ||
-        (rc = E.ws(&m->cross_partial, cross_partial_floats(Bc, m->cfg.cross_heads, Mtok, (int)Dmax / m->cfg.cross_heads))) || (rc = E.ws(&m->ybuf, 2 * Nmax * Dmax)) ||
-        (rc = E.ws(&m->ysbuf, 2 * Mmax * Dmax)))
-        return rc;
+    if ((rc = E.free_workspace()) || (rc = for_each_buffer(m, m->main_ws, m->ctx_ws, m->cross_ws, vm, vc, WsAlloc{E, (size_t)Bc}))) return rc;
+    // `err` is not linear in the batch size (one word per lane: 4 words, lane l at err + l), so it is not part of the layout; nor are the staging
+    // buffers of the whole call's context input, which no lane owns a slice of (the lanes read them as they read the caller's inputs)
+    if ((rc = E.ws(&m->err, 4))) return rc;
     if (m->var.ctx_dummy_token &&
         ((rc = E.ws(&m->ctx_stage, (size_t)Bc * m->cfg.ctx_in_chans * (m->cfg.ctx_seq_len + m->cfg.ctx_tubelet))) || (rc = E.ws(&m->ctx_mask_stage, (size_t)Bc * m->ctx.n_tok))))
         return rc;
@@ -249,33 +161,6 @@ int ensure_workspace(cwm_conj_model* m, int B, int vmain, int vctx) {
     // (the zero fills above ran on the null stream; the lane streams are non-blocking and would not wait for them)
     CWM_HIP_CHECK(hipDeviceSynchronize());
     return 0;
-}
-
-int layernorm_to(Engine& E, const float* x, int rows, int D, const float* g, const float* b, bf16* out, int planes, hipStream_t s) {
-    LayerNormParams ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.x = x; ln.ldx = D; ln.gamma = g; ln.beta = b; ln.eps = E.ln_eps; ln.D = D; ln.rows = rows;
-    ln.out = out; ln.out_plane = (int64_t)rows * D; ln.ldo = D;
-    return E.run_layernorm(ln, planes, s);
-}
-
-// y = A W^T in the GEMM A-operand layout (what the MFMA cross attention reads its token fragments from)
-int linear_operand(Engine& E, const bf16* A, int rows, int K, const LinearW& L, bf16* out, int planes, hipStream_t s) {
-    GemmParams g = gemm_base(A, K, L, rows, planes);
-    g.epi = EPI_BF16; g.out_hi = out; g.out_plane = (int64_t)rows * L.N; g.ldo = L.N;
-    return E.run_gemm(g, planes, s);
-}
-
-int linear_f32(Engine& E, const bf16* A, int rows, int K, const LinearW& L, float* C, const float* resid, int planes, hipStream_t s) {
-    GemmParams g = gemm_base(A, K, L, rows, planes);
-    g.epi = EPI_F32; g.C = C; g.ldc = L.N; g.resid = resid; g.ldr = L.N;
-    return E.run_gemm(g, planes, s);
-}
-
-int linear_gelu(Engine& E, const bf16* A, int rows, int K, const LinearW& L, bf16* out, int planes, hipStream_t s) {
-    GemmParams g = gemm_base(A, K, L, rows, planes);
-    g.epi = EPI_BF16_GELU; g.out_hi = out; g.out_plane = (int64_t)rows * L.N; g.ldo = L.N;
-    return E.run_gemm(g, planes, s);
 }
 
 // CrossAttentionTransformerBlock.forward (transformer.py:559-583) with with_self_attention=False.
@@ -307,17 +192,17 @@ int run_cross(ConjLane& L, const CrossW& C, float* x, int N, int ci, float* src,
         CWM_HIP_CHECK(hipStreamWaitEvent(s, ev[3], 0));  // the previous block's role B has read qk / v
         CWM_HIP_CHECK(hipStreamWaitEvent(sc, ev[2], 0));  // ... its role A has read qk_src / v_src
     }
-    if ((rc = layernorm_to(E, x, rows, ci, C.n1_g, C.n1_b, L.main.sb.hbuf, planes, s))) return rc;
+    if ((rc = E.layernorm_to(x, rows, ci, C.n1_g, C.n1_b, L.main.sb.hbuf, planes, s))) return rc;
     if (mfma) {
-        if ((rc = linear_operand(E, L.main.sb.hbuf, rows, ci, C.qk, reinterpret_cast<bf16*>(L.qk), planes, s))) return rc;
-        if ((rc = linear_operand(E, L.main.sb.hbuf, rows, ci, C.v, reinterpret_cast<bf16*>(L.v), planes, s))) return rc;
+        if ((rc = E.linear_operand(L.main.sb.hbuf, rows, ci, C.qk, reinterpret_cast<bf16*>(L.cross.qk), planes, s))) return rc;
+        if ((rc = E.linear_operand(L.main.sb.hbuf, rows, ci, C.v, reinterpret_cast<bf16*>(L.cross.v), planes, s))) return rc;
     } else {
-        if ((rc = linear_f32(E, L.main.sb.hbuf, rows, ci, C.qk, L.qk, nullptr, planes, s))) return rc;
-        if ((rc = linear_f32(E, L.main.sb.hbuf, rows, ci, C.v, L.v, nullptr, planes, s))) return rc;
+        if ((rc = E.linear_f32(L.main.sb.hbuf, rows, ci, C.qk, L.cross.qk, nullptr, planes, s))) return rc;
+        if ((rc = E.linear_f32(L.main.sb.hbuf, rows, ci, C.v, L.cross.v, nullptr, planes, s))) return rc;
     }
-    if ((rc = layernorm_to(E, src, rows_s, cs, C.n1s_g, C.n1s_b, L.ctx.sb.hbuf, planes, t))) return rc;
-    if ((rc = linear_f32(E, L.ctx.sb.hbuf, rows_s, cs, C.qk_src, L.qk_src, nullptr, planes, t))) return rc;
-    if ((rc = linear_f32(E, L.ctx.sb.hbuf, rows_s, cs, C.v_src, L.v_src, nullptr, planes, t))) return rc;
+    if ((rc = E.layernorm_to(src, rows_s, cs, C.n1s_g, C.n1s_b, L.ctx.sb.hbuf, planes, t))) return rc;
+    if ((rc = E.linear_f32(L.ctx.sb.hbuf, rows_s, cs, C.qk_src, L.cross.qk_src, nullptr, planes, t))) return rc;
+    if ((rc = E.linear_f32(L.ctx.sb.hbuf, rows_s, cs, C.v_src, L.cross.v_src, nullptr, planes, t))) return rc;
     if (two) {
         CWM_HIP_CHECK(hipEventRecord(ev[0], s));
         CWM_HIP_CHECK(hipEventRecord(ev[1], sc));
@@ -326,9 +211,9 @@ int run_cross(ConjLane& L, const CrossW& C, float* x, int N, int ci, float* src,
     }
     CrossAttnParams ca;
     memset(&ca, 0, sizeof(ca));
-    ca.qk = L.qk; ca.v = L.v; ca.qk_op = reinterpret_cast<const bf16*>(L.qk); ca.v_op = reinterpret_cast<const bf16*>(L.v); ca.qk_src = L.qk_src; ca.v_src = L.v_src; ca.B = B; ca.N = N; ca.M = M; ca.heads = heads; ca.head_dim = hd;
+    ca.qk = L.cross.qk; ca.v = L.cross.v; ca.qk_op = reinterpret_cast<const bf16*>(L.cross.qk); ca.v_op = reinterpret_cast<const bf16*>(L.cross.v); ca.qk_src = L.cross.qk_src; ca.v_src = L.cross.v_src; ca.B = B; ca.N = N; ca.M = M; ca.heads = heads; ca.head_dim = hd;
     ca.scale = 1.0f / sqrtf((float)hd);
-    ca.y = L.ybuf; ca.y_plane = (int64_t)rows * D; ca.y_src = L.ysbuf; ca.y_src_plane = (int64_t)rows_s * D; ca.scores_t = L.scores_t; ca.partial = L.cross_partial;
+    ca.y = L.cross.ybuf; ca.y_plane = (int64_t)rows * D; ca.y_src = L.cross.ysbuf; ca.y_src_plane = (int64_t)rows_s * D; ca.scores_t = L.cross.scores_t; ca.partial = L.cross.cross_partial;
     if (two) {
         if ((rc = launch_cross_attention_mfma_roles(ca, planes, s, sc, 1))) return rc;
         CWM_HIP_CHECK(hipEventRecord(ev[2], s));
@@ -341,44 +226,15 @@ int run_cross(ConjLane& L, const CrossW& C, float* x, int N, int ci, float* src,
                           [&] { return mfma ? launch_cross_attention_mfma(ca, planes, s) : launch_cross_attention(ca, planes, s); })))
             return rc;
     }
-    if ((rc = linear_f32(E, L.ybuf, rows, D, C.proj, x, x, planes, s))) return rc;          // x += proj(y) + b
-    if ((rc = layernorm_to(E, x, rows, ci, C.n2_g, C.n2_b, L.main.sb.hbuf, planes, s))) return rc;
-    if ((rc = linear_gelu(E, L.main.sb.hbuf, rows, ci, C.mlp_t0, L.main.sb.gbuf, planes, s))) return rc;
-    if ((rc = linear_f32(E, L.main.sb.gbuf, rows, C.mlp_t0.N, C.mlp_t2, x, x, planes, s))) return rc;
-    if ((rc = linear_f32(E, L.ysbuf, rows_s, D, C.proj_src, src, src, planes, t))) return rc;
-    if ((rc = layernorm_to(E, src, rows_s, cs, C.n2s_g, C.n2s_b, L.ctx.sb.hbuf, planes, t))) return rc;
-    if ((rc = linear_gelu(E, L.ctx.sb.hbuf, rows_s, cs, C.mlp_s0, L.ctx.sb.gbuf, planes, t))) return rc;
-    if ((rc = linear_f32(E, L.ctx.sb.gbuf, rows_s, C.mlp_s0.N, C.mlp_s2, src, src, planes, t))) return rc;
+    if ((rc = E.linear_f32(L.cross.ybuf, rows, D, C.proj, x, x, planes, s))) return rc;          // x += proj(y) + b
+    if ((rc = E.run_mlp(C.n2_g, C.n2_b, C.mlp_t0, C.mlp_t2, x, B, N, ci, planes, L.main.sb, s))) return rc;
+    if ((rc = E.linear_f32(L.cross.ysbuf, rows_s, D, C.proj_src, src, src, planes, t))) return rc;
+    if ((rc = E.run_mlp(C.n2s_g, C.n2s_b, C.mlp_s0, C.mlp_s2, src, B, M, cs, planes, L.ctx.sb, t))) return rc;
     if (sc != s && !two) {  // VALU fallback: the context stream continues behind the whole block
         CWM_HIP_CHECK(hipEventRecord(ev[0], s));
         CWM_HIP_CHECK(hipStreamWaitEvent(sc, ev[0], 0));
     }
     return 0;
-}
-
-// tokens + pos | null tokens, gathered by the padded mask (pad_and_mask_input, conjoined_vmae.py:125-134)
-int embed_stream(cwm_conj_model* m, StreamW& S, int B, int vmax, int planes, hipStream_t s) {
-    Engine& E = m->eng;
-    const int next = S.n_tok + S.max_pad;
-    GemmParams g = gemm_base(S.tokens_in, S.embed_kpad, S.embed, B * vmax, planes);
-    g.epi = EPI_F32; g.C = S.x_enc; g.ldc = S.enc_dim;
-    g.resid = S.pos_enc_ext; g.ldr = S.enc_dim; g.resid_rowmap = S.perm; g.rows_in = vmax; g.rows_out = vmax; g.map_stride = next;
-    if (int rc = E.run_gemm(g, planes, s)) return rc;
-    if (S.max_pad == 0) return 0;  // unpadded variant: no pad slots
-    return launch_fix_pad_rows(S.x_enc, S.perm, B, next, vmax, S.n_tok, S.enc_dim, S.null_enc, s);
-}
-
-// encoder.norm, encoder_to_decoder, [x_vis + pos_ext[vis] | mask_token + pos_ext[masked]]
-int to_decoder(cwm_conj_model* m, StreamW& S, int B, int vmax, int planes, hipStream_t s) {
-    Engine& E = m->eng;
-    const int next = S.n_tok + S.max_pad;
-    int rc;
-    if ((rc = layernorm_to(E, S.x_enc, B * vmax, S.enc_dim, S.enc_norm_g, S.enc_norm_b, S.sb.hbuf, planes, s))) return rc;
-    GemmParams g = gemm_base(S.sb.hbuf, S.enc_dim, S.e2d, B * vmax, planes);
-    g.epi = EPI_F32; g.C = S.x_dec; g.ldc = S.dec_dim;
-    g.resid = S.pos_dec_ext; g.ldr = S.dec_dim; g.resid_rowmap = S.perm; g.rows_in = vmax; g.rows_out = next; g.map_stride = next;
-    if ((rc = E.run_gemm(g, planes, s))) return rc;
-    return E.run_fill_mask_tokens(S.x_dec, S.mask_token, S.pos_dec_ext, S.perm, B, next, vmax, S.dec_dim, s);
 }
 
 }  // namespace
@@ -436,10 +292,10 @@ extern "C" int cwm_conj_create_ex(const cwm_conj_config* cfg, const cwm_conj_var
     S.n_tok = ctx_tokens; S.max_pad = c.ctx_max_pad; S.out_dim = c.ctx_in_chans * c.ctx_tubelet;
     int rc = 0;
     do {
-        if ((rc = make_stream(E, A, "main_stream.", mc.in_chans * mc.patch * mc.patch, {mc.enc_dim, mc.in_chans, 1, mc.patch, mc.patch}, mc.enc_depth,
+        if ((rc = E.make_stream(A, "main_stream.", mc.in_chans * mc.patch * mc.patch, {mc.enc_dim, mc.in_chans, 1, mc.patch, mc.patch}, mc.enc_depth,
                               mc.dec_depth, mc.mlp_ratio, true, v.padded)))
             break;
-        if ((rc = make_stream(E, S, "context_stream.", c.ctx_in_chans * c.ctx_tubelet, {c.ctx_enc_dim, c.ctx_in_chans, c.ctx_tubelet, 1, 1}, mc.enc_depth,
+        if ((rc = E.make_stream(S, "context_stream.", c.ctx_in_chans * c.ctx_tubelet, {c.ctx_enc_dim, c.ctx_in_chans, c.ctx_tubelet, 1, 1}, mc.enc_depth,
                               mc.dec_depth, mc.mlp_ratio, false, v.padded)))
             break;
         if (v.ctx_dummy_token) {  // ImuEncoder.dummy_token, registered between context_stream.mask_token and the patch embed
@@ -492,10 +348,10 @@ static int conj_forward_lane(ConjLane& L, const cwm_conj_forward_args* a, int b0
     cwm_conj_model* m = L.m;
     const cwm_conj_config& c = m->cfg;
     const cwm_config& mc = c.main;
-    StreamW& A = L.main;
-    StreamW& S = L.ctx;
+    const StreamW &A = m->main, &S = m->ctx;
+    StreamWs &Aw = L.main, &Sw = L.ctx;
     const int vm = a->n_vis_max, vc = a->n_vis_ctx_max;
-    const int Nx = A.n_tok + A.max_pad, Mx = S.n_tok + S.max_pad;
+    const int Nx = A.n_slots(), Mx = S.n_slots();
     const int n_out = Nx - vm;
     Engine& E = m->eng;
     const int planes = a->mode == CWM_MODE_PARITY ? 2 : 1;
@@ -536,10 +392,10 @@ static int conj_forward_lane(ConjLane& L, const cwm_conj_forward_args* a, int b0
     have_prev = false;
     // a13: padded masks -> permutations [visible slots ascending | masked slots ascending] over n_tok + max_pad slots
     CWM_HIP_CHECK(hipMemsetAsync(L.err, 0, sizeof(int), s));
-    if ((rc = launch_pad_mask(mask_in, B, A.n_tok, A.max_pad, vm, A.ext_mask, s))) return rc;
-    if ((rc = launch_mask_to_perm(A.ext_mask, B, Nx, vm, A.perm, L.err, s))) return rc;
-    if ((rc = launch_pad_mask(ctx_mask_in, B, S.n_tok, S.max_pad, vc, S.ext_mask, s))) return rc;
-    if ((rc = launch_mask_to_perm(S.ext_mask, B, Mx, vc, S.perm, L.err, s))) return rc;
+    if ((rc = launch_pad_mask(mask_in, B, A.n_tok, A.max_pad, vm, Aw.ext_mask, s))) return rc;
+    if ((rc = launch_mask_to_perm(Aw.ext_mask, B, Nx, vm, Aw.perm, L.err, s))) return rc;
+    if ((rc = launch_pad_mask(ctx_mask_in, B, S.n_tok, S.max_pad, vc, Sw.ext_mask, s))) return rc;
+    if ((rc = launch_mask_to_perm(Sw.ext_mask, B, Mx, vc, Sw.perm, L.err, s))) return rc;
 
     // a2/a14: tokenise both streams (visible slots only)
     if (m->var.main_input == CWM_CONJ_INPUT_FLOWBACK_RGB01) {
@@ -548,8 +404,8 @@ static int conj_forward_lane(ConjLane& L, const cwm_conj_forward_args* a, int b0
         fg.fwd = a->flow_fwd_dev + b0 * a->flow_fwd_stride_b; fg.f_sb = a->flow_fwd_stride_b; fg.f_sc = a->flow_fwd_stride_c;
         fg.bwd = a->flow_bwd_dev + b0 * a->flow_bwd_stride_b; fg.b_sb = a->flow_bwd_stride_b; fg.b_sc = a->flow_bwd_stride_c;
         fg.x = x_in; fg.sb = a->x_stride_b; fg.sc = a->x_stride_c; fg.normalize = a->normalize;
-        fg.H = mc.img_h; fg.W = mc.img_w; fg.P = mc.patch; fg.perm = A.perm; fg.Nt = A.n_tok; fg.perm_stride = Nx; fg.n_rows = vm; fg.B = B;
-        fg.out = A.tokens_in; fg.out_plane = (int64_t)B * vm * A.embed_kpad; fg.ld = A.embed_kpad;
+        fg.H = mc.img_h; fg.W = mc.img_w; fg.P = mc.patch; fg.perm = Aw.perm; fg.Nt = A.n_tok; fg.perm_stride = Nx; fg.n_rows = vm; fg.B = B;
+        fg.out = Aw.tokens_in; fg.out_plane = (int64_t)B * vm * A.embed_kpad; fg.ld = A.embed_kpad;
         if ((rc = E.timed(CWM_KCLASS_PATCH_GATHER, (double)B * vm * 7 * mc.patch * mc.patch * (4.0 + 2.0 * planes), s,
                           [&] { return launch_flow_rgb_gather(fg, planes, s); })))
             return rc;
@@ -557,17 +413,17 @@ static int conj_forward_lane(ConjLane& L, const cwm_conj_forward_args* a, int b0
         PatchGatherParams pg;
         memset(&pg, 0, sizeof(pg));
         pg.x = x_in; pg.sb = a->x_stride_b; pg.sc = a->x_stride_c; pg.st = a->x_stride_t; pg.normalize = a->normalize;
-        pg.C = mc.in_chans; pg.H = mc.img_h; pg.W = mc.img_w; pg.P = mc.patch; pg.perm = A.perm; pg.Nt = A.n_tok; pg.perm_stride = Nx; pg.n_rows = vm; pg.B = B;
-        pg.out = A.tokens_in; pg.out_plane = (int64_t)B * vm * A.embed_kpad; pg.ld = A.embed_kpad;
+        pg.C = mc.in_chans; pg.H = mc.img_h; pg.W = mc.img_w; pg.P = mc.patch; pg.perm = Aw.perm; pg.Nt = A.n_tok; pg.perm_stride = Nx; pg.n_rows = vm; pg.B = B;
+        pg.out = Aw.tokens_in; pg.out_plane = (int64_t)B * vm * A.embed_kpad; pg.ld = A.embed_kpad;
         if ((rc = E.run_patch_gather(pg, planes, s))) return rc;
     }
-    if ((rc = embed_stream(m, A, B, vm, planes, s))) return rc;
+    if ((rc = E.embed_stream(A, Aw, B, vm, planes, s))) return rc;
     ImuGatherParams ig;
     memset(&ig, 0, sizeof(ig));
-    ig.imu = ctx_in; ig.B = B; ig.C = c.ctx_in_chans; ig.L = ctx_len; ig.tubelet = c.ctx_tubelet; ig.perm = S.perm; ig.perm_stride = Mx;
-    ig.n_rows = vc; ig.n_real = S.n_tok; ig.out = S.tokens_in; ig.out_plane = (int64_t)B * vc * S.embed_kpad; ig.ld = S.embed_kpad;
+    ig.imu = ctx_in; ig.B = B; ig.C = c.ctx_in_chans; ig.L = ctx_len; ig.tubelet = c.ctx_tubelet; ig.perm = Sw.perm; ig.perm_stride = Mx;
+    ig.n_rows = vc; ig.n_real = S.n_tok; ig.out = Sw.tokens_in; ig.out_plane = (int64_t)B * vc * S.embed_kpad; ig.ld = S.embed_kpad;
     if ((rc = launch_imu_gather(ig, planes, s))) return rc;
-    if ((rc = embed_stream(m, S, B, vc, planes, s))) return rc;
+    if ((rc = E.embed_stream(S, Sw, B, vc, planes, s))) return rc;
     if ((rc = ctx_follows_main())) return rc;
     }
 
@@ -576,21 +432,21 @@ static int conj_forward_lane(ConjLane& L, const cwm_conj_forward_args* a, int b0
         if (!in_range(1 + i)) continue;
         for (int k = 0; k < c.n_enc_cross; ++k)
             if (c.enc_cross[k] == i &&
-                (rc = run_cross(L, m->enc_cross[k], A.x_enc, vm, A.enc_dim, S.x_enc, vc, S.enc_dim, B, planes, s, sc, m->ev_cross[lane], have_prev)))
+                (rc = run_cross(L, m->enc_cross[k], Aw.x_enc, vm, A.enc_dim, Sw.x_enc, vc, S.enc_dim, B, planes, s, sc, m->ev_cross[lane], have_prev)))
                 return rc;
-        if ((rc = E.run_block(A.enc[i], A.x_enc, B, vm, A.enc_dim, A.enc_heads, planes, A.sb, s))) return rc;
-        if ((rc = E.run_block_small(S.enc[i], S.x_enc, B, vc, S.enc_dim, S.enc_heads, planes, S.sb, sc))) return rc;
+        if ((rc = E.run_block(A.enc[i], Aw.x_enc, B, vm, A.enc_dim, A.enc_heads, planes, Aw.sb, s))) return rc;
+        if ((rc = E.run_block_small(S.enc[i], Sw.x_enc, B, vc, S.enc_dim, S.enc_heads, planes, Sw.sb, sc))) return rc;
     }
-    if (in_range(st_todec) && ((rc = to_decoder(m, A, B, vm, planes, s)) || (rc = to_decoder(m, S, B, vc, planes, sc)))) return rc;
+    if (in_range(st_todec) && ((rc = E.to_decoder(A, Aw, B, vm, planes, s)) || (rc = E.to_decoder(S, Sw, B, vc, planes, sc)))) return rc;
 
     // decoder: cross block AFTER the blocks listed in dec_cross (forward_decoder_blocks :688-720)
     for (int i = 0; i < mc.dec_depth; ++i) {
         if (!in_range(st_todec + 1 + i)) continue;
-        if ((rc = E.run_block(A.dec[i], A.x_dec, B, Nx, A.dec_dim, A.dec_heads, planes, A.sb, s))) return rc;
-        if ((rc = E.run_block_small(S.dec[i], S.x_dec, B, Mx, S.dec_dim, S.dec_heads, planes, S.sb, sc))) return rc;
+        if ((rc = E.run_block(A.dec[i], Aw.x_dec, B, Nx, A.dec_dim, A.dec_heads, planes, Aw.sb, s))) return rc;
+        if ((rc = E.run_block_small(S.dec[i], Sw.x_dec, B, Mx, S.dec_dim, S.dec_heads, planes, Sw.sb, sc))) return rc;
         for (int k = 0; k < c.n_dec_cross; ++k)
             if (c.dec_cross[k] == i &&
-                (rc = run_cross(L, m->dec_cross[k], A.x_dec, Nx, A.dec_dim, S.x_dec, Mx, S.dec_dim, B, planes, s, sc, m->ev_cross[lane], have_prev)))
+                (rc = run_cross(L, m->dec_cross[k], Aw.x_dec, Nx, A.dec_dim, Sw.x_dec, Mx, S.dec_dim, B, planes, s, sc, m->ev_cross[lane], have_prev)))
                 return rc;
     }
     if (!in_range(st_out)) return CWM_OK;
@@ -598,31 +454,15 @@ static int conj_forward_lane(ConjLane& L, const cwm_conj_forward_args* a, int b0
     if (a->y_ctx_tokens_dev) {
         const int n_out_c = Mx - vc;
         float* y_ctx = a->y_ctx_tokens_dev + (size_t)b0 * n_out_c * S.out_dim;
-        LayerNormParams lc;
-        memset(&lc, 0, sizeof(lc));
-        lc.x = S.x_dec; lc.ldx = S.dec_dim; lc.gamma = S.dec_norm_g; lc.beta = S.dec_norm_b; lc.eps = E.ln_eps; lc.D = S.dec_dim;
-        lc.rows = B * n_out_c; lc.rows_out_per_b = n_out_c; lc.rows_in_per_b = Mx; lc.in_offset = vc;
-        lc.out = S.sb.hbuf; lc.out_plane = (int64_t)B * n_out_c * S.dec_dim; lc.ldo = S.dec_dim;
-        if ((rc = E.run_layernorm(lc, planes, sc))) return rc;
-        GemmParams gc = gemm_base(S.sb.hbuf, S.dec_dim, S.head, B * n_out_c, planes);
-        gc.epi = EPI_F32; gc.C = y_ctx; gc.ldc = S.out_dim;
-        if ((rc = E.run_gemm(gc, planes, sc))) return rc;
-        if ((rc = launch_zero_pad_out_rows(y_ctx, S.perm, B, Mx, vc, n_out_c, S.n_tok, S.out_dim, sc))) return rc;
+        if ((rc = E.head_rows(S, Sw, B, n_out_c, y_ctx, planes, sc))) return rc;
+        if ((rc = launch_zero_pad_out_rows(y_ctx, Sw.perm, B, Mx, vc, n_out_c, S.n_tok, S.out_dim, sc))) return rc;
     }
     if ((rc = main_follows_ctx())) return rc;  // the call's stream semantics cover the context stream's work too
 
     // main output: head(norm(x[:, -n_out:])) * ~null_mask   (conjoined_decode :984-1002); the flow -> IMU model may skip it
     if (!y_tokens || n_out == 0) return CWM_OK;
-    LayerNormParams ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.x = A.x_dec; ln.ldx = A.dec_dim; ln.gamma = A.dec_norm_g; ln.beta = A.dec_norm_b; ln.eps = E.ln_eps; ln.D = A.dec_dim;
-    ln.rows = B * n_out; ln.rows_out_per_b = n_out; ln.rows_in_per_b = Nx; ln.in_offset = vm;
-    ln.out = A.sb.hbuf; ln.out_plane = (int64_t)B * n_out * A.dec_dim; ln.ldo = A.dec_dim;
-    if ((rc = E.run_layernorm(ln, planes, s))) return rc;
-    GemmParams g = gemm_base(A.sb.hbuf, A.dec_dim, A.head, B * n_out, planes);
-    g.epi = EPI_F32; g.C = y_tokens; g.ldc = A.out_dim;
-    if ((rc = E.run_gemm(g, planes, s))) return rc;
-    return launch_zero_pad_out_rows(y_tokens, A.perm, B, Nx, vm, n_out, A.n_tok, A.out_dim, s);
+    if ((rc = E.head_rows(A, Aw, B, n_out, y_tokens, planes, s))) return rc;
+    return launch_zero_pad_out_rows(y_tokens, Aw.perm, B, Nx, vm, n_out, A.n_tok, A.out_dim, s);
 }
 
 extern "C" int cwm_conj_forward(cwm_conj_model* m, const cwm_conj_forward_args* a_in) {
@@ -638,7 +478,7 @@ extern "C" int cwm_conj_forward(cwm_conj_model* m, const cwm_conj_forward_args* 
     CWM_REQUIRE(a->y_tokens_dev || a->y_ctx_tokens_dev, "cwm_conj_forward: no output requested");
     CWM_REQUIRE(a->mode == CWM_MODE_FAST || a->mode == CWM_MODE_PARITY, "cwm_conj_forward: bad mode %d", a->mode);
     const int B = a->batch, vm = a->n_vis_max, vc = a->n_vis_ctx_max;
-    const int Nx = m->main.n_tok + m->main.max_pad;
+    const int Nx = m->main.n_slots();
     // (unpadded: a fully visible main stream is allowed when only the context output is asked for -- the decoder then has Nm = 0)
     CWM_REQUIRE(B > 0 && vm > 0 && (vm < Nx || (!m->var.padded && !(a->y_tokens_dev && vm == Nx))) && vc > 0 && vc <= m->ctx.n_tok,
                 "cwm_conj_forward: bad batch / visible counts (%d, %d, %d)", B, vm, vc);

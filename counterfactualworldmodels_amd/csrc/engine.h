@@ -63,6 +63,46 @@ struct StreamBuffers {
     float* qkv_f32 = nullptr;  // only for streams whose head_dim != 64 (small-sequence attention path)
 };
 
+// One token stream (patch / tubelet embed -> encoder -> encoder_to_decoder -> decoder -> head): the plain VMAE predictor is one of them (no padding, no null
+// tokens), a conjoined predictor two.  StreamW is what creation fixes (dims and weights), StreamWs the stream's workspace pointers.
+struct StreamW {
+    int enc_dim = 0, dec_dim = 0, enc_heads = 0, dec_heads = 0, n_tok = 0, max_pad = 0, out_dim = 0, embed_k = 0, embed_kpad = 0;
+    std::vector<BlockW> enc, dec;
+    LinearW embed, e2d, head;
+    float *enc_norm_g = nullptr, *enc_norm_b = nullptr, *dec_norm_g = nullptr, *dec_norm_b = nullptr;
+    float *mask_token = nullptr, *null_enc = nullptr;
+    float *pos_enc_ext = nullptr, *pos_dec_ext = nullptr;  // [n_tok + max_pad][D]; pad rows: 0 (enc) / null_token_dec (dec)
+    int n_slots() const { return n_tok + max_pad; }
+};
+
+// Every buffer is batch-major, so a lane that starts at batch element b0 owns the slice behind the capacity of b0 elements: a lane works on its own copy of
+// this struct (for_each_stream_buffer), next to a reference to the StreamW.
+struct StreamWs {
+    uint8_t* ext_mask = nullptr;  // (a stream that takes the caller's mask as it is leaves it unused: one byte per token)
+    int* perm = nullptr;
+    bf16* tokens_in = nullptr;
+    float *x_enc = nullptr, *x_dec = nullptr;
+    StreamBuffers sb;
+};
+
+// THE layout of a stream's workspace: visit(pointer, elements per batch element) for every buffer.  Every size is linear in the batch size, so the same
+// statement serves the allocation (WsAlloc: per_b * batch capacity elements) and a lane's view (WsShift: pointer += per_b * b0).  vcap = the visible rows per
+// sample the workspace holds -- its CAPACITY (the handle's ws_nvis / ws_vmain / ws_vctx), not a call's count --; small = the stream keeps qkv in fp32
+// (run_block_small) instead of the three bf16 buffers.
+template <typename Visit>
+int for_each_stream_buffer(const StreamW& S, StreamWs& w, int vcap, int mlp_ratio, bool small, Visit&& visit) {
+    const size_t rows_e = (size_t)vcap, rows_d = (size_t)S.n_slots();
+    const size_t act = std::max(rows_e * S.enc_dim, rows_d * S.dec_dim);
+    int rc;
+    if ((rc = visit(w.ext_mask, rows_d)) || (rc = visit(w.perm, rows_d)) || (rc = visit(w.tokens_in, 2 * rows_e * S.embed_kpad)) ||
+        (rc = visit(w.x_enc, rows_e * S.enc_dim)) || (rc = visit(w.x_dec, rows_d * S.dec_dim)) || (rc = visit(w.sb.hbuf, 2 * act)) ||
+        (rc = visit(w.sb.gbuf, 2 * act * mlp_ratio)))
+        return rc;
+    if (small) return visit(w.sb.qkv_f32, 3 * act);
+    if ((rc = visit(w.sb.qbuf, 2 * act)) || (rc = visit(w.sb.kbuf, 2 * act))) return rc;
+    return visit(w.sb.vbuf, 2 * act);
+}
+
 // Encoder rows (batch elements x visible tokens) each half of a batch must keep for the forward to run as two batch lanes (cwm_forward,
 // cwm_conj_forward).  Measured (tools/lane_threshold.py, round 4): ViT-B/8 batch 8 / 10 / 14 (3168 / 3960 / 5544 rows per half) -6 / -7.5 / -10 % with
 // two lanes, batch 6 (2376) +3 %; ViT-L/4 batch 2 (3168) -7 %.  (Rounds 1-3 used 6000: batch >= 16.)
@@ -123,6 +163,9 @@ struct Engine {
     int make_block(BlockW& b, const std::string& pre, int D, int hidden);
     int make_sinusoid(float** dst, int n_pos, int d, int extra_rows = 0);      // VideoMAE/utils.py:251-268 (float64 host)
     int make_pos_embedding_f32(float** dst, int n_pos, int d, int extra_rows = 0);  // transformer.py:37-52 (float32)
+    // weights and state-dict slots of one stream under the key prefix `pre` (S's dims, n_tok, max_pad and out_dim are set by the caller)
+    int make_stream(StreamW& S, const std::string& pre, int embed_k, std::vector<int64_t> embed_shape, int depth_e, int depth_d, int mlp_ratio,
+                    bool sinusoid_f64, bool null_tokens);
 
     int load_weight(const char* key, const float* data, int on_device, const int64_t* shape, int ndim);
     int missing_weights(char* buf, int buflen);
@@ -147,10 +190,24 @@ struct Engine {
     }
     int timer_begin(int kclass, double work, hipStream_t s, EventPair** out);
     int timer_end(EventPair* e, hipStream_t s);
+    // the launches every forward is made of: LayerNorm of `rows` contiguous rows into the GEMM A-operand layout, and y = A W^T + bias in fp32 (+ resid), in
+    // the A-operand layout (what the MFMA cross attention reads its token fragments from), or through GELU in the A-operand layout
+    int layernorm_to(const float* x, int rows, int D, const float* g, const float* b, bf16* out, int planes, hipStream_t s);
+    int linear_f32(const bf16* A, int rows, int K, const LinearW& L, float* C, const float* resid, int planes, hipStream_t s);
+    int linear_operand(const bf16* A, int rows, int K, const LinearW& L, bf16* out, int planes, hipStream_t s);
+    int linear_gelu(const bf16* A, int rows, int K, const LinearW& L, bf16* out, int planes, hipStream_t s);
+    // x += fc2(gelu(fc1(LN x))) on x[B*n_tok, D] (in place): the second half of a Block and of each side of a cross block.  n_keep: see run_block
+    int run_mlp(const float* ln_g, const float* ln_b, const LinearW& fc1, const LinearW& fc2, float* x, int B, int n_tok, int D, int planes, StreamBuffers& sb,
+                hipStream_t s, int n_keep = 0);
     // Block.forward (VideoMAE/utils.py:146-153) on a residual stream x[B*n_tok, D] (in place), head_dim 64
     int run_block(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s, int n_keep = 0);
     // same for short sequences with any head_dim (fp32 VALU attention): the IMU context stream
     int run_block_small(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s);
+    // the pieces of a stream's forward around its blocks, over B samples of n_vis visible rows each (w: the lane's view)
+    int embed_stream(const StreamW& S, const StreamWs& w, int B, int n_vis, int planes, hipStream_t s);
+    int to_decoder(const StreamW& S, const StreamWs& w, int B, int n_vis, int planes, hipStream_t s);
+    // out[B][n_out][head.N] = head(norm(x_dec[:, -n_out:]))
+    int head_rows(const StreamW& S, const StreamWs& w, int B, int n_out, float* out, int planes, hipStream_t s);
 
     int timing_enable(int kclass, int enable);
     int timing_collect(int kclass, cwm_kernel_stats* out);
@@ -167,6 +224,22 @@ int copy_args(Args& dst, const Args* src, size_t min_size, const char* fn, const
     memcpy(&dst, src, std::min<size_t>(src->struct_size, sizeof(dst)));
     return 0;
 }
+
+// The two visitors of a workspace layout (for_each_stream_buffer): allocate every buffer for `batch` elements, or move every pointer behind b0 elements.
+struct WsAlloc {
+    Engine& E;
+    size_t batch;
+    template <typename T>
+    int operator()(T*& p, size_t per_b) const { return E.ws(&p, per_b * batch); }
+};
+struct WsShift {
+    size_t b0;
+    template <typename T>
+    int operator()(T*& p, size_t per_b) const {
+        p += per_b * b0;
+        return 0;
+    }
+};
 
 GemmParams gemm_base(const bf16* A, int lda, const LinearW& L, int M, int planes);
 

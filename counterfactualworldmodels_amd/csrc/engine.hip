@@ -257,6 +257,47 @@ int Engine::make_pos_embedding_f32(float** dst, int n_pos, int d, int extra_rows
     return 0;
 }
 
+int Engine::make_stream(StreamW& S, const std::string& pre, int embed_k, std::vector<int64_t> embed_shape, int depth_e, int depth_d, int mlp_ratio,
+                        bool sinusoid_f64, bool null_tokens) {
+    int rc;
+    S.embed_k = embed_k;
+    S.embed_kpad = round_up(embed_k, 64);
+    if ((rc = make_linear(S.embed, S.enc_dim, embed_k, true))) return rc;
+    add_matrix_slot(pre + "encoder.patch_embed.proj.weight", &S.embed, embed_shape);
+    add_vec_slot(pre + "encoder.patch_embed.proj.bias", S.embed.bias, {S.enc_dim});
+    S.enc.resize(depth_e);
+    S.dec.resize(depth_d);
+    for (int i = 0; i < depth_e; ++i)
+        if ((rc = make_block(S.enc[i], pre + "encoder.blocks." + std::to_string(i) + ".", S.enc_dim, mlp_ratio * S.enc_dim))) return rc;
+    if ((rc = make_vec(&S.enc_norm_g, S.enc_dim)) || (rc = make_vec(&S.enc_norm_b, S.enc_dim))) return rc;
+    add_vec_slot(pre + "encoder.norm.weight", S.enc_norm_g, {S.enc_dim});
+    add_vec_slot(pre + "encoder.norm.bias", S.enc_norm_b, {S.enc_dim});
+    if ((rc = make_linear(S.e2d, S.dec_dim, S.enc_dim, false))) return rc;
+    add_matrix_slot(pre + "encoder_to_decoder.weight", &S.e2d, {S.dec_dim, S.enc_dim});
+    for (int i = 0; i < depth_d; ++i)
+        if ((rc = make_block(S.dec[i], pre + "decoder.blocks." + std::to_string(i) + ".", S.dec_dim, mlp_ratio * S.dec_dim))) return rc;
+    if ((rc = make_vec(&S.dec_norm_g, S.dec_dim)) || (rc = make_vec(&S.dec_norm_b, S.dec_dim))) return rc;
+    add_vec_slot(pre + "decoder.norm.weight", S.dec_norm_g, {S.dec_dim});
+    add_vec_slot(pre + "decoder.norm.bias", S.dec_norm_b, {S.dec_dim});
+    if ((rc = make_linear(S.head, S.out_dim, S.dec_dim, true))) return rc;
+    add_matrix_slot(pre + "decoder.head.weight", &S.head, {S.out_dim, S.dec_dim});
+    add_vec_slot(pre + "decoder.head.bias", S.head.bias, {S.out_dim});
+    if ((rc = make_vec(&S.mask_token, S.dec_dim)) || (rc = make_vec(&S.null_enc, S.enc_dim))) return rc;
+    add_vec_slot(pre + "mask_token", S.mask_token, {1, 1, S.dec_dim});
+    if (null_tokens) add_vec_slot(pre + "null_token_enc", S.null_enc, {1, 1, S.enc_dim});
+    // positional tables with max_pad extra rows; the decoder's pad rows hold null_token_dec (_pad_pos_embed, conjoined_vmae.py:154-165)
+    if (sinusoid_f64) {
+        if ((rc = make_sinusoid(&S.pos_enc_ext, S.n_tok, S.enc_dim, S.max_pad)) || (rc = make_sinusoid(&S.pos_dec_ext, S.n_tok, S.dec_dim, S.max_pad)))
+            return rc;
+    } else {
+        if ((rc = make_pos_embedding_f32(&S.pos_enc_ext, S.n_tok, S.enc_dim, S.max_pad)) ||
+            (rc = make_pos_embedding_f32(&S.pos_dec_ext, S.n_tok, S.dec_dim, S.max_pad)))
+            return rc;
+    }
+    if (null_tokens) add_vec_slot(pre + "null_token_dec", S.pos_dec_ext + (size_t)S.n_tok * S.dec_dim, {1, 1, S.dec_dim}, S.max_pad);
+    return 0;
+}
+
 int Engine::load_weight(const char* key, const float* data, int on_device, const int64_t* shape, int ndim) {
     CWM_REQUIRE(key && data && shape, "load_weight: null argument");
     if (int rc = cwm_require_device(device, "load_weight")) return rc;
@@ -528,6 +569,65 @@ GemmParams gemm_base(const bf16* A, int lda, const LinearW& L, int M, int planes
     return p;
 }
 
+int Engine::layernorm_to(const float* x, int rows, int D, const float* g, const float* b, bf16* out, int planes, hipStream_t s) {
+    LayerNormParams ln;
+    memset(&ln, 0, sizeof(ln));
+    ln.x = x; ln.ldx = D; ln.gamma = g; ln.beta = b; ln.eps = ln_eps; ln.D = D; ln.rows = rows;
+    ln.out = out; ln.out_plane = (int64_t)rows * D; ln.ldo = D;
+    return run_layernorm(ln, planes, s);
+}
+
+int Engine::linear_f32(const bf16* A, int rows, int K, const LinearW& L, float* C, const float* resid, int planes, hipStream_t s) {
+    GemmParams g = gemm_base(A, K, L, rows, planes);
+    g.epi = EPI_F32; g.C = C; g.ldc = L.N; g.resid = resid; g.ldr = L.N;
+    return run_gemm(g, planes, s);
+}
+
+int Engine::linear_operand(const bf16* A, int rows, int K, const LinearW& L, bf16* out, int planes, hipStream_t s) {
+    GemmParams g = gemm_base(A, K, L, rows, planes);
+    g.epi = EPI_BF16; g.out_hi = out; g.out_plane = (int64_t)rows * L.N; g.ldo = L.N;
+    return run_gemm(g, planes, s);
+}
+
+int Engine::linear_gelu(const bf16* A, int rows, int K, const LinearW& L, bf16* out, int planes, hipStream_t s) {
+    GemmParams g = gemm_base(A, K, L, rows, planes);
+    g.epi = EPI_BF16_GELU; g.out_hi = out; g.out_plane = (int64_t)rows * L.N; g.ldo = L.N;
+    return run_gemm(g, planes, s);
+}
+
+// The rows a pruned block keeps (run_block's n_keep): the LAST n_out of every sample's n_tok, compact in the activations and addressed with
+// an offset in the residual stream.
+namespace {
+struct KeptRows {
+    bool part;
+    int n_out, first;
+    KeptRows(int n_tok, int n_keep) : part(n_keep > 0 && n_keep < n_tok), n_out(part ? n_keep : n_tok), first(n_tok - n_out) {}
+};
+}  // namespace
+
+// x[kept rows] += A W^T + bias (one of the two residual GEMMs of a block; A holds the kept rows only)
+static int residual_gemm(Engine& E, const bf16* A, int K, const LinearW& L, float* x, int B, int n_tok, const KeptRows& kr, int planes, hipStream_t s) {
+    GemmParams r = gemm_base(A, K, L, B * kr.n_out, planes);
+    r.epi = EPI_F32; r.C = x; r.ldc = L.N; r.resid = x; r.ldr = L.N;
+    if (kr.part) { r.rows_in = kr.n_out; r.rows_out = n_tok; r.out_row_offset = kr.first; }
+    return E.run_gemm(r, planes, s);
+}
+
+int Engine::run_mlp(const float* ln_g, const float* ln_b, const LinearW& fc1, const LinearW& fc2, float* x, int B, int n_tok, int D, int planes,
+                    StreamBuffers& sb, hipStream_t s, int n_keep) {
+    const KeptRows kr(n_tok, n_keep);
+    const int Mo = B * kr.n_out;
+    int rc;
+    LayerNormParams ln;
+    memset(&ln, 0, sizeof(ln));
+    ln.x = x; ln.ldx = D; ln.gamma = ln_g; ln.beta = ln_b; ln.eps = ln_eps; ln.D = D; ln.rows = Mo;
+    ln.out = sb.hbuf; ln.out_plane = (int64_t)Mo * D; ln.ldo = D;
+    if (kr.part) { ln.rows_out_per_b = kr.n_out; ln.rows_in_per_b = n_tok; ln.in_offset = kr.first; }
+    if ((rc = run_layernorm(ln, planes, s))) return rc;
+    if ((rc = linear_gelu(sb.hbuf, Mo, D, fc1, sb.gbuf, planes, s))) return rc;
+    return residual_gemm(*this, sb.gbuf, fc1.N, fc2, x, B, n_tok, kr, planes, s);
+}
+
 // Block.forward (VideoMAE/utils.py:146-153): x += proj(attn(LN1 x)); x += fc2(gelu(fc1(LN2 x)))
 // n_keep (0 = all): only the LAST n_keep tokens of every sample are needed downstream (the last decoder block: the decoder returns
 // head(norm(x[:, -Nm:])), vmae.py:250-251).  Keys / values still come from all tokens; queries, proj, LN2 and the MLP run on the
@@ -535,15 +635,9 @@ GemmParams gemm_base(const bf16* A, int lda, const LinearW& L, int M, int planes
 int Engine::run_block(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s, int n_keep) {
     const int M = B * n_tok;
     const int64_t hplane = (int64_t)M * D;
-    const int hidden = w.fc1.N;
-    const bool part = n_keep > 0 && n_keep < n_tok;
-    const int n_out = part ? n_keep : n_tok, Mo = B * n_out, first = n_tok - n_out;
+    const KeptRows kr(n_tok, n_keep);
     int rc;
-    LayerNormParams ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.x = x; ln.ldx = D; ln.gamma = w.ln1_g; ln.beta = w.ln1_b; ln.eps = ln_eps; ln.D = D; ln.rows = M;
-    ln.out = sb.hbuf; ln.out_plane = hplane; ln.ldo = D;
-    if ((rc = run_layernorm(ln, planes, s))) return rc;
+    if ((rc = layernorm_to(x, M, D, w.ln1_g, w.ln1_b, sb.hbuf, planes, s))) return rc;
 
     GemmParams g = gemm_base(sb.hbuf, D, w.qkv, M, planes);
     g.epi = EPI_QKV;
@@ -557,44 +651,20 @@ int Engine::run_block(const BlockW& w, float* x, int B, int n_tok, int D, int H,
     AttnParams a;
     memset(&a, 0, sizeof(a));
     a.q = sb.qbuf; a.k = sb.kbuf; a.v = sb.vbuf; a.qk_plane = hplane;
-    a.o = sb.hbuf; a.o_plane = (int64_t)Mo * D; a.ldo = D; a.n_tok = n_tok; a.heads = H; a.batch = B;
-    if (part) { a.q_off = first; a.n_q = n_out; }
+    a.o = sb.hbuf; a.o_plane = (int64_t)B * kr.n_out * D; a.ldo = D; a.n_tok = n_tok; a.heads = H; a.batch = B;
+    if (kr.part) { a.q_off = kr.first; a.n_q = kr.n_out; }
     if ((rc = run_attention(a, planes, s))) return rc;
 
-    // the two residual GEMMs
-    auto residual = [&](GemmParams& r) {
-        r.epi = EPI_F32; r.C = x; r.ldc = D; r.resid = x; r.ldr = D;
-        if (part) { r.rows_in = n_out; r.rows_out = n_tok; r.out_row_offset = first; }
-    };
-    g = gemm_base(sb.hbuf, D, w.proj, Mo, planes);
-    residual(g);
-    if ((rc = run_gemm(g, planes, s))) return rc;
-
-    ln.gamma = w.ln2_g; ln.beta = w.ln2_b;
-    if (part) { ln.rows = Mo; ln.rows_out_per_b = n_out; ln.rows_in_per_b = n_tok; ln.in_offset = first; ln.out_plane = (int64_t)Mo * D; }
-    if ((rc = run_layernorm(ln, planes, s))) return rc;
-    g = gemm_base(sb.hbuf, D, w.fc1, Mo, planes);
-    g.epi = EPI_BF16_GELU; g.out_hi = sb.gbuf; g.out_plane = (int64_t)Mo * hidden; g.ldo = hidden;
-    if ((rc = run_gemm(g, planes, s))) return rc;
-
-    g = gemm_base(sb.gbuf, hidden, w.fc2, Mo, planes);
-    residual(g);
-    return run_gemm(g, planes, s);
+    if ((rc = residual_gemm(*this, sb.hbuf, D, w.proj, x, B, n_tok, kr, planes, s))) return rc;
+    return run_mlp(w.ln2_g, w.ln2_b, w.fc1, w.fc2, x, B, n_tok, D, planes, sb, s, n_keep);
 }
 
 // The same Block for a short sequence (n_tok <= 64) with any head_dim <= 64: qkv stays fp32 and the
 // attention is the small fp32 VALU kernel (the IMU context stream: 25/50 tokens, head_dim 32).
 int Engine::run_block_small(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s) {
     const int M = B * n_tok;
-    const int64_t hplane = (int64_t)M * D;
-    const int hidden = w.fc1.N;
     int rc;
-    LayerNormParams ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.x = x; ln.ldx = D; ln.gamma = w.ln1_g; ln.beta = w.ln1_b; ln.eps = ln_eps; ln.D = D; ln.rows = M;
-    ln.out = sb.hbuf; ln.out_plane = hplane; ln.ldo = D;
-    if ((rc = run_layernorm(ln, planes, s))) return rc;
-
+    if ((rc = layernorm_to(x, M, D, w.ln1_g, w.ln1_b, sb.hbuf, planes, s))) return rc;
     GemmParams g = gemm_base(sb.hbuf, D, w.qkv, M, planes);
     g.epi = EPI_F32; g.C = sb.qkv_f32; g.ldc = 3 * D;
     if ((rc = run_gemm(g, planes, s))) return rc;
@@ -602,25 +672,50 @@ int Engine::run_block_small(const BlockW& w, float* x, int B, int n_tok, int D, 
     SmallAttnParams a;
     memset(&a, 0, sizeof(a));
     a.qkv = sb.qkv_f32; a.B = B; a.n_tok = n_tok; a.heads = H; a.head_dim = D / H;
-    a.o = sb.hbuf; a.o_plane = hplane; a.ldo = D;
+    a.o = sb.hbuf; a.o_plane = (int64_t)M * D; a.ldo = D;
     if ((rc = timed(CWM_KCLASS_SMALL_ATTN, 4.0 * (double)B * H * n_tok * n_tok * (D / H), s, [&] {
              return (tune.conj_attn && small_attention_mfma_ok(n_tok, D / H) && D % 32 == 0) ? launch_small_attention_mfma(a, planes, s) : launch_small_attention(a, planes, s);
          })))
         return rc;
 
-    g = gemm_base(sb.hbuf, D, w.proj, M, planes);
-    g.epi = EPI_F32; g.C = x; g.ldc = D; g.resid = x; g.ldr = D;
+    if ((rc = linear_f32(sb.hbuf, M, D, w.proj, x, x, planes, s))) return rc;
+    return run_mlp(w.ln2_g, w.ln2_b, w.fc1, w.fc2, x, B, n_tok, D, planes, sb, s);
+}
+
+// tokens + pos | null tokens, gathered by the padded mask (pad_and_mask_input, conjoined_vmae.py:125-134): the embed GEMM with bias and the positional
+// table's rows, picked by the permutation, added in the epilogue
+int Engine::embed_stream(const StreamW& S, const StreamWs& w, int B, int n_vis, int planes, hipStream_t s) {
+    const int next = S.n_slots();
+    GemmParams g = gemm_base(w.tokens_in, S.embed_kpad, S.embed, B * n_vis, planes);
+    g.epi = EPI_F32; g.C = w.x_enc; g.ldc = S.enc_dim;
+    g.resid = S.pos_enc_ext; g.ldr = S.enc_dim; g.resid_rowmap = w.perm; g.rows_in = n_vis; g.rows_out = n_vis; g.map_stride = next;
+    if (int rc = run_gemm(g, planes, s)) return rc;
+    if (S.max_pad == 0) return 0;  // no pad slots
+    return launch_fix_pad_rows(w.x_enc, w.perm, B, next, n_vis, S.n_tok, S.enc_dim, S.null_enc, s);
+}
+
+// encoder.norm, encoder_to_decoder (no bias) + pos_ext[vis] written straight into x_dec rows [0, n_vis), mask_token + pos_ext[masked] behind them
+int Engine::to_decoder(const StreamW& S, const StreamWs& w, int B, int n_vis, int planes, hipStream_t s) {
+    const int next = S.n_slots();
+    int rc;
+    if ((rc = layernorm_to(w.x_enc, B * n_vis, S.enc_dim, S.enc_norm_g, S.enc_norm_b, w.sb.hbuf, planes, s))) return rc;
+    GemmParams g = gemm_base(w.sb.hbuf, S.enc_dim, S.e2d, B * n_vis, planes);
+    g.epi = EPI_F32; g.C = w.x_dec; g.ldc = S.dec_dim;
+    g.resid = S.pos_dec_ext; g.ldr = S.dec_dim; g.resid_rowmap = w.perm; g.rows_in = n_vis; g.rows_out = next; g.map_stride = next;
     if ((rc = run_gemm(g, planes, s))) return rc;
+    return run_fill_mask_tokens(w.x_dec, S.mask_token, S.pos_dec_ext, w.perm, B, next, n_vis, S.dec_dim, s);  // (no launch when nothing is masked)
+}
 
-    ln.gamma = w.ln2_g; ln.beta = w.ln2_b;
-    if ((rc = run_layernorm(ln, planes, s))) return rc;
-
-    g = gemm_base(sb.hbuf, D, w.fc1, M, planes);
-    g.epi = EPI_BF16_GELU; g.out_hi = sb.gbuf; g.out_plane = (int64_t)M * hidden; g.ldo = hidden;
-    if ((rc = run_gemm(g, planes, s))) return rc;
-
-    g = gemm_base(sb.gbuf, hidden, w.fc2, M, planes);
-    g.epi = EPI_F32; g.C = x; g.ldc = D; g.resid = x; g.ldr = D;
+int Engine::head_rows(const StreamW& S, const StreamWs& w, int B, int n_out, float* out, int planes, hipStream_t s) {
+    const int next = S.n_slots();
+    LayerNormParams ln;
+    memset(&ln, 0, sizeof(ln));
+    ln.x = w.x_dec; ln.ldx = S.dec_dim; ln.gamma = S.dec_norm_g; ln.beta = S.dec_norm_b; ln.eps = ln_eps; ln.D = S.dec_dim;
+    ln.rows = B * n_out; ln.rows_out_per_b = n_out; ln.rows_in_per_b = next; ln.in_offset = next - n_out;
+    ln.out = w.sb.hbuf; ln.out_plane = (int64_t)B * n_out * S.dec_dim; ln.ldo = S.dec_dim;
+    if (int rc = run_layernorm(ln, planes, s)) return rc;
+    GemmParams g = gemm_base(w.sb.hbuf, S.dec_dim, S.head, B * n_out, planes);
+    g.epi = EPI_F32; g.C = out; g.ldc = S.out_dim;
     return run_gemm(g, planes, s);
 }
 

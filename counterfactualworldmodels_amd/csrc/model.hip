@@ -9,21 +9,21 @@
 
 using namespace cwm;
 
+// The workspace of a forward: the token stream's buffers + what only this model has.  Every buffer is batch-major, so the lane that starts at batch
+// element b0 owns the slice behind the capacity of b0 elements (lane_ws).
+struct ModelWs {
+    StreamWs st;
+    int* rank = nullptr;  // inverse permutation, for the un-embed
+    int* err = nullptr;   // one word per batch row (index_gather_kernel writes every row's, every call: no memset)
+};
+
 struct cwm_model {
     Engine eng;
     cwm_config cfg;
-    int Nt = 0, n_per_frame = 0, patch_k = 0, patch_kpad = 0, out_dim = 0;
-    std::vector<BlockW> enc, dec;
-    LinearW patch, e2d, head;
-    float *enc_norm_g = nullptr, *enc_norm_b = nullptr, *dec_norm_g = nullptr, *dec_norm_b = nullptr;
-    float* mask_token = nullptr;
-    float *pos_enc = nullptr, *pos_dec = nullptr;  // [Nt][De], [Nt][Dd] sinusoid tables
+    StreamW st;  // the model is ONE token stream without padding (max_pad = 0, no null tokens)
     // workspace (grown on demand)
     int ws_batch = 0, ws_nvis = 0;
-    int *perm = nullptr, *rank = nullptr, *err = nullptr;
-    bf16* patches = nullptr;
-    float *x_enc = nullptr, *x_dec = nullptr;
-    StreamBuffers sb;
+    ModelWs ws;
     // batch lanes (cwm_model_set_lanes): a batch whose slices keep >= kMinLaneRows encoder rows each runs as up to `lanes` slices, the first on the
     // caller's stream and the others on streams of `lane_set`, joined by events before cwm_forward returns control of the stream
     int lanes = 2;
@@ -31,33 +31,24 @@ struct cwm_model {
     Lanes lane_set;
 };
 
-// per-lane view of the workspace: every buffer is batch-major, so the lane that starts at batch element b0 owns the slice
-// behind the capacity of b0 elements
-struct LaneWs {
-    int *perm, *rank, *err;
-    bf16* patches;
-    float *x_enc, *x_dec;
-    StreamBuffers sb;
-};
-
 namespace {
+
+// the workspace layout (engine.h for_each_stream_buffer): the stream's buffers for n_vis_cap visible rows per sample, and the inverse permutation
+template <typename Visit>
+int for_each_buffer(const cwm_model* m, ModelWs& w, int n_vis_cap, Visit&& visit) {
+    if (int rc = for_each_stream_buffer(m->st, w.st, n_vis_cap, m->cfg.mlp_ratio, false, visit)) return rc;
+    return visit(w.rank, (size_t)m->st.n_tok);
+}
 
 int ensure_workspace(cwm_model* m, int B, int n_vis) {
     if (B <= m->ws_batch && n_vis <= m->ws_nvis && m->ws_batch > 0) return 0;
     Engine& E = m->eng;
-    if (int rc = E.free_workspace()) return rc;
-    const cwm_config& c = m->cfg;
-    const int Bc = std::max(B, m->ws_batch), Nv = std::max(n_vis, m->ws_nvis), Nt = m->Nt;
-    const size_t rows_e = (size_t)Bc * Nv, rows_d = (size_t)Bc * Nt;
+    const int Bc = std::max(B, m->ws_batch), Nv = std::max(n_vis, m->ws_nvis);
+    m->ws_batch = 0;  // (nothing is usable until all of it is there again)
     int rc;
-    if ((rc = E.ws(&m->perm, rows_d)) || (rc = E.ws(&m->rank, rows_d)) || (rc = E.ws(&m->err, (size_t)Bc + 4))) return rc;
-    if ((rc = E.ws(&m->patches, 2 * rows_e * m->patch_kpad))) return rc;
-    if ((rc = E.ws(&m->x_enc, rows_e * c.enc_dim)) || (rc = E.ws(&m->x_dec, rows_d * c.dec_dim))) return rc;
-    const size_t act = std::max(rows_e * c.enc_dim, rows_d * c.dec_dim);
-    if ((rc = E.ws(&m->sb.hbuf, 2 * act)) || (rc = E.ws(&m->sb.gbuf, 2 * act * c.mlp_ratio)) || (rc = E.ws(&m->sb.qbuf, 2 * act)) ||
-        (rc = E.ws(&m->sb.kbuf, 2 * act)))
-        return rc;
-    if ((rc = E.ws(&m->sb.vbuf, 2 * act))) return rc;
+    if ((rc = E.free_workspace()) || (rc = for_each_buffer(m, m->ws, Nv, WsAlloc{E, (size_t)Bc}))) return rc;
+    // `err` is the one buffer that is not linear in the batch size (B + 4 words), so it is not part of the layout: allocated here, sliced in lane_ws
+    if ((rc = E.ws(&m->ws.err, (size_t)Bc + 4))) return rc;
     m->ws_batch = Bc;
     m->ws_nvis = Nv;
     // (the zero fills above ran on the null stream; the lane streams are non-blocking and would not wait for them)
@@ -65,23 +56,11 @@ int ensure_workspace(cwm_model* m, int B, int n_vis) {
     return 0;
 }
 
-LaneWs lane_ws(const cwm_model* m, int b0) {
-    const cwm_config& c = m->cfg;
-    const size_t rows_e = (size_t)b0 * m->ws_nvis, rows_d = (size_t)b0 * m->Nt;
-    const size_t act = std::max(rows_e * c.enc_dim, rows_d * c.dec_dim);
-    LaneWs w;
-    w.perm = m->perm + rows_d;
-    w.rank = m->rank + rows_d;
-    w.err = m->err + b0;  // one word per batch row (index_gather_kernel writes every row's, every call: no memset)
-    w.patches = m->patches + 2 * rows_e * m->patch_kpad;
-    w.x_enc = m->x_enc + rows_e * c.enc_dim;
-    w.x_dec = m->x_dec + rows_d * c.dec_dim;
-    w.sb = m->sb;
-    w.sb.hbuf += 2 * act;
-    w.sb.gbuf += 2 * act * c.mlp_ratio;
-    w.sb.qbuf += 2 * act;
-    w.sb.kbuf += 2 * act;
-    w.sb.vbuf += 2 * act;
+// the view of the lane that starts at batch element b0: offsets at the workspace's capacity (ws_nvis), whatever the call's n_vis
+ModelWs lane_ws(const cwm_model* m, int b0) {
+    ModelWs w = m->ws;
+    (void)for_each_buffer(m, w, m->ws_nvis, WsShift{(size_t)b0});
+    w.err += b0;
     return w;
 }
 
@@ -105,40 +84,12 @@ extern "C" int cwm_model_create(const cwm_config* cfg, cwm_model** out) {
     Engine& E = m->eng;
     E.ln_eps = c.ln_eps;
     CWM_HIP_CHECK(hipGetDevice(&E.device));
-    m->n_per_frame = (c.img_h / c.patch) * (c.img_w / c.patch);
-    m->Nt = m->n_per_frame * c.num_frames;
-    m->patch_k = c.in_chans * c.patch * c.patch;
-    m->patch_kpad = round_up(m->patch_k, 64);
-    m->out_dim = c.in_chans * c.patch * c.patch;
-    int rc = 0;
-    m->enc.resize(c.enc_depth);
-    m->dec.resize(c.dec_depth);
-    do {
-        if ((rc = E.make_linear(m->patch, c.enc_dim, m->patch_k, true))) break;
-        E.add_matrix_slot("encoder.patch_embed.proj.weight", &m->patch, {c.enc_dim, c.in_chans, 1, c.patch, c.patch});
-        E.add_vec_slot("encoder.patch_embed.proj.bias", m->patch.bias, {c.enc_dim});
-        for (int i = 0; i < c.enc_depth && !rc; ++i)
-            rc = E.make_block(m->enc[i], "encoder.blocks." + std::to_string(i) + ".", c.enc_dim, c.mlp_ratio * c.enc_dim);
-        if (rc) break;
-        if ((rc = E.make_vec(&m->enc_norm_g, c.enc_dim)) || (rc = E.make_vec(&m->enc_norm_b, c.enc_dim))) break;
-        E.add_vec_slot("encoder.norm.weight", m->enc_norm_g, {c.enc_dim});
-        E.add_vec_slot("encoder.norm.bias", m->enc_norm_b, {c.enc_dim});
-        if ((rc = E.make_linear(m->e2d, c.dec_dim, c.enc_dim, false))) break;
-        E.add_matrix_slot("encoder_to_decoder.weight", &m->e2d, {c.dec_dim, c.enc_dim});
-        if ((rc = E.make_vec(&m->mask_token, c.dec_dim))) break;
-        E.add_vec_slot("mask_token", m->mask_token, {1, 1, c.dec_dim});
-        for (int i = 0; i < c.dec_depth && !rc; ++i)
-            rc = E.make_block(m->dec[i], "decoder.blocks." + std::to_string(i) + ".", c.dec_dim, c.mlp_ratio * c.dec_dim);
-        if (rc) break;
-        if ((rc = E.make_vec(&m->dec_norm_g, c.dec_dim)) || (rc = E.make_vec(&m->dec_norm_b, c.dec_dim))) break;
-        E.add_vec_slot("decoder.norm.weight", m->dec_norm_g, {c.dec_dim});
-        E.add_vec_slot("decoder.norm.bias", m->dec_norm_b, {c.dec_dim});
-        if ((rc = E.make_linear(m->head, m->out_dim, c.dec_dim, true))) break;
-        E.add_matrix_slot("decoder.head.weight", &m->head, {m->out_dim, c.dec_dim});
-        E.add_vec_slot("decoder.head.bias", m->head.bias, {m->out_dim});
-        if ((rc = E.make_sinusoid(&m->pos_enc, m->Nt, c.enc_dim))) break;  // vmae.py:75
-        if ((rc = E.make_sinusoid(&m->pos_dec, m->Nt, c.dec_dim))) break;  // vmae.py:366
-    } while (0);
+    StreamW& S = m->st;
+    S.enc_dim = c.enc_dim; S.dec_dim = c.dec_dim; S.enc_heads = c.enc_heads; S.dec_heads = c.dec_heads;
+    S.n_tok = (c.img_h / c.patch) * (c.img_w / c.patch) * c.num_frames; S.out_dim = c.in_chans * c.patch * c.patch;
+    // (the float64 sinusoid tables: vmae.py:75, :366)
+    const int rc = E.make_stream(S, "", c.in_chans * c.patch * c.patch, {c.enc_dim, c.in_chans, 1, c.patch, c.patch}, c.enc_depth, c.dec_depth, c.mlp_ratio,
+                                 true, false);
     if (rc) {
         cwm_model_destroy(m);
         return rc;
@@ -160,25 +111,25 @@ extern "C" int cwm_model_missing_weights(cwm_model* m, char* buf, int buflen) { 
 // a producer GEMM then adds to its store-bound epilogue cost more than the LayerNorm launch they replace, DESIGN.md section 4.6 -- never the
 // default and removed in round 4.)
 
-// One lane: batch elements [b0, b0 + B) of the call, on stream s, in the workspace slice w.
+// One lane: batch elements [b0, b0 + B) of the call, on stream s, in the workspace slice lw.
 // Stages [stage_lo, stage_hi) of the lane's launch sequence: 0 = mask -> permutation, patch gather + embed; 1 .. Le = encoder blocks;
 // Le + 1 = encoder norm + encoder_to_decoder + mask tokens; Le + 2 .. Le + 1 + Ld = decoder blocks; Le + Ld + 2 = norm + head + un-embed.
 // (cwm_forward issues stage by stage over all lanes, so that after a host synchronisation every lane's queue starts filling at once
 // instead of lane 1 waiting behind lane 0's ~136 launches.)
-static int forward_lane(cwm_model* m, const cwm_forward_args* a, int b0, int B, LaneWs w, hipStream_t s, int stage_lo, int stage_hi) {
+static int forward_lane(cwm_model* m, const cwm_forward_args* a, int b0, int B, ModelWs lw, hipStream_t s, int stage_lo, int stage_hi) {
     const cwm_config& c = m->cfg;
-    const int Nt = m->Nt, Nv = a->n_vis, Nm = Nt - Nv;
+    const StreamW& S = m->st;
+    StreamWs& w = lw.st;
+    const int Nt = S.n_tok, Nv = a->n_vis, Nm = Nt - Nv;
     const int Nret = Nm > 0 ? Nm : Nt;
     Engine& E = m->eng;
     const int planes = a->mode == CWM_MODE_PARITY ? 2 : 1;
     const float* x_in = a->x_dev + (int64_t)b0 * a->x_stride_b;
     const uint8_t* mask_in = a->mask_dev + (size_t)b0 * Nt;
-    float* y_tokens = a->y_tokens_dev + (size_t)b0 * Nret * m->out_dim;
+    float* y_tokens = a->y_tokens_dev + (size_t)b0 * Nret * S.out_dim;
     int rc;
     auto in_range = [&](int st) { return st >= stage_lo && st < stage_hi; };
     const int st_e2d = c.enc_depth + 1, st_head = c.enc_depth + c.dec_depth + 2;
-    GemmParams g;
-    LayerNormParams ln;
 
     if (in_range(0)) {
     // a1-a3: mask -> permutation (+ its inverse for the un-embed, + the per-row check of the visible count), frame load (+normalise) and
@@ -188,66 +139,42 @@ static int forward_lane(cwm_model* m, const cwm_forward_args* a, int b0, int B, 
     memset(&pg, 0, sizeof(pg));
     pg.x = x_in; pg.sb = a->x_stride_b; pg.sc = a->x_stride_c; pg.st = a->x_stride_t; pg.normalize = a->normalize;
     pg.C = c.in_chans; pg.H = c.img_h; pg.W = c.img_w; pg.P = c.patch; pg.perm = w.perm; pg.Nt = Nt; pg.n_rows = Nv; pg.B = B;
-    pg.out = w.patches; pg.out_plane = (int64_t)B * Nv * m->patch_kpad; pg.ld = m->patch_kpad;
+    pg.out = w.tokens_in; pg.out_plane = (int64_t)B * Nv * S.embed_kpad; pg.ld = S.embed_kpad;
     if (E.tune.index_fused) {
-        if ((rc = E.run_index_gather(pg, mask_in, Nv, w.perm, a->y_video_dev ? w.rank : nullptr, w.err, planes, s))) return rc;
+        if ((rc = E.run_index_gather(pg, mask_in, Nv, w.perm, a->y_video_dev ? lw.rank : nullptr, lw.err, planes, s))) return rc;
     } else {  // the four launches of rounds 1-4 (A/B and the bitwise cross-check of the fused kernel)
-        CWM_HIP_CHECK(hipMemsetAsync(w.err, 0, (size_t)B * sizeof(int), s));
-        if ((rc = launch_mask_to_perm(mask_in, B, Nt, Nv, w.perm, w.err, s))) return rc;
+        CWM_HIP_CHECK(hipMemsetAsync(lw.err, 0, (size_t)B * sizeof(int), s));
+        if ((rc = launch_mask_to_perm(mask_in, B, Nt, Nv, w.perm, lw.err, s))) return rc;
         if ((rc = E.run_patch_gather(pg, planes, s))) return rc;
-        if (a->y_video_dev && (rc = launch_perm_to_rank(w.perm, w.rank, B, Nt, s))) return rc;
+        if (a->y_video_dev && (rc = launch_perm_to_rank(w.perm, lw.rank, B, Nt, s))) return rc;
     }
-    }
-
-    StreamBuffers sb_enc = w.sb, sb_dec = w.sb;
-    if (in_range(0)) {
-    g = gemm_base(w.patches, m->patch_kpad, m->patch, B * Nv, planes);
-    g.epi = EPI_F32; g.C = w.x_enc; g.ldc = c.enc_dim;
-    g.resid = m->pos_enc; g.ldr = c.enc_dim; g.resid_rowmap = w.perm; g.rows_in = Nv; g.rows_out = Nv; g.map_stride = Nt;
-    if ((rc = E.run_gemm(g, planes, s))) return rc;
+    if ((rc = E.embed_stream(S, w, B, Nv, planes, s))) return rc;
     }
 
     // a4-a6: encoder blocks over the visible tokens
     for (int i = 0; i < c.enc_depth; ++i)
-        if (in_range(1 + i) && (rc = E.run_block(m->enc[i], w.x_enc, B, Nv, c.enc_dim, c.enc_heads, planes, sb_enc, s))) return rc;
+        if (in_range(1 + i) && (rc = E.run_block(S.enc[i], w.x_enc, B, Nv, S.enc_dim, S.enc_heads, planes, w.sb, s))) return rc;
 
-    // a7: encoder.norm, encoder_to_decoder (no bias); a8: + pos[vis] written straight into x_full rows [0,Nv)
-    if (in_range(st_e2d)) {
-    memset(&ln, 0, sizeof(ln));
-    ln.x = w.x_enc; ln.ldx = c.enc_dim; ln.gamma = m->enc_norm_g; ln.beta = m->enc_norm_b; ln.eps = c.ln_eps; ln.D = c.enc_dim;
-    ln.rows = B * Nv; ln.out = w.sb.hbuf; ln.out_plane = (int64_t)B * Nv * c.enc_dim; ln.ldo = c.enc_dim;
-    if ((rc = E.run_layernorm(ln, planes, s))) return rc;
-    g = gemm_base(w.sb.hbuf, c.enc_dim, m->e2d, B * Nv, planes);
-    g.epi = EPI_F32; g.C = w.x_dec; g.ldc = c.dec_dim;
-    g.resid = m->pos_dec; g.ldr = c.dec_dim; g.resid_rowmap = w.perm; g.rows_in = Nv; g.rows_out = Nt; g.map_stride = Nt;
-    if ((rc = E.run_gemm(g, planes, s))) return rc;
-    if (Nm > 0 && (rc = E.run_fill_mask_tokens(w.x_dec, m->mask_token, m->pos_dec, w.perm, B, Nt, Nv, c.dec_dim, s))) return rc;
-    }
+    // a7: encoder.norm, encoder_to_decoder (no bias); a8: + pos[vis] written straight into x_full rows [0,Nv), mask tokens behind them
+    if (in_range(st_e2d) && (rc = E.to_decoder(S, w, B, Nv, planes, s))) return rc;
 
     // a9: decoder blocks over the full token set, norm + head on the last Nm tokens
     // (the last block only has to produce the Nm rows the head reads: option "prune_last_block" = 0 runs it in full)
     const bool pruned = Nm > 0 && E.tune.prune_last_block;
     for (int i = 0; i < c.dec_depth; ++i) {
         const int keep = (i == c.dec_depth - 1 && pruned) ? Nm : 0;
-        if (in_range(st_e2d + 1 + i) && (rc = E.run_block(m->dec[i], w.x_dec, B, Nt, c.dec_dim, c.dec_heads, planes, sb_dec, s, keep))) return rc;
+        if (in_range(st_e2d + 1 + i) && (rc = E.run_block(S.dec[i], w.x_dec, B, Nt, S.dec_dim, S.dec_heads, planes, w.sb, s, keep))) return rc;
     }
     if (!in_range(st_head)) return CWM_OK;
-    memset(&ln, 0, sizeof(ln));
-    ln.x = w.x_dec; ln.ldx = c.dec_dim; ln.gamma = m->dec_norm_g; ln.beta = m->dec_norm_b; ln.eps = c.ln_eps; ln.D = c.dec_dim;
-    ln.rows = B * Nret; ln.rows_out_per_b = Nret; ln.rows_in_per_b = Nt; ln.in_offset = Nt - Nret;
-    ln.out = w.sb.hbuf; ln.out_plane = (int64_t)B * Nret * c.dec_dim; ln.ldo = c.dec_dim;
-    if ((rc = E.run_layernorm(ln, planes, s))) return rc;
-    g = gemm_base(w.sb.hbuf, c.dec_dim, m->head, B * Nret, planes);
-    g.epi = EPI_F32; g.C = y_tokens; g.ldc = m->out_dim;
-    if ((rc = E.run_gemm(g, planes, s))) return rc;
+    if ((rc = E.head_rows(S, w, B, Nret, y_tokens, planes, s))) return rc;
 
     // a11: patch un-embed scatter
     if (a->y_video_dev) {
         const float* xr = a->xraw_dev ? a->xraw_dev + (int64_t)b0 * a->x_stride_b : x_in;
-        UnembedParams u;  // (w.rank: written by the index prologue of stage 0)
+        UnembedParams u;  // (lw.rank: written by the index prologue of stage 0)
         memset(&u, 0, sizeof(u));
         u.y = y_tokens; u.x = xr; u.sb = a->x_stride_b; u.sc = a->x_stride_c; u.st = a->x_stride_t;
-        u.mask = mask_in; u.rank = w.rank; u.B = B; u.T = c.num_frames; u.C = c.in_chans; u.H = c.img_h; u.W = c.img_w;
+        u.mask = mask_in; u.rank = lw.rank; u.B = B; u.T = c.num_frames; u.C = c.in_chans; u.H = c.img_h; u.W = c.img_w;
         u.P = c.patch; u.n_vis = Nv; u.Nm = Nm;
         u.out = a->y_video_dev + (size_t)b0 * c.num_frames * c.in_chans * c.img_h * c.img_w;
         if ((rc = E.run_unembed(u, s))) return rc;
@@ -266,7 +193,7 @@ extern "C" int cwm_forward(cwm_model* m, const cwm_forward_args* a_in) {
     CWM_REQUIRE(a->x_dev && a->mask_dev && a->y_tokens_dev, "cwm_forward: x_dev, mask_dev and y_tokens_dev are required");
     CWM_REQUIRE(a->mode == CWM_MODE_FAST || a->mode == CWM_MODE_PARITY, "cwm_forward: bad mode %d", a->mode);
     const cwm_config& c = m->cfg;
-    const int B = a->batch, Nt = m->Nt, Nv = a->n_vis, Nm = Nt - Nv;
+    const int B = a->batch, Nt = m->st.n_tok, Nv = a->n_vis, Nm = Nt - Nv;
     CWM_REQUIRE(B > 0, "cwm_forward: batch must be positive");
     CWM_REQUIRE(Nv > 0 && Nm >= 0, "cwm_forward: need 0 < n_vis (%d) <= num tokens (%d)", Nv, Nt);
     // nothing masked: the reference decoder then returns head(norm(x)) for ALL tokens (vmae.py:250-253), and its wrapper cannot
@@ -298,7 +225,7 @@ extern "C" int cwm_forward(cwm_model* m, const cwm_forward_args* a_in) {
 
     if (a->check) {
         std::vector<int> herr((size_t)B, 0);
-        CWM_HIP_CHECK(hipMemcpyAsync(herr.data(), m->err, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+        CWM_HIP_CHECK(hipMemcpyAsync(herr.data(), m->ws.err, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
         CWM_HIP_CHECK(hipStreamSynchronize(s));
         if (std::any_of(herr.begin(), herr.end(), [](int e) { return e != 0; })) {
             cwm_set_error("mask rows do not all have n_vis=%d visible tokens (shape '[%d, -1, %d]' is invalid for the gathered input)", Nv, B,

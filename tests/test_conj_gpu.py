@@ -296,3 +296,45 @@ def test_forward_args_struct_size_versions():
     assert torch.equal(yo, yr)
     a.struct_size = 0
     assert lib.cwm_forward(mp._handle, Ct.byref(a)) == _lib.ERR_INVALID
+
+
+@pytest.mark.parametrize("ctx_stream", [1, 0])
+def test_workspace_grows_then_is_sliced_at_its_capacity(ctx_stream):
+    """One handle through B = 1, then B = 3 on two lanes (2 + 1: the workspace grows) with ragged visible counts and ragged context masks, then B = 3 with
+    smaller n_vis_max and n_vis_ctx_max (no regrowth: the second lane's slices of both streams' and the cross blocks' buffers start at offsets taken at the
+    workspace's capacity, not at the call's counts).  Every call launches exactly what a fresh handle launches -- only the addresses differ --, so both
+    outputs are bitwise equal to a fresh handle's; and they are the CPU oracle's.  With the context side stream and without."""
+    seed = 17
+    W = conj_weights(TINY_CONJ, seed)
+    Nf = TINY_CONJ.main.tokens_per_frame
+
+    def handle():
+        m = build(TINY_CONJ, seed)
+        m.set_option("min_lane_rows", 1)
+        m.set_option("conj_ctx_stream", ctx_stream)
+        return m
+
+    def run(m, x, mask, imu, mc):
+        return m(V.preprocess(x).cuda(), mask.cuda(), x_context=imu.cuda(), mask_context=mc.cuda(), output_main=True, output_context=True)
+
+    # (visible main tokens per row -- within max_padding_tokens = 8 of each other --, visible context tokens per row)
+    steps = [([70], [4]), ([70, 66, 72], [4, 3, 4]), ([60, 63, 58], [3, 2, 3])]
+    m = handle()
+    for step, (vis, vis_c) in enumerate(steps):
+        B = len(vis)
+        gen = torch.Generator().manual_seed(seed + step)
+        x = torch.from_numpy(S.synthetic_frames(B, TINY_CONJ.main, seed + step))
+        imu = torch.randn(B, TINY_CONJ.ctx_in_chans, TINY_CONJ.ctx_seq_len, generator=gen)
+        mask = torch.ones(B, 2 * Nf, dtype=torch.bool)
+        mc = torch.ones(B, TINY_CONJ.ctx_tokens, dtype=torch.bool)
+        for b in range(B):
+            mask[b, torch.randperm(2 * Nf, generator=gen)[: vis[b]]] = False
+            mc[b, torch.randperm(TINY_CONJ.ctx_tokens, generator=gen)[: vis_c[b]]] = False
+        y, y_c = run(m, x, mask, imu, mc)
+        y_new, y_c_new = run(handle(), x, mask, imu, mc)
+        assert torch.equal(y, y_new) and torch.equal(y_c, y_c_new), (step, (y - y_new).abs().max().item(), (y_c - y_c_new).abs().max().item())
+        with torch.no_grad():
+            y_ref, y_c_ref = CO.conj_forward(W, TINY_SPEC, V.preprocess(x), mask, imu, mc, output_context=True)
+        err, err_c = (y.cpu() - y_ref).abs().max().item(), (y_c.cpu() - y_c_ref).abs().max().item()
+        print(f"[conj workspace step {step}, ctx_stream {ctx_stream}] vs oracle: main {err:.2e} context {err_c:.2e}")
+        assert y.shape == y_ref.shape and y_c.shape == y_c_ref.shape and err <= 3e-4 and err_c <= 3e-4, (step, err, err_c)

@@ -553,3 +553,48 @@ def test_mid_batches_run_two_lanes(B):
     y1 = m(x, mask, n_vis=792)
     m.set_lanes(2)
     assert (y2 - y1).abs().max().item() <= 5e-5
+
+
+def test_workspace_grows_then_is_sliced_at_its_capacity():
+    """One handle through a growing and then shrinking sequence of calls: B = 1; B = 5 on 3 lanes (2 + 2 + 1: the workspace grows); B = 5 on 2 lanes with
+    fewer visible tokens (no regrowth: the lanes' slices start at offsets taken at the workspace's capacity, which is larger than the call's count); B = 2 on
+    2 lanes through `predict_video` (the inverse permutation is sliced too).  Every call launches exactly what a fresh handle with the same weights, option
+    and lane count launches -- only the addresses differ --, so the outputs are bitwise equal; and they are the CPU oracle's.  A mask row with the wrong
+    visible count in the LAST lane of the 3-lane call still raises the reference's error."""
+    seed = 21
+    W = {k: torch.from_numpy(v) for k, v in S.synthetic_state_dict(TINY, seed).items()}
+
+    def handle(lanes):
+        m = build(TINY, seed)
+        m.set_option("min_lane_rows", 1)
+        m.sync_weights(torch.device("cuda:0"))
+        m.set_lanes(lanes)
+        return m
+
+    def run(m, x, mask, video):
+        if video:
+            return m.predict_video(x.cuda(), mask.cuda())
+        return m(O.preprocess(x).cuda(), mask.cuda()), None
+
+    m = handle(2)
+    for step, (B, lanes, k_vis, video) in enumerate([(1, 2, 6, False), (5, 3, 6, False), (5, 2, 2, False), (2, 2, 4, True)]):
+        x = torch.from_numpy(S.synthetic_frames(B, TINY, seed + step))
+        mask = torch.from_numpy(S.synthetic_masks(B, TINY, k_vis, seed + step))
+        assert int((~mask).sum(1).max()) == int((~mask).sum(1).min()) == TINY.tokens_per_frame + k_vis
+        m.set_lanes(lanes)
+        y, v = run(m, x, mask, video)
+        y_new, v_new = run(handle(lanes), x, mask, video)
+        assert torch.equal(y, y_new), (step, (y - y_new).abs().max().item())
+        with torch.no_grad():
+            v_ref, y_ref = O.predict(W, TINY_SPEC, x, mask, frame=None, return_tokens=True)
+        err = (y.cpu() - y_ref).abs().max().item()
+        print(f"[workspace step {step}] tokens vs oracle {err:.2e}")
+        assert y.shape == y_ref.shape and err <= 2e-4, (step, err)
+        if video:
+            assert torch.equal(v, v_new), step
+            assert (v.cpu() - v_ref).abs().max().item() <= 2e-4, step
+        if step == 1:
+            bad = mask.clone()
+            bad[B - 1, int(torch.nonzero(~bad[B - 1])[0])] = True    # row 4 = the third lane: one visible token fewer
+            with pytest.raises(RuntimeError, match="is invalid for"):
+                m(O.preprocess(x).cuda(), bad.cuda(), n_vis=TINY.tokens_per_frame + k_vis)
