@@ -52,48 +52,12 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnParams p) {
 
     // ---- Q fragments (B operand): lane (q = qcol, half hh) holds Q[q][16 s + 8 hh + 0..7] --------
     bf16x8 qf[PLANES][4];
-    {
-        const int qrow = p.q_off + min(q0 + qcol, NQ - 1);
-#pragma unroll
-        for (int pl = 0; pl < PLANES; ++pl)
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                qf[pl][s] = *reinterpret_cast<const bf16x8*>(Qb + (size_t)pl * p.qk_plane + (size_t)qrow * 64 + s * 16 + hh * 8);
-    }
+    load_q_fragments<PLANES>(qf, Qb, p.qk_plane, p.q_off + min(q0 + qcol, NQ - 1), hh);
 
-    // ---- staging bookkeeping: 512 16-byte chunks per tile (row = key, 8 chunks of 8 d), 2 per thread ----
-    int st_row[2], st_chunk[2], st_koff[2], st_voff[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int idx = tid + i * 256;
-        st_row[i] = idx >> 3;
-        st_chunk[i] = idx & 7;
-        st_koff[i] = lds_off128(st_row[i], st_chunk[i]);
-        st_voff[i] = lds_off_v(st_row[i], st_chunk[i]);
-    }
-    u32x4 rk[PLANES][2], rv[PLANES][2];
-    auto load_tiles = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            // keys past the sequence end re-read the last row: finite values, and P is exactly 0 there
-            const size_t off = (size_t)min(kt * 64 + st_row[i], N - 1) * 64 + st_chunk[i] * 8;
-#pragma unroll
-            for (int pl = 0; pl < PLANES; ++pl) {
-                rk[pl][i] = *reinterpret_cast<const u32x4*>(Kb + (size_t)pl * p.qk_plane + off);
-                rv[pl][i] = *reinterpret_cast<const u32x4*>(Vb + (size_t)pl * p.qk_plane + off);
-            }
-        }
-    };
-    auto store_tiles = [&](int stage) {
-        char* base = smem + stage * STAGE_BYTES;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int pl = 0; pl < PLANES; ++pl) {
-                *reinterpret_cast<u32x4*>(base + pl * TILE_BYTES + st_koff[i]) = rk[pl][i];
-                *reinterpret_cast<u32x4*>(base + (PLANES + pl) * TILE_BYTES + st_voff[i]) = rv[pl][i];
-            }
-    };
+    KvStage<PLANES, 1> st;  // register-staged K / V tile (attention_device.h)
+    st.init(tid);
+    auto load_tiles = [&](int kt) { st.load(0, Kb, Vb, p.qk_plane, kt, N); };
+    auto store_tiles = [&](int stage) { st.store(0, smem + stage * STAGE_BYTES); };
 
     // ---- fragment read offsets -------------------------------------------------------------------
     // K (A operand of S^T): row = key kb*32 + qcol, 16-byte chunk = 2 s + hh
@@ -102,17 +66,8 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnParams p) {
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int s = 0; s < 4; ++s) k_off[kb][s] = lds_off128(kb * 32 + qcol, 2 * s + hh);
-    // V^T (A operand of O^T) by transposed reads.  16-lane group g = lane >> 4 reads the block {keys 4 (g >> 1) + 0..3
-    // (+ 16 ks, + 8 for the second half of the fragment)} x {d = 32 db + 16 (g & 1) + 0..15}: lane 4 q + pc of the group
-    // supplies the address of key row q, d columns 4 pc .. 4 pc + 3, and lane i receives d column i (= 32 db + lane % 32)
-    // with key q in element q.  Key offsets 16 ks + 8 half are multiples of 4, so the swizzle bit is (q >> 1) & 1 and
-    // they are plain immediates; the two db blocks differ by the swizzled chunk bit -> one base register each.
-    int v_base[2];
-    {
-        const int g = lane >> 4, q = (lane >> 2) & 3, pc = lane & 3;
-#pragma unroll
-        for (int db = 0; db < 2; ++db) v_base[db] = lds_off_v(4 * (g >> 1) + q, db * 4 + (g & 1) * 2 + (pc >> 1)) + (pc & 1) * 8;
-    }
+    // V^T (A operand of O^T) by transposed reads (v_tr_offset, attention_device.h)
+    const int v_base[2] = {v_tr_offset(lane, 0), v_tr_offset(lane, 1)};
 
     f32x16 oacc[2];
 #pragma unroll
@@ -154,13 +109,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) sacc[kb][r] = 0.f;
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                if constexpr (PLANES == 2) {
-                    sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[kb][s][PLANES - 1], qf[0][s], sacc[kb], 0, 0, 0);
-                    sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[kb][s][0], qf[1][s], sacc[kb], 0, 0, 0);
-                }
-                sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[kb][s][0], qf[0][s], sacc[kb], 0, 0, 0);
-            }
+            for (int s = 0; s < 4; ++s) mfma_split<PLANES>(sacc[kb], kfr[kb][s][0], kfr[kb][s][PLANES - 1], qf[0][s], qf[PLANES - 1][s]);
         }
         __builtin_amdgcn_sched_barrier(0);
         bf16x4 vfr[4][2][PLANES][2];  // [k-step][d-block][plane][half]: transposed reads
@@ -180,12 +129,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnParams p) {
         if constexpr (LAST) {
             if (N & 63) {
 #pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int key = kt * 64 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                        if (key >= N) sacc[kb][r] = -INFINITY;
-                    }
+                for (int kb = 0; kb < 2; ++kb) mask_rows_from(sacc[kb], kt * 64 + kb * 32, hh, N);
             }
         }
         float mx = sacc[0][0];
@@ -222,23 +166,9 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnParams p) {
         for (int ks = 0; ks < 4; ++ks) {
             const int kb = ks >> 1, s = ks & 1;
             bf16x8 ph, plo;
+            p_fragments<PLANES>(sacc[kb], s, ph, plo);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float pv = sacc[kb][8 * s + j];
-                const bf16 hi = (bf16)pv;
-                ph[j] = hi;
-                if constexpr (PLANES == 2) plo[j] = (bf16)(pv - (float)hi);
-            }
-#pragma unroll
-            for (int db = 0; db < 2; ++db) {
-                const bf16x8 vf = __builtin_shufflevector(vfr[ks][db][0][0], vfr[ks][db][0][1], 0, 1, 2, 3, 4, 5, 6, 7);
-                if constexpr (PLANES == 2) {
-                    const bf16x8 vl = __builtin_shufflevector(vfr[ks][db][PLANES - 1][0], vfr[ks][db][PLANES - 1][1], 0, 1, 2, 3, 4, 5, 6, 7);
-                    oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph, oacc[db], 0, 0, 0);
-                    oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, plo, oacc[db], 0, 0, 0);
-                }
-                oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, ph, oacc[db], 0, 0, 0);
-            }
+            for (int db = 0; db < 2; ++db) mfma_split<PLANES>(oacc[db], join_halves(vfr[ks][db][0]), join_halves(vfr[ks][db][PLANES - 1]), ph, plo);
         }
         }  // active
 
@@ -257,22 +187,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnParams p) {
     if (q < NQ) {
         const int64_t orow = (int64_t)b * NQ + q;
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                bf16x4 hi4, lo4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float v = oacc[db][4 * g + e] * inv;
-                    const bf16 hi = (bf16)v;
-                    hi4[e] = hi;
-                    if constexpr (PLANES == 2) lo4[e] = (bf16)(v - (float)hi);
-                }
-                const int d0 = db * 32 + 8 * g + 4 * hh;
-                bf16* dst = p.o + a_pos<PLANES>(orow, p.ldo, h * 64 + d0);  // GEMM A-operand layout (common.h)
-                *reinterpret_cast<bf16x4*>(dst) = hi4;
-                if constexpr (PLANES == 2) *reinterpret_cast<bf16x4*>(dst + kLoOffset) = lo4;
-            }
+        for (int db = 0; db < 2; ++db) store_o_block<PLANES>(p.o, orow, p.ldo, h * 64 + db * 32, oacc[db], inv, hh);
     }
 }
 

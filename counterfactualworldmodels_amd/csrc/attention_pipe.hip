@@ -64,13 +64,10 @@ __device__ __forceinline__ void qk_plain(const PipeWave<PLANES>& w, const char* 
         for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
 #pragma unroll
         for (int sx = 0; sx < 4; ++sx) {
-            const bf16x8 kf = *reinterpret_cast<const bf16x8*>(kbase + w.k_off[kb][sx]);
-            if constexpr (PLANES == 2) {
-                const bf16x8 kl = *reinterpret_cast<const bf16x8*>(kbase + TILE_BYTES + w.k_off[kb][sx]);
-                s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kl, w.qf[0][sx], s[kb], 0, 0, 0);
-                s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, w.qf[1][sx], s[kb], 0, 0, 0);
-            }
-            s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, w.qf[0][sx], s[kb], 0, 0, 0);
+            bf16x8 kf[PLANES];
+#pragma unroll
+            for (int pl = 0; pl < PLANES; ++pl) kf[pl] = *reinterpret_cast<const bf16x8*>(kbase + pl * TILE_BYTES + w.k_off[kb][sx]);
+            mfma_split<PLANES>(s[kb], kf[0], kf[PLANES - 1], w.qf[0][sx], w.qf[PLANES - 1][sx]);
         }
     }
 }
@@ -156,14 +153,8 @@ __device__ __forceinline__ void pipe_tile(PipeWave<PLANES>& w, f32x16 (&sc)[2], 
 
     if constexpr (LASTK) {
         if (N & 63) {  // keys past the sequence end (last tile only)
-            const int hh4 = 4 * w.hh;
 #pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kt * 64 + kb * 32 + (r & 3) + 8 * (r >> 2) + hh4;
-                    if (key >= N) sc[kb][r] = -INFINITY;
-                }
+            for (int kb = 0; kb < 2; ++kb) mask_rows_from(sc[kb], kt * 64 + kb * 32, w.hh, N);
         }
     }
 
@@ -335,14 +326,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_pipe_kerne
 
     PipeWave<PLANES> w;
     w.hh = hh;
-    {
-        const int qrow = p.q_off + min(q0 + qcol, NQ - 1);
-#pragma unroll
-        for (int pl = 0; pl < PLANES; ++pl)
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                w.qf[pl][s] = *reinterpret_cast<const bf16x8*>(Qb + (size_t)pl * p.qk_plane + (size_t)qrow * 64 + s * 16 + hh * 8);
-    }
+    load_q_fragments<PLANES>(w.qf, Qb, p.qk_plane, p.q_off + min(q0 + qcol, NQ - 1), hh);
 
     // ---- LDS-DMA bookkeeping: piece = 8 key rows x 128 B; lane l lands at chunk l % 8 of row l / 8 ----
     int st_lds[NP], st_koff[NP], st_voff[NP];  // LDS offset of the piece; byte offset of the lane's 16-byte chunk inside a K / V tile
@@ -385,12 +369,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_pipe_kerne
 #pragma unroll
         for (int s = 0; s < 4; ++s) w.k_off[kb][s] = lds_off128(kb * 32 + qcol, 2 * s + hh);
     unsigned v_addr[2];  // LDS addresses of this lane's transposed-read blocks in V slot 0
-    {
-        const int g = lane >> 4, q = (lane >> 2) & 3, pc = lane & 3;
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
-            v_addr[db] = (unsigned)(size_t)(lds_void*)(smem + V_BASE + lds_off_v(4 * (g >> 1) + q, db * 4 + (g & 1) * 2 + (pc >> 1)) + (pc & 1) * 8);
-    }
+    for (int db = 0; db < 2; ++db) v_addr[db] = (unsigned)(size_t)(lds_void*)(smem + V_BASE + v_tr_offset(lane, db));
 
 #pragma unroll
     for (int db = 0; db < 2; ++db)
@@ -468,22 +448,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_pipe_kerne
         if (q < NQ) {
             const int64_t orow = (int64_t)b * NQ + q;
 #pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    bf16x4 hi4, lo4;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float v = w.oacc[db][4 * g + e] * inv;
-                        const bf16 hi = (bf16)v;
-                        hi4[e] = hi;
-                        if constexpr (PLANES == 2) lo4[e] = (bf16)(v - (float)hi);
-                    }
-                    const int d0 = db * 32 + 8 * g + 4 * hh;
-                    bf16* dst = p.o + a_pos<PLANES>(orow, p.ldo, h * 64 + d0);  // GEMM A-operand layout (common.h)
-                    *reinterpret_cast<bf16x4*>(dst) = hi4;
-                    if constexpr (PLANES == 2) *reinterpret_cast<bf16x4*>(dst + kLoOffset) = lo4;
-                }
+            for (int db = 0; db < 2; ++db) store_o_block<PLANES>(p.o, orow, p.ldo, h * 64 + db * 32, w.oacc[db], inv, hh);
         }
     };
 

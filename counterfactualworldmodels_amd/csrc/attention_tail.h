@@ -35,61 +35,22 @@ __device__ __forceinline__ void attention_tail_block(const AttnParams& p, char* 
     const bf16* Vb = p.v + (size_t)bh * N * 64;
 
     bf16x8 qf[PLANES][4];
-    {
-        const int qrow = p.q_off + min(q0 + qcol, NQ - 1);
-#pragma unroll
-        for (int pl = 0; pl < PLANES; ++pl)
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                qf[pl][s] = *reinterpret_cast<const bf16x8*>(Qb + (size_t)pl * p.qk_plane + (size_t)qrow * 64 + s * 16 + hh * 8);
-    }
-    // staging: 512 16-byte chunks per tile and plane (row = key, 8 chunks of 8 d), 2 per thread
-    int st_row[2], st_chunk[2], st_koff[2], st_voff[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int idx = tid + i * 256;
-        st_row[i] = idx >> 3;
-        st_chunk[i] = idx & 7;
-        st_koff[i] = lds_off128(st_row[i], st_chunk[i]);
-        st_voff[i] = lds_off_v(st_row[i], st_chunk[i]);
-    }
+    load_q_fragments<PLANES>(qf, Qb, p.qk_plane, p.q_off + min(q0 + qcol, NQ - 1), hh);
     const int nkt = (N + 63) / 64, npass = (nkt + 1) / 2;
-    u32x4 rk[2][PLANES][2], rv[2][PLANES][2];
+    KvStage<PLANES, 2> st;  // a pass stages two key tiles, tile t of the pass into LDS stage t
+    st.init(tid);
     auto load_pair = [&](int pass) {
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int kt = min(2 * pass + t, nkt - 1);  // (an odd tile count: the second slot of the last pass is never read)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const size_t off = (size_t)min(kt * 64 + st_row[i], N - 1) * 64 + st_chunk[i] * 8;  // rows past the end: finite values, P = 0 there
-#pragma unroll
-                for (int pl = 0; pl < PLANES; ++pl) {
-                    rk[t][pl][i] = *reinterpret_cast<const u32x4*>(Kb + (size_t)pl * p.qk_plane + off);
-                    rv[t][pl][i] = *reinterpret_cast<const u32x4*>(Vb + (size_t)pl * p.qk_plane + off);
-                }
-            }
-        }
+        for (int t = 0; t < 2; ++t) st.load(t, Kb, Vb, p.qk_plane, min(2 * pass + t, nkt - 1), N);  // (an odd tile count: the second slot of the last pass is never read)
     };
     auto store_pair = [&]() {
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int pl = 0; pl < PLANES; ++pl) {
-                    *reinterpret_cast<u32x4*>(smem + t * STAGE_BYTES + pl * TILE_BYTES + st_koff[i]) = rk[t][pl][i];
-                    *reinterpret_cast<u32x4*>(smem + t * STAGE_BYTES + (PLANES + pl) * TILE_BYTES + st_voff[i]) = rv[t][pl][i];
-                }
+        for (int t = 0; t < 2; ++t) st.store(t, smem + t * STAGE_BYTES);
     };
     int k_off[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) k_off[s] = lds_off128(kb * 32 + qcol, 2 * s + hh);
-    int v_base[2];
-    {
-        const int g = lane >> 4, q = (lane >> 2) & 3, pc = lane & 3;
-#pragma unroll
-        for (int db = 0; db < 2; ++db) v_base[db] = lds_off_v(4 * (g >> 1) + q, db * 4 + (g & 1) * 2 + (pc >> 1)) + (pc & 1) * 8;
-    }
+    const int v_base[2] = {v_tr_offset(lane, 0), v_tr_offset(lane, 1)};
 
     f32x16 oacc[2];
 #pragma unroll
@@ -110,13 +71,10 @@ __device__ __forceinline__ void attention_tail_block(const AttnParams& p, char* 
             for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(base + k_off[s]);
-                if constexpr (PLANES == 2) {
-                    const bf16x8 kl = *reinterpret_cast<const bf16x8*>(base + TILE_BYTES + k_off[s]);
-                    sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kl, qf[0][s], sacc, 0, 0, 0);
-                    sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[PLANES - 1][s], sacc, 0, 0, 0);
-                }
-                sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[0][s], sacc, 0, 0, 0);
+                bf16x8 kf[PLANES];
+#pragma unroll
+                for (int pl = 0; pl < PLANES; ++pl) kf[pl] = *reinterpret_cast<const bf16x8*>(base + pl * TILE_BYTES + k_off[s]);
+                mfma_split<PLANES>(sacc, kf[0], kf[PLANES - 1], qf[0][s], qf[PLANES - 1][s]);
             }
             bf16x4 vfr[2][2][PLANES][2];  // [k-step][d-block][plane][half]
 #pragma unroll
@@ -129,11 +87,7 @@ __device__ __forceinline__ void attention_tail_block(const AttnParams& p, char* 
                         vfr[ks][db][pl][0] = lds_read_tr16(vb);
                         vfr[ks][db][pl][1] = lds_read_tr16(vb + 1024);
                     }
-            if (kt == nkt - 1 && (N & 63)) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (kt * 64 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh >= N) sacc[r] = -INFINITY;
-            }
+            if (kt == nkt - 1 && (N & 63)) mask_rows_from(sacc, kt * 64 + kb * 32, hh, N);
             float mx = sacc[0];
 #pragma unroll
             for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sacc[r]);
@@ -157,23 +111,9 @@ __device__ __forceinline__ void attention_tail_block(const AttnParams& p, char* 
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 bf16x8 ph, plo;
+                p_fragments<PLANES>(sacc, ks, ph, plo);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float pv = sacc[8 * ks + j];
-                    const bf16 hi = (bf16)pv;
-                    ph[j] = hi;
-                    if constexpr (PLANES == 2) plo[j] = (bf16)(pv - (float)hi);
-                }
-#pragma unroll
-                for (int db = 0; db < 2; ++db) {
-                    const bf16x8 vf = __builtin_shufflevector(vfr[ks][db][0][0], vfr[ks][db][0][1], 0, 1, 2, 3, 4, 5, 6, 7);
-                    if constexpr (PLANES == 2) {
-                        const bf16x8 vl = __builtin_shufflevector(vfr[ks][db][PLANES - 1][0], vfr[ks][db][PLANES - 1][1], 0, 1, 2, 3, 4, 5, 6, 7);
-                        oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph, oacc[db], 0, 0, 0);
-                        oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, plo, oacc[db], 0, 0, 0);
-                    }
-                    oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, ph, oacc[db], 0, 0, 0);
-                }
+                for (int db = 0; db < 2; ++db) mfma_split<PLANES>(oacc[db], join_halves(vfr[ks][db][0]), join_halves(vfr[ks][db][PLANES - 1]), ph, plo);
             }
         }
         // (the next pair is requested only now: held in registers across the MFMA section it would cost the regular path of the
@@ -225,22 +165,7 @@ __device__ __forceinline__ void attention_tail_block(const AttnParams& p, char* 
     if (q < NQ) {
         const int64_t orow = (int64_t)b * NQ + q;
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                bf16x4 hi4, lo4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float v = oacc[db][4 * g + e] * inv;
-                    const bf16 hi = (bf16)v;
-                    hi4[e] = hi;
-                    if constexpr (PLANES == 2) lo4[e] = (bf16)(v - (float)hi);
-                }
-                const int d0 = db * 32 + 8 * g + 4 * hh;
-                bf16* dst = p.o + a_pos<PLANES>(orow, p.ldo, h * 64 + d0);
-                *reinterpret_cast<bf16x4*>(dst) = hi4;
-                if constexpr (PLANES == 2) *reinterpret_cast<bf16x4*>(dst + kLoOffset) = lo4;
-            }
+        for (int db = 0; db < 2; ++db) store_o_block<PLANES>(p.o, orow, p.ldo, h * 64 + db * 32, oacc[db], inv, hh);
     }
 }
 

@@ -40,22 +40,6 @@ __device__ __forceinline__ int ctx_pos(int m) {
     return (m & ~31) + (w & 16) + 8 * ((r >> 2) & 1) + ((r >> 3) << 2) + (r & 3);
 }
 
-template <int PLANES>
-__device__ __forceinline__ void p_fragments(const f32x16& s, int ks, bf16x8& ph, bf16x8& plo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float pv = s[8 * ks + j];
-        const bf16 hi = (bf16)pv;
-        ph[j] = hi;
-        if constexpr (PLANES == 2) plo[j] = (bf16)(pv - (float)hi);
-    }
-}
-
-__device__ __forceinline__ float sum_lane_xor32(float x) {
-    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-}
-
 }  // namespace
 
 // partial[((bh * kCrossSplit2 + split) * M + m) * (hd + 4) + {d | hd: local max (log2 domain, scaled) | hd + 1: local sum}]
@@ -143,12 +127,9 @@ __global__ __launch_bounds__(ROLE == 0 ? 512 : 256, 2) void cross_attn_mfma_kern
                     for (int mt = 0; mt < MT; ++mt) {
                         const char* ka = kl + (mt * 32 + qcol) * KROW + ((g * KG + i) * 16 + hh * 8) * 2;
                         const bf16x8 kh = *reinterpret_cast<const bf16x8*>(ka);
-                        if constexpr (PLANES == 2) {
-                            const bf16x8 klo = *reinterpret_cast<const bf16x8*>(ka + KPLANE);
-                            sacc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(klo, qf[g & 1][i][0], sacc[mt], 0, 0, 0);
-                            sacc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, qf[g & 1][i][PLANES - 1], sacc[mt], 0, 0, 0);
-                        }
-                        sacc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, qf[g & 1][i][0], sacc[mt], 0, 0, 0);
+                        bf16x8 klo;
+                        if constexpr (PLANES == 2) klo = *reinterpret_cast<const bf16x8*>(ka + KPLANE);
+                        mfma_split<PLANES>(sacc[mt], kh, klo, qf[g & 1][i][0], qf[g & 1][i][PLANES - 1]);
                     }
             }
             // softmax over the context (rows of S^T): 16 rows per block in this lane, the other 16 in lane ^ 32
@@ -157,8 +138,7 @@ __global__ __launch_bounds__(ROLE == 0 ? 512 : 256, 2) void cross_attn_mfma_kern
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int ctx = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                    if (ctx >= M) sacc[mt][r] = -INFINITY;
+                    if (mt * 32 + acc_row(r, hh) >= M) sacc[mt][r] = -INFINITY;
                     mx = fmaxf(mx, sacc[mt][r]);
                 }
             mx = max_lane_xor32(mx);
@@ -195,17 +175,16 @@ __global__ __launch_bounds__(ROLE == 0 ? 512 : 256, 2) void cross_attn_mfma_kern
                         if (db0 + i >= NDB) continue;
                         const char* va = vl + ((db0 + i) * 32 + qcol) * VROW + (ks * 16 + hh * 8) * 2;
                         const bf16x8 vf = *reinterpret_cast<const bf16x8*>(va);
-                        if constexpr (PLANES == 2) {
-                            const bf16x8 vlo = *reinterpret_cast<const bf16x8*>(va + VPLANE);
-                            oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vlo, ph[ks], oacc[i], 0, 0, 0);
-                            oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, plo[ks], oacc[i], 0, 0, 0);
-                        }
-                        oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, ph[ks], oacc[i], 0, 0, 0);
+                        bf16x8 vlo;
+                        if constexpr (PLANES == 2) vlo = *reinterpret_cast<const bf16x8*>(va + VPLANE);
+                        mfma_split<PLANES>(oacc[i], vf, vlo, ph[ks], plo[ks]);
                     }
                 if (tok < N) {
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
                         if (db0 + i >= NDB) continue;
+                        // (store_o_block spelled out: through the helper hipcc allocates the fast-mode instantiations differently -- 98 -> 72 VGPRs
+                        // at head_dim 192 -- and the helpers were introduced with every kernel's registers unchanged)
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
                             bf16x4 hi4, lo4;
@@ -228,12 +207,7 @@ __global__ __launch_bounds__(ROLE == 0 ? 512 : 256, 2) void cross_attn_mfma_kern
     } else {
     // =================================== role B: context update ===================================
     char* vimg = vl + wave * (PLANES * VT);
-    int v_base[2];
-    {
-        const int g = lane >> 4, q = (lane >> 2) & 3, pc = lane & 3;  // see attention.hip: the transposed read of a [key][64 d] image
-#pragma unroll
-        for (int db = 0; db < 2; ++db) v_base[db] = lds_off_v(4 * (g >> 1) + q, db * 4 + (g & 1) * 2 + (pc >> 1)) + (pc & 1) * 8;
-    }
+    const int v_base[2] = {v_tr_offset(lane, 0), v_tr_offset(lane, 1)};  // the transposed read of a [key][64 d] image
     f32x16 oacc[MT][NDB];
     float m_run[MT], l_run[MT];
 #pragma unroll
@@ -264,12 +238,9 @@ __global__ __launch_bounds__(ROLE == 0 ? 512 : 256, 2) void cross_attn_mfma_kern
                 for (int mt = 0; mt < MT; ++mt) {
                     const char* ka = kl + (mt * 32 + qcol) * KROW + ((g * KGB + i) * 16 + hh * 8) * 2;
                     const bf16x8 kh = *reinterpret_cast<const bf16x8*>(ka);
-                    if constexpr (PLANES == 2) {
-                        const bf16x8 klo = *reinterpret_cast<const bf16x8*>(ka + KPLANE);
-                        sacc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf[g & 1][i][PLANES - 1], kh, sacc[mt], 0, 0, 0);
-                        sacc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf[g & 1][i][0], klo, sacc[mt], 0, 0, 0);
-                    }
-                    sacc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf[g & 1][i][0], kh, sacc[mt], 0, 0, 0);
+                    bf16x8 klo;
+                    if constexpr (PLANES == 2) klo = *reinterpret_cast<const bf16x8*>(ka + KPLANE);
+                    mfma_split<PLANES>(sacc[mt], qf[g & 1][i][0], qf[g & 1][i][PLANES - 1], kh, klo);
                 }
         }
         // online softmax over the tokens (rows of S^T) per context column
@@ -279,7 +250,7 @@ __global__ __launch_bounds__(ROLE == 0 ? 512 : 256, 2) void cross_attn_mfma_kern
             float mx = -INFINITY;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                if (ragged && tok0 + (r & 3) + 8 * (r >> 2) + 4 * hh >= N) sacc[mt][r] = -INFINITY;
+                if (ragged && tok0 + acc_row(r, hh) >= N) sacc[mt][r] = -INFINITY;
                 mx = fmaxf(mx, sacc[mt][r]);
             }
             mx = max_lane_xor32(mx);
@@ -334,24 +305,16 @@ __global__ __launch_bounds__(ROLE == 0 ? 512 : 256, 2) void cross_attn_mfma_kern
                 if (2 * t + db2 >= NDB) continue;
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    bf16x4 v0[PLANES], v1[PLANES];
+                    bf16x4 vfr[PLANES][2];
 #pragma unroll
                     for (int pl = 0; pl < PLANES; ++pl) {
                         const char* vb = vimg + pl * VT + v_base[db2] + ks * 2048;
-                        v0[pl] = lds_read_tr16(vb);
-                        v1[pl] = lds_read_tr16(vb + 1024);
+                        vfr[pl][0] = lds_read_tr16(vb);
+                        vfr[pl][1] = lds_read_tr16(vb + 1024);
                     }
-                    const bf16x8 vf = __builtin_shufflevector(v0[0], v1[0], 0, 1, 2, 3, 4, 5, 6, 7);
+                    const bf16x8 vf = join_halves(vfr[0]), vlo = join_halves(vfr[PLANES - 1]);
 #pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        f32x16& o = oacc[mt][2 * t + db2];
-                        if constexpr (PLANES == 2) {
-                            const bf16x8 vlo = __builtin_shufflevector(v0[PLANES - 1], v1[PLANES - 1], 0, 1, 2, 3, 4, 5, 6, 7);
-                            o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vlo, ph[mt][ks], o, 0, 0, 0);
-                            o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, plo[mt][ks], o, 0, 0, 0);
-                        }
-                        o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, ph[mt][ks], o, 0, 0, 0);
-                    }
+                    for (int mt = 0; mt < MT; ++mt) mfma_split<PLANES>(oacc[mt][2 * t + db2], vf, vlo, ph[mt][ks], plo[mt][ks]);
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -446,16 +409,10 @@ __global__ __launch_bounds__(64) void small_attn_mfma_kernel(const SmallAttnPara
 #pragma unroll
             for (int r = 0; r < 16; ++r) sacc[kt][r] = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                if constexpr (PLANES == 2) {
-                    sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(klo[kt][ks], qh[qt][ks], sacc[kt], 0, 0, 0);
-                    sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh[kt][ks], ql[qt][ks], sacc[kt], 0, 0, 0);
-                }
-                sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh[kt][ks], qh[qt][ks], sacc[kt], 0, 0, 0);
-            }
+            for (int ks = 0; ks < 2; ++ks) mfma_split<PLANES>(sacc[kt], kh[kt][ks], klo[kt][ks], qh[qt][ks], ql[qt][ks]);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                if (kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh >= N) sacc[kt][r] = -INFINITY;
+                if (kt * 32 + acc_row(r, hh) >= N) sacc[kt][r] = -INFINITY;
                 mx = fmaxf(mx, sacc[kt][r]);
             }
         }
@@ -481,20 +438,16 @@ __global__ __launch_bounds__(64) void small_attn_mfma_kernel(const SmallAttnPara
                 p_fragments<PLANES>(sacc[kt], ks, ph, plo);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {  // V^T fragment: lane (d = qcol, half hh), element j = key 16 ks + 8 (j >> 2) + 4 hh + (j & 3)
-                    const int key = kt * 32 + 16 * ks + 8 * (j >> 2) + 4 * hh + (j & 3);
+                    const int key = kt * 32 + 16 * ks + acc_row(j, hh);
                     const float v = base[(size_t)min(key, N - 1) * 3 * D + 2 * D + qcol];
                     const bf16 x = (bf16)v;
                     vh[j] = x;
                     if constexpr (PLANES == 2) vlo[j] = (bf16)(v - (float)x);
                 }
-                if constexpr (PLANES == 2) {
-                    oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vlo, ph, oacc, 0, 0, 0);
-                    oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, plo, oacc, 0, 0, 0);
-                }
-                oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, ph, oacc, 0, 0, 0);
+                mfma_split<PLANES>(oacc, vh, vlo, ph, plo);
             }
         const int q = qt * 32 + qcol;
-        if (q < N) {
+        if (q < N) {  // (store_o_block spelled out, as in role A above: the two-block instantiations move from 150 / 141 to 174 / 153 VGPRs through the helper)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 bf16x4 hi4, lo4;
