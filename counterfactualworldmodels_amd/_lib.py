@@ -238,6 +238,53 @@ class CwmDevRaftConvArgs(C.Structure):
     ]
 
 
+DEV_GATHER_PATCH, DEV_GATHER_INDEX, DEV_GATHER_FLOW_RGB, DEV_GATHER_IMU, DEV_GATHER_INDEX_UNFUSED = range(5)
+
+
+class CwmDevGatherArgs(C.Structure):
+    """include/cwm_hip_dev.h cwm_dev_gather_args (development library only)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("kind", C.c_int32),
+        ("mode", C.c_int32),
+        ("normalize", C.c_int32),
+        ("x", C.c_void_p),
+        ("sb", C.c_int64),
+        ("sc", C.c_int64),
+        ("st", C.c_int64),
+        ("fwd", C.c_void_p),
+        ("bwd", C.c_void_p),
+        ("f_sb", C.c_int64),
+        ("f_sc", C.c_int64),
+        ("b_sb", C.c_int64),
+        ("b_sc", C.c_int64),
+        ("B", C.c_int32),
+        ("C", C.c_int32),
+        ("H", C.c_int32),
+        ("W", C.c_int32),
+        ("P", C.c_int32),
+        ("L", C.c_int32),
+        ("tubelet", C.c_int32),
+        ("Nt", C.c_int32),
+        ("n_rows", C.c_int32),
+        ("perm_stride", C.c_int32),
+        ("n_vis", C.c_int32),
+        ("mask", C.c_void_p),
+        ("perm", C.c_void_p),
+        ("rank", C.c_void_p),
+        ("err_rows", C.c_void_p),
+        ("out", C.c_void_p),
+        ("ld", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
+def new_dev_gather_args() -> CwmDevGatherArgs:
+    a = CwmDevGatherArgs()
+    a.struct_size = C.sizeof(CwmDevGatherArgs)
+    return a
+
+
 def new_dev_raft_conv_args() -> CwmDevRaftConvArgs:
     a = CwmDevRaftConvArgs()
     a.struct_size = C.sizeof(CwmDevRaftConvArgs)
@@ -351,6 +398,7 @@ DEV_SIGNATURES = {
     "cwm_dev_raft_motion_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "cwm_dev_raft_gru_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "cwm_dev_raft_flow_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+    "cwm_dev_gather": (C.c_int, [C.POINTER(CwmDevGatherArgs)]),
 }
 
 # the keys cwm_model_set_option / cwm_conj_set_option know (include/cwm_hip.h; csrc/engine.hip tuning_field)

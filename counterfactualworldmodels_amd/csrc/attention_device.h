@@ -121,12 +121,7 @@ __device__ __forceinline__ void mfma_split(f32x16& acc, const bf16x8& a_hi, cons
 template <int PLANES>
 __device__ __forceinline__ void p_fragments(const f32x16& s, int ks, bf16x8& ph, bf16x8& plo) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float pv = s[8 * ks + j];
-        const bf16 hi = (bf16)pv;
-        ph[j] = hi;
-        if constexpr (PLANES == 2) plo[j] = (bf16)(pv - (float)hi);
-    }
+    for (int j = 0; j < 8; ++j) split_bf16_at<PLANES>(s[8 * ks + j], ph, plo, j);
 }
 
 // row (of 32) that accumulator element r holds in lane half hh
@@ -145,15 +140,8 @@ __device__ __forceinline__ void store_o_block(bf16* o, int64_t row, int ld, int 
     for (int g = 0; g < 4; ++g) {
         bf16x4 hi4, lo4;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float v = acc[4 * g + e] * mul;
-            const bf16 hi = (bf16)v;
-            hi4[e] = hi;
-            if constexpr (PLANES == 2) lo4[e] = (bf16)(v - (float)hi);
-        }
-        bf16* dst = o + a_pos<PLANES>(row, ld, col0 + 8 * g + 4 * hh);
-        *reinterpret_cast<bf16x4*>(dst) = hi4;
-        if constexpr (PLANES == 2) *reinterpret_cast<bf16x4*>(dst + kLoOffset) = lo4;
+        for (int e = 0; e < 4; ++e) split_bf16_at<PLANES>(acc[4 * g + e] * mul, hi4, lo4, e);
+        store_operand_split<PLANES>(o, row, ld, col0 + 8 * g + 4 * hh, hi4, lo4);
     }
 }
 

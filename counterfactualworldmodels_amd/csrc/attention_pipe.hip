@@ -77,10 +77,7 @@ template <int PLANES>
 __device__ __forceinline__ void split_pair(const f32x16 (&sc)[2], int ks, int j, bf16x8& ph, bf16x8& plo) {
 #pragma unroll
     for (int e = 2 * j; e < 2 * j + 2; ++e) {
-        const float pv = sc[ks >> 1][8 * (ks & 1) + e];
-        const bf16 hi = (bf16)pv;
-        ph[e] = hi;
-        if constexpr (PLANES == 2) plo[e] = (bf16)(pv - (float)hi);
+        split_bf16_at<PLANES>(sc[ks >> 1][8 * (ks & 1) + e], ph, plo, e);
     }
 }
 
@@ -555,10 +552,7 @@ __global__ __launch_bounds__(256) void attention_combine_kernel(const AttnParams
     }
     const float v = o / l;
     const int b = bh / p.heads, h = bh - b * p.heads;
-    bf16* dst = p.o + a_pos<PLANES>((int64_t)b * NQ + q, p.ldo, h * 64 + d);
-    const bf16 hi = (bf16)v;
-    *dst = hi;
-    if constexpr (PLANES == 2) dst[kLoOffset] = (bf16)(v - (float)hi);
+    store_operand<PLANES>(p.o, (int64_t)b * NQ + q, p.ldo, h * 64 + d, v);
 }
 
 // scratch of the key-split tail round: at most one round of partial workgroups (512 x 128 queries x 68 floats = 17.8 MB), one buffer per

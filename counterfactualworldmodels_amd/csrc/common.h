@@ -34,6 +34,64 @@ __device__ __forceinline__ size_t a_pos(int64_t row, int ld, int col) {
 }
 constexpr int kLoOffset = 32;
 
+// ---- operand WRITERS: the one place that knows where the lo plane lies.  Producers write through these, readers through a_pos. ----
+
+// Register-only split, element j of a hi / lo vector pair.  PLANES == 1 neither computes nor names `lo`: the one-plane kernels keep
+// their register counts (the same point as mfma_split, attention_device.h).
+template <int PLANES, class V>
+__device__ __forceinline__ void split_bf16_at(float v, V& hi, V& lo, int j) {
+    const bf16 h = (bf16)v;
+    hi[j] = h;
+    if constexpr (PLANES == 2) lo[j] = (bf16)(v - (float)h);
+}
+// ... of 4 values, and of 8 (two f32x4: elements 0-3, 4-7)
+template <int PLANES>
+__device__ __forceinline__ void split_bf16v(const f32x4& v, bf16x4& hi, bf16x4& lo) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) split_bf16_at<PLANES>(v[e], hi, lo, e);
+}
+template <int PLANES>
+__device__ __forceinline__ void split_bf16v(const f32x4& v0, const f32x4& v1, bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) split_bf16_at<PLANES>(v0[e], hi, lo, e);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) split_bf16_at<PLANES>(v1[e], hi, lo, 4 + e);
+}
+
+// An already split group (V = bf16, bf16x4, bf16x8) to columns k .. of `row`: one store per plane.  k is a multiple of the group's
+// width, so the group never straddles a 32-k [hi | lo] block.
+template <int PLANES, class V>
+__device__ __forceinline__ void store_operand_split(bf16* A, int64_t row, int ld, int k, const V& hi, const V& lo) {
+    bf16* d = A + a_pos<PLANES>(row, ld, k);
+    *reinterpret_cast<V*>(d) = hi;
+    if constexpr (PLANES == 2) *reinterpret_cast<V*>(d + kLoOffset) = lo;
+}
+
+template <int PLANES>
+__device__ __forceinline__ void store_operand(bf16* A, int64_t row, int ld, int k, float v) {
+    const bf16 h = (bf16)v;
+    bf16 l;
+    if constexpr (PLANES == 2) l = (bf16)(v - (float)h);
+    store_operand_split<PLANES>(A, row, ld, k, h, l);
+}
+template <int PLANES>
+__device__ __forceinline__ void store_operand4(bf16* A, int64_t row, int ld, int k, const f32x4& v) {
+    bf16x4 hi, lo;
+    split_bf16v<PLANES>(v, hi, lo);
+    store_operand_split<PLANES>(A, row, ld, k, hi, lo);
+}
+template <int PLANES>
+__device__ __forceinline__ void store_operand8(bf16* A, int64_t row, int ld, int k, const f32x4& v0, const f32x4& v1) {
+    bf16x8 hi, lo;
+    split_bf16v<PLANES>(v0, v1, hi, lo);
+    store_operand_split<PLANES>(A, row, ld, k, hi, lo);
+}
+// zeros in columns k_from .. ld - 1 of `row` (the K padding of a producer whose K is not a multiple of the GEMM's k tile)
+template <int PLANES>
+__device__ __forceinline__ void zero_operand_tail(bf16* A, int64_t row, int ld, int k_from) {
+    for (int k = k_from; k < ld; ++k) store_operand_split<PLANES>(A, row, ld, k, (bf16)0.f, (bf16)0.f);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

@@ -183,21 +183,13 @@ __global__ __launch_bounds__(ROLE == 0 ? 512 : 256, 2) void cross_attn_mfma_kern
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
                         if (db0 + i >= NDB) continue;
-                        // (store_o_block spelled out: through the helper hipcc allocates the fast-mode instantiations differently -- 98 -> 72 VGPRs
-                        // at head_dim 192 -- and the helpers were introduced with every kernel's registers unchanged)
+                        // (the loop of attention_device.h store_o_block written here, on common.h store_operand4: through store_o_block hipcc allocates
+                        // the fast-mode instantiations differently -- 98 -> 72 VGPRs at head_dim 192; through store_operand4 every instantiation keeps
+                        // its registers; DESIGN.md sections 4.2, 4.13)
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
-                            bf16x4 hi4, lo4;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const float v = oacc[i][4 * g + e];
-                                const bf16 hi = (bf16)v;
-                                hi4[e] = hi;
-                                if constexpr (PLANES == 2) lo4[e] = (bf16)(v - (float)hi);
-                            }
-                            bf16* dst = p.y + a_pos<PLANES>(row, D, h * HD + (db0 + i) * 32 + 8 * g + 4 * hh);  // GEMM A-operand layout (the projection reads it)
-                            *reinterpret_cast<bf16x4*>(dst) = hi4;
-                            if constexpr (PLANES == 2) *reinterpret_cast<bf16x4*>(dst + kLoOffset) = lo4;
+                            const f32x4 v = f32x4{oacc[i][4 * g], oacc[i][4 * g + 1], oacc[i][4 * g + 2], oacc[i][4 * g + 3]};
+                            store_operand4<PLANES>(p.y, row, D, h * HD + (db0 + i) * 32 + 8 * g + 4 * hh, v);  // (the projection reads it)
                         }
                     }
                 }
@@ -359,11 +351,7 @@ __global__ __launch_bounds__(256) void cross_attn_combine_kernel(const CrossAttn
         l = fmaf(part[s * sstride + hd + 1], w, l);
         acc = fmaf(part[s * sstride + t], w, acc);
     }
-    bf16 hi, lo;
-    split_bf16(acc / l, hi, lo);
-    bf16* dst = p.y_src + a_pos<PLANES>((int64_t)b * M + m, D, h * hd + t);
-    *dst = hi;
-    if constexpr (PLANES == 2) dst[kLoOffset] = lo;
+    store_operand<PLANES>(p.y_src, (int64_t)b * M + m, D, h * hd + t, acc / l);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -439,28 +427,18 @@ __global__ __launch_bounds__(64) void small_attn_mfma_kernel(const SmallAttnPara
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {  // V^T fragment: lane (d = qcol, half hh), element j = key 16 ks + 8 (j >> 2) + 4 hh + (j & 3)
                     const int key = kt * 32 + 16 * ks + acc_row(j, hh);
-                    const float v = base[(size_t)min(key, N - 1) * 3 * D + 2 * D + qcol];
-                    const bf16 x = (bf16)v;
-                    vh[j] = x;
-                    if constexpr (PLANES == 2) vlo[j] = (bf16)(v - (float)x);
+                    split_bf16_at<PLANES>(base[(size_t)min(key, N - 1) * 3 * D + 2 * D + qcol], vh, vlo, j);
                 }
                 mfma_split<PLANES>(oacc, vh, vlo, ph, plo);
             }
         const int q = qt * 32 + qcol;
-        if (q < N) {  // (store_o_block spelled out, as in role A above: the two-block instantiations move from 150 / 141 to 174 / 153 VGPRs through the helper)
+        if (q < N) {  // (store_o_block's loop written here, as in role A above: through store_o_block the two-block instantiations move from 150 / 141 to 174 / 153 VGPRs)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                bf16x4 hi4, lo4;
+                bf16x4 hi4, lo4;  // (split per element: through store_operand4 the <1, 2> instantiation takes two more VGPRs)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float v = oacc[4 * g + e] * inv;
-                    const bf16 x = (bf16)v;
-                    hi4[e] = x;
-                    if constexpr (PLANES == 2) lo4[e] = (bf16)(v - (float)x);
-                }
-                bf16* dst = p.o + a_pos<PLANES>((int64_t)b * N + q, p.ldo, h * HD + 8 * g + 4 * hh);
-                *reinterpret_cast<bf16x4*>(dst) = hi4;
-                if constexpr (PLANES == 2) *reinterpret_cast<bf16x4*>(dst + kLoOffset) = lo4;
+                for (int e = 0; e < 4; ++e) split_bf16_at<PLANES>(oacc[4 * g + e] * inv, hi4, lo4, e);
+                store_operand_split<PLANES>(p.o, (int64_t)b * N + q, p.ldo, h * HD + 8 * g + 4 * hh, hi4, lo4);
             }
         }
     }

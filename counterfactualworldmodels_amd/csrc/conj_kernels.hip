@@ -88,11 +88,7 @@ __global__ void imu_gather_kernel(const ImuGatherParams p) {
         const int c = k / p.tubelet, s = k - c * p.tubelet;
         v = p.imu[((size_t)b * p.C + c) * p.L + tau * p.tubelet + s];
     }
-    bf16 hi, lo;
-    split_bf16(v, hi, lo);
-    bf16* dst = p.out + a_pos<PLANES>(row, p.ld, k);
-    *dst = hi;
-    if constexpr (PLANES == 2) dst[kLoOffset] = lo;
+    store_operand<PLANES>(p.out, row, p.ld, k, v);
 }
 
 int launch_imu_gather(const ImuGatherParams& p, int planes, hipStream_t stream) {
@@ -175,13 +171,7 @@ __global__ __launch_bounds__(64) void small_attention_kernel(const SmallAttnPara
     const float inv = 1.0f / l;
 #pragma unroll
     for (int d = 0; d < MAXD; ++d)
-        if (d < hd) {
-            bf16 hi, lo;
-            split_bf16(o[d] * inv, hi, lo);
-            bf16* dst = p.o + a_pos<PLANES>((int64_t)b * N + t, p.ldo, h * hd + d);
-            *dst = hi;
-            if constexpr (PLANES == 2) dst[kLoOffset] = lo;
-        }
+        if (d < hd) store_operand<PLANES>(p.o, (int64_t)b * N + t, p.ldo, h * hd + d, o[d] * inv);
 }
 
 int launch_small_attention(const SmallAttnParams& p, int planes, hipStream_t stream) {
@@ -281,18 +271,12 @@ __global__ __launch_bounds__(256) void cross_attn_main_kernel(const CrossAttnPar
             }
         }
         if (nv) {
-            bf16* dst = p.y + a_pos<PLANES>((int64_t)b * N + n, D, h * hd + g * 32);  // one whole 32-column operand block
 #pragma unroll
-            for (int c = 0; c < 32; c += 8) {
+            for (int c = 0; c < 32; c += 8) {  // one whole 32-column operand block
                 bf16x8 hv, lv;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const bf16 hi = (bf16)acc[c + e];
-                    hv[e] = hi;
-                    lv[e] = (bf16)(acc[c + e] - (float)hi);
-                }
-                *reinterpret_cast<bf16x8*>(dst + c) = hv;
-                if constexpr (PLANES == 2) *reinterpret_cast<bf16x8*>(dst + kLoOffset + c) = lv;
+                for (int e = 0; e < 8; ++e) split_bf16_at<PLANES>(acc[c + e], hv, lv, e);
+                store_operand_split<PLANES>(p.y, (int64_t)b * N + n, D, h * hd + g * 32 + c, hv, lv);
             }
         }
     }
@@ -387,11 +371,7 @@ __global__ __launch_bounds__(256) void cross_attn_src_combine_kernel(const Cross
         l = fmaf(part[s * sstride + hd + 1], w, l);
         acc = fmaf(part[s * sstride + t], w, acc);
     }
-    bf16 hi, lo;
-    split_bf16(acc / l, hi, lo);
-    bf16* dst = p.y_src + a_pos<PLANES>((int64_t)b * M + m, D, h * hd + t);
-    *dst = hi;
-    if constexpr (PLANES == 2) dst[kLoOffset] = lo;
+    store_operand<PLANES>(p.y_src, (int64_t)b * M + m, D, h * hd + t, acc / l);
 }
 
 size_t cross_attention_partial_floats(int B, int heads, int M, int head_dim) { return (size_t)B * heads * kCrossSplit * M * (head_dim + 2); }

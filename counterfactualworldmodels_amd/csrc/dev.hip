@@ -376,3 +376,68 @@ extern "C" int cwm_dev_raft_flow_update(float* coords_dev, const float* delta_de
     CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return CWM_OK;
 }
+
+// ---- the operand gathers one launch at a time (tests/test_gather_kernels_gpu.py) ----
+extern "C" int cwm_dev_gather(const cwm_dev_gather_args* args) {
+    CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_gather_args), "cwm_dev_gather: args->struct_size must be sizeof(cwm_dev_gather_args)");
+    const cwm_dev_gather_args& a = *args;
+    hipStream_t s = (hipStream_t)a.stream;
+    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_gather: bad mode");
+    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    CWM_REQUIRE(a.out && a.x && a.B > 0 && a.n_rows > 0 && a.Nt > 0 && a.ld > 0 && a.ld % (planes == 2 ? 32 : 4) == 0,
+                "cwm_dev_gather: bad argument (rows of ld = %d need a multiple of 32 in parity mode, of 4 in fast mode)", a.ld);
+    const int L = a.perm_stride ? a.perm_stride : a.Nt;
+    CWM_REQUIRE(L >= a.Nt && a.n_rows <= L, "cwm_dev_gather: %d rows per sample of a %d-slot permutation over %d tokens", a.n_rows, L, a.Nt);
+    int rc = 0;
+    if (a.kind == CWM_DEV_GATHER_IMU) {
+        CWM_REQUIRE(a.perm && a.C > 0 && a.tubelet > 0 && a.C * a.tubelet <= a.ld && (int64_t)a.Nt * a.tubelet <= a.L, "cwm_dev_gather: bad IMU geometry");
+        ImuGatherParams g;
+        memset(&g, 0, sizeof(g));
+        g.imu = a.x;
+        g.B = a.B, g.C = a.C, g.L = a.L, g.tubelet = a.tubelet;
+        g.perm = a.perm, g.perm_stride = L, g.n_rows = a.n_rows, g.n_real = a.Nt;
+        g.out = (bf16*)a.out, g.ld = a.ld;
+        rc = launch_imu_gather(g, planes, s);
+    } else {
+        CWM_REQUIRE(a.P > 0 && a.P % 4 == 0 && a.H > 0 && a.W > 0 && a.H % a.P == 0 && a.W % a.P == 0, "cwm_dev_gather: bad frame geometry");
+        const int n = (a.H / a.P) * (a.W / a.P);
+        CWM_REQUIRE(((uintptr_t)a.x & 15) == 0 && a.sb % 4 == 0 && a.sc % 4 == 0 && a.st % 4 == 0, "cwm_dev_gather: frames must be 16-byte aligned, strides multiples of 4");
+        if (a.kind == CWM_DEV_GATHER_FLOW_RGB) {
+            CWM_REQUIRE(a.perm && a.Nt == n, "cwm_dev_gather: the flow-RGB gather has one frame of %d tokens", n);
+            FlowRgbGatherParams g;
+            memset(&g, 0, sizeof(g));
+            g.fwd = a.fwd, g.bwd = a.bwd, g.f_sb = a.f_sb, g.f_sc = a.f_sc, g.b_sb = a.b_sb, g.b_sc = a.b_sc;
+            g.x = a.x, g.sb = a.sb, g.sc = a.sc;
+            g.normalize = a.normalize, g.H = a.H, g.W = a.W, g.P = a.P;
+            g.perm = a.perm, g.Nt = a.Nt, g.n_rows = a.n_rows, g.perm_stride = L, g.B = a.B;
+            g.out = (bf16*)a.out, g.ld = a.ld;
+            rc = launch_flow_rgb_gather(g, planes, s);
+        } else {
+            CWM_REQUIRE(a.C > 0 && a.Nt % n == 0, "cwm_dev_gather: %d tokens are no whole number of %d-token frames", a.Nt, n);
+            PatchGatherParams g;
+            memset(&g, 0, sizeof(g));
+            g.x = a.x, g.sb = a.sb, g.sc = a.sc, g.st = a.st;
+            g.normalize = a.normalize, g.C = a.C, g.H = a.H, g.W = a.W, g.P = a.P;
+            g.perm = a.perm, g.Nt = a.Nt, g.n_rows = a.n_rows, g.perm_stride = a.perm_stride, g.B = a.B;
+            g.out = (bf16*)a.out, g.ld = a.ld;
+            if (a.kind == CWM_DEV_GATHER_PATCH) {
+                CWM_REQUIRE(a.perm, "cwm_dev_gather: the patch gather reads perm");
+                rc = launch_patch_gather(g, planes, s);
+            } else if (a.kind == CWM_DEV_GATHER_INDEX) {
+                CWM_REQUIRE(a.mask && a.perm && a.err_rows, "cwm_dev_gather: the index gather needs mask, perm and err_rows");
+                rc = launch_index_gather(g, a.mask, a.n_vis, a.perm, a.rank, a.err_rows, planes, s);
+            } else if (a.kind == CWM_DEV_GATHER_INDEX_UNFUSED) {
+                CWM_REQUIRE(a.mask && a.perm && a.rank && a.err_rows, "cwm_dev_gather: the unfused index prologue needs mask, perm, rank and err_rows");
+                CWM_HIP_CHECK(hipMemsetAsync(a.err_rows, 0, (size_t)a.B * sizeof(int), s));
+                if ((rc = launch_mask_to_perm(a.mask, a.B, L, a.n_vis, a.perm, a.err_rows, s))) return rc;
+                if ((rc = launch_patch_gather(g, planes, s))) return rc;
+                rc = launch_perm_to_rank(a.perm, a.rank, a.B, L, s);
+            } else {
+                CWM_REQUIRE(false, "cwm_dev_gather: unknown kind %d", a.kind);
+            }
+        }
+    }
+    if (rc) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize(s));
+    return CWM_OK;
+}

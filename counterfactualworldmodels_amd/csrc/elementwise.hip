@@ -59,25 +59,16 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const LayerNormParams p)
     for (int i = 0; i < MAXI; ++i) {
         const int idx = lane * 8 + i * 512;
         if (idx < p.D) {
-            bf16* out = p.out + a_pos<PLANES>(r, p.ldo, idx);
-            bf16x8 hv, lv;
+            f32x4 y[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const f32x4 g = *reinterpret_cast<const f32x4*>(p.gamma + idx + 4 * h);
                 const f32x4 be = *reinterpret_cast<const f32x4*>(p.beta + idx + 4 * h);
-                f32x4 y;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    y[e] = (v[i][h][e] - mean) * rstd * g[e] + be[e];
-                    bf16 hh, ll;
-                    split_bf16(y[e], hh, ll);
-                    hv[4 * h + e] = hh;
-                    lv[4 * h + e] = ll;
-                }
-                if (p.out_f32) *reinterpret_cast<f32x4*>(p.out_f32 + (size_t)r * p.D + idx + 4 * h) = y;
+                for (int e = 0; e < 4; ++e) y[h][e] = (v[i][h][e] - mean) * rstd * g[e] + be[e];
+                if (p.out_f32) *reinterpret_cast<f32x4*>(p.out_f32 + (size_t)r * p.D + idx + 4 * h) = y[h];
             }
-            *reinterpret_cast<bf16x8*>(out) = hv;
-            if constexpr (PLANES == 2) *reinterpret_cast<bf16x8*>(out + kLoOffset) = lv;
+            store_operand8<PLANES>(p.out, r, p.ldo, idx, y[0], y[1]);
         }
     }
 }
@@ -99,30 +90,35 @@ int launch_layernorm(const LayerNormParams& p, int planes, hipStream_t stream) {
 // `cat([vis, masked])` (vmae.py:555-557): visible tokens in ascending token index, then masked
 // tokens in ascending token index.  Integer-exact; one workgroup per sample, block-wide scan.
 // ---------------------------------------------------------------------------------------------
+// Exclusive prefix of `count` over the 256 threads of a workgroup, in thread order, and the workgroup's total: an inclusive shuffle scan per
+// wave, the four wave totals through LDS (`wave_tot`, 4 ints), ONE __syncthreads (which callers may rely on for their own LDS writes).
+__device__ __forceinline__ int block_exclusive_scan256(int count, int* wave_tot, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = count;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += v;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    int before = incl - count;
+    for (int w = 0; w < wave; ++w) before += wave_tot[w];
+    total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    return before;
+}
+
 __global__ __launch_bounds__(256) void mask_to_perm_kernel(const uint8_t* mask, int Nt, int n_vis, int* perm, int* err) {
-    __shared__ int counts[256];
-    __shared__ int total_vis;
+    __shared__ int wave_tot[4];
     const int b = blockIdx.x, t = threadIdx.x;
     const uint8_t* m = mask + (size_t)b * Nt;
     const int per = (Nt + 255) / 256;
     const int lo = min(t * per, Nt), hi = min(lo + per, Nt);
     int c = 0;
     for (int i = lo; i < hi; ++i) c += (m[i] == 0);
-    counts[t] = c;
-    __syncthreads();
-    if (t == 0) {
-        int run = 0;
-        for (int i = 0; i < 256; ++i) {
-            const int v = counts[i];
-            counts[i] = run;
-            run += v;
-        }
-        total_vis = run;
-        if (run != n_vis) atomicExch(err, 1);
-    }
-    __syncthreads();
-    int vis_before = counts[t];
-    const int tv = total_vis;
+    int tv;
+    int vis_before = block_exclusive_scan256(c, wave_tot, tv);
+    if (t == 0 && tv != n_vis) atomicExch(err, 1);
     int* pr = perm + (size_t)b * Nt;
     for (int i = lo; i < hi; ++i) {
         if (m[i] == 0) {
@@ -162,6 +158,46 @@ int launch_perm_to_rank(const int* perm, int* rank, int B, int Nt, hipStream_t s
 // per-token, so gathering first is identical and skips the masked half of frame 2.
 // One thread per (row, c, ph): reads P contiguous pixels, writes P contiguous bf16.
 // ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void imagenet_mean_std(int c, float& mean, float& stdv) {
+    mean = (c == 0) ? 0.485f : (c == 1) ? 0.456f : 0.406f;
+    stdv = (c == 0) ? 0.229f : (c == 1) ? 0.224f : 0.225f;
+}
+
+// The body of every tubelet gather, one (row, channel, patch row) item: P contiguous pixels at `src` -> columns kbase .. kbase + P - 1 of
+// operand row `row`, as (a - shift) / div when `arith`, as they are otherwise.  A pad slot (the null token of a padded predictor: no pixels
+// behind it) reads nothing and writes exact zeros.
+template <int PLANES>
+__device__ __forceinline__ void gather_item(const float* src, bool pad_slot, bool arith, float shift, float div, bf16* out, int64_t row, int ld, int kbase, int P) {
+    for (int pw = 0; pw < P; pw += 4) {
+        const f32x4 v = pad_slot ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(src + pw);
+        bf16x4 hv, lv;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float a = v[e];
+            if (arith && !pad_slot) a = (a - shift) / div;
+            split_bf16_at<PLANES>(a, hv, lv, e);
+        }
+        store_operand_split<PLANES>(out, row, ld, kbase + pw, hv, lv);
+    }
+}
+
+// Item `rem` = (channel, patch row) of token `tau` of sample b -> operand row `row`; item 0 also zeroes the row's K padding (K = C*P*P up to ld)
+template <int PLANES>
+__device__ __forceinline__ void patch_gather_item(const PatchGatherParams& p, int b, int64_t row, int rem, int tau) {
+    const int c = rem / p.P, ph = rem - c * p.P;
+    const bool pad_slot = tau >= p.Nt;
+    const int tt = pad_slot ? 0 : tau;
+    const int gw = p.W / p.P;
+    const int n = (p.H / p.P) * gw;
+    const int t = tt / n, hw = tt - t * n;
+    const int hy = hw / gw, wx = hw - hy * gw;
+    const float* src = p.x + b * p.sb + c * p.sc + t * p.st + (int64_t)(hy * p.P + ph) * p.W + wx * p.P;
+    float mean, stdv;
+    imagenet_mean_std(c, mean, stdv);
+    gather_item<PLANES>(src, pad_slot, p.normalize != 0, mean, stdv, p.out, row, p.ld, c * p.P * p.P + ph * p.P, p.P);
+    if (rem == 0) zero_operand_tail<PLANES>(p.out, row, p.ld, p.C * p.P * p.P);
+}
+
 template <int PLANES>
 __global__ __launch_bounds__(256) void patch_gather_kernel(const PatchGatherParams p) {
     const int per_row = p.C * p.P;
@@ -170,44 +206,8 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const PatchGatherPara
     if (gid >= total) return;
     const int row = (int)(gid / per_row);
     const int rem = (int)(gid - (int64_t)row * per_row);
-    const int c = rem / p.P, ph = rem - c * p.P;
     const int b = row / p.n_rows, i = row - b * p.n_rows;
-    const int tau = p.perm[(size_t)b * (p.perm_stride ? p.perm_stride : p.Nt) + i];
-    const int gw = p.W / p.P;
-    const int n = (p.H / p.P) * gw;
-    const int t = tau / n, hw = tau - t * n;
-    const int hy = hw / gw, wx = hw - hy * gw;
-    const float* src = p.x + b * p.sb + c * p.sc + t * p.st + (int64_t)(hy * p.P + ph) * p.W + wx * p.P;
-    const float mean = (c == 0) ? 0.485f : (c == 1) ? 0.456f : 0.406f;
-    const float stdv = (c == 0) ? 0.229f : (c == 1) ? 0.224f : 0.225f;
-    const int kbase = c * p.P * p.P + ph * p.P;
-    const bool pad_slot = tau >= p.Nt;  // null-token pad slot of a padded predictor: no pixels behind it
-    for (int pw = 0; pw < p.P; pw += 4) {
-        const float4 v = pad_slot ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(src + pw);
-        float f[4] = {v.x, v.y, v.z, v.w};
-        bf16x4 hv, lv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float a = f[e];
-            if (p.normalize && !pad_slot) a = (a - mean) / stdv;
-            bf16 hi, lo;
-            split_bf16(a, hi, lo);
-            hv[e] = hi;
-            lv[e] = lo;
-        }
-        bf16* dst = p.out + a_pos<PLANES>(row, p.ld, kbase + pw);
-        *reinterpret_cast<bf16x4*>(dst) = hv;
-        if constexpr (PLANES == 2) *reinterpret_cast<bf16x4*>(dst + kLoOffset) = lv;
-    }
-    // zero the K padding (K = C*P*P rounded up to ld) once per row
-    if (rem == 0) {
-        const int K = p.C * p.P * p.P;
-        for (int k = K; k < p.ld; ++k) {
-            bf16* z = p.out + a_pos<PLANES>(row, p.ld, k);
-            *z = (bf16)0.f;
-            if constexpr (PLANES == 2) z[kLoOffset] = (bf16)0.f;
-        }
-    }
+    patch_gather_item<PLANES>(p, b, row, rem, p.perm[(size_t)b * (p.perm_stride ? p.perm_stride : p.Nt) + i]);
 }
 
 int launch_patch_gather(const PatchGatherParams& p, int planes, hipStream_t stream) {
@@ -253,39 +253,11 @@ __global__ __launch_bounds__(256) void flow_rgb_gather_kernel(const FlowRgbGathe
         src = (c < 2 ? p.fwd + b * p.f_sb + (c & 1) * p.f_sc : p.bwd + b * p.b_sb + (c & 1) * p.b_sc) + pix;
         div = 0.5f * (float)((c & 1) ? p.H : p.W);
     } else {
-        const int rc = c - 4;
-        src = p.x + b * p.sb + rc * p.sc + pix;
-        if (p.normalize) {
-            const float mean = (rc == 0) ? 0.485f : (rc == 1) ? 0.456f : 0.406f;
-            const float stdv = (rc == 0) ? 0.229f : (rc == 1) ? 0.224f : 0.225f;
-            div = stdv;
-            shift = mean;
-        }
+        src = p.x + b * p.sb + (c - 4) * p.sc + pix;
+        if (p.normalize) imagenet_mean_std(c - 4, shift, div);
     }
-    const int kbase = c * p.P * p.P + ph * p.P;
-    for (int pw = 0; pw < p.P; pw += 4) {
-        const float4 v = pad_slot ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(src + pw);
-        float f[4] = {v.x, v.y, v.z, v.w};
-        bf16x4 hv, lv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float a = pad_slot ? 0.f : (f[e] - shift) / div;
-            bf16 hi, lo;
-            split_bf16(a, hi, lo);
-            hv[e] = hi;
-            lv[e] = lo;
-        }
-        bf16* dst = p.out + a_pos<PLANES>(row, p.ld, kbase + pw);
-        *reinterpret_cast<bf16x4*>(dst) = hv;
-        if constexpr (PLANES == 2) *reinterpret_cast<bf16x4*>(dst + kLoOffset) = lv;
-    }
-    if (rem == 0) {  // K padding, once per row
-        for (int k = C * p.P * p.P; k < p.ld; ++k) {
-            bf16* z = p.out + a_pos<PLANES>(row, p.ld, k);
-            *z = (bf16)0.f;
-            if constexpr (PLANES == 2) z[kLoOffset] = (bf16)0.f;
-        }
-    }
+    gather_item<PLANES>(src, pad_slot, true, shift, div, p.out, row, p.ld, c * p.P * p.P + ph * p.P, p.P);
+    if (rem == 0) zero_operand_tail<PLANES>(p.out, row, p.ld, C * p.P * p.P);
 }
 
 int launch_flow_rgb_gather(const FlowRgbGatherParams& p, int planes, hipStream_t stream) {
@@ -321,7 +293,7 @@ __global__ __launch_bounds__(256) void index_gather_kernel(const PatchGatherPara
                                                            int* __restrict__ rank_out, int* __restrict__ err_rows) {
     extern __shared__ int vis_tab[];  // [n_rows]
     __shared__ int wave_tot[4];
-    const int b = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int b = blockIdx.y, t = threadIdx.x;
     const int L = p.perm_stride ? p.perm_stride : p.Nt;  // mask row length (padded predictors: real tokens + pad slots)
     const uint8_t* m = mask + (size_t)b * L;
     // perm / rank of the sample are written by ALL of its workgroups (every one has the whole scan anyway): thread slice t belongs to workgroup t mod nw.
@@ -330,132 +302,63 @@ __global__ __launch_bounds__(256) void index_gather_kernel(const PatchGatherPara
     const bool writer = (t % nw) == (int)blockIdx.x;
     int* pr = perm_out + (size_t)b * L;
     int* rk = rank_out ? rank_out + (size_t)b * L : nullptr;
-    int total_vis;
-    if ((L & 15) == 0 && L <= 256 * 32 && ((uintptr_t)mask & 15) == 0) {
-        // Round 6: the thread's slice of the mask row -- 16 or 32 consecutive bytes -- comes in with one or two 16-byte loads and STAYS in registers for the
-        // second pass.  (Round 5: (L + 255) / 256 = 25 single-byte loads per thread at a 25-byte lane stride, twice; on the long rows of ViT-L/4
-        // -- L = 6272 -- that scan, repeated by each of the sample's ~150 workgroups, was most of the launch: 27 - 34 us for 10 MB, now 20 - 23.)
-        const int per = L <= 256 * 16 ? 16 : 32;
-        const int lo = t * per;
-        u32x4 w0 = u32x4{0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u}, w1 = w0;  // (past the row: "masked", never counted)
+    // Is token i visible?  Rows of whole 16-byte groups: the thread's slice of the mask row -- 16 or 32 consecutive bytes -- comes in with one or two
+    // 16-byte loads and STAYS in registers for the second pass (round 6.  Round 5: (L + 255) / 256 = 25 single-byte loads per thread at a 25-byte
+    // lane stride, twice; on the long rows of ViT-L/4 -- L = 6272 -- that scan, repeated by each of the sample's ~150 workgroups, was most of the
+    // launch: 27 - 34 us for 10 MB, now 20 - 23.)  Other rows (test-sized grids): the byte loop, the mask read twice.
+    const bool vec = (L & 15) == 0 && L <= 256 * 32 && ((uintptr_t)mask & 15) == 0;
+    const int per = !vec ? (L + 255) / 256 : L <= 256 * 16 ? 16 : 32;
+    const int lo = min(t * per, L), hi = min(lo + per, L);
+    u32x4 w0 = u32x4{0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u}, w1 = w0;  // (past the row: "masked", never counted)
+    int c = 0;
+    if (vec) {
         if (lo < L) w0 = *reinterpret_cast<const u32x4*>(m + lo);
         if (per == 32 && lo + 16 < L) w1 = *reinterpret_cast<const u32x4*>(m + lo + 16);
-        const int n_mine = lo >= L ? 0 : min(per, L - lo);
-        auto zero_bytes = [](unsigned x) {  // number of bytes of x that are 0 (any non-zero byte = masked, as `m[i] == 0` read it)
+        auto zero_bytes = [](unsigned x) {  // number of bytes of x that are 0 (any non-zero byte = masked, as `m[i] == 0` reads it)
             const unsigned y = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
             return __popc(~(y | x | 0x7F7F7F7Fu));
         };
-        int c = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) c += zero_bytes(w0[q]) + zero_bytes(w1[q]);
-        int incl = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
+    } else {
+        for (int i = lo; i < hi; ++i) c += (m[i] == 0);
+    }
+    int total_vis;
+    int v = block_exclusive_scan256(c, wave_tot, total_vis);
+    auto emit = [&](int i, bool visible) {
+        if (visible) {
+            if (v < p.n_rows) vis_tab[v] = i;
+            if (writer) {
+                pr[v] = i;
+                if (rk) rk[i] = v;
+            }
+            ++v;
+        } else if (writer) {
+            const int pos = total_vis + (i - v);
+            pr[pos] = i;
+            if (rk) rk[i] = pos;
         }
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        int v = incl - c;
-        for (int w2 = 0; w2 < wave; ++w2) v += wave_tot[w2];
-        total_vis = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    };
+    if (vec) {
 #pragma unroll
         for (int k = 0; k < 32; ++k) {
-            if (k < n_mine) {
+            if (k < hi - lo) {
                 const unsigned word = k < 16 ? w0[(k >> 2) & 3] : w1[(k >> 2) & 3];
-                const bool visible = ((word >> (8 * (k & 3))) & 0xFFu) == 0;
-                const int i = lo + k;
-                if (visible) {
-                    if (v < p.n_rows) vis_tab[v] = i;
-                    if (writer) {
-                        pr[v] = i;
-                        if (rk) rk[i] = v;
-                    }
-                    ++v;
-                } else if (writer) {
-                    const int pos = total_vis + (i - v);
-                    pr[pos] = i;
-                    if (rk) rk[i] = pos;
-                }
+                emit(lo + k, ((word >> (8 * (k & 3))) & 0xFFu) == 0);
             }
         }
-    } else {  // rows that are not whole 16-byte groups (test-sized grids): the byte loop
-        const int per = (L + 255) / 256;
-        const int lo = min(t * per, L), hi = min(lo + per, L);
-        int c = 0;
-        for (int i = lo; i < hi; ++i) c += (m[i] == 0);
-        int incl = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
-        }
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        int v = incl - c;
-        for (int w2 = 0; w2 < wave; ++w2) v += wave_tot[w2];
-        total_vis = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-        for (int i = lo; i < hi; ++i) {
-            if (m[i] == 0) {
-                if (v < p.n_rows) vis_tab[v] = i;
-                if (writer) {
-                    pr[v] = i;
-                    if (rk) rk[i] = v;
-                }
-                ++v;
-            } else if (writer) {
-                const int pos = total_vis + (i - v);
-                pr[pos] = i;
-                if (rk) rk[i] = pos;
-            }
-        }
+    } else {
+        for (int i = lo; i < hi; ++i) emit(i, m[i] == 0);
     }
     if (blockIdx.x == 0 && t == 0) err_rows[b] = total_vis != n_vis ? 1 : 0;
     __syncthreads();
 
     const int per_row = p.C * p.P;
     const int total = p.n_rows * per_row;
-    const int gw = p.W / p.P;
-    const int n = (p.H / p.P) * gw;
     for (int gid = blockIdx.x * 256 + t; gid < total; gid += gridDim.x * 256) {
         const int i = gid / per_row;
-        const int rem = gid - i * per_row;
-        const int ch = rem / p.P, ph = rem - ch * p.P;
-        const int tau = i < total_vis ? vis_tab[i] : p.Nt;  // (a row with too few visible tokens is reported through err_rows: its missing rows read nothing)
-        const bool pad_slot = tau >= p.Nt;                  // null-token pad slot of a padded predictor: no pixels behind it
-        const int tt = pad_slot ? 0 : tau;
-        const int tf = tt / n, hw = tt - tf * n;
-        const int hy = hw / gw, wx = hw - hy * gw;
-        const float* src = p.x + b * p.sb + ch * p.sc + tf * p.st + (int64_t)(hy * p.P + ph) * p.W + wx * p.P;
-        const float mean = (ch == 0) ? 0.485f : (ch == 1) ? 0.456f : 0.406f;
-        const float stdv = (ch == 0) ? 0.229f : (ch == 1) ? 0.224f : 0.225f;
-        const int kbase = ch * p.P * p.P + ph * p.P;
-        const int64_t row = (int64_t)b * p.n_rows + i;
-        for (int pw = 0; pw < p.P; pw += 4) {
-            const float4 q = pad_slot ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(src + pw);
-            float f[4] = {q.x, q.y, q.z, q.w};
-            bf16x4 hv, lv;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float a = f[e];
-                if (p.normalize && !pad_slot) a = (a - mean) / stdv;
-                bf16 hi2, lo2;
-                split_bf16(a, hi2, lo2);
-                hv[e] = hi2;
-                lv[e] = lo2;
-            }
-            bf16* dst = p.out + a_pos<PLANES>(row, p.ld, kbase + pw);
-            *reinterpret_cast<bf16x4*>(dst) = hv;
-            if constexpr (PLANES == 2) *reinterpret_cast<bf16x4*>(dst + kLoOffset) = lv;
-        }
-        if (rem == 0) {  // zero the K padding (K = C*P*P rounded up to ld) once per row
-            const int K = p.C * p.P * p.P;
-            for (int k = K; k < p.ld; ++k) {
-                bf16* z = p.out + a_pos<PLANES>(row, p.ld, k);
-                *z = (bf16)0.f;
-                if constexpr (PLANES == 2) z[kLoOffset] = (bf16)0.f;
-            }
-        }
+        // (a row with too few visible tokens is reported through err_rows: its missing rows read nothing)
+        patch_gather_item<PLANES>(p, b, (int64_t)b * p.n_rows + i, gid - i * per_row, i < total_vis ? vis_tab[i] : p.Nt);
     }
 }
 
@@ -747,7 +650,7 @@ constexpr int kFlipMaxTokens = 16384;
 __global__ __launch_bounds__(256) void mask_flip_picks_kernel(uint8_t* __restrict__ mask, int Nt, const int* __restrict__ table) {
     __shared__ unsigned bits[kFlipMaxTokens / 32];
     __shared__ int wave_tot[4];
-    const int R = table[0], r = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int R = table[0], r = blockIdx.x, t = threadIdx.x;
     const int row = table[1 + r], p0 = table[1 + R + r], p1 = table[1 + R + r + 1], to = table[2 + 2 * R + r];
     const int* picks = table + 2 + 3 * R;
     uint8_t* m = mask + (size_t)row * Nt;
@@ -761,16 +664,8 @@ __global__ __launch_bounds__(256) void mask_flip_picks_kernel(uint8_t* __restric
     const int lo = min(t * per, Nt), hi = min(lo + per, Nt);
     int c = 0;
     for (int i = lo; i < hi; ++i) c += ((m[i] != 0) != (to != 0));  // candidates: tokens whose state is not `to` yet
-    int incl = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();  // (also: the bitmap is complete)
-    int v = incl - c;
-    for (int w2 = 0; w2 < wave; ++w2) v += wave_tot[w2];
+    int total;
+    int v = block_exclusive_scan256(c, wave_tot, total);  // (its barrier also completes the bitmap)
     for (int i = lo; i < hi; ++i) {
         if ((m[i] != 0) != (to != 0)) {
             if (bits[v >> 5] & (1u << (v & 31))) m[i] = (uint8_t)(to ? 1 : 0);

@@ -103,14 +103,8 @@ __global__ void pack_weight_kernel(const float* src, int N, int K, bf16* hi, bf1
     if (i >= (int64_t)Npad * Kpad) return;
     const int n = (int)(i / Kpad), k = (int)(i - (int64_t)n * Kpad);
     float v = (n < N && k < K) ? src[(size_t)n * K + k] : 0.f;
-    bf16 h, l;
-    split_bf16(v, h, l);
-    if (hi) hi[i] = h;
-    if (il) {
-        bf16* d = il + a_pos<2>(n, Kpad, k);
-        d[0] = h;
-        d[kLoOffset] = l;
-    }
+    if (hi) store_operand<1>(hi, n, Kpad, k, v);
+    if (il) store_operand<2>(il, n, Kpad, k, v);
 }
 
 int launch_pack_weight(const float* src, int N, int K, bf16* hi, bf16* il, int Npad, int Kpad, hipStream_t stream) {

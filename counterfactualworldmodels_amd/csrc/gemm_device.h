@@ -125,7 +125,7 @@ __device__ __forceinline__ void epilogue_frag(const GemmParams& p, const RowMap&
         return;
     }
     bf16* dst;
-    int64_t plane;
+    int64_t plane;  // the lo plane's distance from dst
     if (p.epi == EPI_QKV) {
         const int D = p.qkv_dim;
         const int which = nb / D;  // 0 q, 1 k, 2 v (uniform per 16-column fragment)
@@ -135,22 +135,15 @@ __device__ __forceinline__ void epilogue_frag(const GemmParams& p, const RowMap&
         dst = qkv_out_base(p, which) + ((size_t)(rm.b * p.heads + h) * p.n_tok + rm.tok) * p.head_dim + d;
         plane = p.qk_plane;
     } else {
-        if (p.epi == EPI_BF16_GELU) {
-#pragma unroll
-            for (int r = 0; r < 4; r += 4) v = gelu_erf4(v);
-        }
+        if (p.epi == EPI_BF16_GELU) v = gelu_erf4(v);
         dst = p.out_hi + a_pos<PLANES>(rm.out_row, p.ldo, n);  // A-operand layout of the next GEMM
         plane = kLoOffset;
     }
     bf16x4 hv, lv;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const bf16 hi = (bf16)v[r];
-        hv[r] = hi;
-        lv[r] = (bf16)(v[r] - (float)hi);
-    }
+    split_bf16v<PLANES>(v, hv, lv);
     if (p.debug & 1) {
-        asm volatile("" ::"v"(hv), "v"(lv), "v"(dst));
+        if constexpr (PLANES == 2) asm volatile("" ::"v"(hv), "v"(lv), "v"(dst));
+        else asm volatile("" ::"v"(hv), "v"(dst));
         return;
     }
     *reinterpret_cast<bf16x4*>(dst) = hv;
@@ -275,12 +268,7 @@ __device__ __forceinline__ void epilogue_piece_seq(const GemmParams& p, Frag fra
                         v *= p.q_scale;
                     }
                     bf16x4 hv, lv;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const bf16 hi = (bf16)v[e];
-                        hv[e] = hi;
-                        lv[e] = (bf16)(v[e] - (float)hi);
-                    }
+                    split_bf16v<PLANES>(v, hv, lv);
                     const int ch = j * 2 + (fq >> 1), sub = (fq & 1) * 8;
                     *reinterpret_cast<bf16x4*>(wlds + r * 128 + ((ch ^ (r & 7)) << 4) + sub) = hv;
                     if constexpr (PLANES == 2) *reinterpret_cast<bf16x4*>(wlds + r * 128 + (((ch + 4) ^ (r & 7)) << 4) + sub) = lv;
@@ -449,18 +437,15 @@ __device__ __forceinline__ void epilogue_direct(const GemmParams& p, Frag frag, 
                 if (p.epi == EPI_BF16_GELU) v = gelu_erf4(v);
                 else if (which == 0 && p.epi == EPI_QKV) v *= p.q_scale;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const bf16 hi = (bf16)v[e];
-                    hv[j * 4 + e] = hi;
-                    lv[j * 4 + e] = (bf16)(v[e] - (float)hi);
-                }
+                for (int e = 0; e < 4; ++e) split_bf16_at<PLANES>(v[e], hv, lv, j * 4 + e);
             }
             const bool ok = info.x >= 0 && n < p.N;
             bf16* d = base + (size_t)max(info.x, 0) * row_mul;  // (info.x < 0: a row past M -- the lane stores to the trash buffer instead)
             gbf16x8* dh = ok ? (gbf16x8*)d : (gbf16x8*)trash;
             gbf16x8* dl = ok ? (gbf16x8*)(d + lo_off) : (gbf16x8*)trash;
             if (p.debug & 1) {
-                asm volatile("" ::"v"(hv), "v"(lv), "v"(dh), "v"(dl));
+                if constexpr (PLANES == 2) asm volatile("" ::"v"(hv), "v"(lv), "v"(dh), "v"(dl));
+                else asm volatile("" ::"v"(hv), "v"(dh), "v"(dl));
                 continue;
             }
             *dh = hv;

@@ -283,11 +283,7 @@ __global__ void pad_split_rows_kernel(const float* src, int rows, int K, bf16* o
     if (i >= (int64_t)rows * Kpad) return;
     const int r = (int)(i / Kpad), k = (int)(i - (int64_t)r * Kpad);
     const float v = k < K ? src[(size_t)r * K + k] : 0.f;
-    bf16 h, l;
-    split_bf16(v, h, l);
-    bf16* d = out + a_pos<PLANES>(r, Kpad, k);
-    d[0] = h;
-    if constexpr (PLANES == 2) d[kLoOffset] = l;
+    store_operand<PLANES>(out, r, Kpad, k, v);
 }
 
 // qkv [B,N,3,H,64] fp32 -> Q (scaled), K, V [B*H,N,64]

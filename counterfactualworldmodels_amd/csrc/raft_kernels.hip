@@ -14,19 +14,6 @@ namespace {
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
 
-template <int PLANES>
-__device__ __forceinline__ void store_operand(bf16* A, int64_t row, int Kpad, int k, float v) {
-    bf16* d = A + a_pos<PLANES>(row, Kpad, k);
-    if constexpr (PLANES == 1) {
-        d[0] = (bf16)v;
-    } else {
-        bf16 h, l;
-        split_bf16(v, h, l);
-        d[0] = h;
-        d[kLoOffset] = l;
-    }
-}
-
 // value of channel c of one source at pixel `pix` (of image `img`, spatial position (y, x))
 __device__ __forceinline__ float src_value(const ConvSrc& s, int64_t pix, int img, int y, int x, int c) {
     if (s.coords) return s.coords[pix * 2 + c] - (float)(c ? y : x);  // flow = coords1 - coords0
@@ -80,22 +67,13 @@ __global__ void im2col_kernel(const Im2colParams p) {
                     }
                 }
             }
-            if constexpr (PLANES == 1) {
-                hv[j] = (bf16)v;
-            } else {
-                bf16 h, l;
-                split_bf16(v, h, l);
-                hv[j] = h;
-                lv[j] = l;
-            }
+            split_bf16_at<PLANES>(v, hv, lv, j);
             if (++c == Ctot) {
                 c = 0;
                 ++tap;
             }
         }
-        bf16* d = p.A + a_pos<PLANES>(m, p.Kpad, kb);
-        *reinterpret_cast<bf16x8*>(d) = hv;
-        if constexpr (PLANES == 2) *reinterpret_cast<bf16x8*>(d + kLoOffset) = lv;
+        store_operand_split<PLANES>(p.A, m, p.Kpad, kb, hv, lv);
     }
 }
 
@@ -413,12 +391,8 @@ __global__ void pack_conv_kernel(const float* w, const float* gamma, const float
         v = w[(((int64_t)n * C + c) * kh + ky) * kw + kx];
         if (gamma) v = v * (gamma[n] / sqrtf(var[n] + eps));
     }
-    bf16 h, l;
-    split_bf16(v, h, l);
-    bf16* d = il + a_pos<2>(row0 + n, Kpad, k);
-    d[0] = h;
-    d[kLoOffset] = l;
-    hi[a_pos<1>(row0 + n, Kpad, k)] = h;  // the fast plane: the folded weight rounded once (split_bf16's hi is (bf16)v)
+    store_operand<2>(il, row0 + n, Kpad, k, v);
+    store_operand<1>(hi, row0 + n, Kpad, k, v);  // the fast plane: the folded weight rounded once (the parity hi plane is the same (bf16)v)
 }
 
 __global__ void pack_bias_kernel(const float* b, const float* gamma, const float* beta, const float* mean, const float* var, float eps, int N,

@@ -111,6 +111,39 @@ CWM_API int cwm_dev_raft_gru_update(float* h_dev, const float* zr_dev, const flo
 /* coords [M][2] += delta[m * ld + (0, 1)] */
 CWM_API int cwm_dev_raft_flow_update(float* coords_dev, const float* delta_dev, int ld, int64_t M, void* stream);
 
+/* ---- the operand gathers one launch at a time (tests/test_gather_kernels_gpu.py) ----------------------------------------------------------------
+ * launch_patch_gather / launch_index_gather / launch_flow_rgb_gather / launch_imu_gather (csrc/kernels.h) on caller-owned device buffers; the
+ * stream is synchronised before the call returns.  `out` is the GEMM A operand, [B * n_rows] rows of planes * ld bf16 in the layout of csrc/common.h
+ * a_pos (planes 2 parity, 1 fast); the caller's buffers must be as large as the geometry says. */
+#define CWM_DEV_GATHER_PATCH 0         /* reads perm */
+#define CWM_DEV_GATHER_INDEX 1         /* reads mask; writes perm, rank (optional) and err_rows[B] = (visible count of the row != n_vis) */
+#define CWM_DEV_GATHER_FLOW_RGB 2      /* reads perm; 7 channels [fwd x, fwd y, bwd x, bwd y, R, G, B] of one frame */
+#define CWM_DEV_GATHER_IMU 3           /* reads perm; x = imu [B][C][L], token l = samples tubelet * l .. of every channel */
+#define CWM_DEV_GATHER_INDEX_UNFUSED 4 /* what INDEX replaced: mask_to_perm, patch gather, perm_to_rank; err_rows[0] = (any row's count != n_vis) */
+typedef struct cwm_dev_gather_args {
+    uint32_t struct_size;
+    int32_t kind; /* CWM_DEV_GATHER_* */
+    int32_t mode; /* CWM_MODE_PARITY or CWM_MODE_FAST */
+    int32_t normalize; /* imagenet-normalise the RGB channels in the kernel */
+    const float* x; /* frames: element (b, c, t, y, x) at b * sb + c * sc + t * st + y * W + x (FLOW_RGB: one frame, st unused); IMU: the signal */
+    int64_t sb, sc, st;
+    const float *fwd, *bwd; /* FLOW_RGB: forward / backward flow, element (b, c, y, x) at b * f_sb + c * f_sc + y * W + x (b_sb, b_sc likewise) */
+    int64_t f_sb, f_sc, b_sb, b_sc;
+    int32_t B, C, H, W, P;
+    int32_t L, tubelet; /* IMU */
+    int32_t Nt;          /* real tokens per sample: permutation entries >= Nt are pad slots (zero rows) */
+    int32_t n_rows;      /* rows gathered per sample */
+    int32_t perm_stride; /* slots per row of mask / perm / rank; 0: Nt */
+    int32_t n_vis;       /* INDEX, INDEX_UNFUSED: the visible count every mask row must have */
+    const uint8_t* mask; /* INDEX, INDEX_UNFUSED: [B][slots], 0 = visible */
+    int32_t* perm;       /* [B][slots] */
+    int32_t* rank;       /* [B][slots] */
+    int32_t* err_rows;   /* [B] */
+    void* out;
+    int32_t ld;
+    void* stream;
+} cwm_dev_gather_args;
+CWM_API int cwm_dev_gather(const cwm_dev_gather_args* args);
 
 #ifdef __cplusplus
 }

@@ -74,3 +74,26 @@ def mask_to_perm(mask, n_vis, lib=None):
     perm = torch.empty(B, Nt, device=dev(), dtype=torch.int32)
     _lib.check(lib.cwm_mask_to_perm(m_d.data_ptr(), B, Nt, n_vis, perm.data_ptr(), stream()), lib)
     return perm.cpu()
+
+
+# ---- the GEMM A-operand layout (csrc/common.h a_pos) as the kernel-level tests read it ----
+NAN_BF16 = 0x7FC0  # what the operand buffers are pre-filled with
+
+
+def new_operand(M, Kpad, planes):
+    return torch.full((M, planes * Kpad), NAN_BF16, dtype=torch.int16, device="cuda")
+
+
+def decode(A, planes, Kpad):
+    """The layout csrc/common.h documents -> (hi, lo) bf16 [M, Kpad] on the CPU (lo None in fast mode): fast rows are row-major; parity rows are
+    [32 hi | 32 lo] per 64 elements"""
+    a = A.cpu()
+    M = a.shape[0]
+    if planes == 1:
+        return a.view(torch.bfloat16), None
+    b = a.view(M, Kpad // 32, 2, 32)
+    return b[:, :, 0].reshape(M, Kpad).view(torch.bfloat16), b[:, :, 1].reshape(M, Kpad).view(torch.bfloat16)
+
+
+def bits(t):
+    return t.contiguous().view(torch.int16)

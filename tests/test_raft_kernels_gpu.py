@@ -14,12 +14,12 @@ import torch
 import torch.nn.functional as F
 
 from counterfactualworldmodels_amd import _lib
+from gpu_utils import NAN_BF16, bits, decode, new_operand  # the operand layout's test helpers
 from test_kernels_gpu import TOL  # the project's GEMM bounds (max-abs on O(1) outputs)
 
 pytestmark = pytest.mark.gpu
 
 MODES = {"parity": (_lib.MODE_PARITY, 2), "fast": (_lib.MODE_FAST, 1)}
-NAN_BF16 = 0x7FC0       # what the operand buffers are pre-filled with
 SENTINEL = 0x7FA5A5A5   # a NaN payload no kernel produces: what the output buffers are pre-filled with
 EPS = 1e-5              # the model's instance-norm / batch-norm epsilon
 H0, W0, N_IMG = 9, 11, 2  # odd sides, 198 rows (no multiple of any tile), a second image
@@ -145,25 +145,6 @@ def unfold_rows(v, k, stride, pad):
     u = F.unfold(v.permute(0, 3, 1, 2), k, padding=pad, stride=stride)  # [n, C * kh * kw, L], channel-major
     L = u.shape[-1]
     return u.view(n, C, k[0] * k[1], L).permute(0, 3, 2, 1).reshape(n * L, k[0] * k[1] * C)
-
-
-def new_operand(M, Kpad, planes):
-    return torch.full((M, planes * Kpad), NAN_BF16, dtype=torch.int16, device="cuda")
-
-
-def decode(A, planes, Kpad):
-    """The layout csrc/common.h documents -> (hi, lo) bf16 [M, Kpad] on the CPU (lo None in fast mode): fast rows are row-major; parity rows are
-    [32 hi | 32 lo] per 64 elements"""
-    a = A.cpu()
-    M = a.shape[0]
-    if planes == 1:
-        return a.view(torch.bfloat16), None
-    b = a.view(M, Kpad // 32, 2, 32)
-    return b[:, :, 0].reshape(M, Kpad).view(torch.bfloat16), b[:, :, 1].reshape(M, Kpad).view(torch.bfloat16)
-
-
-def bits(t):
-    return t.contiguous().view(torch.int16)
 
 
 def check_operand(name, A, ref, mode, arithmetic):
