@@ -347,6 +347,10 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] * 6,
     ),
+    "cwm_multi_shift_prompts": (
+        C.c_int,
+        [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3,
+    ),
     "cwm_flow_features": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]),
     "cwm_flow_cov": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4),
     "cwm_flow_transform_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

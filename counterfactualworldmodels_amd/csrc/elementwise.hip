@@ -628,6 +628,145 @@ int launch_shift_prompts(const ShiftPromptParams& p, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Multi-shift prompts: K steps per prompt, step k moving its own set of patches of frame `frame` by its own PIXEL shift (sy_k, sx_k).
+// Reference: `MultiShiftPatchesAndMask.forward` (perturbation.py:644-779) = K rounds of `ShiftPatchesAndMask.perturb` in fractional mode
+// (:245-289: pad, centre-crop, patchify and blend the whole frame per step, per sample).  Step k leaves a destination patch (pi, pj) holding the
+// pixels at (y - sy_k, x - sx_k) of the frame as step k-1 left it whenever the source cell (pi - my_k, pj - mx_k) is one of its points
+// (my = sy / P truncated toward zero: the mask moves by whole patches only), zeros where that leaves the image; so an output pixel is found by
+// walking the steps BACKWARDS from its own position.  Pure copies and zeros: bit-exact.  Semantics in full: include/cwm_hip.h.
+// ---------------------------------------------------------------------------------------------
+// Steps k .. 0 for one pixel at (cy, cx), which is inside the image; false once the position has left the image (the pixel is 0).  Every table read is
+// behind the grid test, and a step is taken only from a cell inside the grid, which bounds |s| by (grid + 1) P: no overflow whatever the table holds.
+__device__ __forceinline__ bool multi_shift_walk(const uint8_t* __restrict__ pts, const int* __restrict__ sh, int k, int Nt, int P, int gh, int gw, int H, int W,
+                                                 int& cy, int& cx) {
+    for (; k >= 0; --k) {
+        const int sy = sh[2 * k], sx = sh[2 * k + 1];
+        const int pi = cy / P - sy / P, pj = cx / P - sx / P;  // (C division truncates toward zero: sign(s) (|s| // P))
+        if (pi >= 0 && pi < gh && pj >= 0 && pj < gw && pts[(size_t)k * Nt + pi * gw + pj]) {
+            cy -= sy;
+            cx -= sx;
+            if (cy < 0 || cy >= H || cx < 0 || cx >= W) return false;
+        }
+    }
+    return true;
+}
+
+// One thread = 4 horizontally adjacent pixels of one image row, all C channels (the walk does not depend on the channel).  The four pixels share ONE walk
+// while they sit 4-aligned inside one patch: then they take the same decisions, and a step whose sx is a multiple of 4 keeps them so (16-byte loads).
+// The first step that breaks this -- sx not a multiple of 4, or P not a multiple of 4 and the group straddling two patches -- splits the group into four
+// walks over the remaining steps and dword loads.  Rows whose sx are all multiples of 4 never split; frames other than `frame` are plain copies.
+// Stores are whole 16-byte groups of the output row either way, streaming like the single-shift kernel's.
+__global__ __launch_bounds__(256) void multi_shift_prompts_x_kernel(const MultiShiftParams p) {
+    const int w4 = p.W / 4;
+    const int64_t total = (int64_t)p.B * p.S * p.T * p.H * w4;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= total) return;
+    int64_t r = gid;
+    const int x0 = (int)(r % w4) * 4; r /= w4;
+    const int y = (int)(r % p.H); r /= p.H;
+    const int t = (int)(r % p.T);
+    const int i = (int)(r / p.T);
+    const int b = i / p.S;
+    const int ft = p.fix_passive == 1 ? 0 : t;
+    const int H = p.H, W = p.W, P = p.P;
+    const size_t plane = (size_t)H * W;
+    const float* __restrict__ src = p.x + ((size_t)b * p.T + ft) * p.C * plane;
+    float* __restrict__ dst = p.x_out + ((size_t)i * p.T + t) * p.C * plane + (size_t)y * W + x0;
+    int cy = y, cx = x0, k = -1;
+    bool split = false, alive = true;
+    const int gw = W / P, gh = H / P, n = gh * gw, Nt = p.T * n;
+    const uint8_t* __restrict__ pts = p.points + (size_t)i * p.K * Nt + (size_t)p.frame * n;  // step k of frame `frame` at pts + k Nt
+    const int* __restrict__ sh = p.shifts + (size_t)i * p.K * 2;
+    if (t == p.frame) {
+        for (k = p.K - 1; k >= 0; --k) {
+            if (cx % P + 3 >= P) { split = true; break; }  // (P % 4 != 0 only) step k is still to be taken, per pixel
+            const int sy = sh[2 * k], sx = sh[2 * k + 1];
+            const int pi = cy / P - sy / P, pj = cx / P - sx / P;
+            if (pi >= 0 && pi < gh && pj >= 0 && pj < gw && pts[(size_t)k * Nt + pi * gw + pj]) {
+                cy -= sy;
+                cx -= sx;
+                if (sx & 3) { split = true; --k; break; }  // taken by all four, but they are no longer one aligned group
+                if (cy < 0 || cy >= H || cx < 0 || cx >= W) { alive = false; break; }  // (W % 4 == 0: all four inside or all four outside)
+            }
+        }
+    }
+    if (!split) {
+        const float* s = src + (alive ? (size_t)cy * W + cx : 0);
+        for (int c0 = 0; c0 < p.C; c0 += 4) {
+            f32x4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                v[j] = (alive && c0 + j < p.C) ? *reinterpret_cast<const f32x4*>(s + (size_t)(c0 + j) * plane) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (c0 + j < p.C) __builtin_nontemporal_store(v[j], reinterpret_cast<f32x4*>(dst + (size_t)(c0 + j) * plane));
+        }
+        return;
+    }
+    int off[4];  // source offset inside a channel plane, -1 = outside the image (constant padding: 0)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int py = cy, px = cx + j;
+        const bool ok = py >= 0 && py < H && px >= 0 && px < W && multi_shift_walk(pts, sh, k, Nt, P, gh, gw, H, W, py, px);
+        off[j] = ok ? py * W + px : -1;
+    }
+    for (int c = 0; c < p.C; ++c) {
+        const float* s = src + (size_t)c * plane;
+        f32x4 v;
+        v.x = off[0] >= 0 ? s[off[0]] : 0.f;
+        v.y = off[1] >= 0 ? s[off[1]] : 0.f;
+        v.z = off[2] >= 0 ? s[off[2]] : 0.f;
+        v.w = off[3] >= 0 ? s[off[3]] : 0.f;
+        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst + (size_t)c * plane));
+    }
+}
+
+// mask_out = AND_k step_k; step_k = (M_k | A_k) & shifted_k with base masks, shifted_k without (the reference's `_has_base_mask`, perturbation.py:697-714,
+// 774-778), shifted_k = !A_k moved by (my_k, mx_k) patches in frame `frame` (cells whose source is outside the grid are masked), !A_k elsewhere.
+__global__ __launch_bounds__(256) void multi_shift_prompts_mask_kernel(const MultiShiftParams p) {
+    const int gw = p.W / p.P, gh = p.H / p.P, n = gh * gw, Nt = p.T * n;
+    const int64_t total = (int64_t)p.B * p.S * Nt;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= total) return;
+    const int i = (int)(gid / Nt), tau = (int)(gid - (int64_t)i * Nt);
+    const int t = tau / n, hw = tau - t * n;
+    const uint8_t* __restrict__ pts = p.points + (size_t)i * p.K * Nt;
+    const int* __restrict__ sh = p.shifts + (size_t)i * p.K * 2;
+    uint8_t out = 1;
+    for (int k = 0; k < p.K; ++k) {
+        const uint8_t a = pts[(size_t)k * Nt + tau] != 0;
+        uint8_t shifted = !a;
+        if (t == p.frame) {
+            const int pi = hw / gw - sh[2 * k] / p.P, pj = hw % gw - sh[2 * k + 1] / p.P;
+            shifted = (pi >= 0 && pi < gh && pj >= 0 && pj < gw) ? (pts[(size_t)k * Nt + (size_t)t * n + pi * gw + pj] == 0) : 1;
+        }
+        uint8_t step = shifted;
+        if (p.masks) {
+            const uint8_t m = p.masks[((size_t)i * p.mask_steps + (p.mask_steps == 1 ? 0 : k)) * Nt + tau] != 0;
+            step = (m | a) & shifted;
+        }
+        out &= step;
+    }
+    p.mask_out[gid] = out;
+}
+
+int launch_multi_shift_prompts(const MultiShiftParams& p, hipStream_t stream) {
+    CWM_REQUIRE(p.K >= 1 && p.K <= kMultiShiftMaxSteps, "multi_shift_prompts: K=%d steps, need 1 <= K <= %d", p.K, kMultiShiftMaxSteps);
+    CWM_REQUIRE(p.P > 0 && p.W % 4 == 0 && p.H % p.P == 0 && p.W % p.P == 0,
+                "multi_shift_prompts: bad patch/image size (H=%d W=%d P=%d: W must be a multiple of 4, H and W multiples of P)", p.H, p.W, p.P);
+    CWM_REQUIRE(p.frame >= 0 && p.frame < p.T, "multi_shift_prompts: frame out of range");
+    CWM_REQUIRE(p.fix_passive == 0 || p.fix_passive == 1, "multi_shift_prompts: fix_passive must be 0 or 1");
+    CWM_REQUIRE(!p.masks || p.mask_steps == 1 || p.mask_steps == p.K, "multi_shift_prompts: mask_steps=%d, need 1 or K=%d", p.mask_steps, p.K);
+    CWM_REQUIRE((((uintptr_t)p.x | (uintptr_t)p.x_out) & 15) == 0, "multi_shift_prompts: the frames must be 16-byte aligned");
+    const int64_t tx = (int64_t)p.B * p.S * p.T * p.H * (p.W / 4);
+    const int64_t tm = (int64_t)p.B * p.S * p.T * (p.H / p.P) * (p.W / p.P);
+    if (p.x_out) hipLaunchKernelGGL(multi_shift_prompts_x_kernel, dim3((unsigned)((tx + 255) / 256)), dim3(256), 0, stream, p);
+    if (p.mask_out) hipLaunchKernelGGL(multi_shift_prompts_mask_kernel, dim3((unsigned)((tm + 255) / 256)), dim3(256), 0, stream, p);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // `RectangularizeMasks` on device masks (masking.py:90-132) without reading the masks back: the host needs only the per-row COUNTS to decide
 // the target and to draw the reference's `torch.randperm(#candidates)[:surplus]` per changed row (the draws depend on the counts alone); the
 // picks -- "the k-th masked (or visible) token of row r in ascending order" -- come back as a small table and are applied here, every pick of a

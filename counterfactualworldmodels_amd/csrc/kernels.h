@@ -210,6 +210,19 @@ struct ShiftPromptParams {
 int launch_shift_prompts(const ShiftPromptParams& p, hipStream_t stream);
 int launch_prompt_table_expand(const int* table, int S, int n, int gw, int T, int frame, uint8_t* active, uint8_t* passive, int* shifts, hipStream_t stream);
 
+constexpr int kMultiShiftMaxSteps = 8;  // K of cwm_multi_shift_prompts (a backward walk of K dependent table reads per pixel)
+struct MultiShiftParams {
+    const float* x;         // [B][T][C][H][W] contiguous frames
+    int B, S, K, T, C, H, W, P, frame, fix_passive, mask_steps;
+    const uint8_t* points;  // [B*S][K][Nt], non-zero at the patches step k moves (step-major: a wave reads adjacent cells of ONE step)
+    const uint8_t* masks;   // [B*S][mask_steps][Nt] base masks (non-zero = masked), mask_steps = K or 1 (one mask for every step); NULL = none
+    const int* shifts;      // [B*S][K][2] (sy, sx) in pixels
+    float* x_out;           // [B*S][T][C][H][W]
+    uint8_t* mask_out;      // [B*S][Nt]
+};
+
+int launch_multi_shift_prompts(const MultiShiftParams& p, hipStream_t stream);
+
 // ---- IMU-conditioned conjoined predictor (conj_kernels.hip) ------------------------------------------
 struct SmallAttnParams {
     const float* qkv;  // [B*n_tok][3*heads*head_dim] fp32 (bias already added; q NOT yet scaled)

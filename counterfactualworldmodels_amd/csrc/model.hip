@@ -484,3 +484,18 @@ extern "C" int cwm_shift_prompts(const float* x_dev, int B, int T, int C, int H,
     return launch_shift_prompts(p, (hipStream_t)stream);
 }
 
+extern "C" int cwm_multi_shift_prompts(const float* x_dev, int B, int T, int C, int H, int W, int P, int frame, int S, int K, int fix_passive,
+                                       const uint8_t* points_dev, const uint8_t* masks_dev, int mask_steps, const int32_t* shifts_dev, int max_abs_shift,
+                                       float* x_out_dev, uint8_t* mask_out_dev, void* stream) {
+    CWM_REQUIRE(points_dev && shifts_dev && (x_dev || !x_out_dev), "cwm_multi_shift_prompts: null argument");
+    CWM_REQUIRE(x_out_dev || mask_out_dev, "cwm_multi_shift_prompts: null outputs (x_out_dev and mask_out_dev are both NULL)");
+    CWM_REQUIRE(B > 0 && S > 0 && T > 0 && C > 0 && P > 0 && H > 0 && W > 0, "cwm_multi_shift_prompts: bad sizes");
+    CWM_REQUIRE(max_abs_shift >= 0 && max_abs_shift < (H < W ? H : W), "cwm_multi_shift_prompts: shifts up to %d px, need |s| < min(H=%d, W=%d)", max_abs_shift, H, W);
+    MultiShiftParams p;
+    memset(&p, 0, sizeof(p));
+    p.x = x_dev; p.B = B; p.S = S; p.K = K; p.T = T; p.C = C; p.H = H; p.W = W; p.P = P; p.frame = frame; p.fix_passive = fix_passive;
+    p.points = points_dev; p.masks = masks_dev; p.mask_steps = masks_dev ? mask_steps : 0; p.shifts = shifts_dev;
+    p.x_out = x_out_dev; p.mask_out = mask_out_dev;
+    return launch_multi_shift_prompts(p, (hipStream_t)stream);
+}
+

@@ -25,6 +25,7 @@ from torch import nn
 from . import _lib
 from .config import IMAGENET_MEAN, IMAGENET_STD
 from .masking import RectangularizeMasks, upsample_masks
+from .perturbation import MultiShiftPatchesAndMask
 from .conjoined_vmae import ConjoinedPaddedVisionTransformer
 from .vmae import PretrainVisionTransformer
 
@@ -77,6 +78,9 @@ class PredictorBasedGenerator(nn.Module):
         self.mask_generator = mask_generator
         self.mask_rectangularizer = RectangularizeMasks("min")
         self.max_shift_fraction = max_shift_fraction
+        # prediction.py:59-64: pixel shifts, several patch groups per prompt; its numpy stream is its own (seed 0), its torch.manual_seed(0) the one above
+        self.multi_patch_shifter = MultiShiftPatchesAndMask(patch_size=self.patch_size, max_shift_fraction=max_shift_fraction, padding_mode="constant",
+                                                            allow_fractional_shifts=True)
         self.keypoint_predictor = keypoint_predictor
         if keypoint_predictor is not None:
             self.load_predictor(keypoint_predictor_load_path, model=keypoint_predictor)

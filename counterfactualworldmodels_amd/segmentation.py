@@ -19,6 +19,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .perturbation import multi_shift_rows
 from .prediction import PredictorBasedGenerator, _RectBatch
 from .sampling import FlowSampleFilter, RotatedTableEnergyMaskingGenerator, boltzmann
 
@@ -265,6 +266,78 @@ class FlowGenerator(PredictorBasedGenerator):
             self.max_shift_fraction = max_shift_fraction
         y_mocos = self.predict_counterfactual_videos(x, active_patches, passive_patches, shifts, num_samples, sample_batch_size, fix_passive,
                                                      frame, **kwargs)
+        return y_mocos, self.predict_flow(y_mocos, backward=backward, iters=raft_iters)
+
+    # ---- multi-shift counterfactuals: K patch groups per prompt, each moved by its own pixel shift (perturbation.py:644-779) ----------
+    def _multi_shift_table(self, shifts, K):
+        """[S',K,2] pixel shifts from K pairs (S' = 1: shared by the samples), S lists of K pairs, or a [2,K] / [2,K,S] array or tensor; each
+        sample's sequence is normalised as the shifter normalises its `shift_sequence` (one pair broadcasts over the K steps)."""
+        shifter = self.multi_patch_shifter
+        shifter.set_num_shifts(K)
+        if hasattr(shifts, "shape"):
+            arr = shifts.detach().cpu().numpy() if torch.is_tensor(shifts) else np.asarray(shifts)
+            assert arr.ndim in (2, 3) and arr.shape[0] == 2, arr.shape
+            per_sample = [arr] if arr.ndim == 2 else [arr[..., s] for s in range(arr.shape[-1])]
+        else:
+            seq = list(shifts)
+            nested = isinstance(seq[0], (list, tuple, np.ndarray)) and isinstance(seq[0][0], (list, tuple, np.ndarray))
+            per_sample = seq if nested else [seq]
+        return np.array([shifter._preprocess_shifts_sequence(s) for s in per_sample], dtype=np.int64).reshape(len(per_sample), K, 2)
+
+    def _multi_shift_batch(self, x, active_patches, shifts, passive_patches, num_samples, fix_passive, frame, row_kwargs) -> _RectBatch:
+        x, fix_passive = self._two_frame_movie(x, fix_passive)
+        self.set_input(x)
+        B = x.shape[0]
+        assert active_patches.dim() in (3, 4), "active_patches is [B,Nt,K] or [B,Nt,K,S], got %s" % (tuple(active_patches.shape),)
+        K = active_patches.size(2)
+        passive = self.get_zeros_mask() if passive_patches is None else passive_patches
+        # the number of samples: the patches' sample axis, else the shifts', else num_samples
+        S = active_patches.size(3) if active_patches.dim() == 4 else (passive.size(-1) if passive.dim() == 3 else None)
+        if shifts is None:  # K random shifts per sample from the shifter's own stream, sample by sample: what S calls of the reference's shifter draw
+            S = num_samples if S is None else S
+            shifter = self.multi_patch_shifter
+            shifter.image_size, shifter.max_shift_fraction = tuple(x.shape[-2:]), self.max_shift_fraction
+            shifter.set_num_shifts(K)
+            table = np.array([shifter._preprocess_shifts_sequence(None) for _ in range(S)], dtype=np.int64).reshape(S, K, 2)
+        else:
+            table = self._multi_shift_table(shifts, K)
+            if S is None:
+                S = table.shape[0] if table.shape[0] > 1 else num_samples
+            if table.shape[0] == 1:
+                table = np.broadcast_to(table, (S, K, 2))
+            assert table.shape[0] == S, (table.shape, S)
+        Nt = active_patches.size(1)
+        # '(b s)' rows, step-major tables: points [R,K,Nt] (moved = the 0s of active_patches), one base mask per row (the passive patches)
+        points = torch.logical_not(active_patches.bool())
+        points = points.permute(0, 3, 2, 1) if points.dim() == 4 else points.permute(0, 2, 1)[:, None].expand(-1, S, -1, -1)
+        passive = passive.permute(0, 2, 1) if passive.dim() == 3 else passive[:, None].expand(-1, S, -1)
+        x_shift, mask_shift = multi_shift_rows(x, points.reshape(B * S, K, Nt), passive.reshape(B * S, 1, Nt), np.broadcast_to(table[None], (B, S, K, 2)),
+                                               self.patch_size[-1], frame, fix_passive=fix_passive, samples_per_movie=S)
+        self.shifts = [np.array(table[s]) for _ in range(B) for s in range(S)]
+        mask_shift = self.mask_rectangularizer(mask_shift)
+        batch = _RectBatch(x_shift, mask_shift, self.mask_rectangularizer.last_num_masked)
+        for k, v in row_kwargs.items():  # per-movie tensors (the IMU stream) follow their movie's S prompts
+            if torch.is_tensor(v) and v.shape[0] == B and B != batch.rows:
+                v = self.sample_tile(v, S)
+            batch.row_kwargs[k] = v
+        return batch
+
+    def predict_multi_shift_counterfactual_videos(self, x, active_patches, shifts=None, passive_patches=None, num_samples=8, sample_batch_size=8,
+                                                  fix_passive=True, frame=1, **kwargs):
+        """y_mocos [B*S,T,C,H,W] for S counterfactuals per movie in each of which K groups of patches move by K separate PIXEL shifts, applied in
+        order (`MultiShiftPatchesAndMask`).  active_patches [B,Nt,K] (shared by the samples) or [B,Nt,K,S], 0 = moved at step k; passive_patches
+        [B,Nt] / [B,Nt,S], 0 = revealed in place (default: frame 0); shifts: see `_multi_shift_table`.  All B*S prompts come from one kernel
+        call and are rectangularised once; `self.shifts` holds each row's [K,2] shifts."""
+        batch = self._multi_shift_batch(x, active_patches, shifts, passive_patches, num_samples, fix_passive, frame, self._conditioning_kwargs(x, kwargs))
+        y = self._run_rect_batch(batch, rows_per_call=sample_batch_size)
+        self.reset_padding_masks()
+        return y
+
+    def predict_multi_shift_counterfactual_videos_and_flows(self, x, active_patches, shifts=None, passive_patches=None, num_samples=8,
+                                                            sample_batch_size=8, fix_passive=True, frame=1, raft_iters=None, backward=False, **kwargs):
+        """(y_mocos [B*S,T,C,H,W], flow_mocos [B*S,T-1,2,H,W]): `predict_multi_shift_counterfactual_videos`, then the flow model."""
+        y_mocos = self.predict_multi_shift_counterfactual_videos(x, active_patches, shifts, passive_patches, num_samples, sample_batch_size, fix_passive,
+                                                                 frame, **kwargs)
         return y_mocos, self.predict_flow(y_mocos, backward=backward, iters=raft_iters)
 
     # ---- statistics over the flow samples (segmentation.py:250-276, 479-547): device kernels, see flowstats.py ----------

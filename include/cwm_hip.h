@@ -284,6 +284,35 @@ CWM_API int cwm_shift_prompts(const float* x_dev, int B, int T, int C, int H, in
                       const uint8_t* active_dev, const uint8_t* masks_dev, const int32_t* shifts_dev, float* x_out_dev,
                       uint8_t* mask_out_dev, void* stream);
 
+/* Multi-shift prompts (0.10.3): K steps per prompt, each moving ITS OWN set of patches of frame `frame` by ITS OWN pixel shift, for R = B*S prompts at once.
+ * replaces: MultiShiftPatchesAndMask.forward (perturbation.py:644-779; the generator's `multi_patch_shifter`, prediction.py:59-64) = K rounds of
+ *           ShiftPatchesAndMask.perturb in fractional mode (:227-289: pad / centre-crop / patchify / blend of the whole frame per step), looped per sample,
+ *           BEFORE the mask rectangulariser (host).
+ * Tables, one row per prompt i = b*S + s ('(b s)' order; prompt i reads movie i / S), Nt = T (H/P) (W/P) tokens, n = (H/P)(W/P):
+ *   points_dev [R,K,Nt] uint8  A_k: non-zero = this patch is moved at step k (the reference's perturbation_points_sequence[i,:,k]; only frame `frame` moves).
+ *                              STEP-MAJOR, not the reference's [R,Nt,K]: adjacent threads handle adjacent cells of one step, so a wave's reads of a step are
+ *                              consecutive bytes instead of bytes K apart.
+ *   masks_dev  [R,mask_steps,Nt] uint8  M_k: non-zero = masked (mask_sequence[i,:,k]); mask_steps = K, or 1 for one base mask shared by every step.
+ *                              NULL = the reference's call without points (A_k := ~M_k, no base mask: pass ~M_k as points_dev).
+ *   shifts_dev [R,K,2] int32   (sy_k, sx_k) in PIXELS, any sign, not tied to P.  max_abs_shift is the caller's bound on |s| over the table (the library does
+ *                              not read device tables on the host); it must be < min(H, W).  The kernels test every access against the grid and the image
+ *                              whatever the table holds.
+ * With my_k = sign(sy_k) (|sy_k| / P) (truncated toward zero: sy = -3, P = 8 gives 0), mx_k likewise, f = frame:
+ *   mask:   shifted_k[t,pi,pj] = !A_k[f, pi - my_k, pj - mx_k] for t == f (1 if that cell is outside the grid), !A_k[t,pi,pj] for t != f;
+ *           step_k = (M_k | A_k) & shifted_k with masks_dev, shifted_k without;  mask_out [R,Nt] = AND_k step_k (visible if any step leaves it visible).
+ *   frames: x_out [R,T,C,H,W]; frames t != f are copies.  For pixel (y, x) of frame f keep a position (cy, cx) = (y, x) and walk k = K .. 1: if the cell
+ *           (cy / P - my_k, cx / P - mx_k) is inside the grid and A_k is set there in frame f, (cy, cx) -= (sy_k, sx_k); a position that leaves the image
+ *           makes the pixel 0 (the reference's constant padding; only the sub-patch remainder at a border does that).  The output is the input pixel at the
+ *           final position: steps compose in order, a later step wins where destinations overlap, and the result is bit-exact.
+ * fix_passive: 0 = the movie as given, 1 = every output frame reads frame 0 (make_static_movie, prediction.py:731-739).  Requires W % 4 == 0, H % P == 0,
+ * W % P == 0, 1 <= K <= 8, 16-byte aligned frames; a violation is CWM_ERR_INVALID and nothing is launched.  x_out_dev or mask_out_dev may be NULL (x_dev too
+ * with x_out_dev), as in cwm_shift_prompts.  K = 1 with a whole-patch shift is cwm_shift_prompts with active = !A, masks = M, fix_passive 0 / 1.
+ * Not reproduced from the reference: `_check_shapes` assigning to the read-only property `num_shifts` (:668-682 against :171-175; forward cannot run as
+ * written), and `m_seq.expand(1, 1, num_shifts)` (:709) failing for a [B,N] mask with [B,N,K] points (mask_steps = 1 here).  Asynchronous on `stream`. */
+CWM_API int cwm_multi_shift_prompts(const float* x_dev, int B, int T, int C, int H, int W, int P, int frame, int S, int K, int fix_passive,
+                            const uint8_t* points_dev, const uint8_t* masks_dev, int mask_steps, const int32_t* shifts_dev, int max_abs_shift,
+                            float* x_out_dev, uint8_t* mask_out_dev, void* stream);
+
 /* ---- flow-sample statistics: the reductions over the S counterfactual flow samples -------------
  * flows: fp32 device tensor addressed as flows[b*strides[0] + c*strides[1] + y*strides[2] + x*strides[3] + s*strides[4]]
  * (elements), so both the reference's [B,C,H,W,S] view and the sample-major [(b s),C,H,W] batch the flow model emits work
