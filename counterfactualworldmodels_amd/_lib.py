@@ -173,6 +173,29 @@ def new_raft_forward_args() -> CwmRaftForwardArgs:
     return a
 
 
+class CwmRaftForwardExArgs(C.Structure):
+    """include/cwm_hip.h cwm_raft_forward_ex_args (0.10.4): the frozen cwm_raft_forward_args as `base`, the warm start and the per-iteration outputs"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", CwmRaftForwardArgs),
+        ("flow_init_dev", C.c_void_p),
+        ("flow_init_stride_b", C.c_int64),
+        ("flow_init_stride_t", C.c_int64),
+        ("flow_init_stride_c", C.c_int64),
+        ("flow_iters_dev", C.c_void_p),
+        ("flow_iters_stride_i", C.c_int64),
+        ("head_iters_dev", C.c_void_p),
+        ("head_iters_stride_i", C.c_int64),
+    ]
+
+
+def new_raft_forward_ex_args() -> CwmRaftForwardExArgs:
+    a = CwmRaftForwardExArgs()
+    a.struct_size = C.sizeof(CwmRaftForwardExArgs)
+    a.base.struct_size = C.sizeof(CwmRaftForwardArgs)
+    return a
+
+
 class CwmDevConvSrc(C.Structure):
     _fields_ = [
         ("p", C.c_void_p),
@@ -378,6 +401,7 @@ SIGNATURES = {
     "cwm_raft_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "cwm_raft_missing_weights": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "cwm_raft_forward": (C.c_int, [C.c_void_p, C.POINTER(CwmRaftForwardArgs)]),
+    "cwm_raft_forward_ex": (C.c_int, [C.c_void_p, C.POINTER(CwmRaftForwardExArgs)]),
     "cwm_raft_corr_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_raft_convex_upsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_raft_head_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

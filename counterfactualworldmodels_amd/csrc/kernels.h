@@ -347,6 +347,8 @@ int launch_instnorm_stats(const float* x, int n_img, int HW, int C, float eps, f
 int launch_residual_join(const ConvSrc& X, const ConvSrc& Y, int n_img, int HW, float* out, hipStream_t s);
 int launch_cnet_split(const float* cn, int64_t M, float* h, float* x, hipStream_t s);
 int launch_coords_init(float* coords, int64_t M, int h8, int w8, hipStream_t s);
+// coords = grid + init (the warm start): element (c, y, x) of pair (g, t) = (pr / ppg, pr % ppg) of the planar field at init[g * sb + t * st + c * sc + y * w8 + x]
+int launch_coords_init_flow(float* coords, int P, int ppg, int h8, int w8, const float* init, int64_t sb, int64_t st, int64_t sc, hipStream_t s);
 int launch_corr(const float* f1, const float* f2, int P, int N, int D, float* corr, hipStream_t s);
 int launch_corr_pool(const float* in, int64_t maps, int h, int w, float* out, hipStream_t s);
 int launch_corr_lookup(const CorrLookupParams& p, int planes, hipStream_t s);

@@ -146,6 +146,18 @@ __global__ void coords_init_kernel(float* coords, int64_t M, int h8, int w8) {
     }
 }
 
+// The warm start (raft_model.py:241-242): coords1 = grid + flow_init.  Element (c, y, x) of pair pr = (g, t) of the planar init field is at
+// init[g * sb + t * st + c * sc + y * w8 + x] (a stride of 0 shares one field); one thread per low-resolution pixel, one float2 store of (x, y).
+__global__ void coords_init_flow_kernel(float* coords, int64_t M, int h8, int w8, int ppg, const float* init, int64_t sb, int64_t st, int64_t sc) {
+    const int64_t hw = (int64_t)h8 * w8;
+    for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (int64_t)gridDim.x * blockDim.x) {
+        const int pr = (int)(m / hw), r = (int)(m - (int64_t)pr * hw);
+        const int g = pr / ppg, t = pr - g * ppg;
+        const float* f = init + g * sb + t * st + r;
+        reinterpret_cast<float2*>(coords)[m] = make_float2((float)(r % w8) + f[0], (float)(r / w8) + f[sc]);
+    }
+}
+
 // corr[p][i][j] = <f1[p][i], f2[p][j]> / sqrt(256), fp32 FMA (CorrBlock.corr); 64 x 64 tiles, 4 x 4 per thread
 __global__ void __launch_bounds__(256) corr_kernel(const float* f1, const float* f2, int N, int D, float scale, float* corr) {
     __shared__ float As[16][64 + 4];
@@ -451,6 +463,13 @@ int launch_cnet_split(const float* cn, int64_t M, float* h, float* x, hipStream_
 
 int launch_coords_init(float* coords, int64_t M, int h8, int w8, hipStream_t s) {
     hipLaunchKernelGGL(coords_init_kernel, dim3(grid_for(M)), dim3(256), 0, s, coords, M, h8, w8);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_coords_init_flow(float* coords, int P, int ppg, int h8, int w8, const float* init, int64_t sb, int64_t st, int64_t sc, hipStream_t s) {
+    const int64_t M = (int64_t)P * h8 * w8;
+    hipLaunchKernelGGL(coords_init_flow_kernel, dim3(grid_for(M)), dim3(256), 0, s, coords, M, h8, w8, ppg, init, sb, st, sc);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -4,7 +4,8 @@
 // GEMM on launch_gemm whose fp32 epilogue writes straight into a channel slice of an NHWC buffer.  The call chooses the arithmetic of these
 // convolutions (cwm_raft_forward_args.mode): parity (split-bf16 operands, planes = 2) or fast (one bf16 plane per operand, planes = 1);
 // everything between them -- norm statistics, residual join, correlation, lookup, coordinates, GRU update, upsampling -- is fp32 in both.  The mask head and
-// the upsampling run once, after the last iteration (the reference computes them every iteration and returns the last).  So does the optional
+// the upsampling run once, after the last iteration (the reference computes them every iteration and returns the last), unless a call asks for
+// every iteration's prediction (cwm_raft_forward_ex: flow_iters_dev / head_iters_dev; the same entry point takes the warm start, flow_init_dev).  So does the optional
 // output head (raft_model.py:152-159, output_dim = 1: the keypoint predictor): output_block.0 as one more 3x3 convolution, then the 256 -> 1
 // projection and the one-channel convex upsampling as kernels of their own (raft_kernels.hip).
 #include <stddef.h>
@@ -286,7 +287,17 @@ int run_encoder(cwm_raft_model* m, const Encoder& e, const ImageSrc& image, int 
     return run_conv(m, e.conv2, im2col_of(a), n, h, w, m->enc_A, out, e.conv2.L.N, planes, s);
 }
 
-int forward(cwm_raft_model* m, const cwm_raft_forward_args& a) {
+// What cwm_raft_forward_ex adds to a forward; all null: the plain forward of cwm_raft_forward, launch for launch.
+struct ForwardExtras {
+    const float* init = nullptr;  // flow_init: coords1 = grid + init
+    int64_t init_sb = 0, init_st = 0, init_sc = 0;
+    float* flow_iters = nullptr;  // flow_up of iteration i at + i * flow_iters_si, addressed inside with the flow strides of the call
+    int64_t flow_iters_si = 0;
+    float* head_iters = nullptr;  // the upsampled output_block(net) of iteration i, likewise with the head strides
+    int64_t head_iters_si = 0;
+};
+
+int forward(cwm_raft_model* m, const cwm_raft_forward_args& a, const ForwardExtras& ex) {
     hipStream_t s = (hipStream_t)a.stream;
     const int planes = a.mode == CWM_MODE_FAST ? 1 : 2;
     const int ppg = a.pairs > 0 ? a.pairs : 1;
@@ -329,11 +340,65 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a) {
     lp.M = M;
     lp.A = m->corrA;
     lp.Kpad = kLookupKpad;
-    if ((rc = launch_coords_init(m->coords, M, h8, w8, s))) return rc;
+    if (ex.init) {
+        if ((rc = launch_coords_init_flow(m->coords, P, ppg, h8, w8, ex.init, ex.init_sb, ex.init_st, ex.init_sc, s))) return rc;
+    } else if ((rc = launch_coords_init(m->coords, M, h8, w8, s))) {
+        return rc;
+    }
     ConvSrc flow_src;
     memset(&flow_src, 0, sizeof(flow_src));
     flow_src.C = 2;
     flow_src.coords = m->coords;
+    const bool per_iter = ex.flow_iters || ex.head_iters;
+    // mask = 0.25 * mask.2(relu(mask.0(net))) (when `with_mask`), then the convex upsampling of the current flow to `flow_out` and / or of
+    // output_block(net) to `head_out` (either may be null), both addressed with the strides of the call; `flow_low`: coords1 - coords0, contiguous
+    auto outputs = [&](float* flow_out, float* head_out, float* flow_low, bool with_mask) -> int {
+        int rc;
+        if (with_mask) {
+            // `fh` is free once the flow head's second convolution has read it
+            if ((rc = run_conv(m, m->mask0, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, planes, s))) return rc;
+            if ((rc = run_conv(m, m->mask2, im2col_of(src_of(m->fh, 256, nullptr, 1)), P, h8, w8, m->updA, m->mask, 576, planes, s))) return rc;
+        }
+        if (flow_out) {
+            ConvexUpParams up;
+            memset(&up, 0, sizeof(up));
+            up.coords = m->coords;
+            up.mask = m->mask;
+            up.mask_ld = 576;
+            up.mask_scale = 0.25f;
+            up.P = P;
+            up.ppg = ppg;
+            up.h8 = h8;
+            up.w8 = w8;
+            up.out = flow_out;
+            up.out_sb = a.flow_stride_b;
+            up.out_st = a.flow_stride_t;
+            up.out_sc = a.flow_stride_c;
+            if ((rc = launch_convex_upsample(up, s))) return rc;
+        }
+        if (flow_low && (rc = launch_flow_low(m->coords, P, h8, w8, flow_low, s))) return rc;
+        if (head_out) {
+            // out = output_block.2(relu(output_block.0(net))), upsampled with the same mask in place of the flow (raft_model.py:257-267).  `fh` is free
+            // once mask.2 has read it, and `d` (the flow head's delta) once this iteration's flow update has: the projected map goes there.
+            if ((rc = run_conv(m, m->out0, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, planes, s))) return rc;
+            if ((rc = launch_head_project(m->fh, 256, m->raw[kHeadKeys[2]].dev, m->raw[kHeadKeys[3]].dev, M, m->d, s))) return rc;
+            ConvexUp1Params u1;
+            memset(&u1, 0, sizeof(u1));
+            u1.value = m->d;
+            u1.mask = m->mask;
+            u1.mask_ld = 576;
+            u1.mask_scale = 0.25f;
+            u1.P = P;
+            u1.ppg = ppg;
+            u1.h8 = h8;
+            u1.w8 = w8;
+            u1.out = head_out;
+            u1.out_sb = a.head_stride_b;
+            u1.out_st = a.head_stride_t;
+            if ((rc = launch_convex_upsample1(u1, s))) return rc;
+        }
+        return 0;
+    };
     for (int it = 0; it < a.iters; ++it) {
         // BasicMotionEncoder
         if ((rc = launch_corr_lookup(lp, planes, s))) return rc;
@@ -360,47 +425,14 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a) {
         if ((rc = run_conv(m, m->fh1, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, planes, s))) return rc;
         if ((rc = run_conv(m, m->fh2, im2col_of(src_of(m->fh, 256, nullptr, 1)), P, h8, w8, m->updA, m->d, 16, planes, s))) return rc;
         if ((rc = launch_flow_update(m->coords, m->d, 16, M, s))) return rc;
+        // the per-iteration outputs (raft_model.py:257-269 keeps every iteration's flow_up): the mask head and the upsampling of this iteration's state
+        if (per_iter && (rc = outputs(ex.flow_iters ? ex.flow_iters + it * ex.flow_iters_si : nullptr,
+                                      ex.head_iters ? ex.head_iters + it * ex.head_iters_si : nullptr, nullptr, true)))
+            return rc;
     }
-    // mask = 0.25 * mask.2(relu(mask.0(net))), once; convex upsampling of the last flow (skipped when only the head output is asked for)
-    if ((rc = run_conv(m, m->mask0, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, planes, s))) return rc;
-    if ((rc = run_conv(m, m->mask2, im2col_of(src_of(m->fh, 256, nullptr, 1)), P, h8, w8, m->updA, m->mask, 576, planes, s))) return rc;
-    ConvexUpParams up;
-    memset(&up, 0, sizeof(up));
-    up.coords = m->coords;
-    up.mask = m->mask;
-    up.mask_ld = 576;
-    up.mask_scale = 0.25f;
-    up.P = P;
-    up.ppg = ppg;
-    up.h8 = h8;
-    up.w8 = w8;
-    up.out = a.flow_dev;
-    up.out_sb = a.flow_stride_b;
-    up.out_st = a.flow_stride_t;
-    up.out_sc = a.flow_stride_c;
-    if (a.flow_dev && (rc = launch_convex_upsample(up, s))) return rc;
-    if (a.flow_low_dev && (rc = launch_flow_low(m->coords, P, h8, w8, a.flow_low_dev, s))) return rc;
-    if (a.head_dev) {
-        // out = output_block.2(relu(output_block.0(net))), upsampled with the same mask in place of the flow (raft_model.py:257-267).  `fh` is free
-        // once mask.2 has read it, and `d` (the flow head's delta) once the last flow update has: the projected map goes there.
-        if ((rc = run_conv(m, m->out0, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, planes, s))) return rc;
-        if ((rc = launch_head_project(m->fh, 256, m->raw[kHeadKeys[2]].dev, m->raw[kHeadKeys[3]].dev, M, m->d, s))) return rc;
-        ConvexUp1Params u1;
-        memset(&u1, 0, sizeof(u1));
-        u1.value = m->d;
-        u1.mask = m->mask;
-        u1.mask_ld = 576;
-        u1.mask_scale = 0.25f;
-        u1.P = P;
-        u1.ppg = ppg;
-        u1.h8 = h8;
-        u1.w8 = w8;
-        u1.out = a.head_dev;
-        u1.out_sb = a.head_stride_b;
-        u1.out_st = a.head_stride_t;
-        if ((rc = launch_convex_upsample1(u1, s))) return rc;
-    }
-    return 0;
+    // Without per-iteration outputs the mask head and the upsampling run once, here, after the last iteration.  With them `mask` already holds the
+    // last iteration's mask: the final outputs read it.
+    return outputs(a.flow_dev, a.head_dev, a.flow_low_dev, !per_iter && (a.flow_dev || a.head_dev));
 }
 
 }  // namespace
@@ -478,33 +510,66 @@ extern "C" int cwm_raft_missing_weights(cwm_raft_model* m, char* buf, int buflen
     return missing;
 }
 
-extern "C" int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* args) {
-    CWM_REQUIRE(m && args, "cwm_raft_forward: null argument");
+namespace {
+
+// The checks and the forward body that cwm_raft_forward and cwm_raft_forward_ex share; `fn`: the entry point named in the messages, `plain`: it is
+// cwm_raft_forward (the messages then do not speak of the ex struct's fields).
+int checked_forward(cwm_raft_model* m, const cwm_raft_forward_args* args, const ForwardExtras& ex, const char* fn, bool plain) {
     // a caller built against the 0.10.0 header (the struct ended at `stream`) or the 0.10.1 one (at `head_stride_c`) passes that size: the fields
     // appended since read as zero (no head; mode 0 = parity)
     cwm_raft_forward_args a_copy;
-    if (int rc = copy_args(a_copy, args, offsetof(cwm_raft_forward_args, stream) + sizeof(void*), "cwm_raft_forward")) return rc;
+    if (int rc = copy_args(a_copy, args, offsetof(cwm_raft_forward_args, stream) + sizeof(void*), "cwm_raft_forward",
+                           plain ? "" : "; this is cwm_raft_forward_ex_args.base.struct_size"))
+        return rc;
     const cwm_raft_forward_args& a = a_copy;
-    if (int rc = cwm_require_device(m->eng.device, "cwm_raft_forward")) return rc;
-    CWM_REQUIRE(a.image1_dev && a.image2_dev && (a.flow_dev || a.head_dev), "cwm_raft_forward: image1, image2 and one of flow / head are required");
-    CWM_REQUIRE(a.batch >= 1 && a.pairs >= 0, "cwm_raft_forward: batch = %d, pairs = %d", a.batch, a.pairs);
-    CWM_REQUIRE(a.height > 0 && a.width > 0 && a.height % 8 == 0 && a.width % 8 == 0, "cwm_raft_forward: H = %d and W = %d must be multiples of 8",
-                a.height, a.width);
+    if (int rc = cwm_require_device(m->eng.device, fn)) return rc;
+    CWM_REQUIRE(a.image1_dev && a.image2_dev, "%s: image1 and image2 are required", fn);
+    CWM_REQUIRE(a.flow_dev || a.head_dev || ex.flow_iters || ex.head_iters,
+                "%s: no output requested: one of flow / head%s is required", fn, plain ? "" : " / flow_iters / head_iters");
+    CWM_REQUIRE(a.batch >= 1 && a.pairs >= 0, "%s: batch = %d, pairs = %d", fn, a.batch, a.pairs);
+    CWM_REQUIRE(a.height > 0 && a.width > 0 && a.height % 8 == 0 && a.width % 8 == 0, "%s: H = %d and W = %d must be multiples of 8", fn, a.height,
+                a.width);
     CWM_REQUIRE(a.height / 8 >= 16 && a.width / 8 >= 16,
-                "cwm_raft_forward: H / 8 = %d and W / 8 = %d must be at least 16 (the coarsest correlation level would have a side of 1)", a.height / 8,
+                "%s: H / 8 = %d and W / 8 = %d must be at least 16 (the coarsest correlation level would have a side of 1)", fn, a.height / 8,
                 a.width / 8);
-    CWM_REQUIRE(a.iters >= 1, "cwm_raft_forward: iters = %d must be >= 1", a.iters);
-    CWM_REQUIRE(a.mode == 0 || a.mode == CWM_MODE_PARITY || a.mode == CWM_MODE_FAST,
-                "cwm_raft_forward: mode = %d must be 0 or CWM_MODE_PARITY (parity) or CWM_MODE_FAST", a.mode);
+    CWM_REQUIRE(a.iters >= 1, "%s: iters = %d must be >= 1", fn, a.iters);
+    CWM_REQUIRE(a.mode == 0 || a.mode == CWM_MODE_PARITY || a.mode == CWM_MODE_FAST, "%s: mode = %d must be 0 or CWM_MODE_PARITY (parity) or CWM_MODE_FAST",
+                fn, a.mode);
     const int planes = a.mode == CWM_MODE_FAST ? 1 : 2;
     const int64_t M = (int64_t)a.batch * std::max(a.pairs, 1) * (a.height / 8) * (a.width / 8);
-    CWM_REQUIRE(M * 2304 * planes < (1ll << 32), "cwm_raft_forward: batch too large (%lld low-resolution pixels): split it", (long long)M);
+    CWM_REQUIRE(M * 2304 * planes < (1ll << 32), "%s: batch too large (%lld low-resolution pixels): split it", fn, (long long)M);
     char buf[256];
     const int missing = cwm_raft_missing_weights(m, buf, sizeof(buf));
-    CWM_REQUIRE(missing == 0, "cwm_raft_forward: %d weights missing (first: %s)", missing, buf);
-    if (a.head_dev)
-        for (const char* k : kHeadKeys) CWM_REQUIRE(m->raw[k].loaded, "cwm_raft_forward: the output head was asked for (head_dev) but %s is not loaded", k);
-    return forward(m, a);
+    CWM_REQUIRE(missing == 0, "%s: %d weights missing (first: %s)", fn, missing, buf);
+    if (a.head_dev || ex.head_iters)
+        for (const char* k : kHeadKeys)
+            CWM_REQUIRE(m->raw[k].loaded, "%s: the output head was asked for (%s) but %s is not loaded", fn, a.head_dev ? "head_dev" : "head_iters_dev", k);
+    return forward(m, a, ex);
+}
+
+}  // namespace
+
+extern "C" int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* args) {
+    CWM_REQUIRE(m && args, "cwm_raft_forward: null argument");
+    return checked_forward(m, args, ForwardExtras(), "cwm_raft_forward", true);
+}
+
+extern "C" int cwm_raft_forward_ex(cwm_raft_model* m, const cwm_raft_forward_ex_args* args) {
+    CWM_REQUIRE(m && args, "cwm_raft_forward_ex: null argument");
+    // the first struct of its name: one size.  (`base` keeps the size rules of cwm_raft_forward_args.)
+    CWM_REQUIRE(args->struct_size == sizeof(cwm_raft_forward_ex_args),
+                "cwm_raft_forward_ex: args->struct_size = %u is not a cwm_raft_forward_ex_args (set it to sizeof(cwm_raft_forward_ex_args) = %zu)",
+                args->struct_size, sizeof(cwm_raft_forward_ex_args));
+    ForwardExtras ex;
+    ex.init = args->flow_init_dev;
+    ex.init_sb = args->flow_init_stride_b;
+    ex.init_st = args->flow_init_stride_t;
+    ex.init_sc = args->flow_init_stride_c;
+    ex.flow_iters = args->flow_iters_dev;
+    ex.flow_iters_si = args->flow_iters_stride_i;
+    ex.head_iters = args->head_iters_dev;
+    ex.head_iters_si = args->head_iters_stride_i;
+    return checked_forward(m, &args->base, ex, "cwm_raft_forward_ex", false);
 }
 
 // ---- stand-alone kernels (kernel tests) -------------------------------------------------------------------------------

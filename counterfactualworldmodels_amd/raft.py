@@ -1,7 +1,7 @@
 """RAFT-large optical flow on the GPU: drop-in for `cwm.models.raft.raft_model.load_raft_model` / `RAFT` (raft_model.py:55-300).
 
 The module keeps the reference's parameter tree (179 state-dict tensors: `fnet`, `cnet`, `update_block`), so checkpoints load unchanged,
-and runs its forward pass in libcwm_hip.so (`cwm_raft_forward`): HIP kernels and GEMMs in parity (split-bf16) arithmetic by default or,
+and runs its forward pass in libcwm_hip.so (`cwm_raft_forward`; `cwm_raft_forward_ex` for a warm start or the per-iteration list): HIP kernels and GEMMs in parity (split-bf16) arithmetic by default or,
 with `mixed_precision=True` / `set_mode("fast")`, with bf16 operands; no PyTorch operator and no CPU fallback.  The configuration is the reference's inference one:
 BasicEncoder fnet (instance norm) and cnet (eval batch norm), 4 correlation levels of radius 4, BasicUpdateBlock with SepConvGRU, convex
 upsampling.
@@ -10,6 +10,7 @@ upsampling.
     flow_model = load_raft_model("raft-large.pth").cuda().eval()
     flows = flow_model(x, iters=24)              # x [B,T,3,H,W] in [0,1] -> [B,T-1,2,H,W] pixels
     flows_back = flow_model(x, backward=True)    # pairs (x[t+1], x[t]), in reversed order
+    flows_warm = flow_model(x, flow_init=f8)     # f8 [B or 1,2,H/8,W/8]: RAFT's warm start, e.g. the previous pair's low-resolution flow
 
 With `output_dim=1` the model owns the reference's `output_block` (raft_model.py:152-159; 183 state-dict tensors) and returns its convex-upsampled
 value in place of the flow: the keypoint predictor of the demo notebook,
@@ -121,8 +122,14 @@ class RAFT(LibraryModule):
     - multiframe (default): `model(x[B,T,3,H,W], iters=24, backward=False)` -> [B,T-1,2,H,W] pixel flows (flow_up of the last iteration);
       x is in [0,1] with scale_inputs=True (in [0,255] otherwise); backward=True computes the pairs (x[t+1], x[t]) and returns them in
       reversed order, as the reference's `flows.insert(0, ...)`.
-    - multiframe=False: `model(image1, image2, iters=24, test_mode=True)` on [B,3,H,W] images in [0,255] -> (coords1 - coords0 [B,2,H/8,W/8],
-      flow_up [B,2,H,W]).
+    - multiframe=False: `model(image1, image2, iters=24, flow_init=None, upsample=True, test_mode=True)` on [B,3,H,W] images in [0,255] ->
+      (coords1 - coords0 [B,2,H/8,W/8], flow_up [B,2,H,W]); with `test_mode=False` the list of every iteration's flow_up (`iters` tensors [B,2,H,W],
+      views of one buffer; the last equals the flow_up above).  `upsample` is ignored, as in the reference.
+    - `flow_init` (both calls; raft_model.py:241-242): RAFT's warm start, a flow [B,2,H/8,W/8] or [1,2,H/8,W/8] in 1/8-resolution pixels (channel 0 = x)
+      added to the initial coordinates; any float dtype (cast to fp32), on the frames' device.  The multi-frame call gives the same field to every
+      pair, also with backward=True, and accepts `test_mode` (its result is the last iteration's flow_up either way, raft_model.py:297).
+    Without `flow_init` and with test_mode=True a call is `cwm_raft_forward`: the mask head and the upsampling run once.  Otherwise it is
+    `cwm_raft_forward_ex`; only test_mode=False makes them run in every iteration.
     `self.iters`, when set, overrides the call's `iters`.  H and W must be multiples of 8 with H/8, W/8 >= 16.
     With `args.output_dim == 1` the 2-channel flow_up above is the 1-channel upsampled `output_block(net)` (raft_model.py:257-267): [B,T-1,1,H,W],
     and (coords1 - coords0, up [B,1,H,W]) from the two-image call.
@@ -181,15 +188,21 @@ class RAFT(LibraryModule):
 
     # ---- C-ABI plumbing (the handle and sync_weights live in _handle.LibraryModule; the library folds the batch norms and packs the
     # convolutions at the next forward.  cwm_raft_* has no per-handle options, lanes or kernel timing: the arithmetic mode travels with each call) -------
-    _ABI = {role: "cwm_raft_" + role for role in ("destroy", "load_weight", "forward")}
+    _ABI = {role: "cwm_raft_" + role for role in ("destroy", "load_weight", "forward", "forward_ex")}
 
     def _create(self, lib, h):
         return lib.cwm_raft_create(C.byref(h))
 
-    def _run(self, x1, x2, B, pairs, H, W, scale, iters, out, out_strides, flow_low=None):
+    def _run(self, x1, x2, B, pairs, H, W, scale, iters, out, out_strides, flow_low=None, flow_init=None, per_iteration=None):
+        """One library forward.  `out` = (pointer,) of the last iteration's output, addressed with `out_strides` (b, t, c), or None.  Without
+        `flow_init` and `per_iteration` the call is `cwm_raft_forward`; with either, `cwm_raft_forward_ex`: `flow_init` [B or 1, 2, H/8, W/8] fp32
+        goes to every pair, `per_iteration` = (pointer, stride between iterations) receives every iteration's output, addressed inside an
+        iteration's block with `out_strides`."""
         dev = x1.device
         self.sync_weights(dev)
-        a = _lib.new_raft_forward_args()
+        extended = flow_init is not None or per_iteration is not None
+        ex = _lib.new_raft_forward_ex_args() if extended else None
+        a = ex.base if extended else _lib.new_raft_forward_args()
         a.image1_dev, a.image2_dev = x1.data_ptr(), x2.data_ptr()
         a.image1_stride_b, a.image1_stride_t, a.image1_stride_c = x1.stride(0), x1.stride(1), x1.stride(2)
         a.image2_stride_b, a.image2_stride_t, a.image2_stride_c = x2.stride(0), x2.stride(1), x2.stride(2)
@@ -198,15 +211,27 @@ class RAFT(LibraryModule):
         a.iters = int(iters)
         a.mode = _lib.mode_id(self.mode)
         if self.output_dim is None:
-            a.flow_dev = out[0]
+            a.flow_dev = out[0] if out is not None else None
             a.flow_stride_b, a.flow_stride_t, a.flow_stride_c = out_strides
         else:  # the head's value is what is upsampled; the flow's own upsampling is not asked for
-            a.head_dev = out[0]
+            a.head_dev = out[0] if out is not None else None
             a.head_stride_b, a.head_stride_t, a.head_stride_c = out_strides
         a.flow_low_dev = _lib.ptr(flow_low)
         a.stream = _lib.current_stream_handle(dev)
+        if flow_init is not None:  # one field for every pair (stride_t = 0), and for every batch row when its batch is 1
+            ex.flow_init_dev = flow_init.data_ptr()
+            ex.flow_init_stride_b = flow_init.stride(0) if flow_init.shape[0] > 1 else 0
+            ex.flow_init_stride_t, ex.flow_init_stride_c = 0, flow_init.stride(1)
+        if per_iteration is not None:
+            if self.output_dim is None:
+                ex.flow_iters_dev, ex.flow_iters_stride_i = per_iteration
+            else:
+                ex.head_iters_dev, ex.head_iters_stride_i = per_iteration
         with torch.cuda.device(dev):
-            self._check(self._fn["forward"](self._handle, C.byref(a)))
+            if extended:
+                self._check(self._fn["forward_ex"](self._handle, C.byref(ex)))
+            else:
+                self._check(self._fn["forward"](self._handle, C.byref(a)))
 
     @staticmethod
     def _frames(x: torch.Tensor) -> torch.Tensor:
@@ -219,42 +244,63 @@ class RAFT(LibraryModule):
             x = x.contiguous()
         return x
 
+    @staticmethod
+    def _flow_init(flow_init, B: int, H: int, W: int, device) -> Optional[torch.Tensor]:
+        """The warm start as the library reads it: fp32 [B or 1, 2, H/8, W/8] on the frames' device with contiguous rows; None stays None."""
+        if flow_init is None:
+            return None
+        want = "[%d,2,%d,%d] or [1,2,%d,%d]" % (B, H // 8, W // 8, H // 8, W // 8)
+        if not torch.is_tensor(flow_init) or not flow_init.is_floating_point():
+            raise RuntimeError("flow_init must be a floating-point tensor %s, got %r" % (want, type(flow_init).__name__ if not torch.is_tensor(flow_init) else flow_init.dtype))
+        if flow_init.dim() != 4 or flow_init.shape[0] not in (1, B) or tuple(flow_init.shape[1:]) != (2, H // 8, W // 8):
+            raise RuntimeError("flow_init must be %s for frames [%d,3,%d,%d], got %s" % (want, B, H, W, tuple(flow_init.shape)))
+        if flow_init.device != device:
+            raise RuntimeError("flow_init %s is on %s but the frames [%d,3,%d,%d] are on %s" % (tuple(flow_init.shape), flow_init.device, B, H, W, device))
+        f = flow_init.detach().float()
+        if f.stride(-1) != 1 or f.stride(-2) != f.shape[-1]:
+            f = f.contiguous()
+        return f
+
     @torch.no_grad()
     def _forward_two_images(self, image1, image2, iters=24, flow_init=None, upsample=True, test_mode=True, **kwargs):
-        """raft_model.py:205-274 with test_mode=True: (coords1 - coords0, flow_up) for images in [0,255]."""
-        if flow_init is not None:
-            raise NotImplementedError("flow_init is not supported")
-        if not test_mode:
-            raise NotImplementedError("test_mode=False (the per-iteration flow list of training) is not supported")
+        """raft_model.py:199-274: for images in [0,255], (coords1 - coords0, flow_up) with test_mode=True and the list of every iteration's flow_up
+        with test_mode=False; `flow_init` [B or 1, 2, H/8, W/8] (1/8-resolution pixels) is added to the initial coordinates."""
         if self.iters is not None:
             iters = self.iters
         x1, x2 = self._frames(image1), self._frames(image2)
         if x1.dim() != 4 or x1.shape != x2.shape or x1.shape[1] != 3:
             raise RuntimeError("expected two [B,3,H,W] images of one shape, got %s and %s" % (tuple(image1.shape), tuple(image2.shape)))
         B, _, H, W = x1.shape
+        init = self._flow_init(flow_init, B, H, W, x1.device)
+        v1, v2 = x1.unsqueeze(1), x2.unsqueeze(1)
+        if not test_mode:  # every iteration's prediction: one buffer [iters,B,C,H,W], returned as the list of its views
+            ups = torch.empty(max(int(iters), 0), B, self.output_dim or 2, H, W, device=x1.device)
+            self._run(v1, v2, B, 1, H, W, 1.0, iters, None, (ups.stride(1), 0, ups.stride(2)), flow_init=init, per_iteration=(ups.data_ptr(), ups.stride(0)))
+            return list(ups.unbind(0))
         up = torch.empty(B, self.output_dim or 2, H, W, device=x1.device)
         low = torch.empty(B, 2, H // 8, W // 8, device=x1.device)
-        v1, v2 = x1.unsqueeze(1), x2.unsqueeze(1)
-        self._run(v1, v2, B, 1, H, W, 1.0, iters, (up.data_ptr(),), (up.stride(0), 0, up.stride(1)), flow_low=low)
+        self._run(v1, v2, B, 1, H, W, 1.0, iters, (up.data_ptr(),), (up.stride(0), 0, up.stride(1)), flow_low=low, flow_init=init)
         return low, up
 
     @torch.no_grad()
     def forward(self, *args, **kwargs):
         if not self.multiframe:
             return self._forward_two_images(*args, **kwargs)
-        x = args[0]
-        iters = args[1] if len(args) > 1 else kwargs.get("iters", 24)
-        if kwargs.get("flow_init") is not None:
-            raise NotImplementedError("flow_init is not supported")
+        return self._forward_multiframe(*args, **kwargs)
+
+    def _forward_multiframe(self, x, iters=24, flow_init=None, upsample=True, test_mode=True, backward=False, **kwargs):
+        """raft_model.py:276-300: the reference hands everything after x to every pair's two-image call (:297), so the arguments are those of
+        `_forward_two_images`, plus `backward`."""
         if self.iters is not None:
             iters = self.iters
-        backward = kwargs.get("backward", False)
         if x.dim() != 5:
             raise RuntimeError("RAFT (multiframe) expects x [B,T,3,H,W], got %s" % (tuple(x.shape),))
         x = self._frames(x)
         B, T, Cc, H, W = x.shape
         if Cc != 3:
             raise RuntimeError("RAFT expects 3-channel frames, got %s" % (tuple(x.shape),))
+        # test_mode: either way the reference keeps `[-1]` of what the pair's call returns, the last iteration's flow_up: nothing to choose here
+        init = self._flow_init(flow_init, B, H, W, x.device)  # the same field for every pair, forward or backward
         scale = 255.0 if self.scale_inputs else 1.0
         if T == 1:  # a single frame is repeated (raft_model.py:287-288): the pair (x0, x0)
             first, second, pairs = x, x, 1
@@ -264,9 +310,9 @@ class RAFT(LibraryModule):
         if backward:  # pairs (x[t+1], x[t]), stored at index pairs - 1 - t
             first, second = second, first
             ptr = out.data_ptr() + (pairs - 1) * out.stride(1) * out.element_size()
-            self._run(first, second, B, pairs, H, W, scale, iters, (ptr,), (out.stride(0), -out.stride(1), out.stride(2)))
+            self._run(first, second, B, pairs, H, W, scale, iters, (ptr,), (out.stride(0), -out.stride(1), out.stride(2)), flow_init=init)
         else:
-            self._run(first, second, B, pairs, H, W, scale, iters, (out.data_ptr(),), (out.stride(0), out.stride(1), out.stride(2)))
+            self._run(first, second, B, pairs, H, W, scale, iters, (out.data_ptr(),), (out.stride(0), out.stride(1), out.stride(2)), flow_init=init)
         return out
 
 

@@ -462,6 +462,35 @@ typedef struct cwm_raft_forward_args {
 } cwm_raft_forward_args;
 CWM_API int cwm_raft_forward(cwm_raft_model* m, const cwm_raft_forward_args* args);
 
+/* The same forward with RAFT's warm start and its per-iteration outputs (0.10.4).
+ * replaces: the `flow_init` and `test_mode=False` arguments of `RAFT._forward_two_images` (raft_model.py:199-274): `coords1 = coords1 + flow_init`
+ * (raft_model.py:241-242) and the list `flow_predictions` of every iteration's upsampled prediction (raft_model.py:244-274); through
+ * raft_model.py:297 the multi-frame `RAFT.forward` hands both to every pair.
+ * With the three optional pointers NULL this is cwm_raft_forward(m, &args->base), launch for launch: the mask head and the upsampling run once, after
+ * the last iteration.  With flow_iters_dev or head_iters_dev they run in every iteration (the reference always does), and the final outputs of
+ * `base`, when asked for, are produced as well.  cwm_raft_forward_args is frozen; what is added to the forward is added here. */
+typedef struct cwm_raft_forward_ex_args {
+    uint32_t struct_size;            /* sizeof(cwm_raft_forward_ex_args); anything else: CWM_ERR_INVALID naming struct_size */
+    cwm_raft_forward_args base;      /* as for cwm_raft_forward, base.struct_size rules included; base.flow_dev and base.head_dev may both be NULL when
+                                      * a per-iteration output is given; base.flow_low_dev receives coords1 - coords0 with the init included (the
+                                      * reference's first return value); base.mode chooses parity or fast */
+    /* in, optional: the initial flow in 1/8-resolution pixels, channel 0 = x: element (c, y, x) of pair (b, t) at flow_init_dev + b*flow_init_stride_b +
+     * t*flow_init_stride_t + c*flow_init_stride_c + y*(W/8) + x, rows of W/8 contiguous.  A stride may be 0: one field for all pairs (stride_t) or for
+     * all batch rows (stride_b) */
+    const float* flow_init_dev;
+    int64_t flow_init_stride_b, flow_init_stride_t, flow_init_stride_c;
+    /* out, optional: flow_up of iteration i (0 <= i < base.iters) in the block at flow_iters_dev + i*flow_iters_stride_i, addressed inside the block
+     * as base.flow_dev is: with base.flow_stride_b / _t / _c (a negative _t included) */
+    float* flow_iters_dev;
+    int64_t flow_iters_stride_i;
+    /* out, optional: the convex-upsampled output_block(net) of iteration i at head_iters_dev + i*head_iters_stride_i, addressed inside the block
+     * with base.head_stride_b / _t / _c.  Needs the four output_block weights: otherwise CWM_ERR_INVALID naming the first missing key, as head_dev */
+    float* head_iters_dev;
+    int64_t head_iters_stride_i;
+} cwm_raft_forward_ex_args;
+/* At least one of base.flow_dev, base.head_dev, flow_iters_dev, head_iters_dev must be given. */
+CWM_API int cwm_raft_forward_ex(cwm_raft_model* m, const cwm_raft_forward_ex_args* args);
+
 /* Stand-alone RAFT kernels (kernel tests; the same launches as the model):
  *   cwm_raft_corr_lookup      fmap1 / fmap2 [P, h8, w8, 256] (NHWC), coords [P, h8, w8, 2] (x, y) -> out [P, h8, w8, 324]: CorrBlock (corr.py:12-60)
  *                             built and indexed at coords, feature l*81 + a*9 + b sampled at (x / 2^l + a - 4, y / 2^l + b - 4).  Synchronises.

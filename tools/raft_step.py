@@ -6,7 +6,11 @@ once, ~122 GFLOP per pair), one JSON line per batch size.  For the kernel split 
 
 `--output-dim 1` times the keypoint predictor instead (the model with the output head: one more 3x3 convolution, the 256 -> 1 projection and a
 one-channel convex upsampling in place of the flow's two-channel one); its FLOPs add the head's convolution and projection.
-`--mode fast` times the bf16-operand mode instead of parity; every line names its mode."""
+`--mode fast` times the bf16-operand mode instead of parity; every line names its mode.
+`--flow-init` times a warm-started forward (`flow_init`: one seeded [1,2,H/8,W/8] field for every pair; one more small launch).
+`--per-iteration` times the list form (the two-image call with `test_mode=False`: the mask head and the upsampling in every iteration, +0.69 GFLOP
+and one full-resolution write each) and prints, per iteration, max-abs and mean-abs of (prediction i - prediction i-1) in pixels: how fast the
+flow settles, which is what `set_raft_iters` is chosen from."""
 import argparse
 import json
 import os
@@ -30,6 +34,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--output-dim", type=int, default=None, choices=[1], help="time the keypoint forward (the output head) instead of the flow forward")
     ap.add_argument("--mode", default="parity", choices=["parity", "fast"], help="arithmetic of the convolutions (RAFT.set_mode)")
+    ap.add_argument("--flow-init", action="store_true", help="time a warm-started forward (flow_init)")
+    ap.add_argument("--per-iteration", action="store_true", help="time the list form (test_mode=False) and print how much each iteration moves the prediction")
     args = ap.parse_args()
     H, W = args.size
     m = RAFT(_args(output_dim=args.output_dim)) if args.output_dim else RAFT()
@@ -40,19 +46,40 @@ def main():
     flops = C.raft_algorithmic_flops(H, W, args.iters)
     if args.output_dim:  # output_block.0 (3x3, 128 -> 256) and output_block.2 (256 -> output_dim) at 1/8 resolution
         flops += 2.0 * (H // 8) * (W // 8) * 256 * (128 * 9 + args.output_dim)
+    if args.per_iteration:  # the mask head (3x3, 128 -> 256, and 1x1, 256 -> 576) in every iteration instead of once; with the head, output_block too
+        per_it = 2.0 * (H // 8) * (W // 8) * 256 * (128 * 9 + 576)
+        if args.output_dim:
+            per_it += 2.0 * (H // 8) * (W // 8) * 256 * (128 * 9 + args.output_dim)
+        flops += (args.iters - 1) * per_it
+    init = None
+    if args.flow_init:
+        g = torch.Generator().manual_seed(2)
+        init = (4.0 * torch.rand(1, 2, H // 8, W // 8, generator=g) - 2.0).cuda()
     for B in args.batch:
         x = torch.from_numpy(S.raft_frames(B, H, W, 1)).cuda()
+        if args.per_iteration:
+            x1, x2 = (x[:, 0] * 255.0).contiguous(), (x[:, 1] * 255.0).contiguous()
+
+            def run():
+                return m._forward_two_images(x1, x2, iters=args.iters, flow_init=init, test_mode=False)
+        else:
+            def run():
+                return m(x, iters=args.iters, flow_init=init)
         for _ in range(args.warmup):
-            m(x, iters=args.iters)
+            run()
         torch.cuda.synchronize()
         times = []
         for _ in range(args.steps):
             t0 = time.perf_counter()
-            m(x, iters=args.iters)
+            out = run()
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
         ms = 1e3 * float(np.median(times))
-        print(json.dumps({"output": "keypoints" if args.output_dim else "flow", "mode": m.mode, "batch": B, "size": [H, W], "iters": args.iters, "ms_median": round(ms, 3), "ms_min": round(1e3 * min(times), 3),
+        if args.per_iteration:
+            for i in range(1, len(out)):
+                d = (out[i] - out[i - 1]).abs()
+                print(json.dumps({"batch": B, "iteration": i + 1, "step_max_abs_px": round(d.max().item(), 4), "step_mean_abs_px": round(d.mean().item(), 5)}), flush=True)
+        print(json.dumps({"output": "keypoints" if args.output_dim else "flow", "mode": m.mode, "flow_init": bool(args.flow_init), "per_iteration": bool(args.per_iteration), "batch": B, "size": [H, W], "iters": args.iters, "ms_median": round(ms, 3), "ms_min": round(1e3 * min(times), 3),
                           "pairs_per_s": round(B / (ms / 1e3), 2), "gflop_per_pair": round(flops / 1e9, 2),
                           "tflops": round(B * flops / (ms / 1e3) / 1e12, 2)}), flush=True)
 
