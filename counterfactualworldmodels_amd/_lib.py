@@ -308,6 +308,86 @@ def new_dev_gather_args() -> CwmDevGatherArgs:
     return a
 
 
+DEV_CONJ_VALU, DEV_CONJ_MFMA = 0, 1
+DEV_CONJ_PAD_MASK, DEV_CONJ_FIX_PAD_ROWS, DEV_CONJ_ZERO_PAD_OUT_ROWS, DEV_CONJ_IMU_APPEND_DUMMY = range(4)
+
+
+class CwmDevConjCrossAttentionArgs(C.Structure):
+    """include/cwm_hip_dev.h cwm_dev_conj_cross_attention_args (development library only)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mode", C.c_int32),
+        ("impl", C.c_int32),
+        ("roles", C.c_int32),
+        ("qk", C.c_void_p),
+        ("v", C.c_void_p),
+        ("qk_src", C.c_void_p),
+        ("v_src", C.c_void_p),
+        ("B", C.c_int32),
+        ("N", C.c_int32),
+        ("M", C.c_int32),
+        ("heads", C.c_int32),
+        ("head_dim", C.c_int32),
+        ("scale", C.c_float),
+        ("y", C.c_void_p),
+        ("y_src", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
+class CwmDevConjSmallAttentionArgs(C.Structure):
+    """include/cwm_hip_dev.h cwm_dev_conj_small_attention_args (development library only)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mode", C.c_int32),
+        ("impl", C.c_int32),
+        ("qkv", C.c_void_p),
+        ("B", C.c_int32),
+        ("n_tok", C.c_int32),
+        ("heads", C.c_int32),
+        ("head_dim", C.c_int32),
+        ("o", C.c_void_p),
+        ("ldo", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
+class CwmDevConjPadArgs(C.Structure):
+    """include/cwm_hip_dev.h cwm_dev_conj_pad_args (development library only)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("kind", C.c_int32),
+        ("B", C.c_int32),
+        ("mask", C.c_void_p),
+        ("N", C.c_int32),
+        ("P", C.c_int32),
+        ("vmax", C.c_int32),
+        ("ext_mask", C.c_void_p),
+        ("x", C.c_void_p),
+        ("perm", C.c_void_p),
+        ("perm_stride", C.c_int32),
+        ("n_rows", C.c_int32),
+        ("n_vis", C.c_int32),
+        ("n_real", C.c_int32),
+        ("D", C.c_int32),
+        ("token", C.c_void_p),
+        ("imu", C.c_void_p),
+        ("dummy", C.c_void_p),
+        ("C", C.c_int32),
+        ("L", C.c_int32),
+        ("T", C.c_int32),
+        ("out", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
+def new_dev_conj_args(cls):
+    """a zeroed cwm_dev_conj_*_args of the given structure class with its struct_size set"""
+    a = cls()
+    a.struct_size = C.sizeof(cls)
+    return a
+
+
 def new_dev_raft_conv_args() -> CwmDevRaftConvArgs:
     a = CwmDevRaftConvArgs()
     a.struct_size = C.sizeof(CwmDevRaftConvArgs)
@@ -427,6 +507,9 @@ DEV_SIGNATURES = {
     "cwm_dev_raft_gru_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "cwm_dev_raft_flow_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "cwm_dev_gather": (C.c_int, [C.POINTER(CwmDevGatherArgs)]),
+    "cwm_dev_conj_cross_attention": (C.c_int, [C.POINTER(CwmDevConjCrossAttentionArgs)]),
+    "cwm_dev_conj_small_attention": (C.c_int, [C.POINTER(CwmDevConjSmallAttentionArgs)]),
+    "cwm_dev_conj_pad": (C.c_int, [C.POINTER(CwmDevConjPadArgs)]),
 }
 
 # the keys cwm_model_set_option / cwm_conj_set_option know (include/cwm_hip.h; csrc/engine.hip tuning_field)

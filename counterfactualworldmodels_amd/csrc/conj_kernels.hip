@@ -376,17 +376,27 @@ __global__ __launch_bounds__(256) void cross_attn_src_combine_kernel(const Cross
 
 size_t cross_attention_partial_floats(int B, int heads, int M, int head_dim) { return (size_t)B * heads * kCrossSplit * M * (head_dim + 2); }
 
+// LDS of cross_attn_main_kernel: K1, K2, V_src [M][hd] and the 64 tokens' main-side scores [64][M + 1], fp32
+constexpr size_t kCrossMainLdsCap = 160 * 1024;
+size_t cross_attention_lds_bytes(int M, int head_dim) { return ((size_t)3 * M * head_dim + (size_t)64 * (M + 1)) * sizeof(float); }
+bool cross_attention_ok(int M, int head_dim) {
+    return M > 0 && M <= 64 && head_dim > 0 && head_dim <= 256 && head_dim % 32 == 0 && cross_attention_lds_bytes(M, head_dim) <= kCrossMainLdsCap;
+}
+
 int launch_cross_attention(const CrossAttnParams& p, int planes, hipStream_t stream) {
     CWM_REQUIRE(p.M > 0 && p.M <= 64 && p.head_dim > 0 && p.head_dim <= 256 && p.head_dim % 32 == 0,
                 "cross_attention: needs M <= 64 and head_dim a multiple of 32, <= 256 (got %d, %d)", p.M, p.head_dim);
+    const size_t smem = cross_attention_lds_bytes(p.M, p.head_dim);
+    // (before the first launch: a main kernel that cannot start would leave scores_t unwritten under the two launches behind it)
+    CWM_REQUIRE(cross_attention_ok(p.M, p.head_dim), "cross_attention: M %d x head_dim %d needs %zu bytes of LDS, more than the %zu of a workgroup", p.M, p.head_dim,
+                smem, kCrossMainLdsCap);
     CWM_REQUIRE(p.scores_t && p.partial, "cross_attention: scratch buffers missing");
-    const size_t smem = ((size_t)3 * p.M * p.head_dim + (size_t)64 * (p.M + 1)) * sizeof(float);
     const dim3 g1((p.N + 63) / 64, p.B * p.heads), g2(kCrossSplit, p.B * p.heads), g3(p.M, p.B * p.heads);
     if (planes == 1) {
-        if (int rc = cwm_set_max_lds((const void*)cross_attn_main_kernel<1>, 160 * 1024)) return rc;  // per (device, kernel): engine.hip
+        if (int rc = cwm_set_max_lds((const void*)cross_attn_main_kernel<1>, (int)kCrossMainLdsCap)) return rc;  // per (device, kernel): engine.hip
         hipLaunchKernelGGL(cross_attn_main_kernel<1>, g1, dim3(256), smem, stream, p);
     } else {
-        if (int rc = cwm_set_max_lds((const void*)cross_attn_main_kernel<2>, 160 * 1024)) return rc;
+        if (int rc = cwm_set_max_lds((const void*)cross_attn_main_kernel<2>, (int)kCrossMainLdsCap)) return rc;
         hipLaunchKernelGGL(cross_attn_main_kernel<2>, g1, dim3(256), smem, stream, p);
     }
     if (p.M <= 32) hipLaunchKernelGGL(cross_attn_src_partial_kernel<32>, g2, dim3(256), 0, stream, p);

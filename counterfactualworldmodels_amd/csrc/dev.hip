@@ -441,3 +441,124 @@ extern "C" int cwm_dev_gather(const cwm_dev_gather_args* args) {
     CWM_HIP_CHECK(hipStreamSynchronize(s));
     return CWM_OK;
 }
+
+// ---- the conjoined predictor's attention and padding kernels one call at a time (tests/test_conj_kernels_gpu.py) ----
+namespace {
+// fp32 [rows][K] -> the operand layout the MFMA cross attention reads its main-stream projections in (what Engine::linear_operand writes in a forward)
+template <int PLANES>
+__global__ void stage_operand_kernel(const float* src, int64_t rows, int K, bf16* out) {  // K a multiple of 4
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= rows * K) return;
+    const int64_t r = i / K;
+    store_operand4<PLANES>(out, r, K, (int)(i - r * K), *reinterpret_cast<const f32x4*>(src + i));
+}
+int stage_operand(const float* src, int64_t rows, int K, bf16* out, int planes, hipStream_t s) {
+    const unsigned grid = (unsigned)((rows * K / 4 + 255) / 256);
+    if (planes == 2)
+        hipLaunchKernelGGL(stage_operand_kernel<2>, dim3(grid), dim3(256), 0, s, src, rows, K, out);
+    else
+        hipLaunchKernelGGL(stage_operand_kernel<1>, dim3(grid), dim3(256), 0, s, src, rows, K, out);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+extern "C" int cwm_dev_conj_cross_attention(const cwm_dev_conj_cross_attention_args* args) {
+    CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_conj_cross_attention_args),
+                "cwm_dev_conj_cross_attention: args->struct_size must be sizeof(cwm_dev_conj_cross_attention_args)");
+    const cwm_dev_conj_cross_attention_args& a = *args;
+    hipStream_t s = (hipStream_t)a.stream;
+    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_conj_cross_attention: bad mode");
+    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    CWM_REQUIRE(a.impl == CWM_DEV_CONJ_VALU || a.impl == CWM_DEV_CONJ_MFMA, "cwm_dev_conj_cross_attention: unknown impl %d", a.impl);
+    const bool mfma = a.impl == CWM_DEV_CONJ_MFMA;
+    CWM_REQUIRE(a.roles >= 1 && a.roles <= 3 && (mfma || a.roles == 3), "cwm_dev_conj_cross_attention: roles = %d (MFMA: 1, 2 or 3; VALU: 3)", a.roles);
+    CWM_REQUIRE(a.qk && a.v && a.qk_src && a.v_src && a.y && a.y_src, "cwm_dev_conj_cross_attention: null argument");
+    CWM_REQUIRE(a.B > 0 && a.N > 0 && a.M > 0 && a.heads > 0 && a.head_dim > 0 && (int64_t)a.B * a.N * 4 * a.heads * a.head_dim < (1ll << 31),
+                "cwm_dev_conj_cross_attention: bad geometry");
+    const int D = a.heads * a.head_dim;
+    CWM_REQUIRE(D % 32 == 0, "cwm_dev_conj_cross_attention: operand rows of %d columns (need a multiple of 32)", D);
+    if (mfma) {
+        CWM_REQUIRE(cross_attention_mfma_ok(a.head_dim, a.M), "cwm_dev_conj_cross_attention: the MFMA form has no kernel for head_dim %d, M %d", a.head_dim, a.M);
+        CWM_REQUIRE(cross_attention_mfma_fits(a.B, a.N, a.heads, a.head_dim), "cwm_dev_conj_cross_attention: too large for the MFMA form's 32-bit offsets");
+    } else {
+        CWM_REQUIRE(cross_attention_ok(a.M, a.head_dim), "cwm_dev_conj_cross_attention: the VALU form refuses M %d, head_dim %d (%zu bytes of LDS)", a.M, a.head_dim,
+                    cross_attention_lds_bytes(a.M, a.head_dim));
+    }
+    const int64_t rows = (int64_t)a.B * a.N;
+    Scratch sc;
+    CrossAttnParams p;
+    memset(&p, 0, sizeof(p));
+    p.qk = a.qk, p.v = a.v, p.qk_src = a.qk_src, p.v_src = a.v_src;
+    p.B = a.B, p.N = a.N, p.M = a.M, p.heads = a.heads, p.head_dim = a.head_dim, p.scale = a.scale;
+    p.y = (bf16*)a.y, p.y_plane = rows * D, p.y_src = (bf16*)a.y_src, p.y_src_plane = (int64_t)a.B * a.M * D;
+    int rc;
+    if (mfma) {
+        bf16* qk_op = sc.get<bf16>((size_t)rows * 2 * D * planes);
+        bf16* v_op = sc.get<bf16>((size_t)rows * D * planes);
+        p.partial = sc.get<float>(cross_attention_mfma_partial_floats(a.B, a.heads, a.M, a.head_dim));
+        CWM_REQUIRE(qk_op && v_op && p.partial, "cwm_dev_conj_cross_attention: out of device memory");
+        if ((rc = stage_operand(a.qk, rows, 2 * D, qk_op, planes, s)) || (rc = stage_operand(a.v, rows, D, v_op, planes, s))) return rc;
+        p.qk_op = qk_op, p.v_op = v_op;
+        if ((rc = launch_cross_attention_mfma_roles(p, planes, s, s, a.roles))) return rc;
+    } else {
+        p.scores_t = sc.get<float>((size_t)a.B * a.heads * a.M * a.N);
+        p.partial = sc.get<float>(cross_attention_partial_floats(a.B, a.heads, a.M, a.head_dim));
+        CWM_REQUIRE(p.scores_t && p.partial, "cwm_dev_conj_cross_attention: out of device memory");
+        if ((rc = launch_cross_attention(p, planes, s))) return rc;
+    }
+    CWM_HIP_CHECK(hipStreamSynchronize(s));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_conj_small_attention(const cwm_dev_conj_small_attention_args* args) {
+    CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_conj_small_attention_args),
+                "cwm_dev_conj_small_attention: args->struct_size must be sizeof(cwm_dev_conj_small_attention_args)");
+    const cwm_dev_conj_small_attention_args& a = *args;
+    hipStream_t s = (hipStream_t)a.stream;
+    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_conj_small_attention: bad mode");
+    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    CWM_REQUIRE(a.impl == CWM_DEV_CONJ_VALU || a.impl == CWM_DEV_CONJ_MFMA, "cwm_dev_conj_small_attention: unknown impl %d", a.impl);
+    CWM_REQUIRE(a.qkv && a.o && a.B > 0 && a.heads > 0, "cwm_dev_conj_small_attention: bad argument");
+    CWM_REQUIRE(a.n_tok > 0 && a.n_tok <= 64 && a.head_dim > 0 && a.head_dim <= 64, "cwm_dev_conj_small_attention: needs n_tok <= 64 and head_dim <= 64 (got %d, %d)",
+                a.n_tok, a.head_dim);
+    CWM_REQUIRE(a.impl == CWM_DEV_CONJ_VALU || small_attention_mfma_ok(a.n_tok, a.head_dim), "cwm_dev_conj_small_attention: the MFMA form needs head_dim 32 (got %d)",
+                a.head_dim);
+    const int D = a.heads * a.head_dim;
+    CWM_REQUIRE(D % 4 == 0 && a.ldo % 32 == 0 && a.ldo >= D, "cwm_dev_conj_small_attention: %d columns in operand rows of ldo = %d (a multiple of 32)", D, a.ldo);
+    SmallAttnParams p;
+    memset(&p, 0, sizeof(p));
+    p.qkv = a.qkv;
+    p.B = a.B, p.n_tok = a.n_tok, p.heads = a.heads, p.head_dim = a.head_dim;
+    p.o = (bf16*)a.o, p.o_plane = (int64_t)a.B * a.n_tok * a.ldo, p.ldo = a.ldo;
+    if (int rc = a.impl == CWM_DEV_CONJ_MFMA ? launch_small_attention_mfma(p, planes, s) : launch_small_attention(p, planes, s)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize(s));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_conj_pad(const cwm_dev_conj_pad_args* args) {
+    CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_conj_pad_args), "cwm_dev_conj_pad: args->struct_size must be sizeof(cwm_dev_conj_pad_args)");
+    const cwm_dev_conj_pad_args& a = *args;
+    hipStream_t s = (hipStream_t)a.stream;
+    CWM_REQUIRE(a.B > 0, "cwm_dev_conj_pad: bad batch");
+    int rc = 0;
+    if (a.kind == CWM_DEV_CONJ_PAD_MASK) {
+        CWM_REQUIRE(a.mask && a.ext_mask && a.N > 0 && a.P >= 0 && a.vmax >= 0, "cwm_dev_conj_pad: bad pad-mask argument");
+        rc = launch_pad_mask(a.mask, a.B, a.N, a.P, a.vmax, a.ext_mask, s);
+    } else if (a.kind == CWM_DEV_CONJ_FIX_PAD_ROWS) {
+        CWM_REQUIRE(a.x && a.perm && a.token && a.n_rows > 0 && a.D > 0 && a.perm_stride >= a.n_rows && a.n_real >= 0, "cwm_dev_conj_pad: bad fix-pad-rows argument");
+        rc = launch_fix_pad_rows(a.x, a.perm, a.B, a.perm_stride, a.n_rows, a.n_real, a.D, a.token, s);
+    } else if (a.kind == CWM_DEV_CONJ_ZERO_PAD_OUT_ROWS) {
+        CWM_REQUIRE(a.x && a.perm && a.n_rows > 0 && a.D > 0 && a.n_vis >= 0 && a.perm_stride >= a.n_vis + a.n_rows && a.n_real >= 0,
+                    "cwm_dev_conj_pad: bad zero-pad-out-rows argument");
+        rc = launch_zero_pad_out_rows(a.x, a.perm, a.B, a.perm_stride, a.n_vis, a.n_rows, a.n_real, a.D, s);
+    } else if (a.kind == CWM_DEV_CONJ_IMU_APPEND_DUMMY) {
+        CWM_REQUIRE(a.imu && a.mask && a.dummy && a.out && a.ext_mask && a.C > 0 && a.L > 0 && a.T > 0 && a.N > 0, "cwm_dev_conj_pad: bad append-dummy argument");
+        rc = launch_imu_append_dummy(a.imu, a.mask, a.dummy, a.B, a.C, a.L, a.T, a.N, a.out, a.ext_mask, s);
+    } else {
+        CWM_REQUIRE(false, "cwm_dev_conj_pad: unknown kind %d", a.kind);
+    }
+    if (rc) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize(s));
+    return CWM_OK;
+}

@@ -275,6 +275,8 @@ struct CrossAttnParams {
 };
 int launch_cross_attention(const CrossAttnParams& p, int planes, hipStream_t stream);       // fp32 VALU kernels: qk / v fp32, scores_t + partial scratch
 size_t cross_attention_partial_floats(int B, int heads, int M, int head_dim);
+size_t cross_attention_lds_bytes(int M, int head_dim);  // what the VALU main kernel asks for ...
+bool cross_attention_ok(int M, int head_dim);           // ... and whether it fits (M <= 64, head_dim a multiple of 32 <= 256, the LDS of one workgroup)
 int launch_cross_attention_mfma(const CrossAttnParams& p, int planes, hipStream_t stream);  // MFMA kernel: qk_op / v_op, partial scratch
 int launch_cross_attention_mfma_roles(const CrossAttnParams& p, int planes, hipStream_t stream_a, hipStream_t stream_b, int roles);  // bit 0: main update on stream_a, bit 1: context update on stream_b
 bool cross_attention_mfma_ok(int head_dim, int M);

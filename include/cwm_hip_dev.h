@@ -145,6 +145,71 @@ typedef struct cwm_dev_gather_args {
 } cwm_dev_gather_args;
 CWM_API int cwm_dev_gather(const cwm_dev_gather_args* args);
 
+/* ---- the conjoined predictor's attention and padding kernels one call at a time (tests/test_conj_kernels_gpu.py) -------------------------------
+ * csrc/conj_kernels.hip (fp32 VALU forms, padding bookkeeping) and csrc/conj_attention.hip (MFMA forms) on caller-owned device buffers; the stream
+ * is synchronised before a call returns.  Outputs named "operand" are rows of planes * width bf16 in the layout of csrc/common.h a_pos (planes 2
+ * parity, 1 fast).  A shape that the chosen form's precondition rejects (cross_attention_mfma_ok / cross_attention_mfma_fits, cross_attention_ok,
+ * small_attention_mfma_ok) comes back as an error before anything is launched or allocated: the outputs are untouched. */
+#define CWM_DEV_CONJ_VALU 0 /* launch_cross_attention / launch_small_attention */
+#define CWM_DEV_CONJ_MFMA 1 /* launch_cross_attention_mfma_roles / launch_small_attention_mfma */
+
+/* `BidirectionalCrossAttention.forward` on the projected tensors, D = heads * head_dim: per head the first head_dim columns of the 2 * head_dim slice
+ * of qk / qk_src give y = softmax_M(scale q1 k1^T) v_src, the second give y_src = softmax_N(scale q2_src k2^T) v.  The MFMA form reads qk and v in the
+ * operand layout: the entry stages them itself (the common.h writers).  scores_t and partial are allocated inside. */
+typedef struct cwm_dev_conj_cross_attention_args {
+    uint32_t struct_size;
+    int32_t mode;  /* CWM_MODE_PARITY or CWM_MODE_FAST */
+    int32_t impl;  /* CWM_DEV_CONJ_* */
+    int32_t roles; /* bit 0: the main-stream update (y), bit 1: the context update (y_src); MFMA: 1, 2 or 3 (both on `stream`), VALU: 3 */
+    const float* qk;     /* [B * N][2 D] */
+    const float* v;      /* [B * N][D] */
+    const float* qk_src; /* [B * M][2 D] */
+    const float* v_src;  /* [B * M][D] */
+    int32_t B, N, M, heads, head_dim;
+    float scale;
+    void* y;     /* operand, [B * N] rows of width D */
+    void* y_src; /* operand, [B * M] rows of width D */
+    void* stream;
+} cwm_dev_conj_cross_attention_args;
+CWM_API int cwm_dev_conj_cross_attention(const cwm_dev_conj_cross_attention_args* args);
+
+/* `Attention.forward` of the context stream on qkv [B * n_tok][3 * heads * head_dim] (bias added, q not yet scaled): o = softmax(q k^T / sqrt(head_dim)) v
+ * in columns [0, heads * head_dim) of operand rows of width ldo (a multiple of 32, >= heads * head_dim); the other columns are not written. */
+typedef struct cwm_dev_conj_small_attention_args {
+    uint32_t struct_size;
+    int32_t mode;
+    int32_t impl; /* CWM_DEV_CONJ_*: VALU n_tok <= 64 and head_dim <= 64, MFMA n_tok <= 64 and head_dim 32 */
+    const float* qkv;
+    int32_t B, n_tok, heads, head_dim;
+    void* o;
+    int32_t ldo;
+    void* stream;
+} cwm_dev_conj_small_attention_args;
+CWM_API int cwm_dev_conj_small_attention(const cwm_dev_conj_small_attention_args* args);
+
+#define CWM_DEV_CONJ_PAD_MASK 0          /* ext_mask [B][N + P] = [mask [B][N] | pad slot j masked unless j < vmax - visible(b)] */
+#define CWM_DEV_CONJ_FIX_PAD_ROWS 1      /* rows i of x [B * n_rows][D] with perm[b][i] >= n_real := token [D] */
+#define CWM_DEV_CONJ_ZERO_PAD_OUT_ROWS 2 /* rows j of x [B * n_rows][D] with perm[b][n_vis + j] >= n_real := 0 */
+#define CWM_DEV_CONJ_IMU_APPEND_DUMMY 3  /* out [B][C][L + T] = [imu [B][C][L] | dummy [C][T]], ext_mask [B][N + 1] = [mask [B][N] | 0] */
+typedef struct cwm_dev_conj_pad_args {
+    uint32_t struct_size;
+    int32_t kind; /* CWM_DEV_CONJ_PAD_* .. CWM_DEV_CONJ_IMU_APPEND_DUMMY */
+    int32_t B;
+    const uint8_t* mask; /* PAD_MASK, IMU_APPEND_DUMMY: [B][N], non-zero = masked */
+    int32_t N, P, vmax;
+    uint8_t* ext_mask;
+    float* x;            /* FIX_PAD_ROWS, ZERO_PAD_OUT_ROWS */
+    const int32_t* perm; /* [B][perm_stride] */
+    int32_t perm_stride, n_rows, n_vis, n_real, D;
+    const float* token;
+    const float* imu;    /* IMU_APPEND_DUMMY */
+    const float* dummy;
+    int32_t C, L, T;
+    float* out;
+    void* stream;
+} cwm_dev_conj_pad_args;
+CWM_API int cwm_dev_conj_pad(const cwm_dev_conj_pad_args* args);
+
 #ifdef __cplusplus
 }
 #endif
