@@ -201,11 +201,11 @@ extern "C" int cwm_bench_attention(int B, int H, int N, int mode, int iters, dou
 }
 
 // ---- RAFT kernels one at a time (tests/test_raft_kernels_gpu.py) ---------------------------------------------------------------------------------
-// The launches of raft_model.hip on caller-owned buffers: the model's packing kernels, launch_im2col and launch_gemm with this thread's options.
+// The launches of raft_model.hip on caller-owned buffers.  A convolution is made of what the model's run_conv / prepare are made of (kernels.h
+// set_conv_geometry, pack_conv_parts, conv_gemm) and launched by launch_gemm with this thread's options.
 namespace {
 ConvSrc conv_src_of(const cwm_dev_conv_src& d) {
-    ConvSrc s;
-    memset(&s, 0, sizeof(s));
+    ConvSrc s = {};
     s.p = d.p;
     s.ld = d.ld ? d.ld : d.C;
     s.C = d.C;
@@ -228,8 +228,7 @@ extern "C" int cwm_dev_raft_conv(const cwm_dev_raft_conv_args* args) {
     const bool frames = a.image[0] != nullptr, operand_only = a.flags & CWM_DEV_CONV_OPERAND_ONLY, keep = a.flags & CWM_DEV_CONV_KEEP_OPERAND;
     CWM_REQUIRE(!(operand_only && keep), "cwm_dev_raft_conv: flags ask for the operand only and for no operand");
     CWM_REQUIRE(a.n_img > 0 && a.H > 0 && a.W > 0 && a.kh > 0 && a.kw > 0 && a.stride > 0 && a.pad_h >= 0 && a.pad_w >= 0, "cwm_dev_raft_conv: bad geometry");
-    Im2colParams ip;
-    memset(&ip, 0, sizeof(ip));
+    Im2colParams ip = {};
     if (frames) {
         CWM_REQUIRE(a.image[1] && a.P > 0 && a.ppg > 0 && a.P % a.ppg == 0 && a.img0 >= 0 && a.img0 + a.n_img <= 2 * a.P,
                     "cwm_dev_raft_conv: images [%d, %d) of 2 x %d pairs (%d per group)", a.img0, a.img0 + a.n_img, a.P, a.ppg);
@@ -251,19 +250,9 @@ extern "C" int cwm_dev_raft_conv(const cwm_dev_raft_conv_args* args) {
         for (int i = 0; i < a.nsrc; ++i) ip.src[i] = conv_src_of(a.src[i]);
     }
     const int cin = ip.src[0].C + (ip.nsrc > 1 ? ip.src[1].C : 0), K = a.kh * a.kw * cin, Kpad = round_up(K, 64);
-    ip.n_img = a.n_img;
-    ip.H = a.H;
-    ip.W = a.W;
-    ip.kh = a.kh;
-    ip.kw = a.kw;
-    ip.stride = a.stride;
-    ip.pad_h = a.pad_h;
-    ip.pad_w = a.pad_w;
-    ip.OH = (a.H + 2 * a.pad_h - a.kh) / a.stride + 1;
-    ip.OW = (a.W + 2 * a.pad_w - a.kw) / a.stride + 1;
+    set_conv_geometry(ip, a.n_img, a.H, a.W, a.kh, a.kw, a.stride, a.pad_h, a.pad_w, Kpad);
     ip.c_lo = a.c_lo;
     ip.c_hi = a.c_hi;
-    ip.Kpad = Kpad;
     CWM_REQUIRE(a.H + 2 * a.pad_h >= a.kh && a.W + 2 * a.pad_w >= a.kw, "cwm_dev_raft_conv: the kernel is larger than the padded input");
     CWM_REQUIRE(a.c_hi <= a.c_lo || (a.A && a.c_lo >= 0 && a.c_hi <= cin), "cwm_dev_raft_conv: a partial rewrite [%d, %d) of %d channels needs the caller's A",
                 a.c_lo, a.c_hi, cin);
@@ -282,9 +271,11 @@ extern "C" int cwm_dev_raft_conv(const cwm_dev_raft_conv_args* args) {
     if (!operand_only) {
         CWM_REQUIRE(a.nparts == 1 || a.nparts == 2, "cwm_dev_raft_conv: nparts = %d", a.nparts);
         int n = 0;
+        ConvPartW parts[2];
         for (int i = 0; i < a.nparts; ++i) {
             const cwm_dev_conv_part& p = a.part[i];
             CWM_REQUIRE(p.w && p.b && p.n > 0 && (!p.bn_gamma || (p.bn_beta && p.bn_mean && p.bn_var)), "cwm_dev_raft_conv: bad weight part %d", i);
+            parts[i] = ConvPartW{p.w, p.b, p.bn_gamma, p.bn_beta, p.bn_mean, p.bn_var, p.n};
             n += p.n;
         }
         // the model's LinearW (engine.hip make_linear): N = the output channels rounded up to 16, zero rows / bias beyond them
@@ -298,25 +289,8 @@ extern "C" int cwm_dev_raft_conv(const cwm_dev_raft_conv_args* args) {
         CWM_HIP_CHECK(hipMemsetAsync(w_hi, 0, plane * sizeof(bf16), s));
         CWM_HIP_CHECK(hipMemsetAsync(w_il, 0, 2 * plane * sizeof(bf16), s));
         CWM_HIP_CHECK(hipMemsetAsync(bias, 0, (size_t)Npad * sizeof(float), s));
-        int row0 = 0;
-        for (int i = 0; i < a.nparts; ++i) {
-            const cwm_dev_conv_part& p = a.part[i];
-            if (int rc = launch_pack_conv(p.w, p.b, p.bn_gamma, p.bn_beta, p.bn_mean, p.bn_var, a.bn_eps, p.n, cin, a.kh, a.kw, Kpad, row0, w_il, w_hi, bias, s))
-                return rc;
-            row0 += p.n;
-        }
-        GemmParams g;
-        memset(&g, 0, sizeof(g));
-        g.A = A;
-        g.lda = Kpad;
-        g.W = planes == 2 ? w_il : w_hi;
-        g.M = (int)M;
-        g.N = N;
-        g.K = Kpad;
-        g.bias = bias;
-        g.epi = EPI_F32;
-        g.C = a.out + a.col0;
-        g.ldc = a.ldc;
+        if (int rc = pack_conv_parts(parts, a.nparts, a.bn_eps, cin, a.kh, a.kw, Kpad, w_il, w_hi, bias, s)) return rc;
+        GemmParams g = conv_gemm(A, planes == 2 ? w_il : w_hi, bias, (int)M, N, Kpad, a.out + a.col0, a.ldc);
         g.tune = &thread_tuning();
         if (int rc = launch_gemm(g, planes, s)) return rc;
     }

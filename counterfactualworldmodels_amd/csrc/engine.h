@@ -42,6 +42,7 @@ struct Slot {
     int repeat = 1;          // SLOT_VECTOR: number of consecutive copies written at dst
     int64_t numel = 0;
     bool loaded = false;
+    bool optional = false;  // missing_weights does not count it (the handle that set it checks for itself where the tensor is needed)
 };
 
 struct EventPair {
@@ -132,6 +133,7 @@ struct Engine {
     Tuning tune = thread_tuning();  // this model's execution options (cwm_model_set_option); every launch of the model carries a pointer to it
     float ln_eps = 1e-6f;
     std::map<std::string, Slot> slots;
+    uint64_t loads = 0;  // load_weight calls that changed a stored tensor (not those into an ignored slot): a handle that derives data from its slots compares it
     std::vector<void*> allocs;     // weights etc., freed on destroy
     std::vector<void*> ws_allocs;  // workspace, re-allocated when it has to grow
     KernelTimer timers[CWM_KCLASS_COUNT];

@@ -334,6 +334,7 @@ int Engine::load_weight(const char* key, const float* data, int on_device, const
         }
     }
     s.loaded = true;
+    ++loads;
     return CWM_OK;
 }
 
@@ -341,7 +342,7 @@ int Engine::missing_weights(char* buf, int buflen) {
     int missing = 0;
     if (buf && buflen > 0) buf[0] = 0;
     for (auto& kv : slots)
-        if (!kv.second.loaded) {
+        if (!kv.second.loaded && !kv.second.optional) {
             if (!missing && buf && buflen > 0) snprintf(buf, buflen, "%s", kv.first.c_str());
             ++missing;
         }

@@ -327,21 +327,37 @@ struct CorrLookupParams {
     float* out;           // instead of A (out != nullptr): fp32 [M][out_ld], features [0, levels*81) (cwm_raft_corr_lookup)
     int out_ld;
 };
+// RAFT.upsample_flow of a C-channel low-resolution field (C = 2: the flow, C = 1: the output head's map): the 3 x 3 neighbourhood times 8, combined
+// with the softmax of the 9 x 64 mask
 struct ConvexUpParams {
-    const float* coords;  // [P][h8][w8][2] (flow = coords - (x, y)), or nullptr: flow [P][2][h8][w8]
-    const float* flow;
+    const float* coords;  // [P][h8][w8][2]: the field is the flow coords - (x, y) (C = 2 only), or nullptr:
+    const float* value;   // the field itself, planar [P][C][h8][w8]
     const float* mask;    // [P][h8][w8][mask_ld]: channel k*64 + i*8 + j, times mask_scale
     int mask_ld;
     float mask_scale;
-    int P, ppg, h8, w8;
+    int C, P, ppg, h8, w8;
     float* out;           // pair pr = (g, t): out + g * out_sb + t * out_st + c * out_sc + Y * 8w8 + X
     int64_t out_sb, out_st, out_sc;
 };
+// the params of a launch on a mask of 576 channels per pixel; the field is `coords` (C = 2) or `value`, one of them null
+ConvexUpParams convex_up_params(int C, const float* coords, const float* value, const float* mask, float mask_scale, int P, int ppg, int h8, int w8, float* out,
+                                int64_t out_sb, int64_t out_st, int64_t out_sc);
+// A convolution is three statements, each made once here for the model (raft_model.hip run_conv / prepare) and the development entry point (dev.hip
+// cwm_dev_raft_conv): its geometry in the im2col params, its weight parts packed into one GEMM operand, and the GEMM's params.  The launch of the GEMM is the
+// caller's (Engine::run_gemm, or launch_gemm with the thread's options).
+// n_img images of H x W under a kh x kw kernel: the output size OH x OW and the rest of the geometry (the sources, c_lo / c_hi and A are the caller's)
+void set_conv_geometry(Im2colParams& ip, int n_img, int H, int W, int kh, int kw, int stride, int pad_h, int pad_w, int Kpad);
+// One weight part [n][cin][kh][kw] (+ bias [n]) of a convolution; gamma != nullptr folds the eval-mode batch norm (gamma, beta, mean, var, each [n]) that
+// follows the convolution
+struct ConvPartW {
+    const float *w, *b, *gamma, *beta, *mean, *var;
+    int n;
+};
+// part i -> rows row0 .. row0 + n of the packed operand (w_il: parity layout, w_hi: fast) and bias[row0 ..], row0 = the output channels of the parts before it
+int pack_conv_parts(const ConvPartW* parts, int nparts, float eps, int cin, int kh, int kw, int Kpad, bf16* w_il, bf16* w_hi, float* bias, hipStream_t s);
+// C[:, 0:N] (row stride ldc: a column slice of an NHWC buffer) = A W^T + bias in fp32; W in the layout of the launch's planes
+GemmParams conv_gemm(const bf16* A, const bf16* W, const float* bias, int M, int N, int Kpad, float* C, int ldc);
 // planes: the layout of A (common.h a_pos): 2 = split-bf16 hi / lo (parity), 1 = one bf16 plane (fast); the same for launch_corr_lookup
-// One weight part [n][cin][kh][kw] (+ bias [n]) of a convolution -> rows row0 .. row0 + n of its packed GEMM operand (w_il: parity layout, w_hi: fast) and
-// bias[row0 ..]; gamma != nullptr folds the eval-mode batch norm (gamma, beta, mean, var, eps) that follows the convolution
-int launch_pack_conv(const float* w, const float* b, const float* gamma, const float* beta, const float* mean, const float* var, float eps, int n, int cin,
-                     int kh, int kw, int Kpad, int row0, bf16* w_il, bf16* w_hi, float* bias, hipStream_t s);
 int launch_im2col(const Im2colParams& p, int planes, hipStream_t s);
 // stats [n_img][C] (mean, rstd) pairs; work: 2 * n_img * kInstNormMaxChunks * C doubles
 constexpr int kInstNormMaxChunks = 16;
@@ -360,22 +376,11 @@ int launch_flow_update(float* coords, const float* delta, int ld, int64_t M, hip
 int launch_convex_upsample(const ConvexUpParams& p, hipStream_t s);
 int launch_flow_low(const float* coords, int P, int h8, int w8, float* out, hipStream_t s);
 // The output head (raft_model.py:152-159, 257-267; output_dim = 1).  launch_head_project: value[m] = bias[0] + sum_c w[c] * relu(hidden[m * ld + c]) over
-// the 256 channels of output_block.0's result, fp32, one wave per low-resolution pixel.  launch_convex_upsample1: RAFT.upsample_flow of that planar
-// one-channel map (times 8, as a flow) with the 9 x 64 softmax mask.
-struct ConvexUp1Params {
-    const float* value;   // [P][h8][w8]
-    const float* mask;    // [P][h8][w8][mask_ld]: channel k*64 + i*8 + j, times mask_scale
-    int mask_ld;
-    float mask_scale;
-    int P, ppg, h8, w8;
-    float* out;           // pair pr = (g, t): out + g * out_sb + t * out_st + Y * 8w8 + X
-    int64_t out_sb, out_st;
-};
+// the 256 channels of output_block.0's result, fp32, one wave per low-resolution pixel; launch_convex_upsample with C = 1 then upsamples that planar map.
+constexpr int kHeadHidden = 256;
+int launch_head_project(const float* hidden, int ld, const float* w, const float* bias, int64_t M, float* value, hipStream_t s);
 // CorrBlock built from two feature maps [P][h8 * w8][256] and indexed at coords [P * h8 * w8][2]: the pyramid (allocated and freed inside), then the lookup
 // as fp32 `out` [M][324], or (out == nullptr) as convc1's Kpad = 384 operand A in the layout of `planes`.  Synchronises the stream.
 int raft_corr_lookup_run(const float* fmap1, const float* fmap2, const float* coords, int P, int h8, int w8, float* out, bf16* A, int planes, hipStream_t s);
-constexpr int kHeadHidden = 256;
-int launch_head_project(const float* hidden, int ld, const float* w, const float* bias, int64_t M, float* value, hipStream_t s);
-int launch_convex_upsample1(const ConvexUp1Params& p, hipStream_t s);
 
 }  // namespace cwm

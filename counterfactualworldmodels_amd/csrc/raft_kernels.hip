@@ -1,7 +1,9 @@
 // RAFT-large optical flow (cwm/models/raft): the kernels around the convolution GEMMs.  Activations are fp32 NHWC; a convolution is an
 // explicit im2col into the GEMM's A operand (common.h a_pos: split-bf16 hi/lo in parity mode, one bf16 plane in fast mode; K order
 // (ky, kx, c), zero padded to Kpad) and one launch_gemm with the EPI_F32 epilogue.  Activation functions, normalisations and the GRU's r*h are applied where an operand is read, never as a pass of
-// their own, except the residual join of the encoders and the GRU state update.
+// their own, except the residual join of the encoders and the GRU state update.  Below the kernels: launch_flat, the one launch of every grid-stride kernel
+// here; the three statements a convolution launch is made of (set_conv_geometry, pack_conv_parts, conv_gemm), shared by raft_model.hip and dev.hip; and the
+// launchers.  One convex-upsampling kernel serves the flow (2 channels, read from the coordinates) and the output head's map (1 channel, planar).
 #include <math.h>
 
 #include <algorithm>
@@ -278,10 +280,12 @@ __global__ void flow_update_kernel(float* coords, const float* delta, int ld, in
         coords[i] = coords[i] + delta[(i >> 1) * ld + (i & 1)];
 }
 
-// RAFT.upsample_flow: out[c, 8y+i, 8x+j] = sum_k softmax_k(mask[k*64 + i*8 + j]) * 8 flow[c, y+ky-1, x+kx-1] (k = 3ky + kx, zero padding)
+// RAFT.upsample_flow of a C-channel field v: out[c, 8y+i, 8x+j] = sum_k softmax_k(mask[k*64 + i*8 + j]) * 8 v[c, y+ky-1, x+kx-1] (k = 3ky + kx, zero
+// padding).  v is the flow coords - (x, y) (p.coords, C = 2) or the planar p.value; one output pixel (all C channels) per thread.
+template <int C>
 __global__ void convex_upsample_kernel(const ConvexUpParams p) {
     const int H = 8 * p.h8, W = 8 * p.w8;
-    const int64_t total = (int64_t)p.P * H * W;
+    const int64_t total = (int64_t)p.P * H * W, hw = (int64_t)p.h8 * p.w8;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int pr = (int)(i / ((int64_t)H * W));
         const int q = (int)(i - (int64_t)pr * H * W), Y = q / W, X = q - Y * W;
@@ -300,29 +304,25 @@ __global__ void convex_upsample_kernel(const ConvexUpParams p) {
             e[k] = expf(e[k] - mx);
             s += e[k];
         }
-        float o0 = 0.f, o1 = 0.f;
+        float o[C] = {};
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
-            float f0 = 0.f, f1 = 0.f;
+            float f[C] = {};
             if (yy >= 0 && yy < p.h8 && xx >= 0 && xx < p.w8) {
-                const int64_t n = ((int64_t)pr * p.h8 + yy) * p.w8 + xx;
-                if (p.coords) {
-                    f0 = 8.f * (p.coords[2 * n] - (float)xx);
-                    f1 = 8.f * (p.coords[2 * n + 1] - (float)yy);
-                } else {
-                    f0 = 8.f * p.flow[(int64_t)pr * 2 * p.h8 * p.w8 + (int64_t)yy * p.w8 + xx];
-                    f1 = 8.f * p.flow[((int64_t)pr * 2 + 1) * p.h8 * p.w8 + (int64_t)yy * p.w8 + xx];
-                }
+                const int64_t r = (int64_t)yy * p.w8 + xx;
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+                    f[c] = 8.f * (C == 2 && p.coords ? p.coords[2 * (pr * hw + r) + c] - (float)(c ? yy : xx) : p.value[((int64_t)pr * C + c) * hw + r]);
             }
             const float w = e[k] / s;
-            o0 += w * f0;
-            o1 += w * f1;
+#pragma unroll
+            for (int c = 0; c < C; ++c) o[c] += w * f[c];
         }
         const int g = pr / p.ppg, t = pr - g * p.ppg;
-        float* o = p.out + g * p.out_sb + t * p.out_st + (int64_t)Y * W + X;
-        o[0] = o0;
-        o[p.out_sc] = o1;
+        float* dst = p.out + g * p.out_sb + t * p.out_st + (int64_t)Y * W + X;
+#pragma unroll
+        for (int c = 0; c < C; ++c) dst[c * p.out_sc] = o[c];
     }
 }
 
@@ -355,41 +355,6 @@ __global__ void __launch_bounds__(256) head_project_kernel(const float* hidden, 
     }
 }
 
-// RAFT.upsample_flow of a one-channel planar map: out[8y+i, 8x+j] = sum_k softmax_k(mask[k*64 + i*8 + j]) * 8 value[y+ky-1, x+kx-1]
-__global__ void convex_upsample1_kernel(const ConvexUp1Params p) {
-    const int H = 8 * p.h8, W = 8 * p.w8;
-    const int64_t total = (int64_t)p.P * H * W;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int pr = (int)(i / ((int64_t)H * W));
-        const int q = (int)(i - (int64_t)pr * H * W), Y = q / W, X = q - Y * W;
-        const int y = Y >> 3, x = X >> 3, sub = (Y & 7) * 8 + (X & 7);
-        const int64_t pix = ((int64_t)pr * p.h8 + y) * p.w8 + x;
-        const float* mk = p.mask + pix * p.mask_ld + sub;
-        float e[9], mx = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            e[k] = mk[k * 64] * p.mask_scale;
-            mx = fmaxf(mx, e[k]);
-        }
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            e[k] = expf(e[k] - mx);
-            s += e[k];
-        }
-        float o = 0.f;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
-            float f = 0.f;
-            if (yy >= 0 && yy < p.h8 && xx >= 0 && xx < p.w8) f = 8.f * p.value[((int64_t)pr * p.h8 + yy) * p.w8 + xx];
-            o += (e[k] / s) * f;
-        }
-        const int g = pr / p.ppg, t = pr - g * p.ppg;
-        p.out[g * p.out_sb + t * p.out_st + (int64_t)Y * W + X] = o;
-    }
-}
-
 // Convolution weights [N][C][kh][kw] -> rows row0 .. row0 + N of the GEMM's W operand in K order (ky, kx, c), zero padded to Kpad, in both layouts
 // (il: parity, hi: fast); an eval-mode batch norm after the convolution is folded in: w * gamma / sqrt(var + eps), (b - mean) * gamma / sqrt(var + eps) + beta
 __global__ void pack_conv_kernel(const float* w, const float* gamma, const float* var, float eps, int N, int C, int kh, int kw, int Kpad, int row0,
@@ -416,7 +381,13 @@ __global__ void pack_bias_kernel(const float* b, const float* gamma, const float
 
 unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 1 << 20); }
 
-}  // namespace
+// the launch of every grid-stride kernel over n elements: 256 threads, one element per thread up to 2^20 workgroups
+template <typename Kernel, typename... Args>
+int launch_flat(Kernel kernel, int64_t n, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n)), dim3(256), 0, s, args...);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
 
 int launch_pack_conv(const float* w, const float* b, const float* gamma, const float* beta, const float* mean, const float* var, float eps, int n, int cin,
                      int kh, int kw, int Kpad, int row0, bf16* w_il, bf16* w_hi, float* bias, hipStream_t s) {
@@ -425,6 +396,47 @@ int launch_pack_conv(const float* w, const float* b, const float* gamma, const f
     hipLaunchKernelGGL(pack_bias_kernel, dim3((n + 255) / 256), dim3(256), 0, s, b, gamma, beta, mean, var, eps, n, bias + row0);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+}  // namespace
+
+void set_conv_geometry(Im2colParams& ip, int n_img, int H, int W, int kh, int kw, int stride, int pad_h, int pad_w, int Kpad) {
+    ip.n_img = n_img;
+    ip.H = H;
+    ip.W = W;
+    ip.kh = kh;
+    ip.kw = kw;
+    ip.stride = stride;
+    ip.pad_h = pad_h;
+    ip.pad_w = pad_w;
+    ip.OH = (H + 2 * pad_h - kh) / stride + 1;
+    ip.OW = (W + 2 * pad_w - kw) / stride + 1;
+    ip.Kpad = Kpad;
+}
+
+int pack_conv_parts(const ConvPartW* parts, int nparts, float eps, int cin, int kh, int kw, int Kpad, bf16* w_il, bf16* w_hi, float* bias, hipStream_t s) {
+    int row0 = 0;
+    for (int i = 0; i < nparts; ++i) {
+        const ConvPartW& p = parts[i];
+        if (int rc = launch_pack_conv(p.w, p.b, p.gamma, p.beta, p.mean, p.var, eps, p.n, cin, kh, kw, Kpad, row0, w_il, w_hi, bias, s)) return rc;
+        row0 += p.n;
+    }
+    return 0;
+}
+
+GemmParams conv_gemm(const bf16* A, const bf16* W, const float* bias, int M, int N, int Kpad, float* C, int ldc) {
+    GemmParams g = {};
+    g.A = A;
+    g.lda = Kpad;
+    g.W = W;
+    g.M = M;
+    g.N = N;
+    g.K = Kpad;
+    g.bias = bias;
+    g.epi = EPI_F32;
+    g.C = C;
+    g.ldc = ldc;
+    return g;
 }
 
 int launch_im2col(const Im2colParams& p, int planes, hipStream_t s) {
@@ -450,28 +462,16 @@ int launch_instnorm_stats(const float* x, int n_img, int HW, int C, float eps, f
 
 int launch_residual_join(const ConvSrc& X, const ConvSrc& Y, int n_img, int HW, float* out, hipStream_t s) {
     const int64_t total = (int64_t)n_img * HW * Y.C;
-    hipLaunchKernelGGL(residual_join_kernel, dim3(grid_for(total)), dim3(256), 0, s, X, Y, total, HW, out);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_flat(residual_join_kernel, total, s, X, Y, total, HW, out);
 }
 
-int launch_cnet_split(const float* cn, int64_t M, float* h, float* x, hipStream_t s) {
-    hipLaunchKernelGGL(cnet_split_kernel, dim3(grid_for(M * 128)), dim3(256), 0, s, cn, M, h, x);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
+int launch_cnet_split(const float* cn, int64_t M, float* h, float* x, hipStream_t s) { return launch_flat(cnet_split_kernel, M * 128, s, cn, M, h, x); }
 
-int launch_coords_init(float* coords, int64_t M, int h8, int w8, hipStream_t s) {
-    hipLaunchKernelGGL(coords_init_kernel, dim3(grid_for(M)), dim3(256), 0, s, coords, M, h8, w8);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
+int launch_coords_init(float* coords, int64_t M, int h8, int w8, hipStream_t s) { return launch_flat(coords_init_kernel, M, s, coords, M, h8, w8); }
 
 int launch_coords_init_flow(float* coords, int P, int ppg, int h8, int w8, const float* init, int64_t sb, int64_t st, int64_t sc, hipStream_t s) {
     const int64_t M = (int64_t)P * h8 * w8;
-    hipLaunchKernelGGL(coords_init_flow_kernel, dim3(grid_for(M)), dim3(256), 0, s, coords, M, h8, w8, ppg, init, sb, st, sc);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_flat(coords_init_flow_kernel, M, s, coords, M, h8, w8, ppg, init, sb, st, sc);
 }
 
 int launch_corr(const float* f1, const float* f2, int P, int N, int D, float* corr, hipStream_t s) {
@@ -483,57 +483,55 @@ int launch_corr(const float* f1, const float* f2, int P, int N, int D, float* co
 
 int launch_corr_pool(const float* in, int64_t maps, int h, int w, float* out, hipStream_t s) {
     const int oh = h / 2, ow = w / 2;
-    hipLaunchKernelGGL(corr_pool_kernel, dim3(grid_for(maps * oh * ow)), dim3(256), 0, s, in, maps, h, w, out, oh, ow);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_flat(corr_pool_kernel, maps * oh * ow, s, in, maps, h, w, out, oh, ow);
 }
 
 int launch_corr_lookup(const CorrLookupParams& p, int planes, hipStream_t s) {
-    hipLaunchKernelGGL(planes == 2 ? corr_lookup_kernel<2> : corr_lookup_kernel<1>, dim3(grid_for(p.M * p.Kpad)), dim3(256), 0, s, p);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_flat(planes == 2 ? corr_lookup_kernel<2> : corr_lookup_kernel<1>, p.M * p.Kpad, s, p);
 }
 
 int launch_motion_finish(float* x, const float* coords, int64_t M, int h8, int w8, hipStream_t s) {
-    hipLaunchKernelGGL(motion_finish_kernel, dim3(grid_for(M * 128)), dim3(256), 0, s, x, coords, M, h8, w8);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_flat(motion_finish_kernel, M * 128, s, x, coords, M, h8, w8);
 }
 
-int launch_gru_update(float* h, const float* zr, const float* q, int64_t M, hipStream_t s) {
-    hipLaunchKernelGGL(gru_update_kernel, dim3(grid_for(M * 128)), dim3(256), 0, s, h, zr, q, M);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
+int launch_gru_update(float* h, const float* zr, const float* q, int64_t M, hipStream_t s) { return launch_flat(gru_update_kernel, M * 128, s, h, zr, q, M); }
 
 int launch_flow_update(float* coords, const float* delta, int ld, int64_t M, hipStream_t s) {
-    hipLaunchKernelGGL(flow_update_kernel, dim3(grid_for(2 * M)), dim3(256), 0, s, coords, delta, ld, M);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_flat(flow_update_kernel, 2 * M, s, coords, delta, ld, M);
+}
+
+ConvexUpParams convex_up_params(int C, const float* coords, const float* value, const float* mask, float mask_scale, int P, int ppg, int h8, int w8, float* out,
+                                int64_t out_sb, int64_t out_st, int64_t out_sc) {
+    ConvexUpParams p = {};
+    p.coords = coords;
+    p.value = value;
+    p.mask = mask;
+    p.mask_ld = 576;
+    p.mask_scale = mask_scale;
+    p.C = C;
+    p.P = P;
+    p.ppg = ppg;
+    p.h8 = h8;
+    p.w8 = w8;
+    p.out = out;
+    p.out_sb = out_sb;
+    p.out_st = out_st;
+    p.out_sc = out_sc;
+    return p;
 }
 
 int launch_convex_upsample(const ConvexUpParams& p, hipStream_t s) {
-    hipLaunchKernelGGL(convex_upsample_kernel, dim3(grid_for((int64_t)p.P * 64 * p.h8 * p.w8)), dim3(256), 0, s, p);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_flat(p.C == 2 ? convex_upsample_kernel<2> : convex_upsample_kernel<1>, (int64_t)p.P * 64 * p.h8 * p.w8, s, p);
 }
 
 int launch_flow_low(const float* coords, int P, int h8, int w8, float* out, hipStream_t s) {
-    hipLaunchKernelGGL(flow_low_kernel, dim3(grid_for((int64_t)2 * P * h8 * w8)), dim3(256), 0, s, coords, P, h8, w8, out);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_flat(flow_low_kernel, (int64_t)2 * P * h8 * w8, s, coords, P, h8, w8, out);
 }
 
 int launch_head_project(const float* hidden, int ld, const float* w, const float* bias, int64_t M, float* value, hipStream_t s) {
     CWM_REQUIRE(ld >= kHeadHidden && ld % 4 == 0 && ((uintptr_t)hidden & 15) == 0 && ((uintptr_t)w & 15) == 0,
                 "head_project: rows of %d floats and 16-byte aligned operands are required (ld = %d)", kHeadHidden, ld);
     hipLaunchKernelGGL(head_project_kernel, dim3(grid_for(M * kWave)), dim3(256), 0, s, hidden, ld, w, bias, M, value);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-int launch_convex_upsample1(const ConvexUp1Params& p, hipStream_t s) {
-    hipLaunchKernelGGL(convex_upsample1_kernel, dim3(grid_for((int64_t)p.P * 64 * p.h8 * p.w8)), dim3(256), 0, s, p);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }

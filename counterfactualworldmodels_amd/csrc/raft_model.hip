@@ -7,7 +7,11 @@
 // the upsampling run once, after the last iteration (the reference computes them every iteration and returns the last), unless a call asks for
 // every iteration's prediction (cwm_raft_forward_ex: flow_iters_dev / head_iters_dev; the same entry point takes the warm start, flow_init_dev).  So does the optional
 // output head (raft_model.py:152-159, output_dim = 1: the keypoint predictor): output_block.0 as one more 3x3 convolution, then the 256 -> 1
-// projection and the one-channel convex upsampling as kernels of their own (raft_kernels.hip).
+// projection as a kernel of its own and the convex upsampling kernel once more, on one channel (raft_kernels.hip).
+// The state dict lives in the engine's slot table (engine.h Slot: the raw fp32 tensors as vector slots, num_batches_tracked ignored; the head's keys and
+// num_batches_tracked optional); prepare() packs the convolutions from it when Engine::loads has moved.  What a convolution launch is made of (geometry,
+// packing of the weight parts, GEMM params) is stated once in raft_kernels.hip, for this file and for dev.hip's cwm_dev_raft_conv; the correlation pyramid
+// once here (build_pyramid), for the forward and the stand-alone lookup.
 #include <stddef.h>
 
 #include "engine.h"
@@ -20,15 +24,6 @@ constexpr int kMaxPlanes = 2;  // the im2col workspaces hold the parity layout, 
 constexpr int kFeat = 256;  // fnet output width
 constexpr int kLookupKpad = 384;  // 4 levels x 81 = 324 correlation features, padded to the GEMM's K granule
 constexpr int kMaxEncImages = 32;  // images per encoder pass (bounds the im2col buffer: 29 MB per 224^2 image)
-
-struct Raw {
-    std::vector<int64_t> shape;
-    int64_t numel = 0;
-    float* dev = nullptr;
-    bool loaded = false;
-    bool required = true;
-    bool head = false;  // output_block.*: loaded only by models with the output head; not counted as missing
-};
 
 struct ConvPart {
     std::string w, b, bn;  // weight / bias keys; bn: prefix of the batch norm folded into this convolution ("" = none)
@@ -56,8 +51,7 @@ struct Encoder {
 const char* const kHeadKeys[4] = {"output_block.0.weight", "output_block.0.bias", "output_block.2.weight", "output_block.2.bias"};
 
 ConvSrc src_of(const float* p, int C, const float* stats = nullptr, int relu = 0, int ld = 0) {
-    ConvSrc s;
-    memset(&s, 0, sizeof(s));
+    ConvSrc s = {};
     s.p = p;
     s.C = C;
     s.ld = ld ? ld : C;
@@ -69,10 +63,9 @@ ConvSrc src_of(const float* p, int C, const float* stats = nullptr, int relu = 0
 }  // namespace
 
 struct cwm_raft_model {
-    Engine eng;
-    std::map<std::string, Raw> raw;
+    Engine eng;  // its slot table holds the raw fp32 tensors of the state dict (Slot::dst), from which prepare() packs the convolutions
     std::vector<RaftConv*> convs;
-    bool dirty = true;
+    uint64_t packed_at = ~0ull;  // eng.loads when the convolutions were last packed
     Encoder fnet, cnet;
     RaftConv convc1, convc2, convf1, convf2, conv, zr[2], q[2], fh1, fh2, mask0, mask2, out0;
     // workspace (cached by shape)
@@ -88,18 +81,12 @@ struct cwm_raft_model {
 
 namespace {
 
-void add_raw(cwm_raft_model* m, const std::string& key, std::vector<int64_t> shape, bool required = true) {
-    Raw r;
-    r.shape = shape;
-    r.numel = 1;
-    for (auto v : shape) r.numel *= v;
-    r.required = required;
-    m->raw[key] = r;
-}
+const Slot& slot(cwm_raft_model* m, const std::string& key) { return m->eng.slots.at(key); }
 
 void add_bn(cwm_raft_model* m, const std::string& pre, int c) {
-    for (const char* p : {"weight", "bias", "running_mean", "running_var"}) add_raw(m, pre + "." + p, {c});
-    add_raw(m, pre + ".num_batches_tracked", {}, false);
+    for (const char* p : {"weight", "bias", "running_mean", "running_var"}) m->eng.add_vec_slot(pre + "." + p, nullptr, {c});
+    m->eng.add_ignored_slot(pre + ".num_batches_tracked", {});
+    m->eng.slots[pre + ".num_batches_tracked"].optional = true;
 }
 
 int make_conv(cwm_raft_model* m, RaftConv& cv, std::vector<ConvPart> parts, int cin, int kh, int kw, int stride, int pad_h, int pad_w) {
@@ -112,8 +99,8 @@ int make_conv(cwm_raft_model* m, RaftConv& cv, std::vector<ConvPart> parts, int 
     cv.parts = parts;
     int n = 0;
     for (auto& p : parts) {
-        add_raw(m, p.w, {p.n, cin, kh, kw});
-        add_raw(m, p.b, {p.n});
+        m->eng.add_vec_slot(p.w, nullptr, {p.n, cin, kh, kw});
+        m->eng.add_vec_slot(p.b, nullptr, {p.n});
         n += p.n;
     }
     m->convs.push_back(&cv);
@@ -152,38 +139,32 @@ int make_encoder(cwm_raft_model* m, Encoder& e, const std::string& pre, bool ins
     return make_conv(m, e.conv2, {{pre + "conv2.weight", pre + "conv2.bias", "", out_dim}}, 128, 1, 1, 1, 0, 0);
 }
 
+// Packs every convolution whose weights are loaded (the caller has checked that none but the optional ones is missing), when a load has changed one
 int prepare(cwm_raft_model* m) {
-    if (!m->dirty) return 0;
-    char buf[256];
-    const int missing = cwm_raft_missing_weights(m, buf, sizeof(buf));
-    CWM_REQUIRE(missing == 0, "cwm_raft_forward: %d weights missing (first: %s)", missing, buf);
+    if (m->packed_at == m->eng.loads) return 0;
     for (RaftConv* cv : m->convs) {
-        int row0 = 0;
-        if (!m->raw[cv->parts[0].w].loaded || !m->raw[cv->parts[0].b].loaded) continue;  // output_block.0 of a model without the head
+        if (!slot(m, cv->parts[0].w).loaded || !slot(m, cv->parts[0].b).loaded) continue;  // output_block.0 of a model without the head
+        std::vector<ConvPartW> parts;
         for (auto& p : cv->parts) {
-            const float *g = nullptr, *be = nullptr, *mu = nullptr, *var = nullptr;
+            ConvPartW w = {slot(m, p.w).dst, slot(m, p.b).dst, nullptr, nullptr, nullptr, nullptr, p.n};
             if (!p.bn.empty()) {
-                g = m->raw[p.bn + ".weight"].dev;
-                be = m->raw[p.bn + ".bias"].dev;
-                mu = m->raw[p.bn + ".running_mean"].dev;
-                var = m->raw[p.bn + ".running_var"].dev;
+                w.gamma = slot(m, p.bn + ".weight").dst;
+                w.beta = slot(m, p.bn + ".bias").dst;
+                w.mean = slot(m, p.bn + ".running_mean").dst;
+                w.var = slot(m, p.bn + ".running_var").dst;
             }
-            if (int rc = launch_pack_conv(m->raw[p.w].dev, m->raw[p.b].dev, g, be, mu, var, 1e-5f, p.n, cv->cin, cv->kh, cv->kw, cv->L.Kpad, row0, cv->L.w_il,
-                                          cv->L.w, cv->L.bias, 0))
-                return rc;
-            row0 += p.n;
+            parts.push_back(w);
         }
+        if (int rc = pack_conv_parts(parts.data(), (int)parts.size(), 1e-5f, cv->cin, cv->kh, cv->kw, cv->L.Kpad, cv->L.w_il, cv->L.w, cv->L.bias, 0)) return rc;
     }
     CWM_HIP_CHECK(hipGetLastError());
     CWM_HIP_CHECK(hipDeviceSynchronize());
-    m->dirty = false;
+    m->packed_at = m->eng.loads;
     return 0;
 }
 
-int level_sides(int s, int l) {
-    for (int i = 0; i < l; ++i) s /= 2;
-    return s;
-}
+// side of pyramid level l (avg_pool2d(2, stride 2), floor, l times)
+int level_sides(int s, int l) { return s >> l; }
 
 int ensure_workspace(cwm_raft_model* m, int P, int H, int W) {
     if (m->ws_P >= P && m->ws_H == H && m->ws_W == W) return 0;
@@ -215,30 +196,15 @@ int ensure_workspace(cwm_raft_model* m, int P, int H, int W) {
 // the operand layout of `planes`
 int run_conv(cwm_raft_model* m, const RaftConv& cv, Im2colParams ip, int n_img, int H, int W, bf16* A, float* C, int ldc, int planes, hipStream_t s,
              bool skip_im2col = false) {
-    ip.n_img = n_img;
-    ip.H = H;
-    ip.W = W;
-    ip.kh = cv.kh;
-    ip.kw = cv.kw;
-    ip.stride = cv.stride;
-    ip.pad_h = cv.pad_h;
-    ip.pad_w = cv.pad_w;
-    ip.OH = (H + 2 * cv.pad_h - cv.kh) / cv.stride + 1;
-    ip.OW = (W + 2 * cv.pad_w - cv.kw) / cv.stride + 1;
+    set_conv_geometry(ip, n_img, H, W, cv.kh, cv.kw, cv.stride, cv.pad_h, cv.pad_w, cv.L.Kpad);
     ip.A = A;
-    ip.Kpad = cv.L.Kpad;
     if (!skip_im2col)
         if (int rc = launch_im2col(ip, planes, s)) return rc;
-    GemmParams g = gemm_base(A, cv.L.Kpad, cv.L, n_img * ip.OH * ip.OW, planes);
-    g.epi = EPI_F32;
-    g.C = C;
-    g.ldc = ldc;
-    return m->eng.run_gemm(g, planes, s);
+    return m->eng.run_gemm(conv_gemm(A, planes == 2 ? cv.L.w_il : cv.L.w, cv.L.bias, n_img * ip.OH * ip.OW, cv.L.N, cv.L.Kpad, C, ldc), planes, s);
 }
 
 Im2colParams im2col_of(const ConvSrc& a, const ConvSrc* b = nullptr) {
-    Im2colParams ip;
-    memset(&ip, 0, sizeof(ip));
+    Im2colParams ip = {};
     ip.src[0] = a;
     ip.nsrc = 1;
     if (b) {
@@ -287,6 +253,26 @@ int run_encoder(cwm_raft_model* m, const Encoder& e, const ImageSrc& image, int 
     return run_conv(m, e.conv2, im2col_of(a), n, h, w, m->enc_A, out, e.conv2.L.N, planes, s);
 }
 
+// CorrBlock.__init__ and the params of its lookups: the all-pairs correlation of two feature maps [P][h8 * w8][256] into pyr[0], its three poolings into
+// pyr[1 .. 3] (level l: [M][h8 >> l][w8 >> l]), and `lp` over them at `coords`; the destination (A, or out / out_ld) is the caller's
+int build_pyramid(const float* fmap1, const float* fmap2, const float* coords, int P, int h8, int w8, float* const* pyr, CorrLookupParams& lp, hipStream_t s) {
+    const int64_t M = (int64_t)P * h8 * w8;
+    lp = CorrLookupParams{};
+    lp.levels = 4;
+    lp.coords = coords;
+    lp.M = M;
+    lp.Kpad = kLookupKpad;
+    if (int rc = launch_corr(fmap1, fmap2, P, h8 * w8, kFeat, pyr[0], s)) return rc;
+    for (int l = 0; l < 4; ++l) {
+        lp.pyr[l] = pyr[l];
+        lp.h[l] = level_sides(h8, l);
+        lp.w[l] = level_sides(w8, l);
+        if (l > 0)
+            if (int rc = launch_corr_pool(pyr[l - 1], M, lp.h[l - 1], lp.w[l - 1], pyr[l], s)) return rc;
+    }
+    return 0;
+}
+
 // What cwm_raft_forward_ex adds to a forward; all null: the plain forward of cwm_raft_forward, launch for launch.
 struct ForwardExtras {
     const float* init = nullptr;  // flow_init: coords1 = grid + init
@@ -305,15 +291,8 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a, const ForwardExtr
     const int64_t hw8 = (int64_t)h8 * w8, M = P * hw8;
     int rc;
     if ((rc = prepare(m)) || (rc = ensure_workspace(m, P, H, W))) return rc;
-    ImageSrc img;
-    memset(&img, 0, sizeof(img));
-    img.base[0] = a.image1_dev;
-    img.base[1] = a.image2_dev;
-    img.sb[0] = a.image1_stride_b; img.st[0] = a.image1_stride_t; img.sc[0] = a.image1_stride_c;
-    img.sb[1] = a.image2_stride_b; img.st[1] = a.image2_stride_t; img.sc[1] = a.image2_stride_c;
-    img.P = P;
-    img.ppg = ppg;
-    img.scale = a.input_scale;
+    const ImageSrc img = {{a.image1_dev, a.image2_dev},           {a.image1_stride_b, a.image2_stride_b}, {a.image1_stride_t, a.image2_stride_t},
+                          {a.image1_stride_c, a.image2_stride_c}, P, ppg, a.input_scale};
     // feature network over image1 and image2 of every pair (instance norm is per image: any grouping gives the same result)
     for (int i0 = 0; i0 < 2 * P; i0 += kMaxEncImages) {
         const int n = std::min(kMaxEncImages, 2 * P - i0);
@@ -326,27 +305,15 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a, const ForwardExtr
     }
     if ((rc = launch_cnet_split(m->cn, M, m->h, m->x, s))) return rc;
     // correlation pyramid
-    if ((rc = launch_corr(m->fmap, m->fmap + M * kFeat, P, (int)hw8, kFeat, m->pyr[0], s))) return rc;
     CorrLookupParams lp;
-    memset(&lp, 0, sizeof(lp));
-    lp.levels = 4;
-    for (int l = 0; l < 4; ++l) {
-        lp.pyr[l] = m->pyr[l];
-        lp.h[l] = level_sides(h8, l);
-        lp.w[l] = level_sides(w8, l);
-        if (l > 0 && (rc = launch_corr_pool(m->pyr[l - 1], M, lp.h[l - 1], lp.w[l - 1], m->pyr[l], s))) return rc;
-    }
-    lp.coords = m->coords;
-    lp.M = M;
+    if ((rc = build_pyramid(m->fmap, m->fmap + M * kFeat, m->coords, P, h8, w8, m->pyr, lp, s))) return rc;
     lp.A = m->corrA;
-    lp.Kpad = kLookupKpad;
     if (ex.init) {
         if ((rc = launch_coords_init_flow(m->coords, P, ppg, h8, w8, ex.init, ex.init_sb, ex.init_st, ex.init_sc, s))) return rc;
     } else if ((rc = launch_coords_init(m->coords, M, h8, w8, s))) {
         return rc;
     }
-    ConvSrc flow_src;
-    memset(&flow_src, 0, sizeof(flow_src));
+    ConvSrc flow_src = {};
     flow_src.C = 2;
     flow_src.coords = m->coords;
     const bool per_iter = ex.flow_iters || ex.head_iters;
@@ -360,20 +327,8 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a, const ForwardExtr
             if ((rc = run_conv(m, m->mask2, im2col_of(src_of(m->fh, 256, nullptr, 1)), P, h8, w8, m->updA, m->mask, 576, planes, s))) return rc;
         }
         if (flow_out) {
-            ConvexUpParams up;
-            memset(&up, 0, sizeof(up));
-            up.coords = m->coords;
-            up.mask = m->mask;
-            up.mask_ld = 576;
-            up.mask_scale = 0.25f;
-            up.P = P;
-            up.ppg = ppg;
-            up.h8 = h8;
-            up.w8 = w8;
-            up.out = flow_out;
-            up.out_sb = a.flow_stride_b;
-            up.out_st = a.flow_stride_t;
-            up.out_sc = a.flow_stride_c;
+            const ConvexUpParams up =
+                convex_up_params(2, m->coords, nullptr, m->mask, 0.25f, P, ppg, h8, w8, flow_out, a.flow_stride_b, a.flow_stride_t, a.flow_stride_c);
             if ((rc = launch_convex_upsample(up, s))) return rc;
         }
         if (flow_low && (rc = launch_flow_low(m->coords, P, h8, w8, flow_low, s))) return rc;
@@ -381,21 +336,9 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a, const ForwardExtr
             // out = output_block.2(relu(output_block.0(net))), upsampled with the same mask in place of the flow (raft_model.py:257-267).  `fh` is free
             // once mask.2 has read it, and `d` (the flow head's delta) once this iteration's flow update has: the projected map goes there.
             if ((rc = run_conv(m, m->out0, im2col_of(src_of(m->h, 128)), P, h8, w8, m->updA, m->fh, 256, planes, s))) return rc;
-            if ((rc = launch_head_project(m->fh, 256, m->raw[kHeadKeys[2]].dev, m->raw[kHeadKeys[3]].dev, M, m->d, s))) return rc;
-            ConvexUp1Params u1;
-            memset(&u1, 0, sizeof(u1));
-            u1.value = m->d;
-            u1.mask = m->mask;
-            u1.mask_ld = 576;
-            u1.mask_scale = 0.25f;
-            u1.P = P;
-            u1.ppg = ppg;
-            u1.h8 = h8;
-            u1.w8 = w8;
-            u1.out = head_out;
-            u1.out_sb = a.head_stride_b;
-            u1.out_st = a.head_stride_t;
-            if ((rc = launch_convex_upsample1(u1, s))) return rc;
+            if ((rc = launch_head_project(m->fh, 256, slot(m, kHeadKeys[2]).dst, slot(m, kHeadKeys[3]).dst, M, m->d, s))) return rc;
+            const ConvexUpParams up = convex_up_params(1, nullptr, m->d, m->mask, 0.25f, P, ppg, h8, w8, head_out, a.head_stride_b, a.head_stride_t, 0);
+            if ((rc = launch_convex_upsample(up, s))) return rc;
         }
         return 0;
     };
@@ -464,11 +407,11 @@ extern "C" int cwm_raft_create(cwm_raft_model** out) {
             (rc = make_conv(m, m->mask2, {part("mask.2", 576)}, 256, 1, 1, 1, 0, 0)))
             break;
         if ((rc = make_conv(m, m->out0, {ConvPart{kHeadKeys[0], kHeadKeys[1], "", kHeadHidden}}, 128, 3, 3, 1, 1, 1))) break;
-        add_raw(m, kHeadKeys[2], {1, kHeadHidden, 1, 1});
-        add_raw(m, kHeadKeys[3], {1});
-        for (const char* k : kHeadKeys) m->raw[k].head = true;
-        for (auto& kv : m->raw)
-            if ((rc = m->eng.alloc((void**)&kv.second.dev, (size_t)std::max<int64_t>(kv.second.numel, 1) * sizeof(float), true, false))) break;
+        m->eng.add_vec_slot(kHeadKeys[2], nullptr, {1, kHeadHidden, 1, 1});
+        m->eng.add_vec_slot(kHeadKeys[3], nullptr, {1});
+        for (const char* k : kHeadKeys) m->eng.slots[k].optional = true;  // loaded only by models with the output head, which a forward that asks for it checks
+        for (auto& kv : m->eng.slots)  // the raw fp32 tensors (registered above without a buffer): every vector slot's destination
+            if (kv.second.kind == SLOT_VECTOR && (rc = m->eng.make_vec(&kv.second.dst, (int)kv.second.numel))) break;
     } while (0);
     if (rc) {
         delete m;
@@ -483,32 +426,11 @@ extern "C" void cwm_raft_destroy(cwm_raft_model* m) { delete m; }
 extern "C" int cwm_raft_load_weight(cwm_raft_model* m, const char* key, const float* data, int on_device, const int64_t* shape, int ndim) {
     CWM_REQUIRE(m && key && data && (shape || ndim == 0), "cwm_raft_load_weight: null argument");
     if (int rc = cwm_require_device(m->eng.device, "cwm_raft_load_weight")) return rc;
-    auto it = m->raw.find(key);
-    CWM_REQUIRE(it != m->raw.end(), "unexpected key in state_dict: %s", key);
-    Raw& r = it->second;
-    bool same = (int)r.shape.size() == ndim;
-    for (int i = 0; same && i < ndim; ++i) same = r.shape[i] == shape[i];
-    CWM_REQUIRE(same, "size mismatch for %s", key);
-    if (!r.required) {  // num_batches_tracked: accepted, not used
-        r.loaded = true;
-        return CWM_OK;
-    }
-    CWM_HIP_CHECK(hipMemcpy(r.dev, data, (size_t)r.numel * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    r.loaded = true;
-    m->dirty = true;
-    return CWM_OK;
+    static const int64_t no_shape = 0;  // a 0-dimensional tensor (num_batches_tracked) may come with a null shape
+    return m->eng.load_weight(key, data, on_device, shape ? shape : &no_shape, ndim);
 }
 
-extern "C" int cwm_raft_missing_weights(cwm_raft_model* m, char* buf, int buflen) {
-    int missing = 0;
-    if (buf && buflen > 0) buf[0] = 0;
-    for (auto& kv : m->raw)
-        if (kv.second.required && !kv.second.head && !kv.second.loaded) {
-            if (!missing && buf && buflen > 0) snprintf(buf, buflen, "%s", kv.first.c_str());
-            ++missing;
-        }
-    return missing;
-}
+extern "C" int cwm_raft_missing_weights(cwm_raft_model* m, char* buf, int buflen) { return m->eng.missing_weights(buf, buflen); }
 
 namespace {
 
@@ -539,11 +461,11 @@ int checked_forward(cwm_raft_model* m, const cwm_raft_forward_args* args, const 
     const int64_t M = (int64_t)a.batch * std::max(a.pairs, 1) * (a.height / 8) * (a.width / 8);
     CWM_REQUIRE(M * 2304 * planes < (1ll << 32), "%s: batch too large (%lld low-resolution pixels): split it", fn, (long long)M);
     char buf[256];
-    const int missing = cwm_raft_missing_weights(m, buf, sizeof(buf));
+    const int missing = m->eng.missing_weights(buf, sizeof(buf));
     CWM_REQUIRE(missing == 0, "%s: %d weights missing (first: %s)", fn, missing, buf);
     if (a.head_dev || ex.head_iters)
         for (const char* k : kHeadKeys)
-            CWM_REQUIRE(m->raw[k].loaded, "%s: the output head was asked for (%s) but %s is not loaded", fn, a.head_dev ? "head_dev" : "head_iters_dev", k);
+            CWM_REQUIRE(slot(m, k).loaded, "%s: the output head was asked for (%s) but %s is not loaded", fn, a.head_dev ? "head_dev" : "head_iters_dev", k);
     return forward(m, a, ex);
 }
 
@@ -575,26 +497,16 @@ extern "C" int cwm_raft_forward_ex(cwm_raft_model* m, const cwm_raft_forward_ex_
 // ---- stand-alone kernels (kernel tests) -------------------------------------------------------------------------------
 int cwm::raft_corr_lookup_run(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev, bf16* A,
                               int planes, hipStream_t s) {
-    const int64_t N = (int64_t)h8 * w8, M = P * N;
+    const int64_t M = (int64_t)P * h8 * w8;
     float* pyr[4] = {nullptr, nullptr, nullptr, nullptr};
     int rc = 0;
-    CorrLookupParams lp;
-    memset(&lp, 0, sizeof(lp));
-    lp.levels = 4;
-    for (int l = 0; l < 4 && !rc; ++l) {
-        lp.h[l] = level_sides(h8, l);
-        lp.w[l] = level_sides(w8, l);
-        if (hipMalloc((void**)&pyr[l], (size_t)M * lp.h[l] * lp.w[l] * sizeof(float)) != hipSuccess) {
+    for (int l = 0; l < 4 && !rc; ++l)
+        if (hipMalloc((void**)&pyr[l], (size_t)M * level_sides(h8, l) * level_sides(w8, l) * sizeof(float)) != hipSuccess) {
             cwm_set_error("cwm_raft_corr_lookup: out of device memory");
             rc = CWM_ERR_HIP;
         }
-        lp.pyr[l] = pyr[l];
-    }
-    if (!rc) rc = launch_corr(fmap1_dev, fmap2_dev, P, (int)N, kFeat, pyr[0], s);
-    for (int l = 1; l < 4 && !rc; ++l) rc = launch_corr_pool(pyr[l - 1], M, lp.h[l - 1], lp.w[l - 1], pyr[l], s);
-    lp.coords = coords_dev;
-    lp.M = M;
-    lp.Kpad = kLookupKpad;
+    CorrLookupParams lp = {};
+    if (!rc) rc = build_pyramid(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, pyr, lp, s);
     if (out_dev) {
         lp.out = out_dev;
         lp.out_ld = 324;
@@ -619,20 +531,8 @@ extern "C" int cwm_raft_corr_lookup(const float* fmap1_dev, const float* fmap2_d
 
 extern "C" int cwm_raft_convex_upsample(const float* flow_dev, const float* mask_dev, int P, int h8, int w8, float* out_dev, void* stream) {
     CWM_REQUIRE(flow_dev && mask_dev && out_dev && P > 0 && h8 > 0 && w8 > 0, "cwm_raft_convex_upsample: bad argument");
-    ConvexUpParams up;
-    memset(&up, 0, sizeof(up));
-    up.flow = flow_dev;
-    up.mask = mask_dev;
-    up.mask_ld = 576;
-    up.mask_scale = 1.f;
-    up.P = P;
-    up.ppg = 1;
-    up.h8 = h8;
-    up.w8 = w8;
-    up.out = out_dev;
-    up.out_sb = (int64_t)2 * 64 * h8 * w8;
-    up.out_sc = (int64_t)64 * h8 * w8;
-    return launch_convex_upsample(up, (hipStream_t)stream);
+    const int64_t plane = (int64_t)64 * h8 * w8;
+    return launch_convex_upsample(convex_up_params(2, nullptr, flow_dev, mask_dev, 1.f, P, 1, h8, w8, out_dev, 2 * plane, 0, plane), (hipStream_t)stream);
 }
 
 extern "C" int cwm_raft_head_project(const float* hidden_dev, const float* weight_dev, const float* bias_dev, int64_t M, float* value_dev, void* stream) {
@@ -642,17 +542,5 @@ extern "C" int cwm_raft_head_project(const float* hidden_dev, const float* weigh
 
 extern "C" int cwm_raft_convex_upsample1(const float* value_dev, const float* mask_dev, int P, int h8, int w8, float* out_dev, void* stream) {
     CWM_REQUIRE(value_dev && mask_dev && out_dev && P > 0 && h8 > 0 && w8 > 0, "cwm_raft_convex_upsample1: bad argument");
-    ConvexUp1Params up;
-    memset(&up, 0, sizeof(up));
-    up.value = value_dev;
-    up.mask = mask_dev;
-    up.mask_ld = 576;
-    up.mask_scale = 1.f;
-    up.P = P;
-    up.ppg = 1;
-    up.h8 = h8;
-    up.w8 = w8;
-    up.out = out_dev;
-    up.out_sb = (int64_t)64 * h8 * w8;
-    return launch_convex_upsample1(up, (hipStream_t)stream);
+    return launch_convex_upsample(convex_up_params(1, nullptr, value_dev, mask_dev, 1.f, P, 1, h8, w8, out_dev, (int64_t)64 * h8 * w8, 0, 0), (hipStream_t)stream);
 }

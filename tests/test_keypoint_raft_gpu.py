@@ -1,4 +1,4 @@
-"""The keypoint RAFT (`output_dim=1`: the output head of csrc/raft_model.hip, `head_project_kernel` / `convex_upsample1_kernel` of
+"""The keypoint RAFT (`output_dim=1`: the output head of csrc/raft_model.hip, `head_project_kernel` / `convex_upsample_kernel<1>` of
 csrc/raft_kernels.hip) on the GPU against the reference's golden outputs (tests/golden/make_golden_movability.py), its stand-alone kernels
 against torch restatements, and the C ABI around it (optional weights, `struct_size` versions).
 
@@ -13,11 +13,11 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from counterfactualworldmodels_amd import _lib, synthetic as S
 from counterfactualworldmodels_amd.prediction import PredictorBasedGenerator
 from counterfactualworldmodels_amd.raft import RAFT, _args, load_raft_model
+from test_raft_gpu import CONVEX_SHAPES, convex_case, padded_out, upsample_restated
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -147,23 +147,20 @@ def test_head_project_kernel_vs_restatement():
 def test_convex_upsample1_kernel_vs_restatement():
     lib = _lib.get_lib()
     g = torch.Generator().manual_seed(6)
-    P, h, w = 3, 16, 19
-    value = (3.0 * torch.randn(P, 1, h, w, generator=g)).cuda()
-    mask = (2.0 * torch.randn(P, h, w, 576, generator=g)).cuda()
-    out = torch.empty(P, 1, 8 * h, 8 * w, device="cuda")
-    _lib.check(lib.cwm_raft_convex_upsample1(value.data_ptr(), mask.data_ptr(), P, h, w, out.data_ptr(), None))
-    torch.cuda.synchronize()
-    m = torch.softmax(mask.permute(0, 3, 1, 2).reshape(P, 1, 9, 8, 8, h, w), dim=2)  # RAFT.upsample_flow (raft_model.py:177-188), C = 1
-    up = F.unfold(8 * value, [3, 3], padding=1).view(P, 1, 9, 1, 1, h, w)
-    ref = torch.sum(m * up, dim=2).permute(0, 1, 4, 2, 5, 3).reshape(P, 1, 8 * h, 8 * w)
-    err = (out - ref).abs().max().item()
-    print(f"[convex upsample, one channel] max-abs {err:.3e}")
-    assert err <= 1e-4
-    # one channel of the two-channel kernel computes the same thing
-    two = torch.empty(P, 2, 8 * h, 8 * w, device="cuda")
-    _lib.check(lib.cwm_raft_convex_upsample(value.expand(P, 2, h, w).contiguous().data_ptr(), mask.data_ptr(), P, h, w, two.data_ptr(), None))
-    torch.cuda.synchronize()
-    assert (two[:, :1] - out).abs().max().item() <= 1e-5
+    for P, h, w in CONVEX_SHAPES:
+        value, mask = convex_case(1, P, h, w, g)
+        out, guard = padded_out(P, 1, h, w)
+        _lib.check(lib.cwm_raft_convex_upsample1(value.data_ptr(), mask.data_ptr(), P, h, w, out.data_ptr(), None))
+        torch.cuda.synchronize()
+        err = (out - upsample_restated(value, mask)).abs().max().item()  # RAFT.upsample_flow (raft_model.py:177-188), C = 1
+        print(f"[convex upsample, one channel {P}x{h}x{w}] max-abs {err:.3e}")
+        assert err <= 1e-4
+        assert torch.all(guard == -77.0)
+        # one kernel is behind both entry points: channel 0 of the two-channel call on the same mask is the same bits
+        two = torch.empty(P, 2, 8 * h, 8 * w, device="cuda")
+        _lib.check(lib.cwm_raft_convex_upsample(value.expand(P, 2, h, w).contiguous().data_ptr(), mask.data_ptr(), P, h, w, two.data_ptr(), None))
+        torch.cuda.synchronize()
+        assert torch.equal(two[:, :1], out) and torch.equal(two[:, 1:], out)
 
 
 # ---- the C ABI around the head ------------------------------------------------------------------------------------------------

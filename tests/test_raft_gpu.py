@@ -126,21 +126,48 @@ def test_corr_lookup_kernel_vs_restatement():
     assert (ref == 0).any()  # the test reaches the zero padding
 
 
+def upsample_restated(field, mask):
+    """RAFT.upsample_flow (raft_model.py:177-188) of a field [P, C, h, w] with the mask [P, h, w, 576], on the device of its inputs."""
+    P, C, h, w = field.shape
+    m = torch.softmax(mask.permute(0, 3, 1, 2).reshape(P, 1, 9, 8, 8, h, w), dim=2)
+    up = F.unfold(8 * field, [3, 3], padding=1).view(P, C, 9, 1, 1, h, w)
+    return torch.sum(m * up, dim=2).permute(0, 1, 4, 2, 5, 3).reshape(P, C, 8 * h, 8 * w)
+
+
+# 2 x 3 x 5: fourteen of the fifteen low-resolution pixels touch a border (every zero-padded neighbour pattern, the four corners included), and the 1920 outputs
+# per channel are no multiple of 256: the last workgroup is partial
+CONVEX_SHAPES = ((3, 16, 19), (2, 3, 5))
+
+
+def convex_case(C, P, h, w, g):
+    """Inputs of one convex-upsampling case on the GPU: the field [P, C, h, w] and the mask; the restatement is checked on the CPU first (finite, and no
+    channel constant: at a shape this small a degenerate reference would pass anything)."""
+    field = 3.0 * torch.randn(P, C, h, w, generator=g)
+    mask = 2.0 * torch.randn(P, h, w, 576, generator=g)
+    ref = upsample_restated(field, mask)
+    assert ref.shape == (P, C, 8 * h, 8 * w) and torch.isfinite(ref).all() and (ref.flatten(2).std(dim=2) > 0).all()
+    return field.cuda(), mask.cuda()
+
+
+def padded_out(P, C, h, w):
+    """An output buffer with 64 floats behind it that no launch may touch: (view, the guard)."""
+    n = P * C * 64 * h * w
+    buf = torch.full((n + 64,), -77.0, device="cuda")
+    return buf[:n].view(P, C, 8 * h, 8 * w), buf[n:]
+
+
 def test_convex_upsample_kernel_vs_restatement():
     lib = _lib.get_lib()
     g = torch.Generator().manual_seed(4)
-    P, h, w = 3, 16, 19
-    flow = (3.0 * torch.randn(P, 2, h, w, generator=g)).cuda()
-    mask = (2.0 * torch.randn(P, h, w, 576, generator=g)).cuda()
-    out = torch.empty(P, 2, 8 * h, 8 * w, device="cuda")
-    _lib.check(lib.cwm_raft_convex_upsample(flow.data_ptr(), mask.data_ptr(), P, h, w, out.data_ptr(), None))
-    torch.cuda.synchronize()
-    m = torch.softmax(mask.permute(0, 3, 1, 2).reshape(P, 1, 9, 8, 8, h, w), dim=2)
-    up = F.unfold(8 * flow, [3, 3], padding=1).view(P, 2, 9, 1, 1, h, w)
-    ref = torch.sum(m * up, dim=2).permute(0, 1, 4, 2, 5, 3).reshape(P, 2, 8 * h, 8 * w)
-    err = (out - ref).abs().max().item()
-    print(f"[convex upsample] max-abs {err:.3e}")
-    assert err <= 1e-4
+    for P, h, w in CONVEX_SHAPES:
+        flow, mask = convex_case(2, P, h, w, g)
+        out, guard = padded_out(P, 2, h, w)
+        _lib.check(lib.cwm_raft_convex_upsample(flow.data_ptr(), mask.data_ptr(), P, h, w, out.data_ptr(), None))
+        torch.cuda.synchronize()
+        err = (out - upsample_restated(flow, mask)).abs().max().item()
+        print(f"[convex upsample {P}x{h}x{w}] max-abs {err:.3e}")
+        assert err <= 1e-4
+        assert torch.all(guard == -77.0)
 
 
 # ---- integration, determinism, batching, errors ---------------------------------------------------------------------
