@@ -486,6 +486,7 @@ SIGNATURES = {
     "cwm_raft_convex_upsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_raft_head_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "cwm_raft_convex_upsample1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cwm_raft_forward_interpolate": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_last_error": (C.c_char_p, []),
     "cwm_version": (C.c_char_p, []),
     "cwm_source_hash": (C.c_char_p, []),

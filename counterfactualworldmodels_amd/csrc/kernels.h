@@ -375,6 +375,10 @@ int launch_gru_update(float* h, const float* zr, const float* q, int64_t M, hipS
 int launch_flow_update(float* coords, const float* delta, int ld, int64_t M, hipStream_t s);
 int launch_convex_upsample(const ConvexUpParams& p, hipStream_t s);
 int launch_flow_low(const float* coords, int P, int h8, int w8, float* out, hipStream_t s);
+// forward_interpolate (raft/utils.py:28-56) of P planar fields [2][h8][w8] (rows contiguous; field p at flow + p * stride_p, its channel c at + c * stride_c)
+// -> out [P][2][h8][w8] contiguous: every target takes the valid source that lands nearest to it (double arithmetic, lowest index among equals; zeros
+// when none is valid).  Brute force, N^2 distances per field: h8 * w8 <= 65536.  out must not overlap flow.
+int launch_forward_interpolate(const float* flow, int64_t stride_p, int64_t stride_c, int P, int h8, int w8, float* out, hipStream_t s);
 // The output head (raft_model.py:152-159, 257-267; output_dim = 1).  launch_head_project: value[m] = bias[0] + sum_c w[c] * relu(hidden[m * ld + c]) over
 // the 256 channels of output_block.0's result, fp32, one wave per low-resolution pixel; launch_convex_upsample with C = 1 then upsamples that planar map.
 constexpr int kHeadHidden = 256;

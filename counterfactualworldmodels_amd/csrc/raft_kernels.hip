@@ -337,6 +337,52 @@ __global__ void flow_low_kernel(const float* coords, int P, int h8, int w8, floa
     }
 }
 
+// forward_interpolate (raft/utils.py:28-56): carry a flow along itself.  Source pixel i = (y0, x0) of pair blockIdx.x / bpp lands at (x0 + dx[i], y0 + dy[i]),
+// in double, where the sums are exact; target g takes both channels of the valid source with the smallest squared distance, the lowest i among equals
+// (ascending scan, replaced on `<` only), zeros when no source is valid.  One target per thread; the sources pass through LDS in chunks of
+// kFinterpChunk landing points, every lane reading the same address (a broadcast).  An invalid source (landing outside the open rectangle
+// (0, w8) x (0, h8), or a NaN / infinite component) is staged as (+inf, +inf): its distance is +inf, which is never < the best, +inf at the start.
+// Products and the sum are separately rounded (no fma): the order of near-equal distances is that of the same expression in numpy.
+constexpr int kFinterpThreads = 256, kFinterpChunk = 1024;
+__global__ void __launch_bounds__(kFinterpThreads) forward_interpolate_kernel(const float* flow, int64_t stride_p, int64_t stride_c, int bpp, int h8, int w8,
+                                                                             float* out) {
+#pragma clang fp contract(off)
+    __shared__ double2 land[kFinterpChunk];
+    const int N = h8 * w8;
+    const int pr = blockIdx.x / bpp, tgt = (blockIdx.x - pr * bpp) * kFinterpThreads + threadIdx.x;
+    const float* dx = flow + pr * stride_p;
+    const float* dy = dx + stride_c;
+    const double gx = (double)(tgt % w8), gy = (double)(tgt / w8);
+    double best = INFINITY;
+    int best_i = -1;
+    for (int base = 0; base < N; base += kFinterpChunk) {
+        const int cnt = min(kFinterpChunk, N - base);
+        __syncthreads();  // the previous chunk has been read
+        for (int j = threadIdx.x; j < cnt; j += kFinterpThreads) {
+            const int i = base + j;
+            const double x1 = (double)(i % w8) + (double)dx[i], y1 = (double)(i / w8) + (double)dy[i];
+            const bool valid = x1 > 0.0 && x1 < (double)w8 && y1 > 0.0 && y1 < (double)h8;
+            land[j] = valid ? make_double2(x1, y1) : make_double2(INFINITY, INFINITY);
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int j = 0; j < cnt; ++j) {
+            const double2 s = land[j];
+            const double ex = gx - s.x, ey = gy - s.y;
+            const double d = ex * ex + ey * ey;
+            if (d < best) {
+                best = d;
+                best_i = base + j;
+            }
+        }
+    }
+    if (tgt < N) {
+        float* o = out + (int64_t)pr * 2 * N + tgt;
+        o[0] = best_i < 0 ? 0.f : dx[best_i];
+        o[N] = best_i < 0 ? 0.f : dy[best_i];
+    }
+}
+
 // output_block.2 on relu(output_block.0(net)): one wave per low-resolution pixel, four consecutive channels per lane (one 16-byte load of the
 // row and of the weight each), the 256 products summed in fp32 by the wave butterfly.
 __global__ void __launch_bounds__(256) head_project_kernel(const float* hidden, int ld, const float* w, const float* bias, int64_t M, float* value) {
@@ -528,7 +574,24 @@ int launch_flow_low(const float* coords, int P, int h8, int w8, float* out, hipS
     return launch_flat(flow_low_kernel, (int64_t)2 * P * h8 * w8, s, coords, P, h8, w8, out);
 }
 
-int launch_head_project(const float* hidden, int ld, const float* w, const float* bias, int64_t M, float* value, hipStream_t s) {
+int launch_forward_interpolate(const float* flow, int64_t stride_p, int64_t stride_c, int P, int h8, int w8, float* out, hipStream_t s) {
+    CWM_REQUIRE(flow && out && P >= 1 && h8 >= 1 && w8 >= 1, "forward_interpolate: bad argument (P = %d, grid %d x %d)", P, h8, w8);
+    const int64_t N = (int64_t)h8 * w8;
+    CWM_REQUIRE(N <= 65536, "forward_interpolate: a grid of %d x %d = %lld pixels exceeds 65536 (every target scans every source: the cost is N^2)", h8, w8,
+                (long long)N);
+    const int64_t bpp = (N + kFinterpThreads - 1) / kFinterpThreads;
+    CWM_REQUIRE(P * bpp < (1ll << 31) && 2 * P * N < (1ll << 31), "forward_interpolate: %d fields of %lld pixels exceed 32-bit indexing", P, (long long)N);
+    // what is read: rows [0, N) of channels 0, 1 of fields 0 .. P - 1 (strides of either sign); what is written: [P][2][N]
+    const int64_t lo = std::min<int64_t>(0, (P - 1) * stride_p) + std::min<int64_t>(0, stride_c);
+    const int64_t hi = std::max<int64_t>(0, (P - 1) * stride_p) + std::max<int64_t>(0, stride_c) + N;
+    const intptr_t f = (intptr_t)flow, o = (intptr_t)out, fsz = sizeof(float);
+    CWM_REQUIRE(o + 2 * P * N * fsz <= f + lo * fsz || f + hi * fsz <= o, "forward_interpolate: out overlaps flow (every target reads other pixels' sources)");
+    hipLaunchKernelGGL(forward_interpolate_kernel, dim3((unsigned)(P * bpp)), dim3(kFinterpThreads), 0, s, flow, stride_p, stride_c, (int)bpp, h8, w8, out);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_head_project(const float* hidden, int ld,const float* w, const float* bias, int64_t M, float* value, hipStream_t s) {
     CWM_REQUIRE(ld >= kHeadHidden && ld % 4 == 0 && ((uintptr_t)hidden & 15) == 0 && ((uintptr_t)w & 15) == 0,
                 "head_project: rows of %d floats and 16-byte aligned operands are required (ld = %d)", kHeadHidden, ld);
     hipLaunchKernelGGL(head_project_kernel, dim3(grid_for(M * kWave)), dim3(256), 0, s, hidden, ld, w, bias, M, value);

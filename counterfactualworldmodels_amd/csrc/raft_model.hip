@@ -535,6 +535,11 @@ extern "C" int cwm_raft_convex_upsample(const float* flow_dev, const float* mask
     return launch_convex_upsample(convex_up_params(2, nullptr, flow_dev, mask_dev, 1.f, P, 1, h8, w8, out_dev, 2 * plane, 0, plane), (hipStream_t)stream);
 }
 
+extern "C" int cwm_raft_forward_interpolate(const float* flow_dev, int64_t stride_p, int64_t stride_c, int P, int h8, int w8, float* out_dev, void* stream) {
+    CWM_REQUIRE(flow_dev && out_dev, "cwm_raft_forward_interpolate: null pointer");
+    return launch_forward_interpolate(flow_dev, stride_p, stride_c, P, h8, w8, out_dev, (hipStream_t)stream);
+}
+
 extern "C" int cwm_raft_head_project(const float* hidden_dev, const float* weight_dev, const float* bias_dev, int64_t M, float* value_dev, void* stream) {
     CWM_REQUIRE(hidden_dev && weight_dev && bias_dev && value_dev && M > 0, "cwm_raft_head_project: bad argument");
     return launch_head_project(hidden_dev, kHeadHidden, weight_dev, bias_dev, M, value_dev, (hipStream_t)stream);

@@ -11,6 +11,7 @@ upsampling.
     flows = flow_model(x, iters=24)              # x [B,T,3,H,W] in [0,1] -> [B,T-1,2,H,W] pixels
     flows_back = flow_model(x, backward=True)    # pairs (x[t+1], x[t]), in reversed order
     flows_warm = flow_model(x, flow_init=f8)     # f8 [B or 1,2,H/8,W/8]: RAFT's warm start, e.g. the previous pair's low-resolution flow
+    flows_video = flow_model(x, warm_start=True) # each pair started from forward_interpolate(low-resolution flow of the pair before), on the device
 
 With `output_dim=1` the model owns the reference's `output_block` (raft_model.py:152-159; 183 state-dict tensors) and returns its convex-upsampled
 value in place of the flow: the keypoint predictor of the demo notebook,
@@ -117,6 +118,39 @@ def _args(**kw) -> argparse.Namespace:
     return a
 
 
+def _forward_interpolate_into(src: torch.Tensor, dst: torch.Tensor) -> None:
+    """`cwm_raft_forward_interpolate` of src [P,2,h,w] (fp32, rows contiguous, any field and channel strides) into dst [P,2,h,w] (fp32, contiguous), on the
+    current stream of src's device; nothing is synchronised."""
+    P, _, h, w = src.shape
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.get_lib().cwm_raft_forward_interpolate(src.data_ptr(), src.stride(0), src.stride(1), P, h, w, dst.data_ptr(),
+                                                               _lib.current_stream_handle(src.device)))
+
+
+@torch.no_grad()
+def forward_interpolate(flow: torch.Tensor) -> torch.Tensor:
+    """raft/utils.py:28-56 on the device: the flow [2,h,w] (or P of them, [P,2,h,w]; channel 0 = x) carried along itself.  Pixel (x0, y0) lands at
+    (x0 + dx, y0 + dy); every grid point takes the flow of the source that lands nearest to it, among those landing strictly inside (0, w) x (0, h).
+    This is what RAFT's warm start feeds to the next pair as `flow_init`.  Any float dtype; a strided view is read in place when its rows are
+    contiguous.  Returns fp32 of the same shape on the same device, on the current stream, without a host synchronisation.
+    Not the reference's: equal distances go to the lowest source index (scipy's KD-tree order is its own), and a field with no valid source gives
+    zeros, a cold start (scipy returns NaN or raises)."""
+    if not torch.is_tensor(flow) or not flow.is_floating_point():
+        raise RuntimeError("forward_interpolate needs a floating-point tensor [2,h,w] or [P,2,h,w], got %r"
+                           % (type(flow).__name__ if not torch.is_tensor(flow) else flow.dtype,))
+    if not flow.is_cuda:
+        raise RuntimeError("forward_interpolate needs a CUDA/HIP tensor (no CPU fallback); got %s" % flow.device)
+    if flow.dim() not in (3, 4) or flow.shape[-3] != 2 or flow.numel() == 0:
+        raise RuntimeError("forward_interpolate expects a flow [2,h,w] or [P,2,h,w], got %s" % (tuple(flow.shape),))
+    f = flow.detach().float()
+    f = f.unsqueeze(0) if f.dim() == 3 else f
+    if f.stride(-1) != 1 or f.stride(-2) != f.shape[-1]:
+        f = f.contiguous()
+    out = torch.empty(f.shape, dtype=torch.float32, device=f.device)
+    _forward_interpolate_into(f, out)
+    return out if flow.dim() == 4 else out[0]
+
+
 class RAFT(LibraryModule):
     """Drop-in for the reference's `RAFT` (large, inference).  Calls:
     - multiframe (default): `model(x[B,T,3,H,W], iters=24, backward=False)` -> [B,T-1,2,H,W] pixel flows (flow_up of the last iteration);
@@ -128,6 +162,8 @@ class RAFT(LibraryModule):
     - `flow_init` (both calls; raft_model.py:241-242): RAFT's warm start, a flow [B,2,H/8,W/8] or [1,2,H/8,W/8] in 1/8-resolution pixels (channel 0 = x)
       added to the initial coordinates; any float dtype (cast to fp32), on the frames' device.  The multi-frame call gives the same field to every
       pair, also with backward=True, and accepts `test_mode` (its result is the last iteration's flow_up either way, raft_model.py:297).
+    - `warm_start=True` (multi-frame call): the pairs run as a chain, each started from `forward_interpolate` (this module; raft/utils.py:28-56) of the
+      low-resolution flow of the pair before it; `flow_init` then starts the first pair of the chain only (`_forward_multiframe`).
     Without `flow_init` and with test_mode=True a call is `cwm_raft_forward`: the mask head and the upsampling run once.  Otherwise it is
     `cwm_raft_forward_ex`; only test_mode=False makes them run in every iteration.
     `self.iters`, when set, overrides the call's `iters`.  H and W must be multiples of 8 with H/8, W/8 >= 16.
@@ -288,9 +324,14 @@ class RAFT(LibraryModule):
             return self._forward_two_images(*args, **kwargs)
         return self._forward_multiframe(*args, **kwargs)
 
-    def _forward_multiframe(self, x, iters=24, flow_init=None, upsample=True, test_mode=True, backward=False, **kwargs):
+    def _forward_multiframe(self, x, iters=24, flow_init=None, upsample=True, test_mode=True, backward=False, warm_start=False, **kwargs):
         """raft_model.py:276-300: the reference hands everything after x to every pair's two-image call (:297), so the arguments are those of
-        `_forward_two_images`, plus `backward`."""
+        `_forward_two_images`, plus `backward`.
+        `warm_start=True` (not in the reference's forward: RAFT's video protocol, raft/utils.py:28-56) runs the pairs one after another, all B rows per
+        library call, and starts each pair from `forward_interpolate` of the low-resolution flow of the pair before it in the chain, a field per batch row.
+        With `backward` the chain runs from the last pair to the first (the flow of (x[t+1], x[t]) lives on frame t+1's grid and is carried to frame
+        t's); the outputs keep their order.  `flow_init` then starts the first pair of the chain only; without it that pair is cold.  Nothing in the chain
+        synchronises with the host.  With T <= 2 there is no chain: the call is the one without the keyword."""
         if self.iters is not None:
             iters = self.iters
         if x.dim() != 5:
@@ -307,6 +348,19 @@ class RAFT(LibraryModule):
         else:
             first, second, pairs = x[:, :-1], x[:, 1:], T - 1
         out = torch.empty(B, pairs, self.output_dim or 2, H, W, device=x.device)
+        if warm_start and pairs > 1:
+            # two [B,2,H/8,W/8] buffers: a pair's coords1 - coords0 (the flow, also under the output head) and its forward interpolation, the next init
+            low, carried = torch.empty(2, B, 2, H // 8, W // 8, device=x.device).unbind(0)
+            strides = (out.stride(0), 0, out.stride(2))
+            for k in range(pairs):  # step k of the chain is pair t, stored at index `at`
+                t = pairs - 1 - k if backward else k
+                at = pairs - 1 - t if backward else t
+                a, b = (x[:, t + 1:t + 2], x[:, t:t + 1]) if backward else (x[:, t:t + 1], x[:, t + 1:t + 2])
+                self._run(a, b, B, 1, H, W, scale, iters, (out[:, at].data_ptr(),), strides, flow_low=low if k + 1 < pairs else None, flow_init=init)
+                if k + 1 < pairs:
+                    _forward_interpolate_into(low, carried)
+                    init = carried
+            return out
         if backward:  # pairs (x[t+1], x[t]), stored at index pairs - 1 - t
             first, second = second, first
             ptr = out.data_ptr() + (pairs - 1) * out.stride(1) * out.element_size()

@@ -132,6 +132,8 @@ class FlowGenerator(PredictorBasedGenerator):
             self.flow_model.set_iters(iters)
 
     def predict_flow(self, vid, backward=False, iters=None, **kwargs):
+        """Keyword arguments go to the flow model: with the package's RAFT, `flow_init=` (a warm start for every pair) and `warm_start=True` (a movie's
+        pairs as a chain, each started from the forward-interpolated flow of the pair before it; raft.RAFT._forward_multiframe)."""
         if self.flow_model is None:
             raise RuntimeError("this FlowGenerator has no flow_model (the reference plugs RAFT in here; any module called as "
                                "flow_model(video[B,T,C,H,W], backward=...) -> [B,T-1,2,H,W] works)")

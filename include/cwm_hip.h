@@ -504,6 +504,19 @@ CWM_API int cwm_raft_convex_upsample(const float* flow_dev, const float* mask_de
 CWM_API int cwm_raft_head_project(const float* hidden_dev, const float* weight_dev, const float* bias_dev, int64_t M, float* value_dev, void* stream);
 CWM_API int cwm_raft_convex_upsample1(const float* value_dev, const float* mask_dev, int P, int h8, int w8, float* out_dev, void* stream);
 
+/* RAFT's forward interpolation on the device: a low-resolution flow carried along itself onto the next frame's grid, which is what the warm-start
+ * protocol feeds to the next pair as `flow_init` (added after 0.10.4; the version string is unchanged).
+ * replaces: `forward_interpolate` (raft/utils.py:28-56): a `.cpu().numpy()` copy and two scipy `griddata(..., method='nearest')` queries per field.
+ * in:  P planar fields [2, h8, w8] (channel 0 = dx, 1 = dy, 1/8-resolution pixels), rows of w8 contiguous: element (c, y, x) of field p at
+ *      flow_dev + p*stride_p + c*stride_c + y*w8 + x (strides in elements, of either sign).
+ * out: out_dev [P, 2, h8, w8] contiguous.
+ * Source pixel i = y0*w8 + x0 lands at x1 = x0 + dx[i], y1 = y0 + dy[i], summed in double (exact).  It is valid iff
+ * x1 > 0 && x1 < w8 && y1 > 0 && y1 < h8, all four strict, so a NaN or infinite component is invalid.  Target (gx, gy) takes both channels of the valid
+ * source with the smallest (gx - x1)^2 + (gy - y1)^2 in double; among equal distances the lowest i wins.  With no valid source the field is zeros (a
+ * cold start; scipy returns NaN or raises there).  Brute force: h8*w8 <= 65536.  CWM_ERR_INVALID when out_dev overlaps what is read (every target
+ * reads other pixels' sources), and for a null pointer, P < 1, h8 < 1 or w8 < 1.  No model handle; does not synchronise the stream. */
+CWM_API int cwm_raft_forward_interpolate(const float* flow_dev, int64_t stride_p, int64_t stride_c, int P, int h8, int w8, float* out_dev, void* stream);
+
 CWM_API const char* cwm_last_error(void);
 /* "cwm_hip <version> gfx950" */
 CWM_API const char* cwm_version(void);

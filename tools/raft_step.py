@@ -10,7 +10,12 @@ one-channel convex upsampling in place of the flow's two-channel one); its FLOPs
 `--flow-init` times a warm-started forward (`flow_init`: one seeded [1,2,H/8,W/8] field for every pair; one more small launch).
 `--per-iteration` times the list form (the two-image call with `test_mode=False`: the mask head and the upsampling in every iteration, +0.69 GFLOP
 and one full-resolution write each) and prints, per iteration, max-abs and mean-abs of (prediction i - prediction i-1) in pixels: how fast the
-flow settles, which is what `set_raft_iters` is chosen from."""
+flow settles, which is what `set_raft_iters` is chosen from.
+`--warm-start --frames T` times a movie of T frames three ways in one process and prints one line with all three: the warm chain on the device
+(`warm_start=True`: T-1 forwards one after another with `forward_interpolate` between them), the cold multi-frame call on the same
+movie (all pairs in one launch set), and the same chain with the interpolation done on the host between two-image calls, by the numpy restatement
+of tests/raft_video_restatement.py: the synchronisation, the copy down, the search and the copy back a user of the reference's protocol pays; and the
+interpolation kernel alone."""
 import argparse
 import json
 import os
@@ -22,7 +27,55 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from counterfactualworldmodels_amd import config as C, synthetic as S  # noqa: E402
-from counterfactualworldmodels_amd.raft import RAFT, _args  # noqa: E402
+from counterfactualworldmodels_amd.raft import RAFT, _args, forward_interpolate  # noqa: E402
+
+
+def timed(run, warmup, steps):
+    """median and min ms of run() followed by a device synchronise"""
+    for _ in range(warmup):
+        run()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(steps):
+        t0 = time.perf_counter()
+        run()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    return 1e3 * float(np.median(times)), 1e3 * min(times)
+
+
+def warm_start_lines(m, args):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import raft_video_restatement as R
+
+    H, W = args.size
+    T = args.frames
+    for B in args.batch:
+        x = torch.from_numpy(S.raft_frames(B, H, W, 1, frames=T)).cuda()
+        x255 = x * 255.0
+
+        def host_chain():
+            init, ups = None, []
+            for t in range(T - 1):
+                low, up = m._forward_two_images(x255[:, t], x255[:, t + 1], iters=args.iters, flow_init=init)
+                ups.append(up)
+                if t + 1 < T - 1:  # .cpu() synchronises; the search runs on the host; the result goes back up
+                    init = torch.from_numpy(R.forward_interpolate(low.cpu().numpy())).cuda()
+            return ups
+
+        low = m._forward_two_images(x255[:, 0], x255[:, 1], iters=args.iters)[0]
+        chain = timed(lambda: m(x, iters=args.iters, warm_start=True), args.warmup, args.steps)
+        cold = timed(lambda: m(x, iters=args.iters), args.warmup, args.steps)
+        host = timed(host_chain, args.warmup, args.steps)
+        kern = timed(lambda: forward_interpolate(low), args.warmup, max(args.steps, 20))
+        same = all(torch.equal(a, b) for a, b in zip(host_chain(), m(x, iters=args.iters, warm_start=True).unbind(1)))
+        print(json.dumps({"warm_start": True, "mode": m.mode, "batch": B, "frames": T, "size": [H, W], "iters": args.iters,
+                          "chain_device_ms": round(chain[0], 3), "chain_device_ms_min": round(chain[1], 3),
+                          "cold_multiframe_ms": round(cold[0], 3), "cold_multiframe_ms_min": round(cold[1], 3),
+                          "chain_through_host_ms": round(host[0], 3), "chain_through_host_ms_min": round(host[1], 3),
+                          "forward_interpolate_ms": round(kern[0], 4), "device_chain_equals_host_chain": bool(same),
+                          "chain_device_ms_per_pair": round(chain[0] / (B * (T - 1)), 3), "cold_ms_per_pair": round(cold[0] / (B * (T - 1)), 3),
+                          "chain_through_host_ms_per_pair": round(host[0] / (B * (T - 1)), 3)}), flush=True)
 
 
 def main():
@@ -36,7 +89,11 @@ def main():
     ap.add_argument("--mode", default="parity", choices=["parity", "fast"], help="arithmetic of the convolutions (RAFT.set_mode)")
     ap.add_argument("--flow-init", action="store_true", help="time a warm-started forward (flow_init)")
     ap.add_argument("--per-iteration", action="store_true", help="time the list form (test_mode=False) and print how much each iteration moves the prediction")
+    ap.add_argument("--warm-start", action="store_true", help="time a warm-started movie: the device chain, the cold call and the chain through the host")
+    ap.add_argument("--frames", type=int, default=4, help="frames of the movie of --warm-start")
     args = ap.parse_args()
+    if args.warm_start and (args.frames < 3 or args.flow_init or args.per_iteration):
+        ap.error("--warm-start needs --frames >= 3 and excludes --flow-init and --per-iteration")
     H, W = args.size
     m = RAFT(_args(output_dim=args.output_dim)) if args.output_dim else RAFT()
     m.set_mode(args.mode)
@@ -51,6 +108,8 @@ def main():
         if args.output_dim:
             per_it += 2.0 * (H // 8) * (W // 8) * 256 * (128 * 9 + args.output_dim)
         flops += (args.iters - 1) * per_it
+    if args.warm_start:
+        return warm_start_lines(m, args)
     init = None
     if args.flow_init:
         g = torch.Generator().manual_seed(2)
