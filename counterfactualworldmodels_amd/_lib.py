@@ -37,6 +37,17 @@ def mode_id(mode) -> int:
         raise ValueError("mode must be 'fast' or 'parity', got %r" % (mode,))
 
 
+RAFT_CORR_ALL_PAIRS, RAFT_CORR_ON_THE_FLY = 0, 1  # include/cwm_hip.h cwm_raft_set_corr
+_RAFT_CORRS = {"all_pairs": RAFT_CORR_ALL_PAIRS, "on_the_fly": RAFT_CORR_ON_THE_FLY}
+
+
+def raft_corr_id(corr) -> int:
+    try:
+        return _RAFT_CORRS[corr]
+    except (KeyError, TypeError):
+        raise ValueError("corr must be 'all_pairs' or 'on_the_fly', got %r" % (corr,))
+
+
 class CwmConfig(C.Structure):
     _fields_ = [
         ("img_h", C.c_int32),
@@ -483,6 +494,9 @@ SIGNATURES = {
     "cwm_raft_forward": (C.c_int, [C.c_void_p, C.POINTER(CwmRaftForwardArgs)]),
     "cwm_raft_forward_ex": (C.c_int, [C.c_void_p, C.POINTER(CwmRaftForwardExArgs)]),
     "cwm_raft_corr_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cwm_raft_set_corr": (C.c_int, [C.c_void_p, C.c_int]),
+    "cwm_raft_workspace_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cwm_raft_corr_lookup_on_the_fly": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_raft_convex_upsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_raft_head_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "cwm_raft_convex_upsample1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -501,6 +515,7 @@ DEV_SIGNATURES = {
     "cwm_debug_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "cwm_dev_raft_conv": (C.c_int, [C.POINTER(CwmDevRaftConvArgs)]),
     "cwm_dev_raft_corr_lookup_operand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cwm_dev_raft_corr_lookup_on_the_fly_operand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_dev_raft_instnorm_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "cwm_dev_raft_residual_join": (C.c_int, [C.POINTER(CwmDevConvSrc), C.POINTER(CwmDevConvSrc), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_dev_raft_cnet_split": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -310,9 +310,12 @@ def raft_state_dict_schema(output_dim=None) -> "OrderedDict[str, tuple]":
     return s
 
 
-def raft_algorithmic_flops(height: int, width: int, iters: int) -> float:
+def raft_algorithmic_flops(height: int, width: int, iters: int, corr: str = "all_pairs") -> float:
     """FLOPs one frame pair costs on this package's path (2*M*N*K per convolution and for the correlation; the mask head and the
-    convex upsampling run once, after the last iteration)."""
+    convex upsampling run once, after the last iteration).  `corr="on_the_fly"` (RAFT.set_corr) books, in place of the all-pairs product, the
+    dot products a lookup needs: 4 levels x 100 integer neighbours x 2 * 256 = 204.8 kFLOP per 1/8-resolution pixel and iteration."""
+    if corr not in ("all_pairs", "on_the_fly"):
+        raise ValueError("corr must be 'all_pairs' or 'on_the_fly', got %r" % (corr,))
     def conv(hw, n, c, k):
         return 2.0 * hw * n * c * k
 
@@ -320,8 +323,9 @@ def raft_algorithmic_flops(height: int, width: int, iters: int) -> float:
     enc = conv(h2, 64, 3, 49) + 4 * conv(h2, 64, 64, 9)
     enc += conv(h4, 96, 64, 9) + conv(h4, 96, 96, 9) * 3 + conv(h4, 96, 64, 1)
     enc += conv(h8, 128, 96, 9) + conv(h8, 128, 128, 9) * 3 + conv(h8, 128, 96, 1) + conv(h8, 256, 128, 1)
-    corr = 2.0 * h8 * h8 * 256
     upd = (conv(h8, 256, 324, 1) + conv(h8, 192, 256, 9) + conv(h8, 128, 2, 49) + conv(h8, 64, 128, 9) + conv(h8, 126, 256, 9)
            + 6 * conv(h8, 128, 384, 5) + conv(h8, 256, 128, 9) + conv(h8, 2, 256, 9))
     mask = conv(h8, 256, 128, 9) + conv(h8, 576, 256, 1)
-    return 3 * enc + corr + iters * upd + mask
+    if corr == "on_the_fly":
+        return 3 * enc + iters * (upd + RAFT_CORR_LEVELS * 100 * 2.0 * 256 * h8) + mask
+    return 3 * enc + 2.0 * h8 * h8 * 256 + iters * upd + mask

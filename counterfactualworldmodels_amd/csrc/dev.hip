@@ -305,6 +305,14 @@ extern "C" int cwm_dev_raft_corr_lookup_operand(const float* fmap1_dev, const fl
     return raft_corr_lookup_run(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, nullptr, (bf16*)A_dev, mode == CWM_MODE_PARITY ? 2 : 1, (hipStream_t)stream);
 }
 
+extern "C" int cwm_dev_raft_corr_lookup_on_the_fly_operand(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8,
+                                                           int mode, void* A_dev, void* stream) {
+    CWM_REQUIRE(fmap1_dev && fmap2_dev && coords_dev && A_dev && P > 0 && h8 >= 8 && w8 >= 8, "cwm_dev_raft_corr_lookup_on_the_fly_operand: bad argument");
+    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_dev_raft_corr_lookup_on_the_fly_operand: bad mode");
+    return raft_corr_lookup_on_the_fly_run(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, nullptr, (bf16*)A_dev, mode == CWM_MODE_PARITY ? 2 : 1,
+                                           (hipStream_t)stream);
+}
+
 extern "C" int cwm_dev_raft_instnorm_stats(const float* x_dev, int n_img, int HW, int C, float eps, float* stats_dev, void* stream) {
     CWM_REQUIRE(x_dev && stats_dev && n_img > 0 && HW > 0 && C > 0, "cwm_dev_raft_instnorm_stats: bad argument");
     Scratch sc;

@@ -136,6 +136,7 @@ struct Engine {
     uint64_t loads = 0;  // load_weight calls that changed a stored tensor (not those into an ignored slot): a handle that derives data from its slots compares it
     std::vector<void*> allocs;     // weights etc., freed on destroy
     std::vector<void*> ws_allocs;  // workspace, re-allocated when it has to grow
+    uint64_t ws_bytes = 0;         // bytes asked of alloc() for the workspace held now (free_workspace resets it)
     KernelTimer timers[CWM_KCLASS_COUNT];
     struct SplitKWs {
         float* slabs;

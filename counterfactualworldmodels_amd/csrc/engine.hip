@@ -132,6 +132,7 @@ Engine::~Engine() {
 int Engine::alloc(void** p, size_t bytes, bool zero, bool workspace) {
     CWM_HIP_CHECK(hipMalloc(p, bytes ? bytes : 16));
     (workspace ? ws_allocs : allocs).push_back(*p);
+    if (workspace) ws_bytes += bytes;
     if (zero) CWM_HIP_CHECK(hipMemset(*p, 0, bytes ? bytes : 16));
     return 0;
 }
@@ -140,6 +141,7 @@ int Engine::free_workspace() {
     CWM_HIP_CHECK(hipDeviceSynchronize());
     for (void* p : ws_allocs) (void)hipFree(p);
     ws_allocs.clear();
+    ws_bytes = 0;
     return 0;
 }
 

@@ -327,6 +327,18 @@ struct CorrLookupParams {
     float* out;           // instead of A (out != nullptr): fp32 [M][out_ld], features [0, levels*81) (cwm_raft_corr_lookup)
     int out_ld;
 };
+// The same lookup without the correlation volume (AlternateCorrBlock, corr.py:63-91): the two feature maps, fmap2 also pooled to levels 1 .. 3
+struct CorrOnTheFlyParams {
+    const float* fmap1;     // [M][256]
+    const float* fmap2[4];  // level l: [P][h[l]][w[l]][256], l times avg_pool2d(2, stride 2) of fmap2
+    int h[4], w[4];
+    const float* coords;    // [M][2]
+    int64_t M, hw8;         // rows, and rows per pair (h[0] * w[0])
+    bf16* A;                // as CorrLookupParams
+    int Kpad;
+    float* out;
+    int out_ld;
+};
 // RAFT.upsample_flow of a C-channel low-resolution field (C = 2: the flow, C = 1: the output head's map): the 3 x 3 neighbourhood times 8, combined
 // with the softmax of the 9 x 64 mask
 struct ConvexUpParams {
@@ -370,6 +382,10 @@ int launch_coords_init_flow(float* coords, int P, int ppg, int h8, int w8, const
 int launch_corr(const float* f1, const float* f2, int P, int N, int D, float* corr, hipStream_t s);
 int launch_corr_pool(const float* in, int64_t maps, int h, int w, float* out, hipStream_t s);
 int launch_corr_lookup(const CorrLookupParams& p, int planes, hipStream_t s);
+// avg_pool2d(2, stride 2), floor, of an NHWC map [P][h][w][C] -> [P][h / 2][w / 2][C] (C a multiple of 4, 16-byte aligned maps)
+int launch_fmap_pool(const float* in, int64_t P, int h, int w, int C, float* out, hipStream_t s);
+// launch_corr_lookup's features from the feature maps themselves: every tap's correlation is computed when it is looked up (fp32 FMA, fixed order)
+int launch_corr_lookup_on_the_fly(const CorrOnTheFlyParams& p, int planes, hipStream_t s);
 int launch_motion_finish(float* x, const float* coords, int64_t M, int h8, int w8, hipStream_t s);
 int launch_gru_update(float* h, const float* zr, const float* q, int64_t M, hipStream_t s);
 int launch_flow_update(float* coords, const float* delta, int ld, int64_t M, hipStream_t s);
@@ -386,5 +402,8 @@ int launch_head_project(const float* hidden, int ld, const float* w, const float
 // CorrBlock built from two feature maps [P][h8 * w8][256] and indexed at coords [P * h8 * w8][2]: the pyramid (allocated and freed inside), then the lookup
 // as fp32 `out` [M][324], or (out == nullptr) as convc1's Kpad = 384 operand A in the layout of `planes`.  Synchronises the stream.
 int raft_corr_lookup_run(const float* fmap1, const float* fmap2, const float* coords, int P, int h8, int w8, float* out, bf16* A, int planes, hipStream_t s);
+// The same result from AlternateCorrBlock's form: what is allocated and freed inside is fmap2's three poolings, not a correlation volume.  Synchronises the stream.
+int raft_corr_lookup_on_the_fly_run(const float* fmap1, const float* fmap2, const float* coords, int P, int h8, int w8, float* out, bf16* A, int planes,
+                                    hipStream_t s);
 
 }  // namespace cwm

@@ -4,6 +4,8 @@
 // their own, except the residual join of the encoders and the GRU state update.  Below the kernels: launch_flat, the one launch of every grid-stride kernel
 // here; the three statements a convolution launch is made of (set_conv_geometry, pack_conv_parts, conv_gemm), shared by raft_model.hip and dev.hip; and the
 // launchers.  One convex-upsampling kernel serves the flow (2 channels, read from the coordinates) and the output head's map (1 channel, planar).
+// The correlation lookup has two kernels behind one contract: corr_lookup_kernel samples the all-pairs pyramid, corr_lookup_on_the_fly_kernel computes the
+// correlation of every tap it needs from the feature maps (no pyramid); both take taps and weights from lookup_tap.
 #include <math.h>
 
 #include <algorithm>
@@ -217,6 +219,18 @@ __global__ void corr_pool_kernel(const float* in, int64_t maps, int h, int w, fl
     }
 }
 
+// One axis of a lookup sample: coordinate c (level 0) displaced by d pixels on level l, whose side is `side` -> the left / upper tap i0 and the weight w of
+// the tap after it.  The pixel coordinate is what grid_sample(align_corners=True) recovers from bilinear_sampler's normalisation, roundings included, so
+// the two lookup kernels below take their taps and weights from one expression.
+__device__ __forceinline__ void lookup_tap(float c, int l, int side, int d, int& i0, float& w) {
+    const float cx = c / (float)(1 << l) + (float)d;
+    const float gx = 2.f * cx / (float)(side - 1) - 1.f;
+    const float ix = (gx + 1.f) * (0.5f * (float)(side - 1));
+    const float fx = floorf(ix);
+    i0 = (int)fx;
+    w = ix - fx;
+}
+
 // CorrBlock.__call__: feature l*81 + a*9 + b of row m samples level l at (x + a - 4, y + b - 4) (the meshgrid(dy, dx) order), bilinear with
 // zero padding as grid_sample(align_corners=True) after bilinear_sampler's normalisation; written as convc1's A operand (Kpad 384) in the
 // layout of PLANES, or as fp32 (p.out)
@@ -230,13 +244,10 @@ __global__ void corr_lookup_kernel(const CorrLookupParams p) {
         if (f < p.levels * 81) {
             const int l = f / 81, a = (f - l * 81) / 9, b = f % 9;
             const int H = p.h[l], W = p.w[l];
-            const float cx = p.coords[2 * m] / (float)(1 << l) + (float)(a - 4);
-            const float cy = p.coords[2 * m + 1] / (float)(1 << l) + (float)(b - 4);
-            const float gx = 2.f * cx / (float)(W - 1) - 1.f, gy = 2.f * cy / (float)(H - 1) - 1.f;
-            const float ix = (gx + 1.f) * (0.5f * (float)(W - 1)), iy = (gy + 1.f) * (0.5f * (float)(H - 1));
-            const float fx = floorf(ix), fy = floorf(iy);
-            const int x0 = (int)fx, y0 = (int)fy;
-            const float wx = ix - fx, wy = iy - fy;
+            int x0, y0;
+            float wx, wy;
+            lookup_tap(p.coords[2 * m], l, W, a - 4, x0, wx);
+            lookup_tap(p.coords[2 * m + 1], l, H, b - 4, y0, wy);
             const float* map = p.pyr[l] + m * (int64_t)H * W;
             auto at = [&](int yy, int xx) { return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? map[(int64_t)yy * W + xx] : 0.f; };
             v = at(y0, x0) * ((1.f - wx) * (1.f - wy)) + at(y0, x0 + 1) * (wx * (1.f - wy)) + at(y0 + 1, x0) * ((1.f - wx) * wy) +
@@ -246,6 +257,130 @@ __global__ void corr_lookup_kernel(const CorrLookupParams p) {
         }
         if (p.out) p.out[m * p.out_ld + f] = v;
         else store_operand<PLANES>(p.A, m, p.Kpad, f, v);
+    }
+}
+
+// avg_pool2d(2, stride 2), floor, of an NHWC feature map [P][h][w][C] -> [P][h / 2][w / 2][C]: the next level of fmap2 for the on-the-fly lookup
+// (AlternateCorrBlock.__init__, corr.py:63-73).  Four channels per thread; the four pixels are added in corr_pool_kernel's order.
+__global__ void fmap_pool_kernel(const float* in, int64_t P, int h, int w, int C, float* out, int oh, int ow) {
+    const int c4n = C >> 2;
+    const int64_t total = P * oh * ow * c4n;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t pix = i / c4n;
+        const int c4 = (int)(i - pix * c4n);
+        const int64_t pr = pix / ((int64_t)oh * ow);
+        const int q = (int)(pix - pr * oh * ow), y = q / ow, x = q - y * ow;
+        const float4* s = reinterpret_cast<const float4*>(in + ((pr * h + 2 * y) * w + 2 * x) * C) + c4;
+        const float4 a = s[0], b = s[c4n], c = s[(int64_t)w * c4n], d = s[(int64_t)w * c4n + c4n];
+        float4 acc = a;
+        acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w;
+        acc.x += c.x; acc.y += c.y; acc.z += c.z; acc.w += c.w;
+        acc.x += d.x; acc.y += d.y; acc.z += d.z; acc.w += d.w;
+        reinterpret_cast<float4*>(out)[i] = make_float4(acc.x / 4.f, acc.y / 4.f, acc.z / 4.f, acc.w / 4.f);
+    }
+}
+
+// AlternateCorrBlock.__call__ (corr.py:75-91) under corr_lookup_kernel's contract: the same features of the same taps and weights (lookup_tap), each
+// tap's correlation computed here, <fmap1[m], fmap2_l[tap]> / 16 with fmap2_l the l times pooled fmap2 (pooling is linear: the pooled correlation of
+// CorrBlock up to summation order).  One workgroup per row m, wave l on level l:
+//   1. The nine displacements of an axis share their fraction, so their taps are i0 + a and i0 + a + 1 with one i0 -- or, when the pixel coordinate lies
+//      within an ulp of an integer, with i0 and i0 - 1 mixed: the taps of a level fall into a window of 10 x 10 integer positions at
+//      (xbase, ybase) = the smallest tap - displacement of each axis, 11 (kOtfWin) along an axis in the mixed case: its extent is the largest tap + 2.
+//   2. The wave computes the 256-long dot product of every position in the intersection of that window and the level: eight lanes per position, 32
+//      channels per lane as eight 16-byte loads (the eight lanes of a group read 128 contiguous bytes), fp32 FMA in channel order, then the DPP sum of
+//      the group: a fixed order, no atomics.  A position outside the level is neither read nor stored: the blend takes it as 0, as the zero padding does.
+//   3. The 324 features (and the K padding) are blended from the window in LDS by all 256 threads, with corr_lookup_kernel's expression.
+constexpr int kOtfWin = 11;
+constexpr int kOtfFar = 1 << 24;  // taps are clamped to +-kOtfFar: far outside every level either way, and differences of taps stay in range
+template <int PLANES>
+__global__ void __launch_bounds__(256) corr_lookup_on_the_fly_kernel(const CorrOnTheFlyParams p) {
+    __shared__ float dots[4][kOtfWin * kOtfWin];
+    __shared__ int tap_i[4][2][9];  // [level][x, y][displacement]: the first tap, relative to the window's origin
+    __shared__ float tap_w[4][2][9];
+    __shared__ int base[4][2];
+    const int lane = threadIdx.x & (kWave - 1), l = threadIdx.x / kWave;
+    const int grp = lane >> 3, sub = lane & 7;
+    const int H = p.h[l], W = p.w[l];
+    for (int64_t m = xcd_remap(blockIdx.x, gridDim.x); m < p.M; m += gridDim.x) {
+        const float2 c = reinterpret_cast<const float2*>(p.coords)[m];
+        const int a = lane % 9;  // lanes 0 .. 8 hold the nine displacements
+        int x0, y0;
+        float wx, wy;
+        lookup_tap(c.x, l, W, a - 4, x0, wx);
+        lookup_tap(c.y, l, H, a - 4, y0, wy);
+        x0 = max(-kOtfFar, min(kOtfFar, x0));
+        y0 = max(-kOtfFar, min(kOtfFar, y0));
+        const int xr = x0 - a, yr = y0 - a;
+        int xbase = __shfl(xr, 0, kWave), ybase = __shfl(yr, 0, kWave), xlast = __shfl(x0, 0, kWave), ylast = __shfl(y0, 0, kWave);
+#pragma unroll
+        for (int j = 1; j < 9; ++j) {
+            xbase = min(xbase, __shfl(xr, j, kWave));
+            ybase = min(ybase, __shfl(yr, j, kWave));
+            xlast = max(xlast, __shfl(x0, j, kWave));
+            ylast = max(ylast, __shfl(y0, j, kWave));
+        }
+        // the part of the window that taps reach (the largest tap and the one after it) and that lies in the level: columns [qx0, qx0 + nx), rows [qy0, qy0 + ny)
+        const int qx0 = min(kOtfWin, max(0, -xbase)), qy0 = min(kOtfWin, max(0, -ybase));
+        const int nx = max(0, min(min(kOtfWin, xlast - xbase + 2), W - xbase) - qx0), ny = max(0, min(min(kOtfWin, ylast - ybase + 2), H - ybase) - qy0);
+        if (lane < 9) {
+            tap_i[l][0][lane] = x0 - xbase;
+            tap_w[l][0][lane] = wx;
+            tap_i[l][1][lane] = y0 - ybase;
+            tap_w[l][1][lane] = wy;
+        }
+        if (lane == 0) {
+            base[l][0] = xbase;
+            base[l][1] = ybase;
+        }
+        const float4* f1 = reinterpret_cast<const float4*>(p.fmap1 + m * 256) + sub;
+        float4 q[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) q[i] = f1[8 * i];
+        const float* lvl = p.fmap2[l] + (m / p.hw8) * H * W * 256;
+        const int n = nx * ny;
+        int qy = grp / max(nx, 1), qx = grp - qy * nx;  // position qi = s * 8 + grp of the nx x ny rectangle, kept as (qx, qy)
+        for (int s = 0; s * 8 < n; ++s) {
+            const int qi = s * 8 + grp;
+            float acc = 0.f;
+            if (qi < n) {
+                const float4* r = reinterpret_cast<const float4*>(lvl + ((int64_t)(ybase + qy0 + qy) * W + xbase + qx0 + qx) * 256) + sub;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const float4 v = r[8 * i];
+                    acc = fmaf(q[i].x, v.x, acc);
+                    acc = fmaf(q[i].y, v.y, acc);
+                    acc = fmaf(q[i].z, v.z, acc);
+                    acc = fmaf(q[i].w, v.w, acc);
+                }
+            }
+            acc = group8_sum(acc);
+            if (sub == 0 && qi < n) dots[l][(qy0 + qy) * kOtfWin + qx0 + qx] = acc * 0.0625f;  // / sqrt(256)
+            for (qx += 8; qx >= nx && qy < ny; ++qy) qx -= nx;
+        }
+        __syncthreads();
+        for (int f = threadIdx.x; f < p.Kpad; f += blockDim.x) {
+            float v = 0.f;
+            if (f < 4 * 81) {
+                const int fl = f / 81, fa = (f - fl * 81) / 9, fb = f % 9;
+                const int Hl = p.h[fl], Wl = p.w[fl];
+                const int tx = tap_i[fl][0][fa], ty = tap_i[fl][1][fb];
+                const int X0 = base[fl][0] + tx, Y0 = base[fl][1] + ty;
+                // (a tap beyond the window can only come from a coordinate too large to have a fraction: it is outside the level, and not read)
+                const int jx = max(0, min(kOtfWin - 2, tx)), jy = max(0, min(kOtfWin - 2, ty));
+                const float ux = tap_w[fl][0][fa], uy = tap_w[fl][1][fb];
+                const float* d = dots[fl];
+                auto at = [&](int dy, int dx) {
+                    const int yy = Y0 + dy, xx = X0 + dx;
+                    return (yy >= 0 && yy < Hl && xx >= 0 && xx < Wl) ? d[(jy + dy) * kOtfWin + jx + dx] : 0.f;
+                };
+                v = at(0, 0) * ((1.f - ux) * (1.f - uy)) + at(0, 1) * (ux * (1.f - uy)) + at(1, 0) * ((1.f - ux) * uy) + at(1, 1) * (ux * uy);
+            } else if (p.out) {
+                continue;
+            }
+            if (p.out) p.out[m * p.out_ld + f] = v;
+            else store_operand<PLANES>(p.A, m, p.Kpad, f, v);
+        }
+        __syncthreads();  // the window is free for the next row
     }
 }
 
@@ -534,6 +669,23 @@ int launch_corr_pool(const float* in, int64_t maps, int h, int w, float* out, hi
 
 int launch_corr_lookup(const CorrLookupParams& p, int planes, hipStream_t s) {
     return launch_flat(planes == 2 ? corr_lookup_kernel<2> : corr_lookup_kernel<1>, p.M * p.Kpad, s, p);
+}
+
+int launch_fmap_pool(const float* in, int64_t P, int h, int w, int C, float* out, hipStream_t s) {
+    CWM_REQUIRE(C % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0, "fmap_pool: %d channels in 16-byte aligned maps are required", C);
+    const int oh = h / 2, ow = w / 2;
+    return launch_flat(fmap_pool_kernel, P * oh * ow * (C / 4), s, in, P, h, w, C, out, oh, ow);
+}
+
+int launch_corr_lookup_on_the_fly(const CorrOnTheFlyParams& p, int planes, hipStream_t s) {
+    bool aligned = ((uintptr_t)p.fmap1 & 15) == 0 && ((uintptr_t)p.coords & 7) == 0;
+    for (const float* f : p.fmap2) aligned = aligned && ((uintptr_t)f & 15) == 0;
+    CWM_REQUIRE(aligned && p.M > 0 && p.hw8 > 0 && p.M % p.hw8 == 0, "corr_lookup_on_the_fly: 16-byte aligned feature maps and whole pairs are required");
+    // one workgroup of four waves (one per level) per row
+    hipLaunchKernelGGL(planes == 2 ? corr_lookup_on_the_fly_kernel<2> : corr_lookup_on_the_fly_kernel<1>, dim3((unsigned)std::min<int64_t>(p.M, 1 << 20)),
+                       dim3(4 * kWave), 0, s, p);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 int launch_motion_finish(float* x, const float* coords, int64_t M, int h8, int w8, hipStream_t s) {

@@ -11,7 +11,9 @@
 // The state dict lives in the engine's slot table (engine.h Slot: the raw fp32 tensors as vector slots, num_batches_tracked ignored; the head's keys and
 // num_batches_tracked optional); prepare() packs the convolutions from it when Engine::loads has moved.  What a convolution launch is made of (geometry,
 // packing of the weight parts, GEMM params) is stated once in raft_kernels.hip, for this file and for dev.hip's cwm_dev_raft_conv; the correlation pyramid
-// once here (build_pyramid), for the forward and the stand-alone lookup.
+// once here (build_pyramid), for the forward and the stand-alone lookup.  A handle may instead compute the correlations at lookup time
+// (cwm_raft_set_corr, AlternateCorrBlock of raft/corr.py:63-91): build_fmap_levels pools fmap2 three times in place of the pyramid, and the lookup of
+// every iteration is corr_lookup_on_the_fly_kernel; nothing else of the forward changes.
 #include <stddef.h>
 
 #include "engine.h"
@@ -68,12 +70,14 @@ struct cwm_raft_model {
     uint64_t packed_at = ~0ull;  // eng.loads when the convolutions were last packed
     Encoder fnet, cnet;
     RaftConv convc1, convc2, convf1, convf2, conv, zr[2], q[2], fh1, fh2, mask0, mask2, out0;
-    // workspace (cached by shape)
-    int ws_P = 0, ws_H = 0, ws_W = 0;
+    int corr = CWM_RAFT_CORR_ALL_PAIRS;  // cwm_raft_set_corr
+    // workspace (cached by shape and by `corr`)
+    int ws_P = 0, ws_H = 0, ws_W = 0, ws_corr = CWM_RAFT_CORR_ALL_PAIRS;
     float *enc_act[4] = {nullptr, nullptr, nullptr, nullptr}, *enc_stats[4] = {nullptr, nullptr, nullptr, nullptr};
     bf16* enc_A = nullptr;
     double* enc_norm_work = nullptr;
     float *fmap = nullptr, *cn = nullptr, *pyr[4] = {nullptr, nullptr, nullptr, nullptr};
+    float* f2lvl[4] = {nullptr, nullptr, nullptr, nullptr};  // on-the-fly correlation: fmap2 pooled to levels 1 .. 3 (level 0 is fmap's second half) in place of pyr
     bf16 *corrA = nullptr, *updA = nullptr;
     float *c1 = nullptr, *cf = nullptr, *f1 = nullptr, *x = nullptr, *h = nullptr, *zrb = nullptr, *qb = nullptr, *fh = nullptr, *d = nullptr,
           *coords = nullptr, *mask = nullptr;
@@ -167,7 +171,7 @@ int prepare(cwm_raft_model* m) {
 int level_sides(int s, int l) { return s >> l; }
 
 int ensure_workspace(cwm_raft_model* m, int P, int H, int W) {
-    if (m->ws_P >= P && m->ws_H == H && m->ws_W == W) return 0;
+    if (m->ws_P >= P && m->ws_H == H && m->ws_W == W && m->ws_corr == m->corr) return 0;
     Engine& E = m->eng;
     if (int rc = E.free_workspace()) return rc;
     m->ws_P = 0;
@@ -179,7 +183,12 @@ int ensure_workspace(cwm_raft_model* m, int P, int H, int W) {
     if (rc || (rc = E.ws(&m->enc_A, (size_t)(n * hw2 * 576 * kMaxPlanes))) || (rc = E.ws(&m->enc_norm_work, (size_t)(2 * n * kInstNormMaxChunks * 128))))
         return rc;
     if ((rc = E.ws(&m->fmap, (size_t)(2 * M * kFeat))) || (rc = E.ws(&m->cn, (size_t)(M * 256)))) return rc;
-    for (int l = 0; l < 4 && !rc; ++l) rc = E.ws(&m->pyr[l], (size_t)(M * level_sides(H / 8, l) * level_sides(W / 8, l)));
+    for (int l = 0; l < 4; ++l) m->pyr[l] = m->f2lvl[l] = nullptr;
+    for (int l = 0; l < 4 && !rc; ++l) {
+        const int64_t hw = (int64_t)level_sides(H / 8, l) * level_sides(W / 8, l);
+        if (m->corr == CWM_RAFT_CORR_ALL_PAIRS) rc = E.ws(&m->pyr[l], (size_t)(M * hw));
+        else if (l > 0) rc = E.ws(&m->f2lvl[l], (size_t)(P * hw * kFeat));
+    }
     if (rc || (rc = E.ws(&m->corrA, (size_t)(M * kLookupKpad * kMaxPlanes))) || (rc = E.ws(&m->updA, (size_t)(M * 2304 * kMaxPlanes)))) return rc;
     if ((rc = E.ws(&m->c1, (size_t)(M * 256))) || (rc = E.ws(&m->cf, (size_t)(M * 256))) || (rc = E.ws(&m->f1, (size_t)(M * 128))) ||
         (rc = E.ws(&m->x, (size_t)(M * 256))) || (rc = E.ws(&m->h, (size_t)(M * 128))) || (rc = E.ws(&m->zrb, (size_t)(M * 256))) ||
@@ -189,6 +198,7 @@ int ensure_workspace(cwm_raft_model* m, int P, int H, int W) {
     m->ws_P = P;
     m->ws_H = H;
     m->ws_W = W;
+    m->ws_corr = m->corr;
     return 0;
 }
 
@@ -273,6 +283,26 @@ int build_pyramid(const float* fmap1, const float* fmap2, const float* coords, i
     return 0;
 }
 
+// AlternateCorrBlock.__init__ (corr.py:63-73) and the params of its lookups: fmap2 [P][h8][w8][256] pooled into lvl[1 .. 3] (level l: [P][h8 >> l][w8 >> l][256];
+// level 0 is fmap2 itself), and `lp` over them and fmap1 at `coords`; the destination is the caller's
+int build_fmap_levels(const float* fmap1, const float* fmap2, const float* coords, int P, int h8, int w8, float* const* lvl, CorrOnTheFlyParams& lp,
+                      hipStream_t s) {
+    lp = CorrOnTheFlyParams{};
+    lp.fmap1 = fmap1;
+    lp.coords = coords;
+    lp.hw8 = (int64_t)h8 * w8;
+    lp.M = P * lp.hw8;
+    lp.Kpad = kLookupKpad;
+    for (int l = 0; l < 4; ++l) {
+        lp.fmap2[l] = l ? lvl[l] : fmap2;
+        lp.h[l] = level_sides(h8, l);
+        lp.w[l] = level_sides(w8, l);
+        if (l > 0)
+            if (int rc = launch_fmap_pool(lp.fmap2[l - 1], P, lp.h[l - 1], lp.w[l - 1], kFeat, lvl[l], s)) return rc;
+    }
+    return 0;
+}
+
 // What cwm_raft_forward_ex adds to a forward; all null: the plain forward of cwm_raft_forward, launch for launch.
 struct ForwardExtras {
     const float* init = nullptr;  // flow_init: coords1 = grid + init
@@ -304,10 +334,17 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a, const ForwardExtr
         if ((rc = run_encoder(m, m->cnet, img, i0, n, H, W, m->cn + (int64_t)i0 * hw8 * 256, planes, s))) return rc;
     }
     if ((rc = launch_cnet_split(m->cn, M, m->h, m->x, s))) return rc;
-    // correlation pyramid
-    CorrLookupParams lp;
-    if ((rc = build_pyramid(m->fmap, m->fmap + M * kFeat, m->coords, P, h8, w8, m->pyr, lp, s))) return rc;
-    lp.A = m->corrA;
+    // correlation pyramid, or the levels of fmap2 from which the lookup computes its taps (m->ws_corr: what the workspace was planned for)
+    const bool on_the_fly = m->ws_corr == CWM_RAFT_CORR_ON_THE_FLY;
+    CorrLookupParams lp = {};
+    CorrOnTheFlyParams lq = {};
+    if (on_the_fly) {
+        if ((rc = build_fmap_levels(m->fmap, m->fmap + M * kFeat, m->coords, P, h8, w8, m->f2lvl, lq, s))) return rc;
+        lq.A = m->corrA;
+    } else {
+        if ((rc = build_pyramid(m->fmap, m->fmap + M * kFeat, m->coords, P, h8, w8, m->pyr, lp, s))) return rc;
+        lp.A = m->corrA;
+    }
     if (ex.init) {
         if ((rc = launch_coords_init_flow(m->coords, P, ppg, h8, w8, ex.init, ex.init_sb, ex.init_st, ex.init_sc, s))) return rc;
     } else if ((rc = launch_coords_init(m->coords, M, h8, w8, s))) {
@@ -344,7 +381,7 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a, const ForwardExtr
     };
     for (int it = 0; it < a.iters; ++it) {
         // BasicMotionEncoder
-        if ((rc = launch_corr_lookup(lp, planes, s))) return rc;
+        if ((rc = on_the_fly ? launch_corr_lookup_on_the_fly(lq, planes, s) : launch_corr_lookup(lp, planes, s))) return rc;
         if ((rc = run_conv(m, m->convc1, Im2colParams{}, P, h8, w8, m->corrA, m->c1, 256, planes, s, true))) return rc;
         if ((rc = run_conv(m, m->convc2, im2col_of(src_of(m->c1, 256, nullptr, 1)), P, h8, w8, m->updA, m->cf, 256, planes, s))) return rc;
         if ((rc = run_conv(m, m->convf1, im2col_of(flow_src), P, h8, w8, m->updA, m->f1, 128, planes, s))) return rc;
@@ -494,6 +531,20 @@ extern "C" int cwm_raft_forward_ex(cwm_raft_model* m, const cwm_raft_forward_ex_
     return checked_forward(m, &args->base, ex, "cwm_raft_forward_ex", false);
 }
 
+extern "C" int cwm_raft_set_corr(cwm_raft_model* m, int corr) {
+    CWM_REQUIRE(m, "cwm_raft_set_corr: null argument");
+    CWM_REQUIRE(corr == CWM_RAFT_CORR_ALL_PAIRS || corr == CWM_RAFT_CORR_ON_THE_FLY,
+                "cwm_raft_set_corr: corr = %d must be CWM_RAFT_CORR_ALL_PAIRS (0) or CWM_RAFT_CORR_ON_THE_FLY (1)", corr);
+    m->corr = corr;  // the next forward re-plans the workspace when this differs from what it was planned for
+    return CWM_OK;
+}
+
+extern "C" int cwm_raft_workspace_bytes(cwm_raft_model* m, uint64_t* out) {
+    CWM_REQUIRE(m && out, "cwm_raft_workspace_bytes: null argument");
+    *out = m->eng.ws_bytes;
+    return CWM_OK;
+}
+
 // ---- stand-alone kernels (kernel tests) -------------------------------------------------------------------------------
 int cwm::raft_corr_lookup_run(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev, bf16* A,
                               int planes, hipStream_t s) {
@@ -527,6 +578,39 @@ extern "C" int cwm_raft_corr_lookup(const float* fmap1_dev, const float* fmap2_d
                                     void* stream) {
     CWM_REQUIRE(fmap1_dev && fmap2_dev && coords_dev && out_dev && P > 0 && h8 >= 8 && w8 >= 8, "cwm_raft_corr_lookup: bad argument");
     return raft_corr_lookup_run(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, out_dev, nullptr, 2, (hipStream_t)stream);
+}
+
+int cwm::raft_corr_lookup_on_the_fly_run(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev, bf16* A,
+                                         int planes, hipStream_t s) {
+    float* lvl[4] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = 0;
+    for (int l = 1; l < 4 && !rc; ++l)
+        if (hipMalloc((void**)&lvl[l], (size_t)P * level_sides(h8, l) * level_sides(w8, l) * kFeat * sizeof(float)) != hipSuccess) {
+            cwm_set_error("cwm_raft_corr_lookup_on_the_fly: out of device memory");
+            rc = CWM_ERR_HIP;
+        }
+    CorrOnTheFlyParams lp = {};
+    if (!rc) rc = build_fmap_levels(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, lvl, lp, s);
+    if (out_dev) {
+        lp.out = out_dev;
+        lp.out_ld = 324;
+    } else {
+        lp.A = A;
+    }
+    if (!rc) rc = launch_corr_lookup_on_the_fly(lp, planes, s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) {
+        cwm_set_error("cwm_raft_corr_lookup_on_the_fly: stream synchronisation failed");
+        rc = CWM_ERR_HIP;
+    }
+    for (float* p : lvl)
+        if (p) (void)hipFree(p);
+    return rc;
+}
+
+extern "C" int cwm_raft_corr_lookup_on_the_fly(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev,
+                                               void* stream) {
+    CWM_REQUIRE(fmap1_dev && fmap2_dev && coords_dev && out_dev && P > 0 && h8 >= 8 && w8 >= 8, "cwm_raft_corr_lookup_on_the_fly: bad argument");
+    return raft_corr_lookup_on_the_fly_run(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, out_dev, nullptr, 2, (hipStream_t)stream);
 }
 
 extern "C" int cwm_raft_convex_upsample(const float* flow_dev, const float* mask_dev, int P, int h8, int w8, float* out_dev, void* stream) {

@@ -20,6 +20,13 @@ value in place of the flow: the keypoint predictor of the demo notebook,
     keypoints = keypoint_predictor.cuda()(x)                   # [B,T-1,1,H,W]
 
 The reference's `--mixed_precision` is the fast mode: `load_raft_model(path, mixed_precision=True)`, or `model.set_mode("fast")` at any time.
+
+For large frames and long movies, `load_raft_model(path, corr="on_the_fly")` or `model.set_corr("on_the_fly")` computes the correlations a lookup needs
+when it needs them (the reference's `AlternateCorrBlock`, raft/corr.py:63-91) instead of building the all-pairs volume, which grows with the square of
+the frame area; `model.workspace_bytes()` tells what a forward holds.  Frames whose sides are no multiple of 8 go through `InputPadder`:
+
+    padder = InputPadder(x.shape)                # raft/utils.py:9-26
+    flows = padder.unpad(flow_model(*padder.pad(x)))
 """
 from __future__ import annotations
 
@@ -30,6 +37,7 @@ from typing import Optional
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 from ._handle import LibraryModule, _NoForward
@@ -112,7 +120,7 @@ class BasicUpdateBlock(_NoForward):
 
 def _args(**kw) -> argparse.Namespace:
     a = argparse.Namespace(corr_levels=RAFT_CORR_LEVELS, corr_radius=RAFT_CORR_RADIUS, output_dim=None, iters=None, dropout=0.0, mixed_precision=False,
-                           small=False, gpus=[0], multiframe=True, scale_inputs=True, alternate_corr=False)
+                           small=False, gpus=[0], multiframe=True, scale_inputs=True, alternate_corr=False, corr="all_pairs")
     for k, v in kw.items():
         setattr(a, k, v)
     return a
@@ -125,6 +133,32 @@ def _forward_interpolate_into(src: torch.Tensor, dst: torch.Tensor) -> None:
     with torch.cuda.device(src.device):
         _lib.check(_lib.get_lib().cwm_raft_forward_interpolate(src.data_ptr(), src.stride(0), src.stride(1), P, h, w, dst.data_ptr(),
                                                                _lib.current_stream_handle(src.device)))
+
+
+class InputPadder:
+    """raft/utils.py:9-26: pads frames so that both sides are multiples of 8, which the forward requires (436 x 1024 -> 440 x 1024), and crops a result
+    back.  `dims` is a shape ending in (H, W); mode "sintel" splits both paddings between the two borders, any other mode ("kitti") puts the vertical one
+    below.  `pad` replicates the border pixels of tensors with any number of leading dimensions ([B,3,H,W] or the multi-frame [B,T,3,H,W]) and returns
+    a list; `unpad` is a view of the last two dimensions."""
+
+    def __init__(self, dims, mode="sintel"):
+        h, w = int(dims[-2]), int(dims[-1])
+        add_h, add_w = -h % 8, -w % 8  # what each side lacks to the next multiple of 8
+        left = add_w // 2
+        top = add_h // 2 if mode == "sintel" else 0
+        self.ht, self.wd = h, w
+        self._pad = [left, add_w - left, top, add_h - top]  # F.pad's order: left, right, top, bottom
+
+    def pad(self, *inputs):
+        out = []
+        for x in inputs:  # F.pad's replicate mode takes 3 or 4 dimensions: fold the leading ones into one
+            y = F.pad(x.reshape(1, -1, x.shape[-2], x.shape[-1]), self._pad, mode="replicate")
+            out.append(y.reshape(*x.shape[:-2], y.shape[-2], y.shape[-1]))
+        return out
+
+    def unpad(self, x):
+        left, right, top, bottom = self._pad
+        return x[..., top:x.shape[-2] - bottom, left:x.shape[-1] - right]
 
 
 @torch.no_grad()
@@ -172,7 +206,10 @@ class RAFT(LibraryModule):
     Arithmetic: `self.mode` is "parity" (split-bf16 convolutions, the default) or "fast" (every convolution with bf16 operands and fp32 accumulation;
     norm statistics, correlation, lookup, coordinates, GRU update and upsampling stay fp32: the reference's autocast split, raft_model.py:218-252).
     It is "fast" when `args.mixed_precision` is true and changes with `set_mode`; nothing else chooses it.  In particular fp16 / bf16 frames do NOT turn
-    the fast mode on (the reference's autocast does, raft_model.py:219): they are upcast to fp32 and run in the model's mode."""
+    the fast mode on (the reference's autocast does, raft_model.py:219): they are upcast to fp32 and run in the model's mode.
+    Correlation: `self.corr` is "all_pairs" (the default: the volume of `CorrBlock`, built once per forward) or "on_the_fly" (the taps of every lookup
+    computed from the two feature maps, `AlternateCorrBlock` of raft/corr.py:63-91: no volume, so the workspace grows with the frame area and not with
+    its square).  It comes from `args.corr` and changes with `set_corr`; both give the same flow up to fp32 summation order, in either mode."""
 
     def __init__(self, args: Optional[argparse.Namespace] = None):
         super().__init__()
@@ -183,7 +220,10 @@ class RAFT(LibraryModule):
         if self.output_dim is not None and self.output_dim != 1:
             raise NotImplementedError("the output_dim head of RAFT is provided for output_dim = 1 only (the keypoint predictor), got %r" % (self.output_dim,))
         if getattr(self.args, "alternate_corr", False):
-            raise NotImplementedError("alternate_corr (the alt_cuda_corr extension) is not provided: the all-pairs correlation runs in the library")
+            raise NotImplementedError("alternate_corr (the alt_cuda_corr extension) is not provided: the all-pairs correlation runs in the library; "
+                                      "the library's own on-the-fly correlation is chosen with corr=\"on_the_fly\"")
+        self.corr = getattr(self.args, "corr", "all_pairs")
+        _lib.raft_corr_id(self.corr)
         self.multiframe = getattr(self.args, "multiframe", True)
         self.scale_inputs = getattr(self.args, "scale_inputs", True)
         self.hidden_dim = RAFT_HIDDEN
@@ -217,14 +257,29 @@ class RAFT(LibraryModule):
         self.mode = mode
         return self
 
+    def set_corr(self, corr: str):
+        """"all_pairs" or "on_the_fly" for the forwards that follow (the first one after a change re-plans the workspace)."""
+        _lib.raft_corr_id(corr)
+        self.corr = corr
+        return self
+
+    def workspace_bytes(self) -> int:
+        """Bytes of activation workspace the library handle holds: what the last forward's shape and `corr` asked for (0 before the first forward)."""
+        if self._handle is None:
+            return 0
+        n = C.c_uint64()
+        self._check(self._fn["workspace_bytes"](self._handle, C.byref(n)))
+        return int(n.value)
+
     def freeze_bn(self):
         for m in self.modules():
             if isinstance(m, nn.BatchNorm2d):
                 m.eval()
 
     # ---- C-ABI plumbing (the handle and sync_weights live in _handle.LibraryModule; the library folds the batch norms and packs the
-    # convolutions at the next forward.  cwm_raft_* has no per-handle options, lanes or kernel timing: the arithmetic mode travels with each call) -------
-    _ABI = {role: "cwm_raft_" + role for role in ("destroy", "load_weight", "forward", "forward_ex")}
+    # convolutions at the next forward.  cwm_raft_* has no lanes or kernel timing: the arithmetic mode travels with each call, and the one per-handle
+    # option, the form of the correlation, is set before each forward) -------
+    _ABI = {role: "cwm_raft_" + role for role in ("destroy", "load_weight", "forward", "forward_ex", "set_corr", "workspace_bytes")}
 
     def _create(self, lib, h):
         return lib.cwm_raft_create(C.byref(h))
@@ -263,6 +318,7 @@ class RAFT(LibraryModule):
                 ex.flow_iters_dev, ex.flow_iters_stride_i = per_iteration
             else:
                 ex.head_iters_dev, ex.head_iters_stride_i = per_iteration
+        self._check(self._fn["set_corr"](self._handle, _lib.raft_corr_id(self.corr)))
         with torch.cuda.device(dev):
             if extended:
                 self._check(self._fn["forward_ex"](self._handle, C.byref(ex)))

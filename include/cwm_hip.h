@@ -504,6 +504,30 @@ CWM_API int cwm_raft_convex_upsample(const float* flow_dev, const float* mask_de
 CWM_API int cwm_raft_head_project(const float* hidden_dev, const float* weight_dev, const float* bias_dev, int64_t M, float* value_dev, void* stream);
 CWM_API int cwm_raft_convex_upsample1(const float* value_dev, const float* mask_dev, int P, int h8, int w8, float* out_dev, void* stream);
 
+/* The correlation computed at lookup time (added after 0.10.4; the version string is unchanged).
+ * replaces: `AlternateCorrBlock` (raft/corr.py:63-91; `args.alternate_corr`), whose CUDA extension `alt_cuda_corr` the reference does not ship.
+ * A handle builds, per forward, either the all-pairs correlation volume and its three poolings (CorrBlock, corr.py:12-60: 4 * M * sum_l h_l * w_l bytes
+ * for the M = batch * pairs * H/8 * W/8 low-resolution pixels of a call, about 5.3 * (H/8 * W/8)^2 bytes per pair) or only fmap2's three poolings
+ * (1024 * batch * pairs * sum_{l>=1} h_l * w_l bytes), from which every iteration's lookup computes the correlations of the taps it reads: per level the
+ * 256-long dot products of the 11 x 11 integer positions around the sample window, fp32 FMA in a fixed order, blended with the all-pairs lookup's taps and
+ * weights.  Pooling is linear, so the two agree up to fp32 summation order (about 5e-6 on values of order 1); both are deterministic.  The on-the-fly form
+ * costs 4 * 100 * 2 * 256 = 204.8 kFLOP per low-resolution pixel and iteration in place of 2 * 256 * H/8 * W/8 once: fewer above about 640 x 960 at 24
+ * iterations, and the only form that fits when the volume does not.
+ *   cwm_raft_set_corr         CWM_RAFT_CORR_ALL_PAIRS (the default) or CWM_RAFT_CORR_ON_THE_FLY for the forwards of this handle that follow, in either
+ *                             arithmetic mode; the next forward re-plans the workspace when the value changed (the pyramid is not allocated on the fly).
+ *                             Any other value: CWM_ERR_INVALID, and the handle keeps what it had.  Per handle because cwm_raft_forward_args is frozen.
+ *   cwm_raft_workspace_bytes  the bytes of activation workspace the handle holds now (0 before the first forward): what its last plan asked for.
+ *   cwm_raft_corr_lookup_on_the_fly  cwm_raft_corr_lookup (arguments, checks, output, synchronisation) from the feature maps alone: what it allocates
+ *                             inside is fmap2's poolings, not P * (h8 * w8)^2 floats.  As there, h8 and w8 from 8 to 15 are accepted but leave level 3
+ *                             with a side of 1, whose normalisation divides by side - 1 = 0: the 81 features of that level are then NaN (nothing is
+ *                             read out of bounds).  cwm_raft_forward refuses such sizes; give both calls h8, w8 >= 16 for finite output. */
+#define CWM_RAFT_CORR_ALL_PAIRS 0
+#define CWM_RAFT_CORR_ON_THE_FLY 1
+CWM_API int cwm_raft_set_corr(cwm_raft_model* m, int corr);
+CWM_API int cwm_raft_workspace_bytes(cwm_raft_model* m, uint64_t* out);
+CWM_API int cwm_raft_corr_lookup_on_the_fly(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev,
+                                            void* stream);
+
 /* RAFT's forward interpolation on the device: a low-resolution flow carried along itself onto the next frame's grid, which is what the warm-start
  * protocol feeds to the next pair as `flow_init` (added after 0.10.4; the version string is unchanged).
  * replaces: `forward_interpolate` (raft/utils.py:28-56): a `.cpu().numpy()` copy and two scipy `griddata(..., method='nearest')` queries per field.

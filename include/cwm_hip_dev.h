@@ -98,6 +98,9 @@ CWM_API int cwm_dev_raft_conv(const cwm_dev_raft_conv_args* args);
 /* cwm_raft_corr_lookup's pyramid and lookup, written as convc1's operand: [P * h8 * w8] rows of planes * 384 bf16 (features 0..323, then zeros) */
 CWM_API int cwm_dev_raft_corr_lookup_operand(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, int mode,
                                              void* A_dev, void* stream);
+/* the same operand from cwm_raft_corr_lookup_on_the_fly's form (AlternateCorrBlock, raft/corr.py:63-91): fmap2's poolings and the lookup that computes its taps */
+CWM_API int cwm_dev_raft_corr_lookup_on_the_fly_operand(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, int mode,
+                                                        void* A_dev, void* stream);
 /* InstanceNorm2d statistics of x [n_img][HW][C]: stats [n_img][C][2] = (mean, 1 / sqrt(biased var + eps)) */
 CWM_API int cwm_dev_raft_instnorm_stats(const float* x_dev, int n_img, int HW, int C, float eps, float* stats_dev, void* stream);
 /* out[pix][c] = relu(X + Y) over Y->C channels, both read as a cwm_dev_conv_src (no gate / coords); out [n_img * HW][C] may be X->p */

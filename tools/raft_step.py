@@ -7,6 +7,8 @@ once, ~122 GFLOP per pair), one JSON line per batch size.  For the kernel split 
 `--output-dim 1` times the keypoint predictor instead (the model with the output head: one more 3x3 convolution, the 256 -> 1 projection and a
 one-channel convex upsampling in place of the flow's two-channel one); its FLOPs add the head's convolution and projection.
 `--mode fast` times the bf16-operand mode instead of parity; every line names its mode.
+`--corr on_the_fly` times the forward that computes its correlations at lookup time (RAFT.set_corr) and books its FLOPs; every line names
+the form and the bytes of workspace the handle holds after the timed forwards (`workspace_bytes`).
 `--flow-init` times a warm-started forward (`flow_init`: one seeded [1,2,H/8,W/8] field for every pair; one more small launch).
 `--per-iteration` times the list form (the two-image call with `test_mode=False`: the mask head and the upsampling in every iteration, +0.69 GFLOP
 and one full-resolution write each) and prints, per iteration, max-abs and mean-abs of (prediction i - prediction i-1) in pixels: how fast the
@@ -70,6 +72,7 @@ def warm_start_lines(m, args):
         kern = timed(lambda: forward_interpolate(low), args.warmup, max(args.steps, 20))
         same = all(torch.equal(a, b) for a, b in zip(host_chain(), m(x, iters=args.iters, warm_start=True).unbind(1)))
         print(json.dumps({"warm_start": True, "mode": m.mode, "batch": B, "frames": T, "size": [H, W], "iters": args.iters,
+                          "corr": m.corr, "workspace_bytes": m.workspace_bytes(),
                           "chain_device_ms": round(chain[0], 3), "chain_device_ms_min": round(chain[1], 3),
                           "cold_multiframe_ms": round(cold[0], 3), "cold_multiframe_ms_min": round(cold[1], 3),
                           "chain_through_host_ms": round(host[0], 3), "chain_through_host_ms_min": round(host[1], 3),
@@ -87,6 +90,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--output-dim", type=int, default=None, choices=[1], help="time the keypoint forward (the output head) instead of the flow forward")
     ap.add_argument("--mode", default="parity", choices=["parity", "fast"], help="arithmetic of the convolutions (RAFT.set_mode)")
+    ap.add_argument("--corr", default="all_pairs", choices=["all_pairs", "on_the_fly"], help="the correlation: the all-pairs volume, or computed at lookup time (RAFT.set_corr)")
     ap.add_argument("--flow-init", action="store_true", help="time a warm-started forward (flow_init)")
     ap.add_argument("--per-iteration", action="store_true", help="time the list form (test_mode=False) and print how much each iteration moves the prediction")
     ap.add_argument("--warm-start", action="store_true", help="time a warm-started movie: the device chain, the cold call and the chain through the host")
@@ -97,10 +101,11 @@ def main():
     H, W = args.size
     m = RAFT(_args(output_dim=args.output_dim)) if args.output_dim else RAFT()
     m.set_mode(args.mode)
+    m.set_corr(args.corr)
     sd = S.raft_state_dict(0, output_dim=args.output_dim) if args.output_dim else S.raft_state_dict(0)
     m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
     m = m.cuda().eval()
-    flops = C.raft_algorithmic_flops(H, W, args.iters)
+    flops = C.raft_algorithmic_flops(H, W, args.iters, corr=args.corr)
     if args.output_dim:  # output_block.0 (3x3, 128 -> 256) and output_block.2 (256 -> output_dim) at 1/8 resolution
         flops += 2.0 * (H // 8) * (W // 8) * 256 * (128 * 9 + args.output_dim)
     if args.per_iteration:  # the mask head (3x3, 128 -> 256, and 1x1, 256 -> 576) in every iteration instead of once; with the head, output_block too
@@ -138,7 +143,7 @@ def main():
             for i in range(1, len(out)):
                 d = (out[i] - out[i - 1]).abs()
                 print(json.dumps({"batch": B, "iteration": i + 1, "step_max_abs_px": round(d.max().item(), 4), "step_mean_abs_px": round(d.mean().item(), 5)}), flush=True)
-        print(json.dumps({"output": "keypoints" if args.output_dim else "flow", "mode": m.mode, "flow_init": bool(args.flow_init), "per_iteration": bool(args.per_iteration), "batch": B, "size": [H, W], "iters": args.iters, "ms_median": round(ms, 3), "ms_min": round(1e3 * min(times), 3),
+        print(json.dumps({"output": "keypoints" if args.output_dim else "flow", "mode": m.mode, "corr": m.corr, "flow_init": bool(args.flow_init), "per_iteration": bool(args.per_iteration), "batch": B, "size": [H, W], "iters": args.iters, "workspace_bytes": m.workspace_bytes(), "ms_median": round(ms, 3), "ms_min": round(1e3 * min(times), 3),
                           "pairs_per_s": round(B / (ms / 1e3), 2), "gflop_per_pair": round(flops / 1e9, 2),
                           "tflops": round(B * flops / (ms / 1e3) / 1e12, 2)}), flush=True)
 
