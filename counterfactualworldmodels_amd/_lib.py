@@ -392,6 +392,18 @@ class CwmDevConjPadArgs(C.Structure):
     ]
 
 
+class CwmDevGemmPlanPart(C.Structure):
+    _fields_ = [("m_offset", C.c_int32), ("M", C.c_int32), ("kernel", C.c_int32), ("splitk", C.c_int32)]
+
+
+class CwmDevGemmPlanOut(C.Structure):
+    """include/cwm_hip_dev.h cwm_dev_gemm_plan_out (development library only)"""
+    _fields_ = [("cfg", C.c_int32), ("nparts", C.c_int32), ("part", CwmDevGemmPlanPart * 2)]
+
+
+DEV_GEMM_KERNEL_128, DEV_GEMM_KERNEL_DEEP128, DEV_GEMM_KERNEL_DEEP64, DEV_GEMM_KERNEL_8PHASE = range(4)
+
+
 def new_dev_conj_args(cls):
     """a zeroed cwm_dev_conj_*_args of the given structure class with its struct_size set"""
     a = cls()
@@ -509,6 +521,7 @@ SIGNATURES = {
 # ... and every symbol of include/cwm_hip_dev.h: only libcwm_hip_dev.so (get_dev_lib) has these
 DEV_SIGNATURES = {
     "cwm_gemm_tile_override": (C.c_int, [C.c_int] * 6),
+    "cwm_dev_gemm_plan": (C.c_int, [C.c_int] * 8 + [C.POINTER(CwmDevGemmPlanOut)]),
     "cwm_bench_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "cwm_bench_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "cwm_debug_set": (C.c_int, [C.c_char_p, C.c_int]),

@@ -109,6 +109,34 @@ extern "C" int cwm_gemm_tile_override(int M, int N, int K, int epi, int overlapp
     return 0;
 }
 
+// What gemm_plan decides for a launch of this shape under this thread's options: nothing is launched and no device is needed.
+extern "C" int cwm_dev_gemm_plan(int M, int N, int K, int epi, int mode, int overlapped, int forced_cfg, int cus, cwm_dev_gemm_plan_out* out) {
+    CWM_REQUIRE(out && epi >= 0 && epi <= 3 && forced_cfg >= 0 && cus >= 0, "cwm_dev_gemm_plan: bad argument");
+    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_dev_gemm_plan: bad mode");
+    static_assert(CWM_DEV_GEMM_KERNEL_128 == GEMM_KERNEL_128 && CWM_DEV_GEMM_KERNEL_DEEP128 == GEMM_KERNEL_DEEP128 &&
+                      CWM_DEV_GEMM_KERNEL_DEEP64 == GEMM_KERNEL_DEEP64 && CWM_DEV_GEMM_KERNEL_8PHASE == GEMM_KERNEL_8PHASE,
+                  "cwm_hip_dev.h names the kernels of kernels.h GemmKernel");
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.M = M; p.N = N; p.K = K; p.lda = K; p.epi = epi;
+    p.ldc = p.ldr = p.ldo = N;                                                   // dense outputs, as cwm_bench_gemm makes them
+    p.rows_in = p.n_tok = M; p.qkv_dim = N / 3; p.head_dim = 64;  // EPI_QKV: one sample of M tokens, heads of 64
+    p.overlapped = overlapped ? 1 : 0;
+    p.tune = &thread_tuning();
+    GemmPlan plan;
+    if (int rc = gemm_plan(p, mode == CWM_MODE_PARITY ? 2 : 1, forced_cfg, cus ? cus : gemm_cu_count(), &plan)) return rc;
+    memset(out, 0, sizeof(*out));
+    out->cfg = plan.cfg;
+    out->nparts = plan.nparts;
+    for (int i = 0; i < plan.nparts; ++i) {
+        out->part[i].m_offset = plan.part[i].m_offset;
+        out->part[i].M = plan.part[i].M;
+        out->part[i].kernel = plan.part[i].kernel;
+        out->part[i].splitk = plan.part[i].splitk;
+    }
+    return CWM_OK;
+}
+
 extern "C" int cwm_bench_gemm(int M, int N, int K, int mode, int epi, int iters, double* avg_us) {
     CWM_REQUIRE(avg_us && M > 0 && N > 0 && K > 0 && iters > 0, "cwm_bench_gemm: bad argument");
     CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_bench_gemm: bad mode");

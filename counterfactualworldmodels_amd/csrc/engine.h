@@ -176,6 +176,7 @@ struct Engine {
     int set_option(const char* fn, const char* key, int value);  // cwm_model_set_option / cwm_conj_set_option
 
     int run_gemm(const GemmParams& p, int planes, hipStream_t s);
+    int attach_splitk_workspace(GemmParams& p, hipStream_t s);  // this stream's entry of splitk_ws, created or evicted as needed
     int run_attention(const AttnParams& p, int planes, hipStream_t s);
     // the HBM-bound edge kernels, booked by class with their algorithmic bytes (cwm_hip.h CWM_KCLASS_*)
     int run_layernorm(const LayerNormParams& p, int planes, hipStream_t s);

@@ -425,55 +425,49 @@ int Engine::timer_end(EventPair* e, hipStream_t s) {
     return 0;
 }
 
+// This stream's split-K workspace, created on first need (32 MB + counters; at most kMaxSplitKStreams per engine: a caller that rotates streams evicts
+// the oldest), attached to a launch whose plan splits K.
+int Engine::attach_splitk_workspace(GemmParams& p, hipStream_t s) {
+    auto it = splitk_ws.find(s);
+    if (it == splitk_ws.end()) {
+        if (splitk_ws.size() >= kMaxSplitKStreams) {
+            // evict the workspace of the stream that used one longest ago.  (hipFree waits for the device, so a launch of that stream
+            // that still reads it finishes first; the stream itself may be gone -- a caller that rotates streams has usually destroyed
+            // it --, so it is not touched.)  The entry leaves the table before anything here can fail.
+            auto victim = splitk_ws.begin();
+            for (auto w = splitk_ws.begin(); w != splitk_ws.end(); ++w)
+                if (w->second.last_use < victim->second.last_use) victim = w;
+            const SplitKWs old = victim->second;
+            splitk_ws.erase(victim);
+            (void)hipFree(old.slabs);
+            (void)hipFree(old.counts);
+        }
+        SplitKWs w = {nullptr, nullptr, 0};
+        if (int rc = splitk_workspace_alloc(&w.slabs, &w.counts, s)) return rc;
+        it = splitk_ws.emplace(s, w).first;
+    }
+    it->second.last_use = ++splitk_clock;
+    p.sk2_slabs = it->second.slabs;
+    p.sk2_count = it->second.counts;
+    return 0;
+}
+
+// One GEMM of the model: planned once (gemm.hip gemm_plan), then launched part by part -- the two kernels of a mixed-tiling launch are booked
+// separately, so that the per-kernel averages of a timed run are those rocprofv3 sees.
 int Engine::run_gemm(const GemmParams& p_in, int planes, hipStream_t s) {
     GemmParams p = p_in;
     p.overlapped = overlapped;
     p.tune = &tune;
-    const int cfg = gemm_choose_tile(p, planes);
-    {   // a launch (or the 128x128 remainder of a mixed-tiling launch: fc2 of a single-lane batch) that takes the deep-ring kernel's split-K
-        // path carries this stream's workspace, created on first need (32 MB + counters; at most kMaxSplitKStreams per engine: a caller
-        // that rotates streams evicts the oldest)
-        GemmParams big, rest;
-        const bool split = (cfg == 1 && gemm_splitk_parts(p, planes) > 1) ||
-                           (cfg == 6 && gemm_mixed_split(p, &big, &rest) && gemm_splitk_parts(rest, planes) > 1);
-        if (split) {
-            auto it = splitk_ws.find(s);
-            if (it == splitk_ws.end()) {
-                if (splitk_ws.size() >= kMaxSplitKStreams) {
-                    // evict the workspace of the stream that used one longest ago.  (hipFree waits for the device, so a launch of that stream
-                    // that still reads it finishes first; the stream itself may be gone -- a caller that rotates streams has usually destroyed
-                    // it --, so it is not touched.)  The entry leaves the table before anything here can fail.
-                    auto victim = splitk_ws.begin();
-                    for (auto w = splitk_ws.begin(); w != splitk_ws.end(); ++w)
-                        if (w->second.last_use < victim->second.last_use) victim = w;
-                    const SplitKWs old = victim->second;
-                    splitk_ws.erase(victim);
-                    (void)hipFree(old.slabs);
-                    (void)hipFree(old.counts);
-                }
-                SplitKWs w = {nullptr, nullptr, 0};
-                if (int rc = splitk_workspace_alloc(&w.slabs, &w.counts, s)) return rc;
-                it = splitk_ws.emplace(s, w).first;
-            }
-            it->second.last_use = ++splitk_clock;
-            p.sk2_slabs = it->second.slabs;
-            p.sk2_count = it->second.counts;
-        }
-    }
-    GemmParams part[2];
-    int cfgs[2] = {cfg, 0}, nparts = 1;
-    part[0] = p;
-    if (cfg == 6 && timers[CWM_KCLASS_GEMM].enabled && gemm_mixed_split(p, &part[0], &part[1])) {
-        // timed runs book the two kernels of a mixed-tiling launch separately (so that the per-kernel averages are those rocprofv3 sees)
-        cfgs[0] = 4;
-        cfgs[1] = 1;
-        nparts = 2;
-    }
-    for (int i = 0; i < nparts; ++i) {
+    GemmPlan plan;
+    if (int rc = gemm_plan(p, planes, 0, gemm_cu_count(), &plan)) return rc;
+    if (plan.splits_k())
+        if (int rc = attach_splitk_workspace(p, s)) return rc;
+    for (int i = 0; i < plan.nparts; ++i) {
+        const GemmPlan::Part& part = plan.part[i];
         EventPair* e;
-        if (int rc = timer_begin(CWM_KCLASS_GEMM, 2.0 * part[i].M * (double)part[i].N * part[i].K, s, &e)) return rc;
-        if (e) e->sub = (cfgs[i] == 3 || cfgs[i] == 4) ? CWM_KCLASS_GEMM_WIDE : CWM_KCLASS_GEMM_NARROW;
-        if (int rc = (nparts == 2 ? launch_gemm_tile(part[i], planes, cfgs[i], s) : launch_gemm(part[i], planes, s))) return rc;
+        if (int rc = timer_begin(CWM_KCLASS_GEMM, 2.0 * part.M * (double)p.N * p.K, s, &e)) return rc;
+        if (e) e->sub = part.kernel == GEMM_KERNEL_8PHASE ? CWM_KCLASS_GEMM_WIDE : CWM_KCLASS_GEMM_NARROW;
+        if (int rc = launch_gemm_part(p, planes, plan, i, s)) return rc;
         if (int rc = timer_end(e, s)) return rc;
     }
     return 0;

@@ -4,9 +4,11 @@
 // fc1/fc2, :93 qkv, :119 proj; vmae.py:547 encoder_to_decoder, :251 head; the Conv3d patch embed of
 // VideoMAE/utils.py:174-197 expressed as an im2col GEMM).
 //
-// Kernels in this file (launch_gemm picks per shape, gemm_choose_tile):
-//   gemm_bf16_kernel<PLANES, BM, BN, WM, WN>  one barrier + vmcnt(0) per K tile, 2-stage LDS ring; used as 128x128 / 256 threads
+// Kernels in this file (gemm_plan picks per shape; launch_gemm_part launches):
+//   gemm_bf16_kernel<PLANES, BM, BN, WM, WN>  one barrier + vmcnt(0) per K tile, 2-stage LDS ring; used as 128x128 / 512 threads (8 waves)
 //                                            with two workgroups per CU for narrow outputs (N <= 768) and remainders
+//   gemm_bf16_kernel<..., STAGES = 4>         the same loop on a 4-stage ring, 128x128 / 512 threads or 64x128 / 256 threads: launches of at most
+//                                            one tile per CU, optionally with K split over the idle CUs
 //   gemm8p_kernel<PLANES>                     256x256 / 512 threads, 8-phase main loop (staggered wave groups, LDS-DMA in flight
 //                                            across raw barriers): wide outputs (N >= 1024) and whole rounds of narrow ones
 // Common to both:
@@ -583,28 +585,7 @@ int splitk_workspace_alloc(float** slabs, unsigned** counts, hipStream_t stream)
     return 0;
 }
 
-// Does this launch take the split-K path of the deep-ring kernel?  (the engine creates a stream's workspace only then)
-// Tile height of the deep-ring kernel for a launch with at most one 128x128 tile per CU: 64 rows when the 128-row grid would leave half of the
-// CUs idle (batch 1: 792 rows = 7 row tiles, the last one 24 rows; qkv 126 tiles on 256 CUs -> 13 x 18 = 234 tiles of half the work each).
-// "gemm_debug" bit 8 keeps 128.
 static inline const Tuning& tn(const GemmParams& p) { return p.tune ? *p.tune : default_tuning(); }
-
-static int deep_tile_rows(const GemmParams& p) {
-    const int tiles128 = ((p.M + 127) / 128) * ((p.N + 127) / 128);
-    return (tiles128 * 2 <= gemm_cu_count() && p.M > 64 && !(tn(p).gemm_debug & 256)) ? 64 : 128;
-}
-
-int gemm_splitk_parts(const GemmParams& p, int planes) {
-    if (tn(p).gemm_debug & (4 | 32)) return 1;
-    const int tiles128 = ((p.M + 127) / 128) * ((p.N + 127) / 128);
-    const int cus = gemm_cu_count();
-    if (tiles128 > cus) return 1;
-    const int bm = deep_tile_rows(p);
-    const int tiles = ((p.M + bm - 1) / bm) * ((p.N + 127) / 128);
-    const int nk_all = p.K / (64 / planes);
-    const int sk = std::min(std::min(cus / tiles, nk_all / 12), 8);
-    return sk >= 3 ? sk : 1;
-}
 
 int gemm_cu_count() {
     static int cus = 0;
@@ -618,40 +599,42 @@ int gemm_cu_count() {
     return cus;
 }
 
-static int launch_gemm_cfg(GemmParams& p, int planes, int cfg, hipStream_t stream);
-
-// Mixed tiling (tile configuration 6): the leading rows that fill whole rounds of 256x256 tiles go to the 8-phase kernel, the
-// remaining rows to 128x128 tiles.  Both kernels apply the same product sequence to every accumulator, so the result does not
-// depend on the split.  Returns false if the shape has no such split.
-bool gemm_mixed_split(const GemmParams& p, GemmParams* big, GemmParams* rest) {
-    const int tiles_n = (p.N + 255) / 256, tiles_m = (p.M + 255) / 256;
-    const int cus = gemm_cu_count();
-    const int rounds = (tiles_m * tiles_n) / cus;
-    const int big_rows = std::min(tiles_m - 1, rounds * cus / tiles_n);  // m-tile rows of the 8-phase part
-    if (rounds < 1 || big_rows < 1) return false;
-    *big = p;
-    *rest = p;
-    big->M = big_rows * 256;
-    rest->m_offset = p.m_offset + big->M;
-    rest->M = p.M - big->M;
-    return true;
-}
-
-static int launch_gemm_checked(const GemmParams& p_in, int planes, int forced_cfg, hipStream_t stream);
-
-// One launch with a given tile configuration (1 .. 5), after launch_gemm's argument checks.  (The configuration is an explicit
-// argument all the way down: no process-global is touched, so forwards on two host threads cannot race on it.)
-int launch_gemm_tile(const GemmParams& p_in, int planes, int cfg, hipStream_t stream) { return launch_gemm_checked(p_in, planes, cfg, stream); }
-
-int launch_gemm(const GemmParams& p_in, int planes, hipStream_t stream) { return launch_gemm_checked(p_in, planes, 0, stream); }
-
-// Tile configuration for a launch: Tuning.gemm_tile (development switch) if set, else the development library's per-shape hook, else the measured rule.
-int gemm_choose_tile(const GemmParams& p, int planes) {
-    (void)planes;
+// Everything that is decided before a GEMM launch, decided here and nowhere else: the argument checks, the epilogue form, the tile configuration
+// (Tuning.gemm_tile -- or `forced_cfg` > 0 -- if set, else the development library's per-shape hook, else the measured rule), the row split of mixed
+// tiling, and per part the kernel and its split-K count.  Host arithmetic only (no HIP call): `cus` is the caller's gemm_cu_count().
+int gemm_plan(const GemmParams& p, int planes, int forced_cfg, int cus, GemmPlan* plan) {
     const Tuning& t = tn(p);
-    int cfg = t.gemm_tile;
+    CWM_REQUIRE(planes == 1 || planes == 2, "gemm: planes must be 1 or 2");
+    CWM_REQUIRE(p.K % 64 == 0, "gemm: K=%d must be a multiple of 64", p.K);
+    CWM_REQUIRE(p.lda % 8 == 0, "gemm: lda=%d must be a multiple of 8", p.lda);
+    CWM_REQUIRE(p.M > 0 && p.N > 0, "gemm: empty problem M=%d N=%d", p.M, p.N);
+    CWM_REQUIRE(p.N % 16 == 0, "gemm: N=%d must be a multiple of 16", p.N);
+    if (p.epi == EPI_F32) {
+        CWM_REQUIRE(p.ldc % 4 == 0 && (!p.resid || p.ldr % 4 == 0), "gemm: ldc/ldr must be multiples of 4");
+    } else if (p.epi == EPI_QKV) {
+        CWM_REQUIRE(p.rows_in == p.n_tok && p.N == 3 * p.qkv_dim && p.head_dim % 4 == 0, "gemm: bad QKV epilogue setup");
+        CWM_REQUIRE(p.qkv_dim % 16 == 0, "gemm: QKV epilogue needs the model width (%d) to be a multiple of 16", p.qkv_dim);
+    } else {
+        CWM_REQUIRE(p.ldo % 4 == 0, "gemm: ldo must be a multiple of 4");
+        CWM_REQUIRE(planes == 1 || p.ldo % 32 == 0, "gemm: split-bf16 output rows are whole [32 hi | 32 lo] blocks: ldo=%d must be a multiple of 32", p.ldo);
+    }
+    // ---- LDS-staged epilogue whenever its 16-byte row segments are aligned (always, for the predictor's widths) ----
+    plan->staged = 0;
+    if (t.gemm_staged) {
+        if (p.epi == EPI_F32) plan->staged = 1;
+        else if (p.epi == EPI_QKV) plan->staged = (p.qkv_dim % 32 == 0 && p.head_dim % 32 == 0);
+        else plan->staged = (p.ldo % 8 == 0);
+    }
+    // LDS-DMA source addresses are 32-bit element offsets from the operand base pointers (one VGPR per piece): the operands must stay
+    // below 2^32 elements (parity-mode fc2 of ViT-L/4 reaches that at batch ~165: chunk M on the host beyond it)
+    CWM_REQUIRE((int64_t)(p.m_offset + p.M) * p.lda * planes < (1ll << 32) && (int64_t)(((p.N + 255) / 256) * 256) * p.K * planes < (1ll << 32),
+                "gemm: operand too large for 32-bit element offsets (M=%d lda=%d N=%d K=%d planes=%d): split the batch", p.m_offset + p.M, p.lda,
+                p.N, p.K, planes);
+    plan->direct = (t.gemm_direct && plan->staged && (p.epi != EPI_F32 || t.gemm_direct >= 2)) ? 1 : 0;
+
+    // ---- tile configuration: 0 auto, 1: 128x128, 4: 256x256 8-phase, 6: 4 + 1 by rows ----
+    int cfg = forced_cfg > 0 ? forced_cfg : t.gemm_tile;
     if (cfg == 0 && t.tile_hook) cfg = t.tile_hook(p.M, p.N, p.K, p.epi, p.overlapped ? 1 : 0);
-    // 0 auto, 1: 128x128, 4: 256x256 8-phase, 6: 4 + 1 by rows
     if (cfg == 0) {
         // Measured on MI355X (tools/microbench.py gemm / gemm_mid / gemm_l4: B/8 at batch 8, 16, 32 and L/4 batch 8, both modes;
         // profiles/r1n_*, r1o_*, r1p_* logs).  The 256x256 8-phase kernel has the fastest main loop (~1.6 PFLOP/s of executed MFMA
@@ -675,7 +658,6 @@ int gemm_choose_tile(const GemmParams& p, int planes) {
             // (a half-width last column tile holds its CU for ~0.6 of a full tile's time: counted as such when the fill of the rounds is judged)
             const int64_t tiles_m = (p.M + 255) / 256, tiles_n = (p.N + 255) / 256;
             const int64_t tiles = (half_ok && p.N % 256 == 128) ? tiles_m * (tiles_n - 1) + (tiles_m * 3 + 4) / 5 : tiles_m * tiles_n;
-            const int cus = gemm_cu_count();
             if (tiles < cus) {
                 // one partial round: from half the CUs up.  Inside a two-lane call the other lane fills the idle CUs, and the launches whose tile is long (K >= 1024:
                 // fc2) or whose epilogue is the direct one (bf16 outputs) win on the 8-phase kernel from 0.4 of the CUs (tools/autotune_step.py and
@@ -705,125 +687,122 @@ int gemm_choose_tile(const GemmParams& p, int planes) {
             }
         }
     }
-    return cfg;
-}
-
-static int launch_gemm_checked(const GemmParams& p_in, int planes, int forced_cfg, hipStream_t stream) {
-    GemmParams p = p_in;
-    const Tuning& t = tn(p);
-    p.debug = t.gemm_debug;
-    CWM_REQUIRE(planes == 1 || planes == 2, "gemm: planes must be 1 or 2");
-    CWM_REQUIRE(p.K % 64 == 0, "gemm: K=%d must be a multiple of 64", p.K);
-    CWM_REQUIRE(p.lda % 8 == 0, "gemm: lda=%d must be a multiple of 8", p.lda);
-    CWM_REQUIRE(p.M > 0 && p.N > 0, "gemm: empty problem M=%d N=%d", p.M, p.N);
-    CWM_REQUIRE(p.N % 16 == 0, "gemm: N=%d must be a multiple of 16", p.N);
-    if (p.epi == EPI_F32) {
-        CWM_REQUIRE(p.ldc % 4 == 0 && (!p.resid || p.ldr % 4 == 0), "gemm: ldc/ldr must be multiples of 4");
-    } else if (p.epi == EPI_QKV) {
-        CWM_REQUIRE(p.rows_in == p.n_tok && p.N == 3 * p.qkv_dim && p.head_dim % 4 == 0, "gemm: bad QKV epilogue setup");
-        CWM_REQUIRE(p.qkv_dim % 16 == 0, "gemm: QKV epilogue needs the model width (%d) to be a multiple of 16", p.qkv_dim);
-    } else {
-        CWM_REQUIRE(p.ldo % 4 == 0, "gemm: ldo must be a multiple of 4");
-        CWM_REQUIRE(planes == 1 || p.ldo % 32 == 0, "gemm: split-bf16 output rows are whole [32 hi | 32 lo] blocks: ldo=%d must be a multiple of 32", p.ldo);
-    }
-    // ---- LDS-staged epilogue whenever its 16-byte row segments are aligned (always, for the predictor's widths) ----
-    p.staged = 0;
-    if (t.gemm_staged) {
-        if (p.epi == EPI_F32) p.staged = 1;
-        else if (p.epi == EPI_QKV) p.staged = (p.qkv_dim % 32 == 0 && p.head_dim % 32 == 0);
-        else p.staged = (p.ldo % 8 == 0);
-    }
-    // LDS-DMA source addresses are 32-bit element offsets from the operand base pointers (one VGPR per piece): the operands must stay
-    // below 2^32 elements (parity-mode fc2 of ViT-L/4 reaches that at batch ~165: chunk M on the host beyond it)
-    CWM_REQUIRE((int64_t)(p.m_offset + p.M) * p.lda * planes < (1ll << 32) && (int64_t)(((p.N + 255) / 256) * 256) * p.K * planes < (1ll << 32),
-                "gemm: operand too large for 32-bit element offsets (M=%d lda=%d N=%d K=%d planes=%d): split the batch", p.m_offset + p.M, p.lda,
-                p.N, p.K, planes);
-    p.direct = (t.gemm_direct && p.staged && (p.epi != EPI_F32 || t.gemm_direct >= 2)) ? 1 : 0;
-    int cfg = forced_cfg > 0 ? forced_cfg : gemm_choose_tile(p, planes);
+    // ---- rows.  Mixed tiling (6): the leading rows that fill whole rounds of 256x256 tiles go to the 8-phase kernel, the remaining rows to 128x128
+    // tiles.  Both kernels apply the same product sequence to every accumulator, so the result does not depend on the split.  A shape without a whole
+    // round has no such split and runs on 128x128 tiles.
+    plan->nparts = 1;
+    plan->part[0].m_offset = p.m_offset;
+    plan->part[0].M = p.M;
     if (cfg == 6) {
-        GemmParams a, b;
-        if (gemm_mixed_split(p, &a, &b)) {
-            if (int rc = launch_gemm_cfg(a, planes, 4, stream)) return rc;
-            return launch_gemm_cfg(b, planes, 1, stream);
+        const int tiles_n = (p.N + 255) / 256, tiles_m = (p.M + 255) / 256;
+        const int rounds = (tiles_m * tiles_n) / cus;
+        const int big_rows = std::min(tiles_m - 1, rounds * cus / tiles_n);  // m-tile rows of the 8-phase part
+        if (rounds >= 1 && big_rows >= 1) {
+            plan->nparts = 2;
+            plan->part[0].M = big_rows * 256;
+            plan->part[1].m_offset = p.m_offset + big_rows * 256;
+            plan->part[1].M = p.M - big_rows * 256;
+        } else {
+            cfg = 1;
         }
-        cfg = 1;
     }
-    return launch_gemm_cfg(p, planes, cfg, stream);
-}
-
-static int launch_gemm_cfg(GemmParams& p, int planes, int cfg, hipStream_t stream) {
-    typedef void (*kern_t)(const GemmParams);
-    CWM_REQUIRE(cfg == 1 || cfg == 4, "gemm: unknown tile configuration %d (1: 128x128, 4: 256x256 8-phase)", cfg);
-    const int dbg = tn(p).gemm_debug;
-    if (cfg == 4) {
-        static const kern_t k8[2] = {gemm8p_kernel<1>, gemm8p_kernel<2>};
-        const size_t smem8 = 2 * 4 * 128 * 128;
-        kern_t k = k8[planes - 1];
-        if (int rc = cwm_set_max_lds((const void*)k, (int)smem8)) return rc;
-        const int tiles8 = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-        hipLaunchKernelGGL(k, dim3(tiles8), dim3(512), smem8, stream, p);
-        CWM_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    // 128x128 tiles, at most one workgroup per CU (fewer tiles than CUs): the 4-stage ring hides the staging latency that the second
-    // co-resident workgroup hides in bigger launches ("gemm_debug" bit 2 switches it off for A/B runs)
-    const int tiles128 = ((p.M + 127) / 128) * ((p.N + 127) / 128);
-    const int cus = gemm_cu_count();
-    const bool deep = !(dbg & 4) && tiles128 <= cus;
-    p.splitk = 1;
-    if (deep && !(dbg & 32)) {
+    CWM_REQUIRE(cfg == 1 || cfg == 4 || cfg == 6, "gemm: unknown tile configuration %d (1: 128x128, 4: 256x256 8-phase, 6: mixed)", cfg);
+    plan->cfg = cfg;
+    // ---- the kernel of each part ----
+    for (int i = 0; i < plan->nparts; ++i) {
+        GemmPlan::Part& part = plan->part[i];
+        part.splitk = 1;
+        if (cfg == 4 || (cfg == 6 && i == 0)) {
+            part.kernel = GEMM_KERNEL_8PHASE;
+            continue;
+        }
+        // 128x128 tiles as 8-wave workgroups (64x32 per wave), two per CU = FOUR waves per SIMD: measured 5-25 % faster than the 4-wave form (two
+        // waves per SIMD) on every model shape -- the extra waves cover the per-K-tile barrier + LDS-DMA latency that the simple loop exposes.
+        // (Rounds 1-4 also carried 256x128 and 256x256 tiles on this loop and the 4-wave forms: never selected by the rule above, removed in round 5.)
+        part.kernel = GEMM_KERNEL_128;
+        // 128x128 tiles, at most one workgroup per CU (fewer tiles than CUs): the 4-stage ring hides the staging latency that the second
+        // co-resident workgroup hides in bigger launches ("gemm_debug" bit 2 switches it off for A/B runs)
+        const int tiles128 = ((part.M + 127) / 128) * ((p.N + 127) / 128);
+        if ((t.gemm_debug & 4) || tiles128 > cus) continue;
+        // 8 waves of 64x32 (two per SIMD cover each other's LDS / barrier latency; the 4-wave form measured slower and was removed in round 5), or
+        // 64x128 tiles as 4 waves of 64x32 where the 128-row grid would leave half of the CUs idle (batch 1: 792 rows = 7 row tiles, the last one
+        // 24 rows; qkv 126 tiles on 256 CUs -> 13 x 18 = 234 tiles of half the work each).  "gemm_debug" bit 8 keeps 128.
+        const int bm = (tiles128 * 2 <= cus && part.M > 64 && !(t.gemm_debug & 256)) ? 64 : 128;
+        part.kernel = bm == 64 ? GEMM_KERNEL_DEEP64 : GEMM_KERNEL_DEEP128;
+        if (t.gemm_debug & 32) continue;
         // fill the idle CUs of a latency-bound launch by cutting K: only where it pays (measured, ViT-B/8 batch 1: fc2 65 -> 32 us with
         // 6 parts, decoder fc2 36 -> 26 us; two parts of a K = 768 qkv projection LOSE 6 us to the hand-off) -- at least three parts of at
         // least 12 K tiles each; the parts of a tile are reduced in a fixed order (deterministic)
-        const int sk = gemm_splitk_parts(p, planes);
-        if (sk >= 3) {
-            if (!p.sk2_slabs) {
-                // callers without a workspace of their own (the stand-alone entry points, cwm_linear): one workspace per (device,
-                // stream), created under a lock -- launches on one stream are ordered, so they may share it; two streams never do
-                struct Ws { float* slabs; unsigned* counts; };
-                static std::mutex mu;
-                static std::map<std::pair<int, hipStream_t>, Ws> table;
-                int dev = 0;
-                CWM_HIP_CHECK(hipGetDevice(&dev));
-                std::lock_guard<std::mutex> lock(mu);
-                auto it = table.find(std::make_pair(dev, stream));
-                if (it == table.end()) {
-                    Ws w = {nullptr, nullptr};
-                    if (int rc = splitk_workspace_alloc(&w.slabs, &w.counts, stream)) return rc;
-                    it = table.emplace(std::make_pair(dev, stream), w).first;
-                }
-                p.sk2_slabs = it->second.slabs;
-                p.sk2_count = it->second.counts;
-            }
-            p.splitk = sk;
-        }
+        const int tiles = ((part.M + bm - 1) / bm) * ((p.N + 127) / 128);
+        const int nk_all = p.K / (64 / planes);
+        const int sk = std::min(std::min(cus / tiles, nk_all / 12), 8);
+        if (sk >= 3) part.splitk = sk;
     }
-    if (deep) {
-        // 8 waves of 64x32 (two per SIMD cover each other's LDS / barrier latency; the 4-wave form measured slower and was removed in round 5), or
-        // 64x128 tiles as 4 waves of 64x32 where the 128-row grid would leave half of the CUs idle
-        static const kern_t deep128w8[2] = {gemm_bf16_kernel<1, 128, 128, 2, 4, 4>, gemm_bf16_kernel<2, 128, 128, 2, 4, 4>};
-        static const kern_t deep64[2] = {gemm_bf16_kernel<1, 64, 128, 1, 4, 4>, gemm_bf16_kernel<2, 64, 128, 1, 4, 4>};
-        const int bm = deep_tile_rows(p);
-        const size_t smem = (size_t)4 * (bm + 128) * 128;
-        kern_t k = bm == 64 ? deep64[planes - 1] : deep128w8[planes - 1];
-        const int tiles = ((p.M + bm - 1) / bm) * ((p.N + 127) / 128);
-        if (int rc = cwm_set_max_lds((const void*)k, (int)smem)) return rc;
-        hipLaunchKernelGGL(k, dim3(tiles * p.splitk), dim3(bm == 64 ? 256 : 512), smem, stream, p);
-        CWM_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    // 128x128 tiles as 8-wave workgroups (64x32 per wave), two per CU = FOUR waves per SIMD: measured 5-25 % faster than the 4-wave form (two
-    // waves per SIMD) on every model shape -- the extra waves cover the per-K-tile barrier + LDS-DMA latency that the simple loop exposes.
-    // (Rounds 1-4 also carried 256x128 and 256x256 tiles on this loop and the 4-wave forms: never selected by the rule above, removed in round 5.)
-    static const kern_t kerns[2] = {gemm_bf16_kernel<1, 128, 128, 2, 4>, gemm_bf16_kernel<2, 128, 128, 2, 4>};
-    // (the epilogue's eight 8-KiB wave buffers fill the 64-KiB operand ring; the row table sits behind them)
-    const size_t smem = (size_t)2 * (128 + 128) * 128 + 4096;
-    const int tiles = ((p.M + 127) / 128) * ((p.N + 127) / 128);
-    kern_t k = kerns[planes - 1];
-    CWM_REQUIRE(smem >= (size_t)8 * 8192 + (size_t)128 * 16 + (size_t)128 * 8, "gemm: dynamic LDS too small for the staged epilogue (wave buffers + row table)");
-    if (int rc = cwm_set_max_lds((const void*)k, (int)smem)) return rc;
-    hipLaunchKernelGGL(k, dim3(tiles), dim3(512), smem, stream, p);
+    return 0;
+}
+
+// Launches part `i` of a plan made from these parameters.  A part that splits K needs the caller's workspace (sk2_slabs / sk2_count): one per stream
+// that launches at a time -- the engine's own (engine.hip), or launch_gemm's process-wide one.
+int launch_gemm_part(const GemmParams& p_in, int planes, const GemmPlan& plan, int i, hipStream_t stream) {
+    typedef void (*kern_t)(const GemmParams);
+    struct Shape {
+        kern_t kernel[2];  // fast, parity
+        int bm, bn, threads;
+        size_t smem;
+    };
+    static const Shape shapes[4] = {
+        // GEMM_KERNEL_128 (the epilogue's eight 8-KiB wave buffers fill the 64-KiB operand ring; the row table sits behind them)
+        {{gemm_bf16_kernel<1, 128, 128, 2, 4>, gemm_bf16_kernel<2, 128, 128, 2, 4>}, 128, 128, 512, (size_t)2 * (128 + 128) * 128 + 4096},
+        // GEMM_KERNEL_DEEP128, GEMM_KERNEL_DEEP64: the 4-stage ring
+        {{gemm_bf16_kernel<1, 128, 128, 2, 4, 4>, gemm_bf16_kernel<2, 128, 128, 2, 4, 4>}, 128, 128, 512, (size_t)4 * (128 + 128) * 128},
+        {{gemm_bf16_kernel<1, 64, 128, 1, 4, 4>, gemm_bf16_kernel<2, 64, 128, 1, 4, 4>}, 64, 128, 256, (size_t)4 * (64 + 128) * 128},
+        // GEMM_KERNEL_8PHASE
+        {{gemm8p_kernel<1>, gemm8p_kernel<2>}, 256, 256, 512, (size_t)2 * 4 * 128 * 128},
+    };
+    static_assert((size_t)2 * (128 + 128) * 128 + 4096 >= (size_t)8 * 8192 + (size_t)128 * 16 + (size_t)128 * 8,
+                  "gemm: dynamic LDS too small for the staged epilogue (wave buffers + row table)");
+    const GemmPlan::Part& part = plan.part[i];
+    const Shape& k = shapes[part.kernel];
+    GemmParams p = p_in;
+    p.m_offset = part.m_offset;
+    p.M = part.M;
+    p.splitk = part.splitk;
+    p.staged = plan.staged;
+    p.direct = plan.direct;
+    p.debug = tn(p).gemm_debug;
+    CWM_REQUIRE(part.splitk == 1 || (p.sk2_slabs && p.sk2_count), "gemm: a launch that splits K needs the caller's split-K workspace");
+    if (int rc = cwm_set_max_lds((const void*)k.kernel[planes - 1], (int)k.smem)) return rc;
+    const int tiles = ((p.M + k.bm - 1) / k.bm) * ((p.N + k.bn - 1) / k.bn);
+    hipLaunchKernelGGL(k.kernel[planes - 1], dim3(tiles * part.splitk), dim3(k.threads), k.smem, stream, p);
     CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// The stand-alone callers (cwm_linear, the development library's entry points): plan for the current device and launch the parts.  They have no
+// workspace of their own, so a launch that splits K takes one per (device, stream) from a process-wide table, created under a lock and never freed --
+// launches on one stream are ordered, so they may share it; two streams never do.  (A model's launches go through Engine::run_gemm and never come here.)
+int launch_gemm(const GemmParams& p_in, int planes, hipStream_t stream) {
+    GemmPlan plan;
+    if (int rc = gemm_plan(p_in, planes, 0, gemm_cu_count(), &plan)) return rc;
+    GemmParams p = p_in;
+    if (plan.splits_k() && !p.sk2_slabs) {
+        struct Ws { float* slabs; unsigned* counts; };
+        static std::mutex mu;
+        static std::map<std::pair<int, hipStream_t>, Ws> table;
+        int dev = 0;
+        CWM_HIP_CHECK(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lock(mu);
+        auto it = table.find(std::make_pair(dev, stream));
+        if (it == table.end()) {
+            Ws w = {nullptr, nullptr};
+            if (int rc = splitk_workspace_alloc(&w.slabs, &w.counts, stream)) return rc;
+            it = table.emplace(std::make_pair(dev, stream), w).first;
+        }
+        p.sk2_slabs = it->second.slabs;
+        p.sk2_count = it->second.counts;
+    }
+    for (int i = 0; i < plan.nparts; ++i)
+        if (int rc = launch_gemm_part(p, planes, plan, i, stream)) return rc;
     return 0;
 }
 

@@ -9,7 +9,7 @@ namespace cwm {
 // test suite.  A launch reads them through its parameter struct (GemmParams.tune, AttnParams.tune; nullptr = the defaults), a forward through its
 // Engine -- never from a global, so two models in one process cannot change each other's kernels.
 struct Tuning {
-    int gemm_tile = 0;     // 0 automatic per shape (gemm_choose_tile), 1: 128x128, 4: 256x256 8-phase, 6: 8-phase rounds + 128x128 remainder rows
+    int gemm_tile = 0;     // 0 automatic per shape (gemm_plan), 1: 128x128, 4: 256x256 8-phase, 6: 8-phase rounds + 128x128 remainder rows
     int gemm_debug = 0;    // bit mask of ablations / A-B switches: 1 skip the epilogue's global stores, 2 skip the epilogue, 4 no 4-stage ring for small launches,
                            // 8 skip every LayerNorm launch (timing only), 32 no split-K, 128 the one-lane tile choice also inside a two-lane call, 256 small launches keep
                            // 128-row tiles where the default takes 64x128 ones, 512 bf16-output GEMMs with K < 512 stay on 128x128 tiles, 1024 no half-width column tiles in the
@@ -50,7 +50,7 @@ struct GemmParams {
     const bf16* W;
     int lda;
     int M, N, K;
-    int m_offset;       // this launch covers rows [m_offset, m_offset + M) of the problem (launch_gemm's mixed-tile split); usually 0
+    int m_offset;       // this launch covers rows [m_offset, m_offset + M) of the problem (the parts of gemm_plan's mixed-tile split); usually 0
     const float* bias;  // [N] or nullptr
     int epi;
     // row mapping (rows_in == 0: identity).  m = b*rows_in + i  ->  out row b*rows_out + i,
@@ -74,24 +74,44 @@ struct GemmParams {
     int64_t qk_plane;
     int qkv_dim, heads, head_dim, n_tok;
     float q_scale;
-    // split-K of the latency-bound small launches (gemm.hip, deep-ring 128x128 kernel); filled in by launch_gemm
-    int splitk;              // K is cut into this many ranges, one workgroup each (1: off)
+    // split-K of the latency-bound small launches (gemm.hip, deep-ring kernels).  The workspace is the launching stream's, attached by whoever plans the
+    // launch (Engine::run_gemm: the engine's own; launch_gemm: the process-wide table) when a part of the plan splits K
+    int splitk;              // set by launch_gemm_part from the plan: K is cut into this many ranges, one workgroup each (1: off)
     float* sk2_slabs;        // [tiles * splitk][128 * 128] fp32 partial accumulators
     unsigned* sk2_count;     // [tiles] arrival counters (0 between launches)
-    int staged;  // set by launch_gemm: epilogue through LDS with full-line global accesses (gemm.hip)
-    int direct;  // set by launch_gemm: 16-byte stores straight from the accumulators, W tile staged with permuted rows (gemm_device.h epilogue_direct)
+    int staged;  // set by launch_gemm_part from the plan: epilogue through LDS with full-line global accesses (gemm.hip)
+    int direct;  // set by launch_gemm_part from the plan: 16-byte stores straight from the accumulators, W tile staged with permuted rows (gemm_device.h epilogue_direct)
     int overlapped;  // set by the engine: the launch runs beside another lane's kernels, so a partly filled last round of workgroups is not lost
-    int debug;  // set by launch_gemm from tune->gemm_debug (the kernels read bits 0 / 1: skip the epilogue's global stores / the epilogue)
+    int debug;  // set by launch_gemm_part from tune->gemm_debug (the kernels read bits 0 / 1: skip the epilogue's global stores / the epilogue)
     const Tuning* tune;  // execution options of the calling model (nullptr: defaults)
 };
 
 constexpr int kSplitKSlots = 512;  // >= CUs: a split launch has at most one part per CU
 int splitk_workspace_alloc(float** slabs, unsigned** counts, hipStream_t stream);  // counters zeroed on `stream`
-int gemm_splitk_parts(const GemmParams& p, int planes);  // K ranges the deep-ring 128x128 kernel would cut this launch into (1: no split-K)
+// Everything decided before a GEMM launch, by gemm_plan and nowhere else; launch_gemm_part turns part i into one kernel launch.
+enum GemmKernel : int {
+    GEMM_KERNEL_128 = 0,      // 128x128 tiles, 2-stage ring, two workgroups per CU
+    GEMM_KERNEL_DEEP128 = 1,  // 128x128 tiles, 4-stage ring: at most one tile per CU; may split K
+    GEMM_KERNEL_DEEP64 = 2,   // 64x128 tiles, 4-stage ring: at most half a 128-row tile per CU; may split K
+    GEMM_KERNEL_8PHASE = 3,   // 256x256 tiles, 8-phase main loop
+};
+struct GemmPlan {
+    int cfg;     // the tile configuration in the vocabulary of Tuning.gemm_tile: 1, 4, or 6 (two parts: 8-phase rounds, then the remaining rows)
+    int nparts;  // 1 or 2
+    struct Part {
+        int m_offset, M;  // rows [m_offset, m_offset + M) of the problem
+        int kernel;       // GemmKernel
+        int splitk;       // K ranges (1: no split-K; more only on the deep-ring kernels)
+    } part[2];
+    int staged, direct;  // epilogue form (GemmParams)
+    bool splits_k() const { return part[0].splitk > 1 || (nparts == 2 && part[1].splitk > 1); }
+};
+// Checks the arguments and fills `plan` for a device of `cus` compute units; forced_cfg > 0 replaces the options' and the rule's tile choice.  No HIP call.
+int gemm_plan(const GemmParams& p, int planes, int forced_cfg, int cus, GemmPlan* plan);
+// One kernel launch: part i of the plan made from `p`.  A part that splits K needs p.sk2_slabs / p.sk2_count.
+int launch_gemm_part(const GemmParams& p, int planes, const GemmPlan& plan, int i, hipStream_t stream);
+// Plan + launch for callers outside an engine (cwm_linear, the development entry points); split-K workspace from a process-wide per-(device, stream) table
 int launch_gemm(const GemmParams& p, int planes, hipStream_t stream);
-int gemm_choose_tile(const GemmParams& p, int planes);
-bool gemm_mixed_split(const GemmParams& p, GemmParams* big, GemmParams* rest);  // tile configuration 6
-int launch_gemm_tile(const GemmParams& p, int planes, int cfg, hipStream_t stream);  // 1: 128x128, 4: 256x256 8-phase, 6: mixed (Tuning.gemm_tile)
 int gemm_cu_count();  // compute units of the current device, rounded down to a multiple of the 8 XCDs (256 on MI355X)
 int gemm_prof_dump();  // builds with -DCWM_GEMM_PROF: per-workgroup timers of gemm8p_kernel -> /tmp/gemm_blocks.bin
 

@@ -19,6 +19,24 @@ extern "C" {
  * The table is process-wide; it reaches the launches of this thread's stand-alone calls and of models created on this thread AFTER the first call. */
 CWM_API int cwm_gemm_tile_override(int M, int N, int K, int epi, int overlapped, int cfg);
 
+/* What the library decides before a GEMM launch of M x N x K (K a multiple of 64, N of 16; epi as above; mode CWM_MODE_*; overlapped = inside a two-lane
+ * forward) under THIS THREAD's options (cwm_debug_set "gemm_tile", "gemm_debug" ..., cwm_gemm_tile_override): the tile configuration 1, 4 or 6 and, for each
+ * of its one or two kernel launches, the rows, the kernel and the number of K ranges.  forced_cfg > 0 stands for a "gemm_tile" of that value; cus = the
+ * compute units to plan for, 0: the current device's (256 without one).  Launches nothing and needs no device. */
+#define CWM_DEV_GEMM_KERNEL_128 0     /* 128x128 tiles, 2-stage ring */
+#define CWM_DEV_GEMM_KERNEL_DEEP128 1 /* 128x128 tiles, 4-stage ring (at most one tile per CU) */
+#define CWM_DEV_GEMM_KERNEL_DEEP64 2  /* 64x128 tiles, 4-stage ring */
+#define CWM_DEV_GEMM_KERNEL_8PHASE 3  /* 256x256 tiles, 8-phase main loop */
+typedef struct cwm_dev_gemm_plan_out {
+    int32_t cfg, nparts;
+    struct {
+        int32_t m_offset, M; /* rows [m_offset, m_offset + M) */
+        int32_t kernel;      /* CWM_DEV_GEMM_KERNEL_* */
+        int32_t splitk;      /* 1: K is not split */
+    } part[2];               /* part[1] is zero when nparts is 1 */
+} cwm_dev_gemm_plan_out;
+CWM_API int cwm_dev_gemm_plan(int M, int N, int K, int epi, int mode, int overlapped, int forced_cfg, int cus, cwm_dev_gemm_plan_out* out);
+
 /* ---- diagnostics: single-kernel micro-benchmarks on random operands (tools/microbench.py) ---------
  * epi: 0 = fp32 out + bias + in-place residual (proj/fc2 form), 1 = bias + GELU -> bf16 (fc1 form),
  *      3 = QKV head scatter (N must be 3*64*heads, M = batch*n_tok with n_tok = M / batch).
