@@ -404,6 +404,20 @@ class CwmDevGemmPlanOut(C.Structure):
 DEV_GEMM_KERNEL_128, DEV_GEMM_KERNEL_DEEP128, DEV_GEMM_KERNEL_DEEP64, DEV_GEMM_KERNEL_8PHASE = range(4)
 
 
+class CwmDevFlowFormsOut(C.Structure):
+    """include/cwm_hip_dev.h cwm_dev_flow_forms_out (development library only): the kernel form per entry point, DEV_FLOW_* below"""
+    _fields_ = [(n, C.c_int32) for n in ("features", "motion", "count", "finish", "zero", "pack")]
+
+
+DEV_FLOW_REFUSED = -1
+DEV_FLOW_FEATURES_SCALAR, DEV_FLOW_FEATURES_VEC4 = range(2)
+DEV_FLOW_MOTION_STRIDED, DEV_FLOW_MOTION_TILE, DEV_FLOW_MOTION_ROWS16, DEV_FLOW_MOTION_ROWS32, DEV_FLOW_MOTION_ROWS64 = range(5)
+DEV_FLOW_COUNT_PLANES, DEV_FLOW_COUNT_PLANES_VEC, DEV_FLOW_COUNT_PACKED, DEV_FLOW_COUNT_PACKED_VEC = range(4)
+DEV_FLOW_FINISH_V1, DEV_FLOW_FINISH_V4 = range(2)
+DEV_FLOW_ZERO_PLANES, DEV_FLOW_ZERO_PLANES_VEC, DEV_FLOW_ZERO_SCATTER = range(3)
+DEV_FLOW_PACK_TRANSPOSE = 0
+
+
 def new_dev_conj_args(cls):
     """a zeroed cwm_dev_conj_*_args of the given structure class with its struct_size set"""
     a = cls()
@@ -522,6 +536,7 @@ SIGNATURES = {
 DEV_SIGNATURES = {
     "cwm_gemm_tile_override": (C.c_int, [C.c_int] * 6),
     "cwm_dev_gemm_plan": (C.c_int, [C.c_int] * 8 + [C.POINTER(CwmDevGemmPlanOut)]),
+    "cwm_dev_flow_forms": (C.c_int, [C.POINTER(C.c_int64)] + [C.c_int] * 5 + [C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_int64), C.c_uint64, C.c_int, C.POINTER(CwmDevFlowFormsOut)]),
     "cwm_bench_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "cwm_bench_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "cwm_debug_set": (C.c_int, [C.c_char_p, C.c_int]),

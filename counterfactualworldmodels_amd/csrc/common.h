@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace cwm {
 
 typedef __bf16 bf16;
@@ -118,6 +120,14 @@ __device__ __forceinline__ float group8_sum(float v) {
     v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
     v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, true));  // row_half_mirror
     return v;
+}
+
+// A run-time value as a template argument: calls fn(std::integral_constant<int, N>{}) for the N of the list that equals n (launch sites: `K<q.value>`).
+// Returns false, having called nothing, when n is not in the list.  Call sites pass a bool or a `? :` over the listed values, so that cannot happen there; a site
+// that passes anything else must check the result.
+template <int... Ns, class F>
+static inline bool dispatch_int(int n, F&& fn) {
+    return ((n == Ns && (fn(std::integral_constant<int, Ns>{}), true)) || ...);
 }
 
 // XCD-aware bijective remap of a linear workgroup id (guide §5.5 T1): blocks b and b+8 share an

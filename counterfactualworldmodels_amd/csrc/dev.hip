@@ -10,6 +10,7 @@
 
 #include "../../include/cwm_hip_dev.h"
 #include "engine.h"
+#include "flow_view.h"
 
 using namespace cwm;
 
@@ -134,6 +135,36 @@ extern "C" int cwm_dev_gemm_plan(int M, int N, int K, int epi, int mode, int ove
         out->part[i].kernel = plan.part[i].kernel;
         out->part[i].splitk = plan.part[i].splitk;
     }
+    return CWM_OK;
+}
+
+// The forms flow_view.h picks for these flow samples, entry point by entry point: its functions, called as the entry points call them.
+extern "C" int cwm_dev_flow_forms(const int64_t* strides, int B, int C, int H, int W, int S, uint64_t flows_addr, uint64_t aux_addr, int normalize_per_sample,
+                                  const int64_t* mask_strides, uint64_t mask_addr, int patches_per_frame, cwm_dev_flow_forms_out* out) {
+    CWM_REQUIRE(out && mask_strides, "cwm_dev_flow_forms: null pointer");
+    static_assert(CWM_DEV_FLOW_REFUSED == FLOW_REFUSED && CWM_DEV_FLOW_FEATURES_VEC4 == FEATURES_VEC4 && CWM_DEV_FLOW_MOTION_TILE == MOTION_TILE &&
+                      CWM_DEV_FLOW_MOTION_ROWS16 == MOTION_ROWS16 && CWM_DEV_FLOW_MOTION_ROWS32 == MOTION_ROWS32 && CWM_DEV_FLOW_MOTION_ROWS64 == MOTION_ROWS64 &&
+                      CWM_DEV_FLOW_COUNT_PLANES_VEC == COUNT_PLANES_VEC && CWM_DEV_FLOW_COUNT_PACKED == COUNT_PACKED && CWM_DEV_FLOW_COUNT_PACKED_VEC == COUNT_PACKED_VEC &&
+                      CWM_DEV_FLOW_FINISH_V4 == FINISH_V4 && CWM_DEV_FLOW_ZERO_PLANES_VEC == ZERO_PLANES_VEC && CWM_DEV_FLOW_ZERO_SCATTER == ZERO_SCATTER &&
+                      CWM_DEV_FLOW_FEATURES_SCALAR == FEATURES_SCALAR && CWM_DEV_FLOW_MOTION_STRIDED == MOTION_STRIDED && CWM_DEV_FLOW_COUNT_PLANES == COUNT_PLANES &&
+                      CWM_DEV_FLOW_FINISH_V1 == FINISH_V1 && CWM_DEV_FLOW_ZERO_PLANES == ZERO_PLANES && CWM_DEV_FLOW_PACK_TRANSPOSE == PACK_TRANSPOSE,
+                  "cwm_hip_dev.h names the forms of flow_view.h FlowForm");
+    const float* flows = reinterpret_cast<const float*>((uintptr_t)flows_addr);
+    out->features = out->motion = out->count = out->finish = out->zero = out->pack = FLOW_REFUSED;
+    FlowView v;
+    if (flow_view("cwm_dev_flow_forms", false, flows, strides, B, C, H, W, S, &v) == 0) {
+        const FlowLayout l = flow_layout(v, (uintptr_t)aux_addr);
+        out->features = flow_features_form(v, l);
+        out->motion = flow_motion_form(v, l, normalize_per_sample != 0);
+    }
+    if (flow_view("cwm_dev_flow_forms", true, flows, strides, B, C, H, W, S, &v) == 0) {
+        const FlowLayout l = flow_layout(v, 0);
+        out->count = flow_count_form(v, l);
+        out->finish = flow_finish_form(S, mask_strides, (uintptr_t)mask_addr, patches_per_frame);
+        out->zero = flow_zero_form(v, l);
+        out->pack = flow_pack_form(l);
+    }
+    cwm_set_error("%s", "");  // (a refusal is reported through the -1 fields: the checks' texts do not outlive a call that succeeded)
     return CWM_OK;
 }
 

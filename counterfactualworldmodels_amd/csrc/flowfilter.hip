@@ -16,13 +16,12 @@
 // cwm_flow_filter_apply writes zeros over the rejected samples and reads no flow element; cwm_flow_filter_pack transposes the sample-outermost batch into the
 // packed [B,2,H,W,S] tensor the reference returns (`.contiguous()`), writing zeros for rejected samples without reading them.
 //
-// Layouts (element strides of [B,2,H,W,S], as cwm_flow_features): "planes" = every (b, s, c) plane is H W contiguous floats (the `_batch_to_samples` view of the
-// flow model's [(b s),1,2,H,W] output: 16-byte loads along the pixels); "packed" = sample axis innermost, (H,W,S) contiguous (`.contiguous()`, `torch.cat(.., -1)`:
-// 16-byte loads along the samples); anything else takes the strided form of the planes kernel.
+// Layouts and which form a launch takes: flow_view.h.  "planes" are read with 16-byte loads along the pixels, "packed" along the samples, anything else 4 bytes at a time.
 #include <cmath>
 
 #include "../../include/cwm_hip.h"
 #include "common.h"
+#include "flow_view.h"
 #include "kernels.h"
 
 namespace cwm {
@@ -52,8 +51,9 @@ __device__ __forceinline__ void block_add2(int cnt, int cor, int* __restrict__ a
     }
 }
 
-// one (b, s) per blockIdx.(z, y), kFiltPixPerBlock pixels per blockIdx.x.  VEC: sw == 1, sh == W, H W % 4 == 0, 16-byte aligned planes.
-template <bool VEC>
+// one (b, s) per blockIdx.(z, y), kFiltPixPerBlock pixels per blockIdx.x.  VEC: contiguous, 16-byte aligned planes of a multiple of 4 pixels.
+// (Not on a FlowView: from a struct hipcc vectorises the scalar loop eight wide instead of two, 107 registers instead of 28.)
+template <int VEC>
 __global__ __launch_bounds__(256) void flow_filter_count_kernel(const float* __restrict__ f, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int64_t ss, int H,
                                                                 int W, int S, float thr, int* __restrict__ area, int* __restrict__ corner) {
     const int s = blockIdx.y, b = blockIdx.z, HW = H * W;
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void flow_filter_count_kernel(const float* __r
     if (VEC) {
         for (int e = e0 + 4 * (int)threadIdx.x; e < e1; e += 1024) {  // e % 4 == 0 and HW % 4 == 0: e + 3 < e1
             const float4 a = *reinterpret_cast<const float4*>(u + e), c = *reinterpret_cast<const float4*>(v + e);
-            const float m[4] = {sqrtf(a.x * a.x + c.x * c.x), sqrtf(a.y * a.y + c.y * c.y), sqrtf(a.z * a.z + c.z * c.z), sqrtf(a.w * a.w + c.w * c.w)};
+            const float m[4] = {flow_mag2(a.x, c.x), flow_mag2(a.y, c.y), flow_mag2(a.z, c.z), flow_mag2(a.w, c.w)};
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (m[k] > thr) {
@@ -76,8 +76,7 @@ __global__ __launch_bounds__(256) void flow_filter_count_kernel(const float* __r
         for (int e = e0 + (int)threadIdx.x; e < e1; e += 256) {
             const int y = e / W, x = e - y * W;
             const int64_t off = (int64_t)y * sh + (int64_t)x * sw;
-            const float a = u[off], c = v[off];
-            if (sqrtf(a * a + c * c) > thr) {
+            if (flow_mag2(u[off], v[off]) > thr) {
                 ++cnt;
                 cor += corner_hits(e, W, HW);
             }
@@ -88,7 +87,7 @@ __global__ __launch_bounds__(256) void flow_filter_count_kernel(const float* __r
 
 // packed layout: a workgroup takes tile_pix consecutive pixels = tile_pix * S consecutive floats per channel; per-sample counts in LDS (integer atomics), then one
 // global atomic per (workgroup, sample with a non-zero count).  VEC: S % 4 == 0 (a 16-byte load = 4 samples of one pixel), aligned base and strides.
-template <bool VEC>
+template <int VEC>
 __global__ __launch_bounds__(256) void flow_filter_count_packed_kernel(const float* __restrict__ f, int64_t sb, int64_t sc, int HW, int W, int S, int tile_pix,
                                                                        float thr, int* __restrict__ area, int* __restrict__ corner) {
     extern __shared__ int cnt[];  // [S] area, [S] corners
@@ -101,7 +100,7 @@ __global__ __launch_bounds__(256) void flow_filter_count_packed_kernel(const flo
     if (VEC) {
         for (int e = 4 * (int)threadIdx.x; e < n; e += 1024) {  // n % 4 == 0
             const float4 a = *reinterpret_cast<const float4*>(u + e), c = *reinterpret_cast<const float4*>(v + e);
-            const float m[4] = {sqrtf(a.x * a.x + c.x * c.x), sqrtf(a.y * a.y + c.y * c.y), sqrtf(a.z * a.z + c.z * c.z), sqrtf(a.w * a.w + c.w * c.w)};
+            const float m[4] = {flow_mag2(a.x, c.x), flow_mag2(a.y, c.y), flow_mag2(a.z, c.z), flow_mag2(a.w, c.w)};
             if (m[0] > thr || m[1] > thr || m[2] > thr || m[3] > thr) {
                 const int p = e / S, s = e - p * S, ch = corner_hits(pix0 + p, W, HW);
 #pragma unroll
@@ -114,8 +113,7 @@ __global__ __launch_bounds__(256) void flow_filter_count_packed_kernel(const flo
         }
     } else {
         for (int e = threadIdx.x; e < n; e += 256) {
-            const float a = u[e], c = v[e];
-            if (sqrtf(a * a + c * c) > thr) {
+            if (flow_mag2(u[e], v[e]) > thr) {
                 const int p = e / S, s = e - p * S, ch = corner_hits(pix0 + p, W, HW);
                 atomicAdd(&cnt[s], 1);
                 if (ch) atomicAdd(&cnt[S + s], ch);
@@ -137,19 +135,15 @@ __device__ __forceinline__ void bilinear_axis(int dst, int in, int out, int& i0,
     l1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
 }
 
-__device__ __forceinline__ float mag_at(const float* __restrict__ fs, int64_t sc, int64_t off) {
-    const float a = fs[off], c = fs[off + sc];
-    return sqrtf(a * a + c * c);
-}
-
-__device__ float patch_tap(const float* __restrict__ fs, int64_t sc, int64_t sh, int64_t sw, int H, int W, int h, int w, int p) {
+__device__ float patch_tap(const FlowView& fv, const float* __restrict__ fs, int h, int w, int p) {
     const int dy = p / w, dx = p - dy * w;
     int y0, y1, x0, x1;
     float ly, lx;
-    bilinear_axis(dy, H, h, y0, y1, ly);
-    bilinear_axis(dx, W, w, x0, x1, lx);
-    const float m00 = mag_at(fs, sc, y0 * sh + x0 * sw), m01 = mag_at(fs, sc, y0 * sh + x1 * sw);
-    const float m10 = mag_at(fs, sc, y1 * sh + x0 * sw), m11 = mag_at(fs, sc, y1 * sh + x1 * sw);
+    bilinear_axis(dy, fv.H, h, y0, y1, ly);
+    bilinear_axis(dx, fv.W, w, x0, x1, lx);
+    auto mag_at = [&](int64_t off) { return flow_mag2(fs[off], fs[off + fv.sc]); };
+    const float m00 = mag_at(y0 * fv.sh + x0 * fv.sw), m01 = mag_at(y0 * fv.sh + x1 * fv.sw);
+    const float m10 = mag_at(y1 * fv.sh + x0 * fv.sw), m11 = mag_at(y1 * fv.sh + x1 * fv.sw);
     return (1.f - ly) * ((1.f - lx) * m00 + lx * m01) + ly * ((1.f - lx) * m10 + lx * m11);
 }
 
@@ -157,18 +151,17 @@ __device__ float patch_tap(const float* __restrict__ fs, int64_t sc, int64_t sh,
 // axis is contiguous and S % 4 == 0).  Row slot r (0 .. 63) covers patches [r chunk, (r + 1) chunk) in order; the 64 partials of a sample are then added in slot order:
 // the same additions whatever V is.
 template <int V>
-__global__ __launch_bounds__(1024) void flow_filter_finish_kernel(const float* __restrict__ f, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int64_t ss, int H, int W,
-                                                                  int S, const uint8_t* __restrict__ act, int64_t ab, int64_t ap, int64_t as, int h, int w,
+__global__ __launch_bounds__(1024) void flow_filter_finish_kernel(const FlowView fv, const uint8_t* __restrict__ act, int64_t ab, int64_t ap, int64_t as, int h, int w,
                                                                   int methods, float thr, float area_thr, float corner_thr, const int* __restrict__ area,
                                                                   const int* __restrict__ corner, float* __restrict__ patch_mag, uint8_t* __restrict__ reject) {
     __shared__ float part[kFinRows][64];
     __shared__ int npart[kFinRows][64];
     constexpr int LPR = 64 / V;      // lanes per row slot
     constexpr int RPS = 1024 / LPR;  // row slots per sweep
-    const int b = blockIdx.y, s0 = blockIdx.x * 64, hw = h * w, chunk = (hw + kFinRows - 1) / kFinRows;
+    const int b = blockIdx.y, s0 = blockIdx.x * 64, hw = h * w, chunk = (hw + kFinRows - 1) / kFinRows, S = fv.S;
     const int l = threadIdx.x % LPR, sl = V * l, s = s0 + sl;
     const uint8_t* ab2 = act + b * ab + (int64_t)hw * ap;  // frame 2
-    const float* fb = f + b * sb;
+    const float* fb = fv.f + b * fv.sb;
     for (int r = threadIdx.x / LPR; r < kFinRows; r += RPS) {
         float acc[V];
         int n[V];
@@ -191,7 +184,7 @@ __global__ __launch_bounds__(1024) void flow_filter_finish_kernel(const float* _
 #pragma unroll
                     for (int k = 0; k < V; ++k)
                         if (((m[j] >> (8 * k)) & 0xFFu) == 0u) {
-                            acc[k] += patch_tap(fb + (int64_t)(s + k) * ss, sc, sh, sw, H, W, h, w, p + j);
+                            acc[k] += patch_tap(fv, fb + (int64_t)(s + k) * fv.ss, h, w, p + j);
                             ++n[k];
                         }
             }
@@ -216,20 +209,19 @@ __global__ __launch_bounds__(1024) void flow_filter_finish_kernel(const float* _
     patch_mag[i] = pm;
     bool rej = false;  // NaN compares false everywhere, as in torch
     if (methods & CWM_FLOW_FILTER_PATCH_MAGNITUDE) rej |= pm < thr;
-    if (methods & CWM_FLOW_FILTER_FLOW_AREA) rej |= (float)area[i] / (float)(H * W) > area_thr;
+    if (methods & CWM_FLOW_FILTER_FLOW_AREA) rej |= (float)area[i] / (float)(fv.H * fv.W) > area_thr;
     if (methods & CWM_FLOW_FILTER_NUM_CORNERS) rej |= (float)corner[i] >= corner_thr;
     reject[i] = rej ? 1 : 0;
 }
 
 // zero the rejected samples, planes form: a rejected (b, s, c) plane is one contiguous block; workgroups of kept samples leave at once.  VEC as above.
-template <bool VEC>
-__global__ __launch_bounds__(256) void flow_filter_zero_planes_kernel(float* __restrict__ f, int64_t sb, int64_t sc, int64_t ss, int HW, int S,
-                                                                      const uint8_t* __restrict__ reject) {
-    const int s = blockIdx.y, b = blockIdx.z;
-    if (!reject[(size_t)b * S + s]) return;
-    float* u = f + b * sb + s * ss;
+template <int VEC>
+__global__ __launch_bounds__(256) void flow_filter_zero_planes_kernel(const FlowView fv, const uint8_t* __restrict__ reject) {
+    const int s = blockIdx.y, b = blockIdx.z, HW = fv.H * fv.W;
+    if (!reject[(size_t)b * fv.S + s]) return;
+    float* u = const_cast<float*>(fv.f) + b * fv.sb + s * fv.ss;  // (cwm_flow_filter_apply's flows are not const)
     const int e0 = blockIdx.x * kFiltPixPerBlock, e1 = min(e0 + kFiltPixPerBlock, HW);
-    for (int c = 0; c < 2; ++c, u += sc) {
+    for (int c = 0; c < 2; ++c, u += fv.sc) {
         if (VEC)
             for (int e = e0 + 4 * (int)threadIdx.x; e < e1; e += 1024) *reinterpret_cast<float4*>(u + e) = make_float4(0.f, 0.f, 0.f, 0.f);
         else
@@ -239,11 +231,10 @@ __global__ __launch_bounds__(256) void flow_filter_zero_planes_kernel(float* __r
 
 // any other layout (the packed one included): a workgroup lists the rejected samples of its b, then writes one zero per (channel, pixel of its tile, rejected
 // sample), the rejected samples innermost (neighbours in the packed layout).  Kept samples are neither read nor written.
-__global__ __launch_bounds__(256) void flow_filter_zero_scatter_kernel(float* __restrict__ f, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int64_t ss, int H, int W,
-                                                                       int S, int tile_pix, const uint8_t* __restrict__ reject) {
+__global__ __launch_bounds__(256) void flow_filter_zero_scatter_kernel(const FlowView fv, int tile_pix, const uint8_t* __restrict__ reject) {
     extern __shared__ int rej_list[];  // [S]
     __shared__ int n_rej;
-    const int b = blockIdx.y, pix0 = blockIdx.x * tile_pix, HW = H * W;
+    const int b = blockIdx.y, pix0 = blockIdx.x * tile_pix, W = fv.W, HW = fv.H * W, S = fv.S;
     if (threadIdx.x == 0) {  // (in sample order: the writes of neighbouring lanes then go to increasing addresses)
         int n = 0;
         for (int s = 0; s < S; ++s)
@@ -253,13 +244,13 @@ __global__ __launch_bounds__(256) void flow_filter_zero_scatter_kernel(float* __
     __syncthreads();
     const int nr = n_rej, npix = min(tile_pix, HW - pix0);
     if (nr == 0) return;
-    float* fb = f + b * sb;
+    float* fb = const_cast<float*>(fv.f) + b * fv.sb;
     const int64_t total = (int64_t)npix * nr;
     for (int64_t i = threadIdx.x; i < total; i += blockDim.x) {
         const int pl = (int)(i / nr), e = pix0 + pl, y = e / W, x = e - y * W;
-        const int64_t off = (int64_t)y * sh + (int64_t)x * sw + (int64_t)rej_list[(int)(i - (int64_t)pl * nr)] * ss;
+        const int64_t off = (int64_t)y * fv.sh + (int64_t)x * fv.sw + (int64_t)rej_list[(int)(i - (int64_t)pl * nr)] * fv.ss;
         fb[off] = 0.f;
-        fb[off + sc] = 0.f;
+        fb[off + fv.sc] = 0.f;
     }
 }
 
@@ -282,17 +273,6 @@ __global__ __launch_bounds__(256) void flow_filter_pack_kernel(const float* __re
     }
 }
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static int check_flows(const char* who, const void* flows, const int64_t* strides, int B, int C, int H, int W, int S) {
-    CWM_REQUIRE(flows && strides, "%s: null pointer", who);
-    CWM_REQUIRE(B >= 1 && S >= 1 && H >= 1, "%s: B=%d, H=%d, S=%d must be >= 1", who, B, H, S);
-    CWM_REQUIRE(C == 2, "%s: flow samples have C=2 channels, got C=%d", who, C);
-    CWM_REQUIRE(H == W, "%s: H=%d != W=%d (the patch grid is inferred from a square image, sampling.py:186)", who, H, W);
-    CWM_REQUIRE((int64_t)H * W <= (1 << 30) && S <= 65535 && B <= 65535, "%s: H W=%lld, S=%d or B=%d beyond the launch grid", who, (long long)H * W, S, B);
-    return 0;
-}
-
 }  // namespace cwm
 
 using namespace cwm;
@@ -301,7 +281,8 @@ extern "C" int cwm_flow_filter_stats(const float* flows_dev, const int64_t* stri
                                      const int64_t* active_strides, int Np, int methods, float flow_magnitude_threshold, float flow_area_threshold,
                                      float num_corners_threshold, float* patch_mag_dev, int32_t* area_count_dev, int32_t* corner_count_dev, uint8_t* reject_dev,
                                      void* stream) {
-    if (int rc = check_flows("cwm_flow_filter_stats", flows_dev, strides, B, C, H, W, S)) return rc;
+    FlowView v;
+    if (int rc = flow_view("cwm_flow_filter_stats", true, flows_dev, strides, B, C, H, W, S, &v)) return rc;
     CWM_REQUIRE(active_dev && active_strides && patch_mag_dev && area_count_dev && corner_count_dev && reject_dev, "cwm_flow_filter_stats: null pointer");
     CWM_REQUIRE(Np >= 2 && Np % 2 == 0, "cwm_flow_filter_stats: Np=%d must be the (even) patch count of two frames", Np);
     const int h = (int)std::sqrt((double)(Np / 2));  // sampling.py:188: h = w = int((Np / 2) ** 0.5)
@@ -310,75 +291,59 @@ extern "C" int cwm_flow_filter_stats(const float* flows_dev, const int64_t* stri
                 "cwm_flow_filter_stats: unknown bits in methods=0x%x", methods);
     hipStream_t st = (hipStream_t)stream;
     const int HW = H * W;
-    const int64_t sb = strides[0], sc = strides[1], sh = strides[2], sw = strides[3], ss = strides[4];
     CWM_HIP_CHECK(hipMemsetAsync(area_count_dev, 0, (size_t)B * S * sizeof(int32_t), st));
     CWM_HIP_CHECK(hipMemsetAsync(corner_count_dev, 0, (size_t)B * S * sizeof(int32_t), st));
-    const bool base4 = aligned16(flows_dev) && sb % 4 == 0 && sc % 4 == 0;
-    const bool packed = ss == 1 && sw == S && sh == (int64_t)W * S && S <= 8192;
-    if (packed) {
-        const int tile = S <= 32 ? 256 : S <= 64 ? 128 : 64;
+    const FlowForm count = flow_count_form(v, flow_layout(v, 0));
+    if (count == COUNT_PACKED || count == COUNT_PACKED_VEC) {
+        const int tile = mag_tile_pix(S);
         const dim3 grid((unsigned)((HW + tile - 1) / tile), (unsigned)B);
-        const size_t smem = (size_t)2 * S * sizeof(int);
-        if (base4 && S % 4 == 0)
-            hipLaunchKernelGGL(flow_filter_count_packed_kernel<true>, grid, dim3(256), smem, st, flows_dev, sb, sc, HW, W, S, tile, flow_magnitude_threshold,
-                               area_count_dev, corner_count_dev);
-        else
-            hipLaunchKernelGGL(flow_filter_count_packed_kernel<false>, grid, dim3(256), smem, st, flows_dev, sb, sc, HW, W, S, tile, flow_magnitude_threshold,
-                               area_count_dev, corner_count_dev);
+        dispatch_int<0, 1>(count == COUNT_PACKED_VEC, [&](auto vec) {
+            hipLaunchKernelGGL(flow_filter_count_packed_kernel<vec.value>, grid, dim3(256), (size_t)2 * S * sizeof(int), st, v.f, v.sb, v.sc, HW, W, S, tile,
+                               flow_magnitude_threshold, area_count_dev, corner_count_dev);
+        });
     } else {
         const dim3 grid((unsigned)((HW + kFiltPixPerBlock - 1) / kFiltPixPerBlock), (unsigned)S, (unsigned)B);
-        if (sw == 1 && sh == W && HW % 4 == 0 && base4 && ss % 4 == 0)
-            hipLaunchKernelGGL(flow_filter_count_kernel<true>, grid, dim3(256), 0, st, flows_dev, sb, sc, sh, sw, ss, H, W, S, flow_magnitude_threshold, area_count_dev,
-                               corner_count_dev);
-        else
-            hipLaunchKernelGGL(flow_filter_count_kernel<false>, grid, dim3(256), 0, st, flows_dev, sb, sc, sh, sw, ss, H, W, S, flow_magnitude_threshold, area_count_dev,
-                               corner_count_dev);
+        dispatch_int<0, 1>(count == COUNT_PLANES_VEC, [&](auto vec) {
+            hipLaunchKernelGGL(flow_filter_count_kernel<vec.value>, grid, dim3(256), 0, st, v.f, v.sb, v.sc, v.sh, v.sw, v.ss, H, W, S, flow_magnitude_threshold,
+                               area_count_dev, corner_count_dev);
+        });
     }
     CWM_HIP_CHECK(hipGetLastError());
-    const int64_t ab = active_strides[0], ap = active_strides[1], as = active_strides[2];
-    const dim3 fgrid((unsigned)((S + 63) / 64), (unsigned)B);
-    const bool mask4 = as == 1 && S % 4 == 0 && ab % 4 == 0 && ap % 4 == 0 && (((uintptr_t)active_dev + (uintptr_t)((int64_t)h * h * ap)) & 3) == 0;
-    if (mask4)
-        hipLaunchKernelGGL(flow_filter_finish_kernel<4>, fgrid, dim3(1024), 0, st, flows_dev, sb, sc, sh, sw, ss, H, W, S, active_dev, ab, ap, as, h, h, methods,
-                           flow_magnitude_threshold, flow_area_threshold, num_corners_threshold, area_count_dev, corner_count_dev, patch_mag_dev, reject_dev);
-    else
-        hipLaunchKernelGGL(flow_filter_finish_kernel<1>, fgrid, dim3(1024), 0, st, flows_dev, sb, sc, sh, sw, ss, H, W, S, active_dev, ab, ap, as, h, h, methods,
-                           flow_magnitude_threshold, flow_area_threshold, num_corners_threshold, area_count_dev, corner_count_dev, patch_mag_dev, reject_dev);
+    dispatch_int<1, 4>(flow_finish_form(S, active_strides, (uintptr_t)active_dev, h * h) == FINISH_V4 ? 4 : 1, [&](auto V) {
+        hipLaunchKernelGGL(flow_filter_finish_kernel<V.value>, dim3((unsigned)((S + 63) / 64), (unsigned)B), dim3(1024), 0, st, v, active_dev, active_strides[0], active_strides[1],
+                           active_strides[2], h, h, methods, flow_magnitude_threshold, flow_area_threshold, num_corners_threshold, area_count_dev, corner_count_dev, patch_mag_dev,
+                           reject_dev);
+    });
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 extern "C" int cwm_flow_filter_apply(float* flows_dev, const int64_t* strides, int B, int C, int H, int W, int S, const uint8_t* reject_dev, void* stream) {
-    if (int rc = check_flows("cwm_flow_filter_apply", flows_dev, strides, B, C, H, W, S)) return rc;
+    FlowView v;
+    if (int rc = flow_view("cwm_flow_filter_apply", true, flows_dev, strides, B, C, H, W, S, &v)) return rc;
     CWM_REQUIRE(reject_dev, "cwm_flow_filter_apply: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    const int HW = H * W;
-    const int64_t sb = strides[0], sc = strides[1], sh = strides[2], sw = strides[3], ss = strides[4];
-    if (sw == 1 && sh == W) {
-        const dim3 grid((unsigned)((HW + kFiltPixPerBlock - 1) / kFiltPixPerBlock), (unsigned)S, (unsigned)B);
-        if (HW % 4 == 0 && aligned16(flows_dev) && sb % 4 == 0 && sc % 4 == 0 && ss % 4 == 0)
-            hipLaunchKernelGGL(flow_filter_zero_planes_kernel<true>, grid, dim3(256), 0, st, flows_dev, sb, sc, ss, HW, S, reject_dev);
-        else
-            hipLaunchKernelGGL(flow_filter_zero_planes_kernel<false>, grid, dim3(256), 0, st, flows_dev, sb, sc, ss, HW, S, reject_dev);
-    } else {
-        CWM_REQUIRE(S <= 8192, "cwm_flow_filter_apply: S=%d > 8192 in a layout whose (H, W) planes are not contiguous", S);
-        const int tile = 256;
-        hipLaunchKernelGGL(flow_filter_zero_scatter_kernel, dim3((unsigned)((HW + tile - 1) / tile), (unsigned)B), dim3(256), (size_t)S * sizeof(int), st, flows_dev, sb,
-                           sc, sh, sw, ss, H, W, S, tile, reject_dev);
-    }
+    const int HW = H * W, tile = 256;
+    const FlowForm zero = flow_zero_form(v, flow_layout(v, 0));
+    CWM_REQUIRE(zero != FLOW_REFUSED, "cwm_flow_filter_apply: S=%d > 8192 in a layout whose (H, W) planes are not contiguous", S);
+    const dim3 grid((unsigned)((HW + kFiltPixPerBlock - 1) / kFiltPixPerBlock), (unsigned)S, (unsigned)B);  // (planes)
+    if (zero == ZERO_SCATTER)
+        hipLaunchKernelGGL(flow_filter_zero_scatter_kernel, dim3((unsigned)((HW + tile - 1) / tile), (unsigned)B), dim3(256), (size_t)S * sizeof(int), st, v, tile, reject_dev);
+    else
+        dispatch_int<0, 1>(zero == ZERO_PLANES_VEC, [&](auto vec) { hipLaunchKernelGGL(flow_filter_zero_planes_kernel<vec.value>, grid, dim3(256), 0, st, v, reject_dev); });
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 extern "C" int cwm_flow_filter_pack(const float* flows_dev, const int64_t* strides, int B, int C, int H, int W, int S, const uint8_t* reject_dev, float* out_dev,
                                     void* stream) {
-    if (int rc = check_flows("cwm_flow_filter_pack", flows_dev, strides, B, C, H, W, S)) return rc;
+    FlowView v;
+    if (int rc = flow_view("cwm_flow_filter_pack", true, flows_dev, strides, B, C, H, W, S, &v)) return rc;
     CWM_REQUIRE(reject_dev && out_dev, "cwm_flow_filter_pack: null pointer");
-    CWM_REQUIRE(strides[3] == 1 && strides[2] == W && strides[1] == (int64_t)H * W,
+    CWM_REQUIRE(flow_pack_form(flow_layout(v, 0)) != FLOW_REFUSED,
                 "cwm_flow_filter_pack: every sample must be one contiguous [2,H,W] block (the sample-outermost view of the flow model's output)");
-    const int N = 2 * H * W;
-    hipLaunchKernelGGL(flow_filter_pack_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)((S + 63) / 64), (unsigned)B), dim3(256), 0, (hipStream_t)stream, flows_dev,
-                       strides[0], strides[4], N, S, reject_dev, out_dev);
+    hipLaunchKernelGGL(flow_filter_pack_kernel, dim3((unsigned)((2 * H * W + 63) / 64), (unsigned)((S + 63) / 64), (unsigned)B), dim3(256), 0, (hipStream_t)stream, v.f, v.sb,
+                       v.ss, 2 * H * W, S, reject_dev, out_dev);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }

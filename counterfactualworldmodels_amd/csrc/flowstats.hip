@@ -14,57 +14,37 @@
 // call, so that ranks which all-gather the small feature matrix each produce a row slab (dist.py).
 #include "../../include/cwm_hip.h"
 #include "common.h"
+#include "flow_view.h"
 #include "kernels.h"
 
 namespace cwm {
 
 // ---- features: X[b][p][s] = sqrt(mean_c(avgpool_ds(flow[b][c])^2)) ----------------------------------------------------
-__global__ void flow_features_kernel(const float* __restrict__ f, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int64_t ss, int B, int C, int H,
-                                     int W, int S, int ds, float* __restrict__ x) {
-    const int Wd = W / ds, P = (H / ds) * Wd;
+// V = 4: the sample axis is innermost (ss == 1) and S a multiple of 4 -- four samples per thread, 16-byte loads (a quarter of the load instructions)
+template <int V>
+__global__ void flow_features_kernel(const FlowView v, int ds, float* __restrict__ x) {
+    typedef __attribute__((ext_vector_type(V))) float vec;
+    const int B = v.B, C = v.C, S = v.S, Wd = v.W / ds, P = (v.H / ds) * Wd, SV = S / V;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)B * P * S) return;
-    const int s = (int)(i % S);
-    const int64_t bp = i / S;
+    if (i >= (int64_t)B * P * SV) return;
+    const int s = (int)(i % SV) * V;
+    const int64_t bp = i / SV;
     const int pidx = (int)(bp % P), b = (int)(bp / P);
     const int py = pidx / Wd, px = pidx - py * Wd;
     const float inv_area = 1.0f / (float)(ds * ds);
-    float acc = 0.f;
+    vec acc = 0.f;
     for (int c = 0; c < C; ++c) {
-        const float* fc = f + b * sb + c * sc + s * ss;
-        float pool = 0.f;
+        const float* fc = v.f + b * v.sb + c * v.sc + (V == 1 ? s * v.ss : s);
+        vec pool = 0.f;
         for (int dy = 0; dy < ds; ++dy)
-            for (int dx = 0; dx < ds; ++dx) pool += fc[(int64_t)(py * ds + dy) * sh + (int64_t)(px * ds + dx) * sw];
-        pool *= inv_area;
-        acc += pool * pool;
-    }
-    x[i] = sqrtf(acc / (float)C);
-}
-
-// the same with the sample axis innermost (ss == 1) and S a multiple of 4: four samples per thread, 16-byte loads (a quarter of the load instructions)
-__global__ void flow_features4_kernel(const float* __restrict__ f, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int B, int C, int H, int W, int S, int ds,
-                                      float* __restrict__ x) {
-    const int Wd = W / ds, P = (H / ds) * Wd, S4 = S / 4;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)B * P * S4) return;
-    const int s = (int)(i % S4) * 4;
-    const int64_t bp = i / S4;
-    const int pidx = (int)(bp % P), b = (int)(bp / P);
-    const int py = pidx / Wd, px = pidx - py * Wd;
-    const float inv_area = 1.0f / (float)(ds * ds);
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int c = 0; c < C; ++c) {
-        const float* fc = f + b * sb + c * sc + s;
-        f32x4 pool = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int dy = 0; dy < ds; ++dy)
-            for (int dx = 0; dx < ds; ++dx) pool += *reinterpret_cast<const f32x4*>(fc + (int64_t)(py * ds + dy) * sh + (int64_t)(px * ds + dx) * sw);
+            for (int dx = 0; dx < ds; ++dx) pool += *reinterpret_cast<const vec*>(fc + (int64_t)(py * ds + dy) * v.sh + (int64_t)(px * ds + dx) * v.sw);
         pool = pool * inv_area;
         acc += pool * pool;
     }
-    f32x4 o;
+    vec o;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) o[r] = sqrtf(acc[r] / (float)C);
-    *reinterpret_cast<f32x4*>(x + ((size_t)b * P + pidx) * S + s) = o;
+    for (int r = 0; r < V; ++r) o[r] = sqrtf(acc[r] / (float)C);
+    *reinterpret_cast<vec*>(x + ((size_t)b * P + pidx) * S + s) = o;
 }
 
 // ---- centre the rows; inverse standard deviations for the correlation form ----------------------------------------------
@@ -447,15 +427,6 @@ __global__ __launch_bounds__(256) void flow_apply_kernel(float* __restrict__ x, 
 }
 
 // ---- motion maps ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float flow_mag(const float* f, int64_t sc, int C) {
-    float a = 0.f;
-    for (int c = 0; c < C; ++c) {
-        const float v = f[c * sc];
-        a += v * v;
-    }
-    return sqrtf(a);
-}
-
 __device__ __forceinline__ void block_minmax(float& mn, float& mx, float* red) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -477,33 +448,32 @@ __device__ __forceinline__ void block_minmax(float& mn, float& mx, float* red) {
 }
 
 // per (b, s): min and max over (H, W) of the flow magnitude -> mm[b][s] = {min, max}
-__global__ void flow_mag_minmax_kernel(const float* __restrict__ f, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int64_t ss, int C, int H, int W,
-                                       int S, float2* __restrict__ mm) {
+__global__ void flow_mag_minmax_kernel(const FlowView v, float2* __restrict__ mm) {
     __shared__ float red[32];
-    const int s = blockIdx.x, b = blockIdx.y;
-    const float* fb = f + b * sb + s * ss;
+    const int s = blockIdx.x, b = blockIdx.y, W = v.W;
+    const float* fb = v.f + b * v.sb + s * v.ss;
     float mn = INFINITY, mx = -INFINITY;
-    for (int e = threadIdx.x; e < H * W; e += blockDim.x) {
+    for (int e = threadIdx.x; e < v.H * W; e += blockDim.x) {
         const int y = e / W, x = e - y * W;
-        const float m = flow_mag(fb + (int64_t)y * sh + (int64_t)x * sw, sc, C);
+        const float m = sqrtf(flow_mag_sq<float>(fb + (int64_t)y * v.sh + (int64_t)x * v.sw, v.sc, v.C));
         mn = fminf(mn, m);
         mx = fmaxf(mx, m);
     }
     block_minmax(mn, mx, red);
-    if (threadIdx.x == 0) mm[(size_t)b * S + s] = make_float2(mn, mx);
+    if (threadIdx.x == 0) mm[(size_t)b * v.S + s] = make_float2(mn, mx);
 }
 
 // sum over the S samples of the (optionally per-sample range-normalised) magnitude -> sum[b][y][x]
-__global__ void flow_motion_sum_kernel(const float* __restrict__ f, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int64_t ss, int B, int C, int H,
-                                       int W, int S, const float2* __restrict__ mm, float eps, float* __restrict__ sum) {
+__global__ void flow_motion_sum_kernel(const FlowView v, const float2* __restrict__ mm, float eps, float* __restrict__ sum) {
+    const int H = v.H, W = v.W, S = v.S;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)B * H * W) return;
+    if (i >= (int64_t)v.B * H * W) return;
     const int b = (int)(i / (H * W)), e = (int)(i - (int64_t)b * H * W);
     const int y = e / W, x = e - y * W;
-    const float* fp = f + b * sb + (int64_t)y * sh + (int64_t)x * sw;
+    const float* fp = v.f + b * v.sb + (int64_t)y * v.sh + (int64_t)x * v.sw;
     float acc = 0.f;
     for (int s = 0; s < S; ++s) {
-        float m = flow_mag(fp + s * ss, sc, C);
+        float m = sqrtf(flow_mag_sq<float>(fp + s * v.ss, v.sc, v.C));
         if (mm) {
             const float2 r = mm[(size_t)b * S + s];
             m = (m - r.x) / fmaxf(r.y - r.x, eps);
@@ -527,22 +497,12 @@ __global__ void flow_motion_sum_kernel(const float* __restrict__ f, int64_t sb, 
 // workgroup g uses copy g mod kRangeReplicas, and the consumers fold the copies (min / max are exact in any order).
 constexpr int kRangeReplicas = 8;
 
-// pixels per workgroup: 256 for S <= 32, 128 for S <= 64, else 64 (mag_tile_pix): the tile stays <= 34 KB, and at S = 24 a quarter as many workgroups hit the S range
-// atomics (784 workgroups x 24 samples on 48 addresses were the whole 24-us launch)
-static inline int mag_tile_pix(int S) { return S <= 32 ? 256 : S <= 64 ? 128 : 64; }
-
 __device__ __forceinline__ void mag_tile_to_lds(const float* __restrict__ f, int64_t sb, int64_t sc, int b, int C, int HW, int S, int pix0, int tile_pix, float* mag) {
-    const int npix = min(tile_pix, HW - pix0);
-    const int n = npix * S;
+    const int n = min(tile_pix, HW - pix0) * S;
     const float* fb = f + b * sb + (int64_t)pix0 * S;
     for (int e = threadIdx.x; e < n; e += blockDim.x) {
-        float a = 0.f;
-        for (int c = 0; c < C; ++c) {
-            const float v = fb[c * sc + e];
-            a += v * v;
-        }
         const int pl = e / S;
-        mag[pl * (S + 1) + (e - pl * S)] = sqrtf(a);
+        mag[pl * (S + 1) + (e - pl * S)] = sqrtf(flow_mag_sq<float>(fb, sc, C, e));
     }
 }
 
@@ -628,11 +588,7 @@ __global__ __launch_bounds__(256) void flow_mag_minmax_rows_kernel(const float* 
         for (int i = 0; i < kRowPixPerWave; i += PPL) {
             const int pix = pix0 + i + sub;
             if (pix < HW) {
-                f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-                for (int c = 0; c < C; ++c) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(fb + c * sc + (int64_t)pix * S + ch * 256 + s4);
-                    a += v * v;
-                }
+                const f32x4 a = flow_mag_sq<f32x4>(fb, sc, C, (int64_t)pix * S + ch * 256 + s4);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float m = sqrtf(a[r]);
@@ -700,11 +656,7 @@ __global__ __launch_bounds__(256) void flow_motion_sum_rows_kernel(const float* 
         }
     };
     auto piece = [&](int pix, int ch, const f32x4& lo, const f32x4& range) {
-        f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int c = 0; c < C; ++c) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(fb + c * sc + (int64_t)pix * S + ch * 256 + s4);
-            a += v * v;
-        }
+        const f32x4 a = flow_mag_sq<f32x4>(fb, sc, C, (int64_t)pix * S + ch * 256 + s4);
         float part = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -795,20 +747,15 @@ using namespace cwm;
 
 extern "C" int cwm_flow_features(const float* flows_dev, const int64_t* strides, int B, int C, int H, int W, int S, int downsample, float* x_dev,
                                  void* stream) {
-    CWM_REQUIRE(flows_dev && strides && x_dev && B > 0 && C > 0 && H > 0 && W > 0 && S > 0, "cwm_flow_features: bad argument");
+    FlowView v;
+    if (int rc = flow_view("cwm_flow_features", false, flows_dev, strides, B, C, H, W, S, &v)) return rc;
+    CWM_REQUIRE(x_dev, "cwm_flow_features: null pointer");
     CWM_REQUIRE(downsample >= 1 && H % downsample == 0 && W % downsample == 0, "cwm_flow_features: downsample=%d must divide H=%d and W=%d",
                 downsample, H, W);
-    if (strides[4] == 1 && S % 4 == 0 && ((uintptr_t)flows_dev & 15) == 0 && ((uintptr_t)x_dev & 15) == 0 && strides[0] % 4 == 0 && strides[1] % 4 == 0 && strides[2] % 4 == 0 &&
-        strides[3] % 4 == 0) {
-        const int64_t total4 = (int64_t)B * (H / downsample) * (W / downsample) * (S / 4);
-        hipLaunchKernelGGL(flow_features4_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, flows_dev, strides[0], strides[1], strides[2],
-                           strides[3], B, C, H, W, S, downsample, x_dev);
-        CWM_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    const int64_t total = (int64_t)B * (H / downsample) * (W / downsample) * S;
-    hipLaunchKernelGGL(flow_features_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, flows_dev, strides[0],
-                       strides[1], strides[2], strides[3], strides[4], B, C, H, W, S, downsample, x_dev);
+    dispatch_int<1, 4>(flow_features_form(v, flow_layout(v, (uintptr_t)x_dev)) == FEATURES_VEC4 ? 4 : 1, [&](auto V) {
+        const int64_t total = (int64_t)B * (H / downsample) * (W / downsample) * (S / V.value);
+        hipLaunchKernelGGL(flow_features_kernel<V.value>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, v, downsample, x_dev);
+    });
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -897,62 +844,44 @@ extern "C" size_t cwm_flow_motion_work_bytes(int B, int S) {
 
 extern "C" int cwm_flow_motion_sum(const float* flows_dev, const int64_t* strides, int B, int C, int H, int W, int S, int normalize_per_sample,
                                    float eps, float* minmax_work_dev, float* sum_dev, void* stream) {
-    CWM_REQUIRE(flows_dev && strides && sum_dev && B > 0 && C > 0 && H > 0 && W > 0 && S > 0, "cwm_flow_motion_sum: bad argument");
-    CWM_REQUIRE(!normalize_per_sample || minmax_work_dev, "cwm_flow_motion_sum: per-sample normalisation needs the work buffer (cwm_flow_motion_work_bytes)");
+    FlowView v;
+    if (int rc = flow_view("cwm_flow_motion_sum", false, flows_dev, strides, B, C, H, W, S, &v)) return rc;
+    CWM_REQUIRE(sum_dev, "cwm_flow_motion_sum: null pointer");
+    const FlowForm form = flow_motion_form(v, flow_layout(v, (uintptr_t)minmax_work_dev), normalize_per_sample != 0);
+    CWM_REQUIRE(form != FLOW_REFUSED, "cwm_flow_motion_sum: per-sample normalisation needs the work buffer (cwm_flow_motion_work_bytes)");
     hipStream_t s = (hipStream_t)stream;
-    // the reference's layout (sample axis innermost, (H, W, S) packed): the coalesced kernels; any other strides: the strided ones
-    const int tile_mm = mag_tile_pix(S), tile_sum = 64;  // (the range pass wants few workgroups -- fewer atomics --, the sum pass many)
-    const size_t smem_mm = (size_t)tile_mm * (S + 1) * sizeof(float);
-    const size_t smem_sum = ((size_t)tile_sum * (S + 1) + 2 * (size_t)S) * sizeof(float);
-    const bool packed = strides[4] == 1 && strides[3] == S && strides[2] == (int64_t)W * S;
-    const int q = S == 64 ? 16 : S == 128 ? 32 : (S % 256 == 0 ? 64 : 0);  // lanes per pixel of the register form (0: the LDS-tile form)
-    const bool rows_form = packed && q && strides[0] % 4 == 0 && strides[1] % 4 == 0 && ((uintptr_t)flows_dev & 15) == 0 &&
-                           (!normalize_per_sample || ((uintptr_t)minmax_work_dev & 15) == 0);
-    const bool tile_form = !rows_form && packed && smem_mm <= 150 * 1024 && smem_sum <= 150 * 1024;
-    if (rows_form || tile_form) {
-        const int HW = H * W;
-        // work buffer (cwm_flow_motion_work_bytes): kRangeReplicas x [B][S] min bits, then as many max bits
-        unsigned *mn = nullptr, *mx = nullptr;
-        if (normalize_per_sample) {
-            const size_t n = (size_t)kRangeReplicas * B * S;
-            mn = reinterpret_cast<unsigned*>(minmax_work_dev);
-            mx = mn + n;
-            CWM_HIP_CHECK(hipMemsetAsync(mn, 0xFF, n * sizeof(unsigned), s));
-            CWM_HIP_CHECK(hipMemsetAsync(mx, 0x00, n * sizeof(unsigned), s));
-        }
-        if (rows_form) {
-            const dim3 grid((unsigned)((HW + 4 * kRowPixPerWave - 1) / (4 * kRowPixPerWave)), (unsigned)B);
-            if (normalize_per_sample) {
-                if (q == 16) hipLaunchKernelGGL(flow_mag_minmax_rows_kernel<16>, grid, dim3(256), 0, s, flows_dev, strides[0], strides[1], C, HW, S, mn, mx);
-                else if (q == 32) hipLaunchKernelGGL(flow_mag_minmax_rows_kernel<32>, grid, dim3(256), 0, s, flows_dev, strides[0], strides[1], C, HW, S, mn, mx);
-                else hipLaunchKernelGGL(flow_mag_minmax_rows_kernel<64>, grid, dim3(256), 0, s, flows_dev, strides[0], strides[1], C, HW, S, mn, mx);
-            }
-            if (q == 16) hipLaunchKernelGGL(flow_motion_sum_rows_kernel<16>, grid, dim3(256), 0, s, flows_dev, strides[0], strides[1], C, HW, S, mn, mx, eps, sum_dev);
-            else if (q == 32) hipLaunchKernelGGL(flow_motion_sum_rows_kernel<32>, grid, dim3(256), 0, s, flows_dev, strides[0], strides[1], C, HW, S, mn, mx, eps, sum_dev);
-            else hipLaunchKernelGGL(flow_motion_sum_rows_kernel<64>, grid, dim3(256), 0, s, flows_dev, strides[0], strides[1], C, HW, S, mn, mx, eps, sum_dev);
-        } else {
-            if (smem_mm > 48 * 1024)
-                if (int rc = cwm_set_max_lds((const void*)flow_mag_minmax_packed_kernel, (int)smem_mm)) return rc;
-            if (smem_sum > 48 * 1024)
-                if (int rc = cwm_set_max_lds((const void*)flow_motion_sum_packed_kernel, (int)smem_sum)) return rc;
-            if (normalize_per_sample)
-                hipLaunchKernelGGL(flow_mag_minmax_packed_kernel, dim3((unsigned)((HW + tile_mm - 1) / tile_mm), (unsigned)B), dim3(256), smem_mm, s, flows_dev, strides[0],
-                                   strides[1], C, HW, S, tile_mm, mn, mx);
-            hipLaunchKernelGGL(flow_motion_sum_packed_kernel, dim3((unsigned)((HW + tile_sum - 1) / tile_sum), (unsigned)B), dim3(256), smem_sum, s, flows_dev, strides[0],
-                               strides[1], C, HW, S, tile_sum, mn, mx, eps, sum_dev);
-        }
+    const int HW = H * W;
+    if (form == MOTION_STRIDED) {
+        float2* mm = normalize_per_sample ? reinterpret_cast<float2*>(minmax_work_dev) : nullptr;
+        if (mm) hipLaunchKernelGGL(flow_mag_minmax_kernel, dim3((unsigned)S, (unsigned)B), dim3(256), 0, s, v, mm);
+        hipLaunchKernelGGL(flow_motion_sum_kernel, dim3((unsigned)(((int64_t)B * HW + 255) / 256)), dim3(256), 0, s, v, mm, eps, sum_dev);
         CWM_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    float2* mm = nullptr;
+    // work buffer (cwm_flow_motion_work_bytes): kRangeReplicas x [B][S] min bits, then as many max bits
+    unsigned *mn = nullptr, *mx = nullptr;
     if (normalize_per_sample) {
-        mm = reinterpret_cast<float2*>(minmax_work_dev);
-        hipLaunchKernelGGL(flow_mag_minmax_kernel, dim3((unsigned)S, (unsigned)B), dim3(256), 0, s, flows_dev, strides[0], strides[1], strides[2],
-                           strides[3], strides[4], C, H, W, S, mm);
+        const size_t n = (size_t)kRangeReplicas * B * S;
+        mn = reinterpret_cast<unsigned*>(minmax_work_dev);
+        mx = mn + n;
+        CWM_HIP_CHECK(hipMemsetAsync(mn, 0xFF, n * sizeof(unsigned), s));
+        CWM_HIP_CHECK(hipMemsetAsync(mx, 0x00, n * sizeof(unsigned), s));
     }
-    const int64_t total = (int64_t)B * H * W;
-    hipLaunchKernelGGL(flow_motion_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, flows_dev, strides[0], strides[1],
-                       strides[2], strides[3], strides[4], B, C, H, W, S, mm, eps, sum_dev);
+    if (form == MOTION_TILE) {
+        const int tile_mm = mag_tile_pix(S);
+        const size_t smem_mm = motion_range_lds(S), smem_sum = motion_sum_lds(S);
+        if (int rc = smem_mm > 48 * 1024 ? cwm_set_max_lds((const void*)flow_mag_minmax_packed_kernel, (int)smem_mm) : 0) return rc;
+        if (int rc = smem_sum > 48 * 1024 ? cwm_set_max_lds((const void*)flow_motion_sum_packed_kernel, (int)smem_sum) : 0) return rc;
+        const dim3 grid_mm((unsigned)((HW + tile_mm - 1) / tile_mm), (unsigned)B), grid_sum((unsigned)((HW + kSumTilePix - 1) / kSumTilePix), (unsigned)B);
+        if (mn) hipLaunchKernelGGL(flow_mag_minmax_packed_kernel, grid_mm, dim3(256), smem_mm, s, v.f, v.sb, v.sc, C, HW, S, tile_mm, mn, mx);
+        hipLaunchKernelGGL(flow_motion_sum_packed_kernel, grid_sum, dim3(256), smem_sum, s, v.f, v.sb, v.sc, C, HW, S, kSumTilePix, mn, mx, eps, sum_dev);
+    } else {  // lanes per pixel: 16, 32, 64
+        const dim3 grid((unsigned)((HW + 4 * kRowPixPerWave - 1) / (4 * kRowPixPerWave)), (unsigned)B);
+        dispatch_int<16, 32, 64>(form == MOTION_ROWS16 ? 16 : form == MOTION_ROWS32 ? 32 : 64, [&](auto q) {
+            if (mn) hipLaunchKernelGGL(flow_mag_minmax_rows_kernel<q.value>, grid, dim3(256), 0, s, v.f, v.sb, v.sc, C, HW, S, mn, mx);
+            hipLaunchKernelGGL(flow_motion_sum_rows_kernel<q.value>, grid, dim3(256), 0, s, v.f, v.sb, v.sc, C, HW, S, mn, mx, eps, sum_dev);
+        });
+    }
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -34,6 +34,13 @@ def _strides5(flows: torch.Tensor):
     return flows, (C.c_int64 * 5)(*flows.stride())
 
 
+def _sample_outermost(flows: torch.Tensor) -> bool:
+    """csrc/flow_view.h FlowLayout.sample_outer, the layout `cwm_flow_filter_pack` takes: every (b, s) is one contiguous [C, H, W] block (the
+    `_batch_to_samples` view of the flow model's output)"""
+    H, W = flows.shape[2:4]
+    return flows.stride(3) == 1 and flows.stride(2) == W and flows.stride(1) == H * W
+
+
 def _require_cuda(t: torch.Tensor, what: str):
     _lib.require_gpu()
     if not t.is_cuda:

@@ -19,7 +19,7 @@ from torch import nn
 from torch.distributions.categorical import Categorical
 
 from . import _lib
-from .flowstats import _require_cuda, _strides5
+from .flowstats import _require_cuda, _sample_outermost, _strides5
 from .masking import MaskingGenerator, upsample_masks
 
 
@@ -250,7 +250,7 @@ class FlowSampleFilter(nn.Module):
             _lib.check(lib.cwm_flow_filter_apply(flows.data_ptr(), strides, B, Cc, H, W, S, reject.data_ptr(), stream))
             if flows.is_contiguous():
                 out = flows
-            elif flows.stride(3) == 1 and flows.stride(2) == W and flows.stride(1) == H * W:
+            elif _sample_outermost(flows):
                 # the view `_batch_to_samples` hands over: one transposing pass (kept samples read once, zeros written for the others)
                 out = torch.empty((B, Cc, H, W, S), device=flows.device, dtype=torch.float32)
                 _lib.check(lib.cwm_flow_filter_pack(flows.data_ptr(), strides, B, Cc, H, W, S, reject.data_ptr(), out.data_ptr(), stream))

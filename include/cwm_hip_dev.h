@@ -37,6 +37,36 @@ typedef struct cwm_dev_gemm_plan_out {
 } cwm_dev_gemm_plan_out;
 CWM_API int cwm_dev_gemm_plan(int M, int N, int K, int epi, int mode, int overlapped, int forced_cfg, int cus, cwm_dev_gemm_plan_out* out);
 
+/* Which kernel form each entry point that takes flow samples [B, C, H, W, S] would launch (csrc/flow_view.h: the same functions the entry points call): element
+ * strides, sizes, the address of the flows and the entry point's other address -- cwm_flow_features: the output; cwm_flow_motion_sum: the work buffer (0: none) --,
+ * and for cwm_flow_filter_stats the mask [B, 2 patches_per_frame, S]: its strides (b, patch, s) and its address.  CWM_DEV_FLOW_REFUSED where the entry point refuses the flows or
+ * the layout (the filter's: C != 2, H != W ...; the checks of an entry point's other arguments are not part of this).  Launches nothing and needs no device. */
+#define CWM_DEV_FLOW_REFUSED (-1)
+#define CWM_DEV_FLOW_FEATURES_SCALAR 0
+#define CWM_DEV_FLOW_FEATURES_VEC4 1    /* four samples per thread, 16-byte loads */
+#define CWM_DEV_FLOW_MOTION_STRIDED 0
+#define CWM_DEV_FLOW_MOTION_TILE 1      /* packed: magnitudes of a pixel tile in LDS */
+#define CWM_DEV_FLOW_MOTION_ROWS16 2    /* packed: 16 / 32 / 64 lanes x 16 bytes own a pixel's samples (S = 64 / 128 / a multiple of 256) */
+#define CWM_DEV_FLOW_MOTION_ROWS32 3
+#define CWM_DEV_FLOW_MOTION_ROWS64 4
+#define CWM_DEV_FLOW_COUNT_PLANES 0     /* also the strided form */
+#define CWM_DEV_FLOW_COUNT_PLANES_VEC 1
+#define CWM_DEV_FLOW_COUNT_PACKED 2
+#define CWM_DEV_FLOW_COUNT_PACKED_VEC 3
+#define CWM_DEV_FLOW_FINISH_V1 0
+#define CWM_DEV_FLOW_FINISH_V4 1        /* the mask bytes of four samples per 32-bit load */
+#define CWM_DEV_FLOW_ZERO_PLANES 0
+#define CWM_DEV_FLOW_ZERO_PLANES_VEC 1
+#define CWM_DEV_FLOW_ZERO_SCATTER 2
+#define CWM_DEV_FLOW_PACK_TRANSPOSE 0
+typedef struct cwm_dev_flow_forms_out {
+    int32_t features, motion; /* cwm_flow_features, cwm_flow_motion_sum */
+    int32_t count, finish;    /* cwm_flow_filter_stats: the counting pass and the finish kernel */
+    int32_t zero, pack;       /* cwm_flow_filter_apply, cwm_flow_filter_pack */
+} cwm_dev_flow_forms_out;
+CWM_API int cwm_dev_flow_forms(const int64_t* strides, int B, int C, int H, int W, int S, uint64_t flows_addr, uint64_t aux_addr, int normalize_per_sample,
+                               const int64_t* mask_strides, uint64_t mask_addr, int patches_per_frame, cwm_dev_flow_forms_out* out);
+
 /* ---- diagnostics: single-kernel micro-benchmarks on random operands (tools/microbench.py) ---------
  * epi: 0 = fp32 out + bias + in-place residual (proj/fc2 form), 1 = bias + GELU -> bf16 (fc1 form),
  *      3 = QKV head scatter (N must be 3*64*heads, M = batch*n_tok with n_tok = M / batch).

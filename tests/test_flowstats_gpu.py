@@ -271,3 +271,24 @@ def test_full_grid_properties():
     assert not FS.compute_flow_cov(const, downsample=2).any()
     mm = FS.compute_mean_motion_map(fl)
     assert mm.shape == (1, 1, 224, 224) and mm.min().item() == 0.0 and abs(mm.max().item() - 1.0) <= 1e-6
+
+
+def test_layout_refusals_come_before_any_launch():
+    """What csrc/flow_view.h's forms refuse (tests/test_flow_forms_cpu.py has the table), the entry points refuse with CWM_ERR_INVALID and their own name -- on real
+    buffers, which stay untouched."""
+    import ctypes
+
+    from counterfactualworldmodels_amd import _lib
+
+    lib = _lib.get_lib()
+    fl = torch.ones(1, 2, 4, 4, 8193, device="cuda")  # packed, more samples than the scatter form's list holds
+    keep = fl.clone()
+    rej = torch.ones(1, 8193, device="cuda", dtype=torch.uint8)
+    out = torch.zeros_like(fl)
+    st = (ctypes.c_int64 * 5)(*fl.stride())
+    args = (fl.data_ptr(), st, 1, 2, 4, 4, 8193)
+    assert lib.cwm_flow_filter_apply(*args, rej.data_ptr(), None) == -1 and b"cwm_flow_filter_apply: S=8193 > 8192" in lib.cwm_last_error()
+    assert lib.cwm_flow_filter_pack(*args, rej.data_ptr(), out.data_ptr(), None) == -1 and b"cwm_flow_filter_pack: every sample must be one contiguous" in lib.cwm_last_error()
+    assert lib.cwm_flow_motion_sum(*args, 1, 0.01, None, out.data_ptr(), None) == -1 and b"cwm_flow_motion_sum: per-sample normalisation needs" in lib.cwm_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(fl, keep) and not out.any()
