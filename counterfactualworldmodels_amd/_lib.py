@@ -392,6 +392,81 @@ class CwmDevConjPadArgs(C.Structure):
     ]
 
 
+class CwmDevGemmArgs(C.Structure):
+    """include/cwm_hip_dev.h cwm_dev_gemm_args (development library only)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mode", C.c_int32),
+        ("epi", C.c_int32),
+        ("a", C.c_void_p),
+        ("w", C.c_void_p),
+        ("bias", C.c_void_p),
+        ("M", C.c_int32),
+        ("N", C.c_int32),
+        ("K", C.c_int32),
+        ("rows_in", C.c_int32),
+        ("rows_out", C.c_int32),
+        ("out_row_offset", C.c_int32),
+        ("map_stride", C.c_int32),
+        ("resid_rowmap", C.c_void_p),
+        ("C", C.c_void_p),
+        ("ldc", C.c_int32),
+        ("resid", C.c_void_p),
+        ("ldr", C.c_int32),
+        ("out", C.c_void_p),
+        ("ldo", C.c_int32),
+        ("q_out", C.c_void_p),
+        ("k_out", C.c_void_p),
+        ("v_out", C.c_void_p),
+        ("qk_plane", C.c_int64),
+        ("heads", C.c_int32),
+        ("head_dim", C.c_int32),
+        ("n_tok", C.c_int32),
+        ("q_scale", C.c_float),
+        ("plan_forms", C.POINTER(C.c_int32)),
+        ("stream", C.c_void_p),
+    ]
+
+
+class CwmDevAttentionArgs(C.Structure):
+    """include/cwm_hip_dev.h cwm_dev_attention_args (development library only)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mode", C.c_int32),
+        ("qkv", C.c_void_p),
+        ("B", C.c_int32),
+        ("N", C.c_int32),
+        ("H", C.c_int32),
+        ("q_off", C.c_int32),
+        ("n_q", C.c_int32),
+        ("o", C.c_void_p),
+        ("ldo", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
+class CwmDevLayernormArgs(C.Structure):
+    """include/cwm_hip_dev.h cwm_dev_layernorm_args (development library only)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mode", C.c_int32),
+        ("x", C.c_void_p),
+        ("ldx", C.c_int32),
+        ("gamma", C.c_void_p),
+        ("beta", C.c_void_p),
+        ("eps", C.c_float),
+        ("D", C.c_int32),
+        ("rows", C.c_int32),
+        ("rows_out_per_b", C.c_int32),
+        ("rows_in_per_b", C.c_int32),
+        ("in_offset", C.c_int32),
+        ("out", C.c_void_p),
+        ("ldo", C.c_int32),
+        ("out_f32", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
 class CwmDevGemmPlanPart(C.Structure):
     _fields_ = [("m_offset", C.c_int32), ("M", C.c_int32), ("kernel", C.c_int32), ("splitk", C.c_int32)]
 
@@ -419,7 +494,7 @@ DEV_FLOW_PACK_TRANSPOSE = 0
 
 
 def new_dev_conj_args(cls):
-    """a zeroed cwm_dev_conj_*_args of the given structure class with its struct_size set"""
+    """a zeroed cwm_dev_*_args of the given structure class (conj, gemm, attention, layernorm) with its struct_size set"""
     a = cls()
     a.struct_size = C.sizeof(cls)
     return a
@@ -554,6 +629,10 @@ DEV_SIGNATURES = {
     "cwm_dev_conj_cross_attention": (C.c_int, [C.POINTER(CwmDevConjCrossAttentionArgs)]),
     "cwm_dev_conj_small_attention": (C.c_int, [C.POINTER(CwmDevConjSmallAttentionArgs)]),
     "cwm_dev_conj_pad": (C.c_int, [C.POINTER(CwmDevConjPadArgs)]),
+    "cwm_dev_gemm": (C.c_int, [C.POINTER(CwmDevGemmArgs)]),
+    "cwm_dev_attention": (C.c_int, [C.POINTER(CwmDevAttentionArgs)]),
+    "cwm_dev_layernorm": (C.c_int, [C.POINTER(CwmDevLayernormArgs)]),
+    "cwm_dev_fill_mask_tokens": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
 }
 
 # the keys cwm_model_set_option / cwm_conj_set_option know (include/cwm_hip.h; csrc/engine.hip tuning_field)

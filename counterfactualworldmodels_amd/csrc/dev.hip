@@ -17,23 +17,6 @@ using namespace cwm;
 void cwm_set_pretend_device(int d);  // engine.hip
 
 namespace {
-struct Scratch {
-    std::vector<void*> ptrs;
-    ~Scratch() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    T* get(size_t count, bool zero = false) {
-        void* p = nullptr;
-        if (hipMalloc(&p, count * sizeof(T) + 16) != hipSuccess) return nullptr;
-        ptrs.push_back(p);
-        if (zero) (void)hipMemset(p, 0, count * sizeof(T));
-        return (T*)p;
-    }
-};
-}  // namespace
-
-namespace {
 __global__ void fill_random_bf16_kernel(bf16* dst, int64_t n, unsigned seed, float scale) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -601,5 +584,114 @@ extern "C" int cwm_dev_conj_pad(const cwm_dev_conj_pad_args* args) {
     }
     if (rc) return rc;
     CWM_HIP_CHECK(hipStreamSynchronize(s));
+    return CWM_OK;
+}
+
+// ---- the ViT engine's own launch forms one at a time (tests/test_engine_kernels_gpu.py) ----
+// The parameters engine.hip builds for its row-mapped GEMMs (residual_gemm, embed_stream, to_decoder), the Q/K/V scatter and the pruned block's query
+// window, LayerNorm on mapped rows (run_mlp, head_rows) and the mask-token fill, each as one launch on the caller's buffers.
+extern "C" int cwm_dev_gemm(const cwm_dev_gemm_args* args) {
+    CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_gemm_args), "cwm_dev_gemm: args->struct_size must be sizeof(cwm_dev_gemm_args)");
+    const cwm_dev_gemm_args& a = *args;
+    hipStream_t s = (hipStream_t)a.stream;
+    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_gemm: bad mode");
+    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    CWM_REQUIRE(a.a && a.w && a.M > 0 && a.N > 0 && a.K > 0 && a.epi >= EPI_F32 && a.epi <= EPI_QKV, "cwm_dev_gemm: bad argument");
+    CWM_REQUIRE(a.rows_in >= 0 && a.out_row_offset >= 0 && (a.rows_in > 0 || (!a.resid_rowmap && a.out_row_offset == 0)),
+                "cwm_dev_gemm: a row map or row offset needs rows_in > 0");
+    if (a.rows_in > 0) {
+        CWM_REQUIRE(a.M % a.rows_in == 0 && a.rows_in + a.out_row_offset <= a.rows_out, "cwm_dev_gemm: %d rows as samples of %d rows at offset %d of %d", a.M,
+                    a.rows_in, a.out_row_offset, a.rows_out);
+        CWM_REQUIRE(!a.resid_rowmap || a.map_stride >= a.rows_in, "cwm_dev_gemm: a residual row map of %d entries per sample for %d rows", a.map_stride, a.rows_in);
+    }
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.M = a.M; p.N = a.N; p.K = p.lda = round_up(a.K, 64);
+    p.epi = a.epi;
+    p.rows_in = a.rows_in; p.rows_out = a.rows_out; p.out_row_offset = a.out_row_offset; p.map_stride = a.map_stride; p.resid_rowmap = a.resid_rowmap;
+    if (a.epi == EPI_F32) {
+        CWM_REQUIRE(a.C && a.ldc >= a.N && (!a.resid || a.ldr >= a.N), "cwm_dev_gemm: the fp32 output needs C and rows of at least N columns");
+        CWM_REQUIRE(!a.resid_rowmap || a.resid, "cwm_dev_gemm: a residual row map without a residual");
+        p.C = a.C; p.ldc = a.ldc; p.resid = a.resid; p.ldr = a.ldr;
+    } else if (a.epi == EPI_QKV) {
+        CWM_REQUIRE(a.q_out && a.k_out && a.v_out && a.heads > 0 && a.head_dim > 0 && a.n_tok > 0 && a.N == 3 * a.heads * a.head_dim && a.M % a.n_tok == 0,
+                    "cwm_dev_gemm: the Q/K/V scatter needs the three outputs, N = 3 * heads * head_dim and whole samples of n_tok rows");
+        CWM_REQUIRE(planes == 1 || a.qk_plane >= (int64_t)a.M * a.heads * a.head_dim, "cwm_dev_gemm: the lo plane would overlap the hi plane");
+        p.q_out = (bf16*)a.q_out; p.k_out = (bf16*)a.k_out; p.v_out = (bf16*)a.v_out; p.qk_plane = a.qk_plane;
+        p.qkv_dim = a.heads * a.head_dim; p.heads = a.heads; p.head_dim = a.head_dim; p.n_tok = a.n_tok; p.q_scale = a.q_scale;
+    } else {
+        CWM_REQUIRE(a.out && a.ldo >= a.N, "cwm_dev_gemm: the operand output needs out and rows of at least N columns");
+        p.out_hi = (bf16*)a.out; p.ldo = a.ldo;
+    }
+    p.tune = &thread_tuning();
+    GemmPlan plan;
+    if (int rc = gemm_plan(p, planes, 0, gemm_cu_count(), &plan)) return rc;  // the launcher's own refusals, before anything is staged
+    if (a.plan_forms) a.plan_forms[0] = plan.staged, a.plan_forms[1] = plan.direct;
+    Scratch sc;
+    LinearOperands op;
+    if (int rc = stage_linear_operands(sc, "cwm_dev_gemm", a.a, a.w, a.bias, a.M, a.N, a.K, planes, s, &op)) return rc;
+    p.A = op.A; p.W = op.W;
+    p.bias = a.bias ? op.bias : nullptr;
+    if (int rc = launch_gemm(p, planes, s)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize(s));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_attention(const cwm_dev_attention_args* args) {
+    CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_attention_args), "cwm_dev_attention: args->struct_size must be sizeof(cwm_dev_attention_args)");
+    const cwm_dev_attention_args& a = *args;
+    hipStream_t s = (hipStream_t)a.stream;
+    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_attention: bad mode");
+    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    CWM_REQUIRE(a.qkv && a.o && a.B > 0 && a.N > 0 && a.H > 0, "cwm_dev_attention: bad argument");
+    CWM_REQUIRE(a.q_off >= 0 && a.n_q >= 0 && a.q_off + a.n_q <= a.N && (a.n_q > 0 || a.q_off == 0), "cwm_dev_attention: query rows [%d, %d) of %d tokens", a.q_off,
+                a.q_off + a.n_q, a.N);
+    const int D = a.H * 64;
+    CWM_REQUIRE(a.ldo >= D && a.ldo % (planes == 2 ? 32 : 4) == 0, "cwm_dev_attention: %d columns in operand rows of ldo = %d (a multiple of 32 in parity mode, of 4 in fast mode)",
+                D, a.ldo);
+    const int64_t qk_plane = (int64_t)a.B * a.N * D;
+    Scratch sc;
+    bf16* q = sc.get<bf16>(2 * qk_plane);
+    bf16* k = sc.get<bf16>(2 * qk_plane);
+    bf16* v = sc.get<bf16>(2 * qk_plane);
+    CWM_REQUIRE(q && k && v, "cwm_dev_attention: out of device memory");
+    if (int rc = launch_qkv_scatter(a.qkv, a.B, a.N, a.H, 0.125f, q, k, v, qk_plane, s)) return rc;
+    AttnParams p;
+    memset(&p, 0, sizeof(p));
+    p.q = q; p.k = k; p.v = v; p.qk_plane = qk_plane;
+    p.o = (bf16*)a.o; p.o_plane = (int64_t)a.B * (a.n_q ? a.n_q : a.N) * a.ldo; p.ldo = a.ldo;
+    p.n_tok = a.N; p.heads = a.H; p.batch = a.B;
+    p.q_off = a.q_off; p.n_q = a.n_q;
+    p.tune = &thread_tuning();
+    if (int rc = launch_attention(p, planes, s)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize(s));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_layernorm(const cwm_dev_layernorm_args* args) {
+    CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_layernorm_args), "cwm_dev_layernorm: args->struct_size must be sizeof(cwm_dev_layernorm_args)");
+    const cwm_dev_layernorm_args& a = *args;
+    hipStream_t s = (hipStream_t)a.stream;
+    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_layernorm: bad mode");
+    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    CWM_REQUIRE(a.x && a.gamma && a.beta && a.out && a.rows > 0 && a.D > 0 && a.ldx >= a.D, "cwm_dev_layernorm: bad argument");
+    CWM_REQUIRE(a.rows_out_per_b >= 0 && a.in_offset >= 0 &&
+                    (a.rows_out_per_b == 0 ? a.in_offset == 0 : a.rows % a.rows_out_per_b == 0 && a.in_offset + a.rows_out_per_b <= a.rows_in_per_b),
+                "cwm_dev_layernorm: %d rows as samples of %d rows at offset %d of %d", a.rows, a.rows_out_per_b, a.in_offset, a.rows_in_per_b);
+    LayerNormParams ln;
+    memset(&ln, 0, sizeof(ln));
+    ln.x = a.x; ln.ldx = a.ldx; ln.gamma = a.gamma; ln.beta = a.beta; ln.eps = a.eps; ln.D = a.D; ln.rows = a.rows;
+    ln.rows_out_per_b = a.rows_out_per_b; ln.rows_in_per_b = a.rows_in_per_b; ln.in_offset = a.in_offset;
+    ln.out = (bf16*)a.out; ln.out_plane = (int64_t)a.rows * a.ldo; ln.ldo = a.ldo; ln.out_f32 = a.out_f32;
+    if (int rc = launch_layernorm(ln, planes, s)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize(s));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_fill_mask_tokens(float* x_full_dev, const float* mask_token_dev, const float* pos_dev, const int32_t* perm_dev, int B, int Nt, int n_vis,
+                                        int D, void* stream) {
+    CWM_REQUIRE(x_full_dev && mask_token_dev && pos_dev && perm_dev && B > 0 && D > 0 && n_vis >= 0 && n_vis <= Nt, "cwm_dev_fill_mask_tokens: bad argument");
+    if (int rc = launch_fill_mask_tokens(x_full_dev, mask_token_dev, pos_dev, perm_dev, B, Nt, n_vis, D, (hipStream_t)stream)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return CWM_OK;
 }

@@ -76,6 +76,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const LayerNormParams p)
 int launch_layernorm(const LayerNormParams& p, int planes, hipStream_t stream) {
     CWM_REQUIRE(p.D % 8 == 0 && p.D <= 1024, "layernorm: D=%d must be a multiple of 8 and <= 1024", p.D);
     CWM_REQUIRE(p.ldx % 4 == 0 && p.ldo % 8 == 0, "layernorm: row strides must be multiples of 4 (input) / 8 (output)");
+    // (a_pos puts column c of a split row at 64 (c / 32) + c % 32, its lo half 32 further: the last block of a row whose ldo is no multiple of 32 would reach
+    // into the next row -- D = 40 in rows of ldo = 40 wrote the lo half of columns 32..39 of row r over the hi half of columns 16..23 of row r + 1)
+    CWM_REQUIRE(p.ldo >= p.D && (planes == 1 || p.ldo % 32 == 0),
+                "layernorm: %d columns in output rows of ldo=%d (split-bf16 rows are whole [32 hi | 32 lo] blocks: a multiple of 32)", p.D, p.ldo);
     const int blocks = (p.rows + 3) / 4;
     if (planes == 1)
         hipLaunchKernelGGL(layernorm_kernel<1>, dim3(blocks), dim3(256), 0, stream, p);

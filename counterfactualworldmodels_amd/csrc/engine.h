@@ -250,4 +250,32 @@ GemmParams gemm_base(const bf16* A, int lda, const LinearW& L, int M, int planes
 // fp32 [N][K] -> bf16 [Npad][Kpad] (hi only) and [Npad][2*Kpad] (hi/lo interleaved), zero padded
 int launch_pack_weight(const float* src, int N, int K, bf16* hi, bf16* il, int Npad, int Kpad, hipStream_t stream);
 
+// ---- what the stand-alone entry points (model.hip) and the development ones (dev.hip) share ----
+// Device buffers of one call, freed when it returns.  They allocate per call: not for hot loops.
+struct Scratch {
+    std::vector<void*> ptrs;
+    ~Scratch() {
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+    template <typename T>
+    T* get(size_t count, bool zero = false) {
+        void* p = nullptr;
+        if (hipMalloc(&p, count * sizeof(T) + 16) != hipSuccess) return nullptr;
+        ptrs.push_back(p);
+        if (zero) (void)hipMemset(p, 0, count * sizeof(T));
+        return (T*)p;
+    }
+};
+// fp32 a [M][K], w [N][K], bias [N] (or nullptr) as a GEMM reads them in the mode of `planes`: A rows in the operand layout with K zero-padded to Kp =
+// round_up(K, 64), W packed by launch_pack_weight to Np = round_up(N, 256) rows, bias [Np] zero beyond N.  The buffers are `sc`'s (model.hip).
+struct LinearOperands {
+    bf16 *A, *W;
+    float* bias;
+    int Kp, Np;
+};
+int stage_linear_operands(Scratch& sc, const char* who, const float* a, const float* w, const float* bias, int M, int N, int K, int planes, hipStream_t s,
+                          LinearOperands* out);
+// qkv [B, N, 3, H, 64] fp32 -> Q (times scale), K, V [B * H, N, 64], hi plane and lo plane (qk_plane elements further) whatever the mode (model.hip)
+int launch_qkv_scatter(const float* qkv, int B, int N, int H, float scale, bf16* q, bf16* k, bf16* v, int64_t qk_plane, hipStream_t s);
+
 }  // namespace cwm

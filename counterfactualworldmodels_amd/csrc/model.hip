@@ -261,21 +261,6 @@ extern "C" int cwm_timing_collect(cwm_model* m, int kclass, cwm_kernel_stats* ou
 // stand-alone kernel entry points (tests).  They allocate scratch per call: not for hot loops.
 // ---------------------------------------------------------------------------------------------
 namespace {
-struct Scratch {
-    std::vector<void*> ptrs;
-    ~Scratch() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    T* get(size_t count, bool zero = false) {
-        void* p = nullptr;
-        if (hipMalloc(&p, count * sizeof(T) + 16) != hipSuccess) return nullptr;
-        ptrs.push_back(p);
-        if (zero) (void)hipMemset(p, 0, count * sizeof(T));
-        return (T*)p;
-    }
-};
-
 // fp32 [rows][K] -> GEMM A-operand layout of the given mode (common.h a_pos), K zero-padded to Kpad
 template <int PLANES>
 __global__ void pad_split_rows_kernel(const float* src, int rows, int K, bf16* out, int Kpad) {
@@ -316,6 +301,32 @@ __global__ void merge_planes_kernel(const bf16* in, float* out, int rows, int ld
 }
 }  // namespace
 
+int cwm::stage_linear_operands(Scratch& sc, const char* who, const float* a, const float* w, const float* bias, int M, int N, int K, int planes, hipStream_t s,
+                               LinearOperands* out) {
+    const int Kp = round_up(K, 64), Np = round_up(N, 256);
+    out->Kp = Kp;
+    out->Np = Np;
+    out->A = sc.get<bf16>((size_t)2 * M * Kp);
+    out->W = sc.get<bf16>((size_t)2 * Np * Kp);
+    out->bias = sc.get<float>(Np, true);
+    CWM_REQUIRE(out->A && out->W && out->bias, "%s: out of device memory", who);
+    const unsigned gridA = (unsigned)(((int64_t)M * Kp + 255) / 256);
+    if (planes == 2)
+        hipLaunchKernelGGL(pad_split_rows_kernel<2>, dim3(gridA), dim3(256), 0, s, a, M, K, out->A, Kp);
+    else
+        hipLaunchKernelGGL(pad_split_rows_kernel<1>, dim3(gridA), dim3(256), 0, s, a, M, K, out->A, Kp);
+    if (int rc = launch_pack_weight(w, N, K, planes == 1 ? out->W : nullptr, planes == 2 ? out->W : nullptr, Np, Kp, s)) return rc;
+    if (bias) CWM_HIP_CHECK(hipMemcpyAsync(out->bias, bias, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+int cwm::launch_qkv_scatter(const float* qkv, int B, int N, int H, float scale, bf16* q, bf16* k, bf16* v, int64_t qk_plane, hipStream_t s) {
+    const int64_t total = (int64_t)B * N * 3 * H * 64;
+    hipLaunchKernelGGL(qkv_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, B, N, H, scale, q, k, v, qk_plane);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int cwm_split_bf16(const float* x_dev, int64_t n, void* hi_dev, void* lo_dev, void* stream) {
     CWM_REQUIRE(x_dev && hi_dev && n >= 0, "cwm_split_bf16: bad argument");
     return launch_split_bf16(x_dev, n, (bf16*)hi_dev, (bf16*)lo_dev, (hipStream_t)stream);
@@ -327,25 +338,16 @@ extern "C" int cwm_linear(const float* a_dev, const float* w_dev, const float* b
     CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_linear: bad mode");
     hipStream_t s = (hipStream_t)stream;
     const int planes = mode == CWM_MODE_PARITY ? 2 : 1;
-    const int Kp = round_up(K, 64), Np = round_up(N, 256);
     Scratch sc;
-    bf16* A = sc.get<bf16>((size_t)2 * M * Kp);
-    bf16* W = sc.get<bf16>((size_t)2 * Np * Kp);
-    float* bias = sc.get<float>(Np, true);
+    LinearOperands op;
+    if (int rc = stage_linear_operands(sc, "cwm_linear", a_dev, w_dev, bias_dev, M, N, K, planes, s, &op)) return rc;
     const int ldg = round_up(N, 32);  // operand-layout rows are whole [32 hi | 32 lo] blocks
     bf16* G = gelu ? sc.get<bf16>((size_t)2 * M * ldg) : nullptr;
-    CWM_REQUIRE(A && W && bias && (!gelu || G), "cwm_linear: out of device memory");
-    const unsigned gridA = (unsigned)(((int64_t)M * Kp + 255) / 256);
-    if (planes == 2)
-        hipLaunchKernelGGL(pad_split_rows_kernel<2>, dim3(gridA), dim3(256), 0, s, a_dev, M, K, A, Kp);
-    else
-        hipLaunchKernelGGL(pad_split_rows_kernel<1>, dim3(gridA), dim3(256), 0, s, a_dev, M, K, A, Kp);
-    if (int rc = launch_pack_weight(w_dev, N, K, planes == 1 ? W : nullptr, planes == 2 ? W : nullptr, Np, Kp, s)) return rc;
-    if (bias_dev) CWM_HIP_CHECK(hipMemcpyAsync(bias, bias_dev, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));
+    CWM_REQUIRE(!gelu || G, "cwm_linear: out of device memory");
     GemmParams p;
     memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = Kp; p.W = W;
-    p.M = M; p.N = N; p.K = Kp; p.bias = bias;
+    p.A = op.A; p.lda = op.Kp; p.W = op.W;
+    p.M = M; p.N = N; p.K = op.Kp; p.bias = op.bias;
     if (gelu) {
         p.epi = EPI_BF16_GELU; p.out_hi = G; p.ldo = ldg;
     } else {
@@ -377,8 +379,7 @@ extern "C" int cwm_attention(const float* qkv_dev, float* o_dev, int B, int N, i
     bf16* v = sc.get<bf16>(2 * qk_plane);
     bf16* o = sc.get<bf16>(2 * qk_plane);
     CWM_REQUIRE(q && k && v && o, "cwm_attention: out of device memory");
-    const int64_t total = (int64_t)B * N * 3 * D;
-    hipLaunchKernelGGL(qkv_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv_dev, B, N, H, 0.125f, q, k, v, qk_plane);
+    if (int rc = launch_qkv_scatter(qkv_dev, B, N, H, 0.125f, q, k, v, qk_plane, s)) return rc;
     AttnParams a;
     memset(&a, 0, sizeof(a));
     a.q = q; a.k = k; a.v = v; a.qk_plane = qk_plane; a.o = o; a.o_plane = qk_plane; a.ldo = D;
@@ -398,12 +399,13 @@ extern "C" int cwm_layernorm(const float* x_dev, const float* gamma_dev, const f
     CWM_REQUIRE(x_dev && gamma_dev && beta_dev && y_dev && rows > 0, "cwm_layernorm: bad argument");
     hipStream_t s = (hipStream_t)stream;
     Scratch sc;
-    bf16* tmp = sc.get<bf16>((size_t)2 * rows * D);
+    const int ldo = round_up(D, 32);  // operand-layout rows are whole [32 hi | 32 lo] blocks
+    bf16* tmp = sc.get<bf16>((size_t)2 * rows * ldo);
     CWM_REQUIRE(tmp, "cwm_layernorm: out of device memory");
     LayerNormParams ln;
     memset(&ln, 0, sizeof(ln));
     ln.x = x_dev; ln.ldx = D; ln.gamma = gamma_dev; ln.beta = beta_dev; ln.eps = eps; ln.D = D; ln.rows = rows;
-    ln.out = tmp; ln.out_plane = (int64_t)rows * D; ln.ldo = D; ln.out_f32 = y_dev;
+    ln.out = tmp; ln.out_plane = (int64_t)rows * ldo; ln.ldo = ldo; ln.out_f32 = y_dev;
     if (int rc = launch_layernorm(ln, 2, s)) return rc;
     CWM_HIP_CHECK(hipStreamSynchronize(s));
     return CWM_OK;

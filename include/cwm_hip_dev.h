@@ -261,6 +261,83 @@ typedef struct cwm_dev_conj_pad_args {
 } cwm_dev_conj_pad_args;
 CWM_API int cwm_dev_conj_pad(const cwm_dev_conj_pad_args* args);
 
+/* ---- the ViT engine's own launch forms one at a time (tests/test_engine_kernels_gpu.py) -----------------------------------------------------------
+ * launch_gemm / launch_attention / launch_layernorm / launch_fill_mask_tokens (csrc/kernels.h) with the parameters only csrc/engine.hip builds -- row
+ * maps, the Q/K/V scatter, a query window, mapped LayerNorm rows -- on caller-owned device buffers, with this thread's execution options; the stream
+ * is synchronised before a call returns.  "Operand" buffers are rows of planes * width bf16 in the layout of csrc/common.h a_pos (planes 2 parity, 1
+ * fast).  What the launchers refuse (and what the checks named below refuse) comes back as an error before anything is launched; none of the entry
+ * points checks that the buffers are as large as the geometry says. */
+
+/* One GEMM out = a w^T + bias through launch_gemm: a [M][K], w [N][K], bias [N] (optional) are fp32 and staged exactly as cwm_linear stages them (K
+ * zero-padded to a multiple of 64, the weight packed by the engine's packer); everything else is csrc/kernels.h GemmParams as it stands:
+ *   rows: rows_in == 0: identity.  Else row m = b * rows_in + i -> out row b * rows_out + i + out_row_offset; residual row = resid_rowmap ?
+ *         resid_rowmap[b * map_stride + i] : the out row.  (Needs M % rows_in == 0 and i + out_row_offset < rows_out.)
+ *   epi 0: C[out row][0..N) (row stride ldc) = acc + bias (+ resid[residual row][..], row stride ldr; resid may be C itself)
+ *   epi 1 / 2: out[out row][0..N) (operand, width ldo) = split(gelu(acc + bias)) / split(acc + bias)
+ *   epi 3: N = 3 * heads * head_dim, rows_in = n_tok: column c = which * D + h * head_dim + d of row (b, tok) -> {q_out, k_out, v_out}[which]
+ *          [(b * heads + h) * n_tok + tok][d], Q times q_scale; the lo plane lies qk_plane elements behind the hi plane (parity mode only) */
+typedef struct cwm_dev_gemm_args {
+    uint32_t struct_size;
+    int32_t mode; /* CWM_MODE_PARITY or CWM_MODE_FAST */
+    int32_t epi;  /* 0 .. 3, as for cwm_gemm_tile_override */
+    const float* a;
+    const float* w;
+    const float* bias; /* optional */
+    int32_t M, N, K;
+    int32_t rows_in, rows_out, out_row_offset, map_stride;
+    const int32_t* resid_rowmap; /* optional: [M / rows_in][map_stride] */
+    float* C;
+    int32_t ldc;
+    const float* resid; /* optional */
+    int32_t ldr;
+    void* out;
+    int32_t ldo;
+    void *q_out, *k_out, *v_out;
+    int64_t qk_plane;
+    int32_t heads, head_dim, n_tok;
+    float q_scale;
+    int32_t* plan_forms; /* optional, host: [2] = the epilogue form gemm_plan chose for THIS launch (staged, direct) */
+    void* stream;
+} cwm_dev_gemm_args;
+CWM_API int cwm_dev_gemm(const cwm_dev_gemm_args* args);
+
+/* Self-attention of head_dim 64 over the queries [q_off, q_off + n_q) of every sample (n_q == 0: all N): qkv [B][N][3 * H * 64] fp32 is scattered to
+ * Q (times 0.125), K, V as cwm_attention does, then launch_attention writes O as an operand of [B * (n_q ? n_q : N)] rows of width ldo (>= 64 H; a multiple
+ * of 32 in parity mode, of 4 in fast mode), head h at columns 64 h ..; other rows and columns of `o` are not written. */
+typedef struct cwm_dev_attention_args {
+    uint32_t struct_size;
+    int32_t mode;
+    const float* qkv;
+    int32_t B, N, H, q_off, n_q;
+    void* o;
+    int32_t ldo;
+    void* stream;
+} cwm_dev_attention_args;
+CWM_API int cwm_dev_attention(const cwm_dev_attention_args* args);
+
+/* LayerNorm of `rows` rows of D columns: output row r reads input row (r / rows_out_per_b) * rows_in_per_b + in_offset + r % rows_out_per_b of x (row
+ * stride ldx; rows_out_per_b == 0: row r) and writes row r of the operand `out` (width ldo >= D: a multiple of 32 in parity mode, of 8 in fast mode;
+ * columns >= D are not written) and, if given, of out_f32 [rows][D]. */
+typedef struct cwm_dev_layernorm_args {
+    uint32_t struct_size;
+    int32_t mode;
+    const float* x;
+    int32_t ldx;
+    const float* gamma;
+    const float* beta;
+    float eps;
+    int32_t D, rows, rows_out_per_b, rows_in_per_b, in_offset;
+    void* out;
+    int32_t ldo;
+    float* out_f32; /* optional */
+    void* stream;
+} cwm_dev_layernorm_args;
+CWM_API int cwm_dev_layernorm(const cwm_dev_layernorm_args* args);
+
+/* x_full [B][Nt][D]: rows n_vis .. Nt - 1 of every sample = mask_token [D] + pos[perm[b][row]] (pos rows of D floats, perm [B][Nt]); D a multiple of 4 */
+CWM_API int cwm_dev_fill_mask_tokens(float* x_full_dev, const float* mask_token_dev, const float* pos_dev, const int32_t* perm_dev, int B, int Nt, int n_vis,
+                                     int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
