@@ -633,6 +633,7 @@ DEV_SIGNATURES = {
     "cwm_dev_attention": (C.c_int, [C.POINTER(CwmDevAttentionArgs)]),
     "cwm_dev_layernorm": (C.c_int, [C.POINTER(CwmDevLayernormArgs)]),
     "cwm_dev_fill_mask_tokens": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "cwm_dev_unembed": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int64] * 3 + [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),
 }
 
 # the keys cwm_model_set_option / cwm_conj_set_option know (include/cwm_hip.h; csrc/engine.hip tuning_field)

@@ -695,3 +695,36 @@ extern "C" int cwm_dev_fill_mask_tokens(float* x_full_dev, const float* mask_tok
     CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return CWM_OK;
 }
+
+// cwm_unembed with the engine's strided frames (model.hip run_forward: x_stride_b / _c / _t of the caller's tensor): mask -> perm -> rank -> launch_unembed
+extern "C" int cwm_dev_unembed(const float* y_tokens_dev, const float* x_dev, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_t, const uint8_t* mask_dev,
+                               int B, int T, int C, int H, int W, int P, int n_vis, float* out_dev, void* stream) {
+    CWM_REQUIRE(y_tokens_dev && x_dev && mask_dev && out_dev && B > 0 && T > 0 && C > 0 && H > 0 && W > 0, "cwm_dev_unembed: bad argument");
+    CWM_REQUIRE(P > 0 && H % P == 0 && W % P == 0, "cwm_dev_unembed: image size must be divisible by the patch size");
+    CWM_REQUIRE(x_stride_c >= (int64_t)H * W && x_stride_t >= 0 && x_stride_b >= 0, "cwm_dev_unembed: channel planes of %d x %d pixels at a stride of %lld", H, W,
+                (long long)x_stride_c);
+    const int Nt = T * (H / P) * (W / P);
+    CWM_REQUIRE(n_vis >= 0 && n_vis <= Nt, "cwm_dev_unembed: n_vis = %d of %d tokens", n_vis, Nt);
+    hipStream_t s = (hipStream_t)stream;
+    Scratch sc;
+    int* perm = sc.get<int>((size_t)B * Nt);
+    int* rank = sc.get<int>((size_t)B * Nt);
+    int* err = sc.get<int>(4, true);
+    CWM_REQUIRE(perm && rank && err, "cwm_dev_unembed: out of device memory");
+    int rc;
+    if ((rc = launch_mask_to_perm(mask_dev, B, Nt, n_vis, perm, err, s))) return rc;
+    if ((rc = launch_perm_to_rank(perm, rank, B, Nt, s))) return rc;
+    UnembedParams u;
+    memset(&u, 0, sizeof(u));
+    u.y = y_tokens_dev; u.x = x_dev; u.sb = x_stride_b; u.st = x_stride_t; u.sc = x_stride_c;
+    u.mask = mask_dev; u.rank = rank; u.B = B; u.T = T; u.C = C; u.H = H; u.W = W; u.P = P; u.n_vis = n_vis; u.Nm = Nt - n_vis; u.out = out_dev;
+    if ((rc = launch_unembed(u, s))) return rc;
+    int herr = 0;
+    CWM_HIP_CHECK(hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, s));
+    CWM_HIP_CHECK(hipStreamSynchronize(s));
+    if (herr) {
+        cwm_set_error("mask rows do not all have n_vis=%d visible tokens", n_vis);
+        return CWM_ERR_MASK;
+    }
+    return CWM_OK;
+}

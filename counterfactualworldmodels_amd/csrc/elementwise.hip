@@ -436,6 +436,13 @@ int launch_fill_mask_tokens(float* x_full, const float* mask_token, const float*
 // `Patchify` (patches.py:74,98-102): feature index f = (ph*P + pw)*C + c; visible patches take the
 // RAW (un-normalised) wrapper input.  One thread per 4 horizontally adjacent output pixels.
 // ---------------------------------------------------------------------------------------------
+// Four floats at an address that is only 4-byte aligned: what the generic kernel below moves.  It is the form for everything unembed3_kernel refuses --
+// C != 3, a frame or output pointer off the 16-byte grid, batch / time / channel strides that are no multiple of 4 -- so its groups of four pixels may
+// start at any float.
+struct __attribute__((packed, aligned(4))) Float4A4 {
+    float v[4];
+};
+
 __global__ __launch_bounds__(256) void unembed_kernel(const UnembedParams p) {
     const int w4 = p.W / 4;
     const int64_t total = (int64_t)p.B * p.T * p.C * p.H * w4;
@@ -452,15 +459,15 @@ __global__ __launch_bounds__(256) void unembed_kernel(const UnembedParams p) {
     const int n = (p.H / p.P) * gw;
     const int Nt = p.T * n;
     const int tau = t * n + (y / p.P) * gw + (x0 / p.P);
-    float4 o;
+    Float4A4 o;
     if (p.mask[(size_t)b * Nt + tau]) {
         const int j = p.rank[(size_t)b * Nt + tau] - p.n_vis;
         const float* yp = p.y + ((size_t)b * p.Nm + j) * (p.P * p.P * p.C) + ((y % p.P) * p.P + (x0 % p.P)) * p.C + c;
-        o = make_float4(yp[0], yp[p.C], yp[2 * p.C], yp[3 * p.C]);
+        o = Float4A4{{yp[0], yp[p.C], yp[2 * p.C], yp[3 * p.C]}};
     } else {
-        o = *reinterpret_cast<const float4*>(p.x + b * p.sb + t * p.st + c * p.sc + (int64_t)y * p.W + x0);
+        o = *reinterpret_cast<const Float4A4*>(p.x + b * p.sb + t * p.st + c * p.sc + (int64_t)y * p.W + x0);
     }
-    *reinterpret_cast<float4*>(p.out + ((((size_t)b * p.T + t) * p.C + c) * p.H + y) * p.W + x0) = o;
+    *reinterpret_cast<Float4A4*>(p.out + ((((size_t)b * p.T + t) * p.C + c) * p.H + y) * p.W + x0) = o;
 }
 
 // C == 3 (every predictor of the path): one thread per 4 horizontally adjacent pixels of ALL THREE channels.  A masked patch row is
@@ -596,8 +603,10 @@ __global__ __launch_bounds__(256) void shift_prompts_mask_kernel(const ShiftProm
 // The prompt table of the counterfactual batch (BASELINE configs[3]; interface.py:370-377: one active patch of frame `frame` per prompt, moved by (dy, dx)
 // patches, nothing passive) -> the dense operands of the kernels above: passive[i] = "frame 0 visible, every later frame masked", active[i] = passive[i] with the
 // prompt's patch cleared, shifts[i] = (dy, dx).  One launch instead of the ten tensor operations that built them on rank 0's critical path (dist.py prompt_hooks).
-__global__ __launch_bounds__(256) void prompt_table_expand_kernel(const int* __restrict__ table, int S, int n, int gw, int T, int frame, uint8_t* __restrict__ active,
+// A table cell outside the grid (h outside [0, gh) or w outside [0, gw)) clears nothing: its linear index h gw + w would name another cell, or another frame.
+__global__ __launch_bounds__(256) void prompt_table_expand_kernel(const int* __restrict__ table, int S, int gh, int gw, int T, int frame, uint8_t* __restrict__ active,
                                                                   uint8_t* __restrict__ passive, int* __restrict__ shifts) {
+    const int n = gh * gw;
     const int Nt = T * n;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (int64_t)S * Nt) return;
@@ -605,13 +614,14 @@ __global__ __launch_bounds__(256) void prompt_table_expand_kernel(const int* __r
     const int h = table[4 * i], w = table[4 * i + 1];
     const uint8_t pas = tau >= n ? 1 : 0;
     passive[gid] = pas;
-    active[gid] = (tau == frame * n + h * gw + w) ? 0 : pas;
+    const bool in_grid = h >= 0 && h < gh && w >= 0 && w < gw;
+    active[gid] = (in_grid && tau == frame * n + h * gw + w) ? 0 : pas;
     if (tau < 2) shifts[2 * i + tau] = table[4 * i + 2 + tau];
 }
 
-int launch_prompt_table_expand(const int* table, int S, int n, int gw, int T, int frame, uint8_t* active, uint8_t* passive, int* shifts, hipStream_t stream) {
-    const int64_t total = (int64_t)S * T * n;
-    hipLaunchKernelGGL(prompt_table_expand_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, table, S, n, gw, T, frame, active, passive, shifts);
+int launch_prompt_table_expand(const int* table, int S, int gh, int gw, int T, int frame, uint8_t* active, uint8_t* passive, int* shifts, hipStream_t stream) {
+    const int64_t total = (int64_t)S * T * gh * gw;
+    hipLaunchKernelGGL(prompt_table_expand_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, table, S, gh, gw, T, frame, active, passive, shifts);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -788,14 +798,16 @@ __global__ __launch_bounds__(256) void mask_row_counts_kernel(const uint8_t* __r
     if (threadIdx.x == 0) counts[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-// table: [R | rows[R] | offsets[R + 1] | to_value[R] | picks[offsets[R]]]; one workgroup per changed row
+// table: [R | rows[R] | offsets[R + 1] | to_value[R] | picks[offsets[R]]]; one workgroup per changed row.  A table row whose index is outside [0, B) names no
+// row of the mask: its workgroup leaves (the whole workgroup, before the first barrier) and the other rows get their picks.
 constexpr int kFlipMaxTokens = 16384;
-__global__ __launch_bounds__(256) void mask_flip_picks_kernel(uint8_t* __restrict__ mask, int Nt, const int* __restrict__ table) {
+__global__ __launch_bounds__(256) void mask_flip_picks_kernel(uint8_t* __restrict__ mask, int B, int Nt, const int* __restrict__ table) {
     __shared__ unsigned bits[kFlipMaxTokens / 32];
     __shared__ int wave_tot[4];
     const int R = table[0], r = blockIdx.x, t = threadIdx.x;
     const int row = table[1 + r], p0 = table[1 + R + r], p1 = table[1 + R + r + 1], to = table[2 + 2 * R + r];
     const int* picks = table + 2 + 3 * R;
+    if (row < 0 || row >= B) return;
     uint8_t* m = mask + (size_t)row * Nt;
     for (int i = t; i < (Nt + 31) / 32; i += 256) bits[i] = 0u;
     __syncthreads();
@@ -823,10 +835,10 @@ int launch_mask_row_counts(const uint8_t* mask, int B, int Nt, int* counts, hipS
     return 0;
 }
 
-int launch_mask_flip_picks(uint8_t* mask, int Nt, const int* table, int n_rows, hipStream_t stream) {
+int launch_mask_flip_picks(uint8_t* mask, int B, int Nt, const int* table, int n_rows, hipStream_t stream) {
     CWM_REQUIRE(Nt <= kFlipMaxTokens, "mask_flip_picks: rows of %d tokens exceed the %d-token pick bitmap", Nt, kFlipMaxTokens);
     if (n_rows == 0) return 0;
-    hipLaunchKernelGGL(mask_flip_picks_kernel, dim3((unsigned)n_rows), dim3(256), 0, stream, mask, Nt, table);
+    hipLaunchKernelGGL(mask_flip_picks_kernel, dim3((unsigned)n_rows), dim3(256), 0, stream, mask, B, Nt, table);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -163,7 +163,7 @@ int launch_layernorm(const LayerNormParams& p, int planes, hipStream_t stream);
 int launch_mask_to_perm(const uint8_t* mask, int B, int Nt, int n_vis, int* perm, int* err, hipStream_t stream);
 // RectangularizeMasks on device masks (elementwise.hip): masked count per row; apply the host's picks [R | rows | offsets | to_value | picks] in place
 int launch_mask_row_counts(const uint8_t* mask, int B, int Nt, int* counts, hipStream_t stream);
-int launch_mask_flip_picks(uint8_t* mask, int Nt, const int* table, int n_rows, hipStream_t stream);
+int launch_mask_flip_picks(uint8_t* mask, int B, int Nt, const int* table, int n_rows, hipStream_t stream);  // table rows outside [0, B) are skipped
 
 struct PatchGatherParams {
     const float* x;  // frames; element (b,c,t,y,x) at b*sb + c*sc + t*st + y*W + x
@@ -228,7 +228,7 @@ struct ShiftPromptParams {
 };
 
 int launch_shift_prompts(const ShiftPromptParams& p, hipStream_t stream);
-int launch_prompt_table_expand(const int* table, int S, int n, int gw, int T, int frame, uint8_t* active, uint8_t* passive, int* shifts, hipStream_t stream);
+int launch_prompt_table_expand(const int* table, int S, int gh, int gw, int T, int frame, uint8_t* active, uint8_t* passive, int* shifts, hipStream_t stream);
 
 constexpr int kMultiShiftMaxSteps = 8;  // K of cwm_multi_shift_prompts (a backward walk of K dependent table reads per pixel)
 struct MultiShiftParams {

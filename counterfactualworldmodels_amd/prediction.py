@@ -447,6 +447,10 @@ class PredictorBasedGenerator(nn.Module):
             # reads frame 0 for every output frame, so the T-fold copy need not exist
             if not (T == 1 and fix_passive is True):
                 raise RuntimeError("num_frames=%d needs a one-frame movie and fix_passive=True" % num_frames)
+            # ONE movie only: the kernel finds movie b at (b T + frame) C H W with T = num_frames, which for b > 0 lies past the end of a tensor of B frames
+            if B != 1:
+                raise RuntimeError("num_frames=%d is the form for one movie given as its first frame; got %d movies of one frame: pass the %d-frame movies "
+                                   "themselves (make_static_movie)" % (num_frames, B, num_frames))
             T = int(num_frames)
         R, N = passive.shape
         x = x.to(torch.float32).contiguous() if frames else None  # (masks only: the frames are not read; no 1.2-MB materialisation of an expanded movie on rank 0's path)

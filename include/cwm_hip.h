@@ -260,7 +260,8 @@ CWM_API int cwm_unembed(const float* y_tokens_dev, const float* x_dev, const uin
  *   cwm_mask_flip_picks  applies the host's picks in place.  table_dev (int32): [R | rows[R] | offsets[R+1] | to_value[R] | picks[offsets[R]]] --
  *                        for changed row rows[i], every pick k in picks[offsets[i] .. offsets[i+1]) sets the k-th token (ascending position, 0-based,
  *                        counted on the row as it was BEFORE the call) whose state is not to_value[i] (0 = un-mask a masked token, 1 = mask a
- *                        visible one) to to_value[i].  n_rows = R.  Rows of at most 16384 tokens.  Both asynchronous on `stream`. */
+ *                        visible one) to to_value[i].  n_rows = R.  Rows of at most 16384 tokens.  A table row whose rows[i] is outside [0, B) is skipped:
+ *                        nothing is written for it.  Both asynchronous on `stream`. */
 CWM_API int cwm_mask_row_counts(const uint8_t* mask_dev, int B, int Nt, int32_t* counts_dev, void* stream);
 CWM_API int cwm_mask_flip_picks(uint8_t* mask_dev, int B, int Nt, const int32_t* table_dev, int n_rows, void* stream);
 
@@ -277,7 +278,8 @@ CWM_API int cwm_mask_flip_picks(uint8_t* mask_dev, int B, int Nt, const int32_t*
 /* The prompt table of a counterfactual batch -> the dense operands of cwm_shift_prompts, in one launch (no counterpart in the reference, which builds the
  * masks prompt by prompt on the host: interface.py:370-377, segmentation.py:324-338).  table_dev int32 [S,4] rows (active_h, active_w, dy, dx): ONE active
  * patch of frame `frame` (>= 1) per prompt, moved by (dy, dx) patches, nothing passive.  Writes passive [S,Nt] (frame 0 visible, later frames masked),
- * active [S,Nt] (= passive with the prompt's patch cleared) and shifts [S,2].  Cells outside the grid clear nothing.  Asynchronous on `stream`. */
+ * active [S,Nt] (= passive with the prompt's patch cleared) and shifts [S,2].  A row whose cell is outside the grid (active_h outside [0, grid_h) or active_w
+ * outside [0, grid_w)) clears nothing -- the kernel tests both coordinates, not the linear index -- and its shift is still copied.  Asynchronous on `stream`. */
 CWM_API int cwm_prompt_table_expand(const int32_t* table_dev, int S, int T, int grid_h, int grid_w, int frame, uint8_t* active_dev, uint8_t* passive_dev,
                             int32_t* shifts_dev, void* stream);
 CWM_API int cwm_shift_prompts(const float* x_dev, int B, int T, int C, int H, int W, int P, int frame, int S, int fix_passive,

@@ -338,6 +338,13 @@ CWM_API int cwm_dev_layernorm(const cwm_dev_layernorm_args* args);
 CWM_API int cwm_dev_fill_mask_tokens(float* x_full_dev, const float* mask_token_dev, const float* pos_dev, const int32_t* perm_dev, int B, int Nt, int n_vis,
                                      int D, void* stream);
 
+/* cwm_unembed (cwm_hip.h) on frames addressed as the engine addresses them: element (b, t, c, y, x) of x at b x_stride_b + t x_stride_t + c x_stride_c + y W + x
+ * (rows and pixels contiguous; x_stride_c >= H W).  mask -> permutation -> rank -> launch_unembed: out [B,T,C,H,W] contiguous = y at masked patches, x at visible
+ * ones.  C == 3 with 16-byte aligned x / y / out and strides that are multiples of 4 takes the three-channel kernel, everything else the generic one.
+ * CWM_ERR_MASK if a row does not have n_vis visible tokens. */
+CWM_API int cwm_dev_unembed(const float* y_tokens_dev, const float* x_dev, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_t, const uint8_t* mask_dev,
+                            int B, int T, int C, int H, int W, int P, int n_vis, float* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -395,8 +395,8 @@ def create_motion_counterfactuals(x_btchw, masks_bns, active_bns, shifts, P: int
     """`FlowGenerator.create_motion_counterfactuals` (segmentation.py:278-344) before the final
     `mask_rectangularizer` call: returns (x_shift [B*S,...], mask_shift [B*S,Nt]) in '(b s)' order."""
     B, N, S = masks_bns.shape
-    if fix_passive:  # make_static_movie(x[:,0:1], T=2)  (prediction.py:731-739)
-        x_btchw = x_btchw[:, 0:1].repeat(1, 2, 1, 1, 1)
+    if fix_passive:  # make_static_movie(x[:,0:1], T=T)  (prediction.py:731-739)
+        x_btchw = x_btchw[:, 0:1].repeat(1, x_btchw.shape[1], 1, 1, 1)
     xs, ms = [], []
     for b in range(B):
         for s in range(S):

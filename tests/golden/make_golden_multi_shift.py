@@ -109,7 +109,31 @@ def kernel_cases():
     m, p = tables(rng, 2, 32, 32, 8, 3, 4, 1); add("base_mask_2d", 32, 32, 8, 1, m[..., 0], p, rand_shifts(3, 8), expand_mask=True)
     m, p = tables(rng, 2, 32, 32, 8, 1, 5, 1); add("k1", 32, 32, 8, 1, m, p, [[-8, 16]])
     m, p = tables(rng, 2, 32, 32, 8, MAX_STEPS, 3, 1); add("k_max", 32, 32, 8, 1, m, p, rand_shifts(MAX_STEPS, 8))
+    # Patch sizes that are no multiple of 4 (a group of four pixels can lie across two patches) on non-square frames, a 2 x 4, a 4 x 2 and a 2 x 2 grid.  Their
+    # tables come from a generator of their own, drawn after everything above: the sixteen cases above do not change.  Each has an sx that is a multiple of 4
+    # and one that is not, a point whose destination leaves the grid, and a cell that two steps write to (asserted in run_kernel_cases).
+    rng2 = np.random.Generator(np.random.PCG64(20250117))
+    m, p = tables(rng2, 2, 12, 24, 6, 3, 3, 1); add("p6_12x24", 12, 24, 6, 1, m, p, [[6, 8], [-7, 7], [3, -4]])
+    m, p = tables(rng2, 2, 24, 12, 6, 2, 3, 0); add("p6_24x12", 24, 12, 6, 0, m, p, [[-6, 4], [-11, -7]])
+    m, p = tables(rng2, 2, 24, 24, 12, 4, 2, 1); add("p12_24x24", 24, 24, 12, 1, m, p, [[12, 0], [0, -12], [-5, 16], [13, 7]])
     return out
+
+
+NON_MULTIPLE_OF_4_CASES = ("p6_12x24", "p6_24x12", "p12_24x24")
+
+
+def leaving_destinations(case):
+    """Number of (movie, step, point) triples of frame `frame` whose destination cell is outside the grid."""
+    H, W, P, f = case["H"], case["W"], case["P"], case["frame"] % 2
+    gh, gw = H // P, W // P
+    n = gh * gw
+    count = 0
+    for k, (sy, sx) in enumerate(case["shifts"]):
+        my, mx = int(np.sign(sy)) * (abs(sy) // P), int(np.sign(sx)) * (abs(sx) // P)
+        for b in range(case["points"].shape[0]):
+            for c in np.flatnonzero(case["points"][b, f * n:(f + 1) * n, k]):
+                count += not (0 <= c // gw + my < gh and 0 <= c % gw + mx < gw)
+    return count
 
 
 def overlapping_destinations(case):
@@ -164,6 +188,11 @@ def run_kernel_cases(ns, out):
               % (tag, len(c["shifts"]), moved, zeros, overlap, (~mask_ps).sum(1).tolist()))
     assert total_zero > 0 and total_overlap > 0, (total_zero, total_overlap)
     assert meta["border_subpatch"]["zeros"] > 0 and meta["overlap"]["overlap"] > 0 and meta["k_max"]["K"] == MAX_STEPS
+    for tag in NON_MULTIPLE_OF_4_CASES:
+        sx = [s[1] for s in cases[tag]["shifts"]]
+        assert cases[tag]["P"] % 4 != 0 or tag == "p12_24x24"
+        assert meta[tag]["K"] >= 2 and any(v % 4 == 0 for v in sx) and any(v % 4 != 0 for v in sx), tag
+        assert meta[tag]["zeros"] > 0 and meta[tag]["overlap"] > 0 and leaving_destinations(cases[tag]) > 0, (tag, meta[tag], leaving_destinations(cases[tag]))
     out["cases"] = np.array(json.dumps(meta))
     out["max_steps"] = np.array(MAX_STEPS)
 
@@ -264,6 +293,16 @@ def main():
     run_shift_forms(ns, out)
     run_e2e(ns, out)
     path = os.path.join(HERE, "multi_shift.npz")
+    if os.path.exists(path):
+        # what the fixture held before this run comes out byte for byte: every array but the JSON index of the cases, and that index entry by entry
+        old = np.load(path)
+        for k in old.files:
+            if k != "cases":
+                assert k in out and np.asarray(out[k]).dtype == old[k].dtype and np.asarray(out[k]).shape == old[k].shape \
+                    and np.asarray(out[k]).tobytes() == old[k].tobytes(), "array %s of the existing multi_shift.npz changed" % k
+        old_meta, new_meta = json.loads(str(old["cases"])), json.loads(str(out["cases"]))
+        assert list(new_meta)[:len(old_meta)] == list(old_meta) and all(new_meta[t] == old_meta[t] for t in old_meta), "a recorded case changed"
+        print("[golden] multi_shift.npz: all %d existing arrays byte-identical, %d new" % (len(old.files), len(out) - len(old.files)))
     np.savez_compressed(path, **out)
     print("[golden] multi_shift.npz %.0f kB" % (os.path.getsize(path) / 1024))
 

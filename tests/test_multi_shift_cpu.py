@@ -13,7 +13,8 @@ from test_motion_sampling_cpu import GOLDEN, TINY
 
 FIXTURE = os.path.join(GOLDEN, "multi_shift.npz")
 REQUIRED_CASES = ["p8_random", "p4_random_frame0", "wide_k4", "border_subpatch", "negative_subpatch", "axis_and_zero_steps", "odd_sx", "sx_multiples_of_4",
-                  "chain", "overlap", "leaves_frame", "frame_minus1", "no_points", "base_mask_2d", "k1", "k_max"]
+                  "chain", "overlap", "leaves_frame", "frame_minus1", "no_points", "base_mask_2d", "k1", "k_max",
+                  "p6_12x24", "p6_24x12", "p12_24x24"]
 
 
 def load_cases():
@@ -92,7 +93,7 @@ def test_fixture_shapes_and_non_vacuity():
         Nt = 2 * (H // P) * (W // P)
         x = input_frames(2, H, W)
         x_p, mask_ps, masks, shifts = g["case_%s_x_p" % tag], g["case_%s_mask_ps" % tag], g["case_%s_masks" % tag], g["case_%s_shifts" % tag]
-        assert (H, W) in ((32, 32), (32, 48)) and x_p.shape == x.shape and x_p.dtype == np.float32 and mask_ps.shape == (2, Nt) and mask_ps.dtype == bool, tag
+        assert (H, W) in ((32, 32), (32, 48), (12, 24), (24, 12), (24, 24)) and x_p.shape == x.shape and x_p.dtype == np.float32 and mask_ps.shape == (2, Nt) and mask_ps.dtype == bool, tag
         assert shifts.shape == (K, 2) and np.abs(shifts).max() < min(H, W) and masks.shape in ((2, Nt, K), (2, Nt)), tag
         assert (("case_%s_points" % tag) in g.files) == c["has_points"] and (not c["has_points"] or g["case_%s_points" % tag].shape == (2, Nt, K))
         f = c["frame"] % 2
@@ -109,6 +110,12 @@ def test_fixture_shapes_and_non_vacuity():
     assert [list(r) for r in g["case_axis_and_zero_steps_shifts"]] == [[0, 11], [-9, 0], [0, 0]]
     # leaves_frame: the token whose destination is outside the grid is gone, the other one arrived
     assert (~g["case_leaves_frame_mask_ps"]).sum(1).tolist() == [1, 1]
+    # patch sizes the 16-byte path cannot assume, on non-square grids: K >= 2, an sx that is a multiple of 4 and one that is not, zeros from outside the
+    # frame, a cell two steps write to
+    assert [(meta[t]["H"], meta[t]["W"], meta[t]["P"]) for t in ("p6_12x24", "p6_24x12", "p12_24x24")] == [(12, 24, 6), (24, 12, 6), (24, 24, 12)]
+    for t in ("p6_12x24", "p6_24x12", "p12_24x24"):
+        sx = g["case_%s_shifts" % t][:, 1]
+        assert meta[t]["K"] >= 2 and (sx % 4 == 0).any() and (sx % 4 != 0).any() and meta[t]["zeros"] > 0 and meta[t]["overlap"] > 0, t
     # the end-to-end record: two movies, S = 4 rows of K = 3 steps, rectangular masks
     for movie in (0, 1):
         t = "e2e_m%d_" % movie
