@@ -530,6 +530,7 @@ SIGNATURES = {
     "cwm_model_missing_weights": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "cwm_forward": (C.c_int, [C.c_void_p, C.POINTER(CwmForwardArgs)]),
     "cwm_model_set_lanes": (C.c_int, [C.c_void_p, C.c_int]),
+    "cwm_model_set_ragged": (C.c_int, [C.c_void_p, C.c_int]),
     "cwm_model_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "cwm_conj_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "cwm_conj_create": (C.c_int, [C.POINTER(CwmConjConfig), C.POINTER(C.c_void_p)]),
@@ -549,6 +550,7 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     ),
     "cwm_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "cwm_attention_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "cwm_layernorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "cwm_mask_to_perm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_unembed": (

@@ -22,7 +22,10 @@
 
 namespace cwm {
 
-template <int PLANES>
+// RAGGED (AttnParams.key_len): batch row b attends to keys [0, key_len[b]) -- the key loop, the clamp of the staged rows and the mask of the last tile
+// take that length where the rectangular kernel takes n_tok, which stays the row stride.  A compile-time variant: with RAGGED = false every
+// `if constexpr` below leaves the rectangular kernel's code.
+template <int PLANES, bool RAGGED = false>
 __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnParams p) {
     constexpr int TILE_BYTES = 64 * 64 * 2;              // one 64x64 bf16 tile
     constexpr int STAGE_BYTES = TILE_BYTES * 2 * PLANES;  // K planes, then V^T planes
@@ -35,16 +38,26 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnParams p) {
     const int N = p.n_tok;
     int qt, bh;
     attn_tile_of_block(p.n_q > 0 ? p.n_q : p.n_tok, 128, p.remap != 0, qt, bh);
-    if (attention_is_split_tail(p, qt, gridDim.x, p.n_q > 0 ? p.n_q : p.n_tok)) {  // ragged last tile of <= 32 rows: the four waves split the keys
-        attention_tail_block<PLANES>(p, smem, bh, qt * 128, p.n_q > 0 ? p.n_q : p.n_tok);
-        return;
+    if constexpr (!RAGGED) {
+        if (attention_is_split_tail(p, qt, gridDim.x, p.n_q > 0 ? p.n_q : p.n_tok)) {  // ragged last tile of <= 32 rows: the four waves split the keys
+            attention_tail_block<PLANES>(p, smem, bh, qt * 128, p.n_q > 0 ? p.n_q : p.n_tok);
+            return;
+        }
     }
     const int b = bh / p.heads, h = bh - b * p.heads;
+    int NK = N;  // keys of this batch row
+    if constexpr (RAGGED) {
+        NK = p.key_len[b];
+        // a query tile wholly past the row's length has nothing to write; a length outside [1, N] is the caller's error (reported by whoever
+        // filled key_len): no key loop, no store.  Uniform over the workgroup and ahead of the first barrier.
+        if (NK < 1 || NK > N || qt * 128 >= NK) return;
+    }
     const int q0 = qt * 128 + wave * 32;
     // a wave whose 32 query rows all lie past the sequence end (N = 792: three of the 28 wave slots per head) only helps to
     // stage the K / V tiles: its MFMA / softmax work is skipped, leaving the matrix pipe to the co-resident workgroup
     const int NQ = p.n_q > 0 ? p.n_q : p.n_tok;  // queries are rows [q_off, q_off + NQ) (last decoder block: the masked tokens only)
-    const bool active = q0 < NQ;
+    const int QL = RAGGED ? NK : NQ;  // query rows that are computed and stored (ragged launches have n_q == 0: NQ == N >= NK)
+    const bool active = q0 < QL;
 
     const bf16* Qb = p.q + (size_t)bh * N * 64;
     const bf16* Kb = p.k + (size_t)bh * N * 64;
@@ -52,11 +65,11 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnParams p) {
 
     // ---- Q fragments (B operand): lane (q = qcol, half hh) holds Q[q][16 s + 8 hh + 0..7] --------
     bf16x8 qf[PLANES][4];
-    load_q_fragments<PLANES>(qf, Qb, p.qk_plane, p.q_off + min(q0 + qcol, NQ - 1), hh);
+    load_q_fragments<PLANES>(qf, Qb, p.qk_plane, p.q_off + min(q0 + qcol, QL - 1), hh);
 
     KvStage<PLANES, 1> st;  // register-staged K / V tile (attention_device.h)
     st.init(tid);
-    auto load_tiles = [&](int kt) { st.load(0, Kb, Vb, p.qk_plane, kt, N); };
+    auto load_tiles = [&](int kt) { st.load(0, Kb, Vb, p.qk_plane, kt, NK); };
     auto store_tiles = [&](int stage) { st.store(0, smem + stage * STAGE_BYTES); };
 
     // ---- fragment read offsets -------------------------------------------------------------------
@@ -77,7 +90,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnParams p) {
     float m_run = -1e30f, l_run = 0.f;
     const float kLog2e = 1.4426950408889634f;
 
-    const int nkt = (N + 63) / 64;
+    const int nkt = (NK + 63) / 64;
     load_tiles(0);
     store_tiles(0);
     __syncthreads();
@@ -127,9 +140,9 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnParams p) {
 
         // ---- online softmax (per query column; lanes l and l^32 share a query) ------------------
         if constexpr (LAST) {
-            if (N & 63) {
+            if (NK & 63) {
 #pragma unroll
-                for (int kb = 0; kb < 2; ++kb) mask_rows_from(sacc[kb], kt * 64 + kb * 32, hh, N);
+                for (int kb = 0; kb < 2; ++kb) mask_rows_from(sacc[kb], kt * 64 + kb * 32, hh, NK);
             }
         }
         float mx = sacc[0][0];
@@ -184,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnParams p) {
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
     const int q = q0 + qcol;
-    if (q < NQ) {
+    if (q < QL) {
         const int64_t orow = (int64_t)b * NQ + q;
 #pragma unroll
         for (int db = 0; db < 2; ++db) store_o_block<PLANES>(p.o, orow, p.ldo, h * 64 + db * 32, oacc[db], inv, hh);
@@ -202,6 +215,7 @@ int launch_attention(const AttnParams& p_in, int planes, hipStream_t stream) {
     CWM_REQUIRE(p.ldo % 4 == 0, "attention: ldo must be a multiple of 4");
     CWM_REQUIRE((int64_t)p.n_tok * 128 < (1ll << 31), "attention: %d tokens exceed the 32-bit tile offsets within one (batch, head)", p.n_tok);
     CWM_REQUIRE(p.q_off >= 0 && p.n_q >= 0 && p.q_off + p.n_q <= p.n_tok, "attention: query rows [%d, %d) outside the %d tokens", p.q_off, p.q_off + p.n_q, p.n_tok);
+    CWM_REQUIRE(!p.key_len || p.n_q == 0, "attention: per-row key counts (key_len) go with queries over all rows (n_q = 0), got n_q = %d", p.n_q);
     const int nqb = ((p.n_q > 0 ? p.n_q : p.n_tok) + 127) / 128;
     // Measured (tools/microbench.py attn_sweep / attn, MI355X, round 6: profiles/r6_microbench_attn_sweep.log, r6_microbench_attn.log -- 12 heads, ~2.4e8 score
     // elements per launch at every length):
@@ -218,11 +232,18 @@ int launch_attention(const AttnParams& p_in, int planes, hipStream_t stream) {
     CWM_REQUIRE(kern == 1, "attention: unknown kernel %d (1: 4-wave, 3: software-pipelined)", kern);
     const dim3 grid(nqb, p.batch * p.heads);
     const size_t smem = (size_t)2 * (64 * 64 * 2) * 2 * planes;
-    if (planes == 1) {
-        hipLaunchKernelGGL(attention_kernel<1>, grid, dim3(256), smem, stream, p);
+    if (p.key_len) {
+        if (planes == 1) {
+            hipLaunchKernelGGL((attention_kernel<1, true>), grid, dim3(256), smem, stream, p);
+        } else {
+            if (int rc = cwm_set_max_lds((const void*)attention_kernel<2, true>, (int)smem)) return rc;
+            hipLaunchKernelGGL((attention_kernel<2, true>), grid, dim3(256), smem, stream, p);
+        }
+    } else if (planes == 1) {
+        hipLaunchKernelGGL((attention_kernel<1>), grid, dim3(256), smem, stream, p);
     } else {
         if (int rc = cwm_set_max_lds((const void*)attention_kernel<2>, (int)smem)) return rc;
-        hipLaunchKernelGGL(attention_kernel<2>, grid, dim3(256), smem, stream, p);
+        hipLaunchKernelGGL((attention_kernel<2>), grid, dim3(256), smem, stream, p);
     }
     CWM_HIP_CHECK(hipGetLastError());
     return 0;

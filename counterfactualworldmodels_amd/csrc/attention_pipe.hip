@@ -277,7 +277,12 @@ __device__ __forceinline__ void pipe_tile(PipeWave<PLANES>& w, f32x16 (&sc)[2], 
 
 }  // namespace
 
-template <int PLANES, int NW>
+// RAGGED (AttnParams.key_len): batch row b attends to keys [0, key_len[b]).  That length stands where the rectangular kernel has n_tok in everything
+// that counts keys -- the number of key tiles, the row clamp of the staged tiles (rows past the length re-read the row's last valid key, so what the
+// padding rows hold, NaN included, never reaches LDS), the mask and the half-tile skips of the last tile -- while n_tok stays the row stride.  The two
+// schedule refinements that depend on the length (the key-split ragged query tile, the key-split last round) are off for these launches.  A
+// compile-time variant: with RAGGED = false every `if constexpr` below leaves the rectangular kernel's code.
+template <int PLANES, int NW, bool RAGGED = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_pipe_kernel(const AttnParams p) {
     constexpr int TILE_BYTES = 64 * 64 * 2;         // one 64x64 bf16 tile
     constexpr int SLOT_BYTES = TILE_BYTES * PLANES;  // hi [, lo] planes of one K or V tile
@@ -307,15 +312,24 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_pipe_kerne
     }
     int qt, bh;
     attn_tile_of_item(item, p.ks_nqb, p.batch * p.heads, NQ, 32 * NW, p.remap != 0, qt, bh);
-    if constexpr (NW == 4) {
+    if constexpr (NW == 4 && !RAGGED) {
         if (attention_is_split_tail(p, qt, p.ks_nqb, NQ)) {  // ragged last tile of <= 32 rows: the four waves split the keys (attention_tail.h)
             attention_tail_block<PLANES>(p, smem, bh, qt * 128, NQ);
             return;
         }
     }
     const int b = bh / p.heads, h = bh - b * p.heads;
+    int NK = N;  // keys of this batch row
+    if constexpr (RAGGED) {
+        NK = p.key_len[b];
+        // a query tile wholly past the row's length has nothing to write; a length outside [1, N] is the caller's error (reported by whoever
+        // filled key_len): no key loop, no store.  Uniform over the workgroup and ahead of the first barrier.
+        if (NK < 1 || NK > N || qt * (32 * NW) >= NK) return;
+        nkt = (NK + 63) / 64;  // (launch_pipe keeps the key-split round off: kt0 = 0 and this workgroup has the whole key range)
+    }
+    const int QL = RAGGED ? NK : NQ;  // query rows that are computed and stored (ragged launches have n_q == 0: NQ == N >= NK)
     const int q0 = qt * (32 * NW) + wave * 32;
-    const bool active = q0 < NQ;  // idle waves (query rows past the end) only stage tiles and keep the barrier count
+    const bool active = q0 < QL;  // idle waves (query rows past the end) only stage tiles and keep the barrier count
 
     const bf16* Qb = p.q + (size_t)bh * N * 64;
     const bf16* Kb = p.k + (size_t)bh * N * 64;
@@ -323,7 +337,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_pipe_kerne
 
     PipeWave<PLANES> w;
     w.hh = hh;
-    load_q_fragments<PLANES>(w.qf, Qb, p.qk_plane, p.q_off + min(q0 + qcol, NQ - 1), hh);
+    load_q_fragments<PLANES>(w.qf, Qb, p.qk_plane, p.q_off + min(q0 + qcol, QL - 1), hh);
 
     // ---- LDS-DMA bookkeeping: piece = 8 key rows x 128 B; lane l lands at chunk l % 8 of row l / 8 ----
     int st_lds[NP], st_koff[NP], st_voff[NP];  // LDS offset of the piece; byte offset of the lane's 16-byte chunk inside a K / V tile
@@ -341,7 +355,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_pipe_kerne
     // CLAMP: the tile may be the last one of a ragged sequence -- rows past the end re-read the last key (P is exactly 0 there).
     // The steady-state loop stages tiles that cannot be the last one and pays a single v_add per piece.
     auto tile_off = [&](int kt, int toff, auto clamp_c) -> unsigned {
-        if constexpr (decltype(clamp_c)::value) return (unsigned)(min(kt * 64 + (toff >> 7), N - 1) * 128 + (toff & 127));
+        if constexpr (decltype(clamp_c)::value) return (unsigned)(min(kt * 64 + (toff >> 7), NK - 1) * 128 + (toff & 127));
         else return (unsigned)(kt * 8192 + toff);
     };
     // key tile kt -> ring slot `slot` (0 / 1)
@@ -398,7 +412,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_pipe_kerne
         };                                                                                                                             \
         PROF_T(0);                                                                                                                     \
         if (active) {                                                                                                                  \
-            pipe_tile<PLANES, KIND, 2 * NP>(w, SC, SN, smem + (ks_ ^ 1) * SLOT_BYTES, v_addr[0] + ks_ * SLOT_BYTES, v_addr[1] + ks_ * SLOT_BYTES, kt_, N,  \
+            pipe_tile<PLANES, KIND, 2 * NP>(w, SC, SN, smem + (ks_ ^ 1) * SLOT_BYTES, v_addr[0] + ks_ * SLOT_BYTES, v_addr[1] + ks_ * SLOT_BYTES, kt_, NK, \
                                             (KIND) == TILE_PENULT && half_last, half_last, dma PROF_ARGS);                             \
         } else {                                                                                                                       \
             if ((KIND) == TILE_STEADY) stage_k(kt_ + 2, ks_);                                                                          \
@@ -418,7 +432,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_pipe_kerne
 #define PROF_ARGS
 #endif
     // the sequence's last key tile is in this workgroup's range and at most half full (pipe_tile: half_next / half_this)
-    const bool half_last = nkt == nkt_all && ((N - 1) & 63) < 32;
+    const bool half_last = (RAGGED || nkt == nkt_all) && ((NK - 1) & 63) < 32;
 
     // ---- normalise and store O[q][h*64 + d] (or, key-split tail round: leave (O^T unnormalised, running max, sum) of this key range for
     // attention_combine_kernel) ----
@@ -442,7 +456,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_pipe_kerne
             return;
         }
         const float inv = 1.0f / l_tot;
-        if (q < NQ) {
+        if (q < QL) {
             const int64_t orow = (int64_t)b * NQ + q;
 #pragma unroll
             for (int db = 0; db < 2; ++db) store_o_block<PLANES>(p.o, orow, p.ldo, h * 64 + db * 32, w.oacc[db], inv, hh);
@@ -573,7 +587,7 @@ static int ksplit_scratch(hipStream_t stream, float** out) {
     return 0;
 }
 
-template <int PLANES, int NW>
+template <int PLANES, int NW, bool RAGGED = false>
 static int launch_pipe(const AttnParams& p_in, hipStream_t stream) {
     AttnParams p = p_in;
     const int nq = p.n_q > 0 ? p.n_q : p.n_tok;
@@ -585,7 +599,7 @@ static int launch_pipe(const AttnParams& p_in, hipStream_t stream) {
     p.ks_parts = 0;
     p.ks_scratch = nullptr;
     int extra = 0;
-    if (NW == 4 && (p.tune ? p.tune->attn_ksplit : 1)) {
+    if (NW == 4 && !RAGGED && (p.tune ? p.tune->attn_ksplit : 1)) {
         // a last round that fills at most a quarter of the slots (two workgroups per CU) costs most of a workgroup period for a fraction of a
         // round's work: split its items' keys.  Measured (profiles/r4_microbench_attn_ksplit.log): ViT-L/4 decoder (3136 items = 6 rounds + 64,
         // 8 ranges) 1646 -> 1597 us parity, 766 -> 753 us fast; a last round of 128 items in 4 ranges (ViT-L/4 encoder) gains nothing -- the
@@ -609,8 +623,8 @@ static int launch_pipe(const AttnParams& p_in, hipStream_t stream) {
     const unsigned grid = (unsigned)(n_items + extra);
     const size_t smem = (size_t)4 * (64 * 64 * 2) * PLANES;  // 2 K slots + 2 V slots
     if (smem > 48 * 1024)
-        if (int rc = cwm_set_max_lds((const void*)attention_pipe_kernel<PLANES, NW>, (int)smem)) return rc;
-    hipLaunchKernelGGL((attention_pipe_kernel<PLANES, NW>), dim3(grid), dim3(64 * NW), smem, stream, p);
+        if (int rc = cwm_set_max_lds((const void*)attention_pipe_kernel<PLANES, NW, RAGGED>, (int)smem)) return rc;
+    hipLaunchKernelGGL((attention_pipe_kernel<PLANES, NW, RAGGED>), dim3(grid), dim3(64 * NW), smem, stream, p);
     if (p.ks_parts > 0)
         hipLaunchKernelGGL((attention_combine_kernel<PLANES>), dim3((unsigned)((n_items - p.ks_main) * 32)), dim3(256), 0, stream, p);
     CWM_HIP_CHECK(hipGetLastError());
@@ -620,6 +634,7 @@ static int launch_pipe(const AttnParams& p_in, hipStream_t stream) {
 // 4 waves: 128 queries per workgroup, two workgroups per CU.  (8 waves -- 256 queries, one workgroup per CU, half the
 // LDS-DMA work per query -- measured 5-15 % slower: the barrier then couples all eight waves of the CU.)
 int launch_attention_pipe(const AttnParams& p, int planes, hipStream_t stream) {
+    if (p.key_len) return planes == 1 ? launch_pipe<1, 4, true>(p, stream) : launch_pipe<2, 4, true>(p, stream);
     return planes == 1 ? launch_pipe<1, 4>(p, stream) : launch_pipe<2, 4>(p, stream);
 }
 

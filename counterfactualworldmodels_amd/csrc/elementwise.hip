@@ -112,7 +112,8 @@ __device__ __forceinline__ int block_exclusive_scan256(int count, int* wave_tot,
     return before;
 }
 
-__global__ __launch_bounds__(256) void mask_to_perm_kernel(const uint8_t* mask, int Nt, int n_vis, int* perm, int* err) {
+// Ragged batches (n_vis_min > 0): a row may have n_vis_min .. n_vis visible tokens, and its count goes to counts[b].
+__global__ __launch_bounds__(256) void mask_to_perm_kernel(const uint8_t* mask, int Nt, int n_vis, int* perm, int* err, int n_vis_min, int* counts) {
     __shared__ int wave_tot[4];
     const int b = blockIdx.x, t = threadIdx.x;
     const uint8_t* m = mask + (size_t)b * Nt;
@@ -122,7 +123,8 @@ __global__ __launch_bounds__(256) void mask_to_perm_kernel(const uint8_t* mask, 
     for (int i = lo; i < hi; ++i) c += (m[i] == 0);
     int tv;
     int vis_before = block_exclusive_scan256(c, wave_tot, tv);
-    if (t == 0 && tv != n_vis) atomicExch(err, 1);
+    if (t == 0 && (n_vis_min > 0 ? (tv < n_vis_min || tv > n_vis) : tv != n_vis)) atomicExch(err, 1);
+    if (t == 0 && counts) counts[b] = tv;
     int* pr = perm + (size_t)b * Nt;
     for (int i = lo; i < hi; ++i) {
         if (m[i] == 0) {
@@ -135,7 +137,14 @@ __global__ __launch_bounds__(256) void mask_to_perm_kernel(const uint8_t* mask, 
 }
 
 int launch_mask_to_perm(const uint8_t* mask, int B, int Nt, int n_vis, int* perm, int* err, hipStream_t stream) {
-    hipLaunchKernelGGL(mask_to_perm_kernel, dim3(B), dim3(256), 0, stream, mask, Nt, n_vis, perm, err);
+    hipLaunchKernelGGL(mask_to_perm_kernel, dim3(B), dim3(256), 0, stream, mask, Nt, n_vis, perm, err, 0, (int*)nullptr);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_mask_to_perm_ragged(const uint8_t* mask, int B, int Nt, int n_vis_min, int n_vis, int* perm, int* err, int* counts, hipStream_t stream) {
+    CWM_REQUIRE(n_vis_min > 0 && n_vis_min <= n_vis && counts, "mask_to_perm (ragged): bad argument");
+    hipLaunchKernelGGL(mask_to_perm_kernel, dim3(B), dim3(256), 0, stream, mask, Nt, n_vis, perm, err, n_vis_min, counts);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -294,7 +303,7 @@ int launch_flow_rgb_gather(const FlowRgbGatherParams& p, int planes, hipStream_t
 // ---------------------------------------------------------------------------------------------
 template <int PLANES>
 __global__ __launch_bounds__(256) void index_gather_kernel(const PatchGatherParams p, const uint8_t* __restrict__ mask, int n_vis, int* __restrict__ perm_out,
-                                                           int* __restrict__ rank_out, int* __restrict__ err_rows) {
+                                                           int* __restrict__ rank_out, int* __restrict__ err_rows, int n_vis_min, int* __restrict__ counts) {
     extern __shared__ int vis_tab[];  // [n_rows]
     __shared__ int wave_tot[4];
     const int b = blockIdx.y, t = threadIdx.x;
@@ -354,7 +363,12 @@ __global__ __launch_bounds__(256) void index_gather_kernel(const PatchGatherPara
     } else {
         for (int i = lo; i < hi; ++i) emit(i, m[i] == 0);
     }
-    if (blockIdx.x == 0 && t == 0) err_rows[b] = total_vis != n_vis ? 1 : 0;
+    // (ragged batches, n_vis_min > 0: n_vis is the cap; the rows of a sample behind its count are gathered as pad slots -- zeros -- and are padding
+    // all through the encoder)
+    if (blockIdx.x == 0 && t == 0) {
+        err_rows[b] = (n_vis_min > 0 ? (total_vis < n_vis_min || total_vis > n_vis) : total_vis != n_vis) ? 1 : 0;
+        if (counts) counts[b] = total_vis;
+    }
     __syncthreads();
 
     const int per_row = p.C * p.P;
@@ -366,7 +380,9 @@ __global__ __launch_bounds__(256) void index_gather_kernel(const PatchGatherPara
     }
 }
 
-int launch_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_vis, int* perm, int* rank, int* err_rows, int planes, hipStream_t stream) {
+int launch_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_vis, int* perm, int* rank, int* err_rows, int planes, hipStream_t stream,
+                        int n_vis_min, int* counts) {
+    CWM_REQUIRE(n_vis_min == 0 || (n_vis_min > 0 && n_vis_min <= n_vis && counts), "index_gather: ragged rows need 0 < n_vis_min <= n_vis and a count array");
     CWM_REQUIRE(p.P % 4 == 0 && p.W % 4 == 0, "index_gather: patch size and width must be multiples of 4");
     CWM_REQUIRE(p.C == 3 || !p.normalize, "index_gather: imagenet normalisation needs 3 channels");
     CWM_REQUIRE(p.ld >= p.C * p.P * p.P && p.ld % 4 == 0, "index_gather: bad ld");
@@ -377,9 +393,9 @@ int launch_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_v
     const dim3 grid((unsigned)per_sample, (unsigned)p.B);
     const size_t smem = (size_t)p.n_rows * sizeof(int);
     if (planes == 1)
-        hipLaunchKernelGGL(index_gather_kernel<1>, grid, dim3(256), smem, stream, p, mask, n_vis, perm, rank, err_rows);
+        hipLaunchKernelGGL(index_gather_kernel<1>, grid, dim3(256), smem, stream, p, mask, n_vis, perm, rank, err_rows, n_vis_min, counts);
     else
-        hipLaunchKernelGGL(index_gather_kernel<2>, grid, dim3(256), smem, stream, p, mask, n_vis, perm, rank, err_rows);
+        hipLaunchKernelGGL(index_gather_kernel<2>, grid, dim3(256), smem, stream, p, mask, n_vis, perm, rank, err_rows, n_vis_min, counts);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -427,6 +443,36 @@ int launch_fill_mask_tokens(float* x_full, const float* mask_token, const float*
     if (rows == 0) return 0;
     hipLaunchKernelGGL(fill_mask_tokens4_kernel, dim3((unsigned)((rows_q * (D / 4) + 255) / 256)), dim3(256), 0, stream, x_full, mask_token, pos, perm, Nt,
                        n_vis, D, rows, rows_q);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// Ragged batches: sample b has counts[b] (>= n_vis_min) visible tokens, so its mask tokens are rows [counts[b], Nt).  The encoder_to_decoder GEMM
+// before this launch wrote rows [0, cap) of every sample, padding rows [counts[b], cap) included: those are overwritten here.  One thread per four
+// columns of a row of [n_vis_min, Nt); rows below the sample's count are left alone.
+__global__ __launch_bounds__(256) void fill_mask_tokens_ragged_kernel(float* x_full, const float* mask_token, const float* pos, const int* perm,
+                                                                      const int* counts, int Nt, int n_vis_min, int D, int64_t total) {
+    const int d4 = D / 4;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= total) return;
+    const int64_t row = gid / d4;
+    const int c4 = (int)(gid - row * d4);
+    const int nm = Nt - n_vis_min;
+    const int b = (int)(row / nm), j = n_vis_min + (int)(row - (int64_t)b * nm);
+    if (j < counts[b]) return;
+    const size_t orow = (size_t)b * Nt + j;
+    const float4 mt = *reinterpret_cast<const float4*>(mask_token + c4 * 4);
+    const float4 pe = *reinterpret_cast<const float4*>(pos + (size_t)perm[orow] * D + c4 * 4);
+    *reinterpret_cast<float4*>(x_full + orow * D + c4 * 4) = make_float4(mt.x + pe.x, mt.y + pe.y, mt.z + pe.z, mt.w + pe.w);
+}
+
+int launch_fill_mask_tokens_ragged(float* x_full, const float* mask_token, const float* pos, const int* perm, const int* counts, int B, int Nt, int n_vis_min,
+                                   int D, hipStream_t stream) {
+    CWM_REQUIRE(D % 4 == 0 && counts && n_vis_min > 0 && n_vis_min <= Nt, "fill_mask_tokens (ragged): bad argument");
+    const int64_t total = (int64_t)B * (Nt - n_vis_min) * (D / 4);
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(fill_mask_tokens_ragged_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x_full, mask_token, pos, perm, counts, Nt,
+                       n_vis_min, D, total);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }

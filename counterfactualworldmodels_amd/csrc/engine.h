@@ -181,7 +181,8 @@ struct Engine {
     // the HBM-bound edge kernels, booked by class with their algorithmic bytes (cwm_hip.h CWM_KCLASS_*)
     int run_layernorm(const LayerNormParams& p, int planes, hipStream_t s);
     int run_patch_gather(const PatchGatherParams& p, int planes, hipStream_t s);
-    int run_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_vis, int* perm, int* rank, int* err_rows, int planes, hipStream_t s);
+    int run_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_vis, int* perm, int* rank, int* err_rows, int planes, hipStream_t s,
+                         int n_vis_min = 0, int* counts = nullptr);  // (n_vis_min > 0: ragged batches, kernels.h launch_index_gather)
     int run_fill_mask_tokens(float* x_full, const float* mask_token, const float* pos, const int* perm, int B, int Nt, int n_vis, int D, hipStream_t s);
     int run_unembed(const UnembedParams& p, hipStream_t s);
     // `launch()` between an event pair of class `kclass` (no events unless the class is enabled); work = FLOPs or bytes
@@ -204,12 +205,15 @@ struct Engine {
     int run_mlp(const float* ln_g, const float* ln_b, const LinearW& fc1, const LinearW& fc2, float* x, int B, int n_tok, int D, int planes, StreamBuffers& sb,
                 hipStream_t s, int n_keep = 0);
     // Block.forward (VideoMAE/utils.py:146-153) on a residual stream x[B*n_tok, D] (in place), head_dim 64
-    int run_block(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s, int n_keep = 0);
+    // key_len (device, [B]; nullptr: all n_tok): the keys sample b attends to -- the encoder blocks of a ragged batch (AttnParams.key_len)
+    int run_block(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s, int n_keep = 0,
+                  const int* key_len = nullptr);
     // same for short sequences with any head_dim (fp32 VALU attention): the IMU context stream
     int run_block_small(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s);
     // the pieces of a stream's forward around its blocks, over B samples of n_vis visible rows each (w: the lane's view)
     int embed_stream(const StreamW& S, const StreamWs& w, int B, int n_vis, int planes, hipStream_t s);
-    int to_decoder(const StreamW& S, const StreamWs& w, int B, int n_vis, int planes, hipStream_t s);
+    // counts (device, [B]; nullptr: every sample has n_vis): sample b has counts[b] in [n_vis_min, n_vis] encoder rows, mask tokens from there on
+    int to_decoder(const StreamW& S, const StreamWs& w, int B, int n_vis, int planes, hipStream_t s, const int* counts = nullptr, int n_vis_min = 0);
     // out[B][n_out][head.N] = head(norm(x_dec[:, -n_out:]))
     int head_rows(const StreamW& S, const StreamWs& w, int B, int n_out, float* out, int planes, hipStream_t s);
 

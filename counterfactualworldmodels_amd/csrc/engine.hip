@@ -492,11 +492,12 @@ int Engine::run_patch_gather(const PatchGatherParams& p, int planes, hipStream_t
     return timed(CWM_KCLASS_PATCH_GATHER, (double)p.B * p.n_rows * p.C * p.P * p.P * (4.0 + 2.0 * planes), s, [&] { return launch_patch_gather(p, planes, s); });
 }
 
-int Engine::run_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_vis, int* perm, int* rank, int* err_rows, int planes, hipStream_t s) {
+int Engine::run_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_vis, int* perm, int* rank, int* err_rows, int planes, hipStream_t s,
+                             int n_vis_min, int* counts) {
     // booked with the patch gather's class and bytes (+ the mask row in, the permutation and its inverse out)
     const int L = p.perm_stride ? p.perm_stride : p.Nt;
     return timed(CWM_KCLASS_PATCH_GATHER, (double)p.B * p.n_rows * p.C * p.P * p.P * (4.0 + 2.0 * planes) + (double)p.B * L * (1.0 + 4.0 + (rank ? 4.0 : 0.0)), s,
-                 [&] { return launch_index_gather(p, mask, n_vis, perm, rank, err_rows, planes, s); });
+                 [&] { return launch_index_gather(p, mask, n_vis, perm, rank, err_rows, planes, s, n_vis_min, counts); });
 }
 
 int Engine::run_fill_mask_tokens(float* x_full, const float* mask_token, const float* pos, const int* perm, int B, int Nt, int n_vis, int D,
@@ -623,7 +624,7 @@ int Engine::run_mlp(const float* ln_g, const float* ln_b, const LinearW& fc1, co
 // n_keep (0 = all): only the LAST n_keep tokens of every sample are needed downstream (the last decoder block: the decoder returns
 // head(norm(x[:, -Nm:])), vmae.py:250-251).  Keys / values still come from all tokens; queries, proj, LN2 and the MLP run on the
 // kept rows only (compact activations, residual rows addressed with an offset).  Kept rows are bit-identical to the full block.
-int Engine::run_block(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s, int n_keep) {
+int Engine::run_block(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s, int n_keep, const int* key_len) {
     const int M = B * n_tok;
     const int64_t hplane = (int64_t)M * D;
     const KeptRows kr(n_tok, n_keep);
@@ -644,6 +645,8 @@ int Engine::run_block(const BlockW& w, float* x, int B, int n_tok, int D, int H,
     a.q = sb.qbuf; a.k = sb.kbuf; a.v = sb.vbuf; a.qk_plane = hplane;
     a.o = sb.hbuf; a.o_plane = (int64_t)B * kr.n_out * D; a.ldo = D; a.n_tok = n_tok; a.heads = H; a.batch = B;
     if (kr.part) { a.q_off = kr.first; a.n_q = kr.n_out; }
+    // (ragged batch: O rows at and past a sample's count are not written -- hbuf keeps LN1's rows there, finite padding for the row-wise launches below)
+    a.key_len = key_len;
     if ((rc = run_attention(a, planes, s))) return rc;
 
     if ((rc = residual_gemm(*this, sb.hbuf, D, w.proj, x, B, n_tok, kr, planes, s))) return rc;
@@ -686,7 +689,7 @@ int Engine::embed_stream(const StreamW& S, const StreamWs& w, int B, int n_vis, 
 }
 
 // encoder.norm, encoder_to_decoder (no bias) + pos_ext[vis] written straight into x_dec rows [0, n_vis), mask_token + pos_ext[masked] behind them
-int Engine::to_decoder(const StreamW& S, const StreamWs& w, int B, int n_vis, int planes, hipStream_t s) {
+int Engine::to_decoder(const StreamW& S, const StreamWs& w, int B, int n_vis, int planes, hipStream_t s, const int* counts, int n_vis_min) {
     const int next = S.n_slots();
     int rc;
     if ((rc = layernorm_to(w.x_enc, B * n_vis, S.enc_dim, S.enc_norm_g, S.enc_norm_b, w.sb.hbuf, planes, s))) return rc;
@@ -694,6 +697,9 @@ int Engine::to_decoder(const StreamW& S, const StreamWs& w, int B, int n_vis, in
     g.epi = EPI_F32; g.C = w.x_dec; g.ldc = S.dec_dim;
     g.resid = S.pos_dec_ext; g.ldr = S.dec_dim; g.resid_rowmap = w.perm; g.rows_in = n_vis; g.rows_out = next; g.map_stride = next;
     if ((rc = run_gemm(g, planes, s))) return rc;
+    if (counts)  // ragged batch: the GEMM above also wrote the padding rows [counts[b], n_vis) of every sample; the mask tokens start at counts[b]
+        return timed(CWM_KCLASS_FILL_MASK, (double)B * (next - n_vis_min) * S.dec_dim * 4.0, s,
+                     [&] { return launch_fill_mask_tokens_ragged(w.x_dec, S.mask_token, S.pos_dec_ext, w.perm, counts, B, next, n_vis_min, S.dec_dim, s); });
     return run_fill_mask_tokens(w.x_dec, S.mask_token, S.pos_dec_ext, w.perm, B, next, n_vis, S.dec_dim, s);  // (no launch when nothing is masked)
 }
 

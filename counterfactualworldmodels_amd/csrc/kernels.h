@@ -133,6 +133,11 @@ struct AttnParams {
     float* ks_scratch;  // [items - ks_main][ks_parts][128 queries][68]: O[64], max, sum, -, -
     int tail_split;  // set by launch_attention: a ragged last query tile of at most 32 rows splits the KEYS over its four waves (attention_tail.h; "attn_tail" switch)
     const Tuning* tune;  // execution options of the calling model (nullptr: defaults)
+    // Ragged batches (device, one entry per batch row; nullptr: every row attends to all n_tok keys -- the launch of every caller before it existed).
+    // Batch row b attends to keys [0, key_len[b]); n_tok stays the row stride and the capacity.  Query rows at and past key_len[b] are not written.
+    // A length outside [1, n_tok] makes the row's workgroups exit without a store.  Needs n_q == 0; runs the regular schedule (no key-split tail tile,
+    // no key-split last round: DESIGN.md section 8.14).  Last member, so that the offsets of the fields above are those of the rectangular launch.
+    const int* key_len;
 };
 
 int launch_attention(const AttnParams& p, int planes, hipStream_t stream);
@@ -200,10 +205,17 @@ struct FlowRgbGatherParams {
 int launch_flow_rgb_gather(const FlowRgbGatherParams& p, int planes, hipStream_t stream);
 // mask[B][L] (L = perm_stride or Nt) -> perm[B][L], rank[B][L] (inverse; may be nullptr), err_rows[b] = (visible count of row b != n_vis), and the
 // gather of the first n_rows visible tokens of every sample, in one launch (elementwise.hip index_gather_kernel); p.perm is not read
-int launch_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_vis, int* perm, int* rank, int* err_rows, int planes, hipStream_t stream);
+// Ragged batches (n_vis_min > 0): err_rows[b] = (count outside [n_vis_min, n_vis]), counts[b] = the row's visible count; rows behind it are gathered as zeros
+int launch_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_vis, int* perm, int* rank, int* err_rows, int planes, hipStream_t stream,
+                        int n_vis_min = 0, int* counts = nullptr);
+// launch_mask_to_perm for rows of n_vis_min .. n_vis visible tokens: err[0] is set for a row outside that range, counts[b] = the row's visible count
+int launch_mask_to_perm_ragged(const uint8_t* mask, int B, int Nt, int n_vis_min, int n_vis, int* perm, int* err, int* counts, hipStream_t stream);
 
 // x_full[b][n_vis + j][:] = mask_token + pos[perm[b][n_vis + j]]   (vmae.py:556-557)
 int launch_fill_mask_tokens(float* x_full, const float* mask_token, const float* pos, const int* perm, int B, int Nt, int n_vis, int D, hipStream_t stream);
+// the same for rows [counts[b], Nt) of sample b (counts[b] >= n_vis_min; rows below n_vis_min are never touched)
+int launch_fill_mask_tokens_ragged(float* x_full, const float* mask_token, const float* pos, const int* perm, const int* counts, int B, int Nt, int n_vis_min,
+                                   int D, hipStream_t stream);
 
 struct UnembedParams {
     const float* y;  // [B][Nm][P*P*C], feature order (ph, pw, c)

@@ -15,6 +15,7 @@ struct ModelWs {
     StreamWs st;
     int* rank = nullptr;  // inverse permutation, for the un-embed
     int* err = nullptr;   // one word per batch row (index_gather_kernel writes every row's, every call: no memset)
+    int* counts = nullptr;  // ragged batches (cwm_model_set_ragged): visible tokens per batch row, written by the index prologue (behind `err` in its allocation)
 };
 
 struct cwm_model {
@@ -27,6 +28,8 @@ struct cwm_model {
     // batch lanes (cwm_model_set_lanes): a batch whose slices keep >= kMinLaneRows encoder rows each runs as up to `lanes` slices, the first on the
     // caller's stream and the others on streams of `lane_set`, joined by events before cwm_forward returns control of the stream
     int lanes = 2;
+    // cwm_model_set_ragged: 0 = every row of a call has args->n_vis visible tokens; > 0 = between this many and args->n_vis
+    int ragged_min = 0;
     static constexpr int kMaxLanes = Lanes::kMax;
     Lanes lane_set;
 };
@@ -47,8 +50,10 @@ int ensure_workspace(cwm_model* m, int B, int n_vis) {
     m->ws_batch = 0;  // (nothing is usable until all of it is there again)
     int rc;
     if ((rc = E.free_workspace()) || (rc = for_each_buffer(m, m->ws, Nv, WsAlloc{E, (size_t)Bc}))) return rc;
-    // `err` is the one buffer that is not linear in the batch size (B + 4 words), so it is not part of the layout: allocated here, sliced in lane_ws
-    if ((rc = E.ws(&m->ws.err, (size_t)Bc + 4))) return rc;
+    // `err` is the one buffer that is not linear in the batch size (B + 4 words, and as many again for the rows' visible counts), so it is not part of the
+    // layout: allocated here, sliced in lane_ws
+    if ((rc = E.ws(&m->ws.err, (size_t)2 * Bc + 8))) return rc;
+    m->ws.counts = m->ws.err + Bc + 4;
     m->ws_batch = Bc;
     m->ws_nvis = Nv;
     // (the zero fills above ran on the null stream; the lane streams are non-blocking and would not wait for them)
@@ -61,6 +66,7 @@ ModelWs lane_ws(const cwm_model* m, int b0) {
     ModelWs w = m->ws;
     (void)for_each_buffer(m, w, m->ws_nvis, WsShift{(size_t)b0});
     w.err += b0;
+    w.counts += b0;
     return w;
 }
 
@@ -120,7 +126,11 @@ static int forward_lane(cwm_model* m, const cwm_forward_args* a, int b0, int B, 
     const cwm_config& c = m->cfg;
     const StreamW& S = m->st;
     StreamWs& w = lw.st;
-    const int Nt = S.n_tok, Nv = a->n_vis, Nm = Nt - Nv;
+    // ragged batch (cwm_model_set_ragged): Nv is the cap of the rows' visible counts, which the index prologue leaves in lw.counts; the encoder runs Nv
+    // rows per sample of which sample b attends to its first counts[b]; the decoder's output rows are the last Nt - ragged_min of every sample
+    const int rg_min = m->ragged_min;
+    const int* counts = rg_min > 0 ? lw.counts : nullptr;
+    const int Nt = S.n_tok, Nv = a->n_vis, Nm = Nt - (rg_min > 0 ? rg_min : Nv);
     const int Nret = Nm > 0 ? Nm : Nt;
     Engine& E = m->eng;
     const int planes = a->mode == CWM_MODE_PARITY ? 2 : 1;
@@ -141,10 +151,11 @@ static int forward_lane(cwm_model* m, const cwm_forward_args* a, int b0, int B, 
     pg.C = c.in_chans; pg.H = c.img_h; pg.W = c.img_w; pg.P = c.patch; pg.perm = w.perm; pg.Nt = Nt; pg.n_rows = Nv; pg.B = B;
     pg.out = w.tokens_in; pg.out_plane = (int64_t)B * Nv * S.embed_kpad; pg.ld = S.embed_kpad;
     if (E.tune.index_fused) {
-        if ((rc = E.run_index_gather(pg, mask_in, Nv, w.perm, a->y_video_dev ? lw.rank : nullptr, lw.err, planes, s))) return rc;
+        if ((rc = E.run_index_gather(pg, mask_in, Nv, w.perm, a->y_video_dev ? lw.rank : nullptr, lw.err, planes, s, rg_min, lw.counts))) return rc;
     } else {  // the four launches of rounds 1-4 (A/B and the bitwise cross-check of the fused kernel)
         CWM_HIP_CHECK(hipMemsetAsync(lw.err, 0, (size_t)B * sizeof(int), s));
-        if ((rc = launch_mask_to_perm(mask_in, B, Nt, Nv, w.perm, lw.err, s))) return rc;
+        if ((rc = rg_min > 0 ? launch_mask_to_perm_ragged(mask_in, B, Nt, rg_min, Nv, w.perm, lw.err, lw.counts, s) : launch_mask_to_perm(mask_in, B, Nt, Nv, w.perm, lw.err, s)))
+            return rc;
         if ((rc = E.run_patch_gather(pg, planes, s))) return rc;
         if (a->y_video_dev && (rc = launch_perm_to_rank(w.perm, lw.rank, B, Nt, s))) return rc;
     }
@@ -153,10 +164,10 @@ static int forward_lane(cwm_model* m, const cwm_forward_args* a, int b0, int B, 
 
     // a4-a6: encoder blocks over the visible tokens
     for (int i = 0; i < c.enc_depth; ++i)
-        if (in_range(1 + i) && (rc = E.run_block(S.enc[i], w.x_enc, B, Nv, S.enc_dim, S.enc_heads, planes, w.sb, s))) return rc;
+        if (in_range(1 + i) && (rc = E.run_block(S.enc[i], w.x_enc, B, Nv, S.enc_dim, S.enc_heads, planes, w.sb, s, 0, counts))) return rc;
 
     // a7: encoder.norm, encoder_to_decoder (no bias); a8: + pos[vis] written straight into x_full rows [0,Nv), mask tokens behind them
-    if (in_range(st_e2d) && (rc = E.to_decoder(S, w, B, Nv, planes, s))) return rc;
+    if (in_range(st_e2d) && (rc = E.to_decoder(S, w, B, Nv, planes, s, counts, rg_min))) return rc;
 
     // a9: decoder blocks over the full token set, norm + head on the last Nm tokens
     // (the last block only has to produce the Nm rows the head reads: option "prune_last_block" = 0 runs it in full)
@@ -175,7 +186,8 @@ static int forward_lane(cwm_model* m, const cwm_forward_args* a, int b0, int B, 
         memset(&u, 0, sizeof(u));
         u.y = y_tokens; u.x = xr; u.sb = a->x_stride_b; u.sc = a->x_stride_c; u.st = a->x_stride_t;
         u.mask = mask_in; u.rank = lw.rank; u.B = B; u.T = c.num_frames; u.C = c.in_chans; u.H = c.img_h; u.W = c.img_w;
-        u.P = c.patch; u.n_vis = Nv; u.Nm = Nm;
+        // (ragged batch: y row j of every sample is decoder row ragged_min + j, whatever the sample's own count -- and `rank` is the decoder row)
+        u.P = c.patch; u.n_vis = Nt - Nm; u.Nm = Nm;
         u.out = a->y_video_dev + (size_t)b0 * c.num_frames * c.in_chans * c.img_h * c.img_w;
         if ((rc = E.run_unembed(u, s))) return rc;
     }
@@ -195,6 +207,8 @@ extern "C" int cwm_forward(cwm_model* m, const cwm_forward_args* a_in) {
     const cwm_config& c = m->cfg;
     const int B = a->batch, Nt = m->st.n_tok, Nv = a->n_vis, Nm = Nt - Nv;
     CWM_REQUIRE(B > 0, "cwm_forward: batch must be positive");
+    CWM_REQUIRE(m->ragged_min <= Nv, "cwm_forward: the handle takes rows of at least %d visible tokens (cwm_model_set_ragged), more than the call's cap n_vis = %d",
+                m->ragged_min, Nv);
     CWM_REQUIRE(Nv > 0 && Nm >= 0, "cwm_forward: need 0 < n_vis (%d) <= num tokens (%d)", Nv, Nt);
     // nothing masked: the reference decoder then returns head(norm(x)) for ALL tokens (vmae.py:250-253), and its wrapper cannot
     // compose a video from that (prediction.py:252-254 would assign Nt rows to an empty selection)
@@ -227,6 +241,10 @@ extern "C" int cwm_forward(cwm_model* m, const cwm_forward_args* a_in) {
         std::vector<int> herr((size_t)B, 0);
         CWM_HIP_CHECK(hipMemcpyAsync(herr.data(), m->ws.err, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
         CWM_HIP_CHECK(hipStreamSynchronize(s));
+        if (m->ragged_min > 0 && std::any_of(herr.begin(), herr.end(), [](int e) { return e != 0; })) {
+            cwm_set_error("mask rows do not all have between %d (cwm_model_set_ragged) and n_vis=%d visible tokens", m->ragged_min, Nv);
+            return CWM_ERR_MASK;
+        }
         if (std::any_of(herr.begin(), herr.end(), [](int e) { return e != 0; })) {
             cwm_set_error("mask rows do not all have n_vis=%d visible tokens (shape '[%d, -1, %d]' is invalid for the gathered input)", Nv, B,
                           c.enc_dim);
@@ -239,6 +257,13 @@ extern "C" int cwm_forward(cwm_model* m, const cwm_forward_args* a_in) {
 extern "C" int cwm_model_set_lanes(cwm_model* m, int lanes) {
     CWM_REQUIRE(m && lanes >= 1 && lanes <= cwm_model::kMaxLanes, "cwm_model_set_lanes: lanes must be 1 .. %d", cwm_model::kMaxLanes);
     m->lanes = lanes;
+    return CWM_OK;
+}
+
+extern "C" int cwm_model_set_ragged(cwm_model* m, int n_vis_min) {
+    CWM_REQUIRE(m && n_vis_min >= 0 && n_vis_min <= m->st.n_tok, "cwm_model_set_ragged: n_vis_min must be 0 (rectangular batches) or a visible count up to %d",
+                m ? m->st.n_tok : 0);
+    m->ragged_min = n_vis_min;
     return CWM_OK;
 }
 
@@ -297,6 +322,25 @@ __global__ void merge_planes_kernel(const bf16* in, float* out, int rows, int ld
     if (i >= (int64_t)rows * ld) return;
     const int r = (int)(i / ld), c = (int)(i - (int64_t)r * ld);
     const bf16* s = in + a_pos<PLANES>(r, ld_in, c);
+    out[i] = (float)s[0] + (PLANES == 2 ? (float)s[kLoOffset] : 0.f);
+}
+
+// cwm_attention_ragged: bad[0] = 1 when a row's key count is outside [1, N]
+__global__ void key_len_check_kernel(const int* key_len, int B, int N, int* bad) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B && (key_len[b] < 1 || key_len[b] > N)) bad[0] = 1;
+}
+
+// merge_planes_kernel for [B][N] rows of which the first key_len[b] of every batch row were written; the others, and every row when the check above
+// flagged a length, are left as the caller passed them
+template <int PLANES>
+__global__ void merge_planes_ragged_kernel(const bf16* in, float* out, int B, int N, int ld, const int* key_len, const int* bad) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)B * N * ld || bad[0]) return;
+    const int r = (int)(i / ld), c = (int)(i - (int64_t)r * ld);
+    const int b = r / N;
+    if (r - b * N >= key_len[b]) return;
+    const bf16* s = in + a_pos<PLANES>(r, ld, c);
     out[i] = (float)s[0] + (PLANES == 2 ? (float)s[kLoOffset] : 0.f);
 }
 }  // namespace
@@ -391,6 +435,45 @@ extern "C" int cwm_attention(const float* qkv_dev, float* o_dev, int B, int N, i
     else
         hipLaunchKernelGGL(merge_planes_kernel<1>, dim3((unsigned)((qk_plane + 255) / 256)), dim3(256), 0, s, o, o_dev, B * N, D, D);
     CWM_HIP_CHECK(hipStreamSynchronize(s));
+    return CWM_OK;
+}
+
+// cwm_attention with a key count per batch row (AttnParams.key_len): what a predictor needs to run rows with different numbers of visible tokens as one
+// batch, where the reference equalises the counts first (RectangularizeMasks, prediction.py:421) because its gather reshapes to one count (vmae.py:167)
+extern "C" int cwm_attention_ragged(const float* qkv_dev, const int32_t* key_len_dev, float* o_dev, int B, int N, int H, int mode, void* stream) {
+    CWM_REQUIRE(qkv_dev && key_len_dev && o_dev && B > 0 && N > 0 && H > 0, "cwm_attention_ragged: bad argument");
+    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_attention_ragged: bad mode");
+    hipStream_t s = (hipStream_t)stream;
+    const int planes = mode == CWM_MODE_PARITY ? 2 : 1;
+    const int D = H * 64;
+    const int64_t qk_plane = (int64_t)B * N * D;
+    Scratch sc;
+    bf16* q = sc.get<bf16>(2 * qk_plane);
+    bf16* k = sc.get<bf16>(2 * qk_plane);
+    bf16* v = sc.get<bf16>(2 * qk_plane);
+    bf16* o = sc.get<bf16>(2 * qk_plane);
+    int* bad = sc.get<int>(4, true);
+    CWM_REQUIRE(q && k && v && o && bad, "cwm_attention_ragged: out of device memory");
+    hipLaunchKernelGGL(key_len_check_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, key_len_dev, B, N, bad);
+    if (int rc = launch_qkv_scatter(qkv_dev, B, N, H, 0.125f, q, k, v, qk_plane, s)) return rc;
+    AttnParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.k = k; a.v = v; a.qk_plane = qk_plane; a.o = o; a.o_plane = qk_plane; a.ldo = D;
+    a.n_tok = N; a.heads = H; a.batch = B;
+    a.key_len = key_len_dev;
+    a.tune = &thread_tuning();
+    if (int rc = launch_attention(a, planes, s)) return rc;
+    if (planes == 2)
+        hipLaunchKernelGGL(merge_planes_ragged_kernel<2>, dim3((unsigned)((qk_plane + 255) / 256)), dim3(256), 0, s, o, o_dev, B, N, D, key_len_dev, bad);
+    else
+        hipLaunchKernelGGL(merge_planes_ragged_kernel<1>, dim3((unsigned)((qk_plane + 255) / 256)), dim3(256), 0, s, o, o_dev, B, N, D, key_len_dev, bad);
+    int hbad = 0;
+    CWM_HIP_CHECK(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    CWM_HIP_CHECK(hipStreamSynchronize(s));
+    if (hbad) {
+        cwm_set_error("cwm_attention_ragged: a key count is outside [1, N = %d]; o_dev was not written", N);
+        return CWM_ERR_INVALID;
+    }
     return CWM_OK;
 }
 

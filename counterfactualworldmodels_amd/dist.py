@@ -495,6 +495,10 @@ def prompt_hooks(G, frame: Optional[int] = -1):
     (active_h, active_w, dy, dx): one active patch of frame 1 moved by (dy, dx) patches, nothing passive (cfg 4)."""
     from .prediction import _RectBatch
 
+    if getattr(G, "ragged_batches", False):
+        raise NotImplementedError("the sharded prompt path is rectangular: it equalises the masks of all prompts once, on rank 0; build the generator with "
+                                  "ragged_batches=False for it")
+
     def build(xb, rows, frames=True):
         """The prompt rows -> (frames [n,T,C,H,W] | None, masks [n,Nt]): `cwm_prompt_table_expand` (table -> dense active / passive masks + shifts, one launch) and
         `cwm_shift_prompts` on the image as a static two-frame movie (only frame 0 exists in memory)."""

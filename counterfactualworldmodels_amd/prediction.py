@@ -51,6 +51,7 @@ class _RectBatch:
     row_kwargs: Dict[str, object] = field(default_factory=dict)
     weights_synced: bool = False          # `_as_rect` ran the predictor's sync_weights() already (before the mask read-back)
     out: Optional[torch.Tensor] = None    # output video allocated there too (fused path)
+    n_vis_range: Optional[tuple] = None   # ragged batch (`ragged_batches`): the rows' visible counts lie in [lo, hi]; the masks are as they were built
 
     @property
     def rows(self) -> int:
@@ -62,8 +63,13 @@ class PredictorBasedGenerator(nn.Module):
 
     def __init__(self, predictor=None, predictor_load_path=None, keypoint_predictor=None, keypoint_predictor_load_path=None,
                  error_func=None, imagenet_normalize_inputs=False, temporal_dim=2, seed=0, mask_generator=None, raft_iters=None,
-                 max_shift_fraction=0.15, **kwargs):
+                 max_shift_fraction=0.15, ragged_batches=False, **kwargs):
         super().__init__()
+        # True: rows with different visible-token counts run as ONE ragged batch per library call (vmae.py forward(..., ragged=True)) where the
+        # reference -- and the default here -- first un-masks random masked patches of the rows with fewer visible tokens until the counts agree
+        # (`mask_rectangularizer`).  Masks then stay exactly as they were built, nothing is drawn from torch's global RNG, and a batched row is
+        # predicted as it would be alone.
+        self.ragged_batches = bool(ragged_batches)
         self.set_predictor(predictor, predictor_load_path)
         self.error_func = error_func if error_func is not None else nn.MSELoss(reduction="none")
         self.imagenet_normalize_inputs = bool(imagenet_normalize_inputs)
@@ -161,7 +167,11 @@ class PredictorBasedGenerator(nn.Module):
     def generate_mask(self, x=None):
         assert self.mask_generator is not None
         x = self.x if x is None else x
-        return self.mask_rectangularizer(self.mask_generator(x).view(x.size(0), -1).to(x.device))
+        mask = self.mask_generator(x).view(x.size(0), -1).to(x.device)
+        if self.ragged_batches:
+            self._require_ragged()
+            return mask
+        return self.mask_rectangularizer(mask)
 
     def set_new_mask(self, x=None):
         self.mask = self.generate_mask(self.x if x is None else x)
@@ -257,6 +267,27 @@ class PredictorBasedGenerator(nn.Module):
     def _uses_fused_path(self, extra_args, row_kwargs) -> bool:
         return isinstance(self.predictor, PretrainVisionTransformer) and self.t_dim == 2 and not extra_args and not row_kwargs
 
+    def _require_ragged(self, extra_args=(), row_kwargs=None, fused_call=True):
+        """`ragged_batches` needs the plain predictor on its fused path; everything else says why not, at the call."""
+        if self._is_padded or not isinstance(self.predictor, PretrainVisionTransformer):
+            raise RuntimeError("ragged_batches=True is for the plain VMAE predictor: %s takes rows with different visible counts through its null-token "
+                               "padding already" % type(self.predictor).__name__)
+        if not fused_call or not self._uses_fused_path(extra_args, row_kwargs or {}):
+            raise RuntimeError("ragged_batches=True runs on the fused predict path only (a two-frame movie on the GPU, no extra predictor arguments); this call "
+                               "would go through the predictor's plain forward, whose rows must have equal visible counts")
+
+    def _equalise(self, mask) -> tuple:
+        """(mask, n_masked, n_vis_range) for the rows of a multi-row call: rectangularised as the reference does (prediction.py:421; in place, on torch's
+        global RNG), or -- `ragged_batches` -- untouched, with the range of the rows' visible counts.  Either way the call's one host read-back."""
+        if not self.ragged_batches:
+            mask = self.mask_rectangularizer(mask)
+            return mask, self.mask_rectangularizer.last_num_masked, None
+        self._require_ragged()
+        n_masked = mask.reshape(mask.shape[0], -1).sum(1)
+        hi_m, lo_m = (int(v) for v in torch.stack([n_masked.max(), n_masked.min()]).tolist())
+        Nt = mask[0].numel()
+        return mask, None, (Nt - hi_m, Nt - lo_m)
+
     def _run_rect_batch(self, batch: _RectBatch, rows_per_call: Optional[int] = None, extra_args: Sequence = ()) -> torch.Tensor:
         """All rows of `batch` -> videos [R,T,C,H,W], `rows_per_call` rows per library call, every call writing its slice
         of ONE output tensor.  With `n_masked` known nothing here reads the device back, so the calls queue up behind each
@@ -266,6 +297,8 @@ class PredictorBasedGenerator(nn.Module):
         Nt = batch.mask.shape[1]
         n_vis = None if batch.n_masked is None else Nt - batch.n_masked
         fused = self._uses_fused_path(extra_args, batch.row_kwargs)
+        if batch.n_vis_range is not None:
+            self._require_ragged(extra_args, batch.row_kwargs, fused_call=batch.x.is_cuda and batch.x.dim() == 5)
         out = None
         if fused:
             out = batch.out if batch.out is not None else torch.empty(batch.x.shape, device=batch.x.device, dtype=torch.float32)
@@ -273,6 +306,10 @@ class PredictorBasedGenerator(nn.Module):
         for r0 in range(0, R, step):
             r1 = min(r0 + step, R)
             xs, ms = batch.x[r0:r1], batch.mask[r0:r1]
+            if fused and batch.n_vis_range is not None:  # (the range was read from these very masks: nothing left to check)
+                self.predictor.predict_video(xs, ms, normalize=self.imagenet_normalize_inputs, check=False, out_video=out[r0:r1],
+                                             weights_synced=batch.weights_synced, ragged=True, n_vis_range=batch.n_vis_range)
+                continue
             if fused:
                 self.predictor.predict_video(xs, ms, normalize=self.imagenet_normalize_inputs, n_vis=n_vis, check=n_vis is None,
                                              out_video=out[r0:r1], weights_synced=batch.weights_synced)
@@ -302,11 +339,12 @@ class PredictorBasedGenerator(nn.Module):
             self.predictor.sync_weights(x.device)
             synced = True
             out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-        n_masked = None
+        n_masked, n_vis_range = None, None
         if x.size(0) > 1:
-            mask = self.mask_rectangularizer(mask)
-            n_masked = self.mask_rectangularizer.last_num_masked
-        return _RectBatch(x, mask, n_masked, dict(row_kwargs or {}), synced, out)
+            if self.ragged_batches:
+                self._require_ragged(extra_args, row_kwargs, fused_call=for_video and x.is_cuda and x.dim() == 5)
+            mask, n_masked, n_vis_range = self._equalise(mask)
+        return _RectBatch(x, mask, n_masked, dict(row_kwargs or {}), synced, out, n_vis_range)
 
     @staticmethod
     def _select_frame(video, frame):
@@ -479,6 +517,9 @@ class PredictorBasedGenerator(nn.Module):
         x_shift, mask_shift = self._shift_rows(x, mask.reshape(x.shape[0], -1), active_patches.reshape(x.shape[0], -1), table, frame,
                                                fix_passive=fix_passive)
         self._record_shift(dy, dx)
+        if self.ragged_batches:
+            self._require_ragged()
+            return x_shift, mask_shift
         return x_shift, self.mask_rectangularizer(mask_shift)
 
     def get_counterfactual_prediction(self, x, mask=None, active_patches=None, shift=None, fix_passive=False, **kwargs):

@@ -175,8 +175,8 @@ class FlowGenerator(PredictorBasedGenerator):
                                                table, frame, fix_passive, samples_per_movie=S)
         for dy, dx in rows:
             self._record_shift(dy, dx)
-        mask_shift = self.mask_rectangularizer(mask_shift)
-        return _RectBatch(x_shift, mask_shift, self.mask_rectangularizer.last_num_masked)
+        mask_shift, n_masked, n_vis_range = self._equalise(mask_shift)
+        return _RectBatch(x_shift, mask_shift, n_masked, n_vis_range=n_vis_range)
 
     def create_motion_counterfactuals(self, x, masks, active_patches=None, shifts=None, frame=1, num_samples=None, fix_passive=True,
                                       reset_shifts=False):
@@ -316,8 +316,8 @@ class FlowGenerator(PredictorBasedGenerator):
         x_shift, mask_shift = multi_shift_rows(x, points.reshape(B * S, K, Nt), passive.reshape(B * S, 1, Nt), np.broadcast_to(table[None], (B, S, K, 2)),
                                                self.patch_size[-1], frame, fix_passive=fix_passive, samples_per_movie=S)
         self.shifts = [np.array(table[s]) for _ in range(B) for s in range(S)]
-        mask_shift = self.mask_rectangularizer(mask_shift)
-        batch = _RectBatch(x_shift, mask_shift, self.mask_rectangularizer.last_num_masked)
+        mask_shift, n_masked, n_vis_range = self._equalise(mask_shift)
+        batch = _RectBatch(x_shift, mask_shift, n_masked, n_vis_range=n_vis_range)
         for k, v in row_kwargs.items():  # per-movie tensors (the IMU stream) follow their movie's S prompts
             if torch.is_tensor(v) and v.shape[0] == B and B != batch.rows:
                 v = self.sample_tile(v, S)

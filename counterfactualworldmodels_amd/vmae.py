@@ -142,7 +142,7 @@ class PretrainVisionTransformer(LibraryModule):
 
     # ---- C-ABI plumbing (the handle, sync_weights and the options live in _handle.LibraryModule) -------
     _ABI = {"destroy": "cwm_model_destroy", "load_weight": "cwm_model_load_weight", "forward": "cwm_forward", "set_option": "cwm_model_set_option",
-            "set_lanes": "cwm_model_set_lanes", "timing_enable": "cwm_timing_enable", "timing_collect": "cwm_timing_collect"}
+            "set_lanes": "cwm_model_set_lanes", "set_ragged": "cwm_model_set_ragged", "timing_enable": "cwm_timing_enable", "timing_collect": "cwm_timing_collect"}
 
     def _create(self, lib, h):
         c = self.cfg
@@ -152,7 +152,8 @@ class PretrainVisionTransformer(LibraryModule):
         )
         return lib.cwm_model_create(C.byref(ccfg), C.byref(h))
 
-    def _run(self, x, strides, normalize, mask, n_vis, want_video, xraw=None, check=True, out_tokens=None, out_video=None, weights_synced=False):
+    def _run(self, x, strides, normalize, mask, n_vis, want_video, xraw=None, check=True, out_tokens=None, out_video=None, weights_synced=False,
+             ragged=False, n_vis_range=None):
         _lib.require_gpu()
         if not x.is_cuda:
             raise RuntimeError("PretrainVisionTransformer.forward needs a CUDA/HIP tensor (no CPU fallback); got %s" % x.device)
@@ -165,9 +166,22 @@ class PretrainVisionTransformer(LibraryModule):
         mask = mask.to(device=dev, dtype=torch.bool).reshape(B, -1).contiguous()
         if mask.shape[1] != Nt:
             raise RuntimeError("mask has %d tokens per row, model expects %d" % (mask.shape[1], Nt))
+        n_vis_min = 0
+        if ragged:
+            # rows with different visible counts as ONE batch (cwm_model_set_ragged): `hi` is the cap the encoder runs at, `lo` sizes the output
+            vis = Nt - mask.sum(1, dtype=torch.int32)  # (device; read back only when the caller gave no range)
+            if n_vis_range is None:
+                lo, hi = (int(v) for v in torch.stack([vis.min(), vis.max()]).tolist())
+            else:
+                lo, hi = (int(v) for v in n_vis_range)
+            if not 0 < lo <= hi <= Nt:
+                raise RuntimeError("n_vis_range=(%d, %d): need 0 < lo <= hi <= %d tokens" % (lo, hi, Nt))
+            n_vis, n_vis_min = hi, lo
+        elif n_vis_range is not None:
+            raise RuntimeError("n_vis_range goes with ragged=True")
         if n_vis is None:
             n_vis = Nt - int(mask[0].sum().item())
-        Nm = Nt - n_vis
+        Nm = Nt - (n_vis_min if ragged else n_vis)
         # nothing masked: the reference returns head(norm(x)) for all Nt tokens (vmae.py:250-253)
         y = self._out_buffer(out_tokens, (B, Nm if Nm > 0 else Nt, c.out_dim), dev)
         video = self._out_buffer(out_video, (B, c.num_frames, c.in_chans, c.img_size[0], c.img_size[1]), dev) if want_video else None
@@ -176,7 +190,14 @@ class PretrainVisionTransformer(LibraryModule):
             _lib.ptr(video), _lib.ptr(xraw), _lib.mode_id(self.mode), int(check), _lib.current_stream_handle(dev),
         )
         with torch.cuda.device(dev):
+            if ragged or self.__dict__.get("_ragged_set"):  # (a handle that never ran a ragged batch is never told about them)
+                self._check(self._fn["set_ragged"](self._handle, n_vis_min))
+                self.__dict__["_ragged_set"] = bool(ragged)
             self._check(self._fn["forward"](self._handle, C.byref(args)))
+        if ragged and Nm > 0:
+            # row b's predictions are its last Nt - Nv_b rows; what the library leaves before them is unspecified: zeroed (on the device, no read-back)
+            lead = (vis - n_vis_min).clamp_(min=0)
+            y.masked_fill_((torch.arange(y.shape[1], device=dev)[None, :] < lead[:, None])[:, :, None], 0.0)
         return y, video
 
     @staticmethod
@@ -201,30 +222,35 @@ class PretrainVisionTransformer(LibraryModule):
 
     # ---- reference forward: vmae.py:539-560 ------------------------------------------------------
     @torch.no_grad()
-    def forward(self, x, mask, timestamps=None, *args, n_vis: Optional[int] = None, check: bool = True, **kwargs):
+    def forward(self, x, mask, timestamps=None, *args, n_vis: Optional[int] = None, check: bool = True, ragged: bool = False, n_vis_range=None, **kwargs):
         """x: float[B,C,T,H,W] (already pre-processed by the caller, any strides), mask: bool[B,Nt]
-        with equal visible counts per row.  Returns float[B,Nm,C*P*P]."""
+        with equal visible counts per row.  Returns float[B,Nm,C*P*P].
+
+        ragged=True: the rows of `mask` may have different visible counts, between `lo` and `hi` = n_vis_range (without it one read-back of the
+        counts' minimum and maximum).  Every row is predicted from exactly its own visible tokens, as it would be alone at batch 1.  Returns
+        float[B, Nt - lo, C*P*P]: row b's predictions are its LAST Nt - Nv_b rows (ascending token order), the rows before them are zero."""
         if x.dim() != 5 or x.shape[1] != self.cfg.in_chans or x.shape[2] != self.cfg.num_frames:
             raise RuntimeError("expected x of shape [B,%d,%d,H,W], got %s" % (self.cfg.in_chans, self.cfg.num_frames, tuple(x.shape)))
         if tuple(x.shape[-2:]) != tuple(self.cfg.img_size):
             raise RuntimeError("input image size %s does not match the model's %s" % (tuple(x.shape[-2:]), self.cfg.img_size))
         x, strides = self._frame_strides(x, 1, 2)
-        y, _ = self._run(x, strides, False, mask, n_vis, False, check=check)
+        y, _ = self._run(x, strides, False, mask, n_vis, False, check=check, ragged=ragged, n_vis_range=n_vis_range)
         return y
 
     @torch.no_grad()
     def predict_video(self, x_btchw, mask, normalize: bool = True, n_vis: Optional[int] = None, check: bool = True,
-                      out_tokens: Optional[torch.Tensor] = None, out_video: Optional[torch.Tensor] = None, weights_synced: bool = False):
+                      out_tokens: Optional[torch.Tensor] = None, out_video: Optional[torch.Tensor] = None, weights_synced: bool = False,
+                      ragged: bool = False, n_vis_range=None):
         """Fused wrapper path: raw [B,T,C,H,W] frames in [0,1] -> (tokens [B,Nm,C*P*P], video
         [B,T,C,H,W]) = `_preprocess` + forward + `pred_patches_to_video`
-        (prediction.py:304-312, :419-422, :245-259) in one library call."""
+        (prediction.py:304-312, :419-422, :245-259) in one library call.  ragged / n_vis_range: as `forward` (tokens [B, Nt - lo, C*P*P])."""
         if x_btchw.dim() != 5 or x_btchw.shape[2] != self.cfg.in_chans or x_btchw.shape[1] != self.cfg.num_frames:
             raise RuntimeError("expected x of shape [B,%d,%d,H,W], got %s" % (self.cfg.num_frames, self.cfg.in_chans, tuple(x_btchw.shape)))
         x, strides = self._frame_strides(x_btchw, 2, 1)
         # (weights_synced: the caller has just run sync_weights() itself -- the wrapper does, BEFORE its mask read-back, so that the walk over the
         # parameters overlaps the previous call's kernels instead of delaying this call's first launch)
         return self._run(x, strides, normalize, mask, n_vis, True, xraw=x, check=check, out_tokens=out_tokens, out_video=out_video,
-                         weights_synced=weights_synced)
+                         weights_synced=weights_synced, ragged=ragged, n_vis_range=n_vis_range)
 
 
 # ---- factories (same names / defaults as vmae.py:597-619) -------------------------------------------

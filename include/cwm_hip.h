@@ -103,6 +103,15 @@ CWM_API int cwm_forward(cwm_model* m, const cwm_forward_args* args);
  * with events inside cwm_forward, so the caller sees ordinary stream semantics; results are those of the single-lane call up to the
  * kernel choice per GEMM shape (fp32 re-association, < 1e-5).  lanes = 1: everything on args->stream. */
 CWM_API int cwm_model_set_lanes(cwm_model* m, int lanes); /* 1 .. 4 (lane l owns batch rows [ceil(B l / n), ceil(B (l + 1) / n)); fewer lanes are used when a lane would keep < 3000 encoder rows); more than two lanes measured slower on MI355X */
+/* Ragged batches.  0 (the default): every row of a cwm_forward has args->n_vis visible tokens, anything else is CWM_ERR_MASK -- the reference's failing
+ * reshape `x[~mask].reshape(B, -1, C)` (vmae.py:167), which its wrappers avoid by un-masking random masked patches of the shorter rows until the counts agree
+ * (RectangularizeMasks, prediction.py:421).  n_vis_min > 0: a row may have between n_vis_min and args->n_vis visible tokens (args->n_vis is the cap;
+ * n_vis_min > args->n_vis is CWM_ERR_INVALID; with args->check a row outside the range is CWM_ERR_MASK, naming the range).  Every row is then predicted
+ * from exactly the tokens its own mask leaves visible, as the reference predicts it alone at batch 1: the encoder runs args->n_vis rows per sample and
+ * row b's attention reads its first Nv_b only, whatever the rows behind them hold.  y_tokens_dev is [B, Nt - n_vis_min, out]: the predictions of row b
+ * are its LAST Nt - Nv_b rows, in ascending token order; the rows before them are unspecified.  y_video_dev as before.  Per handle because
+ * cwm_forward_args is frozen.  Lanes, options and modes are unaffected. */
+CWM_API int cwm_model_set_ragged(cwm_model* m, int n_vis_min);
 
 /* Execution options of ONE model handle (no counterpart in the reference).  The defaults are the measured best and what production callers run;
  * the other values exist for same-box A/B measurements and for the bitwise cross-checks of the test suite.  Options are per handle: two models in
@@ -243,6 +252,15 @@ CWM_API int cwm_linear(const float* a_dev, const float* w_dev, const float* bias
 /* O[B,N,H*64] = softmax(q k^T) v per head from a packed qkv activation [B,N,3*H*64] (fp32 device),
  * q scaled by 64^-0.5 after bias as in VideoMAE/utils.py:94-113. */
 CWM_API int cwm_attention(const float* qkv_dev, float* o_dev, int B, int N, int H, int mode, void* stream);
+/* The same with a key count per batch row: row b attends to keys [0, key_len_dev[b]) of its N rows (N stays the row stride), and O rows
+ * [0, key_len_dev[b]) of row b are written -- the others keep what o_dev held.  What rows b's q, k and v hold at and past its count never reaches a
+ * written row, NaN and Inf included (those keys are not staged; a partly valid key tile re-reads the row's last valid key).  This is the kernel a
+ * predictor needs for rows with different numbers of visible tokens: the reference's gather `x[~mask].reshape(B, -1, C)` (vmae.py:167) takes one
+ * count for the whole batch, which is why its wrapper first un-masks random masked patches until the counts agree (RectangularizeMasks,
+ * prediction.py:421).  With every count = N the result is bit-identical to cwm_attention under options "attn_tail" = 0, "attn_ksplit" = 0: ragged
+ * launches run the regular schedule.  A count outside [1, N] is checked on the device: CWM_ERR_INVALID after the call's synchronisation, and
+ * o_dev is not written at all. */
+CWM_API int cwm_attention_ragged(const float* qkv_dev, const int32_t* key_len_dev, float* o_dev, int B, int N, int H, int mode, void* stream);
 /* y = LayerNorm(x) (fp32 in/out, eps, affine).  replaces nn.LayerNorm at VideoMAE/utils.py:148-149 */
 CWM_API int cwm_layernorm(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* y_dev, int rows, int D,
                   float eps, void* stream);
