@@ -636,6 +636,11 @@ DEV_SIGNATURES = {
     "cwm_dev_layernorm": (C.c_int, [C.POINTER(CwmDevLayernormArgs)]),
     "cwm_dev_fill_mask_tokens": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
     "cwm_dev_unembed": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int64] * 3 + [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),
+    # the launch forms of a ragged batch (tests/test_ragged_kernels_gpu.py)
+    "cwm_dev_gather_ragged": (C.c_int, [C.POINTER(CwmDevGatherArgs), C.c_int, C.c_void_p]),
+    "cwm_dev_attention_ragged": (C.c_int, [C.POINTER(CwmDevAttentionArgs), C.c_void_p]),
+    "cwm_dev_fill_mask_tokens_ragged": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
+    "cwm_dev_unembed_ragged": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int64] * 3 + [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
 }
 
 # the keys cwm_model_set_option / cwm_conj_set_option know (include/cwm_hip.h; csrc/engine.hip tuning_field)

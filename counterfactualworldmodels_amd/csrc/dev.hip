@@ -402,9 +402,11 @@ extern "C" int cwm_dev_raft_flow_update(float* coords_dev, const float* delta_de
 }
 
 // ---- the operand gathers one launch at a time (tests/test_gather_kernels_gpu.py) ----
-extern "C" int cwm_dev_gather(const cwm_dev_gather_args* args) {
+// ragged: cwm_dev_gather_ragged's call (INDEX / INDEX_UNFUSED with the launch forms of a ragged batch: n_vis_min and counts go to the launchers as they are)
+static int dev_gather(const cwm_dev_gather_args* args, bool ragged, int n_vis_min, int* counts) {
     CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_gather_args), "cwm_dev_gather: args->struct_size must be sizeof(cwm_dev_gather_args)");
     const cwm_dev_gather_args& a = *args;
+    CWM_REQUIRE(!ragged || a.kind == CWM_DEV_GATHER_INDEX || a.kind == CWM_DEV_GATHER_INDEX_UNFUSED, "cwm_dev_gather_ragged: kind %d has no ragged form", a.kind);
     hipStream_t s = (hipStream_t)a.stream;
     CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_gather: bad mode");
     const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
@@ -449,11 +451,14 @@ extern "C" int cwm_dev_gather(const cwm_dev_gather_args* args) {
                 rc = launch_patch_gather(g, planes, s);
             } else if (a.kind == CWM_DEV_GATHER_INDEX) {
                 CWM_REQUIRE(a.mask && a.perm && a.err_rows, "cwm_dev_gather: the index gather needs mask, perm and err_rows");
-                rc = launch_index_gather(g, a.mask, a.n_vis, a.perm, a.rank, a.err_rows, planes, s);
+                rc = ragged ? launch_index_gather(g, a.mask, a.n_vis, a.perm, a.rank, a.err_rows, planes, s, n_vis_min, counts)
+                            : launch_index_gather(g, a.mask, a.n_vis, a.perm, a.rank, a.err_rows, planes, s);
             } else if (a.kind == CWM_DEV_GATHER_INDEX_UNFUSED) {
                 CWM_REQUIRE(a.mask && a.perm && a.rank && a.err_rows, "cwm_dev_gather: the unfused index prologue needs mask, perm, rank and err_rows");
                 CWM_HIP_CHECK(hipMemsetAsync(a.err_rows, 0, (size_t)a.B * sizeof(int), s));
-                if ((rc = launch_mask_to_perm(a.mask, a.B, L, a.n_vis, a.perm, a.err_rows, s))) return rc;
+                if ((rc = ragged ? launch_mask_to_perm_ragged(a.mask, a.B, L, n_vis_min, a.n_vis, a.perm, a.err_rows, counts, s)
+                                 : launch_mask_to_perm(a.mask, a.B, L, a.n_vis, a.perm, a.err_rows, s)))
+                    return rc;
                 if ((rc = launch_patch_gather(g, planes, s))) return rc;
                 rc = launch_perm_to_rank(a.perm, a.rank, a.B, L, s);
             } else {
@@ -465,6 +470,10 @@ extern "C" int cwm_dev_gather(const cwm_dev_gather_args* args) {
     CWM_HIP_CHECK(hipStreamSynchronize(s));
     return CWM_OK;
 }
+
+extern "C" int cwm_dev_gather(const cwm_dev_gather_args* args) { return dev_gather(args, false, 0, nullptr); }
+
+extern "C" int cwm_dev_gather_ragged(const cwm_dev_gather_args* args, int n_vis_min, int32_t* counts_dev) { return dev_gather(args, true, n_vis_min, counts_dev); }
 
 // ---- the conjoined predictor's attention and padding kernels one call at a time (tests/test_conj_kernels_gpu.py) ----
 namespace {
@@ -637,9 +646,11 @@ extern "C" int cwm_dev_gemm(const cwm_dev_gemm_args* args) {
     return CWM_OK;
 }
 
-extern "C" int cwm_dev_attention(const cwm_dev_attention_args* args) {
+static int dev_attention(const cwm_dev_attention_args* args, const int* key_len) {
     CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_attention_args), "cwm_dev_attention: args->struct_size must be sizeof(cwm_dev_attention_args)");
     const cwm_dev_attention_args& a = *args;
+    // (launch_attention refuses this too, but only after the Q/K/V scatter below has been launched)
+    CWM_REQUIRE(!key_len || a.n_q == 0, "cwm_dev_attention: per-row key counts (key_len) go with queries over all rows (n_q = 0), got n_q = %d", a.n_q);
     hipStream_t s = (hipStream_t)a.stream;
     CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_attention: bad mode");
     const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
@@ -662,10 +673,18 @@ extern "C" int cwm_dev_attention(const cwm_dev_attention_args* args) {
     p.o = (bf16*)a.o; p.o_plane = (int64_t)a.B * (a.n_q ? a.n_q : a.N) * a.ldo; p.ldo = a.ldo;
     p.n_tok = a.N; p.heads = a.H; p.batch = a.B;
     p.q_off = a.q_off; p.n_q = a.n_q;
+    p.key_len = key_len;
     p.tune = &thread_tuning();
     if (int rc = launch_attention(p, planes, s)) return rc;
     CWM_HIP_CHECK(hipStreamSynchronize(s));
     return CWM_OK;
+}
+
+extern "C" int cwm_dev_attention(const cwm_dev_attention_args* args) { return dev_attention(args, nullptr); }
+
+extern "C" int cwm_dev_attention_ragged(const cwm_dev_attention_args* args, const int32_t* key_len_dev) {
+    CWM_REQUIRE(key_len_dev, "cwm_dev_attention_ragged: null key_len_dev");
+    return dev_attention(args, key_len_dev);
 }
 
 extern "C" int cwm_dev_layernorm(const cwm_dev_layernorm_args* args) {
@@ -696,9 +715,18 @@ extern "C" int cwm_dev_fill_mask_tokens(float* x_full_dev, const float* mask_tok
     return CWM_OK;
 }
 
+extern "C" int cwm_dev_fill_mask_tokens_ragged(float* x_full_dev, const float* mask_token_dev, const float* pos_dev, const int32_t* perm_dev,
+                                               const int32_t* counts_dev, int B, int Nt, int n_vis_min, int D, void* stream) {
+    CWM_REQUIRE(x_full_dev && mask_token_dev && pos_dev && perm_dev && B > 0 && Nt > 0 && D > 0, "cwm_dev_fill_mask_tokens_ragged: bad argument");
+    if (int rc = launch_fill_mask_tokens_ragged(x_full_dev, mask_token_dev, pos_dev, perm_dev, counts_dev, B, Nt, n_vis_min, D, (hipStream_t)stream)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return CWM_OK;
+}
+
 // cwm_unembed with the engine's strided frames (model.hip run_forward: x_stride_b / _c / _t of the caller's tensor): mask -> perm -> rank -> launch_unembed
-extern "C" int cwm_dev_unembed(const float* y_tokens_dev, const float* x_dev, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_t, const uint8_t* mask_dev,
-                               int B, int T, int C, int H, int W, int P, int n_vis, float* out_dev, void* stream) {
+// n_vis_min > 0: the ragged batch's form (forward_lane) -- rows of n_vis_min .. n_vis visible tokens, y rows = decoder rows n_vis_min ..
+static int dev_unembed(const float* y_tokens_dev, const float* x_dev, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_t, const uint8_t* mask_dev, int B, int T,
+                       int C, int H, int W, int P, int n_vis_min, int n_vis, float* out_dev, void* stream) {
     CWM_REQUIRE(y_tokens_dev && x_dev && mask_dev && out_dev && B > 0 && T > 0 && C > 0 && H > 0 && W > 0, "cwm_dev_unembed: bad argument");
     CWM_REQUIRE(P > 0 && H % P == 0 && W % P == 0, "cwm_dev_unembed: image size must be divisible by the patch size");
     CWM_REQUIRE(x_stride_c >= (int64_t)H * W && x_stride_t >= 0 && x_stride_b >= 0, "cwm_dev_unembed: channel planes of %d x %d pixels at a stride of %lld", H, W,
@@ -710,21 +738,38 @@ extern "C" int cwm_dev_unembed(const float* y_tokens_dev, const float* x_dev, in
     int* perm = sc.get<int>((size_t)B * Nt);
     int* rank = sc.get<int>((size_t)B * Nt);
     int* err = sc.get<int>(4, true);
-    CWM_REQUIRE(perm && rank && err, "cwm_dev_unembed: out of device memory");
+    int* counts = sc.get<int>((size_t)B);
+    CWM_REQUIRE(perm && rank && err && counts, "cwm_dev_unembed: out of device memory");
     int rc;
-    if ((rc = launch_mask_to_perm(mask_dev, B, Nt, n_vis, perm, err, s))) return rc;
+    if ((rc = n_vis_min > 0 ? launch_mask_to_perm_ragged(mask_dev, B, Nt, n_vis_min, n_vis, perm, err, counts, s) : launch_mask_to_perm(mask_dev, B, Nt, n_vis, perm, err, s)))
+        return rc;
+    const int y0 = n_vis_min > 0 ? n_vis_min : n_vis;  // the decoder row of y row 0
     if ((rc = launch_perm_to_rank(perm, rank, B, Nt, s))) return rc;
     UnembedParams u;
     memset(&u, 0, sizeof(u));
     u.y = y_tokens_dev; u.x = x_dev; u.sb = x_stride_b; u.st = x_stride_t; u.sc = x_stride_c;
-    u.mask = mask_dev; u.rank = rank; u.B = B; u.T = T; u.C = C; u.H = H; u.W = W; u.P = P; u.n_vis = n_vis; u.Nm = Nt - n_vis; u.out = out_dev;
+    u.mask = mask_dev; u.rank = rank; u.B = B; u.T = T; u.C = C; u.H = H; u.W = W; u.P = P; u.n_vis = y0; u.Nm = Nt - y0; u.out = out_dev;
     if ((rc = launch_unembed(u, s))) return rc;
     int herr = 0;
     CWM_HIP_CHECK(hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, s));
     CWM_HIP_CHECK(hipStreamSynchronize(s));
     if (herr) {
-        cwm_set_error("mask rows do not all have n_vis=%d visible tokens", n_vis);
+        if (n_vis_min > 0)
+            cwm_set_error("mask rows do not all have between %d and n_vis=%d visible tokens", n_vis_min, n_vis);
+        else
+            cwm_set_error("mask rows do not all have n_vis=%d visible tokens", n_vis);
         return CWM_ERR_MASK;
     }
     return CWM_OK;
+}
+
+extern "C" int cwm_dev_unembed(const float* y_tokens_dev, const float* x_dev, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_t, const uint8_t* mask_dev,
+                               int B, int T, int C, int H, int W, int P, int n_vis, float* out_dev, void* stream) {
+    return dev_unembed(y_tokens_dev, x_dev, x_stride_b, x_stride_c, x_stride_t, mask_dev, B, T, C, H, W, P, 0, n_vis, out_dev, stream);
+}
+
+extern "C" int cwm_dev_unembed_ragged(const float* y_tokens_dev, const float* x_dev, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_t, const uint8_t* mask_dev,
+                                      int B, int T, int C, int H, int W, int P, int n_vis_min, int n_vis, float* out_dev, void* stream) {
+    CWM_REQUIRE(n_vis_min > 0, "cwm_dev_unembed_ragged: n_vis_min = %d (a ragged batch has a least count > 0)", n_vis_min);
+    return dev_unembed(y_tokens_dev, x_dev, x_stride_b, x_stride_c, x_stride_t, mask_dev, B, T, C, H, W, P, n_vis_min, n_vis, out_dev, stream);
 }

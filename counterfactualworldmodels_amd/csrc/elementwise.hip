@@ -507,7 +507,9 @@ __global__ __launch_bounds__(256) void unembed_kernel(const UnembedParams p) {
     const int tau = t * n + (y / p.P) * gw + (x0 / p.P);
     Float4A4 o;
     if (p.mask[(size_t)b * Nt + tau]) {
-        const int j = p.rank[(size_t)b * Nt + tau] - p.n_vis;
+        // (a row with fewer visible tokens than n_vis -- reported through the prologue's err, but this launch is already queued by then -- has masked tokens
+        // of rank < n_vis: they read y row 0 instead of rows in front of the sample's, which for sample 0 lie in front of the buffer)
+        const int j = max(p.rank[(size_t)b * Nt + tau] - p.n_vis, 0);
         const float* yp = p.y + ((size_t)b * p.Nm + j) * (p.P * p.P * p.C) + ((y % p.P) * p.P + (x0 % p.P)) * p.C + c;
         o = Float4A4{{yp[0], yp[p.C], yp[2 * p.C], yp[3 * p.C]}};
     } else {
@@ -540,7 +542,7 @@ __global__ __launch_bounds__(256) void unembed3_kernel(const UnembedParams p) {
         const int y = y0 + k * hh;
         const int tau = t * n + (y / p.P) * gw + (x0 / p.P);
         if (p.mask[(size_t)b * Nt + tau]) {
-            const int j = p.rank[(size_t)b * Nt + tau] - p.n_vis;
+            const int j = max(p.rank[(size_t)b * Nt + tau] - p.n_vis, 0);  // (< 0: a row that err reports -- see unembed_kernel)
             const float4* yp = reinterpret_cast<const float4*>(p.y + ((size_t)b * p.Nm + j) * (p.P * p.P * 3) + ((y % p.P) * p.P + (x0 % p.P)) * 3);
             const float4 a = yp[0], bb = yp[1], c = yp[2];  // px0 (r g b) px1 (r | g b) px2 (r g | b) px3 (r g b)
             o[k][0] = make_float4(a.x, a.w, bb.z, c.y);

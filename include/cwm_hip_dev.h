@@ -196,6 +196,15 @@ typedef struct cwm_dev_gather_args {
 } cwm_dev_gather_args;
 CWM_API int cwm_dev_gather(const cwm_dev_gather_args* args);
 
+/* The index prologue of a ragged batch (cwm_model_set_ragged; tests/test_ragged_kernels_gpu.py): args as above with kind INDEX or INDEX_UNFUSED, args->n_vis the
+ * CAP of the rows' visible counts, n_vis_min the least count a row may have and counts_dev [B] (device) the rows' visible counts, written by the launch.
+ *   INDEX          launch_index_gather(..., n_vis_min, counts): err_rows[b] = (count of row b outside [n_vis_min, n_vis]); operand rows [count, n_rows) of a sample are zeros
+ *   INDEX_UNFUSED  what csrc/model.hip issues with "index_fused" = 0: memset of err_rows, launch_mask_to_perm_ragged, launch_patch_gather, launch_perm_to_rank;
+ *                  err_rows[0] = (any row outside the range); operand rows [count, n_rows) are the tokens perm[count ..], i.e. masked ones (written, values unspecified)
+ * Nothing of n_vis_min / counts_dev is checked here: the launchers' own refusals come back (before their launch; the unfused form's memset of err_rows has
+ * been issued by then, as in the model). */
+CWM_API int cwm_dev_gather_ragged(const cwm_dev_gather_args* args, int n_vis_min, int32_t* counts_dev);
+
 /* ---- the conjoined predictor's attention and padding kernels one call at a time (tests/test_conj_kernels_gpu.py) -------------------------------
  * csrc/conj_kernels.hip (fp32 VALU forms, padding bookkeeping) and csrc/conj_attention.hip (MFMA forms) on caller-owned device buffers; the stream
  * is synchronised before a call returns.  Outputs named "operand" are rows of planes * width bf16 in the layout of csrc/common.h a_pos (planes 2
@@ -314,6 +323,10 @@ typedef struct cwm_dev_attention_args {
     void* stream;
 } cwm_dev_attention_args;
 CWM_API int cwm_dev_attention(const cwm_dev_attention_args* args);
+/* The same launch with a key count per batch row, as the encoder blocks of a ragged batch issue it (AttnParams.key_len, device [B]; Engine::run_block):
+ * sample b attends to keys [0, key_len[b]) and only its O rows [0, key_len[b]) are written -- in place, into whatever `o` holds (the engine: LN1's rows);
+ * a length outside [1, N] writes nothing for that sample.  A query window (n_q > 0) together with key_len is refused before anything is launched. */
+CWM_API int cwm_dev_attention_ragged(const cwm_dev_attention_args* args, const int32_t* key_len_dev);
 
 /* LayerNorm of `rows` rows of D columns: output row r reads input row (r / rows_out_per_b) * rows_in_per_b + in_offset + r % rows_out_per_b of x (row
  * stride ldx; rows_out_per_b == 0: row r) and writes row r of the operand `out` (width ldo >= D: a multiple of 32 in parity mode, of 8 in fast mode;
@@ -337,6 +350,10 @@ CWM_API int cwm_dev_layernorm(const cwm_dev_layernorm_args* args);
 /* x_full [B][Nt][D]: rows n_vis .. Nt - 1 of every sample = mask_token [D] + pos[perm[b][row]] (pos rows of D floats, perm [B][Nt]); D a multiple of 4 */
 CWM_API int cwm_dev_fill_mask_tokens(float* x_full_dev, const float* mask_token_dev, const float* pos_dev, const int32_t* perm_dev, int B, int Nt, int n_vis,
                                      int D, void* stream);
+/* launch_fill_mask_tokens_ragged: the same for rows [counts[b], Nt) of sample b (counts device [B], every one >= n_vis_min > 0); rows [0, counts[b]) are not
+ * written, whatever n_vis_min.  n_vis_min == Nt launches nothing. */
+CWM_API int cwm_dev_fill_mask_tokens_ragged(float* x_full_dev, const float* mask_token_dev, const float* pos_dev, const int32_t* perm_dev,
+                                            const int32_t* counts_dev, int B, int Nt, int n_vis_min, int D, void* stream);
 
 /* cwm_unembed (cwm_hip.h) on frames addressed as the engine addresses them: element (b, t, c, y, x) of x at b x_stride_b + t x_stride_t + c x_stride_c + y W + x
  * (rows and pixels contiguous; x_stride_c >= H W).  mask -> permutation -> rank -> launch_unembed: out [B,T,C,H,W] contiguous = y at masked patches, x at visible
@@ -344,6 +361,11 @@ CWM_API int cwm_dev_fill_mask_tokens(float* x_full_dev, const float* mask_token_
  * CWM_ERR_MASK if a row does not have n_vis visible tokens. */
 CWM_API int cwm_dev_unembed(const float* y_tokens_dev, const float* x_dev, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_t, const uint8_t* mask_dev,
                             int B, int T, int C, int H, int W, int P, int n_vis, float* out_dev, void* stream);
+/* The un-embed of a ragged batch (csrc/model.hip forward_lane): rows of n_vis_min .. n_vis visible tokens, y_tokens [B][Nt - n_vis_min][P*P*C] with row j of every
+ * sample = decoder row n_vis_min + j, so a sample's own predictions are its LAST Nt - count rows.  mask -> permutation (launch_mask_to_perm_ragged) -> rank ->
+ * launch_unembed with n_vis = n_vis_min, Nm = Nt - n_vis_min.  CWM_ERR_MASK if a row's count is outside [n_vis_min, n_vis] (out_dev is written all the same). */
+CWM_API int cwm_dev_unembed_ragged(const float* y_tokens_dev, const float* x_dev, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_t, const uint8_t* mask_dev,
+                                   int B, int T, int C, int H, int W, int P, int n_vis_min, int n_vis, float* out_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -87,8 +87,9 @@ def normalized(tok, P):
 
 # ---- the call and the check ------------------------------------------------------------------------------------------------------------------------
 def gather_call(dev, kind, mode, out, ld, B, n_rows, Nt, perm_stride=0, x=None, frames=None, C=0, P=0, normalize=0, flows=None, imu=None, tubelet=0,
-                mask=None, n_vis=0, perm=None, rank=None, err_rows=None):
-    """x: (device buffer, strided CPU view [B, T, C, H, W] of it); flows: two of the same with [B, 2, H, W] views; imu: device [B, C, L]"""
+                mask=None, n_vis=0, perm=None, rank=None, err_rows=None, ragged=None, check=True):
+    """x: (device buffer, strided CPU view [B, T, C, H, W] of it); flows: two of the same with [B, 2, H, W] views; imu: device [B, C, L].
+    ragged = (n_vis_min, counts device tensor or None): through cwm_dev_gather_ragged, n_vis being the cap.  -> the status (raised unless check=False)"""
     a = _lib.new_dev_gather_args()
     a.kind, a.mode, a.normalize = kind, MODES[mode][0], normalize
     if imu is not None:
@@ -110,7 +111,13 @@ def gather_call(dev, kind, mode, out, ld, B, n_rows, Nt, perm_stride=0, x=None, 
         if t is not None:
             setattr(a, name, t.data_ptr())
     a.out, a.ld, a.stream = out.data_ptr(), ld, None
-    _lib.check(dev.cwm_dev_gather(ctypes.byref(a)), dev)
+    if ragged is None:
+        rc = dev.cwm_dev_gather(ctypes.byref(a))
+    else:
+        rc = dev.cwm_dev_gather_ragged(ctypes.byref(a), ragged[0], _lib.ptr(ragged[1]))
+    if check:
+        _lib.check(rc, dev)
+    return rc
 
 
 def check_operand(name, A, ref, exact, mode, rows=None):

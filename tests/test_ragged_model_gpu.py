@@ -204,3 +204,106 @@ def test_generator_predict_on_unequal_rows():
     rect = G.predict(x, md, frame=None)
     assert len(set((~md).sum(1).tolist())) == 1 and not torch.equal(md, mask)
     assert torch.isfinite(rect).all() and (rect.cpu() - torch.from_numpy(g["video"])).abs().max().item() > 2e-4
+
+
+# ---- properties of the ragged forward that the fixtures cannot see (TINY, ragged_tiny.npz) --------------------------------------------------------------
+MODES = ("parity", "fast")
+
+
+@pytest.fixture(scope="module")
+def tiny():
+    """frames, masks and counts of ragged_tiny.npz on the device, and one model per mode"""
+    g = np.load(os.path.join(GOLDEN, "ragged_tiny.npz"))
+    n_vis = g["n_vis"].tolist()
+    assert len(set(n_vis)) >= 3 and max(n_vis) < TINY.num_tokens - 1
+    models = {mode: build(TINY, int(g["seed"]), mode) for mode in MODES}
+    return models, torch.from_numpy(g["x"]).cuda(), torch.from_numpy(g["mask"]).cuda(), n_vis
+
+
+def masked_pixels(mask):
+    """bool [B, T, C, H, W] of the TINY geometry: the pixels of the masked patches"""
+    return O.patches_to_video(mask.cpu()[..., None].expand(-1, -1, 192).float(), 2, 3, 32, 32, 8).bool()
+
+
+def same_bits(a, b):
+    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_ragged_fused_and_unfused_index_prologue_give_the_same_bits(tiny, mode):
+    """The two forms differ in what the padding rows [count, cap) of the embed operand hold (zeros / masked tokens); every launch that reads those rows
+    is row-wise and planned alike, and the attention never stages them: each row's predictions and the video agree bit for bit."""
+    models, x, mask, n_vis = tiny
+    m = models[mode]
+    out = {}
+    try:
+        for fused in (1, 0):
+            m.set_option("index_fused", fused)
+            out[fused] = m.predict_video(x, mask, ragged=True)
+    finally:
+        m.set_option("index_fused", 1)
+    for a, b in zip(own_rows(out[1][0], n_vis, TINY.num_tokens), own_rows(out[0][0], n_vis, TINY.num_tokens)):
+        assert a.shape[0] > 0 and torch.isfinite(a).all() and same_bits(a, b), (mode, (a - b).abs().max().item())
+    assert same_bits(out[1][1], out[0][1])
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_nan_under_the_mask_never_reaches_a_prediction(tiny, mode):
+    """The raw pixels of every masked patch are NaN.  Ragged, fused: they are never read.  Ragged, unfused: the patch gather reads perm[count .. cap), masked
+    tokens, into the padding rows, which are NaN from there on.  Rectangular (equal counts): never read.  Tokens and the masked part of the video are
+    bitwise what the clean input gives, and the video holds no NaN."""
+    models, x, mask, n_vis = tiny
+    m = models[mode]
+    Nt = TINY.num_tokens
+    eq_mask = torch.from_numpy(S.synthetic_masks(4, TINY, 4, 11)).cuda()
+    assert len(set((~eq_mask).sum(1).tolist())) == 1
+    cases = [("ragged fused", mask, dict(ragged=True), 1), ("ragged unfused", mask, dict(ragged=True), 0), ("rectangular", eq_mask, {}, 1)]
+    try:
+        for name, mk, kw, fused in cases:
+            hidden = masked_pixels(mk)
+            xn = x.clone()
+            xn[hidden.cuda()] = float("nan")
+            assert torch.isnan(xn).any() and hidden.any() and not hidden.all()
+            m.set_option("index_fused", fused)
+            y0, v0 = m.predict_video(x, mk, **kw)
+            y1, v1 = m.predict_video(xn, mk, **kw)
+            assert not torch.isnan(v1).any(), (mode, name, "NaN in the video")
+            assert torch.isfinite(y0).all() and same_bits(y1, y0), (mode, name, "tokens")
+            assert same_bits(v1.cpu()[hidden], v0.cpu()[hidden]), (mode, name, "masked part of the video")
+            assert same_bits(v1.cpu()[~hidden], x.cpu()[~hidden]), (mode, name, "visible part of the video")
+    finally:
+        m.set_option("index_fused", 1)
+    assert Nt - max(n_vis) > 0
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_ragged_cap_above_every_count(tiny, mode):
+    """n_vis_range = (lo, Nt - 1): every sample carries padding rows, the encoder's M grows from 4 x 22 to 4 x 31 rows -- other tilings at most, which the
+    file holds to REASSOC_TOL."""
+    models, x, mask, n_vis = tiny
+    m = models[mode]
+    Nt, lo, hi = TINY.num_tokens, min(n_vis), max(n_vis)
+    xp = O.preprocess(x.cpu()).cuda()
+    tight = m(xp, mask, ragged=True, n_vis_range=(lo, hi))
+    loose = m(xp, mask, ragged=True, n_vis_range=(lo, Nt - 1))
+    assert tight.shape == loose.shape == (4, Nt - lo, 192)
+    for b, (a, c) in enumerate(zip(own_rows(tight, n_vis, Nt), own_rows(loose, n_vis, Nt))):
+        d = (a - c).abs().max().item()
+        print("ragged tiny %s row %d: cap %d against cap %d: %.3e" % (mode, b, hi, Nt - 1, d))
+        assert torch.isfinite(c).all() and d <= REASSOC_TOL, (mode, b, d)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_ragged_batch_on_a_dirty_workspace_equals_a_fresh_handle(tiny, mode):
+    """A rectangular batch with large-magnitude inputs -- more samples and more visible tokens than the ragged batch needs, so the workspace is not
+    re-allocated -- leaves every shared buffer full of stale rows; the ragged batch after it is bitwise what a fresh handle computes."""
+    models, x, mask, n_vis = tiny
+    m = models[mode]
+    fresh = build(TINY, 3, mode)
+    y_fresh, v_fresh = fresh.predict_video(x, mask, ragged=True)
+    big = 1e4 * O.preprocess(torch.from_numpy(S.synthetic_frames(6, TINY, 9))).cuda()
+    big_mask = torch.from_numpy(S.synthetic_masks(6, TINY, 8, 9)).cuda()
+    assert int((~big_mask[0]).sum()) > max(n_vis) and big.abs().max().item() > 1e4
+    m(big, big_mask)
+    y, v = m.predict_video(x, mask, ragged=True)
+    assert torch.isfinite(y_fresh).all() and same_bits(y, y_fresh) and same_bits(v, v_fresh), (mode, (y - y_fresh).abs().max().item())
