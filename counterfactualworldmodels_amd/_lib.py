@@ -644,7 +644,7 @@ DEV_SIGNATURES = {
 }
 
 # the keys cwm_model_set_option / cwm_conj_set_option know (include/cwm_hip.h; csrc/engine.hip tuning_field)
-OPTION_KEYS = ("gemm_tile", "gemm_debug", "gemm_staged", "gemm_direct", "attn_kernel", "attn_remap", "attn_tail", "attn_ksplit", "prune_last_block", "index_fused",
+OPTION_KEYS = ("gemm_tile", "gemm_debug", "gemm_staged", "gemm_direct", "attn_kernel", "attn_remap", "attn_tail", "attn_ksplit", "prune_last_block", "mask_token_tables","index_fused",
                "min_lane_rows", "conj_ctx_stream", "conj_attn")
 GEMM_DEBUG_TIMING_ONLY = 1 | 2 | 8  # ablation bits that make a forward return wrong outputs: refused by the production setters (development library: cwm_debug_set)
 

@@ -623,9 +623,12 @@ extern "C" int cwm_dev_gemm(const cwm_dev_gemm_args* args) {
         CWM_REQUIRE(!a.resid_rowmap || a.resid, "cwm_dev_gemm: a residual row map without a residual");
         p.C = a.C; p.ldc = a.ldc; p.resid = a.resid; p.ldr = a.ldr;
     } else if (a.epi == EPI_QKV) {
-        CWM_REQUIRE(a.q_out && a.k_out && a.v_out && a.heads > 0 && a.head_dim > 0 && a.n_tok > 0 && a.N == 3 * a.heads * a.head_dim && a.M % a.n_tok == 0,
-                    "cwm_dev_gemm: the Q/K/V scatter needs the three outputs, N = 3 * heads * head_dim and whole samples of n_tok rows");
-        CWM_REQUIRE(planes == 1 || a.qk_plane >= (int64_t)a.M * a.heads * a.head_dim, "cwm_dev_gemm: the lo plane would overlap the hi plane");
+        CWM_REQUIRE(a.q_out && a.k_out && a.v_out && a.heads > 0 && a.head_dim > 0 && a.n_tok > 0 && a.N == 3 * a.heads * a.head_dim &&
+                        (a.rows_in > 0 ? a.rows_in <= a.n_tok : a.M % a.n_tok == 0),
+                    "cwm_dev_gemm: the Q/K/V scatter needs the three outputs, N = 3 * heads * head_dim and whole samples of n_tok rows (or of their first rows_in)");
+        // (samples of rows_in <= n_tok rows each own n_tok output rows)
+        CWM_REQUIRE(planes == 1 || a.qk_plane >= (int64_t)(a.rows_in > 0 ? a.M / a.rows_in : a.M / a.n_tok) * a.n_tok * a.heads * a.head_dim,
+                    "cwm_dev_gemm: the lo plane would overlap the hi plane");
         p.q_out = (bf16*)a.q_out; p.k_out = (bf16*)a.k_out; p.v_out = (bf16*)a.v_out; p.qk_plane = a.qk_plane;
         p.qkv_dim = a.heads * a.head_dim; p.heads = a.heads; p.head_dim = a.head_dim; p.n_tok = a.n_tok; p.q_scale = a.q_scale;
     } else {

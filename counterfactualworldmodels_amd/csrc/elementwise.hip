@@ -478,6 +478,69 @@ int launch_fill_mask_tokens_ragged(float* x_full, const float* mask_token, const
 }
 
 // ---------------------------------------------------------------------------------------------
+// decoder block 0, masked half of Q / K / V: LN1 and the Q/K/V projection of mask_token + pos[p] depend on the weights and p only, so they come from a
+// table of Nt rows (engine.hip Engine::dec0_table) instead of the GEMM.  A (sample, masked row) is `cpr` = 3 * planes * H * 8 chunks of 16 bytes: chunk c =
+// ((which * planes + pl) * H + h) * 8 + e is elements 8 e .. 8 e + 7 of head h in plane pl of Q / K / V.  FOUR rows per thread, the permutation entries and
+// then the table chunks all requested before the first store (as fill_mask_tokens4_kernel); consecutive lanes copy consecutive chunks, whole 128-byte head rows.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dec0_gather_kernel(const bf16* tab, const int* perm, bf16* q, bf16* k, bf16* v, int64_t qk_plane, int Nt, int n_vis, int H,
+                                                          int planes, int64_t rows, int64_t rows_q) {
+    const int cpr = 3 * planes * H * 8;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= rows_q * cpr) return;
+    const int64_t r0 = gid / cpr;
+    const int c = (int)(gid - r0 * cpr);
+    const int e = c & 7, h = (c >> 3) % H, wp = (c >> 3) / H;  // wp = which * planes + pl
+    const int which = wp / planes, pl = wp - which * planes;
+    const int nm = Nt - n_vis;
+    const bf16* src = tab + ((size_t)wp * H + h) * Nt * 64 + e * 8;
+    bf16* dst = (which == 0 ? q : which == 1 ? k : v) + (size_t)pl * qk_plane + e * 8;
+    constexpr int R = 4;
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+    size_t orow[R];
+    int tau[R];
+    bool live[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const int64_t row = r0 + i * rows_q;
+        live[i] = row < rows;
+        const int64_t rr = live[i] ? row : 0;
+        const int b = (int)(rr / nm), j = n_vis + (int)(rr - (int64_t)b * nm);
+        orow[i] = ((size_t)b * H + h) * Nt + j;
+        tau[i] = perm[(size_t)b * Nt + j];
+    }
+    u32x4 val[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) val[i] = *reinterpret_cast<const u32x4*>(src + (size_t)min(max(tau[i], 0), Nt - 1) * 64);
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+        if (live[i]) *reinterpret_cast<u32x4*>(dst + orow[i] * 64) = val[i];
+}
+
+int launch_dec0_gather(const bf16* tab, const int* perm, bf16* q, bf16* k, bf16* v, int64_t qk_plane, int B, int Nt, int n_vis, int H, int planes, hipStream_t stream) {
+    CWM_REQUIRE(tab && perm && q && k && v && B > 0 && H > 0 && n_vis >= 0 && n_vis <= Nt && (planes == 1 || planes == 2) && qk_plane % 8 == 0,
+                "dec0_gather: bad argument");
+    const int64_t rows = (int64_t)B * (Nt - n_vis), rows_q = (rows + 3) / 4;
+    if (rows == 0) return 0;
+    const int64_t total = rows_q * 3 * planes * H * 8;
+    hipLaunchKernelGGL(dec0_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, tab, perm, q, k, v, qk_plane, Nt, n_vis, H, planes, rows, rows_q);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+__global__ void iota_kernel(int* perm, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) perm[i] = i;
+}
+
+int launch_iota(int* perm, int n, hipStream_t stream) {
+    CWM_REQUIRE(perm && n > 0, "iota: bad argument");
+    hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, perm, n);
+    CWM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Patch un-embed scatter.  Reference: `pred_patches_to_video` (prediction.py:245-259) with
 // `Patchify` (patches.py:74,98-102): feature index f = (ph*P + pw)*C + c; visible patches take the
 // RAW (un-normalised) wrapper input.  One thread per 4 horizontally adjacent output pixels.

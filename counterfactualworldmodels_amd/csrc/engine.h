@@ -146,6 +146,16 @@ struct Engine {
     uint64_t splitk_clock = 0;
     static constexpr size_t kMaxSplitKStreams = 8;
     std::map<hipStream_t, SplitKWs> splitk_ws;  // one split-K workspace per stream that has launched a split GEMM (batch lanes run concurrently); created lazily, capped
+    // Decoder block 0 of the plain VMAE predictor, mask-token rows: LN1 and the Q/K/V projection of mask_token + pos_dec[p] depend on the weights and the token
+    // position p only -- not on the sample, the input or the call -- so they are kept as a table of n_tok rows per arithmetic mode ([fast, parity]) in the
+    // Q / K / V element format: [q hi(, q lo), k hi(, k lo), v hi(, v lo)] planes of [heads][n_tok][64].  Built lazily on the forward's stream by the same
+    // LayerNorm kernel and GEMM launch path as the rows of a forward (rows are independent in both: the same bits); stale after any load_weight.
+    struct Dec0Table {
+        bf16* qkv = nullptr;
+        uint64_t loads = 0;  // Engine::loads when it was built
+        bool built = false;
+    };
+    Dec0Table dec0_tab[2];
 
     ~Engine();
     int alloc(void** p, size_t bytes, bool zero, bool workspace);
@@ -175,7 +185,7 @@ struct Engine {
     int require_weights(const char* fn);                            // CWM_ERR_INVALID naming the first tensor that was never loaded
     int set_option(const char* fn, const char* key, int value);  // cwm_model_set_option / cwm_conj_set_option
 
-    int run_gemm(const GemmParams& p, int planes, hipStream_t s);
+    int run_gemm(const GemmParams& p, int planes, hipStream_t s, bool book = true);  // book = false: not counted by the kernel timers
     int attach_splitk_workspace(GemmParams& p, hipStream_t s);  // this stream's entry of splitk_ws, created or evicted as needed
     int run_attention(const AttnParams& p, int planes, hipStream_t s);
     // the HBM-bound edge kernels, booked by class with their algorithmic bytes (cwm_hip.h CWM_KCLASS_*)
@@ -206,8 +216,13 @@ struct Engine {
                 hipStream_t s, int n_keep = 0);
     // Block.forward (VideoMAE/utils.py:146-153) on a residual stream x[B*n_tok, D] (in place), head_dim 64
     // key_len (device, [B]; nullptr: all n_tok): the keys sample b attends to -- the encoder blocks of a ragged batch (AttnParams.key_len)
+    // tab_rows (with tab_vis, tab_perm; nullptr: off): decoder block 0 of a rectangular batch -- rows [tab_vis, n_tok) of every sample are mask tokens, whose
+    // Q / K / V rows are copied from the table (dec0_table) at the positions tab_perm[b][j]; LN1 and the Q/K/V GEMM run over the first tab_vis rows only
     int run_block(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s, int n_keep = 0,
-                  const int* key_len = nullptr);
+                  const int* key_len = nullptr, const bf16* tab_rows = nullptr, int tab_vis = 0, const int* tab_perm = nullptr);
+    // The table of this mode, (re)built on stream s when it is missing or a weight was loaded since; x_tmp [n_tok][dec_dim] fp32, h_tmp [2][n_tok][dec_dim] bf16 and
+    // perm_tmp [n_tok] are scratch of the caller (workspace buffers nothing on s or behind it still needs)
+    int dec0_table(const StreamW& S, int planes, float* x_tmp, bf16* h_tmp, int* perm_tmp, hipStream_t s, const bf16** tab);
     // same for short sequences with any head_dim (fp32 VALU attention): the IMU context stream
     int run_block_small(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s);
     // the pieces of a stream's forward around its blocks, over B samples of n_vis visible rows each (w: the lane's view)

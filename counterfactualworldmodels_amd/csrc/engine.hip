@@ -72,7 +72,7 @@ static const TuningField* tuning_field(const char* key) {
     typedef TuningField Field;
     static const Field fields[] = {{"gemm_tile", &Tuning::gemm_tile}, {"gemm_debug", &Tuning::gemm_debug}, {"gemm_staged", &Tuning::gemm_staged},
                                    {"gemm_direct", &Tuning::gemm_direct}, {"attn_kernel", &Tuning::attn_kernel}, {"attn_remap", &Tuning::attn_remap},
-                                   {"attn_tail", &Tuning::attn_tail}, {"attn_ksplit", &Tuning::attn_ksplit}, {"prune_last_block", &Tuning::prune_last_block}, {"index_fused", &Tuning::index_fused},
+                                   {"attn_tail", &Tuning::attn_tail}, {"attn_ksplit", &Tuning::attn_ksplit}, {"prune_last_block", &Tuning::prune_last_block}, {"mask_token_tables", &Tuning::mask_token_tables}, {"index_fused", &Tuning::index_fused},
                                    {"min_lane_rows", &Tuning::min_lane_rows}, {"conj_ctx_stream", &Tuning::conj_ctx_stream}, {"conj_attn", &Tuning::conj_attn}};
     for (const Field& f : fields)
         if (!strcmp(key, f.name)) return &f;
@@ -454,7 +454,7 @@ int Engine::attach_splitk_workspace(GemmParams& p, hipStream_t s) {
 
 // One GEMM of the model: planned once (gemm.hip gemm_plan), then launched part by part -- the two kernels of a mixed-tiling launch are booked
 // separately, so that the per-kernel averages of a timed run are those rocprofv3 sees.
-int Engine::run_gemm(const GemmParams& p_in, int planes, hipStream_t s) {
+int Engine::run_gemm(const GemmParams& p_in, int planes, hipStream_t s, bool book) {
     GemmParams p = p_in;
     p.overlapped = overlapped;
     p.tune = &tune;
@@ -464,8 +464,9 @@ int Engine::run_gemm(const GemmParams& p_in, int planes, hipStream_t s) {
         if (int rc = attach_splitk_workspace(p, s)) return rc;
     for (int i = 0; i < plan.nparts; ++i) {
         const GemmPlan::Part& part = plan.part[i];
-        EventPair* e;
-        if (int rc = timer_begin(CWM_KCLASS_GEMM, 2.0 * part.M * (double)p.N * p.K, s, &e)) return rc;
+        EventPair* e = nullptr;
+        if (book)
+            if (int rc = timer_begin(CWM_KCLASS_GEMM, 2.0 * part.M * (double)p.N * p.K, s, &e)) return rc;
         if (e) e->sub = part.kernel == GEMM_KERNEL_8PHASE ? CWM_KCLASS_GEMM_WIDE : CWM_KCLASS_GEMM_NARROW;
         if (int rc = launch_gemm_part(p, planes, plan, i, s)) return rc;
         if (int rc = timer_end(e, s)) return rc;
@@ -624,21 +625,32 @@ int Engine::run_mlp(const float* ln_g, const float* ln_b, const LinearW& fc1, co
 // n_keep (0 = all): only the LAST n_keep tokens of every sample are needed downstream (the last decoder block: the decoder returns
 // head(norm(x[:, -Nm:])), vmae.py:250-251).  Keys / values still come from all tokens; queries, proj, LN2 and the MLP run on the
 // kept rows only (compact activations, residual rows addressed with an offset).  Kept rows are bit-identical to the full block.
-int Engine::run_block(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s, int n_keep, const int* key_len) {
+int Engine::run_block(const BlockW& w, float* x, int B, int n_tok, int D, int H, int planes, StreamBuffers& sb, hipStream_t s, int n_keep, const int* key_len,
+                      const bf16* tab_rows, int tab_vis, const int* tab_perm) {
     const int M = B * n_tok;
     const int64_t hplane = (int64_t)M * D;
     const KeptRows kr(n_tok, n_keep);
+    // the rows LN1 and the Q/K/V projection compute: all, or (decoder block 0 with the table) the first tab_vis of every sample, compact in hbuf
+    const int n_in = tab_rows ? tab_vis : n_tok, Mi = B * n_in;
     int rc;
-    if ((rc = layernorm_to(x, M, D, w.ln1_g, w.ln1_b, sb.hbuf, planes, s))) return rc;
+    LayerNormParams ln;
+    memset(&ln, 0, sizeof(ln));
+    ln.x = x; ln.ldx = D; ln.gamma = w.ln1_g; ln.beta = w.ln1_b; ln.eps = ln_eps; ln.D = D; ln.rows = Mi;
+    ln.out = sb.hbuf; ln.out_plane = (int64_t)Mi * D; ln.ldo = D;
+    if (tab_rows) { ln.rows_out_per_b = n_in; ln.rows_in_per_b = n_tok; ln.in_offset = 0; }
+    if ((rc = run_layernorm(ln, planes, s))) return rc;
 
-    GemmParams g = gemm_base(sb.hbuf, D, w.qkv, M, planes);
+    GemmParams g = gemm_base(sb.hbuf, D, w.qkv, Mi, planes);
     g.epi = EPI_QKV;
-    g.rows_in = n_tok; g.rows_out = n_tok; g.map_stride = n_tok;
+    g.rows_in = n_in; g.rows_out = n_tok; g.map_stride = n_tok;
     g.q_out = sb.qbuf; g.k_out = sb.kbuf; g.v_out = sb.vbuf;
     g.qk_plane = hplane;
     g.qkv_dim = D; g.heads = H; g.head_dim = D / H; g.n_tok = n_tok;
-    g.q_scale = 1.0f / sqrtf((float)(D / H));
-    if ((rc = run_gemm(g, planes, s))) return rc;
+    g.q_scale = 1.0f / sqrtf((float)(D / H));    if ((rc = run_gemm(g, planes, s))) return rc;
+    if (tab_rows && (rc = timed(CWM_KCLASS_FILL_MASK, (double)B * (n_tok - n_in) * 3.0 * D * 2.0 * planes, s, [&] {
+                         return launch_dec0_gather(tab_rows, tab_perm, sb.qbuf, sb.kbuf, sb.vbuf, hplane, B, n_tok, n_in, H, planes, s);
+                     })))
+        return rc;
 
     AttnParams a;
     memset(&a, 0, sizeof(a));
@@ -701,6 +713,42 @@ int Engine::to_decoder(const StreamW& S, const StreamWs& w, int B, int n_vis, in
         return timed(CWM_KCLASS_FILL_MASK, (double)B * (next - n_vis_min) * S.dec_dim * 4.0, s,
                      [&] { return launch_fill_mask_tokens_ragged(w.x_dec, S.mask_token, S.pos_dec_ext, w.perm, counts, B, next, n_vis_min, S.dec_dim, s); });
     return run_fill_mask_tokens(w.x_dec, S.mask_token, S.pos_dec_ext, w.perm, B, next, n_vis, S.dec_dim, s);  // (no launch when nothing is masked)
+}
+
+// Row p of the table = what decoder block 0 computes for a mask token at position p: x = mask_token + pos_dec[p] (the fill kernel over the identity
+// permutation), LN1, the Q/K/V projection with its scatter (one sample of n_tok tokens) -- the forward's own kernels, whose rows are independent of each other.
+// (Not booked by the kernel timers: it runs once per weight set, not per forward.)
+int Engine::dec0_table(const StreamW& S, int planes, float* x_tmp, bf16* h_tmp, int* perm_tmp, hipStream_t s, const bf16** tab) {
+    Dec0Table& t = dec0_tab[planes - 1];
+    const int Nt = S.n_tok, D = S.dec_dim, H = S.dec_heads;
+    const int64_t plane = (int64_t)Nt * D;
+    if (!t.qkv) {
+        void* p = nullptr;
+        if (int rc = alloc(&p, (size_t)3 * planes * plane * sizeof(bf16), true, false)) return rc;
+        CWM_HIP_CHECK(hipDeviceSynchronize());  // (the zero fill ran on the null stream, which a non-blocking stream does not wait for)
+        t.qkv = (bf16*)p;
+    }
+    *tab = t.qkv;
+    if (t.built && t.loads == loads) return 0;
+    const BlockW& w = S.dec[0];
+    int rc;
+    if ((rc = launch_iota(perm_tmp, Nt, s)) || (rc = launch_fill_mask_tokens(x_tmp, S.mask_token, S.pos_dec_ext, perm_tmp, 1, Nt, 0, D, s))) return rc;
+    LayerNormParams ln;
+    memset(&ln, 0, sizeof(ln));
+    ln.x = x_tmp; ln.ldx = D; ln.gamma = w.ln1_g; ln.beta = w.ln1_b; ln.eps = ln_eps; ln.D = D; ln.rows = Nt;
+    ln.out = h_tmp; ln.out_plane = plane; ln.ldo = D;
+    if ((rc = launch_layernorm(ln, planes, s))) return rc;
+    GemmParams g = gemm_base(h_tmp, D, w.qkv, Nt, planes);
+    g.epi = EPI_QKV;
+    g.rows_in = Nt; g.rows_out = Nt; g.map_stride = Nt;
+    g.q_out = t.qkv; g.k_out = t.qkv + planes * plane; g.v_out = t.qkv + 2 * planes * plane;
+    g.qk_plane = plane;
+    g.qkv_dim = D; g.heads = H; g.head_dim = D / H; g.n_tok = Nt;
+    g.q_scale = 1.0f / sqrtf((float)(D / H));
+    if ((rc = run_gemm(g, planes, s, false))) return rc;
+    t.built = true;
+    t.loads = loads;
+    return 0;
 }
 
 int Engine::head_rows(const StreamW& S, const StreamWs& w, int B, int n_out, float* out, int planes, hipStream_t s) {

@@ -324,8 +324,15 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && BN == 128 && WM * WN ==
 // waves 4-7 rows 64-127), so one phase after the reads suffices; W half-tiles are read by both groups, and
 // the leading group re-stages them two phases after the read (W0 read in P1 -> staged in P3, W1 P2 -> P4).
 
-// One 256x256 tile (HALF: its columns 128 .. 255 are all padding -- see above) of the 8-phase kernel.
-template <int PLANES, bool HALF>
+// Half-height row tile (round 7): when the tile's rows 128 .. 255 all lie past M (M mod 256 in 1 .. 128: the 16 x 792 = 12672 encoder rows of a lane,
+// 49.5 row tiles), the quadrants (1, .) are all padding -- their MFMA clusters, their A1 fragment reads and the A1 half-tile's LDS-DMA are skipped.  Every
+// barrier stays, so the hand-off reasoning below is unchanged; a K tile issues three half-tiles (A0, W0, W1 of tile t + 2), all of them after tile t + 1's
+// last piece: the counted wait is a vmcnt(4) in FRONT of the W1 pieces (A0 and W0 of tile t + 2 stay in flight across it, W1 follows it), and the
+// epilogue runs over the two pieces that hold rows.  Same product sequence per accumulator: bit-identical.  ("gemm_debug" bit 2048 restores the full
+// tile; a tile that is both ragged in rows and half-width runs as the half-width instance.)
+
+// One 256x256 tile (HALF: its columns 128 .. 255 are all padding; HALF_M: its rows 128 .. 255 are -- see above) of the 8-phase kernel.
+template <int PLANES, bool HALF, bool HALF_M = false>
 __device__ __forceinline__ void gemm8p_tile(const GemmParams& p, char* smem, int m0, int n0) {
     GEMM_PROF_BEGIN();
     constexpr int HALF_BYTES = 128 * 128;      // 128 rows x 128 B
@@ -425,7 +432,20 @@ __device__ __forceinline__ void gemm8p_tile(const GemmParams& p, char* smem, int
     const int nk = p.K / (64 / PLANES);
     // ---- prologue: all of tile 0, then A0 / W0 / W1 of tile 1 ----
     // (the waits leave tile 1's pieces in flight: three half-tiles = 6 pieces, two = 4 for a half-width tile)
-    if constexpr (!HALF) {
+    static_assert(!(HALF && HALF_M), "a tile is half-width or half-height, not both");
+    if constexpr (HALF_M) {
+        stage(H_A0{}, 0, 0);
+        stage(H_W0{}, 0, 0);
+        stage(H_W1{}, 0, 0);
+        if (nk > 1) {
+            stage(H_A0{}, 1, 1);
+            stage(H_W0{}, 1, 1);
+            stage(H_W1{}, 1, 1);
+            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    } else if constexpr (!HALF) {
         stage(H_A0{}, 0, 0);
         stage(H_W0{}, 0, 0);
         stage(H_W1{}, 0, 0);
@@ -459,7 +479,8 @@ __device__ __forceinline__ void gemm8p_tile(const GemmParams& p, char* smem, int
         // ---- P1: quadrant (0, 0) ----
         read_w(base, 0, bw0);
         read_a(base, 0);
-        if (t + 1 < nk) stage(H_A1{}, buf ^ 1, t + 1);
+        if constexpr (!HALF_M)
+            if (t + 1 < nk) stage(H_A1{}, buf ^ 1, t + 1);
         CWM_PHASE_BARRIER();
         mfma_quadrant(acc[0][0], bw0);
         CWM_PHASE_BARRIER();
@@ -470,22 +491,26 @@ __device__ __forceinline__ void gemm8p_tile(const GemmParams& p, char* smem, int
         if constexpr (!HALF) mfma_quadrant(acc[0][1], bw1);
         CWM_PHASE_BARRIER();
         // ---- P3: quadrant (1, 1) ----
-        read_a(base, 1);
+        if constexpr (!HALF_M) read_a(base, 1);
         if (t + 2 < nk) stage(H_W0{}, buf, t + 2);
         CWM_PHASE_BARRIER();
-        if constexpr (!HALF) mfma_quadrant(acc[1][1], bw1);
+        if constexpr (!HALF && !HALF_M) mfma_quadrant(acc[1][1], bw1);
         CWM_PHASE_BARRIER();
-        // ---- P4: quadrant (1, 0); retire tile t+1 (A1(t+1) was issued in P1: the two / three half-tiles issued since may stay in flight) ----
+        // ---- P4: quadrant (1, 0); retire tile t+1 (A1(t+1) was issued in P1: the two / three half-tiles issued since may stay in flight; a
+        // half-height tile has no A1 and issued tile t+1's last piece in P4(t-1): the three half-tiles of this K tile may stay in flight) ----
         if (t + 2 >= nk) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         } else if constexpr (HALF) {
             asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        } else if constexpr (HALF_M) {
+            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // A0(t+2) and W0(t+2) stay in flight; W1(t+1), the last piece of tile t+1, has landed
+            stage(H_W1{}, buf, t + 2);
         } else {
             stage(H_W1{}, buf, t + 2);
             asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         }
         CWM_PHASE_BARRIER();
-        mfma_quadrant(acc[1][0], bw0);
+        if constexpr (!HALF_M) mfma_quadrant(acc[1][0], bw0);
         CWM_PHASE_BARRIER();
     }
     if (wr == 0) CWM_PHASE_BARRIER();  // balance the stagger barrier
@@ -514,6 +539,9 @@ __device__ __forceinline__ void gemm8p_tile(const GemmParams& p, char* smem, int
         if constexpr (HALF)
             epilogue_direct<PLANES, 2>(
                 p, [&](int pi, int i, int j) { return acc[pi][0][i][j]; }, [&](int pi) { return pi * 128 + wr * 64; }, [&](int) { return n0 + wc * 32; }, tab, lane);
+        else if constexpr (HALF_M)
+            epilogue_direct<PLANES, 2>(
+                p, [&](int pi, int i, int j) { return acc[0][pi][i][j]; }, [&](int) { return wr * 64; }, [&](int pi) { return n0 + pi * 128 + wc * 32; }, tab, lane);
         else
             epilogue_direct<PLANES, 4>(
                 p, [&](int pi, int i, int j) { return acc[pi >> 1][pi & 1][i][j]; }, [&](int pi) { return (pi >> 1) * 128 + wr * 64; },
@@ -529,6 +557,10 @@ __device__ __forceinline__ void gemm8p_tile(const GemmParams& p, char* smem, int
             epilogue_piece_seq<PLANES, 2>(
                 p, [&](int pi, int i, int j) { return acc[pi][0][i][j]; }, [&](int pi) { return pi * 128 + wr * 64; }, [&](int) { return n0 + wc * 32; },
                 smem + wave * 8192, tab, lane);
+        else if constexpr (HALF_M)
+            epilogue_piece_seq<PLANES, 2>(
+                p, [&](int pi, int i, int j) { return acc[0][pi][i][j]; }, [&](int) { return wr * 64; }, [&](int pi) { return n0 + pi * 128 + wc * 32; },
+                smem + wave * 8192, tab, lane);
         else
             epilogue_piece_seq<PLANES, 4>(
                 p, [&](int pi, int i, int j) { return acc[pi >> 1][pi & 1][i][j]; }, [&](int pi) { return (pi >> 1) * 128 + wr * 64; },
@@ -538,7 +570,7 @@ __device__ __forceinline__ void gemm8p_tile(const GemmParams& p, char* smem, int
     }
     const int ncol = (lane >> 4) * 4;
 #pragma unroll
-    for (int qm = 0; qm < 2; ++qm)
+    for (int qm = 0; qm < (HALF_M ? 1 : 2); ++qm)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int m = m0 + qm * 128 + wr * 64 + i * 16 + (lane & 15);
@@ -568,9 +600,10 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmParams p) {
     const int gm = min(tiles_m - first_m, GROUP_M);
     const int in_g = id - g * group_sz;
     const int m0 = (first_m + (in_g % gm)) * 256, n0 = (in_g / gm) * 256;
-    // two instances of the tile, chosen once per workgroup (launch-uniform per tile column): each has its own main loop with ONE counted wait --
-    // no branch on the tile kind inside the loops (tools/asm_lds_lint.py checks the two loops against their own piece counts)
+    // three instances of the tile, chosen once per workgroup (launch-uniform per tile column / tile row): each has its own main loop with ONE counted
+    // wait -- no branch on the tile kind inside the loops (tools/asm_lds_lint.py checks the three loops against their own piece counts)
     if (n0 + 128 >= p.N && !(p.debug & 1024)) gemm8p_tile<PLANES, true>(p, smem, m0, n0);
+    else if (m0 + 128 >= p.M && !(p.debug & 2048)) gemm8p_tile<PLANES, false, true>(p, smem, m0, n0);
     else gemm8p_tile<PLANES, false>(p, smem, m0, n0);
 }
 
@@ -612,7 +645,8 @@ int gemm_plan(const GemmParams& p, int planes, int forced_cfg, int cus, GemmPlan
     if (p.epi == EPI_F32) {
         CWM_REQUIRE(p.ldc % 4 == 0 && (!p.resid || p.ldr % 4 == 0), "gemm: ldc/ldr must be multiples of 4");
     } else if (p.epi == EPI_QKV) {
-        CWM_REQUIRE(p.rows_in == p.n_tok && p.N == 3 * p.qkv_dim && p.head_dim % 4 == 0, "gemm: bad QKV epilogue setup");
+        // (rows_in < n_tok: every sample's first rows_in tokens only -- decoder block 0 computes the visible rows and copies the rest from a table)
+        CWM_REQUIRE(p.rows_in > 0 && p.rows_in <= p.n_tok && p.N == 3 * p.qkv_dim && p.head_dim % 4 == 0, "gemm: bad QKV epilogue setup");
         CWM_REQUIRE(p.qkv_dim % 16 == 0, "gemm: QKV epilogue needs the model width (%d) to be a multiple of 16", p.qkv_dim);
     } else {
         CWM_REQUIRE(p.ldo % 4 == 0, "gemm: ldo must be a multiple of 4");

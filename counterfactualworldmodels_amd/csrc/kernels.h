@@ -13,7 +13,8 @@ struct Tuning {
     int gemm_debug = 0;    // bit mask of ablations / A-B switches: 1 skip the epilogue's global stores, 2 skip the epilogue, 4 no 4-stage ring for small launches,
                            // 8 skip every LayerNorm launch (timing only), 32 no split-K, 128 the one-lane tile choice also inside a two-lane call, 256 small launches keep
                            // 128-row tiles where the default takes 64x128 ones, 512 bf16-output GEMMs with K < 512 stay on 128x128 tiles, 1024 no half-width column tiles in the
-                           // 8-phase kernel (and N = 384 back on 128x128 tiles)
+                           // 8-phase kernel (and N = 384 back on 128x128 tiles), 2048 no half-height row tiles in the 8-phase kernel (a ragged last row tile of at most
+                           // 128 rows runs as a full tile)
     int gemm_staged = 1;   // 0: the per-fragment epilogue of round 1 everywhere (it stays the fallback for unaligned widths)
     int gemm_direct = 1;   // 1: bf16-output epilogues store 16 bytes per lane straight from the accumulators; 2: the fp32-output ones too; 0: LDS-staged everywhere
     int attn_kernel = 0;   // 0 automatic, 1: 4-wave kernel (attention.hip), 3: software-pipelined kernel (attention_pipe.hip)
@@ -22,6 +23,7 @@ struct Tuning {
     int attn_ksplit = 1;   // 0: a nearly empty last round of workgroups runs its items whole instead of cutting them into key ranges
     int index_fused = 1;       // 0: the index prologue as the four launches of rounds 1-4 (memset, mask_to_perm, patch_gather, perm_to_rank) instead of one
     int prune_last_block = 1;  // 0: the last decoder block runs over all tokens
+    int mask_token_tables = 1; // 0: decoder block 0 runs LN1 and the Q/K/V projection over the mask-token rows too instead of copying them from the per-position table
     int min_lane_rows = 0;     // encoder rows per half batch from which a forward splits into two lanes; 0: the model family's default (engine.h)
     int conj_ctx_stream = 1;   // 0: the IMU-conditioned model's context stream on the lane's own stream
     int conj_attn = 1;         // 0: the fp32 VALU cross / context attention kernels instead of the MFMA ones
@@ -216,6 +218,13 @@ int launch_fill_mask_tokens(float* x_full, const float* mask_token, const float*
 // the same for rows [counts[b], Nt) of sample b (counts[b] >= n_vis_min; rows below n_vis_min are never touched)
 int launch_fill_mask_tokens_ragged(float* x_full, const float* mask_token, const float* pos, const int* perm, const int* counts, int B, int Nt, int n_vis_min,
                                    int D, hipStream_t stream);
+
+// Decoder block 0's Q / K / V rows of the mask tokens, copied from the per-position table (engine.hip Engine::dec0_table):
+// {q, k, v}[pl * qk_plane + ((b * H + h) * Nt + j) * 64 ..] = tab[(which * planes + pl) * Nt * H * 64 + (h * Nt + perm[b * Nt + j]) * 64 ..] for j in [n_vis, Nt),
+// planes = 1 (fast: hi only) or 2 (hi, lo).  16-byte copies; a perm entry outside [0, Nt) is clamped.
+int launch_dec0_gather(const bf16* tab, const int* perm, bf16* q, bf16* k, bf16* v, int64_t qk_plane, int B, int Nt, int n_vis, int H, int planes, hipStream_t stream);
+// perm[i] = i for i < n (the table's own rows are the token positions in order)
+int launch_iota(int* perm, int n, hipStream_t stream);
 
 struct UnembedParams {
     const float* y;  // [B][Nm][P*P*C], feature order (ph, pw, c)

@@ -122,7 +122,8 @@ extern "C" int cwm_model_missing_weights(cwm_model* m, char* buf, int buflen) { 
 // Le + 1 = encoder norm + encoder_to_decoder + mask tokens; Le + 2 .. Le + 1 + Ld = decoder blocks; Le + Ld + 2 = norm + head + un-embed.
 // (cwm_forward issues stage by stage over all lanes, so that after a host synchronisation every lane's queue starts filling at once
 // instead of lane 1 waiting behind lane 0's ~136 launches.)
-static int forward_lane(cwm_model* m, const cwm_forward_args* a, int b0, int B, ModelWs lw, hipStream_t s, int stage_lo, int stage_hi) {
+// dec0_tab (nullptr: off): the mask-token rows of decoder block 0's Q / K / V come from this table (Engine::dec0_table) instead of LN1 and the GEMM
+static int forward_lane(cwm_model* m, const cwm_forward_args* a, int b0, int B, ModelWs lw, hipStream_t s, int stage_lo, int stage_hi, const bf16* dec0_tab) {
     const cwm_config& c = m->cfg;
     const StreamW& S = m->st;
     StreamWs& w = lw.st;
@@ -174,7 +175,8 @@ static int forward_lane(cwm_model* m, const cwm_forward_args* a, int b0, int B, 
     const bool pruned = Nm > 0 && E.tune.prune_last_block;
     for (int i = 0; i < c.dec_depth; ++i) {
         const int keep = (i == c.dec_depth - 1 && pruned) ? Nm : 0;
-        if (in_range(st_e2d + 1 + i) && (rc = E.run_block(S.dec[i], w.x_dec, B, Nt, S.dec_dim, S.dec_heads, planes, w.sb, s, keep))) return rc;
+        const bf16* tab = i == 0 ? dec0_tab : nullptr;
+        if (in_range(st_e2d + 1 + i) && (rc = E.run_block(S.dec[i], w.x_dec, B, Nt, S.dec_dim, S.dec_heads, planes, w.sb, s, keep, nullptr, tab, Nv, w.perm))) return rc;
     }
     if (!in_range(st_head)) return CWM_OK;
     if ((rc = E.head_rows(S, w, B, Nret, y_tokens, planes, s))) return rc;
@@ -217,6 +219,11 @@ extern "C" int cwm_forward(cwm_model* m, const cwm_forward_args* a_in) {
     if (int rc = m->eng.require_weights("cwm_forward")) return rc;
     if (int rc = ensure_workspace(m, B, Nv)) return rc;
     hipStream_t s = (hipStream_t)a->stream;
+    // Decoder block 0's mask-token rows from the per-position table (option "mask_token_tables"; a rectangular batch with masked tokens): looked up -- after a weight
+    // load, rebuilt -- on the caller's stream before the lanes fork, in the first lane's workspace, which stage 0 then overwrites
+    const bf16* dec0_tab = nullptr;
+    if (m->eng.tune.mask_token_tables && Nm > 0 && m->ragged_min == 0)
+        if (int rc = m->eng.dec0_table(m->st, a->mode == CWM_MODE_PARITY ? 2 : 1, m->ws.st.x_dec, m->ws.st.sb.hbuf, m->ws.st.perm, s, &dec0_tab)) return rc;
 
     // Batch lanes: between two dependent kernels the queue idles ~6 us (x 136 kernels = 5 % of a batch-32 step) and every kernel ends in a
     // partially filled round of workgroups; further, independent slices of the batch on other queues fill both.
@@ -232,7 +239,7 @@ extern "C" int cwm_forward(cwm_model* m, const cwm_forward_args* a_in) {
     const int n_stages = c.enc_depth + c.dec_depth + 3;
     for (int st = 0; st < n_stages && !rc; ++st)
         for (int l = 0; l < n_lanes && !rc; ++l)
-            rc = forward_lane(m, a, first[l], first[l + 1] - first[l], lane_ws(m, first[l]), m->lane_set.stream(l, s), st, st + 1);
+            rc = forward_lane(m, a, first[l], first[l + 1] - first[l], lane_ws(m, first[l]), m->lane_set.stream(l, s), st, st + 1, dec0_tab);
     m->eng.overlapped = 0;
     if (int jrc = m->lane_set.join(s)) return jrc;  // (even after a failed launch)
     if (rc) return rc;

@@ -122,13 +122,16 @@ CWM_API int cwm_model_set_ragged(cwm_model* m, int n_vis_min);
  *   "gemm_direct"  1: bf16-output epilogues store 16 bytes per lane straight from the accumulators; 2: the fp32-output ones too; 0: LDS-staged
  *   "gemm_staged"  0: the per-fragment epilogue of round 1
  *   "gemm_debug"   bit mask of result-preserving A/B switches: 4 no 4-stage ring for small launches, 32 no split-K, 128 the one-lane tile choice also inside a two-lane call, 256 small launches
- *                  keep 128-row tiles, 512 bf16-output GEMMs with K < 512 stay on 128x128 tiles, 1024 no half-width column tiles in the 8-phase kernel
+ *                  keep 128-row tiles, 512 bf16-output GEMMs with K < 512 stay on 128x128 tiles, 1024 no half-width column tiles in the 8-phase kernel,
+ *                  2048 no half-height row tiles in the 8-phase kernel
  *   "attn_kernel"  0 automatic, 1: 4-wave kernel, 3: software-pipelined kernel
  *   "attn_remap"   0: plain workgroup order instead of one XCD per (batch, head) with the ragged query tiles last
  *   "attn_tail"    0: the regular schedule also for a ragged last query tile of <= 32 rows
  *   "attn_ksplit"  0: a nearly empty last round of workgroups runs its items whole instead of cutting them into key ranges
  *   "index_fused"       0: the index prologue (mask -> permutation, its inverse, the row check, the patch gather) as the four launches of rounds 1-4
  *   "prune_last_block"  0: the last decoder block runs over all tokens
+ *   "mask_token_tables" 0: the first decoder block computes LN1 and Q / K / V of the mask-token rows in every call instead of copying them from a per-position
+ *                       table built once per weight set and mode (plain predictor, rectangular batches with masked tokens; outputs bit-identical)
  *   "min_lane_rows"     encoder rows per half batch from which a forward splits into two lanes (0: the default, 3000 / 12000 for the IMU model)
  *   "conj_attn"         0: the fp32 VALU cross / context attention kernels of the IMU-conditioned model instead of the MFMA ones
  *   "conj_ctx_stream"   0: the IMU-conditioned model's context stream on the lane's own stream instead of a side stream */

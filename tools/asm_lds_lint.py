@@ -133,7 +133,9 @@ def vmcnt_spec(kernel):
     m = re.search(r"gemm8p_kernelILi(\d)E", kernel)
     if m:  # P1: A1(t+1)  P2: A0(t+2)  P3: W0(t+2)  P4: W1(t+2), two pieces per wave each; vmcnt(6) leaves the three youngest half-tiles in flight.
         # Half-width column tiles (round 5) skip W1: three half-tiles per K tile, vmcnt(4) leaves the two youngest in flight
-        return {"loop": {6: (8, 8), 4: (6, 6)}, "prologue": [(14, 6), (10, 4)]}
+        # Half-height row tiles (round 7) skip A1: three half-tiles per K tile (A0, W0, W1 of tile t+2), all younger than tile t+1's last piece; the wait
+        # stands BEFORE the W1 pieces, so it is a vmcnt(4) with four of the six pieces in front of it ("loop_alt": a second variant of an immediate)
+        return {"loop": {6: (8, 8), 4: (6, 6)}, "loop_alt": {4: [(6, 4)]}, "prologue": [(14, 6), (10, 4), (12, 6)]}
     m = re.search(r"gemm_bf16_kernelILi(\d)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", kernel)
     if m:
         _, bm, bn, wm, wn, stages = (int(x) for x in m.groups())
@@ -256,8 +258,10 @@ def lint_vmcnt(text):
                 for t in nxt:
                     stack.append((t, n2, waits2, True))
             for imm, (n, before, ln) in sorted(best.items()):
-                seen_loop_imms.add(imm)
+                seen_loop_imms.add((imm, (n, before)))
                 want = spec["loop"].get(imm)
+                if (n, before) in spec.get("loop_alt", {}).get(imm, ()):
+                    continue
                 if want is None:
                     hits.append((kernel, ln, "counted wait vmcnt(%d) is not one the source places in this loop (%s)" % (imm, sorted(spec["loop"]))))
                 elif (n, before) != want:
@@ -270,9 +274,9 @@ def lint_vmcnt(text):
                              "the loop holds %d LDS-DMA instructions, the source issues %d per iteration (a duplicated or hoisted piece?)" % (static, per_iter)))
             if paths == 0:
                 hits.append((kernel, blocks[start]["ins"][0][0] if blocks[start]["ins"] else 0, "no path around the loop with the counted wait was found"))
-        for imm in spec["loop"]:
-            if imm not in seen_loop_imms:
-                hits.append((kernel, 0, "the source's loop wait vmcnt(%d) was not found on any path around a loop" % imm))
+        for imm, v in [(imm, v) for imm, v in spec["loop"].items()] + [(imm, v) for imm, vs in spec.get("loop_alt", {}).items() for v in vs]:
+            if (imm, v) not in seen_loop_imms:
+                hits.append((kernel, 0, "the source's loop wait vmcnt(%d) (%d / %d pieces) was not found on any path around a loop" % (imm, v[0], v[1])))
         # rule c: the prologue waits.  The code in front of a main loop is scanned in LAYOUT order (its branches re-test launch-uniform conditions --
         # K of one tile? -- that a path enumeration cannot relate to each other; the source issues the pieces and the wait in one straight sequence, and
         # that is what the text must show): pieces from the region's start up to each counted wait; any other vector-memory instruction between the
