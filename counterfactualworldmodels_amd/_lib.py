@@ -86,6 +86,36 @@ class CwmForwardArgs(C.Structure):
     ]
 
 
+class CwmPatchErrorArgs(C.Structure):
+    """cwm_patch_error_args (include/cwm_hip.h); new_patch_error_args() sets struct_size"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("y_tokens_dev", C.c_void_p),
+        ("x_dev", C.c_void_p),
+        ("x_stride_b", C.c_int64),
+        ("x_stride_t", C.c_int64),
+        ("x_stride_c", C.c_int64),
+        ("target_dev", C.c_void_p),
+        ("target_stride_b", C.c_int64),
+        ("target_stride_t", C.c_int64),
+        ("target_stride_c", C.c_int64),
+        ("mask_dev", C.c_void_p),
+        ("region_dev", C.c_void_p),
+        ("batch", C.c_int32),
+        ("T", C.c_int32),
+        ("C", C.c_int32),
+        ("H", C.c_int32),
+        ("W", C.c_int32),
+        ("P", C.c_int32),
+        ("n_vis", C.c_int32),
+        ("frame", C.c_int32),
+        ("map_dev", C.c_void_p),
+        ("mean_dev", C.c_void_p),
+        ("scratch_dev", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
 class CwmConjConfig(C.Structure):
     _fields_ = [
         ("main", CwmConfig),
@@ -512,6 +542,12 @@ def new_forward_args() -> CwmForwardArgs:
     return a
 
 
+def new_patch_error_args() -> CwmPatchErrorArgs:
+    a = CwmPatchErrorArgs()
+    a.struct_size = C.sizeof(CwmPatchErrorArgs)
+    return a
+
+
 def new_conj_forward_args() -> CwmConjForwardArgs:
     a = CwmConjForwardArgs()
     a.struct_size = C.sizeof(CwmConjForwardArgs)
@@ -557,6 +593,7 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     ),
+    "cwm_patch_error": (C.c_int, [C.POINTER(CwmPatchErrorArgs)]),
     "cwm_mask_row_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_mask_flip_picks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cwm_prompt_table_expand": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),

@@ -238,6 +238,27 @@ struct UnembedParams {
 
 int launch_unembed(const UnembedParams& p, hipStream_t stream);
 
+// Per-patch squared error of the prediction against target frames, from the predicted tokens (elementwise.hip patch_error_map_kernel):
+// map[b][t][i][j] = (1 / P^2) sum_{pixels of patch (i,j)} sum_c (pred_f - target_t)^2, pred_f = frame f of what launch_unembed would build (f = frame, or t when
+// frame < 0); mean[b] = sum(map * region) / max(sum(region), 1).  No allocation, no synchronisation, no atomics: two calls on the same inputs are bit-equal.
+struct PatchErrorParams {
+    const float* y;        // [B][Nm][P*P*C], feature order (ph, pw, c), as UnembedParams::y; the row of a masked token is its rank among the row's masked tokens
+    const float* x;        // frames, element (b,t,c,y,x) at b*sb + t*st + c*sc + y*W + x
+    int64_t sb, st, sc;
+    const float* target;   // the same with tb / tt / tc; nullptr = x
+    int64_t tb, tt, tc;
+    const uint8_t* mask;   // [B][Nt]
+    const float* region;   // [B][T][H/P][W/P] weights; nullptr = ones
+    int B, T, C, H, W, P;  // C <= 8, P in {4, 8, 16}
+    int n_vis, Nm;         // Nm = Nt - n_vis rows of y per sample; the row index is clamped into [0, Nm)
+    int frame;             // predicted frame compared with EVERY target frame, or -1: frame t with target frame t
+    float* map;            // [B][T][H/P][W/P] or nullptr
+    float* mean;           // [B] or nullptr
+    float* scratch;        // [B][T][H/P][W/P]: holds the map when only the mean is asked for (map == nullptr)
+};
+
+int launch_patch_error(const PatchErrorParams& p, hipStream_t stream);
+
 struct ShiftPromptParams {
     const float* x;         // [B][T][C][H][W] contiguous frames
     int B, S, T, C, H, W, P, frame, fix_passive;

@@ -547,6 +547,22 @@ extern "C" int cwm_unembed(const float* y_tokens_dev, const float* x_dev, const 
     return CWM_OK;
 }
 
+extern "C" int cwm_patch_error(const cwm_patch_error_args* a) {
+    CWM_REQUIRE(a && a->struct_size == sizeof(cwm_patch_error_args), "cwm_patch_error: args->struct_size must be sizeof(cwm_patch_error_args)");
+    CWM_REQUIRE(a->x_dev && a->mask_dev && a->batch > 0, "cwm_patch_error: x_dev, mask_dev and a positive batch are required");
+    PatchErrorParams p;
+    memset(&p, 0, sizeof(p));
+    p.y = a->y_tokens_dev;
+    p.x = a->x_dev; p.sb = a->x_stride_b; p.st = a->x_stride_t; p.sc = a->x_stride_c;
+    p.target = a->target_dev; p.tb = a->target_stride_b; p.tt = a->target_stride_t; p.tc = a->target_stride_c;
+    p.mask = a->mask_dev; p.region = a->region_dev;
+    p.B = a->batch; p.T = a->T; p.C = a->C; p.H = a->H; p.W = a->W; p.P = a->P;
+    p.n_vis = a->n_vis; p.frame = a->frame;
+    if (p.P > 0 && p.T > 0 && p.H > 0 && p.W > 0) p.Nm = p.T * (p.H / p.P) * (p.W / p.P) - p.n_vis;  // (launch_patch_error checks the sizes themselves)
+    p.map = a->map_dev; p.mean = a->mean_dev; p.scratch = a->scratch_dev;
+    return launch_patch_error(p, (hipStream_t)a->stream);
+}
+
 extern "C" int cwm_mask_row_counts(const uint8_t* mask_dev, int B, int Nt, int32_t* counts_dev, void* stream) {
     CWM_REQUIRE(mask_dev && counts_dev && B > 0 && Nt > 0, "cwm_mask_row_counts: bad argument");
     return launch_mask_row_counts(mask_dev, B, Nt, counts_dev, (hipStream_t)stream);

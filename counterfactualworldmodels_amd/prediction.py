@@ -328,7 +328,7 @@ class PredictorBasedGenerator(nn.Module):
                 self.reset_padding_masks()  # like the reference, prediction.py:451-452)
         return out if fused else (pieces[0] if len(pieces) == 1 else torch.cat(pieces, 0))
 
-    def _as_rect(self, x, mask, row_kwargs=None, extra_args=(), for_video=False) -> _RectBatch:
+    def _as_rect(self, x, mask, row_kwargs=None, extra_args=(), for_video=False, alloc_video=True) -> _RectBatch:
         """Equalise the masked count over the rows the way the reference does for every multi-row call (prediction.py:421):
         in place, on torch's global RNG, and -- the one host sync -- remember the count."""
         # Host work that does not depend on the mask goes FIRST: the read-back below waits for everything queued on the stream (the previous
@@ -338,7 +338,8 @@ class PredictorBasedGenerator(nn.Module):
         if for_video and x.is_cuda and x.dim() == 5 and self._uses_fused_path(extra_args, row_kwargs or {}):
             self.predictor.sync_weights(x.device)
             synced = True
-            out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+            if alloc_video:  # (False: the fused call wants the tokens only -- `_region_error_fused`)
+                out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
         n_masked, n_vis_range = None, None
         if x.size(0) > 1:
             if self.ragged_batches:
@@ -378,6 +379,210 @@ class PredictorBasedGenerator(nn.Module):
         if frame is not None:
             target = target[:, frame].unsqueeze(1)
         return self.error_func(pred, target).sum(dim, True)
+
+    # ---- errors on a target region (prediction.py:324-329, 542-615) ----------------------------------------------------
+    def _get_error(self, pred, gt, dim=-3, frame=None):
+        """error_func of the last gt.shape[1] predicted frames against gt, summed over `dim` (prediction.py:324-329)."""
+        return self.error_func(pred[:, -gt.shape[1]:], gt).sum(dim, True)
+
+    def predict_with_mask(self, mask, invert_mask=False, *args, **kwargs):
+        """`predict` on the generator's own input (`set_input`) with `mask` (or its complement); prediction.py:542-546."""
+        assert self.x is not None
+        if invert_mask:
+            mask = ~mask
+        return self.predict(self.x, mask.view(*self.inp_mask_shape), *args, **kwargs)
+
+    def error_with_mask(self, mask, invert_mask=False, frame=-1, *args, **kwargs):
+        """Per-pixel error [B,1,1,H,W] of `predict_with_mask` against frame `frame` of the generator's input (prediction.py:548-551)."""
+        x_pred = self.predict_with_mask(mask, invert_mask, *args, **kwargs)
+        return self._get_error(x_pred[:, frame].unsqueeze(1), self.x[:, frame].unsqueeze(1), dim=-3)
+
+    def _patch3(self, patch_size=None):
+        ps = tuple(self.patch_size if patch_size is None else patch_size)
+        return ps if len(ps) == 3 else (1,) + ps
+
+    def _error_takes_fused_path(self, x, target, region, aggregate_over_patches, patch_size, kwargs) -> bool:
+        """The fused path of `get_error_on_target_region`: tokens -> per-patch errors in one kernel (cwm_patch_error), no predicted video."""
+        if not (self._uses_fused_path((), kwargs) and x.is_cuda and x.dim() == 5 and aggregate_over_patches):
+            return False
+        if not (isinstance(self.error_func, nn.MSELoss) and self.error_func.reduction == "none"):
+            return False
+        if patch_size is not None and self._patch3(patch_size) != self._patch3():
+            return False
+        B, T, _, H, W = x.shape
+        P = self.patch_size[-1]
+        if self._patch3() != (1, P, P) or tuple(region.shape) != (B, T, H // P, W // P):
+            return False
+        return target is None or (tuple(target.shape) == tuple(x.shape) and target.device == x.device)
+
+    def _region_error_fused(self, x, batch: _RectBatch, region, target, frame, want_mean):
+        """(map [B,T,h,w], mean [B] or None) for the rows of a rectangular `batch` whose frames are `x` (any batch stride, 0 included): the predictor's
+        tokens (normalisation fused, no video) and then ONE library call that turns tokens, frames and mask into per-patch errors.  Nothing here
+        reads the device back when the batch knows its masked count."""
+        pred = self.predictor
+        dev = x.device
+        B, T, Cc, H, W = x.shape
+        P = self.patch_size[-1]
+        Nt = T * (H // P) * (W // P)
+        mask = batch.mask.to(device=dev, dtype=torch.bool).reshape(B, Nt).contiguous()
+        n_masked = batch.n_masked if batch.n_masked is not None else int(mask[0].sum().item())  # (one row, or a caller that did not count: as `_run`)
+        xs, (sb, sc, st) = pred._frame_strides(x, 2, 1)
+        y = None
+        if n_masked > 0:  # (nothing masked: every patch is the input's, there is no token to predict)
+            y, _ = pred._run(xs, (sb, sc, st), self.imagenet_normalize_inputs, mask, Nt - n_masked, False, check=False, weights_synced=batch.weights_synced)
+        a = _lib.new_patch_error_args()
+        a.y_tokens_dev = _lib.ptr(y)
+        a.x_dev, a.x_stride_b, a.x_stride_t, a.x_stride_c = xs.data_ptr(), sb, st, sc
+        if target is not None:
+            tg, (tb, tc, tt) = pred._frame_strides(target, 2, 1)
+            a.target_dev, a.target_stride_b, a.target_stride_t, a.target_stride_c = tg.data_ptr(), tb, tt, tc
+        region = region.to(device=dev, dtype=torch.float32).contiguous()
+        emap = torch.empty((B, T, H // P, W // P), device=dev, dtype=torch.float32)
+        mean = torch.empty((B,), device=dev, dtype=torch.float32) if want_mean else None
+        a.mask_dev, a.region_dev = mask.data_ptr(), region.data_ptr()
+        a.batch, a.T, a.C, a.H, a.W, a.P = B, T, Cc, H, W, P
+        a.n_vis, a.frame = Nt - n_masked, (-1 if frame is None else frame % T)
+        a.map_dev, a.mean_dev, a.stream = emap.data_ptr(), _lib.ptr(mean), _lib.current_stream_handle(dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.get_lib().cwm_patch_error(C.byref(a)))
+        return emap, mean
+
+    def get_error_on_target_region(self, x, mask, target_mask, target=None, average_error=True, frame=-1, aggregate_over_patches=True, patch_size=None,
+                                   **kwargs):
+        """How wrong the prediction of (x, mask) is on a region (prediction.py:553-574).  The region is `1 - target_mask`: the patches VISIBLE in a
+        [B,Nt] target mask, or any [B,T,h,w] tensor of weights.  The error is `error_func` summed over the channels and averaged over each patch,
+        [B,T,h,w]: with an integer `frame` the ONE predicted frame against EVERY frame of the target (`target`, default x), with frame=None frame t
+        against frame t.  average_error: [B], the region-weighted mean (region sum clamped to >= 1); otherwise the region-weighted map.
+        aggregate_over_patches=False: the per-pixel error [B,T,1,H,W].  Unlike the reference, which needs `set_input` or `predict` first (its
+        `mask_shape` reads `inp_shape`), the image size is taken from `x`.
+
+        The plain predictor on the GPU with the default MSE error computes this from the predicted tokens in one kernel (cwm_patch_error) and never
+        builds the predicted video; everything else -- conjoined predictors, a custom error_func, aggregate_over_patches=False, another patch_size,
+        extra predictor arguments, a ragged batch -- composes `predict`, `error_func` and `avg_pool3d` as the reference does."""
+        B, T = x.shape[:2]
+        ps = self._patch3()
+        h, w = x.shape[-2] // ps[-2], x.shape[-1] // ps[-1]
+        if target_mask.dim() == 2:
+            region = 1 - target_mask.view(B, -1, h, w).to(x)
+        else:
+            region = 1 - target_mask.to(x)
+        if self._error_takes_fused_path(x, target, region, aggregate_over_patches, patch_size, kwargs):
+            self.set_image_size(x.shape[-2:])
+            self.inp_shape = x.shape
+            batch = self._as_rect(x, mask, for_video=True, alloc_video=False)
+            if batch.n_vis_range is not None and batch.n_vis_range[0] == batch.n_vis_range[1]:  # a `ragged_batches` generator whose rows agree
+                batch.n_masked, batch.n_vis_range = batch.mask[0].numel() - batch.n_vis_range[0], None
+            if batch.n_vis_range is None:
+                emap, mean = self._region_error_fused(x, batch, region, target, frame, want_mean=average_error)
+                return mean if average_error else emap * region
+            # (rows with different counts: the ragged forward's token layout is not the kernel's -- composed below; nothing was drawn or changed)
+        error = self._get_error(self.predict(x, mask, frame=frame, **kwargs), x if target is None else target)
+        if not aggregate_over_patches:
+            return error
+        ps = self._patch3(patch_size)
+        error = nn.functional.avg_pool3d(error.transpose(1, 2), ps, stride=ps).squeeze(1) * region
+        if not average_error:
+            return error
+        return error.sum((1, 2, 3)) / region.sum((1, 2, 3)).clamp(min=1)
+
+    @staticmethod
+    def unmask_one_patch(mask, idx=None, mask_shape=None, inplace=False, frame=0):
+        """`mask` with one patch made visible (prediction.py:580-607).  Without `mask_shape`: mask [B,N], token `idx` of every row.  With it: the mask
+        is viewed as [-1, *mask_shape] and `idx` is (h, w) -- in frame `frame` --, (t, h, w) for every row, or (b, t, h, w) for one."""
+        shape = mask.shape
+        if not inplace:
+            mask = mask.clone()
+        if mask_shape is None:
+            assert len(shape) == 2, "If you don't pass a mask shape, it must be [B,N]"
+            mask[:, idx] = False
+            return mask
+        if isinstance(idx, (list, tuple)) and len(idx) == 2:
+            idx = [frame] + list(idx)
+        idx = [int(i) for i in idx]
+        assert len(idx) in (len(mask_shape), len(mask_shape) + 1), (idx, mask_shape)
+        grid = mask.view(-1, *mask_shape)
+        if len(idx) == len(mask_shape):
+            grid[(slice(None),) + tuple(idx)] = False
+        else:
+            grid[tuple(idx)] = False
+        return grid.view(*shape)
+
+    @staticmethod
+    def patch_idx_list_from_mask(mask):
+        """[b, t, h, w] of every visible patch of a [B,T,h,w] mask, in row-major order (prediction.py:609-615)."""
+        assert len(mask.shape) == 4, mask.shape
+        return [list(p) for p in np.argwhere(~mask.bool().cpu().numpy())]
+
+    # ---- error-guided unmasking (no counterpart in the reference: the search its keypoint net distils) -----------------
+    def greedy_unmask(self, x, mask, target_mask=None, num_steps=1, candidates=None, num_candidates=None, frame=-1, target=None, sample_batch_size=None,
+                      return_scores=False):
+        """Reveal, `num_steps` times, the masked patch of frame `frame` whose un-masking leaves the lowest mean error on the region
+        (`get_error_on_target_region`; the default region is every patch of `frame`).  x [1,T,C,H,W], mask [1,Nt]; tokens are indices into the Nt
+        tokens of the mask.  The candidates of a step are the still-masked tokens of `frame` -- of `candidates` if given; `num_candidates` of them
+        drawn with `self.rng.choice(..., replace=False)` and sorted, if given.  Row c of a step's batch is the current mask with candidate c un-masked,
+        so all rows have equal counts: nothing is rectangularised and torch's global RNG is not touched.  The frames go in as a stride-0 expand of
+        x, never copied, and the rows are scored on the fused path in chunks of `sample_batch_size`, with one host read-back per step.  The pick is the
+        lowest score; among equal scores the lowest token index.  Returns (mask_out [1,Nt], picks [num_steps], scores [num_steps]) and, with
+        return_scores, a list of each step's (candidates, scores)."""
+        if x.dim() != 5 or x.shape[0] != 1:
+            raise ValueError("greedy_unmask searches the prompts of ONE movie: x must be [1,T,C,H,W], got %s" % (tuple(x.shape),))
+        if frame is None:
+            raise ValueError("greedy_unmask un-masks patches of one frame: frame must be an index")
+        _, T, _, H, W = x.shape
+        P = self.patch_size[-1]
+        h, w = H // P, W // P
+        n, Nt = h * w, T * h * w
+        f = frame % T
+        dev = x.device
+        cur = mask.reshape(1, Nt).to(device=dev, dtype=torch.bool).clone()
+        if target_mask is None:
+            region = torch.zeros((1, T, h, w), device=dev, dtype=torch.float32)
+            region[:, f] = 1
+        elif target_mask.dim() == 2:
+            region = 1 - target_mask.view(1, -1, h, w).to(x)
+        else:
+            region = 1 - target_mask.to(x)
+        if not self._error_takes_fused_path(x, target, region, True, None, {}):
+            raise RuntimeError("greedy_unmask scores its candidates on the fused error path: the plain VMAE predictor on the GPU, a two-frame movie "
+                               "[1,T,C,H,W], the default MSE error_func and a [1,T,h,w] region")
+        self.set_image_size(x.shape[-2:])
+        self.inp_shape = x.shape
+        self.predictor.sync_weights(dev)
+        host = cur[0].cpu().numpy().copy()  # the search's state on the host: read once, then kept in step with `cur`
+        n_masked = int(host.sum())
+        allowed = None if candidates is None else np.unique(np.asarray(candidates, dtype=np.int64).reshape(-1))
+        picks, best, trace = [], [], []
+        for _ in range(int(num_steps)):
+            cand = f * n + np.flatnonzero(host[f * n:(f + 1) * n])
+            if allowed is not None:
+                cand = cand[np.isin(cand, allowed)]
+            if num_candidates is not None and len(cand) > num_candidates:
+                cand = np.sort(self.rng.choice(cand, size=int(num_candidates), replace=False))
+            if len(cand) == 0:
+                raise ValueError("greedy_unmask: no masked candidate token is left in frame %d after %d steps" % (f, len(picks)))
+            R = len(cand)
+            rows = cur.expand(R, Nt).clone()
+            rows[torch.arange(R, device=dev), torch.from_numpy(cand).to(dev)] = False
+            step = R if not sample_batch_size else max(1, int(sample_batch_size))
+            scores = torch.empty((R,), device=dev, dtype=torch.float32)
+            for r0 in range(0, R, step):
+                r1 = min(r0 + step, R)
+                k = r1 - r0
+                chunk = _RectBatch(x.expand(k, -1, -1, -1, -1), rows[r0:r1], n_masked - 1, weights_synced=True)
+                _, mean = self._region_error_fused(chunk.x, chunk, region.expand(k, -1, -1, -1), None if target is None else target.expand(k, -1, -1, -1, -1),
+                                                   frame, want_mean=True)
+                scores[r0:r1] = mean
+            s = scores.cpu().numpy()  # the step's one read-back
+            order = np.lexsort((cand, s))  # by score, equal scores by token index
+            pick = int(cand[order[0]])
+            picks.append(pick)
+            best.append(float(s[order[0]]))
+            trace.append((cand.copy(), s.copy()))
+            host[pick] = False
+            cur[0, pick] = False
+            n_masked -= 1
+        out = (cur, np.asarray(picks, dtype=np.int64), np.asarray(best, dtype=np.float32))
+        return out + (trace,) if return_scores else out
 
     # ---- per-sample batching (prediction.py:456-540) -----------------------------------------------------------------
     def sample_tile(self, z, num_samples):

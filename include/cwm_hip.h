@@ -274,6 +274,36 @@ CWM_API int cwm_mask_to_perm(const uint8_t* mask_dev, int B, int Nt, int n_vis, 
 CWM_API int cwm_unembed(const float* y_tokens_dev, const float* x_dev, const uint8_t* mask_dev, int B, int T, int C, int H, int W,
                 int P, int n_vis, float* out_dev, void* stream);
 
+typedef struct cwm_patch_error_args {
+    uint32_t struct_size;          /* sizeof(cwm_patch_error_args); anything else: CWM_ERR_INVALID naming struct_size */
+    const float* y_tokens_dev;     /* [B, Nt - n_vis, C*P*P] predicted tokens, feature order (ph pw c), as cwm_forward writes them; may be NULL when n_vis == Nt */
+    /* frames: element (b, t, c, y, x) at x_dev[b*x_stride_b + t*x_stride_t + c*x_stride_c + y*W + x]; a batch stride of 0 shares one movie among the rows */
+    const float* x_dev;
+    int64_t x_stride_b, x_stride_t, x_stride_c;
+    const float* target_dev;       /* the frames the prediction is compared with, with their own strides; NULL = x_dev */
+    int64_t target_stride_b, target_stride_t, target_stride_c;
+    const uint8_t* mask_dev;       /* bool [B, Nt], 1 = masked: the mask the tokens were predicted for */
+    const float* region_dev;       /* [B, T, H/P, W/P] fp32 weights of the mean; NULL = ones */
+    int32_t batch, T, C, H, W, P;  /* C <= 8; P 4, 8 or 16; H and W multiples of P */
+    int32_t n_vis;                 /* visible tokens per row of mask_dev (y_tokens_dev has Nt - n_vis rows per sample) */
+    int32_t frame;                 /* the predicted frame that is compared with EVERY target frame, or -1: frame t with target frame t */
+    float* map_dev;                /* out [B, T, H/P, W/P] or NULL */
+    float* mean_dev;               /* out [B] or NULL */
+    float* scratch_dev;            /* [B, T, H/P, W/P] floats, needed only when map_dev is NULL and mean_dev is not */
+    void* stream;
+} cwm_patch_error_args;
+
+/* Per-patch prediction error without the predicted video.
+ * replaces: `_get_error` prediction.py:324-329 (MSELoss summed over the channels) of `predict` against the target, and the avg_pool3d over each patch,
+ *           the region weighting and the mean of `get_error_on_target_region` prediction.py:553-574:
+ *   map[b][t][i][j] = (1 / P^2) sum_{pixels of patch (i,j)} sum_c (pred_f - target_t)^2,  pred_f = frame f of pred_patches_to_video(y, x, mask): y at the masked
+ *                     patches of frame f, x at its visible ones; f = frame, or t when frame = -1
+ *   mean[b]         = sum(map * region) / max(sum(region), 1)
+ * Asynchronous on `stream`: nothing is allocated and the host is not synchronised.  The row of y_tokens_dev that belongs to a masked token is its rank among
+ * the row's masked tokens, counted on the device and clamped into [0, Nt - n_vis): no mask content makes the call read outside its buffers.  All sums have a
+ * fixed order (no atomics): two calls on the same inputs give the same bits. */
+CWM_API int cwm_patch_error(const cwm_patch_error_args* args);
+
 /* `RectangularizeMasks` (masking.py:90-132) on device masks without reading them back.  The reference equalises the masked count of
  * the rows of a batch by un-masking / masking `torch.randperm(#candidates)[:surplus]` of a row's masked / visible tokens (one draw of the global CPU
  * generator per changed row, in row order).  The draws depend on the per-row COUNTS alone, so:
