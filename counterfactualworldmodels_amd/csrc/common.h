@@ -124,7 +124,8 @@ __device__ __forceinline__ float group8_sum(float v) {
 
 // A run-time value as a template argument: calls fn(std::integral_constant<int, N>{}) for the N of the list that equals n (launch sites: `K<q.value>`).
 // Returns false, having called nothing, when n is not in the list.  Call sites pass a bool or a `? :` over the listed values, so that cannot happen there; a site
-// that passes anything else must check the result.
+// that passes anything else must check the result.  (The compiler emits the kernels a generic lambda instantiates in the REVERSE of the list's order; the launch
+// sites list the values so that each object file keeps the order its kernels had under the `if (planes == 1) K<1> else K<2>` pairs they replaced.)
 template <int... Ns, class F>
 static inline bool dispatch_int(int n, F&& fn) {
     return ((n == Ns && (fn(std::integral_constant<int, Ns>{}), true)) || ...);

@@ -450,13 +450,10 @@ int launch_small_attention_mfma(const SmallAttnParams& p, int planes, hipStream_
     CWM_REQUIRE(small_attention_mfma_ok(p.n_tok, p.head_dim), "small_attention (MFMA): needs head_dim 32 and n_tok <= 64 (got %d, %d)", p.head_dim, p.n_tok);
     CWM_REQUIRE((p.heads * p.head_dim) % 4 == 0 && p.ldo % 32 == 0, "small_attention (MFMA): bad widths");
     const dim3 grid(p.B * p.heads), block(64);
-    if (planes == 2) {
-        if (p.n_tok <= 32) hipLaunchKernelGGL((small_attn_mfma_kernel<2, 1>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((small_attn_mfma_kernel<2, 2>), grid, block, 0, stream, p);
-    } else {
-        if (p.n_tok <= 32) hipLaunchKernelGGL((small_attn_mfma_kernel<1, 1>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((small_attn_mfma_kernel<1, 2>), grid, block, 0, stream, p);
-    }
+    dispatch_int<1, 2>(planes == 2 ? 2 : 1, [&](auto pl) {
+        if (p.n_tok <= 32) hipLaunchKernelGGL((small_attn_mfma_kernel<pl.value, 1>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((small_attn_mfma_kernel<pl.value, 2>), grid, block, 0, stream, p);
+    });
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }

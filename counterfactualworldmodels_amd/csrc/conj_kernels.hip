@@ -93,10 +93,7 @@ __global__ void imu_gather_kernel(const ImuGatherParams p) {
 
 int launch_imu_gather(const ImuGatherParams& p, int planes, hipStream_t stream) {
     const int64_t total = (int64_t)p.B * p.n_rows * p.ld;
-    if (planes == 1)
-        hipLaunchKernelGGL(imu_gather_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p);
-    else
-        hipLaunchKernelGGL(imu_gather_kernel<2>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p);
+    dispatch_int<2, 1>(planes == 1 ? 1 : 2, [&](auto pl) { hipLaunchKernelGGL(imu_gather_kernel<pl.value>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p); });
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -176,10 +173,7 @@ __global__ __launch_bounds__(64) void small_attention_kernel(const SmallAttnPara
 
 int launch_small_attention(const SmallAttnParams& p, int planes, hipStream_t stream) {
     CWM_REQUIRE(p.n_tok > 0 && p.n_tok <= 64 && p.head_dim > 0 && p.head_dim <= 64, "small_attention: needs n_tok <= 64 and head_dim <= 64 (got %d, %d)", p.n_tok, p.head_dim);
-    if (planes == 1)
-        hipLaunchKernelGGL(small_attention_kernel<1>, dim3(p.B * p.heads), dim3(64), 0, stream, p);
-    else
-        hipLaunchKernelGGL(small_attention_kernel<2>, dim3(p.B * p.heads), dim3(64), 0, stream, p);
+    dispatch_int<2, 1>(planes == 1 ? 1 : 2, [&](auto pl) { hipLaunchKernelGGL(small_attention_kernel<pl.value>, dim3(p.B * p.heads), dim3(64), 0, stream, p); });
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -392,17 +386,15 @@ int launch_cross_attention(const CrossAttnParams& p, int planes, hipStream_t str
                 smem, kCrossMainLdsCap);
     CWM_REQUIRE(p.scores_t && p.partial, "cross_attention: scratch buffers missing");
     const dim3 g1((p.N + 63) / 64, p.B * p.heads), g2(kCrossSplit, p.B * p.heads), g3(p.M, p.B * p.heads);
-    if (planes == 1) {
-        if (int rc = cwm_set_max_lds((const void*)cross_attn_main_kernel<1>, (int)kCrossMainLdsCap)) return rc;  // per (device, kernel): engine.hip
-        hipLaunchKernelGGL(cross_attn_main_kernel<1>, g1, dim3(256), smem, stream, p);
-    } else {
-        if (int rc = cwm_set_max_lds((const void*)cross_attn_main_kernel<2>, (int)kCrossMainLdsCap)) return rc;
-        hipLaunchKernelGGL(cross_attn_main_kernel<2>, g1, dim3(256), smem, stream, p);
-    }
+    int rc = 0;
+    dispatch_int<2, 1>(planes == 1 ? 1 : 2, [&](auto pl) {
+        rc = cwm_set_max_lds((const void*)cross_attn_main_kernel<pl.value>, (int)kCrossMainLdsCap);  // per (device, kernel): engine.hip
+        if (!rc) hipLaunchKernelGGL(cross_attn_main_kernel<pl.value>, g1, dim3(256), smem, stream, p);
+    });
+    if (rc) return rc;
     if (p.M <= 32) hipLaunchKernelGGL(cross_attn_src_partial_kernel<32>, g2, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(cross_attn_src_partial_kernel<64>, g2, dim3(256), 0, stream, p);
-    if (planes == 1) hipLaunchKernelGGL(cross_attn_src_combine_kernel<1>, g3, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(cross_attn_src_combine_kernel<2>, g3, dim3(256), 0, stream, p);
+    dispatch_int<2, 1>(planes == 1 ? 1 : 2, [&](auto pl) { hipLaunchKernelGGL(cross_attn_src_combine_kernel<pl.value>, g3, dim3(256), 0, stream, p); });
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }

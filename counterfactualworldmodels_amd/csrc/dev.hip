@@ -37,6 +37,30 @@ void fill_bf16(bf16* d, int64_t n, unsigned seed, float scale) {
 void fill_f32(float* d, int64_t n, unsigned seed, float scale) {
     hipLaunchKernelGGL(fill_random_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d, n, seed, scale);
 }
+// *avg_us = the mean time of `iters` calls of launch() on `stream` after 3 warm-up calls; the two events are destroyed on every path
+template <typename F>
+int time_launches(int iters, hipStream_t stream, F&& launch, double* avg_us) {
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+    } ev;
+    CWM_HIP_CHECK(hipEventCreate(&ev.e0));
+    CWM_HIP_CHECK(hipEventCreate(&ev.e1));
+    for (int i = 0; i < 3; ++i)
+        if (int rc = launch()) return rc;
+    CWM_HIP_CHECK(hipEventRecord(ev.e0, stream));
+    for (int i = 0; i < iters; ++i)
+        if (int rc = launch()) return rc;
+    CWM_HIP_CHECK(hipEventRecord(ev.e1, stream));
+    CWM_HIP_CHECK(hipEventSynchronize(ev.e1));
+    float ms = 0.f;
+    CWM_HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *avg_us = 1e3 * ms / iters;
+    return CWM_OK;
+}
 }  // namespace
 
 
@@ -96,19 +120,20 @@ extern "C" int cwm_gemm_tile_override(int M, int N, int K, int epi, int overlapp
 // What gemm_plan decides for a launch of this shape under this thread's options: nothing is launched and no device is needed.
 extern "C" int cwm_dev_gemm_plan(int M, int N, int K, int epi, int mode, int overlapped, int forced_cfg, int cus, cwm_dev_gemm_plan_out* out) {
     CWM_REQUIRE(out && epi >= 0 && epi <= 3 && forced_cfg >= 0 && cus >= 0, "cwm_dev_gemm_plan: bad argument");
-    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_dev_gemm_plan: bad mode");
+    int planes;
+    if (int rc = mode_planes("cwm_dev_gemm_plan", mode, &planes)) return rc;
     static_assert(CWM_DEV_GEMM_KERNEL_128 == GEMM_KERNEL_128 && CWM_DEV_GEMM_KERNEL_DEEP128 == GEMM_KERNEL_DEEP128 &&
                       CWM_DEV_GEMM_KERNEL_DEEP64 == GEMM_KERNEL_DEEP64 && CWM_DEV_GEMM_KERNEL_8PHASE == GEMM_KERNEL_8PHASE,
                   "cwm_hip_dev.h names the kernels of kernels.h GemmKernel");
     GemmParams p;
     memset(&p, 0, sizeof(p));
     p.M = M; p.N = N; p.K = K; p.lda = K; p.epi = epi;
-    p.ldc = p.ldr = p.ldo = N;                                                   // dense outputs, as cwm_bench_gemm makes them
-    p.rows_in = p.n_tok = M; p.qkv_dim = N / 3; p.head_dim = 64;  // EPI_QKV: one sample of M tokens, heads of 64
+    p.ldc = p.ldr = p.ldo = N;  // dense outputs, as cwm_bench_gemm makes them
+    if (epi == EPI_QKV) set_qkv_epilogue(p, M, M, N / 3, 64, nullptr, nullptr, nullptr, 0);  // one sample of M tokens, heads of 64
     p.overlapped = overlapped ? 1 : 0;
     p.tune = &thread_tuning();
     GemmPlan plan;
-    if (int rc = gemm_plan(p, mode == CWM_MODE_PARITY ? 2 : 1, forced_cfg, cus ? cus : gemm_cu_count(), &plan)) return rc;
+    if (int rc = gemm_plan(p, planes, forced_cfg, cus ? cus : gemm_cu_count(), &plan)) return rc;
     memset(out, 0, sizeof(*out));
     out->cfg = plan.cfg;
     out->nparts = plan.nparts;
@@ -153,8 +178,8 @@ extern "C" int cwm_dev_flow_forms(const int64_t* strides, int B, int C, int H, i
 
 extern "C" int cwm_bench_gemm(int M, int N, int K, int mode, int epi, int iters, double* avg_us) {
     CWM_REQUIRE(avg_us && M > 0 && N > 0 && K > 0 && iters > 0, "cwm_bench_gemm: bad argument");
-    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_bench_gemm: bad mode");
-    const int planes = mode == CWM_MODE_PARITY ? 2 : 1;
+    int planes;
+    if (int rc = mode_planes("cwm_bench_gemm", mode, &planes)) return rc;
     const int Kp = round_up(K, 64), Np = round_up(N, 256);
     Scratch sc;
     bf16* A = sc.get<bf16>((size_t)2 * M * Kp);
@@ -177,37 +202,19 @@ extern "C" int cwm_bench_gemm(int M, int N, int K, int mode, int epi, int iters,
         p.epi = epi == 1 ? EPI_BF16_GELU : EPI_BF16; p.out_hi = G; p.ldo = N;
     } else if (epi == 3) {
         CWM_REQUIRE(N % 192 == 0, "cwm_bench_gemm: QKV epilogue needs N = 3*64*heads");
-        const int D = N / 3, H = D / 64, n_tok = 792 <= M && M % 792 == 0 ? 792 : M, B = M / n_tok;
-        (void)B;
-        p.epi = EPI_QKV; p.rows_in = n_tok; p.rows_out = n_tok; p.map_stride = n_tok;
-        p.q_out = G; p.k_out = G2; p.v_out = G3; p.qk_plane = (int64_t)M * D;
-        p.qkv_dim = D; p.heads = H; p.head_dim = 64; p.n_tok = n_tok; p.q_scale = 0.125f;
+        const int n_tok = 792 <= M && M % 792 == 0 ? 792 : M;
+        set_qkv_epilogue(p, n_tok, n_tok, N / 3, 64, G, G2, G3, (int64_t)M * (N / 3));
     } else {
         p.epi = EPI_F32; p.C = Cm; p.ldc = N; p.resid = Cm; p.ldr = N;
     }
     p.tune = &thread_tuning();
-    hipEvent_t e0, e1;
-    CWM_HIP_CHECK(hipEventCreate(&e0));
-    CWM_HIP_CHECK(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i)
-        if (int rc = launch_gemm(p, planes, 0)) return rc;
-    CWM_HIP_CHECK(hipEventRecord(e0, 0));
-    for (int i = 0; i < iters; ++i)
-        if (int rc = launch_gemm(p, planes, 0)) return rc;
-    CWM_HIP_CHECK(hipEventRecord(e1, 0));
-    CWM_HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    CWM_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *avg_us = 1e3 * ms / iters;
-    return CWM_OK;
+    return time_launches(iters, 0, [&] { return launch_gemm(p, planes, 0); }, avg_us);
 }
 
 extern "C" int cwm_bench_attention(int B, int H, int N, int mode, int iters, double* avg_us) {
     CWM_REQUIRE(avg_us && B > 0 && H > 0 && N > 0 && iters > 0, "cwm_bench_attention: bad argument");
-    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_bench_attention: bad mode");
-    const int planes = mode == CWM_MODE_PARITY ? 2 : 1;
+    int planes;
+    if (int rc = mode_planes("cwm_bench_attention", mode, &planes)) return rc;
     const int D = H * 64;
     const int64_t qk_plane = (int64_t)B * N * D;
     Scratch sc;
@@ -219,27 +226,9 @@ extern "C" int cwm_bench_attention(int B, int H, int N, int mode, int iters, dou
     fill_bf16(q, 2 * qk_plane, 5, 0.5f);
     fill_bf16(k, 2 * qk_plane, 6, 1.0f);
     fill_bf16(v, 2 * qk_plane, 7, 1.0f);
-    AttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.q = q; a.k = k; a.v = v; a.qk_plane = qk_plane; a.o = o; a.o_plane = qk_plane; a.ldo = D;
-    a.n_tok = N; a.heads = H; a.batch = B;
+    AttnParams a = attn_dense(q, k, v, qk_plane, o, qk_plane, D, B, H, N);
     a.tune = &thread_tuning();
-    hipEvent_t e0, e1;
-    CWM_HIP_CHECK(hipEventCreate(&e0));
-    CWM_HIP_CHECK(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i)
-        if (int rc = launch_attention(a, planes, 0)) return rc;
-    CWM_HIP_CHECK(hipEventRecord(e0, 0));
-    for (int i = 0; i < iters; ++i)
-        if (int rc = launch_attention(a, planes, 0)) return rc;
-    CWM_HIP_CHECK(hipEventRecord(e1, 0));
-    CWM_HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    CWM_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *avg_us = 1e3 * ms / iters;
-    return CWM_OK;
+    return time_launches(iters, 0, [&] { return launch_attention(a, planes, 0); }, avg_us);
 }
 
 // ---- RAFT kernels one at a time (tests/test_raft_kernels_gpu.py) ---------------------------------------------------------------------------------
@@ -265,8 +254,8 @@ extern "C" int cwm_dev_raft_conv(const cwm_dev_raft_conv_args* args) {
     CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_raft_conv_args), "cwm_dev_raft_conv: args->struct_size must be sizeof(cwm_dev_raft_conv_args)");
     const cwm_dev_raft_conv_args& a = *args;
     hipStream_t s = (hipStream_t)a.stream;
-    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_raft_conv: bad mode");
-    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    int planes;
+    if (int rc = mode_planes("cwm_dev_raft_conv", a.mode, &planes)) return rc;
     const bool frames = a.image[0] != nullptr, operand_only = a.flags & CWM_DEV_CONV_OPERAND_ONLY, keep = a.flags & CWM_DEV_CONV_KEEP_OPERAND;
     CWM_REQUIRE(!(operand_only && keep), "cwm_dev_raft_conv: flags ask for the operand only and for no operand");
     CWM_REQUIRE(a.n_img > 0 && a.H > 0 && a.W > 0 && a.kh > 0 && a.kw > 0 && a.stride > 0 && a.pad_h >= 0 && a.pad_w >= 0, "cwm_dev_raft_conv: bad geometry");
@@ -343,16 +332,17 @@ extern "C" int cwm_dev_raft_conv(const cwm_dev_raft_conv_args* args) {
 extern "C" int cwm_dev_raft_corr_lookup_operand(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, int mode,
                                                 void* A_dev, void* stream) {
     CWM_REQUIRE(fmap1_dev && fmap2_dev && coords_dev && A_dev && P > 0 && h8 >= 8 && w8 >= 8, "cwm_dev_raft_corr_lookup_operand: bad argument");
-    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_dev_raft_corr_lookup_operand: bad mode");
-    return raft_corr_lookup_run(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, nullptr, (bf16*)A_dev, mode == CWM_MODE_PARITY ? 2 : 1, (hipStream_t)stream);
+    int planes;
+    if (int rc = mode_planes("cwm_dev_raft_corr_lookup_operand", mode, &planes)) return rc;
+    return raft_corr_lookup_run(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, nullptr, (bf16*)A_dev, planes, (hipStream_t)stream);
 }
 
 extern "C" int cwm_dev_raft_corr_lookup_on_the_fly_operand(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8,
                                                            int mode, void* A_dev, void* stream) {
     CWM_REQUIRE(fmap1_dev && fmap2_dev && coords_dev && A_dev && P > 0 && h8 >= 8 && w8 >= 8, "cwm_dev_raft_corr_lookup_on_the_fly_operand: bad argument");
-    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_dev_raft_corr_lookup_on_the_fly_operand: bad mode");
-    return raft_corr_lookup_on_the_fly_run(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, nullptr, (bf16*)A_dev, mode == CWM_MODE_PARITY ? 2 : 1,
-                                           (hipStream_t)stream);
+    int planes;
+    if (int rc = mode_planes("cwm_dev_raft_corr_lookup_on_the_fly_operand", mode, &planes)) return rc;
+    return raft_corr_lookup_on_the_fly_run(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, nullptr, (bf16*)A_dev, planes, (hipStream_t)stream);
 }
 
 extern "C" int cwm_dev_raft_instnorm_stats(const float* x_dev, int n_img, int HW, int C, float eps, float* stats_dev, void* stream) {
@@ -402,14 +392,15 @@ extern "C" int cwm_dev_raft_flow_update(float* coords_dev, const float* delta_de
 }
 
 // ---- the operand gathers one launch at a time (tests/test_gather_kernels_gpu.py) ----
-// ragged: cwm_dev_gather_ragged's call (INDEX / INDEX_UNFUSED with the launch forms of a ragged batch: n_vis_min and counts go to the launchers as they are)
+// ragged: cwm_dev_gather_ragged's call (INDEX / INDEX_UNFUSED with the launch forms of a ragged batch: n_vis_min and counts go to the launchers as they are; the
+// entry point refuses a least count of 0, which the launchers take for a rectangular batch)
 static int dev_gather(const cwm_dev_gather_args* args, bool ragged, int n_vis_min, int* counts) {
     CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_gather_args), "cwm_dev_gather: args->struct_size must be sizeof(cwm_dev_gather_args)");
     const cwm_dev_gather_args& a = *args;
     CWM_REQUIRE(!ragged || a.kind == CWM_DEV_GATHER_INDEX || a.kind == CWM_DEV_GATHER_INDEX_UNFUSED, "cwm_dev_gather_ragged: kind %d has no ragged form", a.kind);
     hipStream_t s = (hipStream_t)a.stream;
-    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_gather: bad mode");
-    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    int planes;
+    if (int rc = mode_planes("cwm_dev_gather", a.mode, &planes)) return rc;
     CWM_REQUIRE(a.out && a.x && a.B > 0 && a.n_rows > 0 && a.Nt > 0 && a.ld > 0 && a.ld % (planes == 2 ? 32 : 4) == 0,
                 "cwm_dev_gather: bad argument (rows of ld = %d need a multiple of 32 in parity mode, of 4 in fast mode)", a.ld);
     const int L = a.perm_stride ? a.perm_stride : a.Nt;
@@ -451,14 +442,12 @@ static int dev_gather(const cwm_dev_gather_args* args, bool ragged, int n_vis_mi
                 rc = launch_patch_gather(g, planes, s);
             } else if (a.kind == CWM_DEV_GATHER_INDEX) {
                 CWM_REQUIRE(a.mask && a.perm && a.err_rows, "cwm_dev_gather: the index gather needs mask, perm and err_rows");
-                rc = ragged ? launch_index_gather(g, a.mask, a.n_vis, a.perm, a.rank, a.err_rows, planes, s, n_vis_min, counts)
-                            : launch_index_gather(g, a.mask, a.n_vis, a.perm, a.rank, a.err_rows, planes, s);
+                rc = launch_index_gather(g, a.mask, a.n_vis, a.perm, a.rank, a.err_rows, planes, s, n_vis_min, counts);
             } else if (a.kind == CWM_DEV_GATHER_INDEX_UNFUSED) {
                 CWM_REQUIRE(a.mask && a.perm && a.rank && a.err_rows, "cwm_dev_gather: the unfused index prologue needs mask, perm, rank and err_rows");
                 CWM_HIP_CHECK(hipMemsetAsync(a.err_rows, 0, (size_t)a.B * sizeof(int), s));
-                if ((rc = ragged ? launch_mask_to_perm_ragged(a.mask, a.B, L, n_vis_min, a.n_vis, a.perm, a.err_rows, counts, s)
-                                 : launch_mask_to_perm(a.mask, a.B, L, a.n_vis, a.perm, a.err_rows, s)))
-                    return rc;
+                CWM_REQUIRE(!ragged || n_vis_min != 0, "mask_to_perm (ragged): bad argument");
+                if ((rc = launch_mask_to_perm(a.mask, a.B, L, a.n_vis, a.perm, a.err_rows, s, n_vis_min, counts))) return rc;
                 if ((rc = launch_patch_gather(g, planes, s))) return rc;
                 rc = launch_perm_to_rank(a.perm, a.rank, a.B, L, s);
             } else {
@@ -487,10 +476,7 @@ __global__ void stage_operand_kernel(const float* src, int64_t rows, int K, bf16
 }
 int stage_operand(const float* src, int64_t rows, int K, bf16* out, int planes, hipStream_t s) {
     const unsigned grid = (unsigned)((rows * K / 4 + 255) / 256);
-    if (planes == 2)
-        hipLaunchKernelGGL(stage_operand_kernel<2>, dim3(grid), dim3(256), 0, s, src, rows, K, out);
-    else
-        hipLaunchKernelGGL(stage_operand_kernel<1>, dim3(grid), dim3(256), 0, s, src, rows, K, out);
+    dispatch_int<1, 2>(planes == 2 ? 2 : 1, [&](auto pl) { hipLaunchKernelGGL(stage_operand_kernel<pl.value>, dim3(grid), dim3(256), 0, s, src, rows, K, out); });
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -501,8 +487,8 @@ extern "C" int cwm_dev_conj_cross_attention(const cwm_dev_conj_cross_attention_a
                 "cwm_dev_conj_cross_attention: args->struct_size must be sizeof(cwm_dev_conj_cross_attention_args)");
     const cwm_dev_conj_cross_attention_args& a = *args;
     hipStream_t s = (hipStream_t)a.stream;
-    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_conj_cross_attention: bad mode");
-    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    int planes;
+    if (int rc = mode_planes("cwm_dev_conj_cross_attention", a.mode, &planes)) return rc;
     CWM_REQUIRE(a.impl == CWM_DEV_CONJ_VALU || a.impl == CWM_DEV_CONJ_MFMA, "cwm_dev_conj_cross_attention: unknown impl %d", a.impl);
     const bool mfma = a.impl == CWM_DEV_CONJ_MFMA;
     CWM_REQUIRE(a.roles >= 1 && a.roles <= 3 && (mfma || a.roles == 3), "cwm_dev_conj_cross_attention: roles = %d (MFMA: 1, 2 or 3; VALU: 3)", a.roles);
@@ -549,8 +535,8 @@ extern "C" int cwm_dev_conj_small_attention(const cwm_dev_conj_small_attention_a
                 "cwm_dev_conj_small_attention: args->struct_size must be sizeof(cwm_dev_conj_small_attention_args)");
     const cwm_dev_conj_small_attention_args& a = *args;
     hipStream_t s = (hipStream_t)a.stream;
-    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_conj_small_attention: bad mode");
-    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    int planes;
+    if (int rc = mode_planes("cwm_dev_conj_small_attention", a.mode, &planes)) return rc;
     CWM_REQUIRE(a.impl == CWM_DEV_CONJ_VALU || a.impl == CWM_DEV_CONJ_MFMA, "cwm_dev_conj_small_attention: unknown impl %d", a.impl);
     CWM_REQUIRE(a.qkv && a.o && a.B > 0 && a.heads > 0, "cwm_dev_conj_small_attention: bad argument");
     CWM_REQUIRE(a.n_tok > 0 && a.n_tok <= 64 && a.head_dim > 0 && a.head_dim <= 64, "cwm_dev_conj_small_attention: needs n_tok <= 64 and head_dim <= 64 (got %d, %d)",
@@ -603,8 +589,8 @@ extern "C" int cwm_dev_gemm(const cwm_dev_gemm_args* args) {
     CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_gemm_args), "cwm_dev_gemm: args->struct_size must be sizeof(cwm_dev_gemm_args)");
     const cwm_dev_gemm_args& a = *args;
     hipStream_t s = (hipStream_t)a.stream;
-    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_gemm: bad mode");
-    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    int planes;
+    if (int rc = mode_planes("cwm_dev_gemm", a.mode, &planes)) return rc;
     CWM_REQUIRE(a.a && a.w && a.M > 0 && a.N > 0 && a.K > 0 && a.epi >= EPI_F32 && a.epi <= EPI_QKV, "cwm_dev_gemm: bad argument");
     CWM_REQUIRE(a.rows_in >= 0 && a.out_row_offset >= 0 && (a.rows_in > 0 || (!a.resid_rowmap && a.out_row_offset == 0)),
                 "cwm_dev_gemm: a row map or row offset needs rows_in > 0");
@@ -655,30 +641,17 @@ static int dev_attention(const cwm_dev_attention_args* args, const int* key_len)
     // (launch_attention refuses this too, but only after the Q/K/V scatter below has been launched)
     CWM_REQUIRE(!key_len || a.n_q == 0, "cwm_dev_attention: per-row key counts (key_len) go with queries over all rows (n_q = 0), got n_q = %d", a.n_q);
     hipStream_t s = (hipStream_t)a.stream;
-    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_attention: bad mode");
-    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    int planes;
+    if (int rc = mode_planes("cwm_dev_attention", a.mode, &planes)) return rc;
     CWM_REQUIRE(a.qkv && a.o && a.B > 0 && a.N > 0 && a.H > 0, "cwm_dev_attention: bad argument");
     CWM_REQUIRE(a.q_off >= 0 && a.n_q >= 0 && a.q_off + a.n_q <= a.N && (a.n_q > 0 || a.q_off == 0), "cwm_dev_attention: query rows [%d, %d) of %d tokens", a.q_off,
                 a.q_off + a.n_q, a.N);
     const int D = a.H * 64;
     CWM_REQUIRE(a.ldo >= D && a.ldo % (planes == 2 ? 32 : 4) == 0, "cwm_dev_attention: %d columns in operand rows of ldo = %d (a multiple of 32 in parity mode, of 4 in fast mode)",
                 D, a.ldo);
-    const int64_t qk_plane = (int64_t)a.B * a.N * D;
     Scratch sc;
-    bf16* q = sc.get<bf16>(2 * qk_plane);
-    bf16* k = sc.get<bf16>(2 * qk_plane);
-    bf16* v = sc.get<bf16>(2 * qk_plane);
-    CWM_REQUIRE(q && k && v, "cwm_dev_attention: out of device memory");
-    if (int rc = launch_qkv_scatter(a.qkv, a.B, a.N, a.H, 0.125f, q, k, v, qk_plane, s)) return rc;
-    AttnParams p;
-    memset(&p, 0, sizeof(p));
-    p.q = q; p.k = k; p.v = v; p.qk_plane = qk_plane;
-    p.o = (bf16*)a.o; p.o_plane = (int64_t)a.B * (a.n_q ? a.n_q : a.N) * a.ldo; p.ldo = a.ldo;
-    p.n_tok = a.N; p.heads = a.H; p.batch = a.B;
-    p.q_off = a.q_off; p.n_q = a.n_q;
-    p.key_len = key_len;
-    p.tune = &thread_tuning();
-    if (int rc = launch_attention(p, planes, s)) return rc;
+    bf16* o;
+    if (int rc = attention_from_qkv(sc, "cwm_dev_attention", a.qkv, key_len, (bf16*)a.o, a.ldo, a.B, a.N, a.H, a.q_off, a.n_q, planes, s, &o)) return rc;
     CWM_HIP_CHECK(hipStreamSynchronize(s));
     return CWM_OK;
 }
@@ -694,17 +667,14 @@ extern "C" int cwm_dev_layernorm(const cwm_dev_layernorm_args* args) {
     CWM_REQUIRE(args && args->struct_size == sizeof(cwm_dev_layernorm_args), "cwm_dev_layernorm: args->struct_size must be sizeof(cwm_dev_layernorm_args)");
     const cwm_dev_layernorm_args& a = *args;
     hipStream_t s = (hipStream_t)a.stream;
-    CWM_REQUIRE(a.mode == CWM_MODE_FAST || a.mode == CWM_MODE_PARITY, "cwm_dev_layernorm: bad mode");
-    const int planes = a.mode == CWM_MODE_PARITY ? 2 : 1;
+    int planes;
+    if (int rc = mode_planes("cwm_dev_layernorm", a.mode, &planes)) return rc;
     CWM_REQUIRE(a.x && a.gamma && a.beta && a.out && a.rows > 0 && a.D > 0 && a.ldx >= a.D, "cwm_dev_layernorm: bad argument");
     CWM_REQUIRE(a.rows_out_per_b >= 0 && a.in_offset >= 0 &&
                     (a.rows_out_per_b == 0 ? a.in_offset == 0 : a.rows % a.rows_out_per_b == 0 && a.in_offset + a.rows_out_per_b <= a.rows_in_per_b),
                 "cwm_dev_layernorm: %d rows as samples of %d rows at offset %d of %d", a.rows, a.rows_out_per_b, a.in_offset, a.rows_in_per_b);
-    LayerNormParams ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.x = a.x; ln.ldx = a.ldx; ln.gamma = a.gamma; ln.beta = a.beta; ln.eps = a.eps; ln.D = a.D; ln.rows = a.rows;
-    ln.rows_out_per_b = a.rows_out_per_b; ln.rows_in_per_b = a.rows_in_per_b; ln.in_offset = a.in_offset;
-    ln.out = (bf16*)a.out; ln.out_plane = (int64_t)a.rows * a.ldo; ln.ldo = a.ldo; ln.out_f32 = a.out_f32;
+    LayerNormParams ln = layernorm_rows(a.x, a.ldx, a.D, a.gamma, a.beta, a.eps, a.rows, (bf16*)a.out, a.ldo, a.rows_out_per_b, a.rows_in_per_b, a.in_offset);
+    ln.out_f32 = a.out_f32;
     if (int rc = launch_layernorm(ln, planes, s)) return rc;
     CWM_HIP_CHECK(hipStreamSynchronize(s));
     return CWM_OK;
@@ -721,12 +691,13 @@ extern "C" int cwm_dev_fill_mask_tokens(float* x_full_dev, const float* mask_tok
 extern "C" int cwm_dev_fill_mask_tokens_ragged(float* x_full_dev, const float* mask_token_dev, const float* pos_dev, const int32_t* perm_dev,
                                                const int32_t* counts_dev, int B, int Nt, int n_vis_min, int D, void* stream) {
     CWM_REQUIRE(x_full_dev && mask_token_dev && pos_dev && perm_dev && B > 0 && Nt > 0 && D > 0, "cwm_dev_fill_mask_tokens_ragged: bad argument");
-    if (int rc = launch_fill_mask_tokens_ragged(x_full_dev, mask_token_dev, pos_dev, perm_dev, counts_dev, B, Nt, n_vis_min, D, (hipStream_t)stream)) return rc;
+    CWM_REQUIRE(counts_dev && n_vis_min > 0, "fill_mask_tokens (ragged): bad argument");  // (the launcher would take a call without them for a rectangular batch)
+    if (int rc = launch_fill_mask_tokens(x_full_dev, mask_token_dev, pos_dev, perm_dev, B, Nt, n_vis_min, D, (hipStream_t)stream, counts_dev, n_vis_min)) return rc;
     CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return CWM_OK;
 }
 
-// cwm_unembed with the engine's strided frames (model.hip run_forward: x_stride_b / _c / _t of the caller's tensor): mask -> perm -> rank -> launch_unembed
+// cwm_unembed with the engine's strided frames (model.hip forward_lane: x_stride_b / _c / _t of the caller's tensor): mask -> perm -> rank -> launch_unembed
 // n_vis_min > 0: the ragged batch's form (forward_lane) -- rows of n_vis_min .. n_vis visible tokens, y rows = decoder rows n_vis_min ..
 static int dev_unembed(const float* y_tokens_dev, const float* x_dev, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_t, const uint8_t* mask_dev, int B, int T,
                        int C, int H, int W, int P, int n_vis_min, int n_vis, float* out_dev, void* stream) {
@@ -736,34 +707,8 @@ static int dev_unembed(const float* y_tokens_dev, const float* x_dev, int64_t x_
                 (long long)x_stride_c);
     const int Nt = T * (H / P) * (W / P);
     CWM_REQUIRE(n_vis >= 0 && n_vis <= Nt, "cwm_dev_unembed: n_vis = %d of %d tokens", n_vis, Nt);
-    hipStream_t s = (hipStream_t)stream;
-    Scratch sc;
-    int* perm = sc.get<int>((size_t)B * Nt);
-    int* rank = sc.get<int>((size_t)B * Nt);
-    int* err = sc.get<int>(4, true);
-    int* counts = sc.get<int>((size_t)B);
-    CWM_REQUIRE(perm && rank && err && counts, "cwm_dev_unembed: out of device memory");
-    int rc;
-    if ((rc = n_vis_min > 0 ? launch_mask_to_perm_ragged(mask_dev, B, Nt, n_vis_min, n_vis, perm, err, counts, s) : launch_mask_to_perm(mask_dev, B, Nt, n_vis, perm, err, s)))
-        return rc;
-    const int y0 = n_vis_min > 0 ? n_vis_min : n_vis;  // the decoder row of y row 0
-    if ((rc = launch_perm_to_rank(perm, rank, B, Nt, s))) return rc;
-    UnembedParams u;
-    memset(&u, 0, sizeof(u));
-    u.y = y_tokens_dev; u.x = x_dev; u.sb = x_stride_b; u.st = x_stride_t; u.sc = x_stride_c;
-    u.mask = mask_dev; u.rank = rank; u.B = B; u.T = T; u.C = C; u.H = H; u.W = W; u.P = P; u.n_vis = y0; u.Nm = Nt - y0; u.out = out_dev;
-    if ((rc = launch_unembed(u, s))) return rc;
-    int herr = 0;
-    CWM_HIP_CHECK(hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, s));
-    CWM_HIP_CHECK(hipStreamSynchronize(s));
-    if (herr) {
-        if (n_vis_min > 0)
-            cwm_set_error("mask rows do not all have between %d and n_vis=%d visible tokens", n_vis_min, n_vis);
-        else
-            cwm_set_error("mask rows do not all have n_vis=%d visible tokens", n_vis);
-        return CWM_ERR_MASK;
-    }
-    return CWM_OK;
+    return unembed_from_mask("cwm_dev_unembed", y_tokens_dev, x_dev, x_stride_b, x_stride_c, x_stride_t, mask_dev, B, T, C, H, W, P, n_vis_min, n_vis, out_dev,
+                             (hipStream_t)stream);
 }
 
 extern "C" int cwm_dev_unembed(const float* y_tokens_dev, const float* x_dev, int64_t x_stride_b, int64_t x_stride_c, int64_t x_stride_t, const uint8_t* mask_dev,

@@ -81,10 +81,7 @@ int launch_layernorm(const LayerNormParams& p, int planes, hipStream_t stream) {
     CWM_REQUIRE(p.ldo >= p.D && (planes == 1 || p.ldo % 32 == 0),
                 "layernorm: %d columns in output rows of ldo=%d (split-bf16 rows are whole [32 hi | 32 lo] blocks: a multiple of 32)", p.D, p.ldo);
     const int blocks = (p.rows + 3) / 4;
-    if (planes == 1)
-        hipLaunchKernelGGL(layernorm_kernel<1>, dim3(blocks), dim3(256), 0, stream, p);
-    else
-        hipLaunchKernelGGL(layernorm_kernel<2>, dim3(blocks), dim3(256), 0, stream, p);
+    dispatch_int<2, 1>(planes == 1 ? 1 : 2, [&](auto pl) { hipLaunchKernelGGL(layernorm_kernel<pl.value>, dim3(blocks), dim3(256), 0, stream, p); });
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -136,14 +133,8 @@ __global__ __launch_bounds__(256) void mask_to_perm_kernel(const uint8_t* mask, 
     }
 }
 
-int launch_mask_to_perm(const uint8_t* mask, int B, int Nt, int n_vis, int* perm, int* err, hipStream_t stream) {
-    hipLaunchKernelGGL(mask_to_perm_kernel, dim3(B), dim3(256), 0, stream, mask, Nt, n_vis, perm, err, 0, (int*)nullptr);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-int launch_mask_to_perm_ragged(const uint8_t* mask, int B, int Nt, int n_vis_min, int n_vis, int* perm, int* err, int* counts, hipStream_t stream) {
-    CWM_REQUIRE(n_vis_min > 0 && n_vis_min <= n_vis && counts, "mask_to_perm (ragged): bad argument");
+int launch_mask_to_perm(const uint8_t* mask, int B, int Nt, int n_vis, int* perm, int* err, hipStream_t stream, int n_vis_min, int* counts) {
+    CWM_REQUIRE(n_vis_min == 0 || (n_vis_min > 0 && n_vis_min <= n_vis && counts), "mask_to_perm (ragged): bad argument");
     hipLaunchKernelGGL(mask_to_perm_kernel, dim3(B), dim3(256), 0, stream, mask, Nt, n_vis, perm, err, n_vis_min, counts);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
@@ -229,10 +220,7 @@ int launch_patch_gather(const PatchGatherParams& p, int planes, hipStream_t stre
     CWM_REQUIRE(p.ld >= p.C * p.P * p.P && p.ld % 4 == 0, "patch_gather: bad ld");
     const int64_t total = (int64_t)p.B * p.n_rows * p.C * p.P;
     const int blocks = (int)((total + 255) / 256);
-    if (planes == 1)
-        hipLaunchKernelGGL(patch_gather_kernel<1>, dim3(blocks), dim3(256), 0, stream, p);
-    else
-        hipLaunchKernelGGL(patch_gather_kernel<2>, dim3(blocks), dim3(256), 0, stream, p);
+    dispatch_int<2, 1>(planes == 1 ? 1 : 2, [&](auto pl) { hipLaunchKernelGGL(patch_gather_kernel<pl.value>, dim3(blocks), dim3(256), 0, stream, p); });
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -284,10 +272,7 @@ int launch_flow_rgb_gather(const FlowRgbGatherParams& p, int planes, hipStream_t
     const int64_t total = (int64_t)p.B * p.n_rows * 7 * p.P;
     const int blocks = (int)((total + 255) / 256);
     if (blocks == 0) return 0;
-    if (planes == 1)
-        hipLaunchKernelGGL(flow_rgb_gather_kernel<1>, dim3(blocks), dim3(256), 0, stream, p);
-    else
-        hipLaunchKernelGGL(flow_rgb_gather_kernel<2>, dim3(blocks), dim3(256), 0, stream, p);
+    dispatch_int<2, 1>(planes == 1 ? 1 : 2, [&](auto pl) { hipLaunchKernelGGL(flow_rgb_gather_kernel<pl.value>, dim3(blocks), dim3(256), 0, stream, p); });
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -392,10 +377,9 @@ int launch_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_v
     const int per_sample = (p.n_rows * p.C * p.P + 255) / 256;
     const dim3 grid((unsigned)per_sample, (unsigned)p.B);
     const size_t smem = (size_t)p.n_rows * sizeof(int);
-    if (planes == 1)
-        hipLaunchKernelGGL(index_gather_kernel<1>, grid, dim3(256), smem, stream, p, mask, n_vis, perm, rank, err_rows, n_vis_min, counts);
-    else
-        hipLaunchKernelGGL(index_gather_kernel<2>, grid, dim3(256), smem, stream, p, mask, n_vis, perm, rank, err_rows, n_vis_min, counts);
+    dispatch_int<2, 1>(planes == 1 ? 1 : 2, [&](auto pl) {
+        hipLaunchKernelGGL(index_gather_kernel<pl.value>, grid, dim3(256), smem, stream, p, mask, n_vis, perm, rank, err_rows, n_vis_min, counts);
+    });
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -437,16 +421,6 @@ __global__ __launch_bounds__(256) void fill_mask_tokens4_kernel(float* x_full, c
         if (live[i]) *reinterpret_cast<float4*>(x_full + orow[i] * D + c4 * 4) = make_float4(mt.x + pe[i].x, mt.y + pe[i].y, mt.z + pe[i].z, mt.w + pe[i].w);
 }
 
-int launch_fill_mask_tokens(float* x_full, const float* mask_token, const float* pos, const int* perm, int B, int Nt, int n_vis, int D, hipStream_t stream) {
-    CWM_REQUIRE(D % 4 == 0, "fill_mask_tokens: D must be a multiple of 4");
-    const int64_t rows = (int64_t)B * (Nt - n_vis), rows_q = (rows + 7) / 8;
-    if (rows == 0) return 0;
-    hipLaunchKernelGGL(fill_mask_tokens4_kernel, dim3((unsigned)((rows_q * (D / 4) + 255) / 256)), dim3(256), 0, stream, x_full, mask_token, pos, perm, Nt,
-                       n_vis, D, rows, rows_q);
-    CWM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
 // Ragged batches: sample b has counts[b] (>= n_vis_min) visible tokens, so its mask tokens are rows [counts[b], Nt).  The encoder_to_decoder GEMM
 // before this launch wrote rows [0, cap) of every sample, padding rows [counts[b], cap) included: those are overwritten here.  One thread per four
 // columns of a row of [n_vis_min, Nt); rows below the sample's count are left alone.
@@ -466,13 +440,22 @@ __global__ __launch_bounds__(256) void fill_mask_tokens_ragged_kernel(float* x_f
     *reinterpret_cast<float4*>(x_full + orow * D + c4 * 4) = make_float4(mt.x + pe.x, mt.y + pe.y, mt.z + pe.z, mt.w + pe.w);
 }
 
-int launch_fill_mask_tokens_ragged(float* x_full, const float* mask_token, const float* pos, const int* perm, const int* counts, int B, int Nt, int n_vis_min,
-                                   int D, hipStream_t stream) {
-    CWM_REQUIRE(D % 4 == 0 && counts && n_vis_min > 0 && n_vis_min <= Nt, "fill_mask_tokens (ragged): bad argument");
-    const int64_t total = (int64_t)B * (Nt - n_vis_min) * (D / 4);
-    if (total == 0) return 0;
-    hipLaunchKernelGGL(fill_mask_tokens_ragged_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x_full, mask_token, pos, perm, counts, Nt,
-                       n_vis_min, D, total);
+int launch_fill_mask_tokens(float* x_full, const float* mask_token, const float* pos, const int* perm, int B, int Nt, int n_vis, int D, hipStream_t stream,
+                            const int* counts, int n_vis_min) {
+    if (counts || n_vis_min > 0) {
+        CWM_REQUIRE(D % 4 == 0 && counts && n_vis_min > 0 && n_vis_min <= Nt, "fill_mask_tokens (ragged): bad argument");
+        const int64_t total = (int64_t)B * (Nt - n_vis_min) * (D / 4);
+        if (total == 0) return 0;
+        hipLaunchKernelGGL(fill_mask_tokens_ragged_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x_full, mask_token, pos, perm, counts, Nt,
+                           n_vis_min, D, total);
+        CWM_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    CWM_REQUIRE(D % 4 == 0, "fill_mask_tokens: D must be a multiple of 4");
+    const int64_t rows = (int64_t)B * (Nt - n_vis), rows_q = (rows + 7) / 8;
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(fill_mask_tokens4_kernel, dim3((unsigned)((rows_q * (D / 4) + 255) / 256)), dim3(256), 0, stream, x_full, mask_token, pos, perm, Nt,
+                       n_vis, D, rows, rows_q);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }

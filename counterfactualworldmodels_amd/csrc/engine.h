@@ -193,7 +193,8 @@ struct Engine {
     int run_patch_gather(const PatchGatherParams& p, int planes, hipStream_t s);
     int run_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_vis, int* perm, int* rank, int* err_rows, int planes, hipStream_t s,
                          int n_vis_min = 0, int* counts = nullptr);  // (n_vis_min > 0: ragged batches, kernels.h launch_index_gather)
-    int run_fill_mask_tokens(float* x_full, const float* mask_token, const float* pos, const int* perm, int B, int Nt, int n_vis, int D, hipStream_t s);
+    int run_fill_mask_tokens(float* x_full, const float* mask_token, const float* pos, const int* perm, int B, int Nt, int n_vis, int D, hipStream_t s,
+                             const int* counts = nullptr, int n_vis_min = 0);  // (counts: ragged batches, kernels.h launch_fill_mask_tokens)
     int run_unembed(const UnembedParams& p, hipStream_t s);
     // `launch()` between an event pair of class `kclass` (no events unless the class is enabled); work = FLOPs or bytes
     template <typename F>
@@ -207,7 +208,9 @@ struct Engine {
     int timer_end(EventPair* e, hipStream_t s);
     // the launches every forward is made of: LayerNorm of `rows` contiguous rows into the GEMM A-operand layout, and y = A W^T + bias in fp32 (+ resid), in
     // the A-operand layout (what the MFMA cross attention reads its token fragments from), or through GELU in the A-operand layout
-    int layernorm_to(const float* x, int rows, int D, const float* g, const float* b, bf16* out, int planes, hipStream_t s);
+    int layernorm_to(const float* x, int rows, int D, const float* g, const float* b, bf16* out, int planes, hipStream_t s) {
+        return run_layernorm(layernorm_rows(x, D, D, g, b, ln_eps, rows, out, D), planes, s);
+    }
     int linear_f32(const bf16* A, int rows, int K, const LinearW& L, float* C, const float* resid, int planes, hipStream_t s);
     int linear_operand(const bf16* A, int rows, int K, const LinearW& L, bf16* out, int planes, hipStream_t s);
     int linear_gelu(const bf16* A, int rows, int K, const LinearW& L, bf16* out, int planes, hipStream_t s);
@@ -265,11 +268,25 @@ struct WsShift {
 };
 
 GemmParams gemm_base(const bf16* A, int lda, const LinearW& L, int M, int planes);
+// The Q/K/V projection of B samples' first n_in of n_tok rows (A: [B * n_in][D], D = L.N / 3) with its per-head scatter.  Decoder block 0's table is built by the
+// same statement as a forward's rows (Engine::dec0_table, Engine::run_block): the two must stay bit-equal.
+inline GemmParams qkv_gemm(const bf16* A, const LinearW& L, int B, int n_in, int n_tok, int H, bf16* q, bf16* k, bf16* v, int64_t qk_plane, int planes) {
+    const int D = L.N / 3;
+    GemmParams g = gemm_base(A, D, L, B * n_in, planes);
+    set_qkv_epilogue(g, n_in, n_tok, D, D / H, q, k, v, qk_plane);
+    return g;
+}
 
 // fp32 [N][K] -> bf16 [Npad][Kpad] (hi only) and [Npad][2*Kpad] (hi/lo interleaved), zero padded
 int launch_pack_weight(const float* src, int N, int K, bf16* hi, bf16* il, int Npad, int Kpad, hipStream_t stream);
 
 // ---- what the stand-alone entry points (model.hip) and the development ones (dev.hip) share ----
+// The arithmetic mode of an entry point `fn` as the number of bf16 planes its operands have (fast: 1, parity: 2)
+static inline int mode_planes(const char* fn, int mode, int* planes) {
+    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "%s: bad mode", fn);
+    *planes = mode == CWM_MODE_PARITY ? 2 : 1;
+    return 0;
+}
 // Device buffers of one call, freed when it returns.  They allocate per call: not for hot loops.
 struct Scratch {
     std::vector<void*> ptrs;
@@ -296,5 +313,16 @@ int stage_linear_operands(Scratch& sc, const char* who, const float* a, const fl
                           LinearOperands* out);
 // qkv [B, N, 3, H, 64] fp32 -> Q (times scale), K, V [B * H, N, 64], hi plane and lo plane (qk_plane elements further) whatever the mode (model.hip)
 int launch_qkv_scatter(const float* qkv, int B, int N, int H, float scale, bf16* q, bf16* k, bf16* v, int64_t qk_plane, hipStream_t s);
+// Attention on qkv [B, N, 3, H, 64] fp32 with this thread's options (model.hip): Q / K / V scattered into `sc`'s buffers, then one launch_attention that writes
+// O into o_dst in the operand layout (rows of ldo columns; nullptr: a buffer of `sc`, rows of H * 64).  key_len: AttnParams.key_len or nullptr; q_off / n_q: the
+// query window (0, 0: all rows).  *o_out = where O went.  Nothing is synchronised.
+int attention_from_qkv(Scratch& sc, const char* who, const float* qkv, const int* key_len, bf16* o_dst, int ldo, int B, int N, int H, int q_off, int n_q, int planes,
+                       hipStream_t s, bf16** o_out);
+// mask -> permutation -> rank -> un-embed of y into out, frames x at strides (sb, sc, st); n_vis_min > 0: rows of n_vis_min .. n_vis visible tokens, y row 0 =
+// decoder row n_vis_min (a ragged batch).  Synchronises; CWM_ERR_MASK with the text of the case when a row's count is off (model.hip)
+int unembed_from_mask(const char* who, const float* y, const float* x, int64_t sb, int64_t sc, int64_t st, const uint8_t* mask, int B, int T, int C, int H, int W, int P,
+                      int n_vis_min, int n_vis, float* out, hipStream_t s);
+// Reads err[0] back on s (synchronising): CWM_ERR_MASK with the text of the case (n_vis_min > 0: a ragged batch's range) when it is set
+int check_mask_err(const int* err, int n_vis_min, int n_vis, hipStream_t s);
 
 }  // namespace cwm

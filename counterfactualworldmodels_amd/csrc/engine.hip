@@ -501,10 +501,11 @@ int Engine::run_index_gather(const PatchGatherParams& p, const uint8_t* mask, in
                  [&] { return launch_index_gather(p, mask, n_vis, perm, rank, err_rows, planes, s, n_vis_min, counts); });
 }
 
-int Engine::run_fill_mask_tokens(float* x_full, const float* mask_token, const float* pos, const int* perm, int B, int Nt, int n_vis, int D,
-                                 hipStream_t s) {
-    return timed(CWM_KCLASS_FILL_MASK, (double)B * (Nt - n_vis) * D * 4.0, s,
-                 [&] { return launch_fill_mask_tokens(x_full, mask_token, pos, perm, B, Nt, n_vis, D, s); });
+int Engine::run_fill_mask_tokens(float* x_full, const float* mask_token, const float* pos, const int* perm, int B, int Nt, int n_vis, int D, hipStream_t s,
+                                 const int* counts, int n_vis_min) {
+    // (a ragged batch is booked with the rows its launch covers: from the least count on)
+    return timed(CWM_KCLASS_FILL_MASK, (double)B * (Nt - (counts ? n_vis_min : n_vis)) * D * 4.0, s,
+                 [&] { return launch_fill_mask_tokens(x_full, mask_token, pos, perm, B, Nt, n_vis, D, s, counts, n_vis_min); });
 }
 
 int Engine::run_unembed(const UnembedParams& p, hipStream_t s) {
@@ -562,14 +563,6 @@ GemmParams gemm_base(const bf16* A, int lda, const LinearW& L, int M, int planes
     return p;
 }
 
-int Engine::layernorm_to(const float* x, int rows, int D, const float* g, const float* b, bf16* out, int planes, hipStream_t s) {
-    LayerNormParams ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.x = x; ln.ldx = D; ln.gamma = g; ln.beta = b; ln.eps = ln_eps; ln.D = D; ln.rows = rows;
-    ln.out = out; ln.out_plane = (int64_t)rows * D; ln.ldo = D;
-    return run_layernorm(ln, planes, s);
-}
-
 int Engine::linear_f32(const bf16* A, int rows, int K, const LinearW& L, float* C, const float* resid, int planes, hipStream_t s) {
     GemmParams g = gemm_base(A, K, L, rows, planes);
     g.epi = EPI_F32; g.C = C; g.ldc = L.N; g.resid = resid; g.ldr = L.N;
@@ -611,12 +604,7 @@ int Engine::run_mlp(const float* ln_g, const float* ln_b, const LinearW& fc1, co
     const KeptRows kr(n_tok, n_keep);
     const int Mo = B * kr.n_out;
     int rc;
-    LayerNormParams ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.x = x; ln.ldx = D; ln.gamma = ln_g; ln.beta = ln_b; ln.eps = ln_eps; ln.D = D; ln.rows = Mo;
-    ln.out = sb.hbuf; ln.out_plane = (int64_t)Mo * D; ln.ldo = D;
-    if (kr.part) { ln.rows_out_per_b = kr.n_out; ln.rows_in_per_b = n_tok; ln.in_offset = kr.first; }
-    if ((rc = run_layernorm(ln, planes, s))) return rc;
+    if ((rc = run_layernorm(layernorm_rows(x, D, D, ln_g, ln_b, ln_eps, Mo, sb.hbuf, D, kr.part ? kr.n_out : 0, n_tok, kr.first), planes, s))) return rc;
     if ((rc = linear_gelu(sb.hbuf, Mo, D, fc1, sb.gbuf, planes, s))) return rc;
     return residual_gemm(*this, sb.gbuf, fc1.N, fc2, x, B, n_tok, kr, planes, s);
 }
@@ -631,31 +619,16 @@ int Engine::run_block(const BlockW& w, float* x, int B, int n_tok, int D, int H,
     const int64_t hplane = (int64_t)M * D;
     const KeptRows kr(n_tok, n_keep);
     // the rows LN1 and the Q/K/V projection compute: all, or (decoder block 0 with the table) the first tab_vis of every sample, compact in hbuf
-    const int n_in = tab_rows ? tab_vis : n_tok, Mi = B * n_in;
+    const int n_in = tab_rows ? tab_vis : n_tok;
     int rc;
-    LayerNormParams ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.x = x; ln.ldx = D; ln.gamma = w.ln1_g; ln.beta = w.ln1_b; ln.eps = ln_eps; ln.D = D; ln.rows = Mi;
-    ln.out = sb.hbuf; ln.out_plane = (int64_t)Mi * D; ln.ldo = D;
-    if (tab_rows) { ln.rows_out_per_b = n_in; ln.rows_in_per_b = n_tok; ln.in_offset = 0; }
-    if ((rc = run_layernorm(ln, planes, s))) return rc;
-
-    GemmParams g = gemm_base(sb.hbuf, D, w.qkv, Mi, planes);
-    g.epi = EPI_QKV;
-    g.rows_in = n_in; g.rows_out = n_tok; g.map_stride = n_tok;
-    g.q_out = sb.qbuf; g.k_out = sb.kbuf; g.v_out = sb.vbuf;
-    g.qk_plane = hplane;
-    g.qkv_dim = D; g.heads = H; g.head_dim = D / H; g.n_tok = n_tok;
-    g.q_scale = 1.0f / sqrtf((float)(D / H));    if ((rc = run_gemm(g, planes, s))) return rc;
+    if ((rc = run_layernorm(layernorm_rows(x, D, D, w.ln1_g, w.ln1_b, ln_eps, B * n_in, sb.hbuf, D, tab_rows ? n_in : 0, n_tok, 0), planes, s))) return rc;
+    if ((rc = run_gemm(qkv_gemm(sb.hbuf, w.qkv, B, n_in, n_tok, H, sb.qbuf, sb.kbuf, sb.vbuf, hplane, planes), planes, s))) return rc;
     if (tab_rows && (rc = timed(CWM_KCLASS_FILL_MASK, (double)B * (n_tok - n_in) * 3.0 * D * 2.0 * planes, s, [&] {
                          return launch_dec0_gather(tab_rows, tab_perm, sb.qbuf, sb.kbuf, sb.vbuf, hplane, B, n_tok, n_in, H, planes, s);
                      })))
         return rc;
 
-    AttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.q = sb.qbuf; a.k = sb.kbuf; a.v = sb.vbuf; a.qk_plane = hplane;
-    a.o = sb.hbuf; a.o_plane = (int64_t)B * kr.n_out * D; a.ldo = D; a.n_tok = n_tok; a.heads = H; a.batch = B;
+    AttnParams a = attn_dense(sb.qbuf, sb.kbuf, sb.vbuf, hplane, sb.hbuf, (int64_t)B * kr.n_out * D, D, B, H, n_tok);
     if (kr.part) { a.q_off = kr.first; a.n_q = kr.n_out; }
     // (ragged batch: O rows at and past a sample's count are not written -- hbuf keeps LN1's rows there, finite padding for the row-wise launches below)
     a.key_len = key_len;
@@ -709,10 +682,8 @@ int Engine::to_decoder(const StreamW& S, const StreamWs& w, int B, int n_vis, in
     g.epi = EPI_F32; g.C = w.x_dec; g.ldc = S.dec_dim;
     g.resid = S.pos_dec_ext; g.ldr = S.dec_dim; g.resid_rowmap = w.perm; g.rows_in = n_vis; g.rows_out = next; g.map_stride = next;
     if ((rc = run_gemm(g, planes, s))) return rc;
-    if (counts)  // ragged batch: the GEMM above also wrote the padding rows [counts[b], n_vis) of every sample; the mask tokens start at counts[b]
-        return timed(CWM_KCLASS_FILL_MASK, (double)B * (next - n_vis_min) * S.dec_dim * 4.0, s,
-                     [&] { return launch_fill_mask_tokens_ragged(w.x_dec, S.mask_token, S.pos_dec_ext, w.perm, counts, B, next, n_vis_min, S.dec_dim, s); });
-    return run_fill_mask_tokens(w.x_dec, S.mask_token, S.pos_dec_ext, w.perm, B, next, n_vis, S.dec_dim, s);  // (no launch when nothing is masked)
+    // (no launch when nothing is masked.  Ragged batch: the GEMM above also wrote the padding rows [counts[b], n_vis) of every sample; the mask tokens start at counts[b])
+    return run_fill_mask_tokens(w.x_dec, S.mask_token, S.pos_dec_ext, w.perm, B, next, n_vis, S.dec_dim, s, counts, n_vis_min);
 }
 
 // Row p of the table = what decoder block 0 computes for a mask token at position p: x = mask_token + pos_dec[p] (the fill kernel over the identity
@@ -733,19 +704,8 @@ int Engine::dec0_table(const StreamW& S, int planes, float* x_tmp, bf16* h_tmp, 
     const BlockW& w = S.dec[0];
     int rc;
     if ((rc = launch_iota(perm_tmp, Nt, s)) || (rc = launch_fill_mask_tokens(x_tmp, S.mask_token, S.pos_dec_ext, perm_tmp, 1, Nt, 0, D, s))) return rc;
-    LayerNormParams ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.x = x_tmp; ln.ldx = D; ln.gamma = w.ln1_g; ln.beta = w.ln1_b; ln.eps = ln_eps; ln.D = D; ln.rows = Nt;
-    ln.out = h_tmp; ln.out_plane = plane; ln.ldo = D;
-    if ((rc = launch_layernorm(ln, planes, s))) return rc;
-    GemmParams g = gemm_base(h_tmp, D, w.qkv, Nt, planes);
-    g.epi = EPI_QKV;
-    g.rows_in = Nt; g.rows_out = Nt; g.map_stride = Nt;
-    g.q_out = t.qkv; g.k_out = t.qkv + planes * plane; g.v_out = t.qkv + 2 * planes * plane;
-    g.qk_plane = plane;
-    g.qkv_dim = D; g.heads = H; g.head_dim = D / H; g.n_tok = Nt;
-    g.q_scale = 1.0f / sqrtf((float)(D / H));
-    if ((rc = run_gemm(g, planes, s, false))) return rc;
+    if ((rc = launch_layernorm(layernorm_rows(x_tmp, D, D, w.ln1_g, w.ln1_b, ln_eps, Nt, h_tmp, D), planes, s))) return rc;
+    if ((rc = run_gemm(qkv_gemm(h_tmp, w.qkv, 1, Nt, Nt, H, t.qkv, t.qkv + planes * plane, t.qkv + 2 * planes * plane, plane, planes), planes, s, false))) return rc;
     t.built = true;
     t.loads = loads;
     return 0;
@@ -753,15 +713,9 @@ int Engine::dec0_table(const StreamW& S, int planes, float* x_tmp, bf16* h_tmp, 
 
 int Engine::head_rows(const StreamW& S, const StreamWs& w, int B, int n_out, float* out, int planes, hipStream_t s) {
     const int next = S.n_slots();
-    LayerNormParams ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.x = w.x_dec; ln.ldx = S.dec_dim; ln.gamma = S.dec_norm_g; ln.beta = S.dec_norm_b; ln.eps = ln_eps; ln.D = S.dec_dim;
-    ln.rows = B * n_out; ln.rows_out_per_b = n_out; ln.rows_in_per_b = next; ln.in_offset = next - n_out;
-    ln.out = w.sb.hbuf; ln.out_plane = (int64_t)B * n_out * S.dec_dim; ln.ldo = S.dec_dim;
+    const LayerNormParams ln = layernorm_rows(w.x_dec, S.dec_dim, S.dec_dim, S.dec_norm_g, S.dec_norm_b, ln_eps, B * n_out, w.sb.hbuf, S.dec_dim, n_out, next, next - n_out);
     if (int rc = run_layernorm(ln, planes, s)) return rc;
-    GemmParams g = gemm_base(w.sb.hbuf, S.dec_dim, S.head, B * n_out, planes);
-    g.epi = EPI_F32; g.C = out; g.ldc = S.out_dim;
-    return run_gemm(g, planes, s);
+    return linear_f32(w.sb.hbuf, B * n_out, S.dec_dim, S.head, out, nullptr, planes, s);
 }
 
 }  // namespace cwm

@@ -88,6 +88,17 @@ struct GemmParams {
     const Tuning* tune;  // execution options of the calling model (nullptr: defaults)
 };
 
+// The EPI_QKV fields of a launch, written here and nowhere else: samples of n_in rows (the first n_in of n_tok tokens each) scattered per head into
+// q / k / v [B * heads][n_tok][head_dim], Q times head_dim^-0.5.  (With a LinearW: engine.h qkv_gemm.)
+inline void set_qkv_epilogue(GemmParams& p, int n_in, int n_tok, int D, int head_dim, bf16* q, bf16* k, bf16* v, int64_t qk_plane) {
+    p.epi = EPI_QKV;
+    p.rows_in = n_in; p.rows_out = n_tok; p.map_stride = n_tok;
+    p.q_out = q; p.k_out = k; p.v_out = v;
+    p.qk_plane = qk_plane;
+    p.qkv_dim = D; p.heads = D / head_dim; p.head_dim = head_dim; p.n_tok = n_tok;
+    p.q_scale = 1.0f / sqrtf((float)head_dim);
+}
+
 constexpr int kSplitKSlots = 512;  // >= CUs: a split launch has at most one part per CU
 int splitk_workspace_alloc(float** slabs, unsigned** counts, hipStream_t stream);  // counters zeroed on `stream`
 // Everything decided before a GEMM launch, by gemm_plan and nowhere else; launch_gemm_part turns part i into one kernel launch.
@@ -142,6 +153,15 @@ struct AttnParams {
     const int* key_len;
 };
 
+// Attention over all N tokens of B * H (batch, head) pairs, O rows of ldo columns; q_off / n_q (a query window), key_len and tune are the caller's to set
+inline AttnParams attn_dense(const bf16* q, const bf16* k, const bf16* v, int64_t qk_plane, bf16* o, int64_t o_plane, int ldo, int B, int H, int N) {
+    AttnParams a = {};
+    a.q = q; a.k = k; a.v = v; a.qk_plane = qk_plane;
+    a.o = o; a.o_plane = o_plane; a.ldo = ldo;
+    a.n_tok = N; a.heads = H; a.batch = B;
+    return a;
+}
+
 int launch_attention(const AttnParams& p, int planes, hipStream_t stream);
 int attention_pipe_prof(int i);  // per-phase s_memtime totals of block 0 wave 0 (builds with -DCWM_ATTN_PROF only)
 int launch_attention_pipe(const AttnParams& p, int planes, hipStream_t stream);  // attention_pipe.hip; arguments checked by launch_attention
@@ -163,11 +183,22 @@ struct LayerNormParams {
     float* out_f32;  // optional fp32 copy of the normalised rows ([rows][D]); may be nullptr
 };
 
+// `rows` rows of D columns into out [planes][rows][ldo]; rows_out_per_b > 0: the per-sample row window of the struct (the other two are not read without it)
+inline LayerNormParams layernorm_rows(const float* x, int ldx, int D, const float* gamma, const float* beta, float eps, int rows, bf16* out, int ldo,
+                                      int rows_out_per_b = 0, int rows_in_per_b = 0, int in_offset = 0) {
+    LayerNormParams p = {};
+    p.x = x; p.ldx = ldx; p.gamma = gamma; p.beta = beta; p.eps = eps; p.D = D; p.rows = rows;
+    p.rows_out_per_b = rows_out_per_b; p.rows_in_per_b = rows_in_per_b; p.in_offset = in_offset;
+    p.out = out; p.out_plane = (int64_t)rows * ldo; p.ldo = ldo;
+    return p;
+}
+
 int launch_layernorm(const LayerNormParams& p, int planes, hipStream_t stream);
 
 // mask[B,Nt] (1 = masked) -> perm[B,Nt] = [visible tokens ascending | masked tokens ascending];
 // err[0] is set to 1 if any row's visible count != n_vis.
-int launch_mask_to_perm(const uint8_t* mask, int B, int Nt, int n_vis, int* perm, int* err, hipStream_t stream);
+// Ragged batches (n_vis_min > 0): err[0] is set for a row of fewer than n_vis_min or more than n_vis visible tokens, counts[b] = the row's visible count
+int launch_mask_to_perm(const uint8_t* mask, int B, int Nt, int n_vis, int* perm, int* err, hipStream_t stream, int n_vis_min = 0, int* counts = nullptr);
 // RectangularizeMasks on device masks (elementwise.hip): masked count per row; apply the host's picks [R | rows | offsets | to_value | picks] in place
 int launch_mask_row_counts(const uint8_t* mask, int B, int Nt, int* counts, hipStream_t stream);
 int launch_mask_flip_picks(uint8_t* mask, int B, int Nt, const int* table, int n_rows, hipStream_t stream);  // table rows outside [0, B) are skipped
@@ -210,14 +241,11 @@ int launch_flow_rgb_gather(const FlowRgbGatherParams& p, int planes, hipStream_t
 // Ragged batches (n_vis_min > 0): err_rows[b] = (count outside [n_vis_min, n_vis]), counts[b] = the row's visible count; rows behind it are gathered as zeros
 int launch_index_gather(const PatchGatherParams& p, const uint8_t* mask, int n_vis, int* perm, int* rank, int* err_rows, int planes, hipStream_t stream,
                         int n_vis_min = 0, int* counts = nullptr);
-// launch_mask_to_perm for rows of n_vis_min .. n_vis visible tokens: err[0] is set for a row outside that range, counts[b] = the row's visible count
-int launch_mask_to_perm_ragged(const uint8_t* mask, int B, int Nt, int n_vis_min, int n_vis, int* perm, int* err, int* counts, hipStream_t stream);
 
 // x_full[b][n_vis + j][:] = mask_token + pos[perm[b][n_vis + j]]   (vmae.py:556-557)
-int launch_fill_mask_tokens(float* x_full, const float* mask_token, const float* pos, const int* perm, int B, int Nt, int n_vis, int D, hipStream_t stream);
-// the same for rows [counts[b], Nt) of sample b (counts[b] >= n_vis_min; rows below n_vis_min are never touched)
-int launch_fill_mask_tokens_ragged(float* x_full, const float* mask_token, const float* pos, const int* perm, const int* counts, int B, int Nt, int n_vis_min,
-                                   int D, hipStream_t stream);
+// counts != nullptr (ragged batches): the same for rows [counts[b], Nt) of sample b (counts[b] >= n_vis_min > 0; rows below n_vis_min are never touched, n_vis is not read)
+int launch_fill_mask_tokens(float* x_full, const float* mask_token, const float* pos, const int* perm, int B, int Nt, int n_vis, int D, hipStream_t stream,
+                            const int* counts = nullptr, int n_vis_min = 0);
 
 // Decoder block 0's Q / K / V rows of the mask tokens, copied from the per-position table (engine.hip Engine::dec0_table):
 // {q, k, v}[pl * qk_plane + ((b * H + h) * Nt + j) * 64 ..] = tab[(which * planes + pl) * Nt * H * 64 + (h * Nt + perm[b * Nt + j]) * 64 ..] for j in [n_vis, Nt),

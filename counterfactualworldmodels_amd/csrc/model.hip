@@ -155,8 +155,7 @@ static int forward_lane(cwm_model* m, const cwm_forward_args* a, int b0, int B, 
         if ((rc = E.run_index_gather(pg, mask_in, Nv, w.perm, a->y_video_dev ? lw.rank : nullptr, lw.err, planes, s, rg_min, lw.counts))) return rc;
     } else {  // the four launches of rounds 1-4 (A/B and the bitwise cross-check of the fused kernel)
         CWM_HIP_CHECK(hipMemsetAsync(lw.err, 0, (size_t)B * sizeof(int), s));
-        if ((rc = rg_min > 0 ? launch_mask_to_perm_ragged(mask_in, B, Nt, rg_min, Nv, w.perm, lw.err, lw.counts, s) : launch_mask_to_perm(mask_in, B, Nt, Nv, w.perm, lw.err, s)))
-            return rc;
+        if ((rc = launch_mask_to_perm(mask_in, B, Nt, Nv, w.perm, lw.err, s, rg_min, lw.counts))) return rc;
         if ((rc = E.run_patch_gather(pg, planes, s))) return rc;
         if (a->y_video_dev && (rc = launch_perm_to_rank(w.perm, lw.rank, B, Nt, s))) return rc;
     }
@@ -248,13 +247,11 @@ extern "C" int cwm_forward(cwm_model* m, const cwm_forward_args* a_in) {
         std::vector<int> herr((size_t)B, 0);
         CWM_HIP_CHECK(hipMemcpyAsync(herr.data(), m->ws.err, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
         CWM_HIP_CHECK(hipStreamSynchronize(s));
-        if (m->ragged_min > 0 && std::any_of(herr.begin(), herr.end(), [](int e) { return e != 0; })) {
-            cwm_set_error("mask rows do not all have between %d (cwm_model_set_ragged) and n_vis=%d visible tokens", m->ragged_min, Nv);
-            return CWM_ERR_MASK;
-        }
         if (std::any_of(herr.begin(), herr.end(), [](int e) { return e != 0; })) {
-            cwm_set_error("mask rows do not all have n_vis=%d visible tokens (shape '[%d, -1, %d]' is invalid for the gathered input)", Nv, B,
-                          c.enc_dim);
+            if (m->ragged_min > 0)
+                cwm_set_error("mask rows do not all have between %d (cwm_model_set_ragged) and n_vis=%d visible tokens", m->ragged_min, Nv);
+            else
+                cwm_set_error("mask rows do not all have n_vis=%d visible tokens (shape '[%d, -1, %d]' is invalid for the gathered input)", Nv, B, c.enc_dim);
             return CWM_ERR_MASK;
         }
     }
@@ -323,11 +320,14 @@ __global__ void qkv_scatter_kernel(const float* qkv, int B, int N, int H, float 
 }
 
 // GEMM A-operand layout (row length ld_in, a multiple of 32) -> fp32 [rows][ld]
+// key_len (with bad and N; nullptr: every row): the rows are [B][N], of which the first key_len[b] of every batch row were written; the others, and every row when
+// key_len_check_kernel flagged a length in bad[0], are left as the caller passed them
 template <int PLANES>
-__global__ void merge_planes_kernel(const bf16* in, float* out, int rows, int ld, int ld_in) {
+__global__ void merge_planes_kernel(const bf16* in, float* out, int rows, int ld, int ld_in, const int* key_len, const int* bad, int N) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)rows * ld) return;
     const int r = (int)(i / ld), c = (int)(i - (int64_t)r * ld);
+    if (key_len && (bad[0] || r % N >= key_len[r / N])) return;
     const bf16* s = in + a_pos<PLANES>(r, ld_in, c);
     out[i] = (float)s[0] + (PLANES == 2 ? (float)s[kLoOffset] : 0.f);
 }
@@ -336,19 +336,6 @@ __global__ void merge_planes_kernel(const bf16* in, float* out, int rows, int ld
 __global__ void key_len_check_kernel(const int* key_len, int B, int N, int* bad) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B && (key_len[b] < 1 || key_len[b] > N)) bad[0] = 1;
-}
-
-// merge_planes_kernel for [B][N] rows of which the first key_len[b] of every batch row were written; the others, and every row when the check above
-// flagged a length, are left as the caller passed them
-template <int PLANES>
-__global__ void merge_planes_ragged_kernel(const bf16* in, float* out, int B, int N, int ld, const int* key_len, const int* bad) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)B * N * ld || bad[0]) return;
-    const int r = (int)(i / ld), c = (int)(i - (int64_t)r * ld);
-    const int b = r / N;
-    if (r - b * N >= key_len[b]) return;
-    const bf16* s = in + a_pos<PLANES>(r, ld, c);
-    out[i] = (float)s[0] + (PLANES == 2 ? (float)s[kLoOffset] : 0.f);
 }
 }  // namespace
 
@@ -362,10 +349,7 @@ int cwm::stage_linear_operands(Scratch& sc, const char* who, const float* a, con
     out->bias = sc.get<float>(Np, true);
     CWM_REQUIRE(out->A && out->W && out->bias, "%s: out of device memory", who);
     const unsigned gridA = (unsigned)(((int64_t)M * Kp + 255) / 256);
-    if (planes == 2)
-        hipLaunchKernelGGL(pad_split_rows_kernel<2>, dim3(gridA), dim3(256), 0, s, a, M, K, out->A, Kp);
-    else
-        hipLaunchKernelGGL(pad_split_rows_kernel<1>, dim3(gridA), dim3(256), 0, s, a, M, K, out->A, Kp);
+    dispatch_int<1, 2>(planes == 2 ? 2 : 1, [&](auto pl) { hipLaunchKernelGGL(pad_split_rows_kernel<pl.value>, dim3(gridA), dim3(256), 0, s, a, M, K, out->A, Kp); });
     if (int rc = launch_pack_weight(w, N, K, planes == 1 ? out->W : nullptr, planes == 2 ? out->W : nullptr, Np, Kp, s)) return rc;
     if (bias) CWM_HIP_CHECK(hipMemcpyAsync(out->bias, bias, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));
     return 0;
@@ -386,9 +370,9 @@ extern "C" int cwm_split_bf16(const float* x_dev, int64_t n, void* hi_dev, void*
 extern "C" int cwm_linear(const float* a_dev, const float* w_dev, const float* bias_dev, const float* resid_dev, float* c_dev, int M,
                           int N, int K, int gelu, int mode, void* stream) {
     CWM_REQUIRE(a_dev && w_dev && c_dev && M > 0 && N > 0 && K > 0, "cwm_linear: bad argument");
-    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_linear: bad mode");
+    int planes;
+    if (int rc = mode_planes("cwm_linear", mode, &planes)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int planes = mode == CWM_MODE_PARITY ? 2 : 1;
     Scratch sc;
     LinearOperands op;
     if (int rc = stage_linear_operands(sc, "cwm_linear", a_dev, w_dev, bias_dev, M, N, K, planes, s, &op)) return rc;
@@ -408,80 +392,68 @@ extern "C" int cwm_linear(const float* a_dev, const float* w_dev, const float* b
     if (int rc = launch_gemm(p, planes, s)) return rc;
     if (gelu) {
         const unsigned gridG = (unsigned)(((int64_t)M * N + 255) / 256);
-        if (planes == 2)
-            hipLaunchKernelGGL(merge_planes_kernel<2>, dim3(gridG), dim3(256), 0, s, G, c_dev, M, N, ldg);
-        else
-            hipLaunchKernelGGL(merge_planes_kernel<1>, dim3(gridG), dim3(256), 0, s, G, c_dev, M, N, ldg);
+        dispatch_int<1, 2>(planes, [&](auto pl) {
+            hipLaunchKernelGGL(merge_planes_kernel<pl.value>, dim3(gridG), dim3(256), 0, s, G, c_dev, M, N, ldg, (const int*)nullptr, (const int*)nullptr, 0);
+        });
     }
     CWM_HIP_CHECK(hipStreamSynchronize(s));
+    return CWM_OK;
+}
+
+int cwm::attention_from_qkv(Scratch& sc, const char* who, const float* qkv, const int* key_len, bf16* o_dst, int ldo, int B, int N, int H, int q_off, int n_q, int planes,
+                            hipStream_t s, bf16** o_out) {
+    const int64_t qk_plane = (int64_t)B * N * H * 64, o_plane = (int64_t)B * (n_q ? n_q : N) * ldo;
+    bf16* q = sc.get<bf16>(2 * qk_plane);
+    bf16* k = sc.get<bf16>(2 * qk_plane);
+    bf16* v = sc.get<bf16>(2 * qk_plane);
+    bf16* o = o_dst ? o_dst : sc.get<bf16>(2 * o_plane);
+    CWM_REQUIRE(q && k && v && o, "%s: out of device memory", who);
+    if (int rc = launch_qkv_scatter(qkv, B, N, H, 0.125f, q, k, v, qk_plane, s)) return rc;
+    AttnParams a = attn_dense(q, k, v, qk_plane, o, o_plane, ldo, B, H, N);
+    a.q_off = q_off; a.n_q = n_q;
+    a.key_len = key_len;
+    a.tune = &thread_tuning();
+    *o_out = o;
+    return launch_attention(a, planes, s);
+}
+
+// cwm_attention, and with a key count per batch row (AttnParams.key_len) cwm_attention_ragged: what a predictor needs to run rows with different numbers of visible
+// tokens as one batch, where the reference equalises the counts first (RectangularizeMasks, prediction.py:421) because its gather reshapes to one count (vmae.py:167)
+static int attention_entry(const char* who, const float* qkv_dev, const int32_t* key_len_dev, float* o_dev, int B, int N, int H, int mode, void* stream) {
+    int planes;
+    if (int rc = mode_planes(who, mode, &planes)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int D = H * 64;
+    Scratch sc;
+    int* bad = nullptr;
+    if (key_len_dev) {
+        bad = sc.get<int>(4, true);
+        CWM_REQUIRE(bad, "%s: out of device memory", who);
+        hipLaunchKernelGGL(key_len_check_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, key_len_dev, B, N, bad);
+    }
+    bf16* o;
+    if (int rc = attention_from_qkv(sc, who, qkv_dev, key_len_dev, nullptr, D, B, N, H, 0, 0, planes, s, &o)) return rc;
+    dispatch_int<1, 2>(planes, [&](auto pl) {
+        hipLaunchKernelGGL(merge_planes_kernel<pl.value>, dim3((unsigned)(((int64_t)B * N * D + 255) / 256)), dim3(256), 0, s, o, o_dev, B * N, D, D, key_len_dev, bad, N);
+    });
+    int hbad = 0;
+    if (bad) CWM_HIP_CHECK(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    CWM_HIP_CHECK(hipStreamSynchronize(s));
+    if (hbad) {
+        cwm_set_error("%s: a key count is outside [1, N = %d]; o_dev was not written", who, N);
+        return CWM_ERR_INVALID;
+    }
     return CWM_OK;
 }
 
 extern "C" int cwm_attention(const float* qkv_dev, float* o_dev, int B, int N, int H, int mode, void* stream) {
     CWM_REQUIRE(qkv_dev && o_dev && B > 0 && N > 0 && H > 0, "cwm_attention: bad argument");
-    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_attention: bad mode");
-    hipStream_t s = (hipStream_t)stream;
-    const int planes = mode == CWM_MODE_PARITY ? 2 : 1;
-    const int D = H * 64;
-    const int64_t qk_plane = (int64_t)B * N * D;
-    Scratch sc;
-    bf16* q = sc.get<bf16>(2 * qk_plane);
-    bf16* k = sc.get<bf16>(2 * qk_plane);
-    bf16* v = sc.get<bf16>(2 * qk_plane);
-    bf16* o = sc.get<bf16>(2 * qk_plane);
-    CWM_REQUIRE(q && k && v && o, "cwm_attention: out of device memory");
-    if (int rc = launch_qkv_scatter(qkv_dev, B, N, H, 0.125f, q, k, v, qk_plane, s)) return rc;
-    AttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.q = q; a.k = k; a.v = v; a.qk_plane = qk_plane; a.o = o; a.o_plane = qk_plane; a.ldo = D;
-    a.n_tok = N; a.heads = H; a.batch = B;
-    a.tune = &thread_tuning();
-    if (int rc = launch_attention(a, planes, s)) return rc;
-    if (planes == 2)
-        hipLaunchKernelGGL(merge_planes_kernel<2>, dim3((unsigned)((qk_plane + 255) / 256)), dim3(256), 0, s, o, o_dev, B * N, D, D);
-    else
-        hipLaunchKernelGGL(merge_planes_kernel<1>, dim3((unsigned)((qk_plane + 255) / 256)), dim3(256), 0, s, o, o_dev, B * N, D, D);
-    CWM_HIP_CHECK(hipStreamSynchronize(s));
-    return CWM_OK;
+    return attention_entry("cwm_attention", qkv_dev, nullptr, o_dev, B, N, H, mode, stream);
 }
 
-// cwm_attention with a key count per batch row (AttnParams.key_len): what a predictor needs to run rows with different numbers of visible tokens as one
-// batch, where the reference equalises the counts first (RectangularizeMasks, prediction.py:421) because its gather reshapes to one count (vmae.py:167)
 extern "C" int cwm_attention_ragged(const float* qkv_dev, const int32_t* key_len_dev, float* o_dev, int B, int N, int H, int mode, void* stream) {
     CWM_REQUIRE(qkv_dev && key_len_dev && o_dev && B > 0 && N > 0 && H > 0, "cwm_attention_ragged: bad argument");
-    CWM_REQUIRE(mode == CWM_MODE_FAST || mode == CWM_MODE_PARITY, "cwm_attention_ragged: bad mode");
-    hipStream_t s = (hipStream_t)stream;
-    const int planes = mode == CWM_MODE_PARITY ? 2 : 1;
-    const int D = H * 64;
-    const int64_t qk_plane = (int64_t)B * N * D;
-    Scratch sc;
-    bf16* q = sc.get<bf16>(2 * qk_plane);
-    bf16* k = sc.get<bf16>(2 * qk_plane);
-    bf16* v = sc.get<bf16>(2 * qk_plane);
-    bf16* o = sc.get<bf16>(2 * qk_plane);
-    int* bad = sc.get<int>(4, true);
-    CWM_REQUIRE(q && k && v && o && bad, "cwm_attention_ragged: out of device memory");
-    hipLaunchKernelGGL(key_len_check_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, key_len_dev, B, N, bad);
-    if (int rc = launch_qkv_scatter(qkv_dev, B, N, H, 0.125f, q, k, v, qk_plane, s)) return rc;
-    AttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.q = q; a.k = k; a.v = v; a.qk_plane = qk_plane; a.o = o; a.o_plane = qk_plane; a.ldo = D;
-    a.n_tok = N; a.heads = H; a.batch = B;
-    a.key_len = key_len_dev;
-    a.tune = &thread_tuning();
-    if (int rc = launch_attention(a, planes, s)) return rc;
-    if (planes == 2)
-        hipLaunchKernelGGL(merge_planes_ragged_kernel<2>, dim3((unsigned)((qk_plane + 255) / 256)), dim3(256), 0, s, o, o_dev, B, N, D, key_len_dev, bad);
-    else
-        hipLaunchKernelGGL(merge_planes_ragged_kernel<1>, dim3((unsigned)((qk_plane + 255) / 256)), dim3(256), 0, s, o, o_dev, B, N, D, key_len_dev, bad);
-    int hbad = 0;
-    CWM_HIP_CHECK(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    CWM_HIP_CHECK(hipStreamSynchronize(s));
-    if (hbad) {
-        cwm_set_error("cwm_attention_ragged: a key count is outside [1, N = %d]; o_dev was not written", N);
-        return CWM_ERR_INVALID;
-    }
-    return CWM_OK;
+    return attention_entry("cwm_attention_ragged", qkv_dev, key_len_dev, o_dev, B, N, H, mode, stream);
 }
 
 extern "C" int cwm_layernorm(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* y_dev, int rows, int D, float eps,
@@ -492,12 +464,24 @@ extern "C" int cwm_layernorm(const float* x_dev, const float* gamma_dev, const f
     const int ldo = round_up(D, 32);  // operand-layout rows are whole [32 hi | 32 lo] blocks
     bf16* tmp = sc.get<bf16>((size_t)2 * rows * ldo);
     CWM_REQUIRE(tmp, "cwm_layernorm: out of device memory");
-    LayerNormParams ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.x = x_dev; ln.ldx = D; ln.gamma = gamma_dev; ln.beta = beta_dev; ln.eps = eps; ln.D = D; ln.rows = rows;
-    ln.out = tmp; ln.out_plane = (int64_t)rows * ldo; ln.ldo = ldo; ln.out_f32 = y_dev;
+    LayerNormParams ln = layernorm_rows(x_dev, D, D, gamma_dev, beta_dev, eps, rows, tmp, ldo);
+    ln.out_f32 = y_dev;
     if (int rc = launch_layernorm(ln, 2, s)) return rc;
     CWM_HIP_CHECK(hipStreamSynchronize(s));
+    return CWM_OK;
+}
+
+int cwm::check_mask_err(const int* err, int n_vis_min, int n_vis, hipStream_t s) {
+    int herr = 0;
+    CWM_HIP_CHECK(hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, s));
+    CWM_HIP_CHECK(hipStreamSynchronize(s));
+    if (herr) {
+        if (n_vis_min > 0)
+            cwm_set_error("mask rows do not all have between %d and n_vis=%d visible tokens", n_vis_min, n_vis);
+        else
+            cwm_set_error("mask rows do not all have n_vis=%d visible tokens", n_vis);
+        return CWM_ERR_MASK;
+    }
     return CWM_OK;
 }
 
@@ -508,43 +492,35 @@ extern "C" int cwm_mask_to_perm(const uint8_t* mask_dev, int B, int Nt, int n_vi
     int* err = sc.get<int>(4, true);
     CWM_REQUIRE(err, "cwm_mask_to_perm: out of device memory");
     if (int rc = launch_mask_to_perm(mask_dev, B, Nt, n_vis, perm_dev, err, s)) return rc;
-    int herr = 0;
-    CWM_HIP_CHECK(hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, s));
-    CWM_HIP_CHECK(hipStreamSynchronize(s));
-    if (herr) {
-        cwm_set_error("mask rows do not all have n_vis=%d visible tokens", n_vis);
-        return CWM_ERR_MASK;
-    }
-    return CWM_OK;
+    return check_mask_err(err, 0, n_vis, s);
+}
+
+int cwm::unembed_from_mask(const char* who, const float* y, const float* x, int64_t sb, int64_t sc, int64_t st, const uint8_t* mask, int B, int T, int C, int H, int W,
+                           int P, int n_vis_min, int n_vis, float* out, hipStream_t s) {
+    const int Nt = T * (H / P) * (W / P);
+    Scratch tmp;
+    int* perm = tmp.get<int>((size_t)B * Nt);
+    int* rank = tmp.get<int>((size_t)B * Nt);
+    int* err = tmp.get<int>(4, true);
+    int* counts = n_vis_min > 0 ? tmp.get<int>((size_t)B) : nullptr;
+    CWM_REQUIRE(perm && rank && err && (counts || n_vis_min == 0), "%s: out of device memory", who);
+    int rc;
+    if ((rc = launch_mask_to_perm(mask, B, Nt, n_vis, perm, err, s, n_vis_min, counts))) return rc;
+    if ((rc = launch_perm_to_rank(perm, rank, B, Nt, s))) return rc;
+    const int y0 = n_vis_min > 0 ? n_vis_min : n_vis;  // the decoder row of y row 0
+    UnembedParams u = {};
+    u.y = y; u.x = x; u.sb = sb; u.st = st; u.sc = sc;
+    u.mask = mask; u.rank = rank; u.B = B; u.T = T; u.C = C; u.H = H; u.W = W; u.P = P; u.n_vis = y0; u.Nm = Nt - y0; u.out = out;
+    if ((rc = launch_unembed(u, s))) return rc;
+    return check_mask_err(err, n_vis_min, n_vis, s);
 }
 
 extern "C" int cwm_unembed(const float* y_tokens_dev, const float* x_dev, const uint8_t* mask_dev, int B, int T, int C, int H, int W, int P,
                            int n_vis, float* out_dev, void* stream) {
     CWM_REQUIRE(y_tokens_dev && x_dev && mask_dev && out_dev, "cwm_unembed: null argument");
     CWM_REQUIRE(P > 0 && H % P == 0 && W % P == 0, "cwm_unembed: image size must be divisible by the patch size");
-    hipStream_t s = (hipStream_t)stream;
-    const int Nt = T * (H / P) * (W / P);
-    Scratch sc;
-    int* perm = sc.get<int>((size_t)B * Nt);
-    int* rank = sc.get<int>((size_t)B * Nt);
-    int* err = sc.get<int>(4, true);
-    CWM_REQUIRE(perm && rank && err, "cwm_unembed: out of device memory");
-    int rc;
-    if ((rc = launch_mask_to_perm(mask_dev, B, Nt, n_vis, perm, err, s))) return rc;
-    if ((rc = launch_perm_to_rank(perm, rank, B, Nt, s))) return rc;
-    UnembedParams u;
-    memset(&u, 0, sizeof(u));
-    u.y = y_tokens_dev; u.x = x_dev; u.sb = (int64_t)T * C * H * W; u.st = (int64_t)C * H * W; u.sc = (int64_t)H * W;
-    u.mask = mask_dev; u.rank = rank; u.B = B; u.T = T; u.C = C; u.H = H; u.W = W; u.P = P; u.n_vis = n_vis; u.Nm = Nt - n_vis; u.out = out_dev;
-    if ((rc = launch_unembed(u, s))) return rc;
-    int herr = 0;
-    CWM_HIP_CHECK(hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, s));
-    CWM_HIP_CHECK(hipStreamSynchronize(s));
-    if (herr) {
-        cwm_set_error("mask rows do not all have n_vis=%d visible tokens", n_vis);
-        return CWM_ERR_MASK;
-    }
-    return CWM_OK;
+    return unembed_from_mask("cwm_unembed", y_tokens_dev, x_dev, (int64_t)T * C * H * W, (int64_t)H * W, (int64_t)C * H * W, mask_dev, B, T, C, H, W, P, 0, n_vis, out_dev,
+                             (hipStream_t)stream);
 }
 
 extern "C" int cwm_patch_error(const cwm_patch_error_args* a) {
