@@ -294,12 +294,20 @@ struct Scratch {
         for (void* p : ptrs) (void)hipFree(p);
     }
     template <typename T>
-    T* get(size_t count, bool zero = false) {
+    T* get(size_t count) {
         void* p = nullptr;
         if (hipMalloc(&p, count * sizeof(T) + 16) != hipSuccess) return nullptr;
         ptrs.push_back(p);
-        if (zero) (void)hipMemset(p, 0, count * sizeof(T));
         return (T*)p;
+    }
+    // Zeroed ON THE STREAM that uses the buffer.  (hipMemset runs on the null stream, which a non-blocking stream does not wait for, and while the null stream
+    // is busy it returns before the fill has landed: the call then read what the block last held -- the error word or the bias of an earlier call -- and the
+    // fill could land on top of what the call had written; tests/test_stream_order_gpu.py protocol B)
+    template <typename T>
+    T* get_zeroed(size_t count, hipStream_t s) {
+        T* p = get<T>(count);
+        if (p && hipMemsetAsync(p, 0, count * sizeof(T), s) != hipSuccess) return nullptr;
+        return p;
     }
 };
 // fp32 a [M][K], w [N][K], bias [N] (or nullptr) as a GEMM reads them in the mode of `planes`: A rows in the operand layout with K zero-padded to Kp =

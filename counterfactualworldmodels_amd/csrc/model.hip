@@ -346,7 +346,7 @@ int cwm::stage_linear_operands(Scratch& sc, const char* who, const float* a, con
     out->Np = Np;
     out->A = sc.get<bf16>((size_t)2 * M * Kp);
     out->W = sc.get<bf16>((size_t)2 * Np * Kp);
-    out->bias = sc.get<float>(Np, true);
+    out->bias = sc.get_zeroed<float>(Np, s);
     CWM_REQUIRE(out->A && out->W && out->bias, "%s: out of device memory", who);
     const unsigned gridA = (unsigned)(((int64_t)M * Kp + 255) / 256);
     dispatch_int<1, 2>(planes == 2 ? 2 : 1, [&](auto pl) { hipLaunchKernelGGL(pad_split_rows_kernel<pl.value>, dim3(gridA), dim3(256), 0, s, a, M, K, out->A, Kp); });
@@ -427,7 +427,7 @@ static int attention_entry(const char* who, const float* qkv_dev, const int32_t*
     Scratch sc;
     int* bad = nullptr;
     if (key_len_dev) {
-        bad = sc.get<int>(4, true);
+        bad = sc.get_zeroed<int>(4, s);
         CWM_REQUIRE(bad, "%s: out of device memory", who);
         hipLaunchKernelGGL(key_len_check_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, key_len_dev, B, N, bad);
     }
@@ -489,7 +489,7 @@ extern "C" int cwm_mask_to_perm(const uint8_t* mask_dev, int B, int Nt, int n_vi
     CWM_REQUIRE(mask_dev && perm_dev && B > 0 && Nt > 0, "cwm_mask_to_perm: bad argument");
     hipStream_t s = (hipStream_t)stream;
     Scratch sc;
-    int* err = sc.get<int>(4, true);
+    int* err = sc.get_zeroed<int>(4, s);
     CWM_REQUIRE(err, "cwm_mask_to_perm: out of device memory");
     if (int rc = launch_mask_to_perm(mask_dev, B, Nt, n_vis, perm_dev, err, s)) return rc;
     return check_mask_err(err, 0, n_vis, s);
@@ -501,7 +501,7 @@ int cwm::unembed_from_mask(const char* who, const float* y, const float* x, int6
     Scratch tmp;
     int* perm = tmp.get<int>((size_t)B * Nt);
     int* rank = tmp.get<int>((size_t)B * Nt);
-    int* err = tmp.get<int>(4, true);
+    int* err = tmp.get_zeroed<int>(4, s);
     int* counts = n_vis_min > 0 ? tmp.get<int>((size_t)B) : nullptr;
     CWM_REQUIRE(perm && rank && err && (counts || n_vis_min == 0), "%s: out of device memory", who);
     int rc;
