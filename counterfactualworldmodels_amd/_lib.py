@@ -116,6 +116,20 @@ class CwmPatchErrorArgs(C.Structure):
     ]
 
 
+class CwmTokenResponseArgs(C.Structure):
+    """cwm_token_response_args (include/cwm_hip.h): cwm_patch_error_args as `base` (geometry, mask, tokens, per-patch map, scratch and the stream), the
+    prediction compared against and the outputs; new_token_response_args() sets struct_size"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", CwmPatchErrorArgs),
+        ("y_ref_dev", C.c_void_p),
+        ("y_ref_stride_b", C.c_int64),
+        ("pixel_map_dev", C.c_void_p),
+        ("peak_index_dev", C.c_void_p),
+        ("stats_dev", C.c_void_p),
+    ]
+
+
 class CwmConjConfig(C.Structure):
     _fields_ = [
         ("main", CwmConfig),
@@ -548,6 +562,13 @@ def new_patch_error_args() -> CwmPatchErrorArgs:
     return a
 
 
+def new_token_response_args() -> CwmTokenResponseArgs:
+    a = CwmTokenResponseArgs()
+    a.struct_size = C.sizeof(CwmTokenResponseArgs)
+    a.base.struct_size = C.sizeof(CwmPatchErrorArgs)
+    return a
+
+
 def new_conj_forward_args() -> CwmConjForwardArgs:
     a = CwmConjForwardArgs()
     a.struct_size = C.sizeof(CwmConjForwardArgs)
@@ -594,6 +615,7 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     ),
     "cwm_patch_error": (C.c_int, [C.POINTER(CwmPatchErrorArgs)]),
+    "cwm_token_response": (C.c_int, [C.POINTER(CwmTokenResponseArgs)]),
     "cwm_mask_row_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_mask_flip_picks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cwm_prompt_table_expand": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),

@@ -287,6 +287,26 @@ struct PatchErrorParams {
 
 int launch_patch_error(const PatchErrorParams& p, hipStream_t stream);
 
+// Response of a perturbation, from the predicted tokens of the perturbed rows and of the clean one (elementwise.hip token_response_kernel):
+// r[b][Y][X] = sum_c (y - y_ref)^2 at the masked patches of frame `frame`, 0 at its visible ones; its per-patch mean, its first maximum, its sum and its
+// centroid.  No allocation, no synchronisation, no atomics: two calls on the same inputs are bit-equal.
+struct TokenResponseParams {
+    const float* y;        // [B][Nm][P*P*C], as PatchErrorParams::y
+    const float* y_ref;    // the same for the clean prediction; row b at b * ref_sb (0: one reference for all rows)
+    int64_t ref_sb;
+    const uint8_t* mask;   // [B][Nt]: the mask of y AND y_ref
+    int B, T, C, H, W, P;  // C <= 8, P in {4, 8, 16}
+    int n_vis, Nm;
+    int frame;             // 0 .. T-1
+    float* map;            // [B][H/P][W/P] or nullptr
+    float* pixel_map;      // [B][H][W] or nullptr
+    int* peak_index;       // [B] or nullptr: Y * W + X
+    float* stats;          // [B][4] or nullptr: peak, mass, centroid_y, centroid_x
+    float* scratch;        // [B][H/P][8]: per-workgroup partials (peak, its index as int bits, mass, sum r Y, sum r X); needed with peak_index or stats
+};
+
+int launch_token_response(const TokenResponseParams& p, hipStream_t stream);
+
 struct ShiftPromptParams {
     const float* x;         // [B][T][C][H][W] contiguous frames
     int B, S, T, C, H, W, P, frame, fix_passive;

@@ -539,6 +539,20 @@ extern "C" int cwm_patch_error(const cwm_patch_error_args* a) {
     return launch_patch_error(p, (hipStream_t)a->stream);
 }
 
+extern "C" int cwm_token_response(const cwm_token_response_args* a) {
+    CWM_REQUIRE(a && a->struct_size == sizeof(cwm_token_response_args), "cwm_token_response: args->struct_size must be sizeof(cwm_token_response_args)");
+    const cwm_patch_error_args& g = a->base;
+    TokenResponseParams p;
+    memset(&p, 0, sizeof(p));
+    p.y = g.y_tokens_dev; p.y_ref = a->y_ref_dev; p.ref_sb = a->y_ref_stride_b;
+    p.mask = g.mask_dev;
+    p.B = g.batch; p.T = g.T; p.C = g.C; p.H = g.H; p.W = g.W; p.P = g.P;
+    p.n_vis = g.n_vis; p.frame = g.frame;
+    if (p.P > 0 && p.T > 0 && p.H > 0 && p.W > 0) p.Nm = p.T * (p.H / p.P) * (p.W / p.P) - p.n_vis;  // (launch_token_response checks the sizes themselves)
+    p.map = g.map_dev; p.pixel_map = a->pixel_map_dev; p.peak_index = a->peak_index_dev; p.stats = a->stats_dev; p.scratch = g.scratch_dev;
+    return launch_token_response(p, (hipStream_t)g.stream);
+}
+
 extern "C" int cwm_mask_row_counts(const uint8_t* mask_dev, int B, int Nt, int32_t* counts_dev, void* stream) {
     CWM_REQUIRE(mask_dev && counts_dev && B > 0 && Nt > 0, "cwm_mask_row_counts: bad argument");
     return launch_mask_row_counts(mask_dev, B, Nt, counts_dev, (hipStream_t)stream);

@@ -1,4 +1,6 @@
-"""`MultiShiftPatchesAndMask`: several groups of patches moved by separate pixel shifts in one prompt (reference:
+"""Prompt perturbations.  `AddMarkers` (at the end of this file): the reference's marker counterfactuals, cwm/models/perturbation.py:329-476, plain torch.
+
+`MultiShiftPatchesAndMask`: several groups of patches moved by separate pixel shifts in one prompt (reference:
 cwm/models/perturbation.py:644-779, the generator's `multi_patch_shifter`, prediction.py:59-64).
 
 Same constructor arguments and call signature as the reference class, `(x, mask_sequence, perturbation_points_sequence=None,
@@ -167,3 +169,155 @@ class MultiShiftPatchesAndMask(nn.Module):
         table = np.broadcast_to(np.asarray(s_seq, dtype=np.int64)[None], (B, len(s_seq), 2))
         x_p, mask_ps = multi_shift_rows(x, points.permute(0, 2, 1), masks, table, P, frame, fix_passive=fix_passive)
         return x_p, mask_ps.view(m_seq.shape[:2])
+
+
+# ---- markers (reference: cwm/models/perturbation.py:329-476) ------------------------------------------------------------------------------------------------
+class MarkerShape:
+    """[ph, pw] float64 stencils of a marker: 'full', or 'cross' -- the rows and columns less than one pixel from the patch centre (perturbation.py:329-354)."""
+
+    shapes = ["full", "cross"]
+
+    def __init__(self, size):
+        self.size = tuple(int(s) for s in size)
+
+    def __call__(self, shape="full"):
+        if shape not in self.shapes:
+            raise NotImplementedError("%s not in set of shapes %s" % (shape, self.shapes))
+        if shape == "full":
+            return np.ones(self.size)
+        rows, cols = (np.abs(np.arange(s) - (s - 1) / 2) < 1.0 for s in self.size)
+        return (rows[:, None] | cols[None, :]).astype(np.float64)
+
+
+def paint_markers(img, markers, b, t, h, w, patch_hw):
+    """Marker k, [C,ph,pw], painted into patch (h[k], w[k]) of img[b[k], t[k]] IN PLACE, all K at once: where the marker's channel sum is > 0 the marker,
+    elsewhere the image (perturbation.py:405-411, the same arithmetic: m * marker + (1 - m) * image).  The K patches must be different ones (markers that
+    share a patch compose in order and are painted one call each).  img [R,T',C,H,W]; b, t, h, w: long tensors [K]."""
+    ph, pw = patch_hw
+    R, Tn, Cc, H, W = img.shape
+    v = img.view(R, Tn, Cc, H // ph, ph, W // pw, pw)
+    m = (markers.sum(1, True) > 0).to(img.dtype)
+    v[b, t, :, h, :, w, :] = m * markers + (1 - m) * v[b, t, :, h, :, w, :]  # (the indexed dimensions come first: [K,C,ph,pw])
+    return img
+
+
+class AddMarkers(nn.Module):
+    """Paint markers into patches of one frame and make those patches visible (reference class: perturbation.py:356-476, on `PatchPerturbation.forward`,
+    :99-113): the prompt of "where does this point go".  Same constructor and call arguments, numpy draws in the same order (per marker: the shape, then
+    the colour), frames and masks bit-equal to the reference's.  Plain torch on the tensors' device, CPU included.
+
+    What the reference does, kept: a call with neither `patch_idx_list` nor `num_random_patches` marks nothing (its "everywhere visible" branch reads a
+    mask it has just replaced by all-ones, :415, :424-427); a marked patch that was masked comes back visible (:455-456, :474); with `frame` an index, a
+    4-entry patch index counts its frame from `frame` (0 is `frame`, :446).  What it does not do, provided: 2- and 3-entry indices, (h, w) and (b, h, w),
+    which its painter accepts (:391-403) and its un-masking loop then fails on (:456) -- they mean row 0 / row b, frame 0 of the marked frames.  A mask
+    whose grid is not the patch grid (its stride branch, :464-472) raises NotImplementedError."""
+
+    def __init__(self, patch_size, marker_shapes=["full"], marker_color=[1, 0, 0], seed=0, **kwargs):
+        super().__init__()
+        self.patch_size = tuple(patch_size) if isinstance(patch_size, (tuple, list)) else (1, patch_size, patch_size)
+        if len(self.patch_size) == 2:
+            self.patch_size = (1,) + self.patch_size
+        self.marker_shapes = marker_shapes
+        self.marker_func = MarkerShape(size=self.patch_size[-2:])
+        self.marker_color = marker_color
+        # the reference's PatchPerturbation.__init__ (perturbation.py:26-28): a numpy stream of its own, and the GLOBAL torch generator seeded
+        self.seed = seed
+        self.rng = np.random.RandomState(seed=seed)
+        self.torch_rng = torch.manual_seed(seed)
+
+    def _get_marker_color(self, num_channels):
+        if self.marker_color is None:
+            return self.rng.random((3))
+        if isinstance(self.marker_color[0], (list, tuple, np.ndarray)):
+            return np.array((self.marker_color)[self.rng.choice(range(len(self.marker_color)))])
+        assert len(self.marker_color) == num_channels
+        return np.array(self.marker_color)
+
+    def sample_marker(self, num_channels=3):
+        """[C,ph,pw] float64: one draw of the shape, then the colour's (perturbation.py:384-389)"""
+        shape = self.marker_func(self.rng.choice(self.marker_shapes))
+        color = self._get_marker_color(num_channels)
+        return shape[None] * color[:, None, None]
+
+    def sample_markers(self, count, like, num_channels=3):
+        """`count` markers in draw order as one tensor [count,C,ph,pw] of `like`'s dtype and device"""
+        ph, pw = self.patch_size[-2:]
+        host = np.stack([self.sample_marker(num_channels) for _ in range(count)]) if count else np.zeros((0, num_channels, ph, pw))
+        return torch.tensor(host, device=like.device, dtype=like.dtype)
+
+    def sample_random_patch(self, batch_size, frames, grid):
+        """one (b, t, h, w) per row, three draws each (perturbation.py:79-91)"""
+        out = []
+        for b in range(batch_size):
+            t = self.rng.choice(frames)
+            out.append([b, int(t), int(self.rng.randint(grid[0])), int(self.rng.randint(grid[1]))])
+        return out
+
+    @staticmethod
+    def _complete(idx):
+        idx = [int(i) for i in (idx.tolist() if hasattr(idx, "tolist") else idx)]
+        assert len(idx) in (2, 3, 4), idx
+        return {2: [0, 0] + idx, 3: [idx[0], 0] + idx[1:], 4: idx}[len(idx)]
+
+    def forward(self, x, mask=None, perturbation_points=None, patch_idx_list=None, frame=0, num_random_patches=0):
+        if mask is None:
+            raise ValueError("AddMarkers needs the mask the markers are added to")
+        assert x.dim() == 5, x.shape
+        B, T, Cc, H, W = x.shape
+        pt, ph, pw = self.patch_size
+        grid = (T // pt, H // ph, W // pw)
+        mask = mask.clone()
+        if perturbation_points is None:
+            base = mask
+        else:
+            mask[perturbation_points] = 1
+            base = torch.logical_not(perturbation_points)
+        if int(np.prod(grid)) != int(np.prod(base.shape[1:])):
+            raise NotImplementedError("AddMarkers: a mask of %d tokens per row for a patch grid of %s" % (int(np.prod(base.shape[1:])), grid))
+        if frame is not None:
+            frame = frame % T
+        if patch_idx_list is None and not bool(num_random_patches):
+            patches = []
+        elif bool(num_random_patches):
+            patches = []
+            for _ in range(num_random_patches):
+                patches.extend(self.sample_random_patch(B, [0] if frame is not None else list(range(T)), grid[-2:]))
+        else:
+            assert hasattr(patch_idx_list, "__len__")
+            patches = patch_idx_list
+            if not isinstance(patches[0], (list, tuple, torch.Tensor, np.ndarray)):
+                patches = [patches]
+        patches = [self._complete(p) for p in patches]
+        x_marked = (x[:, frame].unsqueeze(1) if frame is not None else x).clone(memory_format=torch.contiguous_format)
+        visible = torch.ones((B, 1 if frame is not None else grid[0]) + grid[1:], dtype=torch.bool, device=x.device)
+        if patches:
+            markers = self.sample_markers(len(patches), x, Cc)
+            host = np.asarray(patches, dtype=np.int64)
+            # rows and frames as indexing a tensor (negative counts from the end); patch rows and columns inside the grid, where the reference's painter works
+            sizes = np.array([B, x_marked.shape[1], grid[1], grid[2]])
+            low = np.array([-B, -x_marked.shape[1], 0, 0])
+            if ((host < low) | (host >= sizes)).any():
+                raise IndexError("patch index outside rows, frames and grid %s: %s" % (sizes.tolist(), host[((host < low) | (host >= sizes)).any(1)].tolist()))
+            host = host % sizes
+            # markers on different patches all at once; a patch marked again starts another pass, so that its markers compose in list order
+            seen, passes = {}, []
+            for k, key in enumerate(map(tuple, host.tolist())):
+                n = seen.get(key, 0)
+                seen[key] = n + 1
+                if n == len(passes):
+                    passes.append([])
+                passes[n].append(k)
+            idx = torch.from_numpy(host).to(x.device)
+            for ks in passes:
+                sel = idx[ks]
+                paint_markers(x_marked, markers[ks], sel[:, 0], sel[:, 1], sel[:, 2], sel[:, 3], (ph, pw))
+            visible[idx[:, 0], idx[:, 1], idx[:, 2], idx[:, 3]] = False
+        if frame is not None:
+            x_marked = torch.cat([x[:, :frame], x_marked, x[:, frame + 1:]], 1)
+            full = torch.ones((B,) + grid, dtype=torch.bool, device=x.device)
+            full[:, frame] = visible[:, 0]
+            visible = full
+        mask_marked = torch.minimum(visible.view(base.shape), base)
+        if perturbation_points is not None:
+            mask_marked = torch.minimum(mask, mask_marked)
+        return x_marked, mask_marked

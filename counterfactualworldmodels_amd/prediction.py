@@ -25,7 +25,7 @@ from torch import nn
 from . import _lib
 from .config import IMAGENET_MEAN, IMAGENET_STD
 from .masking import RectangularizeMasks, upsample_masks
-from .perturbation import MultiShiftPatchesAndMask
+from .perturbation import AddMarkers, MultiShiftPatchesAndMask, paint_markers
 from .conjoined_vmae import ConjoinedPaddedVisionTransformer
 from .vmae import PretrainVisionTransformer
 
@@ -58,6 +58,17 @@ class _RectBatch:
         return self.x.shape[0]
 
 
+@dataclass
+class MarkerResponses:
+    """What `predict_marker_responses` returns for K markers: where each response peaks, how strong it is and where its weight lies.  Host arrays, but `maps`."""
+
+    peak_yx: np.ndarray    # [K,2] int64: (Y, X) of the first maximum of the response
+    peak: np.ndarray       # [K] float32: the response there
+    mass: np.ndarray       # [K] float32: the response summed over the frame
+    centroid: np.ndarray   # [K,2] float32: (Y, X) weighted by the response; the peak position where mass == 0
+    maps: Optional[torch.Tensor] = None  # [K,H,W] on the device, with return_maps
+
+
 class PredictorBasedGenerator(nn.Module):
     """Factual / counterfactual predictions from a masked predictor (reference class: prediction.py:17)."""
 
@@ -87,6 +98,8 @@ class PredictorBasedGenerator(nn.Module):
         # prediction.py:59-64: pixel shifts, several patch groups per prompt; its numpy stream is its own (seed 0), its torch.manual_seed(0) the one above
         self.multi_patch_shifter = MultiShiftPatchesAndMask(patch_size=self.patch_size, max_shift_fraction=max_shift_fraction, padding_mode="constant",
                                                             allow_fractional_shifts=True)
+        # the default marker of `predict_marker_responses` (perturbation.py:356-368: 'full', colour [1,0,0]); its torch.manual_seed(0) is again the one above
+        self.marker = AddMarkers(patch_size=self.patch_size)
         self.keypoint_predictor = keypoint_predictor
         if keypoint_predictor is not None:
             self.load_predictor(keypoint_predictor_load_path, model=keypoint_predictor)
@@ -583,6 +596,134 @@ class PredictorBasedGenerator(nn.Module):
             n_masked -= 1
         out = (cur, np.asarray(picks, dtype=np.int64), np.asarray(best, dtype=np.float32))
         return out + (trace,) if return_scores else out
+
+    # ---- marker counterfactuals: where a perturbation lands (perturbation.py:356-476 is the prompt; the read-out has no counterpart in the reference) ------
+    @staticmethod
+    def _marker_patches(patch_idx_list) -> np.ndarray:
+        """[K,3] (t, h, w) from entries (h, w) -- frame 0 --, (t, h, w) or (0, t, h, w): the conventions of `make_visible_from_patch_idx_list`"""
+        rows = []
+        for p in patch_idx_list:
+            p = [int(i) for i in (p.tolist() if hasattr(p, "tolist") else p)]
+            if len(p) not in (2, 3, 4):
+                raise ValueError("predict_marker_responses: a patch is (h, w), (t, h, w) or (0, t, h, w), got %s" % (p,))
+            if len(p) == 4 and p[0] != 0:
+                raise ValueError("predict_marker_responses marks ONE movie: the row of a (b, t, h, w) entry must be 0, got %s" % (p,))
+            rows.append(([0] + p if len(p) == 2 else p)[-3:])
+        if not rows:
+            raise ValueError("predict_marker_responses: patch_idx_list is empty")
+        return np.asarray(rows, dtype=np.int64)
+
+    @staticmethod
+    def _response_statistics(r):
+        """(peak_index [K] int64, stats [K,4]: peak, mass, centroid_y, centroid_x) of response maps r [K,H,W] in torch: the contract of cwm_token_response"""
+        K, H, W = r.shape
+        flat = r.reshape(K, -1)
+        idx = flat.argmax(1)
+        peak = flat.gather(1, idx[:, None])[:, 0]
+        mass = flat.sum(1)
+        Y = torch.arange(H, device=r.device, dtype=r.dtype)[None, :, None]
+        X = torch.arange(W, device=r.device, dtype=r.dtype)[None, None, :]
+        empty = mass == 0
+        cy = torch.where(empty, torch.div(idx, W, rounding_mode="floor").to(r.dtype), (r * Y).sum((1, 2)) / mass)
+        cx = torch.where(empty, (idx % W).to(r.dtype), (r * X).sum((1, 2)) / mass)
+        return idx, torch.stack([peak, mass, cy, cx], 1)
+
+    def _responses_take_fused_path(self, x, kwargs) -> bool:
+        """The fused path of `predict_marker_responses`: tokens of the marked rows and of the clean row -> one kernel (cwm_token_response), no predicted video."""
+        return x.is_cuda and x.dim() == 5 and self._uses_fused_path((), kwargs)
+
+    def predict_marker_responses(self, x, patch_idx_list, mask=None, frame=-1, marker=None, sample_batch_size=None, return_maps=False, **kwargs):
+        """Where K marker counterfactuals land.  x [1,T,C,H,W] is one movie; prompt k is x with ONE marker (`marker`, an `AddMarkers`; default a 'full'
+        marker of colour [1,0,0]) painted into patch k of `patch_idx_list` -- (h, w) in frame 0, (t, h, w) or (0, t, h, w) -- under `mask` (default:
+        `get_zeros_mask(frame=-1)`).  The response of prompt k is r_k[Y][X] = sum_c (prediction_k - clean prediction)^2 over predicted frame `frame`.
+        Returns a `MarkerResponses`: peak_yx [K,2] (the first maximum of r_k, as torch.argmax), peak [K], mass [K] = sum r_k, centroid [K,2] =
+        sum r_k (Y, X) / mass (the peak position when mass == 0), on the host, and with return_maps the maps [K,H,W] on the device.
+
+        The marked patches must be visible under `mask` and lie in another frame than `frame` (ValueError otherwise): all rows then keep the clean row's
+        mask, their predicted tokens line up with the clean row's, and a visible patch of `frame` is the same input pixel in every row.  The plain predictor on the GPU predicts the clean row once and the K rows in chunks of `sample_batch_size`, all to
+        TOKENS, and each chunk is one library call (cwm_token_response) on its tokens and the clean row's: no predicted video and no difference map is
+        built, and the host reads the results back once, at the end (the mask once, before anything is queued).  Everything else -- a conjoined predictor, predictor keyword arguments (tensors of one
+        row), CPU tensors, temporal_dim 1 -- composes `predict`, the squared difference and the same statistics in torch, chunked the same way."""
+        if x.dim() != 5 or x.shape[0] != 1:
+            raise ValueError("predict_marker_responses marks ONE movie: x must be [1,T,C,H,W], got %s" % (tuple(x.shape),))
+        if frame is None:
+            raise ValueError("predict_marker_responses reads the response in one predicted frame: frame must be an index")
+        _, T, Cc, H, W = x.shape
+        P = self.patch_size[-1]
+        h, w = H // P, W // P
+        n, Nt = h * w, T * h * w
+        f = frame % T
+        dev = x.device
+        self.set_image_size(x.shape[-2:])
+        self.inp_shape = x.shape
+        marker = self.marker if marker is None else marker
+        if tuple(marker.patch_size[-2:]) != (P, P):
+            raise ValueError("the marker's patches are %s, the predictor's %d x %d" % (tuple(marker.patch_size[-2:]), P, P))
+        patches = self._marker_patches(patch_idx_list)
+        if (patches < 0).any() or (patches >= np.array([T, h, w])).any():
+            raise ValueError("predict_marker_responses: a patch outside the %d x %d x %d grid" % (T, h, w))
+        if (patches[:, 0] == f).any():
+            raise ValueError("predict_marker_responses reads the response in predicted frame %d: a marker goes into another frame, got %s" % (
+                f, patches[patches[:, 0] == f].tolist()))
+        K = len(patches)
+        mask = (self.get_zeros_mask(x, frame=-1) if mask is None else mask).reshape(1, Nt).to(device=dev, dtype=torch.bool)
+        host = mask[0].cpu().numpy()
+        tokens = patches[:, 0] * n + patches[:, 1] * w + patches[:, 2]
+        if host[tokens].any():
+            raise ValueError("predict_marker_responses: marked patches must be visible under the mask; masked: %s" % patches[host[tokens]].tolist())
+        n_masked = int(host.sum())
+        markers = marker.sample_markers(K, x, Cc)  # (the marker's numpy draws, in list order)
+        where = torch.from_numpy(patches).to(dev)
+        step = K if not sample_batch_size else max(1, int(sample_batch_size))
+        fused = self._responses_take_fused_path(x, kwargs)
+        index = torch.empty((K,), device=dev, dtype=torch.int32)
+        stats = torch.empty((K, 4), device=dev, dtype=torch.float32)
+        maps = torch.empty((K, H, W), device=dev, dtype=torch.float32) if return_maps else None
+
+        def prompts(r0, r1):
+            xk = x.to(torch.float32).expand(r1 - r0, -1, -1, -1, -1).clone(memory_format=torch.contiguous_format)
+            sel = where[r0:r1]
+            return paint_markers(xk, markers[r0:r1], torch.arange(r1 - r0, device=dev), sel[:, 0], sel[:, 1], sel[:, 2], (P, P))
+
+        if fused:
+            pred = self.predictor
+            pred.sync_weights(dev)
+
+            def tokens_of(frames, rows):
+                if n_masked == 0:  # (nothing masked: nothing is predicted, every response is 0)
+                    return None
+                xs, strides = pred._frame_strides(frames, 2, 1)
+                return pred._run(xs, strides, self.imagenet_normalize_inputs, rows, Nt - n_masked, False, check=False, weights_synced=True)[0]
+
+            y_ref = tokens_of(x, mask)
+            scratch = torch.empty((min(step, K), h, 8), device=dev, dtype=torch.float32)
+            a = _lib.new_token_response_args()
+            g = a.base
+            g.batch, g.T, g.C, g.H, g.W, g.P, g.n_vis, g.frame = 0, T, Cc, H, W, P, Nt - n_masked, f
+            g.scratch_dev, g.stream = scratch.data_ptr(), _lib.current_stream_handle(dev)
+            a.y_ref_dev, a.y_ref_stride_b = _lib.ptr(y_ref), 0
+            for r0 in range(0, K, step):
+                r1 = min(r0 + step, K)
+                rows = mask.expand(r1 - r0, Nt).contiguous()
+                y = tokens_of(prompts(r0, r1), rows)
+                g.batch, g.y_tokens_dev, g.mask_dev = r1 - r0, _lib.ptr(y), rows.data_ptr()
+                a.peak_index_dev, a.stats_dev = index[r0:r1].data_ptr(), stats[r0:r1].data_ptr()
+                a.pixel_map_dev = maps[r0:r1].data_ptr() if return_maps else None
+                with torch.cuda.device(dev):
+                    _lib.check(_lib.get_lib().cwm_token_response(C.byref(a)))
+        else:
+            clean = self.predict(x, mask.clone(), frame=f, **kwargs)
+            for r0 in range(0, K, step):
+                r1 = min(r0 + step, K)
+                kw = {k: (v.expand(r1 - r0, *v.shape[1:]) if torch.is_tensor(v) and v.shape[0] == 1 else v) for k, v in kwargs.items()}
+                video = self.predict(prompts(r0, r1), mask.expand(r1 - r0, Nt).clone(), frame=f, **kw)
+                r = ((video - clean) ** 2).sum(2)[:, 0].to(torch.float32)
+                index[r0:r1], stats[r0:r1] = self._response_statistics(r)
+                if return_maps:
+                    maps[r0:r1] = r
+        packed = torch.cat([index.view(torch.float32)[:, None], stats], 1).cpu().numpy()  # the call's one read-back (the indices travel as their bits)
+        flat, s = packed[:, 0].copy().view(np.int32).astype(np.int64), packed[:, 1:]
+        return MarkerResponses(np.stack([flat // W, flat % W], 1), s[:, 0].copy(), s[:, 1].copy(), s[:, 2:4].copy(), maps)
 
     # ---- per-sample batching (prediction.py:456-540) -----------------------------------------------------------------
     def sample_tile(self, z, num_samples):

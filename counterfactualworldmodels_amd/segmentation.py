@@ -342,6 +342,41 @@ class FlowGenerator(PredictorBasedGenerator):
                                                                  frame, **kwargs)
         return y_mocos, self.predict_flow(y_mocos, backward=backward, iters=raft_iters)
 
+    # ---- flow from marker counterfactuals: no flow network (no counterpart in the reference; its `AddMarkers` is the prompt) ---------------------------
+    @staticmethod
+    def marker_displacements(patches_hw, responses, patch, use_centroid=False):
+        """[K,2] float32 (dx, dy) -- RAFT's channel order -- from the centre of marked patch k, (h P + (P - 1) / 2, w P + (P - 1) / 2), to where its
+        response peaks (`responses.peak_yx`) or has its centroid (`responses.centroid`)"""
+        hw = np.asarray(patches_hw, dtype=np.float64).reshape(-1, 2)
+        centre = hw * patch + (patch - 1) / 2.0
+        to = np.asarray(responses.centroid if use_centroid else responses.peak_yx, dtype=np.float64)
+        return np.stack([to[:, 1] - centre[:, 1], to[:, 0] - centre[:, 0]], 1).astype(np.float32)
+
+    def predict_perturbation_flow(self, x, points=None, grid_stride=None, mask=None, use_centroid=False, min_mass=0., **kw):
+        """Displacements read out of the predictor itself: a marker is painted into a frame-0 patch of movie x [1,T,C,H,W], and where the prediction of
+        the last frame changes most is where that patch went (`predict_marker_responses`, whose keywords `kw` are passed on: marker, sample_batch_size,
+        frame).  points: K patches (h, w) -> displacements [K,2] as (dx, dy) in pixels, from the patch centre to the peak of the response, or to its
+        centroid.  grid_stride s instead: every s-th patch in both directions -> (flow [2, h // s, w // s], valid [h // s, w // s] = mass > min_mass):
+        a response of no weight says nothing about where its patch went.  Tensors on x's device."""
+        if (points is None) == (grid_stride is None):
+            raise ValueError("predict_perturbation_flow: give the patches as `points` or a `grid_stride`, not both")
+        P = self.patch_size[-1]
+        h, w = x.shape[-2] // P, x.shape[-1] // P
+        if grid_stride is not None:
+            s = int(grid_stride)
+            hh, ww = h // s, w // s
+            if s < 1 or hh < 1 or ww < 1:
+                raise ValueError("grid_stride = %s for a grid of %d x %d patches" % (grid_stride, h, w))
+            hw = np.stack(np.meshgrid(np.arange(hh) * s, np.arange(ww) * s, indexing="ij"), -1).reshape(-1, 2)
+        else:
+            hw = np.asarray([[int(i) for i in (p.tolist() if hasattr(p, "tolist") else p)] for p in points], dtype=np.int64).reshape(-1, 2)
+        res = self.predict_marker_responses(x, hw.tolist(), mask=mask, **kw)
+        flow = torch.from_numpy(self.marker_displacements(hw, res, P, use_centroid)).to(x.device)
+        if grid_stride is None:
+            return flow
+        valid = torch.from_numpy(res.mass > min_mass).to(x.device)
+        return flow.view(hh, ww, 2).permute(2, 0, 1).contiguous(), valid.view(hh, ww)
+
     # ---- statistics over the flow samples (segmentation.py:250-276, 479-547): device kernels, see flowstats.py ----------
     def compute_flow_samples_magnitude(self, flows, normalize=True, dim=-4, eps=1e-2):
         from . import flowstats

@@ -304,6 +304,33 @@ typedef struct cwm_patch_error_args {
  * fixed order (no atomics): two calls on the same inputs give the same bits. */
 CWM_API int cwm_patch_error(const cwm_patch_error_args* args);
 
+typedef struct cwm_token_response_args {
+    uint32_t struct_size;            /* sizeof(cwm_token_response_args); anything else: CWM_ERR_INVALID naming struct_size */
+    /* read: y_tokens_dev, mask_dev, batch, T, C, H, W, P, n_vis, frame (0 .. T-1), map_dev ([B, H/P, W/P] or NULL), scratch_dev, stream; the frame, target,
+     * region and mean fields are ignored, and so is base.struct_size */
+    cwm_patch_error_args base;
+    const float* y_ref_dev;          /* [B or 1, Nt - n_vis, C*P*P]: the prediction the tokens are compared against, same layout and same mask */
+    int64_t y_ref_stride_b;          /* elements between its rows' token blocks; 0 shares one reference prediction among all rows */
+    float* pixel_map_dev;            /* out [B, H, W] or NULL */
+    int32_t* peak_index_dev;         /* out [B] or NULL: Y*W + X of the peak */
+    float* stats_dev;                /* out [B, 4] or NULL: peak, mass, centroid_y, centroid_x */
+} cwm_token_response_args;
+
+/* Where two predictions of the same prompt geometry differ, without either predicted video: the response of a perturbation (the reference's marker
+ * counterfactuals, `AddMarkers` cwm/models/perturbation.py:356-476: "where does this point go") read from the predicted tokens of the perturbed rows and of
+ * the clean one.
+ * replaces: `predict` prediction.py:406-454 of both prompts, their squared difference summed over the channels, and its argmax / sum / centroid in torch.
+ *   With f = base.frame, n = (H/P)(W/P), pixel (Y, X) of frame f in patch (i, j), token tau = f n + i (W/P) + j:
+ *   r[b][Y][X] = sum_c (y[b][row][k] - y_ref[b][row][k])^2, c = 0 .. C-1 in that order from 0.f; row = the rank of tau among the masked tokens of row b,
+ *                clamped into [0, Nt - n_vis); k = (ph P + pw) C + c;  r = 0 where tau is visible (both predictions copy the same input pixel there)
+ *   base.map_dev   the mean of r over each patch, summed in the order cwm_patch_error sums
+ *   peak_index     the first maximum of r in linear order over ALL pixels of the frame (torch.argmax); a NaN is the maximum, the first NaN wins
+ *   stats          peak = r at that pixel; mass = sum r; centroid = sum r (Y, X) / mass, and the peak position (as floats) when mass == 0
+ * Asynchronous on base.stream: nothing is allocated and the host is not synchronised.  All sums have a fixed order (no atomics): two calls on the same
+ * inputs give the same bits.  base.scratch_dev, [B, H/P, 8] floats of per-workgroup partials, is required whenever peak_index_dev or stats_dev is set.
+ * Limits as cwm_patch_error: P 4, 8 or 16, C <= 8, W/P <= 256.  Argument errors: CWM_ERR_INVALID with a message, before anything is launched. */
+CWM_API int cwm_token_response(const cwm_token_response_args* args);
+
 /* `RectangularizeMasks` (masking.py:90-132) on device masks without reading them back.  The reference equalises the masked count of
  * the rows of a batch by un-masking / masking `torch.randperm(#candidates)[:surplus]` of a row's masked / visible tokens (one draw of the global CPU
  * generator per changed row, in row order).  The draws depend on the per-row COUNTS alone, so:
