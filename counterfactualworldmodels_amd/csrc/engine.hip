@@ -478,7 +478,9 @@ int Engine::run_attention(const AttnParams& p_in, int planes, hipStream_t s) {
     AttnParams p = p_in;
     p.tune = &tune;
     EventPair* e;
-    const double fl = 4.0 * (double)p.n_tok * p.n_tok * 64.0 * p.heads * p.batch;
+    // (a query window -- the pruned last decoder block -- computes n_q query rows against all n_tok keys)
+    const int n_q = p.n_q > 0 ? p.n_q : p.n_tok;
+    const double fl = 4.0 * (double)n_q * p.n_tok * 64.0 * p.heads * p.batch;
     if (int rc = timer_begin(CWM_KCLASS_ATTENTION, fl, s, &e)) return rc;
     if (int rc = launch_attention(p, planes, s)) return rc;
     return timer_end(e, s);
@@ -503,7 +505,8 @@ int Engine::run_index_gather(const PatchGatherParams& p, const uint8_t* mask, in
 
 int Engine::run_fill_mask_tokens(float* x_full, const float* mask_token, const float* pos, const int* perm, int B, int Nt, int n_vis, int D, hipStream_t s,
                                  const int* counts, int n_vis_min) {
-    // (a ragged batch is booked with the rows its launch covers: from the least count on)
+    // (a ragged batch is booked with the rows its launch covers: from the least count on; nothing masked: no launch, so nothing is booked)
+    if (Nt - (counts ? n_vis_min : n_vis) <= 0) return launch_fill_mask_tokens(x_full, mask_token, pos, perm, B, Nt, n_vis, D, s, counts, n_vis_min);
     return timed(CWM_KCLASS_FILL_MASK, (double)B * (Nt - (counts ? n_vis_min : n_vis)) * D * 4.0, s,
                  [&] { return launch_fill_mask_tokens(x_full, mask_token, pos, perm, B, Nt, n_vis, D, s, counts, n_vis_min); });
 }

@@ -222,15 +222,23 @@ CWM_API int cwm_conj_timing_enable(cwm_conj_model* m, int kclass, int enable);
 CWM_API int cwm_conj_timing_collect(cwm_conj_model* m, int kclass, struct cwm_kernel_stats* out);
 
 /* ---- timing hooks (bench.py roofline): HIP events around every launch of one kernel class ------ */
-#define CWM_KCLASS_GEMM 0        /* every GEMM launch */
-#define CWM_KCLASS_ATTENTION 1
+#define CWM_KCLASS_GEMM 0        /* every GEMM launch: 2*M*N*K with M the rows the launch computes (a pruned block: B * kept rows) and K rounded up to 64 (the
+                                  * operand is zero-padded to whole 64-element K tiles, which the hardware executes: K = 48 and 96, the patch-4 and IMU embeds, book 64 and 128) */
+#define CWM_KCLASS_ATTENTION 1   /* 4 * n_q * N * 64 per (batch, head): n_q query rows against N keys -- n_q = N, except the pruned last decoder block ("prune_last_block"),
+                                  * whose launch computes the Nm rows the head reads.  A ragged handle (cwm_model_set_ragged) is booked by launch extent: every class takes
+                                  * the cap args->n_vis as the rows per sample, and attention the full N although row b reads its first Nv_b keys only (the counts live
+                                  * on the device) */
 #define CWM_KCLASS_GEMM_WIDE 2   /* the GEMM launches that ran the 256x256 8-phase kernel (wide N with at least half a round of tiles: qkv, fc1, whole rounds of fc2) */
 #define CWM_KCLASS_GEMM_NARROW 3 /* ... the 128x128 kernels (proj, narrow N, head, patch embed, mixed-tiling remainders); both enabled / collected with class 0 */
 /* HBM-bound edge kernels (SURVEY.md 8d "reported separately as achieved GB/s"): for these classes `total_flops` holds the
  * algorithmic BYTES of the launches (each input element read once, each output element written once), not FLOPs */
 #define CWM_KCLASS_LAYERNORM 4    /* rows * D * (4 read + 2 * planes written) */
-#define CWM_KCLASS_PATCH_GATHER 5 /* visible tokens * C*P*P * (4 read + 2 * planes written) */
-#define CWM_KCLASS_FILL_MASK 6    /* B * Nm * Dd * 4 written (the positional rows come from L2) */
+#define CWM_KCLASS_PATCH_GATHER 5 /* visible tokens * C*P*P * (4 read + 2 * planes written); the fused index prologue ("index_fused", one launch) adds B * Nt * (1 mask byte
+                                   * read + 4 permutation written + 4 inverse permutation written when y_video_dev is set); with "index_fused" = 0 only the gather launch
+                                   * of the four is booked */
+#define CWM_KCLASS_FILL_MASK 6    /* the mask-token fill: B * Nm * Dd * 4 written (the positional rows come from L2; a ragged handle: Nm = Nt - n_vis_min, the rows its launch
+                                   * covers; no launch when Nm = 0) -- and, with "mask_token_tables", the copy of decoder block 0's mask-token Q / K / V rows from the
+                                   * table: one more launch of B * (Nt - n_vis) * 3 * Dd * 2 * planes written (the table's rows come from L2) */
 #define CWM_KCLASS_UNEMBED 7      /* B * T*C*H*W * (4 read + 4 written) */
 /* IMU-conditioned model only (cwm_conj_timing_*): FLOPs again */
 #define CWM_KCLASS_CROSS_ATTN 8   /* BidirectionalCrossAttention, both directions: 2 * (4 * N * M * hd) per head */
@@ -239,7 +247,7 @@ CWM_API int cwm_conj_timing_collect(cwm_conj_model* m, int kclass, struct cwm_ke
 typedef struct cwm_kernel_stats {
     int64_t launches;
     double total_ms;    /* sum of launch durations (HIP events on the launch stream) */
-    double total_flops; /* algorithmic FLOPs (2*M*N*K; attention 4*N*N*hd per head) of those launches; BYTES for classes 4-7 */
+    double total_flops; /* algorithmic FLOPs (2*M*N*K with K rounded up to 64; attention 4*n_q*N*hd per head) of those launches; BYTES for classes 4-7 */
 } cwm_kernel_stats;
 CWM_API int cwm_timing_enable(cwm_model* m, int kclass, int enable);
 /* Synchronises the recorded events, accumulates, and resets the event pool. */
