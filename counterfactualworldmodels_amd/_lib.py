@@ -658,6 +658,8 @@ SIGNATURES = {
     "cwm_raft_corr_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_raft_set_corr": (C.c_int, [C.c_void_p, C.c_int]),
     "cwm_raft_workspace_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cwm_raft_set_share_frames": (C.c_int, [C.c_void_p, C.c_int]),
+    "cwm_raft_encoder_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "cwm_raft_corr_lookup_on_the_fly": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_raft_convex_upsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_raft_head_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -683,6 +685,14 @@ DEV_SIGNATURES = {
     "cwm_dev_raft_instnorm_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "cwm_dev_raft_residual_join": (C.c_int, [C.POINTER(CwmDevConvSrc), C.POINTER(CwmDevConvSrc), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_dev_raft_cnet_split": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cwm_dev_raft_frame_slots": (C.c_int, [C.POINTER(CwmRaftForwardArgs), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cwm_dev_raft_corr_lookup_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                                 C.c_void_p, C.c_void_p]),
+    "cwm_dev_raft_fmap_pool_slots": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cwm_dev_raft_corr_lookup_on_the_fly_slots": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                                            C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "cwm_dev_raft_cnet_split_slots": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cwm_dev_raft_motion_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "cwm_dev_raft_gru_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "cwm_dev_raft_flow_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),

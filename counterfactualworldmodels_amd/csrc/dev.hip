@@ -370,6 +370,84 @@ extern "C" int cwm_dev_raft_cnet_split(const float* cn_dev, int64_t M, float* h_
     return CWM_OK;
 }
 
+// ---- frames shared between the pairs of a RAFT forward (tests/test_raft_share_cpu.py, tests/test_raft_share_kernels_gpu.py) ----
+extern "C" int cwm_dev_raft_frame_slots(const cwm_raft_forward_args* args, int share, int* slot1, int* slot2, int* cslot, int* n_fnet, int* n_cnet) {
+    CWM_REQUIRE(args && slot1 && slot2 && cslot && n_fnet && n_cnet, "cwm_dev_raft_frame_slots: null argument");
+    cwm_raft_forward_args a;
+    if (int rc = copy_args(a, args, offsetof(cwm_raft_forward_args, stream) + sizeof(void*), "cwm_dev_raft_frame_slots")) return rc;
+    CWM_REQUIRE(a.batch >= 1 && a.pairs >= 0 && (share == 0 || share == 1), "cwm_dev_raft_frame_slots: batch = %d, pairs = %d, share = %d", a.batch, a.pairs,
+                share);
+    const int ppg = a.pairs > 0 ? a.pairs : 1;
+    const float* const imgs[2] = {a.image1_dev, a.image2_dev};
+    const int64_t sb[2] = {a.image1_stride_b, a.image2_stride_b}, st[2] = {a.image1_stride_t, a.image2_stride_t},
+                  sc[2] = {a.image1_stride_c, a.image2_stride_c};
+    const FramePlan fp = raft_frame_plan(a.batch, ppg, imgs, sb, st, sc, share != 0);
+    for (int p = 0; p < a.batch * ppg; ++p) {
+        slot1[p] = (int)(fp.base1 + slot_at(fp.s1, p));
+        slot2[p] = (int)(fp.base2 + slot_at(fp.s2, p));
+        cslot[p] = (int)slot_at(fp.sc, p);
+    }
+    *n_fnet = fp.n_fnet;
+    *n_cnet = fp.n_cnet;
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_raft_corr_lookup_slots(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int ppg, int h8, int w8, int64_t s1b,
+                                              int64_t s1t, int64_t s2b, int64_t s2t, float* out_dev, void* stream) {
+    CWM_REQUIRE(fmap1_dev && fmap2_dev && coords_dev && out_dev && P > 0 && ppg > 0 && P % ppg == 0 && h8 >= 8 && w8 >= 8 && s1b >= 0 && s1t >= 0 && s2b >= 0 &&
+                    s2t >= 0,
+                "cwm_dev_raft_corr_lookup_slots: bad argument");
+    return raft_corr_lookup_run(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, out_dev, nullptr, 2, (hipStream_t)stream, SlotMap{ppg, s1b, s1t},
+                                SlotMap{ppg, s2b, s2t});
+}
+
+extern "C" int cwm_dev_raft_fmap_pool_slots(const float* in_dev, int n_out, int nt, int64_t in_sb, int64_t in_st, int h, int w, int C, float* out_dev,
+                                            void* stream) {
+    CWM_REQUIRE(in_dev && out_dev && n_out > 0 && nt > 0 && in_sb >= 0 && in_st >= 0 && h >= 2 && w >= 2 && C > 0, "cwm_dev_raft_fmap_pool_slots: bad argument");
+    if (int rc = launch_fmap_pool(in_dev, n_out, h, w, C, out_dev, (hipStream_t)stream, SlotMap{nt, in_sb, in_st})) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_raft_corr_lookup_on_the_fly_slots(const float* fmap1_dev, const float* const* fmap2_levels_dev, const float* coords_dev, int P, int ppg,
+                                                         int h8, int w8, int64_t s1b, int64_t s1t, int64_t s2b, int64_t s2t, int64_t s2pb, int64_t s2pt,
+                                                         float* out_dev, void* stream) {
+    CWM_REQUIRE(fmap1_dev && fmap2_levels_dev && coords_dev && out_dev && P > 0 && ppg > 0 && P % ppg == 0 && h8 >= 8 && w8 >= 8 && s1b >= 0 && s1t >= 0 &&
+                    s2b >= 0 && s2t >= 0 && s2pb >= 0 && s2pt >= 0,
+                "cwm_dev_raft_corr_lookup_on_the_fly_slots: bad argument");
+    CorrOnTheFlyParams lp = {};
+    lp.fmap1 = fmap1_dev;
+    lp.coords = coords_dev;
+    lp.hw8 = (int64_t)h8 * w8;
+    lp.M = P * lp.hw8;
+    lp.Kpad = 384;
+    lp.out = out_dev;
+    lp.out_ld = 324;
+    lp.ppg = ppg;
+    lp.s1b = s1b;
+    lp.s1t = s1t;
+    for (int l = 0; l < 4; ++l) {
+        CWM_REQUIRE(fmap2_levels_dev[l], "cwm_dev_raft_corr_lookup_on_the_fly_slots: level %d is null", l);
+        lp.fmap2[l] = fmap2_levels_dev[l];
+        lp.h[l] = h8 >> l;
+        lp.w[l] = w8 >> l;
+        lp.s2b[l] = l ? s2pb : s2b;
+        lp.s2t[l] = l ? s2pt : s2t;
+    }
+    if (int rc = launch_corr_lookup_on_the_fly(lp, 2, (hipStream_t)stream)) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return CWM_OK;
+}
+
+extern "C" int cwm_dev_raft_cnet_split_slots(const float* cn_dev, int64_t M, int64_t hw8, int ppg, int64_t sb, int64_t st, float* h_dev, float* x_dev,
+                                             void* stream) {
+    CWM_REQUIRE(cn_dev && h_dev && x_dev && M > 0 && hw8 > 0 && M % hw8 == 0 && ppg > 0 && (M / hw8) % ppg == 0 && sb >= 0 && st >= 0,
+                "cwm_dev_raft_cnet_split_slots: bad argument");
+    if (int rc = launch_cnet_split(cn_dev, M, h_dev, x_dev, (hipStream_t)stream, hw8, SlotMap{ppg, sb, st})) return rc;
+    CWM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return CWM_OK;
+}
+
 extern "C" int cwm_dev_raft_motion_finish(float* x_dev, const float* coords_dev, int64_t M, int h8, int w8, void* stream) {
     CWM_REQUIRE(x_dev && coords_dev && M > 0 && h8 > 0 && w8 > 0, "cwm_dev_raft_motion_finish: bad argument");
     if (int rc = launch_motion_finish(x_dev, coords_dev, M, h8, w8, (hipStream_t)stream)) return rc;

@@ -417,6 +417,38 @@ struct ImageSrc {
     int P, ppg;
     float scale;
 };
+// One run of distinct frames of a forward that shares frames (FramePlan): frame j is (g, t) = (j / nt, j % nt) at base + g * sb + t * st, n of them.
+// As an ImageSrc it is {base, -} with P = n and ppg = nt: the launches of a run read "image1" only.
+struct FrameRun {
+    const float* base;
+    int64_t sb, st, sc;
+    int n, nt;
+};
+// Where the per-frame operand of pair pr = (g, t) = (pr / ppg, pr % ppg) lies, in units of one frame's map: g * sb + t * st past the operand's pointer.
+// One map per pair, in pair order (a forward that shares nothing): {1, 1, 0}.
+struct SlotMap {
+    int ppg;
+    int64_t sb, st;
+};
+constexpr SlotMap kPairSlots = {1, 1, 0};
+// Which frames a forward's encoders run on, and where each pair finds the maps of its two images (raft_model.hip raft_frame_plan).  Made on the host from
+// the call's two image sources alone: two images are one frame when their address and channel stride are equal, and the plan merges only what one of
+// three patterns shows to be equal -- P1: a source with stride_t == 0 is one frame per batch row; P2: a source with stride_b == 0 is one frame for all
+// rows; P3: two sources of identical strides with image2 = image1 + k * stride_t, k in {0, +1, -1} (one frame repeated, a movie, a movie backwards) are
+// one run of pairs + |k| frames per row.  Anything else (and every call with `share` off, or with a negative stride) runs every pair's two images: 2 P fnet and P cnet images.
+struct FramePlan {
+    bool shared;         // false: nothing merged (the slot maps are the identity)
+    int n_fnet, n_cnet;  // frames through fnet / cnet
+    int n2;              // distinct image2 frames (what the on-the-fly correlation pools)
+    FrameRun frun[2];    // the frames of fnet in slot order: run 0, then run 1 (n = 0: none); n_fnet = frun[0].n + frun[1].n
+    FrameRun crun;       // the frames of cnet (image1's own): n_cnet = crun.n
+    int64_t base1, base2;    // pair (g, t): fmap1 at slot base1 + s1, fmap2 at base2 + s2 of fnet's output, the context map at slot sc of cnet's,
+    SlotMap s1, s2, sc, s2p; // the pooled levels of fmap2 at slot s2p of image2's own frame order;
+    SlotMap pool;            // image2's frame j lies at slot base2 + pool(j) of fnet's output
+};
+FramePlan raft_frame_plan(int batch, int ppg, const float* const img[2], const int64_t sb[2], const int64_t st[2], const int64_t sc[2], bool share);
+// the slot of pair pr under a map, on the host
+inline int64_t slot_at(const SlotMap& m, int64_t pr) { return (pr / m.ppg) * m.sb + (pr % m.ppg) * m.st; }
 struct Im2colParams {
     ConvSrc src[2];  // the input channels are src[0] then src[1] (nsrc = 2: the GRU's [h | x])
     int nsrc;
@@ -448,6 +480,10 @@ struct CorrOnTheFlyParams {
     int Kpad;
     float* out;
     int out_ld;
+    // frames shared between pairs (ppg > 0; all zero: fmap1 and every level hold one map per pair, in pair order): the maps of pair (g, t) are
+    // g * sb + t * st maps past fmap1 (s1) and past fmap2[l] (s2[l]: level 0 lies in the encoder's frame order, the pooled levels in image2's own)
+    int ppg;
+    int64_t s1b, s1t, s2b[4], s2t[4];
 };
 // RAFT.upsample_flow of a C-channel low-resolution field (C = 2: the flow, C = 1: the output head's map): the 3 x 3 neighbourhood times 8, combined
 // with the softmax of the 9 x 64 mask
@@ -485,15 +521,18 @@ int launch_im2col(const Im2colParams& p, int planes, hipStream_t s);
 constexpr int kInstNormMaxChunks = 16;
 int launch_instnorm_stats(const float* x, int n_img, int HW, int C, float eps, float* stats, double* work, hipStream_t s);
 int launch_residual_join(const ConvSrc& X, const ConvSrc& Y, int n_img, int HW, float* out, hipStream_t s);
-int launch_cnet_split(const float* cn, int64_t M, float* h, float* x, hipStream_t s);
+// `cs`: where pair pr's context map [hw8][256] lies in cn (kPairSlots: cn is [M][256], one map per pair)
+int launch_cnet_split(const float* cn, int64_t M, float* h, float* x, hipStream_t s, int64_t hw8 = 1, SlotMap cs = kPairSlots);
 int launch_coords_init(float* coords, int64_t M, int h8, int w8, hipStream_t s);
 // coords = grid + init (the warm start): element (c, y, x) of pair (g, t) = (pr / ppg, pr % ppg) of the planar field at init[g * sb + t * st + c * sc + y * w8 + x]
 int launch_coords_init_flow(float* coords, int P, int ppg, int h8, int w8, const float* init, int64_t sb, int64_t st, int64_t sc, hipStream_t s);
-int launch_corr(const float* f1, const float* f2, int P, int N, int D, float* corr, hipStream_t s);
+// corr[p] = f1[slot s1 of p] f2[slot s2 of p]^T / sqrt(D) for the P pairs; kPairSlots: f1 and f2 are [P][N][D]
+int launch_corr(const float* f1, const float* f2, int P, int N, int D, float* corr, hipStream_t s, SlotMap s1 = kPairSlots, SlotMap s2 = kPairSlots);
 int launch_corr_pool(const float* in, int64_t maps, int h, int w, float* out, hipStream_t s);
 int launch_corr_lookup(const CorrLookupParams& p, int planes, hipStream_t s);
 // avg_pool2d(2, stride 2), floor, of an NHWC map [P][h][w][C] -> [P][h / 2][w / 2][C] (C a multiple of 4, 16-byte aligned maps)
-int launch_fmap_pool(const float* in, int64_t P, int h, int w, int C, float* out, hipStream_t s);
+// `is`: map j of the output pools the input map at slot `is` of j (kPairSlots: the input is [P] maps in order)
+int launch_fmap_pool(const float* in, int64_t P, int h, int w, int C, float* out, hipStream_t s, SlotMap is = kPairSlots);
 // launch_corr_lookup's features from the feature maps themselves: every tap's correlation is computed when it is looked up (fp32 FMA, fixed order)
 int launch_corr_lookup_on_the_fly(const CorrOnTheFlyParams& p, int planes, hipStream_t s);
 int launch_motion_finish(float* x, const float* coords, int64_t M, int h8, int w8, hipStream_t s);
@@ -511,7 +550,9 @@ constexpr int kHeadHidden = 256;
 int launch_head_project(const float* hidden, int ld, const float* w, const float* bias, int64_t M, float* value, hipStream_t s);
 // CorrBlock built from two feature maps [P][h8 * w8][256] and indexed at coords [P * h8 * w8][2]: the pyramid (allocated and freed inside), then the lookup
 // as fp32 `out` [M][324], or (out == nullptr) as convc1's Kpad = 384 operand A in the layout of `planes`.  Synchronises the stream.
-int raft_corr_lookup_run(const float* fmap1, const float* fmap2, const float* coords, int P, int h8, int w8, float* out, bf16* A, int planes, hipStream_t s);
+// s1 / s2: where pair p's maps lie in fmap1 / fmap2 (kPairSlots: one map per pair, as above).
+int raft_corr_lookup_run(const float* fmap1, const float* fmap2, const float* coords, int P, int h8, int w8, float* out, bf16* A, int planes, hipStream_t s,
+                         SlotMap s1 = kPairSlots, SlotMap s2 = kPairSlots);
 // The same result from AlternateCorrBlock's form: what is allocated and freed inside is fmap2's three poolings, not a correlation volume.  Synchronises the stream.
 int raft_corr_lookup_on_the_fly_run(const float* fmap1, const float* fmap2, const float* coords, int P, int h8, int w8, float* out, bf16* A, int planes,
                                     hipStream_t s);

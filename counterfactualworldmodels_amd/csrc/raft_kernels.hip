@@ -132,13 +132,22 @@ __global__ void residual_join_kernel(const ConvSrc X, const ConvSrc Y, int64_t t
     }
 }
 
-// cnet output [M][256] -> h = tanh(net) [M][128], x[:, 0:128] = relu(inp)  (x row stride 256)
-__global__ void cnet_split_kernel(const float* cn, int64_t M, float* h, float* x) {
+// the slot of pair pr under `sm` (kernels.h SlotMap)
+__device__ __forceinline__ int64_t slot_of(const SlotMap& sm, int64_t pr) {
+    const int64_t g = pr / sm.ppg;
+    return g * sm.sb + (pr - g * sm.ppg) * sm.st;
+}
+
+// cnet output -> h = tanh(net) [M][128], x[:, 0:128] = relu(inp)  (x row stride 256), per pair; the context map [hw8][256] of pair pr is the one at
+// slot `cs` of pr in cn (pairs that share their first frame share it)
+__global__ void cnet_split_kernel(const float* cn, int64_t M, float* h, float* x, int64_t hw8, SlotMap cs) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M * 128; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t m = i >> 7;
         const int c = (int)(i & 127);
-        h[i] = tanhf(cn[m * 256 + c]);
-        x[m * 256 + c] = fmaxf(cn[m * 256 + 128 + c], 0.f);
+        const int64_t pr = m / hw8;
+        const float* src = cn + ((slot_of(cs, pr) - pr) * hw8 + m) * 256;
+        h[i] = tanhf(src[c]);
+        x[m * 256 + c] = fmaxf(src[128 + c], 0.f);
     }
 }
 
@@ -162,13 +171,13 @@ __global__ void coords_init_flow_kernel(float* coords, int64_t M, int h8, int w8
     }
 }
 
-// corr[p][i][j] = <f1[p][i], f2[p][j]> / sqrt(256), fp32 FMA (CorrBlock.corr); 64 x 64 tiles, 4 x 4 per thread
-__global__ void __launch_bounds__(256) corr_kernel(const float* f1, const float* f2, int N, int D, float scale, float* corr) {
+// corr[p][i][j] = <f1[slot s1 of p][i], f2[slot s2 of p][j]> / sqrt(256), fp32 FMA (CorrBlock.corr); 64 x 64 tiles, 4 x 4 per thread
+__global__ void __launch_bounds__(256) corr_kernel(const float* f1, const float* f2, int N, int D, float scale, float* corr, SlotMap s1, SlotMap s2) {
     __shared__ float As[16][64 + 4];
     __shared__ float Bs[16][64 + 4];
     const int p = blockIdx.z, i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
-    const float* a = f1 + (int64_t)p * N * D;
-    const float* b = f2 + (int64_t)p * N * D;
+    const float* a = f1 + slot_of(s1, p) * N * D;
+    const float* b = f2 + slot_of(s2, p) * N * D;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int lr = threadIdx.x >> 2, lk = (threadIdx.x & 3) * 4;
     float acc[4][4] = {};
@@ -261,8 +270,9 @@ __global__ void corr_lookup_kernel(const CorrLookupParams p) {
 }
 
 // avg_pool2d(2, stride 2), floor, of an NHWC feature map [P][h][w][C] -> [P][h / 2][w / 2][C]: the next level of fmap2 for the on-the-fly lookup
-// (AlternateCorrBlock.__init__, corr.py:63-73).  Four channels per thread; the four pixels are added in corr_pool_kernel's order.
-__global__ void fmap_pool_kernel(const float* in, int64_t P, int h, int w, int C, float* out, int oh, int ow) {
+// (AlternateCorrBlock.__init__, corr.py:63-73).  Four channels per thread; the four pixels are added in corr_pool_kernel's order.  Output map j pools
+// the input map at slot `is` of j.
+__global__ void fmap_pool_kernel(const float* in, int64_t P, int h, int w, int C, float* out, int oh, int ow, SlotMap is) {
     const int c4n = C >> 2;
     const int64_t total = P * oh * ow * c4n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -270,7 +280,7 @@ __global__ void fmap_pool_kernel(const float* in, int64_t P, int h, int w, int C
         const int c4 = (int)(i - pix * c4n);
         const int64_t pr = pix / ((int64_t)oh * ow);
         const int q = (int)(pix - pr * oh * ow), y = q / ow, x = q - y * ow;
-        const float4* s = reinterpret_cast<const float4*>(in + ((pr * h + 2 * y) * w + 2 * x) * C) + c4;
+        const float4* s = reinterpret_cast<const float4*>(in + ((slot_of(is, pr) * h + 2 * y) * w + 2 * x) * C) + c4;
         const float4 a = s[0], b = s[c4n], c = s[(int64_t)w * c4n], d = s[(int64_t)w * c4n + c4n];
         float4 acc = a;
         acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w;
@@ -332,11 +342,19 @@ __global__ void __launch_bounds__(256) corr_lookup_on_the_fly_kernel(const CorrO
             base[l][0] = xbase;
             base[l][1] = ybase;
         }
-        const float4* f1 = reinterpret_cast<const float4*>(p.fmap1 + m * 256) + sub;
+        // the two maps of this row's pair: one per pair in pair order, or (p.ppg > 0) where the strides of the forward's shared frames put them
+        const int64_t pr = m / p.hw8;
+        int64_t m1 = m, slot2 = pr;
+        if (p.ppg > 0) {
+            const int64_t g = pr / p.ppg, t = pr - g * p.ppg;
+            m1 = (g * p.s1b + t * p.s1t - pr) * p.hw8 + m;
+            slot2 = g * p.s2b[l] + t * p.s2t[l];
+        }
+        const float4* f1 = reinterpret_cast<const float4*>(p.fmap1 + m1 * 256) + sub;
         float4 q[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) q[i] = f1[8 * i];
-        const float* lvl = p.fmap2[l] + (m / p.hw8) * H * W * 256;
+        const float* lvl = p.fmap2[l] + slot2 * H * W * 256;
         const int n = nx * ny;
         int qy = grp / max(nx, 1), qx = grp - qy * nx;  // position qi = s * 8 + grp of the nx x ny rectangle, kept as (qx, qy)
         for (int s = 0; s * 8 < n; ++s) {
@@ -646,7 +664,10 @@ int launch_residual_join(const ConvSrc& X, const ConvSrc& Y, int n_img, int HW, 
     return launch_flat(residual_join_kernel, total, s, X, Y, total, HW, out);
 }
 
-int launch_cnet_split(const float* cn, int64_t M, float* h, float* x, hipStream_t s) { return launch_flat(cnet_split_kernel, M * 128, s, cn, M, h, x); }
+int launch_cnet_split(const float* cn, int64_t M, float* h, float* x, hipStream_t s, int64_t hw8, SlotMap cs) {
+    CWM_REQUIRE(hw8 > 0 && M % hw8 == 0 && cs.ppg > 0, "cnet_split: %lld rows are not whole maps of %lld", (long long)M, (long long)hw8);
+    return launch_flat(cnet_split_kernel, M * 128, s, cn, M, h, x, hw8, cs);
+}
 
 int launch_coords_init(float* coords, int64_t M, int h8, int w8, hipStream_t s) { return launch_flat(coords_init_kernel, M, s, coords, M, h8, w8); }
 
@@ -655,9 +676,9 @@ int launch_coords_init_flow(float* coords, int P, int ppg, int h8, int w8, const
     return launch_flat(coords_init_flow_kernel, M, s, coords, M, h8, w8, ppg, init, sb, st, sc);
 }
 
-int launch_corr(const float* f1, const float* f2, int P, int N, int D, float* corr, hipStream_t s) {
-    CWM_REQUIRE(D % 16 == 0, "corr: feature width %d must be a multiple of 16", D);
-    hipLaunchKernelGGL(corr_kernel, dim3((N + 63) / 64, (N + 63) / 64, P), dim3(256), 0, s, f1, f2, N, D, 1.f / sqrtf((float)D), corr);
+int launch_corr(const float* f1, const float* f2, int P, int N, int D, float* corr, hipStream_t s, SlotMap s1, SlotMap s2) {
+    CWM_REQUIRE(D % 16 == 0 && s1.ppg > 0 && s2.ppg > 0, "corr: feature width %d must be a multiple of 16", D);
+    hipLaunchKernelGGL(corr_kernel, dim3((N + 63) / 64, (N + 63) / 64, P), dim3(256), 0, s, f1, f2, N, D, 1.f / sqrtf((float)D), corr, s1, s2);
     CWM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -671,16 +692,16 @@ int launch_corr_lookup(const CorrLookupParams& p, int planes, hipStream_t s) {
     return launch_flat(planes == 2 ? corr_lookup_kernel<2> : corr_lookup_kernel<1>, p.M * p.Kpad, s, p);
 }
 
-int launch_fmap_pool(const float* in, int64_t P, int h, int w, int C, float* out, hipStream_t s) {
-    CWM_REQUIRE(C % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0, "fmap_pool: %d channels in 16-byte aligned maps are required", C);
+int launch_fmap_pool(const float* in, int64_t P, int h, int w, int C, float* out, hipStream_t s, SlotMap is) {
+    CWM_REQUIRE(C % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0 && is.ppg > 0, "fmap_pool: %d channels in 16-byte aligned maps are required", C);
     const int oh = h / 2, ow = w / 2;
-    return launch_flat(fmap_pool_kernel, P * oh * ow * (C / 4), s, in, P, h, w, C, out, oh, ow);
+    return launch_flat(fmap_pool_kernel, P * oh * ow * (C / 4), s, in, P, h, w, C, out, oh, ow, is);
 }
 
 int launch_corr_lookup_on_the_fly(const CorrOnTheFlyParams& p, int planes, hipStream_t s) {
     bool aligned = ((uintptr_t)p.fmap1 & 15) == 0 && ((uintptr_t)p.coords & 7) == 0;
     for (const float* f : p.fmap2) aligned = aligned && ((uintptr_t)f & 15) == 0;
-    CWM_REQUIRE(aligned && p.M > 0 && p.hw8 > 0 && p.M % p.hw8 == 0, "corr_lookup_on_the_fly: 16-byte aligned feature maps and whole pairs are required");
+    CWM_REQUIRE(aligned && p.M > 0 && p.hw8 > 0 && p.M % p.hw8 == 0 && p.ppg >= 0, "corr_lookup_on_the_fly: 16-byte aligned feature maps and whole pairs are required");
     // one workgroup of four waves (one per level) per row
     hipLaunchKernelGGL(planes == 2 ? corr_lookup_on_the_fly_kernel<2> : corr_lookup_on_the_fly_kernel<1>, dim3((unsigned)std::min<int64_t>(p.M, 1 << 20)),
                        dim3(4 * kWave), 0, s, p);

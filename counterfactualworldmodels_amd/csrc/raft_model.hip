@@ -13,7 +13,9 @@
 // packing of the weight parts, GEMM params) is stated once in raft_kernels.hip, for this file and for dev.hip's cwm_dev_raft_conv; the correlation pyramid
 // once here (build_pyramid), for the forward and the stand-alone lookup.  A handle may instead compute the correlations at lookup time
 // (cwm_raft_set_corr, AlternateCorrBlock of raft/corr.py:63-91): build_fmap_levels pools fmap2 three times in place of the pyramid, and the lookup of
-// every iteration is corr_lookup_on_the_fly_kernel; nothing else of the forward changes.
+// every iteration is corr_lookup_on_the_fly_kernel; nothing else of the forward changes.  A handle may also run the encoders once per distinct frame of a
+// call (cwm_raft_set_share_frames): raft_frame_plan reads what repeats off the two image sources' strides, the encoders run over the plan's frames, and the
+// consumers of their maps (correlation, fmap2's poolings, the on-the-fly lookup, the context split) find each pair's maps by slot (kernels.h FramePlan, SlotMap).
 #include <stddef.h>
 
 #include "engine.h"
@@ -71,8 +73,10 @@ struct cwm_raft_model {
     Encoder fnet, cnet;
     RaftConv convc1, convc2, convf1, convf2, conv, zr[2], q[2], fh1, fh2, mask0, mask2, out0;
     int corr = CWM_RAFT_CORR_ALL_PAIRS;  // cwm_raft_set_corr
-    // workspace (cached by shape and by `corr`)
-    int ws_P = 0, ws_H = 0, ws_W = 0, ws_corr = CWM_RAFT_CORR_ALL_PAIRS;
+    int share = 0;                       // cwm_raft_set_share_frames
+    int last_fnet = 0, last_cnet = 0;    // cwm_raft_encoder_images: what the last forward's plan ran through each encoder
+    // workspace (cached by shape, by `corr` and by the frame counts of the plan: pairs, fnet frames, cnet frames, distinct image2 frames)
+    int ws_P = 0, ws_nf = 0, ws_nc = 0, ws_n2 = 0, ws_H = 0, ws_W = 0, ws_corr = CWM_RAFT_CORR_ALL_PAIRS;
     float *enc_act[4] = {nullptr, nullptr, nullptr, nullptr}, *enc_stats[4] = {nullptr, nullptr, nullptr, nullptr};
     bf16* enc_A = nullptr;
     double* enc_norm_work = nullptr;
@@ -170,24 +174,25 @@ int prepare(cwm_raft_model* m) {
 // side of pyramid level l (avg_pool2d(2, stride 2), floor, l times)
 int level_sides(int s, int l) { return s >> l; }
 
-int ensure_workspace(cwm_raft_model* m, int P, int H, int W) {
-    if (m->ws_P >= P && m->ws_H == H && m->ws_W == W && m->ws_corr == m->corr) return 0;
+// P pairs whose encoders run on nf (fnet) and nc (cnet) frames, n2 of them distinct second images: 2 P, P and P unless the forward shares frames
+int ensure_workspace(cwm_raft_model* m, int P, int nf, int nc, int n2, int H, int W) {
+    if (m->ws_P >= P && m->ws_nf >= nf && m->ws_nc >= nc && m->ws_n2 >= n2 && m->ws_H == H && m->ws_W == W && m->ws_corr == m->corr) return 0;
     Engine& E = m->eng;
     if (int rc = E.free_workspace()) return rc;
     m->ws_P = 0;
     const int64_t hw2 = (int64_t)(H / 2) * (W / 2), hw8 = (int64_t)(H / 8) * (W / 8), M = P * hw8;
-    const int64_t n = std::min(2 * P, kMaxEncImages);
+    const int64_t n = std::min(std::max(nf, nc), kMaxEncImages);
     int rc = 0;
     for (int i = 0; i < 4 && !rc; ++i) rc = E.ws(&m->enc_act[i], (size_t)(n * hw2 * 64));
     for (int i = 0; i < 4 && !rc; ++i) rc = E.ws(&m->enc_stats[i], (size_t)(n * 128 * 2));
     if (rc || (rc = E.ws(&m->enc_A, (size_t)(n * hw2 * 576 * kMaxPlanes))) || (rc = E.ws(&m->enc_norm_work, (size_t)(2 * n * kInstNormMaxChunks * 128))))
         return rc;
-    if ((rc = E.ws(&m->fmap, (size_t)(2 * M * kFeat))) || (rc = E.ws(&m->cn, (size_t)(M * 256)))) return rc;
+    if ((rc = E.ws(&m->fmap, (size_t)(nf * hw8 * kFeat))) || (rc = E.ws(&m->cn, (size_t)(nc * hw8 * 256)))) return rc;
     for (int l = 0; l < 4; ++l) m->pyr[l] = m->f2lvl[l] = nullptr;
     for (int l = 0; l < 4 && !rc; ++l) {
         const int64_t hw = (int64_t)level_sides(H / 8, l) * level_sides(W / 8, l);
         if (m->corr == CWM_RAFT_CORR_ALL_PAIRS) rc = E.ws(&m->pyr[l], (size_t)(M * hw));
-        else if (l > 0) rc = E.ws(&m->f2lvl[l], (size_t)(P * hw * kFeat));
+        else if (l > 0) rc = E.ws(&m->f2lvl[l], (size_t)(n2 * hw * kFeat));
     }
     if (rc || (rc = E.ws(&m->corrA, (size_t)(M * kLookupKpad * kMaxPlanes))) || (rc = E.ws(&m->updA, (size_t)(M * 2304 * kMaxPlanes)))) return rc;
     if ((rc = E.ws(&m->c1, (size_t)(M * 256))) || (rc = E.ws(&m->cf, (size_t)(M * 256))) || (rc = E.ws(&m->f1, (size_t)(M * 128))) ||
@@ -196,6 +201,9 @@ int ensure_workspace(cwm_raft_model* m, int P, int H, int W) {
         (rc = E.ws(&m->coords, (size_t)(M * 2))) || (rc = E.ws(&m->mask, (size_t)(M * 576))))
         return rc;
     m->ws_P = P;
+    m->ws_nf = nf;
+    m->ws_nc = nc;
+    m->ws_n2 = n2;
     m->ws_H = H;
     m->ws_W = W;
     m->ws_corr = m->corr;
@@ -224,8 +232,11 @@ Im2colParams im2col_of(const ConvSrc& a, const ConvSrc* b = nullptr) {
     return ip;
 }
 
-// BasicEncoder.forward (extractor.py:160-192) on images [img0, img0 + n) of `image`; output [n][H/8 * W/8][out width] at `out`
-int run_encoder(cwm_raft_model* m, const Encoder& e, const ImageSrc& image, int img0, int n, int H, int W, float* out, int planes, hipStream_t s) {
+// BasicEncoder.forward (extractor.py:160-192) on images [img0, img0 + n) of `image`; output [n][H/8 * W/8][out width] at `out`.  `runs` (a forward that
+// shares frames): the images are frames [img0, img0 + n) of the `nruns` runs laid end to end instead; conv1's operand is then written run by run (one
+// im2col launch per run the pass touches, at that run's rows of A) and multiplied once.
+int run_encoder(cwm_raft_model* m, const Encoder& e, const ImageSrc& image, int img0, int n, int H, int W, float* out, int planes, hipStream_t s,
+                const FrameRun* runs = nullptr, int nruns = 0) {
     int rc;
     float** act = m->enc_act;
     float** st = m->enc_stats;
@@ -234,7 +245,21 @@ int run_encoder(cwm_raft_model* m, const Encoder& e, const ImageSrc& image, int 
     Im2colParams ip = im2col_of(src_of(nullptr, 3));
     ip.image = image;
     ip.img0 = img0;
-    if ((rc = run_conv(m, e.conv1, ip, n, H, W, m->enc_A, act[0], 64, planes, s))) return rc;
+    if (runs) {
+        int first = 0;  // the first frame of run r
+        for (int r = 0; r < nruns; first += runs[r].n, ++r) {
+            const int lo = std::max(img0, first), hi = std::min(img0 + n, first + runs[r].n);
+            if (lo >= hi) continue;
+            Im2colParams iq = ip;
+            iq.image = ImageSrc{{runs[r].base, runs[r].base}, {runs[r].sb, runs[r].sb}, {runs[r].st, runs[r].st}, {runs[r].sc, runs[r].sc}, runs[r].n, runs[r].nt,
+                                image.scale};
+            iq.img0 = lo - first;
+            set_conv_geometry(iq, hi - lo, H, W, e.conv1.kh, e.conv1.kw, e.conv1.stride, e.conv1.pad_h, e.conv1.pad_w, e.conv1.L.Kpad);
+            iq.A = m->enc_A + (size_t)(lo - img0) * iq.OH * iq.OW * e.conv1.L.Kpad * planes;
+            if ((rc = launch_im2col(iq, planes, s))) return rc;
+        }
+    }
+    if ((rc = run_conv(m, e.conv1, ip, n, H, W, m->enc_A, act[0], 64, planes, s, runs != nullptr))) return rc;
     int h = H / 2, w = W / 2, C = 64;
     if (e.instance && (rc = launch_instnorm_stats(act[0], n, h * w, C, eps, st[0], m->enc_norm_work, s))) return rc;
     ConvSrc a = src_of(act[0], C, e.instance ? st[0] : nullptr, 1);
@@ -264,15 +289,17 @@ int run_encoder(cwm_raft_model* m, const Encoder& e, const ImageSrc& image, int 
 }
 
 // CorrBlock.__init__ and the params of its lookups: the all-pairs correlation of two feature maps [P][h8 * w8][256] into pyr[0], its three poolings into
-// pyr[1 .. 3] (level l: [M][h8 >> l][w8 >> l]), and `lp` over them at `coords`; the destination (A, or out / out_ld) is the caller's
-int build_pyramid(const float* fmap1, const float* fmap2, const float* coords, int P, int h8, int w8, float* const* pyr, CorrLookupParams& lp, hipStream_t s) {
+// pyr[1 .. 3] (level l: [M][h8 >> l][w8 >> l]), and `lp` over them at `coords`; the destination (A, or out / out_ld) is the caller's.  s1 / s2: where
+// pair p's maps lie in fmap1 / fmap2 (kPairSlots: one per pair); the pyramid is per pair either way.
+int build_pyramid(const float* fmap1, const float* fmap2, const float* coords, int P, int h8, int w8, float* const* pyr, CorrLookupParams& lp, hipStream_t s,
+                  SlotMap s1 = kPairSlots, SlotMap s2 = kPairSlots) {
     const int64_t M = (int64_t)P * h8 * w8;
     lp = CorrLookupParams{};
     lp.levels = 4;
     lp.coords = coords;
     lp.M = M;
     lp.Kpad = kLookupKpad;
-    if (int rc = launch_corr(fmap1, fmap2, P, h8 * w8, kFeat, pyr[0], s)) return rc;
+    if (int rc = launch_corr(fmap1, fmap2, P, h8 * w8, kFeat, pyr[0], s, s1, s2)) return rc;
     for (int l = 0; l < 4; ++l) {
         lp.pyr[l] = pyr[l];
         lp.h[l] = level_sides(h8, l);
@@ -284,10 +311,20 @@ int build_pyramid(const float* fmap1, const float* fmap2, const float* coords, i
 }
 
 // AlternateCorrBlock.__init__ (corr.py:63-73) and the params of its lookups: fmap2 [P][h8][w8][256] pooled into lvl[1 .. 3] (level l: [P][h8 >> l][w8 >> l][256];
-// level 0 is fmap2 itself), and `lp` over them and fmap1 at `coords`; the destination is the caller's
+// level 0 is fmap2 itself), and `lp` over them and fmap1 at `coords`; the destination is the caller's.  `fp` (a forward that shares frames): fmap1 and
+// fmap2 are the plan's, every distinct second image is pooled once (fp->n2 maps per level) and the lookup finds each pair's maps by the plan's slots.
 int build_fmap_levels(const float* fmap1, const float* fmap2, const float* coords, int P, int h8, int w8, float* const* lvl, CorrOnTheFlyParams& lp,
-                      hipStream_t s) {
+                      hipStream_t s, const FramePlan* fp = nullptr) {
     lp = CorrOnTheFlyParams{};
+    if (fp) {
+        lp.ppg = fp->s1.ppg;
+        lp.s1b = fp->s1.sb;
+        lp.s1t = fp->s1.st;
+        for (int l = 0; l < 4; ++l) {
+            lp.s2b[l] = l ? fp->s2p.sb : fp->s2.sb;
+            lp.s2t[l] = l ? fp->s2p.st : fp->s2.st;
+        }
+    }
     lp.fmap1 = fmap1;
     lp.coords = coords;
     lp.hw8 = (int64_t)h8 * w8;
@@ -298,7 +335,8 @@ int build_fmap_levels(const float* fmap1, const float* fmap2, const float* coord
         lp.h[l] = level_sides(h8, l);
         lp.w[l] = level_sides(w8, l);
         if (l > 0)
-            if (int rc = launch_fmap_pool(lp.fmap2[l - 1], P, lp.h[l - 1], lp.w[l - 1], kFeat, lvl[l], s)) return rc;
+            if (int rc = launch_fmap_pool(lp.fmap2[l - 1], fp ? fp->n2 : P, lp.h[l - 1], lp.w[l - 1], kFeat, lvl[l], s, fp && l == 1 ? fp->pool : kPairSlots))
+                return rc;
     }
     return 0;
 }
@@ -320,29 +358,39 @@ int forward(cwm_raft_model* m, const cwm_raft_forward_args& a, const ForwardExtr
     const int P = a.batch * ppg, H = a.height, W = a.width, h8 = H / 8, w8 = W / 8;
     const int64_t hw8 = (int64_t)h8 * w8, M = P * hw8;
     int rc;
-    if ((rc = prepare(m)) || (rc = ensure_workspace(m, P, H, W))) return rc;
+    // the frames the encoders run on: every pair's image1 and image2, or (cwm_raft_set_share_frames) each distinct frame of a recognised pattern once
+    const float* const imgs[2] = {a.image1_dev, a.image2_dev};
+    const int64_t isb[2] = {a.image1_stride_b, a.image2_stride_b}, ist[2] = {a.image1_stride_t, a.image2_stride_t},
+                  isc[2] = {a.image1_stride_c, a.image2_stride_c};
+    const FramePlan fp = raft_frame_plan(a.batch, ppg, imgs, isb, ist, isc, m->share != 0);
+    if ((rc = prepare(m)) || (rc = ensure_workspace(m, P, fp.n_fnet, fp.n_cnet, fp.n2, H, W))) return rc;
+    m->last_fnet = fp.n_fnet;
+    m->last_cnet = fp.n_cnet;
     const ImageSrc img = {{a.image1_dev, a.image2_dev},           {a.image1_stride_b, a.image2_stride_b}, {a.image1_stride_t, a.image2_stride_t},
                           {a.image1_stride_c, a.image2_stride_c}, P, ppg, a.input_scale};
-    // feature network over image1 and image2 of every pair (instance norm is per image: any grouping gives the same result)
-    for (int i0 = 0; i0 < 2 * P; i0 += kMaxEncImages) {
-        const int n = std::min(kMaxEncImages, 2 * P - i0);
-        if ((rc = run_encoder(m, m->fnet, img, i0, n, H, W, m->fmap + (int64_t)i0 * hw8 * kFeat, planes, s))) return rc;
+    // feature network over image1 and image2 of every pair, or over the plan's frames (instance norm is per image: any grouping gives the same result)
+    for (int i0 = 0; i0 < fp.n_fnet; i0 += kMaxEncImages) {
+        const int n = std::min(kMaxEncImages, fp.n_fnet - i0);
+        if ((rc = run_encoder(m, m->fnet, img, i0, n, H, W, m->fmap + (int64_t)i0 * hw8 * kFeat, planes, s, fp.shared ? fp.frun : nullptr, 2))) return rc;
     }
-    // context network over image1
-    for (int i0 = 0; i0 < P; i0 += kMaxEncImages) {
-        const int n = std::min(kMaxEncImages, P - i0);
-        if ((rc = run_encoder(m, m->cnet, img, i0, n, H, W, m->cn + (int64_t)i0 * hw8 * 256, planes, s))) return rc;
+    // context network over image1, or over the distinct first images
+    for (int i0 = 0; i0 < fp.n_cnet; i0 += kMaxEncImages) {
+        const int n = std::min(kMaxEncImages, fp.n_cnet - i0);
+        if ((rc = run_encoder(m, m->cnet, img, i0, n, H, W, m->cn + (int64_t)i0 * hw8 * 256, planes, s, fp.shared ? &fp.crun : nullptr, 1))) return rc;
     }
-    if ((rc = launch_cnet_split(m->cn, M, m->h, m->x, s))) return rc;
+    // the GRU state and input are per pair; pairs of one first frame read one context map
+    if ((rc = launch_cnet_split(m->cn, M, m->h, m->x, s, hw8, fp.shared ? fp.sc : kPairSlots))) return rc;
+    const float* fmap1 = m->fmap + fp.base1 * hw8 * kFeat;
+    const float* fmap2 = m->fmap + fp.base2 * hw8 * kFeat;
     // correlation pyramid, or the levels of fmap2 from which the lookup computes its taps (m->ws_corr: what the workspace was planned for)
     const bool on_the_fly = m->ws_corr == CWM_RAFT_CORR_ON_THE_FLY;
     CorrLookupParams lp = {};
     CorrOnTheFlyParams lq = {};
     if (on_the_fly) {
-        if ((rc = build_fmap_levels(m->fmap, m->fmap + M * kFeat, m->coords, P, h8, w8, m->f2lvl, lq, s))) return rc;
+        if ((rc = build_fmap_levels(fmap1, fmap2, m->coords, P, h8, w8, m->f2lvl, lq, s, fp.shared ? &fp : nullptr))) return rc;
         lq.A = m->corrA;
     } else {
-        if ((rc = build_pyramid(m->fmap, m->fmap + M * kFeat, m->coords, P, h8, w8, m->pyr, lp, s))) return rc;
+        if ((rc = build_pyramid(fmap1, fmap2, m->coords, P, h8, w8, m->pyr, lp, s, fp.shared ? fp.s1 : kPairSlots, fp.shared ? fp.s2 : kPairSlots))) return rc;
         lp.A = m->corrA;
     }
     if (ex.init) {
@@ -539,6 +587,66 @@ extern "C" int cwm_raft_set_corr(cwm_raft_model* m, int corr) {
     return CWM_OK;
 }
 
+extern "C" int cwm_raft_set_share_frames(cwm_raft_model* m, int on) {
+    CWM_REQUIRE(m, "cwm_raft_set_share_frames: null argument");
+    CWM_REQUIRE(on == 0 || on == 1, "cwm_raft_set_share_frames: on = %d must be 0 or 1", on);
+    m->share = on;  // the next forward plans its frames, and its workspace from their counts
+    return CWM_OK;
+}
+
+extern "C" int cwm_raft_encoder_images(cwm_raft_model* m, int* fnet_images, int* cnet_images) {
+    CWM_REQUIRE(m && fnet_images && cnet_images, "cwm_raft_encoder_images: null argument");
+    *fnet_images = m->last_fnet;
+    *cnet_images = m->last_cnet;
+    return CWM_OK;
+}
+
+FramePlan cwm::raft_frame_plan(int batch, int ppg, const float* const img[2], const int64_t sb[2], const int64_t st[2], const int64_t sc[2], bool share) {
+    const int P = batch * ppg;
+    for (int w = 0; w < 2; ++w) share = share && sb[w] >= 0 && st[w] >= 0 && sc[w] >= 0;
+    // a source's own frames: P1 / P2 fold the axis along which its stride is 0
+    int nb[2], nt[2];
+    SlotMap own[2];
+    for (int w = 0; w < 2; ++w) {
+        nb[w] = share && sb[w] == 0 && batch > 1 ? 1 : batch;
+        nt[w] = share && st[w] == 0 && ppg > 1 ? 1 : ppg;
+        own[w] = SlotMap{ppg, nb[w] > 1 ? nt[w] : 0, nt[w] > 1 ? 1 : 0};
+    }
+    // P3: image2 = image1 + k * stride_t under identical strides
+    int k = 2;  // none
+    if (share && sb[0] == sb[1] && st[0] == st[1] && sc[0] == sc[1]) {
+        const ptrdiff_t d = img[1] - img[0];
+        if (d == 0) k = 0;
+        else if (ppg > 1 && st[0] > 0 && d == st[0]) k = 1;  // (a single pair per row has no interior frame to share)
+        else if (ppg > 1 && st[0] > 0 && d == -st[0]) k = -1;
+    }
+    FramePlan fp = {};
+    for (int w = 0; w < 2; ++w) fp.frun[w] = FrameRun{img[w], sb[w], st[w], sc[w], nb[w] * nt[w], nt[w]};
+    fp.crun = fp.frun[0];  // cnet: image1's own frames
+    fp.n_cnet = fp.crun.n;
+    fp.sc = own[0];
+    fp.n2 = nb[1] * nt[1];
+    fp.s2p = own[1];
+    if (k == 0) {  // one run serves both images
+        fp.frun[1].n = 0;
+        fp.s1 = fp.s2 = own[0];
+    } else if (k == 1 || k == -1) {  // one run of ppg + 1 frames per row, from whichever image comes first in memory
+        const int first = k == 1 ? 0 : 1;
+        fp.frun[0] = FrameRun{img[first], sb[0], st[0], sc[0], nb[0] * (ppg + 1), ppg + 1};
+        fp.frun[1].n = 0;
+        fp.s1 = fp.s2 = SlotMap{ppg, nb[0] > 1 ? ppg + 1 : 0, 1};
+        (first == 0 ? fp.base2 : fp.base1) = 1;
+    } else {  // image1's frames, then image2's
+        fp.s1 = own[0];
+        fp.s2 = own[1];
+        fp.base2 = fp.frun[0].n;
+    }
+    fp.n_fnet = fp.frun[0].n + fp.frun[1].n;
+    fp.pool = SlotMap{nt[1], fp.s2.sb, fp.s2.st};
+    fp.shared = k != 2 || fp.n_fnet != 2 * P || fp.n_cnet != P;
+    return fp;
+}
+
 extern "C" int cwm_raft_workspace_bytes(cwm_raft_model* m, uint64_t* out) {
     CWM_REQUIRE(m && out, "cwm_raft_workspace_bytes: null argument");
     *out = m->eng.ws_bytes;
@@ -547,7 +655,7 @@ extern "C" int cwm_raft_workspace_bytes(cwm_raft_model* m, uint64_t* out) {
 
 // ---- stand-alone kernels (kernel tests) -------------------------------------------------------------------------------
 int cwm::raft_corr_lookup_run(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev, bf16* A,
-                              int planes, hipStream_t s) {
+                              int planes, hipStream_t s, SlotMap s1, SlotMap s2) {
     const int64_t M = (int64_t)P * h8 * w8;
     float* pyr[4] = {nullptr, nullptr, nullptr, nullptr};
     int rc = 0;
@@ -557,7 +665,7 @@ int cwm::raft_corr_lookup_run(const float* fmap1_dev, const float* fmap2_dev, co
             rc = CWM_ERR_HIP;
         }
     CorrLookupParams lp = {};
-    if (!rc) rc = build_pyramid(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, pyr, lp, s);
+    if (!rc) rc = build_pyramid(fmap1_dev, fmap2_dev, coords_dev, P, h8, w8, pyr, lp, s, s1, s2);
     if (out_dev) {
         lp.out = out_dev;
         lp.out_ld = 324;

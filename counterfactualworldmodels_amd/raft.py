@@ -27,6 +27,12 @@ the frame area; `model.workspace_bytes()` tells what a forwar
 
     padder = InputPadder(x.shape)                # raft/utils.py:9-26
     flows = padder.unpad(flow_model(*padder.pad(x)))
+
+`load_raft_model(path, share_frames=True)` or `model.set_share_frames(True)` runs the two encoders once per distinct frame of a call instead of once
+per pair: the interior frames of a movie, a single repeated frame, and the first frame that S counterfactual samples share,
+
+    flows = flow_model.flow_pairs(x0.expand(B, S, 3, H, W), predicted)   # [B,S,2,H,W]; fnet on B * (S + 1) images, cnet on B
+    flow_model.last_encoder_images                                       # (fnet images, cnet images) of the last forward
 """
 from __future__ import annotations
 
@@ -120,7 +126,7 @@ class BasicUpdateBlock(_NoForward):
 
 def _args(**kw) -> argparse.Namespace:
     a = argparse.Namespace(corr_levels=RAFT_CORR_LEVELS, corr_radius=RAFT_CORR_RADIUS, output_dim=None, iters=None, dropout=0.0, mixed_precision=False,
-                           small=False, gpus=[0], multiframe=True, scale_inputs=True, alternate_corr=False, corr="all_pairs")
+                           small=False, gpus=[0], multiframe=True, scale_inputs=True, alternate_corr=False, corr="all_pairs", share_frames=False)
     for k, v in kw.items():
         setattr(a, k, v)
     return a
@@ -209,7 +215,13 @@ class RAFT(LibraryModule):
     the fast mode on (the reference's autocast does, raft_model.py:219): they are upcast to fp32 and run in the model's mode.
     Correlation: `self.corr` is "all_pairs" (the default: the volume of `CorrBlock`, built once per forward) or "on_the_fly" (the taps of every lookup
     computed from the two feature maps, `AlternateCorrBlock` of raft/corr.py:63-91: no volume, so the workspace grows with the frame area and not with
-    its square).  It comes from `args.corr` and changes with `set_corr`; both give the same flow up to fp32 summation order, in either mode."""
+    its square).  It comes from `args.corr` and changes with `set_corr`; both give the same flow up to fp32 summation order, in either mode.
+    Shared frames: with `self.share_frames` (False by default; `args.share_frames`, `set_share_frames`) a forward runs fnet once per distinct frame and
+    cnet once per distinct first image of the call.  What repeats is read off the strides of the two image views the call hands to the library: a view
+    expanded over the pairs or over the batch (stride 0), a movie's `x[:, :-1]` / `x[:, 1:]` (T frames per row through fnet in place of 2 (T - 1)), a
+    single repeated frame.  The multi-frame call needs nothing more than the flag; `flow_pairs` takes the two views directly.  The result agrees with
+    the unshared one as one pair does between batches of different sizes (fp32 summation order), not bit for bit.  `warm_start=True` runs pair by pair
+    and shares nothing between its calls.  `last_encoder_images` tells what the last forward ran."""
 
     def __init__(self, args: Optional[argparse.Namespace] = None):
         super().__init__()
@@ -224,6 +236,7 @@ class RAFT(LibraryModule):
                                       "the library's own on-the-fly correlation is chosen with corr=\"on_the_fly\"")
         self.corr = getattr(self.args, "corr", "all_pairs")
         _lib.raft_corr_id(self.corr)
+        self.share_frames = bool(getattr(self.args, "share_frames", False))
         self.multiframe = getattr(self.args, "multiframe", True)
         self.scale_inputs = getattr(self.args, "scale_inputs", True)
         self.hidden_dim = RAFT_HIDDEN
@@ -263,6 +276,20 @@ class RAFT(LibraryModule):
         self.corr = corr
         return self
 
+    def set_share_frames(self, on: bool = True):
+        """Run the encoders once per distinct frame (True) or once per pair (False, the default) in the forwards that follow."""
+        self.share_frames = bool(on)
+        return self
+
+    @property
+    def last_encoder_images(self):
+        """(fnet images, cnet images) of the last forward; (0, 0) before the first."""
+        if self._handle is None:
+            return (0, 0)
+        f, c = C.c_int(), C.c_int()
+        self._check(self._fn["encoder_images"](self._handle, C.byref(f), C.byref(c)))
+        return (int(f.value), int(c.value))
+
     def workspace_bytes(self) -> int:
         """Bytes of activation workspace the library handle holds: what the last forward's shape and `corr` asked for (0 before the first forward)."""
         if self._handle is None:
@@ -278,17 +305,18 @@ class RAFT(LibraryModule):
 
     # ---- C-ABI plumbing (the handle and sync_weights live in _handle.LibraryModule; the library folds the batch norms and packs the
     # convolutions at the next forward.  cwm_raft_* has no lanes or kernel timing: the arithmetic mode travels with each call, and the one per-handle
-    # option, the form of the correlation, is set before each forward) -------
-    _ABI = {role: "cwm_raft_" + role for role in ("destroy", "load_weight", "forward", "forward_ex", "set_corr", "workspace_bytes")}
+    # options, the form of the correlation and the sharing of frames, are set before each forward) -------
+    _ABI = {role: "cwm_raft_" + role for role in ("destroy", "load_weight", "forward", "forward_ex", "set_corr", "workspace_bytes", "set_share_frames",
+                                                  "encoder_images")}
 
     def _create(self, lib, h):
         return lib.cwm_raft_create(C.byref(h))
 
-    def _run(self, x1, x2, B, pairs, H, W, scale, iters, out, out_strides, flow_low=None, flow_init=None, per_iteration=None):
+    def _run(self, x1, x2, B, pairs, H, W, scale, iters, out, out_strides, flow_low=None, flow_init=None, per_iteration=None, share=None):
         """One library forward.  `out` = (pointer,) of the last iteration's output, addressed with `out_strides` (b, t, c), or None.  Without
         `flow_init` and `per_iteration` the call is `cwm_raft_forward`; with either, `cwm_raft_forward_ex`: `flow_init` [B or 1, 2, H/8, W/8] fp32
         goes to every pair, `per_iteration` = (pointer, stride between iterations) receives every iteration's output, addressed inside an
-        iteration's block with `out_strides`."""
+        iteration's block with `out_strides`.  `share`: the call's sharing of frames (None: the model's)."""
         dev = x1.device
         self.sync_weights(dev)
         extended = flow_init is not None or per_iteration is not None
@@ -319,6 +347,7 @@ class RAFT(LibraryModule):
             else:
                 ex.head_iters_dev, ex.head_iters_stride_i = per_iteration
         self._check(self._fn["set_corr"](self._handle, _lib.raft_corr_id(self.corr)))
+        self._check(self._fn["set_share_frames"](self._handle, int(bool(self.share_frames if share is None else share))))
         with torch.cuda.device(dev):
             if extended:
                 self._check(self._fn["forward_ex"](self._handle, C.byref(ex)))
@@ -375,6 +404,31 @@ class RAFT(LibraryModule):
         return low, up
 
     @torch.no_grad()
+    def flow_pairs(self, first, second, iters=24, flow_init=None, backward=False, share=None):
+        """The flows of the pairs (first[b, s], second[b, s]): `first` and `second` [B,S,3,H,W] in the model's input range (in [0,1] with
+        scale_inputs=True) -> [B,S,C,H,W], C = 2 or `output_dim`.  `backward=True` computes the pairs (second[b, s], first[b, s]), in the same order.
+        Either argument may be an expanded view, with stride 0 over S or over B: with sharing on (`share`; None = the model's `share_frames`) such a
+        frame goes through the encoders once, e.g. `flow_pairs(x0.expand(-1, S, -1, -1, -1), predicted, share=True)` for S samples of one first frame.
+        With sharing off every pair is computed in full, as by the multi-frame call.
+        A tensor that is not fp32 must be converted BEFORE it is expanded: converting an expanded view materialises the copies, and the call is then
+        correct but shares nothing.  `flow_init` [B or 1, 2, H/8, W/8] starts every pair, as in the multi-frame call."""
+        if self.iters is not None:
+            iters = self.iters
+        if first.dim() != 5 or first.shape != second.shape or first.shape[2] != 3:
+            raise RuntimeError("flow_pairs expects two [B,S,3,H,W] tensors of one shape, got %s and %s" % (tuple(first.shape), tuple(second.shape)))
+        x1, x2 = self._frames(first), self._frames(second)
+        if x1.device != x2.device:
+            raise RuntimeError("flow_pairs: first is on %s, second on %s" % (x1.device, x2.device))
+        B, S, _, H, W = x1.shape
+        init = self._flow_init(flow_init, B, H, W, x1.device)
+        if backward:
+            x1, x2 = x2, x1
+        out = torch.empty(B, S, self.output_dim or 2, H, W, device=x1.device)
+        self._run(x1, x2, B, S, H, W, 255.0 if self.scale_inputs else 1.0, iters, (out.data_ptr(),), (out.stride(0), out.stride(1), out.stride(2)),
+                  flow_init=init, share=share)
+        return out
+
+    @torch.no_grad()
     def forward(self, *args, **kwargs):
         if not self.multiframe:
             return self._forward_two_images(*args, **kwargs)
@@ -426,15 +480,16 @@ class RAFT(LibraryModule):
         return out
 
 
-def load_raft_model(load_path=default_raft_ckpt, ignore_prefix=None, multiframe=True, scale_inputs=True, output_dim=None, **kwargs):
+def load_raft_model(load_path=default_raft_ckpt, ignore_prefix=None, multiframe=True, scale_inputs=True, output_dim=None, share_frames=False, **kwargs):
     """raft_model.py:55-101: builds RAFT-large and loads a checkpoint (`module.` and `ignore_prefix` stripped from the keys, strict=False);
-    with `output_dim=1` and no path, a freshly initialised keypoint model."""
+    with `output_dim=1` and no path, a freshly initialised keypoint model.  `share_frames=True`: the encoders once per distinct frame of a call
+    (`RAFT.set_share_frames`); the other keywords (`mixed_precision`, `corr`, ...) go to the model's `args`."""
     if ((load_path is None) or (not os.path.exists(load_path))) and (output_dim is None):
         print("%s is not a valid raft checkpoint" % load_path)
         raise ValueError("You must download RAFT checkpoints with cwm/models/raft/download_raft_checkpoints.sh\n"
                          + "Checkpoints will be downloaded to CounterfactualWorldModels/checkpoints/raft_checkpoints/")
     args = _args(**kwargs)
-    args.multiframe, args.scale_inputs, args.output_dim = multiframe, scale_inputs, output_dim
+    args.multiframe, args.scale_inputs, args.output_dim, args.share_frames = multiframe, scale_inputs, output_dim, bool(share_frames)
     model = RAFT(args)
     if load_path is None:
         print("created a new %s with %d parameters" % (type(model).__name__, sum([v.numel() for v in model.parameters()])))

@@ -54,9 +54,12 @@ class FlowGenerator(PredictorBasedGenerator):
     _DEFAULT_FILTER = object()  # (the reference's default argument is one filter instance shared by every generator; here each gets its own)
 
     def __init__(self, *args, flow_model=None, flow_model_load_path=None, raft_iters=None, flow_sample_filter=_DEFAULT_FILTER,
-                 flow_sample_filter_params=None, patch_sampling_func=RotatedTableEnergyMaskingGenerator, patch_sampling_kwargs=None, **kwargs):
+                 flow_sample_filter_params=None, patch_sampling_func=RotatedTableEnergyMaskingGenerator, patch_sampling_kwargs=None,
+                 share_static_frame=False, **kwargs):
         super().__init__(*args, **kwargs)
         self.flow_model = flow_model
+        # the S counterfactuals of a movie begin with the same frame 0: let the flow model encode it once (`_counterfactual_flows`)
+        self.share_static_frame = bool(share_static_frame)
         if flow_model is not None and flow_model_load_path is not None:
             self.load_predictor(flow_model_load_path, model=flow_model)
         self.raft_iters = raft_iters
@@ -140,6 +143,31 @@ class FlowGenerator(PredictorBasedGenerator):
         if iters is not None:
             self.set_raft_iters(iters)
         return self.flow_model(vid, backward=backward, **kwargs).to(vid)
+
+    def _counterfactual_flows(self, y_mocos, mask, frame, backward=False, raft_iters=None):
+        """The flows of the counterfactual videos y_mocos [(b s),T,C,H,W] predicted under `mask` [(b s),Nt] for the generator's input `self.x`.
+        With `share_static_frame`, when the flow model has `flow_pairs` (raft.RAFT), the movie has two frames, frame 1 was predicted and no token of
+        frame 0 is masked in any row -- only then is frame 0 of every video the input frame bit for bit -- the S videos of a movie go to the flow
+        model as the pairs (input frame 0, frame 1 of sample s) with frame 0 expanded over the samples, so that its features are computed once per
+        movie; the check of the masks is the call's one extra read-back, a single bool.  In every other case this is
+        `predict_flow(y_mocos)`, as without the flag."""
+        fm = self.flow_model
+        x = self.x
+        shared = (self.share_static_frame and fm is not None and hasattr(fm, "flow_pairs") and y_mocos.dim() == 5 and y_mocos.shape[1] == 2 and frame == 1
+                  and x is not None and x.dim() == 5 and y_mocos.shape[0] % x.shape[0] == 0 and tuple(x.shape[2:]) == tuple(y_mocos.shape[2:]))
+        if shared:
+            R = y_mocos.shape[0]
+            t = self.mask_shape[0]
+            shared = t == 2 and not bool(mask.reshape(R, t, -1)[:, 0].any())
+        if not shared:
+            return self.predict_flow(y_mocos, backward=backward, iters=raft_iters)
+        if raft_iters is not None:
+            self.set_raft_iters(raft_iters)
+        B, S = x.shape[0], y_mocos.shape[0] // x.shape[0]
+        x0 = x[:, :1].to(device=y_mocos.device, dtype=torch.float32)  # (converted before it is expanded: an expanded view must keep its stride 0)
+        second = y_mocos[:, 1].reshape(B, S, *y_mocos.shape[2:])
+        flows = fm.flow_pairs(x0.expand(-1, S, -1, -1, -1), second, backward=backward, share=True)
+        return flows.reshape(B * S, 1, *flows.shape[2:]).to(y_mocos)
 
     @staticmethod
     def batch_to_samples(flows, t=0, B=1):
@@ -266,9 +294,11 @@ class FlowGenerator(PredictorBasedGenerator):
         the shifts, passive patches revealed in place (segmentation.py:346-432)."""
         if max_shift_fraction is not None and shifts is None:
             self.max_shift_fraction = max_shift_fraction
-        y_mocos = self.predict_counterfactual_videos(x, active_patches, passive_patches, shifts, num_samples, sample_batch_size, fix_passive,
-                                                     frame, **kwargs)
-        return y_mocos, self.predict_flow(y_mocos, backward=backward, iters=raft_iters)
+        batch = self._counterfactual_batch(x, active_patches, passive_patches, shifts, num_samples, fix_passive, frame,
+                                           self._conditioning_kwargs(x, kwargs))
+        y_mocos = self._run_rect_batch(batch, rows_per_call=sample_batch_size)
+        self.reset_padding_masks()
+        return y_mocos, self._counterfactual_flows(y_mocos, batch.mask, frame, backward, raft_iters)
 
     # ---- multi-shift counterfactuals: K patch groups per prompt, each moved by its own pixel shift (perturbation.py:644-779) ----------
     def _multi_shift_table(self, shifts, K):
@@ -338,9 +368,10 @@ class FlowGenerator(PredictorBasedGenerator):
     def predict_multi_shift_counterfactual_videos_and_flows(self, x, active_patches, shifts=None, passive_patches=None, num_samples=8,
                                                             sample_batch_size=8, fix_passive=True, frame=1, raft_iters=None, backward=False, **kwargs):
         """(y_mocos [B*S,T,C,H,W], flow_mocos [B*S,T-1,2,H,W]): `predict_multi_shift_counterfactual_videos`, then the flow model."""
-        y_mocos = self.predict_multi_shift_counterfactual_videos(x, active_patches, shifts, passive_patches, num_samples, sample_batch_size, fix_passive,
-                                                                 frame, **kwargs)
-        return y_mocos, self.predict_flow(y_mocos, backward=backward, iters=raft_iters)
+        batch = self._multi_shift_batch(x, active_patches, shifts, passive_patches, num_samples, fix_passive, frame, self._conditioning_kwargs(x, kwargs))
+        y_mocos = self._run_rect_batch(batch, rows_per_call=sample_batch_size)
+        self.reset_padding_masks()
+        return y_mocos, self._counterfactual_flows(y_mocos, batch.mask, frame, backward, raft_iters)
 
     # ---- flow from marker counterfactuals: no flow network (no counterpart in the reference; its `AddMarkers` is the prompt) ---------------------------
     @staticmethod

@@ -616,6 +616,27 @@ CWM_API int cwm_raft_workspace_bytes(cwm_raft_model* m, uint64_t* out);
 CWM_API int cwm_raft_corr_lookup_on_the_fly(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int h8, int w8, float* out_dev,
                                             void* stream);
 
+/* The encoders once per distinct frame of a call (added after 0.10.4; the version string is unchanged).
+ * replaces: the per-pair encoder passes of the reference's multi-frame loop (raft_model.py:276-300 calls the two-image forward, fnet on both images and
+ * cnet on the first, for every pair), and of `predict_counterfactual_videos_and_flows` (segmentation.py:431), whose S predicted videos of one movie
+ * all begin with the same frame 0.
+ * A forward's two image sources already say which images repeat: two images are the same frame when their device address and their channel stride are
+ * equal.  With sharing on, the forward recognises, from batch, pairs and the two sources' strides alone (on the host: no device read, no upload),
+ *   P1  a source with stride_t == 0 and pairs > 1: one frame per batch row;
+ *   P2  a source with stride_b == 0 and batch > 1: one frame for all rows;
+ *   P3  two sources of identical strides with image2 = image1 + k * stride_t, k in {0, +1, -1}: one frame repeated, a movie (pairs + 1 frames per row
+ *       in place of 2 * pairs), a movie whose pairs run backwards;
+ * P1 and P2 per source, independently.  fnet then runs once per distinct frame and cnet once per distinct first image, and the correlation, the
+ * lookup and the GRU's initial state find each pair's maps by frame.  Any other call (partial overlaps, a negative stride, different channel strides)
+ * runs as with sharing off: 2 * batch * pairs fnet images and batch * pairs cnet images, launch for launch.  Images whose addresses differ are never
+ * merged.  The GEMM plan of an encoder pass depends on its row count, so a shared forward agrees with an unshared one as the same pair does in batches
+ * of different sizes (up to fp32 summation order), not bit for bit; the workspace is planned from the distinct counts and never grows.
+ *   cwm_raft_set_share_frames  on = 1 / 0 (the default) for the forwards of this handle that follow.  Any other value: CWM_ERR_INVALID, and the handle
+ *                              keeps what it had.  Per handle because cwm_raft_forward_args is frozen.
+ *   cwm_raft_encoder_images    how many images the handle's last forward ran through fnet and through cnet; both 0 before the first forward. */
+CWM_API int cwm_raft_set_share_frames(cwm_raft_model* m, int on);
+CWM_API int cwm_raft_encoder_images(cwm_raft_model* m, int* fnet_images, int* cnet_images);
+
 /* RAFT's forward interpolation on the device: a low-resolution flow carried along itself onto the next frame's grid, which is what the warm-start
  * protocol feeds to the next pair as `flow_init` (added after 0.10.4; the version string is unchanged).
  * replaces: `forward_interpolate` (raft/utils.py:28-56): a `.cpu().numpy()` copy and two scipy `griddata(..., method='nearest')` queries per field.

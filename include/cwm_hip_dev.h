@@ -155,6 +155,26 @@ CWM_API int cwm_dev_raft_instnorm_stats(const float* x_dev, int n_img, int HW, i
 CWM_API int cwm_dev_raft_residual_join(const cwm_dev_conv_src* X, const cwm_dev_conv_src* Y, int n_img, int HW, float* out_dev, void* stream);
 /* cn [M][256] -> h [M][128] = tanh(cn[:, :128]), x[m * 256 + c] = relu(cn[:, 128:]) for c < 128 */
 CWM_API int cwm_dev_raft_cnet_split(const float* cn_dev, int64_t M, float* h_dev, float* x_dev, void* stream);
+/* ---- frames shared between the pairs of a forward (cwm_hip.h cwm_raft_set_share_frames; tests/test_raft_share_*.py) ----
+ * cwm_dev_raft_frame_slots is the forward's frame plan made queryable, on the host alone (no GPU, nothing is read through the pointers): for the call
+ * `args` describes (batch, pairs, the two image sources) and share = 0 / 1, pair p = b * pairs + t has its image1 at slot1[p] and its image2 at slot2[p]
+ * of the n_fnet frames fnet runs on, and its context at cslot[p] of the n_cnet frames cnet runs on.  slot1 / slot2 / cslot: host arrays of
+ * batch * max(pairs, 1) ints.
+ * The four consumers of the encoders' maps, addressed by slot: the map of pair (g, t) = (p / ppg, p % ppg) lies g * sb + t * st maps past the operand's
+ * pointer (sb = ppg, st = 1: one map per pair, the forms above).  None checks that the buffers reach as far as the strides say.
+ *   cwm_dev_raft_corr_lookup_slots             cwm_raft_corr_lookup with fmap1 / fmap2 [frames, h8, w8, 256] addressed by (s1b, s1t) / (s2b, s2t)
+ *   cwm_dev_raft_fmap_pool_slots               out [n_out, h / 2, w / 2, C] = avg_pool2d(2) of the input map at (j / nt) * in_sb + (j % nt) * in_st, j < n_out
+ *   cwm_dev_raft_corr_lookup_on_the_fly_slots  the lookup of cwm_raft_corr_lookup_on_the_fly on the caller's four levels of fmap2 (an array of four device
+ *                                              pointers, on the host): level 0 addressed by (s2b, s2t), the pooled levels by (s2pb, s2pt), fmap1 by (s1b, s1t)
+ *   cwm_dev_raft_cnet_split_slots              cwm_dev_raft_cnet_split with cn [frames, hw8, 256] addressed by (sb, st); h and x stay per pair */
+CWM_API int cwm_dev_raft_frame_slots(const cwm_raft_forward_args* args, int share, int* slot1, int* slot2, int* cslot, int* n_fnet, int* n_cnet);
+CWM_API int cwm_dev_raft_corr_lookup_slots(const float* fmap1_dev, const float* fmap2_dev, const float* coords_dev, int P, int ppg, int h8, int w8, int64_t s1b,
+                                           int64_t s1t, int64_t s2b, int64_t s2t, float* out_dev, void* stream);
+CWM_API int cwm_dev_raft_fmap_pool_slots(const float* in_dev, int n_out, int nt, int64_t in_sb, int64_t in_st, int h, int w, int C, float* out_dev, void* stream);
+CWM_API int cwm_dev_raft_corr_lookup_on_the_fly_slots(const float* fmap1_dev, const float* const* fmap2_levels_dev, const float* coords_dev, int P, int ppg, int h8,
+                                                      int w8, int64_t s1b, int64_t s1t, int64_t s2b, int64_t s2t, int64_t s2pb, int64_t s2pt, float* out_dev,
+                                                      void* stream);
+CWM_API int cwm_dev_raft_cnet_split_slots(const float* cn_dev, int64_t M, int64_t hw8, int ppg, int64_t sb, int64_t st, float* h_dev, float* x_dev, void* stream);
 /* x [M][256]: columns 128..253 -> relu, 254 / 255 = coords [M][2] - (x, y) of the pixel on the h8 x w8 grid */
 CWM_API int cwm_dev_raft_motion_finish(float* x_dev, const float* coords_dev, int64_t M, int h8, int w8, void* stream);
 /* h [M][128] = (1 - z) h + z tanh(q), z = sigmoid(zr[m * 256 + c]), q [M][128] */

@@ -17,7 +17,10 @@ flow settles, which is what `set_raft_iters` is chosen from.
 (`warm_start=True`: T-1 forwards one after another with `forward_interpolate` between them), the cold multi-frame call on the same
 movie (all pairs in one launch set), and the same chain with the interpolation done on the host between two-image calls, by the numpy restatement
 of tests/raft_video_restatement.py: the synchronisation, the copy down, the search and the copy back a user of the reference's protocol pays; and the
-interpolation kernel alone."""
+interpolation kernel alone.
+`--share` turns `share_frames` on (the encoders once per distinct frame of a call) for whatever else is timed; `--frames T` without
+`--warm-start` times the cold multi-frame call on a movie of T frames.  `--shared-first S` times B rows x S pairs on one first frame per row through
+`RAFT.flow_pairs`, with the flag off and then on in one session, and prints both with `last_encoder_images` (fnet, cnet) and their ratio."""
 import argparse
 import json
 import os
@@ -81,6 +84,26 @@ def warm_start_lines(m, args):
                           "chain_through_host_ms_per_pair": round(host[0] / (B * (T - 1)), 3)}), flush=True)
 
 
+def shared_first_lines(m, args):
+    """B rows x S pairs on one first frame per row (`flow_pairs` on an expanded view): unshared, then shared, in one session"""
+    H, W = args.size
+    S_ = args.shared_first
+    for B in args.batch:
+        x = torch.from_numpy(S.raft_frames(B, H, W, 1, frames=S_ + 1)).cuda()
+        first, second = x[:, :1].expand(-1, S_, -1, -1, -1), x[:, 1:]
+        res = {}
+        for share in (False, True, False, True):  # (each setting twice, alternating: a drift of the clock would show)
+            ms = timed(lambda: m.flow_pairs(first, second, iters=args.iters, share=share), args.warmup, args.steps)
+            res.setdefault(share, []).append((ms, m.last_encoder_images, m.workspace_bytes()))
+        off, on = (min(res[k], key=lambda r: r[0][0]) for k in (False, True))
+        err = (m.flow_pairs(first, second, iters=args.iters, share=True) - m.flow_pairs(first, second, iters=args.iters, share=False)).abs().max().item()
+        print(json.dumps({"shared_first": S_, "mode": m.mode, "corr": m.corr, "batch": B, "size": [H, W], "iters": args.iters,
+                          "off_ms_median": round(off[0][0], 3), "off_ms_min": round(off[0][1], 3), "off_encoder_images": list(off[1]), "off_workspace_bytes": off[2],
+                          "on_ms_median": round(on[0][0], 3), "on_ms_min": round(on[0][1], 3), "on_encoder_images": list(on[1]), "on_workspace_bytes": on[2],
+                          "all_ms_median": {str(k): [round(r[0][0], 3) for r in v] for k, v in res.items()},
+                          "on_over_off": round(on[0][0] / off[0][0], 4), "max_abs_on_minus_off_px": err}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 8, 32])
@@ -94,14 +117,21 @@ def main():
     ap.add_argument("--flow-init", action="store_true", help="time a warm-started forward (flow_init)")
     ap.add_argument("--per-iteration", action="store_true", help="time the list form (test_mode=False) and print how much each iteration moves the prediction")
     ap.add_argument("--warm-start", action="store_true", help="time a warm-started movie: the device chain, the cold call and the chain through the host")
-    ap.add_argument("--frames", type=int, default=4, help="frames of the movie of --warm-start")
+    ap.add_argument("--frames", type=int, default=None, help="frames of the movie (default 2; 4 with --warm-start)")
+    ap.add_argument("--share", action="store_true", help="share_frames: the encoders once per distinct frame of a call (RAFT.set_share_frames)")
+    ap.add_argument("--shared-first", type=int, default=None, metavar="S", help="time B rows x S pairs on one first frame per row (flow_pairs), flag off and on")
     args = ap.parse_args()
+    if args.frames is None:
+        args.frames = 4 if args.warm_start else 2
+    if args.shared_first is not None and (args.shared_first < 1 or args.warm_start or args.per_iteration or args.flow_init or args.output_dim):
+        ap.error("--shared-first S >= 1 times the flow forward only: it excludes --warm-start, --per-iteration, --flow-init and --output-dim")
     if args.warm_start and (args.frames < 3 or args.flow_init or args.per_iteration):
         ap.error("--warm-start needs --frames >= 3 and excludes --flow-init and --per-iteration")
     H, W = args.size
     m = RAFT(_args(output_dim=args.output_dim)) if args.output_dim else RAFT()
     m.set_mode(args.mode)
     m.set_corr(args.corr)
+    m.set_share_frames(args.share)
     sd = S.raft_state_dict(0, output_dim=args.output_dim) if args.output_dim else S.raft_state_dict(0)
     m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
     m = m.cuda().eval()
@@ -115,12 +145,15 @@ def main():
         flops += (args.iters - 1) * per_it
     if args.warm_start:
         return warm_start_lines(m, args)
+    if args.shared_first is not None:
+        return shared_first_lines(m, args)
     init = None
     if args.flow_init:
         g = torch.Generator().manual_seed(2)
         init = (4.0 * torch.rand(1, 2, H // 8, W // 8, generator=g) - 2.0).cuda()
     for B in args.batch:
-        x = torch.from_numpy(S.raft_frames(B, H, W, 1)).cuda()
+        x = torch.from_numpy(S.raft_frames(B, H, W, 1, frames=args.frames)).cuda()
+        pairs = B * max(args.frames - 1, 1)
         if args.per_iteration:
             x1, x2 = (x[:, 0] * 255.0).contiguous(), (x[:, 1] * 255.0).contiguous()
 
@@ -143,9 +176,10 @@ def main():
             for i in range(1, len(out)):
                 d = (out[i] - out[i - 1]).abs()
                 print(json.dumps({"batch": B, "iteration": i + 1, "step_max_abs_px": round(d.max().item(), 4), "step_mean_abs_px": round(d.mean().item(), 5)}), flush=True)
-        print(json.dumps({"output": "keypoints" if args.output_dim else "flow", "mode": m.mode, "corr": m.corr, "flow_init": bool(args.flow_init), "per_iteration": bool(args.per_iteration), "batch": B, "size": [H, W], "iters": args.iters, "workspace_bytes": m.workspace_bytes(), "ms_median": round(ms, 3), "ms_min": round(1e3 * min(times), 3),
-                          "pairs_per_s": round(B / (ms / 1e3), 2), "gflop_per_pair": round(flops / 1e9, 2),
-                          "tflops": round(B * flops / (ms / 1e3) / 1e12, 2)}), flush=True)
+        print(json.dumps({"output": "keypoints" if args.output_dim else "flow", "mode": m.mode, "corr": m.corr, "flow_init": bool(args.flow_init), "per_iteration": bool(args.per_iteration), "batch": B, "frames": args.frames, "share_frames": m.share_frames,
+                          "encoder_images": list(m.last_encoder_images), "size": [H, W], "iters": args.iters, "workspace_bytes": m.workspace_bytes(), "ms_median": round(ms, 3), "ms_min": round(1e3 * min(times), 3),
+                          "pairs_per_s": round(pairs / (ms / 1e3), 2), "gflop_per_pair": round(flops / 1e9, 2),
+                          "tflops": round(pairs * flops / (ms / 1e3) / 1e12, 2)}), flush=True)
 
 
 if __name__ == "__main__":
