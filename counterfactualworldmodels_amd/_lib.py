@@ -130,6 +130,25 @@ class CwmTokenResponseArgs(C.Structure):
     ]
 
 
+class CwmUnmaskStepArgs(C.Structure):
+    """cwm_unmask_step_args (include/cwm_hip.h): cwm_patch_error_args as `base` (the error map's inputs, the mask and the stream), the frame, the selection rule
+    and the outputs; new_unmask_step_args() sets struct_size"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", CwmPatchErrorArgs),
+        ("frame", C.c_int32),
+        ("num_reveal", C.c_int32),
+        ("mode", C.c_int32),
+        ("self_mask", C.c_int32),
+        ("threshold_dev", C.c_void_p),
+        ("e_dev", C.c_void_p),
+        ("mask_out_dev", C.c_void_p),
+        ("picks_dev", C.c_void_p),
+        ("dist_dev", C.c_void_p),
+        ("frontier_dev", C.c_void_p),
+    ]
+
+
 class CwmConjConfig(C.Structure):
     _fields_ = [
         ("main", CwmConfig),
@@ -569,6 +588,13 @@ def new_token_response_args() -> CwmTokenResponseArgs:
     return a
 
 
+def new_unmask_step_args() -> CwmUnmaskStepArgs:
+    a = CwmUnmaskStepArgs()
+    a.struct_size = C.sizeof(CwmUnmaskStepArgs)
+    a.base.struct_size = C.sizeof(CwmPatchErrorArgs)
+    return a
+
+
 def new_conj_forward_args() -> CwmConjForwardArgs:
     a = CwmConjForwardArgs()
     a.struct_size = C.sizeof(CwmConjForwardArgs)
@@ -616,6 +642,7 @@ SIGNATURES = {
     ),
     "cwm_patch_error": (C.c_int, [C.POINTER(CwmPatchErrorArgs)]),
     "cwm_token_response": (C.c_int, [C.POINTER(CwmTokenResponseArgs)]),
+    "cwm_unmask_step": (C.c_int, [C.POINTER(CwmUnmaskStepArgs)]),
     "cwm_mask_row_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_mask_flip_picks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cwm_prompt_table_expand": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),

@@ -307,6 +307,30 @@ struct TokenResponseParams {
 
 int launch_token_response(const TokenResponseParams& p, hipStream_t stream);
 
+// One step of frontier unmasking on frame `frame` of a mask (unmask.hip unmask_select_kernel): the L-inf distance transform of the frame's grid (the reference's
+// patch_distance_transform, bit for bit), the frontier d <= threshold on the masked cells, and the reveal of the k masked cells that rank first by (frontier,
+// key descending with NaN first, index ascending).  One workgroup per batch row; no allocation, no synchronisation, no atomics.
+constexpr int kUnmaskMaxCells = 4096;  // patches per frame (the row's state lives in LDS)
+constexpr int kUnmaskMaxReveal = 64;
+struct UnmaskStepParams {
+    const uint8_t* mask;     // [B][T * gh * gw]
+    int B, T, gh, gw, frame;
+    int k;                   // cells revealed per row; 0: dist and frontier only, map / region / e are not read
+    int race;                // 0: key = err; 1: key = max(err, 0) / e (a NaN err stays NaN)
+    int self_mask;           // dist: the visible cells get the grid's maximum
+    const float* threshold;  // [1] on the device; negative (or nullptr): every masked cell is frontier
+    const float* map;        // [B][T][gh][gw]: err = map[b][frame] ...
+    const float* region;     // ... times region[b][frame] when given
+    const float* e;          // [B][gh * gw], race mode
+    uint8_t* mask_out;       // [B][T * gh * gw] or nullptr: mask with the picks cleared; must not overlap mask
+    int* picks;              // [B][k] or nullptr: token indices in pick order, -1 once the frame has no masked cell left
+    float* dist;             // [B][gh * gw] or nullptr
+    uint8_t* frontier;       // [B][gh * gw] or nullptr
+};
+
+int check_unmask_select(const UnmaskStepParams& p);  // the argument checks of the launch alone: 0 or CWM_ERR_INVALID with a message
+int launch_unmask_select(const UnmaskStepParams& p, hipStream_t stream);
+
 struct ShiftPromptParams {
     const float* x;         // [B][T][C][H][W] contiguous frames
     int B, S, T, C, H, W, P, frame, fix_passive;

@@ -164,6 +164,116 @@ def upsample_masks(masks: torch.Tensor, size) -> torch.Tensor:
     return masks.view(*shape[:-2], H, W)
 
 
+# ---- mask morphology: how far a masked patch is from a visible one (masking.py:32-71) --------------------------------------
+_DT_MAX_CELLS = 4096  # cwm_unmask_step holds one grid in LDS
+_NO_GAP = 1 << 20
+
+
+def _check_grids(masks):
+    if not isinstance(masks, torch.Tensor) or masks.dim() != 4:
+        raise ValueError("patch_distance_transform: masks must be a [B,T,h,w] tensor, got %s" % (tuple(masks.shape) if isinstance(masks, torch.Tensor) else type(masks),))
+    if masks.dtype != torch.bool:
+        raise TypeError("patch_distance_transform: masks must be bool (True = masked), got %s" % masks.dtype)
+    h, w = masks.shape[-2:]
+    if h < 3 or w < 3:
+        raise ValueError("patch_distance_transform: the distances are in units of (h-1)//2 and (w-1)//2 patches, which is 0 for a %d x %d grid "
+                         "(the reference divides by zero): h and w must be at least 3" % (h, w))
+
+
+def _distance_numerators(masks: torch.Tensor) -> torch.Tensor:
+    """K [N,h,w] int64 for grids [N,h,w]: sy sx d, found in integers.  A column pass gives the vertical gap g to the nearest visible cell of every column, a
+    row pass min over the columns x' of max(g sx, |x - x'| sy); 0 for a grid without a visible cell."""
+    N, h, w = masks.shape
+    sy, sx = (h - 1) // 2, (w - 1) // 2
+    dev = masks.device
+    ys, xs = torch.arange(h, device=dev), torch.arange(w, device=dev)
+    dy = (ys[:, None] - ys[None, :]).abs()  # [y, vy]
+    dx = (xs[:, None] - xs[None, :]).abs() * sy  # [x, vx]
+    out = torch.empty((N, h, w), dtype=torch.int64, device=dev)
+    step = max(1, (1 << 22) // (h * w * max(h, w)))
+    for n0 in range(0, N, step):
+        m = masks[n0:n0 + step]
+        gap = torch.where(m[:, None], _NO_GAP, dy[None, :, :, None]).amin(2)  # [N, y, vy, x] -> [N, y, x]
+        k = torch.where(gap[:, :, None, :] >= _NO_GAP, _NO_GAP * _NO_GAP, torch.maximum(gap[:, :, None, :] * sx, dx[None, None])).amin(3)  # [N, y, x, vx] -> [N, y, x]
+        out[n0:n0 + step] = torch.where(k >= _NO_GAP * _NO_GAP, 0, k)
+    return out
+
+
+def _unmask_step_grids(masks: torch.Tensor, self_mask: bool, threshold=None):
+    """(dist [N,h,w], frontier [N,h,w] bool or None) of device grids [N,h,w] through the library (cwm_unmask_step with nothing to reveal)"""
+    import ctypes as C
+
+    from . import _lib
+
+    N, h, w = masks.shape
+    if h * w > _DT_MAX_CELLS:
+        raise ValueError("patch_distance_transform on the device holds a grid in LDS: at most %d patches, got %d x %d" % (_DT_MAX_CELLS, h, w))
+    dev = masks.device
+    m = masks.contiguous()
+    dist = torch.empty((N, h, w), device=dev, dtype=torch.float32)
+    a = _lib.new_unmask_step_args()
+    a.base.mask_dev = m.data_ptr()
+    a.base.batch, a.base.T, a.base.P, a.base.H, a.base.W = N, 1, 4, 4 * h, 4 * w
+    a.base.stream = _lib.current_stream_handle(dev)
+    a.frame, a.num_reveal, a.self_mask = 0, 0, int(bool(self_mask))
+    a.dist_dev = dist.data_ptr()
+    front = thr = None
+    if threshold is not None:
+        thr = torch.tensor([threshold], dtype=torch.float32).to(dev)
+        front = torch.empty((N, h, w), device=dev, dtype=torch.uint8)
+        a.threshold_dev, a.frontier_dev = thr.data_ptr(), front.data_ptr()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.get_lib().cwm_unmask_step(C.byref(a)))
+    return dist, (None if front is None else front.bool())
+
+
+def patch_distance_transform(masks: torch.Tensor, self_mask: bool = True) -> torch.Tensor:
+    """For each patch of masks [B,T,h,w] (True = masked) the L-inf distance to the nearest visible patch of its grid, in units of (h-1)//2 rows and (w-1)//2
+    columns: float32 [B,T,h,w], bit-equal to masking.py:32-56.  A grid without a visible patch is all zeros; with `self_mask` the visible patches get the
+    grid's maximum.  The reference loops in Python over every visible patch of every grid; here the nearest patch is found in integers (the candidates'
+    fractions compared by cross-multiplication) and only the winner is divided, once, in fp32 -- on the device in one kernel (cwm_unmask_step), on CPU
+    tensors in a few vectorised torch ops.  h or w below 3 divides by zero in the reference and is refused."""
+    _check_grids(masks)
+    B, T, h, w = masks.shape
+    if B * T == 0:
+        return torch.zeros((B, T, h, w), dtype=torch.float32, device=masks.device)
+    grids = masks.reshape(B * T, h, w)
+    if masks.is_cuda:
+        return _unmask_step_grids(grids, self_mask)[0].view(B, T, h, w)
+    k = _distance_numerators(grids)
+    den = float(((h - 1) // 2) * ((w - 1) // 2))
+    d = k.to(torch.float32) / den
+    if self_mask:
+        d = torch.where(grids, d, (k.amax((1, 2), keepdim=True).to(torch.float32) / den).expand_as(d))
+    return d.view(B, T, h, w)
+
+
+def patches_adjacent_to_visible(masks: torch.Tensor, radius=1, size=None) -> torch.Tensor:
+    """Which patches lie within `radius` patches (of the shorter side's unit) of a visible one (masking.py:58-71): bool, visible patches included only when
+    the grid's largest distance is within the radius (the reference's self_mask).  radius=None returns the masks; radius=0 the soft map
+    (max - d) / max(max, 1).  The threshold is the reference's: `r * radius` as a Python float, compared with the float32 distances by torch."""
+    if size is not None:
+        masks = masks.view(-1, 1, *size)
+    if radius is None:
+        return masks
+    h, w = masks.shape[-2:]
+    dists = patch_distance_transform(masks)
+    if radius != 0:
+        r = 1 / ((min(h, w) - 1) // 2)
+        return dists <= (r * radius)
+    rmax = dists.amax((-1, -2), keepdim=True)
+    return (rmax - dists) / rmax.clip(min=1.0)
+
+
+def frontier_threshold(h: int, w: int, radius) -> float:
+    """The threshold of `patches_adjacent_to_visible` for an integer radius, as the float32 comparison sees it; -1 (no restriction) for radius None"""
+    if radius is None:
+        return -1.0
+    if radius <= 0:
+        raise ValueError("a frontier radius is a positive number of patches or None, got %r" % (radius,))
+    return float(torch.tensor((1 / ((min(h, w) - 1) // 2)) * radius, dtype=torch.float32))
+
+
 # ---- mask generators that PRODUCE the prompts' masks (masking.py:267-401, 478-545) ---------------------------------------
 class MaskingGenerator(torch.nn.Module):
     """Uniformly random masks, one per frame: `num_masks_per_frame = int(mask_ratio * cells)` of the (clumped) grid cells are

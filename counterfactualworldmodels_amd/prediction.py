@@ -24,6 +24,7 @@ from torch import nn
 
 from . import _lib
 from .config import IMAGENET_MEAN, IMAGENET_STD
+from . import masking
 from .masking import RectangularizeMasks, upsample_masks
 from .perturbation import AddMarkers, MultiShiftPatchesAndMask, paint_markers
 from .conjoined_vmae import ConjoinedPaddedVisionTransformer
@@ -237,6 +238,25 @@ class PredictorBasedGenerator(nn.Module):
             stride = self.inp_shape[-1] // grid.size(-1)
         grid = self.make_visible_from_patch_idx_list(grid, patch_idx_list, stride=stride, b=b, t=frame)
         return grid.view(grid.size(0), -1)
+
+    def get_nearby_patches(self, mask, radius=1, upsample=False, shape=None):
+        """The patches of `mask` (viewed as [-1, *mask_shape], or `shape`) within `radius` of a visible one: `masking.patches_adjacent_to_visible` on the
+        mask image, optionally upsampled to the input's pixels (prediction.py:345-351)."""
+        nearby = masking.patches_adjacent_to_visible(self.get_mask_image(mask, shape=shape), radius=radius, size=None)
+        if upsample:
+            nearby = upsample_masks(nearby, size=self.inp_shape[-2:])
+        return nearby
+
+    def generate_cutout_mask(self, patch_idx_list, radius=1, stride=None, b=0, frame=-1):
+        """The mask of `generate_mask_from_patch_idx_list` with frame `frame` replaced by `patches_adjacent_to_visible` of itself, the listed patches
+        included (prediction.py:650-659); [B,Nt].  The reference slices `mask[:, frame:frame+1]`, which is empty for its own default frame=-1, and raises
+        there; a negative frame is taken as `frame % T` here."""
+        mask = self.get_mask_image(self.generate_mask_from_patch_idx_list(patch_idx_list, stride=stride, b=b, frame=frame))
+        f = frame % mask.size(1)
+        cutout = masking.patches_adjacent_to_visible(mask[:, f:f + 1], radius=radius)
+        cutout = torch.maximum(cutout, ~mask[:, f:f + 1])
+        mask[:, f] = cutout[:, 0]
+        return mask.flatten(1)
 
     def get_masked_pred_patches(self, preds, mask, invert=False, fill_value=None):
         """`preds` [B,T',C,H,W] with everything outside the masked patches zeroed (or replaced by `fill_value`: a tensor of
@@ -528,7 +548,7 @@ class PredictorBasedGenerator(nn.Module):
 
     # ---- error-guided unmasking (no counterpart in the reference: the search its keypoint net distils) -----------------
     def greedy_unmask(self, x, mask, target_mask=None, num_steps=1, candidates=None, num_candidates=None, frame=-1, target=None, sample_batch_size=None,
-                      return_scores=False):
+                      return_scores=False, radius=None):
         """Reveal, `num_steps` times, the masked patch of frame `frame` whose un-masking leaves the lowest mean error on the region
         (`get_error_on_target_region`; the default region is every patch of `frame`).  x [1,T,C,H,W], mask [1,Nt]; tokens are indices into the Nt
         tokens of the mask.  The candidates of a step are the still-masked tokens of `frame` -- of `candidates` if given; `num_candidates` of them
@@ -536,7 +556,11 @@ class PredictorBasedGenerator(nn.Module):
         so all rows have equal counts: nothing is rectangularised and torch's global RNG is not touched.  The frames go in as a stride-0 expand of
         x, never copied, and the rows are scored on the fused path in chunks of `sample_batch_size`, with one host read-back per step.  The pick is the
         lowest score; among equal scores the lowest token index.  Returns (mask_out [1,Nt], picks [num_steps], scores [num_steps]) and, with
-        return_scores, a list of each step's (candidates, scores)."""
+        return_scores, a list of each step's (candidates, scores).
+
+        An integer `radius` keeps, of each step's candidates, those on the frontier of the current mask: the masked patches of `frame` within `radius` of a
+        visible one (`masking.patches_adjacent_to_visible`, computed from the host copy of the mask: no extra read-back).  A step whose candidates have
+        none on the frontier searches them all.  radius=None is the search over all candidates."""
         if x.dim() != 5 or x.shape[0] != 1:
             raise ValueError("greedy_unmask searches the prompts of ONE movie: x must be [1,T,C,H,W], got %s" % (tuple(x.shape),))
         if frame is None:
@@ -569,6 +593,11 @@ class PredictorBasedGenerator(nn.Module):
             cand = f * n + np.flatnonzero(host[f * n:(f + 1) * n])
             if allowed is not None:
                 cand = cand[np.isin(cand, allowed)]
+            if radius is not None:
+                near = self._frontier_candidates(host[f * n:(f + 1) * n], h, w, radius)
+                on_frontier = cand[np.isin(cand, f * n + near)]
+                if len(on_frontier):
+                    cand = on_frontier
             if num_candidates is not None and len(cand) > num_candidates:
                 cand = np.sort(self.rng.choice(cand, size=int(num_candidates), replace=False))
             if len(cand) == 0:
@@ -596,6 +625,135 @@ class PredictorBasedGenerator(nn.Module):
             n_masked -= 1
         out = (cur, np.asarray(picks, dtype=np.int64), np.asarray(best, dtype=np.float32))
         return out + (trace,) if return_scores else out
+
+    @staticmethod
+    def _frontier_candidates(frame_mask, h, w, radius) -> np.ndarray:
+        """cells of one frame's host mask [h*w] that are masked and within `radius` of a visible one (the CPU path of masking.patches_adjacent_to_visible)"""
+        grid = torch.from_numpy(np.ascontiguousarray(frame_mask, dtype=np.bool_)).view(1, 1, h, w)
+        near = masking.patches_adjacent_to_visible(grid, radius=radius) & grid
+        return np.flatnonzero(near.view(-1).numpy())
+
+    @staticmethod
+    def _select_reveal(err, frame_mask, frontier, k, e=None):
+        """The selection rule of cwm_unmask_step in torch: err [B,n] float32, frame_mask / frontier [B,n] bool, e [B,n] (race) or None -> cells [B,k] int64,
+        -1 where a row has run out of masked cells.  Order: frontier before the other masked cells, the higher key first (NaN above every number),
+        the lower index first -- two stable sorts."""
+        key = err if e is None else err.clamp(min=0) / e
+        by_key = torch.sort(key, dim=1, descending=True, stable=True).indices
+        cls = frontier.to(torch.int8) + frame_mask.to(torch.int8)  # 2 frontier, 1 masked, 0 visible
+        by_cls = torch.sort(torch.gather(cls, 1, by_key), dim=1, descending=True, stable=True)
+        cells = torch.gather(by_key, 1, by_cls.indices)
+        cells = torch.where(by_cls.values > 0, cells, torch.full_like(cells, -1))
+        if k > cells.shape[1]:
+            cells = torch.cat([cells, torch.full((cells.shape[0], k - cells.shape[1]), -1, dtype=cells.dtype, device=cells.device)], 1)
+        return cells[:, :k]
+
+    def frontier_unmask(self, x, mask, num_steps=1, num_reveal=1, radius=1, frame=-1, target_mask=None, target=None, sample=False, generator=None,
+                        return_trace=False):
+        """Unmasking that grows outward from what is visible, guided by where the prediction is still wrong: `num_steps` times, predict (x, mask) once for the
+        whole batch, take the per-patch error on the region (`get_error_on_target_region`; the default region is every patch of `frame`), and reveal in
+        every row the `num_reveal` masked patches of `frame` with the largest error among those within `radius` of a visible patch
+        (`masking.patches_adjacent_to_visible`; radius=None: among all).  A row with fewer frontier patches than `num_reveal` fills up from its other masked
+        patches; equal errors go to the lower index; a frame without a visible patch has every patch on the frontier.  sample=True draws the patches
+        without replacement with probability proportional to max(error, 0) instead (an exponential race: the key is error / e with e ~ Exp(1) drawn
+        from `generator` on x's device).
+
+        x [B,T,C,H,W], mask [B,Nt] with the same masked count in every row.  Returns (mask_out [B,Nt], picks [B,num_steps,num_reveal] int64 token
+        indices on x's device, errors [B,num_steps]: the region's mean error before each step's reveal) and, with return_trace, a list of each step's
+        (error map [B,T,h,w], frontier [B,h,w] bool).  One read-back before the loop (the counts), none inside it: on the fused error path a step is the
+        forward to tokens and one library call (cwm_unmask_step).  CPU tensors, conjoined predictors and a custom error_func compose
+        `get_error_on_target_region`, the torch distance transform and the same selection rule in torch.
+
+        This is what the reference's `EnergySampleUnmask` (perturbation.py:589-640) was meant to be; that class does not run."""
+        if x.dim() != 5:
+            raise ValueError("frontier_unmask: x must be [B,T,C,H,W], got %s" % (tuple(x.shape),))
+        if frame is None:
+            raise ValueError("frontier_unmask un-masks patches of one frame: frame must be an index")
+        B, T, _, H, W = x.shape
+        P = self.patch_size[-1]
+        h, w = H // P, W // P
+        n, Nt = h * w, T * h * w
+        f = frame % T
+        k, steps = int(num_reveal), int(num_steps)
+        if k < 1 or steps < 1:
+            raise ValueError("frontier_unmask: num_steps and num_reveal must be at least 1")
+        dev = x.device
+        cur = mask.reshape(B, Nt).to(device=dev, dtype=torch.bool).clone()
+        thr = masking.frontier_threshold(h, w, radius)
+        if target_mask is None:
+            region = torch.zeros((B, T, h, w), device=dev, dtype=torch.float32)
+            region[:, f] = 1
+        elif target_mask.dim() == 2:
+            region = 1 - target_mask.view(B, -1, h, w).to(x)
+        else:
+            region = 1 - target_mask.to(x)
+        rows = cur.sum(1)
+        lo, hi, in_frame = (int(v) for v in torch.stack([rows.min(), rows.max(), cur[:, f * n:(f + 1) * n].sum(1).min()]).tolist())  # the one read-back
+        if lo != hi:
+            raise ValueError("frontier_unmask: every row of the mask must have the same masked count (got %d .. %d): rectangularise it first" % (lo, hi))
+        if in_frame < steps * k:
+            raise ValueError("frontier_unmask: %d steps of %d patches need %d masked patches in frame %d of every row, a row has %d" % (steps, k, steps * k, f, in_frame))
+        self.set_image_size(x.shape[-2:])
+        self.inp_shape = x.shape
+        fused = self._error_takes_fused_path(x, target, region, True, None, {}) and k <= 64 and n <= 4096 and min(h, w) >= 3
+        if min(h, w) < 3:
+            raise ValueError("frontier_unmask: the frontier needs a grid of at least 3 x 3 patches, got %d x %d" % (h, w))
+        picks = torch.empty((steps, B, k), device=dev, dtype=torch.int32 if fused else torch.int64)
+        errors = torch.empty((steps, B), device=dev, dtype=torch.float32)
+        trace = []
+        draw = (lambda: torch.empty((B, n), device=dev, dtype=torch.float32).exponential_(generator=generator)) if sample else (lambda: None)
+        if fused:
+            pred = self.predictor
+            pred.sync_weights(dev)
+            xs, (sb, sc, st) = pred._frame_strides(x, 2, 1)
+            region = region.contiguous()
+            thr_dev = torch.tensor([thr], dtype=torch.float32).to(dev)
+            nxt = torch.empty_like(cur)
+            a = _lib.new_unmask_step_args()
+            g = a.base
+            g.x_dev, g.x_stride_b, g.x_stride_t, g.x_stride_c = xs.data_ptr(), sb, st, sc
+            if target is not None:
+                tg, (tb, tc, tt) = pred._frame_strides(target, 2, 1)
+                g.target_dev, g.target_stride_b, g.target_stride_t, g.target_stride_c = tg.data_ptr(), tb, tt, tc
+            g.region_dev = region.data_ptr()
+            g.batch, g.T, g.C, g.H, g.W, g.P = B, T, x.shape[2], H, W, P
+            g.frame, g.stream = f, _lib.current_stream_handle(dev)
+            a.frame, a.num_reveal, a.mode, a.threshold_dev = f, k, int(bool(sample)), thr_dev.data_ptr()
+            emap = torch.empty((B, T, h, w), device=dev, dtype=torch.float32)
+            front = torch.empty((B, h, w), device=dev, dtype=torch.uint8) if return_trace else None
+            for s in range(steps):
+                n_masked = lo - s * k
+                y, _ = pred._run(xs, (sb, sc, st), self.imagenet_normalize_inputs, cur, Nt - n_masked, False, check=False, weights_synced=True)
+                e = draw()
+                if return_trace:
+                    emap = torch.empty((B, T, h, w), device=dev, dtype=torch.float32)
+                    front = torch.empty((B, h, w), device=dev, dtype=torch.uint8)
+                g.y_tokens_dev, g.mask_dev, g.n_vis = _lib.ptr(y), cur.data_ptr(), Nt - n_masked
+                g.map_dev, g.mean_dev = emap.data_ptr(), errors[s].data_ptr()
+                a.e_dev, a.mask_out_dev, a.picks_dev, a.frontier_dev = _lib.ptr(e), nxt.data_ptr(), picks[s].data_ptr(), _lib.ptr(front)
+                with torch.cuda.device(dev):
+                    _lib.check(_lib.get_lib().cwm_unmask_step(C.byref(a)))
+                if return_trace:
+                    trace.append((emap, front.bool()))
+                cur, nxt = nxt, cur
+        else:
+            tm = (1 - region) if target_mask is None else target_mask
+            for s in range(steps):
+                emap = self.get_error_on_target_region(x, cur.clone(), tm, target=target, average_error=False, frame=frame)  # [B,T,h,w], region-weighted
+                errors[s] = emap.sum((1, 2, 3)) / region.sum((1, 2, 3)).clamp(min=1)
+                fm = cur[:, f * n:(f + 1) * n]
+                if thr < 0:
+                    front = fm
+                else:
+                    front = fm & (masking.patch_distance_transform(fm.reshape(B, 1, h, w), self_mask=False).view(B, n) <= thr)
+                cells = self._select_reveal(emap[:, f].reshape(B, n).float(), fm, front, k, draw())
+                picks[s] = f * n + cells
+                cur = cur.clone()
+                cur[torch.arange(B, device=dev)[:, None], f * n + cells] = False
+                if return_trace:
+                    trace.append((emap, front.view(B, h, w)))
+        out = (cur, picks.permute(1, 0, 2).to(torch.int64).contiguous(), errors.t().contiguous())
+        return out + (trace,) if return_trace else out
 
     # ---- marker counterfactuals: where a perturbation lands (perturbation.py:356-476 is the prompt; the read-out has no counterpart in the reference) ------
     @staticmethod

@@ -339,6 +339,43 @@ typedef struct cwm_token_response_args {
  * Limits as cwm_patch_error: P 4, 8 or 16, C <= 8, W/P <= 256.  Argument errors: CWM_ERR_INVALID with a message, before anything is launched. */
 CWM_API int cwm_token_response(const cwm_token_response_args* args);
 
+typedef struct cwm_unmask_step_args {
+    uint32_t struct_size;            /* sizeof(cwm_unmask_step_args); anything else: CWM_ERR_INVALID naming struct_size */
+    /* num_reveal > 0: every field as cwm_patch_error reads it (map_dev or scratch_dev is required: the selection reads the map from it); base.struct_size is
+     * ignored.  num_reveal == 0: only mask_dev, batch, T, H, W, P and the stream are read */
+    cwm_patch_error_args base;
+    int32_t frame;                   /* 0 .. T-1: the frame of the mask whose cells are measured and revealed */
+    int32_t num_reveal;              /* k, 0 .. 64 cells revealed per row; 0: dist_dev and frontier_dev only */
+    int32_t mode;                    /* 0 top: key = err; 1 race: key = max(err, 0) / e (a NaN err stays NaN) */
+    int32_t self_mask;               /* dist_dev: non-zero gives the visible cells the grid's maximum (patch_distance_transform's self_mask) */
+    const float* threshold_dev;      /* [1] on the device: frontier = masked and d <= threshold; a negative value (or NULL) = every masked cell */
+    const float* e_dev;              /* [B, n] positive draws of the race (torch.empty(...).exponential_()); race mode only */
+    uint8_t* mask_out_dev;           /* out [B, Nt] or NULL: base.mask_dev with the picks cleared; must not overlap base.mask_dev */
+    int32_t* picks_dev;              /* out [B, k] or NULL: token indices in pick order; -1 once the frame of a row has no masked cell left */
+    float* dist_dev;                 /* out [B, n] or NULL */
+    uint8_t* frontier_dev;           /* out [B, n] uint8 or NULL */
+} cwm_unmask_step_args;
+
+/* One step of unmasking that grows outward from what is visible, guided by where the prediction is still wrong, without a host read-back.
+ * replaces: `patch_distance_transform` cwm/models/masking.py:32-56 and `patches_adjacent_to_visible` masking.py:58-71 (the integer-radius branch), as
+ *           `get_nearby_patches` prediction.py:345-351 uses them, on device masks; the selection is what `EnergySampleUnmask` (perturbation.py:589-640, which
+ *           does not run in the reference) was meant to do.
+ *   With f = frame, gh = H/P, gw = W/P, n = gh gw, sy = (gh-1)/2, sx = (gw-1)/2 (integer divisions) and cell = i gw + j:
+ *   d[b][cell]        = min over the visible cells v of frame f of row b of max(|i - vi| / sy, |j - vj| / sx) in fp32, bit-equal to the reference; 0 everywhere when
+ *                       the frame has no visible cell; with self_mask the visible cells hold the maximum of d over the grid
+ *   frontier[b][cell] = cell is masked and (threshold < 0 or d <= threshold).  The host computes the threshold as the reference does:
+ *                       float32(radius * (1 / ((min(gh, gw) - 1) / 2)))
+ *   err[b][cell]      = map[b][f][cell] of cwm_patch_error on `base` (launched first: base.map_dev and base.mean_dev hold what that call writes, bit for bit), times
+ *                       base.region_dev[b][f][cell] when a region is given
+ *   The k cells revealed in row b are the first k masked cells of frame f in the order: frontier cells before the other masked cells; the higher key first, a NaN
+ *   above every number (torch.sort) and -0 equal to +0; the lower index first.  picks[b][r] = f n + cell of the r-th; a row with fewer than k masked cells
+ *   in the frame leaves its surplus picks at -1 and clears nothing for them.
+ * Asynchronous on base.stream: nothing is allocated, the host is not synchronised, no atomics, fixed order -- two calls on the same inputs give the same bits.
+ * One workgroup per row holds the frame's state in LDS.  No mask content makes the call read or write outside its buffers.
+ * Limits: gh, gw >= 3 (the reference divides by sy and sx), n <= 4096, k <= 64, and with k > 0 the limits of cwm_patch_error.  Argument errors: CWM_ERR_INVALID with
+ * a message, before anything is launched. */
+CWM_API int cwm_unmask_step(const cwm_unmask_step_args* args);
+
 /* `RectangularizeMasks` (masking.py:90-132) on device masks without reading them back.  The reference equalises the masked count of
  * the rows of a batch by un-masking / masking `torch.randperm(#candidates)[:surplus]` of a row's masked / visible tokens (one draw of the global CPU
  * generator per changed row, in row order).  The draws depend on the per-row COUNTS alone, so:
