@@ -149,6 +149,39 @@ class CwmUnmaskStepArgs(C.Structure):
     ]
 
 
+class CwmSegmentStepArgs(C.Structure):
+    """cwm_segment_step_args (include/cwm_hip.h): cwm_patch_error_args as `base` (batch, T, H, W, P and the stream are read), the flow samples by five strides, the
+    seeds, the thresholds, the selection and the outputs; new_segment_step_args() sets struct_size"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", CwmPatchErrorArgs),
+        ("flows_dev", C.c_void_p),
+        ("flow_strides", C.c_int64 * 5),
+        ("C", C.c_int32),
+        ("S", C.c_int32),
+        ("seeds_dev", C.c_void_p),
+        ("dirs_dev", C.c_void_p),
+        ("min_seed_mag", C.c_float),
+        ("abs_thresh", C.c_float),
+        ("rel_thresh", C.c_float),
+        ("vote_frac", C.c_float),
+        ("cos_min", C.c_float),
+        ("inside_frac", C.c_float),
+        ("k_active", C.c_int32),
+        ("k_passive", C.c_int32),
+        ("ring_radius", C.c_int32),
+        ("keys_dev", C.c_void_p),
+        ("seed_ref_dev", C.c_void_p),
+        ("votes_dev", C.c_void_p),
+        ("segment_dev", C.c_void_p),
+        ("cover_dev", C.c_void_p),
+        ("stats_dev", C.c_void_p),
+        ("picks_dev", C.c_void_p),
+        ("active_out_dev", C.c_void_p),
+        ("passive_out_dev", C.c_void_p),
+    ]
+
+
 class CwmConjConfig(C.Structure):
     _fields_ = [
         ("main", CwmConfig),
@@ -595,6 +628,14 @@ def new_unmask_step_args() -> CwmUnmaskStepArgs:
     return a
 
 
+def new_segment_step_args() -> CwmSegmentStepArgs:
+    a = CwmSegmentStepArgs()
+    a.struct_size = C.sizeof(CwmSegmentStepArgs)
+    a.base.struct_size = C.sizeof(CwmPatchErrorArgs)
+    a.base.T = 2
+    return a
+
+
 def new_conj_forward_args() -> CwmConjForwardArgs:
     a = CwmConjForwardArgs()
     a.struct_size = C.sizeof(CwmConjForwardArgs)
@@ -643,6 +684,7 @@ SIGNATURES = {
     "cwm_patch_error": (C.c_int, [C.POINTER(CwmPatchErrorArgs)]),
     "cwm_token_response": (C.c_int, [C.POINTER(CwmTokenResponseArgs)]),
     "cwm_unmask_step": (C.c_int, [C.POINTER(CwmUnmaskStepArgs)]),
+    "cwm_segment_step": (C.c_int, [C.POINTER(CwmSegmentStepArgs)]),
     "cwm_mask_row_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_mask_flip_picks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cwm_prompt_table_expand": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),

@@ -57,6 +57,7 @@ enum FlowForm {
     FEATURES_SCALAR = 0, FEATURES_VEC4, MOTION_STRIDED = 0, MOTION_TILE, MOTION_ROWS16, MOTION_ROWS32, MOTION_ROWS64,
     COUNT_PLANES = 0, COUNT_PLANES_VEC, COUNT_PACKED, COUNT_PACKED_VEC, FINISH_V1 = 0, FINISH_V4,
     ZERO_PLANES = 0, ZERO_PLANES_VEC, ZERO_SCATTER, PACK_TRANSPOSE = 0,
+    VOTE_STRIDED = 0, VOTE_PLANES_VEC, VOTE_PACKED,  // (cwm_segment_step; not read out by cwm_dev_flow_forms)
 };
 
 // cwm_flow_features (aux: the output): four samples per thread
@@ -88,6 +89,14 @@ static inline FlowForm flow_zero_form(const FlowView& v, const FlowLayout& l) {
     return v.S <= 8192 ? ZERO_SCATTER : FLOW_REFUSED;
 }
 static inline FlowForm flow_pack_form(const FlowLayout& l) { return l.sample_outer ? PACK_TRANSPOSE : FLOW_REFUSED; }
+// cwm_segment_step, the vote pass (aux: the votes, [B][H W] bytes).  Packed: a tile of 64 pixels x S samples per workgroup, read as consecutive floats.  Planes (the
+// sample-outermost view among them): four pixels per thread as 16-byte loads and one 4-byte store of their votes, where the addresses allow it.  Everything else, and
+// planes that do not, takes the one-pixel-per-thread form through all five strides -- still coalesced on planes, where adjacent threads read adjacent floats.
+constexpr int kVoteTilePix = 64;
+static inline FlowForm flow_vote_form(const FlowView& v, const FlowLayout& l) {
+    if (l.packed && v.S > 1) return VOTE_PACKED;
+    return l.planes && (v.H * v.W) % 4 == 0 && l.f16 && l.sb4 && l.sc4 && l.ss4 && l.aux16 ? VOTE_PLANES_VEC : VOTE_STRIDED;
+}
 
 // ---- the magnitude: TWO forms, because hipcc rounds them differently and an ulp would move patch_mag or a threshold decision.  The statistics sum v v
 // over the channels from zero; T = float, or f32x4: four adjacent elements as one 16-byte load (f + c sc stays workgroup-uniform where `off` carries the lane's part).

@@ -331,6 +331,34 @@ struct UnmaskStepParams {
 int check_unmask_select(const UnmaskStepParams& p);  // the argument checks of the launch alone: 0 or CWM_ERR_INVALID with a message
 int launch_unmask_select(const UnmaskStepParams& p, hipStream_t stream);
 
+// One step of Spelke-object segmentation (segment.hip; the definition: include/cwm_hip.h cwm_segment_step): seed references, votes over the S flow samples, the
+// 4-connected region of the candidates that hangs on the seed cell, per-patch coverage and the active / passive picks of the next round of counterfactuals.
+// No allocation, no synchronisation, no atomics.
+constexpr int kSegmentMaxSamples = 255;   // votes are bytes
+constexpr int kSegmentMaxPixels = 1 << 18;
+constexpr int kSegmentMaxWords = 8192;    // H ceil(W / 32) words per bitmap: two bitmaps of a row in 64 KiB of LDS
+constexpr int kSegmentMaxPicks = 64;
+struct SegmentStepParams {
+    const float* f;          // flows by five element strides, or nullptr: the init step (S = 0)
+    int64_t sb, sc, sh, sw, ss;
+    int B, H, W, S, P;
+    const int* seeds;        // [B][2] (y, x), clamped on the device
+    const float* dirs;       // [S][2] (dy, dx) or nullptr
+    float min_seed_mag, abs_thresh, rel_thresh, vote_frac, cos_min, inside_frac;
+    int k_active, k_passive, ring_radius;
+    const float* keys;       // [B][2][n] or nullptr
+    float* seed_ref;         // [B][S]: ref_s, NaN where the sample is not valid
+    uint8_t* votes;          // [B][H W]
+    uint8_t* segment;        // [B][H W] or nullptr
+    float* cover;            // [B][n] or nullptr
+    int* stats;              // [B][4] or nullptr
+    int* picks;              // [B][k_active + k_passive] or nullptr
+    uint8_t* active_out;     // [B][2 n] or nullptr
+    uint8_t* passive_out;    // [B][2 n] or nullptr
+};
+int check_segment_step(const SegmentStepParams& p);  // 0 or CWM_ERR_INVALID with a message that names the field
+int launch_segment_step(const SegmentStepParams& p, hipStream_t stream);
+
 struct ShiftPromptParams {
     const float* x;         // [B][T][C][H][W] contiguous frames
     int B, S, T, C, H, W, P, frame, fix_passive;

@@ -2,34 +2,16 @@
 // masked cells of every batch row -- all of one row's state in the LDS of one workgroup.
 #include "common.h"
 #include "kernels.h"
+#include "select_order.h"
 #include <climits>
 
 namespace cwm {
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kSelThreads;
+static_assert(kUnmaskMaxCells == kSelMaxCells, "the rank word keeps the cell index in 12 bits");
 constexpr unsigned kNoGap = 0xFFFFu;  // no visible cell in the column (a real gap is below h <= 1365)
-
-// Orders fp32 keys as torch.sort(descending=True) does: a NaN above every number, -0 equal to +0.
-__device__ __forceinline__ unsigned um_order(float v) {
-    if (v != v) return 0xFFFFFFFFu;
-    if (v == 0.f) v = 0.f;
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ unsigned long long um_max64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
-
-// The maximum of v over the workgroup, in every thread: xor shuffles within a wave, one LDS exchange between the four waves.  `xch` has 4 slots and may be
-// reused after the call returns only behind another barrier (the callers alternate two sets).
-__device__ __forceinline__ unsigned long long um_block_max(unsigned long long v, unsigned long long* xch) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = um_max64(v, (unsigned long long)__shfl_xor((long long)v, o, 64));
-    if ((threadIdx.x & 63) == 0) xch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return um_max64(um_max64(xch[0], xch[1]), um_max64(xch[2], xch[3]));
-}
 
 }  // namespace
 
@@ -99,22 +81,15 @@ __global__ __launch_bounds__(kThreads) void unmask_select_kernel(const UnmaskSte
             float key = erow[c];
             if (rrow) key = key * rrow[c];
             if (p.race) key = key != key ? key : __fdiv_rn(fmaxf(key, 0.f), p.e[(size_t)b * n + c]);
-            w = ((unsigned long long)(front ? 2 : 1) << 44) | ((unsigned long long)um_order(key) << 12) | (unsigned long long)(kUnmaskMaxCells - 1 - c);
+            w = um_rank(front ? 2 : 1, key, c);
         }
         comp[c] = w;
         best = um_max64(best, w);
     }
-    for (int r = 0; r < p.k; ++r) {
-        const unsigned long long win = um_block_max(best, xch[(r + 1) & 1]);
-        const int cell = win ? kUnmaskMaxCells - 1 - (int)(win & (kUnmaskMaxCells - 1)) : -1;
+    um_select_rounds(comp, n, p.k, best, xch, [&](int r, int cell) {
         if (tid == 0 && p.picks) p.picks[(size_t)b * p.k + r] = cell < 0 ? -1 : p.frame * n + cell;
-        if (cell >= 0 && (cell & (kThreads - 1)) == tid) {  // the owner clears the cell and scans its cells again
-            comp[cell] = 0;
-            m[cell] = 0;
-            best = 0;
-            for (int c = tid; c < n; c += kThreads) best = um_max64(best, comp[c]);
-        }
-    }
+        if (cell >= 0 && (cell & (kThreads - 1)) == tid) m[cell] = 0;  // the owner clears the cell
+    });
     if (p.mask_out) {
         __syncthreads();
         const uint8_t* src = p.mask + b * Nt;

@@ -6,9 +6,9 @@ flow samples.  Same names, argument meaning and output shape
                                 FlowGenerator.compute_flow_corrs             :479-547
     cwm/interface.py            compute_flow_cov = partial(compute_flow_corrs, use_covariance=True)  :27-29
 
-All arithmetic runs in `libcwm_hip.so` (flowstats.hip); there is no CPU fallback.  Options of `compute_flow_corrs` the demo
-and interface never switch on (Spearman ranks, thresholds, z-scoring, a custom distance function) raise NotImplementedError
-instead of silently computing something else.
+All arithmetic runs in `libcwm_hip.so` (flowstats.hip); there is no CPU fallback.  The options of `compute_flow_corrs` the demo
+and interface never switch on -- Spearman ranks, the three threshold modes, normalisation and z-scoring -- run on the device too
+(`cwm_flow_transform`); a caller's own `distance_func` is the caller's PyTorch code and runs as PyTorch, its result goes to the kernels.
 
 Sharded form (samples spread over the ranks, as the prompt-sharding driver leaves them): `dist.sharded_flow_corrs` and
 `dist.sharded_mean_motion_map` -- every rank computes the small feature matrix of its own samples, the features are

@@ -408,6 +408,65 @@ class FlowGenerator(PredictorBasedGenerator):
         valid = torch.from_numpy(res.mass > min_mass).to(x.device)
         return flow.view(hh, ww, 2).permute(2, 0, 1).contiguous(), valid.view(hh, ww)
 
+    # ---- Spelke-object segmentation (the reference's README names the use and lists the algorithm as "coming soon"): segment_step.py, csrc/segment.hip ----
+    _SEGMENT_KEYS = ("min_seed_mag", "abs_thresh", "rel_thresh", "vote_frac", "cos_min", "inside_frac", "ring_radius")
+
+    def segment_step(self, flows, seeds, *, min_seed_mag, abs_thresh, rel_thresh=0.5, vote_frac=0.5, dirs=None, cos_min=0.0, k_active=0, k_passive=0,
+                     inside_frac=1.0, ring_radius=1, keys=None, shape=None):
+        """From S counterfactual flows [B,2,H,W,S] and a seed pixel (y, x) per row to the connected region that moves with the seed: the pixels whose flow
+        magnitude reaches max(abs_thresh, rel_thresh * the seed patch's mean magnitude) (and, with `dirs` [S,2] (dy, dx), points within acos(cos_min) of the
+        sample's direction) in at least vote_frac of the samples in which the seed patch itself moved by min_seed_mag, cut down to the 4-connected part that
+        hangs on the seed's patch.  Returns a `SegmentStepResult` (segment, votes, cover, stats, seed_ref and, with k_active > 0, the active / passive masks
+        and picks of the next round: the seed's patch and the k_active - 1 first patches covered to `inside_frac`, the k_passive first untouched patches within
+        `ring_radius` of a touched one; `keys` [B,2,n] rank them, default index order).  Device tensors take one library call (cwm_segment_step; the
+        `_batch_to_samples` view without a copy, nothing read back), CPU tensors the same definition in torch.  flows=None with shape=(B, H, W) is the init
+        step: an empty segment, the seed's patch alone active."""
+        from . import segment_step as SS
+
+        return SS.segment_step(flows, seeds, self.patch_size[-1], min_seed_mag=min_seed_mag, abs_thresh=abs_thresh, rel_thresh=rel_thresh, vote_frac=vote_frac,
+                               dirs=dirs, cos_min=cos_min, k_active=k_active, k_passive=k_passive, inside_frac=inside_frac, ring_radius=ring_radius, keys=keys,
+                               shape=shape)
+
+    def segment_spelke_object(self, x, seeds, num_iters=3, num_samples=8, shift=1, k_active=4, k_passive=4, sample=False, generator=None,
+                              sample_batch_size=None, return_trace=False, **kwargs):
+        """The Spelke object under a seed pixel of every movie of x [B,T,C,H,W], seeds [B,2] (y, x): move the seed's patch in S = num_samples directions, segment
+        what moves with it, then `num_iters - 1` more times move k_active patches inside the segment and pin k_passive just outside it, and segment again.
+        The directions are `segment_step.directions(S, shift)`: the 8 compass shifts of `shift` patches in the order E, S, W, N, SE, SW, NW, NE, cycled to S.
+        Every iteration is one `predict_counterfactual_videos_and_flows` (fix_passive=True, the masks expanded over the samples) and one `segment_step` on the
+        `_batch_to_samples` view with `dirs` = the shifts in pixels; iteration 0 takes its masks from the init step.  sample=True ranks the picks by keys
+        drawn per iteration with torch.rand((B,2,n), generator=generator) on x's device instead of by index.  The thresholds of `segment_step` (default:
+        min_seed_mag = abs_thresh = 1 pixel) are taken from the keywords, the rest goes to the counterfactual driver (raft_iters, timestamps, ...).  Seeds,
+        masks and picks stay on x's device: the loop reads nothing back beyond what the counterfactual driver does.
+        Returns (segment [B,H,W] bool, vote fraction [B,H,W] = votes / max(n_valid, 1)) of the last iteration and, with return_trace, a list of each
+        iteration's (SegmentStepResult, active [B,Nt], passive [B,Nt]) -- the masks that iteration's counterfactuals were made with."""
+        from . import segment_step as SS
+
+        if int(k_active) < 1 or int(num_iters) < 1 or int(num_samples) < 1:
+            raise ValueError("segment_spelke_object: k_active, num_iters and num_samples must be at least 1")
+        step_kw = {"min_seed_mag": 1.0, "abs_thresh": 1.0}
+        step_kw.update({k: kwargs.pop(k) for k in self._SEGMENT_KEYS if k in kwargs})
+        movie, _ = self._two_frame_movie(x, True)
+        B, (H, W) = movie.shape[0], movie.shape[-2:]
+        P, S, dev = self.patch_size[-1], int(num_samples), movie.device
+        n = (H // P) * (W // P)
+        seeds = torch.as_tensor(seeds).to(device=dev, dtype=torch.int32).reshape(B, 2)
+        shifts = SS.directions(S, shift)
+        dirs = torch.tensor([(dy * P, dx * P) for dy, dx in shifts], dtype=torch.float32).to(dev)
+        res = self.segment_step(None, seeds, k_active=k_active, k_passive=k_passive, shape=(B, H, W), **step_kw)
+        active, passive = res.active, res.passive
+        trace = []
+        # the counterfactual driver rectangularises its masks on torch's global CPU generator; the caller's stream of draws is put back as it was
+        with torch.random.fork_rng(devices=[]):
+            for _ in range(int(num_iters)):
+                _, flows = self.predict_counterfactual_videos_and_flows(x, active.unsqueeze(-1).expand(-1, -1, S), passive.unsqueeze(-1).expand(-1, -1, S),
+                                                                        shifts=shifts, num_samples=S, sample_batch_size=sample_batch_size, fix_passive=True, **kwargs)
+                keys = torch.rand((B, 2, n), generator=generator, device=dev) if sample else None
+                res = self.segment_step(self._batch_to_samples(flows), seeds, dirs=dirs, k_active=k_active, k_passive=k_passive, keys=keys, **step_kw)
+                trace.append((res, active, passive))
+                active, passive = res.active, res.passive
+        frac = res.votes.float() / res.stats[:, 0].clamp(min=1).float()[:, None, None]
+        return (res.segment, frac, trace) if return_trace else (res.segment, frac)
+
     # ---- statistics over the flow samples (segmentation.py:250-276, 479-547): device kernels, see flowstats.py ----------
     def compute_flow_samples_magnitude(self, flows, normalize=True, dim=-4, eps=1e-2):
         from . import flowstats

@@ -376,6 +376,58 @@ typedef struct cwm_unmask_step_args {
  * a message, before anything is launched. */
 CWM_API int cwm_unmask_step(const cwm_unmask_step_args* args);
 
+typedef struct cwm_segment_step_args {
+    uint32_t struct_size;            /* sizeof(cwm_segment_step_args); anything else: CWM_ERR_INVALID naming struct_size */
+    /* read: batch, T (must be 2), H, W, P and stream.  Every other field of base is ignored, base.struct_size included */
+    cwm_patch_error_args base;
+    const float* flows_dev;          /* f[b][c][y][x][s] at flows_dev[b st[0] + c st[1] + y st[2] + x st[3] + s st[4]] (elements), st = flow_strides, as
+                                      * cwm_flow_filter_stats takes them; NULL (with S = 0) is the init step */
+    int64_t flow_strides[5];
+    int32_t C, S;                    /* C = 2 (0: x-displacement, 1: y-displacement); 1 <= S <= 255 */
+    const int32_t* seeds_dev;        /* [B, 2] (y, x) pixels, clamped into the image on the device */
+    const float* dirs_dev;           /* [S, 2] (dy, dx), shared by all rows, or NULL: no direction test */
+    float min_seed_mag, abs_thresh, rel_thresh, vote_frac, cos_min, inside_frac;  /* vote_frac must not be a NaN */
+    int32_t k_active, k_passive;     /* 0 .. 64 each; k_active = 0: no selection (k_passive is ignored) */
+    int32_t ring_radius;             /* >= 1, in cells */
+    const float* keys_dev;           /* [B, 2, n]: [b][0] ranks the active picks, [b][1] the passive ones; NULL = every key 0 (index order) */
+    float* seed_ref_dev;             /* out [B, S], required with flows (the vote pass reads it): ref_s, a NaN where sample s is not valid */
+    uint8_t* votes_dev;              /* out [B, H, W], required with flows (the component pass reads it); optional in the init step, which writes zeros */
+    uint8_t* segment_dev;            /* out [B, H, W] 0 / 1, or NULL */
+    float* cover_dev;                /* out [B, H/P, W/P] or NULL */
+    int32_t* stats_dev;              /* out [B, 4] or NULL: n_valid, area, n_candidates, seed_hit */
+    int32_t* picks_dev;              /* out [B, k_active + k_passive] or NULL: n + cell (tokens of frame 1), active picks first; -1: the slot found no cell */
+    uint8_t* active_out_dev;         /* out [B, 2 n] or NULL: frame 0 all 0, frame 1 all 1 with the active picks cleared (0 = active) */
+    uint8_t* passive_out_dev;        /* out [B, 2 n] or NULL: the same with the passive picks cleared (0 = passive and visible) */
+} cwm_segment_step_args;
+
+/* One step of Spelke-object segmentation: from the S counterfactual flows of a seed point to the connected region that moves with it, and to the patches the
+ * next round of counterfactuals moves and pins -- on the device, without a read-back.  No counterpart in the reference, whose README names the use ("asking which
+ * points would also move along with a selected point is a way of segmenting a scene into independently movable Spelke objects") and lists the algorithm as coming.
+ *   With gh = H/P, gw = W/P, n = gh gw, Nt = 2 n, per row b, in this order:
+ *   1 magnitude   m_s(p) = sqrtf(u u + v v) of sample s at pixel p (u: channel 0, v: channel 1): the flow-sample filter's form
+ *   2 seed cell   (y, x) = seeds[b] clamped into [0, H-1] x [0, W-1];  c0 = (y/P) gw + x/P
+ *   3 seed ref    ref_s = (sum of m_s over the P P pixels of cell c0 in row-major order, from 0.f, plain fp32 adds by one thread) / (float)(P P)
+ *   4 valid       sample s is valid iff ref_s >= min_seed_mag (a NaN is not); n_valid = their number
+ *   5 votes       pixel p votes in a valid sample s iff m_s(p) >= fmaxf(abs_thresh, rel_thresh * ref_s) (fmaxf: a NaN operand is ignored) and, with dirs,
+ *                 u dx + v dy >= (cos_min * m_s(p)) * sqrtf(dx dx + dy dy); a NaN compares false.  votes[p] = the number of samples p votes in
+ *   6 candidates  need = max(1, (int)ceilf(vote_frac * (float)n_valid));  candidate[p] = n_valid > 0 && votes[p] >= need
+ *   7 segment     the union of the 4-connected components of `candidate` that hold a candidate pixel of cell c0; empty when the cell has none (seed_hit 0 / 1)
+ *   8 cover       cover[cell] = (#segment pixels of the cell) / (float)(P P): exact
+ *   9 stats       (n_valid, area = #segment pixels, n_candidates, seed_hit)
+ *  10 selection   only when k_active > 0.  inside[cell] = cover >= inside_frac; touched = cover > 0; ring[cell] = !touched and some touched cell lies within
+ *                 Chebyshev distance ring_radius.  Order: the rule of cwm_unmask_step -- the higher key first, a NaN above every number, -0 equal to +0, the
+ *                 lower index first.  Active picks: c0 first and always, then the first k_active - 1 inside cells other than c0.  Passive picks: the first
+ *                 k_passive ring cells.  active_out / passive_out / picks as described at their fields (the convention of cwm_prompt_table_expand).
+ *  11 init step   flows_dev == NULL: no flows, an empty segment -- active_out holds c0 alone, passive_out nothing, votes / segment / cover / stats are zeros.
+ * Three passes: the seed references (one thread per (b, s)); the votes (many workgroups stream the flows once; coalesced for the sample-outermost view of the
+ * flow model's output and for the packed [B,2,H,W,S] layout, any other strides take a strided form); then one workgroup per row holds the candidate and reached
+ * bitmaps in LDS as bit rows, fills components by whole-word sweeps (bounded by H W + 1 sweeps whatever the input), counts coverage and selects.
+ * Asynchronous on base.stream: nothing is allocated, the host is not synchronised, no atomics, fixed order -- two calls on the same inputs give the same bits.
+ * No content of a device table (seeds, flows, keys, NaN or inf among them) makes the call read or write outside its buffers.
+ * Limits: C = 2; P 4, 8 or 16; H % P == 0, W % P == 0; H W <= 2^18 and H ceil(W / 32) <= 8192 (the bit rows); 1 <= S <= 255, or S = 0 with NULL flows; n <= 4096;
+ * k_active, k_passive <= 64; ring_radius >= 1.  Argument errors: CWM_ERR_INVALID with a message that names the field, before anything is launched. */
+CWM_API int cwm_segment_step(const cwm_segment_step_args* args);
+
 /* `RectangularizeMasks` (masking.py:90-132) on device masks without reading them back.  The reference equalises the masked count of
  * the rows of a batch by un-masking / masking `torch.randperm(#candidates)[:surplus]` of a row's masked / visible tokens (one draw of the global CPU
  * generator per changed row, in row order).  The draws depend on the per-row COUNTS alone, so:
