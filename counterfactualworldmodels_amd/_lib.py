@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+from functools import partial
 from typing import Optional
 
 import torch  # noqa: F401  (loads libamdhip64 first; see module docstring)
@@ -274,10 +275,17 @@ class CwmRaftForwardArgs(C.Structure):
     ]
 
 
-def new_raft_forward_args() -> CwmRaftForwardArgs:
-    a = CwmRaftForwardArgs()
-    a.struct_size = C.sizeof(CwmRaftForwardArgs)
+def new_args(cls):
+    """a zeroed args structure with its struct_size set, and its base's where it embeds another args structure as `base` (the read-outs' cwm_patch_error_args,
+    cwm_raft_forward_ex_args' cwm_raft_forward_args)"""
+    a = cls()
+    a.struct_size = C.sizeof(cls)
+    if hasattr(a, "base"):
+        a.base.struct_size = C.sizeof(type(a.base))
     return a
+
+
+new_raft_forward_args = partial(new_args, CwmRaftForwardArgs)
 
 
 class CwmRaftForwardExArgs(C.Structure):
@@ -296,11 +304,7 @@ class CwmRaftForwardExArgs(C.Structure):
     ]
 
 
-def new_raft_forward_ex_args() -> CwmRaftForwardExArgs:
-    a = CwmRaftForwardExArgs()
-    a.struct_size = C.sizeof(CwmRaftForwardExArgs)
-    a.base.struct_size = C.sizeof(CwmRaftForwardArgs)
-    return a
+new_raft_forward_ex_args = partial(new_args, CwmRaftForwardExArgs)
 
 
 class CwmDevConvSrc(C.Structure):
@@ -409,10 +413,7 @@ class CwmDevGatherArgs(C.Structure):
     ]
 
 
-def new_dev_gather_args() -> CwmDevGatherArgs:
-    a = CwmDevGatherArgs()
-    a.struct_size = C.sizeof(CwmDevGatherArgs)
-    return a
+new_dev_gather_args = partial(new_args, CwmDevGatherArgs)
 
 
 DEV_CONJ_VALU, DEV_CONJ_MFMA = 0, 1
@@ -589,57 +590,43 @@ DEV_FLOW_ZERO_PLANES, DEV_FLOW_ZERO_PLANES_VEC, DEV_FLOW_ZERO_SCATTER = range(3)
 DEV_FLOW_PACK_TRANSPOSE = 0
 
 
-def new_dev_conj_args(cls):
-    """a zeroed cwm_dev_*_args of the given structure class (conj, gemm, attention, layernorm) with its struct_size set"""
-    a = cls()
-    a.struct_size = C.sizeof(cls)
-    return a
-
-
-def new_dev_raft_conv_args() -> CwmDevRaftConvArgs:
-    a = CwmDevRaftConvArgs()
-    a.struct_size = C.sizeof(CwmDevRaftConvArgs)
-    return a
-
-
-def new_forward_args() -> CwmForwardArgs:
-    a = CwmForwardArgs()
-    a.struct_size = C.sizeof(CwmForwardArgs)
-    return a
-
-
-def new_patch_error_args() -> CwmPatchErrorArgs:
-    a = CwmPatchErrorArgs()
-    a.struct_size = C.sizeof(CwmPatchErrorArgs)
-    return a
-
-
-def new_token_response_args() -> CwmTokenResponseArgs:
-    a = CwmTokenResponseArgs()
-    a.struct_size = C.sizeof(CwmTokenResponseArgs)
-    a.base.struct_size = C.sizeof(CwmPatchErrorArgs)
-    return a
-
-
-def new_unmask_step_args() -> CwmUnmaskStepArgs:
-    a = CwmUnmaskStepArgs()
-    a.struct_size = C.sizeof(CwmUnmaskStepArgs)
-    a.base.struct_size = C.sizeof(CwmPatchErrorArgs)
-    return a
+new_dev_conj_args = new_args  # (a cwm_dev_*_args of the given structure class: conj, gemm, attention, layernorm)
+new_dev_raft_conv_args = partial(new_args, CwmDevRaftConvArgs)
+new_forward_args = partial(new_args, CwmForwardArgs)
+new_patch_error_args = partial(new_args, CwmPatchErrorArgs)
+new_token_response_args = partial(new_args, CwmTokenResponseArgs)
+new_unmask_step_args = partial(new_args, CwmUnmaskStepArgs)
 
 
 def new_segment_step_args() -> CwmSegmentStepArgs:
-    a = CwmSegmentStepArgs()
-    a.struct_size = C.sizeof(CwmSegmentStepArgs)
-    a.base.struct_size = C.sizeof(CwmPatchErrorArgs)
+    a = new_args(CwmSegmentStepArgs)
     a.base.T = 2
     return a
 
 
-def new_conj_forward_args() -> CwmConjForwardArgs:
-    a = CwmConjForwardArgs()
-    a.struct_size = C.sizeof(CwmConjForwardArgs)
-    return a
+def fill_patch_args(g, *, x=None, target=None, mask=None, region=None, y=None, geometry, n_vis=0, frame=-1, map=None, mean=None, scratch=None, stream):
+    """Fills a cwm_patch_error_args -- alone, or the `.base` of the other read-outs' -- from tensors: the one place that knows its field order.  `x` and `target`
+    are [B,T,C,H,W]-SHAPED views of any (b, t, c) strides, whatever the order of the tensor beneath ([B,C,T,H,W] permuted, a batch stride of 0); their image
+    rows must be contiguous (ValueError otherwise: the kernels address a pixel as y W + x).  geometry = (B, T, C, H, W, P).  Only addresses are stored: the
+    caller keeps the tensors alive until the call has been queued.  Returns g."""
+    def frames(name, v):
+        if v is None:
+            return None, 0, 0, 0
+        if v.dim() != 5 or v.stride(-1) != 1 or v.stride(-2) != v.shape[-1]:
+            raise ValueError("fill_patch_args: %s must be a [B,T,C,H,W]-shaped view with contiguous image rows, got shape %s strides %s" % (
+                name, tuple(v.shape), v.stride()))
+        return v.data_ptr(), v.stride(0), v.stride(1), v.stride(2)
+
+    g.x_dev, g.x_stride_b, g.x_stride_t, g.x_stride_c = frames("x", x)
+    g.target_dev, g.target_stride_b, g.target_stride_t, g.target_stride_c = frames("target", target)
+    g.y_tokens_dev, g.mask_dev, g.region_dev = ptr(y), ptr(mask), ptr(region)
+    g.batch, g.T, g.C, g.H, g.W, g.P = geometry
+    g.n_vis, g.frame = n_vis, frame
+    g.map_dev, g.mean_dev, g.scratch_dev, g.stream = ptr(map), ptr(mean), ptr(scratch), stream
+    return g
+
+
+new_conj_forward_args = partial(new_args, CwmConjForwardArgs)
 
 
 class CwmKernelStats(C.Structure):

@@ -16,6 +16,11 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 // NB: use this native vector (not HIP's struct uint4) for register-staged tiles: arrays of the HIP
 // struct types are not promoted to registers by hipcc and end up in scratch.
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+// Four floats at an address that is only 4-byte aligned: what the generic un-embed and read-out kernels move (C != 3, a pointer off the 16-byte grid, strides
+// that are no multiple of 4), so their groups of four pixels may start at any float.
+struct __attribute__((packed, aligned(4))) Float4A4 {
+    float v[4];
+};
 
 constexpr int kWave = 64;
 

@@ -528,13 +528,7 @@ int launch_iota(int* perm, int n, hipStream_t stream) {
 // `Patchify` (patches.py:74,98-102): feature index f = (ph*P + pw)*C + c; visible patches take the
 // RAW (un-normalised) wrapper input.  One thread per 4 horizontally adjacent output pixels.
 // ---------------------------------------------------------------------------------------------
-// Four floats at an address that is only 4-byte aligned: what the generic kernel below moves.  It is the form for everything unembed3_kernel refuses --
-// C != 3, a frame or output pointer off the 16-byte grid, batch / time / channel strides that are no multiple of 4 -- so its groups of four pixels may
-// start at any float.
-struct __attribute__((packed, aligned(4))) Float4A4 {
-    float v[4];
-};
-
+// (the generic kernel below is the form for everything unembed3_kernel refuses: it moves Float4A4, common.h)
 __global__ __launch_bounds__(256) void unembed_kernel(const UnembedParams p) {
     const int w4 = p.W / 4;
     const int64_t total = (int64_t)p.B * p.T * p.C * p.H * w4;
@@ -622,354 +616,6 @@ int launch_unembed(const UnembedParams& p, hipStream_t stream) {
     const int64_t total = (int64_t)p.B * p.T * p.C * p.H * (p.W / 4);
     hipLaunchKernelGGL(unembed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p);
     CWM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Per-patch prediction error straight from the predicted tokens: `get_error_on_target_region` (prediction.py:553-574) = `_get_error` (:324-329; MSELoss
-// summed over the channels) of `pred_patches_to_video` (:245-259) against the target frames, avg_pool3d over each patch, times the region, averaged --
-// without the predicted video.  map[b][t][i][j] = (1 / P^2) sum over the pixels of patch (i, j) and the channels of (pred_f - target_t)^2, where pred_f is
-// frame f = `frame` (or t: frame < 0) of that video: y at the masked patches of frame f, x at its visible ones.
-//
-// One workgroup per (b, t, patch row i): P image rows of W pixels.  An item is 4 horizontally adjacent pixels of one image row, ALL channels: consecutive
-// lanes read consecutive 16 bytes of an image row of x / target (whole 128-byte lines per wave and channel) and consecutive 16 C bytes of a token of y.  The
-// y row of a masked token is its rank among the row's masked tokens, counted here (the mask bytes in front of the patch row: an integer sum, any order)
-// and clamped into [0, Nm).  Every float sum has a fixed order: an item's 4 C squares in sequence, the items of a patch from LDS in (ph, x) order by one lane.
-// ---------------------------------------------------------------------------------------------
-template <bool A16>
-__device__ __forceinline__ float4 pe_load4(const float* p) {
-    if (A16) return *reinterpret_cast<const float4*>(p);
-    const Float4A4 v = *reinterpret_cast<const Float4A4*>(p);
-    return make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
-}
-
-__device__ __forceinline__ float pe_sq4(float s, const float4& a, const float4& b) {
-    const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z, d3 = a.w - b.w;
-    s += d0 * d0;
-    s += d1 * d1;
-    s += d2 * d2;
-    s += d3 * d3;
-    return s;
-}
-
-// FAST: C == 3 and every pointer and stride on the 16-byte grid (three aligned 16-byte loads of a token's 12 floats, transposed in registers as unembed3_kernel does)
-template <bool FAST>
-__global__ __launch_bounds__(256) void patch_error_map_kernel(const PatchErrorParams p, float* map) {
-    extern __shared__ __align__(16) float pe_lds[];
-    const int gw = p.W / p.P, gh = p.H / p.P, n = gh * gw, Nt = p.T * n;
-    const int w4 = p.W / 4, items = p.P * w4;
-    float* part = pe_lds;                                  // [P][W / 4]: one partial sum per item
-    int* yrow = reinterpret_cast<int*>(pe_lds + items);    // [gw]: y row of patch j, -1 = visible
-    int* cnt = yrow + gw;                                  // [4]: masked tokens in front of the patch row, per wave
-    int r = blockIdx.x;
-    const int i = r % gh; r /= gh;
-    const int t = r % p.T;
-    const int b = r / p.T;
-    const int f = p.frame < 0 ? t : p.frame;
-    const uint8_t* mrow = p.mask + (size_t)b * Nt;
-    const int tau0 = f * n + i * gw;
-    int c0 = 0;
-    for (int k = threadIdx.x; k < tau0; k += 256) c0 += mrow[k] != 0;
-#pragma unroll
-    for (int o = 32; o; o >>= 1) c0 += __shfl_down(c0, o, 64);
-    if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c0;
-    __syncthreads();
-    if ((int)threadIdx.x < gw) {
-        int rk = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-        for (int k = 0; k < (int)threadIdx.x; ++k) rk += mrow[tau0 + k] != 0;
-        // (whatever the mask holds, the row read lies in [0, Nm); with Nm = 0 there is no y and every patch is taken from x)
-        yrow[threadIdx.x] = (mrow[tau0 + threadIdx.x] != 0 && p.Nm > 0) ? min(rk, p.Nm - 1) : -1;
-    }
-    __syncthreads();
-    const float* xb = p.x + b * p.sb + f * p.st;
-    const float* tg = p.target ? p.target + b * p.tb + t * p.tt : p.x + b * p.sb + t * p.st;
-    const int64_t tc = p.target ? p.tc : p.sc;
-    const bool same = xb == tg && tc == p.sc;  // the target IS the frame the visible patches come from: their error is exactly 0, nothing to read
-    const int PPC = p.P * p.P * p.C;
-    for (int it = threadIdx.x; it < items; it += 256) {
-        const int ph = it / w4, x0 = (it - ph * w4) * 4;
-        const int jr = yrow[x0 / p.P];
-        const int64_t off = (int64_t)(i * p.P + ph) * p.W + x0;
-        float s = 0.f;
-        if (jr >= 0) {
-            const float* yp = p.y + ((size_t)b * p.Nm + jr) * PPC + (ph * p.P + (x0 % p.P)) * p.C;
-            if (FAST) {
-                const float4* y4 = reinterpret_cast<const float4*>(yp);
-                const float4 a = y4[0], bb = y4[1], c = y4[2];  // px0 (r g b) px1 (r | g b) px2 (r g | b) px3 (r g b)
-                s = pe_sq4(s, make_float4(a.x, a.w, bb.z, c.y), pe_load4<true>(tg + off));
-                s = pe_sq4(s, make_float4(a.y, bb.x, bb.w, c.z), pe_load4<true>(tg + off + tc));
-                s = pe_sq4(s, make_float4(a.z, bb.y, c.x, c.w), pe_load4<true>(tg + off + 2 * tc));
-            } else {
-                for (int c = 0; c < p.C; ++c)
-                    s = pe_sq4(s, make_float4(yp[c], yp[p.C + c], yp[2 * p.C + c], yp[3 * p.C + c]), pe_load4<false>(tg + off + c * tc));
-            }
-        } else if (!same) {
-            for (int c = 0; c < p.C; ++c) s = pe_sq4(s, pe_load4<FAST>(xb + off + c * p.sc), pe_load4<FAST>(tg + off + c * tc));
-        }
-        part[it] = s;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < gw) {
-        const int q = p.P / 4;
-        float s = 0.f;
-        for (int ph = 0; ph < p.P; ++ph)
-            for (int k = 0; k < q; ++k) s += part[ph * w4 + threadIdx.x * q + k];
-        map[(((size_t)b * p.T + t) * gh + i) * gw + threadIdx.x] = s / (float)(p.P * p.P);
-    }
-}
-
-// mean[b] = sum(map * region) / max(sum(region), 1) (prediction.py:570-573): one workgroup per batch row, lane k sums elements k, k + 256, ... in order, then
-// a halving tree over LDS -- the same order on every call
-__global__ __launch_bounds__(256) void patch_error_mean_kernel(const float* map, const float* region, int n_el, float* mean) {
-    __shared__ float num[256], den[256];
-    const int b = blockIdx.x;
-    float sn = 0.f, sd = 0.f;
-    for (int k = threadIdx.x; k < n_el; k += 256) {
-        const float rg = region ? region[(size_t)b * n_el + k] : 1.f;
-        sn += map[(size_t)b * n_el + k] * rg;
-        sd += rg;
-    }
-    num[threadIdx.x] = sn;
-    den[threadIdx.x] = sd;
-    __syncthreads();
-    for (int o = 128; o; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            num[threadIdx.x] += num[threadIdx.x + o];
-            den[threadIdx.x] += den[threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) mean[b] = num[0] / fmaxf(den[0], 1.f);
-}
-
-int launch_patch_error(const PatchErrorParams& p, hipStream_t stream) {
-    CWM_REQUIRE(p.x && p.mask && p.B > 0 && p.T > 0 && p.C > 0 && p.C <= 8 && p.H > 0 && p.W > 0, "patch_error: bad argument");
-    CWM_REQUIRE((p.P == 4 || p.P == 8 || p.P == 16) && p.H % p.P == 0 && p.W % p.P == 0, "patch_error: patches of 4, 8 or 16 pixels that divide the image, got P = %d for %d x %d", p.P,
-                p.H, p.W);
-    const int gh = p.H / p.P, gw = p.W / p.P;
-    const int64_t Nt = (int64_t)p.T * gh * gw;
-    CWM_REQUIRE(p.n_vis >= 0 && p.n_vis <= Nt && p.Nm == Nt - p.n_vis, "patch_error: n_vis = %d, Nm = %d of %lld tokens", p.n_vis, p.Nm, (long long)Nt);
-    CWM_REQUIRE(p.y || p.Nm == 0, "patch_error: the predicted tokens are required when a token is masked");
-    CWM_REQUIRE(p.frame >= -1 && p.frame < p.T, "patch_error: frame = %d of %d (-1: each)", p.frame, p.T);
-    CWM_REQUIRE(p.sb >= 0 && p.st >= 0 && p.sc >= (int64_t)p.H * p.W && (!p.target || (p.tb >= 0 && p.tt >= 0 && p.tc >= (int64_t)p.H * p.W)),
-                "patch_error: channel planes of %d x %d pixels need a stride of at least that, batch and frame strides >= 0", p.H, p.W);
-    CWM_REQUIRE(p.map || p.mean, "patch_error: neither output requested");
-    float* map = p.map ? p.map : p.scratch;
-    CWM_REQUIRE(map, "patch_error: the mean alone needs scratch for the map ([B][T][H / P][W / P] floats)");
-    const size_t lds = ((size_t)p.P * (p.W / 4) + gw + 4) * sizeof(float);
-    CWM_REQUIRE(gw <= 256 && lds <= 48 * 1024 && (int64_t)p.B * p.T * gh < (1ll << 31), "patch_error: image or batch too large (%d patches per row, %d rows)", gw, p.B * p.T * gh);
-    const dim3 grid((unsigned)(p.B * p.T * gh));
-    const auto off16 = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
-    const bool fast = p.C == 3 && !off16(p.y) && !off16(p.x) && !off16(p.target) && p.sb % 4 == 0 && p.st % 4 == 0 && p.sc % 4 == 0 &&
-                      (!p.target || (p.tb % 4 == 0 && p.tt % 4 == 0 && p.tc % 4 == 0));
-    if (fast)
-        hipLaunchKernelGGL(patch_error_map_kernel<true>, grid, dim3(256), lds, stream, p, map);
-    else
-        hipLaunchKernelGGL(patch_error_map_kernel<false>, grid, dim3(256), lds, stream, p, map);
-    CWM_HIP_CHECK(hipGetLastError());
-    if (p.mean) {
-        hipLaunchKernelGGL(patch_error_mean_kernel, dim3((unsigned)p.B), dim3(256), 0, stream, map, p.region, p.T * gh * gw, p.mean);
-        CWM_HIP_CHECK(hipGetLastError());
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Response of a perturbation straight from two sets of predicted tokens (cwm_token_response): r[b][Y][X] = sum_c (y - y_ref)^2 over frame `frame`, 0 where
-// the frame's patch is visible (both predictions copy the same input pixel there); the per-patch mean of r, its first maximum (torch.argmax: a NaN is the
-// maximum, the first NaN wins), its sum and its centroid -- neither predicted video is built, and one location per row is all that leaves the device.
-//
-// One workgroup per (b, patch row i), items and y rows as patch_error_map_kernel: an item is 4 horizontally adjacent pixels of one image row, all channels.
-// Every float sum has a fixed order: a pixel's C squares in channel order from 0.f; a lane's pixels in ascending pixel index; the 256 lanes by a halving
-// tree over LDS; the H / P workgroups of a row in index order by one lane of token_response_fold_kernel.  The maximum is taken with its index (lower index
-// among equal values), so the order it is folded in does not matter.
-// ---------------------------------------------------------------------------------------------
-// does candidate a = (value, pixel index) come before b as torch.argmax sees them?
-__device__ __forceinline__ bool tr_better(float va, int ia, float vb, int ib) {
-    const bool an = va != va, bn = vb != vb;
-    if (an || bn) return an && (!bn || ia < ib);
-    return va > vb || (va == vb && ia < ib);
-}
-
-constexpr int kTokenResponsePartial = 8;  // floats per workgroup partial: peak, its pixel index (int bits), mass, sum r Y, sum r X, 3 unused
-
-// FAST: C == 3 and every pointer and the reference's row stride on the 16-byte grid
-template <bool FAST>
-__global__ __launch_bounds__(256) void token_response_kernel(const TokenResponseParams p) {
-    extern __shared__ __align__(16) float tr_lds[];  // (all of the kernel's LDS: nothing static in front of the dynamic region)
-    const int gw = p.W / p.P, gh = p.H / p.P, n = gh * gw, Nt = p.T * n;
-    const int w4 = p.W / 4, items = p.P * w4;
-    float* part = tr_lds;                                  // [P][W / 4]: one partial sum per item (patch_error_map_kernel's)
-    int* yrow = reinterpret_cast<int*>(tr_lds + items);    // [gw]: y row of patch j, -1 = visible
-    int* cnt = yrow + gw;                                  // [4]: masked tokens in front of the patch row, per wave
-    float* red_v = reinterpret_cast<float*>(cnt + 4);      // [256] each: the lanes' partials (peak, its index, mass, sum r Y, sum r X)
-    int* red_i = reinterpret_cast<int*>(red_v + 256);
-    float *red_m = red_v + 512, *red_y = red_v + 768, *red_x = red_v + 1024;
-    const int i = blockIdx.x % gh, b = blockIdx.x / gh;
-    const uint8_t* mrow = p.mask + (size_t)b * Nt;
-    const int tau0 = p.frame * n + i * gw;
-    int c0 = 0;
-    for (int k = threadIdx.x; k < tau0; k += 256) c0 += mrow[k] != 0;
-#pragma unroll
-    for (int o = 32; o; o >>= 1) c0 += __shfl_down(c0, o, 64);
-    if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c0;
-    __syncthreads();
-    if ((int)threadIdx.x < gw) {
-        int rk = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-        for (int k = 0; k < (int)threadIdx.x; ++k) rk += mrow[tau0 + k] != 0;
-        // (whatever the mask holds, the row read lies in [0, Nm); with Nm = 0 there are no tokens and the response is 0 everywhere)
-        yrow[threadIdx.x] = (mrow[tau0 + threadIdx.x] != 0 && p.Nm > 0) ? min(rk, p.Nm - 1) : -1;
-    }
-    __syncthreads();
-    const int PPC = p.P * p.P * p.C;
-    const bool reduce = p.scratch != nullptr;
-    float bv = -1.f, sm = 0.f, sy = 0.f, sx = 0.f;  // (-1, INT_MAX): behind every pixel, whose response is >= 0 or NaN
-    int bi = 0x7fffffff;
-    for (int it = threadIdx.x; it < items; it += 256) {
-        const int ph = it / w4, x0 = (it - ph * w4) * 4;
-        const int jr = yrow[x0 / p.P];
-        const int Y = i * p.P + ph;
-        float r[4] = {0.f, 0.f, 0.f, 0.f};
-        float s = 0.f;
-        if (jr >= 0) {
-            const size_t tok = (size_t)jr * PPC + (ph * p.P + (x0 % p.P)) * p.C;
-            const float* yp = p.y + (size_t)b * p.Nm * PPC + tok;
-            const float* rp = p.y_ref + (int64_t)b * p.ref_sb + tok;
-            if (FAST) {
-                const float4* y4 = reinterpret_cast<const float4*>(yp);
-                const float4* r4 = reinterpret_cast<const float4*>(rp);
-                const float4 a = y4[0], bb = y4[1], c = y4[2];  // px0 (r g b) px1 (r | g b) px2 (r g | b) px3 (r g b)
-                const float4 ra = r4[0], rb = r4[1], rc = r4[2];
-                const float d[4][3] = {{a.x - ra.x, a.y - ra.y, a.z - ra.z}, {a.w - ra.w, bb.x - rb.x, bb.y - rb.y},
-                                       {bb.z - rb.z, bb.w - rb.w, c.x - rc.x}, {c.y - rc.y, c.z - rc.z, c.w - rc.w}};
-#pragma unroll
-                for (int px = 0; px < 4; ++px)
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) r[px] += d[px][ch] * d[px][ch];
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch)
-#pragma unroll
-                    for (int px = 0; px < 4; ++px) s += d[px][ch] * d[px][ch];
-            } else {
-#pragma unroll
-                for (int px = 0; px < 4; ++px)
-                    for (int ch = 0; ch < p.C; ++ch) {
-                        const float dd = yp[px * p.C + ch] - rp[px * p.C + ch];
-                        r[px] += dd * dd;
-                    }
-                for (int ch = 0; ch < p.C; ++ch)
-                    s = pe_sq4(s, make_float4(yp[ch], yp[p.C + ch], yp[2 * p.C + ch], yp[3 * p.C + ch]),
-                               make_float4(rp[ch], rp[p.C + ch], rp[2 * p.C + ch], rp[3 * p.C + ch]));
-            }
-        }
-        part[it] = s;
-        if (p.pixel_map) {
-            float* dst = p.pixel_map + ((size_t)b * p.H + Y) * p.W + x0;
-            if (FAST) {
-                *reinterpret_cast<float4*>(dst) = make_float4(r[0], r[1], r[2], r[3]);
-            } else {
-#pragma unroll
-                for (int px = 0; px < 4; ++px) dst[px] = r[px];
-            }
-        }
-        if (reduce) {
-#pragma unroll
-            for (int px = 0; px < 4; ++px) {
-                const int idx = Y * p.W + x0 + px;
-                if (tr_better(r[px], idx, bv, bi)) { bv = r[px]; bi = idx; }
-                sm += r[px];
-                sy += r[px] * (float)Y;
-                sx += r[px] * (float)(x0 + px);
-            }
-        }
-    }
-    __syncthreads();
-    if (p.map && (int)threadIdx.x < gw) {
-        const int q = p.P / 4;
-        float s = 0.f;
-        for (int ph = 0; ph < p.P; ++ph)
-            for (int k = 0; k < q; ++k) s += part[ph * w4 + threadIdx.x * q + k];
-        p.map[((size_t)b * gh + i) * gw + threadIdx.x] = s / (float)(p.P * p.P);
-    }
-    if (!reduce) return;  // (uniform: a kernel argument)
-    red_v[threadIdx.x] = bv; red_i[threadIdx.x] = bi;
-    red_m[threadIdx.x] = sm; red_y[threadIdx.x] = sy; red_x[threadIdx.x] = sx;
-    __syncthreads();
-    for (int o = 128; o; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const int u = threadIdx.x, v = threadIdx.x + o;
-            if (tr_better(red_v[v], red_i[v], red_v[u], red_i[u])) { red_v[u] = red_v[v]; red_i[u] = red_i[v]; }
-            red_m[u] += red_m[v];
-            red_y[u] += red_y[v];
-            red_x[u] += red_x[v];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        float* out = p.scratch + ((size_t)b * gh + i) * kTokenResponsePartial;
-        out[0] = red_v[0];
-        out[1] = __int_as_float(red_i[0]);
-        out[2] = red_m[0];
-        out[3] = red_y[0];
-        out[4] = red_x[0];
-    }
-}
-
-// one lane per row: the row's H / P partials in index order
-__global__ __launch_bounds__(64) void token_response_fold_kernel(const float* partials, int B, int gh, int W, int* peak_index, float* stats) {
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= B) return;
-    const float* in = partials + (size_t)b * gh * kTokenResponsePartial;
-    float bv = -1.f, sm = 0.f, sy = 0.f, sx = 0.f;
-    int bi = 0x7fffffff;
-    for (int i = 0; i < gh; ++i, in += kTokenResponsePartial) {
-        const float v = in[0];
-        const int idx = __float_as_int(in[1]);
-        if (tr_better(v, idx, bv, bi)) { bv = v; bi = idx; }
-        sm += in[2];
-        sy += in[3];
-        sx += in[4];
-    }
-    if (peak_index) peak_index[b] = bi;
-    if (stats) {
-        const bool empty = sm == 0.f;  // nothing to weigh the positions with: the peak's own
-        stats[b * 4 + 0] = bv;
-        stats[b * 4 + 1] = sm;
-        stats[b * 4 + 2] = empty ? (float)(bi / W) : sy / sm;
-        stats[b * 4 + 3] = empty ? (float)(bi % W) : sx / sm;
-    }
-}
-
-int launch_token_response(const TokenResponseParams& p, hipStream_t stream) {
-    CWM_REQUIRE(p.mask && p.B > 0 && p.T > 0 && p.C > 0 && p.C <= 8 && p.H > 0 && p.W > 0, "token_response: mask_dev, a positive batch, T, H, W and 1 <= C <= 8 are required");
-    CWM_REQUIRE((p.P == 4 || p.P == 8 || p.P == 16) && p.H % p.P == 0 && p.W % p.P == 0, "token_response: patches of 4, 8 or 16 pixels that divide the image, got P = %d for %d x %d",
-                p.P, p.H, p.W);
-    const int gh = p.H / p.P, gw = p.W / p.P;
-    const int64_t Nt = (int64_t)p.T * gh * gw;
-    CWM_REQUIRE(p.n_vis >= 0 && p.n_vis <= Nt && p.Nm == Nt - p.n_vis, "token_response: n_vis = %d, Nm = %d of %lld tokens", p.n_vis, p.Nm, (long long)Nt);
-    CWM_REQUIRE(p.frame >= 0 && p.frame < p.T, "token_response: frame = %d of %d (one frame, 0 .. T-1)", p.frame, p.T);
-    CWM_REQUIRE((p.y && p.y_ref) || p.Nm == 0, "token_response: y_tokens_dev and y_ref_dev are required when a token is masked");
-    CWM_REQUIRE(p.ref_sb >= 0, "token_response: y_ref_stride_b = %lld must not be negative", (long long)p.ref_sb);
-    CWM_REQUIRE(p.map || p.pixel_map || p.peak_index || p.stats, "token_response: no output requested");
-    const bool reduce = p.peak_index || p.stats;
-    CWM_REQUIRE(!reduce || p.scratch, "token_response: peak_index_dev and stats_dev need scratch for the per-workgroup partials ([B][H / P][8] floats)");
-    const size_t lds = ((size_t)p.P * (p.W / 4) + gw + 4 + 5 * 256) * sizeof(float);
-    CWM_REQUIRE(gw <= 256 && lds <= 48 * 1024 && (int64_t)p.B * gh < (1ll << 31) && (int64_t)p.H * p.W < (1ll << 31),
-                "token_response: image or batch too large (%d patches per row, %lld workgroups)", gw, (long long)p.B * gh);
-    TokenResponseParams q = p;
-    if (!reduce) q.scratch = nullptr;  // (the kernel reduces when it has somewhere to put the partials)
-    const auto off16 = [](const void* ptr) { return ((uintptr_t)ptr & 15) != 0; };
-    const bool fast = p.C == 3 && !off16(p.y) && !off16(p.y_ref) && !off16(p.pixel_map) && p.ref_sb % 4 == 0;
-    const dim3 grid((unsigned)(p.B * gh));
-    if (fast)
-        hipLaunchKernelGGL(token_response_kernel<true>, grid, dim3(256), lds, stream, q);
-    else
-        hipLaunchKernelGGL(token_response_kernel<false>, grid, dim3(256), lds, stream, q);
-    CWM_HIP_CHECK(hipGetLastError());
-    if (reduce) {
-        hipLaunchKernelGGL(token_response_fold_kernel, dim3((unsigned)((p.B + 63) / 64)), dim3(64), 0, stream, (const float*)q.scratch, p.B, gh, p.W, p.peak_index, p.stats);
-        CWM_HIP_CHECK(hipGetLastError());
-    }
     return 0;
 }
 

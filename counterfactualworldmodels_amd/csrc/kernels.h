@@ -2,6 +2,8 @@
 #pragma once
 #include "common.h"
 
+struct cwm_patch_error_args;  // include/cwm_hip.h
+
 namespace cwm {
 
 // Execution options of one model handle (cwm_model_set_option / cwm_conj_set_option) -- every switch that was a process-wide global of the library
@@ -266,7 +268,25 @@ struct UnembedParams {
 
 int launch_unembed(const UnembedParams& p, hipStream_t stream);
 
-// Per-patch squared error of the prediction against target frames, from the predicted tokens (elementwise.hip patch_error_map_kernel):
+// The geometry every token read-out shares (readout.hip, unmask.hip, segment.hip): a batch of T frames of C x H x W pixels cut into P x P patches, n_vis visible
+// tokens per row and Nm = Nt - n_vis predicted ones, and the frame that is read.  patch_grid_of is the only place that derives Nm; check_patch_grid is the only
+// statement of what a geometry must satisfy.  It always checks batch, T, P, H and W; `needs` names what else the caller reads.  Messages start with `who`,
+// which ends in the prefix of the field names ("cwm_segment_step: base." gives "cwm_segment_step: base.P = 5, ...").
+struct PatchGrid {
+    int B, T, C, H, W, P;  // C <= 8, P in {4, 8, 16}
+    int n_vis, Nm;         // Nm = Nt - n_vis rows of y per sample; the row index is clamped into [0, Nm)
+    int frame;
+};
+enum : unsigned {
+    kGridChannels = 1,   // 1 <= C <= 8
+    kGridTokens = 2,     // 0 <= n_vis <= Nt and Nm = Nt - n_vis
+    kGridFrame = 4,      // 0 <= frame < T
+    kGridFrameEach = 8,  // the same, or -1: each frame against its own
+};
+PatchGrid patch_grid_of(const cwm_patch_error_args& a);
+int check_patch_grid(const char* who, const PatchGrid& g, unsigned needs);  // 0 or CWM_ERR_INVALID with a message that names the field
+
+// Per-patch squared error of the prediction against target frames, from the predicted tokens (readout.hip patch_error_map_kernel):
 // map[b][t][i][j] = (1 / P^2) sum_{pixels of patch (i,j)} sum_c (pred_f - target_t)^2, pred_f = frame f of what launch_unembed would build (f = frame, or t when
 // frame < 0); mean[b] = sum(map * region) / max(sum(region), 1).  No allocation, no synchronisation, no atomics: two calls on the same inputs are bit-equal.
 struct PatchErrorParams {
@@ -277,9 +297,7 @@ struct PatchErrorParams {
     int64_t tb, tt, tc;
     const uint8_t* mask;   // [B][Nt]
     const float* region;   // [B][T][H/P][W/P] weights; nullptr = ones
-    int B, T, C, H, W, P;  // C <= 8, P in {4, 8, 16}
-    int n_vis, Nm;         // Nm = Nt - n_vis rows of y per sample; the row index is clamped into [0, Nm)
-    int frame;             // predicted frame compared with EVERY target frame, or -1: frame t with target frame t
+    PatchGrid g;           // frame: the predicted frame compared with EVERY target frame, or -1: frame t with target frame t
     float* map;            // [B][T][H/P][W/P] or nullptr
     float* mean;           // [B] or nullptr
     float* scratch;        // [B][T][H/P][W/P]: holds the map when only the mean is asked for (map == nullptr)
@@ -287,7 +305,7 @@ struct PatchErrorParams {
 
 int launch_patch_error(const PatchErrorParams& p, hipStream_t stream);
 
-// Response of a perturbation, from the predicted tokens of the perturbed rows and of the clean one (elementwise.hip token_response_kernel):
+// Response of a perturbation, from the predicted tokens of the perturbed rows and of the clean one (readout.hip token_response_kernel):
 // r[b][Y][X] = sum_c (y - y_ref)^2 at the masked patches of frame `frame`, 0 at its visible ones; its per-patch mean, its first maximum, its sum and its
 // centroid.  No allocation, no synchronisation, no atomics: two calls on the same inputs are bit-equal.
 struct TokenResponseParams {
@@ -295,9 +313,7 @@ struct TokenResponseParams {
     const float* y_ref;    // the same for the clean prediction; row b at b * ref_sb (0: one reference for all rows)
     int64_t ref_sb;
     const uint8_t* mask;   // [B][Nt]: the mask of y AND y_ref
-    int B, T, C, H, W, P;  // C <= 8, P in {4, 8, 16}
-    int n_vis, Nm;
-    int frame;             // 0 .. T-1
+    PatchGrid g;           // frame: 0 .. T-1
     float* map;            // [B][H/P][W/P] or nullptr
     float* pixel_map;      // [B][H][W] or nullptr
     int* peak_index;       // [B] or nullptr: Y * W + X

@@ -523,74 +523,6 @@ extern "C" int cwm_unembed(const float* y_tokens_dev, const float* x_dev, const 
                              (hipStream_t)stream);
 }
 
-namespace {
-PatchErrorParams patch_error_params(const cwm_patch_error_args* a) {
-    PatchErrorParams p;
-    memset(&p, 0, sizeof(p));
-    p.y = a->y_tokens_dev;
-    p.x = a->x_dev; p.sb = a->x_stride_b; p.st = a->x_stride_t; p.sc = a->x_stride_c;
-    p.target = a->target_dev; p.tb = a->target_stride_b; p.tt = a->target_stride_t; p.tc = a->target_stride_c;
-    p.mask = a->mask_dev; p.region = a->region_dev;
-    p.B = a->batch; p.T = a->T; p.C = a->C; p.H = a->H; p.W = a->W; p.P = a->P;
-    p.n_vis = a->n_vis; p.frame = a->frame;
-    if (p.P > 0 && p.T > 0 && p.H > 0 && p.W > 0) p.Nm = p.T * (p.H / p.P) * (p.W / p.P) - p.n_vis;  // (launch_patch_error checks the sizes themselves)
-    p.map = a->map_dev; p.mean = a->mean_dev; p.scratch = a->scratch_dev;
-    return p;
-}
-}  // namespace
-
-extern "C" int cwm_patch_error(const cwm_patch_error_args* a) {
-    CWM_REQUIRE(a && a->struct_size == sizeof(cwm_patch_error_args), "cwm_patch_error: args->struct_size must be sizeof(cwm_patch_error_args)");
-    CWM_REQUIRE(a->x_dev && a->mask_dev && a->batch > 0, "cwm_patch_error: x_dev, mask_dev and a positive batch are required");
-    return launch_patch_error(patch_error_params(a), (hipStream_t)a->stream);
-}
-
-extern "C" int cwm_unmask_step(const cwm_unmask_step_args* a) {
-    CWM_REQUIRE(a && a->struct_size == sizeof(cwm_unmask_step_args), "cwm_unmask_step: args->struct_size must be sizeof(cwm_unmask_step_args)");
-    const cwm_patch_error_args& g = a->base;
-    CWM_REQUIRE(g.mask_dev && g.batch > 0 && g.T > 0, "cwm_unmask_step: mask_dev, a positive batch and T are required");
-    CWM_REQUIRE((g.P == 4 || g.P == 8 || g.P == 16) && g.H > 0 && g.W > 0 && g.H % g.P == 0 && g.W % g.P == 0,
-                "cwm_unmask_step: patches of 4, 8 or 16 pixels that divide the image, got P = %d for %d x %d", g.P, g.H, g.W);
-    CWM_REQUIRE(a->mode == 0 || a->mode == 1, "cwm_unmask_step: mode = %d (0 top, 1 race)", a->mode);
-    UnmaskStepParams u;
-    memset(&u, 0, sizeof(u));
-    u.mask = g.mask_dev;
-    u.B = g.batch; u.T = g.T; u.gh = g.H / g.P; u.gw = g.W / g.P; u.frame = a->frame;
-    u.k = a->num_reveal; u.race = a->mode; u.self_mask = a->self_mask != 0;
-    u.threshold = a->threshold_dev; u.e = a->e_dev;
-    u.mask_out = a->mask_out_dev; u.picks = a->picks_dev; u.dist = a->dist_dev; u.frontier = a->frontier_dev;
-    if (u.k <= 0) {  // nothing to reveal: the distance and the frontier alone
-        u.mask_out = nullptr;
-        u.picks = nullptr;
-        return launch_unmask_select(u, (hipStream_t)g.stream);
-    }
-    // Everything that can refuse is checked before the first launch: the selection's own arguments here (with a stand-in for the map), the error map's by its launcher.
-    CWM_REQUIRE(g.x_dev, "cwm_unmask_step: x_dev is required when a cell is revealed");
-    CWM_REQUIRE(g.map_dev || g.scratch_dev, "cwm_unmask_step: base.map_dev or base.scratch_dev ([B, T, H/P, W/P] floats) is required: the selection reads the error map from it");
-    PatchErrorParams p = patch_error_params(&g);
-    if (!p.map && !p.mean) p.map = p.scratch;
-    u.map = p.map ? p.map : p.scratch;
-    u.region = g.region_dev;
-    int rc;
-    if ((rc = check_unmask_select(u))) return rc;
-    if ((rc = launch_patch_error(p, (hipStream_t)g.stream))) return rc;
-    return launch_unmask_select(u, (hipStream_t)g.stream);
-}
-
-extern "C" int cwm_token_response(const cwm_token_response_args* a) {
-    CWM_REQUIRE(a && a->struct_size == sizeof(cwm_token_response_args), "cwm_token_response: args->struct_size must be sizeof(cwm_token_response_args)");
-    const cwm_patch_error_args& g = a->base;
-    TokenResponseParams p;
-    memset(&p, 0, sizeof(p));
-    p.y = g.y_tokens_dev; p.y_ref = a->y_ref_dev; p.ref_sb = a->y_ref_stride_b;
-    p.mask = g.mask_dev;
-    p.B = g.batch; p.T = g.T; p.C = g.C; p.H = g.H; p.W = g.W; p.P = g.P;
-    p.n_vis = g.n_vis; p.frame = g.frame;
-    if (p.P > 0 && p.T > 0 && p.H > 0 && p.W > 0) p.Nm = p.T * (p.H / p.P) * (p.W / p.P) - p.n_vis;  // (launch_token_response checks the sizes themselves)
-    p.map = g.map_dev; p.pixel_map = a->pixel_map_dev; p.peak_index = a->peak_index_dev; p.stats = a->stats_dev; p.scratch = g.scratch_dev;
-    return launch_token_response(p, (hipStream_t)g.stream);
-}
-
 extern "C" int cwm_mask_row_counts(const uint8_t* mask_dev, int B, int Nt, int32_t* counts_dev, void* stream) {
     CWM_REQUIRE(mask_dev && counts_dev && B > 0 && Nt > 0, "cwm_mask_row_counts: bad argument");
     return launch_mask_row_counts(mask_dev, B, Nt, counts_dev, (hipStream_t)stream);

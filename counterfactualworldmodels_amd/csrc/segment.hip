@@ -351,10 +351,9 @@ int launch_votes(const SegmentStepParams& p, const FlowView& v, FlowForm form, h
 }  // namespace
 
 int check_segment_step(const SegmentStepParams& p) {
-    CWM_REQUIRE(p.B > 0 && p.B <= 65535, "cwm_segment_step: base.batch = %d, 1 .. 65535", p.B);
-    CWM_REQUIRE(p.P == 4 || p.P == 8 || p.P == 16, "cwm_segment_step: base.P = %d, patches of 4, 8 or 16 pixels", p.P);
-    CWM_REQUIRE(p.H > 0 && p.H % p.P == 0, "cwm_segment_step: base.H = %d is no positive multiple of P = %d", p.H, p.P);
-    CWM_REQUIRE(p.W > 0 && p.W % p.P == 0, "cwm_segment_step: base.W = %d is no positive multiple of P = %d", p.W, p.P);
+    const PatchGrid g = {p.B, 2, 0, p.H, p.W, p.P, 0, 0, 0};  // (B, T, H, W and P are all it reads; the entry point has checked base.T = 2)
+    if (int rc = check_patch_grid("cwm_segment_step: base.", g, 0)) return rc;
+    CWM_REQUIRE(p.B <= 65535, "cwm_segment_step: base.batch = %d, 1 .. 65535", p.B);
     CWM_REQUIRE((int64_t)p.H * p.W <= kSegmentMaxPixels, "cwm_segment_step: base.H base.W = %lld pixels, at most %d", (long long)p.H * p.W, kSegmentMaxPixels);
     CWM_REQUIRE((int64_t)p.H * words_per_row(p.W) <= kSegmentMaxWords, "cwm_segment_step: base.H = %d rows of %d words (base.W = %d), at most %d words of bit rows", p.H,
                 words_per_row(p.W), p.W, kSegmentMaxWords);

@@ -212,9 +212,7 @@ def _unmask_step_grids(masks: torch.Tensor, self_mask: bool, threshold=None):
     m = masks.contiguous()
     dist = torch.empty((N, h, w), device=dev, dtype=torch.float32)
     a = _lib.new_unmask_step_args()
-    a.base.mask_dev = m.data_ptr()
-    a.base.batch, a.base.T, a.base.P, a.base.H, a.base.W = N, 1, 4, 4 * h, 4 * w
-    a.base.stream = _lib.current_stream_handle(dev)
+    _lib.fill_patch_args(a.base, mask=m, geometry=(N, 1, 0, 4 * h, 4 * w, 4), stream=_lib.current_stream_handle(dev))  # (one frame per grid, cells as 4 x 4 patches)
     a.frame, a.num_reveal, a.self_mask = 0, 0, int(bool(self_mask))
     a.dist_dev = dist.data_ptr()
     front = thr = None
@@ -272,6 +270,21 @@ def frontier_threshold(h: int, w: int, radius) -> float:
     if radius <= 0:
         raise ValueError("a frontier radius is a positive number of patches or None, got %r" % (radius,))
     return float(torch.tensor((1 / ((min(h, w) - 1) // 2)) * radius, dtype=torch.float32))
+
+
+def select_reveal(err, frame_mask, frontier, k, e=None):
+    """The selection rule of cwm_unmask_step and cwm_segment_step (csrc/select_order.h) in torch: err [B,n] float32, frame_mask / frontier [B,n] bool, e [B,n]
+    (race) or None -> cells [B,k] int64, -1 where a row has run out of masked cells.  Order: frontier before the other masked cells, the higher key first
+    (NaN above every number), the lower index first -- two stable sorts."""
+    key = err if e is None else err.clamp(min=0) / e
+    by_key = torch.sort(key, dim=1, descending=True, stable=True).indices
+    cls = frontier.to(torch.int8) + frame_mask.to(torch.int8)  # 2 frontier, 1 masked, 0 visible
+    by_cls = torch.sort(torch.gather(cls, 1, by_key), dim=1, descending=True, stable=True)
+    cells = torch.gather(by_key, 1, by_cls.indices)
+    cells = torch.where(by_cls.values > 0, cells, torch.full_like(cells, -1))
+    if k > cells.shape[1]:
+        cells = torch.cat([cells, torch.full((cells.shape[0], k - cells.shape[1]), -1, dtype=cells.dtype, device=cells.device)], 1)
+    return cells[:, :k]
 
 
 # ---- mask generators that PRODUCE the prompts' masks (masking.py:267-401, 478-545) ---------------------------------------

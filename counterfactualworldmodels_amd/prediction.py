@@ -40,6 +40,12 @@ def imagenet_normalize(x, temporal_dim=1):
     return (x - mean) / std
 
 
+def _region_of(target_mask, x, h, w):
+    """The region an error is read on, `1 - target_mask` in x's dtype: the patches VISIBLE in a [B,Nt] mask, viewed as [B,T,h,w], or one
+    minus any tensor of weights of that shape"""
+    return 1 - (target_mask.view(x.shape[0], -1, h, w) if target_mask.dim() == 2 else target_mask).to(x)
+
+
 @dataclass
 class _RectBatch:
     """R independent prediction rows: frames [R,T,C,H,W] in [0,1], masks [R,Nt] whose rows all mask `n_masked` tokens
@@ -463,19 +469,12 @@ class PredictorBasedGenerator(nn.Module):
         y = None
         if n_masked > 0:  # (nothing masked: every patch is the input's, there is no token to predict)
             y, _ = pred._run(xs, (sb, sc, st), self.imagenet_normalize_inputs, mask, Nt - n_masked, False, check=False, weights_synced=batch.weights_synced)
-        a = _lib.new_patch_error_args()
-        a.y_tokens_dev = _lib.ptr(y)
-        a.x_dev, a.x_stride_b, a.x_stride_t, a.x_stride_c = xs.data_ptr(), sb, st, sc
-        if target is not None:
-            tg, (tb, tc, tt) = pred._frame_strides(target, 2, 1)
-            a.target_dev, a.target_stride_b, a.target_stride_t, a.target_stride_c = tg.data_ptr(), tb, tt, tc
+        tg = None if target is None else pred._frame_strides(target, 2, 1)[0]
         region = region.to(device=dev, dtype=torch.float32).contiguous()
         emap = torch.empty((B, T, H // P, W // P), device=dev, dtype=torch.float32)
         mean = torch.empty((B,), device=dev, dtype=torch.float32) if want_mean else None
-        a.mask_dev, a.region_dev = mask.data_ptr(), region.data_ptr()
-        a.batch, a.T, a.C, a.H, a.W, a.P = B, T, Cc, H, W, P
-        a.n_vis, a.frame = Nt - n_masked, (-1 if frame is None else frame % T)
-        a.map_dev, a.mean_dev, a.stream = emap.data_ptr(), _lib.ptr(mean), _lib.current_stream_handle(dev)
+        a = _lib.fill_patch_args(_lib.new_patch_error_args(), x=xs, target=tg, mask=mask, region=region, y=y, geometry=(B, T, Cc, H, W, P), n_vis=Nt - n_masked,
+                                 frame=-1 if frame is None else frame % T, map=emap, mean=mean, stream=_lib.current_stream_handle(dev))
         with torch.cuda.device(dev):
             _lib.check(_lib.get_lib().cwm_patch_error(C.byref(a)))
         return emap, mean
@@ -492,13 +491,9 @@ class PredictorBasedGenerator(nn.Module):
         The plain predictor on the GPU with the default MSE error computes this from the predicted tokens in one kernel (cwm_patch_error) and never
         builds the predicted video; everything else -- conjoined predictors, a custom error_func, aggregate_over_patches=False, another patch_size,
         extra predictor arguments, a ragged batch -- composes `predict`, `error_func` and `avg_pool3d` as the reference does."""
-        B, T = x.shape[:2]
         ps = self._patch3()
         h, w = x.shape[-2] // ps[-2], x.shape[-1] // ps[-1]
-        if target_mask.dim() == 2:
-            region = 1 - target_mask.view(B, -1, h, w).to(x)
-        else:
-            region = 1 - target_mask.to(x)
+        region = _region_of(target_mask, x, h, w)
         if self._error_takes_fused_path(x, target, region, aggregate_over_patches, patch_size, kwargs):
             self.set_image_size(x.shape[-2:])
             self.inp_shape = x.shape
@@ -633,20 +628,7 @@ class PredictorBasedGenerator(nn.Module):
         near = masking.patches_adjacent_to_visible(grid, radius=radius) & grid
         return np.flatnonzero(near.view(-1).numpy())
 
-    @staticmethod
-    def _select_reveal(err, frame_mask, frontier, k, e=None):
-        """The selection rule of cwm_unmask_step in torch: err [B,n] float32, frame_mask / frontier [B,n] bool, e [B,n] (race) or None -> cells [B,k] int64,
-        -1 where a row has run out of masked cells.  Order: frontier before the other masked cells, the higher key first (NaN above every number),
-        the lower index first -- two stable sorts."""
-        key = err if e is None else err.clamp(min=0) / e
-        by_key = torch.sort(key, dim=1, descending=True, stable=True).indices
-        cls = frontier.to(torch.int8) + frame_mask.to(torch.int8)  # 2 frontier, 1 masked, 0 visible
-        by_cls = torch.sort(torch.gather(cls, 1, by_key), dim=1, descending=True, stable=True)
-        cells = torch.gather(by_key, 1, by_cls.indices)
-        cells = torch.where(by_cls.values > 0, cells, torch.full_like(cells, -1))
-        if k > cells.shape[1]:
-            cells = torch.cat([cells, torch.full((cells.shape[0], k - cells.shape[1]), -1, dtype=cells.dtype, device=cells.device)], 1)
-        return cells[:, :k]
+    _select_reveal = staticmethod(masking.select_reveal)  # (the name the selection had here; tests/test_frontier_unmask_cpu.py reaches it through it)
 
     def frontier_unmask(self, x, mask, num_steps=1, num_reveal=1, radius=1, frame=-1, target_mask=None, target=None, sample=False, generator=None,
                         return_trace=False):
@@ -683,10 +665,8 @@ class PredictorBasedGenerator(nn.Module):
         if target_mask is None:
             region = torch.zeros((B, T, h, w), device=dev, dtype=torch.float32)
             region[:, f] = 1
-        elif target_mask.dim() == 2:
-            region = 1 - target_mask.view(B, -1, h, w).to(x)
         else:
-            region = 1 - target_mask.to(x)
+            region = _region_of(target_mask, x, h, w)
         rows = cur.sum(1)
         lo, hi, in_frame = (int(v) for v in torch.stack([rows.min(), rows.max(), cur[:, f * n:(f + 1) * n].sum(1).min()]).tolist())  # the one read-back
         if lo != hi:
@@ -710,14 +690,7 @@ class PredictorBasedGenerator(nn.Module):
             thr_dev = torch.tensor([thr], dtype=torch.float32).to(dev)
             nxt = torch.empty_like(cur)
             a = _lib.new_unmask_step_args()
-            g = a.base
-            g.x_dev, g.x_stride_b, g.x_stride_t, g.x_stride_c = xs.data_ptr(), sb, st, sc
-            if target is not None:
-                tg, (tb, tc, tt) = pred._frame_strides(target, 2, 1)
-                g.target_dev, g.target_stride_b, g.target_stride_t, g.target_stride_c = tg.data_ptr(), tb, tt, tc
-            g.region_dev = region.data_ptr()
-            g.batch, g.T, g.C, g.H, g.W, g.P = B, T, x.shape[2], H, W, P
-            g.frame, g.stream = f, _lib.current_stream_handle(dev)
+            tg = None if target is None else pred._frame_strides(target, 2, 1)[0]
             a.frame, a.num_reveal, a.mode, a.threshold_dev = f, k, int(bool(sample)), thr_dev.data_ptr()
             emap = torch.empty((B, T, h, w), device=dev, dtype=torch.float32)
             front = torch.empty((B, h, w), device=dev, dtype=torch.uint8) if return_trace else None
@@ -728,8 +701,8 @@ class PredictorBasedGenerator(nn.Module):
                 if return_trace:
                     emap = torch.empty((B, T, h, w), device=dev, dtype=torch.float32)
                     front = torch.empty((B, h, w), device=dev, dtype=torch.uint8)
-                g.y_tokens_dev, g.mask_dev, g.n_vis = _lib.ptr(y), cur.data_ptr(), Nt - n_masked
-                g.map_dev, g.mean_dev = emap.data_ptr(), errors[s].data_ptr()
+                _lib.fill_patch_args(a.base, x=xs, target=tg, mask=cur, region=region, y=y, geometry=(B, T, x.shape[2], H, W, P), n_vis=Nt - n_masked, frame=f,
+                                     map=emap, mean=errors[s], stream=_lib.current_stream_handle(dev))
                 a.e_dev, a.mask_out_dev, a.picks_dev, a.frontier_dev = _lib.ptr(e), nxt.data_ptr(), picks[s].data_ptr(), _lib.ptr(front)
                 with torch.cuda.device(dev):
                     _lib.check(_lib.get_lib().cwm_unmask_step(C.byref(a)))
@@ -746,7 +719,7 @@ class PredictorBasedGenerator(nn.Module):
                     front = fm
                 else:
                     front = fm & (masking.patch_distance_transform(fm.reshape(B, 1, h, w), self_mask=False).view(B, n) <= thr)
-                cells = self._select_reveal(emap[:, f].reshape(B, n).float(), fm, front, k, draw())
+                cells = masking.select_reveal(emap[:, f].reshape(B, n).float(), fm, front, k, draw())
                 picks[s] = f * n + cells
                 cur = cur.clone()
                 cur[torch.arange(B, device=dev)[:, None], f * n + cells] = False
@@ -856,15 +829,13 @@ class PredictorBasedGenerator(nn.Module):
             y_ref = tokens_of(x, mask)
             scratch = torch.empty((min(step, K), h, 8), device=dev, dtype=torch.float32)
             a = _lib.new_token_response_args()
-            g = a.base
-            g.batch, g.T, g.C, g.H, g.W, g.P, g.n_vis, g.frame = 0, T, Cc, H, W, P, Nt - n_masked, f
-            g.scratch_dev, g.stream = scratch.data_ptr(), _lib.current_stream_handle(dev)
             a.y_ref_dev, a.y_ref_stride_b = _lib.ptr(y_ref), 0
             for r0 in range(0, K, step):
                 r1 = min(r0 + step, K)
                 rows = mask.expand(r1 - r0, Nt).contiguous()
                 y = tokens_of(prompts(r0, r1), rows)
-                g.batch, g.y_tokens_dev, g.mask_dev = r1 - r0, _lib.ptr(y), rows.data_ptr()
+                _lib.fill_patch_args(a.base, mask=rows, y=y, geometry=(r1 - r0, T, Cc, H, W, P), n_vis=Nt - n_masked, frame=f, scratch=scratch,
+                                     stream=_lib.current_stream_handle(dev))
                 a.peak_index_dev, a.stats_dev = index[r0:r1].data_ptr(), stats[r0:r1].data_ptr()
                 a.pixel_map_dev = maps[r0:r1].data_ptr() if return_maps else None
                 with torch.cuda.device(dev):

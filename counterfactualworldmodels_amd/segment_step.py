@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .flowstats import _strides5
+from .masking import select_reveal
 
 # the 8 compass shifts (dy, dx) in their fixed order: E, S, W, N, then SE, SW, NW, NE
 COMPASS = ((0, 1), (1, 0), (0, -1), (-1, 0), (1, 1), (1, -1), (-1, -1), (-1, 1))
@@ -39,6 +40,8 @@ class SegmentStepResult:
 
 
 def _check(B, H, W, S, P, k_active, k_passive, ring_radius, init):
+    """What Python must refuse before it allocates the outputs or divides by P; the library's check_patch_grid and check_segment_step (csrc/readout.hip,
+    csrc/segment.hip) are the statement of the limits and refuse everything else"""
     if P not in (4, 8, 16) or H % P or W % P:
         raise ValueError("segment_step: patches of 4, 8 or 16 pixels that divide the image, got P = %d for %d x %d" % (P, H, W))
     if H * W > MAX_PIXELS or (H // P) * (W // P) > MAX_CELLS or H * ((W + 31) // 32) > 8192:
@@ -94,8 +97,7 @@ def segment_step_device(flows, seeds, P, *, min_seed_mag, abs_thresh, rel_thresh
         active=torch.empty((B, 2 * n), device=dev, dtype=torch.bool) if sel else None, passive=torch.empty((B, 2 * n), device=dev, dtype=torch.bool) if sel else None,
         picks=torch.empty((B, K), device=dev, dtype=torch.int32) if sel else None)
     a = _lib.new_segment_step_args()
-    g = a.base
-    g.batch, g.T, g.H, g.W, g.P, g.stream = B, 2, H, W, P, _lib.current_stream_handle(dev)
+    _lib.fill_patch_args(a.base, geometry=(B, 2, 0, H, W, P), stream=_lib.current_stream_handle(dev))
     if not init:
         a.flows_dev, a.C, a.S = flows.data_ptr(), 2, S
         for i in range(5):
@@ -112,9 +114,7 @@ def segment_step_device(flows, seeds, P, *, min_seed_mag, abs_thresh, rel_thresh
 
 def _select(key, eligible, k):
     """cells [B,k] int64 (-1: none left) of the eligible cells in the order of cwm_unmask_step: the higher key first, a NaN above every number, the lower index first"""
-    from .prediction import PredictorBasedGenerator
-
-    return PredictorBasedGenerator._select_reveal(key, eligible, torch.zeros_like(eligible), k)
+    return select_reveal(key, eligible, torch.zeros_like(eligible), k)
 
 
 def segment_step_torch(flows, seeds, P, *, min_seed_mag, abs_thresh, rel_thresh=0.5, vote_frac=0.5, dirs=None, cos_min=0.0, k_active=0, k_passive=0,

@@ -5,6 +5,7 @@ import ctypes
 import os
 
 import numpy as np
+import pytest
 import torch
 
 import patch_error_restatement as PR
@@ -82,6 +83,36 @@ def test_binding_and_header():
     # argument checks need no device: a wrong struct_size and a missing output are refused before anything is launched
     a.struct_size = 8
     assert lib.cwm_patch_error(ctypes.byref(a)) == _lib.ERR_INVALID and b"struct_size" in lib.cwm_last_error()
+
+
+def test_fill_patch_args_reads_pointers_and_strides_from_the_views():
+    """[B,T,C,H,W]-shaped views over a [B,C,T,H,W] tensor and over one movie at batch stride 0: the (b, t, c) strides are the views' own, in that order"""
+    B, T, Cc, H, W, P = 3, 2, 3, 16, 24, 8
+    x = torch.zeros((B, Cc, T, H, W)).permute(0, 2, 1, 3, 4)
+    target = torch.zeros((1, T, Cc, H, W)).expand(B, -1, -1, -1, -1)
+    mask, region, y = torch.zeros((B, 12), dtype=torch.bool), torch.zeros((B, T, 2, 3)), torch.zeros((B, 5, P * P * Cc))
+    emap, mean, scratch = torch.zeros((B, T, 2, 3)), torch.zeros((B,)), torch.zeros((B, T, 2, 3))
+    for cls in (_lib.CwmPatchErrorArgs, _lib.CwmTokenResponseArgs, _lib.CwmUnmaskStepArgs, _lib.CwmSegmentStepArgs):
+        a = _lib.new_args(cls)
+        g = a if cls is _lib.CwmPatchErrorArgs else a.base
+        assert a.struct_size == ctypes.sizeof(cls) and g.struct_size == ctypes.sizeof(_lib.CwmPatchErrorArgs)
+        assert _lib.fill_patch_args(g, x=x, target=target, mask=mask, region=region, y=y, geometry=(B, T, Cc, H, W, P), n_vis=7, frame=1, map=emap, mean=mean,
+                                    scratch=scratch, stream=1234) is g
+        assert (g.x_dev, g.x_stride_b, g.x_stride_t, g.x_stride_c) == (x.data_ptr(), T * Cc * H * W, H * W, T * H * W) == (x.data_ptr(),) + x.stride()[:3]
+        assert (g.target_dev, g.target_stride_b, g.target_stride_t, g.target_stride_c) == (target.data_ptr(), 0, Cc * H * W, H * W)
+        assert (g.y_tokens_dev, g.mask_dev, g.region_dev) == (y.data_ptr(), mask.data_ptr(), region.data_ptr())
+        assert (g.batch, g.T, g.C, g.H, g.W, g.P, g.n_vis, g.frame) == (B, T, Cc, H, W, P, 7, 1)
+        assert (g.map_dev, g.mean_dev, g.scratch_dev, g.stream) == (emap.data_ptr(), mean.data_ptr(), scratch.data_ptr(), 1234)
+        assert g.struct_size == ctypes.sizeof(_lib.CwmPatchErrorArgs)  # left alone
+    # what is not given is NULL / 0, whatever the structure held before; frame defaults to -1 (each frame against its own)
+    _lib.fill_patch_args(g, mask=mask, geometry=(B, T, 0, H, W, P), stream=None)
+    assert (g.x_dev, g.x_stride_c, g.target_dev, g.target_stride_t, g.y_tokens_dev, g.map_dev, g.stream, g.n_vis, g.frame) == (None, 0, None, 0, None, None, None, 0, -1)
+    assert _lib.new_segment_step_args().base.T == 2 and _lib.new_unmask_step_args().struct_size == ctypes.sizeof(_lib.CwmUnmaskStepArgs)
+    for bad in (x[..., ::2], x.transpose(-1, -2), x[:, :, :, :, :W - 1], x[0]):  # rows that are not contiguous, or not five dimensions
+        with pytest.raises(ValueError, match="contiguous image rows"):
+            _lib.fill_patch_args(_lib.new_args(_lib.CwmPatchErrorArgs), x=bad, geometry=(B, T, Cc, H, W, P), stream=None)
+    with pytest.raises(ValueError, match="target"):
+        _lib.fill_patch_args(_lib.new_args(_lib.CwmPatchErrorArgs), x=x, target=x[..., ::2], geometry=(B, T, Cc, H, W, P), stream=None)
 
 
 def test_greedy_golden_is_decided_by_the_frames():

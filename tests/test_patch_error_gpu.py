@@ -32,31 +32,15 @@ def stream():
     return _lib.current_stream_handle(torch.device("cuda:0"))
 
 
-def frame_strides(v):
-    """(b, t, c) strides of a [B,T,C,H,W]-shaped view with contiguous rows"""
-    assert v.stride(-1) == 1 and v.stride(-2) == v.shape[-1]
-    return v.stride(0), v.stride(1), v.stride(2)
-
-
 def run_kernel(y, x, mask, P, frame, target=None, region=None, want_map=True, want_mean=True):
     """`cwm_patch_error` on device tensors; x / target are [B,T,C,H,W]-shaped views of any (b, t, c) strides.  Returns (map, mean), None where not asked for."""
     B, T, Cc, H, W = x.shape
     h, w = H // P, W // P
-    a = _lib.new_patch_error_args()
-    a.y_tokens_dev = _lib.ptr(y)
-    a.x_dev = x.data_ptr()
-    a.x_stride_b, a.x_stride_t, a.x_stride_c = frame_strides(x)
-    if target is not None:
-        a.target_dev = target.data_ptr()
-        a.target_stride_b, a.target_stride_t, a.target_stride_c = frame_strides(target)
-    a.mask_dev, a.region_dev = mask.data_ptr(), _lib.ptr(region)
-    a.batch, a.T, a.C, a.H, a.W, a.P = B, T, Cc, H, W, P
-    a.n_vis = T * h * w - (0 if y is None else y.shape[1])
-    a.frame = -1 if frame is None else frame
     emap = torch.full((B, T, h, w), float("nan"), device="cuda") if want_map else None
     mean = torch.full((B,), float("nan"), device="cuda") if want_mean else None
     scratch = torch.empty((B, T, h, w), device="cuda") if want_mean and not want_map else None
-    a.map_dev, a.mean_dev, a.scratch_dev, a.stream = _lib.ptr(emap), _lib.ptr(mean), _lib.ptr(scratch), stream()
+    a = _lib.fill_patch_args(_lib.new_patch_error_args(), x=x, target=target, mask=mask, region=region, y=y, geometry=(B, T, Cc, H, W, P),
+                             n_vis=T * h * w - (0 if y is None else y.shape[1]), frame=-1 if frame is None else frame, map=emap, mean=mean, scratch=scratch, stream=stream())
     _lib.check(_lib.get_lib().cwm_patch_error(ctypes.byref(a)))
     return emap, mean
 
@@ -140,9 +124,7 @@ def test_each_output_alone_and_two_calls_are_bit_equal():
     assert only_map[1] is None and only_mean[0] is None
     assert torch.equal(only_map[0], both[0]) and torch.equal(only_mean[1], both[1])
     # arguments that cannot be run are refused, naming what is wrong
-    a = _lib.new_patch_error_args()
-    a.x_dev, a.mask_dev, a.batch, a.T, a.C, a.H, a.W, a.P, a.n_vis = x.data_ptr(), mask.data_ptr(), B, T, Cc, H, W, P, T * 24
-    a.x_stride_b, a.x_stride_t, a.x_stride_c = frame_strides(x)
+    a = _lib.fill_patch_args(_lib.new_patch_error_args(), x=x, mask=mask, geometry=(B, T, Cc, H, W, P), n_vis=T * 24, frame=0, stream=None)
     lib = _lib.get_lib()
     assert lib.cwm_patch_error(ctypes.byref(a)) == _lib.ERR_INVALID and b"neither output" in lib.cwm_last_error()
     a.mean_dev = both[1].data_ptr()

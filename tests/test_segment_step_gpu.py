@@ -62,8 +62,7 @@ def run(flows, seeds, P, layout="view", shape=None, skip=(), dirs=None, keys=Non
               "stats": ((B, 4), torch.int32), "picks": ((B, K), torch.int32), "active": ((B, 2 * n), torch.uint8), "passive": ((B, 2 * n), torch.uint8)}
     bufs = {k: guarded(*shapes[k]) for k in OUT if k not in skip}
     a = _lib.new_segment_step_args()
-    g = a.base
-    g.batch, g.T, g.H, g.W, g.P, g.stream = B, 2, H, W, P, stream()
+    _lib.fill_patch_args(a.base, geometry=(B, 2, 0, H, W, P), stream=stream())
     if not init:
         a.flows_dev, a.C, a.S = fd.data_ptr(), 2, S
         for i, st in enumerate(fd.stride()):

@@ -40,8 +40,7 @@ def call(view, seeds, dirs, keys):
            torch.full((B, n), -7.0, device=dev), torch.full((B, 4), -9, dtype=torch.int32, device=dev), torch.full((B, KA + KP), -9, dtype=torch.int32, device=dev),
            torch.full((B, 2 * n), 9, dtype=torch.uint8, device=dev), torch.full((B, 2 * n), 9, dtype=torch.uint8, device=dev)]
     a = _lib.new_segment_step_args()
-    g = a.base
-    g.batch, g.T, g.H, g.W, g.P, g.stream = B, 2, H, W, P, _lib.current_stream_handle(dev)
+    _lib.fill_patch_args(a.base, geometry=(B, 2, 0, H, W, P), stream=_lib.current_stream_handle(dev))
     a.flows_dev, a.C, a.S = f.data_ptr(), 2, S
     for i, st in enumerate(f.stride()):
         a.flow_strides[i] = st

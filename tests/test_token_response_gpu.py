@@ -80,11 +80,6 @@ def run_kernel(y, y_ref, mask, geom, frame, want=("map", "pixels", "index", "sta
     B = mask.shape[0]
     h, w = H // P, W // P
     a = _lib.new_token_response_args()
-    g = a.base
-    g.y_tokens_dev, g.mask_dev = _lib.ptr(y), mask.data_ptr()
-    g.batch, g.T, g.C, g.H, g.W, g.P = B, T, Cc, H, W, P
-    g.n_vis = (T * h * w - (0 if y is None else y.shape[1])) if n_vis is None else n_vis
-    g.frame = frame
     a.y_ref_dev = _lib.ptr(y_ref)
     a.y_ref_stride_b = 0 if y_ref is None or y_ref.shape[0] == 1 else y_ref.stride(0)
     emap = torch.full((B, h, w), float("nan"), device="cuda") if "map" in want else None
@@ -92,7 +87,8 @@ def run_kernel(y, y_ref, mask, geom, frame, want=("map", "pixels", "index", "sta
     index = torch.full((B,), -1, device="cuda", dtype=torch.int32) if "index" in want else None
     stats = torch.full((B, 4), float("nan"), device="cuda") if "stats" in want else None
     work = torch.full((B, h, 8), float("nan"), device="cuda") if scratch and (index is not None or stats is not None) else None
-    g.map_dev, g.scratch_dev, g.stream = _lib.ptr(emap), _lib.ptr(work), stream()
+    _lib.fill_patch_args(a.base, mask=mask, y=y, geometry=(B, T, Cc, H, W, P), n_vis=(T * h * w - (0 if y is None else y.shape[1])) if n_vis is None else n_vis,
+                         frame=frame, map=emap, scratch=work, stream=stream())
     a.pixel_map_dev, a.peak_index_dev, a.stats_dev = _lib.ptr(pixels), _lib.ptr(index), _lib.ptr(stats)
     _lib.check(_lib.get_lib().cwm_token_response(ctypes.byref(a)))
     return emap, pixels, index, stats

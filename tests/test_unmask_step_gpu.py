@@ -49,23 +49,17 @@ def frame_mask(B, h, w, masked_cells_per_row):
     return m
 
 
-def fill(a, x, mask_dev, y, n_vis, region=None):
-    g = a.base
+def fill(a, x, mask_dev, y, n_vis, region=None, **outputs):
     B, _, _, H, W = x.shape
-    g.y_tokens_dev, g.x_dev = _lib.ptr(y), x.data_ptr()
-    g.x_stride_b, g.x_stride_t, g.x_stride_c = x.stride(0), x.stride(1), x.stride(2)
-    g.mask_dev, g.region_dev = mask_dev.data_ptr(), _lib.ptr(region)
-    g.batch, g.T, g.C, g.H, g.W, g.P = B, T, Cc, H, W, P
-    g.n_vis, g.frame, g.stream = n_vis, F, stream()
+    _lib.fill_patch_args(a.base, x=x, mask=mask_dev, region=region, y=y, geometry=(B, T, Cc, H, W, P), n_vis=n_vis, frame=F, stream=stream(), **outputs)
 
 
 def patch_error(x, mask_dev, y, n_vis, region=None):
     B, _, _, H, W = x.shape
     a = _lib.new_unmask_step_args()
-    fill(a, x, mask_dev, y, n_vis, region)
     emap = torch.full((B, T, H // P, W // P), -7.0, device="cuda")
     mean = torch.full((B,), -7.0, device="cuda")
-    a.base.map_dev, a.base.mean_dev = emap.data_ptr(), mean.data_ptr()
+    fill(a, x, mask_dev, y, n_vis, region, map=emap, mean=mean)
     _lib.check(_lib.get_lib().cwm_patch_error(ctypes.byref(a.base)))
     return emap, mean
 
@@ -77,13 +71,9 @@ def run_on_device(x, md, y, k, thr, e=None, region=None, use_scratch=False):
     h, w = H // P, W // P
     n = h * w
     a = _lib.new_unmask_step_args()
-    fill(a, x, md, y, T * n - (0 if y is None else y.shape[1]), region)
     emap = torch.full((B, T, h, w), -7.0, device="cuda")
     mean = torch.full((B,), -7.0, device="cuda")
-    if use_scratch:
-        a.base.scratch_dev = emap.data_ptr()
-    else:
-        a.base.map_dev, a.base.mean_dev = emap.data_ptr(), mean.data_ptr()
+    fill(a, x, md, y, T * n - (0 if y is None else y.shape[1]), region, **(dict(scratch=emap) if use_scratch else dict(map=emap, mean=mean)))
     thr_dev = torch.full((1,), thr, dtype=torch.float32, device="cuda")
     mask_out, picks = torch.full_like(md, True), torch.full((B, k), -9, dtype=torch.int32, device="cuda")
     dist, front = torch.full((B, n), -7.0, device="cuda"), torch.full((B, n), 9, dtype=torch.uint8, device="cuda")
@@ -228,7 +218,7 @@ def test_nothing_to_reveal_reads_only_the_mask(name):
     md = mask.cuda()
     for self_mask in (0, 1):
         a = _lib.new_unmask_step_args()
-        a.base.mask_dev, a.base.batch, a.base.T, a.base.P, a.base.H, a.base.W, a.base.stream = md.data_ptr(), B, T, P, h * P, w * P, stream()
+        _lib.fill_patch_args(a.base, mask=md, geometry=(B, T, 0, h * P, w * P, P), stream=stream())
         a.frame, a.self_mask = F, self_mask
         thr = torch.tensor([UR.threshold(h, w, 1)]).cuda()
         dist = torch.full((B, n), -7.0, device="cuda")
@@ -248,9 +238,8 @@ def test_argument_errors_launch_nothing():
 
     def args():
         a = _lib.new_unmask_step_args()
-        fill(a, x, mask, y, n)
         emap = torch.empty((B, T, h, w), device="cuda")
-        a.base.map_dev = emap.data_ptr()
+        fill(a, x, mask, y, n, map=emap)
         out = torch.full_like(mask, True)
         picks = torch.full((B, 64), -9, dtype=torch.int32, device="cuda")
         a.frame, a.num_reveal, a.mask_out_dev, a.picks_dev = F, 2, out.data_ptr(), picks.data_ptr()

@@ -98,12 +98,8 @@ def main():
     emap = torch.empty((B, 2, cfg.img_size[0] // P, cfg.img_size[1] // P), device="cuda")
     mean = torch.empty((B,), device="cuda")
     region = (1 - target_mask.view(B, 2, *emap.shape[2:]).float()).contiguous()
-    pa = _lib.new_patch_error_args()
-    pa.y_tokens_dev, pa.x_dev, pa.mask_dev, pa.region_dev = y.data_ptr(), x.data_ptr(), mask.data_ptr(), region.data_ptr()
-    pa.x_stride_b, pa.x_stride_t, pa.x_stride_c = x.stride(0), x.stride(1), x.stride(2)
-    pa.batch, pa.T, pa.C, pa.H, pa.W, pa.P = B, 2, cfg.in_chans, cfg.img_size[0], cfg.img_size[1], P
-    pa.n_vis, pa.map_dev, pa.mean_dev = Nt - y.shape[1], emap.data_ptr(), mean.data_ptr()
-    pa.stream = _lib.current_stream_handle(torch.device("cuda:0"))
+    pa = _lib.fill_patch_args(_lib.new_patch_error_args(), x=x, mask=mask, region=region, y=y, geometry=(B, 2, cfg.in_chans, cfg.img_size[0], cfg.img_size[1], P),
+                              n_vis=Nt - y.shape[1], map=emap, mean=mean, stream=_lib.current_stream_handle(torch.device("cuda:0")))
     lib = _lib.get_lib()
     import ctypes
 

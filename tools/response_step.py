@@ -95,10 +95,8 @@ def main():
     scratch = torch.empty((B, H // P, 8), device="cuda")
     pixels = torch.empty((B, H, W), device="cuda")
     a = _lib.new_token_response_args()
-    gm = a.base
-    gm.y_tokens_dev, gm.mask_dev, gm.scratch_dev = y.data_ptr(), mask.data_ptr(), scratch.data_ptr()
-    gm.batch, gm.T, gm.C, gm.H, gm.W, gm.P, gm.n_vis, gm.frame = B, 2, cfg.in_chans, H, W, P, Nt - y.shape[1], 1
-    gm.stream = _lib.current_stream_handle(torch.device("cuda:0"))
+    _lib.fill_patch_args(a.base, mask=mask, y=y, geometry=(B, 2, cfg.in_chans, H, W, P), n_vis=Nt - y.shape[1], frame=1, scratch=scratch,
+                         stream=_lib.current_stream_handle(torch.device("cuda:0")))
     a.y_ref_dev, a.y_ref_stride_b, a.peak_index_dev, a.stats_dev = y_ref.data_ptr(), 0, index.data_ptr(), stats.data_ptr()
     lib = _lib.get_lib()
     for label, pix in (("statistics", None), ("statistics_and_pixel_map", pixels)):

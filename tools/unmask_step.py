@@ -59,11 +59,8 @@ def selection_alone(P, side, B, reps):
     out_mask, picks = torch.empty_like(mask), torch.empty((B, 8), dtype=torch.int32, device="cuda")
     dist = torch.empty((B, n), device="cuda")
     a = _lib.new_unmask_step_args()
-    gb = a.base
-    gb.y_tokens_dev, gb.x_dev, gb.mask_dev = y.data_ptr(), x.data_ptr(), mask.data_ptr()
-    gb.x_stride_b, gb.x_stride_t, gb.x_stride_c = x.stride(0), x.stride(1), x.stride(2)
-    gb.batch, gb.T, gb.C, gb.H, gb.W, gb.P, gb.n_vis, gb.frame = B, 2, 3, H, W, P, n + 8, 1
-    gb.map_dev, gb.mean_dev, gb.stream = emap.data_ptr(), mean.data_ptr(), _lib.current_stream_handle(torch.device("cuda:0"))
+    _lib.fill_patch_args(a.base, x=x, mask=mask, y=y, geometry=(B, 2, 3, H, W, P), n_vis=n + 8, frame=1, map=emap, mean=mean,
+                         stream=_lib.current_stream_handle(torch.device("cuda:0")))
     a.frame, a.threshold_dev, a.mask_out_dev, a.picks_dev = 1, thr.data_ptr(), out_mask.data_ptr(), picks.data_ptr()
     lib = _lib.get_lib()
 
