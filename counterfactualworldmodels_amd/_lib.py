@@ -183,6 +183,33 @@ class CwmSegmentStepArgs(C.Structure):
     ]
 
 
+class CwmSegmentMergeArgs(C.Structure):
+    """cwm_segment_merge_args (include/cwm_hip.h): cwm_patch_error_args as `base` (batch, T, H, W, P and the stream are read), the candidate segments by two
+    strides, the scores, the thresholds, the workspace and the outputs; new_segment_merge_args() sets struct_size"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", CwmPatchErrorArgs),
+        ("K", C.c_int32),
+        ("segs_dev", C.c_void_p),
+        ("seg_strides", C.c_int64 * 2),
+        ("scores_dev", C.c_void_p),
+        ("min_area", C.c_int32),
+        ("max_area", C.c_int32),
+        ("iou_thresh", C.c_float),
+        ("contain_thresh", C.c_float),
+        ("absorb", C.c_int32),
+        ("work_dev", C.c_void_p),
+        ("work_bytes", C.c_uint64),
+        ("labels_dev", C.c_void_p),
+        ("owner_dev", C.c_void_p),
+        ("area_dev", C.c_void_p),
+        ("label_area_dev", C.c_void_p),
+        ("inter_dev", C.c_void_p),
+        ("cover_dev", C.c_void_p),
+        ("stats_dev", C.c_void_p),
+    ]
+
+
 class CwmConjConfig(C.Structure):
     _fields_ = [
         ("main", CwmConfig),
@@ -604,6 +631,12 @@ def new_segment_step_args() -> CwmSegmentStepArgs:
     return a
 
 
+def new_segment_merge_args() -> CwmSegmentMergeArgs:
+    a = new_args(CwmSegmentMergeArgs)
+    a.base.T = 2
+    return a
+
+
 def fill_patch_args(g, *, x=None, target=None, mask=None, region=None, y=None, geometry, n_vis=0, frame=-1, map=None, mean=None, scratch=None, stream):
     """Fills a cwm_patch_error_args -- alone, or the `.base` of the other read-outs' -- from tensors: the one place that knows its field order.  `x` and `target`
     are [B,T,C,H,W]-SHAPED views of any (b, t, c) strides, whatever the order of the tensor beneath ([B,C,T,H,W] permuted, a batch stride of 0); their image
@@ -672,6 +705,8 @@ SIGNATURES = {
     "cwm_token_response": (C.c_int, [C.POINTER(CwmTokenResponseArgs)]),
     "cwm_unmask_step": (C.c_int, [C.POINTER(CwmUnmaskStepArgs)]),
     "cwm_segment_step": (C.c_int, [C.POINTER(CwmSegmentStepArgs)]),
+    "cwm_segment_merge": (C.c_int, [C.POINTER(CwmSegmentMergeArgs)]),
+    "cwm_segment_merge_work_bytes": (C.c_size_t, [C.c_int] * 4),
     "cwm_mask_row_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_mask_flip_picks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cwm_prompt_table_expand": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),

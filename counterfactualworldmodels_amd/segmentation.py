@@ -467,6 +467,41 @@ class FlowGenerator(PredictorBasedGenerator):
         frac = res.votes.float() / res.stats[:, 0].clamp(min=1).float()[:, None, None]
         return (res.segment, frac, trace) if return_trace else (res.segment, frac)
 
+    # ---- scene segmentation: many seeded segments merged into one label map (segment_merge.py, csrc/segment_merge.hip) ----
+    def segment_merge(self, segments, scores=None, *, min_area=1, max_area=0, iou_thresh=0.5, contain_thresh=0.6, absorb=True, want_inter=False):
+        """K candidate segments per row [B,K,H,W] (nonzero = in; a slice of a larger buffer is read in place) and their scores [B,K] (None: index order) to one
+        label map: candidates outside min_area .. max_area pixels (0: no upper bound) are dropped; the others are walked from the highest score down, and one
+        whose intersection with an already-kept candidate exceeds iou_thresh of their union or contain_thresh of the smaller of the two is absorbed by the first
+        such one, else kept as the next label.  Pixels go to the lowest label that holds them; absorb=True paints the absorbed candidates' pixels with their
+        absorber's label.  Returns a `SegmentMergeResult` (labels, owner, area, label_area, inter with want_inter, cover per patch, stats).  Device tensors take
+        one library call (cwm_segment_merge, nothing read back), CPU tensors the same definition in torch."""
+        from . import segment_merge as SM
+
+        return SM.segment_merge(segments, scores, self.patch_size[-1], min_area=min_area, max_area=max_area, iou_thresh=iou_thresh, contain_thresh=contain_thresh,
+                                absorb=absorb, want_inter=want_inter)
+
+    def segment_scene(self, x, seeds=None, num_seeds=8, num_rounds=1, seed_distribution=None, generator=None, score="votes", seed_batch_size=None, free_below=None,
+                      min_area=None, max_area_frac=0.5, iou_thresh=0.5, contain_thresh=0.6, absorb=True, **kwargs):
+        """The Spelke objects of every movie of x [B,T,C,H,W] as one label map: `num_rounds` rounds of `num_seeds` seeds, each seed run through
+        `segment_spelke_object` (x repeated over the round's seeds, in chunks of `seed_batch_size` rows; **kwargs pass through: num_iters, num_samples, the
+        thresholds, raft_iters, ...), every round written into one [B, num_rounds num_seeds, H, W] buffer (at most 64 candidates) and one `segment_merge` over all
+        candidates so far after every round, the strided slice read in place.  score="votes" ranks a candidate by the mean vote fraction inside its segment,
+        (frac * segment).sum / area.clamp(min=1); score="area" by its area.  min_area defaults to one patch, max_area is max_area_frac of the image (a segment
+        larger than that is what camera motion gives).
+        Seeds: round 0 takes `seeds` [B,num_seeds,2] (y, x) when given.  Every other round draws cells of the patch grid -- round 0 among all cells, round r > 0
+        among those the merge leaves uncovered (cover == 0, or cover < free_below) -- without replacement and in proportion to `seed_distribution` ([B,H,W],
+        averaged to patches, or [B,gh,gw]; None: uniform) by the exponential race of `frontier_unmask(sample=True)`: key = p / e, e from `generator`, in the order
+        of `masking.select_reveal`.  A seed is the centre pixel of its cell; a slot that finds no cell is a dead row: seed (-1, -1), an all-zero candidate, never
+        valid.  `predict_keypoints_distribution` and the movability map are the natural seed distributions; they are not wired in.
+        Everything stays on x's device and the loop reads nothing back beyond what the counterfactual driver does; it runs inside
+        torch.random.fork_rng(devices=[]), so the caller's global CPU stream of draws is left as it was.  Returns a `SceneSegmentation` (labels [B,H,W] uint8,
+        num_labels [B], seeds, segments [B,K,H,W] bool, scores, owner, label_area, cover, stats)."""
+        from . import segment_merge as SM
+
+        return SM.segment_scene(self, x, seeds=seeds, num_seeds=num_seeds, num_rounds=num_rounds, seed_distribution=seed_distribution, generator=generator, score=score,
+                                seed_batch_size=seed_batch_size, free_below=free_below, min_area=min_area, max_area_frac=max_area_frac, iou_thresh=iou_thresh,
+                                contain_thresh=contain_thresh, absorb=absorb, **kwargs)
+
     # ---- statistics over the flow samples (segmentation.py:250-276, 479-547): device kernels, see flowstats.py ----------
     def compute_flow_samples_magnitude(self, flows, normalize=True, dim=-4, eps=1e-2):
         from . import flowstats

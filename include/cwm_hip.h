@@ -428,6 +428,57 @@ typedef struct cwm_segment_step_args {
  * k_active, k_passive <= 64; ring_radius >= 1.  Argument errors: CWM_ERR_INVALID with a message that names the field, before anything is launched. */
 CWM_API int cwm_segment_step(const cwm_segment_step_args* args);
 
+typedef struct cwm_segment_merge_args {
+    uint32_t struct_size;            /* sizeof(cwm_segment_merge_args); anything else: CWM_ERR_INVALID naming struct_size */
+    /* read: batch, T (must be 2), H, W, P and the stream.  Every other field of base is ignored, base.struct_size included */
+    cwm_patch_error_args base;
+    int32_t K;                       /* 1 .. 64 candidate segments per row */
+    const uint8_t* segs_dev;         /* candidate (b, k) is the contiguous H W bytes at segs_dev + b seg_strides[0] + k seg_strides[1]; nonzero = in */
+    int64_t seg_strides[2];          /* elements (bytes), not negative: a slice [:, :k] of a [B, Kmax, H, W] buffer, or a [B K, H, W] result, is read in place */
+    const float* scores_dev;         /* [B, K] or NULL: every score 0, which gives index order */
+    int32_t min_area, max_area;      /* >= 0 pixels; max_area == 0 means H W */
+    float iou_thresh, contain_thresh;
+    int32_t absorb;                  /* 0 / 1: paint the absorbed candidates' pixels with their absorber's label */
+    void* work_dev;                  /* 16-byte aligned; its contents on entry do not matter */
+    uint64_t work_bytes;             /* >= cwm_segment_merge_work_bytes(batch, K, H, W) */
+    uint8_t* labels_dev;             /* out [B, H, W] or NULL: 0 = no object, m = 1 .. num_labels */
+    int32_t* owner_dev;              /* out [B, K] or NULL */
+    int32_t* area_dev;               /* out [B, K] or NULL */
+    int32_t* label_area_dev;         /* out [B, K] or NULL */
+    int32_t* inter_dev;              /* out [B, K, K] or NULL */
+    float* cover_dev;                /* out [B, H/P, W/P] or NULL */
+    int32_t* stats_dev;              /* out [B, 4] or NULL: n_valid, num_labels, labelled pixels, n_absorbed */
+} cwm_segment_merge_args;
+
+/* Scene segmentation, the merge: K candidate segments per row -- what K seeds of cwm_segment_step found -- become one label map on the device, without a
+ * read-back.  No counterpart in the reference, whose README names the use and lists the algorithm as coming.
+ *   With gh = H/P, gw = W/P, per row b, in this order:
+ *   1 area        area[k] = the number of nonzero pixels of candidate k
+ *   2 valid       valid[k] = area[k] >= max(1, min_area) && area[k] <= max_area (0: H W).  An empty segment is never valid
+ *   3 inter       inter[j][k] = the number of pixels in both j and k, all K K pairs, valid or not: symmetric, the diagonal is area
+ *   4 order       the valid candidates in the order of cwm_unmask_step: the higher score first, a NaN above every number, -0 equal to +0, the lower index first
+ *   5 suppression walk the order.  k is ABSORBED by the first already-kept j, in the order they were kept, for which
+ *                     (float)inter[j][k] > iou_thresh * (float)(area[j] + area[k] - inter[j][k])   or
+ *                     (float)inter[j][k] > contain_thresh * (float)min(area[j], area[k])
+ *                 (one fp32 multiply and one compare each; a NaN threshold compares false); otherwise k is KEPT and gets the next label 1, 2, ....  Always the
+ *                 candidates' own segments, never a union: the result does not chain.  owner[k] = k's label if kept, its absorber's if absorbed, 0 if not valid
+ *   6 paint       the painting set of label m: its keeper's segment, plus the segments of the candidates it absorbed when `absorb` is set.  labels[p] = the
+ *                 lowest m whose painting set holds p, 0 where there is none: overlaps between kept objects go to the higher-ranked one.  A label's region
+ *                 may end up disconnected
+ *   7 label_area  label_area[m - 1] = the number of pixels with label m, m = 1 .. K; 0 for labels that do not exist
+ *   8 cover       cover[cell] = (#pixels of the cell with a label > 0) / (float)(P P): exact
+ *   9 stats       (n_valid, num_labels, #labelled pixels, n_absorbed = n_valid - num_labels)
+ * Five kernels behind one memset: the bytes are packed into bit words once, pair intersections are popcounts of ANDed words, one wave per row ranks and walks the
+ * candidates, one workgroup per patch row paints.  Sums across workgroups are INTEGER atomics into tables the call zeroes itself on the stream: the same bits
+ * in any order, two calls on the same inputs give the same bits, and the contents of work_dev on entry do not matter.
+ * Asynchronous on base.stream: nothing is allocated and the host is not synchronised.  No content of a device table (NaN and inf scores among them) makes the
+ * call read or write outside its buffers.
+ * Limits: 1 <= K <= 64; P 4, 8 or 16; H % P == 0, W % P == 0; H W <= 2^18; (H/P)(W/P) <= 4096; batch <= 65535; min_area, max_area >= 0; absorb 0 or 1; work_dev
+ * non-NULL and 16-byte aligned, work_bytes large enough.  Argument errors: CWM_ERR_INVALID with a message that names the field, before anything is launched.
+ * cwm_segment_merge_work_bytes returns 0 for sizes the call would refuse. */
+CWM_API int cwm_segment_merge(const cwm_segment_merge_args* args);
+CWM_API size_t cwm_segment_merge_work_bytes(int B, int K, int H, int W);
+
 /* `RectangularizeMasks` (masking.py:90-132) on device masks without reading them back.  The reference equalises the masked count of
  * the rows of a batch by un-masking / masking `torch.randperm(#candidates)[:surplus]` of a row's masked / visible tokens (one draw of the global CPU
  * generator per changed row, in row order).  The draws depend on the per-row COUNTS alone, so:
