@@ -210,6 +210,35 @@ class CwmSegmentMergeArgs(C.Structure):
     ]
 
 
+class CwmSeedSelectArgs(C.Structure):
+    """cwm_seed_select_args (include/cwm_hip.h): cwm_patch_error_args as `base` (batch, H, W, P and the stream are read), the score map as pixels by two strides
+    or as cells, the free cells, the race's draws, the prior cells, the selection rule, the workspace and the outputs; new_seed_select_args() sets struct_size"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", CwmPatchErrorArgs),
+        ("map_dev", C.c_void_p),
+        ("cells", C.c_int32),
+        ("map_strides", C.c_int64 * 2),
+        ("free_dev", C.c_void_p),
+        ("e_dev", C.c_void_p),
+        ("prior_dev", C.c_void_p),
+        ("n_prior", C.c_int32),
+        ("K", C.c_int32),
+        ("radius", C.c_int32),
+        ("peaks_only", C.c_int32),
+        ("abs_thresh", C.c_float),
+        ("rel_thresh", C.c_float),
+        ("work_dev", C.c_void_p),
+        ("work_bytes", C.c_uint64),
+        ("seeds_dev", C.c_void_p),
+        ("cells_dev", C.c_void_p),
+        ("values_dev", C.c_void_p),
+        ("pooled_dev", C.c_void_p),
+        ("peaks_dev", C.c_void_p),
+        ("stats_dev", C.c_void_p),
+    ]
+
+
 class CwmConjConfig(C.Structure):
     _fields_ = [
         ("main", CwmConfig),
@@ -637,6 +666,12 @@ def new_segment_merge_args() -> CwmSegmentMergeArgs:
     return a
 
 
+def new_seed_select_args() -> CwmSeedSelectArgs:
+    a = new_args(CwmSeedSelectArgs)
+    a.base.T = 1
+    return a
+
+
 def fill_patch_args(g, *, x=None, target=None, mask=None, region=None, y=None, geometry, n_vis=0, frame=-1, map=None, mean=None, scratch=None, stream):
     """Fills a cwm_patch_error_args -- alone, or the `.base` of the other read-outs' -- from tensors: the one place that knows its field order.  `x` and `target`
     are [B,T,C,H,W]-SHAPED views of any (b, t, c) strides, whatever the order of the tensor beneath ([B,C,T,H,W] permuted, a batch stride of 0); their image
@@ -707,6 +742,8 @@ SIGNATURES = {
     "cwm_segment_step": (C.c_int, [C.POINTER(CwmSegmentStepArgs)]),
     "cwm_segment_merge": (C.c_int, [C.POINTER(CwmSegmentMergeArgs)]),
     "cwm_segment_merge_work_bytes": (C.c_size_t, [C.c_int] * 4),
+    "cwm_seed_select": (C.c_int, [C.POINTER(CwmSeedSelectArgs)]),
+    "cwm_seed_select_work_bytes": (C.c_size_t, [C.c_int] * 4),
     "cwm_mask_row_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_mask_flip_picks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cwm_prompt_table_expand": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),

@@ -375,6 +375,34 @@ struct SegmentStepParams {
 int check_segment_step(const SegmentStepParams& p);  // 0 or CWM_ERR_INVALID with a message that names the field
 int launch_segment_step(const SegmentStepParams& p, hipStream_t stream);
 
+// Seed selection (seed_select.hip; the definition: include/cwm_hip.h cwm_seed_select): a score map pooled to the patch grid, its peaks, and K rounds of
+// arg-max under non-maximum suppression.  No allocation, no synchronisation, no atomics.
+constexpr int kSeedMaxPicks = 64;
+constexpr int kSeedMaxRadius = 64;
+constexpr int kSeedMaxPrior = 64;
+constexpr int kSeedMaxPixels = 1 << 18;
+struct SeedSelectParams {
+    const float* map;        // pixels: (b, y, x) at b sb + y sr + x; cells: [B][n] contiguous
+    int cells;               // 0 pixels, 1 cells
+    int64_t sb, sr;
+    int B, H, W, P;
+    const uint8_t* free;     // [B][n] or nullptr
+    const float* e;          // [B][n] or nullptr: race mode
+    const int* prior;        // [B][n_prior] or nullptr
+    int n_prior, K, radius, peaks_only;
+    float abs_thresh, rel_thresh;
+    float* w_pooled;         // workspace (pixels form): [B][n] v ...
+    uint8_t* w_offset;       // ... and [B][n] the seed pixel's offset py P + px inside its cell
+    int* seeds;              // [B][K][2] or nullptr
+    int* picks;              // [B][K] or nullptr
+    float* values;           // [B][K] or nullptr
+    float* pooled;           // [B][n] or nullptr
+    uint8_t* peaks;          // [B][n] or nullptr
+    int* stats;              // [B][4] or nullptr
+};
+int launch_seed_pool(const SeedSelectParams& p, hipStream_t stream);    // pixels form: fills w_pooled and w_offset
+int launch_seed_select(const SeedSelectParams& p, hipStream_t stream);  // the pool pass where the form needs it, then the selection
+
 struct ShiftPromptParams {
     const float* x;         // [B][T][C][H][W] contiguous frames
     int B, S, T, C, H, W, P, frame, fix_passive;

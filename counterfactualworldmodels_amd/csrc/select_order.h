@@ -1,4 +1,4 @@
-// The ordering rule of the device selections (cwm_unmask_step, cwm_segment_step), stated once: cells are ranked by (class, key descending with a NaN above every
+// The ordering rule of the device selections (cwm_unmask_step, cwm_segment_step, cwm_segment_merge, cwm_seed_select), stated once: cells are ranked by (class, key descending with a NaN above every
 // number and -0 equal to +0, index ascending), packed into one 64-bit rank word, and k rounds of arg-max over a workgroup of kSelThreads threads take the first k.
 // Fixed order, no atomics.  Cell c belongs to thread c % kSelThreads.
 #pragma once
@@ -46,6 +46,27 @@ __device__ __forceinline__ void um_select_rounds(unsigned long long* comp, int n
         on_pick(r, cell);
         if (cell >= 0 && (cell & (kSelThreads - 1)) == tid) {
             comp[cell] = 0;
+            best = 0;
+            for (int c = tid; c < n; c += kSelThreads) best = um_max64(best, comp[c]);
+        }
+    }
+}
+
+// The same rounds where a pick removes more than itself (cwm_seed_select: every candidate within a window of the pick): removes(cell, c) says whether the pick
+// `cell` takes candidate c out; it must hold for c == cell.  In every round each thread clears its own cells, and a thread that cleared anything scans its cells
+// again.  removes() must depend on the geometry alone, so that the loop reads and writes comp[0 .. n) whatever the words hold.
+template <class OnPick, class Removes>
+__device__ __forceinline__ void um_select_rounds_removing(unsigned long long* comp, int n, int k, unsigned long long best, unsigned long long (*xch)[4], OnPick on_pick,
+                                                          Removes removes) {
+    const int tid = threadIdx.x;
+    for (int r = 0; r < k; ++r) {
+        const int cell = um_rank_cell(um_block_max(best, xch[(r + 1) & 1]));
+        on_pick(r, cell);
+        if (cell < 0) continue;
+        bool cleared = false;
+        for (int c = tid; c < n; c += kSelThreads)
+            if (comp[c] && removes(cell, c)) comp[c] = 0, cleared = true;
+        if (cleared) {
             best = 0;
             for (int c = tid; c < n; c += kSelThreads) best = um_max64(best, comp[c]);
         }

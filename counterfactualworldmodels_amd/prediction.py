@@ -1036,6 +1036,19 @@ class PredictorBasedGenerator(nn.Module):
         value = value - value.amin((-2, -1))
         return value / value.amax((-2, -1)).clamp(min=eps)
 
+    def predict_keypoints(self, x, num_points=8, radius=2, rel_thresh=0.1, power=8):
+        """The K = num_points keypoints of every movie of x [B,T,C,H,W] (no counterpart in the reference, which only ever samples from the map): the strongest
+        local maxima of `predict_keypoints_distribution(x, power)` of the first frame pair, at least rel_thresh of the row's maximum and more than `radius`
+        patches (Chebyshev) apart -- `seed_select.select_seeds(peaks_only=True)`.  Returns (points [B,K,2] int32 (y, x), (-1, -1) where a row has fewer
+        peaks; values [B,K], the map at the points, 0 there).  Without a keypoint predictor the map is constant and has no peaks worth the name: ValueError."""
+        if self.keypoint_predictor is None:
+            raise ValueError("predict_keypoints needs a generator built with a keypoint_predictor")
+        from .seed_select import select_seeds
+        from .segment_merge import keypoints_distribution
+
+        sel = select_seeds(keypoints_distribution(self, x, power), num_points, self.patch_size[-1], radius=radius, peaks_only=True, rel_thresh=rel_thresh)
+        return sel.seeds, sel.values
+
     def forward(self, x, mask=None, frame=None, *args, **kwargs):
         self.set_input(x, mask)
         if mask is None:

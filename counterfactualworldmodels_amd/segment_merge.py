@@ -8,7 +8,8 @@ The definition is the header comment of csrc/segment_merge.hip (include/cwm_hip.
 integer or an integer divided by P P and each threshold test is one float32 multiply and one compare, so both give equal results.
 
 `segment_scene` is the loop on top: rounds of seeds, each run through `FlowGenerator.segment_spelke_object`, merged after every round, the next round's seeds
-drawn among the patches the merge leaves uncovered."""
+drawn among the patches the merge leaves uncovered -- by the exponential race, or through `seed_select.select_seeds` spaced and on the peaks of a keypoint or
+movability map."""
 from __future__ import annotations
 
 import ctypes as C
@@ -185,6 +186,19 @@ def cell_centres(cells, gw, P):
     return torch.where((cells >= 0)[..., None], yx, torch.full_like(yx, -1)).to(torch.int32)
 
 
+def seed_cells(seeds, gw, P):
+    """[B,k] int32 cells of the seeds [B,k,2] (y, x), -1 for a dead slot (-1, -1); x is clamped into the image as `segment_step` clamps a seed (a y below the
+    image gives a cell past the grid, which `select_seeds` ignores)"""
+    cells = torch.div(seeds[..., 0], P, rounding_mode="floor") * gw + torch.div(seeds[..., 1].clamp(0, gw * P - 1), P, rounding_mode="floor")
+    return torch.where(seeds[..., 0] >= 0, cells, torch.full_like(cells, -1)).to(torch.int32)
+
+
+def keypoints_distribution(G, movie, power=8):
+    """[B,H,W]: `G.predict_keypoints_distribution` of the first frame pair of every movie, one row at a time (as in the reference, its normalisation broadcasts
+    for a single row only)"""
+    return torch.cat([G.predict_keypoints_distribution(movie[b:b + 1], power=power)[:, 0] for b in range(movie.shape[0])])
+
+
 def segment_scores(segment, frac, score):
     """[R] float32 scores of R segments [R,H,W] bool with their vote fractions: "votes" the mean vote fraction inside the segment, "area" the area"""
     area = segment.flatten(1).sum(1).to(torch.float32)
@@ -196,9 +210,22 @@ def segment_scores(segment, frac, score):
 
 
 def segment_scene(G, x, seeds=None, num_seeds=8, num_rounds=1, seed_distribution=None, generator=None, score="votes", seed_batch_size=None, free_below=None,
-                  min_area=None, max_area_frac=0.5, iou_thresh=0.5, contain_thresh=0.6, absorb=True, **kwargs) -> SceneSegmentation:
+                  min_area=None, max_area_frac=0.5, iou_thresh=0.5, contain_thresh=0.6, absorb=True, seed_mode="sample", seed_radius=0, seed_rel_thresh=0.,
+                  **kwargs) -> SceneSegmentation:
     """`FlowGenerator.segment_scene` (its docstring says what this does); G is the generator"""
+    from .seed_select import MAX_RADIUS, select_seeds
+
     K, R = int(num_seeds), int(num_rounds)
+    if seed_mode not in ("sample", "peaks"):
+        raise ValueError("segment_scene: seed_mode = %r, 'sample' or 'peaks'" % (seed_mode,))
+    seed_radius = int(seed_radius)
+    if not 0 <= seed_radius <= MAX_RADIUS:
+        raise ValueError("segment_scene: seed_radius = %d cells, 0 .. %d" % (seed_radius, MAX_RADIUS))
+    if isinstance(seed_distribution, str):
+        if seed_distribution != "keypoints":
+            raise ValueError("segment_scene: seed_distribution = %r: a tensor, a callable, None or 'keypoints'" % (seed_distribution,))
+        if getattr(G, "keypoint_predictor", None) is None:
+            raise ValueError("segment_scene: seed_distribution = 'keypoints' needs a generator built with a keypoint_predictor")
     if K < 1 or R < 1 or K * R > MAX_K:
         raise ValueError("segment_scene: num_rounds * num_seeds = %d x %d candidates, 1 .. %d" % (R, K, MAX_K))
     if score not in ("votes", "area"):
@@ -207,7 +234,16 @@ def segment_scene(G, x, seeds=None, num_seeds=8, num_rounds=1, seed_distribution
     B, (H, W) = movie.shape[0], movie.shape[-2:]
     P, dev = G.patch_size[-1], movie.device
     gw = W // P
+    if isinstance(seed_distribution, str):
+        seed_distribution = keypoints_distribution(G, movie)
+    elif callable(seed_distribution) and not torch.is_tensor(seed_distribution):
+        seed_distribution = seed_distribution(movie)
+    if torch.is_tensor(seed_distribution) and seed_distribution.dim() == 4 and seed_distribution.shape[1] == 1:
+        seed_distribution = seed_distribution[:, 0]
     p = patch_distribution(seed_distribution, B, H, W, P, dev)
+    # seed_mode="peaks" on a map of pixels: the seeds are the pixels where the cells peak, not the cells' centres
+    pixels = seed_distribution.to(device=dev, dtype=torch.float32) if torch.is_tensor(seed_distribution) and tuple(seed_distribution.shape) == (B, H, W) else None
+    select = seed_mode == "peaks" or seed_radius > 0  # (otherwise: the draw of draw_seed_cells, as before there was a choice)
     if seeds is not None:
         seeds = torch.as_tensor(seeds).to(device=dev, dtype=torch.int32)
         if tuple(seeds.shape) != (B, K, 2):
@@ -223,10 +259,17 @@ def segment_scene(G, x, seeds=None, num_seeds=8, num_rounds=1, seed_distribution
     merged = None
     with torch.random.fork_rng(devices=[]):  # (the counterfactual driver draws on torch's global CPU generator; the caller's stream of draws is put back)
         for r in range(R):
+            prior = seed_cells(all_seeds[:, :r * K], gw, P) if select and r > 0 else None
             if r == 0 and seeds is not None:
                 rs = seeds
-            else:
+            elif not select:
                 rs = cell_centres(draw_seed_cells(p, free, K, generator), gw, P)
+            elif seed_mode == "peaks":
+                rs = select_seeds(pixels if pixels is not None else p.reshape(B, H // P, gw), K, P, shape=(H, W), radius=seed_radius, peaks_only=True,
+                                  rel_thresh=seed_rel_thresh, free=free, prior=prior).seeds
+            else:
+                e = torch.empty(p.shape, device=dev, dtype=torch.float32).exponential_(generator=generator)  # (the draw of draw_seed_cells)
+                rs = select_seeds(p.reshape(B, H // P, gw), K, P, shape=(H, W), radius=seed_radius, rel_thresh=seed_rel_thresh, free=free, e=e, prior=prior).seeds
             alive = (rs[..., 0] >= 0).reshape(B * K)
             flat = rs.reshape(B * K, 2).clamp(min=0)  # (a dead slot runs on pixel (0, 0) and its segment is cleared)
             segs, sc = [], []

@@ -480,8 +480,17 @@ class FlowGenerator(PredictorBasedGenerator):
         return SM.segment_merge(segments, scores, self.patch_size[-1], min_area=min_area, max_area=max_area, iou_thresh=iou_thresh, contain_thresh=contain_thresh,
                                 absorb=absorb, want_inter=want_inter)
 
+    def select_seeds(self, map, k=8, **kw):
+        """At most k well-spaced seed pixels [B,k,2] per row of a score map -- [B,H,W] pixels or [B,gh,gw] cells of this generator's patch grid: the strongest
+        first, or with `e` an exponential race, under non-maximum suppression of `radius` cells (`seed_select.select_seeds` has the keywords).  Returns a
+        `SeedSelection`.  Device tensors take one library call (cwm_seed_select, nothing read back), CPU tensors the same definition in torch."""
+        from . import seed_select as SS
+
+        return SS.select_seeds(map, k, self.patch_size[-1], **kw)
+
     def segment_scene(self, x, seeds=None, num_seeds=8, num_rounds=1, seed_distribution=None, generator=None, score="votes", seed_batch_size=None, free_below=None,
-                      min_area=None, max_area_frac=0.5, iou_thresh=0.5, contain_thresh=0.6, absorb=True, **kwargs):
+                      min_area=None, max_area_frac=0.5, iou_thresh=0.5, contain_thresh=0.6, absorb=True, seed_mode="sample", seed_radius=0, seed_rel_thresh=0.,
+                      **kwargs):
         """The Spelke objects of every movie of x [B,T,C,H,W] as one label map: `num_rounds` rounds of `num_seeds` seeds, each seed run through
         `segment_spelke_object` (x repeated over the round's seeds, in chunks of `seed_batch_size` rows; **kwargs pass through: num_iters, num_samples, the
         thresholds, raft_iters, ...), every round written into one [B, num_rounds num_seeds, H, W] buffer (at most 64 candidates) and one `segment_merge` over all
@@ -492,7 +501,13 @@ class FlowGenerator(PredictorBasedGenerator):
         among those the merge leaves uncovered (cover == 0, or cover < free_below) -- without replacement and in proportion to `seed_distribution` ([B,H,W],
         averaged to patches, or [B,gh,gw]; None: uniform) by the exponential race of `frontier_unmask(sample=True)`: key = p / e, e from `generator`, in the order
         of `masking.select_reveal`.  A seed is the centre pixel of its cell; a slot that finds no cell is a dead row: seed (-1, -1), an all-zero candidate, never
-        valid.  `predict_keypoints_distribution` and the movability map are the natural seed distributions; they are not wired in.
+        valid.  seed_distribution may also be "keypoints" (`predict_keypoints_distribution` of the movie; needs a keypoint_predictor) or a callable
+        f(movie [B,T,C,H,W]) -> [B,H,W]; a movability map is passed as a tensor, `M(x)[:, 0]` of a `MovabilityPredictor` M.
+        seed_mode="sample" with seed_radius=0 is the draw just described.  With seed_radius > 0 the same exponential draw runs through `select_seeds`: picks of
+        a round keep more than seed_radius cells (Chebyshev) from each other and from every seed of the earlier rounds.  seed_mode="peaks" draws nothing: the
+        seeds are the strongest local maxima of the map among the free cells (`select_seeds(peaks_only=True)`, in round 0 too unless `seeds` is given), at
+        least seed_rel_thresh of the row's maximum, spaced and kept off earlier seeds in the same way; on a [B,H,W] map a seed is the pixel where its cell
+        peaks, not the cell's centre.
         Everything stays on x's device and the loop reads nothing back beyond what the counterfactual driver does; it runs inside
         torch.random.fork_rng(devices=[]), so the caller's global CPU stream of draws is left as it was.  Returns a `SceneSegmentation` (labels [B,H,W] uint8,
         num_labels [B], seeds, segments [B,K,H,W] bool, scores, owner, label_area, cover, stats)."""
@@ -500,7 +515,7 @@ class FlowGenerator(PredictorBasedGenerator):
 
         return SM.segment_scene(self, x, seeds=seeds, num_seeds=num_seeds, num_rounds=num_rounds, seed_distribution=seed_distribution, generator=generator, score=score,
                                 seed_batch_size=seed_batch_size, free_below=free_below, min_area=min_area, max_area_frac=max_area_frac, iou_thresh=iou_thresh,
-                                contain_thresh=contain_thresh, absorb=absorb, **kwargs)
+                                contain_thresh=contain_thresh, absorb=absorb, seed_mode=seed_mode, seed_radius=seed_radius, seed_rel_thresh=seed_rel_thresh, **kwargs)
 
     # ---- statistics over the flow samples (segmentation.py:250-276, 479-547): device kernels, see flowstats.py ----------
     def compute_flow_samples_magnitude(self, flows, normalize=True, dim=-4, eps=1e-2):

@@ -479,6 +479,60 @@ typedef struct cwm_segment_merge_args {
 CWM_API int cwm_segment_merge(const cwm_segment_merge_args* args);
 CWM_API size_t cwm_segment_merge_work_bytes(int B, int K, int H, int W);
 
+typedef struct cwm_seed_select_args {
+    uint32_t struct_size;            /* sizeof(cwm_seed_select_args); anything else: CWM_ERR_INVALID naming struct_size */
+    /* read: batch, H, W, P and the stream.  Every other field of base is ignored, base.struct_size and base.T included */
+    cwm_patch_error_args base;
+    const float* map_dev;            /* the score map: pixels (cells == 0) or one value per cell (cells == 1) */
+    int32_t cells;                   /* 0: map [B, H, W], pixel (b, y, x) at map_dev[b map_strides[0] + y map_strides[1] + x] (elements), so a channel of a
+                                      * [B, C, H, W] tensor or a padded buffer is read in place; 1: map [B, H/P, W/P] contiguous, map_strides ignored */
+    int64_t map_strides[2];          /* batch and row stride, not negative; the row stride is at least W */
+    const uint8_t* free_dev;         /* [B, n] or NULL: a cell with 0 is no candidate; NULL = every cell is free */
+    const float* e_dev;              /* [B, n] or NULL: non-NULL selects race mode, key = max(v, 0) / e */
+    const int32_t* prior_dev;        /* [B, n_prior] or NULL (with n_prior 0): cells of earlier seeds; entries outside 0 .. n-1 (-1 by convention) are ignored */
+    int32_t n_prior;                 /* 0 .. 64 */
+    int32_t K;                       /* 1 .. 64 seeds per row */
+    int32_t radius;                  /* 0 .. 64, Chebyshev, in cells: the spacing of the picks, the window of the peak test, the reach of the prior cells */
+    int32_t peaks_only;              /* 0 / 1: only peaks (step 4) are candidates */
+    float abs_thresh, rel_thresh;    /* abs_thresh: not a NaN, -inf disables it; rel_thresh: finite, <= 0 disables it */
+    void* work_dev;                  /* pixels form only: 16-byte aligned; its contents on entry do not matter.  Not read in the cells form (may be NULL) */
+    uint64_t work_bytes;             /* pixels form: >= cwm_seed_select_work_bytes(batch, H, W, P) */
+    int32_t* seeds_dev;              /* out [B, K, 2] (y, x) or NULL: (-1, -1) for a dead slot */
+    int32_t* cells_dev;              /* out [B, K] or NULL: -1 for a dead slot */
+    float* values_dev;               /* out [B, K] or NULL: v of the picked cell, 0 for a dead slot */
+    float* pooled_dev;               /* out [B, n] or NULL: v */
+    uint8_t* peaks_dev;              /* out [B, n] or NULL: step 4, written whether peaks_only is set or not */
+    int32_t* stats_dev;              /* out [B, 4] or NULL: free non-NaN cells, candidates, picks made, 0 */
+} cwm_seed_select_args;
+
+/* Seed selection: a score map -- a keypoint map, a movability map, the patch distribution of a scene loop -- becomes at most K well-spaced seed pixels per row on
+ * the device, without a read-back: the strongest peaks first, or an exponential race in proportion to the map, both under non-maximum suppression and both
+ * excluding the neighbourhood of earlier seeds.  No counterpart in the reference, whose `sample_patches_from_energy` and `sample_and_visualize_keypoints` only
+ * ever sample and never space.
+ *   With gh = H/P, gw = W/P, n = gh gw, cell c = i gw + j, r = radius, per row b, in this order:
+ *   1 pool        pixels form: v[c] = the maximum over the P P pixels of cell c, NaN pixels ignored; the seed pixel of c is the first pixel in row-major order
+ *                 that attains it (-0 and +0 are equal; v is that pixel's own value); a cell whose pixels are all NaN has v = NaN (and no seed pixel).
+ *                 cells form: v[c] = map[c]; the seed pixel is the cell's centre (i P + P/2, j P + P/2)
+ *   2 row maximum m = the maximum of v over the non-NaN cells of the row, free or not; a row without one has no candidates
+ *   3 threshold   t = abs_thresh if rel_thresh <= 0, else max(abs_thresh, rel_thresh * m): one fp32 multiply
+ *   4 peak        c is a peak iff v[c] is not a NaN and its word (v in the order of cwm_unmask_step, the lower index higher) is the maximum of the words of the
+ *                 non-NaN cells within Chebyshev distance r, free or not, the window clipped at the border: a plateau has one peak per window, its lowest index
+ *   5 candidates  c is free, v[c] is not a NaN, v[c] >= t, c is a peak (with peaks_only), and no prior cell lies within Chebyshev distance r of c (r = 0: the
+ *                 prior cells themselves are excluded)
+ *   6 key         v[c]; in race mode max(v[c], 0) / e[b][c], one correctly rounded division (a NaN key ranks above every number, as in cwm_unmask_step)
+ *   7 selection   K rounds: the candidate that is first in the order of cwm_unmask_step (the higher key first, -0 equal to +0, the lower index first) is picked,
+ *                 then every candidate within Chebyshev distance r of it, itself included, is removed.  A round without a candidate is a dead slot
+ * Two kernels: the pool pass streams the map once (workgroups over (band of cells, cell row, b), 16-byte loads where the addresses allow them, a fixed-order
+ * reduction) into work_dev; one workgroup per row then holds v and the rank words in LDS, tests peaks by a separable windowed maximum and runs the rounds.
+ * The cells form skips the pool pass.  Asynchronous on base.stream: nothing is allocated, the host is not synchronised, no atomics, fixed order -- two calls on
+ * the same inputs give the same bits, and the contents of work_dev on entry do not matter.  No content of a device table (NaN, inf, prior entries out of range)
+ * makes the call read or write outside its buffers.
+ * Limits: P 4, 8 or 16; H % P == 0, W % P == 0; H W <= 2^18; n <= 4096; batch <= 65535; 1 <= K <= 64; 0 <= radius <= 64; 0 <= n_prior <= 64; at least one
+ * output.  Argument errors: CWM_ERR_INVALID with a message that names the field, before anything is launched.  cwm_seed_select_work_bytes returns 0 for sizes
+ * the call would refuse. */
+CWM_API int cwm_seed_select(const cwm_seed_select_args* args);
+CWM_API size_t cwm_seed_select_work_bytes(int B, int H, int W, int P);
+
 /* `RectangularizeMasks` (masking.py:90-132) on device masks without reading them back.  The reference equalises the masked count of
  * the rows of a batch by un-masking / masking `torch.randperm(#candidates)[:surplus]` of a row's masked / visible tokens (one draw of the global CPU
  * generator per changed row, in row order).  The draws depend on the per-row COUNTS alone, so:
