@@ -239,6 +239,45 @@ class CwmSeedSelectArgs(C.Structure):
     ]
 
 
+class CwmSegmentTrackArgs(C.Structure):
+    """cwm_segment_track_args (include/cwm_hip.h): cwm_patch_error_args as `base` (batch, H, W and the stream are read), the previous track map and this frame's
+    label map by a row stride each, the backward flow by two strides, the state in, the linking rule, the workspace and the outputs; new_segment_track_args()
+    sets struct_size"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", CwmPatchErrorArgs),
+        ("prev_dev", C.c_void_p),
+        ("prev_stride", C.c_int64),
+        ("cur_dev", C.c_void_p),
+        ("cur_stride", C.c_int64),
+        ("flow_dev", C.c_void_p),
+        ("flow_strides", C.c_int64 * 2),
+        ("track_id_in_dev", C.c_void_p),
+        ("age_in_dev", C.c_void_p),
+        ("next_id_in_dev", C.c_void_p),
+        ("iou_thresh", C.c_float),
+        ("min_inter", C.c_int32),
+        ("min_area", C.c_int32),
+        ("max_age", C.c_int32),
+        ("carry", C.c_int32),
+        ("work_dev", C.c_void_p),
+        ("work_bytes", C.c_uint64),
+        ("out_dev", C.c_void_p),
+        ("out_stride", C.c_int64),
+        ("track_id_out_dev", C.c_void_p),
+        ("age_out_dev", C.c_void_p),
+        ("next_id_out_dev", C.c_void_p),
+        ("area_dev", C.c_void_p),
+        ("bbox_dev", C.c_void_p),
+        ("moments_dev", C.c_void_p),
+        ("slot_of_cur_dev", C.c_void_p),
+        ("linked_cur_dev", C.c_void_p),
+        ("table_dev", C.c_void_p),
+        ("warped_dev", C.c_void_p),
+        ("stats_dev", C.c_void_p),
+    ]
+
+
 class CwmConjConfig(C.Structure):
     _fields_ = [
         ("main", CwmConfig),
@@ -672,6 +711,12 @@ def new_seed_select_args() -> CwmSeedSelectArgs:
     return a
 
 
+def new_segment_track_args() -> CwmSegmentTrackArgs:
+    a = new_args(CwmSegmentTrackArgs)
+    a.base.T = 1
+    return a
+
+
 def fill_patch_args(g, *, x=None, target=None, mask=None, region=None, y=None, geometry, n_vis=0, frame=-1, map=None, mean=None, scratch=None, stream):
     """Fills a cwm_patch_error_args -- alone, or the `.base` of the other read-outs' -- from tensors: the one place that knows its field order.  `x` and `target`
     are [B,T,C,H,W]-SHAPED views of any (b, t, c) strides, whatever the order of the tensor beneath ([B,C,T,H,W] permuted, a batch stride of 0); their image
@@ -744,6 +789,8 @@ SIGNATURES = {
     "cwm_segment_merge_work_bytes": (C.c_size_t, [C.c_int] * 4),
     "cwm_seed_select": (C.c_int, [C.POINTER(CwmSeedSelectArgs)]),
     "cwm_seed_select_work_bytes": (C.c_size_t, [C.c_int] * 4),
+    "cwm_segment_track": (C.c_int, [C.POINTER(CwmSegmentTrackArgs)]),
+    "cwm_segment_track_work_bytes": (C.c_size_t, [C.c_int] * 3),
     "cwm_mask_row_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_mask_flip_picks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cwm_prompt_table_expand": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),

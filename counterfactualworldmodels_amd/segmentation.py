@@ -517,6 +517,33 @@ class FlowGenerator(PredictorBasedGenerator):
                                 seed_batch_size=seed_batch_size, free_below=free_below, min_area=min_area, max_area_frac=max_area_frac, iou_thresh=iou_thresh,
                                 contain_thresh=contain_thresh, absorb=absorb, seed_mode=seed_mode, seed_radius=seed_radius, seed_rel_thresh=seed_rel_thresh, **kwargs)
 
+    # ---- scene segments through a movie: label maps linked frame to frame by the backward flow (segment_track.py, csrc/segment_track.hip) ----
+    def track_step(self, state, cur_labels, flow=None, **kw):
+        """One frame of tracking: `state` (a `segment_track.TrackState`, or None for the first frame: no previous frame, every label is born), this frame's label
+        map [B,H,W] uint8 as `segment_scene` returns it (None: the frame is carried by the flow alone) and the flow [B,2,H,W] from this frame to the previous
+        one (`predict_flow(backward=True)` of the pair; None: zero motion).  The previous track map is warped onto this frame, overlaps are counted, tracks and
+        labels are linked one to one (intersection above iou_thresh of the union, the larger overlap first), unlinked tracks coast on the flow for up to
+        max_age frames (carry=True) or end, unlinked labels of at least min_area pixels are born into free slots under new ids.  Keywords: iou_thresh=0.3,
+        min_inter=1, min_area=1, max_age=2, carry=True, want_table, want_warped.  Returns a `TrackStepResult` (state, area, bbox, moments, slot_of_cur,
+        linked_cur, stats).  Device tensors take one library call (cwm_segment_track, nothing read back), CPU tensors the same definition in torch."""
+        from . import segment_track as ST
+
+        return ST.track_step(state, cur_labels, flow, **kw)
+
+    def track_scene(self, x, segment_every=1, flow_kwargs=None, iou_thresh=0.3, min_inter=1, min_area=1, max_age=2, carry=True, return_segmentations=False,
+                    **segment_scene_kwargs):
+        """The Spelke objects of a movie x [B,T,C,H,W] with identities that persist over time.  The movie's backward flows come from ONE call,
+        `predict_flow(x, backward=True, **flow_kwargs)` (so `warm_start=True` and the shared encoders of the package's RAFT apply).  Frames t <= T-2 with
+        t % segment_every == 0 are segmented by `segment_scene(x[:, t:t+2], **segment_scene_kwargs)`, in ascending t on the caller's generator; every other
+        frame, the last one included, has no segmentation and is carried by the flow.  Frame by frame `track_step` links the label maps: frame 0 has no
+        previous frame, so every label is born.  ValueError when max_age < segment_every, or carry is off with segment_every > 1: tracks would die between
+        segmentations.  Nothing is read back beyond what `segment_scene` does.  Returns a `TrackedScene` (labels [B,T,H,W] uint8 slots 1 .. 64; track_id, age,
+        area [B,T,64]; bbox, moments, stats; with return_segmentations the per-frame `SceneSegmentation` objects, None for a carried frame)."""
+        from . import segment_track as ST
+
+        return ST.track_scene(self, x, segment_every=segment_every, flow_kwargs=flow_kwargs, iou_thresh=iou_thresh, min_inter=min_inter, min_area=min_area,
+                              max_age=max_age, carry=carry, return_segmentations=return_segmentations, **segment_scene_kwargs)
+
     # ---- statistics over the flow samples (segmentation.py:250-276, 479-547): device kernels, see flowstats.py ----------
     def compute_flow_samples_magnitude(self, flows, normalize=True, dim=-4, eps=1e-2):
         from . import flowstats

@@ -533,6 +533,74 @@ typedef struct cwm_seed_select_args {
 CWM_API int cwm_seed_select(const cwm_seed_select_args* args);
 CWM_API size_t cwm_seed_select_work_bytes(int B, int H, int W, int P);
 
+typedef struct cwm_segment_track_args {
+    uint32_t struct_size;            /* sizeof(cwm_segment_track_args); anything else: CWM_ERR_INVALID naming struct_size */
+    /* read: batch, H, W and the stream.  Every other field of base is ignored, base.struct_size, base.T and base.P included */
+    cwm_patch_error_args base;
+    const uint8_t* prev_dev;         /* row b: the H W contiguous bytes at prev_dev + b prev_stride, the previous frame's track map (0: none, 1 .. 64: a slot); a
+                                      * frame [:, t] of a [B, T, H, W] buffer is read in place.  NULL: no previous frame */
+    int64_t prev_stride;             /* bytes, not negative */
+    const uint8_t* cur_dev;          /* the same with cur_stride: this frame's label map as cwm_segment_merge writes it.  NULL: no segmentation for this frame */
+    int64_t cur_stride;
+    const float* flow_dev;           /* pixel (b, c, y, x) at flow_dev[b flow_strides[0] + c flow_strides[1] + y W + x] (elements); c = 0 horizontal, 1 vertical, in
+                                      * pixels, from THIS frame to the PREVIOUS one, on this frame's grid.  NULL: zero motion */
+    int64_t flow_strides[2];         /* not negative */
+    const int32_t* track_id_in_dev;  /* [B, 64]: 0 = the slot is free, otherwise its persistent id.  The three state inputs are given together or all NULL (an */
+    const int32_t* age_in_dev;       /* [B, 64]                                                       empty state with next_id 1) */
+    const int32_t* next_id_in_dev;   /* [B] */
+    float iou_thresh;
+    int32_t min_inter, min_area;     /* >= 0 pixels */
+    int32_t max_age;                 /* >= 0 frames a track may coast */
+    int32_t carry;                   /* 0 / 1: unlinked tracks with warped pixels coast */
+    void* work_dev;                  /* 16-byte aligned; its contents on entry do not matter */
+    uint64_t work_bytes;             /* >= cwm_segment_track_work_bytes(batch, H, W) */
+    uint8_t* out_dev;                /* out or NULL: row b is the H W bytes at out_dev + b out_stride (a frame of a [B, T, H, W] buffer is written in place) */
+    int64_t out_stride;              /* bytes, at least H W (read with out_dev only) */
+    int32_t* track_id_out_dev;       /* out [B, 64] or NULL.  The state outputs are separate buffers: in and out may NOT alias */
+    int32_t* age_out_dev;            /* out [B, 64] or NULL */
+    int32_t* next_id_out_dev;        /* out [B] or NULL */
+    int32_t* area_dev;               /* out [B, 64] or NULL */
+    int32_t* bbox_dev;               /* out [B, 64, 4] or NULL: (y0, x0, y1, x1) inclusive, (0, 0, -1, -1) for an empty slot */
+    int64_t* moments_dev;            /* out [B, 64, 2] int64 or NULL: (sum y, sum x) */
+    int32_t* slot_of_cur_dev;        /* out [B, 64] or NULL: entry c-1 = the slot of label c, or 0 */
+    int32_t* linked_cur_dev;         /* out [B, 64] or NULL: entry p-1 = the label linked to slot p, or 0 */
+    int32_t* table_dev;              /* out [B, 65, 65] or NULL: n[c][p] */
+    uint8_t* warped_dev;             /* out [B, H, W] or NULL: w */
+    int32_t* stats_dev;              /* out [B, 8] or NULL: linked, born, coasting, ended, dropped labels, live slots out, labelled pixels, 0 */
+} cwm_segment_track_args;
+
+/* Scene segments through a movie: the previous frame's track map is warped onto this frame by the backward flow, its overlaps with this frame's label map are
+ * counted, tracks and labels are linked one to one, unlinked tracks coast or end, unlinked labels are born into free slots, and the result is painted -- on the
+ * device, one call per frame, without a read-back.  No counterpart in the reference.  There are 64 track SLOTS, numbered 1 .. 64.  Per row b, in this order:
+ *   0 inputs   as described at their fields.  A prev or cur byte above 64 counts as 0; a prev slot whose track_id_in is 0 counts as 0.  A slot is LIVE iff its
+ *              track_id_in is not 0
+ *   1 warp     fx = (float)x + u, fy = (float)y + v (one fp32 add each); rx = rintf(fx), ry = rintf(fy) (half to even); the source is inside iff
+ *              rx >= 0 && rx <= W-1 && ry >= 0 && ry <= H-1 in fp32 (a NaN or an inf is outside); w(y,x) = prev[(int)ry][(int)rx] inside, else 0
+ *   2 table    n[c][p] = the number of pixels with cur == c and w == p, c and p in 0 .. 64; area_cur[c] = sum_p n[c][p]; area_w[p] = sum_c n[c][p]
+ *   3 link     (c >= 1, p >= 1) is a candidate iff n[c][p] >= max(1, min_inter) and (float)n[c][p] > iou_thresh * (float)(area_cur[c] + area_w[p] - n[c][p])
+ *              (one fp32 multiply and one compare; a NaN threshold compares false).  Up to 64 rounds in the order of cwm_unmask_step: key (float)n[c][p], the
+ *              higher first, ties to the lower index (c-1) 64 + (p-1).  The winner is linked, slot_of[c] = p; every candidate sharing its c or its p is removed
+ *   4 coast    a live slot p that no pair linked COASTS iff carry && area_w[p] > 0 && age_in[p] + 1 <= max_age: it keeps its id, age_out = age_in + 1.
+ *              Otherwise it ENDS: track_id_out = 0, age_out = 0.  A linked slot keeps its id and gets age 0
+ *   5 births   the unlinked labels c >= 1 with area_cur[c] >= max(1, min_area), in ascending c, each take the lowest slot that was free on entry or ended in
+ *              step 4 and that no earlier birth took; id = the running next_id, counting up from next_id_in (32-bit wrap-around), age 0.  Without a free slot
+ *              the label is dropped, slot_of[c] = 0; unlinked labels below min_area are dropped too.  next_id_out = next_id_in + the number of births
+ *   6 paint    out(y,x) = slot_of[cur(y,x)] where that is > 0; elsewhere w(y,x) if that slot coasts; elsewhere 0
+ *   7 read-outs area, bbox, moments per slot s over the pixels of out with value s
+ *   8 tables   slot_of_cur, linked_cur, table, warped as described at their fields
+ *   9 stats    linked, born, coasting, ended, dropped labels (area_cur >= 1 and no slot), live slots out (track_id_out != 0), labelled pixels of out, 0
+ * Four kernels behind one memset: a count pass (16 pixels per thread, 16-byte loads where the addresses allow them, the warped map kept in work_dev), one
+ * workgroup per row that links, coasts and gives birth, a paint pass, one wave per row that writes the read-outs.  Sums across workgroups are INTEGER atomics
+ * into tables the call zeroes itself on the stream: the same bits in any order, two calls on the same inputs give the same bits, and the contents of work_dev on
+ * entry do not matter.  Asynchronous on base.stream: nothing is allocated and the host is not synchronised.  No content of a device buffer (label and slot
+ * bytes above 64, NaN, inf and huge flows, garbage state) makes the call read or write outside its buffers.  The state buffers in and out may not alias, and
+ * out_dev may not overlap prev_dev or cur_dev.
+ * Limits: 1 <= batch <= 65535; H and W positive multiples of 4, H W <= 2^18; max_age, min_inter, min_area >= 0; carry 0 or 1; strides not negative; the three
+ * state inputs together or not at all; at least one output; work_dev non-NULL and 16-byte aligned, work_bytes large enough.  Argument errors: CWM_ERR_INVALID
+ * with a message that names the field, before anything is launched.  cwm_segment_track_work_bytes returns 0 for sizes the call would refuse. */
+CWM_API int cwm_segment_track(const cwm_segment_track_args* args);
+CWM_API size_t cwm_segment_track_work_bytes(int B, int H, int W);
+
 /* `RectangularizeMasks` (masking.py:90-132) on device masks without reading them back.  The reference equalises the masked count of
  * the rows of a batch by un-masking / masking `torch.randperm(#candidates)[:surplus]` of a row's masked / visible tokens (one draw of the global CPU
  * generator per changed row, in row order).  The draws depend on the per-row COUNTS alone, so:
