@@ -278,6 +278,27 @@ class CwmSegmentTrackArgs(C.Structure):
     ]
 
 
+class CwmFlowConsistencyArgs(C.Structure):
+    """cwm_flow_consistency_args (include/cwm_hip.h): cwm_patch_error_args as `base` (batch, H, W, P and the stream are read), the checked flow and the other
+    flow by two strides each, the threshold, the `both` flag and the outputs; new_flow_consistency_args() sets struct_size"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", CwmPatchErrorArgs),
+        ("a_dev", C.c_void_p),
+        ("a_strides", C.c_int64 * 2),
+        ("o_dev", C.c_void_p),
+        ("o_strides", C.c_int64 * 2),
+        ("alpha", C.c_float),
+        ("beta", C.c_float),
+        ("both", C.c_int32),
+        ("code_dev", C.c_void_p),
+        ("res_dev", C.c_void_p),
+        ("masked_dev", C.c_void_p),
+        ("cell_dev", C.c_void_p),
+        ("stats_dev", C.c_void_p),
+    ]
+
+
 class CwmConjConfig(C.Structure):
     _fields_ = [
         ("main", CwmConfig),
@@ -717,6 +738,12 @@ def new_segment_track_args() -> CwmSegmentTrackArgs:
     return a
 
 
+def new_flow_consistency_args() -> CwmFlowConsistencyArgs:
+    a = new_args(CwmFlowConsistencyArgs)
+    a.base.T = 1
+    return a
+
+
 def fill_patch_args(g, *, x=None, target=None, mask=None, region=None, y=None, geometry, n_vis=0, frame=-1, map=None, mean=None, scratch=None, stream):
     """Fills a cwm_patch_error_args -- alone, or the `.base` of the other read-outs' -- from tensors: the one place that knows its field order.  `x` and `target`
     are [B,T,C,H,W]-SHAPED views of any (b, t, c) strides, whatever the order of the tensor beneath ([B,C,T,H,W] permuted, a batch stride of 0); their image
@@ -791,6 +818,7 @@ SIGNATURES = {
     "cwm_seed_select_work_bytes": (C.c_size_t, [C.c_int] * 4),
     "cwm_segment_track": (C.c_int, [C.POINTER(CwmSegmentTrackArgs)]),
     "cwm_segment_track_work_bytes": (C.c_size_t, [C.c_int] * 3),
+    "cwm_flow_consistency": (C.c_int, [C.POINTER(CwmFlowConsistencyArgs)]),
     "cwm_mask_row_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_mask_flip_picks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cwm_prompt_table_expand": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),

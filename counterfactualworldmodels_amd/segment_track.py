@@ -9,7 +9,9 @@ The definition is the header comment of csrc/segment_track.hip (include/cwm_hip.
 to even as rintf does).  Every output is an integer, the warp is one float32 add per coordinate and the link test one float32 multiply and one compare, so both
 give equal results.
 
-`track_sequence` links a given sequence of label maps; `track_scene` is the loop on top of `FlowGenerator.segment_scene` and ONE backward flow call per movie."""
+`track_sequence` links a given sequence of label maps; `track_scene` is the loop on top of `FlowGenerator.segment_scene` and ONE backward flow call per movie.
+Given the forward flows as well (`track_sequence(fwd_flows=...)`, `track_scene(occlusion=True)`), every step warps along the occlusion-masked backward flow of
+`flow_consistency.check`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -282,10 +284,13 @@ def track_step(state, cur_labels, flow=None, **kw) -> TrackStepResult:
     return (track_step_device if _is_cuda(state, cur_labels, flow) else track_step_torch)(state, cur_labels, flow, **kw)
 
 
-def track_sequence(label_maps, back_flows=None, **kw) -> TrackedScene:
+def track_sequence(label_maps, back_flows=None, fwd_flows=None, occ_alpha=0.01, occ_beta=0.5, **kw) -> TrackedScene:
     """Links a given sequence.  label_maps: [B,T,H,W] uint8, or a list of T entries [B,H,W] / None (None: the frame is carried by the flow alone); back_flows
     [B,T,2,H,W] or None (zero motion): entry t is the flow from frame t to frame t - 1 on frame t's grid, entry 0 is not read.  Frame 0 has no previous frame
-    and no flow: every label is born.  Frames and pairs are read in place and, on the device, written in place; nothing is read back in the loop."""
+    and no flow: every label is born.  Frames and pairs are read in place and, on the device, written in place; nothing is read back in the loop.
+    fwd_flows [B,T,2,H,W] (entry t: the flow from frame t - 1 to frame t on frame t - 1's grid, entry 0 is not read) makes the tracking occlusion-aware: step t
+    gets the MASKED backward flow of `flow_consistency.check(back_flows[:, t], fwd_flows[:, t], occ_alpha, occ_beta)` -- NaN where the round trip fails --, so a
+    disoccluded pixel warps nothing in and is 0 in a carried frame.  The masked flows of the whole movie come from ONE library call before the loop."""
     frames = [label_maps[:, t] for t in range(label_maps.shape[1])] if torch.is_tensor(label_maps) else list(label_maps)
     T = len(frames)
     first = next((f for f in frames if f is not None), None)
@@ -295,6 +300,15 @@ def track_sequence(label_maps, back_flows=None, **kw) -> TrackedScene:
     if back_flows is not None and tuple(back_flows.shape) != (B, T, 2, H, W):
         raise ValueError("track_sequence: back_flows must be [B,T,2,H,W] = (%d, %d, 2, %d, %d), got %s" % (B, T, H, W, tuple(back_flows.shape)))
     dev = first.device
+    if fwd_flows is not None:
+        if back_flows is None or tuple(fwd_flows.shape) != tuple(back_flows.shape):
+            raise ValueError("track_sequence: fwd_flows needs back_flows of the same shape [B,T,2,H,W] = (%d, %d, 2, %d, %d), got %s" % (
+                B, T, H, W, tuple(fwd_flows.shape)))
+        if T > 1:
+            from . import flow_consistency as FC
+
+            masked = FC.check(back_flows[:, 1:], fwd_flows[:, 1:].to(back_flows), alpha=occ_alpha, beta=occ_beta, want_masked=True).masked
+            back_flows = torch.cat([masked[:, :1], masked], 1)  # (entry 0 is not read)
     _check(B, H, W, int(kw.get("min_inter", 1)), int(kw.get("min_area", 1)), int(kw.get("max_age", 2)), int(kw.get("carry", True)))
     labels = torch.empty((B, T, H, W), device=dev, dtype=torch.uint8)
     extra = dict(work=torch.empty((work_bytes(B, H, W),), device=dev, dtype=torch.uint8)) if dev.type == "cuda" else {}
@@ -325,8 +339,17 @@ def backward_pair_flows(G, x, flow_kwargs=None):
     return torch.cat([torch.zeros_like(flows[:, :1]), flows.flip(1)], 1)
 
 
+def forward_pair_flows(G, x, flow_kwargs=None):
+    """[B,T,2,H,W]: entry t >= 1 is the flow from frame t - 1 to frame t on frame t - 1's grid, from ONE `G.predict_flow(x)` call; entry 0 is zeros and is not
+    read"""
+    flows = G.predict_flow(x, **(flow_kwargs or {}))  # [B,T-1,2,H,W]: index j is the pair (x[j], x[j+1])
+    if flows.shape[1] != x.shape[1] - 1:
+        raise ValueError("track_scene: predict_flow returned %d pairs for %d frames" % (flows.shape[1], x.shape[1]))
+    return torch.cat([torch.zeros_like(flows[:, :1]), flows], 1)
+
+
 def track_scene(G, x, segment_every=1, flow_kwargs=None, iou_thresh=0.3, min_inter=1, min_area=1, max_age=2, carry=True, return_segmentations=False,
-                **segment_scene_kwargs):
+                occlusion=False, occ_alpha=0.01, occ_beta=0.5, **segment_scene_kwargs):
     """`FlowGenerator.track_scene` (its docstring says what this does); G is the generator"""
     segment_every, max_age = int(segment_every), int(max_age)
     if x.dim() != 5 or x.shape[1] < 2:
@@ -339,9 +362,10 @@ def track_scene(G, x, segment_every=1, flow_kwargs=None, iou_thresh=0.3, min_int
         raise ValueError("track_scene: carry is off with segment_every = %d: tracks would die between segmentations" % segment_every)
     T = x.shape[1]
     back = backward_pair_flows(G, x, flow_kwargs)
+    occ = dict(fwd_flows=forward_pair_flows(G, x, flow_kwargs), occ_alpha=occ_alpha, occ_beta=occ_beta) if occlusion else {}
     scenes = [G.segment_scene(x[:, t:t + 2], **segment_scene_kwargs) if t <= T - 2 and t % segment_every == 0 else None for t in range(T)]
     tracked = track_sequence([None if s is None else s.labels for s in scenes], back, iou_thresh=iou_thresh, min_inter=min_inter, min_area=min_area,
-                             max_age=max_age, carry=carry)
+                             max_age=max_age, carry=carry, **occ)
     if return_segmentations:
         tracked.segmentations = scenes
     return tracked

@@ -531,18 +531,36 @@ class FlowGenerator(PredictorBasedGenerator):
         return ST.track_step(state, cur_labels, flow, **kw)
 
     def track_scene(self, x, segment_every=1, flow_kwargs=None, iou_thresh=0.3, min_inter=1, min_area=1, max_age=2, carry=True, return_segmentations=False,
-                    **segment_scene_kwargs):
+                    occlusion=False, occ_alpha=0.01, occ_beta=0.5, **segment_scene_kwargs):
         """The Spelke objects of a movie x [B,T,C,H,W] with identities that persist over time.  The movie's backward flows come from ONE call,
         `predict_flow(x, backward=True, **flow_kwargs)` (so `warm_start=True` and the shared encoders of the package's RAFT apply).  Frames t <= T-2 with
         t % segment_every == 0 are segmented by `segment_scene(x[:, t:t+2], **segment_scene_kwargs)`, in ascending t on the caller's generator; every other
         frame, the last one included, has no segmentation and is carried by the flow.  Frame by frame `track_step` links the label maps: frame 0 has no
         previous frame, so every label is born.  ValueError when max_age < segment_every, or carry is off with segment_every > 1: tracks would die between
-        segmentations.  Nothing is read back beyond what `segment_scene` does.  Returns a `TrackedScene` (labels [B,T,H,W] uint8 slots 1 .. 64; track_id, age,
+        segmentations.  occlusion=True makes one more call, `predict_flow(x, **flow_kwargs)`, for the forward flows, and every step warps along the backward
+        flow masked by the forward-backward check (`flow_consistency.check`, occ_alpha and occ_beta): the strip an object uncovers warps nothing in and is 0
+        in a carried frame.  Nothing is read back beyond what `segment_scene` does.  Returns a `TrackedScene` (labels [B,T,H,W] uint8 slots 1 .. 64; track_id, age,
         area [B,T,64]; bbox, moments, stats; with return_segmentations the per-frame `SceneSegmentation` objects, None for a carried frame)."""
         from . import segment_track as ST
 
         return ST.track_scene(self, x, segment_every=segment_every, flow_kwargs=flow_kwargs, iou_thresh=iou_thresh, min_inter=min_inter, min_area=min_area,
-                              max_age=max_age, carry=carry, return_segmentations=return_segmentations, **segment_scene_kwargs)
+                              max_age=max_age, carry=carry, return_segmentations=return_segmentations, occlusion=occlusion, occ_alpha=occ_alpha,
+                              occ_beta=occ_beta, **segment_scene_kwargs)
+
+    # ---- whether a flow vector can be believed: the forward-backward check (flow_consistency.py, csrc/flow_consistency.hip) ----
+    def predict_flow_and_occlusion(self, x, alpha=0.01, beta=0.5, **flow_kwargs):
+        """The forward and backward flows of a movie x [B,T,C,H,W] -- one `predict_flow` call each -- and where they cannot be believed.  Returns
+        (fwd [B,T-1,2,H,W]: pair t from frame t to frame t+1 on frame t's grid; bwd [B,T-1,2,H,W] in PAIR order: pair t from frame t+1 to frame t on frame
+        t+1's grid (a flipped copy of what `predict_flow(backward=True)` stores); occ_fwd, occ_bwd bool [B,T-1,H,W]: the round trip fails or leaves the frame;
+        the `FlowConsistency` of ONE `flow_consistency.check(fwd, bwd, both=True, want_res=True, want_masked=True)` call: index 0 forward, 1 backward)."""
+        from . import flow_consistency as FC
+
+        if x.dim() != 5 or x.shape[1] < 2:
+            raise ValueError("predict_flow_and_occlusion: x must be a movie [B,T,C,H,W] of at least two frames, got %s" % (tuple(x.shape),))
+        fwd = self.predict_flow(x, **flow_kwargs)
+        bwd = self.predict_flow(x, backward=True, **flow_kwargs).flip(1)
+        fc = FC.check(fwd, bwd, alpha=alpha, beta=beta, both=True, want_res=True, want_masked=True)
+        return fwd, bwd, fc.code[0] != 0, fc.code[1] != 0, fc
 
     # ---- statistics over the flow samples (segmentation.py:250-276, 479-547): device kernels, see flowstats.py ----------
     def compute_flow_samples_magnitude(self, flows, normalize=True, dim=-4, eps=1e-2):

@@ -601,6 +601,50 @@ typedef struct cwm_segment_track_args {
 CWM_API int cwm_segment_track(const cwm_segment_track_args* args);
 CWM_API size_t cwm_segment_track_work_bytes(int B, int H, int W);
 
+typedef struct cwm_flow_consistency_args {
+    uint32_t struct_size;            /* sizeof(cwm_flow_consistency_args); anything else: CWM_ERR_INVALID naming struct_size */
+    /* read: batch, H, W, P (for cell_dev only) and the stream.  Every other field of base is ignored, base.struct_size and base.T included */
+    cwm_patch_error_args base;
+    const float* a_dev;              /* the flow being checked: pixel (b, c, y, x) at a_dev[b a_strides[0] + c a_strides[1] + y W + x] (elements), as flow_dev of
+                                      * cwm_segment_track; c = 0 horizontal, 1 vertical, in pixels, on its own grid A, pointing to the other frame.  A
+                                      * [B, T-1, 2, H, W] tensor viewed as B (T-1) rows and one pair of a larger tensor are read in place */
+    int64_t a_strides[2];            /* not negative */
+    const float* o_dev;              /* the other flow, the same with o_strides: on the other frame's grid, pointing back */
+    int64_t o_strides[2];
+    float alpha, beta;               /* finite, >= 0: thr = alpha mag + beta */
+    int32_t both;                    /* 0 / 1: also direction d = 1, the roles of a and o exchanged; D = 1 + both */
+    uint8_t* code_dev;               /* out [D, B, H, W] or NULL: 0 consistent, 1 inconsistent, 2 the target lies outside */
+    float* res_dev;                  /* out [D, B, H, W] or NULL: the squared residual, +inf for code 2 and for a NaN */
+    float* masked_dev;               /* out [D, B, 2, H, W] or NULL: the checked flow where code == 0, the quiet NaN 0x7fc00000 elsewhere */
+    float* cell_dev;                 /* out [D, B, H/P, W/P] or NULL: the fraction of a cell's pixels with code != 0 */
+    int32_t* stats_dev;              /* out [D, B, 4] or NULL: pixels with code 0, code 1, code 2, then 0 */
+} cwm_flow_consistency_args;
+
+/* Forward-backward flow consistency: an occlusion code, the residual and an occlusion-masked flow per pixel, in one call on the device, without a read-back.
+ * No counterpart in the reference.  The masked flow feeds cwm_segment_track as it is: that call treats a NaN flow as "falls outside", so a disoccluded pixel
+ * warps nothing in.  Every arithmetic step below is ONE correctly rounded fp32 operation in the stated order; nothing is contracted into a fused
+ * multiply-add.  Per row b and pixel (y, x) of grid A, with (u, v) = a[:, y, x]:
+ *   1 target   fx = (float)x + u, fy = (float)y + v; the pixel is INSIDE iff fx >= 0 && fx <= W-1 && fy >= 0 && fy <= H-1, tested in fp32 before anything is
+ *              converted to an integer (NaN, inf and huge flows are outside).  Outside: code = 2, res = +inf, and nothing of o is read
+ *   2 sample   x0f = floorf(fx), wx = fx - x0f, ix0 = (int)x0f, ix1 = min(ix0 + 1, W-1); the same in y.  Per channel c of o, with o00 = o[c][iy0][ix0],
+ *              o01 = o[c][iy0][ix1], o10 = o[c][iy1][ix0], o11 = o[c][iy1][ix1]: top = o00 + wx (o01 - o00), bot = o10 + wx (o11 - o10),
+ *              s_c = top + wy (bot - top).  A target exactly on the last column or row is inside, and the clamp keeps its taps in the plane
+ *   3 residual ru = u + s_0, rv = v + s_1, res = ru ru + rv rv; mag = (u u + v v) + (s_0 s_0 + s_1 s_1); thr = alpha mag + beta
+ *   4 decision code = 0 iff res <= thr (equality is consistent), otherwise 1: a NaN anywhere (a NaN or inf sample of o) compares false and gives 1.
+ *              res_out = res if res == res, else +inf
+ *   5 masked   m[:, y, x] = a[:, y, x] where code == 0; elsewhere both channels are the quiet NaN 0x7fc00000
+ *   6 cells    (with cell_dev) cell[i][j] = (the number of the cell's P P pixels with code != 0) / (float)(P P): an integer count and one exact division
+ *   7 stats    per row the numbers of pixels with code 0, code 1 and code 2, then 0: integer sums
+ * both = 1 also produces everything with the roles of a and o exchanged, as direction d = 1 of the outputs' leading dimension.
+ * One kernel (4 pixels per thread, 16 x 64 pixels per workgroup, 16-byte loads and stores where the addresses allow them; the cell counts stay inside a
+ * workgroup), behind one memset of stats_dev, into which the workgroups add with INTEGER atomics: the same bits in any order, two calls on the same inputs give
+ * the same bits.  There is no workspace.  Asynchronous on base.stream: nothing is allocated and the host is not synchronised.  No content of a device buffer
+ * (NaN, inf and huge flows) makes the call read or write outside its buffers.  The outputs may not overlap the inputs.
+ * Limits: 1 <= batch <= 65535; H and W positive multiples of 4, H W <= 2^18; a_dev and o_dev non-NULL, strides not negative; alpha and beta finite and >= 0;
+ * both 0 or 1; at least one output; cell_dev needs P 4, 8 or 16 and H and W multiples of P.  Argument errors: CWM_ERR_INVALID with a message that names the
+ * field, before anything is launched or written. */
+CWM_API int cwm_flow_consistency(const cwm_flow_consistency_args* args);
+
 /* `RectangularizeMasks` (masking.py:90-132) on device masks without reading them back.  The reference equalises the masked count of
  * the rows of a batch by un-masking / masking `torch.randperm(#candidates)[:surplus]` of a row's masked / visible tokens (one draw of the global CPU
  * generator per changed row, in row order).  The draws depend on the per-row COUNTS alone, so:
