@@ -299,6 +299,30 @@ class CwmFlowConsistencyArgs(C.Structure):
     ]
 
 
+class CwmObjectMotionArgs(C.Structure):
+    """cwm_object_motion_args (include/cwm_hip.h): cwm_patch_error_args as `base` (batch, T, H, W and the stream are read), the slot map, the flow, the codes and
+    the other frame's slot map by their batch and frame strides, the thresholds of the fit and the outputs; new_object_motion_args() sets struct_size"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", CwmPatchErrorArgs),
+        ("labels_dev", C.c_void_p),
+        ("labels_strides", C.c_int64 * 2),
+        ("flow_dev", C.c_void_p),
+        ("flow_strides", C.c_int64 * 3),
+        ("code_dev", C.c_void_p),
+        ("code_strides", C.c_int64 * 2),
+        ("other_dev", C.c_void_p),
+        ("other_strides", C.c_int64 * 2),
+        ("min_pixels", C.c_int32),
+        ("min_affine", C.c_int32),
+        ("min_det", C.c_double),
+        ("sums_dev", C.c_void_p),
+        ("counts_dev", C.c_void_p),
+        ("model_dev", C.c_void_p),
+        ("occ_dev", C.c_void_p),
+    ]
+
+
 class CwmConjConfig(C.Structure):
     _fields_ = [
         ("main", CwmConfig),
@@ -744,6 +768,12 @@ def new_flow_consistency_args() -> CwmFlowConsistencyArgs:
     return a
 
 
+def new_object_motion_args() -> CwmObjectMotionArgs:
+    a = new_args(CwmObjectMotionArgs)
+    a.base.T = 1
+    return a
+
+
 def fill_patch_args(g, *, x=None, target=None, mask=None, region=None, y=None, geometry, n_vis=0, frame=-1, map=None, mean=None, scratch=None, stream):
     """Fills a cwm_patch_error_args -- alone, or the `.base` of the other read-outs' -- from tensors: the one place that knows its field order.  `x` and `target`
     are [B,T,C,H,W]-SHAPED views of any (b, t, c) strides, whatever the order of the tensor beneath ([B,C,T,H,W] permuted, a batch stride of 0); their image
@@ -819,6 +849,7 @@ SIGNATURES = {
     "cwm_segment_track": (C.c_int, [C.POINTER(CwmSegmentTrackArgs)]),
     "cwm_segment_track_work_bytes": (C.c_size_t, [C.c_int] * 3),
     "cwm_flow_consistency": (C.c_int, [C.POINTER(CwmFlowConsistencyArgs)]),
+    "cwm_object_motion": (C.c_int, [C.POINTER(CwmObjectMotionArgs)]),
     "cwm_mask_row_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_mask_flip_picks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cwm_prompt_table_expand": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),

@@ -52,8 +52,11 @@ class TrackStepResult:
 
 class TrackedScene:
     """labels [B,T,H,W] uint8 slots; track_id, age, area [B,T,64] int32; bbox [B,T,64,4] int32; moments [B,T,64,2] int64; stats [B,T,8] int32; next_id [B] int32
-    after the last frame; segmentations: the per-frame SceneSegmentation objects (None for a carried frame) when `track_scene` was asked for them"""
-    __slots__ = ("labels", "track_id", "age", "area", "bbox", "moments", "stats", "next_id", "segmentations")
+    after the last frame; segmentations: the per-frame SceneSegmentation objects (None for a carried frame) when `track_scene` was asked for them.  With
+    `motion` (else None): motion [B,T,65,12] float64, motion_counts [B,T,65,4] int32 and occluders [B,T,65,65] int32 of `object_motion.measure`: entry t
+    describes the pair (t, t+1) in the slots of frame t, which track_id[:, t] names (slot 0: everything that is no object, the camera's own motion); entry T-1
+    is zeros"""
+    __slots__ = ("labels", "track_id", "age", "area", "bbox", "moments", "stats", "next_id", "segmentations", "motion", "motion_counts", "occluders")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -284,13 +287,18 @@ def track_step(state, cur_labels, flow=None, **kw) -> TrackStepResult:
     return (track_step_device if _is_cuda(state, cur_labels, flow) else track_step_torch)(state, cur_labels, flow, **kw)
 
 
-def track_sequence(label_maps, back_flows=None, fwd_flows=None, occ_alpha=0.01, occ_beta=0.5, **kw) -> TrackedScene:
+def track_sequence(label_maps, back_flows=None, fwd_flows=None, occ_alpha=0.01, occ_beta=0.5, motion=False, motion_kwargs=None, **kw) -> TrackedScene:
     """Links a given sequence.  label_maps: [B,T,H,W] uint8, or a list of T entries [B,H,W] / None (None: the frame is carried by the flow alone); back_flows
     [B,T,2,H,W] or None (zero motion): entry t is the flow from frame t to frame t - 1 on frame t's grid, entry 0 is not read.  Frame 0 has no previous frame
     and no flow: every label is born.  Frames and pairs are read in place and, on the device, written in place; nothing is read back in the loop.
     fwd_flows [B,T,2,H,W] (entry t: the flow from frame t - 1 to frame t on frame t - 1's grid, entry 0 is not read) makes the tracking occlusion-aware: step t
     gets the MASKED backward flow of `flow_consistency.check(back_flows[:, t], fwd_flows[:, t], occ_alpha, occ_beta)` -- NaN where the round trip fails --, so a
-    disoccluded pixel warps nothing in and is 0 in a carried frame.  The masked flows of the whole movie come from ONE library call before the loop."""
+    disoccluded pixel warps nothing in and is 0 in a carried frame.  The masked flows of the whole movie come from ONE library call before the loop.
+    motion=True (needs fwd_flows) also measures how every slot moves and who hides whom: the check before the loop runs in both directions, so that it gives
+    the forward codes as well, and after the loop ONE `object_motion.measure(labels[:, :-1], fwd_flows[:, 1:], code=forward codes, other=labels[:, 1:],
+    **motion_kwargs)` call over the T-1 pairs, all views read in place, fills `motion`, `motion_counts` and `occluders` of the result."""
+    if motion and fwd_flows is None:
+        raise ValueError("track_sequence: motion=True needs fwd_flows (the forward flows carry the motion and the occlusion codes)")
     frames = [label_maps[:, t] for t in range(label_maps.shape[1])] if torch.is_tensor(label_maps) else list(label_maps)
     T = len(frames)
     first = next((f for f in frames if f is not None), None)
@@ -307,7 +315,12 @@ def track_sequence(label_maps, back_flows=None, fwd_flows=None, occ_alpha=0.01, 
         if T > 1:
             from . import flow_consistency as FC
 
-            masked = FC.check(back_flows[:, 1:], fwd_flows[:, 1:].to(back_flows), alpha=occ_alpha, beta=occ_beta, want_masked=True).masked
+            fwd_pairs = fwd_flows[:, 1:].to(back_flows)  # (a view: entry t - 1 is the pair (t - 1, t))
+            if motion:
+                fc = FC.check(back_flows[:, 1:], fwd_pairs, alpha=occ_alpha, beta=occ_beta, both=True, want_masked=True)
+                masked, fwd_code = fc.masked[0], fc.code[1]  # (index 0: the backward flow checked; index 1: the forward flow checked)
+            else:
+                masked = FC.check(back_flows[:, 1:], fwd_pairs, alpha=occ_alpha, beta=occ_beta, want_masked=True).masked
             back_flows = torch.cat([masked[:, :1], masked], 1)  # (entry 0 is not read)
     _check(B, H, W, int(kw.get("min_inter", 1)), int(kw.get("min_area", 1)), int(kw.get("max_age", 2)), int(kw.get("carry", True)))
     labels = torch.empty((B, T, H, W), device=dev, dtype=torch.uint8)
@@ -325,8 +338,22 @@ def track_sequence(label_maps, back_flows=None, fwd_flows=None, occ_alpha=0.01, 
         res.append(r)
         state = r.state
     stack = lambda name: torch.stack([getattr(r, name) for r in res], 1)  # noqa: E731
-    return TrackedScene(labels=labels, track_id=torch.stack([r.state.track_id for r in res], 1), age=torch.stack([r.state.age for r in res], 1), area=stack("area"),
-                        bbox=stack("bbox"), moments=stack("moments"), stats=stack("stats"), next_id=state.next_id)
+    tracked = TrackedScene(labels=labels, track_id=torch.stack([r.state.track_id for r in res], 1), age=torch.stack([r.state.age for r in res], 1),
+                           area=stack("area"), bbox=stack("bbox"), moments=stack("moments"), stats=stack("stats"), next_id=state.next_id)
+    if motion:
+        from . import object_motion as OM
+
+        def padded(t):  # [B,T-1,...] -> [B,T,...]: entry T-1 is zeros
+            return torch.cat([t, torch.zeros_like(t[:, :1])], 1)
+
+        if T > 1:
+            m = OM.measure(labels[:, :-1], fwd_pairs, code=fwd_code, other=labels[:, 1:], **(motion_kwargs or {}))
+            tracked.motion, tracked.motion_counts, tracked.occluders = padded(m.model), padded(m.counts), padded(m.occluders)
+        else:
+            tracked.motion = torch.zeros((B, 1, _SIDE, 12), device=dev, dtype=torch.float64)
+            tracked.motion_counts = torch.zeros((B, 1, _SIDE, 4), device=dev, dtype=torch.int32)
+            tracked.occluders = torch.zeros((B, 1, _SIDE, _SIDE), device=dev, dtype=torch.int32)
+    return tracked
 
 
 def backward_pair_flows(G, x, flow_kwargs=None):
@@ -349,8 +376,10 @@ def forward_pair_flows(G, x, flow_kwargs=None):
 
 
 def track_scene(G, x, segment_every=1, flow_kwargs=None, iou_thresh=0.3, min_inter=1, min_area=1, max_age=2, carry=True, return_segmentations=False,
-                occlusion=False, occ_alpha=0.01, occ_beta=0.5, **segment_scene_kwargs):
+                occlusion=False, occ_alpha=0.01, occ_beta=0.5, motion=False, motion_kwargs=None, **segment_scene_kwargs):
     """`FlowGenerator.track_scene` (its docstring says what this does); G is the generator"""
+    if motion and not occlusion:
+        raise ValueError("track_scene: motion=True needs occlusion=True (the forward flows and their codes)")
     segment_every, max_age = int(segment_every), int(max_age)
     if x.dim() != 5 or x.shape[1] < 2:
         raise ValueError("track_scene: x must be a movie [B,T,C,H,W] of at least two frames, got %s" % (tuple(x.shape),))
@@ -363,6 +392,8 @@ def track_scene(G, x, segment_every=1, flow_kwargs=None, iou_thresh=0.3, min_int
     T = x.shape[1]
     back = backward_pair_flows(G, x, flow_kwargs)
     occ = dict(fwd_flows=forward_pair_flows(G, x, flow_kwargs), occ_alpha=occ_alpha, occ_beta=occ_beta) if occlusion else {}
+    if motion:
+        occ.update(motion=True, motion_kwargs=motion_kwargs)
     scenes = [G.segment_scene(x[:, t:t + 2], **segment_scene_kwargs) if t <= T - 2 and t % segment_every == 0 else None for t in range(T)]
     tracked = track_sequence([None if s is None else s.labels for s in scenes], back, iou_thresh=iou_thresh, min_inter=min_inter, min_area=min_area,
                              max_age=max_age, carry=carry, **occ)

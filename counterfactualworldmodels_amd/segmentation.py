@@ -531,7 +531,7 @@ class FlowGenerator(PredictorBasedGenerator):
         return ST.track_step(state, cur_labels, flow, **kw)
 
     def track_scene(self, x, segment_every=1, flow_kwargs=None, iou_thresh=0.3, min_inter=1, min_area=1, max_age=2, carry=True, return_segmentations=False,
-                    occlusion=False, occ_alpha=0.01, occ_beta=0.5, **segment_scene_kwargs):
+                    occlusion=False, occ_alpha=0.01, occ_beta=0.5, motion=False, motion_kwargs=None, **segment_scene_kwargs):
         """The Spelke objects of a movie x [B,T,C,H,W] with identities that persist over time.  The movie's backward flows come from ONE call,
         `predict_flow(x, backward=True, **flow_kwargs)` (so `warm_start=True` and the shared encoders of the package's RAFT apply).  Frames t <= T-2 with
         t % segment_every == 0 are segmented by `segment_scene(x[:, t:t+2], **segment_scene_kwargs)`, in ascending t on the caller's generator; every other
@@ -539,13 +539,27 @@ class FlowGenerator(PredictorBasedGenerator):
         previous frame, so every label is born.  ValueError when max_age < segment_every, or carry is off with segment_every > 1: tracks would die between
         segmentations.  occlusion=True makes one more call, `predict_flow(x, **flow_kwargs)`, for the forward flows, and every step warps along the backward
         flow masked by the forward-backward check (`flow_consistency.check`, occ_alpha and occ_beta): the strip an object uncovers warps nothing in and is 0
-        in a carried frame.  Nothing is read back beyond what `segment_scene` does.  Returns a `TrackedScene` (labels [B,T,H,W] uint8 slots 1 .. 64; track_id, age,
+        in a carried frame.  motion=True (needs occlusion=True; no further flow call) also fills `motion`, `motion_counts` and `occluders` of the result with ONE
+        `object_motion.measure` call over the T-1 pairs (keywords: motion_kwargs): how every slot moves to the next frame and who hides whom.  Nothing is read
+        back beyond what `segment_scene` does.  Returns a `TrackedScene` (labels [B,T,H,W] uint8 slots 1 .. 64; track_id, age,
         area [B,T,64]; bbox, moments, stats; with return_segmentations the per-frame `SceneSegmentation` objects, None for a carried frame)."""
         from . import segment_track as ST
 
         return ST.track_scene(self, x, segment_every=segment_every, flow_kwargs=flow_kwargs, iou_thresh=iou_thresh, min_inter=min_inter, min_area=min_area,
                               max_age=max_age, carry=carry, return_segmentations=return_segmentations, occlusion=occlusion, occ_alpha=occ_alpha,
-                              occ_beta=occ_beta, **segment_scene_kwargs)
+                              occ_beta=occ_beta, motion=motion, motion_kwargs=motion_kwargs, **segment_scene_kwargs)
+
+    # ---- how every slot moves and who hides whom (object_motion.py, csrc/object_motion.hip) ----
+    def object_motion(self, labels, flow, code=None, other=None, **kw):
+        """`object_motion.measure`: per slot of `labels` ([B,H,W] or [B,T,H,W] uint8, as `segment_scene` and `track_scene` return them) the pixel counts by
+        class, the sums and the model of a least-squares affine fit to `flow` (from that frame to the other one, on its own grid) -- translation, rotation,
+        looming; slot 0 is the camera's own motion --, and with `code` (the codes of `flow_consistency.check` for this flow) and `other` (the slot map of the
+        other frame) the table of who was hidden behind whom, which `object_motion.occlusion_order` turns into a depth order.  Keywords: min_pixels=1,
+        min_affine=16, min_det=1.0.  Returns an `ObjectMotion` (sums, counts, model, occluders).  Device tensors take one library call (cwm_object_motion,
+        nothing read back), CPU tensors the same definition in torch."""
+        from . import object_motion as OM
+
+        return OM.measure(labels, flow, code=code, other=other, **kw)
 
     # ---- whether a flow vector can be believed: the forward-backward check (flow_consistency.py, csrc/flow_consistency.hip) ----
     def predict_flow_and_occlusion(self, x, alpha=0.01, beta=0.5, **flow_kwargs):

@@ -645,6 +645,65 @@ typedef struct cwm_flow_consistency_args {
  * field, before anything is launched or written. */
 CWM_API int cwm_flow_consistency(const cwm_flow_consistency_args* args);
 
+typedef struct cwm_object_motion_args {
+    uint32_t struct_size;            /* sizeof(cwm_object_motion_args); anything else: CWM_ERR_INVALID naming struct_size */
+    /* read: batch (B), T, H, W and the stream.  Every other field of base is ignored, base.struct_size and base.P included.  Rows r = b T + t, R = B T */
+    cwm_patch_error_args base;
+    const uint8_t* labels_dev;       /* the slot map of frame A: row (b, t) is the H W contiguous bytes at labels_dev + b labels_strides[0] + t labels_strides[1]
+                                      * (0: none, 1 .. 64: a slot; a byte above 64 reads as 0).  A [B, T, H, W] buffer, a [:, :-1] or [:, 1:] slice of one and a
+                                      * plain [B, H, W] (T = 1) are read in place */
+    int64_t labels_strides[2];       /* batch and frame stride in elements, not negative */
+    const float* flow_dev;           /* the flow from A to the other frame on A's grid: pixel (b, t, c, y, x) at flow_dev[b flow_strides[0] + t flow_strides[1] +
+                                      * c flow_strides[2] + y W + x]; c = 0 horizontal, 1 vertical, in pixels */
+    int64_t flow_strides[3];         /* batch, frame and channel stride in elements, not negative */
+    const uint8_t* code_dev;         /* NULL, or what cwm_flow_consistency wrote for this flow, addressed as labels_dev with code_strides */
+    int64_t code_strides[2];
+    const uint8_t* other_dev;        /* NULL, or the slot map of the other frame, addressed as labels_dev with other_strides; given iff occ_dev is */
+    int64_t other_strides[2];
+    int32_t min_pixels;              /* >= 1: a slot with fewer class-0 pixels has no model */
+    int32_t min_affine;              /* >= 3: a slot with fewer class-0 pixels gets a translation only */
+    double min_det;                  /* finite, > 0, in px^4: so does a slot whose det is below it */
+    int64_t* sums_dev;               /* out [R, 65, 16] int64: step 4, entries 14 and 15 are 0 */
+    int32_t* counts_dev;             /* out [R, 65, 4]: pixels of class 0 (believed), 1 (inconsistent), 2 (unusable or leaving the frame), then 0 */
+    double* model_dev;               /* out [R, 65, 12] float64: step 6 */
+    int32_t* occ_dev;                /* out [R, 65, 65] or NULL: occ[l][m], the pixels of slot l that were hidden where slot m stands in the other frame */
+} cwm_object_motion_args;
+
+/* Per-object motion and occlusion order: how every slot of a slot map (cwm_segment_merge, cwm_segment_track) moves between two frames, and which slot stands in
+ * front of which, from the flow, the codes of cwm_flow_consistency and the other frame's slot map, in one call on the device, without a read-back.  Slot 0,
+ * everything that is no object, is summed like any other: its model is the camera's own motion.  No counterpart in the reference, whose README lists read-outs
+ * of this kind as coming ("using counterfactuals to estimate other scene properties").  Per row and pixel (x, y):
+ *   1 slot     l = labels[y][x], or 0 if that is above 64
+ *   2 target   (u, v) = flow[:, y, x]; USABLE iff both are finite and |u| <= 4096 and |v| <= 4096; fx = (float)x + u, fy = (float)y + v (one fp32 add each);
+ *              INSIDE iff fx >= 0 && fx <= W-1 && fy >= 0 && fy <= H-1, in fp32 and before anything is converted: step 1 of cwm_flow_consistency
+ *   3 class    k = 2 if the vector is not usable or the pixel not inside; otherwise 1 if code_dev is given and code[y][x] != 0; otherwise 0.
+ *              counts[l][k] += 1; counts[l][3] stays 0
+ *   4 sums     k = 0 only: qu = (int)rintf(u * 256.0f), qv likewise (the multiply is exact, |q| <= 2^20: the flow is held in 1/256 px).  sums[l][0..13] +=
+ *              1, x, y, x x, x y, y y, qu, qv, x qu, y qu, x qv, y qv, qu qu, qv qv.  x, y < 2^16, so over the at most 2^18 pixels of a row sum x x <= 2^50,
+ *              sum x qu <= 2^54 and sum qu qu <= 2^58: nothing wraps
+ *   5 occluder k = 1 only, and only with other_dev: m = other[(int)rintf(fy)][(int)rintf(fx)], or 0 if that is above 64; occ[l][m] += 1.  The row is the slot
+ *              that was hidden, the column what stands there in the other frame; the diagonal is counted too (a flow that is wrong on the object itself)
+ *   6 model    per row and slot, after all pixels.  Every operator is ONE correctly rounded binary64 operation, evaluated as parenthesised: no fused
+ *              multiply-add, no reciprocal; a sum enters through a round-to-nearest int64 -> double conversion.  With n = (double)N, N = sums[l][0], and S.. the
+ *              other sums:
+ *                mx = (Sx/n)  my = (Sy/n)  mu = (Su/n)  mv = (Sv/n)
+ *                cxx = ((Sxx/n) - (mx mx))  cxy = ((Sxy/n) - (mx my))  cyy = ((Syy/n) - (my my))
+ *                cxu = ((Sxu/n) - (mx mu))  cyu = ((Syu/n) - (my mu))  cxv = ((Sxv/n) - (mx mv))  cyv = ((Syv/n) - (my mv))
+ *                det = ((cxx cyy) - (cxy cxy))
+ *                tu = (mu 2^-8)  tv = (mv 2^-8)  var_u = (((Suu/n) - (mu mu)) 2^-16)  var_v = (((Svv/n) - (mv mv)) 2^-16)
+ *                a11 = ((((cxu cyy) - (cyu cxy)) / det) 2^-8)  a12 = ((((cyu cxx) - (cxu cxy)) / det) 2^-8)  a21, a22: the same with cxv, cyv
+ *              model[l] = (valid, tu, tv, a11, a12, a21, a22, mx, my, var_u, var_v, 0): the predicted flow of a pixel of the object is t + A ((x, y) - (mx, my)).
+ *              valid = 0 and all twelve 0 if N < min_pixels; valid = 2 if N >= min_affine and det >= min_det; otherwise valid = 1 and A = 0
+ * Two kernels behind the memsets of the three integer outputs, which are the accumulation targets (the call zeroes them itself on the stream; there is no
+ * workspace): an accumulate pass (4 pixels per thread, 1024 per workgroup, the tables in LDS, a wave that holds one slot sums over the wave first) that adds its
+ * non-zero entries with INTEGER atomics -- the same bits in any order, two calls on the same inputs give the same bits --, and one thread per (row, slot) for
+ * step 6.  Asynchronous on base.stream: nothing is allocated and the host is not synchronised.  No content of a device buffer (label bytes above 64, NaN, inf and
+ * huge flows, any code byte) makes the call read or write outside its buffers.  The outputs may not overlap the inputs.
+ * Limits: 1 <= batch, 1 <= T, batch T <= 65535; H and W positive multiples of 4, H W <= 2^18; labels_dev and flow_dev non-NULL; strides not negative;
+ * min_pixels >= 1, min_affine >= 3, min_det finite and > 0; sums_dev, counts_dev and model_dev non-NULL; occ_dev non-NULL iff other_dev is.  Argument errors:
+ * CWM_ERR_INVALID with a message that names the field, before anything is launched or written. */
+CWM_API int cwm_object_motion(const cwm_object_motion_args* args);
+
 /* `RectangularizeMasks` (masking.py:90-132) on device masks without reading them back.  The reference equalises the masked count of
  * the rows of a batch by un-masking / masking `torch.randperm(#candidates)[:surplus]` of a row's masked / visible tokens (one draw of the global CPU
  * generator per changed row, in row order).  The draws depend on the per-row COUNTS alone, so:
