@@ -323,6 +323,34 @@ class CwmObjectMotionArgs(C.Structure):
     ]
 
 
+class CwmPointTrackArgs(C.Structure):
+    """cwm_point_track_args (include/cwm_hip.h): cwm_patch_error_args as `base` (batch, T frames, H, W and the stream are read), the pair flows by three strides
+    each, the threshold, the slot maps and the model table by their batch and frame strides, the points, their start frames and the outputs;
+    new_point_track_args() sets struct_size and the defaults alpha = 0.01, beta = 0.5, max_coast = 8"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", CwmPatchErrorArgs),
+        ("fwd_dev", C.c_void_p),
+        ("fwd_strides", C.c_int64 * 3),
+        ("bwd_dev", C.c_void_p),
+        ("bwd_strides", C.c_int64 * 3),
+        ("alpha", C.c_float),
+        ("beta", C.c_float),
+        ("labels_dev", C.c_void_p),
+        ("labels_strides", C.c_int64 * 2),
+        ("model_dev", C.c_void_p),
+        ("model_strides", C.c_int64 * 2),
+        ("points_dev", C.c_void_p),
+        ("start_dev", C.c_void_p),
+        ("K", C.c_int32),
+        ("max_coast", C.c_int32),
+        ("xy_dev", C.c_void_p),
+        ("state_dev", C.c_void_p),
+        ("under_dev", C.c_void_p),
+        ("owner_dev", C.c_void_p),
+    ]
+
+
 class CwmConjConfig(C.Structure):
     _fields_ = [
         ("main", CwmConfig),
@@ -774,6 +802,13 @@ def new_object_motion_args() -> CwmObjectMotionArgs:
     return a
 
 
+def new_point_track_args() -> CwmPointTrackArgs:
+    a = new_args(CwmPointTrackArgs)
+    a.base.T = 2
+    a.alpha, a.beta, a.max_coast = 0.01, 0.5, 8
+    return a
+
+
 def fill_patch_args(g, *, x=None, target=None, mask=None, region=None, y=None, geometry, n_vis=0, frame=-1, map=None, mean=None, scratch=None, stream):
     """Fills a cwm_patch_error_args -- alone, or the `.base` of the other read-outs' -- from tensors: the one place that knows its field order.  `x` and `target`
     are [B,T,C,H,W]-SHAPED views of any (b, t, c) strides, whatever the order of the tensor beneath ([B,C,T,H,W] permuted, a batch stride of 0); their image
@@ -850,6 +885,7 @@ SIGNATURES = {
     "cwm_segment_track_work_bytes": (C.c_size_t, [C.c_int] * 3),
     "cwm_flow_consistency": (C.c_int, [C.POINTER(CwmFlowConsistencyArgs)]),
     "cwm_object_motion": (C.c_int, [C.POINTER(CwmObjectMotionArgs)]),
+    "cwm_point_track": (C.c_int, [C.POINTER(CwmPointTrackArgs)]),
     "cwm_mask_row_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_mask_flip_picks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cwm_prompt_table_expand": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),

@@ -55,8 +55,9 @@ class TrackedScene:
     after the last frame; segmentations: the per-frame SceneSegmentation objects (None for a carried frame) when `track_scene` was asked for them.  With
     `motion` (else None): motion [B,T,65,12] float64, motion_counts [B,T,65,4] int32 and occluders [B,T,65,65] int32 of `object_motion.measure`: entry t
     describes the pair (t, t+1) in the slots of frame t, which track_id[:, t] names (slot 0: everything that is no object, the camera's own motion); entry T-1
-    is zeros"""
-    __slots__ = ("labels", "track_id", "age", "area", "bbox", "moments", "stats", "next_id", "segmentations", "motion", "motion_counts", "occluders")
+    is zeros.  With `points` (else None): points, the `point_track.PointTracks` (xy [B,T,K,2], state and under [B,T,K], owner [B,K]) of the query points
+    through the movie"""
+    __slots__ = ("labels", "track_id", "age", "area", "bbox", "moments", "stats", "next_id", "segmentations", "motion", "motion_counts", "occluders", "points")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -287,7 +288,8 @@ def track_step(state, cur_labels, flow=None, **kw) -> TrackStepResult:
     return (track_step_device if _is_cuda(state, cur_labels, flow) else track_step_torch)(state, cur_labels, flow, **kw)
 
 
-def track_sequence(label_maps, back_flows=None, fwd_flows=None, occ_alpha=0.01, occ_beta=0.5, motion=False, motion_kwargs=None, **kw) -> TrackedScene:
+def track_sequence(label_maps, back_flows=None, fwd_flows=None, occ_alpha=0.01, occ_beta=0.5, motion=False, motion_kwargs=None, points=None, point_kwargs=None,
+                   **kw) -> TrackedScene:
     """Links a given sequence.  label_maps: [B,T,H,W] uint8, or a list of T entries [B,H,W] / None (None: the frame is carried by the flow alone); back_flows
     [B,T,2,H,W] or None (zero motion): entry t is the flow from frame t to frame t - 1 on frame t's grid, entry 0 is not read.  Frame 0 has no previous frame
     and no flow: every label is born.  Frames and pairs are read in place and, on the device, written in place; nothing is read back in the loop.
@@ -296,14 +298,22 @@ def track_sequence(label_maps, back_flows=None, fwd_flows=None, occ_alpha=0.01, 
     disoccluded pixel warps nothing in and is 0 in a carried frame.  The masked flows of the whole movie come from ONE library call before the loop.
     motion=True (needs fwd_flows) also measures how every slot moves and who hides whom: the check before the loop runs in both directions, so that it gives
     the forward codes as well, and after the loop ONE `object_motion.measure(labels[:, :-1], fwd_flows[:, 1:], code=forward codes, other=labels[:, 1:],
-    **motion_kwargs)` call over the T-1 pairs, all views read in place, fills `motion`, `motion_counts` and `occluders` of the result."""
+    **motion_kwargs)` call over the T-1 pairs, all views read in place, fills `motion`, `motion_counts` and `occluders` of the result.
+    points [B,K,2] (x, y) (needs fwd_flows and at least two frames) also follows these points through the movie: after the loop ONE
+    `point_track.track(fwd_flows[:, 1:], points, bwd=back_flows[:, 1:], labels=labels, model=motion, **point_kwargs)` call -- the flows as given (not the masked
+    ones) in pair order, the slot maps and, with motion=True, the models, all views read in place -- fills `points` of the result (keywords: start, alpha, beta,
+    max_coast).  Without motion=True a hidden point coasts on its last believed flow vector."""
     if motion and fwd_flows is None:
         raise ValueError("track_sequence: motion=True needs fwd_flows (the forward flows carry the motion and the occlusion codes)")
+    if points is not None and fwd_flows is None:
+        raise ValueError("track_sequence: points need fwd_flows (a point follows the forward flows)")
     frames = [label_maps[:, t] for t in range(label_maps.shape[1])] if torch.is_tensor(label_maps) else list(label_maps)
     T = len(frames)
     first = next((f for f in frames if f is not None), None)
     if first is None or T < 1:
         raise ValueError("track_sequence: at least one frame must have a label map")
+    if points is not None and T < 2:
+        raise ValueError("track_sequence: points need at least two frames, got %d" % T)
     B, H, W = first.shape
     if back_flows is not None and tuple(back_flows.shape) != (B, T, 2, H, W):
         raise ValueError("track_sequence: back_flows must be [B,T,2,H,W] = (%d, %d, 2, %d, %d), got %s" % (B, T, H, W, tuple(back_flows.shape)))
@@ -316,6 +326,7 @@ def track_sequence(label_maps, back_flows=None, fwd_flows=None, occ_alpha=0.01, 
             from . import flow_consistency as FC
 
             fwd_pairs = fwd_flows[:, 1:].to(back_flows)  # (a view: entry t - 1 is the pair (t - 1, t))
+            back_pairs = back_flows[:, 1:]  # (a view of the flows as given: entry t - 1 is the flow from frame t back to frame t - 1)
             if motion:
                 fc = FC.check(back_flows[:, 1:], fwd_pairs, alpha=occ_alpha, beta=occ_beta, both=True, want_masked=True)
                 masked, fwd_code = fc.masked[0], fc.code[1]  # (index 0: the backward flow checked; index 1: the forward flow checked)
@@ -353,6 +364,10 @@ def track_sequence(label_maps, back_flows=None, fwd_flows=None, occ_alpha=0.01, 
             tracked.motion = torch.zeros((B, 1, _SIDE, 12), device=dev, dtype=torch.float64)
             tracked.motion_counts = torch.zeros((B, 1, _SIDE, 4), device=dev, dtype=torch.int32)
             tracked.occluders = torch.zeros((B, 1, _SIDE, _SIDE), device=dev, dtype=torch.int32)
+    if points is not None:
+        from . import point_track as PT
+
+        tracked.points = PT.track(fwd_pairs, points.to(dev), bwd=back_pairs, labels=labels, model=tracked.motion, **(point_kwargs or {}))
     return tracked
 
 
@@ -376,10 +391,12 @@ def forward_pair_flows(G, x, flow_kwargs=None):
 
 
 def track_scene(G, x, segment_every=1, flow_kwargs=None, iou_thresh=0.3, min_inter=1, min_area=1, max_age=2, carry=True, return_segmentations=False,
-                occlusion=False, occ_alpha=0.01, occ_beta=0.5, motion=False, motion_kwargs=None, **segment_scene_kwargs):
+                occlusion=False, occ_alpha=0.01, occ_beta=0.5, motion=False, motion_kwargs=None, points=None, point_kwargs=None, **segment_scene_kwargs):
     """`FlowGenerator.track_scene` (its docstring says what this does); G is the generator"""
     if motion and not occlusion:
         raise ValueError("track_scene: motion=True needs occlusion=True (the forward flows and their codes)")
+    if points is not None and not occlusion:
+        raise ValueError("track_scene: points need occlusion=True (the forward flows; motion=True as well for coasting on the objects' models)")
     segment_every, max_age = int(segment_every), int(max_age)
     if x.dim() != 5 or x.shape[1] < 2:
         raise ValueError("track_scene: x must be a movie [B,T,C,H,W] of at least two frames, got %s" % (tuple(x.shape),))
@@ -394,6 +411,8 @@ def track_scene(G, x, segment_every=1, flow_kwargs=None, iou_thresh=0.3, min_int
     occ = dict(fwd_flows=forward_pair_flows(G, x, flow_kwargs), occ_alpha=occ_alpha, occ_beta=occ_beta) if occlusion else {}
     if motion:
         occ.update(motion=True, motion_kwargs=motion_kwargs)
+    if points is not None:
+        occ.update(points=points, point_kwargs=point_kwargs)
     scenes = [G.segment_scene(x[:, t:t + 2], **segment_scene_kwargs) if t <= T - 2 and t % segment_every == 0 else None for t in range(T)]
     tracked = track_sequence([None if s is None else s.labels for s in scenes], back, iou_thresh=iou_thresh, min_inter=min_inter, min_area=min_area,
                              max_age=max_age, carry=carry, **occ)

@@ -531,7 +531,7 @@ class FlowGenerator(PredictorBasedGenerator):
         return ST.track_step(state, cur_labels, flow, **kw)
 
     def track_scene(self, x, segment_every=1, flow_kwargs=None, iou_thresh=0.3, min_inter=1, min_area=1, max_age=2, carry=True, return_segmentations=False,
-                    occlusion=False, occ_alpha=0.01, occ_beta=0.5, motion=False, motion_kwargs=None, **segment_scene_kwargs):
+                    occlusion=False, occ_alpha=0.01, occ_beta=0.5, motion=False, motion_kwargs=None, points=None, point_kwargs=None, **segment_scene_kwargs):
         """The Spelke objects of a movie x [B,T,C,H,W] with identities that persist over time.  The movie's backward flows come from ONE call,
         `predict_flow(x, backward=True, **flow_kwargs)` (so `warm_start=True` and the shared encoders of the package's RAFT apply).  Frames t <= T-2 with
         t % segment_every == 0 are segmented by `segment_scene(x[:, t:t+2], **segment_scene_kwargs)`, in ascending t on the caller's generator; every other
@@ -540,14 +540,39 @@ class FlowGenerator(PredictorBasedGenerator):
         segmentations.  occlusion=True makes one more call, `predict_flow(x, **flow_kwargs)`, for the forward flows, and every step warps along the backward
         flow masked by the forward-backward check (`flow_consistency.check`, occ_alpha and occ_beta): the strip an object uncovers warps nothing in and is 0
         in a carried frame.  motion=True (needs occlusion=True; no further flow call) also fills `motion`, `motion_counts` and `occluders` of the result with ONE
-        `object_motion.measure` call over the T-1 pairs (keywords: motion_kwargs): how every slot moves to the next frame and who hides whom.  Nothing is read
+        `object_motion.measure` call over the T-1 pairs (keywords: motion_kwargs): how every slot moves to the next frame and who hides whom.  points [B,K,2] (x, y)
+        (needs occlusion=True; no further flow call) also fills `points` of the result with ONE `point_track.track` call on the flows, slot maps and -- with
+        motion=True -- models the call already has (keywords: point_kwargs: start, alpha, beta, max_coast): where each point is in every frame and when it
+        is hidden.  Nothing is read
         back beyond what `segment_scene` does.  Returns a `TrackedScene` (labels [B,T,H,W] uint8 slots 1 .. 64; track_id, age,
         area [B,T,64]; bbox, moments, stats; with return_segmentations the per-frame `SceneSegmentation` objects, None for a carried frame)."""
         from . import segment_track as ST
 
         return ST.track_scene(self, x, segment_every=segment_every, flow_kwargs=flow_kwargs, iou_thresh=iou_thresh, min_inter=min_inter, min_area=min_area,
                               max_age=max_age, carry=carry, return_segmentations=return_segmentations, occlusion=occlusion, occ_alpha=occ_alpha,
-                              occ_beta=occ_beta, motion=motion, motion_kwargs=motion_kwargs, **segment_scene_kwargs)
+                              occ_beta=occ_beta, motion=motion, motion_kwargs=motion_kwargs, points=points, point_kwargs=point_kwargs, **segment_scene_kwargs)
+
+    # ---- where points go through a movie, and when they are hidden (point_track.py, csrc/point_track.hip) ----
+    def track_points(self, x, points, start=None, scene=None, flows=None, alpha=0.01, beta=0.5, max_coast=8, **flow_kwargs):
+        """`point_track.track` on a movie x [B,T,C,H,W]: points [B,K,2] (x, y) in pixels, each followed from frame `start` ([B,K] int; default 0) to the last
+        frame along the forward flows, believed only where the forward-backward test (alpha, beta) holds.  flows: a given (fwd, bwd) pair, both [B,T-1,2,H,W] in
+        pair order as `predict_flow_and_occlusion` returns them; None makes one `predict_flow(x, **flow_kwargs)` call per direction, as that method does.
+        scene: a `TrackedScene` of the same movie (`track_scene`): its `labels` tell when a point stands on another object than the one it started on -- it is
+        then hidden (state 1) and coasts on its object's motion model `scene.motion` (from `track_scene(motion=True)`; None: on its last believed flow
+        vector) for up to max_coast frames, and is picked up again when it re-emerges.  Returns `PointTracks` (xy [B,T,K,2], state and under [B,T,K], owner
+        [B,K]; state 0 visible, 1 hidden, 2 left the frame, 3 lost, 255 not started).  Device tensors take one library call (cwm_point_track: one kernel
+        launch for the whole movie, nothing read back), CPU tensors the same definition in torch."""
+        from . import point_track as PT
+
+        if flows is None:
+            if x.dim() != 5 or x.shape[1] < 2:
+                raise ValueError("track_points: x must be a movie [B,T,C,H,W] of at least two frames, got %s" % (tuple(x.shape),))
+            fwd = self.predict_flow(x, **flow_kwargs)
+            bwd = self.predict_flow(x, backward=True, **flow_kwargs).flip(1)
+        else:
+            fwd, bwd = flows
+        labels, model = (None, None) if scene is None else (scene.labels, scene.motion)
+        return PT.track(fwd, points.to(fwd.device), bwd=bwd, labels=labels, model=model, start=start, alpha=alpha, beta=beta, max_coast=max_coast)
 
     # ---- how every slot moves and who hides whom (object_motion.py, csrc/object_motion.hip) ----
     def object_motion(self, labels, flow, code=None, other=None, **kw):

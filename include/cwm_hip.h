@@ -704,6 +704,70 @@ typedef struct cwm_object_motion_args {
  * CWM_ERR_INVALID with a message that names the field, before anything is launched or written. */
 CWM_API int cwm_object_motion(const cwm_object_motion_args* args);
 
+typedef struct cwm_point_track_args {
+    uint32_t struct_size;            /* sizeof(cwm_point_track_args); anything else: CWM_ERR_INVALID naming struct_size */
+    /* read: batch (B), T (the number of FRAMES), H, W and the stream.  Every other field of base is ignored, base.struct_size and base.P included */
+    cwm_patch_error_args base;
+    const float* fwd_dev;            /* [B, T-1, 2, H, W] in PAIR order: entry t is the flow from frame t to frame t+1 on frame t's grid; pixel (b, t, c, y, x) at
+                                      * fwd_dev[b fwd_strides[0] + t fwd_strides[1] + c fwd_strides[2] + y W + x]; c = 0 horizontal, 1 vertical, in pixels */
+    int64_t fwd_strides[3];          /* batch, pair and channel stride in elements, not negative */
+    const float* bwd_dev;            /* NULL, or the same shape in pair order, addressed with bwd_strides: entry t is the flow from frame t+1 back to frame t on
+                                      * frame t+1's grid */
+    int64_t bwd_strides[3];
+    float alpha, beta;               /* finite, >= 0: thr = alpha mag + beta of the forward-backward test (read with bwd_dev, checked always) */
+    const uint8_t* labels_dev;       /* NULL, or the slot maps [B, T, H, W]: frame (b, t) is the H W contiguous bytes at labels_dev + b labels_strides[0] +
+                                      * t labels_strides[1]; a byte above 64 reads as 0 */
+    int64_t labels_strides[2];       /* batch and frame stride in elements, not negative */
+    const double* model_dev;         /* NULL, or [B, T, 65, 12] float64 as cwm_object_motion writes model_dev: row (b, t, slot) is the 12 contiguous doubles at
+                                      * model_dev + b model_strides[0] + t model_strides[1] + 12 slot; entry t describes the pair (t, t+1) in the slots of frame
+                                      * t; entry T-1 is not read.  Needs labels_dev; 8-byte aligned */
+    int64_t model_strides[2];        /* batch and frame stride in elements (doubles), not negative */
+    const float* points_dev;         /* [B, K, 2] contiguous: (x, y) in pixels */
+    const int32_t* start_dev;        /* NULL (every point begins in frame 0), or [B, K] contiguous: the frame a point begins in.  A value outside 0 .. T-1 gives
+                                      * a point that is never started */
+    int32_t K;                       /* 1 .. 65536 points per row */
+    int32_t max_coast;               /* >= 0: a point hidden for more than this many consecutive frames is lost */
+    float* xy_dev;                   /* out [B, T, K, 2]: the point in frame t, the quiet NaN 0x7fc00000 twice for a terminal or not-started entry */
+    uint8_t* state_dev;              /* out [B, T, K]: 0 visible, 1 hidden and coasting, 2 left the frame, 3 lost, 255 not started yet */
+    uint8_t* under_dev;              /* out [B, T, K]: the slot the point stands on in frame t (0 without labels, and for a terminal or not-started entry) */
+    uint8_t* owner_dev;              /* out [B, K]: the slot the point stood on in its start frame: the object it is tracked with */
+} cwm_point_track_args;
+
+/* Point tracks through a movie: where K query points per row go over T frames and when they are hidden, in one call and one kernel launch on the device,
+ * without a read-back.  A point follows the forward flow of its pair while it stands on the object it started on and the flow can be believed; otherwise it
+ * coasts on the affine motion model of its object (cwm_object_motion's model_dev: its first consumer) or, without one, on its last believed flow vector, and is
+ * picked up again when it stands on its object once more.  No counterpart in the reference.  Every fp32 step below is ONE correctly rounded fp32 operation in
+ * the stated order and every float64 step one binary64 operation: nothing is contracted into a fused multiply-add.  Per row b and point k, with
+ * s = start[b][k] (0 without start_dev), p_s = points[b][k], last = (0, 0), run = 0; for t = s .. T-1, until a terminal state, which then holds to the last frame:
+ *   1 inside   p = (px, py) is INSIDE iff px >= 0 && px <= W-1 && py >= 0 && py <= H-1, in fp32 and before anything is converted (a NaN or inf point is
+ *              outside).  Outside: state 2 from this frame on
+ *   2 under    under_t = labels[t][(int)rintf(py)][(int)rintf(px)], or 0 if that is above 64, or 0 without labels_dev.  owner = under_s (0 if p_s is outside)
+ *   3 hidden   with labels_dev hidden_t = (under_t != owner); without, hidden_t = (t > s and the step into frame t was a coast).  run = hidden_t ? run + 1 : 0;
+ *              run > max_coast: state 3 from this frame on.  Otherwise state_t = hidden_t ? 1 : 0, xy_t = p, and for t < T-1 the point steps:
+ *   4 flow     tried iff under_t == owner (always without labels_dev).  a_c = the bilinear sample of fwd[t] channel c at p by step 2 of cwm_flow_consistency:
+ *              x0f = floorf(px), wx = px - x0f, ix0 = (int)x0f, ix1 = min(ix0 + 1, W-1), the same in y; top = o00 + wx (o01 - o00),
+ *              bot = o10 + wx (o11 - o10), a_c = top + wy (bot - top).  USABLE iff |a_0| <= 4096 && |a_1| <= 4096 (false for a NaN).
+ *              q = (px + a_0, py + a_1).  Usable and q not INSIDE: the point leaves, p_{t+1} = q (step 1 makes that state 2).  Usable, q inside and bwd_dev
+ *              given: o_c = the same sample of bwd[t] at q; ru = a_0 + o_0, rv = a_1 + o_1, res = ru ru + rv rv; mag = (a_0 a_0 + a_1 a_1) + (o_0 o_0 + o_1 o_1);
+ *              thr = alpha mag + beta (steps 3 and 4 of cwm_flow_consistency with (u, v) = a and s = o).  BELIEVED iff usable, q inside and (no bwd_dev or
+ *              res <= thr).  Believed: p_{t+1} = q, last = a
+ *   5 coast    when the flow step was not tried, or tried and neither believed nor leaving.  c = last.  With model_dev and m = model[b][t][owner],
+ *              m.valid >= 1 (false for a NaN): dx = (double)px - mx, dy = (double)py - my; e0 = a11 dx, e1 = a12 dy, cu = e0 + e1, cu = tu + cu; e0 = a21 dx,
+ *              e1 = a22 dy, cv = e0 + e1, cv = tv + cv; f = ((float)cu, (float)cv), rounded to nearest; c = f if both are finite (valid == 1 has a zero
+ *              matrix: the same lines serve both values).  p_{t+1} = (px + c_0, py + c_1); the step into t+1 counts as a coast
+ * Frames before s, and every frame of a point whose start is outside 0 .. T-1, are state 255.  A terminal (2, 3) or not-started (255) entry has xy = the quiet
+ * NaN 0x7fc00000 twice and under = 0; the owner of a point that never started, or started outside, is 0.  The outputs are frame-major, so that one frame's
+ * points are one slice.
+ * One kernel: a thread owns a point and walks its frames, 64 points (one wave) per workgroup, so that few points still spread over many CUs -- the work of a
+ * point is a chain of dependent cache round trips (the label byte, the eight taps of fwd, the eight taps of bwd where the first eight point, rarely the model
+ * row) that only other waves hide.  Only vector stores; no atomics, no workspace: two calls on the same inputs give the same bits.  Asynchronous on
+ * base.stream: nothing is allocated and the host is not synchronised.  No content of a device buffer (NaN, inf and huge flows, points or model entries, label
+ * bytes above 64, any start) makes the call read or write outside its buffers.  The outputs may not overlap the inputs.
+ * Limits: 1 <= batch <= 65535; 2 <= T <= 4096; H, W >= 1 (no multiple of 4 is asked for), H W <= 2^18; 1 <= K <= 65536; max_coast >= 0; fwd_dev and points_dev
+ * non-NULL; strides not negative; alpha and beta finite and >= 0; model_dev only with labels_dev, and 8-byte aligned; the float and int32 buffers 4-byte
+ * aligned; all four outputs non-NULL.  Argument errors: CWM_ERR_INVALID with a message that names the field, before anything is launched or written. */
+CWM_API int cwm_point_track(const cwm_point_track_args* args);
+
 /* `RectangularizeMasks` (masking.py:90-132) on device masks without reading them back.  The reference equalises the masked count of
  * the rows of a batch by un-masking / masking `torch.randperm(#candidates)[:surplus]` of a row's masked / visible tokens (one draw of the global CPU
  * generator per changed row, in row order).  The draws depend on the per-row COUNTS alone, so:
