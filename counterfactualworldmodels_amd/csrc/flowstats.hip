@@ -427,24 +427,45 @@ __global__ __launch_bounds__(256) void flow_apply_kernel(float* __restrict__ x, 
 }
 
 // ---- motion maps ---------------------------------------------------------------------------------------------------------
+// NaN and Inf as torch has them (segmentation.py:250-276): `amin` / `amax` return NaN for a range that holds one and `clamp(min=eps)` keeps it, so ONE NaN
+// under a normalisation makes every value of that range NaN; fminf / fmaxf drop a NaN.  Every range reduction below therefore carries a NaN in its MAXIMUM
+// (as an unsigned maximum of bit patterns ordered so that a NaN is the greatest: mag_bits, max_key) and leaves the minimum to fminf; range_lo then makes the
+// lower bound NaN too: x - NaN is NaN for every x of the range.  An Inf needs nothing: (x - lo) / inf = 0 and inf / inf = NaN, the reference's own arithmetic.
+__device__ __forceinline__ float range_lo(float lo, float hi) { return hi != hi ? hi : lo; }
+__device__ __forceinline__ float clamp_min(float d, float eps) { return d != d ? d : fmaxf(d, eps); }  // tensor.clamp(min=eps)
+// A flow magnitude is sqrt of a sum of squares: +0 or above, or NaN.  There the unsigned order of the bit patterns is the float order, +inf (0x7F800000) is above
+// every finite value and every NaN (either sign) above +inf: an unsigned maximum of the bits IS torch.amax, NaN included -- and the same bits as fmaxf on finite input.
+__device__ __forceinline__ unsigned mag_bits(float m) { return __float_as_uint(m); }
+// Values of either sign: a key whose unsigned order is the float order (negative: all bits flipped; else the sign bit set), with EVERY NaN as the greatest key.  The
+// reduction over keys costs what fmaxf cost -- a select per step (`a != a ? a : ..`) made hipcc branch at every step of the one-workgroup finish kernel.
+__device__ __forceinline__ unsigned max_key(float x) {
+    const unsigned u = __float_as_uint(x);
+    return x != x ? 0xFFFFFFFFu : (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_max(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }  // (0xFFFFFFFF -> 0x7FFFFFFF: a NaN)
+
+// on entry a thread that met a NaN has mx = NaN; on exit every thread has the range, both ends NaN if any thread had one
 __device__ __forceinline__ void block_minmax(float& mn, float& mx, float* red) {
+    unsigned k = max_key(mx);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         mn = fminf(mn, __shfl_xor(mn, off, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+        k = max(k, (unsigned)__shfl_xor((int)k, off, 64));
     }
     const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         red[wave] = mn;
-        red[16 + wave] = mx;
+        red[16 + wave] = __uint_as_float(k);  // (bits only)
     }
     __syncthreads();
     mn = red[0];
-    mx = red[16];
+    k = __float_as_uint(red[16]);
     for (int w = 1; w < nw; ++w) {
         mn = fminf(mn, red[w]);
-        mx = fmaxf(mx, red[16 + w]);
+        k = max(k, __float_as_uint(red[16 + w]));
     }
+    mx = key_max(k);
+    mn = range_lo(mn, mx);
 }
 
 // per (b, s): min and max over (H, W) of the flow magnitude -> mm[b][s] = {min, max}
@@ -452,13 +473,15 @@ __global__ void flow_mag_minmax_kernel(const FlowView v, float2* __restrict__ mm
     __shared__ float red[32];
     const int s = blockIdx.x, b = blockIdx.y, W = v.W;
     const float* fb = v.f + b * v.sb + s * v.ss;
-    float mn = INFINITY, mx = -INFINITY;
+    float mn = INFINITY;
+    unsigned hb = 0u;  // (the sample has at least one pixel and every magnitude is >= +0: starting from 0 changes no result)
     for (int e = threadIdx.x; e < v.H * W; e += blockDim.x) {
         const int y = e / W, x = e - y * W;
         const float m = sqrtf(flow_mag_sq<float>(fb + (int64_t)y * v.sh + (int64_t)x * v.sw, v.sc, v.C));
         mn = fminf(mn, m);
-        mx = fmaxf(mx, m);
+        hb = max(hb, mag_bits(m));
     }
+    float mx = __uint_as_float(hb);
     block_minmax(mn, mx, red);
     if (threadIdx.x == 0) mm[(size_t)b * v.S + s] = make_float2(mn, mx);
 }
@@ -476,7 +499,7 @@ __global__ void flow_motion_sum_kernel(const FlowView v, const float2* __restric
         float m = sqrtf(flow_mag_sq<float>(fp + s * v.ss, v.sc, v.C));
         if (mm) {
             const float2 r = mm[(size_t)b * S + s];
-            m = (m - r.x) / fmaxf(r.y - r.x, eps);
+            m = (m - r.x) / clamp_min(r.y - r.x, eps);
         }
         acc += m;
     }
@@ -489,13 +512,26 @@ __global__ void flow_motion_sum_kernel(const FlowView v, const float2* __restric
 // H W S floats: a workgroup takes 64 - 256 consecutive pixels (mag_tile_pix) = that many times S consecutive floats per channel, loads them with coalesced 4-byte loads
 // (lanes along the sample axis), keeps the magnitudes in LDS [pixels][S + 1] and then reduces along whichever axis the pass needs:
 //   pass 1 (per-sample range): thread s scans the pixels of its column -> one atomicMin / atomicMax per (workgroup, sample) on the float bits (magnitudes
-//          are >= 0, where unsigned order = float order; min starts at 0xFFFFFFFF, max at 0);
+//          are >= 0, where unsigned order = float order -- mag_bits above);
 //   pass 2 (the sum over the samples): thread p walks the S samples of its pixel IN SAMPLE ORDER -- the same additions in the same order as the strided kernel
 //          above (bit-identical to it).
 // The per-sample range is reduced with atomicMin / atomicMax on the float bits.  Every workgroup of a pass hits the same S addresses: 784 workgroups on 512 (or 48)
 // addresses serialise at L2 (S = 24: 19.6 us of a 9.8-MB pass was the queue of 196 atomics per address).  So there are kRangeReplicas copies of the [B][S] arrays,
 // workgroup g uses copy g mod kRangeReplicas, and the consumers fold the copies (min / max are exact in any order).
+// What the bit patterns mean (the work buffer keeps its size: nothing but the two arrays):
+//   max bits: start at 0 (= +0.0f, the least magnitude: an atomic that would write 0 is skipped, it changes nothing).  A workgroup's maximum is an UNSIGNED maximum of
+//          the bits, so a NaN among its magnitudes (bits above +inf's) wins it and the atomicMax carries it on: after the pass the folded maximum of a sample is
+//          NaN if and only if one of its magnitudes was, as torch.amax.  There is no guard that filters a NaN or an Inf out.
+//   min bits: start at 0xFFFFFFFF (a NaN pattern, above every magnitude).  A workgroup's minimum comes from fminf, which skips NaNs; the atomicMin is left out where it found
+//          nothing below +inf -- a sample of +inf and NaN only keeps 0xFFFFFFFF: its range is NaN either way (inf - inf).  The minimum alone never reports a NaN:
+//   the consumers (range_of_bits) read the lower bound as NaN whenever the maximum is one, and clamp the length with clamp_min, which keeps a NaN.
 constexpr int kRangeReplicas = 8;
+
+__device__ __forceinline__ void range_of_bits(unsigned l, unsigned h, float eps, float& lo, float& len) {
+    const float hi = __uint_as_float(h);
+    lo = range_lo(__uint_as_float(l), hi);
+    len = clamp_min(hi - lo, eps);
+}
 
 __device__ __forceinline__ void mag_tile_to_lds(const float* __restrict__ f, int64_t sb, int64_t sc, int b, int C, int HW, int S, int pix0, int tile_pix, float* mag) {
     const int n = min(tile_pix, HW - pix0) * S;
@@ -514,15 +550,16 @@ __global__ __launch_bounds__(256) void flow_mag_minmax_packed_kernel(const float
     __syncthreads();
     const int npix = min(tile_pix, HW - pix0);
     for (int s = threadIdx.x; s < S; s += blockDim.x) {
-        float mn = INFINITY, mx = -INFINITY;
+        float mn = INFINITY;
+        unsigned hb = 0u;
         for (int pl = 0; pl < npix; ++pl) {
             const float m = mag[pl * (S + 1) + s];
             mn = fminf(mn, m);
-            mx = fmaxf(mx, m);
+            hb = max(hb, mag_bits(m));
         }
         const size_t rep = (size_t)(blockIdx.x % kRangeReplicas) * gridDim.y * S;
-        if (mn == mn && mn != INFINITY) atomicMin(&mn_bits[rep + (size_t)b * S + s], __float_as_uint(mn));
-        if (mx == mx && mx != -INFINITY) atomicMax(&mx_bits[rep + (size_t)b * S + s], __float_as_uint(mx));
+        if (mn != INFINITY) atomicMin(&mn_bits[rep + (size_t)b * S + s], __float_as_uint(mn));
+        if (hb != 0u) atomicMax(&mx_bits[rep + (size_t)b * S + s], hb);
     }
 }
 
@@ -541,9 +578,7 @@ __global__ __launch_bounds__(256) void flow_motion_sum_packed_kernel(const float
                 l = min(l, mn_bits[((size_t)r * gridDim.y + b) * S + s]);
                 h = max(h, mx_bits[((size_t)r * gridDim.y + b) * S + s]);
             }
-            const float lo = __uint_as_float(l);
-            lo_s[s] = lo;
-            len_s[s] = fmaxf(__uint_as_float(h) - lo, eps);
+            range_of_bits(l, h, eps, lo_s[s], len_s[s]);
         }
     __syncthreads();
     const int npix = min(tile_pix, HW - pix0);
@@ -575,7 +610,8 @@ __device__ __forceinline__ float group_sum(float v) {  // sum over aligned group
 template <int Q>
 __global__ __launch_bounds__(256) void flow_mag_minmax_rows_kernel(const float* __restrict__ f, int64_t sb, int64_t sc, int C, int HW, int S,
                                                                    unsigned* __restrict__ mn_bits, unsigned* __restrict__ mx_bits) {
-    __shared__ float red_mn[4][256], red_mx[4][256];
+    __shared__ float red_mn[4][256];
+    __shared__ unsigned red_mx[4][256];
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int PPL = 64 / Q;                  // pixels per wave load
     const int sub = lane / Q, s4 = (lane % Q) * 4;
@@ -583,7 +619,8 @@ __global__ __launch_bounds__(256) void flow_mag_minmax_rows_kernel(const float* 
     const int pix0 = (blockIdx.x * 4 + wave) * kRowPixPerWave;
     const float* fb = f + b * sb;
     for (int ch = 0; ch < chunks; ++ch) {
-        f32x4 mn = f32x4{INFINITY, INFINITY, INFINITY, INFINITY}, mx = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        f32x4 mn = f32x4{INFINITY, INFINITY, INFINITY, INFINITY};
+        u32x4 mx = u32x4{0u, 0u, 0u, 0u};  // bits: see kRangeReplicas
 #pragma unroll 4
         for (int i = 0; i < kRowPixPerWave; i += PPL) {
             const int pix = pix0 + i + sub;
@@ -593,7 +630,7 @@ __global__ __launch_bounds__(256) void flow_mag_minmax_rows_kernel(const float* 
                 for (int r = 0; r < 4; ++r) {
                     const float m = sqrtf(a[r]);
                     mn[r] = fminf(mn[r], m);
-                    mx[r] = fmaxf(mx[r], m);
+                    mx[r] = max(mx[r], mag_bits(m));
                 }
             }
         }
@@ -603,7 +640,7 @@ __global__ __launch_bounds__(256) void flow_mag_minmax_rows_kernel(const float* 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 mn[r] = fminf(mn[r], __shfl_xor(mn[r], off, 64));
-                mx[r] = fmaxf(mx[r], __shfl_xor(mx[r], off, 64));
+                mx[r] = max(mx[r], (unsigned)__shfl_xor((int)mx[r], off, 64));
             }
         if (lane < Q)
 #pragma unroll
@@ -615,10 +652,10 @@ __global__ __launch_bounds__(256) void flow_mag_minmax_rows_kernel(const float* 
         const int ns = Q * 4;  // samples of this piece
         for (int s = threadIdx.x; s < ns; s += 256) {
             const float lo = fminf(fminf(red_mn[0][s], red_mn[1][s]), fminf(red_mn[2][s], red_mn[3][s]));
-            const float hi = fmaxf(fmaxf(red_mx[0][s], red_mx[1][s]), fmaxf(red_mx[2][s], red_mx[3][s]));
+            const unsigned hi = max(max(red_mx[0][s], red_mx[1][s]), max(red_mx[2][s], red_mx[3][s]));
             const size_t rep = (size_t)(blockIdx.x % kRangeReplicas) * gridDim.y * S;
             if (lo != INFINITY) atomicMin(&mn_bits[rep + (size_t)b * S + ch * 256 + s], __float_as_uint(lo));
-            if (hi != -INFINITY) atomicMax(&mx_bits[rep + (size_t)b * S + ch * 256 + s], __float_as_uint(hi));
+            if (hi != 0u) atomicMax(&mx_bits[rep + (size_t)b * S + ch * 256 + s], hi);
         }
         __syncthreads();
     }
@@ -650,8 +687,10 @@ __global__ __launch_bounds__(256) void flow_motion_sum_rows_kernel(const float* 
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                lo[r] = __uint_as_float(l[r]);
-                range[r] = fmaxf(__uint_as_float(h[r]) - lo[r], eps);
+                float lo_r, len_r;
+                range_of_bits(l[r], h[r], eps, lo_r, len_r);
+                lo[r] = lo_r;
+                range[r] = len_r;
             }
         }
     };
@@ -686,12 +725,16 @@ __global__ __launch_bounds__(256) void flow_motion_sum_rows_kernel(const float* 
 }
 
 // map = sum * scale; if normalize: (map - min) / max(max - min, eps) over (H, W) per b.  One workgroup of 1024 threads per b.
+// The values may have either sign (a 4-D input is any map), so a NaN is tracked beside fminf / fmaxf -- as the unsigned maximum of the bits without their sign, which is
+// above +inf's exactly if a value was NaN (two VALU operations per value and no branch: a flag `|= v != v` became 20 branches in this one-workgroup, latency-bound
+// kernel) -- and handed to block_minmax in the maximum.
 // Maps of up to 65536 pixels whose size is a multiple of 4 (224 x 224 = 50176) stay in registers between the range pass and the normalisation: every thread issues its
 // <= 16 independent 16-byte loads at once, one pass over memory (round 6; the two-pass loop below took 25 us for 200 KB -- a chain of 49 dependent 4-byte loads per thread, twice).
 __global__ __launch_bounds__(1024) void flow_map_finish_kernel(float* __restrict__ map, int HW, float scale, int normalize, float eps) {
     __shared__ float red[32];
     float* m = map + (size_t)blockIdx.x * HW;
     float mn = INFINITY, mx = -INFINITY;
+    unsigned top = 0u;  // max over the values of (bits & 0x7FFFFFFF)
     if ((HW & 3) == 0 && HW <= 1024 * 4 * 16 && (((uintptr_t)m) & 15) == 0) {
         f32x4 v[16];
         const int n4 = HW / 4;
@@ -709,13 +752,15 @@ __global__ __launch_bounds__(1024) void flow_map_finish_kernel(float* __restrict
                 for (int r = 0; r < 4; ++r) {
                     mn = fminf(mn, v[k][r]);
                     mx = fmaxf(mx, v[k][r]);
+                    top = max(top, __float_as_uint(v[k][r]) & 0x7FFFFFFFu);
                 }
             }
         }
         float d = 1.f;
         if (normalize) {
+            if (top > 0x7F800000u) mx = __builtin_nanf("");
             block_minmax(mn, mx, red);
-            d = fmaxf(mx - mn, eps);
+            d = clamp_min(mx - mn, eps);
         }
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
@@ -734,10 +779,12 @@ __global__ __launch_bounds__(1024) void flow_map_finish_kernel(float* __restrict
         m[e] = v;
         mn = fminf(mn, v);
         mx = fmaxf(mx, v);
+        top = max(top, __float_as_uint(v) & 0x7FFFFFFFu);
     }
     if (!normalize) return;
+    if (top > 0x7F800000u) mx = __builtin_nanf("");
     block_minmax(mn, mx, red);
-    const float d = fmaxf(mx - mn, eps);
+    const float d = clamp_min(mx - mn, eps);
     for (int e = threadIdx.x; e < HW; e += blockDim.x) m[e] = (m[e] - mn) / d;
 }
 

@@ -844,8 +844,11 @@ CWM_API int cwm_multi_shift_prompts(const float* x_dev, int B, int T, int C, int
  * cwm_flow_motion_sum sum[B][H*W] = sum_s |flow| (magnitude over channels), each sample first range-normalised over (H,W)
  *                     with max(range, eps) if normalize_per_sample (work buffer: cwm_flow_motion_work_bytes(B, S) bytes, 16-byte aligned).
  *                     replaces: compute_flow_samples_magnitude + the `.mean(-1)` numerator (segmentation.py:250-255, :264-268)
+ *                     NaN / Inf as torch.amin / amax / clamp have them: with normalize_per_sample a NaN anywhere in a sample makes that sample's range NaN and
+ *                     so every pixel of sum[b] NaN; an infinite magnitude gives NaN at its own pixel and 0 from that sample elsewhere.
  * cwm_flow_map_finish map = map*scale (scale = 1/S_total), then (map - min)/max(max - min, eps) per b if normalize.
- *                     replaces: segmentation.py:273-275.  Split from the sum so that sample shards can be all-reduced in between. */
+ *                     replaces: segmentation.py:273-275.  Split from the sum so that sample shards can be all-reduced in between.
+ *                     With normalize, one NaN in map[b] makes all of map[b] NaN (the range is NaN and the clamp keeps it); a +Inf becomes NaN at its pixel, 0 elsewhere. */
 CWM_API int cwm_flow_features(const float* flows_dev, const int64_t* strides, int B, int C, int H, int W, int S, int downsample,
                       float* x_dev, void* stream);
 /* cwm_flow_transform  the optional prologues of compute_flow_corrs on the pooled features, in place, in the reference's order
