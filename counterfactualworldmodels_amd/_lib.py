@@ -351,6 +351,32 @@ class CwmPointTrackArgs(C.Structure):
     ]
 
 
+class CwmObjectResponseArgs(C.Structure):
+    """cwm_object_response_args (include/cwm_hip.h): cwm_patch_error_args as `base` (batch scenes, T pushes per scene, H, W and the stream are read), the flow
+    samples by five strides, the slot maps by their scene and push strides, the pushed slots, the shifts, the thresholds and the outputs;
+    new_object_response_args() sets struct_size"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", CwmPatchErrorArgs),
+        ("flows_dev", C.c_void_p),
+        ("flow_strides", C.c_int64 * 5),
+        ("S", C.c_int32),
+        ("labels_dev", C.c_void_p),
+        ("labels_strides", C.c_int64 * 2),
+        ("pushed_dev", C.c_void_p),
+        ("dirs_dev", C.c_void_p),
+        ("min_q2", C.c_int64),
+        ("min_pixels", C.c_int32),
+        ("self_frac", C.c_double),
+        ("move_frac", C.c_double),
+        ("tab_dev", C.c_void_p),
+        ("valid_dev", C.c_void_p),
+        ("agg_dev", C.c_void_p),
+        ("coupling_dev", C.c_void_p),
+        ("stats_dev", C.c_void_p),
+    ]
+
+
 class CwmConjConfig(C.Structure):
     _fields_ = [
         ("main", CwmConfig),
@@ -809,6 +835,12 @@ def new_point_track_args() -> CwmPointTrackArgs:
     return a
 
 
+def new_object_response_args() -> CwmObjectResponseArgs:
+    a = new_args(CwmObjectResponseArgs)
+    a.base.T = 1
+    return a
+
+
 def fill_patch_args(g, *, x=None, target=None, mask=None, region=None, y=None, geometry, n_vis=0, frame=-1, map=None, mean=None, scratch=None, stream):
     """Fills a cwm_patch_error_args -- alone, or the `.base` of the other read-outs' -- from tensors: the one place that knows its field order.  `x` and `target`
     are [B,T,C,H,W]-SHAPED views of any (b, t, c) strides, whatever the order of the tensor beneath ([B,C,T,H,W] permuted, a batch stride of 0); their image
@@ -886,6 +918,7 @@ SIGNATURES = {
     "cwm_flow_consistency": (C.c_int, [C.POINTER(CwmFlowConsistencyArgs)]),
     "cwm_object_motion": (C.c_int, [C.POINTER(CwmObjectMotionArgs)]),
     "cwm_point_track": (C.c_int, [C.POINTER(CwmPointTrackArgs)]),
+    "cwm_object_response": (C.c_int, [C.POINTER(CwmObjectResponseArgs)]),
     "cwm_mask_row_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_mask_flip_picks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cwm_prompt_table_expand": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),

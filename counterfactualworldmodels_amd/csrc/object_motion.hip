@@ -53,6 +53,7 @@
 
 #include "../../include/cwm_hip.h"
 #include "common.h"
+#include "wave_sum.h"
 
 #pragma clang fp contract(off)  // (file scope: a*b-c stays a multiply and a subtraction, in fp32 and in binary64)
 
@@ -118,38 +119,6 @@ __device__ __forceinline__ void mot_flush(const MotAcc& a, int l, unsigned long 
         if (a.suu) mot_lds_add(s + 12, a.suu);
         if (a.svv) mot_lds_add(s + 13, a.svv);
     }
-}
-
-// The sum of v over the 64 lanes of a wave, in every lane (it is wave-uniform); EVERY lane of the wave must call it.  Four DPP steps leave each lane with the sum
-// of its row of 16 lanes -- the neighbour of its pair, of its quad, the mirrored half row, the mirrored row --, and the four rows are read out of lanes 0, 16, 32
-// and 48.  (Six dependent __shfl_xor steps per word are a ds_bpermute round trip each, for 24 words: the kernel took twice as long with them.)
-template <int kCtrl>
-__device__ __forceinline__ int mot_dpp(int v) {
-    return __builtin_amdgcn_update_dpp(0, v, kCtrl, 0xf, 0xf, false);
-}
-constexpr int kDppQuadXor1 = 0xB1, kDppQuadXor2 = 0x4E, kDppRowHalfMirror = 0x141, kDppRowMirror = 0x140;  // quad_perm:[1,0,3,2], quad_perm:[2,3,0,1]
-__device__ __forceinline__ int mot_wave_sum(int v) {
-    v += mot_dpp<kDppQuadXor1>(v);
-    v += mot_dpp<kDppQuadXor2>(v);
-    v += mot_dpp<kDppRowHalfMirror>(v);
-    v += mot_dpp<kDppRowMirror>(v);
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
-}
-template <int kCtrl>
-__device__ __forceinline__ long long mot_dpp64(long long v) {
-    const unsigned lo = (unsigned)mot_dpp<kCtrl>((int)(unsigned)v), hi = (unsigned)mot_dpp<kCtrl>((int)(unsigned)((unsigned long long)v >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ long long mot_lane64(long long v, int lane) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v >> 32), lane);
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ long long mot_wave_sum(long long v) {
-    v += mot_dpp64<kDppQuadXor1>(v);
-    v += mot_dpp64<kDppQuadXor2>(v);
-    v += mot_dpp64<kDppRowHalfMirror>(v);
-    v += mot_dpp64<kDppRowMirror>(v);
-    return mot_lane64(v, 0) + mot_lane64(v, 16) + mot_lane64(v, 32) + mot_lane64(v, 48);
 }
 
 template <bool kVec>
@@ -247,13 +216,13 @@ __global__ __launch_bounds__(kMotThreads) void object_motion_accumulate_kernel(c
         MotAcc w;
         mot_clear(w);
         if (mine) w = a;
-        w.cls = mot_wave_sum(w.cls);
-        w.n = mot_wave_sum(w.n);
+        w.cls = wave_sum(w.cls);
+        w.n = wave_sum(w.n);
         if (w.n) {  // (uniform after the sum)
-            w.sx = mot_wave_sum(w.sx), w.sy = mot_wave_sum(w.sy), w.su = mot_wave_sum(w.su), w.sv = mot_wave_sum(w.sv);
-            w.sxx = mot_wave_sum(w.sxx), w.sxy = mot_wave_sum(w.sxy), w.syy = mot_wave_sum(w.syy);
-            w.sxu = mot_wave_sum(w.sxu), w.syu = mot_wave_sum(w.syu), w.sxv = mot_wave_sum(w.sxv), w.syv = mot_wave_sum(w.syv);
-            w.suu = mot_wave_sum(w.suu), w.svv = mot_wave_sum(w.svv);
+            w.sx = wave_sum(w.sx), w.sy = wave_sum(w.sy), w.su = wave_sum(w.su), w.sv = wave_sum(w.sv);
+            w.sxx = wave_sum(w.sxx), w.sxy = wave_sum(w.sxy), w.syy = wave_sum(w.syy);
+            w.sxu = wave_sum(w.sxu), w.syu = wave_sum(w.syu), w.sxv = wave_sum(w.sxv), w.syv = wave_sum(w.syv);
+            w.suu = wave_sum(w.suu), w.svv = wave_sum(w.svv);
         }
         if ((tid & 63) == 0) mot_flush(w, slot, sum_s, cnt_s);
         if (live && !mine) mot_flush(a, cur, sum_s, cnt_s);

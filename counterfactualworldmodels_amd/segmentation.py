@@ -586,6 +586,26 @@ class FlowGenerator(PredictorBasedGenerator):
 
         return OM.measure(labels, flow, code=code, other=other, **kw)
 
+    # ---- which objects move when one is pushed (object_response.py, csrc/object_response.hip) ----
+    def object_interactions(self, x, labels, slots=None, num_slots=8, num_samples=8, shift=1, k_active=4, k_passive=4, ring_radius=1, sample=False, generator=None,
+                            slot_batch_size=None, sample_batch_size=None, min_mag=1.0, self_frac=0.5, move_frac=0.5, **kwargs):
+        """Push every slot of a slot map and see which other slots move: x [B,T,C,H,W], labels [B,H,W] uint8 as `segment_scene` / `track_scene` give them,
+        slots [K] or [B,K] (default 1 .. num_slots: a fixed count, so nothing is read back to learn how many labels exist).  Per (scene, slot) the k_active
+        cells of the patch grid with the most pixels of the slot are moved (sample=True: picked on torch.rand keys from `generator` among the cells the slot
+        touches) and the first k_passive cells that hold no pixel of any slot within `ring_radius` of it are pinned -- a neighbouring object is never pinned, it
+        must stay free to respond; a slot without a pixel is a dead row.  The rows go through `predict_counterfactual_videos_and_flows` (S = num_samples shifts
+        `segment_step.directions(S, shift)`, fix_passive=True, **kwargs pass through: raft_iters, ...), the movie repeated over `slot_batch_size` slots per call
+        (None: all K), and the `_batch_to_samples` view of each call goes into ONE `object_response.measure` with dirs = the shifts in pixels (thresholds:
+        min_mag, self_frac, move_frac).  Returns an `ObjectInteractions`: tab, valid, agg, coupling, stats [B,K,..], slots, the masks active / passive
+        [B,K,2n], and moves, mutual, carries, tested of `object_response.relations` at its defaults -- `object_response.groups(mutual)` and `merge_labels`
+        repair a map that split one body into several slots.  Everything stays on x's device, nothing is read back beyond what the counterfactual driver does,
+        and the loop runs inside torch.random.fork_rng(devices=[]): the caller's global CPU stream of draws is left as it was."""
+        from . import object_response as OR
+
+        return OR.object_interactions(self, x, labels, slots=slots, num_slots=num_slots, num_samples=num_samples, shift=shift, k_active=k_active, k_passive=k_passive,
+                                      ring_radius=ring_radius, sample=sample, generator=generator, slot_batch_size=slot_batch_size,
+                                      sample_batch_size=sample_batch_size, min_mag=min_mag, self_frac=self_frac, move_frac=move_frac, **kwargs)
+
     # ---- whether a flow vector can be believed: the forward-backward check (flow_consistency.py, csrc/flow_consistency.hip) ----
     def predict_flow_and_occlusion(self, x, alpha=0.01, beta=0.5, **flow_kwargs):
         """The forward and backward flows of a movie x [B,T,C,H,W] -- one `predict_flow` call each -- and where they cannot be believed.  Returns

@@ -768,6 +768,64 @@ typedef struct cwm_point_track_args {
  * aligned; all four outputs non-NULL.  Argument errors: CWM_ERR_INVALID with a message that names the field, before anything is launched or written. */
 CWM_API int cwm_point_track(const cwm_point_track_args* args);
 
+typedef struct cwm_object_response_args {
+    uint32_t struct_size;            /* sizeof(cwm_object_response_args); anything else: CWM_ERR_INVALID naming struct_size */
+    /* read: batch (B scenes), T (K pushes per scene), H, W and the stream.  Every other field of base is ignored, base.struct_size and base.P included.
+     * Rows r = b K + k, R = B K */
+    cwm_patch_error_args base;
+    const float* flows_dev;          /* the counterfactual flow samples [R, 2, H, W, S]: element (r, c, y, x, s) at flows_dev[r st[0] + c st[1] + y st[2] + x st[3] +
+                                      * s st[4]] (elements), st = flow_strides, as cwm_segment_step takes them: the `_batch_to_samples` view of the flow model's
+                                      * output is read in place.  c = 0 horizontal, 1 vertical, in pixels */
+    int64_t flow_strides[5];         /* not negative */
+    int32_t S;                       /* 1 .. 255 samples per push */
+    const uint8_t* labels_dev;       /* the slot map of (b, k): H W contiguous bytes at labels_dev + b labels_strides[0] + k labels_strides[1] (0: none, 1 .. 64: a
+                                      * slot; a byte above 64 reads as 0).  labels_strides[1] = 0 is the normal case: all K pushes of a scene read one map */
+    int64_t labels_strides[2];       /* scene and push stride in elements, not negative */
+    const int32_t* pushed_dev;       /* [R]: the slot pushed in row r; anything outside 1 .. 64 is a dead row */
+    const int32_t* dirs_dev;         /* NULL, or [S, 2] (dy, dx): the shift of sample s in pixels, each |d| <= 4096, shared by all rows */
+    int64_t min_q2;                  /* >= 0: the squared motion threshold in (1/256 px)^2; for a threshold of m pixels, round(256 m)^2 */
+    int32_t min_pixels;              /* >= 1: a sample is valid only if the pushed slot has that many usable pixels */
+    double self_frac, move_frac;     /* finite, in [0, 1]: the share of a slot's usable pixels that must have moved, for the pushed slot and for the others */
+    int64_t* tab_dev;                /* out [R, S, 65, 8] int64: step 4; entry 7 counts the pixels whose flow is not usable */
+    uint8_t* valid_dev;              /* out [R, S]: step 5, 0 / 1 */
+    int64_t* agg_dev;                /* out [R, 65, 4] int64: step 6, (N, M, A, V) */
+    double* coupling_dev;            /* out [R, 65, 4] float64: step 7, (c0, c1, c2, c3) */
+    int32_t* stats_dev;              /* out [R, 4]: step 8 */
+} cwm_object_response_args;
+
+/* Object interactions: which slots of a slot map (cwm_segment_merge, cwm_segment_track) move when one of them is pushed, from the S counterfactual flow samples of
+ * each of K pushes per scene, in one call on the device, without a read-back.  Where cwm_segment_step asks which PIXELS move with a seed, this asks which OBJECTS
+ * move with an object.  No counterpart in the reference, whose README describes the covariance it reads out ("objects adjacent to one another tend to move
+ * together, as some motion counterfactuals include collisions between them").  Every step is an integer operation or ONE correctly rounded binary64 operation,
+ * evaluated as parenthesised.  Per row r, sample s and pixel (x, y):
+ *   1 slot     l = labels[y][x], or 0 if that is above 64
+ *   2 usable   (u, v) = flows[r, :, y, x, s]; USABLE iff |u| <= 4096 and |v| <= 4096 (false for a NaN and an inf).  Not usable: tab[r][s][l][7] += 1 and nothing
+ *              else happens
+ *   3 quantise qu = (int)rintf(u * 256.0f), qv likewise (the multiply is exact); q2 = (int64)qu qu + (int64)qv qv; moved = q2 >= min_q2: an integer comparison,
+ *              no fp32 magnitude exists whose last bit a compiler could move
+ *   4 table    tab[r][s][l][0..6] += 1, moved, qu, qv, moved ? qu : 0, moved ? qv : 0, q2.  |q| <= 2^20 and H W <= 2^18: every sum stays below 2^59
+ * Then per row, with a = pushed[r] and n_l(s), m_l(s), su_l(s), sv_l(s) = entries 0 .. 3 of tab[r][s][l]:
+ *   5 valid    sample s is VALID iff a is in 1 .. 64, n_a(s) >= min_pixels and ((double)m_a(s) / (double)n_a(s)) >= self_frac: the pushed object itself moved.
+ *              valid[r][s] = 1 / 0; n_valid = the number of valid samples
+ *   6 agg      per slot l = 0 .. 64, over the valid samples only: N_l = sum n_l(s); M_l = sum m_l(s); A_l = sum (su_l(s) dx_s + sv_l(s) dy_s), int64, at most 2^59,
+ *              0 without dirs_dev; V_l = the number of valid s with n_l(s) > 0 and ((double)m_l(s) / (double)n_l(s)) >= move_frac.  agg[r][l] = (N, M, A, V)
+ *   7 coupling c0 = ((double)V_l / (double)n_valid), or 0 if n_valid = 0: the share of valid pushes in which l moved
+ *              c1 = ((double)M_l / (double)N_l), or 0 if N_l = 0
+ *              c2 = (((double)A_l / (double)N_l) 2^-8), or 0 if N_l = 0: the mean displacement of l along the push
+ *              c3 = (((double)A_l / (double)N_l) / ((double)A_a / (double)N_a)), or 0 if N_l = 0, N_a = 0 or A_a = 0: the gain, 1 where l moves as far as a
+ *              Slot 0 is a row like any other: how much the background gives way
+ *   8 stats    (n_valid, a or 0 for a dead row, n_a(0) + tab[r][0][a][7] -- the area of the pushed slot; 0 for a dead row --, 0)
+ * Two kernels behind one memset of tab_dev, which is the accumulation target (the call zeroes it itself on the stream; there is no workspace): an accumulate
+ * pass over (chunks of 1024 pixels, S, R) -- 4 pixels per thread, the 65 x 8 table in LDS, a wave that holds one slot sums over the wave first; 16-byte loads
+ * where the view has contiguous planes on their alignment, a scalar form through all five strides otherwise -- that adds its non-zero entries with INTEGER
+ * atomics: the same bits in any order, two calls on the same inputs give the same bits; and one workgroup per row for steps 5 - 8.  Asynchronous on
+ * base.stream: nothing is allocated and the host is not synchronised.  No content of a device buffer (label bytes above 64, NaN, inf and huge flows, any
+ * pushed_dev entry) makes the call read or write outside its buffers.  The outputs may not overlap the inputs.
+ * Limits: 1 <= batch, 1 <= T, batch T <= 65535; H and W positive multiples of 4, H W <= 2^18; 1 <= S <= 255; strides not negative; flows_dev, labels_dev,
+ * pushed_dev and all five outputs non-NULL (dirs_dev may be NULL); min_q2 >= 0; min_pixels >= 1; self_frac and move_frac finite and in [0, 1].  Argument errors:
+ * CWM_ERR_INVALID with a message that names the field, before anything is launched or written. */
+CWM_API int cwm_object_response(const cwm_object_response_args* args);
+
 /* `RectangularizeMasks` (masking.py:90-132) on device masks without reading them back.  The reference equalises the masked count of
  * the rows of a batch by un-masking / masking `torch.randperm(#candidates)[:surplus]` of a row's masked / visible tokens (one draw of the global CPU
  * generator per changed row, in row order).  The draws depend on the per-row COUNTS alone, so:
