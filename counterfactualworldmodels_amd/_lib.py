@@ -377,6 +377,32 @@ class CwmObjectResponseArgs(C.Structure):
     ]
 
 
+class CwmParallaxArgs(C.Structure):
+    """cwm_parallax_args (include/cwm_hip.h): cwm_patch_error_args as `base` (batch rows, H, W and the stream are read), the flow samples by five strides, the
+    shifts, the slot maps by their row stride, the thresholds and the outputs; new_parallax_args() sets struct_size"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base", CwmPatchErrorArgs),
+        ("flows_dev", C.c_void_p),
+        ("flow_strides", C.c_int64 * 5),
+        ("S", C.c_int32),
+        ("dirs_dev", C.c_void_p),
+        ("labels_dev", C.c_void_p),
+        ("labels_stride", C.c_int64),
+        ("ref_slot", C.c_int32),
+        ("min_pixels", C.c_int32),
+        ("min_ref_q", C.c_int64),
+        ("min_samples", C.c_int32),
+        ("par_dev", C.c_void_p),
+        ("spread_dev", C.c_void_p),
+        ("off_dev", C.c_void_p),
+        ("cnt_dev", C.c_void_p),
+        ("ref_dev", C.c_void_p),
+        ("hist_dev", C.c_void_p),
+        ("slot_tab_dev", C.c_void_p),
+    ]
+
+
 class CwmConjConfig(C.Structure):
     _fields_ = [
         ("main", CwmConfig),
@@ -841,6 +867,13 @@ def new_object_response_args() -> CwmObjectResponseArgs:
     return a
 
 
+def new_parallax_args() -> CwmParallaxArgs:
+    a = new_args(CwmParallaxArgs)
+    a.base.T = 1
+    a.ref_slot, a.min_pixels, a.min_ref_q, a.min_samples = -1, 1, 64, 1
+    return a
+
+
 def fill_patch_args(g, *, x=None, target=None, mask=None, region=None, y=None, geometry, n_vis=0, frame=-1, map=None, mean=None, scratch=None, stream):
     """Fills a cwm_patch_error_args -- alone, or the `.base` of the other read-outs' -- from tensors: the one place that knows its field order.  `x` and `target`
     are [B,T,C,H,W]-SHAPED views of any (b, t, c) strides, whatever the order of the tensor beneath ([B,C,T,H,W] permuted, a batch stride of 0); their image
@@ -919,6 +952,7 @@ SIGNATURES = {
     "cwm_object_motion": (C.c_int, [C.POINTER(CwmObjectMotionArgs)]),
     "cwm_point_track": (C.c_int, [C.POINTER(CwmPointTrackArgs)]),
     "cwm_object_response": (C.c_int, [C.POINTER(CwmObjectResponseArgs)]),
+    "cwm_parallax": (C.c_int, [C.POINTER(CwmParallaxArgs)]),
     "cwm_mask_row_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cwm_mask_flip_picks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cwm_prompt_table_expand": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4),

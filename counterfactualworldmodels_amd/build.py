@@ -15,7 +15,7 @@ DEV_SOURCES = ["dev.hip"]
 SOURCES = ["gemm.hip", "attention.hip", "attention_pipe.hip", "elementwise.hip", "conj_kernels.hip", "conj_attention.hip", "flowstats.hip", "flowfilter.hip", "engine.hip", "model.hip",
            "conj_model.hip", "comm.hip",
            "raft_kernels.hip", "raft_model.hip", "readout.hip", "unmask.hip", "segment.hip", "segment_merge.hip", "seed_select.hip", "segment_track.hip",
-           "flow_consistency.hip", "object_motion.hip", "point_track.hip", "object_response.hip"]
+           "flow_consistency.hip", "object_motion.hip", "point_track.hip", "object_response.hip", "parallax.hip"]
 HEADERS = ["exports.map", "common.h", "kernels.h", "gemm_device.h", "attention_device.h", "attention_tail.h", "engine.h", "flow_view.h", "select_order.h", "wave_sum.h", os.path.join("..", "..", "include", "cwm_hip.h"),
            os.path.join("..", "..", "include", "cwm_hip_dev.h")]
 

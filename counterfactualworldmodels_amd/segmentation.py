@@ -144,6 +144,27 @@ class FlowGenerator(PredictorBasedGenerator):
             self.set_raft_iters(iters)
         return self.flow_model(vid, backward=backward, **kwargs).to(vid)
 
+    _FLOW_KEYS = ("iters", "raft_iters", "flow_init", "warm_start")  # the keywords of `predict_video_and_flow` that are the flow model's
+
+    def predict_video_and_flow(self, x=None, mask=None, backward=False, propagate_error=False, **kwargs):
+        """(x_pred [B,T-dt+2,C,H,W], f_pred) -- the prediction of the next frame and its flow (segmentation.py:170-197).  With dt = `sequence_length`, every
+        window x[:, t:t+dt] of the movie (default: the generator's input and mask) gives frame 1 of `predict(window, mask, frame=1)`; x_pred is frame 0 followed
+        by these.  propagate_error=True: the flow of x_pred as one movie; False: per window the flow of (x[t], x_pred[t+1], x[t+2:t+dt]), concatenated over
+        time.  The keywords `_FLOW_KEYS` (iters or raft_iters, flow_init, warm_start) go to the flow model and every other one (x_context, mask_context,
+        timestamps, ...) to `predict`: the reference hands all of them to both, so that its flow model is called with the predictor's x_context
+        (reference defects not reproduced)."""
+        x = self.x if x is None else x
+        mask = self.mask if mask is None else mask
+        flow_kw = {k: kwargs.pop(k) for k in self._FLOW_KEYS if k in kwargs}
+        if "raft_iters" in flow_kw:
+            flow_kw.setdefault("iters", flow_kw.pop("raft_iters"))
+        T, dt = x.size(1), self.sequence_length
+        x_pred = torch.cat([x[:, 0:1]] + [self.predict(x[:, t:t + dt], mask, frame=1, **kwargs).to(x) for t in range(T - dt + 1)], 1)
+        if propagate_error:
+            return x_pred, self.predict_flow(x_pred, backward, **flow_kw)
+        f_pred = [self.predict_flow(torch.cat([x[:, t:t + 1], x_pred[:, t + 1:t + 2], x[:, t + 2:t + dt]], 1), backward, **flow_kw) for t in range(T - dt + 1)]
+        return x_pred, (f_pred[0] if len(f_pred) == 1 else torch.cat(f_pred, 1))
+
     def _counterfactual_flows(self, y_mocos, mask, frame, backward=False, raft_iters=None):
         """The flows of the counterfactual videos y_mocos [(b s),T,C,H,W] predicted under `mask` [(b s),Nt] for the generator's input `self.x`.
         With `share_static_frame`, when the flow model has `flow_pairs` (raft.RAFT), the movie has two frames, frame 1 was predicted and no token of
@@ -606,6 +627,34 @@ class FlowGenerator(PredictorBasedGenerator):
                                       ring_radius=ring_radius, sample=sample, generator=generator, slot_batch_size=slot_batch_size,
                                       sample_batch_size=sample_batch_size, min_mag=min_mag, self_frac=self_frac, move_frac=move_frac, **kwargs)
 
+    # ---- what the scene shows when the viewer moves: ego-motion counterfactuals and their parallax (parallax.py, csrc/parallax.hip) ----
+    def ego_motion_flows(self, x, head_motions=None, shifts=None, num_samples=8, anchors=None, num_anchors=9, shift=2, mask=None, sample_batch_size=None, **kwargs):
+        """S flow samples of every movie of x [B,T,C,H,W] under S motions of the VIEWER: (flows [B,2,H,W,S], dirs int32 [S,2] (dy, dx) in pixels, or None).
+        With `head_motions` ([S,C,L], shared by the movies, or [B,S,C,L], in the predictor's layout; IMU-conditioned generators only) sample s is one row of
+        `predict_imu_video_and_flow` with head motion s, `sample_batch_size` rows per call (None: all B S), every movie under one mask (`mask` [B,Nt], default
+        one `generate_mask` draw); dirs is None, because the image motion a head motion causes is not known in advance -- `parallax.measure` then measures every
+        sample against its own mean flow.  Otherwise the anchored pan: `anchors` ([B,n] patch indices of frame 1; default `num_anchors` cells on an evenly
+        spaced lattice of the patch grid, `parallax.lattice_anchors`) are moved together by shift s of `shifts` (S pairs (dy, dx) in patches; default
+        `segment_step.directions(num_samples, shift)`) in ONE `predict_counterfactual_videos_and_flows` (fix_passive=True; `mask`: its passive patches, default
+        none; **kwargs pass through: raft_iters, head_motion, ...), and dirs is the shifts in pixels.  The flows are the `_batch_to_samples` view of the flow
+        model's output.  Runs inside torch.random.fork_rng(devices=[]): the caller's global CPU stream of draws is left as it was; x is not modified.  Given
+        anchors are checked against the grid (one read-back when they are a device tensor)."""
+        from . import parallax as PX
+
+        return PX.ego_motion_flows(self, x, head_motions=head_motions, shifts=shifts, num_samples=num_samples, anchors=anchors, num_anchors=num_anchors, shift=shift,
+                                   mask=mask, sample_batch_size=sample_batch_size, **kwargs)
+
+    def parallax(self, x, labels=None, min_pixels=1, min_ref=0.25, min_samples=None, want_spread=True, want_off=True, order_min_pixels=16, **kwargs):
+        """Relative depth from motion parallax: `ego_motion_flows(x, **kwargs)` followed by ONE `parallax.measure` on its view (thresholds: min_pixels, min_ref,
+        min_samples).  labels [B,H,W] uint8 as `segment_scene` / `track_scene` give them: the reference motion of a head-motion sample is then the mean flow of
+        slot 0, the background (ref_slot=0), and the per-slot histogram and table are filled.  Returns a `parallax.Parallax` (par, spread, off, cnt, ref, hist,
+        slot_tab, dirs) with nearer [B,65,65] and rank [B,65] of `parallax.depth_order(slot_tab, order_min_pixels)` attached (None without labels).  A pure
+        rotation of the viewer gives a flat map.  Nothing is read back beyond what the counterfactual driver does."""
+        from . import parallax as PX
+
+        return PX.parallax(self, x, labels=labels, min_pixels=min_pixels, min_ref=min_ref, min_samples=min_samples, want_spread=want_spread, want_off=want_off,
+                           order_min_pixels=order_min_pixels, **kwargs)
+
     # ---- whether a flow vector can be believed: the forward-backward check (flow_consistency.py, csrc/flow_consistency.hip) ----
     def predict_flow_and_occlusion(self, x, alpha=0.01, beta=0.5, **flow_kwargs):
         """The forward and backward flows of a movie x [B,T,C,H,W] -- one `predict_flow` call each -- and where they cannot be believed.  Returns
@@ -643,7 +692,8 @@ class ImuGenerator(FlowGenerator):
     """The part of the reference's `ImuGenerator` (segmentation.py:549-754) that the IMU-conditioned driver and the UI use, around
     a conjoined predictor with an IMU context stream (the flow -> IMU head-motion predictor): an all-visible default mask
     generator over the predictor's `mask_size`, `_preprocess`, `num_head_tokens`, `reshape_input` / `reshape_output` and
-    `_is_padded`.  Prediction from dataset dicts (`predict_imu`, `forward`) is not provided."""
+    `_is_padded`.  Prediction from dataset dicts (`predict_imu`, and the `forward` that is it) is not provided; the forward of the IMU-CONDITIONED model,
+    `predict_imu_video_and_flow`, is `ImuConditionedFlowGenerator`'s."""
 
     def __init__(self, *args, head_mask_generator=None, head_mask_ratio=0, always_use_predicted=False, require_none_missing=False, **kwargs):
         super().__init__(*args, **kwargs)
@@ -683,7 +733,9 @@ class ImuConditionedFlowGenerator(FlowGenerator):
     `imu400_8x8patch_2frames_1tube_flowbackrgb01`, which needs a flow model: the generator's `flow_model` is handed to it), estimated
     from the video: `static_head_motion=True` (the default) -> `get_static_imu`, False -> `predict_imu_from_video` (:834-880).  It is
     forwarded exactly as the reference forwards it: as `x_context`, with an all-visible (or, with mask_head_motion, all-masked)
-    `mask_context`, tiled over every movie's prompts."""
+    `mask_context`, tiled over every movie's prompts.  `predict_imu_video_and_flow` (:885-929, and `forward`, :966) asks the plain question -- the next frame
+    and its flow under a given head motion --, and `ego_motion_flows` / `parallax` ask it for S head motions, one per row, and read the answers out as motion
+    parallax (parallax.py)."""
 
     def __init__(self, *args, head_motion_predictor=None, head_motion_load_path=None, head_motion_generator=ImuGenerator,
                  head_motion_kwargs=None, head_motion_mask_generator=None, **kwargs):
@@ -746,6 +798,46 @@ class ImuConditionedFlowGenerator(FlowGenerator):
     def get_zeros_imu(self, x=None):
         x = self.x if x is None else x
         return torch.zeros((x.shape[0], self.head_motion_channels, self.head_tubelet_size * self.num_head_tokens), device=x.device, dtype=x.dtype)
+
+    def predict_imu_video_and_flow(self, x, mask=None, timestamps=None, head_motion=None, mask_head_motion=False, static_head_motion=False, return_flow=True,
+                                   return_head_motion=False, **kwargs):
+        """The next frame and its flow under a GIVEN head motion (segmentation.py:885-929): (y, flow) of `predict_video_and_flow(x, mask, x_context=the head
+        motion, mask_context=all visible, or with mask_head_motion all masked)`.  mask None: one `generate_mask` draw.  The head motion is, in the reference's
+        order of precedence, `head_motion` ([B,C,L] in the predictor's layout, forwarded as it is, as the counterfactual calls take it), else with
+        static_head_motion `get_static_imu()`, else `predict_imu_from_video(x)`; the two estimates are the head-motion predictor's output and go through its
+        generator's `reshape_output`, as in `_conditioning_kwargs`.  return_head_motion=True returns that head motion -- as given, or as estimated ([B,T,F], before
+        the reshape) -- and predicts nothing.  return_flow=False (unused in the reference) skips the flow model: (y, None).  **kwargs: see
+        `predict_video_and_flow`."""
+        self.set_input(x)
+        self.mask = self.generate_mask(x) if mask is None else mask
+        given = head_motion is not None
+        if given:
+            h = head_motion
+        elif static_head_motion:
+            h = self.get_static_imu()
+        else:
+            h = self.predict_imu_from_video(x, timestamps=timestamps)
+        if return_head_motion:
+            return h
+        h_mask = torch.zeros(h.size(0), self.num_head_tokens, dtype=torch.bool, device=h.device)
+        if mask_head_motion:
+            h_mask = ~h_mask
+        kw = dict(kwargs, x_context=h if given else self.head_motion_generator.reshape_output(h), mask_context=h_mask)
+        if timestamps is not None:
+            kw["timestamps"] = timestamps
+        if return_flow:
+            y, flow = self.predict_video_and_flow(x, mask=self.mask, **kw)
+        else:
+            for k in self._FLOW_KEYS:
+                kw.pop(k, None)
+            T, dt = x.size(1), self.sequence_length
+            y, flow = torch.cat([x[:, 0:1]] + [self.predict(x[:, t:t + dt], self.mask, frame=1, **kw).to(x) for t in range(T - dt + 1)], 1), None
+        self.reset_padding_masks()
+        return y, flow
+
+    def forward(self, *args, **kwargs):
+        """segmentation.py:966"""
+        return self.predict_imu_video_and_flow(*args, **kwargs)
 
     def _conditioning_kwargs(self, x, kwargs):
         """segmentation.py:931-963: `head_motion` -> x_context, an all-visible (mask_head_motion: all-masked) mask_context."""

@@ -826,6 +826,70 @@ typedef struct cwm_object_response_args {
  * CWM_ERR_INVALID with a message that names the field, before anything is launched or written. */
 CWM_API int cwm_object_response(const cwm_object_response_args* args);
 
+typedef struct cwm_parallax_args {
+    uint32_t struct_size;            /* sizeof(cwm_parallax_args); anything else: CWM_ERR_INVALID naming struct_size */
+    /* read: batch (R rows), H, W and the stream.  Every other field of base is ignored, base.struct_size, base.T and base.P included */
+    cwm_patch_error_args base;
+    const float* flows_dev;          /* the S ego-motion flow samples [R, 2, H, W, S]: element (r, c, y, x, s) at flows_dev[r st[0] + c st[1] + y st[2] + x st[3] +
+                                      * s st[4]] (elements), st = flow_strides: the `_batch_to_samples` view of the flow model's output is read in place.
+                                      * c = 0 horizontal, 1 vertical, in pixels */
+    int64_t flow_strides[5];         /* not negative */
+    int32_t S;                       /* 1 .. 64 samples */
+    const int32_t* dirs_dev;         /* NULL, or [S, 2] (dy, dx): the image motion sample s was asked for, in pixels, each |d| <= 4096, shared by all rows */
+    const uint8_t* labels_dev;       /* NULL, or the slot map of row r: H W contiguous bytes at labels_dev + r labels_stride (0: none, 1 .. 64: a slot; a byte
+                                      * above 64 reads as 0) */
+    int64_t labels_stride;           /* row stride in elements, not negative */
+    int32_t ref_slot;                /* -1, or 0 .. 64 (needs labels_dev): without dirs_dev the reference motion is measured on the pixels of this slot only */
+    int32_t min_pixels;              /* >= 1: a sample is live only if its reference motion rests on that many pixels */
+    int64_t min_ref_q;               /* 1 .. 2^21: the smallest reference motion, in 1/256 px */
+    int32_t min_samples;             /* 1 .. S: a pixel with fewer live, usable samples has no parallax */
+    float* par_dev;                  /* out [R, H, W]: step 5, the lower median of the motion along the reference, in units of the reference motion */
+    float* spread_dev;               /* out [R, H, W] or NULL: step 5, the interquartile range of the same values */
+    float* off_dev;                  /* out [R, H, W] or NULL: step 5, the lower median of the motion across the reference */
+    uint8_t* cnt_dev;                /* out [R, H, W] or NULL: step 5, the number of live, usable samples */
+    double* ref_dev;                 /* out [R, S, 4] float64, 8-byte aligned: step 3, (mu, mv, den, live).  Without dirs_dev it is also where the sums are gathered */
+    int32_t* hist_dev;               /* out [R, 65, 256] int32, 16-byte aligned; needed with labels_dev, ignored without: step 6 */
+    int32_t* slot_tab_dev;           /* out [R, 65, 8] int32; needed with labels_dev, ignored without: step 7 */
+} cwm_parallax_args;
+
+/* Motion parallax: from S flow samples of one scene under S different motions of the VIEWER (a pan of anchored patches, or a head motion given to an
+ * IMU-conditioned predictor) to a per-pixel parallax map and a per-slot depth table, in one call on the device, without a read-back.  Under a translation of the
+ * viewer near things sweep across the image faster than far ones: the parallax of a pixel is how far it moves along the motion of a reference (the whole image,
+ * or the pixels of one slot), as a multiple of that motion; the median over the samples is the read-out, a slot's histogram of it the depth cue.  A pure
+ * rotation of the viewer moves every pixel alike and gives a flat map.  No counterpart in the reference, whose README lists "using counterfactuals to estimate
+ * other scene properties" as coming.  Every step is an integer operation or ONE correctly rounded binary64 (where stated: binary32) operation, evaluated as
+ * parenthesised; nothing is contracted into a fused multiply-add.  Per row r, sample s and pixel (x, y):
+ *   1 usable   (u, v) = flows[r, :, y, x, s]; USABLE iff |u| <= 4096 and |v| <= 4096 (false for a NaN and an inf): step 2 of cwm_object_response
+ *   2 quantise qu = (int64)rintf(u * 256.0f), qv likewise (round half even; the multiply is exact).  A sample that is not usable contributes nothing anywhere
+ *   3 ref      per (r, s).  With dirs_dev: mu = (double)(256 dx_s), mv = (double)(256 dy_s), N = H W.  Without: SU, SV, N = the int64 sums of qu, qv and 1 over
+ *              the usable pixels of the row in sample s -- with ref_slot >= 0 only over those whose label (a byte above 64 reads as 0) equals ref_slot --;
+ *              mu = ((double)SU / (double)N), mv = ((double)SV / (double)N), both 0 if N = 0.  den = ((mu mu) + (mv mv)): two multiplies and one add, each rounded
+ *              on its own.  The sample is LIVE for the row iff N >= min_pixels and den >= ((double)min_ref_q (double)min_ref_q).  ref[r][s] = (mu, mv, den,
+ *              live ? 1.0 : 0.0)
+ *   4 project  for a usable pixel of a live sample: p = ((((double)qu mu) + ((double)qv mv)) / den), c = (|((double)qu mv) - ((double)qv mu)| / den).  The
+ *              conversions are exact (|q| <= 2^20)
+ *   5 order    n = the number of live, usable samples of the pixel; cnt = n.  n < min_samples: par, spread and off are the quiet NaN 0x7fc00000.  Otherwise
+ *              the n values p are put in ascending order WITH TIES BROKEN BY THE SAMPLE INDEX (-0.0 and +0.0 compare equal: only a stable order makes the
+ *              bits of the result determinate), P[0 .. n-1]; med = P[(n-1)/2] (the lower median), par = (float)med; spread = (float)(P[3(n-1)/4] - P[(n-1)/4]),
+ *              one binary64 subtraction; off = (float)C[(n-1)/2] with the c values ordered by the same rule.  Each is rounded once to binary32, to nearest
+ *   6 hist     only with labels_dev, l = the pixel's label (above 64: 0).  n >= min_samples: b = floor(med 32.0) + 128.0, clamped to 0 .. 255 as a double and
+ *              then converted; hist[r][l][b] += 1.  Otherwise slot_tab[r][l][1] += 1
+ *   7 slots    only with labels_dev: slot_tab[r][l] = (n, n_bad, b_med, b_q1, b_q3, b_min, b_max, 0) with n = the sum of hist[r][l], n_bad from step 6, and
+ *              b_med, b_q1, b_q3 the bins of the order statistics k = (n-1)/2, (n-1)/4, 3(n-1)/4 of step 5: the lowest bin b whose cumulative count
+ *              hist[r][l][0] + .. + hist[r][l][b] exceeds k; b_min and b_max the lowest and highest bin that is not empty.  n = 0: all five are -1
+ * A bin is 1/32 of the reference motion wide and bin 128 starts at 0: the centre of bin b is (b - 127.5) / 32.
+ * Three kernels behind the memsets of the tables the workgroups add into (hist_dev, slot_tab_dev and, without dirs_dev, ref_dev: the call zeroes them itself on
+ * the stream; there is no workspace): the reference sums (skipped with dirs_dev) -- 4 pixels per thread, 16-byte loads where the view has contiguous planes on
+ * their alignment, a scalar form through all five strides otherwise, wave sums, INTEGER atomics --; the pixels -- a thread per pixel whose S projections live in
+ * LDS, ranked by counting; the histogram of the workgroup's first slot is gathered in LDS, and every count reaches memory as an INTEGER atomic --; and the
+ * finalise pass, a wave per (row, slot).  Integer atomics give the same bits in any order: two calls on the same inputs give the same bits.  Asynchronous on
+ * base.stream: nothing is allocated and the host is not synchronised.  No content of a device buffer (label bytes above 64, NaN, inf and huge flows, any
+ * dirs_dev entry) makes the call read or write outside its buffers.  The outputs may not overlap the inputs.
+ * Limits: 1 <= batch <= 65535; H and W positive multiples of 4, H W <= 2^18; 1 <= S <= 64; strides not negative; flows_dev, par_dev and ref_dev non-NULL, and
+ * with labels_dev hist_dev and slot_tab_dev; ref_slot -1 or 0 .. 64, and only with labels_dev; min_pixels >= 1; 1 <= min_ref_q <= 2^21; 1 <= min_samples <= S.
+ * Argument errors: CWM_ERR_INVALID with a message that names the field, before anything is launched or written. */
+CWM_API int cwm_parallax(const cwm_parallax_args* args);
+
 /* `RectangularizeMasks` (masking.py:90-132) on device masks without reading them back.  The reference equalises the masked count of
  * the rows of a batch by un-masking / masking `torch.randperm(#candidates)[:surplus]` of a row's masked / visible tokens (one draw of the global CPU
  * generator per changed row, in row order).  The draws depend on the per-row COUNTS alone, so:
